@@ -12,10 +12,15 @@ Launch: `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus 
 the environment the parent starts N rank processes itself, BEFORE it touches a
 GPU, and relays rank 0's line.  WORLD_SIZE != --gpus is an error.
 
-Prints ONE JSON line on rank 0 (contract in the task description); extra keys:
-roofline (dominant kernel), kernels (every kernel, one untimed pass),
-path_roofline, cpu_baseline (+ cpu_baseline_1t, c1_cpu_ms), c4_fps,
-single_frame_ms, region_limited (the opt-in enhance_region mode; never the value).  Exits non-zero when the occupancy check fails.
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run
+sets up, warms up, times exactly --steps steps, checks the occupancy of the
+last step's frames and prints the line (value, ms_per_step, path_roofline).
+--full adds the legs that take runs of their own: roofline (dominant kernel,
+HIP events live in `--steps` more steps), kernels (every kernel, one untimed
+pass), cpu_baseline (+ cpu_baseline_1t, c1_cpu_ms), c4_fps, single_frame_ms,
+noise_scene, class_api, region_limited (the opt-in enhance_region mode; never
+the value).  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (see dump_outputs).  Exits non-zero when the occupancy check fails.
 """
 import argparse
 import json
@@ -30,6 +35,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most 64 MB in all
+# --dump-outputs budget, shared by the streams of rank 0: frames whose records are written, frames whose per-square
+# statistics and HoughCircles outcomes are written, warped boards (620 x 620 x 3 as float32 = 4.6 MB each)
+DUMP_RESULT_FRAMES, DUMP_DETAIL_FRAMES, DUMP_BOARDS = 2048, 512, 6
 
 
 def algorithmic_bytes(w, h, board=620, n_sq_px=None):
@@ -107,6 +116,86 @@ def rank_reduce(dist, backend, elapsed_s, occ_ok, frames=None):
     fr = torch.tensor([frames], dtype=torch.int64, device=dev)
     dist.all_reduce(fr, op=dist.ReduceOp.SUM)
     return float(t.item()), int(flag.item()) == 0, int(fr.item())
+
+
+def share(total, n, j):
+    """Part j of `total` split as evenly as integers allow over n parts (the first total % n parts get one more)."""
+    return total // n + (1 if j < total % n else 0)
+
+
+def sample_slots(n, k, seed):
+    """Every slot 0..n-1 when n <= k, else a fixed, seeded sample of k of them in increasing order."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def bit_planes(words):
+    """u64 bitsets [...] -> float32 0 / 1 [..., 64] (bit i at index i): exact, where a float64 of the word would not be."""
+    import numpy as np
+    w = np.asarray(words, dtype=np.uint64)
+    return ((w[..., None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(np.float32)
+
+
+def struct_columns(recs, bitset_fields=()):
+    """ctypes records -> float64 [n, columns]: every field in declaration order (arrays flattened); a u64 bitset field
+    becomes 64 columns of 0 / 1.  Every other field is at most 32 bits wide, so float64 holds it exactly."""
+    import numpy as np
+    a = np.ctypeslib.as_array(recs)
+    cols = []
+    for name in a.dtype.names:
+        v = a[name].reshape(len(a), -1)
+        cols.append(bit_planes(v[:, 0]).astype(np.float64) if name in bitset_fields else v.astype(np.float64))
+    return np.concatenate(cols, axis=1)
+
+
+def stream_outputs(pp, N, results, n_results, n_detail, n_boards, seed):
+    """What a caller of the timed path receives from one stream after the last step, as float arrays: the per-frame
+    records of cbv_pipeline_results (bitsets over the 64 squares), the NoiseHandler outputs, and for a seeded sample
+    of the frames the per-square statistics, the HoughCircles outcomes and the warped boards."""
+    import numpy as np
+    F = len(results)
+    out = {}
+    rs = sample_slots(F, n_results, seed)
+    rec = np.ctypeslib.as_array(results)
+    out["frame_results"] = np.stack([bit_planes(rec[name][rs]) for name in rec.dtype.names], axis=1)  # [frames, 8, 64]
+    noise = (N.NoiseResult * F)()
+    pp.ctx.check(pp.ctx.lib.cbv_pipeline_noise_results(pp.h_, 0, F, noise))
+    out["noise_results"] = struct_columns(noise, bitset_fields=("squares",))[rs]
+    out["result_slots"] = rs.astype(np.float64)
+    ds = sample_slots(F, n_detail, seed + 1)
+    if len(ds):
+        out["square_stats"] = np.stack([struct_columns(pp.square_stats(int(s))) for s in ds])  # [frames, squares, 18]
+        if pp._cfg.use_hough:
+            out["hough"] = np.stack([struct_columns(pp.hough(int(s))) for s in ds])  # [frames, 64, 34]
+        out["detail_slots"] = ds.astype(np.float64)
+    bs = sample_slots(F, n_boards, seed + 2)
+    if len(bs):
+        out["warped_boards"] = np.stack([pp.download(2, int(s)).astype(np.float32) for s in bs])  # [boards, 620, 620, 3] BGR
+        out["board_slots"] = bs.astype(np.float64)
+    return out
+
+
+def dump_outputs(directory, stream_ids, pipes, results, N):
+    """--dump-outputs: rank 0's streams after the last timed step, one DIR/<name>.npy per array (float32 / float64),
+    names prefixed with stream<id>_ when the rank runs more than one stream; at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    ns = len(pipes)
+    arrays = {}
+    for j, (sid, pp, res) in enumerate(zip(stream_ids, pipes, results)):
+        prefix = "" if ns == 1 else "stream%d_" % sid
+        outs = stream_outputs(pp, N, res, share(DUMP_RESULT_FRAMES, ns, j), share(DUMP_DETAIL_FRAMES, ns, j),
+                              share(DUMP_BOARDS, ns, j), seed=1000 * (sid + 1))
+        arrays.update((prefix + k, v) for k, v in outs.items())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return total
 
 
 def free_port():
@@ -422,9 +511,16 @@ def main():
     ap.add_argument("--no-class-api", action="store_true", help="skip the class-API (one host frame per call) leg")
     ap.add_argument("--splits", type=int, default=4, help="a step's frames are enqueued as this many consecutive runs "
                     "(the temporal scan of one run overlaps the enhancement of the next)")
+    ap.add_argument("--full", action="store_true", help="also run the legs that take runs of their own (roofline, per-kernel pass, "
+                    "single frame, noise scene, class API, region-limited, 4K, CPU baselines); the --no-* and --cpu-frames options "
+                    "select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(rank 0's streams) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         import torch  # device_count() does not initialise the GPU on this image
@@ -509,20 +605,16 @@ def main():
         pp.reset_state()
     step, splits, bounds = make_step(pipes, Fs, chunk, args.splits)
 
-    def start_profile():
-        ctx.profile_reset()
-        ctx.profile_enable(N.K["BILATERAL"])  # HIP events around the dominant kernel, live in the timed region
-
-    elapsed = timed_steps(step, args.steps, args.warmup, barrier, torch.cuda.synchronize, start_profile)
+    elapsed = timed_steps(step, args.steps, args.warmup, barrier, torch.cuda.synchronize)
     elapsed_local = elapsed
-    torch.cuda.synchronize()
-    bl_ms, bl_n = ctx.profile_read(N.K["BILATERAL"])
-    ctx.profile_enable(-2)
+    results = [pp.results(0, Fs) for pp in pipes]  # the last timed step's per-frame records
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, my_streams, pipes, results, N)
 
     # every frame's raw occupancy must be the scripted position (bit-exact 8x8 grid), on every stream of every rank
     occ_ok = True
-    for sid, pp in zip(my_streams, pipes):
-        res = pp.results(0, Fs)
+    for sid, pp, res in zip(my_streams, pipes, results):
         bad = [i for i in range(Fs) if pp.occupied(res[i], stable=False) != set(S.position_for_frame(i).keys())]
         ok_s = not bad and pp.occupied(res[Fs - 1]) == set(S.position_for_frame(Fs - 1).keys())
         if not ok_s:
@@ -535,6 +627,18 @@ def main():
 
     per_kernel_bytes, path_bytes = algorithmic_bytes(w, h)
     fps = frames_all * args.steps / elapsed  # whole job: the frames all ranks processed / the slowest rank's time
+    bl_ms, bl_n = 0.0, 0
+    if args.full:
+        # the dominant kernel's roofline: HIP events around every k_bilateral launch, live in as many steps again as the
+        # timed region ran (after it, so that the headline is timed without events)
+        barrier()
+        ctx.profile_reset()
+        ctx.profile_enable(N.K["BILATERAL"])
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        bl_ms, bl_n = ctx.profile_read(N.K["BILATERAL"])
+        ctx.profile_enable(-2)
     for pp in pipes[1:]:  # the extra legs below run on one stream
         pp.close()
     n_my_streams, splits_timed = len(pipes), splits
@@ -545,7 +649,7 @@ def main():
     kernels = {}
     single_ms = None
     c4 = None
-    if rank == 0 and not args.no_profile_pass:
+    if args.full and rank == 0 and not args.no_profile_pass:
         # one extra, untimed pass with events around every kernel, on ONE lane so that kernels of
         # different chunks do not overlap and each duration is the kernel's own
         pipe.configure(pts, profile=profile, grid_lines=grid, chunk=args.chunk, lanes=1, enhance_region=args.region, **S.SHIPPED_DETECTOR)
@@ -578,7 +682,7 @@ def main():
             ts.append((time.perf_counter() - a) * 1e3)
         single_ms = round(min(ts), 4)
     region = None
-    if rank == 0 and world == 1 and not args.no_profile_pass and not args.region and not args.no_region_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_profile_pass and not args.region and not args.no_region_leg:
         # NOT the headline: the same stream with cbv_pipeline_config.enhance_region = 1 (CLAHE apply, bilateral and sharpen on
         # the part of each frame the warp samples; the rest only for frames whose region does not saturate to 0 and 255)
         pipe.configure(pts, profile=profile, grid_lines=grid, chunk=args.chunk, lanes=args.lanes, enhance_region=True, **S.SHIPPED_DETECTOR)
@@ -601,16 +705,16 @@ def main():
                           "SURVEY 8(d)'s whole-frame bytes and is not the bench's value"}
         occ_ok = occ_ok and okr
     noise = None
-    if rank == 0 and world == 1 and not args.no_profile_pass and not args.no_noise_leg and not args.region:
+    if args.full and rank == 0 and world == 1 and not args.no_profile_pass and not args.no_noise_leg and not args.region:
         noise = noise_scene_leg(pipe, ctx, N, torch, F, chunk, args, pts, profile, grid, S, kernels)
     class_api = None
-    if rank == 0 and world == 1 and not args.no_profile_pass and not args.no_class_api:
+    if args.full and rank == 0 and world == 1 and not args.no_profile_pass and not args.no_class_api:
         nf = min(F, 48)
         host_frames = [pipe.download(0, i) for i in range(nf)]  # the bench's own stream as camera frames in host memory
         class_api = class_api_leg(host_frames, w, h, pts, grid, profile, S.SHIPPED_DETECTOR)
         occ_ok = occ_ok and class_api["occupancy_check"]
         del host_frames
-    if rank == 0 and world == 1 and not args.no_4k and not args.no_profile_pass:
+    if args.full and rank == 0 and world == 1 and not args.no_4k and not args.no_profile_pass:
         # configs[3]: 3840x2160 frames, bilateral d = 9, device-resident (warp / detect unchanged at 620x620)
         pipe.close()
         F4 = 96
@@ -634,7 +738,7 @@ def main():
         p4.close()
 
     cpu = cpu1 = c1 = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         nthr, ncores, tried = pick_cpu_threads(profile)
         what = ("synthetic %dx%d frames of the bench's own stream through the C oracle (process_pipeline -> warp_image -> split_board -> "
                 "detect_all_pieces); pixel functions in C with OpenMP over rows (team size = fastest of a probe), the 64-square decision loop in "
@@ -707,8 +811,8 @@ def main():
                          "avg_launch_ms": round(avg_ms, 5), "launches": bl_n, "frames_per_launch": frames_per_launch,
                          "binding_resource": "vector-instruction issue, then the LDS weight gather (49 taps/px); HBM traffic equals the algorithmic 2N",
                          "note": "dominant kernel, priced against HBM with its algorithmic bytes 2N as the contract asks; it is bound by "
-                                 "vector-instruction issue and the LDS weight gather, see `valu`; timed live with HIP events in the timed "
-                                 "region (%d lanes: kernels of the other lane share the chip during a launch)" % (args.lanes if args.lanes > 0 else 2),
+                                 "vector-instruction issue and the LDS weight gather, see `valu`; timed live with HIP events in as many steps "
+                                 "as the timed region, run right after it (%d lanes: kernels of the other lane share the chip during a launch)" % (args.lanes if args.lanes > 0 else 2),
                          "valu": {"lane_ops_per_px": round(valu_ops_px, 1), "lane_ops_source": valu_src,
                                   "achieved": round(valu_ach, 2), "peak": round(valu_peak, 1), "unit": "T lane-ops/s",
                                   "frac": round(valu_ach / valu_peak, 4), "note": "peak = 256 CU x 4 SIMD x 32 lanes/clk x 2.4 GHz (full-rate ops); v_sad_u8 and v_cvt_f32_ubyte are half-rate",
@@ -723,9 +827,11 @@ def main():
                                       "pays one more 2N pass (k_normalize)"},
             "kernels": kernels, "single_frame_ms": single_ms, "noise_scene": noise, "class_api": class_api, "region_limited": region, "c4_fps": c4, "cpu_baseline": cpu, "cpu_baseline_1t": cpu1, "c1_cpu_ms": c1,
             "occupancy_check": bool(occ_ok), "hough_squares_last_frame": hough_ran,
-            "device": ctx.name,
+            "device": ctx.name, "full": bool(args.full), "dumped_bytes": dumped,
         }
-        if args.region:
+        if not args.full:
+            out["roofline"] = None  # the live k_bilateral pass runs with --full only
+        if args.region and out["roofline"]:
             # enhance_region = 1: a bilateral launch covers the quad's tiles or their complement, not whole frames, so
             # pricing it with whole-frame bytes / instructions would claim work it does not do (a fraction above 1)
             rf = out["roofline"]

@@ -25,3 +25,39 @@ def test_opencv_leg_reports_absence_and_runs_with_a_cv2_module(monkeypatch):
         r = bench.opencv_leg(320, 240, 2, prof, pts)
         assert r["available"] is True and "error" not in r, r
         assert r["value"] > 0 and set(r["max_abs_diff_vs_oracle"].values()) == {0} and r["max_abs_diff_chain_warped"] == 0
+
+
+def test_dump_helpers_are_exact_and_seeded():
+    """--dump-outputs: u64 bitsets become exact 0 / 1 planes, ctypes records become float64 columns field by field, and
+    the sample of frames is fixed by its seed and covers every frame when the budget allows."""
+    import ctypes as C
+    import numpy as np
+    import bench
+    from chessboard_vision_amd import _native as N
+    w = np.array([0, 1, (1 << 63) | 5, (1 << 64) - 1], dtype=np.uint64)
+    p = bench.bit_planes(w)
+    assert p.dtype == np.float32 and p.shape == (4, 64)
+    assert p[0].sum() == 0 and p[1, 0] == 1 and p[1, 1:].sum() == 0 and p[3].sum() == 64
+    assert list(np.flatnonzero(p[2])) == [0, 2, 63]
+    recs = (N.NoiseResult * 2)()
+    recs[0].state, recs[0].lifted, recs[0].count, recs[0].squares = 3, -1, 7, (1 << 63) | 2
+    cols = bench.struct_columns(recs, bitset_fields=("squares",))
+    assert cols.dtype == np.float64 and cols.shape == (2, 6 + 64)
+    assert list(cols[0, :6]) == [3, 0, 0, -1, 7, 0] and list(np.flatnonzero(cols[0, 6:])) == [1, 63] and cols[1].sum() == 0
+    h = (N.HoughResult * 1)()
+    h[0].cx, h[0].votes, h[0].circles[5][3] = 1.5, 2 ** 31 - 1, 0.25
+    hc = bench.struct_columns(h)
+    assert hc.shape == (1, 10 + 4 * N.HOUGH_KEEP) and hc[0, 3] == 1.5 and hc[0, 6] == 2 ** 31 - 1 and hc[0, -1] == 0.25
+    assert C.sizeof(N.SqStats) // 4 == bench.struct_columns((N.SqStats * 1)()).shape[1]
+    assert list(bench.sample_slots(5, 8, seed=1)) == [0, 1, 2, 3, 4]
+    s = bench.sample_slots(512, 6, seed=1000)
+    assert len(s) == 6 == len(set(s)) and list(s) == sorted(s) and list(s) == list(bench.sample_slots(512, 6, seed=1000))
+    assert [bench.share(6, 4, j) for j in range(4)] == [2, 2, 1, 1] and sum(bench.share(512, 3, j) for j in range(3)) == 512
+
+
+def test_bench_options_full_and_dump_outputs_exist():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and r.stdout.strip() == ""

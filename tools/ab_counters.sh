@@ -9,7 +9,7 @@ for v in A B; do
   cp tools/bin/lib$v.so $L
   out=$PWD/gpurun_out/abc_$v
   rm -rf $out; mkdir -p $out
-  python bench.py --steps 20 --warmup 3 --cpu-frames 0 --no-4k --no-region-leg --no-class-api "$@" > $out/bench.json 2>/dev/null
+  python bench.py --full --steps 20 --warmup 3 --cpu-frames 0 --no-4k --no-region-leg --no-class-api "$@" > $out/bench.json 2>/dev/null
   python - "$v" $out/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ cp $L /tmp/lib_orig.so
 for i in $(seq $R); do
   for v in A B; do
     cp tools/bin/lib$v.so $L
-    python bench.py --steps 20 --warmup 3 --cpu-frames 0 --no-4k "$@" > /tmp/ab.json 2>/dev/null
+    python bench.py --full --steps 20 --warmup 3 --cpu-frames 0 --no-4k "$@" > /tmp/ab.json 2>/dev/null
     python - "$v" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab.json").read().strip().splitlines()[-1])
