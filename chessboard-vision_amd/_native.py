@@ -137,6 +137,17 @@ class PipelineConfig(C.Structure):
                 ("use_hough", C.c_int32), ("hough", HoughParams), ("enhance_region", C.c_int32)]
 
 
+class BoardConfig(C.Structure):
+    """cbv_board_config: the per-board subset of cbv_pipeline_config (cbv_pipeline_add_board)."""
+    _fields_ = [("M", C.c_double * 9), ("board_size", C.c_int32), ("rot180", C.c_int32), ("n_rois", C.c_int32),
+                ("rois", Roi * MAX_SQUARES), ("history_size", C.c_int32), ("min_presence", C.c_double),
+                ("change_threshold", C.c_double), ("z_threshold", C.c_double), ("initial_variance", C.c_double),
+                ("use_hough", C.c_int32), ("hough", HoughParams)]
+
+
+MAX_BOARDS = 8
+
+
 class FrameResult(C.Structure):
     _fields_ = [("raw_occupied", C.c_uint64), ("stable_occupied", C.c_uint64), ("visual_changes", C.c_uint64),
                 ("processed", C.c_uint64), ("changed", C.c_uint64), ("parcial", C.c_uint64), ("total", C.c_uint64),
@@ -238,6 +249,7 @@ def load():
         "cbv_pipeline_set_check_squares": (i32, [vp, i32, i32, vp]),
         "cbv_pipeline_square_stats": (i32, [vp, i32, P(SqStats)]),
         "cbv_pipeline_hough": (i32, [vp, i32, P(HoughResult)]),
+        "cbv_pipeline_add_board": (i32, [vp, P(BoardConfig), P(vp)]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

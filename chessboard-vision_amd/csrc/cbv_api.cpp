@@ -1547,6 +1547,15 @@ struct cbv_pipeline {
     hipStream_t joined_stream = nullptr;
     int max_px = 0; // pixels of the largest square
     bool keep_enhanced = false;
+    // several boards per frame (cbv_pipeline_add_board): a board handle is a pipeline object that holds only the per-board
+    // part (configure's squares part: warped frames, planes, temporal state, results) and `parent`; the parent lists its
+    // boards and keeps the device table the multi-board launches read (BoardDev, board 0 = the parent itself)
+    cbv_pipeline* parent = nullptr;
+    std::vector<cbv_pipeline*> boards;
+    DevBuf d_boards;
+    bool mb_any_hough = false;
+    size_t mb_hough_lds[2] = {0, 0};
+    int mb_max_px = 0, mb_max_S = 0;
 };
 
 // the HoughCircles overflow word of the pinned result mirror (behind its max_frames records)
@@ -1577,6 +1586,7 @@ static cbv_pipeline::RunRec* newest_unjoined(cbv_pipeline* p, int s0, int cnt)
 // make the context's stream wait for every run that is still in flight (lanes and scans)
 static int join_scan(cbv_pipeline* p)
 {
+    if (p->parent) p = p->parent; // a board's buffers are written by its parent's runs
     cbv_ctx* ctx = p->ctx;
     if (cbv_pipeline::RunRec* r = newest_unjoined(p, 0, 0)) {
         CBV_HIP(ctx, hipStreamWaitEvent(ctx->stream, r->scan_ev, 0));
@@ -1589,6 +1599,7 @@ static int join_scan(cbv_pipeline* p)
 // may still be queued: the newest overlapping record covers them)
 static int join_slots(cbv_pipeline* p, int s0, int cnt)
 {
+    if (p->parent) p = p->parent;
     cbv_ctx* ctx = p->ctx;
     retire_runs(p);
     if (cbv_pipeline::RunRec* r = newest_unjoined(p, s0, cnt)) {
@@ -1619,12 +1630,27 @@ extern "C" int cbv_pipeline_create(cbv_ctx* ctx, int w, int h, int max_frames, c
     return CBV_OK;
 }
 
+static int pipeline_upload_boards(cbv_pipeline* p);
+static int pipeline_update_region(cbv_pipeline* p);
+static void board_free(cbv_pipeline* b);
+
 extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
 {
     if (!p) return;
     std::lock_guard<std::recursive_mutex> lock(p->ctx->mu);
     (void)hipSetDevice(p->ctx->device);
+    if (p->parent || !p->boards.empty()) (void)join_scan(p); // runs of the parent in flight (lanes, scan) write every board
     (void)hipStreamSynchronize(p->ctx->stream);
+    if (cbv_pipeline* par = p->parent) { // detach: the other boards and the parent go on as they were
+        par->boards.erase(std::find(par->boards.begin(), par->boards.end(), p));
+        if (!par->boards.empty()) (void)pipeline_upload_boards(par);
+        (void)pipeline_update_region(par);
+        board_free(p);
+        return;
+    }
+    for (cbv_pipeline* b : p->boards) board_free(b);
+    p->boards.clear();
+    dev_free(&p->d_boards);
     for (int l = 0; l < cbv_pipeline::MAX_LANES; l++) {
         if (p->lane_stream[l]) (void)hipStreamSynchronize(p->lane_stream[l]);
         if (p->A[l]) (void)hipFree(p->A[l]);
@@ -1656,68 +1682,30 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
 
 extern "C" void* cbv_pipeline_frames_dev(cbv_pipeline* p) { return p ? p->frames : nullptr; }
 
-extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* cfg)
+// the per-board checks of cbv_pipeline_configure (cbv_pipeline_add_board makes the same)
+static int check_board_cfg(cbv_ctx* ctx, const cbv_pipeline_config* cfg)
 {
-    if (!p || !cfg) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
     if (cfg->n_rois <= 0 || cfg->n_rois > CBV_MAX_SQUARES || cfg->board_size <= 0 || cfg->board_size > 4096)
         return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_configure: bad board/roi configuration");
     if (cfg->history_size < 1 || cfg->history_size > 7) return cbv_fail(ctx, CBV_ERR_ARG, "history_size must be in 1..7");
-    RC(check_params(ctx, &cfg->enhance));
     for (int i = 0; i < cfg->n_rois; i++) {
         const cbv_roi& r = cfg->rois[i];
         if (r.w <= 0 || r.h <= 0 || r.w > CBV_MAX_SQUARE_DIM || r.h > CBV_MAX_SQUARE_DIM || r.x0 < 0 || r.y0 < 0 ||
             r.x0 + r.w > cfg->board_size || r.y0 + r.h > cfg->board_size)
             return cbv_fail(ctx, CBV_ERR_ARG, "roi %d is invalid for a %dx%d board", i, cfg->board_size, cfg->board_size);
     }
-    // every argument check that needs no state is done; from here on a failure leaves the pipeline UNconfigured
-    // (run / results / ... return CBV_ERR_STATE) instead of half reconfigured
-    p->configured = false;
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    p->cfg = *cfg;
-    p->keep_enhanced = cfg->keep_enhanced != 0;
-    int chunk = cfg->chunk;
-    if (chunk <= 0) chunk = 32;
-    if (chunk > p->max_frames) chunk = p->max_frames;
-    p->chunk = chunk;
-    if (!host_invert3x3(cfg->M, p->Minv)) memset(p->Minv, 0, sizeof(p->Minv));
+    return CBV_OK;
+}
+
+// the per-board part of cbv_pipeline_configure: warped frames, square descriptors and planes, temporal state, results
+// (p->cfg, Minv and warped_stride are set)
+static int pipeline_setup_board(cbv_pipeline* p, const cbv_pipeline_config* cfg)
+{
+    cbv_ctx* ctx = p->ctx;
     const int S = cfg->board_size;
-    p->warped_stride = ((size_t)S * S * 3 + 255) & ~(size_t)255;
-    // (re)allocate
-    int lanes = cfg->lanes <= 0 ? 2 : cfg->lanes;
-    if (lanes > cbv_pipeline::MAX_LANES) lanes = cbv_pipeline::MAX_LANES;
-    if ((p->max_frames + chunk - 1) / chunk < lanes) lanes = (p->max_frames + chunk - 1) / chunk;
-    p->n_lanes = lanes;
-    for (int l = 0; l < cbv_pipeline::MAX_LANES; l++) {
-        if (p->A[l]) (void)hipFree(p->A[l]);
-        if (p->B[l]) (void)hipFree(p->B[l]);
-        if (p->C[l]) (void)hipFree(p->C[l]);
-        p->A[l] = p->B[l] = p->C[l] = nullptr;
-    }
-    // region-limited enhancement: the source footprint of the S x S warp = the image of the destination square under
-    // Minv (a projective map keeps the square convex while W > 0 on it: its four corners bound it), + 3 px for the
-    // 1/32-px rounding and the bilinear taps
-    p->use_region = false;
-    if (cfg->enhance_region && !p->keep_enhanced && sharpen_region_ok(cfg->enhance.sharpen_kernel))
-        p->use_region = warp_footprint(p->Minv, S, S, p->w, p->h, &p->region);
     if (p->warped) (void)hipFree(p->warped);
-    if (p->enhanced) (void)hipFree(p->enhanced);
-    p->warped = p->enhanced = nullptr;
-    if (!p->start_ev) CBV_HIP(ctx, hipEventCreateWithFlags(&p->start_ev, hipEventDisableTiming));
-    for (int l = 0; l < lanes; l++) {
-        CBV_HIP(ctx, hipMalloc((void**)&p->A[l], p->g.frame_stride * chunk + 256));
-        CBV_HIP(ctx, hipMalloc((void**)&p->B[l], p->g.frame_stride * chunk + 256));
-        if (p->use_region) CBV_HIP(ctx, hipMalloc((void**)&p->C[l], p->g.frame_stride * chunk + 256));
-        SmallLayout SL;
-        RC(small_layout(ctx, &p->lane_small[l], cfg->enhance.tiles_x * cfg->enhance.tiles_y, chunk, &SL, cfg->enhance.tiles_x, cfg->enhance.tiles_y));
-        RC(dev_ensure(ctx, &p->lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * chunk)));
-        if (l > 0) RC(ctx_worker_stream(ctx, &ctx->lane_streams[l], &p->lane_stream[l]));
-        if (!p->lane_done[l]) CBV_HIP(ctx, hipEventCreateWithFlags(&p->lane_done[l], hipEventDisableTiming));
-    }
+    p->warped = nullptr;
     CBV_HIP(ctx, hipMalloc((void**)&p->warped, p->warped_stride * p->max_frames));
-    if (p->keep_enhanced) CBV_HIP(ctx, hipMalloc((void**)&p->enhanced, p->g.frame_stride * p->max_frames + 256));
     // squares
     const int n = cfg->n_rois;
     p->descs.assign(n, SquareDesc());
@@ -1789,7 +1777,241 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     // plane padding (planes are rounded to 16 B) must read as zero in every frame: k_scan compares whole vectors
     CBV_HIP(ctx, hipMemset(p->d_gray.p, 0, off * p->max_frames));
     CBV_HIP(ctx, hipMemset(p->d_ref.p, 0, off));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* cfg)
+{
+    if (!p || !cfg) return CBV_ERR_ARG;
+    cbv_ctx* ctx = p->ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(p)); // lanes and scan of the last run
+    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: a board handle is configured by cbv_pipeline_add_board");
+    if (!p->boards.empty()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: boards are attached (destroy them first)");
+    RC(check_board_cfg(ctx, cfg));
+    RC(check_params(ctx, &cfg->enhance));
+    // every argument check that needs no state is done; from here on a failure leaves the pipeline UNconfigured
+    // (run / results / ... return CBV_ERR_STATE) instead of half reconfigured
+    p->configured = false;
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    p->cfg = *cfg;
+    p->keep_enhanced = cfg->keep_enhanced != 0;
+    int chunk = cfg->chunk;
+    if (chunk <= 0) chunk = 32;
+    if (chunk > p->max_frames) chunk = p->max_frames;
+    p->chunk = chunk;
+    if (!host_invert3x3(cfg->M, p->Minv)) memset(p->Minv, 0, sizeof(p->Minv));
+    const int S = cfg->board_size;
+    p->warped_stride = ((size_t)S * S * 3 + 255) & ~(size_t)255;
+    // (re)allocate
+    int lanes = cfg->lanes <= 0 ? 2 : cfg->lanes;
+    if (lanes > cbv_pipeline::MAX_LANES) lanes = cbv_pipeline::MAX_LANES;
+    if ((p->max_frames + chunk - 1) / chunk < lanes) lanes = (p->max_frames + chunk - 1) / chunk;
+    p->n_lanes = lanes;
+    for (int l = 0; l < cbv_pipeline::MAX_LANES; l++) {
+        if (p->A[l]) (void)hipFree(p->A[l]);
+        if (p->B[l]) (void)hipFree(p->B[l]);
+        if (p->C[l]) (void)hipFree(p->C[l]);
+        p->A[l] = p->B[l] = p->C[l] = nullptr;
+    }
+    // region-limited enhancement: the source footprint of the S x S warp = the image of the destination square under
+    // Minv (a projective map keeps the square convex while W > 0 on it: its four corners bound it), + 3 px for the
+    // 1/32-px rounding and the bilinear taps
+    p->use_region = false;
+    if (cfg->enhance_region && !p->keep_enhanced && sharpen_region_ok(cfg->enhance.sharpen_kernel))
+        p->use_region = warp_footprint(p->Minv, S, S, p->w, p->h, &p->region);
+    if (p->warped) (void)hipFree(p->warped);
+    if (p->enhanced) (void)hipFree(p->enhanced);
+    p->warped = p->enhanced = nullptr;
+    if (!p->start_ev) CBV_HIP(ctx, hipEventCreateWithFlags(&p->start_ev, hipEventDisableTiming));
+    for (int l = 0; l < lanes; l++) {
+        CBV_HIP(ctx, hipMalloc((void**)&p->A[l], p->g.frame_stride * chunk + 256));
+        CBV_HIP(ctx, hipMalloc((void**)&p->B[l], p->g.frame_stride * chunk + 256));
+        if (p->use_region) CBV_HIP(ctx, hipMalloc((void**)&p->C[l], p->g.frame_stride * chunk + 256));
+        SmallLayout SL;
+        RC(small_layout(ctx, &p->lane_small[l], cfg->enhance.tiles_x * cfg->enhance.tiles_y, chunk, &SL, cfg->enhance.tiles_x, cfg->enhance.tiles_y));
+        RC(dev_ensure(ctx, &p->lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * chunk)));
+        if (l > 0) RC(ctx_worker_stream(ctx, &ctx->lane_streams[l], &p->lane_stream[l]));
+        if (!p->lane_done[l]) CBV_HIP(ctx, hipEventCreateWithFlags(&p->lane_done[l], hipEventDisableTiming));
+    }
+    if (p->keep_enhanced) CBV_HIP(ctx, hipMalloc((void**)&p->enhanced, p->g.frame_stride * p->max_frames + 256));
+    RC(pipeline_setup_board(p, cfg));
     p->configured = true;
+    return CBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// several boards per frame
+// ---------------------------------------------------------------------------
+// the device table of a parent's boards (BoardDev: board 0 = the parent); rebuilt whenever a board is attached or
+// detached or a board's background model appears (calibrate).  Nothing may be in flight: the callers joined the runs.
+static int pipeline_upload_boards(cbv_pipeline* p)
+{
+    cbv_ctx* ctx = p->ctx;
+    if (p->boards.empty()) return CBV_OK;
+    std::vector<cbv_pipeline*> all(1, p);
+    all.insert(all.end(), p->boards.begin(), p->boards.end());
+    std::vector<BoardDev> tab(all.size());
+    p->mb_any_hough = false;
+    p->mb_hough_lds[0] = p->mb_hough_lds[1] = 0;
+    p->mb_max_px = p->mb_max_S = 0;
+    for (size_t k = 0; k < all.size(); k++) {
+        cbv_pipeline* q = all[k];
+        const cbv_pipeline_config& c = q->cfg;
+        BoardDev& T = tab[k];
+        memset(&T, 0, sizeof(T));
+        memcpy(T.Minv, q->Minv, sizeof(T.Minv));
+        T.S = c.board_size;
+        T.rot180 = c.rot180;
+        // launch_warp's block shape of an S x S destination (BLOCK_SZ = 32)
+        int bh0 = 16 < T.S ? 16 : T.S;
+        const int bw0 = 1024 / bh0 < T.S ? 1024 / bh0 : T.S;
+        bh0 = 1024 / bw0 < T.S ? 1024 / bw0 : T.S;
+        T.bw0 = bw0;
+        T.bh0 = bh0;
+        T.warped = q->warped;
+        T.warped_stride = q->warped_stride;
+        T.descs = (const SquareDesc*)q->d_descs.p;
+        T.n = c.n_rois;
+        T.want_hough = c.use_hough;
+        T.masks = (const u8*)q->d_masks.p;
+        T.gray = (u8*)q->d_gray.p;
+        T.plane_total = q->plane_total;
+        T.mean = q->calibrated ? (const float*)q->d_mean.p : nullptr;
+        T.sd = q->calibrated ? (const float*)q->d_var.p + q->plane_total : nullptr;
+        T.z_thresh = (float)c.z_threshold;
+        T.stats = (cbv_sq_stats*)q->d_stats.p;
+        T.dec = (u8*)q->d_dec.p;
+        T.hough = c.use_hough ? (cbv_hough_result*)q->d_hough.p : nullptr;
+        if (c.use_hough) {
+            size_t lds[2];
+            hough_board_cfgs(q->hough_cfg, T.hcfg, lds);
+            if (!lds[0] || !lds[1])
+                return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles stage: %dx%d squares of board %d do not fit the LDS layout",
+                                q->hough_cfg.maxw, q->hough_cfg.maxh, (int)k);
+            p->mb_any_hough = true;
+            p->mb_hough_lds[0] = std::max(p->mb_hough_lds[0], lds[0]);
+            p->mb_hough_lds[1] = std::max(p->mb_hough_lds[1], lds[1]);
+        }
+        T.sp = scan_params(c, q->calibrated);
+        T.ref = (u8*)q->d_ref.p;
+        T.state = (ScanState*)q->d_state.p;
+        T.flags = (u8*)q->d_flags.p;
+        T.results = (cbv_frame_result*)q->d_results.p;
+        T.check = (const u64*)q->d_check.p; // (all-zero sets = no squares_to_check)
+        T.noise_state = (cbv_noise_state*)q->d_noise_state.p;
+        T.noise = (cbv_noise_result*)q->d_noise.p;
+        T.mirror = (cbv_frame_result*)q->h_stage;
+        T.over_src = c.use_hough ? (const u32*)q->d_hough_over.p : nullptr;
+        T.over_dst = pipeline_over_word(q);
+        p->mb_max_px = std::max(p->mb_max_px, q->max_px);
+        p->mb_max_S = std::max(p->mb_max_S, c.board_size);
+    }
+    RC(dev_ensure(ctx, &p->d_boards, sizeof(BoardDev) * tab.size()));
+    CBV_HIP(ctx, hipMemcpyAsync(p->d_boards.p, tab.data(), sizeof(BoardDev) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+// enhance_region of a pipeline with boards: the bounding rectangle of every board's warp footprint (any board without
+// one: the whole frame); the third scratch frame set is allocated when the region first becomes usable
+static int pipeline_update_region(cbv_pipeline* p)
+{
+    cbv_ctx* ctx = p->ctx;
+    const cbv_pipeline_config& cfg = p->cfg;
+    bool use = cfg.enhance_region && !p->keep_enhanced && sharpen_region_ok(cfg.enhance.sharpen_kernel);
+    PxRect u = {0, 0, 0, 0};
+    if (use) use = warp_footprint(p->Minv, cfg.board_size, cfg.board_size, p->w, p->h, &u);
+    for (cbv_pipeline* q : p->boards) {
+        PxRect r;
+        if (!use || !warp_footprint(q->Minv, q->cfg.board_size, q->cfg.board_size, p->w, p->h, &r)) {
+            use = false;
+            break;
+        }
+        u = {std::min(u.x0, r.x0), std::min(u.y0, r.y0), std::max(u.x1, r.x1), std::max(u.y1, r.y1)};
+    }
+    if (use)
+        for (int l = 0; l < p->n_lanes; l++)
+            if (!p->C[l]) CBV_HIP(ctx, hipMalloc((void**)&p->C[l], p->g.frame_stride * p->chunk + 256));
+    p->use_region = use;
+    if (use) p->region = u;
+    return CBV_OK;
+}
+
+// free a board handle's buffers (it has no lanes, frames or runs of its own)
+static void board_free(cbv_pipeline* b)
+{
+    if (b->h_stage) (void)hipHostFree(b->h_stage);
+    if (b->warped) (void)hipFree(b->warped);
+    DevBuf* bufs[] = {&b->d_descs, &b->d_masks, &b->d_gray, &b->d_stats, &b->d_ref, &b->d_state, &b->d_results, &b->d_flags, &b->d_dec, &b->d_noise, &b->d_noise_state, &b->d_coef, &b->d_synth, &b->d_mean, &b->d_var, &b->d_hough, &b->d_check, &b->d_hough_over};
+    for (auto d : bufs) dev_free(d);
+    delete b;
+}
+
+extern "C" int cbv_pipeline_add_board(cbv_pipeline* p, const cbv_board_config* bc, cbv_pipeline** out)
+{
+    if (!p || !bc || !out) return cbv_fail(p ? p->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_add_board: bad arguments");
+    cbv_ctx* ctx = p->ctx;
+    CBV_ENTER(ctx);
+    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_add_board: the parent is itself a board handle");
+    if (!p->configured) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_add_board: the parent is not configured");
+    if ((int)p->boards.size() + 1 >= CBV_MAX_BOARDS)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_add_board: a pipeline holds at most %d boards", CBV_MAX_BOARDS);
+    if (p->max_frames >= (1 << (MB_BOARD_SHIFT - 8)))
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_add_board: at most %d frames in a pipeline with boards", (1 << (MB_BOARD_SHIFT - 8)) - 1);
+    // the board's configuration = the parent's with the board's subset replaced
+    cbv_pipeline_config cfg = p->cfg;
+    memcpy(cfg.M, bc->M, sizeof(cfg.M));
+    cfg.board_size = bc->board_size;
+    cfg.rot180 = bc->rot180;
+    cfg.n_rois = bc->n_rois;
+    memcpy(cfg.rois, bc->rois, sizeof(cfg.rois));
+    cfg.history_size = bc->history_size;
+    cfg.min_presence = bc->min_presence;
+    cfg.change_threshold = bc->change_threshold;
+    cfg.z_threshold = bc->z_threshold;
+    cfg.initial_variance = bc->initial_variance;
+    cfg.use_hough = bc->use_hough;
+    cfg.hough = bc->hough;
+    RC(check_board_cfg(ctx, &cfg));
+    if (cfg.use_hough) RC(hough_params_check(ctx, &cfg.hough));
+    RC(join_scan(p));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // the parent's worklists hold every board's items (grown only: a larger list serves fewer boards as well)
+    for (int l = 0; l < p->n_lanes; l++)
+        RC(dev_ensure(ctx, &p->lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * p->chunk * (p->boards.size() + 2))));
+    cbv_pipeline* b = new cbv_pipeline();
+    b->ctx = ctx;
+    b->w = p->w;
+    b->h = p->h;
+    b->max_frames = p->max_frames;
+    b->g = p->g;
+    b->chunk = p->chunk;
+    b->keep_enhanced = p->keep_enhanced;
+    b->cfg = cfg;
+    if (!host_invert3x3(cfg.M, b->Minv)) memset(b->Minv, 0, sizeof(b->Minv));
+    b->warped_stride = ((size_t)cfg.board_size * cfg.board_size * 3 + 255) & ~(size_t)255;
+    int rc = pipeline_setup_board(b, &cfg);
+    if (rc == CBV_OK) {
+        b->parent = p;
+        b->configured = true;
+        p->boards.push_back(b);
+        rc = pipeline_upload_boards(p);
+        if (rc == CBV_OK) rc = pipeline_update_region(p);
+        if (rc != CBV_OK) {
+            p->boards.pop_back();
+            const std::string err = ctx->err;
+            if (!p->boards.empty()) (void)pipeline_upload_boards(p);
+            (void)pipeline_update_region(p);
+            ctx->err = err;
+        }
+    }
+    if (rc != CBV_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        board_free(b);
+        return rc;
+    }
+    *out = b;
     return CBV_OK;
 }
 
@@ -1819,6 +2041,8 @@ extern "C" int cbv_pipeline_calibrate(cbv_pipeline* p, int slot)
     RC(launch_squares_calibrate(ctx, (const SquareDesc*)p->d_descs.p, p->cfg.n_rois, (const u8*)p->d_gray.p + p->plane_total * slot,
                                 (float*)p->d_mean.p, (float*)p->d_var.p, (float*)p->d_var.p + p->plane_total, (float)p->cfg.initial_variance, nullptr));
     p->calibrated = true;
+    cbv_pipeline* root = p->parent ? p->parent : p;
+    if (!root->boards.empty()) RC(pipeline_upload_boards(root)); // the board's statistics read its model from now on
     return CBV_OK;
 }
 
@@ -1837,6 +2061,7 @@ extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int res
 
 extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr, int stride)
 {
+    if (p && p->parent) return cbv_fail(p->ctx, CBV_ERR_STATE, "cbv_pipeline_upload: frames go to the parent of a board");
     if (!p || !bgr || slot < 0 || slot >= p->max_frames || stride < p->w * 3) return CBV_ERR_ARG;
     cbv_ctx* ctx = p->ctx;
     CBV_ENTER(ctx);
@@ -1851,6 +2076,10 @@ extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)
     if (!p) return nullptr;
     cbv_ctx* ctx = p->ctx;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    if (p->parent) {
+        cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_host_ring: frames go to the parent of a board");
+        return nullptr;
+    }
     if (!p->host_ring) {
         if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
         if (hipHostMalloc((void**)&p->host_ring, p->g.frame_stride * p->max_frames, hipHostMallocDefault) != hipSuccess) {
@@ -1865,6 +2094,7 @@ extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
 {
     if (!p) return CBV_ERR_ARG;
     cbv_ctx* ctx = p->ctx;
+    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_submit: frames go to the parent of a board");
     if (slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_submit: bad slot range");
     if (!p->host_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_submit: cbv_pipeline_host_ring() was never called");
     CBV_ENTER(ctx);
@@ -1910,6 +2140,7 @@ extern "C" int cbv_pipeline_wait_submitted(cbv_pipeline* p)
 extern "C" int cbv_pipeline_synth(cbv_pipeline* p, int slot0, int count, const uint64_t* seeds, const double* Hinv9,
                                   const uint8_t* boards, const cbv_scene* scene)
 {
+    if (p && p->parent) return cbv_fail(p->ctx, CBV_ERR_STATE, "cbv_pipeline_synth: frames go to the parent of a board");
     if (!p || !seeds || !Hinv9 || !boards || !scene || slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return CBV_ERR_ARG;
     cbv_ctx* ctx = p->ctx;
     CBV_ENTER(ctx);
@@ -1962,22 +2193,29 @@ static int pipeline_run_tail(cbv_pipeline* p, cbv_pipeline::RunRec* rec, int slo
         hipStream_t s;
         ~Restore() { c->stream = s; }
     } restore{ctx, main_stream};
+    if (!p->boards.empty()) { // every board's second pass, scan, packing and NoiseHandler: one launch each
+        const BoardDev* tab = (const BoardDev*)p->d_boards.p;
+        const int nb = 1 + (int)p->boards.size();
+        if (p->mb_any_hough)
+            RC(launch_hough_mb(ctx, tab, nb, slot0, (const u32*)rec->retry.p, CBV_MAX_SQUARES * nb * count, p->mb_hough_lds[1], nullptr, 0, 1));
+        const bool mirrored = count <= 4;
+        for (int k = 0; k < nb; k++) {
+            cbv_pipeline* q = k == 0 ? p : p->boards[k - 1];
+            for (int t = 0; t < count; t++) q->slot_mirrored[(size_t)slot0 + t] = mirrored ? 1 : 0;
+        }
+        RC(launch_scan_mb(ctx, tab, nb, slot0, count, mirrored ? 1 : 0));
+        CBV_HIP(ctx, hipEventRecord(rec->scan_ev, scan_on));
+        rec->s0 = slot0;
+        rec->cnt = count;
+        rec->seq = ++p->run_seq;
+        rec->live = true;
+        return CBV_OK;
+    }
     if (cfg.use_hough) // squares whose first HoughCircles pass overflowed (normally none), before the scan reads the decisions
         RC(launch_hough_second(ctx, (const SquareDesc*)p->d_descs.p, n, (const u8*)p->d_gray.p + p->plane_total * slot0, p->plane_total,
                                p->hough_cfg, (cbv_hough_result*)p->d_hough.p + (size_t)CBV_MAX_SQUARES * slot0,
                                (u8*)p->d_dec.p + (size_t)CBV_MAX_SQUARES * slot0, (const u32*)rec->retry.p, n * count));
-    ScanParams sp;
-    sp.n = n;
-    sp.history_size = cfg.history_size;
-    sp.min_presence = cfg.min_presence;
-    sp.change_threshold = cfg.change_threshold;
-    sp.with_model = p->calibrated ? 1 : 0;
-    sp.stable_table = 0;
-    for (int len = 1; len <= 7 && len <= cfg.history_size; len++)
-        for (int sum = 0; sum <= len; sum++)
-            if ((double)sum / (double)len >= cfg.min_presence) sp.stable_table |= 1ull << (len * 8 + sum);
-    sp.thr_is_int = (cfg.change_threshold == (double)(int)cfg.change_threshold && cfg.change_threshold >= 0 && cfg.change_threshold < 256) ? 1 : 0;
-    sp.thr_int = (int)cfg.change_threshold;
+    const ScanParams sp = scan_params(cfg, p->calibrated);
     // A short run (the live-camera case) writes its records to the pinned mirror too: reading them back is then a wait and a
     // host copy instead of two more launches.  Not the long runs: their records would cross PCIe as thousands of 8-byte
     // writes inside the scan stream's critical path (512-frame steps: -0.5 % frames/s, alternating A/B runs); they are
@@ -2008,6 +2246,7 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
 {
     if (!p || !p->configured) return CBV_ERR_STATE;
     cbv_ctx* ctx = p->ctx;
+    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: a board is run by its parent");
     if (slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_run: bad slot range");
     CBV_ENTER(ctx);
     const cbv_pipeline_config& cfg = p->cfg;
@@ -2047,8 +2286,13 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
     // the second-pass list's counter: zeroed before the lanes fork from this stream, or, when the run is ONE chunk, by that
     // chunk's k_warp (a memset is a launch of its own, ~13 us with its bubble in front of a 150 us chain)
     const bool retry_zero_in_warp = chunks == 1;
-    if (cfg.use_hough) {
-        RC(dev_ensure(ctx, &rec->retry, sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * p->max_frames)));
+    // with boards attached, each per-board stage below is one launch for all of them (BoardDev table)
+    const bool mb = !p->boards.empty();
+    const int nb = 1 + (int)p->boards.size();
+    const BoardDev* tab = (const BoardDev*)p->d_boards.p;
+    const bool any_hough = mb ? p->mb_any_hough : cfg.use_hough != 0;
+    if (any_hough) {
+        RC(dev_ensure(ctx, &rec->retry, sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * p->max_frames * nb)));
         if (!retry_zero_in_warp) CBV_HIP(ctx, hipMemsetAsync(rec->retry.p, 0, sizeof(u32), main_stream));
     }
     for (auto& c : p->copies) // ingest copies of these slots must have landed
@@ -2078,13 +2322,24 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
                              p->use_region ? &p->region : nullptr, p->C[lane]);
         if (rc_all) break;
         u8* wdst = p->warped + p->warped_stride * s0;
-        u32* work = cfg.use_hough ? (u32*)p->lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
-        u32* retry0 = cfg.use_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
+        u32* work = any_hough ? (u32*)p->lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
+        u32* retry0 = any_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
         if (p->keep_enhanced) {
             if (hipMemcpyAsync(p->enhanced + p->g.frame_stride * s0, res, p->g.frame_stride * b, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
                 rc_all = cbv_fail(ctx, CBV_ERR_HIP, "copy of the enhanced frames failed");
                 break;
             }
+        }
+        if (mb) {
+            rc_all = launch_warp_mb(ctx, res, p->g, tab, nb, p->mb_max_S, s0, p->keep_enhanced ? NormSrc() : norm, b, work, retry0);
+            if (rc_all) break;
+            rc_all = launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, any_hough, work, p->mb_max_px);
+            if (rc_all) break;
+            if (any_hough)
+                rc_all = launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, p->mb_hough_lds[0], (u32*)rec->retry.p, s0 - slot0, 0);
+            continue;
+        }
+        if (p->keep_enhanced) {
             rc_all = launch_warp(ctx, res, p->g, p->Minv, S, S, cfg.rot180, wdst, S * 3, p->warped_stride, NormSrc(), b, work, retry0);
         } else {
             rc_all = launch_warp(ctx, res, p->g, p->Minv, S, S, cfg.rot180, wdst, S * 3, p->warped_stride, norm, b, work, retry0);
@@ -2202,6 +2457,7 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
     RC(join_scan(p)); // lanes and scan of the last run
     const u8* src;
     size_t bytes;
+    if (p->parent && which != 2) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: a board holds only its warped frames (which = 2)");
     if (which == 0) {
         src = p->frames + p->g.frame_stride * slot;
         bytes = (size_t)p->w * p->h * 3;

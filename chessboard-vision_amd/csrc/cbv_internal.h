@@ -133,6 +133,7 @@ struct cbv_ctx {
     hipStream_t lane_streams[4] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t scan_stream = nullptr, copy_stream = nullptr;
     int lane_rr = 0; // next lane of the round the pipelines' chunks are dealt on (cbv_pipeline_run)
+    bool hough_mb_lds_raised = false; // the same for k_hough's multi-board instance
 };
 int ctx_worker_stream(cbv_ctx* ctx, hipStream_t* slot, hipStream_t* out);
 int ctx_hstage(cbv_ctx* ctx, size_t bytes, u8** p);
@@ -434,3 +435,58 @@ int launch_scan(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, const u8* 
                 const u8* decisions, u8* ref, ScanState* state, u8* flags, cbv_frame_result* results, int count,
                 const u64* check = nullptr, cbv_noise_state* noise_state = nullptr, cbv_noise_result* noise_out = nullptr,
                 ResultMirror mir = ResultMirror());
+
+
+// ---------------------------------------------------------------------------
+// Several boards per frame (cbv_pipeline_add_board): the per-board stages of a chunk are ONE launch each for all boards,
+// the board on the grid.  Every per-board input sits in this device table (one entry per board, board 0 = the pipeline
+// itself); pointers are those of slot 0, the launches add their first slot.  The multi-board kernels rebind their
+// arguments from the entry and then run the single-board bodies unchanged, so a board computes what a pipeline of its
+// own computes.  HoughCircles' worklist and second-pass entries carry the board in their top bits (MB_BOARD_SHIFT).
+// ---------------------------------------------------------------------------
+#define MB_BOARD_SHIFT 29 // work item = board << 29 | frame << 8 | square: frames of a list < 2^21
+struct BoardDev {
+    // warp
+    double Minv[9];
+    int S, rot180, bw0, bh0;
+    u8* warped;
+    size_t warped_stride;
+    // squares + HoughCircles
+    const SquareDesc* descs;
+    int n;
+    int want_hough;              // cbv_pipeline_config::use_hough of the board
+    const u8* masks;
+    u8* gray;                    // [slot] planes, plane_total apart
+    size_t plane_total;
+    const float* mean;           // null until the board is calibrated
+    const float* sd;
+    float z_thresh;
+    int pad0;
+    cbv_sq_stats* stats;         // [slot][n]
+    u8* dec;                     // [slot][CBV_MAX_SQUARES]
+    cbv_hough_result* hough;     // [slot][CBV_MAX_SQUARES], null without use_hough
+    HoughCfg hcfg[2];            // first / second pass, layout and maxc filled (hough_board_cfgs)
+    // temporal scan + NoiseHandler
+    ScanParams sp;
+    u8* ref;
+    ScanState* state;
+    u8* flags;                   // [slot][CBV_MAX_SQUARES]
+    cbv_frame_result* results;   // [slot]
+    const u64* check;            // [slot]
+    cbv_noise_state* noise_state;
+    cbv_noise_result* noise;     // [slot]
+    cbv_frame_result* mirror;    // pinned [slot] (ResultMirror of short runs)
+    const u32* over_src;         // HoughCircles overflow counter, null without use_hough
+    u32* over_dst;               // its pinned copy
+};
+ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
+// per-pass HoughCfg of a board (layout and maxc as launch_hough / launch_hough_second set them); returns the LDS bytes
+// of each pass, 0 when the squares cannot run (the single-board launchers' checks)
+void hough_board_cfgs(HoughCfg base, HoughCfg out[2], size_t lds[2]);
+// one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0
+int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, NormSrc norm, int batch,
+                   u32* zero_word, u32* zero_word2);
+int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
+int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
+                    int retry_frame_base, int pass);
+int launch_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int mirrored);

@@ -69,21 +69,15 @@ __device__ __forceinline__ void hg_sobel(const u8* g, int gs, int x, int y, int&
 
 __device__ __forceinline__ int hg_sel4(int i, int a, int b, int c, int d) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
 
-__global__ __launch_bounds__(HG_NT) void k_hough(const SquareDesc* __restrict__ descs, const u8* __restrict__ gray,
-                                                size_t gray_frame_stride, HoughCfg cfg,
-                                                cbv_hough_result* __restrict__ out, u8* __restrict__ decisions,
-                                                const u32* __restrict__ work, int nsq, int total_items)
+// one work item (square sqi of frame fri) of k_hough / k_hough_mb; rtag = the board's bits of a second-pass entry
+__device__ __forceinline__ void hough_item(const SquareDesc* __restrict__ descs, const u8* __restrict__ gray,
+                                           size_t gray_frame_stride, const HoughCfg& cfg,
+                                           cbv_hough_result* __restrict__ out, u8* __restrict__ decisions, int sqi, int fri, u32 rtag)
 {
     extern __shared__ __align__(16) u8 smem[];
     __shared__ int s_cnt[4]; // 0 weak, 1 edges, 2 centres, 3 circles
     __shared__ int s_over;
-    // Work items: with a worklist (pipeline), work[0] = count and work[1 + i] = frame << 8 | square, filled by
-    // k_squares_stats for the squares whose has_piece the statistics left open; otherwise every (square, frame).
-    // A fixed grid of workgroups strides over the items, so idle workgroups never hold an LDS slot.
-    const int n_items = work ? (int)work[0] : total_items;
-    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const int sqi = work ? (int)(work[1 + item] & 255u) : item % nsq;
-    const int fri = work ? (int)(work[1 + item] >> 8) : item / nsq;
+    {
     const size_t oi = (size_t)fri * CBV_MAX_SQUARES + sqi;
     const SquareDesc d = descs[sqi];
     const int w = d.w, h = d.h, n = w * h;
@@ -346,10 +340,10 @@ __global__ __launch_bounds__(HG_NT) void k_hough(const SquareDesc* __restrict__ 
     if (s_over && cfg.retry) { // workgroup-uniform: hand the square to the second pass, decide nothing here
         if (tid == 0) {
             const u32 k = atomicAdd(&cfg.retry[0], 1u);
-            cfg.retry[1 + k] = ((u32)(fri + cfg.retry_frame_base) << 8) | (u32)sqi;
+            cfg.retry[1 + k] = rtag | ((u32)(fri + cfg.retry_frame_base) << 8) | (u32)sqi;
         }
         __syncthreads(); // s_over / s_cnt are reset at the top of the next item
-        continue;
+        return;
     }
     const int ncent = min(s_cnt[2], cfg.maxc);
     // P6: radius of every centre.  Wave `wave` histograms centre c0 + wave into its own bins, turns them into
@@ -551,7 +545,43 @@ __global__ __launch_bounds__(HG_NT) void k_hough(const SquareDesc* __restrict__ 
     }
     } // wave 0
     __syncthreads(); // LDS is reused by the next item
-    } // items
+    }
+}
+
+__global__ __launch_bounds__(HG_NT) void k_hough(const SquareDesc* __restrict__ descs, const u8* __restrict__ gray,
+                                                size_t gray_frame_stride, HoughCfg cfg,
+                                                cbv_hough_result* __restrict__ out, u8* __restrict__ decisions,
+                                                const u32* __restrict__ work, int nsq, int total_items)
+{
+    // Work items: with a worklist (pipeline), work[0] = count and work[1 + i] = frame << 8 | square, filled by
+    // k_squares_stats for the squares whose has_piece the statistics left open; otherwise every (square, frame).
+    // A fixed grid of workgroups strides over the items, so idle workgroups never hold an LDS slot.
+    const int n_items = work ? (int)work[0] : total_items;
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int sqi = work ? (int)(work[1 + item] & 255u) : item % nsq;
+        const int fri = work ? (int)(work[1 + item] >> 8) : item / nsq;
+        hough_item(descs, gray, gray_frame_stride, cfg, out, decisions, sqi, fri, 0u);
+    }
+}
+
+// every board of a pipeline in one launch: the items of all boards share one list, board << MB_BOARD_SHIFT | frame << 8 |
+// square, and each item runs with its board's descriptors, planes and HoughCfg (`pass`: 0 first, 1 second pass)
+__global__ __launch_bounds__(HG_NT) void k_hough_mb(const BoardDev* __restrict__ tab, int s0, const u32* __restrict__ work, int pass,
+                                                   u32* __restrict__ retry, int retry_frame_base)
+{
+    const int n_items = (int)work[0];
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const u32 e = work[1 + item];
+        const int b = (int)(e >> MB_BOARD_SHIFT);
+        const int sqi = (int)(e & 255u), fri = (int)((e >> 8) & ((1u << (MB_BOARD_SHIFT - 8)) - 1u));
+        const BoardDev& T = tab[b];
+        HoughCfg cfg = T.hcfg[pass];
+        cfg.retry = retry;
+        cfg.retry_frame_base = retry_frame_base;
+        const size_t s = (size_t)s0;
+        hough_item(T.descs, T.gray + s * T.plane_total, T.plane_total, cfg, T.hough + s * CBV_MAX_SQUARES, T.dec + s * CBV_MAX_SQUARES,
+                   sqi, fri, (u32)b << MB_BOARD_SHIFT);
+    }
 }
 
 // LDS layout for squares up to maxw x maxh
@@ -592,6 +622,44 @@ static size_t hough_layout(HoughCfg& cfg)
     return off;
 }
 
+// The set-up shared by the single- and the multi-board launches, so that a board computes what a pipeline of its own does.
+static bool hough_dims_ok(const HoughCfg& cfg) { return !(cfg.maxw < 2 || cfg.maxh < 2 || cfg.maxw > 250 || cfg.maxh > 250); }
+
+// maxc of a pass (retry fields cleared: the launch sets them).  First pass: small candidate lists (two workgroups per CU);
+// squares that overflow them go to `retry`.  Second pass, over the listed squares only (normally none: the workgroups read
+// a zero count and leave): no two 4-neighbours can both be maxima (a > left and a >= right exclude each other), so half
+// the cells + 1 is room for every possible maximum; larger squares are capped by LDS and can still flag an overflow.
+static HoughCfg hough_pass_cfg(HoughCfg cfg, int pass)
+{
+    cfg.retry = nullptr;
+    cfg.retry_frame_base = 0;
+    if (pass == 0) {
+        cfg.maxc = HG_MAXC;
+        return cfg;
+    }
+    const float idp = 1.f / (cfg.dp < 1.f ? 1.f : cfg.dp);
+    const int cells = (int)ceilf(cfg.maxh * idp) * (int)ceilf(cfg.maxw * idp);
+    cfg.maxc = (cells + 1) / 2 + 1;
+    for (;;) {
+        HoughCfg probe = cfg;
+        if (hough_layout(probe) <= 150 * 1024 || cfg.maxc <= HG_MAXC) break;
+        cfg.maxc = cfg.maxc * 3 / 4;
+    }
+    if (cfg.maxc < HG_MAXC) cfg.maxc = HG_MAXC;
+    return cfg;
+}
+
+// as many workgroups as the chip holds at once (LDS-limited), striding over the work items
+static int hough_grid(cbv_ctx* ctx, size_t lds, int max_grid, int total)
+{
+    const int per_cu = (int)(160 * 1024 / (lds + 1024)) < 2 ? ((int)(160 * 1024 / (lds + 1024)) < 1 ? 1 : (int)(160 * 1024 / (lds + 1024))) : 2;
+    int grid = ctx->num_cus * per_cu;
+    if (grid > max_grid) grid = max_grid;
+    if (grid > total) grid = total;
+    if (grid < 1) grid = 1;
+    return grid;
+}
+
 static int launch_hough_pass(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, HoughCfg cfg,
                              cbv_hough_result* out, u8* decisions, const u32* work, int total, int max_grid)
 {
@@ -602,12 +670,7 @@ static int launch_hough_pass(cbv_ctx* ctx, const SquareDesc* descs, int n, const
         CBV_HIP(ctx, hipFuncSetAttribute((const void*)k_hough, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
         ctx->hough_lds_raised = true;
     }
-    // as many workgroups as the chip holds at once (LDS-limited), striding over the work items
-    const int per_cu = (int)(160 * 1024 / (lds + 1024)) < 2 ? ((int)(160 * 1024 / (lds + 1024)) < 1 ? 1 : (int)(160 * 1024 / (lds + 1024))) : 2;
-    int grid = ctx->num_cus * per_cu;
-    if (grid > max_grid) grid = max_grid;
-    if (grid > total) grid = total;
-    if (grid < 1) grid = 1;
+    const int grid = hough_grid(ctx, lds, max_grid, total);
     hipLaunchKernelGGL(k_hough, dim3(grid), dim3(HG_NT), lds, ctx->stream, descs, gray, gray_frame_stride, cfg, out, decisions, work, n, total);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
@@ -616,10 +679,9 @@ static int launch_hough_pass(cbv_ctx* ctx, const SquareDesc* descs, int n, const
 int launch_hough(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, HoughCfg cfg,
                  cbv_hough_result* out, u8* decisions, const u32* work, int batch, u32* retry, int retry_frame_base)
 {
-    if (cfg.maxw < 2 || cfg.maxh < 2 || cfg.maxw > 250 || cfg.maxh > 250)
+    if (!hough_dims_ok(cfg))
         return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles stage: squares must be 2..250 px (got %dx%d)", cfg.maxw, cfg.maxh);
-    // first pass: small candidate lists (two workgroups per CU); squares that overflow them go to `retry`
-    cfg.maxc = HG_MAXC;
+    cfg = hough_pass_cfg(cfg, 0);
     cfg.retry = retry;
     cfg.retry_frame_base = retry_frame_base;
     prof_begin(ctx, CBV_K_HOUGH);
@@ -631,19 +693,31 @@ int launch_hough(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, s
 int launch_hough_second(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, HoughCfg cfg,
                         cbv_hough_result* out, u8* decisions, const u32* retry, int max_items)
 {
-    // Second pass over the listed squares only (normally none: the workgroups read a zero count and leave).
-    // No two 4-neighbours can both be maxima (a > left and a >= right exclude each other), so half the cells
-    // + 1 is room for every possible maximum; larger squares are capped by LDS and can still flag an overflow.
-    const float idp = 1.f / (cfg.dp < 1.f ? 1.f : cfg.dp);
-    const int cells = (int)ceilf(cfg.maxh * idp) * (int)ceilf(cfg.maxw * idp);
-    cfg.maxc = (cells + 1) / 2 + 1;
-    cfg.retry = nullptr;
-    cfg.retry_frame_base = 0;
-    for (;;) {
-        HoughCfg probe = cfg;
-        if (hough_layout(probe) <= 150 * 1024 || cfg.maxc <= HG_MAXC) break;
-        cfg.maxc = cfg.maxc * 3 / 4;
+    return launch_hough_pass(ctx, descs, n, gray, gray_frame_stride, hough_pass_cfg(cfg, 1), out, decisions, retry, max_items, 32);
+}
+
+void hough_board_cfgs(HoughCfg cfg, HoughCfg out[2], size_t lds[2])
+{
+    for (int k = 0; k < 2; k++) {
+        out[k] = hough_pass_cfg(cfg, k);
+        lds[k] = hough_layout(out[k]);
+        if (!hough_dims_ok(cfg) || lds[k] > 150 * 1024) lds[k] = 0;
     }
-    if (cfg.maxc < HG_MAXC) cfg.maxc = HG_MAXC;
-    return launch_hough_pass(ctx, descs, n, gray, gray_frame_stride, cfg, out, decisions, retry, max_items, 32);
+}
+
+int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
+                    int retry_frame_base, int pass)
+{
+    (void)nb;
+    if (lds > 64 * 1024 && !ctx->hough_mb_lds_raised) {
+        CBV_HIP(ctx, hipFuncSetAttribute((const void*)k_hough_mb, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        ctx->hough_mb_lds_raised = true;
+    }
+    const int grid = hough_grid(ctx, lds, pass == 0 ? 1 << 30 : 32, max_items); // (as launch_hough / launch_hough_second)
+    if (pass == 0) prof_begin(ctx, CBV_K_HOUGH);
+    hipLaunchKernelGGL(k_hough_mb, dim3(grid), dim3(HG_NT), lds, ctx->stream, tab, s0, work, pass, pass == 0 ? retry : nullptr,
+                       retry_frame_base);
+    if (pass == 0) prof_end(ctx, CBV_K_HOUGH);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
 }

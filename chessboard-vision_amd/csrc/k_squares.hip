@@ -228,7 +228,7 @@ __device__ __forceinline__ void sq_accum_finish(SqAccum& A, u32* acc, float* zm,
                                                 cbv_sq_stats* __restrict__ out, int nsq, u8* __restrict__ decisions,
                                                 int want_hough, u32* __restrict__ hough_work,
                                                 cbv_hough_result* __restrict__ hough_out, const u32* __restrict__ cnt,
-                                                const DetectMasks dm = DetectMasks())
+                                                const DetectMasks dm = DetectMasks(), u32 wtag = 0)
 {
 #pragma unroll
     for (int k = 0; k < 16; k++) {
@@ -287,7 +287,7 @@ __device__ __forceinline__ void sq_accum_finish(SqAccum& A, u32* acc, float* zm,
             u32 dc = dp == 1 ? 1u : 0u;
             if (want_hough && (dp == 2 || (want_hough == 2 && dp == 1))) {
                 dc |= 16u;
-                if (hough_work) hough_work[1 + atomicAdd(&hough_work[0], 1u)] = ((u32)blockIdx.z << 8) | blockIdx.x;
+                if (hough_work) hough_work[1 + atomicAdd(&hough_work[0], 1u)] = wtag | ((u32)blockIdx.z << 8) | blockIdx.x;
             } else if (want_hough && hough_out) {
                 cbv_hough_result r;
                 memset(&r, 0, sizeof(r));
@@ -336,20 +336,19 @@ __global__ __launch_bounds__(256) void k_squares_stats(const SquareDesc* __restr
 // two (64-128 squares on 256 CUs: then a square's three passes are latency, and four times the lanes cut it).
 // GATE: the class-API launch (one frame: |gray - reference| and detect_all_pieces' per-square gate); the batched pipeline
 // launches compile without it
+// (the body of k_squares_pre5_stats and k_squares_pre5_stats_mb; wtag = the board's bits of a HoughCircles work item)
 template <int NT, bool GATE>
-__global__ __launch_bounds__(NT) void k_squares_pre5_stats(const u8* __restrict__ src, size_t src_frame_stride,
-                                                             const SquareDesc* __restrict__ descs, u8* __restrict__ gray,
-                                                             size_t gray_frame_stride, const float* __restrict__ mean,
-                                                             const float* __restrict__ var, const u8* __restrict__ masks,
-                                                             float z_thresh, cbv_sq_stats* __restrict__ out, int nsq,
-                                                             u8* __restrict__ decisions, int want_hough,
-                                                             u32* __restrict__ hough_work, cbv_hough_result* __restrict__ hough_out,
-                                                             const u8* __restrict__ ref, const DetectMasks dm)
+__device__ __forceinline__ void pre5_stats_body(const u8* __restrict__ src, size_t src_frame_stride,
+                                                const SquareDesc* __restrict__ descs, u8* __restrict__ gray,
+                                                size_t gray_frame_stride, const float* __restrict__ mean,
+                                                const float* __restrict__ var, const u8* __restrict__ masks,
+                                                float z_thresh, cbv_sq_stats* __restrict__ out, int nsq,
+                                                u8* __restrict__ decisions, int want_hough,
+                                                u32* __restrict__ hough_work, cbv_hough_result* __restrict__ hough_out,
+                                                const u8* __restrict__ ref, const DetectMasks dm, u32 wtag,
+                                                u32* acc, float* zm, int* nanf_)
 {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    __shared__ u32 acc[20];
-    __shared__ float zm[NT / 64];
-    __shared__ int nanf_[1];
     const SquareDesc d = descs[blockIdx.x];
     const int w = d.w, h = d.h, n = w * h;
     u8* g = smem;
@@ -420,7 +419,57 @@ __global__ __launch_bounds__(NT) void k_squares_pre5_stats(const u8* __restrict_
         }
     }
     sq_accum_finish(A, acc, zm, nanf_, n, mp != nullptr, out, nsq, decisions, want_hough, hough_work, hough_out, descs[blockIdx.x].cnt,
-                    GATE ? dm : DetectMasks());
+                    GATE ? dm : DetectMasks(), wtag);
+}
+
+template <int NT, bool GATE>
+__global__ __launch_bounds__(NT) void k_squares_pre5_stats(const u8* __restrict__ src, size_t src_frame_stride,
+                                                             const SquareDesc* __restrict__ descs, u8* __restrict__ gray,
+                                                             size_t gray_frame_stride, const float* __restrict__ mean,
+                                                             const float* __restrict__ var, const u8* __restrict__ masks,
+                                                             float z_thresh, cbv_sq_stats* __restrict__ out, int nsq,
+                                                             u8* __restrict__ decisions, int want_hough,
+                                                             u32* __restrict__ hough_work, cbv_hough_result* __restrict__ hough_out,
+                                                             const u8* __restrict__ ref, const DetectMasks dm)
+{
+    __shared__ u32 acc[20];
+    __shared__ float zm[NT / 64];
+    __shared__ int nanf_[1];
+    pre5_stats_body<NT, GATE>(src, src_frame_stride, descs, gray, gray_frame_stride, mean, var, masks, z_thresh, out, nsq, decisions,
+                              want_hough, hough_work, hough_out, ref, dm, 0u, acc, zm, nanf_);
+}
+
+// every board of a pipeline in one launch: grid (CBV_MAX_SQUARES, boards, frames); a board's squares past its n_rois leave
+template <int NT>
+__global__ __launch_bounds__(NT) void k_squares_pre5_stats_mb(const BoardDev* __restrict__ tab, int s0, u32* __restrict__ hough_work)
+{
+    __shared__ u32 acc[20];
+    __shared__ float zm[NT / 64];
+    __shared__ int nanf_[1];
+    const int b = blockIdx.y;
+    const BoardDev& T = tab[b];
+    if ((int)blockIdx.x >= T.n) return;
+    const size_t s = (size_t)s0;
+    pre5_stats_body<NT, false>(T.warped + s * T.warped_stride, T.warped_stride, T.descs, T.gray + s * T.plane_total, T.plane_total,
+                               T.mean, T.sd, T.masks, T.z_thresh, T.stats + s * T.n, T.n, T.dec + s * CBV_MAX_SQUARES,
+                               T.want_hough, T.want_hough ? hough_work : nullptr, T.hough ? T.hough + s * CBV_MAX_SQUARES : nullptr,
+                               nullptr, DetectMasks(), (u32)b << MB_BOARD_SHIFT, acc, zm, nanf_);
+}
+
+int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px)
+{
+    if (max_px <= 0 || max_px > CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM) max_px = CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM;
+    const size_t lds = (size_t)((max_px + 15) & ~15) + 2 * (size_t)max_px;
+    u32* work = any_hough ? hough_work : nullptr;
+    prof_begin(ctx, CBV_K_SQUARES);
+    const dim3 grid(CBV_MAX_SQUARES, nb, batch);
+    if ((long long)CBV_MAX_SQUARES * nb * batch <= 2 * ctx->num_cus)
+        hipLaunchKernelGGL((k_squares_pre5_stats_mb<1024>), grid, dim3(1024), lds, ctx->stream, tab, s0, work);
+    else
+        hipLaunchKernelGGL((k_squares_pre5_stats_mb<256>), grid, dim3(256), lds, ctx->stream, tab, s0, work);
+    prof_end(ctx, CBV_K_SQUARES);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
 }
 
 int launch_squares_pre5_stats(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n, u8* gray,
@@ -713,10 +762,11 @@ __global__ __launch_bounds__(64) void k_scan(const SquareDesc* __restrict__ desc
 // `mirror` (may be null): the same records written to pinned host memory as well, and `over_src` (HoughCircles' overflow
 // counter) copied to `over_dst` there, so that reading results back is a wait and a host copy, not two more launches
 // (ResultMirror).
-__global__ void k_pack_results(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count, ResultMirror mir)
+__device__ __forceinline__ void pack_results_body(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count,
+                                                  ResultMirror mir, int bx)
 {
-    if (mir.over_dst && blockIdx.x == 0 && threadIdx.x == 0) *mir.over_dst = mir.over_src ? *mir.over_src : 0u;
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), sq = threadIdx.x & 63;
+    if (mir.over_dst && bx == 0 && threadIdx.x == 0) *mir.over_dst = mir.over_src ? *mir.over_src : 0u;
+    const int t = bx * 4 + (threadIdx.x >> 6), sq = threadIdx.x & 63;
     if (t >= count) return;
     const u32 fl = sq < n ? flags[(size_t)t * CBV_MAX_SQUARES + sq] : 0u;
     u64* r = (u64*)&results[t];
@@ -729,6 +779,11 @@ __global__ void k_pack_results(const u8* __restrict__ flags, int n, cbv_frame_re
             if (hm) hm[b] = m;
         }
     }
+}
+
+__global__ void k_pack_results(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count, ResultMirror mir)
+{
+    pack_results_body(flags, n, results, count, mir, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -804,8 +859,8 @@ __global__ void k_noise(const u64* __restrict__ changes, size_t stride_words, in
 
 // k_pack_results + k_noise of a run of at most four frames (one workgroup packs them all) in ONE launch: on a run of
 // one frame every launch in the chain is ~4.5 us of latency
-__global__ __launch_bounds__(256) void k_pack_noise(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count,
-                                                     cbv_noise_state* __restrict__ state, cbv_noise_result* __restrict__ out, ResultMirror mir)
+__device__ __forceinline__ void pack_noise_body(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count,
+                                                cbv_noise_state* __restrict__ state, cbv_noise_result* __restrict__ out, ResultMirror mir)
 {
     if (mir.over_dst && threadIdx.x == 0) *mir.over_dst = mir.over_src ? *mir.over_src : 0u;
     const int t = threadIdx.x >> 6, sq = threadIdx.x & 63;
@@ -825,6 +880,12 @@ __global__ __launch_bounds__(256) void k_pack_noise(const u8* __restrict__ flags
     __threadfence_block();
     __syncthreads();
     if (threadIdx.x == 0) d_noise_run(&results[0].visual_changes, sizeof(cbv_frame_result) / 8, count, state, out);
+}
+
+__global__ __launch_bounds__(256) void k_pack_noise(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count,
+                                                     cbv_noise_state* __restrict__ state, cbv_noise_result* __restrict__ out, ResultMirror mir)
+{
+    pack_noise_body(flags, n, results, count, state, out, mir);
 }
 
 int launch_noise(cbv_ctx* ctx, const u64* changes, size_t stride_words, int count, cbv_noise_state* state, cbv_noise_result* out)
@@ -851,4 +912,86 @@ int launch_scan(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, const u8* 
     if (noise_state && count > 4)
         return launch_noise(ctx, &results->visual_changes, sizeof(cbv_frame_result) / 8, count, noise_state, noise_out);
     return CBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the temporal scan, the result packing and NoiseHandler of every board of a pipeline: one launch each, the board on
+// the grid (blockIdx.y of k_scan_mb / k_pack_results_mb, blockIdx.x of k_pack_noise_mb / k_noise_mb)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_scan_mb(const BoardDev* __restrict__ tab, int s0, int count)
+{
+    const BoardDev& T = tab[blockIdx.y];
+    if ((int)blockIdx.x >= T.n) return;
+    const SquareDesc d = T.descs[blockIdx.x];
+    const int nvec = (d.w * d.h + 15) >> 4;
+    const size_t s = (size_t)s0;
+    const u8* gray = T.gray + s * T.plane_total;
+    const u8* dec = T.dec + s * CBV_MAX_SQUARES;
+    u8* flags = T.flags + s * CBV_MAX_SQUARES;
+    const u64* check = T.check ? T.check + s : nullptr;
+    if (nvec <= 512) scan_body<8, 4>(d, T.sp, gray, T.plane_total, dec, T.ref, T.state, flags, count, check);
+    else scan_body<16, 2>(d, T.sp, gray, T.plane_total, dec, T.ref, T.state, flags, count, check);
+}
+
+__device__ __forceinline__ ResultMirror board_mirror(const BoardDev& T, int s0, int mirrored)
+{
+    ResultMirror mir;
+    if (mirrored) {
+        mir.records = T.mirror + s0;
+        mir.over_src = T.over_src;
+        mir.over_dst = T.over_dst;
+    }
+    return mir;
+}
+
+__global__ __launch_bounds__(256) void k_pack_noise_mb(const BoardDev* __restrict__ tab, int s0, int count, int mirrored)
+{
+    const BoardDev& T = tab[blockIdx.x];
+    pack_noise_body(T.flags + (size_t)s0 * CBV_MAX_SQUARES, T.n, T.results + s0, count, T.noise_state, T.noise + s0,
+                    board_mirror(T, s0, mirrored));
+}
+
+__global__ void k_pack_results_mb(const BoardDev* __restrict__ tab, int s0, int count, int mirrored)
+{
+    const BoardDev& T = tab[blockIdx.y];
+    pack_results_body(T.flags + (size_t)s0 * CBV_MAX_SQUARES, T.n, T.results + s0, count, board_mirror(T, s0, mirrored), blockIdx.x);
+}
+
+__global__ void k_noise_mb(const BoardDev* __restrict__ tab, int s0, int count)
+{
+    if (threadIdx.x != 0) return;
+    const BoardDev& T = tab[blockIdx.x];
+    d_noise_run(&T.results[s0].visual_changes, sizeof(cbv_frame_result) / 8, count, T.noise_state, T.noise + s0);
+}
+
+int launch_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int mirrored)
+{
+    prof_begin(ctx, CBV_K_SCAN);
+    hipLaunchKernelGGL(k_scan_mb, dim3(CBV_MAX_SQUARES, nb), dim3(64), 0, ctx->stream, tab, s0, count);
+    if (count <= 4)
+        hipLaunchKernelGGL(k_pack_noise_mb, dim3(nb), dim3(256), 0, ctx->stream, tab, s0, count, mirrored);
+    else
+        hipLaunchKernelGGL(k_pack_results_mb, dim3((count + 3) / 4, nb), dim3(256), 0, ctx->stream, tab, s0, count, mirrored);
+    prof_end(ctx, CBV_K_SCAN);
+    CBV_HIP(ctx, hipGetLastError());
+    if (count > 4) hipLaunchKernelGGL(k_noise_mb, dim3(nb), dim3(64), 0, ctx->stream, tab, s0, count);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated)
+{
+    ScanParams sp;
+    sp.n = cfg.n_rois;
+    sp.history_size = cfg.history_size;
+    sp.min_presence = cfg.min_presence;
+    sp.change_threshold = cfg.change_threshold;
+    sp.with_model = calibrated ? 1 : 0;
+    sp.stable_table = 0;
+    for (int len = 1; len <= 7 && len <= cfg.history_size; len++)
+        for (int sum = 0; sum <= len; sum++)
+            if ((double)sum / (double)len >= cfg.min_presence) sp.stable_table |= 1ull << (len * 8 + sum);
+    sp.thr_is_int = (cfg.change_threshold == (double)(int)cfg.change_threshold && cfg.change_threshold >= 0 && cfg.change_threshold < 256) ? 1 : 0;
+    sp.thr_int = (int)cfg.change_threshold;
+    return sp;
 }

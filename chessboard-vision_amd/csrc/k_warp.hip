@@ -19,11 +19,12 @@ struct WarpM {
 // they are most of the kernel's instructions (about 100 of 190 per output pixel, in double precision): a thread works
 // them out once and samples FPT consecutive frames of the batch with them (blockIdx.z counts groups of FPT frames).
 // CALC: the byte map is worked out here from the frames' [min, max] words (NormSrc::minmax) instead of read from a table.
+// (the body of k_warp and k_warp_mb; bz = the group of frames, blockIdx.z of a single-board launch)
 template <int FPT, bool CALC>
-__global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g, WarpM M, int dw, int dh, int bw0,
-                                               int bh0, int rot180, u8* __restrict__ dst, int dst_stride,
-                                               size_t dst_frame_stride, const u8* __restrict__ norm_lut, const u32* __restrict__ minmax,
-                                               size_t mm_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+__device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, const double* __restrict__ M, int dw, int dh, int bw0,
+                                          int bh0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                          size_t dst_frame_stride, const u8* __restrict__ norm_lut, const u32* __restrict__ minmax,
+                                          size_t mm_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
 {
     __shared__ u8 lut[FPT][256];
     // the pipeline's HoughCircles worklist counter, filled by the NEXT kernel in the stream (k_squares_pre5_stats):
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g
         if (zero_word2) *zero_word2 = 0u; // the run's second-pass list, when this launch is the run's only chunk
     }
     const bool use_lut = CALC || norm_lut != nullptr;
-    const int f0 = blockIdx.z * FPT;
+    const int f0 = bz * FPT;
     const int nf = min(FPT, batch - f0);
     if (CALC) {
 #pragma unroll
@@ -52,13 +53,13 @@ __global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g
     if (dx >= dw || dy >= dh) return;
     const int bx = (dx / bw0) * bw0, x1 = dx - bx; // block origin and offset inside it
     (void)bh0;                                     // rows are evaluated independently of the block row
-    const double X0 = M.m[0] * bx + M.m[1] * dy + M.m[2];
-    const double Y0 = M.m[3] * bx + M.m[4] * dy + M.m[5];
-    const double W0 = M.m[6] * bx + M.m[7] * dy + M.m[8];
-    double W = W0 + M.m[6] * x1;
+    const double X0 = M[0] * bx + M[1] * dy + M[2];
+    const double Y0 = M[3] * bx + M[4] * dy + M[5];
+    const double W0 = M[6] * bx + M[7] * dy + M[8];
+    double W = W0 + M[6] * x1;
     W = W != 0. ? 32. / W : 0.;
-    double fX = (X0 + M.m[0] * x1) * W;
-    double fY = (Y0 + M.m[3] * x1) * W;
+    double fX = (X0 + M[0] * x1) * W;
+    double fY = (Y0 + M[3] * x1) * W;
     fX = fmax(-2147483648.0, fmin(2147483647.0, fX));
     fY = fmax(-2147483648.0, fmin(2147483647.0, fY));
     const int X = d_round_d(fX), Y = d_round_d(fY);
@@ -123,6 +124,56 @@ __global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g
         q[1] = (u8)o[1];
         q[2] = (u8)o[2];
     }
+}
+
+template <int FPT, bool CALC>
+__global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g, WarpM M, int dw, int dh, int bw0,
+                                               int bh0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                               size_t dst_frame_stride, const u8* __restrict__ norm_lut, const u32* __restrict__ minmax,
+                                               size_t mm_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    warp_body<FPT, CALC>(src, g, M.m, dw, dh, bw0, bh0, rot180, dst, dst_stride, dst_frame_stride, norm_lut, minmax, mm_stride,
+                         zero_word, zero_word2, batch, blockIdx.z);
+}
+
+// every board of a pipeline in one launch: blockIdx.z = board * nz + group of frames; the grid covers the largest board
+// and the blocks outside a smaller one leave at once (the shared frames' byte map is the same for every board)
+template <int FPT, bool CALC>
+__global__ __launch_bounds__(256) void k_warp_mb(const u8* __restrict__ src, Geom g, const BoardDev* __restrict__ tab, int nz, int s0,
+                                                  const u8* __restrict__ norm_lut, const u32* __restrict__ minmax, size_t mm_stride,
+                                                  u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
+    warp_body<FPT, CALC>(src, g, T.Minv, T.S, T.S, T.bw0, T.bh0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3,
+                         T.warped_stride, norm_lut, minmax, mm_stride, zero_word, zero_word2, batch, blockIdx.z - b * nz);
+}
+
+int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, NormSrc norm, int batch,
+                   u32* zero_word, u32* zero_word2)
+{
+    prof_begin(ctx, CBV_K_WARP);
+    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
+    dim3 grid((maxS + 63) / 64, (maxS + 3) / 4, nz * nb);
+    if (fpt == 4) {
+        if (norm.minmax)
+            hipLaunchKernelGGL((k_warp_mb<4, true>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, nullptr, norm.minmax, norm.mm_stride,
+                               zero_word, zero_word2, batch);
+        else
+            hipLaunchKernelGGL((k_warp_mb<4, false>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, norm.lut, nullptr, 0, zero_word,
+                               zero_word2, batch);
+    } else {
+        if (norm.minmax)
+            hipLaunchKernelGGL((k_warp_mb<1, true>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, nullptr, norm.minmax, norm.mm_stride,
+                               zero_word, zero_word2, batch);
+        else
+            hipLaunchKernelGGL((k_warp_mb<1, false>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, norm.lut, nullptr, 0, zero_word,
+                               zero_word2, batch);
+    }
+    prof_end(ctx, CBV_K_WARP);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
 }
 
 int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,

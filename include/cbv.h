@@ -452,6 +452,47 @@ CBV_API int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats* o
 /* HoughCircles outcome of one processed slot (cfg.use_hough): CBV_MAX_SQUARES entries, index = roi */
 CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out);
 
+/* ------------------------------------------------------------------ */
+/* several boards seen by one camera                                   */
+/* ------------------------------------------------------------------ */
+/* A configured pipeline holds up to CBV_MAX_BOARDS boards; the pipeline itself is board 0.  Extra boards share its frame
+ * ring, ingest ring, enhancement (cbv_pipeline_config::enhance, chunk, lanes, keep_enhanced, enhance_region) and lanes:
+ * every frame is uploaded and enhanced once, whatever the number of boards.  Each board has its own geometry, detector
+ * settings and temporal state (reference squares, history, ChangeDetector model, NoiseHandler, squares_to_check), and
+ * computes exactly what a pipeline configured with the parent's enhancement and the board's settings computes on the
+ * same frames.  The per-board stages of a run are one kernel launch each for all boards. */
+#define CBV_MAX_BOARDS 8
+
+/* The per-board subset of cbv_pipeline_config (same meaning, same checks). */
+typedef struct {
+    double M[9];                 /* getPerspectiveTransform of the board's quad */
+    int32_t board_size;
+    int32_t rot180;
+    int32_t n_rois;
+    cbv_roi rois[CBV_MAX_SQUARES];
+    int32_t history_size;
+    double min_presence;
+    double change_threshold;
+    double z_threshold;
+    double initial_variance;
+    int32_t use_hough;
+    cbv_hough_params hough;
+} cbv_board_config;
+
+/* Attach a board to a configured pipeline `parent` (not itself a board handle) and return its handle in *board.
+ * cbv_pipeline_run(parent, ...) then processes every attached board for those slots.  A board handle is accepted by the
+ * per-board calls, which act on that board alone: cbv_pipeline_results, _noise_results, _square_stats, _hough,
+ * _download (which = 2), _calibrate, _update_references, _set_check_squares, _reset_state.  On a board handle
+ * cbv_pipeline_run, _upload, _submit, _synth, _configure, _host_ring and _download with which 0 or 1 fail with
+ * CBV_ERR_STATE (_host_ring returns NULL); cbv_pipeline_reset_state(parent) resets board 0 only.
+ * Lifecycle: cbv_pipeline_destroy(board) detaches and frees the board (the other boards are unchanged);
+ * cbv_pipeline_destroy(parent) frees its boards too, and their handles are dead from then on.
+ * cbv_pipeline_configure(parent) fails with CBV_ERR_STATE while boards are attached: destroy them first.
+ * With enhance_region the enhanced region is the bounding rectangle of every board's warp footprint, recomputed on
+ * attach and detach.  Fails with CBV_ERR_ARG on bad arguments (those cbv_pipeline_configure rejects, or a ninth board),
+ * and leaves the parent and its other boards as they were on any failure. */
+CBV_API int cbv_pipeline_add_board(cbv_pipeline* parent, const cbv_board_config* b, cbv_pipeline** board);
+
 #ifdef __cplusplus
 }
 #endif
