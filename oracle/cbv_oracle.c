@@ -27,6 +27,12 @@
  * normalize, the bilateral accumulation), fmaf() is used here too.  The SSE
  * baseline path of the same functions differs by at most 1 LSB on rare pixels.
  *
+ * IPP caveat: an opencv-python x86 wheel is built with IPP-ICV and may route
+ * bilateralFilter, filter2D, GaussianBlur and colour conversions through IPP
+ * instead of the bodies restated here, with its own rounding.  The float64
+ * definitions in tests/ref64.py and the envelopes in tests/ref64_checks.py
+ *  bound what any correct body may return.
+ *
  * Each function cites the reference file:line whose cv2/numpy call it
  * restates.
  */

@@ -1,0 +1,361 @@
+"""Plain float64 restatements of the pixel operations the reference calls, written from the operations' definitions.
+
+This module is the second opinion next to oracle/cbv_oracle.c.  It does not import the oracle, does not follow its
+rounding order and does not use its tables: every function computes what the operation *is* (OpenCV's documented
+formula and conventions) in numpy float64.  Where a stage is continuous the function returns the unrounded float64
+result, so a checker can tell a rounding tie from an error; where the operation itself is defined on integers
+(CLAHE's LUTs, the 15-bit gray form, the 8.8 Gaussian) the integer result is available too.
+
+Images are numpy arrays: uint8 HxWx3 in BGR channel order, or HxW for one channel.
+"""
+import numpy as np
+
+# ---------------------------------------------------------------------------------------------------------------
+# borders
+# ---------------------------------------------------------------------------------------------------------------
+
+
+def reflect101_index(p, n):
+    """cv::BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba): the edge sample is not repeated.  Periodic with period
+    2(n-1); a length-1 axis maps everything to 0."""
+    p = np.asarray(p, dtype=np.int64)
+    if n == 1:
+        return np.zeros_like(p)
+    period = 2 * (n - 1)
+    q = np.mod(p, period)
+    return np.where(q > n - 1, period - q, q)
+
+
+def _pad101(img, ry, rx):
+    h, w = img.shape[:2]
+    yi = reflect101_index(np.arange(-ry, h + ry), h)
+    xi = reflect101_index(np.arange(-rx, w + rx), w)
+    return img[yi][:, xi]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# point operations
+# ---------------------------------------------------------------------------------------------------------------
+
+
+def convert_scale_abs(img, alpha, beta):
+    """cv2.convertScaleAbs: |alpha * x + beta|, before rounding and saturation to u8."""
+    return np.abs(np.asarray(img, np.float64) * alpha + beta)
+
+
+def bgr2hsv(img):
+    """cv2.COLOR_BGR2HSV, 8-bit: V = max(R,G,B); S = 255 (V - min) / V (0 when V = 0); H in degrees is
+    60 (G-B)/diff if V == R, else 120 + 60 (B-R)/diff if V == G, else 240 + 60 (R-G)/diff (0 when diff = 0),
+    +360 when negative, and is stored halved so it lies in [0, 180).  Unrounded; H is circular (180 == 0)."""
+    f = np.asarray(img, np.float64)
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    v = f.max(axis=-1)
+    diff = v - f.min(axis=-1)
+    s = np.where(v > 0, 255.0 * diff / np.where(v > 0, v, 1), 0.0)
+    dd = np.where(diff > 0, diff, 1)
+    h = np.where(v == r, 60.0 * (g - b) / dd, np.where(v == g, 120.0 + 60.0 * (b - r) / dd, 240.0 + 60.0 * (r - g) / dd))
+    h = np.where(diff > 0, h, 0.0)
+    h = np.where(h < 0, h + 360.0, h)
+    return np.stack([h / 2.0, s, v], axis=-1)
+
+
+def hsv2bgr(hsv):
+    """cv2.COLOR_HSV2BGR, 8-bit: H is in half degrees (H * 2 taken modulo 360), S and V scaled by 1/255; the six-sector
+    formula p = V(1-S), q = V(1-S f), t = V(1-S(1-f)).  Returns B, G, R times 255, unrounded."""
+    a = np.asarray(hsv, np.float64)
+    hh = np.mod(a[..., 0] * 2.0, 360.0) / 60.0
+    s, v = a[..., 1] / 255.0, a[..., 2] / 255.0
+    sec = np.floor(hh)
+    f = hh - sec
+    sec = sec.astype(np.int64) % 6
+    p, q, t = v * (1 - s), v * (1 - s * f), v * (1 - s * (1 - f))
+    r = np.choose(sec, [v, q, p, p, t, v])
+    g = np.choose(sec, [t, v, v, q, p, p])
+    b = np.choose(sec, [p, p, t, v, v, q])
+    return np.stack([b, g, r], axis=-1) * 255.0
+
+
+# OpenCV's documented RGB -> XYZ matrix (Rec. 709 primaries) and D65 white point (cvtColor docs, "RGB <-> CIE L*a*b*")
+RGB2XYZ = np.array([[0.412453, 0.357580, 0.180423],
+                    [0.212671, 0.715160, 0.072169],
+                    [0.019334, 0.119193, 0.950227]])
+D65 = np.array([0.950456, 1.0, 1.088754])
+_LAB_T = 0.008856
+
+
+def _srgb_to_linear(c):
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+
+
+def _linear_to_srgb(c):
+    return np.where(c <= 0.0031308, 12.92 * c, 1.055 * np.power(np.maximum(c, 0.0), 1 / 2.4) - 0.055)
+
+
+def bgr2lab(img):
+    """cv2.COLOR_BGR2LAB, 8-bit (sRGB input): sRGB piecewise gamma (c/12.92 up to 0.04045, ((c+0.055)/1.055)^2.4
+    above); XYZ = RGB2XYZ . rgb; X /= Xn, Z /= Zn with the D65 white; f(t) = t^(1/3) above 0.008856 and
+    7.787 t + 16/116 below; L = 116 Y^(1/3) - 16 (903.3 Y at or below 0.008856), a = 500 (f(X) - f(Y)),
+    b = 200 (f(Y) - f(Z)); stored as L * 255/100, a + 128, b + 128.  Unrounded."""
+    f = np.asarray(img, np.float64) / 255.0
+    lin = _srgb_to_linear(f[..., ::-1])                   # BGR -> RGB
+    xyz = lin @ RGB2XYZ.T / D65
+    ft = np.where(xyz > _LAB_T, np.cbrt(xyz), 7.787 * xyz + 16.0 / 116.0)
+    y = xyz[..., 1]
+    L = np.where(y > _LAB_T, 116.0 * np.cbrt(y) - 16.0, 903.3 * y)
+    a = 500.0 * (ft[..., 0] - ft[..., 1])
+    b = 200.0 * (ft[..., 1] - ft[..., 2])
+    return np.stack([L * 255.0 / 100.0, a + 128.0, b + 128.0], axis=-1)
+
+
+def lab2bgr(lab):
+    """cv2.COLOR_LAB2BGR, 8-bit: the inverse of bgr2lab.  L = L8 * 100/255, a = a8 - 128, b = b8 - 128;
+    Y = ((L+16)/116)^3 above L = 903.3 * 0.008856 and L/903.3 below; f(X) = f(Y) + a/500, f(Z) = f(Y) - b/200,
+    each inverted through the same cube / linear pieces; times the D65 white; rgb = RGB2XYZ^-1 . XYZ clipped to
+    [0, 1]; inverse sRGB gamma; times 255.  Returns B, G, R unrounded."""
+    a = np.asarray(lab, np.float64)
+    L, A, B = a[..., 0] * 100.0 / 255.0, a[..., 1] - 128.0, a[..., 2] - 128.0
+    lin_part = L <= 903.3 * _LAB_T
+    y = np.where(lin_part, L / 903.3, ((L + 16.0) / 116.0) ** 3)
+    fy = np.where(lin_part, 7.787 * y + 16.0 / 116.0, (L + 16.0) / 116.0)
+    fx, fz = fy + A / 500.0, fy - B / 200.0
+    ft_t = np.cbrt(_LAB_T)
+
+    def finv(ft):
+        return np.where(ft > ft_t, ft ** 3, (ft - 16.0 / 116.0) / 7.787)
+
+    xyz = np.stack([finv(fx), y, finv(fz)], axis=-1) * D65
+    rgb = np.clip(xyz @ np.linalg.inv(RGB2XYZ).T, 0.0, 1.0)
+    return _linear_to_srgb(rgb)[..., ::-1] * 255.0
+
+
+def bgr2gray(img):
+    """cv2.COLOR_BGR2GRAY: Y = 0.299 R + 0.587 G + 0.114 B (BT.601), unrounded."""
+    f = np.asarray(img, np.float64)
+    return 0.299 * f[..., 2] + 0.587 * f[..., 1] + 0.114 * f[..., 0]
+
+
+def gray_q15_coefficients():
+    """The integer form of BGR2GRAY on 8-bit images: each BT.601 weight rounded to 15 fractional bits, the blue one
+    then adjusted so the three sum to exactly 2^15 (white stays 255).  Returned as (cb, cg, cr)."""
+    cr, cg, cb = (int(round(c * (1 << 15))) for c in (0.299, 0.587, 0.114))
+    cb += (1 << 15) - (cr + cg + cb)
+    return cb, cg, cr
+
+
+def bgr2gray_q15(img):
+    """Integer BGR2GRAY: (cb B + cg G + cr R + 2^14) >> 15 with gray_q15_coefficients()."""
+    cb, cg, cr = gray_q15_coefficients()
+    i = np.asarray(img, np.int64)
+    return ((cb * i[..., 0] + cg * i[..., 1] + cr * i[..., 2] + (1 << 14)) >> 15).astype(np.uint8)
+
+
+def normalize_minmax(img):
+    """cv2.normalize(src, None, 0, 255, NORM_MINMAX): one min and one max over the whole array, every channel
+    together; out = (x - min) * 255 / (max - min).  A flat image (max == min) gives all 0.  Unrounded."""
+    f = np.asarray(img, np.float64)
+    lo, hi = f.min(), f.max()
+    if hi - lo <= 0:
+        return np.zeros_like(f)
+    return (f - lo) * (255.0 / (hi - lo))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# neighbourhood operations
+# ---------------------------------------------------------------------------------------------------------------
+
+
+def filter2d_3x3(img, kernel):
+    """cv2.filter2D(src, -1, kernel) with a 3x3 kernel: correlation (no flip), anchor at the centre, BORDER_REFLECT_101,
+    per channel: out(y, x) = sum_ij k[i, j] * src(y + i - 1, x + j - 1).  Unrounded and unsaturated."""
+    f = np.asarray(img, np.float64)
+    k = np.asarray(kernel, np.float64).reshape(3, 3)
+    h, w = f.shape[:2]
+    p = _pad101(f, 1, 1)
+    out = np.zeros_like(f)
+    for i in range(3):
+        for j in range(3):
+            if k[i, j] != 0:
+                out += k[i, j] * p[i:i + h, j:j + w]
+    return out
+
+
+def gaussian_blur_5x5(gray):
+    """cv2.GaussianBlur(src, (5, 5), 0): sigma 0 with ksize 5 selects the fixed binomial kernel [1 4 6 4 1] / 16,
+    applied separably with BORDER_REFLECT_101.  Unrounded (a multiple of 1/256)."""
+    f = np.asarray(gray, np.float64)
+    h, w = f.shape
+    k = np.array([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
+    p = _pad101(f, 2, 2)
+    tmp = sum(k[j] * p[:, j:j + w] for j in range(5))
+    return sum(k[i] * tmp[i:i + h] for i in range(5))
+
+
+def gaussian_blur_5x5_u8(gray):
+    """The 8-bit GaussianBlur result: the kernel is exact in 8 fractional bits, so the 8-bit path rounds the exact
+    sum once, halves upward (fixed-point +0.5 then shift)."""
+    return np.floor(gaussian_blur_5x5(gray) + 0.5).astype(np.uint8)
+
+
+def otsu_threshold(hist):
+    """cv2.threshold(THRESH_OTSU) on a 256-bin histogram: the t maximising the between-class variance
+    w0 w1 (mu0 - mu1)^2 of the classes [0, t] and [t+1, 255] (0 where a class is empty); the first t on a tie.
+    Returns (t, variance per t)."""
+    hst = np.asarray(hist, np.float64)
+    n = hst.sum()
+    p = hst / n
+    i = np.arange(256, dtype=np.float64)
+    w0 = np.cumsum(p)
+    m0 = np.cumsum(i * p)
+    mt = m0[-1]
+    w1 = 1.0 - w0
+    ok = (w0 > 0) & (w1 > 1e-15)
+    var = np.zeros(256)
+    var[ok] = (mt * w0[ok] - m0[ok]) ** 2 / (w0[ok] * w1[ok])
+    return int(np.argmax(var)), var
+
+
+def bilateral_radius(d, sigma_space):
+    """Neighbourhood radius of cv2.bilateralFilter: d/2 for d > 0, else round(1.5 sigma_space); at least 1."""
+    if sigma_space <= 0:
+        sigma_space = 1.0
+    r = d // 2 if d > 0 else int(np.floor(sigma_space * 1.5 + 0.5))
+    return max(r, 1)
+
+
+def bilateral_taps(d, sigma_space):
+    """Offsets (dy, dx) of the disc i^2 + j^2 <= r^2 that cv2.bilateralFilter sums over."""
+    r = bilateral_radius(d, sigma_space)
+    return [(i, j) for i in range(-r, r + 1) for j in range(-r, r + 1) if i * i + j * j <= r * r]
+
+
+def bilateral(img, d=9, sigma_color=75.0, sigma_space=75.0):
+    """cv2.bilateralFilter on 8UC3: taps on the disc of bilateral_radius(d, sigma_space) (non-positive sigmas become
+    1); weight exp(-(i^2+j^2) / 2 sigma_space^2) * exp(-(|dB|+|dG|+|dR|)^2 / 2 sigma_color^2) with the L1 colour
+    distance to the centre pixel; BORDER_REFLECT_101; out = sum(w I) / sum(w) per channel.  Unrounded."""
+    sc = sigma_color if sigma_color > 0 else 1.0
+    ss = sigma_space if sigma_space > 0 else 1.0
+    r = bilateral_radius(d, sigma_space)
+    f = np.asarray(img, np.float64)
+    h, w = f.shape[:2]
+    p = _pad101(f, r, r)
+    num = np.zeros_like(f)
+    den = np.zeros((h, w))
+    for i, j in bilateral_taps(d, sigma_space):
+        q = p[r + i:r + i + h, r + j:r + j + w]
+        dist = np.abs(q - f).sum(axis=-1)
+        wt = np.exp(-(i * i + j * j) / (2 * ss * ss)) * np.exp(-dist * dist / (2 * sc * sc))
+        num += wt[..., None] * q
+        den += wt
+    return num / den[..., None]
+
+
+def clahe_tiling(h, w, tiles):
+    """(tile_h, tile_w, padded_h, padded_w) of cv2.CLAHE with tileGridSize = tiles = (tiles_x, tiles_y): when the
+    image does not divide into the grid in *both* directions it is padded (BORDER_REFLECT_101, bottom and right) by
+    tiles - (size % tiles) in each direction (a whole extra tile row/column where that axis did divide)."""
+    tx, ty = tiles
+    if w % tx == 0 and h % ty == 0:
+        return h // ty, w // tx, h, w
+    eh, ew = h + ty - h % ty, w + tx - w % tx
+    return eh // ty, ew // tx, eh, ew
+
+
+def clahe_clip(clip_limit, area):
+    """Per-bin clip count: max(int(clip_limit * area / 256), 1) when clip_limit > 0; 0 (no clipping) otherwise."""
+    return max(int(clip_limit * area / 256), 1) if clip_limit > 0 else 0
+
+
+def clahe_luts(gray, clip_limit=3.0, tiles=(8, 8)):
+    """The per-tile lookup tables of cv2.CLAHE: 256-bin histogram of each tile of the REFLECT_101-padded image; bins
+    above the clip count are cut and the excess redistributed, batch = excess // 256 to every bin, then the residual
+    one count each to bins 0, step, 2 step, ... with step = max(256 // residual, 1); LUT = sat(round(cumsum * scale))
+    with scale = 255 / area held as a float32 and the product taken in float32 (which decides exact .5 ties),
+    rounded half to even.  Returns (tiles_y * tiles_x, 256) uint8 in row-major tile order."""
+    g = np.asarray(gray)
+    h, w = g.shape
+    tx, ty = tiles
+    th, tw, eh, ew = clahe_tiling(h, w, tiles)
+    yi = reflect101_index(np.arange(eh), h)
+    xi = reflect101_index(np.arange(ew), w)
+    ext = g[yi][:, xi]
+    area = th * tw
+    clip = clahe_clip(clip_limit, area)
+    scale = np.float32(255.0 / area)
+    luts = np.empty((ty * tx, 256), np.uint8)
+    for y in range(ty):
+        for x in range(tx):
+            hist = np.bincount(ext[y * th:(y + 1) * th, x * tw:(x + 1) * tw].ravel(), minlength=256).astype(np.int64)
+            if clip > 0:
+                excess = int(np.maximum(hist - clip, 0).sum())
+                hist = np.minimum(hist, clip)
+                batch, residual = divmod(excess, 256)
+                hist += batch
+                if residual:
+                    step = max(256 // residual, 1)
+                    idx = np.arange(0, 256, step)[:residual]
+                    hist[idx] += 1
+            cs = np.cumsum(hist)
+            luts[y * tx + x] = np.clip(np.rint(cs.astype(np.float32) * scale), 0, 255).astype(np.uint8)
+    return luts
+
+
+def clahe(gray, clip_limit=3.0, tiles=(8, 8), luts=None):
+    """cv2.CLAHE.apply on 8-bit gray: each pixel's value v is looked up in the four nearest tile LUTs and blended
+    bilinearly at tile coordinates (x / tile_w - 0.5, y / tile_h - 0.5), the neighbour indices clamped to the grid.
+    Unrounded."""
+    g = np.asarray(gray)
+    h, w = g.shape
+    tx, ty = tiles
+    th, tw, _, _ = clahe_tiling(h, w, tiles)
+    if luts is None:
+        luts = clahe_luts(g, clip_limit, tiles)
+    L = luts.astype(np.float64).reshape(ty, tx, 256)
+
+    def axis(n, t, nt):
+        c = np.arange(n) / t - 0.5
+        i1 = np.floor(c).astype(np.int64)
+        frac = c - i1
+        return np.clip(i1, 0, nt - 1), np.clip(i1 + 1, 0, nt - 1), frac
+
+    y1, y2, fy = axis(h, th, ty)
+    x1, x2, fx = axis(w, tw, tx)
+    v = g.astype(np.int64)
+    Y1, Y2, X1, X2 = y1[:, None], y2[:, None], x1[None, :], x2[None, :]
+    FX, FY = fx[None, :], fy[:, None]
+    top = L[Y1, X1, v] * (1 - FX) + L[Y1, X2, v] * FX
+    bot = L[Y2, X1, v] * (1 - FX) + L[Y2, X2, v] * FX
+    return top * (1 - FY) + bot * FY
+
+
+def perspective_source_coords(M, dsize):
+    """Source coordinates of every destination pixel of cv2.warpPerspective(src, M, dsize): (X, Y) = the projective
+    map of (x, y) through M^-1 (M maps source to destination), in float64.  W == 0 maps to (0, 0)."""
+    dw, dh = dsize
+    Mi = np.linalg.inv(np.asarray(M, np.float64))
+    yy, xx = np.mgrid[:dh, :dw].astype(np.float64)
+    W = Mi[2, 0] * xx + Mi[2, 1] * yy + Mi[2, 2]
+    Wi = np.where(W != 0, 1.0 / np.where(W != 0, W, 1.0), 0.0)
+    X = (Mi[0, 0] * xx + Mi[0, 1] * yy + Mi[0, 2]) * Wi
+    Y = (Mi[1, 0] * xx + Mi[1, 1] * yy + Mi[1, 2]) * Wi
+    return X, Y
+
+
+def warp_perspective(img, M, dsize):
+    """cv2.warpPerspective(src, M, dsize) with INTER_LINEAR and BORDER_CONSTANT 0: bilinear interpolation at the exact
+    float64 source point, samples outside the image counting as 0.  Returns (out unrounded, X, Y)."""
+    f = np.asarray(img, np.float64)
+    h, w = f.shape[:2]
+    X, Y = perspective_source_coords(M, dsize)
+    Xc = np.clip(X, -2.0, w + 1.0)          # beyond one pixel outside every tap is 0 anyway
+    Yc = np.clip(Y, -2.0, h + 1.0)
+    x0, y0 = np.floor(Xc).astype(np.int64), np.floor(Yc).astype(np.int64)
+    ax, ay = (Xc - x0)[..., None], (Yc - y0)[..., None]
+
+    def tap(yy, xx):
+        inside = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+        v = f[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)]
+        return np.where(inside[..., None], v, 0.0)
+
+    out = (tap(y0, x0) * (1 - ax) * (1 - ay) + tap(y0, x0 + 1) * ax * (1 - ay)
+           + tap(y0 + 1, x0) * (1 - ax) * ay + tap(y0 + 1, x0 + 1) * ax * ay)
+    return out, X, Y
