@@ -1,5 +1,5 @@
 // C-ABI of libcbv_hip.so (include/cbv.h): context, host-buffer stage entry
-// points, per-square detector state and the device-resident batched pipeline.
+// points and per-square detector state (the device-resident pipeline: cbv_pipeline.cpp).
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -321,26 +321,10 @@ static int check_img(cbv_ctx* ctx, const void* p, int w, int h, int stride, int 
     return CBV_OK;
 }
 
-static Geom tight_geom(int w, int h)
-{
-    Geom g;
-    g.w = w;
-    g.h = h;
-    g.stride = w * 3;
-    g.frame_stride = ((size_t)w * 3 * h + 255) & ~(size_t)255;
-    return g;
-}
-
-#define RC(x)             \
-    do {                  \
-        int rc__ = (x);   \
-        if (rc__) return rc__; \
-    } while (0)
-
 // rows between a host image (any row stride) and a tight device image, asynchronous.  Tight host rows travel as ONE
 // linear copy: the 2-D entry point takes a slower path even when width == pitch (a 1080p frame to pageable memory:
 // 365 us against 119 us, tools/ubench_copy.hip).
-static int rows_h2d(cbv_ctx* ctx, void* dst, const u8* src, int stride, int wbytes, int h)
+int rows_h2d(cbv_ctx* ctx, void* dst, const u8* src, int stride, int wbytes, int h)
 {
     if (stride == wbytes) CBV_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)wbytes * h, hipMemcpyHostToDevice, ctx->stream));
     else CBV_HIP(ctx, hipMemcpy2DAsync(dst, wbytes, src, stride, wbytes, h, hipMemcpyHostToDevice, ctx->stream));
@@ -369,16 +353,6 @@ static int download(cbv_ctx* ctx, const void* src, u8* dst, int wbytes, int h, i
     return CBV_OK;
 }
 
-struct SmallLayout {
-    u32* aux;
-    u8* luts;
-    u32* packed; // CLAHE corner words (k_clahe_lut -> k_clahe_apply), null when not reserved
-    u8* norm_lut;
-    // The buffer's tag says which (tiles, batch) layout of `aux` is known to be as k_reset_aux leaves it: enhance_dev's own
-    // kernels restore that state as they go (launch_clahe_lut, self_clean), so a pass over the same layout needs no reset
-    // launch.  Everything else that writes `aux` leaves the tag 0 (aux_dirty).
-    DevBuf* owner;
-};
 static unsigned long long aux_clean_tag(int tiles, int batch) { return (1ull << 63) | ((unsigned long long)tiles << 32) | (unsigned)batch; }
 static int aux_reset(cbv_ctx* ctx, const SmallLayout& S, int tiles, int batch) // reset for a stand-alone stage
 {
@@ -387,7 +361,7 @@ static int aux_reset(cbv_ctx* ctx, const SmallLayout& S, int tiles, int batch) /
 }
 
 // tiles_x / tiles_y > 0 also reserve the packed CLAHE corner words ([batch][tiles_y + 1][tiles_x + 1][256] u32)
-static int small_layout(cbv_ctx* ctx, DevBuf* buf, int tiles, int batch, SmallLayout* L, int tiles_x = 0, int tiles_y = 0)
+int small_layout(cbv_ctx* ctx, DevBuf* buf, int tiles, int batch, SmallLayout* L, int tiles_x, int tiles_y)
 {
     size_t aux_b = aux_words(tiles) * 4 * batch;
     aux_b = (aux_b + 255) & ~(size_t)255;
@@ -617,8 +591,8 @@ static PxRect px_dilate(PxRect r, int d, Geom g)
 // `region` (with a third buffer C, and only when the caller folds normalize into its own gather): the consumer samples
 // just these pixels of the enhanced frame; see "Region-limited enhancement" in cbv_internal.h.
 // `norm`: where the consumer of a fold_norm result finds cv2.normalize's byte map (NormSrc).
-static int enhance_dev(cbv_ctx* ctx, const u8* src, u8* A, u8* B, Geom g, const cbv_enhance_params* P, SmallLayout S,
-                       int batch, bool fold_norm, u8** result, NormSrc* norm, const PxRect* region = nullptr, u8* C = nullptr)
+int enhance_dev(cbv_ctx* ctx, const u8* src, u8* A, u8* B, Geom g, const cbv_enhance_params* P, SmallLayout S, int batch,
+                bool fold_norm, u8** result, NormSrc* norm, const PxRect* region, u8* C)
 {
     ClaheGeom cg = clahe_geom(g.w, g.h, P->clahe_clip_limit, P->tiles_x, P->tiles_y);
     int tiles = P->tiles_x * P->tiles_y;
@@ -682,7 +656,7 @@ static int enhance_dev(cbv_ctx* ctx, const u8* src, u8* A, u8* B, Geom g, const 
 // convex while W > 0 on it, so its four corners bound it), + 3 px for the 1/32-px rounding and the bilinear taps, clipped
 // to the frame.  False when the map is degenerate on the rectangle or the footprint is empty: callers then take the
 // whole frame.
-static bool warp_footprint(const double* Minv, int dw, int dh, int w, int h, PxRect* out)
+bool warp_footprint(const double* Minv, int dw, int dh, int w, int h, PxRect* out)
 {
     double lo[2] = {1e30, 1e30}, hi[2] = {-1e30, -1e30};
     for (int k = 0; k < 4; k++) {
@@ -706,7 +680,7 @@ static bool warp_footprint(const double* Minv, int dw, int dh, int w, int h, PxR
     return true;
 }
 
-static int check_params(cbv_ctx* ctx, const cbv_enhance_params* P)
+int check_params(cbv_ctx* ctx, const cbv_enhance_params* P)
 {
     if (!P) return cbv_fail(ctx, CBV_ERR_ARG, "enhance params are null");
     if (P->tiles_x <= 0 || P->tiles_y <= 0 || P->tiles_x > 64 || P->tiles_y > 64) return cbv_fail(ctx, CBV_ERR_ARG, "bad CLAHE tile grid");
@@ -831,6 +805,25 @@ static int squares_set_coef(cbv_squares* s, int blur_k)
     return CBV_OK;
 }
 
+size_t square_table(const int* ws, const int* hs, int n, std::vector<SquareDesc>* descs, std::vector<u8>* masks)
+{
+    descs->assign(n, SquareDesc());
+    size_t off = 0;
+    for (int i = 0; i < n; i++) {
+        SquareDesc& d = (*descs)[i];
+        d.w = ws[i];
+        d.h = hs[i];
+        d.plane_off = d.mask_off = (int)off;
+        off += ((size_t)ws[i] * hs[i] + 15) & ~(size_t)15;
+    }
+    masks->assign(off, 0);
+    for (SquareDesc& d : *descs) {
+        build_piece_mask(d.w, d.h, masks->data() + d.mask_off);
+        square_region_counts(masks->data() + d.mask_off, d.w * d.h, d.cnt);
+    }
+    return off;
+}
+
 // (re)build geometry-dependent tables when the set of square shapes changes
 static int squares_set_geometry(cbv_squares* s, const int* ws, const int* hs, int n)
 {
@@ -841,23 +834,11 @@ static int squares_set_geometry(cbv_squares* s, const int* ws, const int* hs, in
     for (int i = 0; i < n; i++) // validate before any state changes: a rejected load leaves the set as it was
         if (ws[i] <= 0 || hs[i] <= 0 || ws[i] > CBV_MAX_SQUARE_DIM || hs[i] > CBV_MAX_SQUARE_DIM)
             return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "square %d is %dx%d; supported up to %dx%d", i, ws[i], hs[i], CBV_MAX_SQUARE_DIM, CBV_MAX_SQUARE_DIM);
-    s->descs.assign(n, SquareDesc());
-    size_t off = 0;
-    for (int i = 0; i < n; i++) {
-        s->descs[i].w = ws[i];
-        s->descs[i].h = hs[i];
-        s->descs[i].plane_off = (int)off;
-        s->descs[i].mask_off = (int)off;
-        off += ((size_t)ws[i] * hs[i] + 15) & ~(size_t)15;
-    }
+    std::vector<u8> masks;
+    const size_t off = square_table(ws, hs, n, &s->descs, &masks);
     s->n = n;
     s->plane_total = off;
     s->has_ref = s->has_model = false;
-    std::vector<u8> masks(off, 0);
-    for (int i = 0; i < n; i++) {
-        build_piece_mask(ws[i], hs[i], masks.data() + s->descs[i].mask_off);
-        square_region_counts(masks.data() + s->descs[i].mask_off, ws[i] * hs[i], s->descs[i].cnt);
-    }
     RC(dev_ensure(ctx, &s->d_masks, off));
     RC(dev_ensure(ctx, &s->d_gray, off));
     RC(dev_ensure(ctx, &s->d_ref, off));
@@ -1021,7 +1002,7 @@ extern "C" int cbv_squares_stats(cbv_squares* s, int use_ref, int use_model, dou
 }
 
 // the checks of hough_cfg that need no square geometry (entry points run them before they change any state)
-static int hough_params_check(cbv_ctx* ctx, const cbv_hough_params* prm)
+int hough_params_check(cbv_ctx* ctx, const cbv_hough_params* prm)
 {
     if (!prm || !(prm->dp > 0) || prm->param1 < 0 || prm->param2 < 0 || !(prm->max_radius_ratio >= 0) || !(prm->min_radius_ratio >= 0))
         return cbv_fail(ctx, CBV_ERR_ARG, "HoughCircles parameters are invalid");
@@ -1031,7 +1012,7 @@ static int hough_params_check(cbv_ctx* ctx, const cbv_hough_params* prm)
     return CBV_OK;
 }
 
-static int hough_cfg(cbv_ctx* ctx, const cbv_hough_params* prm, const std::vector<SquareDesc>& descs, HoughCfg* hc)
+int hough_cfg(cbv_ctx* ctx, const cbv_hough_params* prm, const std::vector<SquareDesc>& descs, HoughCfg* hc)
 {
     RC(hough_params_check(ctx, prm));
     memset(hc, 0, sizeof(*hc));
@@ -1474,965 +1455,6 @@ extern "C" int cbv_squares_geometry(cbv_squares* s, int index, int* w, int* h)
     return CBV_OK;
 }
 
-// ---------------------------------------------------------------------------
-// device-resident batched pipeline
-// ---------------------------------------------------------------------------
-struct cbv_pipeline {
-    cbv_ctx* ctx = nullptr;
-    int w = 0, h = 0, max_frames = 0;
-    Geom g;
-    cbv_pipeline_config cfg;
-    bool configured = false;
-    int chunk = 8;
-    double Minv[9];
-    u8* frames = nullptr;
-    // Lanes: chunk c runs on lane c % n_lanes, each lane with its own HIP stream and scratch, so a
-    // VALU-bound bilateral launch of one chunk overlaps the memory-latency-bound kernels of another.
-    enum { MAX_LANES = 4 };
-    int n_lanes = 1;
-    hipStream_t lane_stream[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t lane_done[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t start_ev = nullptr;
-    u8* A[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    u8* B[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    u8* C[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr}; // third scratch frame set: region-limited enhancement only
-    bool use_region = false;                                  // cfg.enhance_region, keep_enhanced == 0, a usable footprint
-    PxRect region = {0, 0, 0, 0};                             // source pixels the warp samples (+ margin), clipped
-    DevBuf lane_small[MAX_LANES];
-    DevBuf lane_work[MAX_LANES]; // HoughCircles worklist of the lane's current chunk: count, then frame << 8 | square
-    u8* enhanced = nullptr; // [max_frames] when keep_enhanced
-    u8* warped = nullptr;   // [max_frames][S][S][3]
-    size_t warped_stride = 0;
-    DevBuf d_descs, d_masks, d_gray, d_stats, d_ref, d_state, d_results, d_flags, d_dec, d_coef, d_synth, d_mean, d_var, d_noise, d_noise_state, d_hough, d_check, d_hough_over;
-    bool has_check = false; // squares_to_check masks were set
-    HoughCfg hough_cfg;
-    bool calibrated = false;
-    std::vector<SquareDesc> descs;
-    size_t plane_total = 0;
-    // ingest: pinned host mirror of the frame ring, filled by the capture side and copied on its own stream
-    u8* host_ring = nullptr;
-    u8* h_stage = nullptr; // pinned mirror of d_results ([max_frames] records, then the HoughCircles overflow word): written by
-                           // the last kernel of a SHORT run (ResultMirror), by a copy otherwise; read by cbv_pipeline_results
-    size_t h_stage_bytes = 0;
-    std::vector<u8> slot_mirrored; // per slot: the mirror holds the slot's newest record (once its run has finished)
-    hipStream_t copy_stream = nullptr;
-    struct CopyRec {
-        int s0, cnt;
-        hipEvent_t ev;
-        bool pending;
-    };
-    std::vector<CopyRec> copies;
-    // The temporal scan (+ NoiseHandler) of a run goes to its own stream behind the lanes' events, so the next run's
-    // enhancement of OTHER slots overlaps it; scans of successive runs stay ordered on that stream.  (Runs of one or
-    // two frames keep their scan on the caller's stream, after waiting for every run in flight: see cbv_pipeline_run.)
-    hipStream_t scan_stream = nullptr;
-    hipEvent_t main_done = nullptr;
-    // Every run that may still be executing: its slot range and two events on the (in-order) scan stream,
-    // `lanes_ev` = all lanes have read the input frames and written the per-slot buffers, `scan_ev` = the scan has
-    // read them.  A later run (or ingest copy) that touches overlapping slots waits on the NEWEST overlapping
-    // record, which covers the older ones because the scan stream is in order.  Records are recycled once their
-    // scan event has completed.
-    struct RunRec {
-        int s0, cnt;
-        unsigned long long seq;
-        hipEvent_t lanes_ev, scan_ev;
-        bool live;
-        bool one_event; // a run of a frame or two, all on the caller's stream: only scan_ev is recorded (an event between two
-                        // kernels is a ~5 us bubble in a 150 us chain), and it stands for lanes_ev too
-        DevBuf retry; // HoughCircles second-pass list of this run (HoughCfg::retry), frames numbered from the run's slot0
-    };
-    std::vector<RunRec> runs;
-    unsigned long long run_seq = 0;         // sequence number of the newest run
-    unsigned long long joined_seq = 0;      // runs up to this one are ordered before later work on `joined_stream`
-    hipStream_t joined_stream = nullptr;
-    int max_px = 0; // pixels of the largest square
-    bool keep_enhanced = false;
-    // several boards per frame (cbv_pipeline_add_board): a board handle is a pipeline object that holds only the per-board
-    // part (configure's squares part: warped frames, planes, temporal state, results) and `parent`; the parent lists its
-    // boards and keeps the device table the multi-board launches read (BoardDev, board 0 = the parent itself)
-    cbv_pipeline* parent = nullptr;
-    std::vector<cbv_pipeline*> boards;
-    DevBuf d_boards;
-    bool mb_any_hough = false;
-    size_t mb_hough_lds[2] = {0, 0};
-    int mb_max_px = 0, mb_max_S = 0;
-};
-
-// the HoughCircles overflow word of the pinned result mirror (behind its max_frames records)
-static u32* pipeline_over_word(cbv_pipeline* p) { return (u32*)(p->h_stage + ((sizeof(cbv_frame_result) * (size_t)p->max_frames + 7) & ~(size_t)7)); }
-
-static bool ranges_overlap(int a0, int an, int b0, int bn) { return a0 < b0 + bn && b0 < a0 + an; }
-
-static void retire_runs(cbv_pipeline* p)
-{
-    for (auto& r : p->runs)
-        if (r.live && hipEventQuery(r.scan_ev) == hipSuccess) r.live = false;
-}
-
-// newest record that is still in flight, not yet ordered before the context's stream, and overlaps the slots
-// (cnt <= 0: any slots)
-static cbv_pipeline::RunRec* newest_unjoined(cbv_pipeline* p, int s0, int cnt)
-{
-    if (p->joined_stream != p->ctx->stream) { // the caller switched streams: nothing is ordered before the new one
-        p->joined_stream = p->ctx->stream;
-        p->joined_seq = 0;
-    }
-    cbv_pipeline::RunRec* best = nullptr;
-    for (auto& r : p->runs)
-        if (r.live && r.seq > p->joined_seq && (cnt <= 0 || ranges_overlap(s0, cnt, r.s0, r.cnt)) && (!best || r.seq > best->seq)) best = &r;
-    return best;
-}
-
-// make the context's stream wait for every run that is still in flight (lanes and scans)
-static int join_scan(cbv_pipeline* p)
-{
-    if (p->parent) p = p->parent; // a board's buffers are written by its parent's runs
-    cbv_ctx* ctx = p->ctx;
-    if (cbv_pipeline::RunRec* r = newest_unjoined(p, 0, 0)) {
-        CBV_HIP(ctx, hipStreamWaitEvent(ctx->stream, r->scan_ev, 0));
-        p->joined_seq = r->seq;
-    }
-    return CBV_OK;
-}
-
-// make the context's stream wait for the runs in flight that touch these slots (older scans of the same slots
-// may still be queued: the newest overlapping record covers them)
-static int join_slots(cbv_pipeline* p, int s0, int cnt)
-{
-    if (p->parent) p = p->parent;
-    cbv_ctx* ctx = p->ctx;
-    retire_runs(p);
-    if (cbv_pipeline::RunRec* r = newest_unjoined(p, s0, cnt)) {
-        CBV_HIP(ctx, hipStreamWaitEvent(ctx->stream, r->scan_ev, 0));
-        // everything up to r is ordered now; records between joined_seq and r.seq that do not overlap are too
-        p->joined_seq = std::max(p->joined_seq, r->seq);
-    }
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_create(cbv_ctx* ctx, int w, int h, int max_frames, cbv_pipeline** out)
-{
-    if (!ctx || !out || w <= 0 || h <= 0 || max_frames <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_create: bad arguments");
-    CBV_ENTER(ctx);
-    cbv_pipeline* p = new cbv_pipeline();
-    p->ctx = ctx;
-    p->w = w;
-    p->h = h;
-    p->max_frames = max_frames;
-    p->g = tight_geom(w, h);
-    hipError_t e = hipMalloc((void**)&p->frames, p->g.frame_stride * max_frames + 256);
-    if (e != hipSuccess) {
-        const size_t want = p->g.frame_stride * max_frames;
-        delete p;
-        return cbv_fail(ctx, CBV_ERR_HIP, "hipMalloc of %zu bytes for the frame ring failed: %s", want, hipGetErrorString(e));
-    }
-    *out = p;
-    return CBV_OK;
-}
-
-static int pipeline_upload_boards(cbv_pipeline* p);
-static int pipeline_update_region(cbv_pipeline* p);
-static void board_free(cbv_pipeline* b);
-
-extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
-{
-    if (!p) return;
-    std::lock_guard<std::recursive_mutex> lock(p->ctx->mu);
-    (void)hipSetDevice(p->ctx->device);
-    if (p->parent || !p->boards.empty()) (void)join_scan(p); // runs of the parent in flight (lanes, scan) write every board
-    (void)hipStreamSynchronize(p->ctx->stream);
-    if (cbv_pipeline* par = p->parent) { // detach: the other boards and the parent go on as they were
-        par->boards.erase(std::find(par->boards.begin(), par->boards.end(), p));
-        if (!par->boards.empty()) (void)pipeline_upload_boards(par);
-        (void)pipeline_update_region(par);
-        board_free(p);
-        return;
-    }
-    for (cbv_pipeline* b : p->boards) board_free(b);
-    p->boards.clear();
-    dev_free(&p->d_boards);
-    for (int l = 0; l < cbv_pipeline::MAX_LANES; l++) {
-        if (p->lane_stream[l]) (void)hipStreamSynchronize(p->lane_stream[l]);
-        if (p->A[l]) (void)hipFree(p->A[l]);
-        if (p->B[l]) (void)hipFree(p->B[l]);
-        if (p->C[l]) (void)hipFree(p->C[l]);
-        dev_free(&p->lane_small[l]);
-        dev_free(&p->lane_work[l]);
-        if (p->lane_done[l]) (void)hipEventDestroy(p->lane_done[l]);
-    }
-    if (p->start_ev) (void)hipEventDestroy(p->start_ev);
-    if (p->scan_stream) (void)hipStreamSynchronize(p->scan_stream); // (the worker streams belong to the context)
-    for (auto& r : p->runs) {
-        (void)hipEventDestroy(r.lanes_ev);
-        (void)hipEventDestroy(r.scan_ev);
-        dev_free(&r.retry);
-    }
-    if (p->main_done) (void)hipEventDestroy(p->main_done);
-    if (p->copy_stream) (void)hipStreamSynchronize(p->copy_stream);
-    for (auto& c : p->copies) (void)hipEventDestroy(c.ev);
-    if (p->host_ring) (void)hipHostFree(p->host_ring);
-    if (p->h_stage) (void)hipHostFree(p->h_stage);
-    if (p->frames) (void)hipFree(p->frames);
-    if (p->enhanced) (void)hipFree(p->enhanced);
-    if (p->warped) (void)hipFree(p->warped);
-    DevBuf* bufs[] = {&p->d_descs, &p->d_masks, &p->d_gray, &p->d_stats, &p->d_ref, &p->d_state, &p->d_results, &p->d_flags, &p->d_dec, &p->d_noise, &p->d_noise_state, &p->d_coef, &p->d_synth, &p->d_mean, &p->d_var, &p->d_hough, &p->d_check, &p->d_hough_over};
-    for (auto b : bufs) dev_free(b);
-    delete p;
-}
-
-extern "C" void* cbv_pipeline_frames_dev(cbv_pipeline* p) { return p ? p->frames : nullptr; }
-
-// the per-board checks of cbv_pipeline_configure (cbv_pipeline_add_board makes the same)
-static int check_board_cfg(cbv_ctx* ctx, const cbv_pipeline_config* cfg)
-{
-    if (cfg->n_rois <= 0 || cfg->n_rois > CBV_MAX_SQUARES || cfg->board_size <= 0 || cfg->board_size > 4096)
-        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_configure: bad board/roi configuration");
-    if (cfg->history_size < 1 || cfg->history_size > 7) return cbv_fail(ctx, CBV_ERR_ARG, "history_size must be in 1..7");
-    for (int i = 0; i < cfg->n_rois; i++) {
-        const cbv_roi& r = cfg->rois[i];
-        if (r.w <= 0 || r.h <= 0 || r.w > CBV_MAX_SQUARE_DIM || r.h > CBV_MAX_SQUARE_DIM || r.x0 < 0 || r.y0 < 0 ||
-            r.x0 + r.w > cfg->board_size || r.y0 + r.h > cfg->board_size)
-            return cbv_fail(ctx, CBV_ERR_ARG, "roi %d is invalid for a %dx%d board", i, cfg->board_size, cfg->board_size);
-    }
-    return CBV_OK;
-}
-
-// the per-board part of cbv_pipeline_configure: warped frames, square descriptors and planes, temporal state, results
-// (p->cfg, Minv and warped_stride are set)
-static int pipeline_setup_board(cbv_pipeline* p, const cbv_pipeline_config* cfg)
-{
-    cbv_ctx* ctx = p->ctx;
-    const int S = cfg->board_size;
-    if (p->warped) (void)hipFree(p->warped);
-    p->warped = nullptr;
-    CBV_HIP(ctx, hipMalloc((void**)&p->warped, p->warped_stride * p->max_frames));
-    // squares
-    const int n = cfg->n_rois;
-    p->descs.assign(n, SquareDesc());
-    size_t off = 0;
-    for (int i = 0; i < n; i++) {
-        const cbv_roi& r = cfg->rois[i];
-        SquareDesc& d = p->descs[i];
-        d.w = r.w;
-        d.h = r.h;
-        d.cn = 3;
-        d.stride = S * 3;
-        d.src_off = r.y0 * S * 3 + r.x0 * 3;
-        d.plane_off = (int)off;
-        d.mask_off = (int)off;
-        off += ((size_t)r.w * r.h + 15) & ~(size_t)15;
-    }
-    p->plane_total = off;
-    p->max_px = 0;
-    for (int i = 0; i < n; i++) p->max_px = std::max(p->max_px, p->descs[i].w * p->descs[i].h);
-    std::vector<u8> masks(off, 0);
-    for (int i = 0; i < n; i++) {
-        build_piece_mask(p->descs[i].w, p->descs[i].h, masks.data() + p->descs[i].mask_off);
-        square_region_counts(masks.data() + p->descs[i].mask_off, p->descs[i].w * p->descs[i].h, p->descs[i].cnt);
-    }
-    RC(dev_ensure(ctx, &p->d_descs, sizeof(SquareDesc) * n));
-    RC(dev_ensure(ctx, &p->d_masks, off));
-    RC(dev_ensure(ctx, &p->d_gray, off * p->max_frames));
-    RC(dev_ensure(ctx, &p->d_stats, sizeof(cbv_sq_stats) * n * p->max_frames));
-    RC(dev_ensure(ctx, &p->d_ref, off));
-    RC(dev_ensure(ctx, &p->d_mean, off * 4));
-    RC(dev_ensure(ctx, &p->d_var, off * 8)); // variance plane, then its square root
-    p->calibrated = false;
-    RC(dev_ensure(ctx, &p->d_state, sizeof(ScanState) * n));
-    RC(dev_ensure(ctx, &p->d_results, sizeof(cbv_frame_result) * p->max_frames));
-    {
-        const size_t want = sizeof(cbv_frame_result) * (size_t)p->max_frames + 16;
-        if (p->h_stage_bytes < want) {
-            if (p->h_stage) (void)hipHostFree(p->h_stage);
-            p->h_stage = nullptr;
-            p->h_stage_bytes = 0;
-            CBV_HIP(ctx, hipHostMalloc((void**)&p->h_stage, want, hipHostMallocDefault));
-            p->h_stage_bytes = want;
-        }
-        memset(p->h_stage, 0, p->h_stage_bytes);
-        p->slot_mirrored.assign((size_t)p->max_frames, 0);
-    }
-    RC(dev_ensure(ctx, &p->d_flags, (size_t)CBV_MAX_SQUARES * p->max_frames));
-    RC(dev_ensure(ctx, &p->d_dec, (size_t)CBV_MAX_SQUARES * p->max_frames));
-    if (cfg->use_hough) {
-        RC(hough_cfg(ctx, &cfg->hough, p->descs, &p->hough_cfg));
-        RC(dev_ensure(ctx, &p->d_hough, sizeof(cbv_hough_result) * CBV_MAX_SQUARES * p->max_frames));
-        RC(dev_ensure(ctx, &p->d_hough_over, 256));
-        CBV_HIP(ctx, hipMemset(p->d_hough_over.p, 0, 256));
-        p->hough_cfg.overflow_count = (u32*)p->d_hough_over.p;
-    }
-    RC(dev_ensure(ctx, &p->d_noise, sizeof(cbv_noise_result) * p->max_frames));
-    RC(dev_ensure(ctx, &p->d_noise_state, sizeof(cbv_noise_state)));
-    RC(dev_ensure(ctx, &p->d_check, sizeof(u64) * p->max_frames));
-    CBV_HIP(ctx, hipMemset(p->d_check.p, 0, sizeof(u64) * p->max_frames));
-    p->has_check = false;
-    CBV_HIP(ctx, hipMemset(p->d_noise_state.p, 0, sizeof(cbv_noise_state)));
-    int coef[32] = {0};
-    build_gaussian_q8(5, coef);
-    RC(dev_ensure(ctx, &p->d_coef, sizeof(coef)));
-    CBV_HIP(ctx, hipMemcpy(p->d_coef.p, coef, sizeof(coef), hipMemcpyHostToDevice));
-    CBV_HIP(ctx, hipMemcpy(p->d_descs.p, p->descs.data(), sizeof(SquareDesc) * n, hipMemcpyHostToDevice));
-    CBV_HIP(ctx, hipMemcpy(p->d_masks.p, masks.data(), off, hipMemcpyHostToDevice));
-    CBV_HIP(ctx, hipMemset(p->d_state.p, 0, sizeof(ScanState) * n));
-    // plane padding (planes are rounded to 16 B) must read as zero in every frame: k_scan compares whole vectors
-    CBV_HIP(ctx, hipMemset(p->d_gray.p, 0, off * p->max_frames));
-    CBV_HIP(ctx, hipMemset(p->d_ref.p, 0, off));
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* cfg)
-{
-    if (!p || !cfg) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: a board handle is configured by cbv_pipeline_add_board");
-    if (!p->boards.empty()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: boards are attached (destroy them first)");
-    RC(check_board_cfg(ctx, cfg));
-    RC(check_params(ctx, &cfg->enhance));
-    // every argument check that needs no state is done; from here on a failure leaves the pipeline UNconfigured
-    // (run / results / ... return CBV_ERR_STATE) instead of half reconfigured
-    p->configured = false;
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    p->cfg = *cfg;
-    p->keep_enhanced = cfg->keep_enhanced != 0;
-    int chunk = cfg->chunk;
-    if (chunk <= 0) chunk = 32;
-    if (chunk > p->max_frames) chunk = p->max_frames;
-    p->chunk = chunk;
-    if (!host_invert3x3(cfg->M, p->Minv)) memset(p->Minv, 0, sizeof(p->Minv));
-    const int S = cfg->board_size;
-    p->warped_stride = ((size_t)S * S * 3 + 255) & ~(size_t)255;
-    // (re)allocate
-    int lanes = cfg->lanes <= 0 ? 2 : cfg->lanes;
-    if (lanes > cbv_pipeline::MAX_LANES) lanes = cbv_pipeline::MAX_LANES;
-    if ((p->max_frames + chunk - 1) / chunk < lanes) lanes = (p->max_frames + chunk - 1) / chunk;
-    p->n_lanes = lanes;
-    for (int l = 0; l < cbv_pipeline::MAX_LANES; l++) {
-        if (p->A[l]) (void)hipFree(p->A[l]);
-        if (p->B[l]) (void)hipFree(p->B[l]);
-        if (p->C[l]) (void)hipFree(p->C[l]);
-        p->A[l] = p->B[l] = p->C[l] = nullptr;
-    }
-    // region-limited enhancement: the source footprint of the S x S warp = the image of the destination square under
-    // Minv (a projective map keeps the square convex while W > 0 on it: its four corners bound it), + 3 px for the
-    // 1/32-px rounding and the bilinear taps
-    p->use_region = false;
-    if (cfg->enhance_region && !p->keep_enhanced && sharpen_region_ok(cfg->enhance.sharpen_kernel))
-        p->use_region = warp_footprint(p->Minv, S, S, p->w, p->h, &p->region);
-    if (p->warped) (void)hipFree(p->warped);
-    if (p->enhanced) (void)hipFree(p->enhanced);
-    p->warped = p->enhanced = nullptr;
-    if (!p->start_ev) CBV_HIP(ctx, hipEventCreateWithFlags(&p->start_ev, hipEventDisableTiming));
-    for (int l = 0; l < lanes; l++) {
-        CBV_HIP(ctx, hipMalloc((void**)&p->A[l], p->g.frame_stride * chunk + 256));
-        CBV_HIP(ctx, hipMalloc((void**)&p->B[l], p->g.frame_stride * chunk + 256));
-        if (p->use_region) CBV_HIP(ctx, hipMalloc((void**)&p->C[l], p->g.frame_stride * chunk + 256));
-        SmallLayout SL;
-        RC(small_layout(ctx, &p->lane_small[l], cfg->enhance.tiles_x * cfg->enhance.tiles_y, chunk, &SL, cfg->enhance.tiles_x, cfg->enhance.tiles_y));
-        RC(dev_ensure(ctx, &p->lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * chunk)));
-        if (l > 0) RC(ctx_worker_stream(ctx, &ctx->lane_streams[l], &p->lane_stream[l]));
-        if (!p->lane_done[l]) CBV_HIP(ctx, hipEventCreateWithFlags(&p->lane_done[l], hipEventDisableTiming));
-    }
-    if (p->keep_enhanced) CBV_HIP(ctx, hipMalloc((void**)&p->enhanced, p->g.frame_stride * p->max_frames + 256));
-    RC(pipeline_setup_board(p, cfg));
-    p->configured = true;
-    return CBV_OK;
-}
-
-// ---------------------------------------------------------------------------
-// several boards per frame
-// ---------------------------------------------------------------------------
-// the device table of a parent's boards (BoardDev: board 0 = the parent); rebuilt whenever a board is attached or
-// detached or a board's background model appears (calibrate).  Nothing may be in flight: the callers joined the runs.
-static int pipeline_upload_boards(cbv_pipeline* p)
-{
-    cbv_ctx* ctx = p->ctx;
-    if (p->boards.empty()) return CBV_OK;
-    std::vector<cbv_pipeline*> all(1, p);
-    all.insert(all.end(), p->boards.begin(), p->boards.end());
-    std::vector<BoardDev> tab(all.size());
-    p->mb_any_hough = false;
-    p->mb_hough_lds[0] = p->mb_hough_lds[1] = 0;
-    p->mb_max_px = p->mb_max_S = 0;
-    for (size_t k = 0; k < all.size(); k++) {
-        cbv_pipeline* q = all[k];
-        const cbv_pipeline_config& c = q->cfg;
-        BoardDev& T = tab[k];
-        memset(&T, 0, sizeof(T));
-        memcpy(T.Minv, q->Minv, sizeof(T.Minv));
-        T.S = c.board_size;
-        T.rot180 = c.rot180;
-        // launch_warp's block shape of an S x S destination (BLOCK_SZ = 32)
-        int bh0 = 16 < T.S ? 16 : T.S;
-        const int bw0 = 1024 / bh0 < T.S ? 1024 / bh0 : T.S;
-        bh0 = 1024 / bw0 < T.S ? 1024 / bw0 : T.S;
-        T.bw0 = bw0;
-        T.bh0 = bh0;
-        T.warped = q->warped;
-        T.warped_stride = q->warped_stride;
-        T.descs = (const SquareDesc*)q->d_descs.p;
-        T.n = c.n_rois;
-        T.want_hough = c.use_hough;
-        T.masks = (const u8*)q->d_masks.p;
-        T.gray = (u8*)q->d_gray.p;
-        T.plane_total = q->plane_total;
-        T.mean = q->calibrated ? (const float*)q->d_mean.p : nullptr;
-        T.sd = q->calibrated ? (const float*)q->d_var.p + q->plane_total : nullptr;
-        T.z_thresh = (float)c.z_threshold;
-        T.stats = (cbv_sq_stats*)q->d_stats.p;
-        T.dec = (u8*)q->d_dec.p;
-        T.hough = c.use_hough ? (cbv_hough_result*)q->d_hough.p : nullptr;
-        if (c.use_hough) {
-            size_t lds[2];
-            hough_board_cfgs(q->hough_cfg, T.hcfg, lds);
-            if (!lds[0] || !lds[1])
-                return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles stage: %dx%d squares of board %d do not fit the LDS layout",
-                                q->hough_cfg.maxw, q->hough_cfg.maxh, (int)k);
-            p->mb_any_hough = true;
-            p->mb_hough_lds[0] = std::max(p->mb_hough_lds[0], lds[0]);
-            p->mb_hough_lds[1] = std::max(p->mb_hough_lds[1], lds[1]);
-        }
-        T.sp = scan_params(c, q->calibrated);
-        T.ref = (u8*)q->d_ref.p;
-        T.state = (ScanState*)q->d_state.p;
-        T.flags = (u8*)q->d_flags.p;
-        T.results = (cbv_frame_result*)q->d_results.p;
-        T.check = (const u64*)q->d_check.p; // (all-zero sets = no squares_to_check)
-        T.noise_state = (cbv_noise_state*)q->d_noise_state.p;
-        T.noise = (cbv_noise_result*)q->d_noise.p;
-        T.mirror = (cbv_frame_result*)q->h_stage;
-        T.over_src = c.use_hough ? (const u32*)q->d_hough_over.p : nullptr;
-        T.over_dst = pipeline_over_word(q);
-        p->mb_max_px = std::max(p->mb_max_px, q->max_px);
-        p->mb_max_S = std::max(p->mb_max_S, c.board_size);
-    }
-    RC(dev_ensure(ctx, &p->d_boards, sizeof(BoardDev) * tab.size()));
-    CBV_HIP(ctx, hipMemcpyAsync(p->d_boards.p, tab.data(), sizeof(BoardDev) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CBV_OK;
-}
-
-// enhance_region of a pipeline with boards: the bounding rectangle of every board's warp footprint (any board without
-// one: the whole frame); the third scratch frame set is allocated when the region first becomes usable
-static int pipeline_update_region(cbv_pipeline* p)
-{
-    cbv_ctx* ctx = p->ctx;
-    const cbv_pipeline_config& cfg = p->cfg;
-    bool use = cfg.enhance_region && !p->keep_enhanced && sharpen_region_ok(cfg.enhance.sharpen_kernel);
-    PxRect u = {0, 0, 0, 0};
-    if (use) use = warp_footprint(p->Minv, cfg.board_size, cfg.board_size, p->w, p->h, &u);
-    for (cbv_pipeline* q : p->boards) {
-        PxRect r;
-        if (!use || !warp_footprint(q->Minv, q->cfg.board_size, q->cfg.board_size, p->w, p->h, &r)) {
-            use = false;
-            break;
-        }
-        u = {std::min(u.x0, r.x0), std::min(u.y0, r.y0), std::max(u.x1, r.x1), std::max(u.y1, r.y1)};
-    }
-    if (use)
-        for (int l = 0; l < p->n_lanes; l++)
-            if (!p->C[l]) CBV_HIP(ctx, hipMalloc((void**)&p->C[l], p->g.frame_stride * p->chunk + 256));
-    p->use_region = use;
-    if (use) p->region = u;
-    return CBV_OK;
-}
-
-// free a board handle's buffers (it has no lanes, frames or runs of its own)
-static void board_free(cbv_pipeline* b)
-{
-    if (b->h_stage) (void)hipHostFree(b->h_stage);
-    if (b->warped) (void)hipFree(b->warped);
-    DevBuf* bufs[] = {&b->d_descs, &b->d_masks, &b->d_gray, &b->d_stats, &b->d_ref, &b->d_state, &b->d_results, &b->d_flags, &b->d_dec, &b->d_noise, &b->d_noise_state, &b->d_coef, &b->d_synth, &b->d_mean, &b->d_var, &b->d_hough, &b->d_check, &b->d_hough_over};
-    for (auto d : bufs) dev_free(d);
-    delete b;
-}
-
-extern "C" int cbv_pipeline_add_board(cbv_pipeline* p, const cbv_board_config* bc, cbv_pipeline** out)
-{
-    if (!p || !bc || !out) return cbv_fail(p ? p->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_add_board: bad arguments");
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_add_board: the parent is itself a board handle");
-    if (!p->configured) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_add_board: the parent is not configured");
-    if ((int)p->boards.size() + 1 >= CBV_MAX_BOARDS)
-        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_add_board: a pipeline holds at most %d boards", CBV_MAX_BOARDS);
-    if (p->max_frames >= (1 << (MB_BOARD_SHIFT - 8)))
-        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_add_board: at most %d frames in a pipeline with boards", (1 << (MB_BOARD_SHIFT - 8)) - 1);
-    // the board's configuration = the parent's with the board's subset replaced
-    cbv_pipeline_config cfg = p->cfg;
-    memcpy(cfg.M, bc->M, sizeof(cfg.M));
-    cfg.board_size = bc->board_size;
-    cfg.rot180 = bc->rot180;
-    cfg.n_rois = bc->n_rois;
-    memcpy(cfg.rois, bc->rois, sizeof(cfg.rois));
-    cfg.history_size = bc->history_size;
-    cfg.min_presence = bc->min_presence;
-    cfg.change_threshold = bc->change_threshold;
-    cfg.z_threshold = bc->z_threshold;
-    cfg.initial_variance = bc->initial_variance;
-    cfg.use_hough = bc->use_hough;
-    cfg.hough = bc->hough;
-    RC(check_board_cfg(ctx, &cfg));
-    if (cfg.use_hough) RC(hough_params_check(ctx, &cfg.hough));
-    RC(join_scan(p));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // the parent's worklists hold every board's items (grown only: a larger list serves fewer boards as well)
-    for (int l = 0; l < p->n_lanes; l++)
-        RC(dev_ensure(ctx, &p->lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * p->chunk * (p->boards.size() + 2))));
-    cbv_pipeline* b = new cbv_pipeline();
-    b->ctx = ctx;
-    b->w = p->w;
-    b->h = p->h;
-    b->max_frames = p->max_frames;
-    b->g = p->g;
-    b->chunk = p->chunk;
-    b->keep_enhanced = p->keep_enhanced;
-    b->cfg = cfg;
-    if (!host_invert3x3(cfg.M, b->Minv)) memset(b->Minv, 0, sizeof(b->Minv));
-    b->warped_stride = ((size_t)cfg.board_size * cfg.board_size * 3 + 255) & ~(size_t)255;
-    int rc = pipeline_setup_board(b, &cfg);
-    if (rc == CBV_OK) {
-        b->parent = p;
-        b->configured = true;
-        p->boards.push_back(b);
-        rc = pipeline_upload_boards(p);
-        if (rc == CBV_OK) rc = pipeline_update_region(p);
-        if (rc != CBV_OK) {
-            p->boards.pop_back();
-            const std::string err = ctx->err;
-            if (!p->boards.empty()) (void)pipeline_upload_boards(p);
-            (void)pipeline_update_region(p);
-            ctx->err = err;
-        }
-    }
-    if (rc != CBV_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        board_free(b);
-        return rc;
-    }
-    *out = b;
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_reset_state(cbv_pipeline* p)
-{
-    if (!p || !p->configured) return CBV_ERR_STATE;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    CBV_HIP(ctx, hipMemsetAsync(p->d_state.p, 0, sizeof(ScanState) * p->cfg.n_rois, ctx->stream));
-    CBV_HIP(ctx, hipMemsetAsync(p->d_noise_state.p, 0, sizeof(cbv_noise_state), ctx->stream));
-    if (p->d_hough_over.p) {
-        CBV_HIP(ctx, hipMemsetAsync(p->d_hough_over.p, 0, 4, ctx->stream));
-        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the runs that could still write the mirror's copy are behind us
-        *pipeline_over_word(p) = 0;
-    }
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_calibrate(cbv_pipeline* p, int slot)
-{
-    if (!p || !p->configured) return CBV_ERR_STATE;
-    cbv_ctx* ctx = p->ctx;
-    if (slot < 0 || slot >= p->max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_calibrate: bad slot");
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    RC(launch_squares_calibrate(ctx, (const SquareDesc*)p->d_descs.p, p->cfg.n_rois, (const u8*)p->d_gray.p + p->plane_total * slot,
-                                (float*)p->d_mean.p, (float*)p->d_var.p, (float*)p->d_var.p + p->plane_total, (float)p->cfg.initial_variance, nullptr));
-    p->calibrated = true;
-    cbv_pipeline* root = p->parent ? p->parent : p;
-    if (!root->boards.empty()) RC(pipeline_upload_boards(root)); // the board's statistics read its model from now on
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int reset_noise)
-{
-    if (!p || !p->configured) return CBV_ERR_STATE;
-    cbv_ctx* ctx = p->ctx;
-    if (slot < 0 || slot >= p->max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_update_references: bad slot");
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    RC(launch_scan_update_refs(ctx, (const SquareDesc*)p->d_descs.p, p->cfg.n_rois, (const u8*)p->d_gray.p + p->plane_total * slot,
-                               (u8*)p->d_ref.p, (ScanState*)p->d_state.p));
-    if (reset_noise) CBV_HIP(ctx, hipMemsetAsync(p->d_noise_state.p, 0, sizeof(cbv_noise_state), ctx->stream)); // NoiseHandler.reset()
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr, int stride)
-{
-    if (p && p->parent) return cbv_fail(p->ctx, CBV_ERR_STATE, "cbv_pipeline_upload: frames go to the parent of a board");
-    if (!p || !bgr || slot < 0 || slot >= p->max_frames || stride < p->w * 3) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    RC(rows_h2d(ctx, p->frames + p->g.frame_stride * slot, bgr, stride, p->w * 3, p->h));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CBV_OK;
-}
-
-extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)
-{
-    if (!p) return nullptr;
-    cbv_ctx* ctx = p->ctx;
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    if (p->parent) {
-        cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_host_ring: frames go to the parent of a board");
-        return nullptr;
-    }
-    if (!p->host_ring) {
-        if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
-        if (hipHostMalloc((void**)&p->host_ring, p->g.frame_stride * p->max_frames, hipHostMallocDefault) != hipSuccess) {
-            cbv_fail(ctx, CBV_ERR_HIP, "pinned host ring of %zu bytes could not be allocated", p->g.frame_stride * p->max_frames);
-            p->host_ring = nullptr;
-        }
-    }
-    return p->host_ring;
-}
-
-extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
-{
-    if (!p) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_submit: frames go to the parent of a board");
-    if (slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_submit: bad slot range");
-    if (!p->host_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_submit: cbv_pipeline_host_ring() was never called");
-    CBV_ENTER(ctx);
-    if (!p->copy_stream) RC(ctx_worker_stream(ctx, &ctx->copy_stream, &p->copy_stream));
-    // do not overwrite device slots a run that is still in flight reads: ANY such run, not only the last one
-    retire_runs(p);
-    {
-        cbv_pipeline::RunRec* best = nullptr;
-        for (auto& r : p->runs)
-            if (r.live && ranges_overlap(slot0, count, r.s0, r.cnt) && (!best || r.seq > best->seq)) best = &r;
-        if (best) CBV_HIP(ctx, hipStreamWaitEvent(p->copy_stream, best->one_event ? best->scan_ev : best->lanes_ev, 0));
-    }
-    CBV_HIP(ctx, hipMemcpyAsync(p->frames + p->g.frame_stride * slot0, p->host_ring + p->g.frame_stride * slot0,
-                                p->g.frame_stride * count, hipMemcpyHostToDevice, p->copy_stream));
-    cbv_pipeline::CopyRec* rec = nullptr;
-    for (auto& c : p->copies)
-        if (!c.pending) {
-            rec = &c;
-            break;
-        }
-    if (!rec) {
-        cbv_pipeline::CopyRec c{0, 0, nullptr, false};
-        CBV_HIP(ctx, hipEventCreateWithFlags(&c.ev, hipEventDisableTiming));
-        p->copies.push_back(c);
-        rec = &p->copies.back();
-    }
-    rec->s0 = slot0;
-    rec->cnt = count;
-    rec->pending = true;
-    CBV_HIP(ctx, hipEventRecord(rec->ev, p->copy_stream));
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_wait_submitted(cbv_pipeline* p)
-{
-    if (!p) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    if (p->copy_stream) CBV_HIP(ctx, hipStreamSynchronize(p->copy_stream));
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_synth(cbv_pipeline* p, int slot0, int count, const uint64_t* seeds, const double* Hinv9,
-                                  const uint8_t* boards, const cbv_scene* scene)
-{
-    if (p && p->parent) return cbv_fail(p->ctx, CBV_ERR_STATE, "cbv_pipeline_synth: frames go to the parent of a board");
-    if (!p || !seeds || !Hinv9 || !boards || !scene || slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    size_t o_seeds = 0, o_h = (size_t)count * 8, o_b = o_h + 72, o_s = (o_b + (size_t)count * 64 + 15) & ~(size_t)15;
-    size_t total = o_s + sizeof(cbv_scene);
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RC(dev_ensure(ctx, &p->d_synth, total));
-    std::vector<u8> host(total, 0);
-    memcpy(host.data() + o_seeds, seeds, (size_t)count * 8);
-    memcpy(host.data() + o_h, Hinv9, 72);
-    memcpy(host.data() + o_b, boards, (size_t)count * 64);
-    memcpy(host.data() + o_s, scene, sizeof(cbv_scene));
-    CBV_HIP(ctx, hipMemcpy(p->d_synth.p, host.data(), total, hipMemcpyHostToDevice));
-    u8* base = (u8*)p->d_synth.p;
-    RC(launch_synth(ctx, p->frames + p->g.frame_stride * slot0, p->g, (const u64*)(base + o_seeds), (const double*)(base + o_h),
-                    base + o_b, (const cbv_scene*)(base + o_s), count));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CBV_OK;
-}
-
-// second half of cbv_pipeline_run: join the lanes on the scan's stream, HoughCircles second pass, temporal scan, run record
-static int pipeline_run_tail(cbv_pipeline* p, cbv_pipeline::RunRec* rec, int slot0, int count, bool inline_scan, const bool* lane_used,
-                             hipStream_t main_stream)
-{
-    cbv_ctx* ctx = p->ctx;
-    const cbv_pipeline_config& cfg = p->cfg;
-    const int n = cfg.n_rois;
-    if (!p->scan_stream) {
-        RC(ctx_worker_stream(ctx, &ctx->scan_stream, &p->scan_stream));
-        CBV_HIP(ctx, hipEventCreateWithFlags(&p->main_done, hipEventDisableTiming));
-    }
-    hipStream_t scan_on = inline_scan ? main_stream : p->scan_stream;
-    if (!inline_scan) {
-        CBV_HIP(ctx, hipEventRecord(p->main_done, main_stream));
-        CBV_HIP(ctx, hipStreamWaitEvent(scan_on, p->main_done, 0));
-    }
-    // every forked lane is joined, in the inline case too (chunk = 1 puts the second frame of a two-frame run on lane 1)
-    for (int l = 1; l < p->n_lanes; l++)
-        if (lane_used[l]) {
-            CBV_HIP(ctx, hipEventRecord(p->lane_done[l], p->lane_stream[l]));
-            CBV_HIP(ctx, hipStreamWaitEvent(scan_on, p->lane_done[l], 0));
-        }
-    // every lane has read its frames: a later cbv_pipeline_submit may overwrite these slots after this event
-    rec->one_event = inline_scan;
-    if (!inline_scan) CBV_HIP(ctx, hipEventRecord(rec->lanes_ev, scan_on));
-    ctx->stream = scan_on;
-    struct Restore {
-        cbv_ctx* c;
-        hipStream_t s;
-        ~Restore() { c->stream = s; }
-    } restore{ctx, main_stream};
-    if (!p->boards.empty()) { // every board's second pass, scan, packing and NoiseHandler: one launch each
-        const BoardDev* tab = (const BoardDev*)p->d_boards.p;
-        const int nb = 1 + (int)p->boards.size();
-        if (p->mb_any_hough)
-            RC(launch_hough_mb(ctx, tab, nb, slot0, (const u32*)rec->retry.p, CBV_MAX_SQUARES * nb * count, p->mb_hough_lds[1], nullptr, 0, 1));
-        const bool mirrored = count <= 4;
-        for (int k = 0; k < nb; k++) {
-            cbv_pipeline* q = k == 0 ? p : p->boards[k - 1];
-            for (int t = 0; t < count; t++) q->slot_mirrored[(size_t)slot0 + t] = mirrored ? 1 : 0;
-        }
-        RC(launch_scan_mb(ctx, tab, nb, slot0, count, mirrored ? 1 : 0));
-        CBV_HIP(ctx, hipEventRecord(rec->scan_ev, scan_on));
-        rec->s0 = slot0;
-        rec->cnt = count;
-        rec->seq = ++p->run_seq;
-        rec->live = true;
-        return CBV_OK;
-    }
-    if (cfg.use_hough) // squares whose first HoughCircles pass overflowed (normally none), before the scan reads the decisions
-        RC(launch_hough_second(ctx, (const SquareDesc*)p->d_descs.p, n, (const u8*)p->d_gray.p + p->plane_total * slot0, p->plane_total,
-                               p->hough_cfg, (cbv_hough_result*)p->d_hough.p + (size_t)CBV_MAX_SQUARES * slot0,
-                               (u8*)p->d_dec.p + (size_t)CBV_MAX_SQUARES * slot0, (const u32*)rec->retry.p, n * count));
-    const ScanParams sp = scan_params(cfg, p->calibrated);
-    // A short run (the live-camera case) writes its records to the pinned mirror too: reading them back is then a wait and a
-    // host copy instead of two more launches.  Not the long runs: their records would cross PCIe as thousands of 8-byte
-    // writes inside the scan stream's critical path (512-frame steps: -0.5 % frames/s, alternating A/B runs); they are
-    // fetched with one copy when asked for.
-    ResultMirror mir;
-    const bool mirrored = count <= 4;
-    if (mirrored) {
-        mir.records = (cbv_frame_result*)p->h_stage + slot0;
-        mir.over_src = cfg.use_hough ? (const u32*)p->d_hough_over.p : nullptr;
-        mir.over_dst = pipeline_over_word(p);
-    }
-    for (int t = 0; t < count; t++) p->slot_mirrored[(size_t)slot0 + t] = mirrored ? 1 : 0;
-    // + NoiseHandler on the frames' visual_changes sets (game_session.py:165)
-    RC(launch_scan(ctx, (const SquareDesc*)p->d_descs.p, sp, (const u8*)p->d_gray.p + p->plane_total * slot0, p->plane_total,
-                   (const u8*)p->d_dec.p + (size_t)CBV_MAX_SQUARES * slot0, (u8*)p->d_ref.p, (ScanState*)p->d_state.p,
-                   (u8*)p->d_flags.p + (size_t)CBV_MAX_SQUARES * slot0, (cbv_frame_result*)p->d_results.p + slot0, count,
-                   p->has_check ? (const u64*)p->d_check.p + slot0 : nullptr, (cbv_noise_state*)p->d_noise_state.p,
-                   (cbv_noise_result*)p->d_noise.p + slot0, mir));
-    CBV_HIP(ctx, hipEventRecord(rec->scan_ev, scan_on));
-    rec->s0 = slot0;
-    rec->cnt = count;
-    rec->seq = ++p->run_seq;
-    rec->live = true;
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
-{
-    if (!p || !p->configured) return CBV_ERR_STATE;
-    cbv_ctx* ctx = p->ctx;
-    if (p->parent) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: a board is run by its parent");
-    if (slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_run: bad slot range");
-    CBV_ENTER(ctx);
-    const cbv_pipeline_config& cfg = p->cfg;
-    const int S = cfg.board_size, n = cfg.n_rois;
-    // Lane 0 is the context's stream; lanes 1.. are worker streams forked from it and joined before
-    // the temporal scan (which needs every frame's statistics, in order).
-    hipStream_t main_stream = ctx->stream;
-    // A run of one or two frames (the live-camera case) is latency, not throughput: its scan is a few microseconds, less
-    // than the hop to the scan stream and back, so everything stays on the caller's stream, behind every run in flight
-    // (the scans' state is sequential over runs).
-    const bool inline_scan = count <= 2;
-    const int chunks = (count + p->chunk - 1) / p->chunk;
-    // Chunks go round the lanes, and the round continues from run to run and from pipeline to pipeline of this context
-    // (ctx->lane_rr): K camera streams whose runs are one chunk each would otherwise all pile on lane 0 and lose the
-    // overlap of the lanes.  Short (latency) runs start on the caller's stream.
-    const int lane_base = inline_scan ? 0 : ctx->lane_rr % p->n_lanes;
-    if (!inline_scan) ctx->lane_rr = (ctx->lane_rr + chunks) % (12 * 1024);
-    bool lane_used[cbv_pipeline::MAX_LANES] = {false, false, false, false};
-    for (int c = 0; c < chunks && c < p->n_lanes; c++) lane_used[(lane_base + c) % p->n_lanes] = true;
-    if (inline_scan) {
-        retire_runs(p);
-        RC(join_scan(p));
-    } else RC(join_slots(p, slot0, count)); // scans in flight that still read these slots' planes, however many runs back
-    cbv_pipeline::RunRec* rec = nullptr; // the record (and second-pass list) of this run
-    for (auto& r : p->runs)
-        if (!r.live) {
-            rec = &r;
-            break;
-        }
-    if (!rec) {
-        cbv_pipeline::RunRec r{0, 0, 0, nullptr, nullptr, false, false, DevBuf()};
-        CBV_HIP(ctx, hipEventCreateWithFlags(&r.lanes_ev, hipEventDisableTiming));
-        CBV_HIP(ctx, hipEventCreateWithFlags(&r.scan_ev, hipEventDisableTiming));
-        p->runs.push_back(r);
-        rec = &p->runs.back();
-    }
-    // the second-pass list's counter: zeroed before the lanes fork from this stream, or, when the run is ONE chunk, by that
-    // chunk's k_warp (a memset is a launch of its own, ~13 us with its bubble in front of a 150 us chain)
-    const bool retry_zero_in_warp = chunks == 1;
-    // with boards attached, each per-board stage below is one launch for all of them (BoardDev table)
-    const bool mb = !p->boards.empty();
-    const int nb = 1 + (int)p->boards.size();
-    const BoardDev* tab = (const BoardDev*)p->d_boards.p;
-    const bool any_hough = mb ? p->mb_any_hough : cfg.use_hough != 0;
-    if (any_hough) {
-        RC(dev_ensure(ctx, &rec->retry, sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * p->max_frames * nb)));
-        if (!retry_zero_in_warp) CBV_HIP(ctx, hipMemsetAsync(rec->retry.p, 0, sizeof(u32), main_stream));
-    }
-    for (auto& c : p->copies) // ingest copies of these slots must have landed
-        if (c.pending && ranges_overlap(slot0, count, c.s0, c.cnt)) {
-            CBV_HIP(ctx, hipStreamWaitEvent(main_stream, c.ev, 0));
-            c.pending = false;
-        }
-    bool forked = false;
-    for (int l = 1; l < p->n_lanes; l++) forked = forked || lane_used[l];
-    if (forked) {
-        CBV_HIP(ctx, hipEventRecord(p->start_ev, main_stream));
-        for (int l = 1; l < p->n_lanes; l++)
-            if (lane_used[l]) CBV_HIP(ctx, hipStreamWaitEvent(p->lane_stream[l], p->start_ev, 0));
-    }
-    int ci = 0, rc_all = CBV_OK;
-    for (int s0 = slot0; s0 < slot0 + count && rc_all == CBV_OK; s0 += p->chunk, ci++) {
-        const int lane = (lane_base + ci) % p->n_lanes;
-        ctx->stream = lane == 0 ? main_stream : p->lane_stream[lane];
-        SmallLayout SL;
-        rc_all = small_layout(ctx, &p->lane_small[lane], cfg.enhance.tiles_x * cfg.enhance.tiles_y, p->chunk, &SL, cfg.enhance.tiles_x, cfg.enhance.tiles_y);
-        if (rc_all) break;
-        const int b = std::min(p->chunk, slot0 + count - s0);
-        const u8* src = p->frames + p->g.frame_stride * s0;
-        u8* res = nullptr;
-        NormSrc norm;
-        rc_all = enhance_dev(ctx, src, p->A[lane], p->B[lane], p->g, &cfg.enhance, SL, b, !p->keep_enhanced, &res, &norm,
-                             p->use_region ? &p->region : nullptr, p->C[lane]);
-        if (rc_all) break;
-        u8* wdst = p->warped + p->warped_stride * s0;
-        u32* work = any_hough ? (u32*)p->lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
-        u32* retry0 = any_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
-        if (p->keep_enhanced) {
-            if (hipMemcpyAsync(p->enhanced + p->g.frame_stride * s0, res, p->g.frame_stride * b, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
-                rc_all = cbv_fail(ctx, CBV_ERR_HIP, "copy of the enhanced frames failed");
-                break;
-            }
-        }
-        if (mb) {
-            rc_all = launch_warp_mb(ctx, res, p->g, tab, nb, p->mb_max_S, s0, p->keep_enhanced ? NormSrc() : norm, b, work, retry0);
-            if (rc_all) break;
-            rc_all = launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, any_hough, work, p->mb_max_px);
-            if (rc_all) break;
-            if (any_hough)
-                rc_all = launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, p->mb_hough_lds[0], (u32*)rec->retry.p, s0 - slot0, 0);
-            continue;
-        }
-        if (p->keep_enhanced) {
-            rc_all = launch_warp(ctx, res, p->g, p->Minv, S, S, cfg.rot180, wdst, S * 3, p->warped_stride, NormSrc(), b, work, retry0);
-        } else {
-            rc_all = launch_warp(ctx, res, p->g, p->Minv, S, S, cfg.rot180, wdst, S * 3, p->warped_stride, norm, b, work, retry0);
-        }
-        if (rc_all) break;
-        u8* dec = (u8*)p->d_dec.p + (size_t)CBV_MAX_SQUARES * s0;
-        cbv_hough_result* hres = cfg.use_hough ? (cbv_hough_result*)p->d_hough.p + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
-        rc_all = launch_squares_pre5_stats(ctx, wdst, p->warped_stride, (const SquareDesc*)p->d_descs.p, n,
-                                           (u8*)p->d_gray.p + p->plane_total * s0, p->plane_total,
-                                           p->calibrated ? (const float*)p->d_mean.p : nullptr, p->calibrated ? (const float*)p->d_var.p + p->plane_total : nullptr,
-                                           (const u8*)p->d_masks.p, (float)cfg.z_threshold, (cbv_sq_stats*)p->d_stats.p + (size_t)n * s0, b,
-                                           dec, cfg.use_hough, work, hres, p->max_px);
-        if (rc_all) break;
-        if (cfg.use_hough)
-            rc_all = launch_hough(ctx, (const SquareDesc*)p->d_descs.p, n, (const u8*)p->d_gray.p + p->plane_total * s0, p->plane_total,
-                                  p->hough_cfg, hres, dec, work, b, (u32*)rec->retry.p, s0 - slot0);
-    }
-    ctx->stream = main_stream;
-    // A failure after lanes were forked: whatever they already enqueued on these slots and scratch buffers must not outlive
-    // the call unordered (no RunRec goes live for a failed run), whether a lane's launch failed or the join / scan below did.
-    auto drain = [&](int rc) {
-        ctx->stream = main_stream;
-        for (int l = 1; l < p->n_lanes; l++)
-            if (lane_used[l]) (void)hipStreamSynchronize(p->lane_stream[l]);
-        if (p->scan_stream) (void)hipStreamSynchronize(p->scan_stream);
-        (void)hipStreamSynchronize(main_stream);
-        return rc;
-    };
-    if (rc_all) return drain(rc_all);
-    const int rc_tail = pipeline_run_tail(p, rec, slot0, count, inline_scan, lane_used, main_stream);
-    return rc_tail == CBV_OK ? CBV_OK : drain(rc_tail);
-}
-
-extern "C" int cbv_pipeline_set_check_squares(cbv_pipeline* p, int slot0, int count, const uint64_t* roi_masks)
-{
-    if (!p || !p->configured || slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // the last run's scan may still read the masks
-    if (roi_masks) {
-        CBV_HIP(ctx, hipMemcpyAsync((u64*)p->d_check.p + slot0, roi_masks, sizeof(u64) * count, hipMemcpyHostToDevice, ctx->stream));
-        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the caller's buffer may go away
-        p->has_check = true;
-    } else CBV_HIP(ctx, hipMemsetAsync((u64*)p->d_check.p + slot0, 0, sizeof(u64) * count, ctx->stream));
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_results(cbv_pipeline* p, int slot0, int count, cbv_frame_result* out)
-{
-    if (!p || !out || slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    if (!p->configured || !p->h_stage) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_results: the pipeline is not configured");
-    // short runs left their records in pinned host memory (ResultMirror): wait for the runs, copy on the host; the others
-    // are fetched into the same place first (through pinned memory in any case: a copy into the caller's pageable buffer
-    // would be staged by the runtime, one blocking copy at a time)
-    const size_t bytes = sizeof(cbv_frame_result) * (size_t)count;
-    u32* over_h = pipeline_over_word(p);
-    bool have = true;
-    for (int t = 0; t < count; t++) have = have && p->slot_mirrored[(size_t)slot0 + t];
-    if (!have) {
-        CBV_HIP(ctx, hipMemcpyAsync((cbv_frame_result*)p->h_stage + slot0, (cbv_frame_result*)p->d_results.p + slot0, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (p->cfg.use_hough && p->d_hough_over.p) CBV_HIP(ctx, hipMemcpyAsync(over_h, p->d_hough_over.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (!have)
-        for (int t = 0; t < count; t++) p->slot_mirrored[(size_t)slot0 + t] = 1;
-    memcpy(out, (const cbv_frame_result*)p->h_stage + slot0, bytes);
-    const u32 over = *over_h;
-    if (over) {
-        // A truncated candidate list may change has_piece: never hand that over as if it were HoughCircles' answer.  The
-        // counter is cleared on read, so the error is reported ONCE, by the first results call after the runs it
-        // happened in, and later frames are not poisoned; `out` is filled and valid except for the flagged squares.
-        CBV_HIP(ctx, hipMemsetAsync(p->d_hough_over.p, 0, 4, ctx->stream));
-        *over_h = 0; // (nothing is in flight: the next run's last kernel writes the word again)
-        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles: the candidate list overflowed even the second pass on %u square(s) since the "
-                        "previous cbv_pipeline_results; those occupancy bits are not HoughCircles' (cbv_pipeline_hough flags name the squares)", over);
-    }
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_noise_results(cbv_pipeline* p, int slot0, int count, cbv_noise_result* out)
-{
-    if (!p || !out || !p->configured || slot0 < 0 || count <= 0 || slot0 + count > p->max_frames) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    CBV_HIP(ctx, hipMemcpyAsync(out, (cbv_noise_result*)p->d_noise.p + slot0, sizeof(cbv_noise_result) * count, hipMemcpyDeviceToHost, ctx->stream));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CBV_OK;
-}
-
 extern "C" int cbv_noise_run(cbv_ctx* ctx, const uint64_t* changes, int n, cbv_noise_state* state, cbv_noise_result* out)
 {
     if (!ctx || !changes || !state || !out || n <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_noise_run: bad arguments");
@@ -2445,58 +1467,6 @@ extern "C" int cbv_noise_run(cbv_ctx* ctx, const uint64_t* changes, int n, cbv_n
     RC(launch_noise(ctx, (const u64*)base, 1, n, (cbv_noise_state*)(base + b_in + b_out), (cbv_noise_result*)(base + b_in)));
     CBV_HIP(ctx, hipMemcpyAsync(out, base + b_in, (size_t)n * sizeof(cbv_noise_result), hipMemcpyDeviceToHost, ctx->stream));
     CBV_HIP(ctx, hipMemcpyAsync(state, base + b_in + b_out, sizeof(cbv_noise_state), hipMemcpyDeviceToHost, ctx->stream));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8_t* out)
-{
-    if (!p || !out || slot < 0 || slot >= p->max_frames) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    const u8* src;
-    size_t bytes;
-    if (p->parent && which != 2) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: a board holds only its warped frames (which = 2)");
-    if (which == 0) {
-        src = p->frames + p->g.frame_stride * slot;
-        bytes = (size_t)p->w * p->h * 3;
-    } else if (which == 1) {
-        if (!p->enhanced) return cbv_fail(ctx, CBV_ERR_STATE, "enhanced frames are not kept (configure with keep_enhanced = 1)");
-        src = p->enhanced + p->g.frame_stride * slot;
-        bytes = (size_t)p->w * p->h * 3;
-    } else if (which == 2) {
-        if (!p->warped) return cbv_fail(ctx, CBV_ERR_STATE, "pipeline not configured");
-        src = p->warped + p->warped_stride * slot;
-        bytes = (size_t)p->cfg.board_size * p->cfg.board_size * 3;
-    } else
-        return cbv_fail(ctx, CBV_ERR_ARG, "bad buffer selector %d", which);
-    CBV_HIP(ctx, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out)
-{
-    if (!p || !out || slot < 0 || slot >= p->max_frames) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    if (!p->configured || !p->cfg.use_hough) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_hough: the HoughCircles stage is not configured");
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    CBV_HIP(ctx, hipMemcpyAsync(out, (const cbv_hough_result*)p->d_hough.p + (size_t)CBV_MAX_SQUARES * slot,
-                                sizeof(cbv_hough_result) * CBV_MAX_SQUARES, hipMemcpyDeviceToHost, ctx->stream));
-    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CBV_OK;
-}
-
-extern "C" int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats* out)
-{
-    if (!p || !out || !p->configured || slot < 0 || slot >= p->max_frames) return CBV_ERR_ARG;
-    cbv_ctx* ctx = p->ctx;
-    CBV_ENTER(ctx);
-    RC(join_scan(p)); // lanes and scan of the last run
-    CBV_HIP(ctx, hipMemcpyAsync(out, (cbv_sq_stats*)p->d_stats.p + (size_t)p->cfg.n_rois * slot, sizeof(cbv_sq_stats) * p->cfg.n_rois,
-                                hipMemcpyDeviceToHost, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CBV_OK;
 }

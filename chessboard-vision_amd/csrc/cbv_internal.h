@@ -490,3 +490,45 @@ int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int 
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);
 int launch_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int mirrored);
+
+// ---------------------------------------------------------------------------
+// Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline.cpp) shares
+// ---------------------------------------------------------------------------
+#define RC(x)             \
+    do {                  \
+        int rc__ = (x);   \
+        if (rc__) return rc__; \
+    } while (0)
+
+// tightly packed BGR frames, each frame rounded to 256 bytes
+static inline Geom tight_geom(int w, int h)
+{
+    Geom g;
+    g.w = w;
+    g.h = h;
+    g.stride = w * 3;
+    g.frame_stride = ((size_t)w * 3 * h + 255) & ~(size_t)255;
+    return g;
+}
+
+struct SmallLayout {
+    u32* aux;
+    u8* luts;
+    u32* packed; // CLAHE corner words (k_clahe_lut -> k_clahe_apply), null when not reserved
+    u8* norm_lut;
+    // The buffer's tag says which (tiles, batch) layout of `aux` is known to be as k_reset_aux leaves it: enhance_dev's own
+    // kernels restore that state as they go (launch_clahe_lut, self_clean), so a pass over the same layout needs no reset
+    // launch.  Everything else that writes `aux` leaves the tag 0 (aux_dirty).
+    DevBuf* owner;
+};
+int small_layout(cbv_ctx* ctx, DevBuf* buf, int tiles, int batch, SmallLayout* L, int tiles_x = 0, int tiles_y = 0);
+int enhance_dev(cbv_ctx* ctx, const u8* src, u8* A, u8* B, Geom g, const cbv_enhance_params* P, SmallLayout S, int batch,
+                bool fold_norm, u8** result, NormSrc* norm, const PxRect* region = nullptr, u8* C = nullptr);
+bool warp_footprint(const double* Minv, int dw, int dh, int w, int h, PxRect* out);
+int check_params(cbv_ctx* ctx, const cbv_enhance_params* P);
+int rows_h2d(cbv_ctx* ctx, void* dst, const u8* src, int stride, int wbytes, int h);
+int hough_params_check(cbv_ctx* ctx, const cbv_hough_params* prm);
+int hough_cfg(cbv_ctx* ctx, const cbv_hough_params* prm, const std::vector<SquareDesc>& descs, HoughCfg* hc);
+// the square table of n squares ws[i] x hs[i]: descriptors with w, h and the plane / mask offsets (each plane rounded to
+// 16 B), the piece masks and their region counts; returns the bytes of one plane set
+size_t square_table(const int* ws, const int* hs, int n, std::vector<SquareDesc>* descs, std::vector<u8>* masks);

@@ -1,0 +1,1001 @@
+// Device-resident batched pipeline (include/cbv.h, cbv_pipeline_*): frame ring, enhancement lanes, temporal scan, and the
+// boards one camera frame feeds (cbv_pipeline_add_board).
+#include <string.h>
+
+#include <algorithm>
+
+#include "cbv_internal.h"
+
+// One board of a pipeline: what configure's squares part sets up (board_setup).  Board 0 is the pipeline's own; the
+// boards cbv_pipeline_add_board attaches have the same shape.
+struct Board {
+    cbv_pipeline_config cfg; // the pipeline's configuration with the board's subset (cbv_board_config) in it
+    double Minv[9];
+    u8* warped = nullptr; // [max_frames][S][S][3]
+    size_t warped_stride = 0;
+    std::vector<SquareDesc> descs;
+    size_t plane_total = 0;
+    int max_px = 0; // pixels of the largest square
+    DevBuf d_descs, d_masks, d_gray, d_stats, d_ref, d_state, d_results, d_flags, d_dec, d_mean, d_var, d_noise, d_noise_state, d_hough,
+        d_check, d_hough_over;
+    u8* h_stage = nullptr; // pinned mirror of d_results ([max_frames] records, then the HoughCircles overflow word): written by
+                           // the last kernel of a SHORT run (ResultMirror), by a copy otherwise; read by cbv_pipeline_results
+    u32* over_h = nullptr; // the overflow word in h_stage
+    std::vector<u8> slot_mirrored; // per slot: the mirror holds the slot's newest record (once its run has finished)
+    HoughCfg hough_cfg;
+    bool calibrated = false, has_check = false; // has_check: squares_to_check masks were set
+};
+
+struct Pipe;
+
+// The opaque handle: one board of a pipeline.  cbv_pipeline_create returns board 0, which owns the pipeline.
+struct cbv_pipeline {
+    Pipe* pipe;
+    Board b;
+};
+
+// What the boards of a pipeline share: frames, enhancement, lanes, ingest, runs, and the boards' kernel arguments.
+struct Pipe {
+    cbv_ctx* ctx = nullptr;
+    int w = 0, h = 0, max_frames = 0;
+    Geom g;
+    bool configured = false;
+    bool keep_enhanced = false;
+    int chunk = 8;
+    u8* frames = nullptr;
+    // Lanes: chunk c runs on lane c % n_lanes, each lane with its own HIP stream and scratch, so a
+    // VALU-bound bilateral launch of one chunk overlaps the memory-latency-bound kernels of another.
+    enum { MAX_LANES = 4 };
+    int n_lanes = 1;
+    hipStream_t lane_stream[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t lane_done[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t start_ev = nullptr;
+    u8* A[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    u8* B[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    u8* C[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr}; // third scratch frame set: region-limited enhancement only
+    bool use_region = false;                                  // cfg.enhance_region, keep_enhanced == 0, a usable footprint
+    PxRect region = {0, 0, 0, 0};                             // source pixels the warps sample (+ margin), clipped
+    DevBuf lane_small[MAX_LANES];
+    DevBuf lane_work[MAX_LANES]; // HoughCircles worklist of the lane's current chunk: count, then frame << 8 | square
+    u8* enhanced = nullptr;      // [max_frames] when keep_enhanced
+    DevBuf d_synth;
+    // ingest: pinned host mirror of the frame ring, filled by the capture side and copied on its own stream
+    u8* host_ring = nullptr;
+    hipStream_t copy_stream = nullptr;
+    struct CopyRec {
+        int s0, cnt;
+        hipEvent_t ev;
+        bool pending;
+    };
+    std::vector<CopyRec> copies;
+    // The temporal scan (+ NoiseHandler) of a run goes to its own stream behind the lanes' events, so the next run's
+    // enhancement of OTHER slots overlaps it; scans of successive runs stay ordered on that stream.  (Runs of one or
+    // two frames keep their scan on the caller's stream, after waiting for every run in flight: see cbv_pipeline_run.)
+    hipStream_t scan_stream = nullptr;
+    hipEvent_t main_done = nullptr;
+    // Every run that may still be executing: its slot range and two events on the (in-order) scan stream,
+    // `lanes_ev` = all lanes have read the input frames and written the per-slot buffers, `scan_ev` = the scan has
+    // read them.  A later run (or ingest copy) that touches overlapping slots waits on the NEWEST overlapping
+    // record, which covers the older ones because the scan stream is in order.  Records are recycled once their
+    // scan event has completed.
+    struct RunRec {
+        int s0, cnt;
+        unsigned long long seq;
+        hipEvent_t lanes_ev, scan_ev;
+        bool live;
+        bool one_event; // a run of a frame or two, all on the caller's stream: only scan_ev is recorded (an event between two
+                        // kernels is a ~5 us bubble in a 150 us chain), and it stands for lanes_ev too
+        DevBuf retry; // HoughCircles second-pass list of this run (HoughCfg::retry), frames numbered from the run's slot0
+    };
+    std::vector<RunRec> runs;
+    unsigned long long run_seq = 0;    // sequence number of the newest run
+    unsigned long long joined_seq = 0; // runs up to this one are ordered before later work on `joined_stream`
+    hipStream_t joined_stream = nullptr;
+    // the boards (board 0 = the handle cbv_pipeline_create returned) and their kernel arguments: `tab` holds one BoardDev
+    // per board (board_dev), tab[0] feeds the single-board launches; with boards attached it is uploaded to d_boards for the
+    // multi-board launches, which also take the maxima over the boards below
+    std::vector<cbv_pipeline*> boards;
+    std::vector<BoardDev> tab;
+    DevBuf d_boards;
+    bool any_hough = false;
+    size_t hough_lds[2] = {0, 0};
+    int max_px = 0, max_S = 0;
+    Board& b0() const { return boards[0]->b; }
+};
+
+// a handle of a board attached by cbv_pipeline_add_board (not board 0, which stands for the whole pipeline)
+static bool attached(const cbv_pipeline* p) { return p != p->pipe->boards[0]; }
+
+static bool ranges_overlap(int a0, int an, int b0, int bn) { return a0 < b0 + bn && b0 < a0 + an; }
+
+static void retire_runs(Pipe& P)
+{
+    for (auto& r : P.runs)
+        if (r.live && hipEventQuery(r.scan_ev) == hipSuccess) r.live = false;
+}
+
+// newest record that is still in flight, newer than run `after`, and overlaps the slots (cnt <= 0: any slots)
+static Pipe::RunRec* newest_run(Pipe& P, int s0, int cnt, unsigned long long after)
+{
+    Pipe::RunRec* best = nullptr;
+    for (auto& r : P.runs)
+        if (r.live && r.seq > after && (cnt <= 0 || ranges_overlap(s0, cnt, r.s0, r.cnt)) && (!best || r.seq > best->seq)) best = &r;
+    return best;
+}
+
+// ... and not yet ordered before the context's stream
+static Pipe::RunRec* newest_unjoined(Pipe& P, int s0, int cnt)
+{
+    if (P.joined_stream != P.ctx->stream) { // the caller switched streams: nothing is ordered before the new one
+        P.joined_stream = P.ctx->stream;
+        P.joined_seq = 0;
+    }
+    return newest_run(P, s0, cnt, P.joined_seq);
+}
+
+// make the context's stream wait for every run that is still in flight (lanes and scans; they write every board)
+static int join_scan(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    if (Pipe::RunRec* r = newest_unjoined(P, 0, 0)) {
+        CBV_HIP(ctx, hipStreamWaitEvent(ctx->stream, r->scan_ev, 0));
+        P.joined_seq = r->seq;
+    }
+    return CBV_OK;
+}
+
+// make the context's stream wait for the runs in flight that touch these slots (older scans of the same slots
+// may still be queued: the newest overlapping record covers them)
+static int join_slots(Pipe& P, int s0, int cnt)
+{
+    cbv_ctx* ctx = P.ctx;
+    retire_runs(P);
+    if (Pipe::RunRec* r = newest_unjoined(P, s0, cnt)) {
+        CBV_HIP(ctx, hipStreamWaitEvent(ctx->stream, r->scan_ev, 0));
+        // everything up to r is ordered now; records between joined_seq and r.seq that do not overlap are too
+        P.joined_seq = std::max(P.joined_seq, r->seq);
+    }
+    return CBV_OK;
+}
+
+// the kernel arguments of a board: its BoardDev entry, pointers of slot 0 (the launches add their first slot); lds = LDS
+// bytes of its HoughCircles passes (0: the squares do not fit)
+static BoardDev board_dev(const Board& q, size_t lds[2])
+{
+    const cbv_pipeline_config& c = q.cfg;
+    BoardDev T;
+    memset(&T, 0, sizeof(T));
+    memcpy(T.Minv, q.Minv, sizeof(T.Minv));
+    T.S = c.board_size;
+    T.rot180 = c.rot180;
+    // launch_warp's block shape of an S x S destination (BLOCK_SZ = 32)
+    int bh0 = 16 < T.S ? 16 : T.S;
+    const int bw0 = 1024 / bh0 < T.S ? 1024 / bh0 : T.S;
+    bh0 = 1024 / bw0 < T.S ? 1024 / bw0 : T.S;
+    T.bw0 = bw0;
+    T.bh0 = bh0;
+    T.warped = q.warped;
+    T.warped_stride = q.warped_stride;
+    T.descs = (const SquareDesc*)q.d_descs.p;
+    T.n = c.n_rois;
+    T.want_hough = c.use_hough;
+    T.masks = (const u8*)q.d_masks.p;
+    T.gray = (u8*)q.d_gray.p;
+    T.plane_total = q.plane_total;
+    T.mean = q.calibrated ? (const float*)q.d_mean.p : nullptr;
+    T.sd = q.calibrated ? (const float*)q.d_var.p + q.plane_total : nullptr;
+    T.z_thresh = (float)c.z_threshold;
+    T.stats = (cbv_sq_stats*)q.d_stats.p;
+    T.dec = (u8*)q.d_dec.p;
+    T.hough = c.use_hough ? (cbv_hough_result*)q.d_hough.p : nullptr;
+    lds[0] = lds[1] = 0;
+    if (c.use_hough) hough_board_cfgs(q.hough_cfg, T.hcfg, lds);
+    T.sp = scan_params(c, q.calibrated);
+    T.ref = (u8*)q.d_ref.p;
+    T.state = (ScanState*)q.d_state.p;
+    T.flags = (u8*)q.d_flags.p;
+    T.results = (cbv_frame_result*)q.d_results.p;
+    T.check = (const u64*)q.d_check.p; // (all-zero sets = no squares_to_check)
+    T.noise_state = (cbv_noise_state*)q.d_noise_state.p;
+    T.noise = (cbv_noise_result*)q.d_noise.p;
+    T.mirror = (cbv_frame_result*)q.h_stage;
+    T.over_src = c.use_hough ? (const u32*)q.d_hough_over.p : nullptr;
+    T.over_dst = q.over_h;
+    return T;
+}
+
+// Rebuild the boards' kernel arguments whenever a board is set up, attached, detached or calibrated.  The device table
+// and the maxima of the multi-board launches exist only with boards attached.  Nothing may be in flight: the callers
+// joined the runs.
+static int pipeline_tables(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    const int nb = (int)P.boards.size();
+    P.tab.resize(nb);
+    P.any_hough = false;
+    P.hough_lds[0] = P.hough_lds[1] = 0;
+    P.max_px = P.max_S = 0;
+    for (int k = 0; k < nb; k++) {
+        const Board& q = P.boards[k]->b;
+        size_t lds[2];
+        P.tab[k] = board_dev(q, lds);
+        if (q.cfg.use_hough) {
+            // (a single board's launchers check the layout themselves, at run time)
+            if (nb > 1 && (!lds[0] || !lds[1]))
+                return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles stage: %dx%d squares of board %d do not fit the LDS layout",
+                                q.hough_cfg.maxw, q.hough_cfg.maxh, k);
+            P.any_hough = true;
+            P.hough_lds[0] = std::max(P.hough_lds[0], lds[0]);
+            P.hough_lds[1] = std::max(P.hough_lds[1], lds[1]);
+        }
+        P.max_px = std::max(P.max_px, q.max_px);
+        P.max_S = std::max(P.max_S, q.cfg.board_size);
+    }
+    if (nb == 1) return CBV_OK;
+    RC(dev_ensure(ctx, &P.d_boards, sizeof(BoardDev) * nb));
+    CBV_HIP(ctx, hipMemcpyAsync(P.d_boards.p, P.tab.data(), sizeof(BoardDev) * nb, hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+// enhance_region: the bounding rectangle of every board's warp footprint (any board without one: the whole frame); the
+// third scratch frame set is allocated when the region first becomes usable
+static int pipeline_update_region(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    const cbv_pipeline_config& cfg = P.b0().cfg;
+    bool use = cfg.enhance_region && !P.keep_enhanced && sharpen_region_ok(cfg.enhance.sharpen_kernel);
+    PxRect u = {0, 0, 0, 0};
+    for (size_t k = 0; use && k < P.boards.size(); k++) {
+        const Board& q = P.boards[k]->b;
+        PxRect r;
+        use = warp_footprint(q.Minv, q.cfg.board_size, q.cfg.board_size, P.w, P.h, &r);
+        if (use) u = k == 0 ? r : PxRect{std::min(u.x0, r.x0), std::min(u.y0, r.y0), std::max(u.x1, r.x1), std::max(u.y1, r.y1)};
+    }
+    if (use)
+        for (int l = 0; l < P.n_lanes; l++)
+            if (!P.C[l]) CBV_HIP(ctx, hipMalloc((void**)&P.C[l], P.g.frame_stride * P.chunk + 256));
+    P.use_region = use;
+    if (use) P.region = u;
+    return CBV_OK;
+}
+
+// the per-board checks of cbv_pipeline_configure (cbv_pipeline_add_board makes the same)
+static int check_board_cfg(cbv_ctx* ctx, const cbv_pipeline_config* cfg)
+{
+    if (cfg->n_rois <= 0 || cfg->n_rois > CBV_MAX_SQUARES || cfg->board_size <= 0 || cfg->board_size > 4096)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_configure: bad board/roi configuration");
+    if (cfg->history_size < 1 || cfg->history_size > 7) return cbv_fail(ctx, CBV_ERR_ARG, "history_size must be in 1..7");
+    for (int i = 0; i < cfg->n_rois; i++) {
+        const cbv_roi& r = cfg->rois[i];
+        if (r.w <= 0 || r.h <= 0 || r.w > CBV_MAX_SQUARE_DIM || r.h > CBV_MAX_SQUARE_DIM || r.x0 < 0 || r.y0 < 0 ||
+            r.x0 + r.w > cfg->board_size || r.y0 + r.h > cfg->board_size)
+            return cbv_fail(ctx, CBV_ERR_ARG, "roi %d is invalid for a %dx%d board", i, cfg->board_size, cfg->board_size);
+    }
+    return CBV_OK;
+}
+
+// a board's part of cbv_pipeline_configure / cbv_pipeline_add_board: warped frames, square descriptors and planes, temporal
+// state, results
+static int board_setup(const Pipe& P, Board& b, const cbv_pipeline_config& cfg)
+{
+    cbv_ctx* ctx = P.ctx;
+    const int S = cfg.board_size, n = cfg.n_rois;
+    b.cfg = cfg;
+    if (!host_invert3x3(cfg.M, b.Minv)) memset(b.Minv, 0, sizeof(b.Minv));
+    b.warped_stride = ((size_t)S * S * 3 + 255) & ~(size_t)255;
+    if (b.warped) (void)hipFree(b.warped);
+    b.warped = nullptr;
+    CBV_HIP(ctx, hipMalloc((void**)&b.warped, b.warped_stride * P.max_frames));
+    // squares
+    int ws[CBV_MAX_SQUARES], hs[CBV_MAX_SQUARES];
+    for (int i = 0; i < n; i++) {
+        ws[i] = cfg.rois[i].w;
+        hs[i] = cfg.rois[i].h;
+    }
+    std::vector<u8> masks;
+    const size_t off = square_table(ws, hs, n, &b.descs, &masks);
+    b.max_px = 0;
+    for (int i = 0; i < n; i++) {
+        SquareDesc& d = b.descs[i];
+        d.cn = 3;
+        d.stride = S * 3;
+        d.src_off = cfg.rois[i].y0 * S * 3 + cfg.rois[i].x0 * 3;
+        b.max_px = std::max(b.max_px, d.w * d.h);
+    }
+    b.plane_total = off;
+    RC(dev_ensure(ctx, &b.d_descs, sizeof(SquareDesc) * n));
+    RC(dev_ensure(ctx, &b.d_masks, off));
+    RC(dev_ensure(ctx, &b.d_gray, off * P.max_frames));
+    RC(dev_ensure(ctx, &b.d_stats, sizeof(cbv_sq_stats) * n * P.max_frames));
+    RC(dev_ensure(ctx, &b.d_ref, off));
+    RC(dev_ensure(ctx, &b.d_mean, off * 4));
+    RC(dev_ensure(ctx, &b.d_var, off * 8)); // variance plane, then its square root
+    b.calibrated = false;
+    RC(dev_ensure(ctx, &b.d_state, sizeof(ScanState) * n));
+    RC(dev_ensure(ctx, &b.d_results, sizeof(cbv_frame_result) * P.max_frames));
+    const size_t want = sizeof(cbv_frame_result) * (size_t)P.max_frames + 16; // (max_frames is fixed: allocated once)
+    if (!b.h_stage) CBV_HIP(ctx, hipHostMalloc((void**)&b.h_stage, want, hipHostMallocDefault));
+    memset(b.h_stage, 0, want);
+    b.over_h = (u32*)(b.h_stage + ((sizeof(cbv_frame_result) * (size_t)P.max_frames + 7) & ~(size_t)7));
+    b.slot_mirrored.assign((size_t)P.max_frames, 0);
+    RC(dev_ensure(ctx, &b.d_flags, (size_t)CBV_MAX_SQUARES * P.max_frames));
+    RC(dev_ensure(ctx, &b.d_dec, (size_t)CBV_MAX_SQUARES * P.max_frames));
+    if (cfg.use_hough) {
+        RC(hough_cfg(ctx, &cfg.hough, b.descs, &b.hough_cfg));
+        RC(dev_ensure(ctx, &b.d_hough, sizeof(cbv_hough_result) * CBV_MAX_SQUARES * P.max_frames));
+        RC(dev_ensure(ctx, &b.d_hough_over, 256));
+        CBV_HIP(ctx, hipMemset(b.d_hough_over.p, 0, 256));
+        b.hough_cfg.overflow_count = (u32*)b.d_hough_over.p;
+    }
+    RC(dev_ensure(ctx, &b.d_noise, sizeof(cbv_noise_result) * P.max_frames));
+    RC(dev_ensure(ctx, &b.d_noise_state, sizeof(cbv_noise_state)));
+    RC(dev_ensure(ctx, &b.d_check, sizeof(u64) * P.max_frames));
+    CBV_HIP(ctx, hipMemset(b.d_check.p, 0, sizeof(u64) * P.max_frames));
+    b.has_check = false;
+    CBV_HIP(ctx, hipMemset(b.d_noise_state.p, 0, sizeof(cbv_noise_state)));
+    CBV_HIP(ctx, hipMemcpy(b.d_descs.p, b.descs.data(), sizeof(SquareDesc) * n, hipMemcpyHostToDevice));
+    CBV_HIP(ctx, hipMemcpy(b.d_masks.p, masks.data(), off, hipMemcpyHostToDevice));
+    CBV_HIP(ctx, hipMemset(b.d_state.p, 0, sizeof(ScanState) * n));
+    // plane padding (planes are rounded to 16 B) must read as zero in every frame: k_scan compares whole vectors
+    CBV_HIP(ctx, hipMemset(b.d_gray.p, 0, off * P.max_frames));
+    CBV_HIP(ctx, hipMemset(b.d_ref.p, 0, off));
+    return CBV_OK;
+}
+
+// free a board and its handle (board 0's handle too: the pipeline's shared part is freed by its owner)
+static void board_free(cbv_pipeline* p)
+{
+    Board& b = p->b;
+    if (b.h_stage) (void)hipHostFree(b.h_stage);
+    if (b.warped) (void)hipFree(b.warped);
+    DevBuf* bufs[] = {&b.d_descs, &b.d_masks, &b.d_gray, &b.d_stats, &b.d_ref, &b.d_state, &b.d_results, &b.d_flags, &b.d_dec, &b.d_mean,
+                      &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over};
+    for (auto d : bufs) dev_free(d);
+    delete p;
+}
+
+extern "C" int cbv_pipeline_create(cbv_ctx* ctx, int w, int h, int max_frames, cbv_pipeline** out)
+{
+    if (!ctx || !out || w <= 0 || h <= 0 || max_frames <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_create: bad arguments");
+    CBV_ENTER(ctx);
+    Pipe* P = new Pipe();
+    P->ctx = ctx;
+    P->w = w;
+    P->h = h;
+    P->max_frames = max_frames;
+    P->g = tight_geom(w, h);
+    hipError_t e = hipMalloc((void**)&P->frames, P->g.frame_stride * max_frames + 256);
+    if (e != hipSuccess) {
+        const size_t want = P->g.frame_stride * max_frames;
+        delete P;
+        return cbv_fail(ctx, CBV_ERR_HIP, "hipMalloc of %zu bytes for the frame ring failed: %s", want, hipGetErrorString(e));
+    }
+    P->boards.push_back(new cbv_pipeline{P, Board()});
+    *out = P->boards[0];
+    return CBV_OK;
+}
+
+extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
+{
+    if (!p) return;
+    Pipe* P = p->pipe;
+    cbv_ctx* ctx = P->ctx;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    if (P->boards.size() > 1) (void)join_scan(*P); // runs in flight (lanes, scan) write every board
+    (void)hipStreamSynchronize(ctx->stream);
+    if (attached(p)) { // detach: the other boards and board 0 go on as they were
+        P->boards.erase(std::find(P->boards.begin(), P->boards.end(), p));
+        (void)pipeline_tables(*P);
+        (void)pipeline_update_region(*P);
+        board_free(p);
+        return;
+    }
+    for (int l = 0; l < Pipe::MAX_LANES; l++) {
+        if (P->lane_stream[l]) (void)hipStreamSynchronize(P->lane_stream[l]);
+        if (P->A[l]) (void)hipFree(P->A[l]);
+        if (P->B[l]) (void)hipFree(P->B[l]);
+        if (P->C[l]) (void)hipFree(P->C[l]);
+        dev_free(&P->lane_small[l]);
+        dev_free(&P->lane_work[l]);
+        if (P->lane_done[l]) (void)hipEventDestroy(P->lane_done[l]);
+    }
+    if (P->start_ev) (void)hipEventDestroy(P->start_ev);
+    if (P->scan_stream) (void)hipStreamSynchronize(P->scan_stream); // (the worker streams belong to the context)
+    for (auto& r : P->runs) {
+        (void)hipEventDestroy(r.lanes_ev);
+        (void)hipEventDestroy(r.scan_ev);
+        dev_free(&r.retry);
+    }
+    if (P->main_done) (void)hipEventDestroy(P->main_done);
+    if (P->copy_stream) (void)hipStreamSynchronize(P->copy_stream);
+    for (auto& c : P->copies) (void)hipEventDestroy(c.ev);
+    if (P->host_ring) (void)hipHostFree(P->host_ring);
+    if (P->frames) (void)hipFree(P->frames);
+    if (P->enhanced) (void)hipFree(P->enhanced);
+    dev_free(&P->d_synth);
+    dev_free(&P->d_boards);
+    for (cbv_pipeline* q : P->boards) board_free(q); // board 0 (p) included
+    delete P;
+}
+
+extern "C" void* cbv_pipeline_frames_dev(cbv_pipeline* p) { return p && !attached(p) ? p->pipe->frames : nullptr; }
+
+extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* cfg)
+{
+    if (!p || !cfg) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: a board handle is configured by cbv_pipeline_add_board");
+    if (P.boards.size() > 1) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: boards are attached (destroy them first)");
+    RC(check_board_cfg(ctx, cfg));
+    RC(check_params(ctx, &cfg->enhance));
+    // every argument check that needs no state is done; from here on a failure leaves the pipeline UNconfigured
+    // (run / results / ... return CBV_ERR_STATE) instead of half reconfigured
+    P.configured = false;
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    P.keep_enhanced = cfg->keep_enhanced != 0;
+    int chunk = cfg->chunk;
+    if (chunk <= 0) chunk = 32;
+    if (chunk > P.max_frames) chunk = P.max_frames;
+    P.chunk = chunk;
+    // (re)allocate
+    int lanes = cfg->lanes <= 0 ? 2 : cfg->lanes;
+    if (lanes > Pipe::MAX_LANES) lanes = Pipe::MAX_LANES;
+    if ((P.max_frames + chunk - 1) / chunk < lanes) lanes = (P.max_frames + chunk - 1) / chunk;
+    P.n_lanes = lanes;
+    for (int l = 0; l < Pipe::MAX_LANES; l++) {
+        if (P.A[l]) (void)hipFree(P.A[l]);
+        if (P.B[l]) (void)hipFree(P.B[l]);
+        if (P.C[l]) (void)hipFree(P.C[l]);
+        P.A[l] = P.B[l] = P.C[l] = nullptr;
+    }
+    if (P.enhanced) (void)hipFree(P.enhanced);
+    P.enhanced = nullptr;
+    if (!P.start_ev) CBV_HIP(ctx, hipEventCreateWithFlags(&P.start_ev, hipEventDisableTiming));
+    for (int l = 0; l < lanes; l++) {
+        CBV_HIP(ctx, hipMalloc((void**)&P.A[l], P.g.frame_stride * chunk + 256));
+        CBV_HIP(ctx, hipMalloc((void**)&P.B[l], P.g.frame_stride * chunk + 256));
+        SmallLayout SL;
+        RC(small_layout(ctx, &P.lane_small[l], cfg->enhance.tiles_x * cfg->enhance.tiles_y, chunk, &SL, cfg->enhance.tiles_x, cfg->enhance.tiles_y));
+        RC(dev_ensure(ctx, &P.lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * chunk)));
+        if (l > 0) RC(ctx_worker_stream(ctx, &ctx->lane_streams[l], &P.lane_stream[l]));
+        if (!P.lane_done[l]) CBV_HIP(ctx, hipEventCreateWithFlags(&P.lane_done[l], hipEventDisableTiming));
+    }
+    if (P.keep_enhanced) CBV_HIP(ctx, hipMalloc((void**)&P.enhanced, P.g.frame_stride * P.max_frames + 256));
+    RC(board_setup(P, p->b, *cfg));
+    // region-limited enhancement: the source footprint of the S x S warp (warp_footprint)
+    RC(pipeline_update_region(P));
+    RC(pipeline_tables(P));
+    P.configured = true;
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_add_board(cbv_pipeline* p, const cbv_board_config* bc, cbv_pipeline** out)
+{
+    if (!p || !bc || !out) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_add_board: bad arguments");
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_add_board: the parent is itself a board handle");
+    if (!P.configured) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_add_board: the parent is not configured");
+    if ((int)P.boards.size() >= CBV_MAX_BOARDS)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_add_board: a pipeline holds at most %d boards", CBV_MAX_BOARDS);
+    if (P.max_frames >= (1 << (MB_BOARD_SHIFT - 8)))
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_add_board: at most %d frames in a pipeline with boards", (1 << (MB_BOARD_SHIFT - 8)) - 1);
+    // the board's configuration = the pipeline's with the board's subset replaced
+    cbv_pipeline_config cfg = P.b0().cfg;
+    memcpy(cfg.M, bc->M, sizeof(cfg.M));
+    cfg.board_size = bc->board_size;
+    cfg.rot180 = bc->rot180;
+    cfg.n_rois = bc->n_rois;
+    memcpy(cfg.rois, bc->rois, sizeof(cfg.rois));
+    cfg.history_size = bc->history_size;
+    cfg.min_presence = bc->min_presence;
+    cfg.change_threshold = bc->change_threshold;
+    cfg.z_threshold = bc->z_threshold;
+    cfg.initial_variance = bc->initial_variance;
+    cfg.use_hough = bc->use_hough;
+    cfg.hough = bc->hough;
+    RC(check_board_cfg(ctx, &cfg));
+    if (cfg.use_hough) RC(hough_params_check(ctx, &cfg.hough));
+    RC(join_scan(P));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // the lanes' worklists hold every board's items (grown only: a larger list serves fewer boards as well)
+    for (int l = 0; l < P.n_lanes; l++)
+        RC(dev_ensure(ctx, &P.lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * P.chunk * (P.boards.size() + 1))));
+    cbv_pipeline* b = new cbv_pipeline{&P, Board()};
+    int rc = board_setup(P, b->b, cfg);
+    if (rc == CBV_OK) {
+        P.boards.push_back(b);
+        rc = pipeline_tables(P);
+        if (rc == CBV_OK) rc = pipeline_update_region(P);
+        if (rc != CBV_OK) {
+            P.boards.pop_back();
+            const std::string err = ctx->err;
+            (void)pipeline_tables(P);
+            (void)pipeline_update_region(P);
+            ctx->err = err;
+        }
+    }
+    if (rc != CBV_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        board_free(b);
+        return rc;
+    }
+    *out = b;
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_reset_state(cbv_pipeline* p)
+{
+    if (!p || !p->pipe->configured) return CBV_ERR_STATE;
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    CBV_HIP(ctx, hipMemsetAsync(B.d_state.p, 0, sizeof(ScanState) * B.cfg.n_rois, ctx->stream));
+    CBV_HIP(ctx, hipMemsetAsync(B.d_noise_state.p, 0, sizeof(cbv_noise_state), ctx->stream));
+    if (B.d_hough_over.p) {
+        CBV_HIP(ctx, hipMemsetAsync(B.d_hough_over.p, 0, 4, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the runs that could still write the mirror's copy are behind us
+        *B.over_h = 0;
+    }
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_calibrate(cbv_pipeline* p, int slot)
+{
+    if (!p || !p->pipe->configured) return CBV_ERR_STATE;
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    if (slot < 0 || slot >= P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_calibrate: bad slot");
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    RC(launch_squares_calibrate(ctx, (const SquareDesc*)B.d_descs.p, B.cfg.n_rois, (const u8*)B.d_gray.p + B.plane_total * slot,
+                                (float*)B.d_mean.p, (float*)B.d_var.p, (float*)B.d_var.p + B.plane_total, (float)B.cfg.initial_variance, nullptr));
+    B.calibrated = true;
+    return pipeline_tables(P); // the board's statistics read its model from now on
+}
+
+extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int reset_noise)
+{
+    if (!p || !p->pipe->configured) return CBV_ERR_STATE;
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    if (slot < 0 || slot >= P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_update_references: bad slot");
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    RC(launch_scan_update_refs(ctx, (const SquareDesc*)B.d_descs.p, B.cfg.n_rois, (const u8*)B.d_gray.p + B.plane_total * slot,
+                               (u8*)B.d_ref.p, (ScanState*)B.d_state.p));
+    if (reset_noise) CBV_HIP(ctx, hipMemsetAsync(B.d_noise_state.p, 0, sizeof(cbv_noise_state), ctx->stream)); // NoiseHandler.reset()
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr, int stride)
+{
+    if (p && attached(p)) return cbv_fail(p->pipe->ctx, CBV_ERR_STATE, "cbv_pipeline_upload: frames go to the parent of a board");
+    if (!p || !bgr || slot < 0 || slot >= p->pipe->max_frames || stride < p->pipe->w * 3) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    RC(rows_h2d(ctx, P.frames + P.g.frame_stride * slot, bgr, stride, P.w * 3, P.h));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)
+{
+    if (!p) return nullptr;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    if (attached(p)) {
+        cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_host_ring: frames go to the parent of a board");
+        return nullptr;
+    }
+    if (!P.host_ring) {
+        if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
+        if (hipHostMalloc((void**)&P.host_ring, P.g.frame_stride * P.max_frames, hipHostMallocDefault) != hipSuccess) {
+            cbv_fail(ctx, CBV_ERR_HIP, "pinned host ring of %zu bytes could not be allocated", P.g.frame_stride * P.max_frames);
+            P.host_ring = nullptr;
+        }
+    }
+    return P.host_ring;
+}
+
+extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
+{
+    if (!p) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_submit: frames go to the parent of a board");
+    if (slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_submit: bad slot range");
+    if (!P.host_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_submit: cbv_pipeline_host_ring() was never called");
+    CBV_ENTER(ctx);
+    if (!P.copy_stream) RC(ctx_worker_stream(ctx, &ctx->copy_stream, &P.copy_stream));
+    // do not overwrite device slots a run that is still in flight reads: ANY such run, not only the last one
+    retire_runs(P);
+    if (Pipe::RunRec* r = newest_run(P, slot0, count, 0)) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, r->one_event ? r->scan_ev : r->lanes_ev, 0));
+    CBV_HIP(ctx, hipMemcpyAsync(P.frames + P.g.frame_stride * slot0, P.host_ring + P.g.frame_stride * slot0,
+                                P.g.frame_stride * count, hipMemcpyHostToDevice, P.copy_stream));
+    Pipe::CopyRec* rec = nullptr;
+    for (auto& c : P.copies)
+        if (!c.pending) {
+            rec = &c;
+            break;
+        }
+    if (!rec) {
+        Pipe::CopyRec c{0, 0, nullptr, false};
+        CBV_HIP(ctx, hipEventCreateWithFlags(&c.ev, hipEventDisableTiming));
+        P.copies.push_back(c);
+        rec = &P.copies.back();
+    }
+    rec->s0 = slot0;
+    rec->cnt = count;
+    rec->pending = true;
+    CBV_HIP(ctx, hipEventRecord(rec->ev, P.copy_stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_wait_submitted(cbv_pipeline* p)
+{
+    if (!p) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_synth(cbv_pipeline* p, int slot0, int count, const uint64_t* seeds, const double* Hinv9,
+                                  const uint8_t* boards, const cbv_scene* scene)
+{
+    if (p && attached(p)) return cbv_fail(p->pipe->ctx, CBV_ERR_STATE, "cbv_pipeline_synth: frames go to the parent of a board");
+    if (!p || !seeds || !Hinv9 || !boards || !scene || slot0 < 0 || count <= 0 || slot0 + count > p->pipe->max_frames) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    size_t o_seeds = 0, o_h = (size_t)count * 8, o_b = o_h + 72, o_s = (o_b + (size_t)count * 64 + 15) & ~(size_t)15;
+    size_t total = o_s + sizeof(cbv_scene);
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RC(dev_ensure(ctx, &P.d_synth, total));
+    std::vector<u8> host(total, 0);
+    memcpy(host.data() + o_seeds, seeds, (size_t)count * 8);
+    memcpy(host.data() + o_h, Hinv9, 72);
+    memcpy(host.data() + o_b, boards, (size_t)count * 64);
+    memcpy(host.data() + o_s, scene, sizeof(cbv_scene));
+    CBV_HIP(ctx, hipMemcpy(P.d_synth.p, host.data(), total, hipMemcpyHostToDevice));
+    u8* base = (u8*)P.d_synth.p;
+    RC(launch_synth(ctx, P.frames + P.g.frame_stride * slot0, P.g, (const u64*)(base + o_seeds), (const double*)(base + o_h),
+                    base + o_b, (const cbv_scene*)(base + o_s), count));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+// the per-board stages of a chunk of b frames from slot s0 (warp, square statistics, HoughCircles' first pass): with boards
+// attached one launch each for all of them, otherwise the single-board launches with board 0's arguments
+static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, int b, u32* work, u32* retry0, u32* retry, int retry_base)
+{
+    cbv_ctx* ctx = P.ctx;
+    if (P.boards.size() > 1) {
+        const BoardDev* tab = (const BoardDev*)P.d_boards.p;
+        const int nb = (int)P.boards.size();
+        RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
+        RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
+        if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, P.hough_lds[0], retry, retry_base, 0));
+        return CBV_OK;
+    }
+    const BoardDev& T = P.tab[0];
+    u8* wdst = T.warped + T.warped_stride * s0;
+    u8* gray = T.gray + T.plane_total * s0;
+    u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
+    cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
+    RC(launch_warp(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, norm, b, work, retry0));
+    RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
+                                 T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));
+    if (T.want_hough) RC(launch_hough(ctx, T.descs, T.n, gray, T.plane_total, P.b0().hough_cfg, hres, dec, work, b, retry, retry_base));
+    return CBV_OK;
+}
+
+// mark slots [s0, s0 + cnt) of every board as held (or not) by the pinned result mirror
+static void mark_mirrored(Pipe& P, int s0, int cnt, bool held)
+{
+    for (cbv_pipeline* q : P.boards) std::fill(q->b.slot_mirrored.begin() + s0, q->b.slot_mirrored.begin() + s0 + cnt, held ? 1 : 0);
+}
+
+// second half of cbv_pipeline_run: join the lanes on the scan's stream, HoughCircles second pass, temporal scan, run record
+static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, bool inline_scan, const bool* lane_used, hipStream_t main_stream)
+{
+    cbv_ctx* ctx = P.ctx;
+    if (!P.scan_stream) {
+        RC(ctx_worker_stream(ctx, &ctx->scan_stream, &P.scan_stream));
+        CBV_HIP(ctx, hipEventCreateWithFlags(&P.main_done, hipEventDisableTiming));
+    }
+    hipStream_t scan_on = inline_scan ? main_stream : P.scan_stream;
+    if (!inline_scan) {
+        CBV_HIP(ctx, hipEventRecord(P.main_done, main_stream));
+        CBV_HIP(ctx, hipStreamWaitEvent(scan_on, P.main_done, 0));
+    }
+    // every forked lane is joined, in the inline case too (chunk = 1 puts the second frame of a two-frame run on lane 1)
+    for (int l = 1; l < P.n_lanes; l++)
+        if (lane_used[l]) {
+            CBV_HIP(ctx, hipEventRecord(P.lane_done[l], P.lane_stream[l]));
+            CBV_HIP(ctx, hipStreamWaitEvent(scan_on, P.lane_done[l], 0));
+        }
+    // every lane has read its frames: a later cbv_pipeline_submit may overwrite these slots after this event
+    rec->one_event = inline_scan;
+    if (!inline_scan) CBV_HIP(ctx, hipEventRecord(rec->lanes_ev, scan_on));
+    ctx->stream = scan_on;
+    struct Restore {
+        cbv_ctx* c;
+        hipStream_t s;
+        ~Restore() { c->stream = s; }
+    } restore{ctx, main_stream};
+    // A short run (the live-camera case) writes its records to the pinned mirror too: reading them back is then a wait and a
+    // host copy instead of two more launches.  Not the long runs: their records would cross PCIe as thousands of 8-byte
+    // writes inside the scan stream's critical path (512-frame steps: -0.5 % frames/s, alternating A/B runs); they are
+    // fetched with one copy when asked for.
+    const bool mirrored = count <= 4;
+    if (P.boards.size() > 1) { // every board's second pass, scan, packing and NoiseHandler: one launch each
+        const BoardDev* tab = (const BoardDev*)P.d_boards.p;
+        const int nb = (int)P.boards.size();
+        if (P.any_hough)
+            RC(launch_hough_mb(ctx, tab, nb, slot0, (const u32*)rec->retry.p, CBV_MAX_SQUARES * nb * count, P.hough_lds[1], nullptr, 0, 1));
+        RC(launch_scan_mb(ctx, tab, nb, slot0, count, mirrored ? 1 : 0));
+    } else {
+        const BoardDev& T = P.tab[0];
+        const u8* gray = T.gray + T.plane_total * slot0;
+        u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * slot0;
+        if (T.want_hough) // squares whose first HoughCircles pass overflowed (normally none), before the scan reads the decisions
+            RC(launch_hough_second(ctx, T.descs, T.n, gray, T.plane_total, P.b0().hough_cfg, T.hough + (size_t)CBV_MAX_SQUARES * slot0, dec,
+                                   (const u32*)rec->retry.p, T.n * count));
+        ResultMirror mir;
+        if (mirrored) {
+            mir.records = T.mirror + slot0;
+            mir.over_src = T.over_src;
+            mir.over_dst = T.over_dst;
+        }
+        // + NoiseHandler on the frames' visual_changes sets (game_session.py:165)
+        RC(launch_scan(ctx, T.descs, T.sp, gray, T.plane_total, dec, T.ref, T.state, T.flags + (size_t)CBV_MAX_SQUARES * slot0,
+                       T.results + slot0, count, P.b0().has_check ? T.check + slot0 : nullptr, T.noise_state, T.noise + slot0, mir));
+    }
+    CBV_HIP(ctx, hipEventRecord(rec->scan_ev, scan_on));
+    mark_mirrored(P, slot0, count, mirrored);
+    rec->s0 = slot0;
+    rec->cnt = count;
+    rec->seq = ++P.run_seq;
+    rec->live = true;
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
+{
+    if (!p || !p->pipe->configured) return CBV_ERR_STATE;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: a board is run by its parent");
+    if (slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_run: bad slot range");
+    CBV_ENTER(ctx);
+    const cbv_enhance_params& enh = P.b0().cfg.enhance;
+    // Lane 0 is the context's stream; lanes 1.. are worker streams forked from it and joined before
+    // the temporal scan (which needs every frame's statistics, in order).
+    hipStream_t main_stream = ctx->stream;
+    // A run of one or two frames (the live-camera case) is latency, not throughput: its scan is a few microseconds, less
+    // than the hop to the scan stream and back, so everything stays on the caller's stream, behind every run in flight
+    // (the scans' state is sequential over runs).
+    const bool inline_scan = count <= 2;
+    const int chunks = (count + P.chunk - 1) / P.chunk;
+    // Chunks go round the lanes, and the round continues from run to run and from pipeline to pipeline of this context
+    // (ctx->lane_rr): K camera streams whose runs are one chunk each would otherwise all pile on lane 0 and lose the
+    // overlap of the lanes.  Short (latency) runs start on the caller's stream.
+    const int lane_base = inline_scan ? 0 : ctx->lane_rr % P.n_lanes;
+    if (!inline_scan) ctx->lane_rr = (ctx->lane_rr + chunks) % (12 * 1024);
+    bool lane_used[Pipe::MAX_LANES] = {false, false, false, false};
+    for (int c = 0; c < chunks && c < P.n_lanes; c++) lane_used[(lane_base + c) % P.n_lanes] = true;
+    if (inline_scan) {
+        retire_runs(P);
+        RC(join_scan(P));
+    } else RC(join_slots(P, slot0, count)); // scans in flight that still read these slots' planes, however many runs back
+    // until this run's scan is enqueued, the results of its slots come from the device (a failed run leaves them so)
+    mark_mirrored(P, slot0, count, false);
+    Pipe::RunRec* rec = nullptr; // the record (and second-pass list) of this run
+    for (auto& r : P.runs)
+        if (!r.live) {
+            rec = &r;
+            break;
+        }
+    if (!rec) {
+        Pipe::RunRec r{0, 0, 0, nullptr, nullptr, false, false, DevBuf()};
+        CBV_HIP(ctx, hipEventCreateWithFlags(&r.lanes_ev, hipEventDisableTiming));
+        CBV_HIP(ctx, hipEventCreateWithFlags(&r.scan_ev, hipEventDisableTiming));
+        P.runs.push_back(r);
+        rec = &P.runs.back();
+    }
+    // the second-pass list's counter: zeroed before the lanes fork from this stream, or, when the run is ONE chunk, by that
+    // chunk's k_warp (a memset is a launch of its own, ~13 us with its bubble in front of a 150 us chain)
+    const bool retry_zero_in_warp = chunks == 1;
+    if (P.any_hough) {
+        RC(dev_ensure(ctx, &rec->retry, sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * P.max_frames * P.boards.size())));
+        if (!retry_zero_in_warp) CBV_HIP(ctx, hipMemsetAsync(rec->retry.p, 0, sizeof(u32), main_stream));
+    }
+    for (auto& c : P.copies) // ingest copies of these slots must have landed
+        if (c.pending && ranges_overlap(slot0, count, c.s0, c.cnt)) {
+            CBV_HIP(ctx, hipStreamWaitEvent(main_stream, c.ev, 0));
+            c.pending = false;
+        }
+    bool forked = false;
+    for (int l = 1; l < P.n_lanes; l++) forked = forked || lane_used[l];
+    if (forked) {
+        CBV_HIP(ctx, hipEventRecord(P.start_ev, main_stream));
+        for (int l = 1; l < P.n_lanes; l++)
+            if (lane_used[l]) CBV_HIP(ctx, hipStreamWaitEvent(P.lane_stream[l], P.start_ev, 0));
+    }
+    int ci = 0, rc_all = CBV_OK;
+    for (int s0 = slot0; s0 < slot0 + count && rc_all == CBV_OK; s0 += P.chunk, ci++) {
+        const int lane = (lane_base + ci) % P.n_lanes;
+        ctx->stream = lane == 0 ? main_stream : P.lane_stream[lane];
+        SmallLayout SL;
+        rc_all = small_layout(ctx, &P.lane_small[lane], enh.tiles_x * enh.tiles_y, P.chunk, &SL, enh.tiles_x, enh.tiles_y);
+        if (rc_all) break;
+        const int b = std::min(P.chunk, slot0 + count - s0);
+        const u8* src = P.frames + P.g.frame_stride * s0;
+        u8* res = nullptr;
+        NormSrc norm;
+        rc_all = enhance_dev(ctx, src, P.A[lane], P.B[lane], P.g, &enh, SL, b, !P.keep_enhanced, &res, &norm,
+                             P.use_region ? &P.region : nullptr, P.C[lane]);
+        if (rc_all) break;
+        u32* work = P.any_hough ? (u32*)P.lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
+        u32* retry0 = P.any_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
+        if (P.keep_enhanced) {
+            if (hipMemcpyAsync(P.enhanced + P.g.frame_stride * s0, res, P.g.frame_stride * b, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+                rc_all = cbv_fail(ctx, CBV_ERR_HIP, "copy of the enhanced frames failed");
+                break;
+            }
+        }
+        rc_all = pipeline_chunk_boards(P, res, P.keep_enhanced ? NormSrc() : norm, s0, b, work, retry0, (u32*)rec->retry.p, s0 - slot0);
+    }
+    ctx->stream = main_stream;
+    // A failure after lanes were forked: whatever they already enqueued on these slots and scratch buffers must not outlive
+    // the call unordered (no RunRec goes live for a failed run), whether a lane's launch failed or the join / scan below did.
+    auto drain = [&](int rc) {
+        ctx->stream = main_stream;
+        for (int l = 1; l < P.n_lanes; l++)
+            if (lane_used[l]) (void)hipStreamSynchronize(P.lane_stream[l]);
+        if (P.scan_stream) (void)hipStreamSynchronize(P.scan_stream);
+        (void)hipStreamSynchronize(main_stream);
+        return rc;
+    };
+    if (rc_all) return drain(rc_all);
+    const int rc_tail = pipeline_run_tail(P, rec, slot0, count, inline_scan, lane_used, main_stream);
+    return rc_tail == CBV_OK ? CBV_OK : drain(rc_tail);
+}
+
+extern "C" int cbv_pipeline_set_check_squares(cbv_pipeline* p, int slot0, int count, const uint64_t* roi_masks)
+{
+    if (!p || !p->pipe->configured || slot0 < 0 || count <= 0 || slot0 + count > p->pipe->max_frames) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // the last run's scan may still read the masks
+    if (roi_masks) {
+        CBV_HIP(ctx, hipMemcpyAsync((u64*)B.d_check.p + slot0, roi_masks, sizeof(u64) * count, hipMemcpyHostToDevice, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the caller's buffer may go away
+        B.has_check = true;
+    } else CBV_HIP(ctx, hipMemsetAsync((u64*)B.d_check.p + slot0, 0, sizeof(u64) * count, ctx->stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_results(cbv_pipeline* p, int slot0, int count, cbv_frame_result* out)
+{
+    if (!p || !out || slot0 < 0 || count <= 0 || slot0 + count > p->pipe->max_frames) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    if (!P.configured || !B.h_stage) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_results: the pipeline is not configured");
+    // short runs left their records in pinned host memory (ResultMirror): wait for the runs, copy on the host; the others
+    // are fetched into the same place first (through pinned memory in any case: a copy into the caller's pageable buffer
+    // would be staged by the runtime, one blocking copy at a time)
+    const size_t bytes = sizeof(cbv_frame_result) * (size_t)count;
+    bool have = true;
+    for (int t = 0; t < count; t++) have = have && B.slot_mirrored[(size_t)slot0 + t];
+    if (!have) {
+        CBV_HIP(ctx, hipMemcpyAsync((cbv_frame_result*)B.h_stage + slot0, (cbv_frame_result*)B.d_results.p + slot0, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (B.cfg.use_hough && B.d_hough_over.p) CBV_HIP(ctx, hipMemcpyAsync(B.over_h, B.d_hough_over.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (!have)
+        for (int t = 0; t < count; t++) B.slot_mirrored[(size_t)slot0 + t] = 1;
+    memcpy(out, (const cbv_frame_result*)B.h_stage + slot0, bytes);
+    const u32 over = *B.over_h;
+    if (over) {
+        // A truncated candidate list may change has_piece: never hand that over as if it were HoughCircles' answer.  The
+        // counter is cleared on read, so the error is reported ONCE, by the first results call after the runs it
+        // happened in, and later frames are not poisoned; `out` is filled and valid except for the flagged squares.
+        CBV_HIP(ctx, hipMemsetAsync(B.d_hough_over.p, 0, 4, ctx->stream));
+        *B.over_h = 0; // (nothing is in flight: the next run's last kernel writes the word again)
+        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles: the candidate list overflowed even the second pass on %u square(s) since the "
+                        "previous cbv_pipeline_results; those occupancy bits are not HoughCircles' (cbv_pipeline_hough flags name the squares)", over);
+    }
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_noise_results(cbv_pipeline* p, int slot0, int count, cbv_noise_result* out)
+{
+    if (!p || !out || !p->pipe->configured || slot0 < 0 || count <= 0 || slot0 + count > p->pipe->max_frames) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    CBV_HIP(ctx, hipMemcpyAsync(out, (cbv_noise_result*)p->b.d_noise.p + slot0, sizeof(cbv_noise_result) * count, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8_t* out)
+{
+    if (!p || !out || slot < 0 || slot >= p->pipe->max_frames) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    const Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    const u8* src;
+    size_t bytes;
+    if (attached(p) && which != 2) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: a board holds only its warped frames (which = 2)");
+    if (which == 0) {
+        src = P.frames + P.g.frame_stride * slot;
+        bytes = (size_t)P.w * P.h * 3;
+    } else if (which == 1) {
+        if (!P.enhanced) return cbv_fail(ctx, CBV_ERR_STATE, "enhanced frames are not kept (configure with keep_enhanced = 1)");
+        src = P.enhanced + P.g.frame_stride * slot;
+        bytes = (size_t)P.w * P.h * 3;
+    } else if (which == 2) {
+        if (!B.warped) return cbv_fail(ctx, CBV_ERR_STATE, "pipeline not configured");
+        src = B.warped + B.warped_stride * slot;
+        bytes = (size_t)B.cfg.board_size * B.cfg.board_size * 3;
+    } else
+        return cbv_fail(ctx, CBV_ERR_ARG, "bad buffer selector %d", which);
+    CBV_HIP(ctx, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out)
+{
+    if (!p || !out || slot < 0 || slot >= p->pipe->max_frames) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (!P.configured || !p->b.cfg.use_hough) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_hough: the HoughCircles stage is not configured");
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    CBV_HIP(ctx, hipMemcpyAsync(out, (const cbv_hough_result*)p->b.d_hough.p + (size_t)CBV_MAX_SQUARES * slot,
+                                sizeof(cbv_hough_result) * CBV_MAX_SQUARES, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats* out)
+{
+    if (!p || !out || !p->pipe->configured || slot < 0 || slot >= p->pipe->max_frames) return CBV_ERR_ARG;
+    Pipe& P = *p->pipe;
+    const Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    CBV_HIP(ctx, hipMemcpyAsync(out, (cbv_sq_stats*)B.d_stats.p + (size_t)B.cfg.n_rois * slot, sizeof(cbv_sq_stats) * B.cfg.n_rois,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}

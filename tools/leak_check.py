@@ -1,5 +1,5 @@
-"""Create / configure / run / close pipelines and detector objects in a loop and watch the device's free memory and the
-process's RSS: neither may creep.  One-off (GPU box)."""
+"""Create / configure / run / close pipelines (with boards attached and detached in part of the iterations) and detector
+objects in a loop and watch the device's free memory and the process's RSS: neither may creep.  One-off (GPU box)."""
 import os
 import resource
 import sys
@@ -26,10 +26,21 @@ log = []
 for it in range(n):
     p = BoardPipeline(w, h, 16)
     p.configure(pts, profile=S.SHIPPED_PROFILE, chunk=4, lanes=1 + it % 3, enhance_region=bool(it % 2), keep_enhanced=(it % 5 == 0), **S.SHIPPED_DETECTOR)
+    # every other iteration attaches one or two boards (one per half of the frame): the last one is detached while the
+    # pipeline goes on, any other is freed with the pipeline or before it is reconfigured
+    boards = [p.add_board(S.scaled_corners(w // 2, h) + np.float32([c * (w // 2), 0])) for c in range(1 + it // 2 % 2)] if it % 2 else []
     p.synth(0, 16, scene="dim")
     p.run(0, 16)
     p.results(0, 16)
+    for b in boards:
+        b.results(0, 16)
+    if boards:
+        boards.pop().close()
+        p.run(0, 4)
+        p.results(0, 4)
     if it % 3 == 0:
+        for b in boards:  # configure refuses a pipeline with boards attached
+            b.close()
         p.configure(pts, profile={}, chunk=8)  # reconfigure in place
         p.run(0, 8)
         p.results(0, 8)
