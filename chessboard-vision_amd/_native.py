@@ -164,8 +164,16 @@ class NoiseDevState(C.Structure):
                 ("lifted", C.c_int32), ("pending", C.c_uint64)]
 
 
+class RawFrame(C.Structure):
+    """cbv_raw_frame: one camera-native frame in host memory."""
+    _fields_ = [("fmt", C.c_int32), ("stride0", C.c_int32), ("stride1", C.c_int32), ("plane0", C.c_void_p), ("plane1", C.c_void_p)]
+
+
+FMT_BGR, FMT_NV12, FMT_YUYV = 0, 1, 2
+FORMATS = {"bgr": FMT_BGR, "nv12": FMT_NV12, "yuyv": FMT_YUYV}
+
 KERNEL_IDS = ["COLOR_LAB_HIST", "CLAHE_LUT", "CLAHE_APPLY", "BILATERAL", "SHARPEN", "NORM_LUT", "NORMALIZE", "WARP",
-              "SQUARES", "GRAY_BLUR", "OTSU", "THRESHOLD", "SCAN", "SYNTH", "RESET", "HOUGH"]
+              "SQUARES", "GRAY_BLUR", "OTSU", "THRESHOLD", "SCAN", "SYNTH", "RESET", "HOUGH", "INGEST"]
 K = {name: i for i, name in enumerate(KERNEL_IDS)}
 
 _lib = None
@@ -250,6 +258,10 @@ def load():
         "cbv_pipeline_square_stats": (i32, [vp, i32, P(SqStats)]),
         "cbv_pipeline_hough": (i32, [vp, i32, P(HoughResult)]),
         "cbv_pipeline_add_board": (i32, [vp, P(BoardConfig), P(vp)]),
+        "cbv_yuv_to_bgr": (i32, [vp, P(RawFrame), i32, i32, u8p, i32]),
+        "cbv_pipeline_upload_raw": (i32, [vp, i32, P(RawFrame)]),
+        "cbv_pipeline_set_input_format": (i32, [vp, i32]),
+        "cbv_pipeline_host_slot_bytes": (C.c_size_t, [vp]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
@@ -340,3 +352,59 @@ def as_bgr(frame):
     if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < a.shape[1] * 3:
         a = np.ascontiguousarray(a)
     return a
+
+
+def format_id(fmt):
+    """CBV_FMT_* of "bgr" | "nv12" | "yuyv"."""
+    try:
+        return FORMATS[fmt.lower()]
+    except (KeyError, AttributeError):
+        raise ValueError("unknown frame format %r (expected one of %s)" % (fmt, ", ".join(FORMATS)))
+
+
+def _rows(a, what):
+    """uint8 2-D array whose rows are contiguous bytes (row stride free)."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise ValueError("expected uint8 rows for %s, got %s %s" % (what, a.dtype, a.shape))
+    if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def raw_frame(frame, fmt):
+    """(RawFrame, w, h, arrays the struct points into) of a camera-native frame.  "nv12": one [h * 3 // 2, w] array or a
+    (y [h, w], uv [h // 2, w] or [h // 2, w // 2, 2]) pair; "yuyv": [h, w, 2]; "bgr": [h, w, 3].  Row strides are free."""
+    f = format_id(fmt)
+    r = RawFrame()
+    r.fmt = f
+    if f == FMT_BGR:
+        a = as_bgr(frame)
+        r.stride0, r.plane0 = a.strides[0], a.ctypes.data
+        return r, a.shape[1], a.shape[0], (a,)
+    if f == FMT_YUYV:
+        a = np.asarray(frame)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 2:
+            raise ValueError("expected a uint8 HxWx2 YUYV frame, got %s %s" % (a.dtype, a.shape))
+        if a.strides[2] != 1 or a.strides[1] != 2 or a.strides[0] < a.shape[1] * 2:
+            a = np.ascontiguousarray(a)
+        r.stride0, r.plane0 = a.strides[0], a.ctypes.data
+        return r, a.shape[1], a.shape[0], (a,)
+    if isinstance(frame, (tuple, list)):
+        y, uv = frame
+        uv = np.asarray(uv)
+        if uv.ndim == 3 and uv.shape[2] == 2 and uv.strides[2] == 1 and uv.strides[1] == 2:  # [h/2, w/2, 2] view of the U V rows
+            uv = np.lib.stride_tricks.as_strided(uv, shape=(uv.shape[0], uv.shape[1] * 2), strides=(uv.strides[0], 1))
+        elif uv.ndim == 3 and uv.shape[2] == 2:
+            uv = np.ascontiguousarray(uv).reshape(uv.shape[0], uv.shape[1] * 2)
+        y, uv = _rows(y, "the luma plane"), _rows(uv, "the chroma plane")
+        if y.shape[0] % 2 or uv.shape != (y.shape[0] // 2, y.shape[1]):
+            raise ValueError("NV12 planes do not fit: luma %s, chroma %s" % (y.shape, uv.shape))
+    else:
+        a = _rows(frame, "an NV12 frame")
+        if a.shape[0] % 3:
+            raise ValueError("an NV12 frame has h * 3 // 2 rows, got %d" % a.shape[0])
+        h = a.shape[0] // 3 * 2
+        y, uv = a[:h], a[h:]
+    r.stride0, r.plane0, r.stride1, r.plane1 = y.strides[0], y.ctypes.data, uv.strides[0], uv.ctypes.data
+    return r, y.shape[1], y.shape[0], (y, uv)

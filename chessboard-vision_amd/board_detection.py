@@ -58,6 +58,21 @@ def warp_image(img, points, display_size=(1280, 720), margin=100):
     return warped, matrix, board_size
 
 
+def yuv_to_bgr(frame, fmt):
+    """cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_YUY2) on the GPU (include/cbv.h, cbv_yuv_to_bgr): a new
+    uint8 [h, w, 3] array.  `fmt` "nv12": one [h * 3 // 2, w] array or a (y, uv) pair of planes; "yuyv": [h, w, 2].
+    Strided views are taken as they are.  (A BoardPipeline takes such frames directly: upload(fmt=...),
+    set_input_format.)"""
+    from . import _native as N
+    raw, w, h, keep = N.raw_frame(frame, fmt)
+    if raw.fmt == N.FMT_BGR:
+        raise ValueError("yuv_to_bgr converts \"nv12\" or \"yuyv\" frames")
+    ctx = N.context()
+    out = np.empty((h, w, 3), np.uint8)
+    ctx.check(ctx.lib.cbv_yuv_to_bgr(ctx.h, raw, w, h, N.ptr(out), w * 3))
+    return out
+
+
 def crop_inner_squares(img_warped, board_size, offset=0):
     """The warped board without an `offset`-pixel border, as a view, and the new board size (board_detection.py:74-82)."""
     cropped = img_warped[offset:board_size - offset, offset:board_size - offset]

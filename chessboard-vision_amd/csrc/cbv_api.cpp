@@ -79,7 +79,7 @@ void dev_free(DevBuf* b)
 // ---------------------------------------------------------------------------
 static const char* kKernelNames[CBV_K_COUNT] = {
     "k_color_lab_hist", "k_clahe_lut", "k_clahe_apply", "k_bilateral", "k_sharpen", "k_norm_lut", "k_normalize",
-    "k_warp", "k_squares", "k_gray_blur_hist", "k_otsu", "k_threshold", "k_scan", "k_synth", "k_reset_aux", "k_hough"};
+    "k_warp", "k_squares", "k_gray_blur_hist", "k_otsu", "k_threshold", "k_scan", "k_synth", "k_reset_aux", "k_hough", "k_ingest"};
 
 static hipEvent_t prof_get_event(cbv_ctx* ctx)
 {
@@ -741,6 +741,55 @@ extern "C" int cbv_warp_perspective(cbv_ctx* ctx, const uint8_t* bgr, int w, int
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (tm) fprintf(stderr, "warp: h2d %.1f launch %.1f d2h %.1f sync %.1f us (rows %d..%d)\n", t1 - t0, t2 - t1, t3 - t2, now() - t3, y0, y1);
     return CBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// camera-native frames (NV12, YUYV): cv2.cvtColor(COLOR_YUV2BGR_NV12 / _YUY2) on the device
+// ---------------------------------------------------------------------------
+// The rows of one plane into the staging buffer.  Tight rows, and rows with a dword-multiple stride of at most twice their
+// length, travel as they lie (padding included) in ONE linear copy and keep their stride on the device: k_ingest takes
+// strides, and a 2-D copy runs at a fifth of a linear one's rate (rows_h2d).  Anything else is packed by a 2-D copy.
+static int plane_h2d(cbv_ctx* ctx, u8* dst, const u8* src, int stride, int wbytes, int rows, int* dev_stride)
+{
+    const bool as_is = stride == wbytes || ((stride & 3) == 0 && stride <= 2 * wbytes);
+    *dev_stride = as_is ? stride : wbytes;
+    if (as_is) CBV_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)stride * (rows - 1) + wbytes, hipMemcpyHostToDevice, ctx->stream));
+    else RC(rows_h2d(ctx, dst, src, stride, wbytes, rows));
+    return CBV_OK;
+}
+
+int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what)
+{
+    RC(check_raw_format(ctx, raw->fmt, w, h, what));
+    const bool nv12 = raw->fmt == CBV_FMT_NV12;
+    const int wb0 = nv12 ? w : 2 * w;
+    if (!raw->plane0 || raw->stride0 < wb0 || (nv12 && (!raw->plane1 || raw->stride1 < w)))
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes or strides of the raw frame (stride0=%d stride1=%d)", what, raw->stride0, raw->stride1);
+    if ((size_t)w * h > (size_t)1 << 28) return cbv_fail(ctx, CBV_ERR_ARG, "%s: image too large", what);
+    // plane 1 follows plane 0's largest possible device copy (rows of twice their length), on a 256-byte boundary
+    const size_t off1 = ((size_t)2 * wb0 * h + 255) & ~(size_t)255, total = off1 + (nv12 ? (size_t)w * h : 0);
+    RC(dev_ensure(ctx, &ctx->in, total + 256));
+    if (ctx->debug_poison) CBV_HIP(ctx, hipMemsetAsync(ctx->in.p, 0xA5, total, ctx->stream));
+    RawGeom r;
+    r.fmt = raw->fmt;
+    r.stride1 = 0;
+    r.frame_stride = 0;
+    u8* st = (u8*)ctx->in.p;
+    RC(plane_h2d(ctx, st, raw->plane0, raw->stride0, wb0, h, &r.stride0));
+    if (nv12) RC(plane_h2d(ctx, st + off1, raw->plane1, raw->stride1, w, h / 2, &r.stride1));
+    return launch_ingest(ctx, st, nv12 ? st + off1 : nullptr, r, dst, g, 1);
+}
+
+extern "C" int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride)
+{
+    if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_yuv_to_bgr: ctx is null");
+    if (!raw || !bgr || w <= 0 || h <= 0 || bgr_stride < w * 3) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_yuv_to_bgr: bad arguments");
+    RC(check_raw_format(ctx, raw->fmt, w, h, "cbv_yuv_to_bgr"));
+    CBV_ENTER(ctx);
+    const Geom g = tight_geom(w, h);
+    RC(dev_ensure(ctx, &ctx->a, g.frame_stride));
+    RC(raw_h2d_convert(ctx, raw, w, h, (u8*)ctx->a.p, g, "cbv_yuv_to_bgr"));
+    return download(ctx, ctx->a.p, bgr, w * 3, h, bgr_stride);
 }
 
 // ---------------------------------------------------------------------------

@@ -329,6 +329,30 @@ int launch_threshold(cbv_ctx* ctx, const u8* blur, u8* binary, const u32* aux, i
 int launch_synth(cbv_ctx* ctx, u8* dst, Geom g, const u64* seeds_dev, const double* hinv_dev, const u8* boards_dev,
                  const cbv_scene* scene_dev, int batch);
 
+// Raw (camera-native) frames of a batch for k_ingest: plane pointers are those of frame 0, frames `frame_stride` bytes apart
+struct RawGeom {
+    int fmt;              // CBV_FMT_NV12 or CBV_FMT_YUYV
+    int stride0, stride1; // bytes per row of the luma (or YUYV) plane / of NV12's chroma plane
+    size_t frame_stride;
+};
+// tightly packed raw frames, each frame rounded to 256 bytes (the ingest rings); fmt BGR: tight_geom's frame_stride
+static inline size_t raw_frame_bytes(int fmt, int w, int h) { return fmt == CBV_FMT_NV12 ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_YUYV ? 2 : 3); }
+static inline RawGeom tight_raw_geom(int fmt, int w, int h)
+{
+    RawGeom r;
+    r.fmt = fmt;
+    r.stride0 = fmt == CBV_FMT_YUYV ? 2 * w : w;
+    r.stride1 = fmt == CBV_FMT_NV12 ? w : 0;
+    r.frame_stride = (raw_frame_bytes(fmt, w, h) + 255) & ~(size_t)255;
+    return r;
+}
+// CBV_ERR_ARG unless fmt is a YUV format and w (and h, for NV12) is even
+int check_raw_format(cbv_ctx* ctx, int fmt, int w, int h, const char* what);
+// cv2.cvtColor COLOR_YUV2BGR_NV12 / _YUY2 of `batch` raw frames into BGR frames of geometry g (k_ingest.hip)
+int launch_ingest(cbv_ctx* ctx, const u8* plane0, const u8* plane1, RawGeom r, u8* dst, Geom g, int batch);
+// one raw host frame (NV12 / YUYV, strided views) through the context's staging buffer into a BGR device image
+int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
+
 void build_gaussian_q8_sigma(int k, double sigma, int* coef);
 int launch_gray_gauss(cbv_ctx* ctx, const u8* src, int w, int h, int stride, int cn, const int* coef_dev, int k, u8* dst);
 int launch_dilate_rect(cbv_ctx* ctx, const u8* src, int w, int h, int r, u8* dst);

@@ -59,8 +59,12 @@ struct Pipe {
     DevBuf lane_work[MAX_LANES]; // HoughCircles worklist of the lane's current chunk: count, then frame << 8 | square
     u8* enhanced = nullptr;      // [max_frames] when keep_enhanced
     DevBuf d_synth;
-    // ingest: pinned host mirror of the frame ring, filled by the capture side and copied on its own stream
+    // ingest: pinned host mirror of the frame ring, filled by the capture side and copied on its own stream; with a YUV
+    // input format (cbv_pipeline_set_input_format) both it and `raw_ring`, its device copy, hold raw frames, which
+    // k_ingest converts into `frames` behind the copy
     u8* host_ring = nullptr;
+    int in_fmt = CBV_FMT_BGR;
+    u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated with the host ring; null with CBV_FMT_BGR
     hipStream_t copy_stream = nullptr;
     struct CopyRec {
         int s0, cnt;
@@ -412,6 +416,7 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     if (P->copy_stream) (void)hipStreamSynchronize(P->copy_stream);
     for (auto& c : P->copies) (void)hipEventDestroy(c.ev);
     if (P->host_ring) (void)hipHostFree(P->host_ring);
+    if (P->raw_ring) (void)hipFree(P->raw_ring);
     if (P->frames) (void)hipFree(P->frames);
     if (P->enhanced) (void)hipFree(P->enhanced);
     dev_free(&P->d_synth);
@@ -591,6 +596,48 @@ extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr
     return CBV_OK;
 }
 
+extern "C" int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_frame* raw)
+{
+    if (p && attached(p)) return cbv_fail(p->pipe->ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: frames go to the parent of a board");
+    if (!p || !raw || slot < 0 || slot >= p->pipe->max_frames) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_upload_raw: bad arguments");
+    if (raw->fmt == CBV_FMT_BGR) return cbv_pipeline_upload(p, slot, raw->plane0, raw->stride0);
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    RC(check_raw_format(ctx, raw->fmt, P.w, P.h, "cbv_pipeline_upload_raw"));
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // lanes and scan of the last run
+    RC(raw_h2d_convert(ctx, raw, P.w, P.h, P.frames + P.g.frame_stride * slot, P.g, "cbv_pipeline_upload_raw"));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+// bytes between the slots of the ingest rings in the current input format
+static size_t host_slot_bytes(const Pipe& P) { return P.in_fmt == CBV_FMT_BGR ? P.g.frame_stride : tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride; }
+
+extern "C" size_t cbv_pipeline_host_slot_bytes(cbv_pipeline* p)
+{
+    if (!p || attached(p)) return 0;
+    std::lock_guard<std::recursive_mutex> lock(p->pipe->ctx->mu);
+    return host_slot_bytes(*p->pipe);
+}
+
+extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_pipeline_set_input_format: the pipeline is null");
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_set_input_format: frames go to the parent of a board");
+    if (fmt != CBV_FMT_BGR) RC(check_raw_format(ctx, fmt, P.w, P.h, "cbv_pipeline_set_input_format"));
+    CBV_ENTER(ctx);
+    // the copies and conversions in flight read the rings that go away here (both run on the copy stream)
+    if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+    if (P.host_ring) (void)hipHostFree(P.host_ring);
+    if (P.raw_ring) (void)hipFree(P.raw_ring);
+    P.host_ring = P.raw_ring = nullptr;
+    P.in_fmt = fmt;
+    return CBV_OK;
+}
+
 extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)
 {
     if (!p) return nullptr;
@@ -603,9 +650,14 @@ extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)
     }
     if (!P.host_ring) {
         if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
-        if (hipHostMalloc((void**)&P.host_ring, P.g.frame_stride * P.max_frames, hipHostMallocDefault) != hipSuccess) {
-            cbv_fail(ctx, CBV_ERR_HIP, "pinned host ring of %zu bytes could not be allocated", P.g.frame_stride * P.max_frames);
+        const size_t bytes = host_slot_bytes(P) * P.max_frames;
+        if (hipHostMalloc((void**)&P.host_ring, bytes, hipHostMallocDefault) != hipSuccess) {
+            cbv_fail(ctx, CBV_ERR_HIP, "pinned host ring of %zu bytes could not be allocated", bytes);
             P.host_ring = nullptr;
+        } else if (P.in_fmt != CBV_FMT_BGR && hipMalloc((void**)&P.raw_ring, bytes + 256) != hipSuccess) {
+            cbv_fail(ctx, CBV_ERR_HIP, "cbv_pipeline_host_ring: device ring of %zu bytes for the raw frames could not be allocated", bytes);
+            (void)hipHostFree(P.host_ring);
+            P.host_ring = P.raw_ring = nullptr;
         }
     }
     return P.host_ring;
@@ -623,9 +675,26 @@ extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
     if (!P.copy_stream) RC(ctx_worker_stream(ctx, &ctx->copy_stream, &P.copy_stream));
     // do not overwrite device slots a run that is still in flight reads: ANY such run, not only the last one
     retire_runs(P);
-    if (Pipe::RunRec* r = newest_run(P, slot0, count, 0)) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, r->one_event ? r->scan_ev : r->lanes_ev, 0));
-    CBV_HIP(ctx, hipMemcpyAsync(P.frames + P.g.frame_stride * slot0, P.host_ring + P.g.frame_stride * slot0,
-                                P.g.frame_stride * count, hipMemcpyHostToDevice, P.copy_stream));
+    Pipe::RunRec* reader = newest_run(P, slot0, count, 0);
+    if (P.in_fmt == CBV_FMT_BGR) {
+        if (reader) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, reader->one_event ? reader->scan_ev : reader->lanes_ev, 0));
+        CBV_HIP(ctx, hipMemcpyAsync(P.frames + P.g.frame_stride * slot0, P.host_ring + P.g.frame_stride * slot0,
+                                    P.g.frame_stride * count, hipMemcpyHostToDevice, P.copy_stream));
+    } else {
+        // Raw slots to the device raw ring, then their conversion into the frame ring, both on the copy stream: stream order
+        // is the copy -> conversion dependency and keeps a later copy off raw slots an earlier conversion still reads, and
+        // the one event below stands for both.  Only the conversion writes the frames the runs in flight read, so the copy
+        // itself does not wait for them.
+        const RawGeom rg = tight_raw_geom(P.in_fmt, P.w, P.h);
+        u8* raw = P.raw_ring + rg.frame_stride * slot0;
+        CBV_HIP(ctx, hipMemcpyAsync(raw, P.host_ring + rg.frame_stride * slot0, rg.frame_stride * count, hipMemcpyHostToDevice, P.copy_stream));
+        if (reader) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, reader->one_event ? reader->scan_ev : reader->lanes_ev, 0));
+        hipStream_t caller = ctx->stream;
+        ctx->stream = P.copy_stream;
+        const int rc = launch_ingest(ctx, raw, P.in_fmt == CBV_FMT_NV12 ? raw + (size_t)P.w * P.h : nullptr, rg, P.frames + P.g.frame_stride * slot0, P.g, count);
+        ctx->stream = caller;
+        RC(rc);
+    }
     Pipe::CopyRec* rec = nullptr;
     for (auto& c : P.copies)
         if (!c.pending) {

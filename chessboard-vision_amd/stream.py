@@ -145,6 +145,7 @@ class BoardPipeline(_BoardMethods):
         self.rois_rc = []
         self.board_size = 0
         self._boards = []
+        self.input_format = "bgr"
 
     def close(self):
         if self.h_:
@@ -202,21 +203,40 @@ class BoardPipeline(_BoardMethods):
     def frames_ptr(self):
         return self.ctx.lib.cbv_pipeline_frames_dev(self.h_)
 
-    def upload(self, slot, frame):
-        f = N.as_bgr(frame)
-        assert f.shape[:2] == (self.h, self.w)
-        self.ctx.check(self.ctx.lib.cbv_pipeline_upload(self.h_, slot, N.ptr(f), f.strides[0]))
+    def upload(self, slot, frame, fmt="bgr"):
+        """One frame into a slot, synchronous.  `fmt` "nv12" (one [h * 3 // 2, w] array or a (y, uv) pair of possibly
+        strided views) and "yuyv" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h, cbv_pipeline_upload_raw)."""
+        if N.format_id(fmt) == N.FMT_BGR:
+            f = N.as_bgr(frame)
+            assert f.shape[:2] == (self.h, self.w)
+            self.ctx.check(self.ctx.lib.cbv_pipeline_upload(self.h_, slot, N.ptr(f), f.strides[0]))
+            return
+        raw, w, h, keep = N.raw_frame(frame, fmt)
+        if (h, w) != (self.h, self.w):
+            raise ValueError("a %dx%d %s frame does not fit the pipeline's %dx%d frames" % (w, h, fmt, self.w, self.h))
+        self.ctx.check(self.ctx.lib.cbv_pipeline_upload_raw(self.h_, slot, raw))
+
+    def set_input_format(self, fmt):
+        """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12" or "yuyv".  Raw
+        frames cross PCIe as they are and are converted to BGR on the GPU behind their copy.  The ring is freed here and
+        allocated again by the next `host_ring()`: an array that call returned earlier must not be touched any more."""
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt)))
+        self.input_format = fmt.lower()
 
     def host_ring(self):
-        """Pinned host mirror of the frame ring as a numpy array [max_frames, h, w, 3]: the capture side writes
-        frames here, `submit` copies them to the GPU asynchronously."""
+        """Pinned host mirror of the frame ring as a numpy array: the capture side writes frames here, `submit` copies
+        them to the GPU asynchronously.  [max_frames, h, w, 3] for BGR, [max_frames, h * 3 // 2, w] for NV12 (luma rows,
+        then the U V rows), [max_frames, h, w, 2] for YUYV (`set_input_format`)."""
         ptr = self.ctx.lib.cbv_pipeline_host_ring(self.h_)
         if not ptr:
             raise RuntimeError(self.ctx.lib.cbv_last_error(self.ctx.h).decode())
-        fs = (self.w * self.h * 3 + 255) & ~255  # frames are 256-byte aligned in both rings
+        fs = self.ctx.lib.cbv_pipeline_host_slot_bytes(self.h_)  # slots are 256-byte aligned in both rings
         buf = (C.c_uint8 * (fs * self.max_frames)).from_address(ptr)
         flat = np.frombuffer(buf, dtype=np.uint8)
-        return np.lib.stride_tricks.as_strided(flat, shape=(self.max_frames, self.h, self.w, 3), strides=(fs, self.w * 3, 3, 1))
+        w, h = self.w, self.h
+        shape, strides = {"bgr": ((h, w, 3), (w * 3, 3, 1)), "nv12": ((h * 3 // 2, w), (w, 1)),
+                          "yuyv": ((h, w, 2), (w * 2, 2, 1))}[self.input_format]
+        return np.lib.stride_tricks.as_strided(flat, shape=(self.max_frames,) + shape, strides=(fs,) + strides)
 
     def submit(self, slot0, count):
         """Enqueue host ring -> device ring for the slots; run() of those slots waits for the copy."""

@@ -127,7 +127,7 @@ CBV_API const char* cbv_device_name(const cbv_ctx* ctx);
 enum {
     CBV_K_COLOR_LAB_HIST = 0, CBV_K_CLAHE_LUT, CBV_K_CLAHE_APPLY, CBV_K_BILATERAL, CBV_K_SHARPEN,
     CBV_K_NORM_LUT, CBV_K_NORMALIZE, CBV_K_WARP, CBV_K_SQUARES, CBV_K_GRAY_BLUR, CBV_K_OTSU,
-    CBV_K_THRESHOLD, CBV_K_SCAN, CBV_K_SYNTH, CBV_K_RESET, CBV_K_HOUGH, CBV_K_COUNT
+    CBV_K_THRESHOLD, CBV_K_SCAN, CBV_K_SYNTH, CBV_K_RESET, CBV_K_HOUGH, CBV_K_INGEST, CBV_K_COUNT
 };
 CBV_API int cbv_profile_enable(cbv_ctx* ctx, int kid /* -1 = all, -2 = none */);
 CBV_API int cbv_profile_read(cbv_ctx* ctx, int kid, double* total_ms, long long* launches);
@@ -306,8 +306,9 @@ typedef struct {
  * squares that changed the circular test on the same pixels preprocessed the PieceDetector way (k = 5). */
 CBV_API int cbv_squares_detect_changes(cbv_squares* sq, const cbv_host_image* img, const cbv_roi* rois, int n, int blur_k,
                                        const cbv_change_params* prm, cbv_change_result* out /* n */);
-/* tests: fill partially uploaded staging buffers (cbv_warp_perspective's frame, the squares' image rows) with 0xA5
- * before the copy, so a read outside the uploaded part cannot go unnoticed */
+/* tests: fill partially uploaded staging buffers (cbv_warp_perspective's frame, the squares' image rows, the raw frame of
+ * cbv_yuv_to_bgr / cbv_pipeline_upload_raw) with 0xA5 before the copy, so a read outside the uploaded part cannot go
+ * unnoticed */
 CBV_API int cbv_debug_poison(cbv_ctx* ctx, int on);
 
 /* cv2.Canny(img, threshold1, threshold2) with the default aperture 3 and L1 gradient, as
@@ -412,7 +413,8 @@ CBV_API int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* c
 /* device pointer of the input frame ring: [max_frames][h][w][3] uint8 */
 CBV_API void* cbv_pipeline_frames_dev(cbv_pipeline* p);
 CBV_API int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr, int stride);
-/* Ingest front end: a pinned host mirror of the frame ring ([max_frames][h][w][3], allocated on first call) that
+/* Ingest front end: a pinned host mirror of the frame ring ([max_frames][h][w][3], or raw frames after
+ * cbv_pipeline_set_input_format; allocated on first call) that
  * the capture / decode side writes frames into, and an asynchronous copy of slots [slot0, slot0+count) to the
  * device ring on the pipeline's copy stream.  cbv_pipeline_run of those slots waits for their copy; a submit waits
  * for every run still in flight that reads the slots it would overwrite (however many runs back).  Submitting batch k+1 before running batch k
@@ -453,6 +455,46 @@ CBV_API int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats* o
 CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out);
 
 /* ------------------------------------------------------------------ */
+/* camera-native frames: NV12 and YUYV, converted to BGR on the device */
+/* ------------------------------------------------------------------ */
+/* Cameras deliver YUYV and decoders NV12; cv2.VideoCapture converts them to BGR on a host core before the application
+ * sees a frame.  Here the raw frame crosses PCIe (2 or 1.5 bytes per pixel instead of 3) and one kernel writes BGR into
+ * the pipeline's frame ring, so everything downstream is unchanged.  The conversion is cv2.cvtColor's
+ * COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_YUY2 on 8-bit data: BT.601, limited range, fixed point with 20 fraction bits, no
+ * chroma interpolation (a pixel takes the U, V of its 2x2 block or of its horizontal pair).  With
+ * y = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128, h = 1 << 19, in signed 32-bit arithmetic:
+ *     B = sat_u8((y + h + 2116026 * u) >> 20)
+ *     G = sat_u8((y + h -  852492 * v - 409993 * u) >> 20)
+ *     R = sat_u8((y + h + 1673527 * v) >> 20)
+ * Layouts.  NV12: h rows of w luma bytes (plane0), then h / 2 rows of w bytes U V U V ... (plane1); w and h even.
+ * YUYV (YUY2): h rows of 2 w bytes Y0 U Y1 V (plane0); w even. */
+#define CBV_FMT_BGR  0
+#define CBV_FMT_NV12 1
+#define CBV_FMT_YUYV 2
+
+typedef struct {            /* one raw frame in host memory */
+    int32_t fmt;            /* CBV_FMT_* */
+    int32_t stride0, stride1;   /* bytes per row of plane0 / plane1 */
+    const uint8_t* plane0;  /* BGR, YUYV, or the NV12 luma plane */
+    const uint8_t* plane1;  /* NV12 chroma plane, else NULL */
+} cbv_raw_frame;
+
+/* host in, host out: the cvtColor call on its own (fmt = CBV_FMT_NV12 or CBV_FMT_YUYV) */
+CBV_API int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride);
+/* one frame of any format into a slot of the frame ring, synchronous, like cbv_pipeline_upload */
+CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_frame* raw);
+/* Format of the pinned ingest ring; CBV_FMT_BGR is the default.  Waits for the submitted copies, then FREES the pinned
+ * ring: a pointer cbv_pipeline_host_ring returned earlier is dead after this call, and the next cbv_pipeline_host_ring
+ * allocates the ring in the new format ([max_frames] raw frames, tightly packed in the layout above, each slot rounded
+ * to 256 bytes: cbv_pipeline_host_slot_bytes).  With a YUV format cbv_pipeline_submit copies the raw slots to a device
+ * ring of the same layout and converts them into the BGR frame ring behind the copy; its ordering promises are the
+ * same (a run of the slots waits for the copy and its conversion).  On the pipeline only (a board handle:
+ * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, or odd h with NV12, and then nothing has changed. */
+CBV_API int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt);
+/* bytes from one host-ring slot to the next in the current format (a multiple of 256); 0 for a board handle */
+CBV_API size_t cbv_pipeline_host_slot_bytes(cbv_pipeline* p);
+
+/* ------------------------------------------------------------------ */
 /* several boards seen by one camera                                   */
 /* ------------------------------------------------------------------ */
 /* A configured pipeline holds up to CBV_MAX_BOARDS boards; the pipeline itself is board 0.  Extra boards share its frame
@@ -483,8 +525,8 @@ typedef struct {
  * cbv_pipeline_run(parent, ...) then processes every attached board for those slots.  A board handle is accepted by the
  * per-board calls, which act on that board alone: cbv_pipeline_results, _noise_results, _square_stats, _hough,
  * _download (which = 2), _calibrate, _update_references, _set_check_squares, _reset_state.  On a board handle
- * cbv_pipeline_run, _upload, _submit, _synth, _configure, _host_ring and _download with which 0 or 1 fail with
- * CBV_ERR_STATE (_host_ring returns NULL); cbv_pipeline_reset_state(parent) resets board 0 only.
+ * cbv_pipeline_run, _upload, _upload_raw, _submit, _set_input_format, _synth, _configure, _host_ring and _download with
+ * which 0 or 1 fail with CBV_ERR_STATE (_host_ring returns NULL, _host_slot_bytes 0); cbv_pipeline_reset_state(parent) resets board 0 only.
  * Lifecycle: cbv_pipeline_destroy(board) detaches and frees the board (the other boards are unchanged);
  * cbv_pipeline_destroy(parent) frees its boards too, and their handles are dead from then on.
  * cbv_pipeline_configure(parent) fails with CBV_ERR_STATE while boards are attached: destroy them first.

@@ -1,0 +1,37 @@
+"""k_ingest on its own: microseconds per frame and achieved bytes/s (raw bytes read + BGR bytes written) at 1080p and
+4K per format, from the library's event pairs around the launches of cbv_pipeline_submit (cbv_profile_*).  Each submit
+converts a batch whose frames (raw + BGR, about 600 MB) do not fit the 256 MiB Infinity Cache."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+from chessboard_vision_amd import _native as N  # noqa: E402
+from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
+
+HBM_GBPS = 8000.0  # the peak the other roofline rows of DESIGN.md use
+ctx = N.context()
+rng = np.random.default_rng(0)
+for (w, h, n) in ((1920, 1080, 64), (3840, 2160, 16)):
+    for fmt in ("nv12", "yuyv"):
+        p = BoardPipeline(w, h, n)
+        p.set_input_format(fmt)
+        ring = p.host_ring()
+        ring[0] = rng.integers(0, 256, ring[0].shape, dtype=np.uint8)
+        for i in range(1, n):
+            ring[i] = ring[0]
+        p.submit(0, n)
+        p.wait_submitted()
+        ctx.profile_reset()
+        ctx.profile_enable(N.K["INGEST"])
+        for rep in range(10):
+            p.submit(0, n)
+        p.wait_submitted()
+        ms, launches = ctx.profile_read(N.K["INGEST"])
+        ctx.profile_enable(-2)
+        us = ms * 1e3 / (launches * n)
+        nbytes = ring[0].size + w * h * 3
+        gbps = nbytes / us / 1e3
+        print("%-4s %4dx%-4d: %7.2f us/frame, %.0f GB/s (%d B read + %d B written per frame) = %.1f %% of %d GB/s; %d launches of %d frames"
+              % (fmt, w, h, us, gbps, ring[0].size, w * h * 3, 100 * gbps / HBM_GBPS, HBM_GBPS, launches, n), flush=True)
+        p.close()

@@ -1,6 +1,13 @@
 """PCIe-inclusive throughput of the ingest front end (never bench.py's `value`): 1080p frames sit in the pinned
 host ring; batch k+1 is copied (cbv_pipeline_submit) while batch k runs.  Prints H2D-only, compute-only and
-overlapped rates."""
+overlapped rates per input format, all from one process:
+
+    python tools/ingest_timing.py --format all --reps 3
+
+With "nv12" / "yuyv" the ring holds raw frames (BoardPipeline.set_input_format) and a submit is the copy plus the
+conversion kernel; "H2D only" then includes that kernel.  `--reps` alternates the formats and prints every repetition
+and, for each format, the ratio to BGR of the same repetition."""
+import argparse
 import os
 import sys
 import time
@@ -10,50 +17,87 @@ import numpy as np  # noqa: E402
 from chessboard_vision_amd import synth as S  # noqa: E402
 from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--format", default="bgr", choices=["bgr", "nv12", "yuyv", "all"])
+ap.add_argument("--reps", type=int, default=1)
+args = ap.parse_args()
+formats = ["bgr", "nv12", "yuyv"] if args.format == "all" else [args.format]
+
 W, H, HALF, ROUNDS = 1920, 1080, 128, 6
 n = 2 * HALF
 p = BoardPipeline(W, H, n)
 p.configure(S.scaled_corners(W, H), profile=S.SHIPPED_PROFILE, grid_lines=(S.CALIB_GRID_X, S.CALIB_GRID_Y), **S.SHIPPED_DETECTOR)
 p.synth(0, n, scene="dim")
-ring = p.host_ring()
-for i in range(n):
-    ring[i] = p.download(0, i)
-p.run(0, n)
-p.results(0, 1)
+bgr = [p.download(0, i) for i in range(n)]
+
+
+def to_raw(f, fmt):
+    """a camera-native frame of a BGR one (float BT.601 forward transform, chroma of the first pixel of each block)"""
+    if fmt == "bgr":
+        return f
+    b, g, r = (f[..., i].astype(np.float32) for i in range(3))
+    q = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
+    y, u, v = q(16 + 0.257 * r + 0.504 * g + 0.098 * b), q(128 - 0.148 * r - 0.291 * g + 0.439 * b), q(128 + 0.439 * r - 0.368 * g - 0.071 * b)
+    if fmt == "nv12":
+        return np.concatenate([y, np.stack([u[::2, ::2], v[::2, ::2]], axis=-1).reshape(H // 2, W)])
+    out = np.empty((H, W, 2), np.uint8)
+    out[..., 0], out[:, 0::2, 1], out[:, 1::2, 1] = y, u[:, ::2], v[:, ::2]
+    return out
 
 
 def sync():
     p.ctx.check(p.ctx.lib.cbv_ctx_synchronize(p.ctx.h))
+    p.wait_submitted()
     p.results(0, 1)
 
 
-# H2D only
-t0 = time.perf_counter()
-for r in range(ROUNDS):
+def measure(fmt):
+    p.set_input_format(fmt)
+    ring = p.host_ring()
+    for i in range(n):
+        ring[i] = raw[fmt][i]
+    p.submit(0, n)
+    p.run(0, n)
+    sync()
+    # H2D only (+ the conversion of a YUV format)
+    t0 = time.perf_counter()
+    for r in range(ROUNDS):
+        p.submit(0, HALF)
+        p.submit(HALF, HALF)
+    p.run(0, 1)
+    sync()
+    t_copy = time.perf_counter() - t0
+    # compute only
+    t0 = time.perf_counter()
+    for r in range(ROUNDS):
+        p.run(0, HALF)
+        p.run(HALF, HALF)
+    sync()
+    t_run = time.perf_counter() - t0
+    # overlapped: submit the other half, run this half
     p.submit(0, HALF)
-    p.submit(HALF, HALF)
-p.run(0, 1)
-sync()
-t_copy = time.perf_counter() - t0
-# compute only
-t0 = time.perf_counter()
-for r in range(ROUNDS):
-    p.run(0, HALF)
-    p.run(HALF, HALF)
-sync()
-t_run = time.perf_counter() - t0
-# overlapped: submit the other half, run this half
-p.submit(0, HALF)
-t0 = time.perf_counter()
-for r in range(ROUNDS):
-    p.submit(HALF, HALF)
-    p.run(0, HALF)
-    p.submit(0, HALF)
-    p.run(HALF, HALF)
-sync()
-t_ovl = time.perf_counter() - t0
-frames = ROUNDS * n
-gb = frames * W * H * 3 / 1e9
-print("H2D only      : %8.0f frames/s  (%.1f GB/s)" % (frames / t_copy, gb / t_copy))
-print("compute only  : %8.0f frames/s" % (frames / t_run))
-print("submit || run : %8.0f frames/s  (PCIe-inclusive)" % (frames / t_ovl))
+    t0 = time.perf_counter()
+    for r in range(ROUNDS):
+        p.submit(HALF, HALF)
+        p.run(0, HALF)
+        p.submit(0, HALF)
+        p.run(HALF, HALF)
+    sync()
+    t_ovl = time.perf_counter() - t0
+    frames = ROUNDS * n
+    gb = frames * raw[fmt][0].size / 1e9
+    return frames / t_copy, gb / t_copy, frames / t_run, frames / t_ovl
+
+
+raw = {fmt: [to_raw(f, fmt) for f in bgr[:8]] * (n // 8) for fmt in formats}
+for rep in range(args.reps):
+    got = {fmt: measure(fmt) for fmt in formats}
+    for fmt in formats:
+        c, gbs, r, o = got[fmt]
+        tag = "[%s, rep %d] " % (fmt, rep + 1)
+        print(tag + "H2D only      : %8.0f frames/s  (%.1f GB/s)" % (c, gbs))
+        print(tag + "compute only  : %8.0f frames/s" % r)
+        print(tag + "submit || run : %8.0f frames/s  (PCIe-inclusive)" % o)
+        if fmt != "bgr" and "bgr" in got:
+            print(tag + "ratio to bgr  : H2D only %.3f, submit || run %.3f" % (c / got["bgr"][0], o / got["bgr"][3]), flush=True)
+p.close()

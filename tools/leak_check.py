@@ -1,5 +1,5 @@
-"""Create / configure / run / close pipelines (with boards attached and detached in part of the iterations) and detector
-objects in a loop and watch the device's free memory and the process's RSS: neither may creep.  One-off (GPU box)."""
+"""Create / configure / run / close pipelines (with boards attached and detached, and the ingest rings switched between the
+input formats, in part of the iterations) and detector objects in a loop and watch the device's free memory and the process's RSS: neither may creep.  One-off (GPU box)."""
 import os
 import resource
 import sys
@@ -45,6 +45,13 @@ for it in range(n):
         p.run(0, 8)
         p.results(0, 8)
     ring = p.host_ring() if hasattr(p, "host_ring") and it % 4 == 0 else None
+    if it % 2 == 0:  # the ingest rings in every format, back and forth (each switch frees the pinned and the device raw ring)
+        for fmt in ("nv12", "yuyv", "bgr", "nv12"):
+            p.set_input_format(fmt)
+            p.host_ring()[:] = 128
+            p.submit(0, 8)
+            p.run(0, 8)
+            p.results(0, 8)
     p.close()
     e = ImageEnhancer()
     e.profile = S.SHIPPED_PROFILE
