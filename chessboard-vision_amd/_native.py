@@ -175,6 +175,12 @@ FORMATS = {"bgr": FMT_BGR, "nv12": FMT_NV12, "yuyv": FMT_YUYV}
 KERNEL_IDS = ["COLOR_LAB_HIST", "CLAHE_LUT", "CLAHE_APPLY", "BILATERAL", "SHARPEN", "NORM_LUT", "NORMALIZE", "WARP",
               "SQUARES", "GRAY_BLUR", "OTSU", "THRESHOLD", "SCAN", "SYNTH", "RESET", "HOUGH", "INGEST"]
 K = {name: i for i, name in enumerate(KERNEL_IDS)}
+# Kernels outside the default path (they launch only when a feature is switched on) follow the list above in the
+# library's id space (CBV_K_* of include/cbv.h) and are named in K only.
+K["MODEL_SCAN"] = len(KERNEL_IDS)
+
+MODEL_FROZEN, MODEL_EVERY, MODEL_UNCHANGED = 0, 1, 2
+MODEL_MODES = {"frozen": MODEL_FROZEN, "every": MODEL_EVERY, "unchanged": MODEL_UNCHANGED}
 
 _lib = None
 
@@ -262,6 +268,8 @@ def load():
         "cbv_pipeline_upload_raw": (i32, [vp, i32, P(RawFrame)]),
         "cbv_pipeline_set_input_format": (i32, [vp, i32]),
         "cbv_pipeline_host_slot_bytes": (C.c_size_t, [vp]),
+        "cbv_pipeline_set_model_update": (i32, [vp, i32, dbl]),
+        "cbv_pipeline_model": (i32, [vp, i32, i32, vp]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

@@ -468,6 +468,20 @@ int launch_scan(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, const u8* 
 // arguments from the entry and then run the single-board bodies unchanged, so a board computes what a pipeline of its
 // own computes.  HoughCircles' worklist and second-pass entries carry the board in their top bits (MB_BOARD_SHIFT).
 // ---------------------------------------------------------------------------
+// ChangeDetector's z-score statistics AND update_all_references over the frames of a run, in frame order (k_model_scan):
+// the model after frame t is the input of frame t + 1.  mode = CBV_MODEL_FROZEN: nothing to do (the statistics kernels
+// read the model themselves, `mean` / `sd` of the BoardDev), and so for a board that is not calibrated.
+struct ModelScan {
+    int mode;              // CBV_MODEL_*, FROZEN while the board is not calibrated
+    float one_minus, alpha; // (1 - alpha) and alpha narrowed to float32 as launch_squares_ema does
+    float z_thresh;
+    float* mean;           // the model planes, read and written
+    float* var;
+    float* sd;
+};
+int launch_model_scan(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, ModelScan ms,
+                      cbv_sq_stats* stats, u8* decisions, int count, int max_px);
+
 #define MB_BOARD_SHIFT 29 // work item = board << 29 | frame << 8 | square: frames of a list < 2^21
 struct BoardDev {
     // warp
@@ -502,6 +516,8 @@ struct BoardDev {
     cbv_frame_result* mirror;    // pinned [slot] (ResultMirror of short runs)
     const u32* over_src;         // HoughCircles overflow counter, null without use_hough
     u32* over_dst;               // its pinned copy
+    // per-frame background model update (cbv_pipeline_set_model_update): k_model_scan's arguments
+    ModelScan ms;
 };
 ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
 // per-pass HoughCfg of a board (layout and maxc as launch_hough / launch_hough_second set them); returns the LDS bytes
@@ -514,6 +530,7 @@ int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int 
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);
 int launch_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int mirrored);
+int launch_model_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int max_px);
 
 // ---------------------------------------------------------------------------
 // Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline.cpp) shares

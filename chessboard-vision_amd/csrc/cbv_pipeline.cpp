@@ -24,6 +24,9 @@ struct Board {
     std::vector<u8> slot_mirrored; // per slot: the mirror holds the slot's newest record (once its run has finished)
     HoughCfg hough_cfg;
     bool calibrated = false, has_check = false; // has_check: squares_to_check masks were set
+    int model_mode = CBV_MODEL_FROZEN;          // cbv_pipeline_set_model_update
+    double model_alpha = 0.1;
+    bool adaptive() const { return calibrated && model_mode != CBV_MODEL_FROZEN; } // k_model_scan runs for this board
 };
 
 struct Pipe;
@@ -102,6 +105,7 @@ struct Pipe {
     std::vector<BoardDev> tab;
     DevBuf d_boards;
     bool any_hough = false;
+    bool any_adaptive = false; // some board's model follows the frames: k_model_scan runs in front of the temporal scan
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
     Board& b0() const { return boards[0]->b; }
@@ -186,8 +190,19 @@ static BoardDev board_dev(const Board& q, size_t lds[2])
     T.masks = (const u8*)q.d_masks.p;
     T.gray = (u8*)q.d_gray.p;
     T.plane_total = q.plane_total;
-    T.mean = q.calibrated ? (const float*)q.d_mean.p : nullptr;
-    T.sd = q.calibrated ? (const float*)q.d_var.p + q.plane_total : nullptr;
+    // A board whose model follows the frames gets its z-score statistics from k_model_scan, frame after frame on the scan
+    // stream: the statistics kernel of the lanes must not read the model, which the scan of the run before may still write
+    const bool frozen = q.calibrated && !q.adaptive();
+    T.mean = frozen ? (const float*)q.d_mean.p : nullptr;
+    T.sd = frozen ? (const float*)q.d_var.p + q.plane_total : nullptr;
+    T.ms.mode = q.adaptive() ? q.model_mode : CBV_MODEL_FROZEN;
+    // (1 - self.alpha) and self.alpha are python doubles turned float32 by numpy (launch_squares_ema)
+    T.ms.one_minus = (float)(1.0 - q.model_alpha);
+    T.ms.alpha = (float)q.model_alpha;
+    T.ms.z_thresh = (float)c.z_threshold;
+    T.ms.mean = (float*)q.d_mean.p;
+    T.ms.var = (float*)q.d_var.p;
+    T.ms.sd = (float*)q.d_var.p + q.plane_total;
     T.z_thresh = (float)c.z_threshold;
     T.stats = (cbv_sq_stats*)q.d_stats.p;
     T.dec = (u8*)q.d_dec.p;
@@ -208,7 +223,8 @@ static BoardDev board_dev(const Board& q, size_t lds[2])
     return T;
 }
 
-// Rebuild the boards' kernel arguments whenever a board is set up, attached, detached or calibrated.  The device table
+// Rebuild the boards' kernel arguments whenever a board is set up, attached, detached or calibrated, or its model-update
+// mode changes.  The device table
 // and the maxima of the multi-board launches exist only with boards attached.  Nothing may be in flight: the callers
 // joined the runs.
 static int pipeline_tables(Pipe& P)
@@ -216,7 +232,7 @@ static int pipeline_tables(Pipe& P)
     cbv_ctx* ctx = P.ctx;
     const int nb = (int)P.boards.size();
     P.tab.resize(nb);
-    P.any_hough = false;
+    P.any_hough = P.any_adaptive = false;
     P.hough_lds[0] = P.hough_lds[1] = 0;
     P.max_px = P.max_S = 0;
     for (int k = 0; k < nb; k++) {
@@ -232,6 +248,7 @@ static int pipeline_tables(Pipe& P)
             P.hough_lds[0] = std::max(P.hough_lds[0], lds[0]);
             P.hough_lds[1] = std::max(P.hough_lds[1], lds[1]);
         }
+        P.any_adaptive = P.any_adaptive || q.adaptive();
         P.max_px = std::max(P.max_px, q.max_px);
         P.max_S = std::max(P.max_S, q.cfg.board_size);
     }
@@ -568,6 +585,42 @@ extern "C" int cbv_pipeline_calibrate(cbv_pipeline* p, int slot)
     return pipeline_tables(P); // the board's statistics read its model from now on
 }
 
+extern "C" int cbv_pipeline_set_model_update(cbv_pipeline* p, int mode, double alpha)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_pipeline_set_model_update: the board is null");
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    if (mode != CBV_MODEL_FROZEN && mode != CBV_MODEL_EVERY && mode != CBV_MODEL_UNCHANGED)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_set_model_update: unknown mode %d", mode);
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_set_model_update: alpha %g is outside [0, 1]", alpha);
+    CBV_ENTER(ctx);
+    if (B.model_mode == mode && B.model_alpha == alpha) return CBV_OK;
+    // The runs in flight keep their arguments, and what comes next is ordered behind their scans: a board that turns
+    // frozen has its model read by the lanes of the next run, which fork from this stream.
+    RC(join_scan(P));
+    B.model_mode = mode;
+    B.model_alpha = alpha;
+    return P.configured ? pipeline_tables(P) : CBV_OK;
+}
+
+extern "C" int cbv_pipeline_model(cbv_pipeline* p, int which, int roi, float* out)
+{
+    if (!p || !out) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_model: null argument");
+    Pipe& P = *p->pipe;
+    const Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    if (!P.configured || !B.calibrated) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_model: the board is not calibrated");
+    if ((which != 0 && which != 1) || roi < 0 || roi >= B.cfg.n_rois) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_model: bad plane %d or square %d", which, roi);
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // the model scans of the runs in flight
+    const SquareDesc& d = B.descs[roi];
+    const float* src = (const float*)(which == 0 ? B.d_mean.p : B.d_var.p) + d.plane_off;
+    CBV_HIP(ctx, hipMemcpyAsync(out, src, sizeof(float) * d.w * d.h, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
 extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int reset_noise)
 {
     if (!p || !p->pipe->configured) return CBV_ERR_STATE;
@@ -819,6 +872,7 @@ static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, b
         const int nb = (int)P.boards.size();
         if (P.any_hough)
             RC(launch_hough_mb(ctx, tab, nb, slot0, (const u32*)rec->retry.p, CBV_MAX_SQUARES * nb * count, P.hough_lds[1], nullptr, 0, 1));
+        if (P.any_adaptive) RC(launch_model_scan_mb(ctx, tab, nb, slot0, count, P.max_px));
         RC(launch_scan_mb(ctx, tab, nb, slot0, count, mirrored ? 1 : 0));
     } else {
         const BoardDev& T = P.tab[0];
@@ -827,6 +881,9 @@ static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, b
         if (T.want_hough) // squares whose first HoughCircles pass overflowed (normally none), before the scan reads the decisions
             RC(launch_hough_second(ctx, T.descs, T.n, gray, T.plane_total, P.b0().hough_cfg, T.hough + (size_t)CBV_MAX_SQUARES * slot0, dec,
                                    (const u32*)rec->retry.p, T.n * count));
+        // the z-score statistics and the model update of a board whose model follows the frames, before the scan reads the classes
+        if (P.any_adaptive)
+            RC(launch_model_scan(ctx, T.descs, T.n, gray, T.plane_total, T.ms, T.stats + (size_t)T.n * slot0, dec, count, P.b0().max_px));
         ResultMirror mir;
         if (mirrored) {
             mir.records = T.mirror + slot0;

@@ -4,6 +4,8 @@
 //                         (REFLECT_101 at the square's own edges)
 //   k_squares_stats       every sum the host/device decision chains need
 //   k_squares_calibrate / _ema / _set_ref   background-model state updates
+//   k_model_scan          the pipeline's z-score statistics + model update over
+//                         the frames of a run, in frame order
 //   k_scan                detect_all_pieces' temporal logic over a batch of
 //                         frames: 64 independent per-square chains
 #include "cbv_device.h"
@@ -628,6 +630,251 @@ int launch_squares_set_ref_mask(cbv_ctx* ctx, const SquareDesc* descs, int n, co
 int launch_squares_set_ref(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, u8* ref, const u8* select)
 {
     hipLaunchKernelGGL(k_squares_set_ref, dim3(n), dim3(256), 0, ctx->stream, descs, gray, ref, select);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// k_model_scan: the ChangeDetector half of a run when the board's model follows the frames
+// (cbv_pipeline_set_model_update).  Per frame t, in order: detect_changes_detailed's z-score statistics against the model
+// as frame t - 1 left it (change_detector.py:131-139: z_count, z_max and the class bits of the decision byte, which
+// k_squares_pre5_stats leaves clear for such a board), then update_all_references (change_detector.py:77-92) with
+// k_squares_ema's arithmetic, on every square (CBV_MODEL_EVERY) or on the squares the frame did not report
+// (CBV_MODEL_UNCHANGED).  The model after frame t feeds frame t + 1, so the frames are a chain; the pixels are not:
+// one workgroup per square, each lane keeps mean / variance / sd of MS_PPL consecutive pixels in registers for the whole
+// run, the frames' gray bytes (already in memory, one 8-byte load per lane and frame) are fetched MS_DEPTH frames ahead,
+// and the only exchange per frame is the count (ballot + popcount per wave, one LDS word per wave, ONE barrier: the words
+// are double-buffered by frame parity).  Squares of more than MS_PPL * blockDim.x pixels leave the model in memory.
+// ---------------------------------------------------------------------------
+#define MS_PPL 8
+#define MS_DEPTH 4
+#define MS_MAXW 16 // waves of the largest workgroup
+
+// one pixel of update_all_references: k_squares_ema's body
+__device__ __forceinline__ void ms_ema_px(float gv, float one_minus, float alpha, float& mu, float& va, float& sd)
+{
+    const float m1 = one_minus * mu;
+    const float m2 = alpha * gv;
+    const float nm = m1 + m2;
+    const float df = gv - nm;
+    const float d2 = df * df;
+    const float v1 = one_minus * va;
+    const float v2 = alpha * d2;
+    float nv = v1 + v2;
+    if (!(nv >= 10.0f)) nv = (nv != nv) ? nv : 10.0f; // np.maximum propagates NaN
+    mu = nm;
+    va = nv;
+    sd = d_sqrt_rn(nv);
+}
+
+// one pixel of the z-score statistics: sq_accum_px's model part
+__device__ __forceinline__ void ms_z_px(float gv, float mu, float sd, float z_thresh, bool& over, bool& isnan, float& zmax)
+{
+    const float df = fabsf(gv - mu);
+    const float z = __fdiv_rn(df, sd);
+    over = z > z_thresh;
+    isnan = z != z;
+    if (!isnan) zmax = fmaxf(zmax, z);
+}
+
+// the waves' partial results of a frame -> the square's: z_count, z_max (NaN if any z was), and whether the square is in
+// the frame's result dict (sq_accum_finish's thresholds); thread 0 writes the record and the decision bits
+__device__ __forceinline__ bool ms_frame_finish(const uint2* part, int nw, int n, cbv_sq_stats* __restrict__ st, u8* __restrict__ dc, u32 dc_in)
+{
+    u32 cnt = 0, nanf_ = 0;
+    float z = 0.f;
+    for (int k = 0; k < nw; k++) {
+        const uint2 v = part[k];
+        cnt += v.x & 0x7fffffffu;
+        nanf_ |= v.x >> 31;
+        z = fmaxf(z, __uint_as_float(v.y));
+    }
+    const double pct = ((double)cnt / (double)n) * 100.0; // change_detector.py:139 as a Python float
+    const bool in_dict = !(pct < 5.0);
+    if (threadIdx.x == 0) {
+        st->z_count = cnt;
+        st->z_max = nanf_ ? __builtin_nanf("") : z;
+        u32 b = dc_in & ~14u;
+        if (in_dict) b |= 2u | (pct > 75.0 ? 8u : (pct > 15.0 ? 4u : 0u));
+        *dc = (u8)b;
+    }
+    return in_dict;
+}
+
+template <bool REG>
+__device__ __forceinline__ void model_scan_body(const SquareDesc d, const u8* __restrict__ gray, size_t gray_frame_stride,
+                                                const ModelScan ms, cbv_sq_stats* __restrict__ stats, int nsq,
+                                                u8* __restrict__ decisions, int count, int sq, uint2 (*part)[MS_MAXW])
+{
+    const int n = d.w * d.h, npad = (n + 15) & ~15;
+    const int nw = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);
+    const bool every = ms.mode == CBV_MODEL_EVERY;
+    float* __restrict__ meanp = ms.mean + d.plane_off;
+    float* __restrict__ varp = ms.var + d.plane_off;
+    float* __restrict__ sdp = ms.sd + d.plane_off;
+    const u8* g0 = gray + d.plane_off;
+    if (REG) {
+        // pixels i0 .. i0 + 7 of the square; planes are 16-element aligned and padded, so a lane's vectors are inside the
+        // plane whenever its first pixel is (the padding's model values are carried along and never used)
+        const int i0 = (int)threadIdx.x * MS_PPL;
+        const bool active = i0 < npad;
+        float mu[MS_PPL], va[MS_PPL], sd[MS_PPL];
+#pragma unroll
+        for (int k = 0; k < MS_PPL; k++) mu[k] = va[k] = 0.f, sd[k] = 1.f;
+        if (active) {
+#pragma unroll
+            for (int h = 0; h < MS_PPL / 4; h++) {
+                const float4 a = ((const float4*)(meanp + i0))[h], b = ((const float4*)(varp + i0))[h], c = ((const float4*)(sdp + i0))[h];
+                mu[4 * h] = a.x, mu[4 * h + 1] = a.y, mu[4 * h + 2] = a.z, mu[4 * h + 3] = a.w;
+                va[4 * h] = b.x, va[4 * h + 1] = b.y, va[4 * h + 2] = b.z, va[4 * h + 3] = b.w;
+                sd[4 * h] = c.x, sd[4 * h + 1] = c.y, sd[4 * h + 2] = c.z, sd[4 * h + 3] = c.w;
+            }
+        }
+        // the frames' gray bytes and decision byte, MS_DEPTH frames ahead: a shift register, so the frame loop stays rolled
+        uint2 ring[MS_DEPTH];
+        u32 dring[MS_DEPTH];
+        auto fetch = [&](int t, uint2& dst, u32& ddst) {
+            dst = active ? *(const uint2*)(g0 + (size_t)t * gray_frame_stride + i0) : make_uint2(0, 0);
+            ddst = threadIdx.x == 0 ? decisions[(size_t)t * CBV_MAX_SQUARES + sq] : 0u;
+        };
+#pragma unroll
+        for (int j = 0; j < MS_DEPTH; j++) {
+            ring[j] = make_uint2(0, 0), dring[j] = 0;
+            if (j < count) fetch(j, ring[j], dring[j]);
+        }
+#pragma unroll 1
+        for (int t = 0; t < count; t++) {
+            const uint2 cur = ring[0];
+            const u32 dc_in = dring[0];
+#pragma unroll
+            for (int j = 0; j + 1 < MS_DEPTH; j++) ring[j] = ring[j + 1], dring[j] = dring[j + 1];
+            if (t + MS_DEPTH < count) fetch(t + MS_DEPTH, ring[MS_DEPTH - 1], dring[MS_DEPTH - 1]);
+            float gv[MS_PPL];
+#pragma unroll
+            for (int k = 0; k < MS_PPL; k++) gv[k] = (float)(((k < 4 ? cur.x : cur.y) >> ((k & 3) * 8)) & 255u);
+            u32 cnt = 0, nanw = 0;
+            float zmax = 0.f;
+#pragma unroll
+            for (int k = 0; k < MS_PPL; k++) {
+                bool over = false, isnan = false;
+                if (i0 + k < n) ms_z_px(gv[k], mu[k], sd[k], ms.z_thresh, over, isnan, zmax);
+                cnt += (u32)__popcll(__ballot(over));
+                nanw |= __ballot(isnan) != 0ull ? 1u : 0u;
+            }
+            zmax = wave_max_f32(zmax);
+            if ((threadIdx.x & 63) == 0) part[t & 1][wave] = make_uint2(cnt | (nanw << 31), __float_as_uint(zmax));
+            __syncthreads();
+            // CBV_MODEL_EVERY: the update does not depend on the count, only wave 0 (thread 0 writes the record) combines it
+            bool update = true;
+            if (!every || wave == 0) {
+                const bool in_dict = ms_frame_finish(part[t & 1], nw, n, stats + (size_t)t * nsq + sq, decisions + (size_t)t * CBV_MAX_SQUARES + sq, dc_in);
+                update = every || !in_dict;
+            }
+            if (update) {
+#pragma unroll
+                for (int k = 0; k < MS_PPL; k++)
+                    if (i0 + k < n) ms_ema_px(gv[k], ms.one_minus, ms.alpha, mu[k], va[k], sd[k]);
+            }
+        }
+        if (active) {
+#pragma unroll
+            for (int h = 0; h < MS_PPL / 4; h++) {
+                ((float4*)(meanp + i0))[h] = make_float4(mu[4 * h], mu[4 * h + 1], mu[4 * h + 2], mu[4 * h + 3]);
+                ((float4*)(varp + i0))[h] = make_float4(va[4 * h], va[4 * h + 1], va[4 * h + 2], va[4 * h + 3]);
+                ((float4*)(sdp + i0))[h] = make_float4(sd[4 * h], sd[4 * h + 1], sd[4 * h + 2], sd[4 * h + 3]);
+            }
+        }
+    } else {
+        // the model stays in memory; a lane owns the same pixels in every frame, so its own stores order the chain
+        for (int t = 0; t < count; t++) {
+            const u8* g = g0 + (size_t)t * gray_frame_stride;
+            const u32 dc_in = threadIdx.x == 0 ? decisions[(size_t)t * CBV_MAX_SQUARES + sq] : 0u;
+            u32 cnt = 0, nanw = 0;
+            float zmax = 0.f;
+            for (int base = 0; base < n; base += (int)blockDim.x) { // (uniform trip count: the ballots see whole waves)
+                const int i = base + (int)threadIdx.x;
+                bool over = false, isnan = false;
+                if (i < n) {
+                    const float gv = (float)g[i];
+                    float mu = meanp[i], sd = sdp[i];
+                    ms_z_px(gv, mu, sd, ms.z_thresh, over, isnan, zmax);
+                    if (every) {
+                        float va = varp[i];
+                        ms_ema_px(gv, ms.one_minus, ms.alpha, mu, va, sd);
+                        meanp[i] = mu, varp[i] = va, sdp[i] = sd;
+                    }
+                }
+                cnt += (u32)__popcll(__ballot(over));
+                nanw |= __ballot(isnan) != 0ull ? 1u : 0u;
+            }
+            zmax = wave_max_f32(zmax);
+            if ((threadIdx.x & 63) == 0) part[t & 1][wave] = make_uint2(cnt | (nanw << 31), __float_as_uint(zmax));
+            __syncthreads();
+            if (every && wave != 0) continue;
+            const bool in_dict = ms_frame_finish(part[t & 1], nw, n, stats + (size_t)t * nsq + sq, decisions + (size_t)t * CBV_MAX_SQUARES + sq, dc_in);
+            if (!every && !in_dict) {
+                for (int i = threadIdx.x; i < n; i += blockDim.x) {
+                    float mu = meanp[i], va = varp[i], sd = sdp[i];
+                    ms_ema_px((float)g[i], ms.one_minus, ms.alpha, mu, va, sd);
+                    meanp[i] = mu, varp[i] = va, sdp[i] = sd;
+                }
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void model_scan_square(const SquareDesc* __restrict__ descs, const u8* __restrict__ gray, size_t gray_frame_stride,
+                                                  const ModelScan ms, cbv_sq_stats* __restrict__ stats, int nsq, u8* __restrict__ decisions,
+                                                  int count, uint2 (*part)[MS_MAXW])
+{
+    const SquareDesc d = descs[blockIdx.x];
+    if (d.w * d.h <= MS_PPL * (int)blockDim.x) model_scan_body<true>(d, gray, gray_frame_stride, ms, stats, nsq, decisions, count, blockIdx.x, part);
+    else model_scan_body<false>(d, gray, gray_frame_stride, ms, stats, nsq, decisions, count, blockIdx.x, part);
+}
+
+__global__ __launch_bounds__(1024) void k_model_scan(const SquareDesc* __restrict__ descs, const u8* __restrict__ gray, size_t gray_frame_stride,
+                                                      const ModelScan ms, cbv_sq_stats* __restrict__ stats, int nsq,
+                                                      u8* __restrict__ decisions, int count)
+{
+    __shared__ uint2 part[2][MS_MAXW];
+    model_scan_square(descs, gray, gray_frame_stride, ms, stats, nsq, decisions, count, part);
+}
+
+// every board of a pipeline: grid (CBV_MAX_SQUARES, boards); boards whose model is frozen (or not calibrated) leave
+__global__ __launch_bounds__(1024) void k_model_scan_mb(const BoardDev* __restrict__ tab, int s0, int count)
+{
+    __shared__ uint2 part[2][MS_MAXW];
+    const BoardDev& T = tab[blockIdx.y];
+    if ((int)blockIdx.x >= T.n || T.ms.mode == CBV_MODEL_FROZEN) return;
+    const size_t s = (size_t)s0;
+    model_scan_square(T.descs, T.gray + s * T.plane_total, T.plane_total, T.ms, T.stats + s * T.n, T.n, T.dec + s * CBV_MAX_SQUARES, count, part);
+}
+
+// lanes of a workgroup: enough for the largest square at MS_PPL pixels a lane, whole waves, at most 1024
+static int model_scan_threads(int max_px)
+{
+    if (max_px <= 0 || max_px > MS_PPL * 1024) return 1024;
+    const int lanes = (max_px + MS_PPL - 1) / MS_PPL;
+    return (lanes + 63) & ~63;
+}
+
+int launch_model_scan(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, ModelScan ms,
+                      cbv_sq_stats* stats, u8* decisions, int count, int max_px)
+{
+    if (ms.mode == CBV_MODEL_FROZEN) return CBV_OK;
+    prof_begin(ctx, CBV_K_MODEL_SCAN);
+    hipLaunchKernelGGL(k_model_scan, dim3(n), dim3(model_scan_threads(max_px)), 0, ctx->stream, descs, gray, gray_frame_stride, ms, stats, n,
+                       decisions, count);
+    prof_end(ctx, CBV_K_MODEL_SCAN);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_model_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int max_px)
+{
+    prof_begin(ctx, CBV_K_MODEL_SCAN);
+    hipLaunchKernelGGL(k_model_scan_mb, dim3(CBV_MAX_SQUARES, nb), dim3(model_scan_threads(max_px)), 0, ctx->stream, tab, s0, count);
+    prof_end(ctx, CBV_K_MODEL_SCAN);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }

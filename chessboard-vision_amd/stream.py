@@ -88,6 +88,28 @@ class _BoardMethods:
         every square's change (LEVE / PARCIAL / TOTAL) against that background model."""
         self.ctx.check(self.ctx.lib.cbv_pipeline_calibrate(self.h_, slot))
 
+    def set_model_update(self, mode="frozen", alpha=0.1):
+        """What happens to the ChangeDetector model after each frame of the runs enqueued from now on: "frozen" (default)
+        nothing, "every" ChangeDetector.update_all_references on all squares, "unchanged" the same on the squares the
+        frame did not report only (include/cbv.h, cbv_pipeline_set_model_update).  `alpha` is ChangeDetector.alpha."""
+        if not isinstance(mode, int):
+            if str(mode).lower() not in N.MODEL_MODES:
+                raise ValueError("model update mode %r: expected one of %s" % (mode, ", ".join(sorted(N.MODEL_MODES))))
+            mode = N.MODEL_MODES[str(mode).lower()]
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_model_update(self.h_, mode, float(alpha)))
+
+    def model(self, pos):
+        """(mean, variance) float32 planes of the square at (file, rank) after every run enqueued so far:
+        ChangeDetector.means[pos], .variances[pos]."""
+        roi = {(c, 7 - r): i for i, (r, c) in enumerate(self.rois_rc)}[tuple(pos)]
+        w, h = self._cfg.rois[roi].w, self._cfg.rois[roi].h
+        planes = []
+        for which in (0, 1):
+            out = np.empty((h, w), np.float32)
+            self.ctx.check(self.ctx.lib.cbv_pipeline_model(self.h_, which, roi, N.ptr(out)))
+            planes.append(out)
+        return planes[0], planes[1]
+
     def hough(self, slot):
         """HoughCircles outcome of every square of a processed slot (index = roi)."""
         out = (N.HoughResult * N.MAX_SQUARES)()

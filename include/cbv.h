@@ -127,7 +127,7 @@ CBV_API const char* cbv_device_name(const cbv_ctx* ctx);
 enum {
     CBV_K_COLOR_LAB_HIST = 0, CBV_K_CLAHE_LUT, CBV_K_CLAHE_APPLY, CBV_K_BILATERAL, CBV_K_SHARPEN,
     CBV_K_NORM_LUT, CBV_K_NORMALIZE, CBV_K_WARP, CBV_K_SQUARES, CBV_K_GRAY_BLUR, CBV_K_OTSU,
-    CBV_K_THRESHOLD, CBV_K_SCAN, CBV_K_SYNTH, CBV_K_RESET, CBV_K_HOUGH, CBV_K_INGEST, CBV_K_COUNT
+    CBV_K_THRESHOLD, CBV_K_SCAN, CBV_K_SYNTH, CBV_K_RESET, CBV_K_HOUGH, CBV_K_INGEST, CBV_K_MODEL_SCAN, CBV_K_COUNT
 };
 CBV_API int cbv_profile_enable(cbv_ctx* ctx, int kid /* -1 = all, -2 = none */);
 CBV_API int cbv_profile_read(cbv_ctx* ctx, int kid, double* total_ms, long long* launches);
@@ -524,7 +524,7 @@ typedef struct {
 /* Attach a board to a configured pipeline `parent` (not itself a board handle) and return its handle in *board.
  * cbv_pipeline_run(parent, ...) then processes every attached board for those slots.  A board handle is accepted by the
  * per-board calls, which act on that board alone: cbv_pipeline_results, _noise_results, _square_stats, _hough,
- * _download (which = 2), _calibrate, _update_references, _set_check_squares, _reset_state.  On a board handle
+ * _download (which = 2), _calibrate, _update_references, _set_check_squares, _reset_state, _set_model_update, _model.  On a board handle
  * cbv_pipeline_run, _upload, _upload_raw, _submit, _set_input_format, _synth, _configure, _host_ring and _download with
  * which 0 or 1 fail with CBV_ERR_STATE (_host_ring returns NULL, _host_slot_bytes 0); cbv_pipeline_reset_state(parent) resets board 0 only.
  * Lifecycle: cbv_pipeline_destroy(board) detaches and frees the board (the other boards are unchanged);
@@ -534,6 +534,39 @@ typedef struct {
  * attach and detach.  Fails with CBV_ERR_ARG on bad arguments (those cbv_pipeline_configure rejects, or a ninth board),
  * and leaves the parent and its other boards as they were on any failure. */
 CBV_API int cbv_pipeline_add_board(cbv_pipeline* parent, const cbv_board_config* b, cbv_pipeline** board);
+
+/* ------------------------------------------------------------------ */
+/* per-frame update of the ChangeDetector background model             */
+/* ------------------------------------------------------------------ */
+/* cbv_pipeline_calibrate captures the model once; by default it then stays as it is and every later frame is compared
+ * with the calibration frame.  With a model-update mode the board also runs the second half of the reference's class,
+ * ChangeDetector.update_all_references (change_detector.py:67-92), after every frame: for each frame of a run in slot
+ * order (and the runs in the order they were enqueued), first detect_changes_detailed against the model as the frame
+ * before left it (`changed`, `parcial`, `total` of cbv_frame_result and `z_count`, `z_max` of cbv_pipeline_square_stats,
+ * change_detector.py:105-167), then
+ *   CBV_MODEL_FROZEN     nothing (the default);
+ *   CBV_MODEL_EVERY      update_all_references(squares) with no focus squares: mean = (1 - alpha) mean + alpha gray,
+ *                        var = max((1 - alpha) var + alpha (gray - new mean)^2, 10) on every pixel of every square
+ *                        (change_detector.py:77-92), float32 with one rounding per operation, as cbv_squares_ema does it;
+ *   CBV_MODEL_UNCHANGED  the same update on the squares that are NOT in the frame's result dict (pct_changed < 5,
+ *                        change_detector.py:139-141) only, i.e. set_focus_squares(all - reported), update_all_references,
+ *                        clear_focus (change_detector.py:49-65): a square under a hand or a piece that has just moved
+ *                        keeps its model until the caller calibrates again, the others follow the light.  A frame that
+ *                        reports every square updates none.
+ * The PieceDetector side of the results (raw / stable occupancy, visual_changes, processed, circular, NoiseHandler) does
+ * not read the model and is the same in every mode. */
+#define CBV_MODEL_FROZEN    0
+#define CBV_MODEL_EVERY     1
+#define CBV_MODEL_UNCHANGED 2
+/* Mode and `alpha` (ChangeDetector's attribute, change_detector.py:25: 0.1) of one board, any board handle.  Applies to
+ * the runs enqueued after the call; runs in flight keep what they were launched with.  Allowed before or after
+ * cbv_pipeline_calibrate: an uncalibrated board has no model and nothing is updated until it is calibrated.
+ * CBV_ERR_ARG for an unknown mode or an alpha outside [0, 1], and then nothing has changed. */
+CBV_API int cbv_pipeline_set_model_update(cbv_pipeline* board, int mode, double alpha);
+/* The model of square `roi` after every run enqueued so far (waits for them): which = 0 the mean plane
+ * (change_detector.py:44), 1 the variance plane (change_detector.py:45), `out` = w * h floats, row major.  Read only.
+ * CBV_ERR_STATE while the board is not calibrated. */
+CBV_API int cbv_pipeline_model(cbv_pipeline* board, int which, int roi, float* out);
 
 #ifdef __cplusplus
 }
