@@ -134,7 +134,7 @@ class PipelineConfig(C.Structure):
                 ("n_rois", C.c_int32), ("rois", Roi * MAX_SQUARES), ("history_size", C.c_int32),
                 ("min_presence", C.c_double), ("change_threshold", C.c_double), ("chunk", C.c_int32),
                 ("lanes", C.c_int32), ("z_threshold", C.c_double), ("initial_variance", C.c_double), ("keep_enhanced", C.c_int32),
-                ("use_hough", C.c_int32), ("hough", HoughParams), ("enhance_region", C.c_int32)]
+                ("use_hough", C.c_int32), ("hough", HoughParams), ("enhance_region", C.c_int32), ("skip_enhance", C.c_int32)]
 
 
 class BoardConfig(C.Structure):
@@ -178,6 +178,9 @@ K = {name: i for i, name in enumerate(KERNEL_IDS)}
 # Kernels outside the default path (they launch only when a feature is switched on) follow the list above in the
 # library's id space (CBV_K_* of include/cbv.h) and are named in K only.
 K["MODEL_SCAN"] = len(KERNEL_IDS)
+# ... and k_warp_yuv (pipelines without enhancement on raw frames) follows those, under a name of its own
+K_WARP_YUV = K["MODEL_SCAN"] + 1
+K_ALL = dict(K, WARP_YUV=K_WARP_YUV)  # every id by name (K itself stays as tests/test_model_update_host.py pins it)
 
 MODEL_FROZEN, MODEL_EVERY, MODEL_UNCHANGED = 0, 1, 2
 MODEL_MODES = {"frozen": MODEL_FROZEN, "every": MODEL_EVERY, "unchanged": MODEL_UNCHANGED}

@@ -352,6 +352,13 @@ int check_raw_format(cbv_ctx* ctx, int fmt, int w, int h, const char* what);
 int launch_ingest(cbv_ctx* ctx, const u8* plane0, const u8* plane1, RawGeom r, u8* dst, Geom g, int batch);
 // one raw host frame (NV12 / YUYV, strided views) through the context's staging buffer into a BGR device image
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
+// launch_warp on raw frames (k_warp_yuv): the output of launch_ingest followed by launch_warp without a byte map, byte for
+// byte, with no BGR frame in between; g = the frames' width and height.  Interior pixels load both taps of a row at once:
+// 4 bytes at the even column of an NV12 chroma row, 8 bytes at the first tap's pair of a YUYV row, which at sx = w - 2 reach
+// 2 / 4 bytes past the row's w (2 w) bytes.  Callers keep >= 8 readable bytes behind the last row of the last plane of the
+// last frame (the pipeline's raw ring has 256); between rows and frames the bytes read belong to the next row or frame.
+int launch_warp_yuv(cbv_ctx* ctx, const u8* plane0, const u8* plane1, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180,
+                    u8* dst, int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 
 void build_gaussian_q8_sigma(int k, double sigma, int* coef);
 int launch_gray_gauss(cbv_ctx* ctx, const u8* src, int w, int h, int stride, int cn, const int* coef_dev, int k, u8* dst);
@@ -526,6 +533,8 @@ void hough_board_cfgs(HoughCfg base, HoughCfg out[2], size_t lds[2]);
 // one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0
 int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, NormSrc norm, int batch,
                    u32* zero_word, u32* zero_word2);
+int launch_warp_yuv_mb(cbv_ctx* ctx, const u8* plane0, const u8* plane1, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
+                       int batch, u32* zero_word, u32* zero_word2);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);

@@ -44,6 +44,7 @@ struct Pipe {
     Geom g;
     bool configured = false;
     bool keep_enhanced = false;
+    bool skip_enhance = false; // cfg.skip_enhance: the warp samples the frames as they are, no enhancement scratch exists
     int chunk = 8;
     u8* frames = nullptr;
     // Lanes: chunk c runs on lane c % n_lanes, each lane with its own HIP stream and scratch, so a
@@ -67,7 +68,9 @@ struct Pipe {
     // k_ingest converts into `frames` behind the copy
     u8* host_ring = nullptr;
     int in_fmt = CBV_FMT_BGR;
-    u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated with the host ring; null with CBV_FMT_BGR
+    // Without enhancement (skip_enhance) a YUV input format makes the raw ring THE frames: k_warp_yuv samples it, nothing is
+    // converted and `frames` is neither written nor read (raw_mode below).
+    u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated on first use; null with CBV_FMT_BGR
     hipStream_t copy_stream = nullptr;
     struct CopyRec {
         int s0, cnt;
@@ -109,6 +112,7 @@ struct Pipe {
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
     Board& b0() const { return boards[0]->b; }
+    bool raw_mode() const { return skip_enhance && in_fmt != CBV_FMT_BGR; }
 };
 
 // a handle of a board attached by cbv_pipeline_add_board (not board 0, which stands for the whole pipeline)
@@ -454,12 +458,17 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: a board handle is configured by cbv_pipeline_add_board");
     if (P.boards.size() > 1) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_configure: boards are attached (destroy them first)");
     RC(check_board_cfg(ctx, cfg));
-    RC(check_params(ctx, &cfg->enhance));
+    if (cfg->skip_enhance && cfg->keep_enhanced)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_configure: skip_enhance with keep_enhanced (there is no enhanced frame to keep)");
+    if (cfg->skip_enhance && cfg->enhance_region)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_configure: skip_enhance with enhance_region (there is no enhancement to limit)");
+    if (!cfg->skip_enhance) RC(check_params(ctx, &cfg->enhance));
     // every argument check that needs no state is done; from here on a failure leaves the pipeline UNconfigured
     // (run / results / ... return CBV_ERR_STATE) instead of half reconfigured
     P.configured = false;
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     P.keep_enhanced = cfg->keep_enhanced != 0;
+    P.skip_enhance = cfg->skip_enhance != 0;
     int chunk = cfg->chunk;
     if (chunk <= 0) chunk = 32;
     if (chunk > P.max_frames) chunk = P.max_frames;
@@ -478,11 +487,15 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     if (P.enhanced) (void)hipFree(P.enhanced);
     P.enhanced = nullptr;
     if (!P.start_ev) CBV_HIP(ctx, hipEventCreateWithFlags(&P.start_ev, hipEventDisableTiming));
+    if (P.skip_enhance)
+        for (int l = 0; l < Pipe::MAX_LANES; l++) dev_free(&P.lane_small[l]);
     for (int l = 0; l < lanes; l++) {
-        CBV_HIP(ctx, hipMalloc((void**)&P.A[l], P.g.frame_stride * chunk + 256));
-        CBV_HIP(ctx, hipMalloc((void**)&P.B[l], P.g.frame_stride * chunk + 256));
-        SmallLayout SL;
-        RC(small_layout(ctx, &P.lane_small[l], cfg->enhance.tiles_x * cfg->enhance.tiles_y, chunk, &SL, cfg->enhance.tiles_x, cfg->enhance.tiles_y));
+        if (!P.skip_enhance) { // the enhancement's scratch frames, aux blocks and CLAHE tables
+            CBV_HIP(ctx, hipMalloc((void**)&P.A[l], P.g.frame_stride * chunk + 256));
+            CBV_HIP(ctx, hipMalloc((void**)&P.B[l], P.g.frame_stride * chunk + 256));
+            SmallLayout SL;
+            RC(small_layout(ctx, &P.lane_small[l], cfg->enhance.tiles_x * cfg->enhance.tiles_y, chunk, &SL, cfg->enhance.tiles_x, cfg->enhance.tiles_y));
+        }
         RC(dev_ensure(ctx, &P.lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * chunk)));
         if (l > 0) RC(ctx_worker_stream(ctx, &ctx->lane_streams[l], &P.lane_stream[l]));
         if (!P.lane_done[l]) CBV_HIP(ctx, hipEventCreateWithFlags(&P.lane_done[l], hipEventDisableTiming));
@@ -636,6 +649,23 @@ extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int res
     return CBV_OK;
 }
 
+// the raw-frame mode (Pipe::raw_mode) has no BGR frames to write
+static const char* const kRawModeMsg = "the pipeline runs without enhancement on a YUV input format (raw mode): its frames are the raw "
+                                       "ring, written by cbv_pipeline_upload_raw or cbv_pipeline_submit in that format";
+
+// the device ring of raw frames in the current (YUV) input format
+static int ensure_raw_ring(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    if (P.raw_ring) return CBV_OK;
+    const size_t bytes = tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride * P.max_frames;
+    if (hipMalloc((void**)&P.raw_ring, bytes + 256) != hipSuccess) {
+        P.raw_ring = nullptr;
+        return cbv_fail(ctx, CBV_ERR_HIP, "device ring of %zu bytes for the raw frames could not be allocated", bytes);
+    }
+    return CBV_OK;
+}
+
 extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr, int stride)
 {
     if (p && attached(p)) return cbv_fail(p->pipe->ctx, CBV_ERR_STATE, "cbv_pipeline_upload: frames go to the parent of a board");
@@ -643,6 +673,7 @@ extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr
     Pipe& P = *p->pipe;
     cbv_ctx* ctx = P.ctx;
     CBV_ENTER(ctx);
+    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload: %s", kRawModeMsg);
     RC(join_scan(P)); // lanes and scan of the last run
     RC(rows_h2d(ctx, P.frames + P.g.frame_stride * slot, bgr, stride, P.w * 3, P.h));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -659,6 +690,22 @@ extern "C" int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_
     RC(check_raw_format(ctx, raw->fmt, P.w, P.h, "cbv_pipeline_upload_raw"));
     CBV_ENTER(ctx);
     RC(join_scan(P)); // lanes and scan of the last run
+    if (P.raw_mode()) { // the frame as it is into its slot of the raw ring, rows packed
+        if (raw->fmt != P.in_fmt)
+            return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: format %d, but %s (format %d)", raw->fmt, kRawModeMsg, P.in_fmt);
+        const bool nv12 = raw->fmt == CBV_FMT_NV12;
+        const int wb0 = nv12 ? P.w : 2 * P.w;
+        if (!raw->plane0 || raw->stride0 < wb0 || (nv12 && (!raw->plane1 || raw->stride1 < P.w)))
+            return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_upload_raw: bad planes or strides of the raw frame (stride0=%d stride1=%d)", raw->stride0, raw->stride1);
+        RC(ensure_raw_ring(P));
+        // the raw ring is the only frame store here: a copy of this slot that cbv_pipeline_submit left in flight lands first
+        if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+        u8* dst = P.raw_ring + tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride * slot;
+        RC(rows_h2d(ctx, dst, raw->plane0, raw->stride0, wb0, P.h));
+        if (nv12) RC(rows_h2d(ctx, dst + (size_t)P.w * P.h, raw->plane1, raw->stride1, P.w, P.h / 2));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return CBV_OK;
+    }
     RC(raw_h2d_convert(ctx, raw, P.w, P.h, P.frames + P.g.frame_stride * slot, P.g, "cbv_pipeline_upload_raw"));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CBV_OK;
@@ -684,6 +731,10 @@ extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
     CBV_ENTER(ctx);
     // the copies and conversions in flight read the rings that go away here (both run on the copy stream)
     if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+    if (P.raw_mode()) { // ... and so do the runs in flight
+        RC(join_scan(P));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     if (P.host_ring) (void)hipHostFree(P.host_ring);
     if (P.raw_ring) (void)hipFree(P.raw_ring);
     P.host_ring = P.raw_ring = nullptr;
@@ -707,10 +758,9 @@ extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)
         if (hipHostMalloc((void**)&P.host_ring, bytes, hipHostMallocDefault) != hipSuccess) {
             cbv_fail(ctx, CBV_ERR_HIP, "pinned host ring of %zu bytes could not be allocated", bytes);
             P.host_ring = nullptr;
-        } else if (P.in_fmt != CBV_FMT_BGR && hipMalloc((void**)&P.raw_ring, bytes + 256) != hipSuccess) {
-            cbv_fail(ctx, CBV_ERR_HIP, "cbv_pipeline_host_ring: device ring of %zu bytes for the raw frames could not be allocated", bytes);
+        } else if (P.in_fmt != CBV_FMT_BGR && ensure_raw_ring(P) != CBV_OK) {
             (void)hipHostFree(P.host_ring);
-            P.host_ring = P.raw_ring = nullptr;
+            P.host_ring = nullptr;
         }
     }
     return P.host_ring;
@@ -738,13 +788,21 @@ extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
         // is the copy -> conversion dependency and keeps a later copy off raw slots an earlier conversion still reads, and
         // the one event below stands for both.  Only the conversion writes the frames the runs in flight read, so the copy
         // itself does not wait for them.
+        // In raw mode the copy is all: the runs read the raw ring itself, so it is the copy that waits for them.
         const RawGeom rg = tight_raw_geom(P.in_fmt, P.w, P.h);
         u8* raw = P.raw_ring + rg.frame_stride * slot0;
+        hipEvent_t read_ev = reader ? (reader->one_event ? reader->scan_ev : reader->lanes_ev) : nullptr;
+        if (read_ev && P.raw_mode()) { // (the wait goes in front of the copy)
+            CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, read_ev, 0));
+            read_ev = nullptr;
+        }
         CBV_HIP(ctx, hipMemcpyAsync(raw, P.host_ring + rg.frame_stride * slot0, rg.frame_stride * count, hipMemcpyHostToDevice, P.copy_stream));
-        if (reader) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, reader->one_event ? reader->scan_ev : reader->lanes_ev, 0));
+        if (read_ev) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, read_ev, 0));
         hipStream_t caller = ctx->stream;
         ctx->stream = P.copy_stream;
-        const int rc = launch_ingest(ctx, raw, P.in_fmt == CBV_FMT_NV12 ? raw + (size_t)P.w * P.h : nullptr, rg, P.frames + P.g.frame_stride * slot0, P.g, count);
+        const int rc = P.raw_mode() ? CBV_OK
+                                    : launch_ingest(ctx, raw, P.in_fmt == CBV_FMT_NV12 ? raw + (size_t)P.w * P.h : nullptr, rg,
+                                                    P.frames + P.g.frame_stride * slot0, P.g, count);
         ctx->stream = caller;
         RC(rc);
     }
@@ -785,6 +843,7 @@ extern "C" int cbv_pipeline_synth(cbv_pipeline* p, int slot0, int count, const u
     Pipe& P = *p->pipe;
     cbv_ctx* ctx = P.ctx;
     CBV_ENTER(ctx);
+    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_synth: %s", kRawModeMsg);
     RC(join_scan(P)); // lanes and scan of the last run
     size_t o_seeds = 0, o_h = (size_t)count * 8, o_b = o_h + 72, o_s = (o_b + (size_t)count * 64 + 15) & ~(size_t)15;
     size_t total = o_s + sizeof(cbv_scene);
@@ -805,13 +864,22 @@ extern "C" int cbv_pipeline_synth(cbv_pipeline* p, int slot0, int count, const u
 
 // the per-board stages of a chunk of b frames from slot s0 (warp, square statistics, HoughCircles' first pass): with boards
 // attached one launch each for all of them, otherwise the single-board launches with board 0's arguments
+// (res = the BGR frames the warp samples; in raw mode null, and the warp samples the chunk's slots of the raw ring)
 static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, int b, u32* work, u32* retry0, u32* retry, int retry_base)
 {
     cbv_ctx* ctx = P.ctx;
+    RawGeom rg = {};
+    const u8 *raw0 = nullptr, *raw1 = nullptr; // raw mode: the chunk's luma (or YUYV) plane and NV12's chroma plane
+    if (!res) {
+        rg = tight_raw_geom(P.in_fmt, P.w, P.h);
+        raw0 = P.raw_ring + rg.frame_stride * s0;
+        if (P.in_fmt == CBV_FMT_NV12) raw1 = raw0 + (size_t)P.w * P.h;
+    }
     if (P.boards.size() > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         const int nb = (int)P.boards.size();
-        RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
+        if (raw0) RC(launch_warp_yuv_mb(ctx, raw0, raw1, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
+        else RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
         if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, P.hough_lds[0], retry, retry_base, 0));
         return CBV_OK;
@@ -821,7 +889,8 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     u8* gray = T.gray + T.plane_total * s0;
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
     cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
-    RC(launch_warp(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, norm, b, work, retry0));
+    if (raw0) RC(launch_warp_yuv(ctx, raw0, raw1, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
+    else RC(launch_warp(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, norm, b, work, retry0));
     RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
                                  T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));
     if (T.want_hough) RC(launch_hough(ctx, T.descs, T.n, gray, T.plane_total, P.b0().hough_cfg, hres, dec, work, b, retry, retry_base));
@@ -911,6 +980,7 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
     if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: a board is run by its parent");
     if (slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_run: bad slot range");
     CBV_ENTER(ctx);
+    if (P.raw_mode() && !P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: no raw frame was ever uploaded or submitted");
     const cbv_enhance_params& enh = P.b0().cfg.enhance;
     // Lane 0 is the context's stream; lanes 1.. are worker streams forked from it and joined before
     // the temporal scan (which needs every frame's statistics, in order).
@@ -969,18 +1039,22 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
     for (int s0 = slot0; s0 < slot0 + count && rc_all == CBV_OK; s0 += P.chunk, ci++) {
         const int lane = (lane_base + ci) % P.n_lanes;
         ctx->stream = lane == 0 ? main_stream : P.lane_stream[lane];
+        const int b = std::min(P.chunk, slot0 + count - s0);
+        const u8* src = P.frames + P.g.frame_stride * s0;
+        u32* work = P.any_hough ? (u32*)P.lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
+        u32* retry0 = P.any_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
+        if (P.skip_enhance) { // the session's chain: the warp samples the frames as they are (in raw mode the raw ring: no BGR source)
+            rc_all = pipeline_chunk_boards(P, P.raw_mode() ? nullptr : src, NormSrc(), s0, b, work, retry0, (u32*)rec->retry.p, s0 - slot0);
+            continue;
+        }
         SmallLayout SL;
         rc_all = small_layout(ctx, &P.lane_small[lane], enh.tiles_x * enh.tiles_y, P.chunk, &SL, enh.tiles_x, enh.tiles_y);
         if (rc_all) break;
-        const int b = std::min(P.chunk, slot0 + count - s0);
-        const u8* src = P.frames + P.g.frame_stride * s0;
         u8* res = nullptr;
         NormSrc norm;
         rc_all = enhance_dev(ctx, src, P.A[lane], P.B[lane], P.g, &enh, SL, b, !P.keep_enhanced, &res, &norm,
                              P.use_region ? &P.region : nullptr, P.C[lane]);
         if (rc_all) break;
-        u32* work = P.any_hough ? (u32*)P.lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
-        u32* retry0 = P.any_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
         if (P.keep_enhanced) {
             if (hipMemcpyAsync(P.enhanced + P.g.frame_stride * s0, res, P.g.frame_stride * b, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
                 rc_all = cbv_fail(ctx, CBV_ERR_HIP, "copy of the enhanced frames failed");
@@ -1083,7 +1157,17 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
     if (which == 0) {
         src = P.frames + P.g.frame_stride * slot;
         bytes = (size_t)P.w * P.h * 3;
+        if (P.raw_mode()) { // the frames are raw: the slot is converted for the caller
+            if (!P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: no raw frame was ever uploaded or submitted");
+            if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // submitted copies of the slot
+            const RawGeom rg = tight_raw_geom(P.in_fmt, P.w, P.h);
+            const u8* raw = P.raw_ring + rg.frame_stride * slot;
+            RC(dev_ensure(ctx, &ctx->a, P.g.frame_stride + 256));
+            RC(launch_ingest(ctx, raw, P.in_fmt == CBV_FMT_NV12 ? raw + (size_t)P.w * P.h : nullptr, rg, (u8*)ctx->a.p, P.g, 1));
+            src = (const u8*)ctx->a.p;
+        }
     } else if (which == 1) {
+        if (P.skip_enhance) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: the pipeline runs without enhancement (skip_enhance): there are no enhanced frames");
         if (!P.enhanced) return cbv_fail(ctx, CBV_ERR_STATE, "enhanced frames are not kept (configure with keep_enhanced = 1)");
         src = P.enhanced + P.g.frame_stride * slot;
         bytes = (size_t)P.w * P.h * 3;

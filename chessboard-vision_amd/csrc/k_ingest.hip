@@ -1,36 +1,7 @@
 // Ingest: camera-native frames (NV12, YUYV) to the BGR frames every other kernel reads (include/cbv.h, cbv_yuv_to_bgr,
 // cbv_pipeline_upload_raw, cbv_pipeline_submit after cbv_pipeline_set_input_format).  cv2.cvtColor's
 // COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_YUY2 on 8-bit data: BT.601 limited range in fixed point, no chroma interpolation.
-#include "cbv_device.h"
-
-// round(c * 2^20) of 1.164, 2.018, -0.391, -0.813, 1.596
-enum { YUV_SHIFT = 20, YUV_CY = 1220542, YUV_CUB = 2116026, YUV_CUG = -409993, YUV_CVG = -852492, YUV_CVR = 1673527 };
-
-// The chroma part of the three sums, rounding constant included: shared by the pixels of a 2x2 block (NV12) or a pair (YUYV).
-// Everything stays inside signed 32 bits: the luma term is at most (255 - 16) * 1220542 = 291 709 538, the rounding
-// constant 524 288, and the chroma terms are at most 128 * 2116026 = 270 851 328 (B), 128 * (852492 + 409993) =
-// 161 598 080 (G) and 128 * 1673527 = 214 211 456 (R) in magnitude: |sum| <= 563 085 154 < 2^31.
-struct Chroma {
-    int b, g, r;
-};
-__device__ __forceinline__ Chroma d_chroma(int U, int V)
-{
-    const int u = U - 128, v = V - 128, half = 1 << (YUV_SHIFT - 1);
-    return Chroma{half + YUV_CUB * u, half + YUV_CVG * v + YUV_CUG * u, half + YUV_CVR * v};
-}
-
-// sat_u8(v >> 20) as clamp-then-shift: for v < 0 it is 0, for v >= 256 << 20 it is 255, else v >> 20 (no sign left to shift).
-// Not d_sat8(v >> 20): hipcc folds two of those side by side into v_ashr_pk_u8_i32 and ORs the third byte into the same
-// register as if the instruction had cleared its upper half; on the MI355X it keeps it (R came out as bits 16..23 of the
-// B sum on the all-triples frame of tests/test_gpu_yuv.py, which is the guard for this).
-__device__ __forceinline__ u32 d_sat8_shr20(int v) { return (u32)min(max(v, 0), (256 << YUV_SHIFT) - 1) >> YUV_SHIFT; }
-
-// one pixel as b | g << 8 | r << 16
-__device__ __forceinline__ u32 d_yuv_bgr(int Y, const Chroma& c)
-{
-    const int y = max(0, Y - 16) * YUV_CY;
-    return d_sat8_shr20(y + c.b) | (d_sat8_shr20(y + c.g) << 8) | (d_sat8_shr20(y + c.r) << 16);
-}
+#include "cbv_yuv.h"
 
 // four pixels (24 bits each) as the 12 bytes of a BGR row
 __device__ __forceinline__ Px4 d_pack4(u32 q0, u32 q1, u32 q2, u32 q3)

@@ -9,11 +9,72 @@
 // operation; coordinates are quantised to 1/32 px and sampled with the 15-bit
 // fixed-point bilinear table of remap().
 // Also here: the synthetic frame generator used by bench/tests.
-#include "cbv_device.h"
+#include "cbv_yuv.h"
 
 struct WarpM {
     double m[9];
 };
+
+// What a destination pixel samples, whatever the format of the frames: the top-left tap, the four weights, which taps are
+// inside the source, and where the pixel goes.  (warp_body and warp_yuv_body share it.)
+struct WarpTaps {
+    int sx, sy;
+    int w00, w01, w10, w11;
+    bool any_in, x0in, x1in, y0in, y1in, interior;
+    size_t out_off; // byte offset of the pixel inside a destination frame
+};
+
+// destination pixel (dx, dy) of a dw x dh destination; sw x sh = the source frame
+__device__ __forceinline__ WarpTaps warp_taps(int dx, int dy, int sw, int sh, const double* __restrict__ M, int dw, int dh, int bw0, int rot180,
+                                              int dst_stride)
+{
+    WarpTaps t;
+    const int bx = (dx / bw0) * bw0, x1 = dx - bx; // block origin and offset inside it
+    // (rows are evaluated independently of the block row)
+    const double X0 = M[0] * bx + M[1] * dy + M[2];
+    const double Y0 = M[3] * bx + M[4] * dy + M[5];
+    const double W0 = M[6] * bx + M[7] * dy + M[8];
+    double W = W0 + M[6] * x1;
+    W = W != 0. ? 32. / W : 0.;
+    double fX = (X0 + M[0] * x1) * W;
+    double fY = (Y0 + M[3] * x1) * W;
+    fX = fmax(-2147483648.0, fmin(2147483647.0, fX));
+    fY = fmax(-2147483648.0, fmin(2147483647.0, fY));
+    const int X = d_round_d(fX), Y = d_round_d(fY);
+    const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
+    const int fx = X & 31, fy = Y & 31;
+    t.sx = sx;
+    t.sy = sy;
+    t.w00 = (32 - fx) * (32 - fy) * 32;
+    t.w01 = fx * (32 - fy) * 32;
+    t.w10 = (32 - fx) * fy * 32;
+    t.w11 = fx * fy * 32;
+    t.any_in = !(sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0);
+    t.x0in = sx >= 0 && sx < sw;
+    t.x1in = sx + 1 >= 0 && sx + 1 < sw;
+    t.y0in = sy >= 0 && sy < sh;
+    t.y1in = sy + 1 >= 0 && sy + 1 < sh;
+    t.interior = t.x0in && t.x1in && t.y0in && t.y1in;
+    const int ox = rot180 ? dw - 1 - dx : dx, oy = rot180 ? dh - 1 - dy : dy;
+    t.out_off = (size_t)oy * dst_stride + (size_t)ox * 3;
+    return t;
+}
+
+// the pipeline's HoughCircles worklist counter, filled by the NEXT kernel in the stream (k_squares_pre5_stats):
+// zeroed here instead of by a 4-byte memset, which is one more ~4.5 us launch in a single-frame run
+__device__ __forceinline__ void warp_zero_words(u32* __restrict__ zero_word, u32* __restrict__ zero_word2)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
+        if (zero_word) *zero_word = 0u;
+        if (zero_word2) *zero_word2 = 0u; // the run's second-pass list, when this launch is the run's only chunk
+    }
+}
+
+// remap()'s 15-bit fixed-point bilinear of one channel
+__device__ __forceinline__ int warp_blend(int t0, int t1, int t2, int t3, const WarpTaps& t)
+{
+    return d_sat8((t0 * t.w00 + t1 * t.w01 + t2 * t.w10 + t3 * t.w11 + (1 << 14)) >> 15);
+}
 
 // FPT frames per thread: the coordinates of a destination pixel depend on the matrix and the pixel, not on the frame, and
 // they are most of the kernel's instructions (about 100 of 190 per output pixel, in double precision): a thread works
@@ -27,12 +88,7 @@ __device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, co
                                           size_t mm_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
 {
     __shared__ u8 lut[FPT][256];
-    // the pipeline's HoughCircles worklist counter, filled by the NEXT kernel in the stream (k_squares_pre5_stats):
-    // zeroed here instead of by a 4-byte memset, which is one more ~4.5 us launch in a single-frame run
-    if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-        if (zero_word) *zero_word = 0u;
-        if (zero_word2) *zero_word2 = 0u; // the run's second-pass list, when this launch is the run's only chunk
-    }
+    warp_zero_words(zero_word, zero_word2);
     const bool use_lut = CALC || norm_lut != nullptr;
     const int f0 = bz * FPT;
     const int nf = min(FPT, batch - f0);
@@ -48,37 +104,18 @@ __device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, co
         for (int k = 0; k < FPT; k++)
             if (k < nf) lut[k][threadIdx.x] = norm_lut[(size_t)(f0 + k) * 256 + threadIdx.x];
     __syncthreads();
+    (void)bh0;
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= dw || dy >= dh) return;
-    const int bx = (dx / bw0) * bw0, x1 = dx - bx; // block origin and offset inside it
-    (void)bh0;                                     // rows are evaluated independently of the block row
-    const double X0 = M[0] * bx + M[1] * dy + M[2];
-    const double Y0 = M[3] * bx + M[4] * dy + M[5];
-    const double W0 = M[6] * bx + M[7] * dy + M[8];
-    double W = W0 + M[6] * x1;
-    W = W != 0. ? 32. / W : 0.;
-    double fX = (X0 + M[0] * x1) * W;
-    double fY = (Y0 + M[3] * x1) * W;
-    fX = fmax(-2147483648.0, fmin(2147483647.0, fX));
-    fY = fmax(-2147483648.0, fmin(2147483647.0, fY));
-    const int X = d_round_d(fX), Y = d_round_d(fY);
-    const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
-    const int fx = X & 31, fy = Y & 31;
-    const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-    const bool any_in = !(sx >= g.w || sx + 1 < 0 || sy >= g.h || sy + 1 < 0);
-    const bool x0in = sx >= 0 && sx < g.w, x1in = sx + 1 >= 0 && sx + 1 < g.w;
-    const bool y0in = sy >= 0 && sy < g.h, y1in = sy + 1 >= 0 && sy + 1 < g.h;
-    const bool interior = x0in && x1in && y0in && y1in;
-    const size_t tap = (size_t)sy * g.stride + (size_t)sx * 3; // (only dereferenced where the taps are inside)
-    const int ox = rot180 ? dw - 1 - dx : dx, oy = rot180 ? dh - 1 - dy : dy;
-    const size_t out_off = (size_t)oy * dst_stride + (size_t)ox * 3;
+    const WarpTaps t = warp_taps(dx, dy, g.w, g.h, M, dw, dh, bw0, rot180, dst_stride);
+    const size_t tap = (size_t)t.sy * g.stride + (size_t)t.sx * 3; // (only dereferenced where the taps are inside)
     // interior: the two taps of a row are 6 contiguous bytes -> ONE unaligned 8-byte load per row instead of six byte
     // loads (the gather is bound by the number of memory instructions, not by bytes); the two bytes read past the second
     // tap stay inside the buffer (callers keep >= 8 bytes of slack behind the last frame).  All frames' loads are issued
     // before the first is used.
     u64 ta[FPT], tb[FPT];
-    if (interior)
+    if (t.interior)
 #pragma unroll
         for (int k = 0; k < FPT; k++)
             if (k < nf) {
@@ -90,9 +127,9 @@ __device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, co
     for (int k = 0; k < FPT; k++) {
         if (k >= nf) break;
         int o[3] = {0, 0, 0};
-        if (any_in) {
+        if (t.any_in) {
             int v[4][3]; // taps 00, 01, 10, 11
-            if (interior) {
+            if (t.interior) {
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     v[0][c] = (int)((ta[k] >> (8 * c)) & 255);
@@ -105,25 +142,162 @@ __device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, co
                 const u8* p10 = p00 + g.stride;
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
-                    v[0][c] = (x0in && y0in) ? p00[c] : -1;
-                    v[1][c] = (x1in && y0in) ? p00[3 + c] : -1;
-                    v[2][c] = (x0in && y1in) ? p10[c] : -1;
-                    v[3][c] = (x1in && y1in) ? p10[3 + c] : -1;
+                    v[0][c] = (t.x0in && t.y0in) ? p00[c] : -1;
+                    v[1][c] = (t.x1in && t.y0in) ? p00[3 + c] : -1;
+                    v[2][c] = (t.x0in && t.y1in) ? p10[c] : -1;
+                    v[3][c] = (t.x1in && t.y1in) ? p10[3 + c] : -1;
                 }
             }
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                int t[4];
+                int q[4];
 #pragma unroll
-                for (int q = 0; q < 4; q++) t[q] = v[q][c] < 0 ? 0 : (use_lut ? (int)lut[k][v[q][c]] : v[q][c]); // border taps are 0
-                o[c] = d_sat8((t[0] * w00 + t[1] * w01 + t[2] * w10 + t[3] * w11 + (1 << 14)) >> 15);
+                for (int i = 0; i < 4; i++) q[i] = v[i][c] < 0 ? 0 : (use_lut ? (int)lut[k][v[i][c]] : v[i][c]); // border taps are 0
+                o[c] = warp_blend(q[0], q[1], q[2], q[3], t);
             }
         }
-        u8* q = dst + (size_t)(f0 + k) * dst_frame_stride + out_off;
+        u8* q = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
         q[0] = (u8)o[0];
         q[1] = (u8)o[1];
         q[2] = (u8)o[2];
     }
+}
+
+// ---------------------------------------------------------------------------
+// The warp straight from camera-native frames (pipelines without enhancement whose input format is NV12 or YUYV): the
+// BGR frame k_ingest would write is never made.  The conversion is pointwise (a pixel takes the chroma of its 2x2 block
+// or pair, nothing is interpolated), so converting the four taps and blending them is, bit for bit, sampling the
+// converted frame: same coordinates (warp_taps), same conversion (d_yuv_bgr), same blend (warp_blend).  A tap outside
+// the frame is BGR (0, 0, 0) as in k_warp, not the conversion of zero YUV.
+// ---------------------------------------------------------------------------
+// pixel (x, y) of one raw frame with byte loads (the taps of pixels on the frame's border)
+template <int FMT>
+__device__ __forceinline__ u32 d_raw_px(const u8* __restrict__ f0, const u8* __restrict__ f1, const RawGeom& r, int x, int y)
+{
+    if (FMT == CBV_FMT_NV12) {
+        const u8* c = f1 + (size_t)(y >> 1) * r.stride1 + (x & ~1);
+        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x], d_chroma(c[0], c[1]));
+    }
+    const u8* s = f0 + (size_t)y * r.stride0 + (size_t)(x >> 1) * 4;
+    return d_yuv_bgr(s[(x & 1) * 2], d_chroma(s[1], s[3]));
+}
+
+// Interior pixels, per frame and row of taps.  NV12: one 2-byte load holds both luma samples and one 4-byte load at the
+// even column holds U V of the first tap's pair and of the next pair, which is the second tap's when sx is odd (when sx is
+// even both taps share the first); the rows share the chroma row when sy is even.  YUYV: one 8-byte load at the first tap's
+// pair, Y0 U Y1 V | Y2 U Y3 V, holds both taps and their chroma for either parity.  The bytes read past the second tap's
+// pair (sx even) stay inside the buffer: the ring keeps 256 bytes of slack behind the last frame.
+template <int FMT, int FPT>
+__device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u8* __restrict__ p1, RawGeom r, int sw, int sh,
+                                              const double* __restrict__ M, int dw, int dh, int bw0, int rot180, u8* __restrict__ dst,
+                                              int dst_stride, size_t dst_frame_stride, u32* __restrict__ zero_word,
+                                              u32* __restrict__ zero_word2, int batch, int bz)
+{
+    warp_zero_words(zero_word, zero_word2);
+    const int f0 = bz * FPT;
+    const int nf = min(FPT, batch - f0);
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= dw || dy >= dh) return;
+    const WarpTaps t = warp_taps(dx, dy, sw, sh, M, dw, dh, bw0, rot180, dst_stride);
+    const bool odd = t.sx & 1;
+    constexpr bool NV12 = FMT == CBV_FMT_NV12;
+    const bool two_crows = NV12 && (t.sy & 1); // the rows of taps lie in different chroma rows
+    // (offsets are only used where the taps are inside)
+    const size_t l_off = NV12 ? (size_t)t.sy * r.stride0 + (size_t)t.sx : (size_t)t.sy * r.stride0 + (size_t)(t.sx >> 1) * 4;
+    const size_t c_off = (size_t)(t.sy >> 1) * r.stride1 + (size_t)(t.sx & ~1);
+    u64 la[FPT], lb[FPT]; // NV12: 2 luma bytes; YUYV: the 8 bytes of two pairs
+    u32 ca[FPT], cb[FPT]; // NV12: U V U V
+    if (t.interior)
+#pragma unroll
+        for (int k = 0; k < FPT; k++)
+            if (k < nf) {
+                const u8* l = p0 + (size_t)(f0 + k) * r.frame_stride + l_off;
+                if (NV12) {
+                    u16 a, b;
+                    __builtin_memcpy(&a, l, 2);
+                    __builtin_memcpy(&b, l + r.stride0, 2);
+                    la[k] = a;
+                    lb[k] = b;
+                    const u8* c = p1 + (size_t)(f0 + k) * r.frame_stride + c_off;
+                    __builtin_memcpy(&ca[k], c, 4);
+                    cb[k] = ca[k];
+                    if (two_crows) __builtin_memcpy(&cb[k], c + r.stride1, 4);
+                } else {
+                    __builtin_memcpy(&la[k], l, 8);
+                    __builtin_memcpy(&lb[k], l + r.stride0, 8);
+                }
+            }
+#pragma unroll
+    for (int k = 0; k < FPT; k++) {
+        if (k >= nf) break;
+        int o[3] = {0, 0, 0};
+        if (t.any_in) {
+            u32 q[4] = {0u, 0u, 0u, 0u}; // taps 00, 01, 10, 11 as b | g << 8 | r << 16; border taps are 0
+            if (t.interior) {
+                if (NV12) {
+                    const u32 a = ca[k], sa = odd ? a >> 16 : a;
+                    const Chroma a0 = d_chroma(a & 255, (a >> 8) & 255), a1 = d_chroma(sa & 255, (sa >> 8) & 255);
+                    Chroma b0 = a0, b1 = a1;
+                    if (two_crows) {
+                        const u32 b = cb[k], sb = odd ? b >> 16 : b;
+                        b0 = d_chroma(b & 255, (b >> 8) & 255);
+                        b1 = d_chroma(sb & 255, (sb >> 8) & 255);
+                    }
+                    q[0] = d_yuv_bgr((int)(la[k] & 255), a0);
+                    q[1] = d_yuv_bgr((int)((la[k] >> 8) & 255), a1);
+                    q[2] = d_yuv_bgr((int)(lb[k] & 255), b0);
+                    q[3] = d_yuv_bgr((int)((lb[k] >> 8) & 255), b1);
+                } else {
+#pragma unroll
+                    for (int row = 0; row < 2; row++) {
+                        const u64 w = row ? lb[k] : la[k];
+                        const u32 lo = (u32)w, hi = (u32)(w >> 32), s1 = odd ? hi : lo;
+                        const Chroma c0 = d_chroma((lo >> 8) & 255, lo >> 24), c1 = d_chroma((s1 >> 8) & 255, s1 >> 24);
+                        q[2 * row] = d_yuv_bgr((int)((odd ? lo >> 16 : lo) & 255), c0);
+                        q[2 * row + 1] = d_yuv_bgr((int)((odd ? hi : lo >> 16) & 255), c1);
+                    }
+                }
+            } else {
+                const u8* f0p = p0 + (size_t)(f0 + k) * r.frame_stride;
+                const u8* f1p = NV12 ? p1 + (size_t)(f0 + k) * r.frame_stride : nullptr;
+                if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, r, t.sx, t.sy);
+                if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, r, t.sx + 1, t.sy);
+                if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, r, t.sx, t.sy + 1);
+                if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, r, t.sx + 1, t.sy + 1);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                o[c] = warp_blend((int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255),
+                                  (int)((q[3] >> (8 * c)) & 255), t);
+        }
+        u8* out = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
+        out[0] = (u8)o[0];
+        out[1] = (u8)o[1];
+        out[2] = (u8)o[2];
+    }
+}
+
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_yuv(const u8* __restrict__ p0, const u8* __restrict__ p1, RawGeom r, int sw, int sh, WarpM M,
+                                                   int dw, int dh, int bw0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                                   size_t dst_frame_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    warp_yuv_body<FMT, FPT>(p0, p1, r, sw, sh, M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch,
+                            blockIdx.z);
+}
+
+// every board of a pipeline in one launch, as k_warp_mb
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_yuv_mb(const u8* __restrict__ p0, const u8* __restrict__ p1, RawGeom r, int sw, int sh,
+                                                      const BoardDev* __restrict__ tab, int nz, int s0, u32* __restrict__ zero_word,
+                                                      u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
+    warp_yuv_body<FMT, FPT>(p0, p1, r, sw, sh, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3,
+                            T.warped_stride, zero_word, zero_word2, batch, blockIdx.z - b * nz);
 }
 
 template <int FPT, bool CALC>
@@ -176,15 +350,24 @@ int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int
     return CBV_OK;
 }
 
+// WarpPerspectiveInvoker's block shape of a dw x dh destination (BLOCK_SZ = 32)
+static void warp_block_shape(int dw, int dh, int* bw0_out, int* bh0_out)
+{
+    const int BLOCK_SZ = 32;
+    int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : dh;
+    int bw0 = BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : dw;
+    bh0 = BLOCK_SZ * BLOCK_SZ / bw0 < dh ? BLOCK_SZ * BLOCK_SZ / bw0 : dh;
+    *bw0_out = bw0;
+    *bh0_out = bh0;
+}
+
 int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
                 int dst_stride, size_t dst_frame_stride, NormSrc norm, int batch, u32* zero_word, u32* zero_word2)
 {
     WarpM M;
     for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
-    const int BLOCK_SZ = 32;
-    int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : dh;
-    int bw0 = BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : dw;
-    bh0 = BLOCK_SZ * BLOCK_SZ / bw0 < dh ? BLOCK_SZ * BLOCK_SZ / bw0 : dh;
+    int bw0, bh0;
+    warp_block_shape(dw, dh, &bw0, &bh0);
     prof_begin(ctx, CBV_K_WARP);
     // batched launches: four frames per thread (eight: 13 % fewer instructions again, no change on the path); a launch of
     // a frame or two keeps one thread per pixel and frame
@@ -206,6 +389,66 @@ int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw
                                dst_frame_stride, norm.lut, nullptr, 0, zero_word, zero_word2, batch);
     }
     prof_end(ctx, CBV_K_WARP);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+// the raw planes a fused warp may read: what launch_ingest asks of them
+static int check_warp_yuv(cbv_ctx* ctx, const u8* p0, const u8* p1, RawGeom r, Geom g, int batch)
+{
+    RC(check_raw_format(ctx, r.fmt, g.w, g.h, "launch_warp_yuv"));
+    const bool nv12 = r.fmt == CBV_FMT_NV12;
+    if (batch <= 0 || !p0 || (nv12 && !p1) || r.stride0 < (nv12 ? g.w : 2 * g.w) || (nv12 && r.stride1 < g.w))
+        return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_yuv: bad planes or strides");
+    return CBV_OK;
+}
+
+// as launch_warp: four frames per thread in batched launches, one thread per pixel and frame in a launch of a frame or two
+int launch_warp_yuv(cbv_ctx* ctx, const u8* p0, const u8* p1, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
+                    int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2)
+{
+    RC(check_warp_yuv(ctx, p0, p1, r, g, batch));
+    WarpM M;
+    for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
+    int bw0, bh0;
+    warp_block_shape(dw, dh, &bw0, &bh0);
+    const int fpt = batch >= 8 ? 4 : 1;
+    const dim3 grid((dw + 63) / 64, (dh + 3) / 4, (batch + fpt - 1) / fpt);
+    prof_begin(ctx, CBV_K_WARP_YUV);
+#define CBV_WARP_YUV(FMT, FPT)                                                                                                        \
+    hipLaunchKernelGGL((k_warp_yuv<FMT, FPT>), grid, dim3(256), 0, ctx->stream, p0, p1, r, g.w, g.h, M, dw, dh, bw0, rot180, dst, dst_stride, \
+                       dst_frame_stride, zero_word, zero_word2, batch)
+    if (r.fmt == CBV_FMT_NV12) {
+        if (fpt == 4) CBV_WARP_YUV(CBV_FMT_NV12, 4);
+        else CBV_WARP_YUV(CBV_FMT_NV12, 1);
+    } else {
+        if (fpt == 4) CBV_WARP_YUV(CBV_FMT_YUYV, 4);
+        else CBV_WARP_YUV(CBV_FMT_YUYV, 1);
+    }
+#undef CBV_WARP_YUV
+    prof_end(ctx, CBV_K_WARP_YUV);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_warp_yuv_mb(cbv_ctx* ctx, const u8* p0, const u8* p1, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0, int batch,
+                       u32* zero_word, u32* zero_word2)
+{
+    RC(check_warp_yuv(ctx, p0, p1, r, g, batch));
+    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
+    const dim3 grid((maxS + 63) / 64, (maxS + 3) / 4, nz * nb);
+    prof_begin(ctx, CBV_K_WARP_YUV);
+#define CBV_WARP_YUV_MB(FMT, FPT)                                                                                                     \
+    hipLaunchKernelGGL((k_warp_yuv_mb<FMT, FPT>), grid, dim3(256), 0, ctx->stream, p0, p1, r, g.w, g.h, tab, nz, s0, zero_word, zero_word2, batch)
+    if (r.fmt == CBV_FMT_NV12) {
+        if (fpt == 4) CBV_WARP_YUV_MB(CBV_FMT_NV12, 4);
+        else CBV_WARP_YUV_MB(CBV_FMT_NV12, 1);
+    } else {
+        if (fpt == 4) CBV_WARP_YUV_MB(CBV_FMT_YUYV, 4);
+        else CBV_WARP_YUV_MB(CBV_FMT_YUYV, 1);
+    }
+#undef CBV_WARP_YUV_MB
+    prof_end(ctx, CBV_K_WARP_YUV);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }

@@ -188,11 +188,17 @@ class BoardPipeline(_BoardMethods):
                   history_size=_D["history_size"], min_presence=_D["min_presence"], change_threshold=_D["change_threshold"],
                   z_threshold=_D["z_threshold"], initial_variance=_D["initial_variance"], use_hough=_D["use_hough"],
                   min_radius_ratio=_D["min_radius_ratio"], max_radius_ratio=_D["max_radius_ratio"],
-                  hough_param1=_D["hough_param1"], hough_param2=_D["hough_param2"], enhance_region=False):
+                  hough_param1=_D["hough_param1"], hough_param2=_D["hough_param2"], enhance_region=False, enhance=True):
         """`use_hough` and the radii mirror PieceDetector's attributes (piece_detector.py:33-35,222-230);
         pass min_radius / 100 and max_radius / 100 of piece_detector_settings.json as the application does.
         `enhance_region` (only without keep_enhanced): enhance the part of each frame the warp samples first and the rest
-        only when normalize's global min / max could depend on it; every output stays identical (include/cbv.h)."""
+        only when normalize's global min / max could depend on it; every output stays identical (include/cbv.h).
+        `enhance=True` (default) reproduces the composed chain process_pipeline -> warp -> split -> detect.
+        `enhance=False` reproduces what GameSession.on_frame (game_session.py:123-161) and calibrate_sensitivity.py:142-157
+        run: the warp samples the camera frame as it is, then rotate, split and detect; `profile`, the CLAHE and sharpen
+        settings are ignored, `keep_enhanced` and `enhance_region` are errors, and with a YUV `set_input_format` the warp
+        reads the raw frames directly (raw mode: `upload` takes that format only, `synth` is an error, `download(0, slot)`
+        converts the slot)."""
         cfg = N.PipelineConfig()
         e = cfg.enhance
         e.profile = N.ColorProfile.from_dict(profile)
@@ -208,6 +214,7 @@ class BoardPipeline(_BoardMethods):
                                      max_radius_ratio, hough_param1, hough_param2)
         cfg.chunk, cfg.lanes, cfg.keep_enhanced = chunk, lanes, 1 if keep_enhanced else 0
         cfg.enhance_region = 1 if enhance_region else 0
+        cfg.skip_enhance = 0 if enhance else 1
         self.ctx.check(self.ctx.lib.cbv_pipeline_configure(self.h_, cfg))
         self.rois_rc = rois_rc
         self.board_size = S_
@@ -227,7 +234,8 @@ class BoardPipeline(_BoardMethods):
 
     def upload(self, slot, frame, fmt="bgr"):
         """One frame into a slot, synchronous.  `fmt` "nv12" (one [h * 3 // 2, w] array or a (y, uv) pair of possibly
-        strided views) and "yuyv" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h, cbv_pipeline_upload_raw)."""
+        strided views) and "yuyv" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h, cbv_pipeline_upload_raw); in
+        raw mode (`configure(enhance=False)` with a YUV `set_input_format`) the frame is stored as it is."""
         if N.format_id(fmt) == N.FMT_BGR:
             f = N.as_bgr(frame)
             assert f.shape[:2] == (self.h, self.w)

@@ -127,7 +127,8 @@ CBV_API const char* cbv_device_name(const cbv_ctx* ctx);
 enum {
     CBV_K_COLOR_LAB_HIST = 0, CBV_K_CLAHE_LUT, CBV_K_CLAHE_APPLY, CBV_K_BILATERAL, CBV_K_SHARPEN,
     CBV_K_NORM_LUT, CBV_K_NORMALIZE, CBV_K_WARP, CBV_K_SQUARES, CBV_K_GRAY_BLUR, CBV_K_OTSU,
-    CBV_K_THRESHOLD, CBV_K_SCAN, CBV_K_SYNTH, CBV_K_RESET, CBV_K_HOUGH, CBV_K_INGEST, CBV_K_MODEL_SCAN, CBV_K_COUNT
+    CBV_K_THRESHOLD, CBV_K_SCAN, CBV_K_SYNTH, CBV_K_RESET, CBV_K_HOUGH, CBV_K_INGEST, CBV_K_MODEL_SCAN, CBV_K_WARP_YUV,
+    CBV_K_COUNT
 };
 CBV_API int cbv_profile_enable(cbv_ctx* ctx, int kid /* -1 = all, -2 = none */);
 CBV_API int cbv_profile_read(cbv_ctx* ctx, int kid, double* total_ms, long long* launches);
@@ -363,6 +364,12 @@ typedef struct {
                                     only for frames whose region does not already hold both a 0 and a 255 after sharpen
                                     (normalize's global min / max are then 0 / 255 whatever the rest holds).  Every
                                     output is identical to whole-frame enhancement; 0 = always the whole frame */
+    int32_t skip_enhance;        /* 1: no enhancement; the warp samples the camera frame as it is, which is what
+                                    GameSession.on_frame (game_session.py:123-128) and calibrate_sensitivity.py:142-146 run
+                                    in front of the detectors: warp -> rotate -> split -> detect.  `enhance` is ignored;
+                                    with keep_enhanced or enhance_region: CBV_ERR_ARG; cbv_pipeline_download(which = 1):
+                                    CBV_ERR_STATE.  With a YUV input format the warp reads the raw frames (see
+                                    cbv_pipeline_set_input_format).  0: the composed chain enhance -> warp -> detect */
 } cbv_pipeline_config;
 
 /* Per frame result of PieceDetector.detect_all_pieces(use_smoothing=True,
@@ -489,7 +496,12 @@ CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_fra
  * to 256 bytes: cbv_pipeline_host_slot_bytes).  With a YUV format cbv_pipeline_submit copies the raw slots to a device
  * ring of the same layout and converts them into the BGR frame ring behind the copy; its ordering promises are the
  * same (a run of the slots waits for the copy and its conversion).  On the pipeline only (a board handle:
- * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, or odd h with NV12, and then nothing has changed. */
+ * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, or odd h with NV12, and then nothing has changed.
+ * Raw mode: on a pipeline configured with skip_enhance a YUV format makes the raw ring THE frames.  cbv_pipeline_submit
+ * only copies the raw slots, cbv_pipeline_upload_raw (that format only) writes a raw slot, cbv_pipeline_run warps straight
+ * from the raw frames (k_warp_yuv: byte for byte what the conversion followed by the warp gives) and no BGR frame is ever
+ * written; cbv_pipeline_upload (BGR), cbv_pipeline_synth and cbv_pipeline_upload_raw in another format return
+ * CBV_ERR_STATE, cbv_pipeline_download(which = 0) converts the slot on demand.  One format per pipeline at a time. */
 CBV_API int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt);
 /* bytes from one host-ring slot to the next in the current format (a multiple of 256); 0 for a board handle */
 CBV_API size_t cbv_pipeline_host_slot_bytes(cbv_pipeline* p);
