@@ -164,6 +164,28 @@ class NoiseDevState(C.Structure):
                 ("lifted", C.c_int32), ("pending", C.c_uint64)]
 
 
+class SessionConfig(C.Structure):
+    """cbv_session_config: the game session of a board (include/cbv.h)."""
+    _fields_ = [("rule", C.c_int32), ("stability_required", C.c_int32), ("cooldown_frames", C.c_int32),
+                ("scan_period", C.c_int32), ("max_diff", C.c_int32), ("smart_scan", C.c_int32)]
+
+
+class SessionMove(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("move", C.c_uint16), ("status", C.c_uint8), ("candidates", C.c_uint8)]
+
+
+class SessionState(C.Structure):
+    _fields_ = [("sq", C.c_int8 * 64), ("turn", C.c_int32), ("castling", C.c_int32), ("ep", C.c_int32),
+                ("halfmove", C.c_int32), ("fullmove", C.c_int32), ("expected", C.c_uint64), ("smart_mask", C.c_uint64),
+                ("stable_occupancy", C.c_uint64), ("rejected", C.c_uint64), ("rejected_valid", C.c_int32),
+                ("stable_count", C.c_int32), ("c", C.c_int32), ("last_move_c", C.c_int32), ("n_moves", C.c_int32),
+                ("last_candidates", C.c_int32)]
+
+
+SESSION_RULES = {"session": 0, "game_state": 1}
+SESSION_RING = 1024
+
+
 class RawFrame(C.Structure):
     """cbv_raw_frame: one camera-native frame in host memory."""
     _fields_ = [("fmt", C.c_int32), ("stride0", C.c_int32), ("stride1", C.c_int32), ("plane0", C.c_void_p), ("plane1", C.c_void_p)]
@@ -273,6 +295,15 @@ def load():
         "cbv_pipeline_host_slot_bytes": (C.c_size_t, [vp]),
         "cbv_pipeline_set_model_update": (i32, [vp, i32, dbl]),
         "cbv_pipeline_model": (i32, [vp, i32, i32, vp]),
+        "cbv_pipeline_session_begin": (i32, [vp, P(SessionConfig), C.c_char_p]),
+        "cbv_pipeline_session_end": (i32, [vp]),
+        "cbv_pipeline_session_moves": (i32, [vp, P(SessionMove), i32, P(i32)]),
+        "cbv_pipeline_session_state": (i32, [vp, P(SessionState)]),
+        "cbv_session_walk": (i32, [P(SessionConfig), P(SessionState), P(FrameResult), P(NoiseResult), i32, P(SessionMove), P(i32)]),
+        "cbv_session_state_init": (i32, [P(SessionState), C.c_char_p]),
+        "cbv_session_state_fen": (i32, [P(SessionState), C.c_char_p, i32]),
+        "cbv_session_device_legal_moves": (i32, [vp, C.c_char_p, P(C.c_uint16), i32, P(i32)]),
+        "cbv_session_generator_time": (i32, [vp, C.c_char_p, i32, P(dbl)]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

@@ -467,6 +467,24 @@ int launch_scan(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, const u8* 
                 const u64* check = nullptr, cbv_noise_state* noise_state = nullptr, cbv_noise_result* noise_out = nullptr,
                 ResultMirror mir = ResultMirror());
 
+// The game session of a board (include/cbv.h, cbv_pipeline_session_begin; k_session.hip), device resident.  `resume` is
+// the feedback inside a run: the walk stops behind an accepted move at frame t* of the run and stores t* + 1; the next
+// round of the run scans and walks [resume, count) again from the state the move left, count + 1 = the run is finished.
+struct SessionDev {
+    cbv_session_config cfg;
+    cbv_session_state st;
+    int resume;
+    cbv_session_move ring[CBV_SESSION_RING]; // record k of the session sits in ring[k % CBV_SESSION_RING]
+};
+int launch_scan_session(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, const u8* gray, size_t gray_frame_stride,
+                        const u8* decisions, u8* ref, ScanState* state, u8* flags, int count, const u64* check,
+                        const SessionDev* ses, int first_round, u16* hist);
+// packing, NoiseHandler and the session's walk of one round: frames [resume, count) of the run
+int launch_session_walk(cbv_ctx* ctx, const u8* flags, int n, cbv_frame_result* results, int count, cbv_noise_state* noise_state,
+                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round);
+// the wave generator alone, `reps` times on the position at the head of *state_dev (tests, timing)
+int launch_session_legal(cbv_ctx* ctx, const cbv_session_state* state_dev, u16* out_dev, int* n_dev, int reps);
+
 
 // ---------------------------------------------------------------------------
 // Several boards per frame (cbv_pipeline_add_board): the per-board stages of a chunk are ONE launch each for all boards,

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 
+#include "../../include/cbv_chess.h"
 #include "cbv_internal.h"
 
 // One board of a pipeline: what configure's squares part sets up (board_setup).  Board 0 is the pipeline's own; the
@@ -26,6 +27,12 @@ struct Board {
     bool calibrated = false, has_check = false; // has_check: squares_to_check masks were set
     int model_mode = CBV_MODEL_FROZEN;          // cbv_pipeline_set_model_update
     double model_alpha = 0.1;
+    // game session (cbv_pipeline_session_begin): the device state, the per-frame history records of the scan and how many
+    // of the session's move records the host has handed out
+    bool session = false;
+    cbv_session_config ses_cfg = {};
+    DevBuf d_session, d_hist;
+    int ses_drained = 0;
     bool adaptive() const { return calibrated && model_mode != CBV_MODEL_FROZEN; } // k_model_scan runs for this board
 };
 
@@ -109,6 +116,7 @@ struct Pipe {
     DevBuf d_boards;
     bool any_hough = false;
     bool any_adaptive = false; // some board's model follows the frames: k_model_scan runs in front of the temporal scan
+    bool any_session = false;  // some board runs a game session: the boards' scans are launched board by board
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
     Board& b0() const { return boards[0]->b; }
@@ -236,7 +244,7 @@ static int pipeline_tables(Pipe& P)
     cbv_ctx* ctx = P.ctx;
     const int nb = (int)P.boards.size();
     P.tab.resize(nb);
-    P.any_hough = P.any_adaptive = false;
+    P.any_hough = P.any_adaptive = P.any_session = false;
     P.hough_lds[0] = P.hough_lds[1] = 0;
     P.max_px = P.max_S = 0;
     for (int k = 0; k < nb; k++) {
@@ -253,6 +261,7 @@ static int pipeline_tables(Pipe& P)
             P.hough_lds[1] = std::max(P.hough_lds[1], lds[1]);
         }
         P.any_adaptive = P.any_adaptive || q.adaptive();
+        P.any_session = P.any_session || q.session;
         P.max_px = std::max(P.max_px, q.max_px);
         P.max_S = std::max(P.max_S, q.cfg.board_size);
     }
@@ -337,6 +346,7 @@ static int board_setup(const Pipe& P, Board& b, const cbv_pipeline_config& cfg)
     RC(dev_ensure(ctx, &b.d_mean, off * 4));
     RC(dev_ensure(ctx, &b.d_var, off * 8)); // variance plane, then its square root
     b.calibrated = false;
+    b.session = false; // a session belongs to the configuration it began on
     RC(dev_ensure(ctx, &b.d_state, sizeof(ScanState) * n));
     RC(dev_ensure(ctx, &b.d_results, sizeof(cbv_frame_result) * P.max_frames));
     const size_t want = sizeof(cbv_frame_result) * (size_t)P.max_frames + 16; // (max_frames is fixed: allocated once)
@@ -375,7 +385,7 @@ static void board_free(cbv_pipeline* p)
     if (b.h_stage) (void)hipHostFree(b.h_stage);
     if (b.warped) (void)hipFree(b.warped);
     DevBuf* bufs[] = {&b.d_descs, &b.d_masks, &b.d_gray, &b.d_stats, &b.d_ref, &b.d_state, &b.d_results, &b.d_flags, &b.d_dec, &b.d_mean,
-                      &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over};
+                      &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over, &b.d_session, &b.d_hist};
     for (auto d : bufs) dev_free(d);
     delete p;
 }
@@ -903,6 +913,44 @@ static void mark_mirrored(Pipe& P, int s0, int cnt, bool held)
     for (cbv_pipeline* q : P.boards) std::fill(q->b.slot_mirrored.begin() + s0, q->b.slot_mirrored.begin() + s0 + cnt, held ? 1 : 0);
 }
 
+// The scan stage of ONE board for a run: HoughCircles' second pass and the model scan (`with_pre`: not yet done by the
+// multi-board launches), the temporal scan, packing and NoiseHandler; with a game session the rounds of k_session.hip.
+static int board_scan(Pipe& P, const Board& q, const BoardDev& T, int slot0, int count, bool mirrored, bool with_pre, const u32* retry)
+{
+    cbv_ctx* ctx = P.ctx;
+    const u8* gray = T.gray + T.plane_total * slot0;
+    u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * slot0;
+    u8* flags = T.flags + (size_t)CBV_MAX_SQUARES * slot0;
+    if (with_pre && T.want_hough)
+        RC(launch_hough_second(ctx, T.descs, T.n, gray, T.plane_total, q.hough_cfg, T.hough + (size_t)CBV_MAX_SQUARES * slot0, dec,
+                               retry, T.n * count));
+    if (with_pre && q.adaptive())
+        RC(launch_model_scan(ctx, T.descs, T.n, gray, T.plane_total, T.ms, T.stats + (size_t)T.n * slot0, dec, count, q.max_px));
+    ResultMirror mir;
+    if (mirrored) {
+        mir.records = T.mirror + slot0;
+        mir.over_src = T.over_src;
+        mir.over_dst = T.over_dst;
+    }
+    const u64* check = q.has_check ? T.check + slot0 : nullptr;
+    if (!q.session)
+        return launch_scan(ctx, T.descs, T.sp, gray, T.plane_total, dec, T.ref, T.state, flags, T.results + slot0, count, check, T.noise_state,
+                           T.noise + slot0, mir);
+    // Two accepted moves are at least `gap` frames apart, so a run holds at most ceil(count / gap) of them, and one more
+    // round finishes behind the last; rounds that find the run finished return at once.
+    const int gap = std::max(q.ses_cfg.stability_required, q.ses_cfg.cooldown_frames + 1);
+    const int rounds = 1 + (count + gap - 1) / gap;
+    SessionDev* ses = (SessionDev*)q.d_session.p;
+    u16* hist = (u16*)q.d_hist.p + (size_t)CBV_MAX_SQUARES * slot0;
+    for (int k = 0; k < rounds; k++) {
+        prof_begin(ctx, CBV_K_SCAN);
+        RC(launch_scan_session(ctx, T.descs, T.sp, gray, T.plane_total, dec, T.ref, T.state, flags, count, check, ses, k == 0, hist));
+        RC(launch_session_walk(ctx, flags, T.n, T.results + slot0, count, T.noise_state, T.noise + slot0, mir, ses, k == 0));
+        prof_end(ctx, CBV_K_SCAN);
+    }
+    return CBV_OK;
+}
+
 // second half of cbv_pipeline_run: join the lanes on the scan's stream, HoughCircles second pass, temporal scan, run record
 static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, bool inline_scan, const bool* lane_used, hipStream_t main_stream)
 {
@@ -936,7 +984,16 @@ static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, b
     // writes inside the scan stream's critical path (512-frame steps: -0.5 % frames/s, alternating A/B runs); they are
     // fetched with one copy when asked for.
     const bool mirrored = count <= 4;
-    if (P.boards.size() > 1) { // every board's second pass, scan, packing and NoiseHandler: one launch each
+    if (P.any_session) { // boards with a game session scan in rounds of their own: every board's scan is launched by itself
+        const int nb = (int)P.boards.size();
+        if (nb > 1) {
+            const BoardDev* tab = (const BoardDev*)P.d_boards.p;
+            if (P.any_hough)
+                RC(launch_hough_mb(ctx, tab, nb, slot0, (const u32*)rec->retry.p, CBV_MAX_SQUARES * nb * count, P.hough_lds[1], nullptr, 0, 1));
+            if (P.any_adaptive) RC(launch_model_scan_mb(ctx, tab, nb, slot0, count, P.max_px));
+        }
+        for (int k = 0; k < nb; k++) RC(board_scan(P, P.boards[k]->b, P.tab[k], slot0, count, mirrored, nb == 1, (const u32*)rec->retry.p));
+    } else if (P.boards.size() > 1) { // every board's second pass, scan, packing and NoiseHandler: one launch each
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         const int nb = (int)P.boards.size();
         if (P.any_hough)
@@ -1086,6 +1143,9 @@ extern "C" int cbv_pipeline_set_check_squares(cbv_pipeline* p, int slot0, int co
     Board& B = p->b;
     cbv_ctx* ctx = P.ctx;
     CBV_ENTER(ctx);
+    if (B.session && B.ses_cfg.smart_scan)
+        return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_set_check_squares: the board runs a game session with smart_scan, which owns its "
+                                            "check sets (cbv_pipeline_session_begin with smart_scan = 0 leaves them to the caller)");
     RC(join_scan(P)); // the last run's scan may still read the masks
     if (roi_masks) {
         CBV_HIP(ctx, hipMemcpyAsync((u64*)B.d_check.p + slot0, roi_masks, sizeof(u64) * count, hipMemcpyHostToDevice, ctx->stream));
@@ -1208,4 +1268,155 @@ extern "C" int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats
                                 hipMemcpyDeviceToHost, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// game session (include/cbv.h): begin / end / moves / state
+// ---------------------------------------------------------------------------
+static int session_sync(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    RC(join_scan(P)); // lanes and scans of the runs in flight
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_session_begin(cbv_pipeline* p, const cbv_session_config* cfg, const char* fen)
+{
+    if (!p || !cfg) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_session_begin: null argument");
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    if (!P.configured) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_session_begin: the pipeline is not configured");
+    if (B.cfg.n_rois != 64) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_session_begin: a game session needs the 64 squares of a board, this one has %d", B.cfg.n_rois);
+    // (the frame counts are bounded so that board_scan's round count stays far inside an int)
+    const int frames_max = 1 << 24;
+    if ((cfg->rule != CBV_SESSION_RULE_INFER && cfg->rule != CBV_SESSION_RULE_OCCUPANCY) || cfg->stability_required < 1 ||
+        cfg->stability_required > frames_max || cfg->cooldown_frames < 0 || cfg->cooldown_frames > frames_max || cfg->scan_period < 0 || cfg->max_diff < 0)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_begin: bad configuration (rule %d, stability_required %d, cooldown_frames %d, scan_period %d, max_diff %d)",
+                        cfg->rule, cfg->stability_required, cfg->cooldown_frames, cfg->scan_period, cfg->max_diff);
+    std::vector<SessionDev> host(1);
+    memset(host.data(), 0, sizeof(SessionDev));
+    host[0].cfg = *cfg;
+    if (cbv_session_state_init(&host[0].st, fen) != 0) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_begin: not a FEN: %s", fen ? fen : "(null)");
+    CBV_ENTER(ctx);
+    RC(session_sync(P));
+    RC(dev_ensure(ctx, &B.d_session, sizeof(SessionDev)));
+    RC(dev_ensure(ctx, &B.d_hist, sizeof(u16) * CBV_MAX_SQUARES * (size_t)P.max_frames));
+    CBV_HIP(ctx, hipMemcpy(B.d_session.p, host.data(), sizeof(SessionDev), hipMemcpyHostToDevice));
+    B.session = true;
+    B.ses_cfg = *cfg;
+    B.ses_drained = 0;
+    return pipeline_tables(P);
+}
+
+extern "C" int cbv_pipeline_session_end(cbv_pipeline* p)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_pipeline_session_end: the board is null");
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (!p->b.session) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_session_end: no session is running on this board");
+    CBV_ENTER(ctx);
+    RC(session_sync(P));
+    p->b.session = false;
+    return pipeline_tables(P);
+}
+
+static int session_fetch(cbv_pipeline* p, const char* who, std::vector<SessionDev>& host)
+{
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (!p->b.session) return cbv_fail(ctx, CBV_ERR_STATE, "%s: no session is running on this board", who);
+    RC(join_scan(P));
+    host.resize(1);
+    CBV_HIP(ctx, hipMemcpyAsync(host.data(), p->b.d_session.p, sizeof(SessionDev), hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_session_moves(cbv_pipeline* p, cbv_session_move* out, int cap, int* n)
+{
+    if (n) *n = 0;
+    if (!p || !out || cap < 0 || !n) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_session_moves: bad arguments");
+    cbv_ctx* ctx = p->pipe->ctx;
+    CBV_ENTER(ctx);
+    std::vector<SessionDev> host;
+    RC(session_fetch(p, "cbv_pipeline_session_moves", host));
+    const int total = host[0].st.n_moves;
+    int first = p->b.ses_drained;
+    const int waiting = total - first;
+    const int keep = std::min(std::min(waiting, cap), (int)CBV_SESSION_RING);
+    first = total - keep; // the newest `keep`
+    for (int k = 0; k < keep; k++) out[k] = host[0].ring[(u32)(first + k) % CBV_SESSION_RING];
+    *n = keep;
+    p->b.ses_drained = total;
+    if (keep < waiting)
+        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "cbv_pipeline_session_moves: %d moves were waiting, the newest %d are returned (the ring holds %d)", waiting, keep,
+                        (int)CBV_SESSION_RING);
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_session_state(cbv_pipeline* p, cbv_session_state* out)
+{
+    if (!p || !out) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_session_state: null argument");
+    cbv_ctx* ctx = p->pipe->ctx;
+    CBV_ENTER(ctx);
+    std::vector<SessionDev> host;
+    RC(session_fetch(p, "cbv_pipeline_session_state", host));
+    *out = host[0].st;
+    return CBV_OK;
+}
+
+static int session_legal_setup(cbv_ctx* ctx, const char* fen, const char* who)
+{
+    cbv_session_state st;
+    if (!fen || cbv_session_state_init(&st, fen) != 0) return cbv_fail(ctx, CBV_ERR_ARG, "%s: not a FEN", who);
+    RC(dev_ensure(ctx, &ctx->a, sizeof(cbv_session_state) + sizeof(u16) * CBV_MAX_MOVES + 16));
+    CBV_HIP(ctx, hipMemcpyAsync(ctx->a.p, &st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (st is a local)
+    return CBV_OK;
+}
+
+extern "C" int cbv_session_device_legal_moves(cbv_ctx* ctx, const char* fen, uint16_t* out, int cap, int* n)
+{
+    if (!ctx || !out || cap < 0 || !n) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_session_device_legal_moves: bad arguments");
+    CBV_ENTER(ctx);
+    RC(session_legal_setup(ctx, fen, "cbv_session_device_legal_moves"));
+    u8* base = (u8*)ctx->a.p;
+    u16* d_out = (u16*)(base + sizeof(cbv_session_state));
+    int* d_n = (int*)(base + sizeof(cbv_session_state) + sizeof(u16) * CBV_MAX_MOVES);
+    RC(launch_session_legal(ctx, (const cbv_session_state*)base, d_out, d_n, 1));
+    std::vector<u16> host(CBV_MAX_MOVES + 2);
+    CBV_HIP(ctx, hipMemcpyAsync(host.data(), d_out, sizeof(u16) * CBV_MAX_MOVES + sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int cnt;
+    memcpy(&cnt, host.data() + CBV_MAX_MOVES, sizeof(int));
+    *n = cnt;
+    for (int i = 0; i < cnt && i < cap && i < CBV_MAX_MOVES; i++) out[i] = host[i];
+    return CBV_OK;
+}
+
+extern "C" int cbv_session_generator_time(cbv_ctx* ctx, const char* fen, int reps, double* ms)
+{
+    if (!ctx || reps < 1 || reps > (1 << 20) || !ms) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_session_generator_time: bad arguments");
+    CBV_ENTER(ctx);
+    RC(session_legal_setup(ctx, fen, "cbv_session_generator_time"));
+    u8* base = (u8*)ctx->a.p;
+    hipEvent_t e0, e1;
+    CBV_HIP(ctx, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        return cbv_fail(ctx, CBV_ERR_HIP, "cbv_session_generator_time: hipEventCreate failed");
+    }
+    (void)hipEventRecord(e0, ctx->stream);
+    const int rc = launch_session_legal(ctx, (const cbv_session_state*)base, (u16*)(base + sizeof(cbv_session_state)),
+                                        (int*)(base + sizeof(cbv_session_state) + sizeof(u16) * CBV_MAX_MOVES), reps);
+    (void)hipEventRecord(e1, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    float f = 0;
+    (void)hipEventElapsedTime(&f, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    *ms = f;
+    return rc;
 }

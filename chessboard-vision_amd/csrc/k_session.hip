@@ -1,0 +1,175 @@
+// The game session on the device (include/cbv.h, cbv_pipeline_session_begin): the back half of GameSession.on_frame
+// (game_session.py:130-265) for every frame of a run, without a host round trip.
+//
+// A run with a session is a fixed number of ROUNDS on the scan stream, each k_scan_session (k_squares.hip) followed by
+// k_session_walk below.  The scan of a round is speculative: it runs to the end of the run with the references, check
+// sets and NoiseHandler state it started from.  The walk packs the records, runs NoiseHandler and the session's
+// per-frame logic (session_core.h) in frame order, and stops behind the first accepted move at frame t*: everything up to
+// t* is final, everything behind it was scanned with stale state.  It stores resume = t* + 1, the next round redoes
+// [resume, count) from {reference = the planes of t*, cache cleared, history as recorded at t*, fresh NoiseHandler, the
+// new smart mask}, which is what update_references(squares) + noise.reset() leave (game_session.py:219-223).  A round
+// that finds resume > count returns at once.  No workgroup ever waits for another: the rounds are ordered by the stream.
+// Two accepted moves are at least max(stability_required, cooldown_frames + 1) frames apart, which bounds the rounds.
+//
+// The walk is one sequential chain on one wave; the rules use the wave when the walk does reach the generator: lane 0
+// lists the pseudo-legal moves in python-chess order, every lane tests the king's safety of one of them, a ballot and
+// a prefix count keep the order, and the destinations of the smart mask are OR-reduced across the lanes.
+// on_move_detected is taken as always True: the reference's Lichess hook is out of scope.
+#include "cbv_internal.h"
+#include "cbv_device.h"
+#include "noise_core.h"
+#include "session_core.h"
+
+namespace {
+
+struct WalkLds {
+    cbv_movelist cand, legal, scratch;
+};
+
+__device__ __forceinline__ u64 wave_or_u64(u64 v)
+{
+    u32 lo = (u32)v, hi = (u32)(v >> 32);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo |= __shfl_xor(lo, o, WAVE);
+        hi |= __shfl_xor(hi, o, WAVE);
+    }
+    return (u64)hi << 32 | lo;
+}
+
+// list(board.legal_moves) of *b into L->legal, by the whole (single) wave of the workgroup; returns the OR of the
+// destination squares.  *b is uniform and not written meanwhile.
+__device__ u64 wave_gen_legal(const cbv_pos* b, WalkLds* L)
+{
+    const int lane = threadIdx.x;
+    if (lane == 0) cc_gen_candidates(b, &L->cand);
+    __syncthreads();
+    const int n = cc_stored(&L->cand);
+    int base = 0;
+    u64 dests = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const cbv_move m = i < n ? L->cand.m[i] : (cbv_move)CBV_MOVE_NONE;
+        const bool ok = i < n && cc_king_safe(b, m);
+        const u64 bal = __ballot(ok);
+        if (ok) {
+            L->legal.m[base + __popcll(bal & ((1ull << lane) - 1ull))] = m; // base + rank <= i < CBV_MAX_MOVES
+            dests |= 1ull << cc_to(m);
+        }
+        base += __popcll(bal);
+    }
+    if (lane == 0) L->legal.n = base;
+    __syncthreads();
+    return wave_or_u64(dests);
+}
+
+__global__ __launch_bounds__(64) void k_session_walk(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count,
+                                                      cbv_noise_state* __restrict__ noise_state, cbv_noise_result* __restrict__ noise_out,
+                                                      ResultMirror mir, SessionDev* __restrict__ ses, int first_round)
+{
+    __shared__ WalkLds L;
+    __shared__ cbv_session_state st;
+    __shared__ int sh_t, sh_flag;
+    const int lane = threadIdx.x;
+    const int r = first_round ? 0 : ses->resume;
+    if (r > count) return;
+    if (mir.over_dst && lane == 0) *mir.over_dst = mir.over_src ? *mir.over_src : 0u;
+    // the records of [r, count): per-square flag bytes -> the eight square sets (pack_results_body of k_squares.hip)
+    for (int t = r; t < count; t++) {
+        const u32 fl = lane < n ? flags[(size_t)t * CBV_MAX_SQUARES + lane] : 0u;
+        u64* rw = (u64*)&results[t];
+        u64* hm = mir.records ? (u64*)&mir.records[t] : nullptr;
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const u64 m = __ballot((fl >> b) & 1u);
+            if (lane == 0) {
+                rw[b] = m;
+                if (hm) hm[b] = m;
+            }
+        }
+    }
+    const cbv_session_config cfg = ses->cfg;
+    if (lane == 0) {
+        // NoiseHandler over the same frames (speculative behind a move, like the scan: redone by the next round)
+        d_noise_run(&results[r].visual_changes, sizeof(cbv_frame_result) / 8, count - r, noise_state, noise_out + r);
+        st = ses->st;
+    }
+    __syncthreads();
+    int t = r;
+    bool accepted = false;
+    for (;;) {
+        if (lane == 0) { // frames up to the next one on which the rule has to run
+            int tt = t;
+            bool want = false;
+            for (; tt < count; tt++)
+                if (ses_frame_pre(&cfg, &st, results[tt].stable_occupied, noise_out[tt].state == 1)) {
+                    want = true;
+                    break;
+                }
+            sh_t = tt;
+            sh_flag = want ? 1 : 0;
+        }
+        __syncthreads();
+        t = sh_t;
+        if (!sh_flag) break;
+        __syncthreads(); // (sh_flag is rewritten below)
+        wave_gen_legal(ses_pos(&st), &L);
+        if (lane == 0) {
+            cbv_session_move rec;
+            const bool acc = ses_frame_rule(&cfg, &st, results[t].stable_occupied, &L.legal, &L.scratch, &rec);
+            if (acc) ses->ring[(u32)(st.n_moves - 1) % CBV_SESSION_RING] = rec;
+            sh_flag = acc ? 1 : 0;
+        }
+        __syncthreads();
+        accepted = sh_flag != 0;
+        if (accepted) break;
+        t++;
+        __syncthreads();
+    }
+    u64 dests = 0;
+    if (accepted) {
+        dests = wave_gen_legal(ses_pos(&st), &L); // of the new board: its smart mask
+    }
+    if (lane == 0) {
+        if (accepted) {
+            ses_refresh(&st, dests);
+            cbv_noise_state z;
+            z.state = z.stable_count = z.cooldown_count = 0;
+            z.lifted = 0;
+            z.pending = 0;
+            *noise_state = z; // noise.reset()
+            ses->resume = t + 1;
+        } else ses->resume = count + 1;
+        ses->st = st;
+    }
+}
+
+// the generator alone, for tests and timing: `reps` calls on the position at the head of *state
+__global__ __launch_bounds__(64) void k_session_legal(const cbv_session_state* __restrict__ state, u16* __restrict__ out, int* __restrict__ n_out, int reps)
+{
+    __shared__ WalkLds L;
+    __shared__ cbv_pos pos;
+    if (threadIdx.x == 0) pos = *ses_pos(state);
+    __syncthreads();
+    for (int k = 0; k < reps; k++) wave_gen_legal(&pos, &L);
+    const int n = cc_stored(&L.legal);
+    for (int i = threadIdx.x; i < n; i += 64) out[i] = L.legal.m[i];
+    if (threadIdx.x == 0) *n_out = L.legal.n;
+}
+
+} // namespace
+
+int launch_session_walk(cbv_ctx* ctx, const u8* flags, int n, cbv_frame_result* results, int count, cbv_noise_state* noise_state,
+                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round)
+{
+    hipLaunchKernelGGL(k_session_walk, dim3(1), dim3(64), 0, ctx->stream, flags, n, results, count, noise_state, noise_out, mir, ses, first_round);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_session_legal(cbv_ctx* ctx, const cbv_session_state* state_dev, u16* out_dev, int* n_dev, int reps)
+{
+    hipLaunchKernelGGL(k_session_legal, dim3(1), dim3(64), 0, ctx->stream, state_dev, out_dev, n_dev, reps);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}

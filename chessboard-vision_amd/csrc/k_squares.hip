@@ -9,6 +9,7 @@
 //   k_scan                detect_all_pieces' temporal logic over a batch of
 //                         frames: 64 independent per-square chains
 #include "cbv_device.h"
+#include "noise_core.h"
 
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_squares_preprocess(const u8* __restrict__ src, size_t src_frame_stride,
@@ -890,19 +891,45 @@ int launch_model_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int 
 // One WAVE per square: the per-frame reduction is six DPP steps, there is no LDS and no barrier on
 // the critical path of the 512-step chain.
 
-template <int VPT, int SCAN_DEPTH>
+// SESSION (the game session of k_session.hip; false compiles to the scan as it always was): the scan starts at frame
+// `ses->resume` of the run, from what update_references leaves behind the frame before it (reference = that frame's
+// plane, cache cleared, history as recorded in `hist`) when that is not the run's first frame; with smart_scan the
+// check sets come from the session's counter and smart mask; and every frame leaves its history record in `hist`
+// ([frame][CBV_MAX_SQUARES]: hist_bits | hist_len << 8), from which a later round resumes.
+template <int VPT, int SCAN_DEPTH, bool SESSION = false>
 __device__ __forceinline__ void scan_body(const SquareDesc d, const ScanParams sp, const u8* __restrict__ gray,
                                           size_t gray_frame_stride, const u8* __restrict__ decisions,
                                           u8* __restrict__ ref, ScanState* __restrict__ state,
-                                          u8* __restrict__ flags, int count, const u64* __restrict__ check)
+                                          u8* __restrict__ flags, int count, const u64* __restrict__ check,
+                                          const SessionDev* __restrict__ ses = nullptr, int first_round = 0, u16* __restrict__ hist = nullptr)
 {
     const int sq = blockIdx.x;
     const int n = d.w * d.h;
     const int nvec = (n + 15) >> 4;
+    int tb = 0, ses_c = 0, ses_period = 0;
+    u64 ses_mask = 0;
+    bool ses_smart = false;
+    if (SESSION) {
+        tb = first_round ? 0 : ses->resume;
+        if (tb > count) return; // the run is finished: this round has nothing to redo
+        ses_smart = ses->cfg.smart_scan != 0;
+        ses_c = ses->st.c - tb; // counter of the frame in front of the run's frame 0
+        ses_period = ses->cfg.scan_period;
+        ses_mask = ses->st.smart_mask;
+    }
     ScanState st = state[sq];
     uint4 rv[VPT], ring[SCAN_DEPTH][VPT];
     u32 sring[SCAN_DEPTH];
     const uint4* refv = (const uint4*)(ref + d.plane_off);
+    if (SESSION && tb > 0) { // behind an accepted move: update_references from its frame
+        const u32 h = hist[(size_t)(tb - 1) * CBV_MAX_SQUARES + sq];
+        st.has_ref = 1;
+        st.has_cache = 0;
+        st.cached_raw = 0;
+        st.hist_bits = h & 255u;
+        st.hist_len = h >> 8;
+        refv = (const uint4*)(gray + (size_t)(tb - 1) * gray_frame_stride + d.plane_off);
+    }
     auto fetch = [&](int t, uint4* dst, u32& sdst) {
         const uint4* gp = (const uint4*)(gray + (size_t)t * gray_frame_stride + d.plane_off);
 #pragma unroll
@@ -911,7 +938,10 @@ __device__ __forceinline__ void scan_body(const SquareDesc d, const ScanParams s
             dst[k] = vi < nvec ? gp[vi] : make_uint4(0, 0, 0, 0); // lanes past the plane must compare equal
         }
         sdst = decisions[(size_t)t * CBV_MAX_SQUARES + sq];
-        if (check) sdst |= (u32)((check[t] >> sq) & 1ull) << 8; // squares_to_check of that frame
+        if (SESSION && ses_smart) { // the session's own set: none on every scan_period-th frame, else the smart mask
+            const int c = ses_c + t + 1;
+            if (!(ses_period > 0 && c % ses_period == 0)) sdst |= (u32)((ses_mask >> sq) & 1ull) << 8;
+        } else if (check) sdst |= (u32)((check[t] >> sq) & 1ull) << 8; // squares_to_check of that frame
     };
 #pragma unroll
     for (int k = 0; k < VPT; k++) {
@@ -920,8 +950,8 @@ __device__ __forceinline__ void scan_body(const SquareDesc d, const ScanParams s
     }
 #pragma unroll
     for (int j = 0; j < SCAN_DEPTH; j++)
-        if (j < count) fetch(j, ring[j], sring[j]);
-    for (int t0 = 0; t0 < count; t0 += SCAN_DEPTH) {
+        if (tb + j < count) fetch(tb + j, ring[j], sring[j]);
+    for (int t0 = tb; t0 < count; t0 += SCAN_DEPTH) {
 #pragma unroll
         for (int j = 0; j < SCAN_DEPTH; j++) {
             const int t = t0 + j;
@@ -977,6 +1007,7 @@ __device__ __forceinline__ void scan_body(const SquareDesc d, const ScanParams s
                 u32 fl = (raw ? 1u : 0u) | (stable ? 2u : 0u) | (changed ? 4u : 0u) | (should_process ? 8u : 0u);
                 if (in_changes) fl |= 16u | ((dc & 8u) ? 64u : ((dc & 4u) ? 32u : 0u)) | (fresh ? 128u : 0u);
                 flags[(size_t)t * CBV_MAX_SQUARES + sq] = (u8)fl;
+                if (SESSION) hist[(size_t)t * CBV_MAX_SQUARES + sq] = (u16)(st.hist_bits | st.hist_len << 8);
             }
         }
     }
@@ -1003,6 +1034,30 @@ __global__ __launch_bounds__(64) void k_scan(const SquareDesc* __restrict__ desc
     // latency-bound); up to 128 x 128: sixteen vectors, 2 frames ahead
     if (nvec <= 512) scan_body<8, 4>(d, sp, gray, gray_frame_stride, decisions, ref, state, flags, count, check);
     else scan_body<16, 2>(d, sp, gray, gray_frame_stride, decisions, ref, state, flags, count, check);
+}
+
+// k_scan of a board with a game session: one round (k_session.hip enqueues the rounds of a run)
+__global__ __launch_bounds__(64) void k_scan_session(const SquareDesc* __restrict__ descs, ScanParams sp,
+                                                       const u8* __restrict__ gray, size_t gray_frame_stride,
+                                                       const u8* __restrict__ decisions, u8* __restrict__ ref,
+                                                       ScanState* __restrict__ state, u8* __restrict__ flags, int count,
+                                                       const u64* __restrict__ check, const SessionDev* __restrict__ ses, int first_round,
+                                                       u16* __restrict__ hist)
+{
+    const SquareDesc d = descs[blockIdx.x];
+    const int nvec = (d.w * d.h + 15) >> 4;
+    if (nvec <= 512) scan_body<8, 4, true>(d, sp, gray, gray_frame_stride, decisions, ref, state, flags, count, check, ses, first_round, hist);
+    else scan_body<16, 2, true>(d, sp, gray, gray_frame_stride, decisions, ref, state, flags, count, check, ses, first_round, hist);
+}
+
+int launch_scan_session(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, const u8* gray, size_t gray_frame_stride,
+                        const u8* decisions, u8* ref, ScanState* state, u8* flags, int count, const u64* check,
+                        const SessionDev* ses, int first_round, u16* hist)
+{
+    hipLaunchKernelGGL(k_scan_session, dim3(sp.n), dim3(64), 0, ctx->stream, descs, sp, gray, gray_frame_stride, decisions, ref,
+                       state, flags, count, check, ses, first_round, hist);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
 }
 
 // per-square flag bytes of a frame -> the eight 64-bit square sets of cbv_frame_result
@@ -1037,66 +1092,7 @@ __global__ void k_pack_results(const u8* __restrict__ flags, int n, cbv_frame_re
 // NoiseHandler.process (noise_handler.py:49-213): a 3-state machine over the per-frame set of
 // visually changed squares.  Sequential and tiny: one lane walks the frames.
 // ---------------------------------------------------------------------------
-__device__ void d_noise_run(const u64* __restrict__ changes, size_t stride_words, int count, cbv_noise_state* __restrict__ state,
-                            cbv_noise_result* __restrict__ out)
-{
-    const int NOISE_THRESHOLD = 3, STABILITY_FRAMES = 12, COOLDOWN_FRAMES = 5;
-    cbv_noise_state s = *state;
-    for (int t = 0; t < count; t++) {
-        const u64 ch = changes[(size_t)t * stride_words];
-        const int n = __popcll(ch);
-        const bool noisy = n > NOISE_THRESHOLD;
-        const int single = n == 1 ? (int)__ffsll((long long)ch) - 1 : -1;
-        cbv_noise_result r;
-        r.state = 0; r.msg = 0; r.stable = 0; r.lifted = -1; r.count = 0; r.blocked = 0; r.squares = 0;
-        if (s.state == 0) { // IDLE
-            if (n == 0) { r.state = 0; r.msg = 0; }
-            else if (noisy) { s.state = 1; s.cooldown_count = 0; r.state = 1; r.msg = 1; r.count = (u16)n; }
-            else {
-                s.state = 2; s.pending = ch; s.stable_count = 1; s.lifted = single + 1;
-                r.state = 2; r.msg = 2; r.squares = ch; r.lifted = (signed char)single; r.count = 1;
-            }
-        } else if (s.state == 1) { // NOISE_ACTIVE
-            if (noisy) { s.cooldown_count = 0; r.state = 1; r.msg = 6; r.count = (u16)n; }
-            else {
-                s.cooldown_count++;
-                const bool done = (int)s.cooldown_count >= COOLDOWN_FRAMES;
-                if (n == 0) {
-                    if (done) { s.state = 0; s.cooldown_count = 0; r.state = 0; r.msg = 3; }
-                    else { r.state = 1; r.msg = 4; r.count = (u16)s.cooldown_count; }
-                } else if (done) {
-                    s.state = 2; s.pending = ch; s.stable_count = 1;
-                    r.state = 2; r.msg = 7; r.squares = ch;
-                } else { r.state = 1; r.msg = 5; r.count = (u16)n; }
-            }
-        } else { // MOVE_PENDING
-            if (noisy) {
-                s.state = 1; s.pending = 0; s.stable_count = 0; s.cooldown_count = 0;
-                r.state = 1; r.msg = 8; r.count = (u16)n;
-            } else if (n == 0) {
-                s.stable_count++;
-                if ((int)s.stable_count >= STABILITY_FRAMES) {
-                    r.state = 0; r.msg = 9; r.squares = s.pending; r.stable = 1;
-                    s.state = 0; s.pending = 0; s.stable_count = 0; s.cooldown_count = 0; s.lifted = 0;
-                } else { r.state = 2; r.msg = 10; r.squares = s.pending; r.count = (u16)s.stable_count; }
-            } else if (ch == s.pending) {
-                s.stable_count++;
-                if ((int)s.stable_count >= STABILITY_FRAMES) { r.state = 2; r.msg = 11; r.squares = s.pending; r.stable = 1; }
-                else {
-                    r.state = 2; r.msg = 12; r.squares = s.pending; r.count = (u16)s.stable_count;
-                    r.lifted = (signed char)(__popcll(s.pending) == 1 ? s.lifted - 1 : -1);
-                }
-            } else {
-                s.pending = ch; s.stable_count = 1; s.lifted = single + 1;
-                r.state = 2; r.msg = 13; r.squares = ch; r.lifted = (signed char)single; r.count = 1;
-            }
-        }
-        r.blocked = s.state == 1 ? 1 : 0;
-        out[t] = r;
-    }
-    *state = s;
-}
-
+// (d_noise_run: noise_core.h, shared with the game session's walk in k_session.hip)
 __global__ void k_noise(const u64* __restrict__ changes, size_t stride_words, int count, cbv_noise_state* __restrict__ state,
                         cbv_noise_result* __restrict__ out)
 {

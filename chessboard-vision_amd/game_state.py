@@ -64,6 +64,22 @@ class GameState:
         self.board.set_fen(fen)
 
 
+class FrameClock:
+    """Time in frames for StableMoveTracker: a batched run has no wall clock, so the device session (include/cbv.h,
+    cbv_pipeline_session_begin) counts frames, and a host tracker that shall agree with it does the same.  `tick()` once
+    per frame before `process`; calling the clock returns the frame counter (1 for the first frame)."""
+
+    def __init__(self):
+        self.frame = 0
+
+    def tick(self):
+        self.frame += 1
+        return self.frame
+
+    def __call__(self):
+        return self.frame
+
+
 class StableMoveTracker:
     """The move-acceptance logic of GameSession._process_stable_move / _infer_move (game_session.py:181-265)
     without its UI and network side: an occupancy must stay identical for STABILITY_REQUIRED frames, differ from
@@ -76,8 +92,12 @@ class StableMoveTracker:
     STABILITY_REQUIRED = 20
     MOVE_COOLDOWN = 2.0
 
-    def __init__(self, game, clock=None, on_move_detected=None, after_move=None):
+    def __init__(self, game, clock=None, on_move_detected=None, after_move=None, rule="session"):
         import time
+        if rule not in ("session", "game_state"):
+            raise ValueError("rule %r: expected 'session' (GameSession._infer_move) or 'game_state' (process_occupancy_change)" % (rule,))
+        self.rule = rule
+        self.last_status = None  # rule "game_state": the status string of the last process_occupancy_change
         self.game = game
         self.clock = clock or time.time
         self.on_move_detected = on_move_detected or (lambda move: True)
@@ -85,6 +105,18 @@ class StableMoveTracker:
         self.stable_occupancy = None
         self.stable_count = 0
         self.last_move_time = 0
+
+    def use_frame_clock(self, fps=30, cooldown_frames=None):
+        """Count time in frames, as the device session does: MOVE_COOLDOWN becomes `cooldown_frames` (default
+        round(MOVE_COOLDOWN * fps): what "2.0 s" means at that frame rate), the clock a FrameClock the caller ticks once
+        per frame, and no cooldown holds before the first move (the reference's last_move_time = 0 against time.time()).
+        Returns the clock."""
+        if cooldown_frames is None:
+            cooldown_frames = int(round(type(self).MOVE_COOLDOWN * fps))
+        self.MOVE_COOLDOWN = cooldown_frames
+        self.clock = FrameClock()
+        self.last_move_time = float("-inf")
+        return self.clock
 
     def infer_move(self, vision_occupied):
         """(move or None, number of candidate moves) — game_session.py:229-265."""
@@ -108,12 +140,17 @@ class StableMoveTracker:
         now = self.clock()
         if self.stable_count < self.STABILITY_REQUIRED or not (now - self.last_move_time) > self.MOVE_COOLDOWN or noise_active:
             return None
-        move, _ = self.infer_move(vision_occupied)
-        if move is None or not self.on_move_detected(move):
-            return None
-        if move not in self.game.board.legal_moves:
-            return None
-        self.game.board.push(move)
+        if self.rule == "game_state":  # process_occupancy_change recognises and pushes in one step
+            move, self.last_status = self.game.process_occupancy_change(vision_occupied)
+            if move is None:
+                return None
+        else:
+            move, _ = self.infer_move(vision_occupied)
+            if move is None or not self.on_move_detected(move):
+                return None
+            if move not in self.game.board.legal_moves:
+                return None
+            self.game.board.push(move)
         self.last_move_time = now
         self.after_move()
         self.stable_count = 0

@@ -156,6 +156,75 @@ class _BoardMethods:
     def occupied(self, result, stable=True):
         return bits_to_positions(result.stable_occupied if stable else result.raw_occupied, self.rois_rc)
 
+    def session_begin(self, rule="session", fps=30, fen=None, **cfg):
+        """Start a game session on this board (include/cbv.h, cbv_pipeline_session_begin): from now on every frame of
+        every `run` also goes through the back half of GameSession.on_frame on the device (smart-scan check sets, stable
+        move detection, the move rule, and after an accepted move update_references + NoiseHandler.reset()), whatever the
+        run length.  `rule`: "session" = GameSession._infer_move, "game_state" = GameState.process_occupancy_change.
+        Keywords: stability_required (20), cooldown_frames (round(MOVE_COOLDOWN * fps)), scan_period (30), max_diff (4),
+        smart_scan (True).  Returns a Session."""
+        from .game_state import StableMoveTracker
+        if rule not in N.SESSION_RULES:
+            raise ValueError("rule %r: expected one of %s" % (rule, ", ".join(sorted(N.SESSION_RULES))))
+        d = dict(stability_required=StableMoveTracker.STABILITY_REQUIRED, cooldown_frames=int(round(StableMoveTracker.MOVE_COOLDOWN * fps)),
+                 scan_period=30, max_diff=4, smart_scan=True)
+        unknown = set(cfg) - set(d)
+        if unknown:
+            raise TypeError("session_begin: unknown keyword(s) %s" % ", ".join(sorted(unknown)))
+        d.update(cfg)
+        c = N.SessionConfig(N.SESSION_RULES[rule], int(d["stability_required"]), int(d["cooldown_frames"]), int(d["scan_period"]),
+                            int(d["max_diff"]), 1 if d["smart_scan"] else 0)
+        self.ctx.check(self.ctx.lib.cbv_pipeline_session_begin(self.h_, c, fen.encode() if fen is not None else None))
+        return Session(self, c)
+
+
+class Session:
+    """A game session running on a board (`session_begin`).  The host reads back moves and the position; the frames never
+    leave the device."""
+
+    def __init__(self, board, config):
+        self._b, self.config = board, config
+        self.ctx = board.ctx
+        self._open = True
+
+    def state(self):
+        """cbv_session_state after every run enqueued so far."""
+        st = N.SessionState()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_session_state(self._b.h_, st))
+        return st
+
+    def moves(self):
+        """The moves accepted since the previous call: [(frame since session_begin, chess_rules.Move, status string)]."""
+        from . import chess_rules as chess
+        out = (N.SessionMove * N.SESSION_RING)()
+        n = C.c_int()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_session_moves(self._b.h_, out, N.SESSION_RING, C.byref(n)))
+        lib = chess._L()
+        return [(out[i].frame, chess.Move._from_code(out[i].move), lib.cbv_game_status_name(out[i].status).decode()) for i in range(n.value)]
+
+    def fen(self):
+        st = self.state()
+        buf = C.create_string_buffer(128)
+        self.ctx.lib.cbv_session_state_fen(st, buf, 128)
+        return buf.value.decode()
+
+    @property
+    def board(self):
+        """A chess_rules.Board at the session's position (its move stack starts here)."""
+        from . import chess_rules as chess
+        b = chess.Board()
+        b.set_fen(self.fen())
+        return b
+
+    @property
+    def stable_count(self):
+        return self.state().stable_count
+
+    def end(self):
+        if self._open and self._b.h_:
+            self.ctx.check(self.ctx.lib.cbv_pipeline_session_end(self._b.h_))
+        self._open = False
+
 
 class BoardPipeline(_BoardMethods):
     def __init__(self, w, h, max_frames, ctx=None):

@@ -580,6 +580,78 @@ CBV_API int cbv_pipeline_set_model_update(cbv_pipeline* board, int mode, double 
  * CBV_ERR_STATE while the board is not calibrated. */
 CBV_API int cbv_pipeline_model(cbv_pipeline* board, int which, int roi, float* out);
 
+/* ------------------------------------------------------------------ */
+/* game session on the device: stable moves, smart scan, FEN           */
+/* ------------------------------------------------------------------ */
+/* The back half of GameSession.on_frame (game_session.py:130-265) for every frame of every run of a board, on the
+ * device: the smart-scan `squares_to_check` set (:130-154), _process_stable_move (:181-225), the move rule, and after an
+ * accepted move update_references(squares) and noise.reset() (:219-223).  Time is counted in frames.  Per frame, in this
+ * order: c += 1; the frame's check set is None when c % scan_period == 0, else the smart mask (occupied squares plus
+ * (file, 7 - rank) of every legal destination, the reference's own conversion); vision = stable_occupied; when
+ * popcount(expected ^ vision) > max_diff the stable set is emptied and stable_count = 0, else stable_count counts the
+ * frames the set stayed the same; a move is looked for when stable_count >= stability_required, c - last move's c >
+ * cooldown_frames and the frame's NoiseHandler state is not NOISE_ACTIVE; the rule must find exactly one legal move; it
+ * is pushed and recorded, stable_count = 0, the references become THIS frame's squares (cache cleared, history kept,
+ * as cbv_pipeline_update_references) and the NoiseHandler restarts.  on_move_detected is taken as always True (the
+ * Lichess hook of the reference is out of scope).  The frames of a run behind an accepted move are scanned again from
+ * that state inside the run, so a run of any length gives what one-frame runs driven from the host give. */
+#define CBV_SESSION_RULE_INFER     0  /* GameSession._infer_move (game_session.py:229-265) */
+#define CBV_SESSION_RULE_OCCUPANCY 1  /* GameState.process_occupancy_change (game_state.py:40-195) */
+#define CBV_SESSION_RING 1024         /* move records kept between two cbv_pipeline_session_moves calls */
+typedef struct {
+    int32_t rule;               /* CBV_SESSION_RULE_* */
+    int32_t stability_required; /* 20   game_session.py STABILITY_REQUIRED */
+    int32_t cooldown_frames;    /* 60   MOVE_COOLDOWN (2.0 s) at 30 fps */
+    int32_t scan_period;        /* 30   full scan every scan_period-th frame (game_session.py:130) */
+    int32_t max_diff;           /* 4    game_session.py:189 */
+    int32_t smart_scan;         /* 1: the session owns the boards' check sets; 0: they stay the caller's */
+} cbv_session_config;
+typedef struct {
+    int32_t frame;      /* frames since cbv_pipeline_session_begin, 0 based */
+    uint16_t move;      /* cbv_move of include/cbv_chess.h */
+    uint8_t status;     /* CBV_GAME_* (rule 0: CBV_GAME_MOVE_CONFIRMED) */
+    uint8_t candidates; /* candidate moves the rule saw (1) */
+} cbv_session_move;
+typedef struct {
+    int8_t sq[64];              /* 0 empty, piece type | 8 for black; index = python-chess square */
+    int32_t turn, castling, ep, halfmove, fullmove;
+    uint64_t expected;          /* the board's occupancy, ROI numbering */
+    uint64_t smart_mask;        /* the smart-scan set, ROI numbering */
+    uint64_t stable_occupancy;  /* ROI numbering */
+    uint64_t rejected;          /* the last occupancy the rule rejected on this board (valid with rejected_valid) */
+    int32_t rejected_valid;
+    int32_t stable_count;
+    int32_t c;                  /* frames since begin */
+    int32_t last_move_c;        /* c of the last accepted move, 0 = none yet */
+    int32_t n_moves;            /* moves accepted since begin */
+    int32_t last_candidates;    /* candidates (rule 0) or status (rule 1) of the last rule call, -1 = none yet */
+} cbv_session_state;
+/* Start a session on a board (any board handle) of a configured pipeline, from `fen` (NULL = the start position).
+ * CBV_ERR_STATE before cbv_pipeline_configure or on a board that has not 64 squares, CBV_ERR_ARG for a bad FEN or
+ * configuration.  A running session is replaced.  With smart_scan, cbv_pipeline_set_check_squares on the board returns
+ * CBV_ERR_STATE until the session ends; cbv_pipeline_update_references and cbv_pipeline_reset_state stay legal. */
+CBV_API int cbv_pipeline_session_begin(cbv_pipeline* board, const cbv_session_config* cfg, const char* fen);
+/* End it: later runs are what they were before the session, with the check sets the caller had set before it. */
+CBV_API int cbv_pipeline_session_end(cbv_pipeline* board);
+/* The moves accepted since the previous call, oldest first (waits for the runs in flight).  *n = records written.
+ * CBV_ERR_UNSUPPORTED, with the newest records in `out`, when more than CBV_SESSION_RING (or `cap`) were waiting. */
+CBV_API int cbv_pipeline_session_moves(cbv_pipeline* board, cbv_session_move* out, int cap, int* n);
+CBV_API int cbv_pipeline_session_state(cbv_pipeline* board, cbv_session_state* out);
+/* Host buffers, no GPU (ctx may be NULL): the walk itself over n frames from their result and NoiseHandler records;
+ * `state` is read and updated.  Stops behind the first accepted move: returns the frames consumed (n when none was
+ * accepted), *accepted = 1 and *move filled when one was.  Negative on bad arguments. */
+CBV_API int cbv_session_walk(const cbv_session_config* cfg, cbv_session_state* state, const cbv_frame_result* results,
+                             const cbv_noise_result* noise, int n, cbv_session_move* move, int* accepted);
+/* a cbv_session_state at the start of a session from `fen` (NULL = the start position); 0, or CBV_ERR_ARG */
+CBV_API int cbv_session_state_init(cbv_session_state* state, const char* fen);
+/* the FEN of a session state (python-chess Board.fen()); returns the length */
+CBV_API int cbv_session_state_fen(const cbv_session_state* state, char* out, int cap);
+/* The device's wave-parallel legal move generator on one position, for tests: list(board.legal_moves) of `fen` in
+ * python-chess order; *n = count. */
+CBV_API int cbv_session_device_legal_moves(cbv_ctx* ctx, const char* fen, uint16_t* out, int cap, int* n);
+/* ... and its time: one launch that builds the list `reps` times, *ms = the launch's GPU time (timing tools) */
+CBV_API int cbv_session_generator_time(cbv_ctx* ctx, const char* fen, int reps, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
