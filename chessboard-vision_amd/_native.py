@@ -167,7 +167,8 @@ class NoiseDevState(C.Structure):
 class SessionConfig(C.Structure):
     """cbv_session_config: the game session of a board (include/cbv.h)."""
     _fields_ = [("rule", C.c_int32), ("stability_required", C.c_int32), ("cooldown_frames", C.c_int32),
-                ("scan_period", C.c_int32), ("max_diff", C.c_int32), ("smart_scan", C.c_int32)]
+                ("scan_period", C.c_int32), ("max_diff", C.c_int32), ("smart_scan", C.c_int32),
+                ("online", C.c_int32), ("radar", C.c_int32)]
 
 
 class SessionMove(C.Structure):
@@ -179,11 +180,28 @@ class SessionState(C.Structure):
                 ("halfmove", C.c_int32), ("fullmove", C.c_int32), ("expected", C.c_uint64), ("smart_mask", C.c_uint64),
                 ("stable_occupancy", C.c_uint64), ("rejected", C.c_uint64), ("rejected_valid", C.c_int32),
                 ("stable_count", C.c_int32), ("c", C.c_int32), ("last_move_c", C.c_int32), ("n_moves", C.c_int32),
-                ("last_candidates", C.c_int32)]
+                ("last_candidates", C.c_int32), ("waiting_for_opponent", C.c_int32), ("ignored_move", C.c_int32),
+                ("ignored_frame", C.c_int32), ("n_ignored", C.c_int32)]
+
+
+class SessionPos(C.Structure):
+    """cbv_session_pos: the board part of a SessionState."""
+    _fields_ = [("sq", C.c_int8 * 64), ("turn", C.c_int32), ("castling", C.c_int32), ("ep", C.c_int32),
+                ("halfmove", C.c_int32), ("fullmove", C.c_int32)]
+
+
+class SessionEvent(C.Structure):
+    _fields_ = [("at_frame", C.c_int32), ("waiting_for_opponent", C.c_int32), ("pos", SessionPos)]
+
+
+class SessionRadar(C.Structure):
+    _fields_ = [("lifted", C.c_int8), ("destinations", C.c_uint64)]
 
 
 SESSION_RULES = {"session": 0, "game_state": 1}
 SESSION_RING = 1024
+SESSION_ONLINE = {None: 0, "white": 1, "black": 2}
+SESSION_EVENTS = 64
 
 
 class RawFrame(C.Structure):
@@ -302,6 +320,13 @@ def load():
         "cbv_session_walk": (i32, [P(SessionConfig), P(SessionState), P(FrameResult), P(NoiseResult), i32, P(SessionMove), P(i32)]),
         "cbv_session_state_init": (i32, [P(SessionState), C.c_char_p]),
         "cbv_session_state_fen": (i32, [P(SessionState), C.c_char_p, i32]),
+        "cbv_session_pos_from_moves": (i32, [C.c_char_p, P(SessionPos), P(i32)]),
+        "cbv_pipeline_session_sync": (i32, [vp, i32, P(SessionPos), i32]),
+        "cbv_pipeline_session_frames": (i32, [vp, P(i32)]),
+        "cbv_pipeline_session_radar": (i32, [vp, i32, i32, P(SessionRadar)]),
+        "cbv_session_walk_events": (i32, [P(SessionConfig), P(SessionState), P(FrameResult), P(NoiseResult), i32, P(SessionEvent), i32,
+                                          P(i32), P(SessionRadar), P(SessionMove), P(i32)]),
+        "cbv_session_state_init_cfg": (i32, [P(SessionState), P(SessionConfig), C.c_char_p]),
         "cbv_session_device_legal_moves": (i32, [vp, C.c_char_p, P(C.c_uint16), i32, P(i32)]),
         "cbv_session_generator_time": (i32, [vp, C.c_char_p, i32, P(dbl)]),
     }

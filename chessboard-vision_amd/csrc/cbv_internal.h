@@ -481,7 +481,9 @@ int launch_scan_session(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, co
                         const SessionDev* ses, int first_round, u16* hist);
 // packing, NoiseHandler and the session's walk of one round: frames [resume, count) of the run
 int launch_session_walk(cbv_ctx* ctx, const u8* flags, int n, cbv_frame_result* results, int count, cbv_noise_state* noise_state,
-                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round);
+                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round, cbv_session_radar* radar);
+// a board event between two segments of a run (cbv_pipeline_session_sync): *ev is read now and travels with the launch
+int launch_session_event(cbv_ctx* ctx, SessionDev* ses, const cbv_session_event* ev);
 // the wave generator alone, `reps` times on the position at the head of *state_dev (tests, timing)
 int launch_session_legal(cbv_ctx* ctx, const cbv_session_state* state_dev, u16* out_dev, int* n_dev, int reps);
 

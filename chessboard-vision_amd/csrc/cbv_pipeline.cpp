@@ -6,6 +6,7 @@
 
 #include "../../include/cbv_chess.h"
 #include "cbv_internal.h"
+#include "session_core.h"
 
 // One board of a pipeline: what configure's squares part sets up (board_setup).  Board 0 is the pipeline's own; the
 // boards cbv_pipeline_add_board attaches have the same shape.
@@ -33,6 +34,11 @@ struct Board {
     cbv_session_config ses_cfg = {};
     DevBuf d_session, d_hist;
     int ses_drained = 0;
+    // online play: the board events that wait for their frame (cbv_pipeline_session_sync), the session frames enqueued so
+    // far (the session frame index of the next run's first frame) and the radar records, one per slot
+    std::vector<cbv_session_event> ses_events;
+    int ses_frames = 0;
+    DevBuf d_radar;
     bool adaptive() const { return calibrated && model_mode != CBV_MODEL_FROZEN; } // k_model_scan runs for this board
 };
 
@@ -385,7 +391,7 @@ static void board_free(cbv_pipeline* p)
     if (b.h_stage) (void)hipHostFree(b.h_stage);
     if (b.warped) (void)hipFree(b.warped);
     DevBuf* bufs[] = {&b.d_descs, &b.d_masks, &b.d_gray, &b.d_stats, &b.d_ref, &b.d_state, &b.d_results, &b.d_flags, &b.d_dec, &b.d_mean,
-                      &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over, &b.d_session, &b.d_hist};
+                      &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over, &b.d_session, &b.d_hist, &b.d_radar};
     for (auto d : bufs) dev_free(d);
     delete p;
 }
@@ -915,7 +921,7 @@ static void mark_mirrored(Pipe& P, int s0, int cnt, bool held)
 
 // The scan stage of ONE board for a run: HoughCircles' second pass and the model scan (`with_pre`: not yet done by the
 // multi-board launches), the temporal scan, packing and NoiseHandler; with a game session the rounds of k_session.hip.
-static int board_scan(Pipe& P, const Board& q, const BoardDev& T, int slot0, int count, bool mirrored, bool with_pre, const u32* retry)
+static int board_scan(Pipe& P, Board& q, const BoardDev& T, int slot0, int count, bool mirrored, bool with_pre, const u32* retry)
 {
     cbv_ctx* ctx = P.ctx;
     const u8* gray = T.gray + T.plane_total * slot0;
@@ -936,18 +942,42 @@ static int board_scan(Pipe& P, const Board& q, const BoardDev& T, int slot0, int
     if (!q.session)
         return launch_scan(ctx, T.descs, T.sp, gray, T.plane_total, dec, T.ref, T.state, flags, T.results + slot0, count, check, T.noise_state,
                            T.noise + slot0, mir);
-    // Two accepted moves are at least `gap` frames apart, so a run holds at most ceil(count / gap) of them, and one more
-    // round finishes behind the last; rounds that find the run finished return at once.
+    // Two accepted moves are at least `gap` frames apart, so `len` frames hold at most ceil(len / gap) of them, and one more
+    // round finishes behind the last; rounds that find the frames finished return at once.
     const int gap = std::max(q.ses_cfg.stability_required, q.ses_cfg.cooldown_frames + 1);
-    const int rounds = 1 + (count + gap - 1) / gap;
     SessionDev* ses = (SessionDev*)q.d_session.p;
     u16* hist = (u16*)q.d_hist.p + (size_t)CBV_MAX_SQUARES * slot0;
-    for (int k = 0; k < rounds; k++) {
-        prof_begin(ctx, CBV_K_SCAN);
-        RC(launch_scan_session(ctx, T.descs, T.sp, gray, T.plane_total, dec, T.ref, T.state, flags, count, check, ses, k == 0, hist));
-        RC(launch_session_walk(ctx, flags, T.n, T.results + slot0, count, T.noise_state, T.noise + slot0, mir, ses, k == 0));
-        prof_end(ctx, CBV_K_SCAN);
+    cbv_session_radar* radar = q.ses_cfg.radar ? (cbv_session_radar*)q.d_radar.p + slot0 : nullptr;
+    // The run is cut at the board events that fall inside it (cbv_pipeline_session_sync): an event changes the smart mask,
+    // so the frames behind it must not be scanned with the check sets of the board that was.  Each segment is the rounds
+    // above on its own frames, k_session_event sits between them on the same stream, and nothing waits for the host.  With
+    // no event due the one segment is the run.
+    const int c0 = q.ses_frames; // session frame index of the run's first frame
+    size_t e = 0;
+    for (int a = 0; a < count;) {
+        for (; e < q.ses_events.size() && q.ses_events[e].at_frame <= c0 + a; e++) {
+            prof_begin(ctx, CBV_K_SCAN);
+            RC(launch_session_event(ctx, ses, &q.ses_events[e]));
+            prof_end(ctx, CBV_K_SCAN);
+        }
+        int b = count;
+        if (e < q.ses_events.size() && q.ses_events[e].at_frame < c0 + count) b = q.ses_events[e].at_frame - c0;
+        const int len = b - a;
+        ResultMirror smir = mir;
+        if (smir.records) smir.records += a;
+        const size_t sq0 = (size_t)CBV_MAX_SQUARES * a;
+        for (int k = 0, nr = 1 + (len + gap - 1) / gap; k < nr; k++) {
+            prof_begin(ctx, CBV_K_SCAN);
+            RC(launch_scan_session(ctx, T.descs, T.sp, gray + T.plane_total * a, T.plane_total, dec + sq0, T.ref, T.state, flags + sq0, len,
+                                   check ? check + a : nullptr, ses, k == 0, hist + sq0));
+            RC(launch_session_walk(ctx, flags + sq0, T.n, T.results + slot0 + a, len, T.noise_state, T.noise + slot0 + a, smir, ses, k == 0,
+                                   radar ? radar + a : nullptr));
+            prof_end(ctx, CBV_K_SCAN);
+        }
+        a = b;
     }
+    q.ses_events.erase(q.ses_events.begin(), q.ses_events.begin() + e);
+    q.ses_frames += count;
     return CBV_OK;
 }
 
@@ -1292,17 +1322,26 @@ extern "C" int cbv_pipeline_session_begin(cbv_pipeline* p, const cbv_session_con
     // (the frame counts are bounded so that board_scan's round count stays far inside an int)
     const int frames_max = 1 << 24;
     if ((cfg->rule != CBV_SESSION_RULE_INFER && cfg->rule != CBV_SESSION_RULE_OCCUPANCY) || cfg->stability_required < 1 ||
-        cfg->stability_required > frames_max || cfg->cooldown_frames < 0 || cfg->cooldown_frames > frames_max || cfg->scan_period < 0 || cfg->max_diff < 0)
-        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_begin: bad configuration (rule %d, stability_required %d, cooldown_frames %d, scan_period %d, max_diff %d)",
-                        cfg->rule, cfg->stability_required, cfg->cooldown_frames, cfg->scan_period, cfg->max_diff);
+        cfg->stability_required > frames_max || cfg->cooldown_frames < 0 || cfg->cooldown_frames > frames_max || cfg->scan_period < 0 || cfg->max_diff < 0 ||
+        !ses_config_ok(cfg))
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_begin: bad configuration (rule %d, stability_required %d, cooldown_frames %d, scan_period %d, max_diff %d, "
+                        "online %d, radar %d; online needs CBV_SESSION_RULE_INFER)",
+                        cfg->rule, cfg->stability_required, cfg->cooldown_frames, cfg->scan_period, cfg->max_diff, cfg->online, cfg->radar);
     std::vector<SessionDev> host(1);
     memset(host.data(), 0, sizeof(SessionDev));
     host[0].cfg = *cfg;
     if (cbv_session_state_init(&host[0].st, fen) != 0) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_begin: not a FEN: %s", fen ? fen : "(null)");
+    host[0].st.waiting_for_opponent = ses_initial_waiting(cfg, &host[0].st);
     CBV_ENTER(ctx);
     RC(session_sync(P));
     RC(dev_ensure(ctx, &B.d_session, sizeof(SessionDev)));
     RC(dev_ensure(ctx, &B.d_hist, sizeof(u16) * CBV_MAX_SQUARES * (size_t)P.max_frames));
+    if (cfg->radar) {
+        RC(dev_ensure(ctx, &B.d_radar, sizeof(cbv_session_radar) * (size_t)P.max_frames));
+        CBV_HIP(ctx, hipMemset(B.d_radar.p, 0, sizeof(cbv_session_radar) * (size_t)P.max_frames));
+    }
+    B.ses_events.clear();
+    B.ses_frames = 0;
     CBV_HIP(ctx, hipMemcpy(B.d_session.p, host.data(), sizeof(SessionDev), hipMemcpyHostToDevice));
     B.session = true;
     B.ses_cfg = *cfg;
@@ -1319,7 +1358,62 @@ extern "C" int cbv_pipeline_session_end(cbv_pipeline* p)
     CBV_ENTER(ctx);
     RC(session_sync(P));
     p->b.session = false;
+    p->b.ses_events.clear();
     return pipeline_tables(P);
+}
+
+extern "C" int cbv_pipeline_session_sync(cbv_pipeline* p, int at_frame, const cbv_session_pos* pos, int waiting_for_opponent)
+{
+    if (!p || !pos) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_session_sync: null argument");
+    cbv_ctx* ctx = p->pipe->ctx;
+    Board& B = p->b;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu); // (host state only: no device call, no wait)
+    if (!B.session) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_session_sync: no session is running on this board");
+    cbv_session_event ev;
+    ev.at_frame = at_frame;
+    ev.waiting_for_opponent = waiting_for_opponent ? 1 : 0;
+    ev.pos = *pos;
+    bool kings[2] = {false, false};
+    for (int i = 0; i < 64; i++) {
+        const int pc = pos->sq[i];
+        if (pc < 0 || (pc & 7) > 6 || (pc && !(pc & 7))) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_sync: square %d holds %d, not a piece", i, pc);
+        if ((pc & 7) == 6) kings[(pc & 8) ? 1 : 0] = true;
+    }
+    if (!kings[0] || !kings[1] || (pos->turn != 0 && pos->turn != 1) || pos->ep < -1 || pos->ep > 63 || (pos->castling & ~15))
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_sync: not a position (build it with cbv_session_pos_from_moves)");
+    const int last = B.ses_events.empty() ? B.ses_frames : B.ses_events.back().at_frame;
+    const int rc = ses_events_check(B.ses_frames, last, (int)B.ses_events.size(), &ev, 1);
+    if (rc == CBV_ERR_ARG)
+        return cbv_fail(ctx, rc, "cbv_pipeline_session_sync: at_frame %d lies in front of %s %d", at_frame,
+                        at_frame < B.ses_frames ? "the session's next frame" : "the last queued event's frame", at_frame < B.ses_frames ? B.ses_frames : last);
+    if (rc != CBV_OK) return cbv_fail(ctx, rc, "cbv_pipeline_session_sync: %d events are waiting, the queue is full", (int)B.ses_events.size());
+    B.ses_events.push_back(ev);
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_session_frames(cbv_pipeline* p, int* frames)
+{
+    if (!p || !frames) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_session_frames: null argument");
+    cbv_ctx* ctx = p->pipe->ctx;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    if (!p->b.session) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_session_frames: no session is running on this board");
+    *frames = p->b.ses_frames;
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_session_radar(cbv_pipeline* p, int slot0, int n, cbv_session_radar* out)
+{
+    if (!p || !out) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_session_radar: null argument");
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (!p->b.session || !p->b.ses_cfg.radar)
+        return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_session_radar: no session with radar = 1 is running on this board");
+    if (slot0 < 0 || n <= 0 || slot0 + n > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_radar: bad slot range");
+    CBV_ENTER(ctx);
+    RC(join_scan(P));
+    CBV_HIP(ctx, hipMemcpyAsync(out, (cbv_session_radar*)p->b.d_radar.p + slot0, sizeof(cbv_session_radar) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
 }
 
 static int session_fetch(cbv_pipeline* p, const char* who, std::vector<SessionDev>& host)

@@ -347,6 +347,8 @@ int cbv_session_state_init(cbv_session_state* st, const char* fen)
     cc_gen_legal(ses_pos(&t), &legal, &pseudo);
     ses_refresh(&t, ses_dest_squares(&legal));
     t.last_candidates = -1;
+    t.ignored_move = CBV_MOVE_NONE;
+    t.ignored_frame = -1;
     *st = t;
     return 0;
 }
@@ -369,6 +371,97 @@ int cbv_session_walk(const cbv_session_config* cfg, cbv_session_state* st, const
         const u64 vision = results[t].stable_occupied;
         if (!ses_frame_pre(cfg, st, vision, noise && noise[t].state == 1)) continue;
         cc_gen_legal(ses_pos(st), &legal, &scratch);
+        if (!ses_frame_rule(cfg, st, vision, &legal, &scratch, move)) continue;
+        cc_gen_legal(ses_pos(st), &legal, &scratch);
+        ses_refresh(st, ses_dest_squares(&legal));
+        *accepted = 1;
+        return t + 1;
+    }
+    return n;
+}
+
+int cbv_session_state_init_cfg(cbv_session_state* st, const cbv_session_config* cfg, const char* fen)
+{
+    if (!cfg || !ses_config_ok(cfg)) return CBV_ERR_ARG;
+    cbv_session_state t;
+    if (cbv_session_state_init(&t, fen) != 0) return CBV_ERR_ARG;
+    t.waiting_for_opponent = ses_initial_waiting(cfg, &t);
+    *st = t;
+    return 0;
+}
+
+// LichessSession._sync_moves' replay (lichess_session.py:99-105): reset, push_uci per token, failures skipped.  As
+// python-chess's parse_uci, castling is also taken as king-takes-own-rook; "0000" (a null move) is skipped.
+int cbv_session_pos_from_moves(const char* moves, cbv_session_pos* out, int* pushed)
+{
+    if (pushed) *pushed = 0;
+    if (!out) return CBV_ERR_ARG;
+    static_assert(sizeof(cbv_session_pos) == sizeof(cbv_pos), "cbv_session_pos is the POD board");
+    cbv_pos b;
+    if (!parse_fen_pos(&b, START_FEN)) return CBV_ERR_ARG;
+    int n = 0;
+    for (const char* p = moves ? moves : ""; *p;) {
+        while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r') p++;
+        const char* q = p;
+        while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') q++;
+        const int len = (int)(q - p);
+        if ((len == 4 || len == 5) && p[0] >= 'a' && p[0] <= 'h' && p[1] >= '1' && p[1] <= '8' && p[2] >= 'a' && p[2] <= 'h' &&
+            p[3] >= '1' && p[3] <= '8') {
+            const int from = (p[1] - '1') * 8 + (p[0] - 'a');
+            int to = (p[3] - '1') * 8 + (p[2] - 'a');
+            const char* pc = len == 5 ? strchr(PIECE_CHARS + 1, p[4]) : nullptr;
+            const int promo = pc ? (int)(pc - PIECE_CHARS) : 0;
+            if ((b.sq[from] & 7) == KING && file_of(from) == 4 && rank_of(from) == rank_of(to) && b.sq[to] == ((b.sq[from] & 8) | ROOK))
+                to = rank_of(from) * 8 + (file_of(to) == 7 ? 6 : file_of(to) == 0 ? 2 : file_of(to));
+            const cbv_move m = mk(from, to, promo);
+            if ((len == 4 || pc) && legal(&b, m)) {
+                cc_push(&b, m);
+                n++;
+            }
+        }
+        p = q;
+    }
+    memcpy(out, &b, sizeof(b));
+    if (pushed) *pushed = n;
+    return 0;
+}
+
+int cbv_session_walk_events(const cbv_session_config* cfg, cbv_session_state* st, const cbv_frame_result* results,
+                            const cbv_noise_result* noise, int n, const cbv_session_event* events, int n_events, int* events_used,
+                            cbv_session_radar* radar, cbv_session_move* move, int* accepted)
+{
+    if (accepted) *accepted = 0;
+    if (events_used) *events_used = 0;
+    if (!cfg || !st || !results || n < 0 || !move || !accepted || n_events < 0 || (n_events && !events) || !events_used) return CBV_ERR_ARG;
+    if (!ses_config_ok(cfg)) return CBV_ERR_ARG;
+    const int rc = ses_events_check(st->c, st->c, 0, events, n_events);
+    if (rc != CBV_OK) return rc;
+    cbv_movelist legal, scratch;
+    bool have_legal = false; // of the board as it stands
+    int e = 0;
+    for (int t = 0; t < n; t++) {
+        for (; e < n_events && events[e].at_frame == st->c; e++) {
+            ses_apply_event(st, &events[e]);
+            cc_gen_legal(ses_pos(st), &legal, &scratch);
+            have_legal = true;
+            ses_refresh(st, ses_dest_squares(&legal));
+        }
+        *events_used = e;
+        const u64 vision = results[t].stable_occupied;
+        if (radar) {
+            radar[t].lifted = -1;
+            radar[t].destinations = 0;
+            const int roi = cfg->radar ? ses_radar_lifted(st, vision) : -1;
+            if (roi >= 0) {
+                if (!have_legal) cc_gen_legal(ses_pos(st), &legal, &scratch);
+                have_legal = true;
+                radar[t].lifted = (int8_t)roi;
+                radar[t].destinations = cc_flip_rows(ses_radar_dests(&legal, roi ^ 56, 0, 1));
+            }
+        }
+        if (!ses_frame_pre(cfg, st, vision, noise && noise[t].state == 1)) continue;
+        if (!have_legal) cc_gen_legal(ses_pos(st), &legal, &scratch);
+        have_legal = true;
         if (!ses_frame_rule(cfg, st, vision, &legal, &scratch, move)) continue;
         cc_gen_legal(ses_pos(st), &legal, &scratch);
         ses_refresh(st, ses_dest_squares(&legal));

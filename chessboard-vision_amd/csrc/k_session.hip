@@ -14,7 +14,12 @@
 // The walk is one sequential chain on one wave; the rules use the wave when the walk does reach the generator: lane 0
 // lists the pseudo-legal moves in python-chess order, every lane tests the king's safety of one of them, a ballot and
 // a prefix count keep the order, and the destinations of the smart mask are OR-reduced across the lanes.
-// on_move_detected is taken as always True: the reference's Lichess hook is out of scope.
+// The list is built once per walk and kept while the board stands (a rejected rule call, the radar); an accepted move
+// ends the walk.
+// Online play (include/cbv.h): the turn gate is part of ses_frame_rule; a board event (cbv_pipeline_session_sync) is
+// k_session_event between two segments of a run, each segment being the rounds above on its own frames (cbv_pipeline.cpp,
+// board_scan); the radar is computed by the walk in front of the stable-move step of each frame, its destinations as an
+// OR across the lanes over the kept list.
 #include "cbv_internal.h"
 #include "cbv_device.h"
 #include "noise_core.h"
@@ -65,11 +70,12 @@ __device__ u64 wave_gen_legal(const cbv_pos* b, WalkLds* L)
 
 __global__ __launch_bounds__(64) void k_session_walk(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count,
                                                       cbv_noise_state* __restrict__ noise_state, cbv_noise_result* __restrict__ noise_out,
-                                                      ResultMirror mir, SessionDev* __restrict__ ses, int first_round)
+                                                      ResultMirror mir, SessionDev* __restrict__ ses, int first_round,
+                                                      cbv_session_radar* __restrict__ radar)
 {
     __shared__ WalkLds L;
     __shared__ cbv_session_state st;
-    __shared__ int sh_t, sh_flag;
+    __shared__ int sh_t, sh_flag, sh_roi;
     const int lane = threadIdx.x;
     const int r = first_round ? 0 : ses->resume;
     if (r > count) return;
@@ -96,24 +102,50 @@ __global__ __launch_bounds__(64) void k_session_walk(const u8* __restrict__ flag
     }
     __syncthreads();
     int t = r;
-    bool accepted = false;
+    bool accepted = false, have_legal = false; // have_legal: L.legal is the list of the board in st
+    int radar_done = -1, memo_roi = -1;        // lane 0: the frame whose radar record is written; the last lifted square
+    u64 memo_dests = 0;                        // ... and its destinations (the board does not change inside a walk)
     for (;;) {
-        if (lane == 0) { // frames up to the next one on which the rule has to run
-            int tt = t;
-            bool want = false;
-            for (; tt < count; tt++)
-                if (ses_frame_pre(&cfg, &st, results[tt].stable_occupied, noise_out[tt].state == 1)) {
-                    want = true;
+        if (lane == 0) { // frames up to the next one that needs the wave: 1 the rule has to run, 2 the radar needs the list
+            int tt = t, what = 0;
+            for (; tt < count; tt++) {
+                const u64 vision = results[tt].stable_occupied;
+                if (radar && radar_done != tt) {
+                    const int roi = ses_radar_lifted(&st, vision);
+                    if (roi >= 0 && roi != memo_roi) {
+                        sh_roi = roi;
+                        what = 2;
+                        break;
+                    }
+                    radar[tt].lifted = (int8_t)roi;
+                    radar[tt].destinations = roi >= 0 ? memo_dests : 0ull;
+                    radar_done = tt;
+                }
+                if (ses_frame_pre(&cfg, &st, vision, noise_out[tt].state == 1)) {
+                    what = 1;
                     break;
                 }
+            }
             sh_t = tt;
-            sh_flag = want ? 1 : 0;
+            sh_flag = what;
         }
         __syncthreads();
         t = sh_t;
-        if (!sh_flag) break;
+        const int what = sh_flag;
+        if (!what) break;
         __syncthreads(); // (sh_flag is rewritten below)
-        wave_gen_legal(ses_pos(&st), &L);
+        if (!have_legal) wave_gen_legal(ses_pos(&st), &L);
+        have_legal = true;
+        if (what == 2) { // the lifted piece's destinations: every lane takes its share of the list
+            const int roi = sh_roi;
+            const u64 d = cc_flip_rows(wave_or_u64(ses_radar_dests(&L.legal, roi ^ 56, lane, 64)));
+            if (lane == 0) {
+                memo_roi = roi;
+                memo_dests = d;
+            }
+            __syncthreads();
+            continue; // frame t again: lane 0 writes its record from the memo and goes on
+        }
         if (lane == 0) {
             cbv_session_move rec;
             const bool acc = ses_frame_rule(&cfg, &st, results[t].stable_occupied, &L.legal, &L.scratch, &rec);
@@ -144,6 +176,24 @@ __global__ __launch_bounds__(64) void k_session_walk(const u8* __restrict__ flag
     }
 }
 
+// A board event in front of the next segment's first frame: the new board, its legal moves, expected and smart mask.
+// `ev` travels in the kernel arguments, so the host's queue entry is free as soon as the launch returns.
+__global__ __launch_bounds__(64) void k_session_event(SessionDev* __restrict__ ses, const cbv_session_event ev)
+{
+    __shared__ WalkLds L;
+    __shared__ cbv_session_state st;
+    if (threadIdx.x == 0) {
+        st = ses->st;
+        ses_apply_event(&st, &ev);
+    }
+    __syncthreads();
+    const u64 dests = wave_gen_legal(ses_pos(&st), &L);
+    if (threadIdx.x == 0) {
+        ses_refresh(&st, dests);
+        ses->st = st;
+    }
+}
+
 // the generator alone, for tests and timing: `reps` calls on the position at the head of *state
 __global__ __launch_bounds__(64) void k_session_legal(const cbv_session_state* __restrict__ state, u16* __restrict__ out, int* __restrict__ n_out, int reps)
 {
@@ -160,9 +210,17 @@ __global__ __launch_bounds__(64) void k_session_legal(const cbv_session_state* _
 } // namespace
 
 int launch_session_walk(cbv_ctx* ctx, const u8* flags, int n, cbv_frame_result* results, int count, cbv_noise_state* noise_state,
-                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round)
+                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round, cbv_session_radar* radar)
 {
-    hipLaunchKernelGGL(k_session_walk, dim3(1), dim3(64), 0, ctx->stream, flags, n, results, count, noise_state, noise_out, mir, ses, first_round);
+    hipLaunchKernelGGL(k_session_walk, dim3(1), dim3(64), 0, ctx->stream, flags, n, results, count, noise_state, noise_out, mir, ses, first_round,
+                       radar);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_session_event(cbv_ctx* ctx, SessionDev* ses, const cbv_session_event* ev)
+{
+    hipLaunchKernelGGL(k_session_event, dim3(1), dim3(64), 0, ctx->stream, ses, *ev);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }

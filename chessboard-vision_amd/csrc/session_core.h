@@ -4,6 +4,8 @@
 //   ses_frame_pre   steps 1-5 of a frame and the two exact shortcuts: does the rule have to run?
 //   ses_frame_rule  the rule on the legal moves of the board; pushes and records an accepted move
 //   ses_refresh     expected occupancy and smart mask from the legal moves of the (new) board
+// and for online play (LichessSession): ses_frame_rule's turn gate, ses_apply_event (the board part of _sync_moves; the
+// caller follows it with ses_refresh) and ses_radar_lifted / ses_radar_dests (_update_radar_ui).
 #ifndef CBV_SESSION_CORE_H
 #define CBV_SESSION_CORE_H
 #include "../../include/cbv.h"
@@ -53,6 +55,14 @@ CBV_HD inline bool ses_frame_rule(const cbv_session_config* cfg, cbv_session_sta
     } else {
         cand = cc_infer_move(b, legal, scratch, vis_sq, &m);
         st->last_candidates = cand;
+        if (m != CBV_MOVE_NONE && cfg->online && st->waiting_for_opponent) {
+            // on_move_detected returns False (lichess_session.py:46-48): nothing is pushed and nothing restarts; the
+            // occupancy is remembered so that the identical frames behind this one do not ask again
+            st->ignored_move = m;
+            st->ignored_frame = st->c - 1;
+            st->n_ignored += 1;
+            m = CBV_MOVE_NONE;
+        }
         if (m != CBV_MOVE_NONE) cc_push(b, m);
     }
     if (m == CBV_MOVE_NONE) {
@@ -68,6 +78,7 @@ CBV_HD inline bool ses_frame_rule(const cbv_session_config* cfg, cbv_session_sta
     st->stable_count = 0;
     st->rejected_valid = 0;
     st->n_moves += 1;
+    if (cfg->online) st->waiting_for_opponent = 1; // make_move is taken as sent (lichess_session.py:53-55)
     return true;
 }
 
@@ -83,6 +94,68 @@ CBV_HD inline cc_u64 ses_dest_squares(const cbv_movelist* legal)
 {
     cc_u64 d = 0;
     for (int i = 0, n = cc_stored(legal); i < n; i++) d |= cc_bit(cc_to(legal->m[i]));
+    return d;
+}
+
+// ---- online play ----
+
+CBV_HD inline bool ses_config_ok(const cbv_session_config* cfg)
+{
+    if (cfg->online < CBV_SESSION_ONLINE_OFF || cfg->online > CBV_SESSION_ONLINE_BLACK) return false;
+    if (cfg->online && cfg->rule != CBV_SESSION_RULE_INFER) return false; // LichessSession is GameSession._infer_move
+    return cfg->radar == 0 || cfg->radar == 1;
+}
+
+// waiting_for_opponent at the start of a session: not is_my_turn (lichess_client.py:193-204) by the side to move
+CBV_HD inline int ses_initial_waiting(const cbv_session_config* cfg, const cbv_session_state* st)
+{
+    if (!cfg->online) return 0;
+    return (ses_pos(st)->turn != 0) == (cfg->online == CBV_SESSION_ONLINE_WHITE) ? 0 : 1;
+}
+
+// events [0, n) against a session whose next frame is `c`, `waiting` of them already queued: CBV_OK, CBV_ERR_ARG (a frame
+// in the past or out of order), CBV_ERR_UNSUPPORTED (the queue is full)
+CBV_HD inline int ses_events_check(int c, int last_at, int waiting, const cbv_session_event* ev, int n)
+{
+    for (int i = 0; i < n; i++) {
+        if (ev[i].at_frame < c || ev[i].at_frame < last_at) return CBV_ERR_ARG;
+        last_at = ev[i].at_frame;
+    }
+    return waiting + n > CBV_SESSION_EVENTS ? CBV_ERR_UNSUPPORTED : CBV_OK;
+}
+
+// _sync_moves under the lock (lichess_session.py:98-111), the board part; ses_refresh(st, destinations of the new board)
+// completes it.  stable_count, stable_occupancy and last_move_c stay.
+CBV_HD inline void ses_apply_event(cbv_session_state* st, const cbv_session_event* ev)
+{
+    cbv_pos* b = ses_pos(st);
+    for (int i = 0; i < 64; i++) b->sq[i] = ev->pos.sq[i];
+    b->turn = ev->pos.turn;
+    b->castling = ev->pos.castling;
+    b->ep = ev->pos.ep;
+    b->halfmove = ev->pos.halfmove;
+    b->fullmove = ev->pos.fullmove;
+    st->rejected_valid = 0; // the memo belongs to the board that was
+    st->waiting_for_opponent = ev->waiting_for_opponent ? 1 : 0;
+}
+
+// _update_radar_ui (game_session.py:273-285): the ROI index of the one lifted piece of the side to move, or -1
+CBV_HD inline int ses_radar_lifted(const cbv_session_state* st, cc_u64 vision)
+{
+    const cc_u64 lifted = st->expected & ~vision;
+    if (cc_popcount(lifted) != 1) return -1;
+    const int roi = cc_msb(lifted);
+    const int piece = ses_pos(st)->sq[roi ^ 56]; // ROI 8 * (7 - rank) + file -> square 8 * rank + file
+    if (!piece || ((piece & 8) == 0) != (ses_pos(st)->turn != 0)) return -1;
+    return roi;
+}
+
+// destinations (square numbering) of the moves [i0, n) step `step` of `legal` that start on `from_sq`
+CBV_HD inline cc_u64 ses_radar_dests(const cbv_movelist* legal, int from_sq, int i0, int step)
+{
+    cc_u64 d = 0;
+    for (int i = i0, n = cc_stored(legal); i < n; i += step)
+        if (cc_from(legal->m[i]) == from_sq) d |= cc_bit(cc_to(legal->m[i]));
     return d;
 }
 

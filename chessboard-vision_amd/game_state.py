@@ -57,6 +57,28 @@ class GameState:
         status = lib.cbv_game_process_occupancy(self.board._h, square_bits, C.byref(code))
         return chess.Move._from_code(code.value), lib.cbv_game_status_name(status).decode()
 
+    def radar(self, vision_occupied):
+        """GameSession._update_radar_ui (game_session.py:271-291): (lifted square or None, [destinations]) as
+        (file, rank) pairs — the one expected square vision misses, when its piece belongs to the side to move, and
+        where that piece may go."""
+        lifted = self.get_board_occupancy() - set(vision_occupied)
+        if len(lifted) != 1:
+            return None, []
+        (f, r), = lifted
+        piece = self.board.piece_at(chess.square(f, r))
+        if not piece or piece.color != self.board.turn:
+            return None, []
+        return (f, r), [(chess.square_file(m.to_square), chess.square_rank(m.to_square)) for m in self.get_legal_moves_from(f, r)]
+
+    def sync_moves(self, moves_str):
+        """LichessSession._sync_moves' replay (lichess_session.py:99-105): reset, then every UCI token that is legal."""
+        self.board.reset()
+        for uci in (moves_str or "").split():
+            try:
+                self.board.push_uci(uci)
+            except (ValueError, IndexError):
+                pass
+
     def reset(self):
         self.board.reset()
 

@@ -156,13 +156,16 @@ class _BoardMethods:
     def occupied(self, result, stable=True):
         return bits_to_positions(result.stable_occupied if stable else result.raw_occupied, self.rois_rc)
 
-    def session_begin(self, rule="session", fps=30, fen=None, **cfg):
+    def session_begin(self, rule="session", fps=30, fen=None, online=None, radar=False, **cfg):
         """Start a game session on this board (include/cbv.h, cbv_pipeline_session_begin): from now on every frame of
         every `run` also goes through the back half of GameSession.on_frame on the device (smart-scan check sets, stable
         move detection, the move rule, and after an accepted move update_references + NoiseHandler.reset()), whatever the
         run length.  `rule`: "session" = GameSession._infer_move, "game_state" = GameState.process_occupancy_change.
         Keywords: stability_required (20), cooldown_frames (round(MOVE_COOLDOWN * fps)), scan_period (30), max_diff (4),
-        smart_scan (True).  Returns a Session."""
+        smart_scan (True).  `online` "white" / "black": the session of LichessSession for that player (rule "session"
+        only) — moves found while it is the opponent's turn are turned down, and the opponent's moves arrive through
+        Session.sync_moves.  `radar`: every frame leaves the lifted piece and its destinations (Session.radar).
+        Returns a Session."""
         from .game_state import StableMoveTracker
         if rule not in N.SESSION_RULES:
             raise ValueError("rule %r: expected one of %s" % (rule, ", ".join(sorted(N.SESSION_RULES))))
@@ -172,8 +175,10 @@ class _BoardMethods:
         if unknown:
             raise TypeError("session_begin: unknown keyword(s) %s" % ", ".join(sorted(unknown)))
         d.update(cfg)
+        if online not in N.SESSION_ONLINE:
+            raise ValueError("online %r: expected 'white', 'black' or None" % (online,))
         c = N.SessionConfig(N.SESSION_RULES[rule], int(d["stability_required"]), int(d["cooldown_frames"]), int(d["scan_period"]),
-                            int(d["max_diff"]), 1 if d["smart_scan"] else 0)
+                            int(d["max_diff"]), 1 if d["smart_scan"] else 0, N.SESSION_ONLINE[online], 1 if radar else 0)
         self.ctx.check(self.ctx.lib.cbv_pipeline_session_begin(self.h_, c, fen.encode() if fen is not None else None))
         return Session(self, c)
 
@@ -219,6 +224,42 @@ class Session:
     @property
     def stable_count(self):
         return self.state().stable_count
+
+    def sync_moves(self, moves_str, at_frame=None):
+        """LichessSession._sync_moves (lichess_session.py:89-117) in front of session frame `at_frame` (None = the next frame
+        to be enqueued): the board becomes the start position plus the legal tokens of `moves_str`, and
+        waiting_for_opponent follows from the number of tokens and the player's colour as LichessClient.is_my_turn has it
+        (an offline session is never waiting).  Does not wait for the runs in flight."""
+        pos = N.SessionPos()
+        self.ctx.check(self.ctx.lib.cbv_session_pos_from_moves((moves_str or "").encode(), pos, None))
+        count = len((moves_str or "").split())
+        mine = {0: True, 1: count % 2 == 0, 2: count % 2 == 1}[self.config.online]
+        if at_frame is None:
+            nxt = C.c_int()
+            self.ctx.check(self.ctx.lib.cbv_pipeline_session_frames(self._b.h_, C.byref(nxt)))
+            at_frame = nxt.value
+        self.ctx.check(self.ctx.lib.cbv_pipeline_session_sync(self._b.h_, int(at_frame), pos, 0 if mine else 1))
+
+    def radar(self, slot0, n):
+        """GameSession._update_radar_ui per frame of processed slots: [(lifted (file, rank) or None, [(file, rank), ...])],
+        a1 = (0, 0), the destinations in square order (the reference lists them in move order).  Needs
+        session_begin(radar=True)."""
+        out = (N.SessionRadar * n)()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_session_radar(self._b.h_, slot0, n, out))
+        pos = [(c, 7 - r) for (r, c) in self._b.rois_rc]
+        return [(pos[r.lifted] if r.lifted >= 0 else None, sorted(bits_to_positions(r.destinations, self._b.rois_rc))) for r in out]
+
+    @property
+    def waiting_for_opponent(self):
+        return bool(self.state().waiting_for_opponent)
+
+    @property
+    def ignored(self):
+        """(moves turned down so far, the last of them as (frame, chess_rules.Move) or None).  A move is counted once, on
+        the frame the rule found it, not on the identical frames behind it."""
+        from . import chess_rules as chess
+        st = self.state()
+        return st.n_ignored, ((st.ignored_frame, chess.Move._from_code(st.ignored_move)) if st.n_ignored else None)
 
     def end(self):
         if self._open and self._b.h_:

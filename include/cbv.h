@@ -592,9 +592,10 @@ CBV_API int cbv_pipeline_model(cbv_pipeline* board, int which, int roi, float* o
  * frames the set stayed the same; a move is looked for when stable_count >= stability_required, c - last move's c >
  * cooldown_frames and the frame's NoiseHandler state is not NOISE_ACTIVE; the rule must find exactly one legal move; it
  * is pushed and recorded, stable_count = 0, the references become THIS frame's squares (cache cleared, history kept,
- * as cbv_pipeline_update_references) and the NoiseHandler restarts.  on_move_detected is taken as always True (the
- * Lichess hook of the reference is out of scope).  The frames of a run behind an accepted move are scanned again from
- * that state inside the run, so a run of any length gives what one-frame runs driven from the host give. */
+ * as cbv_pipeline_update_references) and the NoiseHandler restarts.  on_move_detected is taken as always True unless
+ * the session is `online` (below: LichessSession's hook, turn gate and opponent moves).  The frames of a run behind an
+ * accepted move are scanned again from that state inside the run, so a run of any length gives what one-frame runs
+ * driven from the host give. */
 #define CBV_SESSION_RULE_INFER     0  /* GameSession._infer_move (game_session.py:229-265) */
 #define CBV_SESSION_RULE_OCCUPANCY 1  /* GameState.process_occupancy_change (game_state.py:40-195) */
 #define CBV_SESSION_RING 1024         /* move records kept between two cbv_pipeline_session_moves calls */
@@ -605,6 +606,8 @@ typedef struct {
     int32_t scan_period;        /* 30   full scan every scan_period-th frame (game_session.py:130) */
     int32_t max_diff;           /* 4    game_session.py:189 */
     int32_t smart_scan;         /* 1: the session owns the boards' check sets; 0: they stay the caller's */
+    int32_t online;             /* CBV_SESSION_ONLINE_*: 0 off, 1 the player is white, 2 black (rule INFER only) */
+    int32_t radar;              /* 1: every frame leaves a cbv_session_radar record (cbv_pipeline_session_radar) */
 } cbv_session_config;
 typedef struct {
     int32_t frame;      /* frames since cbv_pipeline_session_begin, 0 based */
@@ -625,6 +628,11 @@ typedef struct {
     int32_t last_move_c;        /* c of the last accepted move, 0 = none yet */
     int32_t n_moves;            /* moves accepted since begin */
     int32_t last_candidates;    /* candidates (rule 0) or status (rule 1) of the last rule call, -1 = none yet */
+    /* online sessions (all zero / none otherwise): */
+    int32_t waiting_for_opponent; /* LichessSession.waiting_for_opponent: a move the rule finds now is turned down */
+    int32_t ignored_move;       /* cbv_move of the last move turned down, CBV_MOVE_NONE = none yet */
+    int32_t ignored_frame;      /* its frame (as cbv_session_move.frame), -1 = none yet */
+    int32_t n_ignored;          /* rule calls turned down since begin (not the later identical frames the memo skips) */
 } cbv_session_state;
 /* Start a session on a board (any board handle) of a configured pipeline, from `fen` (NULL = the start position).
  * CBV_ERR_STATE before cbv_pipeline_configure or on a board that has not 64 squares, CBV_ERR_ARG for a bad FEN or
@@ -646,6 +654,69 @@ CBV_API int cbv_session_walk(const cbv_session_config* cfg, cbv_session_state* s
 CBV_API int cbv_session_state_init(cbv_session_state* state, const char* fen);
 /* the FEN of a session state (python-chess Board.fen()); returns the length */
 CBV_API int cbv_session_state_fen(const cbv_session_state* state, char* out, int cap);
+
+/* ---- online play: opponent moves, the turn gate and the radar (LichessSession, lichess_session.py) ----
+ * The network client stays with the caller; the session logic it feeds runs on the device.
+ * Turn gate (cfg.online, LichessSession.on_move_detected, lichess_session.py:44-65): waiting_for_opponent starts as
+ * "the side to move is not the player's" (is_my_turn("") for the start position).  While it is set, a move the rule
+ * finds is NOT pushed: no reference refresh, no NoiseHandler restart, stable_count stays; the move goes to ignored_move /
+ * ignored_frame, n_ignored counts the rule call, and the occupancy goes into the `rejected` memo, so the identical frames
+ * behind it do not run the rule again (they are not counted either; the reference runs and turns down the same move on
+ * each of them, which changes nothing).  An accepted own move sets waiting_for_opponent.  lichess.make_move failing is a
+ * network outcome and is taken as success.  cfg.online with CBV_SESSION_RULE_OCCUPANCY is CBV_ERR_ARG.
+ * Board events (LichessSession._sync_moves, lichess_session.py:89-117): the caller replays the game's move list into a
+ * cbv_session_pos and queues it for a frame of the session.  The event takes effect BEFORE frame `at_frame` is processed
+ * (the stream thread holds the lock between two on_frame calls), inside a run of any length and without waiting for the
+ * host: it replaces the board, recomputes `expected` and the smart mask, clears the `rejected` memo and sets
+ * waiting_for_opponent, and nothing else (stable_count, stable_occupancy, last_move_c, the detector's references, cache
+ * and history and the NoiseHandler stay, as in the reference).  The frames from at_frame on use the new smart mask.
+ * Radar (cfg.radar, GameSession._update_radar_ui, game_session.py:271-291): per frame, before its stable-move step and
+ * with the board in force at that frame (events due there applied): when expected & ~vision has exactly one member and
+ * the piece on it has the side to move's colour, `lifted` is that square and `destinations` the union of to_square over
+ * the legal moves from it; else -1 and 0.  ROI numbering, like every square set here.
+ * Out of scope: the HTTP client and its threads, make_move failures, drawing, and the radar of calibrate_sensitivity.py
+ * (ChangeDetector move candidates, not occupancy). */
+#define CBV_SESSION_ONLINE_OFF   0
+#define CBV_SESSION_ONLINE_WHITE 1
+#define CBV_SESSION_ONLINE_BLACK 2
+#define CBV_SESSION_EVENTS 64         /* board events that may wait on a board at a time */
+typedef struct {                /* the board part of cbv_session_state */
+    int8_t sq[64];
+    int32_t turn, castling, ep, halfmove, fullmove;
+} cbv_session_pos;
+typedef struct {
+    int32_t at_frame;           /* session frame (0 based since begin) in front of which the event applies */
+    int32_t waiting_for_opponent;
+    cbv_session_pos pos;
+} cbv_session_event;
+typedef struct {
+    int8_t lifted;              /* ROI index of the lifted piece, -1 = none */
+    uint64_t destinations;      /* ROI-numbered set of its legal destinations */
+} cbv_session_radar;
+/* `moves`: UCI tokens separated by blanks (NULL or "" = none), replayed from the start position as _sync_moves does:
+ * a token that is not a legal move there is skipped.  *pushed (may be NULL) = tokens played.  0, or CBV_ERR_ARG. */
+CBV_API int cbv_session_pos_from_moves(const char* moves, cbv_session_pos* out, int* pushed);
+/* Queue a board event on a board with a session.  CBV_ERR_ARG when at_frame lies below the frames already enqueued for
+ * the session (runs in flight included) or below the last queued event's at_frame; CBV_ERR_UNSUPPORTED when
+ * CBV_SESSION_EVENTS events are waiting; nothing changes in either case.  Does not wait for the runs in flight.  An
+ * event whose frame no run reaches before cbv_pipeline_session_end (or a new begin) is dropped. */
+CBV_API int cbv_pipeline_session_sync(cbv_pipeline* board, int at_frame, const cbv_session_pos* pos, int waiting_for_opponent);
+/* *frames = the frames enqueued for the board's session so far = the session frame index of the next run's first frame
+ * (does not wait for the runs in flight) */
+CBV_API int cbv_pipeline_session_frames(cbv_pipeline* board, int* frames);
+/* the radar records of processed slots (cfg.radar; CBV_ERR_STATE without) */
+CBV_API int cbv_pipeline_session_radar(cbv_pipeline* board, int slot0, int n, cbv_session_radar* out);
+/* cbv_session_walk with board events and the radar, host buffers: `events` (non-decreasing at_frame, none below
+ * state->c, at most CBV_SESSION_EVENTS) apply in front of the frame whose index (state->c before it) they name;
+ * *events_used = how many applied among the frames consumed; `radar` (may be NULL) gets one record per frame consumed.
+ * Returns the frames consumed like cbv_session_walk; CBV_ERR_ARG / CBV_ERR_UNSUPPORTED as cbv_pipeline_session_sync and
+ * cbv_pipeline_session_begin give them, and then nothing has changed. */
+CBV_API int cbv_session_walk_events(const cbv_session_config* cfg, cbv_session_state* state, const cbv_frame_result* results,
+                                    const cbv_noise_result* noise, int n, const cbv_session_event* events, int n_events,
+                                    int* events_used, cbv_session_radar* radar, cbv_session_move* move, int* accepted);
+/* cbv_session_state_init for a session with `cfg` (waiting_for_opponent from cfg->online and the side to move) */
+CBV_API int cbv_session_state_init_cfg(cbv_session_state* state, const cbv_session_config* cfg, const char* fen);
+
 /* The device's wave-parallel legal move generator on one position, for tests: list(board.legal_moves) of `fen` in
  * python-chess order; *n = count. */
 CBV_API int cbv_session_device_legal_moves(cbv_ctx* ctx, const char* fen, uint16_t* out, int cap, int* n);

@@ -1,7 +1,11 @@
 """Frames/s of the game session on the device (BoardPipeline.session_begin) at 1080p, enhance=False, device-resident
 frames, 128-frame runs, against the same runs without a session (the cost of the extra rounds and history records) and
 against the alternative the session replaces: one frame per run plus the host logic.  Also the time of a round that exits
-at once, the time per legal-move-generator call and the cost of sessions on a four-board pipeline.
+at once, the time per legal-move-generator call and the cost of sessions on a four-board pipeline.  And online play
+(session_begin(online=...), Session.sync_moves): the 270-frame 640x480 scene of tests/test_gpu_session.py as one run, as white
+with one board event per black ply, with and without the radar, against the same run with the session offline; the time
+of k_session_event (60 more events queued on the frame of one that is there anyway: no further segment), the extra scan
+rounds per event (SCAN launch counter, the event kernels taken off) and the radar's time per frame.
 
     python tools/session_moves_timing.py [--frames 512] [--reps 5]
 
@@ -34,6 +38,54 @@ def timed(fn, reps):
         fn()
         out.append(time.perf_counter() - t)
     return statistics.median(out)
+
+
+def online_leg(ctx, reps):
+    w, h, fpp, nfr = 640, 480, 30, 270
+    q = BoardPipeline(w, h, nfr)
+    q.configure(S.scaled_corners(w, h), enhance=False)
+    q.synth(0, nfr, scene="normal", frames_per_ply=fpp)
+    uci = ["".join(S.SCRIPT[k][0]) for k in range(8)]
+    events = [(ply * fpp + 12, " ".join(uci[:ply])) for ply in (2, 4, 6, 8)]
+    info = {}
+
+    def leg(name, online, radar, extra=0):
+        def once(count=False):
+            q.reset_state()
+            ses = q.session_begin(rule="session", cooldown_frames=10, online="white" if online else None, radar=radar)
+            if online:
+                for k, (at, ms) in enumerate(events):
+                    for _ in range(1 + (extra if k == 0 else 0)):
+                        ses.sync_moves(ms, at_frame=at)
+            ctx.synchronize()
+            if count:
+                ctx.profile_reset()
+                ctx.profile_enable(-1)
+            t = time.perf_counter()
+            q.run(0, nfr)
+            ctx.synchronize()
+            dt = time.perf_counter() - t
+            if count:
+                info[name] = dict(scan_launches=ctx.profile_read(N.K_ALL["SCAN"])[1], moves=len(ses.moves()), ignored=ses.state().n_ignored)
+                ctx.profile_enable(-2)
+                ctx.profile_reset()
+            ses.end()
+            return dt
+        once(True)
+        once()
+        return statistics.median(once() for _ in range(reps))
+
+    t_off = leg("offline", False, False)
+    t_off_radar = leg("offline_radar", False, True)
+    t_on = leg("online", True, False)
+    t_on_radar = leg("online_radar", True, True)
+    t_on_60 = leg("online_60_more_events", True, False, extra=60)
+    q.close()
+    ne = len(events)
+    return {"online_frames": nfr, "online_events": ne, "ms_offline": t_off * 1e3, "ms_offline_radar": t_off_radar * 1e3, "ms_online": t_on * 1e3,
+            "ms_online_radar": t_on_radar * 1e3, "event_kernel_us": (t_on_60 - t_on) / 60 * 1e6,
+            "extra_scan_rounds_per_event": (info["online"]["scan_launches"] - ne - info["offline"]["scan_launches"]) / ne,
+            "radar_us_per_frame": (t_off_radar - t_off) / nfr * 1e6, "radar_us_per_frame_online": (t_on_radar - t_on) / nfr * 1e6, "online_info": info}
 
 
 def main():
@@ -131,7 +183,8 @@ def main():
         ctx.check(ctx.lib.cbv_session_generator_time(ctx.h, fen, 1, C.byref(ms1)))
         ctx.check(ctx.lib.cbv_session_generator_time(ctx.h, fen, 1001, C.byref(ms2)))
     chess._L()
-    print(json.dumps({"frames": n, "run": RUN, "fps_no_session": n / plain, "fps_session": n / on, "session_moves_first_pass": moves,
+    online = online_leg(ctx, a.reps)
+    print(json.dumps({**online, "frames": n, "run": RUN, "fps_no_session": n / plain, "fps_session": n / on, "session_moves_first_pass": moves,
                       "fps_one_frame_runs_host_logic": n / host, "idle_round_us": idle_round_us,
                       "fps_4_boards_no_session": n / mb_plain, "fps_4_boards_one_session": n / mb_one, "fps_4_boards_four_sessions": n / mb_all,
                       "generator_call_us": (ms2.value - ms1.value) / 1000 * 1e3}))
