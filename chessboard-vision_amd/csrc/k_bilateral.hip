@@ -30,8 +30,20 @@
 //   - taps are accumulated per output in row-major (dy, dx) order exactly like
 //     OpenCV's FMA3-dispatched body: w = space * colour (one rounding, here done
 //     when the table is built), sum = fma(px, w, sum), wsum += w: bit-equal to
-//     the oracle.
+//     the oracle;
+//   - PAIRS (the batched 768-lane form at d = 9; build with BL_NO_PAIRS=1 for the form without it): w(p -> q) and
+//     w(q -> p) are the same table entry (the class depends on dx^2 + dy^2 only, the SAD is symmetric), so a weight
+//     that connects two of a lane's OWN eight outputs is looked up once, by the output whose accumulation order
+//     meets it first, and stays in a register for the other: 6 pairs on each of the two output rows and 16 between
+//     them, 28 of the lane's 392 sad + shift + gather triples (7.1 %), with no LDS traffic, no barrier and no halo
+//     lanes.  The two tile rows that carry these taps are straight-line code that walks the row's pixels in the outer
+//     loop (a pixel's three floats die early, which pays for the 22 weight registers): 119 VGPRs, no scratch, the LDS
+//     size and the tiling are unchanged.  Sharing across lanes (a stash in LDS that a wave fills walking down a band)
+//     would reach half of all lookups, but a weight that crosses dy rows lives dy row steps: 40 dwords per pixel
+//     column, 160 B x 3072 columns = 480 KB for a 768-lane workgroup.  It does not fit at any tiling that keeps the
+//     lanes busy.
 #include "cbv_device.h"
+#include <type_traits>
 
 #define BL_TW 128        // tile width in pixels (32 strips of 4)
 #define BL_HALO 4        // halo in pixels (radius <= 4; 4 keeps ds_read_b128 aligned)
@@ -46,7 +58,8 @@ __host__ __device__ constexpr int bl_row_reach(int R, int dy)
 }
 
 // NT lanes per workgroup (a multiple of 64): 32 strips x NT / 32 row pairs, i.e. tiles of 128 x NT / 16 pixels
-template <int R, int NT>
+// PAIRS: the lane's eight outputs share the tap weights that connect two of them (see the header comment)
+template <int R, int NT, bool PAIRS = false>
 __global__ __launch_bounds__(NT) void k_bilateral(const u8* __restrict__ src, u8* __restrict__ dst, Geom g,
                                                            const BilateralTabs* __restrict__ bt, TileSet ts, int batch,
                                                            SatGate gate)
@@ -189,8 +202,8 @@ __global__ __launch_bounds__(NT) void k_bilateral(const u8* __restrict__ src, u8
         // live registers).  Tile row ly + i is tap row dy = i - R of output row a and dy = i - 1 - R of
         // output row b; every output still sees its taps in ascending (dy, dx) order.
         const u32* rowp0 = &tile[ly * BL_PITCH + sx * 4];
-#pragma unroll 1
-        for (int i = 0; i <= 2 * R + 1; i++) {
+        // One tile row: looks up, for both output rows, the weight of every tap on it and accumulates.
+        auto tile_row = [&](const int i) __attribute__((always_inline)) {
             const uint4* rowp = (const uint4*)(rowp0 + i * BL_PITCH);
             const uint4 q0 = rowp[0], q1 = rowp[1], q2 = rowp[2];
             // table offsets of this row's taps for both output rows: wave-uniform scalar loads (-1 = outside the disc)
@@ -236,6 +249,66 @@ __global__ __launch_bounds__(NT) void k_bilateral(const u8* __restrict__ src, u8
                     }
                 }
             }
+        };
+        // PAIRS: the lane's two OWN tile rows, ly + R (OWN = 0: output row a's dy = 0, row b's dy = -1) and ly + R + 1
+        // (OWN = 1: row a's dy = +1, row b's dy = 0).  A tap of one of the lane's outputs that is another of its outputs
+        // has the same weight in both directions (the class depends on dx^2 + dy^2 only, the SAD is symmetric), so only
+        // the output that needs it FIRST looks it up and leaves it in a register for the other:
+        //   wh[lo][hi]: pixels lo < hi of one output row; hi takes it at dx = lo - hi, lo at dx = hi - lo, later on the row;
+        //   wv[ob][oa]: pixel ob of row b and pixel oa of row a; row b takes it at dy = -1, row a at dy = +1, one row later.
+        // The disc's extent on these rows is known when compiling, so they are straight-line code, and it walks the
+        // row's 12 pixels in the OUTER loop: every output still meets its taps in ascending dx (its accumulation
+        // order, the only order that fixes the result), and a pixel's three floats die before the next one's are made,
+        // which pays for the 22 registers of wh and wv.
+        float wh[4][4], wv[4][4];
+        auto own_row = [&](auto own) __attribute__((always_inline)) {
+            constexpr int OWN = decltype(own)::value;
+            const uint4* rowp = (const uint4*)(rowp0 + (R + OWN) * BL_PITCH);
+            const uint4 q0 = rowp[0], q1 = rowp[1], q2 = rowp[2];
+            const u32 p[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                const float fb = (float)(p[j] & 255u), fg = (float)((p[j] >> 8) & 255u), fr = (float)((p[j] >> 16) & 255u);
+#pragma unroll
+                for (int a = 0; a < 2; a++) {
+                    constexpr int NODY = 0;
+                    const int dy = a == OWN ? NODY : (OWN == 0 ? -1 : 1); // of output row a on this tile row
+#pragma unroll
+                    for (int o = 0; o < 4; o++) {
+                        const int dx = j - 4 - o, po = j - 4; // po: the tap's index in the lane's strip, if 0 .. 3
+                        if ((dx < 0 ? -dx : dx) > bl_row_reach(R, dy < 0 ? -dy : dy)) continue; // outside the disc
+                        const bool mine = po >= 0 && po < 4 && (dx != 0 || dy != 0);
+                        float wgt;
+                        if (mine && dy == 0 && dx > 0)
+                            wgt = wh[o][po];
+                        else if (mine && dy > 0)
+                            wgt = wv[po][o];
+                        else {
+                            const u32 idx = __builtin_amdgcn_sad_u8(p[j], ctr[a][o], (u32)bt->tap_off[dy + R][dx + R]);
+                            wgt = *(const float*)((const u8*)fw + (idx << 2));
+                            if (mine && dy == 0) wh[po][o] = wgt;
+                            if (mine && dy < 0) wv[o][po] = wgt;
+                        }
+                        sb[a][o] = __fmaf_rn(fb, wgt, sb[a][o]);
+                        sg[a][o] = __fmaf_rn(fg, wgt, sg[a][o]);
+                        sr[a][o] = __fmaf_rn(fr, wgt, sr[a][o]);
+                        sw[a][o] = sw[a][o] + wgt;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0); // keeps hipcc from converting all 12 pixels ahead (144 registers)
+            }
+        };
+        if (PAIRS) {
+            // three pieces, not one loop with a special case: wh and wv must not become loop-carried registers
+#pragma unroll 1
+            for (int i = 0; i < R; i++) tile_row(i);
+            own_row(std::integral_constant<int, 0>());
+            own_row(std::integral_constant<int, 1>());
+#pragma unroll 1
+            for (int i = R + 2; i <= 2 * R + 1; i++) tile_row(i);
+        } else {
+#pragma unroll 1
+            for (int i = 0; i <= 2 * R + 1; i++) tile_row(i);
         }
         const int f = here.f;
         const int x = here.px0 + sx * 4;
@@ -303,7 +376,7 @@ PxRect bilateral_region_cover(cbv_ctx* ctx, Geom g, int batch, PxRect need)
     return c;
 }
 
-template <int R, int NT>
+template <int R, int NT, bool PAIRS = false>
 static int launch_bilateral_r(cbv_ctx* ctx, const u8* src, u8* dst, Geom g, int batch, int wgs_per_cu, const EnhanceRegion* er)
 {
     const TileSet ts = bilateral_tiles(g, NT, er);
@@ -314,7 +387,7 @@ static int launch_bilateral_r(cbv_ctx* ctx, const u8* src, u8* dst, Geom g, int 
     if (grid > ntiles) grid = ntiles;
     const SatGate gate = er ? er->gate : SatGate{nullptr, 0};
     prof_begin(ctx, CBV_K_BILATERAL);
-    hipLaunchKernelGGL((k_bilateral<R, NT>), dim3((unsigned)grid), dim3(NT), 0, ctx->stream, src, dst, g, ctx->btabs, ts, batch, gate);
+    hipLaunchKernelGGL((k_bilateral<R, NT, PAIRS>), dim3((unsigned)grid), dim3(NT), 0, ctx->stream, src, dst, g, ctx->btabs, ts, batch, gate);
     prof_end(ctx, CBV_K_BILATERAL);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
@@ -334,6 +407,10 @@ int launch_bilateral(cbv_ctx* ctx, const u8* src, u8* dst, Geom g, int batch, co
     case 1: return launch_bilateral_r<1, 768>(ctx, src, dst, g, batch, 1, er);
     case 2: return launch_bilateral_r<2, 768>(ctx, src, dst, g, batch, 1, er);
     case 3: return launch_bilateral_r<3, 768>(ctx, src, dst, g, batch, 1, er);
-    default: return launch_bilateral_r<4, 768>(ctx, src, dst, g, batch, 1, er);
+#ifdef BL_NO_PAIRS
+    default: return launch_bilateral_r<4, 768>(ctx, src, dst, g, batch, 1, er); // the batched form without weight sharing, for A/B runs
+#else
+    default: return launch_bilateral_r<4, 768, true>(ctx, src, dst, g, batch, 1, er);
+#endif
     }
 }
