@@ -220,7 +220,9 @@ K = {name: i for i, name in enumerate(KERNEL_IDS)}
 K["MODEL_SCAN"] = len(KERNEL_IDS)
 # ... and k_warp_yuv (pipelines without enhancement on raw frames) follows those, under a name of its own
 K_WARP_YUV = K["MODEL_SCAN"] + 1
-K_ALL = dict(K, WARP_YUV=K_WARP_YUV)  # every id by name (K itself stays as tests/test_model_update_host.py pins it)
+# ... and k_change_blur_stats (boards whose ChangeDetector has a blur kernel of its own, set_change_blur) follows that
+K_CHANGE_BLUR = K_WARP_YUV + 1
+K_ALL = dict(K, WARP_YUV=K_WARP_YUV, CHANGE_BLUR=K_CHANGE_BLUR)  # every id by name (K itself stays as tests/test_model_update_host.py pins it)
 
 MODEL_FROZEN, MODEL_EVERY, MODEL_UNCHANGED = 0, 1, 2
 MODEL_MODES = {"frozen": MODEL_FROZEN, "every": MODEL_EVERY, "unchanged": MODEL_UNCHANGED}
@@ -312,6 +314,7 @@ def load():
         "cbv_pipeline_set_input_format": (i32, [vp, i32]),
         "cbv_pipeline_host_slot_bytes": (C.c_size_t, [vp]),
         "cbv_pipeline_set_model_update": (i32, [vp, i32, dbl]),
+        "cbv_pipeline_set_change_blur": (i32, [vp, i32]),
         "cbv_pipeline_model": (i32, [vp, i32, i32, vp]),
         "cbv_pipeline_session_begin": (i32, [vp, P(SessionConfig), C.c_char_p]),
         "cbv_pipeline_session_end": (i32, [vp]),

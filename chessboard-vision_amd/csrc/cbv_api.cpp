@@ -77,10 +77,10 @@ void dev_free(DevBuf* b)
 // ---------------------------------------------------------------------------
 // profiling
 // ---------------------------------------------------------------------------
-static const char* kKernelNames[CBV_K_COUNT] = {
+static const char* kKernelNames[CBV_K_END] = {
     "k_color_lab_hist", "k_clahe_lut", "k_clahe_apply", "k_bilateral", "k_sharpen", "k_norm_lut", "k_normalize",
     "k_warp", "k_squares", "k_gray_blur_hist", "k_otsu", "k_threshold", "k_scan", "k_synth", "k_reset_aux", "k_hough", "k_ingest", "k_model_scan",
-    "k_warp_yuv"};
+    "k_warp_yuv", "k_change_blur_stats"};
 
 static hipEvent_t prof_get_event(cbv_ctx* ctx)
 {
@@ -137,7 +137,7 @@ extern "C" int cbv_profile_enable(cbv_ctx* ctx, int kid)
 
 extern "C" int cbv_profile_read(cbv_ctx* ctx, int kid, double* total_ms, long long* launches)
 {
-    if (!ctx || kid < 0 || kid >= CBV_K_COUNT) return CBV_ERR_ARG;
+    if (!ctx || kid < 0 || kid >= CBV_K_END) return CBV_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     prof_drain(ctx);
     if (total_ms) *total_ms = ctx->prof_ms[kid];
@@ -150,14 +150,14 @@ extern "C" int cbv_profile_reset(cbv_ctx* ctx)
     if (!ctx) return CBV_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     prof_drain(ctx);
-    for (int i = 0; i < CBV_K_COUNT; i++) {
+    for (int i = 0; i < CBV_K_END; i++) {
         ctx->prof_ms[i] = 0;
         ctx->prof_n[i] = 0;
     }
     return CBV_OK;
 }
 
-extern "C" const char* cbv_kernel_name(int kid) { return (kid >= 0 && kid < CBV_K_COUNT) ? kKernelNames[kid] : ""; }
+extern "C" const char* cbv_kernel_name(int kid) { return (kid >= 0 && kid < CBV_K_END) ? kKernelNames[kid] : ""; }
 
 // ---------------------------------------------------------------------------
 // context

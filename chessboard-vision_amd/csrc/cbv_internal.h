@@ -109,8 +109,8 @@ struct cbv_ctx {
     int prof_kid = -2;
     std::vector<ProfSlot> prof_pending;
     std::vector<hipEvent_t> prof_pool;
-    double prof_ms[CBV_K_COUNT] = {0};
-    long long prof_n[CBV_K_COUNT] = {0};
+    double prof_ms[CBV_K_END] = {0};
+    long long prof_n[CBV_K_END] = {0};
 
     // One context = one queue of work: its scratch buffers and `stream` are shared by every object created on it, and
     // cbv_pipeline_run points `stream` at its lanes while it enqueues.  Entry points that touch the GPU hold this lock
@@ -509,6 +509,14 @@ struct ModelScan {
 int launch_model_scan(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, ModelScan ms,
                       cbv_sq_stats* stats, u8* decisions, int count, int max_px);
 
+// The ChangeDetector stage's own blur (cbv_pipeline_set_change_blur): ChangeDetector._preprocess with a kernel other than the
+// PieceDetector's 5 x 5.  cf[j] = the 8.8 fixed-point coefficient (build_gaussian_q8) j taps from the centre: the kernel is
+// symmetric, k = 31 has 16 distinct ones.
+struct ChangeBlur {
+    int k; // odd, 1..31; 5 = the board reads the PieceDetector's planes and k_change_blur_stats does not run for it
+    u32 cf[16];
+};
+
 #define MB_BOARD_SHIFT 29 // work item = board << 29 | frame << 8 | square: frames of a list < 2^21
 struct BoardDev {
     // warp
@@ -545,6 +553,13 @@ struct BoardDev {
     u32* over_dst;               // its pinned copy
     // per-frame background model update (cbv_pipeline_set_model_update): k_model_scan's arguments
     ModelScan ms;
+    // the ChangeDetector planes (k_change_blur_stats writes them, calibrate and k_model_scan read them): `gray` itself
+    // while cb.k == 5; cmean / csd = the model for the z-score statistics of a frozen, calibrated board with cb.k != 5
+    // (`mean` / `sd` are null for such a board: k_squares_pre5_stats leaves the z statistics to k_change_blur_stats)
+    u8* cgray;
+    const float* cmean;
+    const float* csd;
+    ChangeBlur cb;
 };
 ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
 // per-pass HoughCfg of a board (layout and maxc as launch_hough / launch_hough_second set them); returns the LDS bytes
@@ -560,6 +575,12 @@ int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32
                     int retry_frame_base, int pass);
 int launch_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int mirrored);
 int launch_model_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int max_px);
+// ChangeDetector._preprocess with the board's own kernel on `batch` warped frames, and (mean != null) the z-score fields of
+// the records and the class bits of the decision bytes k_squares_pre5_stats wrote before it on the same stream
+int launch_change_blur_stats(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n, u8* plane,
+                             size_t plane_frame_stride, const float* mean, const float* sd, float z_thresh, cbv_sq_stats* stats,
+                             int batch, u8* decisions, const ChangeBlur& cb, int max_px);
+int launch_change_blur_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int max_px);
 
 // ---------------------------------------------------------------------------
 // Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline.cpp) shares

@@ -28,6 +28,14 @@ struct Board {
     bool calibrated = false, has_check = false; // has_check: squares_to_check masks were set
     int model_mode = CBV_MODEL_FROZEN;          // cbv_pipeline_set_model_update
     double model_alpha = 0.1;
+    // cbv_pipeline_set_change_blur: ChangeDetector.blur_kernel.  With 5 the ChangeDetector stage reads d_gray, the
+    // PieceDetector's planes, as it always did; otherwise d_cgray holds its own planes, [max_frames][plane_total], written by
+    // k_change_blur_stats.  slot_blur = the kernel each slot was last run with (0: never run).
+    int change_k = 5;
+    DevBuf d_cgray;
+    std::vector<u8> slot_blur;
+    bool own_blur() const { return change_k != 5; }
+    u8* change_planes() const { return (u8*)(own_blur() ? d_cgray.p : d_gray.p); }
     // game session (cbv_pipeline_session_begin): the device state, the per-frame history records of the scan and how many
     // of the session's move records the host has handed out
     bool session = false;
@@ -123,6 +131,7 @@ struct Pipe {
     bool any_hough = false;
     bool any_adaptive = false; // some board's model follows the frames: k_model_scan runs in front of the temporal scan
     bool any_session = false;  // some board runs a game session: the boards' scans are launched board by board
+    bool any_own_blur = false; // some board's ChangeDetector has a blur kernel of its own: k_change_blur_stats runs behind the statistics
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
     Board& b0() const { return boards[0]->b; }
@@ -184,6 +193,18 @@ static int join_slots(Pipe& P, int s0, int cnt)
     return CBV_OK;
 }
 
+// kernel arguments of k_change_blur_stats for an odd k in 1..31: the centre tap and the taps on one side of it
+static ChangeBlur change_blur_coef(int k)
+{
+    ChangeBlur cb;
+    memset(&cb, 0, sizeof(cb));
+    int coef[32];
+    build_gaussian_q8(k, coef);
+    cb.k = k;
+    for (int j = 0; j <= k / 2; j++) cb.cf[j] = (u32)coef[k / 2 + j];
+    return cb;
+}
+
 // the kernel arguments of a board: its BoardDev entry, pointers of slot 0 (the launches add their first slot); lds = LDS
 // bytes of its HoughCircles passes (0: the squares do not fit)
 static BoardDev board_dev(const Board& q, size_t lds[2])
@@ -210,9 +231,14 @@ static BoardDev board_dev(const Board& q, size_t lds[2])
     T.plane_total = q.plane_total;
     // A board whose model follows the frames gets its z-score statistics from k_model_scan, frame after frame on the scan
     // stream: the statistics kernel of the lanes must not read the model, which the scan of the run before may still write
+    // ... and neither does it for a board with a blur kernel of its own: k_change_blur_stats makes those planes and statistics
     const bool frozen = q.calibrated && !q.adaptive();
-    T.mean = frozen ? (const float*)q.d_mean.p : nullptr;
-    T.sd = frozen ? (const float*)q.d_var.p + q.plane_total : nullptr;
+    T.mean = frozen && !q.own_blur() ? (const float*)q.d_mean.p : nullptr;
+    T.sd = frozen && !q.own_blur() ? (const float*)q.d_var.p + q.plane_total : nullptr;
+    T.cgray = q.change_planes();
+    T.cmean = frozen && q.own_blur() ? (const float*)q.d_mean.p : nullptr;
+    T.csd = frozen && q.own_blur() ? (const float*)q.d_var.p + q.plane_total : nullptr;
+    T.cb = change_blur_coef(q.change_k);
     T.ms.mode = q.adaptive() ? q.model_mode : CBV_MODEL_FROZEN;
     // (1 - self.alpha) and self.alpha are python doubles turned float32 by numpy (launch_squares_ema)
     T.ms.one_minus = (float)(1.0 - q.model_alpha);
@@ -242,7 +268,7 @@ static BoardDev board_dev(const Board& q, size_t lds[2])
 }
 
 // Rebuild the boards' kernel arguments whenever a board is set up, attached, detached or calibrated, or its model-update
-// mode changes.  The device table
+// mode or its ChangeDetector blur kernel changes.  The device table
 // and the maxima of the multi-board launches exist only with boards attached.  Nothing may be in flight: the callers
 // joined the runs.
 static int pipeline_tables(Pipe& P)
@@ -250,7 +276,7 @@ static int pipeline_tables(Pipe& P)
     cbv_ctx* ctx = P.ctx;
     const int nb = (int)P.boards.size();
     P.tab.resize(nb);
-    P.any_hough = P.any_adaptive = P.any_session = false;
+    P.any_hough = P.any_adaptive = P.any_session = P.any_own_blur = false;
     P.hough_lds[0] = P.hough_lds[1] = 0;
     P.max_px = P.max_S = 0;
     for (int k = 0; k < nb; k++) {
@@ -268,6 +294,7 @@ static int pipeline_tables(Pipe& P)
         }
         P.any_adaptive = P.any_adaptive || q.adaptive();
         P.any_session = P.any_session || q.session;
+        P.any_own_blur = P.any_own_blur || q.own_blur();
         P.max_px = std::max(P.max_px, q.max_px);
         P.max_S = std::max(P.max_S, q.cfg.board_size);
     }
@@ -347,6 +374,11 @@ static int board_setup(const Pipe& P, Board& b, const cbv_pipeline_config& cfg)
     RC(dev_ensure(ctx, &b.d_descs, sizeof(SquareDesc) * n));
     RC(dev_ensure(ctx, &b.d_masks, off));
     RC(dev_ensure(ctx, &b.d_gray, off * P.max_frames));
+    if (b.own_blur()) { // a kernel set before this configuration
+        RC(dev_ensure(ctx, &b.d_cgray, off * P.max_frames));
+        CBV_HIP(ctx, hipMemset(b.d_cgray.p, 0, off * P.max_frames));
+    }
+    b.slot_blur.assign((size_t)P.max_frames, 0);
     RC(dev_ensure(ctx, &b.d_stats, sizeof(cbv_sq_stats) * n * P.max_frames));
     RC(dev_ensure(ctx, &b.d_ref, off));
     RC(dev_ensure(ctx, &b.d_mean, off * 4));
@@ -391,7 +423,8 @@ static void board_free(cbv_pipeline* p)
     if (b.h_stage) (void)hipHostFree(b.h_stage);
     if (b.warped) (void)hipFree(b.warped);
     DevBuf* bufs[] = {&b.d_descs, &b.d_masks, &b.d_gray, &b.d_stats, &b.d_ref, &b.d_state, &b.d_results, &b.d_flags, &b.d_dec, &b.d_mean,
-                      &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over, &b.d_session, &b.d_hist, &b.d_radar};
+                      &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over, &b.d_session, &b.d_hist, &b.d_radar,
+                      &b.d_cgray};
     for (auto d : bufs) dev_free(d);
     delete p;
 }
@@ -607,8 +640,11 @@ extern "C" int cbv_pipeline_calibrate(cbv_pipeline* p, int slot)
     cbv_ctx* ctx = P.ctx;
     if (slot < 0 || slot >= P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_calibrate: bad slot");
     CBV_ENTER(ctx);
+    if (B.slot_blur[slot] && B.slot_blur[slot] != B.change_k)
+        return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_calibrate: slot %d was last run with blur kernel %d, the board's is %d now (run the slot again)",
+                        slot, (int)B.slot_blur[slot], B.change_k);
     RC(join_scan(P)); // lanes and scan of the last run
-    RC(launch_squares_calibrate(ctx, (const SquareDesc*)B.d_descs.p, B.cfg.n_rois, (const u8*)B.d_gray.p + B.plane_total * slot,
+    RC(launch_squares_calibrate(ctx, (const SquareDesc*)B.d_descs.p, B.cfg.n_rois, B.change_planes() + B.plane_total * slot,
                                 (float*)B.d_mean.p, (float*)B.d_var.p, (float*)B.d_var.p + B.plane_total, (float)B.cfg.initial_variance, nullptr));
     B.calibrated = true;
     return pipeline_tables(P); // the board's statistics read its model from now on
@@ -630,6 +666,26 @@ extern "C" int cbv_pipeline_set_model_update(cbv_pipeline* p, int mode, double a
     RC(join_scan(P));
     B.model_mode = mode;
     B.model_alpha = alpha;
+    return P.configured ? pipeline_tables(P) : CBV_OK;
+}
+
+extern "C" int cbv_pipeline_set_change_blur(cbv_pipeline* p, int blur_kernel)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_pipeline_set_change_blur: the board is null");
+    Pipe& P = *p->pipe;
+    Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    const int k = std::max(blur_kernel, 1) | 1; // calibrate_sensitivity.py:139
+    if (k > 31) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "cbv_pipeline_set_change_blur: blur kernel %d too large (max 31)", k);
+    // (REFLECT_101 folds as often as it takes, d_reflect101: every kernel fits every square)
+    CBV_ENTER(ctx);
+    if (B.change_k == k) return CBV_OK;
+    RC(join_scan(P)); // the runs in flight keep their arguments; the tables are rebuilt behind them
+    if (k != 5 && P.configured) { // the board's own plane ring (kept from an earlier kernel other than 5)
+        RC(dev_ensure(ctx, &B.d_cgray, B.plane_total * P.max_frames));
+        if (!B.own_blur()) CBV_HIP(ctx, hipMemsetAsync(B.d_cgray.p, 0, B.plane_total * P.max_frames, ctx->stream));
+    }
+    B.change_k = k;
     return P.configured ? pipeline_tables(P) : CBV_OK;
 }
 
@@ -897,6 +953,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
         if (raw0) RC(launch_warp_yuv_mb(ctx, raw0, raw1, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
         else RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
+        if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, s0, b, P.max_px));
         if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, P.hough_lds[0], retry, retry_base, 0));
         return CBV_OK;
     }
@@ -909,6 +966,9 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     else RC(launch_warp(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, norm, b, work, retry0));
     RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
                                  T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));
+    if (P.any_own_blur)
+        RC(launch_change_blur_stats(ctx, wdst, T.warped_stride, T.descs, T.n, T.cgray + T.plane_total * s0, T.plane_total, T.cmean, T.csd,
+                                    T.z_thresh, T.stats + (size_t)T.n * s0, b, dec, T.cb, P.b0().max_px));
     if (T.want_hough) RC(launch_hough(ctx, T.descs, T.n, gray, T.plane_total, P.b0().hough_cfg, hres, dec, work, b, retry, retry_base));
     return CBV_OK;
 }
@@ -931,7 +991,8 @@ static int board_scan(Pipe& P, Board& q, const BoardDev& T, int slot0, int count
         RC(launch_hough_second(ctx, T.descs, T.n, gray, T.plane_total, q.hough_cfg, T.hough + (size_t)CBV_MAX_SQUARES * slot0, dec,
                                retry, T.n * count));
     if (with_pre && q.adaptive())
-        RC(launch_model_scan(ctx, T.descs, T.n, gray, T.plane_total, T.ms, T.stats + (size_t)T.n * slot0, dec, count, q.max_px));
+        RC(launch_model_scan(ctx, T.descs, T.n, T.cgray + T.plane_total * slot0, T.plane_total, T.ms, T.stats + (size_t)T.n * slot0, dec, count,
+                             q.max_px));
     ResultMirror mir;
     if (mirrored) {
         mir.records = T.mirror + slot0;
@@ -1039,7 +1100,8 @@ static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, b
                                    (const u32*)rec->retry.p, T.n * count));
         // the z-score statistics and the model update of a board whose model follows the frames, before the scan reads the classes
         if (P.any_adaptive)
-            RC(launch_model_scan(ctx, T.descs, T.n, gray, T.plane_total, T.ms, T.stats + (size_t)T.n * slot0, dec, count, P.b0().max_px));
+            RC(launch_model_scan(ctx, T.descs, T.n, T.cgray + T.plane_total * slot0, T.plane_total, T.ms, T.stats + (size_t)T.n * slot0, dec, count,
+                                 P.b0().max_px));
         ResultMirror mir;
         if (mirrored) {
             mir.records = T.mirror + slot0;
@@ -1052,6 +1114,7 @@ static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, b
     }
     CBV_HIP(ctx, hipEventRecord(rec->scan_ev, scan_on));
     mark_mirrored(P, slot0, count, mirrored);
+    for (cbv_pipeline* q : P.boards) std::fill(q->b.slot_blur.begin() + slot0, q->b.slot_blur.begin() + slot0 + count, (u8)q->b.change_k);
     rec->s0 = slot0;
     rec->cnt = count;
     rec->seq = ++P.run_seq;

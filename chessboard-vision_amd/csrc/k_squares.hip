@@ -333,6 +333,47 @@ __global__ __launch_bounds__(256) void k_squares_stats(const SquareDesc* __restr
     sq_accum_finish(A, acc, zm, nanf_, n, mean != nullptr, out, nsq, decisions, want_hough, hough_work, hough_out, descs[blockIdx.x].cnt, dm);
 }
 
+// BGR2GRAY of a square's ROI into LDS (u8, rows packed) by NT lanes: four pixels (12 bytes, any alignment) per lane and load
+// instruction, four tasks a lane per round with all their loads issued before the first result is stored
+// (k_squares_preprocess5 explains both)
+template <int NT>
+__device__ __forceinline__ void stage_gray_bgr(const u8* __restrict__ s, const SquareDesc& d, u8* g)
+{
+    const int w = d.w, h = d.h;
+    const int ngx = (w + 3) >> 2, ntask = ngx * h;
+    for (int t0 = threadIdx.x; t0 < ntask; t0 += 4 * NT) {
+        u32 v[4][3];
+        int yy[4], xx[4];
+        bool full[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int t = t0 + q * NT;
+            full[q] = false;
+            if (t < ntask) {
+                yy[q] = t / ngx;
+                xx[q] = (t - yy[q] * ngx) << 2;
+                full[q] = xx[q] + 3 < w;
+                if (full[q]) __builtin_memcpy(v[q], s + (size_t)yy[q] * d.stride + 3 * xx[q], 12);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int t = t0 + q * NT;
+            if (t >= ntask) continue;
+            u8* o = g + yy[q] * w + xx[q];
+            if (full[q]) {
+                o[0] = (u8)d_gray(v[q][0] & 255, (v[q][0] >> 8) & 255, (v[q][0] >> 16) & 255);
+                o[1] = (u8)d_gray(v[q][0] >> 24, v[q][1] & 255, (v[q][1] >> 8) & 255);
+                o[2] = (u8)d_gray((v[q][1] >> 16) & 255, v[q][1] >> 24, v[q][2] & 255);
+                o[3] = (u8)d_gray((v[q][2] >> 8) & 255, (v[q][2] >> 16) & 255, v[q][2] >> 24);
+            } else {
+                const u8* p = s + (size_t)yy[q] * d.stride + 3 * xx[q];
+                for (int k = 0; xx[q] + k < w; k++) o[k] = (u8)d_gray(p[3 * k], p[3 * k + 1], p[3 * k + 2]);
+            }
+        }
+    }
+}
+
 // preprocess (k = 5) and statistics of the pipeline in one pass: the statistics are sums over the plane the blur
 // produces, so they are taken as the pixels leave the vertical pass (one launch and one read of the plane less)
 // NT lanes per square: 256 in batched launches (the chip is full of squares), 1024 when a launch holds only a frame or
@@ -360,40 +401,7 @@ __device__ __forceinline__ void pre5_stats_body(const u8* __restrict__ src, size
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     if (threadIdx.x < 20) acc[threadIdx.x] = 0;
     if (threadIdx.x == 0) nanf_[0] = 0;
-    {
-        const int ngx = (w + 3) >> 2, ntask = ngx * h;
-        for (int t0 = threadIdx.x; t0 < ntask; t0 += 4 * NT) {
-            u32 v[4][3];
-            int yy[4], xx[4];
-            bool full[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int t = t0 + q * NT;
-                full[q] = false;
-                if (t < ntask) {
-                    yy[q] = t / ngx;
-                    xx[q] = (t - yy[q] * ngx) << 2;
-                    full[q] = xx[q] + 3 < w;
-                    if (full[q]) __builtin_memcpy(v[q], s + (size_t)yy[q] * d.stride + 3 * xx[q], 12);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int t = t0 + q * NT;
-                if (t >= ntask) continue;
-                u8* o = g + yy[q] * w + xx[q];
-                if (full[q]) {
-                    o[0] = (u8)d_gray(v[q][0] & 255, (v[q][0] >> 8) & 255, (v[q][0] >> 16) & 255);
-                    o[1] = (u8)d_gray(v[q][0] >> 24, v[q][1] & 255, (v[q][1] >> 8) & 255);
-                    o[2] = (u8)d_gray((v[q][1] >> 16) & 255, v[q][1] >> 24, v[q][2] & 255);
-                    o[3] = (u8)d_gray((v[q][2] >> 8) & 255, (v[q][2] >> 16) & 255, v[q][2] >> 24);
-                } else {
-                    const u8* p = s + (size_t)yy[q] * d.stride + 3 * xx[q];
-                    for (int k = 0; xx[q] + k < w; k++) o[k] = (u8)d_gray(p[3 * k], p[3 * k + 1], p[3 * k + 2]);
-                }
-            }
-        }
-    }
+    stage_gray_bgr<NT>(s, d, g);
     __syncthreads();
     for (int x = tx; x < w; x += 16) {
         const int x0 = d_reflect101(x - 2, w), x1 = d_reflect101(x - 1, w), x3 = d_reflect101(x + 1, w), x4 = d_reflect101(x + 2, w);
@@ -848,7 +856,7 @@ __global__ __launch_bounds__(1024) void k_model_scan_mb(const BoardDev* __restri
     const BoardDev& T = tab[blockIdx.y];
     if ((int)blockIdx.x >= T.n || T.ms.mode == CBV_MODEL_FROZEN) return;
     const size_t s = (size_t)s0;
-    model_scan_square(T.descs, T.gray + s * T.plane_total, T.plane_total, T.ms, T.stats + s * T.n, T.n, T.dec + s * CBV_MAX_SQUARES, count, part);
+    model_scan_square(T.descs, T.cgray + s * T.plane_total, T.plane_total, T.ms, T.stats + s * T.n, T.n, T.dec + s * CBV_MAX_SQUARES, count, part);
 }
 
 // lanes of a workgroup: enough for the largest square at MS_PPL pixels a lane, whole waves, at most 1024
@@ -876,6 +884,182 @@ int launch_model_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int 
     prof_begin(ctx, CBV_K_MODEL_SCAN);
     hipLaunchKernelGGL(k_model_scan_mb, dim3(CBV_MAX_SQUARES, nb), dim3(model_scan_threads(max_px)), 0, ctx->stream, tab, s0, count);
     prof_end(ctx, CBV_K_MODEL_SCAN);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// k_change_blur_stats: ChangeDetector._preprocess (change_detector.py:49-56) of the pipeline for a board whose
+// ChangeDetector.blur_kernel is not the PieceDetector's 5 (cbv_pipeline_set_change_blur): BGR2GRAY + GaussianBlur((k, k), 0)
+// on the square alone, any odd k in 1..31, bit for bit k_squares_preprocess.  It runs behind k_squares_pre5_stats on the same
+// stream and owns the ChangeDetector planes; with a frozen, calibrated model it also fills in what pre5_stats (launched
+// without a model for such a board) left open: z_count and z_max of the records and the class bits of the decision bytes.
+// The shape is pre5's: lanes walk the square as a 16 x 16 grid, gray rows are staged as u8 and the horizontal pass as u16
+// in LDS, reflected columns / rows are resolved once per column / row and tap, and the kernel's symmetry makes it r + 1
+// multiplies per pixel and pass (cf[j] = the coefficient j taps from the centre).  A lane keeps the accumulators of all its
+// rows of a column (horizontal) or all its columns of a row (vertical) in registers while the taps go by.
+// ---------------------------------------------------------------------------
+template <int NT>
+__device__ __forceinline__ void change_blur_body(const u8* __restrict__ src, size_t src_frame_stride, const SquareDesc* __restrict__ descs,
+                                                 u8* __restrict__ plane, size_t plane_frame_stride, const float* __restrict__ mean,
+                                                 const float* __restrict__ sd, float z_thresh, cbv_sq_stats* __restrict__ stats, int nsq,
+                                                 u8* __restrict__ decisions, int blur_k, const u32* cf, uint2* part)
+{
+    constexpr int RSTEP = NT / 16;                      // rows between two rows of a lane
+    constexpr int ROWS = CBV_MAX_SQUARE_DIM / RSTEP;    // rows of a lane at most
+    constexpr int COLS = CBV_MAX_SQUARE_DIM / 16;       // columns of a lane at most
+    extern __shared__ __attribute__((aligned(16))) u8 smem[];
+    const SquareDesc d = descs[blockIdx.x];
+    const int w = d.w, h = d.h, n = w * h;
+    u8* g = smem;
+    u16* hb = (u16*)(smem + ((n + 15) & ~15));
+    const u8* s = src + (size_t)blockIdx.z * src_frame_stride + d.src_off;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const bool with_stats = mean != nullptr;
+    u8* dcp = decisions + (size_t)blockIdx.z * CBV_MAX_SQUARES + blockIdx.x;
+    const u32 dc_in = (with_stats && threadIdx.x == 0) ? *dcp : 0u;
+    stage_gray_bgr<NT>(s, d, g);
+    __syncthreads(); // (the caller's coefficient words are covered too)
+    const int r = blur_k >> 1;
+    // rows / columns a lane of this wave / workgroup can have: the unrolled loops below skip the rest as whole waves; a
+    // lane past the square's edge inside them computes on the edge row / column and stores nothing
+    const int nr = __builtin_amdgcn_readfirstlane((h - 1 - (ty & ~3) + RSTEP) / RSTEP);
+    const int nc = (w + 15) >> 4;
+    if (r > 0) {
+        int row[ROWS];
+#pragma unroll
+        for (int yi = 0; yi < ROWS; yi++) row[yi] = min(ty + yi * RSTEP, h - 1) * w;
+        const u32 c0 = cf[0];
+        for (int x = tx; x < w; x += 16) {
+            u32 acc[ROWS];
+#pragma unroll
+            for (int yi = 0; yi < ROWS; yi++)
+                if (yi < nr) acc[yi] = c0 * g[row[yi] + x];
+            for (int j = 1; j <= r; j++) {
+                const int xl = d_reflect101(x - j, w), xr = d_reflect101(x + j, w);
+                const u32 c = cf[j];
+#pragma unroll
+                for (int yi = 0; yi < ROWS; yi++)
+                    if (yi < nr) acc[yi] += c * ((u32)g[row[yi] + xl] + (u32)g[row[yi] + xr]);
+            }
+#pragma unroll
+            for (int yi = 0; yi < ROWS; yi++)
+                if (yi < nr && ty + yi * RSTEP < h) hb[row[yi] + x] = (u16)min(acc[yi], 65535u);
+        }
+        __syncthreads();
+    }
+    u8* outp = plane + (size_t)blockIdx.z * plane_frame_stride + d.plane_off;
+    const float* mp = with_stats ? mean + d.plane_off : nullptr;
+    const float* sp = with_stats ? sd + d.plane_off : nullptr;
+    u32 cnt = 0;
+    bool nan_seen = false;
+    float zmax = 0.f;
+    // a pixel leaves the blur: into the ChangeDetector plane and, against a frozen model, into the z-score statistics
+    // (sq_accum_px's model part)
+    auto emit = [&](int i, int gv) {
+        outp[i] = (u8)gv;
+        if (with_stats) {
+            bool over, isnan;
+            ms_z_px((float)gv, mp[i], sp[i], z_thresh, over, isnan, zmax);
+            cnt += over ? 1u : 0u;
+            nan_seen = nan_seen || isnan;
+        }
+    };
+    int col[COLS];
+#pragma unroll
+    for (int xi = 0; xi < COLS; xi++) col[xi] = min(tx + 16 * xi, w - 1);
+    for (int y = ty; y < h; y += RSTEP) {
+        if (r == 0) { // k = 1: GaussianBlur((1, 1)) is the gray itself
+#pragma unroll
+            for (int xi = 0; xi < COLS; xi++)
+                if (xi < nc && tx + 16 * xi < w) emit(y * w + col[xi], g[y * w + col[xi]]);
+            continue;
+        }
+        u32 acc[COLS];
+        const u32 c0 = cf[0];
+#pragma unroll
+        for (int xi = 0; xi < COLS; xi++)
+            if (xi < nc) acc[xi] = c0 * hb[y * w + col[xi]];
+        for (int j = 1; j <= r; j++) {
+            const int yu = d_reflect101(y - j, h) * w, yd = d_reflect101(y + j, h) * w;
+            const u32 c = cf[j];
+#pragma unroll
+            for (int xi = 0; xi < COLS; xi++)
+                if (xi < nc) acc[xi] += c * ((u32)hb[yu + col[xi]] + (u32)hb[yd + col[xi]]);
+        }
+#pragma unroll
+        for (int xi = 0; xi < COLS; xi++)
+            if (xi < nc && tx + 16 * xi < w) emit(y * w + col[xi], (int)min((acc[xi] + (1u << 15)) >> 16, 255u));
+    }
+    if (!with_stats) return;
+    cnt = wave_sum_u32(cnt);
+    zmax = wave_max_f32(zmax);
+    const u32 nanw = __ballot(nan_seen) != 0ull ? 1u : 0u;
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = make_uint2(cnt | (nanw << 31), __float_as_uint(zmax));
+    __syncthreads();
+    if (threadIdx.x == 0) ms_frame_finish(part, NT / 64, n, stats + (size_t)blockIdx.z * nsq + blockIdx.x, dcp, dc_in);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_change_blur_stats(const u8* __restrict__ src, size_t src_frame_stride, const SquareDesc* __restrict__ descs,
+                                                            u8* __restrict__ plane, size_t plane_frame_stride, const float* __restrict__ mean,
+                                                            const float* __restrict__ sd, float z_thresh, cbv_sq_stats* __restrict__ stats, int nsq,
+                                                            u8* __restrict__ decisions, const ChangeBlur cb)
+{
+    __shared__ u32 cf[16];
+    __shared__ uint2 part[MS_MAXW];
+    if (threadIdx.x < 16) cf[threadIdx.x] = cb.cf[threadIdx.x];
+    change_blur_body<NT>(src, src_frame_stride, descs, plane, plane_frame_stride, mean, sd, z_thresh, stats, nsq, decisions, cb.k, cf, part);
+}
+
+// every board of a pipeline in one launch: grid (CBV_MAX_SQUARES, boards, frames); boards that keep the default kernel leave
+template <int NT>
+__global__ __launch_bounds__(NT) void k_change_blur_stats_mb(const BoardDev* __restrict__ tab, int s0)
+{
+    __shared__ u32 cf[16];
+    __shared__ uint2 part[MS_MAXW];
+    const BoardDev& T = tab[blockIdx.y];
+    if ((int)blockIdx.x >= T.n || T.cb.k == 5) return;
+    if (threadIdx.x < 16) cf[threadIdx.x] = T.cb.cf[threadIdx.x];
+    const size_t s = (size_t)s0;
+    change_blur_body<NT>(T.warped + s * T.warped_stride, T.warped_stride, T.descs, T.cgray + s * T.plane_total, T.plane_total, T.cmean, T.csd,
+                         T.z_thresh, T.stats + s * T.n, T.n, T.dec + s * CBV_MAX_SQUARES, T.cb.k, cf, part);
+}
+
+// LDS by the largest square of the set, as k_squares_pre5_stats: u8 gray + u16 horizontal pass
+static size_t change_blur_lds(int max_px)
+{
+    if (max_px <= 0 || max_px > CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM) max_px = CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM;
+    return (size_t)((max_px + 15) & ~15) + 2 * (size_t)max_px;
+}
+
+int launch_change_blur_stats(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n, u8* plane,
+                             size_t plane_frame_stride, const float* mean, const float* sd, float z_thresh, cbv_sq_stats* stats,
+                             int batch, u8* decisions, const ChangeBlur& cb, int max_px)
+{
+    const size_t lds = change_blur_lds(max_px);
+    prof_begin(ctx, CBV_K_CHANGE_BLUR);
+    if ((long long)n * batch <= 2 * ctx->num_cus)
+        hipLaunchKernelGGL((k_change_blur_stats<1024>), dim3(n, 1, batch), dim3(1024), lds, ctx->stream, src, src_frame_stride, descs, plane,
+                           plane_frame_stride, mean, sd, z_thresh, stats, n, decisions, cb);
+    else
+        hipLaunchKernelGGL((k_change_blur_stats<256>), dim3(n, 1, batch), dim3(256), lds, ctx->stream, src, src_frame_stride, descs, plane,
+                           plane_frame_stride, mean, sd, z_thresh, stats, n, decisions, cb);
+    prof_end(ctx, CBV_K_CHANGE_BLUR);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_change_blur_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int max_px)
+{
+    const size_t lds = change_blur_lds(max_px);
+    prof_begin(ctx, CBV_K_CHANGE_BLUR);
+    const dim3 grid(CBV_MAX_SQUARES, nb, batch);
+    if ((long long)CBV_MAX_SQUARES * nb * batch <= 2 * ctx->num_cus)
+        hipLaunchKernelGGL((k_change_blur_stats_mb<1024>), grid, dim3(1024), lds, ctx->stream, tab, s0);
+    else
+        hipLaunchKernelGGL((k_change_blur_stats_mb<256>), grid, dim3(256), lds, ctx->stream, tab, s0);
+    prof_end(ctx, CBV_K_CHANGE_BLUR);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }

@@ -7,6 +7,7 @@ per-square temporal state of PieceDetector.detect_all_pieces
 Streams are independent, so N GPUs run N pipelines with no exchange.
 """
 import ctypes as C
+import json
 
 import numpy as np
 
@@ -25,6 +26,26 @@ def bits_to_positions(bits, rois_rc):
 DETECTOR_DEFAULTS = dict(history_size=5, min_presence=0.6, change_threshold=25, z_threshold=2.5, initial_variance=100,
                          use_hough=True, min_radius_ratio=0.20, max_radius_ratio=0.55, hough_param1=100, hough_param2=25)
 _D = DETECTOR_DEFAULTS
+
+
+def load_sensitivity_settings(path="sensitivity_settings.json"):
+    """The ChangeDetector settings calibrate_sensitivity.py saves: {"z_threshold", "initial_variance", "blur_kernel",
+    "alpha"}; the tool's other keys are left out.  z_threshold, initial_variance and blur_kernel are keywords of
+    `configure` / `add_board`, alpha goes to `set_model_update`.  (The reference's ChangeDetector never reads the file
+    itself: only the tool writes and reloads it.)"""
+    with open(path) as f:
+        data = json.load(f)
+    return {"z_threshold": float(data["z_threshold"]), "initial_variance": float(data["initial_variance"]),
+            "blur_kernel": int(data["blur_kernel"]), "alpha": float(data["alpha"])}
+
+
+def classify_hand_bits(changed, total, rois_rc):
+    """ChangeDetector.classify_hand_pattern (change_detector.py:169-201) from the `changed` and `total` bitsets of one
+    frame (bit i = roi i, `rois_rc` as bits_to_positions takes it)."""
+    n = bin(changed).count("1")
+    if bin(total).count("1") >= 2 or n >= 4 or n > 2:
+        return {"is_hand": True, "is_move": False, "move_candidates": set()}
+    return {"is_hand": False, "is_move": n == 2, "move_candidates": bits_to_positions(changed, rois_rc)}
 
 
 def _fill_board(cfg, points, grid_lines, rot180, display_size, margin, history_size, min_presence, change_threshold,
@@ -97,6 +118,23 @@ class _BoardMethods:
                 raise ValueError("model update mode %r: expected one of %s" % (mode, ", ".join(sorted(N.MODEL_MODES))))
             mode = N.MODEL_MODES[str(mode).lower()]
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_model_update(self.h_, mode, float(alpha)))
+
+    def set_change_blur(self, blur_kernel):
+        """ChangeDetector.blur_kernel of this board for the runs enqueued from now on (default 5): values below 1 count as
+        1, then `| 1`, at most 31.  The model is kept; `calibrate_changes` of a slot last run with another kernel raises
+        until the slot is run again (include/cbv.h, cbv_pipeline_set_change_blur)."""
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_change_blur(self.h_, int(blur_kernel)))
+        self._change_blur = max(int(blur_kernel), 1) | 1
+
+    @property
+    def change_blur(self):
+        """The blur kernel the ChangeDetector stage of this board runs with."""
+        return getattr(self, "_change_blur", 5)
+
+    def hand_pattern(self, result):
+        """ChangeDetector.classify_hand_pattern of one frame's cbv_frame_result: what calibrate_sensitivity.py:156-162
+        computes right after detect_changes_detailed."""
+        return classify_hand_bits(result.changed, result.total, self.rois_rc)
 
     def model(self, pos):
         """(mean, variance) float32 planes of the square at (file, rank) after every run enqueued so far:
@@ -298,7 +336,8 @@ class BoardPipeline(_BoardMethods):
                   history_size=_D["history_size"], min_presence=_D["min_presence"], change_threshold=_D["change_threshold"],
                   z_threshold=_D["z_threshold"], initial_variance=_D["initial_variance"], use_hough=_D["use_hough"],
                   min_radius_ratio=_D["min_radius_ratio"], max_radius_ratio=_D["max_radius_ratio"],
-                  hough_param1=_D["hough_param1"], hough_param2=_D["hough_param2"], enhance_region=False, enhance=True):
+                  hough_param1=_D["hough_param1"], hough_param2=_D["hough_param2"], enhance_region=False, enhance=True,
+                  blur_kernel=5):
         """`use_hough` and the radii mirror PieceDetector's attributes (piece_detector.py:33-35,222-230);
         pass min_radius / 100 and max_radius / 100 of piece_detector_settings.json as the application does.
         `enhance_region` (only without keep_enhanced): enhance the part of each frame the warp samples first and the rest
@@ -308,7 +347,8 @@ class BoardPipeline(_BoardMethods):
         run: the warp samples the camera frame as it is, then rotate, split and detect; `profile`, the CLAHE and sharpen
         settings are ignored, `keep_enhanced` and `enhance_region` are errors, and with a YUV `set_input_format` the warp
         reads the raw frames directly (raw mode: `upload` takes that format only, `synth` is an error, `download(0, slot)`
-        converts the slot)."""
+        converts the slot).
+        `blur_kernel`: ChangeDetector.blur_kernel (`set_change_blur`)."""
         cfg = N.PipelineConfig()
         e = cfg.enhance
         e.profile = N.ColorProfile.from_dict(profile)
@@ -330,14 +370,17 @@ class BoardPipeline(_BoardMethods):
         self.board_size = S_
         self.matrix = M
         self._cfg = cfg
+        self.set_change_blur(blur_kernel)
 
-    def add_board(self, points, grid_lines=None, rot180=False, display_size=(1280, 720), margin=100, **detector):
+    def add_board(self, points, grid_lines=None, rot180=False, display_size=(1280, 720), margin=100, blur_kernel=5, **detector):
         """Attach another board seen by the same camera (include/cbv.h, cbv_pipeline_add_board): it shares this
         pipeline's frames and enhancement, and has its own geometry, detector settings (the detector keywords of
         `configure`: history_size, min_presence, change_threshold, z_threshold, initial_variance, use_hough,
-        min_radius_ratio, max_radius_ratio, hough_param1, hough_param2) and temporal state.  `run` processes every
-        attached board.  Returns a Board with the per-board methods of this class."""
-        return Board(self, points, grid_lines, rot180, display_size, margin, **detector)
+        min_radius_ratio, max_radius_ratio, hough_param1, hough_param2), `blur_kernel` (`set_change_blur`) and temporal
+        state.  `run` processes every attached board.  Returns a Board with the per-board methods of this class."""
+        b = Board(self, points, grid_lines, rot180, display_size, margin, **detector)
+        b.set_change_blur(blur_kernel)
+        return b
 
     def frames_ptr(self):
         return self.ctx.lib.cbv_pipeline_frames_dev(self.h_)

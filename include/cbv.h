@@ -130,6 +130,10 @@ enum {
     CBV_K_THRESHOLD, CBV_K_SCAN, CBV_K_SYNTH, CBV_K_RESET, CBV_K_HOUGH, CBV_K_INGEST, CBV_K_MODEL_SCAN, CBV_K_WARP_YUV,
     CBV_K_COUNT
 };
+/* The enumeration above is closed: callers size arrays by CBV_K_COUNT.  Kernels added since then take the ids behind it,
+ * and CBV_K_END is one past the last id cbv_profile_read and cbv_kernel_name know. */
+#define CBV_K_CHANGE_BLUR CBV_K_COUNT /* k_change_blur_stats (cbv_pipeline_set_change_blur) */
+#define CBV_K_END (CBV_K_COUNT + 1)
 CBV_API int cbv_profile_enable(cbv_ctx* ctx, int kid /* -1 = all, -2 = none */);
 CBV_API int cbv_profile_read(cbv_ctx* ctx, int kid, double* total_ms, long long* launches);
 CBV_API int cbv_profile_reset(cbv_ctx* ctx);
@@ -536,7 +540,7 @@ typedef struct {
 /* Attach a board to a configured pipeline `parent` (not itself a board handle) and return its handle in *board.
  * cbv_pipeline_run(parent, ...) then processes every attached board for those slots.  A board handle is accepted by the
  * per-board calls, which act on that board alone: cbv_pipeline_results, _noise_results, _square_stats, _hough,
- * _download (which = 2), _calibrate, _update_references, _set_check_squares, _reset_state, _set_model_update, _model.  On a board handle
+ * _download (which = 2), _calibrate, _update_references, _set_check_squares, _reset_state, _set_model_update, _set_change_blur, _model.  On a board handle
  * cbv_pipeline_run, _upload, _upload_raw, _submit, _set_input_format, _synth, _configure, _host_ring and _download with
  * which 0 or 1 fail with CBV_ERR_STATE (_host_ring returns NULL, _host_slot_bytes 0); cbv_pipeline_reset_state(parent) resets board 0 only.
  * Lifecycle: cbv_pipeline_destroy(board) detaches and frees the board (the other boards are unchanged);
@@ -575,6 +579,18 @@ CBV_API int cbv_pipeline_add_board(cbv_pipeline* parent, const cbv_board_config*
  * cbv_pipeline_calibrate: an uncalibrated board has no model and nothing is updated until it is calibrated.
  * CBV_ERR_ARG for an unknown mode or an alpha outside [0, 1], and then nothing has changed. */
 CBV_API int cbv_pipeline_set_model_update(cbv_pipeline* board, int mode, double alpha);
+/* ChangeDetector.blur_kernel / _kernel of a board (pipeline or attached board), default 5.  Values below 1 count as 1,
+ * then k |= 1 (calibrate_sensitivity.py:139).  Applies to the runs enqueued after the call; the model is kept: the next
+ * frames are preprocessed with the new kernel (change_detector.py:49-56: BGR2GRAY, GaussianBlur((k, k), 0) on the square
+ * alone) and judged against the means and variances as they are.  Only the ChangeDetector side reads it (`changed`,
+ * `parcial`, `total`, `z_count`, `z_max`, cbv_pipeline_calibrate, the model updates, cbv_pipeline_model); detect_piece has
+ * its own 5 x 5 preprocess, so `circular`, the PieceDetector, the NoiseHandler and the game session do not depend on it.
+ * With k = 5 the board is what it was without this call; with another kernel it gets a second ring of planes and one more
+ * kernel per chunk (k_change_blur_stats, CBV_K_CHANGE_BLUR).  Allowed before cbv_pipeline_configure: the kernel stays with
+ * the board.  cbv_pipeline_calibrate(slot) of a slot whose last run used another kernel than the board's current one fails
+ * with CBV_ERR_STATE: run the slot again first.  k > 31: CBV_ERR_UNSUPPORTED (cbv_squares_load's limit), and then nothing
+ * has changed.  REFLECT_101 folds as often as needed, so every kernel fits every square. */
+CBV_API int cbv_pipeline_set_change_blur(cbv_pipeline* board, int blur_kernel);
 /* The model of square `roi` after every run enqueued so far (waits for them): which = 0 the mean plane
  * (change_detector.py:44), 1 the variance plane (change_detector.py:45), `out` = w * h floats, row major.  Read only.
  * CBV_ERR_STATE while the board is not calibrated. */
