@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "cbv_internal.h"
+#include <memory>
 
 thread_local std::string g_cbv_err;
 
@@ -303,6 +304,7 @@ int ctx_set_bilateral(cbv_ctx* ctx, int d, double sc, double ss)
     if (build_bilateral_tabs(d, sc, ss, &ctx->btabs_host) != 0)
         return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "bilateral d=%d not supported (radius <= 4)", d);
     if (ctx->btabs_host.radius > 4) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "bilateral d=%d not supported (radius <= 4)", d);
+    ctx->btabs_offsets_bad = bilateral_offsets_mismatch(&ctx->btabs_host);
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     CBV_HIP(ctx, hipMemcpy(ctx->btabs, &ctx->btabs_host, sizeof(BilateralTabs), hipMemcpyHostToDevice));
     ctx->b_d = d;
@@ -1110,6 +1112,16 @@ extern "C" int cbv_debug_poison(cbv_ctx* ctx, int on)
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     ctx->debug_poison = on ? 1 : 0;
     return CBV_OK;
+}
+
+// Not in include/cbv.h: for tests/test_bilateral_offsets_host.py, which needs no device.  Builds the bilateral tables of
+// (d, sigma_color, sigma_space) on the host and returns the number of taps whose table offset differs from the one the
+// batched d = 9 kernel carries as a compile-time constant (the check launch_bilateral makes); -1: radius not supported.
+extern "C" CBV_API int cbv_debug_bilateral_offsets(int d, double sigma_color, double sigma_space)
+{
+    auto t = std::make_unique<BilateralTabs>();
+    if (build_bilateral_tabs(d, sigma_color, sigma_space, t.get()) != 0 || t->radius > 4) return -1;
+    return bilateral_offsets_mismatch(t.get());
 }
 
 static bool same_desc(const SquareDesc& a, const SquareDesc& b)

@@ -1,10 +1,9 @@
 // cv2.bilateralFilter(d, sigmaColor, sigmaSpace) on 8UC3 (frame_enhancer.py:131).
 //
 // VALU/LDS-bound stencil (49 taps at d = 9), not an HBM-bound one.  Structure:
-//   - persistent workgroups of 768 lanes (12 waves = 3 per SIMD, <= 128 VGPRs),
-//     one per CU, each walking 128x48-pixel tiles; consecutive tiles of one XCD
-//     are neighbours, so halo rows are re-read from that XCD's L2.  Three waves
-//     per SIMD, not four, on purpose: see launch_bilateral;
+//   - persistent workgroups of 768 lanes (12 waves = 3 per SIMD), one per CU, each walking 128x48-pixel tiles;
+//     consecutive tiles of one XCD are neighbours, so halo rows are re-read from that XCD's L2.  Three waves per SIMD,
+//     not four, on purpose: see bilateral_nt;
 //   - the tile (+4 px halo, REFLECT_101 at the image border) sits in LDS as
 //     packed BGRx dwords: |db|+|dg|+|dr| is ONE v_sad_u8; the next tile is
 //     prefetched into registers while the current one is filtered;
@@ -31,17 +30,24 @@
 //     OpenCV's FMA3-dispatched body: w = space * colour (one rounding, here done
 //     when the table is built), sum = fma(px, w, sum), wsum += w: bit-equal to
 //     the oracle;
-//   - PAIRS (the batched 768-lane form at d = 9; build with BL_NO_PAIRS=1 for the form without it): w(p -> q) and
+//   - PAIRS (the batched form at d = 9; build with BL_NO_PAIRS=1 for the 768-lane form without it): w(p -> q) and
 //     w(q -> p) are the same table entry (the class depends on dx^2 + dy^2 only, the SAD is symmetric), so a weight
 //     that connects two of a lane's OWN eight outputs is looked up once, by the output whose accumulation order
 //     meets it first, and stays in a register for the other: 6 pairs on each of the two output rows and 16 between
 //     them, 28 of the lane's 392 sad + shift + gather triples (7.1 %), with no LDS traffic, no barrier and no halo
-//     lanes.  The two tile rows that carry these taps are straight-line code that walks the row's pixels in the outer
-//     loop (a pixel's three floats die early, which pays for the 22 weight registers): 119 VGPRs, no scratch, the LDS
-//     size and the tiling are unchanged.  Sharing across lanes (a stash in LDS that a wave fills walking down a band)
-//     would reach half of all lookups, but a weight that crosses dy rows lives dy row steps: 40 dwords per pixel
-//     column, 160 B x 3072 columns = 480 KB for a 768-lane workgroup.  It does not fit at any tiling that keeps the
-//     lanes busy.
+//     lanes.  Sharing across lanes (a stash in LDS that a wave fills walking down a band) would reach half of all
+//     lookups, but a weight that crosses dy rows lives dy row steps: 40 dwords per pixel column, far more than a CU's
+//     LDS at any tiling that keeps the lanes busy;
+//   - the PAIRS form is straight-line code for the whole tile: every tile row is instantiated with its dy, so the
+//     disc's extent and the class offset of each tap (bl_class_off) are compile-time constants: no scalar branch per
+//     tap, no tap_off loads.  It walks a row's 12 pixels in the outer loop, in half steps (one output row's four
+//     outputs), looks the weights of the next half step up before the current one accumulates, reads the row in
+//     pixel pairs one pair ahead and issues the next tile's prefetch after the lane's two own rows (its registers
+//     are free while the 22 shared weights are live): 93 VGPRs (119 before), no scratch, 61 184 B of LDS, so beside
+//     its three waves per SIMD (3 x 96 allocated registers) 224 registers stay free for the other lane's kernels, 152 before.
+//     BL_NT1024=1 builds it with 1024 lanes on 128x64 tiles, held to 96 registers (five waves per SIMD by registers,
+//     amdgpu_waves_per_eu on that instantiation only: 94 VGPRs, no scratch, 69 888 B), BL_NO_CAP=1 on top of it without
+//     that cap, for A/B runs: both are slower on the path.
 #include "cbv_device.h"
 #include <type_traits>
 
@@ -57,10 +63,73 @@ __host__ __device__ constexpr int bl_row_reach(int R, int dy)
     return rx;
 }
 
+// Table offset of tap (dy, dx), known when compiling: cbv_tables.cpp's rule restated.  A class is a distinct dy^2 + dx^2,
+// numbered by first occurrence in raster tap order; the offset is class x 768, -1 outside the disc.  The straight-line
+// rows use it in place of bt->tap_off (scalar loads there cost SGPRs and, through them, VGPRs); launch_bilateral compares
+// the two before it selects that form.
+__host__ __device__ constexpr int bl_class_off(int R, int dy, int dx)
+{
+    int r2_of_cls[CBV_BL_MAXCLS] = {}, ncls = 0;
+    for (int i = -R; i <= R; i++)
+        for (int j = -R; j <= R; j++) {
+            const int r2 = i * i + j * j;
+            if (r2 > R * R) continue;
+            int c = 0;
+            while (c < ncls && r2_of_cls[c] != r2) c++;
+            if (c == ncls) r2_of_cls[ncls++] = r2;
+            if (i == dy && j == dx) return c * 768;
+        }
+    return -1;
+}
+
+int bilateral_offsets_mismatch(const BilateralTabs* t)
+{
+    const int R = t->radius;
+    int bad = 0;
+    for (int dy = -R; dy <= R; dy++)
+        for (int dx = -R; dx <= R; dx++) bad += bl_class_off(R, dy, dx) != t->tap_off[dy + R][dx + R];
+    return bad;
+}
+
+// bl_class_off for every tap of radius R, as a constant the unrolled straight-line rows index with literal subscripts
+struct BlOffsets {
+    int v[9][9];
+};
+template <int R>
+constexpr BlOffsets bl_make_offsets()
+{
+    BlOffsets t = {};
+    for (int dy = -R; dy <= R; dy++)
+        for (int dx = -R; dx <= R; dx++) t.v[dy + R][dx + R] = bl_class_off(R, dy, dx);
+    return t;
+}
+template <int R>
+__device__ constexpr BlOffsets bl_offsets = bl_make_offsets<R>();
+
+// the disc's extent (bl_row_reach) and the offsets (bl_class_off) are two statements of one rule: they must name the same taps
+constexpr bool bl_disc_rules_agree(int R)
+{
+    for (int dy = -R; dy <= R; dy++)
+        for (int dx = -R; dx <= R; dx++)
+            if ((bl_class_off(R, dy, dx) >= 0) != ((dx < 0 ? -dx : dx) <= bl_row_reach(R, dy < 0 ? -dy : dy))) return false;
+    return true;
+}
+static_assert(bl_disc_rules_agree(1) && bl_disc_rules_agree(2) && bl_disc_rules_agree(3) && bl_disc_rules_agree(4), "bl_class_off and bl_row_reach disagree");
+
+template <int B, int E, class F>
+__device__ __forceinline__ void bl_static_for(F&& f)
+{
+    if constexpr (B < E) {
+        f(std::integral_constant<int, B>());
+        bl_static_for<B + 1, E>(f);
+    }
+}
+
 // NT lanes per workgroup (a multiple of 64): 32 strips x NT / 32 row pairs, i.e. tiles of 128 x NT / 16 pixels
 // PAIRS: the lane's eight outputs share the tap weights that connect two of them (see the header comment)
-template <int R, int NT, bool PAIRS = false>
-__global__ __launch_bounds__(NT) void k_bilateral(const u8* __restrict__ src, u8* __restrict__ dst, Geom g,
+// WAVES: waves per SIMD the register allocation must allow (0 = whatever NT needs)
+template <int R, int NT, bool PAIRS = false, int WAVES = 0>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_bilateral(const u8* __restrict__ src, u8* __restrict__ dst, Geom g,
                                                            const BilateralTabs* __restrict__ bt, TileSet ts, int batch,
                                                            SatGate gate)
 {
@@ -177,14 +246,16 @@ __global__ __launch_bounds__(NT) void k_bilateral(const u8* __restrict__ src, u8
             if (gi < NG) commit(here, gi, pre[k]);
         }
         __syncthreads();
-        // prefetch the next tile while this one is filtered
-        s = next_open(s + gridDim.x);
-        if (s < ntiles) {
-            cur = tile_at(xcd_remap(s, ntiles));
+        // prefetch the next tile while this one is filtered (PAIRS does it further down)
+        if constexpr (!PAIRS) {
+            s = next_open(s + gridDim.x);
+            if (s < ntiles) {
+                cur = tile_at(xcd_remap(s, ntiles));
 #pragma unroll
-            for (int k = 0; k < GPT; k++) {
-                const int gi = tid + k * BL_THREADS;
-                if (gi < NG) prefetch(cur, gi, pre[k]);
+                for (int k = 0; k < GPT; k++) {
+                    const int gi = tid + k * BL_THREADS;
+                    if (gi < NG) prefetch(cur, gi, pre[k]);
+                }
             }
         }
 
@@ -250,62 +321,116 @@ __global__ __launch_bounds__(NT) void k_bilateral(const u8* __restrict__ src, u8
                 }
             }
         };
-        // PAIRS: the lane's two OWN tile rows, ly + R (OWN = 0: output row a's dy = 0, row b's dy = -1) and ly + R + 1
-        // (OWN = 1: row a's dy = +1, row b's dy = 0).  A tap of one of the lane's outputs that is another of its outputs
-        // has the same weight in both directions (the class depends on dx^2 + dy^2 only, the SAD is symmetric), so only
-        // the output that needs it FIRST looks it up and leaves it in a register for the other:
+        // PAIRS: every tile row is straight-line code, one instantiation per row I: tap row dy = I - a - R of output row a
+        // and the disc's extent on it are known when compiling, so there are no per-tap scalar branches and no tap_off
+        // loads.  It walks the row's 12 pixels in the OUTER loop: every output still meets its taps in ascending dx (its
+        // accumulation order, the only order that fixes the result), and a pixel's three floats die before the next
+        // one's are made.
+        // The lane's two OWN tile rows are I = R (output row a's dy = 0, row b's dy = -1) and I = R + 1 (row a's dy = +1,
+        // row b's dy = 0).  A tap of one of the lane's outputs that is another of its outputs has the same weight in
+        // both directions (the class depends on dx^2 + dy^2 only, the SAD is symmetric), so only the output that needs
+        // it FIRST looks it up and leaves it in a register for the other:
         //   wh[lo][hi]: pixels lo < hi of one output row; hi takes it at dx = lo - hi, lo at dx = hi - lo, later on the row;
         //   wv[ob][oa]: pixel ob of row b and pixel oa of row a; row b takes it at dy = -1, row a at dy = +1, one row later.
-        // The disc's extent on these rows is known when compiling, so they are straight-line code, and it walks the
-        // row's 12 pixels in the OUTER loop: every output still meets its taps in ascending dx (its accumulation
-        // order, the only order that fixes the result), and a pixel's three floats die before the next one's are made,
-        // which pays for the 22 registers of wh and wv.
         float wh[4][4], wv[4][4];
-        auto own_row = [&](auto own) __attribute__((always_inline)) {
-            constexpr int OWN = decltype(own)::value;
-            const uint4* rowp = (const uint4*)(rowp0 + (R + OWN) * BL_PITCH);
-            const uint4 q0 = rowp[0], q1 = rowp[1], q2 = rowp[2];
-            const u32 p[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+        // Step U: pixel j of tile row I for output row a, U = (12 * I + j) * 2 + a.  look_up(U) makes the step's four
+        // weights, accumulate(U) uses them; the weights of step U + 1 are looked up before step U accumulates, so the
+        // gathers' latency is covered by a step's FMAs at the price of four more live weights.
+        constexpr int STEPS = 12 * (2 * R + 2) * 2;
+        u32 pq[2];          // the pixel of step U, by the parity of U / 2
+        float wt[2][2][4];  // the weight of step U for output [a][o], by the parity of U
+        float fb = 0.f, fg = 0.f, fr = 0.f;
+        uint2 qa, qb;       // this pixel pair of the tile row and the next one
+        auto look_up = [&](auto step) __attribute__((always_inline)) {
+            constexpr int U = decltype(step)::value, T = U / 2, I = T / 12, j = T % 12, B = U & 1;
+            if (U % 2 == 0) {
+                // the row's 12 pixels come in pairs, one pair ahead: two pairs are live instead of three quads
+                if (T == 0) qb = *(const uint2*)rowp0;
+                if (T % 2 == 0) {
+                    constexpr int P = T / 2 + 1; // the pair after this one: pair P % 6 of tile row P / 6
+                    qa = qb;
+                    if (P < 6 * (2 * R + 2)) qb = *(const uint2*)(rowp0 + (P / 6) * BL_PITCH + (P % 6) * 2);
+                }
+                pq[T & 1] = (T & 1) ? qa.y : qa.x;
+            }
+            const u32 pj = pq[T & 1];
 #pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const float fb = (float)(p[j] & 255u), fg = (float)((p[j] >> 8) & 255u), fr = (float)((p[j] >> 16) & 255u);
+            // Deliberately plain: a one-trip loop, plain `if`s on constants and the clamped index pc.  The same steps written with
+            // `if constexpr` and a compile-time o compile to 114 VGPRs at 768 lanes and to scratch at 1024 (the front end then
+            // unrolls, and hipcc schedules what it sees differently); tests/test_bilateral_resources.py guards the figures.
+            for (int a = U % 2; a <= U % 2; a++) { // one output row per step; a loop so that `continue` skips the step
+                const int dy = I - a - R; // of output row a on this tile row
+                if (dy < -R || dy > R) continue;
 #pragma unroll
-                for (int a = 0; a < 2; a++) {
-                    constexpr int NODY = 0;
-                    const int dy = a == OWN ? NODY : (OWN == 0 ? -1 : 1); // of output row a on this tile row
-#pragma unroll
-                    for (int o = 0; o < 4; o++) {
-                        const int dx = j - 4 - o, po = j - 4; // po: the tap's index in the lane's strip, if 0 .. 3
-                        if ((dx < 0 ? -dx : dx) > bl_row_reach(R, dy < 0 ? -dy : dy)) continue; // outside the disc
-                        const bool mine = po >= 0 && po < 4 && (dx != 0 || dy != 0);
-                        float wgt;
-                        if (mine && dy == 0 && dx > 0)
-                            wgt = wh[o][po];
-                        else if (mine && dy > 0)
-                            wgt = wv[po][o];
-                        else {
-                            const u32 idx = __builtin_amdgcn_sad_u8(p[j], ctr[a][o], (u32)bt->tap_off[dy + R][dx + R]);
-                            wgt = *(const float*)((const u8*)fw + (idx << 2));
-                            if (mine && dy == 0) wh[po][o] = wgt;
-                            if (mine && dy < 0) wv[o][po] = wgt;
-                        }
-                        sb[a][o] = __fmaf_rn(fb, wgt, sb[a][o]);
-                        sg[a][o] = __fmaf_rn(fg, wgt, sg[a][o]);
-                        sr[a][o] = __fmaf_rn(fr, wgt, sr[a][o]);
-                        sw[a][o] = sw[a][o] + wgt;
+                for (int o = 0; o < 4; o++) {
+                    const int dx = j - 4 - o, po = j - 4; // po: the tap's index in the lane's strip, if 0 .. 3
+                    const int pc = po & 3;                // po where `mine` holds; keeps the untaken branches' subscripts inside the arrays
+                    if ((dx < 0 ? -dx : dx) > bl_row_reach(R, dy < 0 ? -dy : dy)) continue; // outside the disc
+                    // the tap is another of the lane's own outputs (on output row a + dy)
+                    const bool mine = po >= 0 && po < 4 && (a + dy == 0 || a + dy == 1) && (dx != 0 || dy != 0);
+                    if (mine && dy == 0 && dx > 0)
+                        wt[B][a][o] = wh[o][pc];
+                    else if (mine && dy > 0)
+                        wt[B][a][o] = wv[pc][o];
+                    else {
+                        const u32 idx = __builtin_amdgcn_sad_u8(pj, ctr[a][o], (u32)bl_offsets<R>.v[dy + R][dx + R]);
+                        const float wgt = *(const float*)((const u8*)fw + (idx << 2));
+                        wt[B][a][o] = wgt;
+                        if (mine && dy == 0) wh[pc][o] = wgt;
+                        if (mine && dy < 0) wv[o][pc] = wgt;
                     }
                 }
-                __builtin_amdgcn_sched_barrier(0); // keeps hipcc from converting all 12 pixels ahead (144 registers)
             }
         };
-        if (PAIRS) {
-            // three pieces, not one loop with a special case: wh and wv must not become loop-carried registers
-#pragma unroll 1
-            for (int i = 0; i < R; i++) tile_row(i);
-            own_row(std::integral_constant<int, 0>());
-            own_row(std::integral_constant<int, 1>());
-#pragma unroll 1
-            for (int i = R + 2; i <= 2 * R + 1; i++) tile_row(i);
+        auto accumulate = [&](auto step) __attribute__((always_inline)) {
+            constexpr int U = decltype(step)::value, T = U / 2, I = T / 12, j = T % 12, B = U & 1;
+            if (U % 2 == 0) {
+                const u32 pj = pq[T & 1];
+                fb = (float)(pj & 255u), fg = (float)((pj >> 8) & 255u), fr = (float)((pj >> 16) & 255u);
+            }
+#pragma unroll
+            for (int a = U % 2; a <= U % 2; a++) { // one output row per step; a loop so that `continue` skips the step
+                const int dy = I - a - R;
+                if (dy < -R || dy > R) continue;
+#pragma unroll
+                for (int o = 0; o < 4; o++) {
+                    const int dx = j - 4 - o;
+                    if ((dx < 0 ? -dx : dx) > bl_row_reach(R, dy < 0 ? -dy : dy)) continue;
+                    const float wgt = wt[B][a][o];
+                    sb[a][o] = __fmaf_rn(fb, wgt, sb[a][o]);
+                    sg[a][o] = __fmaf_rn(fg, wgt, sg[a][o]);
+                    sr[a][o] = __fmaf_rn(fr, wgt, sr[a][o]);
+                    sw[a][o] = sw[a][o] + wgt;
+                }
+                // The step's sums are complete at this point of the instruction stream.  Without it hipcc looks up the
+                // weights of the whole tile first and accumulates afterwards: 168 VGPRs and 1.8 KB of scratch.
+                asm volatile("" : "+v"(sb[a][0]), "+v"(sg[a][0]), "+v"(sr[a][0]), "+v"(sw[a][0]), "+v"(sb[a][1]), "+v"(sg[a][1]), "+v"(sr[a][1]), "+v"(sw[a][1]),
+                             "+v"(sb[a][2]), "+v"(sg[a][2]), "+v"(sr[a][2]), "+v"(sw[a][2]), "+v"(sb[a][3]), "+v"(sg[a][3]), "+v"(sr[a][3]), "+v"(sw[a][3]));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        if constexpr (PAIRS) {
+            constexpr int HALF = 12 * (R + 2) * 2; // the lane's two own rows end here
+            look_up(std::integral_constant<int, 0>());
+            auto step = [&](auto t) __attribute__((always_inline)) {
+                constexpr int U = decltype(t)::value;
+                if constexpr (U + 1 < STEPS) look_up(std::integral_constant<int, U + 1>());
+                accumulate(t);
+            };
+            bl_static_for<0, HALF>(step);
+            // the next tile's prefetch, issued only now: pre is dead while wh and wv are live, and the R tile rows that
+            // follow still cover the loads (the same statements as above: as a lambda shared by both places they cost the
+            // forms without PAIRS six registers)
+            s = next_open(s + gridDim.x);
+            if (s < ntiles) {
+                cur = tile_at(xcd_remap(s, ntiles));
+#pragma unroll
+                for (int k = 0; k < GPT; k++) {
+                    const int gi = tid + k * BL_THREADS;
+                    if (gi < NG) prefetch(cur, gi, pre[k]);
+                }
+            }
+            bl_static_for<HALF, STEPS>(step);
         } else {
 #pragma unroll 1
             for (int i = 0; i <= 2 * R + 1; i++) tile_row(i);
@@ -345,17 +470,30 @@ __global__ __launch_bounds__(NT) void k_bilateral(const u8* __restrict__ src, u8
     }
 }
 
-// NT and workgroups per CU for a launch: 768 lanes = 3 waves per SIMD at <= 128 VGPRs: alone the kernel is 11 % slower
-// than with 1024 lanes (4 waves hide the LDS gather better), but a fourth wave slot and 160 VGPRs per SIMD stay free, so
-// the other lane's kernels run BESIDE it instead of waiting for its persistent workgroups to end; the whole path gains
-// 2-3 % (gpurun sweep, 1080p x 512: 640 lanes 26.0 k frames/s, 768 27.8 k, 896 25.5 k, 1024 27.2 k, 2 x 512 25.9 k).
+// NT and workgroups per CU for a launch.  A batched launch has one persistent workgroup per CU, of 768 lanes = 3 waves
+// per SIMD.  Alone the kernel is faster with 1024 lanes (4 waves hide the LDS gather better), but the other lane's
+// kernels run BESIDE it and the whole path is what counts.  At 116-120 VGPRs 1024 lanes left them 48 registers per SIMD
+// and lost 2-3 % (sweep, 1080p x 512: 640 lanes 26.0 k frames/s, 768 27.8 k, 896 25.5 k, 1024 27.2 k, 2 x 512 25.9 k).
+// Round 5 brought the d = 9 form under 96 VGPRs, where 1024 lanes leave 128 registers and a wave slot: 768 lanes still
+// win, by 1.7 % (BL_NT1024=1 builds the other form).
 // One or two frames (the live-camera case) are too few 128 x 48 tiles for 256 persistent workgroups (a 1080p frame has
 // 345: the second round is a third full).  128 x 32 tiles on TWO 512-lane workgroups per CU (2 x 52 KB of LDS, the same
 // 4 waves per SIMD as one 1024-lane workgroup) put 510 tiles on 512 workgroups in one round.
+#if defined(BL_NT1024) && !defined(BL_NO_PAIRS)
+#define BL_NT9 1024
+#ifdef BL_NO_CAP
+#define BL_WAVES9 0
+#else
+#define BL_WAVES9 5
+#endif
+#else
+#define BL_NT9 768
+#define BL_WAVES9 0
+#endif
 static int bilateral_nt(cbv_ctx* ctx, Geom g, int batch)
 {
     const long long t768 = (long long)((g.w + BL_TW - 1) / BL_TW) * ((g.h + 768 / 16 - 1) / (768 / 16)) * batch;
-    return t768 < 2ll * ctx->num_cus ? 512 : 768;
+    return t768 < 2ll * ctx->num_cus ? 512 : ctx->btabs_host.radius == 4 ? BL_NT9 : 768;
 }
 
 // tiles of the launch: the whole frame, or (region-limited enhancement) the tiles covering er->px / all the others
@@ -376,7 +514,7 @@ PxRect bilateral_region_cover(cbv_ctx* ctx, Geom g, int batch, PxRect need)
     return c;
 }
 
-template <int R, int NT, bool PAIRS = false>
+template <int R, int NT, bool PAIRS = false, int WAVES = 0>
 static int launch_bilateral_r(cbv_ctx* ctx, const u8* src, u8* dst, Geom g, int batch, int wgs_per_cu, const EnhanceRegion* er)
 {
     const TileSet ts = bilateral_tiles(g, NT, er);
@@ -387,7 +525,7 @@ static int launch_bilateral_r(cbv_ctx* ctx, const u8* src, u8* dst, Geom g, int 
     if (grid > ntiles) grid = ntiles;
     const SatGate gate = er ? er->gate : SatGate{nullptr, 0};
     prof_begin(ctx, CBV_K_BILATERAL);
-    hipLaunchKernelGGL((k_bilateral<R, NT, PAIRS>), dim3((unsigned)grid), dim3(NT), 0, ctx->stream, src, dst, g, ctx->btabs, ts, batch, gate);
+    hipLaunchKernelGGL((k_bilateral<R, NT, PAIRS, WAVES>), dim3((unsigned)grid), dim3(NT), 0, ctx->stream, src, dst, g, ctx->btabs, ts, batch, gate);
     prof_end(ctx, CBV_K_BILATERAL);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
@@ -410,7 +548,10 @@ int launch_bilateral(cbv_ctx* ctx, const u8* src, u8* dst, Geom g, int batch, co
 #ifdef BL_NO_PAIRS
     default: return launch_bilateral_r<4, 768>(ctx, src, dst, g, batch, 1, er); // the batched form without weight sharing, for A/B runs
 #else
-    default: return launch_bilateral_r<4, 768, true>(ctx, src, dst, g, batch, 1, er);
+    default:
+        // the straight-line rows carry their table offsets as compile-time constants: never compute with a table they do not fit
+        if (ctx->btabs_offsets_bad) return cbv_fail(ctx, CBV_ERR_STATE, "bilateral: compile-time tap offsets differ from the table's");
+        return launch_bilateral_r<4, BL_NT9, true, BL_WAVES9>(ctx, src, dst, g, batch, 1, er);
 #endif
     }
 }
