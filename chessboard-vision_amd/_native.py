@@ -198,6 +198,29 @@ class SessionRadar(C.Structure):
     _fields_ = [("lifted", C.c_int8), ("destinations", C.c_uint64)]
 
 
+class SweepSetting(C.Structure):
+    """cbv_sweep_setting: one trackbar position of calibrate_sensitivity.py (cbv_pipeline_sweep)."""
+    _fields_ = [("z_threshold", C.c_double), ("initial_variance", C.c_double), ("blur_kernel", C.c_int32), ("pad", C.c_int32)]
+
+
+class SweepRecord(C.Structure):
+    _fields_ = [("changed", C.c_uint64), ("parcial", C.c_uint64), ("total", C.c_uint64), ("z_max", C.c_float),
+                ("n_changed", C.c_uint8), ("n_total", C.c_uint8), ("flags", C.c_uint8), ("lifted", C.c_int8)]
+
+
+class SweepSummary(C.Structure):
+    _fields_ = [("frames_changed", C.c_uint32), ("frames_hand", C.c_uint32), ("frames_move", C.c_uint32),
+                ("frames_lifted", C.c_uint32), ("squares_reported", C.c_uint32), ("z_max", C.c_float)]
+
+
+class SweepInfo(C.Structure):
+    _fields_ = [("planes_ms", C.c_float), ("hist_ms", C.c_float), ("eval_ms", C.c_float), ("kernels_distinct", C.c_int32),
+                ("chunk_frames", C.c_int32)]
+
+
+SWEEP_HAND, SWEEP_MOVE = 1, 2
+SWEEP_MAX_SETTINGS, SWEEP_MAX_CHUNK, SWEEP_DEFAULT_CHUNK = 65536, 64, 16
+
 SESSION_RULES = {"session": 0, "game_state": 1}
 SESSION_RING = 1024
 SESSION_ONLINE = {None: 0, "white": 1, "black": 2}
@@ -317,6 +340,9 @@ def load():
         "cbv_pipeline_set_model_update": (i32, [vp, i32, dbl]),
         "cbv_pipeline_set_change_blur": (i32, [vp, i32]),
         "cbv_pipeline_model": (i32, [vp, i32, i32, vp]),
+        "cbv_pipeline_sweep": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, P(SweepInfo)]),
+        "cbv_pipeline_change_hist": (i32, [vp, i32, i32, i32, vp]),
+        "cbv_sweep_eval_host": (i32, [vp, vp, i32, vp, i32, vp]),
         "cbv_pipeline_session_begin": (i32, [vp, P(SessionConfig), C.c_char_p]),
         "cbv_pipeline_session_end": (i32, [vp]),
         "cbv_pipeline_session_moves": (i32, [vp, P(SessionMove), i32, P(i32)]),

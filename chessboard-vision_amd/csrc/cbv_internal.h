@@ -585,6 +585,23 @@ int launch_change_blur_stats(cbv_ctx* ctx, const u8* src, size_t src_frame_strid
                              int batch, u8* decisions, const ChangeBlur& cb, int max_px);
 int launch_change_blur_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int max_px);
 
+// The ChangeDetector sensitivity sweep (cbv_pipeline_sweep, k_sweep.hip).  A setting as the kernels read it: the float32
+// casts of cbv_pipeline_configure and the setting's place in the caller's list; the call sorts them by blur kernel.
+struct SweepSet {
+    float zt, ivf;
+    u32 index;
+};
+#define SWEEP_HIST_WORDS (CBV_MAX_SQUARES * 256) // u16 elements of one (frame, kernel): [square][d]
+// |gray - calib| histograms of `batch` warped frames under one blur kernel: out[frame * out_frame_stride + square * 256 + d]
+// (u16 elements), `calib` = the plane set (SquareDesc::plane_off) of the calibration frame under the same kernel
+int launch_change_hist(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n, const u8* calib, u16* out,
+                       size_t out_frame_stride, int batch, const ChangeBlur& cb, int max_px);
+// every setting on `frames` frames: hist[frame][kernel][square][d]; sets sorted by kernel, k_begin[nk + 1] = first setting
+// of each kernel; rec (may be null) = [setting index][rec_stride] records, this launch's frames in columns 0..frames - 1;
+// sums (may be null) = [setting index], added to
+int launch_sweep_eval(cbv_ctx* ctx, const u16* hist, int nk, const SquareDesc* descs, int n, const SweepSet* sets, const int* k_begin,
+                      int max_per_k, int frames, cbv_sweep_record* rec, int rec_stride, cbv_sweep_summary* sums);
+
 // ---------------------------------------------------------------------------
 // Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline.cpp) shares
 // ---------------------------------------------------------------------------

@@ -706,6 +706,143 @@ extern "C" int cbv_pipeline_model(cbv_pipeline* p, int which, int roi, float* ou
     return CBV_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The ChangeDetector sensitivity sweep (include/cbv.h, cbv_pipeline_sweep; kernels in k_sweep.hip).  Everything it allocates
+// belongs to the call and is freed when it returns; of the board it reads the warped ring, the square table and slot_blur.
+// ---------------------------------------------------------------------------
+namespace {
+struct SweepCall {
+    DevBuf planes, sets, kbeg, hist, rec, sums;
+    u8* h_rec = nullptr; // pinned staging of a chunk's records
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    ~SweepCall()
+    {
+        for (DevBuf* b : {&planes, &sets, &kbeg, &hist, &rec, &sums}) dev_free(b);
+        if (h_rec) (void)hipHostFree(h_rec);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+} // namespace
+
+// `hist_out` != null: cbv_pipeline_change_hist (one frame, one kernel, no evaluation)
+static int sweep_run(cbv_pipeline* p, const char* who, int calib_slot, int slot0, int count, const cbv_sweep_setting* settings, int ns,
+                     int chunk, cbv_sweep_record* records, cbv_sweep_summary* summaries, cbv_sweep_info* info, u16* hist_out)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the board is null", who);
+    Pipe& P = *p->pipe;
+    const Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    if (!P.configured) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the pipeline is not configured", who);
+    if (!settings || ns <= 0 || count <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "%s: no settings or no frames", who);
+    if (ns > CBV_SWEEP_MAX_SETTINGS) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %d settings (at most %d)", who, ns, CBV_SWEEP_MAX_SETTINGS);
+    if (chunk < 0 || chunk > CBV_SWEEP_MAX_CHUNK) return cbv_fail(ctx, CBV_ERR_ARG, "%s: chunk_frames %d is outside 0..%d", who, chunk, CBV_SWEEP_MAX_CHUNK);
+    if (calib_slot < 0 || calib_slot >= P.max_frames || slot0 < 0 || slot0 > P.max_frames - count)
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: slots outside the ring of %d", who, P.max_frames);
+    std::vector<int> ks;
+    for (int i = 0; i < ns; i++) {
+        const float ivf = (float)settings[i].initial_variance;
+        if (!(ivf > 0.f) || !(ivf <= 3.402823466e38f))
+            return cbv_fail(ctx, CBV_ERR_ARG, "%s: initial_variance %g of setting %d is not a positive finite float32", who, settings[i].initial_variance, i);
+        ks.push_back(std::max(settings[i].blur_kernel, 1) | 1);
+    }
+    std::vector<int> kd(ks);
+    std::sort(kd.begin(), kd.end());
+    kd.erase(std::unique(kd.begin(), kd.end()), kd.end());
+    if (kd.back() > 31) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: blur kernel %d too large (max 31)", who, kd.back());
+    CBV_ENTER(ctx);
+    if (!B.slot_blur[calib_slot]) return cbv_fail(ctx, CBV_ERR_STATE, "%s: slot %d was never run", who, calib_slot);
+    for (int i = 0; i < count; i++)
+        if (!B.slot_blur[slot0 + i]) return cbv_fail(ctx, CBV_ERR_STATE, "%s: slot %d was never run", who, slot0 + i);
+    RC(join_scan(P)); // lanes of the runs in flight write the warped ring
+    const int nk = (int)kd.size(), n = B.cfg.n_rois;
+    if (chunk == 0) chunk = CBV_SWEEP_DEFAULT_CHUNK;
+    chunk = std::min(chunk, count);
+    // the settings by kernel, each with its place in the caller's list
+    std::vector<SweepSet> sets;
+    std::vector<int> kbeg(1, 0);
+    int max_per_k = 0;
+    for (int ki = 0; ki < nk; ki++) {
+        for (int i = 0; i < ns; i++)
+            if (ks[i] == kd[ki]) sets.push_back(SweepSet{(float)settings[i].z_threshold, (float)settings[i].initial_variance, (u32)i});
+        kbeg.push_back((int)sets.size());
+        max_per_k = std::max(max_per_k, kbeg[ki + 1] - kbeg[ki]);
+    }
+    SweepCall S;
+    const bool eval = hist_out == nullptr;
+    RC(dev_ensure(ctx, &S.planes, B.plane_total * nk));
+    RC(dev_ensure(ctx, &S.hist, sizeof(u16) * SWEEP_HIST_WORDS * nk * chunk));
+    if (eval) {
+        RC(dev_ensure(ctx, &S.sets, sizeof(SweepSet) * ns));
+        RC(dev_ensure(ctx, &S.kbeg, sizeof(int) * (nk + 1)));
+        CBV_HIP(ctx, hipMemcpyAsync(S.sets.p, sets.data(), sizeof(SweepSet) * ns, hipMemcpyHostToDevice, ctx->stream));
+        CBV_HIP(ctx, hipMemcpyAsync(S.kbeg.p, kbeg.data(), sizeof(int) * (nk + 1), hipMemcpyHostToDevice, ctx->stream));
+        if (summaries) {
+            RC(dev_ensure(ctx, &S.sums, sizeof(cbv_sweep_summary) * ns));
+            CBV_HIP(ctx, hipMemsetAsync(S.sums.p, 0, sizeof(cbv_sweep_summary) * ns, ctx->stream));
+        }
+        if (records) {
+            RC(dev_ensure(ctx, &S.rec, sizeof(cbv_sweep_record) * ns * chunk));
+            CBV_HIP(ctx, hipHostMalloc((void**)&S.h_rec, sizeof(cbv_sweep_record) * ns * chunk, hipHostMallocDefault));
+        }
+    }
+    for (hipEvent_t& e : S.ev) CBV_HIP(ctx, hipEventCreate(&e));
+    const SquareDesc* descs = (const SquareDesc*)B.d_descs.p;
+    float ms = 0.f, planes_ms = 0.f, hist_ms = 0.f, eval_ms = 0.f;
+    // the calibration planes: ChangeDetector._preprocess of the calibration slot's squares under each kernel
+    CBV_HIP(ctx, hipEventRecord(S.ev[0], ctx->stream));
+    for (int ki = 0; ki < nk; ki++)
+        RC(launch_change_blur_stats(ctx, B.warped + B.warped_stride * calib_slot, B.warped_stride, descs, n, (u8*)S.planes.p + B.plane_total * ki,
+                                    B.plane_total, nullptr, nullptr, 0.f, nullptr, 1, nullptr, change_blur_coef(kd[ki]), B.max_px));
+    CBV_HIP(ctx, hipEventRecord(S.ev[1], ctx->stream));
+    CBV_HIP(ctx, hipEventSynchronize(S.ev[1]));
+    CBV_HIP(ctx, hipEventElapsedTime(&planes_ms, S.ev[0], S.ev[1]));
+    for (int c0 = 0; c0 < count; c0 += chunk) {
+        const int cf = std::min(chunk, count - c0);
+        CBV_HIP(ctx, hipEventRecord(S.ev[0], ctx->stream));
+        for (int ki = 0; ki < nk; ki++)
+            RC(launch_change_hist(ctx, B.warped + B.warped_stride * (slot0 + c0), B.warped_stride, descs, n, (const u8*)S.planes.p + B.plane_total * ki,
+                                  (u16*)S.hist.p + (size_t)SWEEP_HIST_WORDS * ki, (size_t)SWEEP_HIST_WORDS * nk, cf, change_blur_coef(kd[ki]), B.max_px));
+        CBV_HIP(ctx, hipEventRecord(S.ev[1], ctx->stream));
+        if (eval)
+            RC(launch_sweep_eval(ctx, (const u16*)S.hist.p, nk, descs, n, (const SweepSet*)S.sets.p, (const int*)S.kbeg.p, max_per_k, cf,
+                                 (cbv_sweep_record*)S.rec.p, chunk, (cbv_sweep_summary*)S.sums.p));
+        CBV_HIP(ctx, hipEventRecord(S.ev[2], ctx->stream));
+        if (eval && records) CBV_HIP(ctx, hipMemcpyAsync(S.h_rec, S.rec.p, sizeof(cbv_sweep_record) * ns * chunk, hipMemcpyDeviceToHost, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        CBV_HIP(ctx, hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        hist_ms += ms;
+        CBV_HIP(ctx, hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
+        eval_ms += ms;
+        if (eval && records)
+            for (int s = 0; s < ns; s++)
+                memcpy(records + (size_t)s * count + c0, (const cbv_sweep_record*)S.h_rec + (size_t)s * chunk, sizeof(cbv_sweep_record) * cf);
+    }
+    if (eval && summaries) CBV_HIP(ctx, hipMemcpy(summaries, S.sums.p, sizeof(cbv_sweep_summary) * ns, hipMemcpyDeviceToHost));
+    if (hist_out) CBV_HIP(ctx, hipMemcpy(hist_out, S.hist.p, sizeof(u16) * 256 * n, hipMemcpyDeviceToHost));
+    if (info) {
+        info->planes_ms = planes_ms;
+        info->hist_ms = hist_ms;
+        info->eval_ms = eval_ms;
+        info->kernels_distinct = nk;
+        info->chunk_frames = chunk;
+    }
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_sweep(cbv_pipeline* p, int calib_slot, int slot0, int count, const cbv_sweep_setting* settings, int ns, int chunk_frames,
+                                  cbv_sweep_record* records, cbv_sweep_summary* summaries, cbv_sweep_info* info)
+{
+    return sweep_run(p, "cbv_pipeline_sweep", calib_slot, slot0, count, settings, ns, chunk_frames, records, summaries, info, nullptr);
+}
+
+extern "C" int cbv_pipeline_change_hist(cbv_pipeline* p, int calib_slot, int slot, int blur_kernel, uint16_t* out)
+{
+    if (!out) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_change_hist: null argument");
+    const cbv_sweep_setting one = {0.0, 1.0, blur_kernel, 0};
+    return sweep_run(p, "cbv_pipeline_change_hist", calib_slot, slot, 1, &one, 1, 1, nullptr, nullptr, nullptr, out);
+}
+
 extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int reset_noise)
 {
     if (!p || !p->pipe->configured) return CBV_ERR_STATE;

@@ -9,6 +9,7 @@
 //   k_scan                detect_all_pieces' temporal logic over a batch of
 //                         frames: 64 independent per-square chains
 #include "cbv_device.h"
+#include "change_blur.h"
 #include "noise_core.h"
 
 // ---------------------------------------------------------------------------
@@ -331,47 +332,6 @@ __global__ __launch_bounds__(256) void k_squares_stats(const SquareDesc* __restr
         sq_accum_px(A, g[i], m[i], ref != nullptr, ref ? (int)ref[d.plane_off + i] : 0, mean != nullptr,
                     mean ? mean[d.plane_off + i] : 0.f, mean ? var[d.plane_off + i] : 1.f, z_thresh);
     sq_accum_finish(A, acc, zm, nanf_, n, mean != nullptr, out, nsq, decisions, want_hough, hough_work, hough_out, descs[blockIdx.x].cnt, dm);
-}
-
-// BGR2GRAY of a square's ROI into LDS (u8, rows packed) by NT lanes: four pixels (12 bytes, any alignment) per lane and load
-// instruction, four tasks a lane per round with all their loads issued before the first result is stored
-// (k_squares_preprocess5 explains both)
-template <int NT>
-__device__ __forceinline__ void stage_gray_bgr(const u8* __restrict__ s, const SquareDesc& d, u8* g)
-{
-    const int w = d.w, h = d.h;
-    const int ngx = (w + 3) >> 2, ntask = ngx * h;
-    for (int t0 = threadIdx.x; t0 < ntask; t0 += 4 * NT) {
-        u32 v[4][3];
-        int yy[4], xx[4];
-        bool full[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int t = t0 + q * NT;
-            full[q] = false;
-            if (t < ntask) {
-                yy[q] = t / ngx;
-                xx[q] = (t - yy[q] * ngx) << 2;
-                full[q] = xx[q] + 3 < w;
-                if (full[q]) __builtin_memcpy(v[q], s + (size_t)yy[q] * d.stride + 3 * xx[q], 12);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int t = t0 + q * NT;
-            if (t >= ntask) continue;
-            u8* o = g + yy[q] * w + xx[q];
-            if (full[q]) {
-                o[0] = (u8)d_gray(v[q][0] & 255, (v[q][0] >> 8) & 255, (v[q][0] >> 16) & 255);
-                o[1] = (u8)d_gray(v[q][0] >> 24, v[q][1] & 255, (v[q][1] >> 8) & 255);
-                o[2] = (u8)d_gray((v[q][1] >> 16) & 255, v[q][1] >> 24, v[q][2] & 255);
-                o[3] = (u8)d_gray((v[q][2] >> 8) & 255, (v[q][2] >> 16) & 255, v[q][2] >> 24);
-            } else {
-                const u8* p = s + (size_t)yy[q] * d.stride + 3 * xx[q];
-                for (int k = 0; xx[q] + k < w; k++) o[k] = (u8)d_gray(p[3 * k], p[3 * k + 1], p[3 * k + 2]);
-            }
-        }
-    }
 }
 
 // preprocess (k = 5) and statistics of the pipeline in one pass: the statistics are sums over the plane the blur
@@ -905,49 +865,17 @@ __device__ __forceinline__ void change_blur_body(const u8* __restrict__ src, siz
                                                  const float* __restrict__ sd, float z_thresh, cbv_sq_stats* __restrict__ stats, int nsq,
                                                  u8* __restrict__ decisions, int blur_k, const u32* cf, uint2* part)
 {
-    constexpr int RSTEP = NT / 16;                      // rows between two rows of a lane
-    constexpr int ROWS = CBV_MAX_SQUARE_DIM / RSTEP;    // rows of a lane at most
-    constexpr int COLS = CBV_MAX_SQUARE_DIM / 16;       // columns of a lane at most
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const SquareDesc d = descs[blockIdx.x];
-    const int w = d.w, h = d.h, n = w * h;
+    const int n = d.w * d.h;
     u8* g = smem;
     u16* hb = (u16*)(smem + ((n + 15) & ~15));
     const u8* s = src + (size_t)blockIdx.z * src_frame_stride + d.src_off;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const bool with_stats = mean != nullptr;
     u8* dcp = decisions + (size_t)blockIdx.z * CBV_MAX_SQUARES + blockIdx.x;
     const u32 dc_in = (with_stats && threadIdx.x == 0) ? *dcp : 0u;
     stage_gray_bgr<NT>(s, d, g);
     __syncthreads(); // (the caller's coefficient words are covered too)
-    const int r = blur_k >> 1;
-    // rows / columns a lane of this wave / workgroup can have: the unrolled loops below skip the rest as whole waves; a
-    // lane past the square's edge inside them computes on the edge row / column and stores nothing
-    const int nr = __builtin_amdgcn_readfirstlane((h - 1 - (ty & ~3) + RSTEP) / RSTEP);
-    const int nc = (w + 15) >> 4;
-    if (r > 0) {
-        int row[ROWS];
-#pragma unroll
-        for (int yi = 0; yi < ROWS; yi++) row[yi] = min(ty + yi * RSTEP, h - 1) * w;
-        const u32 c0 = cf[0];
-        for (int x = tx; x < w; x += 16) {
-            u32 acc[ROWS];
-#pragma unroll
-            for (int yi = 0; yi < ROWS; yi++)
-                if (yi < nr) acc[yi] = c0 * g[row[yi] + x];
-            for (int j = 1; j <= r; j++) {
-                const int xl = d_reflect101(x - j, w), xr = d_reflect101(x + j, w);
-                const u32 c = cf[j];
-#pragma unroll
-                for (int yi = 0; yi < ROWS; yi++)
-                    if (yi < nr) acc[yi] += c * ((u32)g[row[yi] + xl] + (u32)g[row[yi] + xr]);
-            }
-#pragma unroll
-            for (int yi = 0; yi < ROWS; yi++)
-                if (yi < nr && ty + yi * RSTEP < h) hb[row[yi] + x] = (u16)min(acc[yi], 65535u);
-        }
-        __syncthreads();
-    }
     u8* outp = plane + (size_t)blockIdx.z * plane_frame_stride + d.plane_off;
     const float* mp = with_stats ? mean + d.plane_off : nullptr;
     const float* sp = with_stats ? sd + d.plane_off : nullptr;
@@ -956,7 +884,7 @@ __device__ __forceinline__ void change_blur_body(const u8* __restrict__ src, siz
     float zmax = 0.f;
     // a pixel leaves the blur: into the ChangeDetector plane and, against a frozen model, into the z-score statistics
     // (sq_accum_px's model part)
-    auto emit = [&](int i, int gv) {
+    change_blur_passes<NT>(d, g, hb, blur_k, cf, [&](int i, int gv) {
         outp[i] = (u8)gv;
         if (with_stats) {
             bool over, isnan;
@@ -964,33 +892,7 @@ __device__ __forceinline__ void change_blur_body(const u8* __restrict__ src, siz
             cnt += over ? 1u : 0u;
             nan_seen = nan_seen || isnan;
         }
-    };
-    int col[COLS];
-#pragma unroll
-    for (int xi = 0; xi < COLS; xi++) col[xi] = min(tx + 16 * xi, w - 1);
-    for (int y = ty; y < h; y += RSTEP) {
-        if (r == 0) { // k = 1: GaussianBlur((1, 1)) is the gray itself
-#pragma unroll
-            for (int xi = 0; xi < COLS; xi++)
-                if (xi < nc && tx + 16 * xi < w) emit(y * w + col[xi], g[y * w + col[xi]]);
-            continue;
-        }
-        u32 acc[COLS];
-        const u32 c0 = cf[0];
-#pragma unroll
-        for (int xi = 0; xi < COLS; xi++)
-            if (xi < nc) acc[xi] = c0 * hb[y * w + col[xi]];
-        for (int j = 1; j <= r; j++) {
-            const int yu = d_reflect101(y - j, h) * w, yd = d_reflect101(y + j, h) * w;
-            const u32 c = cf[j];
-#pragma unroll
-            for (int xi = 0; xi < COLS; xi++)
-                if (xi < nc) acc[xi] += c * ((u32)hb[yu + col[xi]] + (u32)hb[yd + col[xi]]);
-        }
-#pragma unroll
-        for (int xi = 0; xi < COLS; xi++)
-            if (xi < nc && tx + 16 * xi < w) emit(y * w + col[xi], (int)min((acc[xi] + (1u << 15)) >> 16, 255u));
-    }
+    });
     if (!with_stats) return;
     cnt = wave_sum_u32(cnt);
     zmax = wave_max_f32(zmax);
@@ -1024,13 +926,6 @@ __global__ __launch_bounds__(NT) void k_change_blur_stats_mb(const BoardDev* __r
     const size_t s = (size_t)s0;
     change_blur_body<NT>(T.warped + s * T.warped_stride, T.warped_stride, T.descs, T.cgray + s * T.plane_total, T.plane_total, T.cmean, T.csd,
                          T.z_thresh, T.stats + s * T.n, T.n, T.dec + s * CBV_MAX_SQUARES, T.cb.k, cf, part);
-}
-
-// LDS by the largest square of the set, as k_squares_pre5_stats: u8 gray + u16 horizontal pass
-static size_t change_blur_lds(int max_px)
-{
-    if (max_px <= 0 || max_px > CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM) max_px = CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM;
-    return (size_t)((max_px + 15) & ~15) + 2 * (size_t)max_px;
 }
 
 int launch_change_blur_stats(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n, u8* plane,

@@ -39,6 +39,64 @@ def load_sensitivity_settings(path="sensitivity_settings.json"):
             "blur_kernel": int(data["blur_kernel"]), "alpha": float(data["alpha"])}
 
 
+# calibrate_sensitivity.py:31-39, the file's keys and the values the tool starts from
+SENSITIVITY_FILE_DEFAULTS = {"sensitivity": 25, "blur_kernel": 5, "stable_frames": 10, "z_threshold": 2.0, "alpha": 0.20,
+                             "initial_variance": 100, "use_gaussian": True}
+
+
+def save_sensitivity_settings(path, z_threshold, initial_variance, blur_kernel, alpha, **other):
+    """Write the file calibrate_sensitivity.py saves (:56-59: json, indent 2) with these ChangeDetector settings.  An
+    existing file keeps every key that is not given here; a new one starts from the tool's defaults (:31-39), as the tool's
+    own load-then-save does.  `other`: further keys of the file (sensitivity, stable_frames, use_gaussian, ...).
+    `load_sensitivity_settings(path)` returns what was written."""
+    data = dict(SENSITIVITY_FILE_DEFAULTS)
+    try:
+        with open(path) as f:
+            data.update(json.load(f))
+    except FileNotFoundError:
+        pass
+    iv = float(initial_variance)
+    data.update(other)
+    data.update(z_threshold=float(z_threshold), initial_variance=int(iv) if iv == int(iv) else iv, blur_kernel=int(blur_kernel),
+                alpha=float(alpha))
+    with open(path, "w") as f:
+        json.dump(data, f, indent=2)
+    return data
+
+
+def sensitivity_trackbar_grid():
+    """(z_thresholds, initial_variances, blur_kernels): every value the trackbars of calibrate_sensitivity.py can produce
+    (:91-98 the ranges, :116-126 and :139 the formulas), duplicates removed, in trackbar order: 51, 80 and 8 values."""
+    def uniq(values):
+        return list(dict.fromkeys(values))
+    z = uniq(max(0.5, min(3.0, 3.0 - s / 20.0)) for s in range(51))
+    iv = uniq(max(10, t * 10) for t in range(81))
+    k = uniq(max(1, b) | 1 for b in range(16))
+    return z, iv, k
+
+
+class SweepResult:
+    """What `sensitivity_sweep` returns.  `settings`: [S] structured array (z_threshold, initial_variance, blur_kernel as
+    given).  With records: `changed`, `parcial`, `total` (uint64 square sets, bit i = roi i), `z_max`, `n_changed`,
+    `n_total`, `is_hand`, `is_move`, `lifted` (roi or -1) as [S, F] arrays.  `summary`: [S] structured array
+    (frames_changed, frames_hand, frames_move, frames_lifted, squares_reported, z_max).  `info`: dict of the GPU times (ms) of
+    the three stages, the number of distinct blur kernels and the chunk."""
+
+    def __init__(self, settings, records, summary, info, rois_rc):
+        self.settings, self.records, self.summary, self.info, self._rois_rc = settings, records, summary, info, rois_rc
+        if records is not None:
+            for name in ("changed", "parcial", "total", "z_max", "n_changed", "n_total", "lifted"):
+                setattr(self, name, records[name])
+            self.is_hand = (records["flags"] & N.SWEEP_HAND) != 0
+            self.is_move = (records["flags"] & N.SWEEP_MOVE) != 0
+
+    def pattern(self, s, i):
+        """ChangeDetector.classify_hand_pattern's dict for setting s on frame i, positions as (file, rank)."""
+        if self.records is None:
+            raise RuntimeError("the sweep was made with records=False")
+        return classify_hand_bits(int(self.changed[s, i]), int(self.total[s, i]), self._rois_rc)
+
+
 def classify_hand_bits(changed, total, rois_rc):
     """ChangeDetector.classify_hand_pattern (change_detector.py:169-201) from the `changed` and `total` bitsets of one
     frame (bit i = roi i, `rois_rc` as bits_to_positions takes it)."""
@@ -135,6 +193,51 @@ class _BoardMethods:
         """ChangeDetector.classify_hand_pattern of one frame's cbv_frame_result: what calibrate_sensitivity.py:156-162
         computes right after detect_changes_detailed."""
         return classify_hand_bits(result.changed, result.total, self.rois_rc)
+
+    def sensitivity_sweep(self, calib_slot, slot0, count, z_thresholds=None, initial_variances=None, blur_kernels=None,
+                          settings=None, records=True, chunk_frames=0):
+        """What calibrate_sensitivity.py's loop reports for many trackbar positions at once (include/cbv.h,
+        cbv_pipeline_sweep): every setting on the processed slots slot0 .. slot0 + count - 1, judged against a model
+        calibrated on `calib_slot` and never updated, exactly as a board configured with that setting would report it.
+        Settings: itertools.product(z_thresholds, initial_variances, blur_kernels), or `settings` = [(z_threshold, initial_variance, blur_kernel)].  The board itself is not touched.  `records=False`
+        returns the per-setting summary only.  Returns a SweepResult."""
+        import itertools
+        if settings is None:
+            if z_thresholds is None or initial_variances is None or blur_kernels is None:
+                raise ValueError("sensitivity_sweep: give z_thresholds, initial_variances and blur_kernels, or settings")
+            settings = list(itertools.product(z_thresholds, initial_variances, blur_kernels))
+        sets = np.zeros(len(settings), N.record_dtype(N.SweepSetting))
+        for i, (z, iv, k) in enumerate(settings):
+            sets[i] = (z, iv, k)
+        rec = np.zeros((len(sets), count), N.record_dtype(N.SweepRecord)) if records else None
+        summ = np.zeros(len(sets), N.record_dtype(N.SweepSummary))
+        info = N.SweepInfo()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_sweep(self.h_, calib_slot, slot0, count, N.ptr(sets), len(sets), chunk_frames,
+                                                       N.ptr(rec) if records else None, N.ptr(summ), info))
+        return SweepResult(sets, rec, summ, {name: getattr(info, name) for name, _ in N.SweepInfo._fields_}, self.rois_rc)
+
+    def change_hist(self, calib_slot, slot, blur_kernel):
+        """[n_rois, 256] uint16: per square the histogram of |gray - calibration gray| of a processed slot against
+        `calib_slot` under ChangeDetector.blur_kernel = `blur_kernel`, the sufficient statistic of the sweep."""
+        out = np.zeros((len(self.rois_rc), 256), np.uint16)
+        self.ctx.check(self.ctx.lib.cbv_pipeline_change_hist(self.h_, calib_slot, slot, int(blur_kernel), N.ptr(out)))
+        return out
+
+    def change_radar(self, pattern, game):
+        """The radar of calibrate_sensitivity.py:173-189 on a classify_hand_pattern dict (`hand_pattern`,
+        `SweepResult.pattern`) and a GameState: with exactly one move candidate, no hand, and a piece of the side to move
+        on that square, (lifted (file, rank), [(file, rank) of that piece's legal destinations, in move order]); else
+        (None, []).  Host code."""
+        from . import chess_rules as chess
+        candidates = pattern.get("move_candidates", set())
+        if len(candidates) != 1 or pattern.get("is_hand"):
+            return None, []
+        lifted = next(iter(candidates))
+        sq = chess.square(*lifted)
+        piece = game.board.piece_at(sq)
+        if not piece or piece.color != game.board.turn:
+            return None, []
+        return lifted, [(chess.square_file(m.to_square), chess.square_rank(m.to_square)) for m in game.board.legal_moves if m.from_square == sq]
 
     def model(self, pos):
         """(mean, variance) float32 planes of the square at (file, rank) after every run enqueued so far:

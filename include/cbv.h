@@ -597,6 +597,58 @@ CBV_API int cbv_pipeline_set_change_blur(cbv_pipeline* board, int blur_kernel);
 CBV_API int cbv_pipeline_model(cbv_pipeline* board, int which, int roi, float* out);
 
 /* ------------------------------------------------------------------ */
+/* ChangeDetector sensitivity sweep on the device                       */
+/* ------------------------------------------------------------------ */
+/* What calibrate_sensitivity.py's loop computes (:110-162) for many trackbar positions at once, on frames already in the
+ * board's warped ring.  The tool calibrates once and never updates the model, so every frame is judged against the blurred
+ * gray of the calibration frame (a u8 plane) with the constant variance initial_variance: a pixel's score is
+ * z = fdiv_rn((float)d, sqrt_rn((float)initial_variance)) with d = |gray - mean| an integer in 0..255, and the 256-bin
+ * histogram of d per (blur kernel, frame, square) answers every (z_threshold, initial_variance) exactly.
+ * DEFINITION: setting s on frame i is what a board gives that was configured with z_threshold, initial_variance and
+ * blur_kernel of s (the float32 casts of cbv_pipeline_configure, the normalisation of cbv_pipeline_set_change_blur: below 1
+ * counts as 1, then |= 1), calibrated by cbv_pipeline_calibrate(calib_slot), left frozen, and run on slot slot0 + i. */
+typedef struct { double z_threshold; double initial_variance; int32_t blur_kernel; int32_t pad; } cbv_sweep_setting;
+typedef struct {              /* one (setting, frame): 32 bytes */
+    uint64_t changed, parcial, total;  /* as in cbv_frame_result */
+    float z_max;              /* max z_score over the reported squares, 0 if none */
+    uint8_t n_changed, n_total;
+    uint8_t flags;            /* 1 is_hand, 2 is_move (classify_hand_pattern, change_detector.py:169-201) */
+    int8_t lifted;            /* roi of the single move candidate when n_changed == 1 and not is_hand, else -1 */
+} cbv_sweep_record;
+#define CBV_SWEEP_HAND 1
+#define CBV_SWEEP_MOVE 2
+typedef struct {              /* one setting over the call's frames */
+    uint32_t frames_changed, frames_hand, frames_move, frames_lifted;
+    uint32_t squares_reported;   /* sum of n_changed */
+    float z_max;
+} cbv_sweep_summary;
+typedef struct { float planes_ms, hist_ms, eval_ms; int32_t kernels_distinct, chunk_frames; } cbv_sweep_info;
+#define CBV_SWEEP_MAX_SETTINGS 65536  /* the tool's trackbars span 51 x 80 x 8 positions */
+#define CBV_SWEEP_MAX_CHUNK 64        /* frames per chunk at most */
+#define CBV_SWEEP_DEFAULT_CHUNK 16    /* chunk_frames = 0 */
+/* Any board handle.  Reads the board's warped ring only: model, planes, statistics, results, temporal state and settings
+ * of the board are neither read nor written, and a pipeline that never calls this launches and allocates nothing for it.
+ * Waits for the runs in flight and returns when `records` ([ns][count], setting major; may be NULL) and `summaries` ([ns],
+ * may be NULL) are filled; `info` (may be NULL) gets the GPU time of the three stages (event pairs: calibration planes,
+ * k_change_hist, k_sweep_eval), the number of distinct blur kernels and the chunk used.  Histograms are made and consumed
+ * in chunks of `chunk_frames` frames (0 = CBV_SWEEP_DEFAULT_CHUNK, at most CBV_SWEEP_MAX_CHUNK), which bounds the call's
+ * own device memory whatever `count` is: chunk x 16 kernels x 32 KiB of histograms (at most 32 MiB), 16 plane sets of the
+ * board, ns x 40 bytes of settings and summaries and, with `records`, ns x chunk x 32 bytes of staging.  The result does not
+ * depend on the chunk.  All of it is freed before the call returns.
+ * CBV_ERR_STATE: not configured, or calib_slot or one of the frame slots was never run.  CBV_ERR_ARG: null or empty
+ * arguments, slots outside the ring, chunk_frames outside 0..CBV_SWEEP_MAX_CHUNK, ns above CBV_SWEEP_MAX_SETTINGS, or an
+ * initial_variance whose float32 value is not finite or not above 0.  CBV_ERR_UNSUPPORTED: a blur kernel above 31.  After
+ * any error nothing has changed. */
+CBV_API int cbv_pipeline_sweep(cbv_pipeline* board, int calib_slot, int slot0, int count, const cbv_sweep_setting* settings, int ns,
+                               int chunk_frames, cbv_sweep_record* records, cbv_sweep_summary* summaries, cbv_sweep_info* info);
+/* The histogram itself: out[roi][d] = pixels of square roi in slot `slot` with |gray - calibration gray| == d under
+ * `blur_kernel` (normalised as above); a square has at most 128 x 128 pixels.  Errors as cbv_pipeline_sweep. */
+CBV_API int cbv_pipeline_change_hist(cbv_pipeline* board, int calib_slot, int slot, int blur_kernel, uint16_t* out);
+/* The host twin of k_sweep_eval, no GPU: hist[n][256] and n_px[n] (pixels per square) of ONE frame, n <= CBV_MAX_SQUARES
+ * -> out[ns]; a setting's blur_kernel is not read (the histograms were made with it).  0, or CBV_ERR_ARG. */
+CBV_API int cbv_sweep_eval_host(const uint16_t* hist, const int32_t* n_px, int n, const cbv_sweep_setting* s, int ns, cbv_sweep_record* out);
+
+/* ------------------------------------------------------------------ */
 /* game session on the device: stable moves, smart scan, FEN           */
 /* ------------------------------------------------------------------ */
 /* The back half of GameSession.on_frame (game_session.py:130-265) for every frame of every run of a board, on the
@@ -690,8 +742,9 @@ CBV_API int cbv_session_state_fen(const cbv_session_state* state, char* out, int
  * with the board in force at that frame (events due there applied): when expected & ~vision has exactly one member and
  * the piece on it has the side to move's colour, `lifted` is that square and `destinations` the union of to_square over
  * the legal moves from it; else -1 and 0.  ROI numbering, like every square set here.
- * Out of scope: the HTTP client and its threads, make_move failures, drawing, and the radar of calibrate_sensitivity.py
- * (ChangeDetector move candidates, not occupancy). */
+ * Out of scope: the HTTP client and its threads, make_move failures and drawing.  (The radar of calibrate_sensitivity.py
+ * works on ChangeDetector move candidates, not occupancy: the sensitivity sweep below gives `lifted` per setting and frame,
+ * and the binding's change_radar finishes it on the host.) */
 #define CBV_SESSION_ONLINE_OFF   0
 #define CBV_SESSION_ONLINE_WHITE 1
 #define CBV_SESSION_ONLINE_BLACK 2
