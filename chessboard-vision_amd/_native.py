@@ -218,6 +218,29 @@ class SweepInfo(C.Structure):
                 ("chunk_frames", C.c_int32)]
 
 
+class PieceSweepRecord(C.Structure):
+    """cbv_piece_sweep_record: one (setting, frame) of cbv_pipeline_piece_sweep."""
+    _fields_ = [("raw_occupied", C.c_uint64), ("stable_occupied", C.c_uint64), ("hough", C.c_uint64), ("tower_top", C.c_uint64),
+                ("center_diff", C.c_uint64), ("symmetry", C.c_uint64), ("r_min", C.c_int16), ("r_max", C.c_int16),
+                ("n_raw", C.c_uint8), ("n_stable", C.c_uint8), ("flags", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class PieceSweepSummary(C.Structure):
+    _fields_ = [("frames", C.c_uint32), ("frames_exact", C.c_uint32), ("missed", C.c_uint32), ("false_pos", C.c_uint32),
+                ("n_hough", C.c_uint32), ("n_tower_top", C.c_uint32), ("n_center_diff", C.c_uint32), ("n_symmetry", C.c_uint32),
+                ("r_min", C.c_int32), ("r_max", C.c_int32), ("n_r", C.c_uint32), ("overflow", C.c_uint32), ("r_sum", C.c_uint64)]
+
+
+class PieceSweepInfo(C.Structure):
+    _fields_ = [("hough_ms", C.c_float), ("eval_ms", C.c_float), ("param1_distinct", C.c_int32), ("chunk_frames", C.c_int32)]
+
+
+class PieceChoice(C.Structure):
+    """What k_piece_sweep_hough leaves per (setting, frame, square); cbv_piece_sweep_eval_host reads arrays of it."""
+    _fields_ = [("kind", C.c_uint8), ("flags", C.c_uint8), ("r", C.c_int16), ("cx", C.c_int16), ("cy", C.c_int16)]
+
+
+PIECE_SWEEP_OVERFLOW, PIECE_SWEEP_MAX_SETTINGS = 1, 65536
 SWEEP_HAND, SWEEP_MOVE = 1, 2
 SWEEP_MAX_SETTINGS, SWEEP_MAX_CHUNK, SWEEP_DEFAULT_CHUNK = 65536, 64, 16
 
@@ -343,6 +366,9 @@ def load():
         "cbv_pipeline_sweep": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, P(SweepInfo)]),
         "cbv_pipeline_change_hist": (i32, [vp, i32, i32, i32, vp]),
         "cbv_sweep_eval_host": (i32, [vp, vp, i32, vp, i32, vp]),
+        "cbv_pipeline_piece_sweep": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, P(PieceSweepInfo)]),
+        "cbv_pipeline_piece_detail": (i32, [vp, i32, P(HoughParams), vp]),
+        "cbv_piece_sweep_eval_host": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
         "cbv_pipeline_session_begin": (i32, [vp, P(SessionConfig), C.c_char_p]),
         "cbv_pipeline_session_end": (i32, [vp]),
         "cbv_pipeline_session_moves": (i32, [vp, P(SessionMove), i32, P(i32)]),

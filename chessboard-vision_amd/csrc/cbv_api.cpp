@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "cbv_internal.h"
+#include "piece_sweep_core.h"
 #include <memory>
 
 thread_local std::string g_cbv_err;
@@ -1212,69 +1213,22 @@ extern "C" int cbv_squares_set_ref_mask(cbv_squares* s, uint64_t mask)
 }
 
 // PieceDetector.detect_piece (piece_detector.py:289-345) for one square from its statistics and its HoughCircles
-// record, in the reference's arithmetic: np.std as an exact integer test, means and differences as float64
-// quotients, np.var of the ring means summed left to right like numpy does for fewer than eight elements.
+// record: the decision itself is piece_decide (piece_sweep_core.h), which the settings sweep shares.
 extern "C" int cbv_decide_piece(const cbv_sq_stats* st, const cbv_hough_result* hg, int w, int h, double circle_threshold,
                                 cbv_piece_result* out)
 {
     if (!st || !out) return CBV_ERR_ARG;
-    out->has_piece = 0;
-    out->method = CBV_METHOD_NONE;
-    out->cx = out->cy = out->radius = 0;
-    out->confidence = 0.0;
-    out->center_border_diff = 0.0;
-    const long long n = st->n, sm = st->sum;
-    if (n * (long long)st->sumsq - sm * sm < 225ll * n * n) return CBV_OK; // np.std(gray) < 15: nothing else is tried
-    if (hg && (hg->flags & CBV_HOUGH_OVERFLOW)) return CBV_ERR_UNSUPPORTED; // never passed on as HoughCircles' answer
-    if (hg && hg->found) {
-        out->has_piece = 1;
-        out->method = hg->kind == 2 ? CBV_METHOD_TOWER_TOP : CBV_METHOD_HOUGH;
-        out->cx = (int)hg->cx; // int(np.float32): toward zero
-        out->cy = (int)hg->cy;
-        out->radius = (int)hg->r;
-        out->confidence = hg->kind == 2 ? 0.75 : 0.9;
-        return CBV_OK;
+    if (hg && (hg->flags & CBV_HOUGH_OVERFLOW) && !piece_uniform(st)) { // never passed on as HoughCircles' answer
+        out->has_piece = 0;
+        out->method = CBV_METHOD_NONE;
+        out->cx = out->cy = out->radius = 0;
+        out->confidence = 0.0;
+        out->center_border_diff = 0.0;
+        return CBV_ERR_UNSUPPORTED;
     }
-    const double zero = 0.0;
-    const double cm = st->center_cnt ? (double)st->center_sum / (double)st->center_cnt : zero / zero; // np.mean of nothing is nan
-    const double bm = st->border_cnt ? (double)st->border_sum / (double)st->border_cnt : zero / zero;
-    const double diff = fabs(cm - bm);
-    out->center_border_diff = diff;
-    const int md = w < h ? w : h;
-    if (diff > 40) {
-        out->has_piece = 1;
-        out->method = CBV_METHOD_CENTER_DIFF;
-        out->cx = w / 2;
-        out->cy = h / 2;
-        out->radius = md / 3;
-        out->confidence = diff / 80 < 1.0 ? diff / 80 : 1.0;
-        return CBV_OK;
-    }
-    double rm[4];
-    int nr = 0;
-    for (int k = 0; k < 4; k++)
-        if (st->ring_cnt[k] > 0) rm[nr++] = (double)st->ring_sum[k] / (double)st->ring_cnt[k];
-    double symmetry = 0.0;
-    if (nr >= 2) {
-        double sum = 0;
-        for (int k = 0; k < nr; k++) sum = sum + rm[k];
-        const double mean = sum / nr;
-        double sq = 0;
-        for (int k = 0; k < nr; k++) {
-            const double x = rm[k] - mean;
-            sq = sq + x * x;
-        }
-        const double var = sq / nr;
-        symmetry = var / 500 < 1.0 ? var / 500 : 1.0;
-    }
-    if (symmetry > circle_threshold) {
-        out->has_piece = 1;
-        out->method = CBV_METHOD_SYMMETRY;
-        out->cx = w / 2;
-        out->cy = h / 2;
-        out->radius = md / 3;
-        out->confidence = symmetry;
-    }
+    const bool found = hg && hg->found;
+    // int(np.float32): toward zero
+    piece_decide(st, found, found ? hg->kind : 0, found ? (int)hg->cx : 0, found ? (int)hg->cy : 0, found ? (int)hg->r : 0, w, h, circle_threshold, out);
     return CBV_OK;
 }
 

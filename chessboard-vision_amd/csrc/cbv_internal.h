@@ -602,6 +602,29 @@ int launch_change_hist(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, con
 int launch_sweep_eval(cbv_ctx* ctx, const u16* hist, int nk, const SquareDesc* descs, int n, const SweepSet* sets, const int* k_begin,
                       int max_per_k, int frames, cbv_sweep_record* rec, int rec_stride, cbv_sweep_summary* sums);
 
+// The PieceDetector settings sweep (cbv_pipeline_piece_sweep, k_piece_sweep.hip).  A setting as the kernels read it: the
+// casts of hough_cfg and the setting's place in the caller's list; the call sorts them so that settings which share the
+// Canny front end, and then the accumulator, follow each other.
+struct PieceSet {
+    float dp;
+    int canny_thr, acc_thr;
+    u32 index;
+    double min_ratio, max_ratio;
+};
+struct PieceChoice; // piece_sweep_core.h
+// LDS bytes of k_piece_sweep_hough for *cfg (maxw, maxh, dp and the ratios set; layout and maxc are filled in):
+// the second pass's layout plus the step table at *off_steps
+size_t piece_sweep_layout(HoughCfg* cfg, int* off_steps);
+// HoughCircles and the pick for every (setting, frame, square): gray / stats = frame 0 of the launch, out[(index *
+// out_frames + frame) * CBV_MAX_SQUARES + square]; cfg.dp = the smallest dp, the ratios = the widest radius span of the sets
+int launch_piece_sweep_hough(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, const cbv_sq_stats* stats,
+                             HoughCfg cfg, const PieceSet* sets, int ns, int frames, PieceChoice* out, int out_frames);
+// decision, history and records of `frames` frames in order: hist[ns][CBV_MAX_SQUARES] and sums[ns] are read and updated,
+// rec (may be null) = [setting][rec_stride], expected (may be null) = [frames]
+int launch_piece_sweep_eval(cbv_ctx* ctx, const SquareDesc* descs, int n, const cbv_sq_stats* stats, const PieceChoice* choices, int choice_frames,
+                            int frames, int ns, const u64* expected, u32* hist, cbv_piece_sweep_record* rec, int rec_stride,
+                            cbv_piece_sweep_summary* sums);
+
 // ---------------------------------------------------------------------------
 // Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline.cpp) shares
 // ---------------------------------------------------------------------------

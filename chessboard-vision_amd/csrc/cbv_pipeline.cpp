@@ -6,6 +6,7 @@
 
 #include "../../include/cbv_chess.h"
 #include "cbv_internal.h"
+#include "piece_sweep_core.h"
 #include "session_core.h"
 
 // One board of a pipeline: what configure's squares part sets up (board_setup).  Board 0 is the pipeline's own; the
@@ -841,6 +842,190 @@ extern "C" int cbv_pipeline_change_hist(cbv_pipeline* p, int calib_slot, int slo
     if (!out) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_change_hist: null argument");
     const cbv_sweep_setting one = {0.0, 1.0, blur_kernel, 0};
     return sweep_run(p, "cbv_pipeline_change_hist", calib_slot, slot, 1, &one, 1, 1, nullptr, nullptr, nullptr, out);
+}
+
+// ---------------------------------------------------------------------------
+// The PieceDetector settings sweep (include/cbv.h, cbv_pipeline_piece_sweep; kernels in k_piece_sweep.hip).  Everything it
+// allocates belongs to the call and is freed when it returns; of the board it reads the gray ring, the square table, the
+// statistics of the slots and slot_blur.
+// ---------------------------------------------------------------------------
+namespace {
+struct PieceSweepCall {
+    DevBuf sets, choices, hist, sums, rec, expected;
+    u8* h_rec = nullptr; // pinned staging of a chunk's records
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    ~PieceSweepCall()
+    {
+        for (DevBuf* b : {&sets, &choices, &hist, &sums, &rec, &expected}) dev_free(b);
+        if (h_rec) (void)hipHostFree(h_rec);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+} // namespace
+
+// `choices_out` != null: cbv_pipeline_piece_detail (one setting, one frame: the circle choices, no evaluation)
+static int piece_sweep_run(cbv_pipeline* p, const char* who, int slot0, int count, const cbv_hough_params* settings, int ns, const uint64_t* expected,
+                           int chunk, cbv_piece_sweep_record* records, cbv_piece_sweep_summary* summary, cbv_piece_sweep_info* info,
+                           PieceChoice* choices_out)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the board is null", who);
+    Pipe& P = *p->pipe;
+    const Board& B = p->b;
+    cbv_ctx* ctx = P.ctx;
+    if (!P.configured) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the pipeline is not configured", who);
+    if (!settings || ns <= 0 || count <= 0 || (!summary && !choices_out)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: no settings, no frames or no summary", who);
+    if (ns > CBV_PIECE_SWEEP_MAX_SETTINGS) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %d settings (at most %d)", who, ns, CBV_PIECE_SWEEP_MAX_SETTINGS);
+    if (chunk < 0 || chunk > CBV_SWEEP_MAX_CHUNK) return cbv_fail(ctx, CBV_ERR_ARG, "%s: chunk_frames %d is outside 0..%d", who, chunk, CBV_SWEEP_MAX_CHUNK);
+    if (slot0 < 0 || slot0 > P.max_frames - count) return cbv_fail(ctx, CBV_ERR_ARG, "%s: slots outside the ring of %d", who, P.max_frames);
+    const int n = B.cfg.n_rois;
+    HoughCfg hc;
+    memset(&hc, 0, sizeof(hc));
+    for (const SquareDesc& d : B.descs) {
+        hc.maxw = std::max(hc.maxw, d.w);
+        hc.maxh = std::max(hc.maxh, d.h);
+    }
+    // the settings as the kernel reads them (the casts of hough_cfg), with the layout's worst case over them
+    std::vector<PieceSet> sets((size_t)ns);
+    for (int i = 0; i < ns; i++) {
+        const cbv_hough_params& s = settings[i];
+        const bool finite = std::isfinite(s.dp) && std::isfinite(s.param1) && std::isfinite(s.param2) && std::isfinite(s.min_radius_ratio) &&
+                            std::isfinite(s.max_radius_ratio);
+        if (!finite || !(s.dp > 0) || !(s.param1 > 0) || !(s.param2 > 0) || !(s.min_radius_ratio >= 0) || !(s.max_radius_ratio >= 0))
+            return cbv_fail(ctx, CBV_ERR_ARG, "%s: setting %d is invalid (dp %g, param1 %g, param2 %g, ratios %g %g)", who, i, s.dp, s.param1, s.param2,
+                            s.min_radius_ratio, s.max_radius_ratio);
+        RC(hough_params_check(ctx, &s));
+        if (s.min_radius_ratio > 1.0 || s.max_radius_ratio > 1.0) // the radius histogram of the layout is sized for radii inside the square
+            return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: setting %d has a radius ratio above 1 (%g, %g)", who, i, s.min_radius_ratio, s.max_radius_ratio);
+        if (s.dp > 16.0) // the narrowest radius span is 2: round(2 / dp * 10) bins must be at least one
+            return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: setting %d has dp %g (at most 16)", who, i, s.dp);
+        PieceSet& t = sets[(size_t)i];
+        t.dp = (float)s.dp < 1.f ? 1.f : (float)s.dp;
+        t.canny_thr = (int)nearbyint(s.param1);
+        t.acc_thr = (int)nearbyint(s.param2);
+        t.index = (u32)i;
+        t.min_ratio = s.min_radius_ratio;
+        t.max_ratio = s.max_radius_ratio;
+        hc.dp = i == 0 ? t.dp : std::min(hc.dp, t.dp);
+    }
+    // The radius histogram of the layout is sized for the widest span any setting can ask of any square: maxRadius is the
+    // square's larger side whenever int(min_dim * max_ratio) is 0 (ratios below 1 / min_dim, the trackbars' first positions),
+    // and min_radius + 2 when it does not exceed the minimum, so with ratios up to 1 the span is at most max(w, h) + 2:
+    // ratios of 0 make hough_layout take that span.
+    hc.min_ratio = hc.max_ratio = 0;
+    {
+        HoughCfg probe = hc;
+        int off = 0;
+        if (hc.maxw < 2 || hc.maxh < 2 || hc.maxw > 250 || hc.maxh > 250 || piece_sweep_layout(&probe, &off) > 150 * 1024)
+            return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: %dx%d squares do not fit the LDS layout of the sweep", who, hc.maxw, hc.maxh);
+    }
+    CBV_ENTER(ctx);
+    for (int i = 0; i < count; i++)
+        if (!B.slot_blur[slot0 + i]) return cbv_fail(ctx, CBV_ERR_STATE, "%s: slot %d was never run", who, slot0 + i);
+    RC(join_scan(P)); // the runs in flight write the gray ring and the statistics
+    // front end shared first (dp, param1), then the accumulator (the integer radii of the first square), then param2
+    const int md0 = std::min(B.descs[0].w, B.descs[0].h);
+    std::stable_sort(sets.begin(), sets.end(), [md0](const PieceSet& a, const PieceSet& b) {
+        if (a.dp != b.dp) return a.dp < b.dp;
+        if (a.canny_thr != b.canny_thr) return a.canny_thr < b.canny_thr;
+        const int a0 = (int)(md0 * a.min_ratio), b0 = (int)(md0 * b.min_ratio), a1 = (int)(md0 * a.max_ratio), b1 = (int)(md0 * b.max_ratio);
+        if (a0 != b0) return a0 < b0;
+        if (a1 != b1) return a1 < b1;
+        if (a.min_ratio != b.min_ratio) return a.min_ratio < b.min_ratio;
+        if (a.max_ratio != b.max_ratio) return a.max_ratio < b.max_ratio;
+        return a.acc_thr < b.acc_thr;
+    });
+    int p1_distinct = 0;
+    for (int i = 0; i < ns; i++)
+        if (i == 0 || sets[i].dp != sets[i - 1].dp || sets[i].canny_thr != sets[i - 1].canny_thr) p1_distinct++;
+    if (chunk == 0) chunk = CBV_SWEEP_DEFAULT_CHUNK;
+    chunk = std::min(chunk, count);
+    const bool eval = choices_out == nullptr;
+    PieceSweepCall S;
+    RC(dev_ensure(ctx, &S.sets, sizeof(PieceSet) * ns));
+    CBV_HIP(ctx, hipMemcpy(S.sets.p, sets.data(), sizeof(PieceSet) * ns, hipMemcpyHostToDevice)); // (pageable sources: copied before the call returns)
+    const size_t choice_bytes = sizeof(PieceChoice) * CBV_MAX_SQUARES * (size_t)ns * chunk;
+    RC(dev_ensure(ctx, &S.choices, choice_bytes));
+    CBV_HIP(ctx, hipMemsetAsync(S.choices.p, 0, choice_bytes, ctx->stream));
+    if (eval) {
+        RC(dev_ensure(ctx, &S.hist, sizeof(u32) * CBV_MAX_SQUARES * ns));
+        CBV_HIP(ctx, hipMemsetAsync(S.hist.p, 0, sizeof(u32) * CBV_MAX_SQUARES * ns, ctx->stream));
+        RC(dev_ensure(ctx, &S.sums, sizeof(cbv_piece_sweep_summary) * ns));
+        CBV_HIP(ctx, hipMemsetAsync(S.sums.p, 0, sizeof(cbv_piece_sweep_summary) * ns, ctx->stream));
+        if (expected) {
+            RC(dev_ensure(ctx, &S.expected, sizeof(u64) * count));
+            CBV_HIP(ctx, hipMemcpy(S.expected.p, expected, sizeof(u64) * count, hipMemcpyHostToDevice));
+        }
+        if (records) {
+            RC(dev_ensure(ctx, &S.rec, sizeof(cbv_piece_sweep_record) * ns * chunk));
+            CBV_HIP(ctx, hipHostMalloc((void**)&S.h_rec, sizeof(cbv_piece_sweep_record) * ns * chunk, hipHostMallocDefault));
+        }
+    }
+    for (hipEvent_t& e : S.ev) CBV_HIP(ctx, hipEventCreate(&e));
+    const SquareDesc* descs = (const SquareDesc*)B.d_descs.p;
+    float ms = 0.f, hough_ms = 0.f, eval_ms = 0.f;
+    for (int c0 = 0; c0 < count; c0 += chunk) {
+        const int cf = std::min(chunk, count - c0);
+        const cbv_sq_stats* stats = (const cbv_sq_stats*)B.d_stats.p + (size_t)n * (slot0 + c0);
+        CBV_HIP(ctx, hipEventRecord(S.ev[0], ctx->stream));
+        RC(launch_piece_sweep_hough(ctx, descs, n, (const u8*)B.d_gray.p + B.plane_total * (slot0 + c0), B.plane_total, stats, hc,
+                                    (const PieceSet*)S.sets.p, ns, cf, (PieceChoice*)S.choices.p, chunk));
+        CBV_HIP(ctx, hipEventRecord(S.ev[1], ctx->stream));
+        if (eval)
+            RC(launch_piece_sweep_eval(ctx, descs, n, stats, (const PieceChoice*)S.choices.p, chunk, cf, ns,
+                                       expected ? (const u64*)S.expected.p + c0 : nullptr, (u32*)S.hist.p, (cbv_piece_sweep_record*)S.rec.p, chunk,
+                                       (cbv_piece_sweep_summary*)S.sums.p));
+        CBV_HIP(ctx, hipEventRecord(S.ev[2], ctx->stream));
+        if (eval && records) CBV_HIP(ctx, hipMemcpyAsync(S.h_rec, S.rec.p, sizeof(cbv_piece_sweep_record) * ns * chunk, hipMemcpyDeviceToHost, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        CBV_HIP(ctx, hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        hough_ms += ms;
+        CBV_HIP(ctx, hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
+        eval_ms += ms;
+        if (eval && records)
+            for (int s = 0; s < ns; s++)
+                memcpy(records + (size_t)s * count + c0, (const cbv_piece_sweep_record*)S.h_rec + (size_t)s * chunk, sizeof(cbv_piece_sweep_record) * cf);
+    }
+    if (eval) CBV_HIP(ctx, hipMemcpy(summary, S.sums.p, sizeof(cbv_piece_sweep_summary) * ns, hipMemcpyDeviceToHost));
+    if (choices_out) CBV_HIP(ctx, hipMemcpy(choices_out, S.choices.p, sizeof(PieceChoice) * CBV_MAX_SQUARES, hipMemcpyDeviceToHost));
+    if (info) {
+        info->hough_ms = hough_ms;
+        info->eval_ms = eval_ms;
+        info->param1_distinct = p1_distinct;
+        info->chunk_frames = chunk;
+    }
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_piece_sweep(cbv_pipeline* p, int slot0, int count, const cbv_hough_params* settings, int ns, const uint64_t* expected,
+                                        int chunk_frames, cbv_piece_sweep_record* records, cbv_piece_sweep_summary* summary,
+                                        cbv_piece_sweep_info* info)
+{
+    return piece_sweep_run(p, "cbv_pipeline_piece_sweep", slot0, count, settings, ns, expected, chunk_frames, records, summary, info, nullptr);
+}
+
+extern "C" int cbv_pipeline_piece_detail(cbv_pipeline* p, int slot, const cbv_hough_params* setting, cbv_piece_result* out)
+{
+    if (!out) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "cbv_pipeline_piece_detail: null argument");
+    PieceChoice ch[CBV_MAX_SQUARES];
+    RC(piece_sweep_run(p, "cbv_pipeline_piece_detail", slot, 1, setting, 1, nullptr, 1, nullptr, nullptr, nullptr, ch));
+    const Board& B = p->b;
+    cbv_ctx* ctx = p->pipe->ctx;
+    const int n = B.cfg.n_rois;
+    std::vector<cbv_sq_stats> st((size_t)n);
+    {
+        CBV_ENTER(ctx);
+        CBV_HIP(ctx, hipMemcpy(st.data(), (const cbv_sq_stats*)B.d_stats.p + (size_t)n * slot, sizeof(cbv_sq_stats) * n, hipMemcpyDeviceToHost));
+    }
+    bool over = false;
+    for (int i = 0; i < n; i++) {
+        memset(&out[i], 0, sizeof(out[i]));
+        piece_decide_choice(&st[(size_t)i], ch[i], B.descs[i].w, B.descs[i].h, &out[i]);
+        out[i].should_process = out[i].evaluated = 1;
+        over = over || (ch[i].flags & CBV_HOUGH_OVERFLOW);
+    }
+    if (over) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "cbv_pipeline_piece_detail: a HoughCircles candidate list overflowed");
+    return CBV_OK;
 }
 
 extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int reset_noise)

@@ -75,6 +75,87 @@ def sensitivity_trackbar_grid():
     return z, iv, k
 
 
+def piece_trackbar_grid():
+    """(min_radius_ratios, max_radius_ratios): every value the MinRadius% (0..50) and MaxRadius% (0..70) trackbars of
+    calibrate_piece_detector.py can produce (:118-121 the ranges, :135 `max(1, v)`, :113-114 `/ 100`), duplicates removed,
+    in trackbar order: 50 and 70 values."""
+    def uniq(values):
+        return list(dict.fromkeys(values))
+    return uniq(max(1, v) / 100 for v in range(51)), uniq(max(1, v) / 100 for v in range(71))
+
+
+# calibrate_piece_detector.py:36-45, the file's keys and the values the tool starts from
+PIECE_FILE_DEFAULTS = {"min_radius": 20, "max_radius": 55, "hough_param1": 100, "hough_param2": 30, "small_min": 12, "small_max": 25,
+                       "knight_aspect_max": 250, "center_diff_thresh": 40}
+
+
+def save_piece_settings(path, min_radius_ratio, max_radius_ratio, **other):
+    """Write the piece_detector_settings.json that calibrate_piece_detector.py saves (:61-66: json, indent 2) and
+    PieceDetector reads at construction (piece_detector.py:52-68): `min_radius` and `max_radius` are integer percent of the
+    square; `other` (hough_param1, hough_param2, small_min, ...) passes through.  An existing file keeps every key that is
+    not given here; a new one starts from the tool's defaults (:36-45).  Returns what was written."""
+    data = dict(PIECE_FILE_DEFAULTS)
+    try:
+        with open(path) as f:
+            data.update(json.load(f))
+    except FileNotFoundError:
+        pass
+    data.update(other)
+    data.update(min_radius=int(round(min_radius_ratio * 100)), max_radius=int(round(max_radius_ratio * 100)))
+    with open(path, "w") as f:
+        json.dump(data, f, indent=2)
+    return data
+
+
+def piece_stats_text(results, sq_size):
+    """The report DetectorCalibrator.export_stats writes to piece_stats.txt (calibrate_piece_detector.py:72-107), as a
+    string: `results` = {(col, row): detect_piece dict} as the tool passes it (`piece_detail`'s dict works: its keys are
+    (file, rank), which the tool's report labels the same way)."""
+    area_square = sq_size ** 2
+    out = [f"=== ESTATISTICAS DE PECAS ({len(results)} casas analisadas) ===\n", f"Square Size: {sq_size}px\n",
+           f"{'CASA':<6} {'STATUS':<10} {'METODO':<15} {'RAIO':<8} {'AREA%':<8} {'BG%':<8} {'CONF'}\n", "-" * 80 + "\n"]
+    count = 0
+    for (col, row), info in results.items():
+        if info["has_piece"]:
+            count += 1
+            coord = f"{chr(ord('a') + col)}{8 - row}"
+            radius = info.get("radius", 0)
+            method = info.get("method", "N/A")
+            conf = info.get("confidence", 0.0)
+            pct_area = (np.pi * (radius ** 2) / area_square) * 100
+            pct_bg = 100 - pct_area
+            out.append(f"{coord:<6} {'PECA':<10} {method:<15} {radius:<8} {pct_area:<8.1f} {pct_bg:<8.1f} {conf:.2%}\n")
+    out.append("-" * 80 + "\n")
+    out.append(f"Total de pecas detectadas: {count}\n")
+    return "".join(out)
+
+
+class PieceSweepResult:
+    """What `piece_sweep` returns.  `settings`: [S] structured array (dp, param1, param2, min_radius_ratio,
+    max_radius_ratio as given).  With records: `raw_occupied`, `stable_occupied`, `hough`, `tower_top`, `center_diff`,
+    `symmetry` (uint64 square sets, bit i = roi i), `n_raw`, `n_stable`, `r_min`, `r_max`, `flags` as [S, F] arrays.
+    `summary`: [S] structured array (frames, frames_exact, missed, false_pos, n_hough, n_tower_top, n_center_diff,
+    n_symmetry, r_min, r_max, n_r, overflow, r_sum).  `info`: dict of the GPU times (ms) of the two kernels, the number of
+    distinct param1 values and the chunk."""
+
+    def __init__(self, settings, records, summary, info, rois_rc):
+        self.settings, self.records, self.summary, self.info, self._rois_rc = settings, records, summary, info, rois_rc
+        if records is not None:
+            for name in records.dtype.names:
+                setattr(self, name, records[name])
+
+    def occupied(self, s, i, stable=True):
+        """{(file, rank)} of setting s on frame i."""
+        if self.records is None:
+            raise RuntimeError("the sweep was made with records=False")
+        return bits_to_positions(int((self.stable_occupied if stable else self.raw_occupied)[s, i]), self._rois_rc)
+
+    def best(self):
+        """Index of the best setting: most frames_exact, then fewest missed + false_pos, then the first."""
+        sm = self.summary
+        return min(range(len(sm)), key=lambda j: (-int(sm["frames_exact"][j]), int(sm["missed"][j]) + int(sm["false_pos"][j]), j))
+
+
 class SweepResult:
     """What `sensitivity_sweep` returns.  `settings`: [S] structured array (z_threshold, initial_variance, blur_kernel as
     given).  With records: `changed`, `parcial`, `total` (uint64 square sets, bit i = roi i), `z_max`, `n_changed`,
@@ -215,6 +296,53 @@ class _BoardMethods:
         self.ctx.check(self.ctx.lib.cbv_pipeline_sweep(self.h_, calib_slot, slot0, count, N.ptr(sets), len(sets), chunk_frames,
                                                        N.ptr(rec) if records else None, N.ptr(summ), info))
         return SweepResult(sets, rec, summ, {name: getattr(info, name) for name, _ in N.SweepInfo._fields_}, self.rois_rc)
+
+    def piece_sweep(self, slot0, count, min_radius_ratios=None, max_radius_ratios=None, param1s=(100,), param2s=(25,),
+                    expected=None, records=True, chunk_frames=16, settings=None):
+        """What calibrate_piece_detector.py shows for many positions of its radius and Hough trackbars at once
+        (include/cbv.h, cbv_pipeline_piece_sweep): every setting on the processed slots slot0 .. slot0 + count - 1, as a
+        fresh PieceDetector with that setting reports them when every square is checked on every frame (raw and smoothed
+        occupancy, methods, radii).  Settings: itertools.product(min_radius_ratios, max_radius_ratios, param1s, param2s), or
+        `settings` = [(min_radius_ratio, max_radius_ratio, param1, param2)].  `expected`: per frame a {(file, rank)} set or a
+        roi bitset, for the summary's frames_exact / missed / false_pos.  The board itself is not touched.  `records=False`
+        returns the per-setting summary only.  Returns a PieceSweepResult."""
+        import itertools
+        if settings is None:
+            if min_radius_ratios is None or max_radius_ratios is None:
+                raise ValueError("piece_sweep: give min_radius_ratios and max_radius_ratios, or settings")
+            settings = list(itertools.product(min_radius_ratios, max_radius_ratios, param1s, param2s))
+        sets = np.zeros(len(settings), N.record_dtype(N.HoughParams))
+        for i, (lo, hi, p1, p2) in enumerate(settings):
+            sets[i] = (1.2, p1, p2, lo, hi)
+        exp = None
+        if expected is not None:
+            if len(expected) != count:
+                raise ValueError("piece_sweep: `expected` needs one entry per frame")
+            roi_of = {(c, 7 - r): i for i, (r, c) in enumerate(self.rois_rc)}
+            exp = np.array([e if isinstance(e, (int, np.integer)) else sum(1 << roi_of[pos] for pos in e) for e in expected], np.uint64)
+        rec = np.zeros((len(sets), count), N.record_dtype(N.PieceSweepRecord)) if records else None
+        summ = np.zeros(len(sets), N.record_dtype(N.PieceSweepSummary))
+        info = N.PieceSweepInfo()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_piece_sweep(self.h_, slot0, count, N.ptr(sets), len(sets), N.ptr(exp) if exp is not None else None,
+                                                             chunk_frames, N.ptr(rec) if records else None, N.ptr(summ), info))
+        return PieceSweepResult(sets, rec, summ, {name: getattr(info, name) for name, _ in N.PieceSweepInfo._fields_}, self.rois_rc)
+
+    def piece_detail(self, slot, min_radius_ratio=_D["min_radius_ratio"], max_radius_ratio=_D["max_radius_ratio"],
+                     param1=_D["hough_param1"], param2=_D["hough_param2"]):
+        """{(file, rank): dict} shaped like detect_all_pieces' results, for one setting on one processed slot: detect_piece
+        of every square (has_piece is the raw value), by the sweep's own kernel (cbv_pipeline_piece_detail)."""
+        out = (N.PieceResult * len(self.rois_rc))()
+        prm = N.HoughParams(1.2, float(param1), float(param2), float(min_radius_ratio), float(max_radius_ratio))
+        self.ctx.check(self.ctx.lib.cbv_pipeline_piece_detail(self.h_, slot, prm, out))
+        res = {}
+        for i, (r, c) in enumerate(self.rois_rc):
+            o = out[i]
+            has = bool(o.has_piece)
+            res[(c, 7 - r)] = {"has_piece": has, "confidence": o.confidence, "center": (o.cx, o.cy) if has else None,
+                               "radius": o.radius if has else None, "method": N.METHOD_NAMES[o.method],
+                               "center_border_diff": o.center_border_diff,
+                               "is_ellipse": False, "axes": None}
+        return res
 
     def change_hist(self, calib_slot, slot, blur_kernel):
         """[n_rois, 256] uint16: per square the histogram of |gray - calibration gray| of a processed slot against

@@ -792,6 +792,76 @@ CBV_API int cbv_session_device_legal_moves(cbv_ctx* ctx, const char* fen, uint16
 /* ... and its time: one launch that builds the list `reps` times, *ms = the launch's GPU time (timing tools) */
 CBV_API int cbv_session_generator_time(cbv_ctx* ctx, const char* fen, int reps, double* ms);
 
+/* ------------------------------------------------------------------ */
+/* PieceDetector radius and Hough settings sweep on the device          */
+/* ------------------------------------------------------------------ */
+/* What calibrate_piece_detector.py shows for a still scene ("Pecas: n/32", the methods, the radii) for many positions of
+ * its MinRadius%, MaxRadius% and Hough trackbars at once, on frames a board has already processed.
+ * DEFINITION: setting s (a cbv_hough_params) on the frames slot0 .. slot0 + count - 1 is what a fresh reference
+ * PieceDetector (history_size 5, min_presence 0.6, circle_threshold 0.6) returns whose min_radius_ratio,
+ * max_radius_ratio, hough_param1 and hough_param2 are s (dp too) when detect_all_pieces(squares_i, use_smoothing=True,
+ * squares_to_check=<all squares>) is called on the frames in order: every square is processed on every frame, so the raw
+ * result of a frame is detect_piece(square) of that frame, the history holds the raw values of the last five frames or
+ * fewer, and has_piece is _get_stable_detection (piece_detector.py:111-122).  Only the HoughCircles step depends on the
+ * setting; the std < 15 gate, the centre-versus-corner difference and the ring symmetry come from the statistics the
+ * board's run left for the slot.  Out of scope: the delta-gated chain per setting (squares_to_check = None keeps the
+ * delta gate on, piece_detector.py:387, so the tool's literal loop is the pipeline's own mode and would need a reference
+ * plane per setting), and visual_changes. */
+typedef struct {              /* one (setting, frame): 56 bytes */
+    uint64_t raw_occupied, stable_occupied;             /* as in cbv_frame_result, bit i = roi i */
+    uint64_t hough, tower_top, center_diff, symmetry;   /* the raw result's method, as square sets */
+    int16_t r_min, r_max;     /* extremes of int(r) over the squares whose method is hough or tower_top, 0 if none */
+    uint8_t n_raw, n_stable;  /* popcounts of raw_occupied and stable_occupied */
+    uint8_t flags;            /* CBV_PIECE_SWEEP_OVERFLOW */
+    uint8_t pad;
+} cbv_piece_sweep_record;
+#define CBV_PIECE_SWEEP_OVERFLOW 1 /* a HoughCircles candidate list of the frame overflowed: the record may be wrong */
+typedef struct {              /* one setting over the call's frames: 56 bytes */
+    uint32_t frames;
+    uint32_t frames_exact;    /* frames with stable_occupied == expected (0 without `expected`) */
+    uint32_t missed;          /* sum of popcount(expected & ~stable_occupied) (0 without `expected`) */
+    uint32_t false_pos;       /* sum of popcount(stable_occupied & ~expected) */
+    uint32_t n_hough, n_tower_top, n_center_diff, n_symmetry; /* sums of the method sets' popcounts */
+    int32_t r_min, r_max;     /* over every (frame, square) with a circle, 0 if none */
+    uint32_t n_r;             /* how many of those */
+    uint32_t overflow;        /* (frame, square) pairs whose candidate list overflowed */
+    uint64_t r_sum;           /* sum of int(r) over them */
+} cbv_piece_sweep_summary;
+typedef struct { float hough_ms, eval_ms; int32_t param1_distinct, chunk_frames; } cbv_piece_sweep_info;
+#define CBV_PIECE_SWEEP_MAX_SETTINGS 65536
+/* Any board handle.  Reads the board's gray ring (the PieceDetector's 5 x 5 planes), its square table and the statistics of
+ * the slots; writes nothing of the board's, and a pipeline that never calls this launches and allocates nothing for it.
+ * Waits for the runs in flight and returns when `records` ([ns][count], setting major; may be NULL) and `summary` ([ns]) are
+ * filled; `expected` (may be NULL) = one occupancy set per frame for frames_exact / missed / false_pos; `info` (may be
+ * NULL) gets the GPU time of the two kernels (event pairs: k_piece_sweep_hough, k_piece_sweep_eval), the number of distinct
+ * param1 values and the chunk used.  Frames are processed in chunks of `chunk_frames` (0 = CBV_SWEEP_DEFAULT_CHUNK, at most
+ * CBV_SWEEP_MAX_CHUNK): the call's own device memory is ns x chunk x 64 x 8 bytes of circle choices, ns x 128 bytes of
+ * history and summaries, the sorted settings and, with `records`, ns x chunk x 56 bytes of staging, all freed before the call
+ * returns.  The result does not depend on the chunk or on the order of the settings.  HoughCircles keeps as many
+ * accumulator maxima per square as the pipeline's second pass does (fewer where the sweep's own LDS table needs the room);
+ * there is no retry: an overflow sets CBV_PIECE_SWEEP_OVERFLOW and counts in `overflow`.
+ * CBV_ERR_STATE: not configured, or a slot that was never run.  CBV_ERR_ARG: null or empty arguments, slots outside the
+ * ring, chunk_frames outside 0..CBV_SWEEP_MAX_CHUNK, ns above CBV_PIECE_SWEEP_MAX_SETTINGS, a ratio that is negative or
+ * not finite, or dp, param1 or param2 not above 0 (or not finite).  CBV_ERR_UNSUPPORTED: squares that do not fit the
+ * kernel's LDS layout, a radius ratio above 1 (the trackbars end at 0.5 and 0.7), or dp above 16.  After any error nothing
+ * has changed. */
+CBV_API int cbv_pipeline_piece_sweep(cbv_pipeline* board, int slot0, int count, const cbv_hough_params* settings, int ns,
+                                     const uint64_t* expected, int chunk_frames, cbv_piece_sweep_record* records,
+                                     cbv_piece_sweep_summary* summary, cbv_piece_sweep_info* info);
+/* detect_piece's dict of every square for ONE (setting, frame), by the sweep's own HoughCircles kernel with ns = 1 and
+ * count = 1: out[n_rois] with has_piece (raw), method, centre, radius, confidence and center_border_diff; changed = 0,
+ * should_process = evaluated = 1.  Errors as cbv_pipeline_piece_sweep; CBV_ERR_UNSUPPORTED (with `out` filled) when a
+ * candidate list overflowed. */
+CBV_API int cbv_pipeline_piece_detail(cbv_pipeline* board, int slot, const cbv_hough_params* setting, cbv_piece_result* out);
+/* The host twin of k_piece_sweep_eval, no GPU: stats[frames][n] (n <= CBV_MAX_SQUARES), ws[n] / hs[n] the squares' sizes,
+ * choices[ns][frames][n] the circle of every (setting, frame, square) as k_piece_sweep_hough leaves it, 8 bytes each:
+ * kind (0 none, 1 hough, 2 tower_top), flags (CBV_HOUGH_OVERFLOW), int16 int(r), int16 int(cx), int16 int(cy).  The frames
+ * are walked in order from an empty history.  expected[frames] may be NULL; records [ns][frames] may be NULL;
+ * summary [ns].  0, or CBV_ERR_ARG. */
+CBV_API int cbv_piece_sweep_eval_host(const cbv_sq_stats* stats, const int32_t* ws, const int32_t* hs, int n, int frames,
+                                      const void* choices, int ns, const uint64_t* expected, cbv_piece_sweep_record* records,
+                                      cbv_piece_sweep_summary* summary);
+
 #ifdef __cplusplus
 }
 #endif
