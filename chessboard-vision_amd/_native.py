@@ -251,12 +251,19 @@ SESSION_EVENTS = 64
 
 
 class RawFrame(C.Structure):
-    """cbv_raw_frame: one camera-native frame in host memory."""
-    _fields_ = [("fmt", C.c_int32), ("stride0", C.c_int32), ("stride1", C.c_int32), ("plane0", C.c_void_p), ("plane1", C.c_void_p)]
+    """cbv_raw_frame: one camera-native frame in host memory (stride2 / plane2: the three-plane formats only)."""
+    _fields_ = [("fmt", C.c_int32), ("stride0", C.c_int32), ("stride1", C.c_int32), ("stride2", C.c_int32), ("plane0", C.c_void_p),
+                ("plane1", C.c_void_p), ("plane2", C.c_void_p)]
 
 
+# The ids are bit fields (include/cbv.h): low nibble 1 = 4:2:0, 2 = packed 4:2:2; 0x10 = V before U; 0x20 = planar chroma
+# (4:2:0) or chroma-first bytes (4:2:2).  The three-plane format is "yuv420p", libav's name: "i420" is NOT a name here.
 FMT_BGR, FMT_NV12, FMT_YUYV = 0, 1, 2
-FORMATS = {"bgr": FMT_BGR, "nv12": FMT_NV12, "yuyv": FMT_YUYV}
+FMT_NV21, FMT_YUV420P, FMT_YV12, FMT_YVYU, FMT_UYVY = 0x11, 0x21, 0x31, 0x12, 0x22
+FORMATS = {"bgr": FMT_BGR, "nv12": FMT_NV12, "yuyv": FMT_YUYV, "nv21": FMT_NV21, "yuv420p": FMT_YUV420P, "yv12": FMT_YV12,
+           "yvyu": FMT_YVYU, "uyvy": FMT_UYVY}
+FORMATS_420 = ("nv12", "nv21", "yuv420p", "yv12")      # ring slots [h * 3 // 2, w]
+FORMATS_422 = ("yuyv", "yvyu", "uyvy")                 # ring slots [h, w, 2]
 
 KERNEL_IDS = ["COLOR_LAB_HIST", "CLAHE_LUT", "CLAHE_APPLY", "BILATERAL", "SHARPEN", "NORM_LUT", "NORMALIZE", "WARP",
               "SQUARES", "GRAY_BLUR", "OTSU", "THRESHOLD", "SCAN", "SYNTH", "RESET", "HOUGH", "INGEST"]
@@ -478,7 +485,8 @@ def as_bgr(frame):
 
 
 def format_id(fmt):
-    """CBV_FMT_* of "bgr" | "nv12" | "yuyv"."""
+    """CBV_FMT_* of "bgr" | "nv12" | "nv21" | "yuv420p" | "yv12" | "yuyv" | "yvyu" | "uyvy".  The three-plane 4:2:0 format goes
+    by libav's name, "yuv420p" (cv2's COLOR_YUV2BGR_I420 / _IYUV); "i420" is an unknown format and raises ValueError."""
     try:
         return FORMATS[fmt.lower()]
     except (KeyError, AttributeError):
@@ -496,38 +504,78 @@ def _rows(a, what):
 
 
 def raw_frame(frame, fmt):
-    """(RawFrame, w, h, arrays the struct points into) of a camera-native frame.  "nv12": one [h * 3 // 2, w] array or a
-    (y [h, w], uv [h // 2, w] or [h // 2, w // 2, 2]) pair; "yuyv": [h, w, 2]; "bgr": [h, w, 3].  Row strides are free."""
+    """(RawFrame, w, h, arrays the struct points into) of a camera-native frame.  Row strides are free unless stated.
+    "nv12" / "nv21": one [h * 3 // 2, w] array or a (y [h, w], chroma [h // 2, w] or [h // 2, w // 2, 2]) pair.
+    "yuv420p" / "yv12": one [h * 3 // 2, w] array, cv2's single-matrix layout with the planes back to back (a strided one is
+    made contiguous first), or a triple of planes in the format's memory order, (y, u, v) for yuv420p and (y, v, u) for
+    yv12, of shapes [h, w], [h // 2, w // 2], [h // 2, w // 2].  ("i420" is not a name: see format_id.)
+    "yuyv" / "yvyu" / "uyvy": [h, w, 2].  "bgr": [h, w, 3].
+    ValueError for other shapes and dtypes, an odd w, and an odd h of a 4:2:0 format."""
     f = format_id(fmt)
+    name = fmt.upper()
+    odd_ok = f in (FMT_NV12, FMT_YUYV)   # these two leave odd sizes to the library's own check (a RuntimeError), as they always did
     r = RawFrame()
     r.fmt = f
     if f == FMT_BGR:
         a = as_bgr(frame)
         r.stride0, r.plane0 = a.strides[0], a.ctypes.data
         return r, a.shape[1], a.shape[0], (a,)
-    if f == FMT_YUYV:
-        a = np.asarray(frame)
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 2:
-            raise ValueError("expected a uint8 HxWx2 YUYV frame, got %s %s" % (a.dtype, a.shape))
+    if f & 15 == FMT_YUYV:
+        a = np.asarray(frame) if not isinstance(frame, (tuple, list)) else None
+        if a is None or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 2:
+            raise ValueError("expected a uint8 HxWx2 %s frame, got %s" % (name, _describe(frame)))
+        if not odd_ok and a.shape[1] % 2:
+            raise ValueError("a %s frame has an even width, got %s" % (name, a.shape))
         if a.strides[2] != 1 or a.strides[1] != 2 or a.strides[0] < a.shape[1] * 2:
             a = np.ascontiguousarray(a)
         r.stride0, r.plane0 = a.strides[0], a.ctypes.data
         return r, a.shape[1], a.shape[0], (a,)
+    planar = bool(f & 0x20)
+    if isinstance(frame, (tuple, list)) and planar:
+        if len(frame) != 3:
+            raise ValueError("a %s frame is one array or three planes, got %d" % (name, len(frame)))
+        y, c1, c2 = (_rows(p, "a %s plane" % name) for p in frame)
+        h, w = y.shape
+        if h % 2 or w % 2 or c1.shape != (h // 2, w // 2) or c2.shape != c1.shape:
+            raise ValueError("%s planes do not fit: luma %s, chroma %s and %s" % (name, y.shape, c1.shape, c2.shape))
+        r.stride0, r.plane0, r.stride1, r.plane1, r.stride2, r.plane2 = (y.strides[0], y.ctypes.data, c1.strides[0], c1.ctypes.data,
+                                                                         c2.strides[0], c2.ctypes.data)
+        return r, w, h, (y, c1, c2)
     if isinstance(frame, (tuple, list)):
+        if len(frame) != 2:
+            raise ValueError("a %s frame is one array or a (luma, chroma) pair, got %d planes" % (name, len(frame)))
         y, uv = frame
         uv = np.asarray(uv)
-        if uv.ndim == 3 and uv.shape[2] == 2 and uv.strides[2] == 1 and uv.strides[1] == 2:  # [h/2, w/2, 2] view of the U V rows
+        if uv.ndim == 3 and uv.shape[2] == 2 and uv.strides[2] == 1 and uv.strides[1] == 2:  # [h/2, w/2, 2] view of the chroma rows
             uv = np.lib.stride_tricks.as_strided(uv, shape=(uv.shape[0], uv.shape[1] * 2), strides=(uv.strides[0], 1))
         elif uv.ndim == 3 and uv.shape[2] == 2:
             uv = np.ascontiguousarray(uv).reshape(uv.shape[0], uv.shape[1] * 2)
         y, uv = _rows(y, "the luma plane"), _rows(uv, "the chroma plane")
-        if y.shape[0] % 2 or uv.shape != (y.shape[0] // 2, y.shape[1]):
-            raise ValueError("NV12 planes do not fit: luma %s, chroma %s" % (y.shape, uv.shape))
+        if y.shape[0] % 2 or uv.shape != (y.shape[0] // 2, y.shape[1]) or (not odd_ok and y.shape[1] % 2):
+            raise ValueError("%s planes do not fit: luma %s, chroma %s" % (name, y.shape, uv.shape))
     else:
-        a = _rows(frame, "an NV12 frame")
+        a = _rows(frame, "the %s frame" % name)
         if a.shape[0] % 3:
-            raise ValueError("an NV12 frame has h * 3 // 2 rows, got %d" % a.shape[0])
+            raise ValueError("the [h * 3 // 2, w] array of a %s frame has a multiple of 3 rows, got %s" % (name, a.shape))
         h = a.shape[0] // 3 * 2
+        if not odd_ok and (h % 2 or a.shape[1] % 2):
+            raise ValueError("a %s frame has an even width and height, got %s" % (name, a.shape))
+        if planar:
+            w = a.shape[1]
+            if a.strides[0] != w:  # the chroma planes are rows of w // 2 bytes back to back: only a contiguous array holds them
+                a = np.ascontiguousarray(a)
+            y = a[:h]
+            c1 = np.ndarray((h // 2, w // 2), np.uint8, a, offset=h * w)
+            c2 = np.ndarray((h // 2, w // 2), np.uint8, a, offset=h * w + (h // 2) * (w // 2))
+            r.stride0, r.plane0, r.stride1, r.plane1, r.stride2, r.plane2 = w, y.ctypes.data, w // 2, c1.ctypes.data, w // 2, c2.ctypes.data
+            return r, w, h, (a, y, c1, c2)
         y, uv = a[:h], a[h:]
     r.stride0, r.plane0, r.stride1, r.plane1 = y.strides[0], y.ctypes.data, uv.strides[0], uv.ctypes.data
     return r, y.shape[1], y.shape[0], (y, uv)
+
+
+def _describe(frame):
+    if isinstance(frame, (tuple, list)):
+        return "%d planes" % len(frame)
+    a = np.asarray(frame)
+    return "%s %s" % (a.dtype, a.shape)

@@ -59,14 +59,16 @@ def warp_image(img, points, display_size=(1280, 720), margin=100):
 
 
 def yuv_to_bgr(frame, fmt):
-    """cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_YUY2) on the GPU (include/cbv.h, cbv_yuv_to_bgr): a new
-    uint8 [h, w, 3] array.  `fmt` "nv12": one [h * 3 // 2, w] array or a (y, uv) pair of planes; "yuyv": [h, w, 2].
-    Strided views are taken as they are.  (A BoardPipeline takes such frames directly: upload(fmt=...),
-    set_input_format.)"""
+    """cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12 / _YUY2 / _YVYU / _UYVY) on the GPU (include/cbv.h,
+    cbv_yuv_to_bgr): a new uint8 [h, w, 3] array.  `fmt` "nv12" / "nv21": one [h * 3 // 2, w] array or a (y, chroma) pair of
+    planes; "yuv420p" / "yv12": one contiguous [h * 3 // 2, w] array or the three planes in memory order, (y, u, v) /
+    (y, v, u); "yuyv" / "yvyu" / "uyvy": [h, w, 2].  cv2's I420 goes by libav's name "yuv420p"; "i420" is an unknown
+    format (ValueError).  Strided views are taken as they are (_native.raw_frame).  (A BoardPipeline takes such frames
+    directly: upload(fmt=...), set_input_format.)"""
     from . import _native as N
     raw, w, h, keep = N.raw_frame(frame, fmt)
     if raw.fmt == N.FMT_BGR:
-        raise ValueError("yuv_to_bgr converts \"nv12\" or \"yuyv\" frames")
+        raise ValueError("yuv_to_bgr converts YUV frames (%s)" % ", ".join(k for k in N.FORMATS if k != "bgr"))
     ctx = N.context()
     out = np.empty((h, w, 3), np.uint8)
     ctx.check(ctx.lib.cbv_yuv_to_bgr(ctx.h, raw, w, h, N.ptr(out), w * 3))

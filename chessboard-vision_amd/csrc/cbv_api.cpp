@@ -748,7 +748,7 @@ extern "C" int cbv_warp_perspective(cbv_ctx* ctx, const uint8_t* bgr, int w, int
 }
 
 // ---------------------------------------------------------------------------
-// camera-native frames (NV12, YUYV): cv2.cvtColor(COLOR_YUV2BGR_NV12 / _YUY2) on the device
+// camera-native frames (include/cbv.h, CBV_FMT_*): cv2.cvtColor(COLOR_YUV2BGR_*) on the device
 // ---------------------------------------------------------------------------
 // The rows of one plane into the staging buffer.  Tight rows, and rows with a dword-multiple stride of at most twice their
 // length, travel as they lie (padding included) in ONE linear copy and keep their stride on the device: k_ingest takes
@@ -762,26 +762,43 @@ static int plane_h2d(cbv_ctx* ctx, u8* dst, const u8* src, int stride, int wbyte
     return CBV_OK;
 }
 
+// the planes and strides of a host frame that its format has (plane2 / stride2 are not read for the other formats: a
+// caller may have been built against the struct that ended with plane1)
+void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides)
+{
+    const int n = raw_fmt_planes(raw->fmt);
+    planes[0] = raw->plane0, strides[0] = raw->stride0;
+    planes[1] = n > 1 ? raw->plane1 : nullptr, strides[1] = n > 1 ? raw->stride1 : 0;
+    planes[2] = n > 2 ? raw->plane2 : nullptr, strides[2] = n > 2 ? raw->stride2 : 0;
+}
+
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what)
 {
     RC(check_raw_format(ctx, raw->fmt, w, h, what));
-    const bool nv12 = raw->fmt == CBV_FMT_NV12;
-    const int wb0 = nv12 ? w : 2 * w;
-    if (!raw->plane0 || raw->stride0 < wb0 || (nv12 && (!raw->plane1 || raw->stride1 < w)))
-        return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes or strides of the raw frame (stride0=%d stride1=%d)", what, raw->stride0, raw->stride1);
+    const u8* planes[3];
+    int strides[3];
+    raw_frame_planes(raw, planes, strides);
+    RC(check_raw_planes(ctx, raw->fmt, w, planes, strides, what));
     if ((size_t)w * h > (size_t)1 << 28) return cbv_fail(ctx, CBV_ERR_ARG, "%s: image too large", what);
-    // plane 1 follows plane 0's largest possible device copy (rows of twice their length), on a 256-byte boundary
-    const size_t off1 = ((size_t)2 * wb0 * h + 255) & ~(size_t)255, total = off1 + (nv12 ? (size_t)w * h : 0);
+    // a plane follows the largest possible device copy of the one before (rows of twice their length), on a 256-byte boundary
+    const int np = raw_fmt_planes(raw->fmt);
+    size_t off[4] = {0, 0, 0, 0};
+    for (int i = 0; i < np; i++)
+        off[i + 1] = (off[i] + (size_t)2 * raw_plane_wbytes(raw->fmt, w, i) * raw_plane_rows(raw->fmt, h, i) + 255) & ~(size_t)255;
+    const size_t total = off[np];
     RC(dev_ensure(ctx, &ctx->in, total + 256));
     if (ctx->debug_poison) CBV_HIP(ctx, hipMemsetAsync(ctx->in.p, 0xA5, total, ctx->stream));
-    RawGeom r;
+    RawGeom r = {};
     r.fmt = raw->fmt;
-    r.stride1 = 0;
-    r.frame_stride = 0;
     u8* st = (u8*)ctx->in.p;
-    RC(plane_h2d(ctx, st, raw->plane0, raw->stride0, wb0, h, &r.stride0));
-    if (nv12) RC(plane_h2d(ctx, st + off1, raw->plane1, raw->stride1, w, h / 2, &r.stride1));
-    return launch_ingest(ctx, st, nv12 ? st + off1 : nullptr, r, dst, g, 1);
+    RawPlanes dev = {{nullptr, nullptr, nullptr}};
+    int dev_stride[3] = {0, 0, 0};
+    for (int i = 0; i < np; i++) {
+        RC(plane_h2d(ctx, st + off[i], planes[i], strides[i], raw_plane_wbytes(raw->fmt, w, i), raw_plane_rows(raw->fmt, h, i), &dev_stride[i]));
+        dev.p[i] = st + off[i];
+    }
+    r.stride0 = dev_stride[0], r.stride1 = dev_stride[1], r.stride2 = dev_stride[2];
+    return launch_ingest(ctx, dev, r, dst, g, 1);
 }
 
 extern "C" int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride)

@@ -334,33 +334,81 @@ int launch_synth(cbv_ctx* ctx, u8* dst, Geom g, const u64* seeds_dev, const doub
 
 // Raw (camera-native) frames of a batch for k_ingest: plane pointers are those of frame 0, frames `frame_stride` bytes apart
 struct RawGeom {
-    int fmt;              // CBV_FMT_NV12 or CBV_FMT_YUYV
-    int stride0, stride1; // bytes per row of the luma (or YUYV) plane / of NV12's chroma plane
+    int fmt;                       // CBV_FMT_* of a YUV format
+    int stride0, stride1, stride2; // bytes per row of plane 0 (luma, or the packed 4:2:2 bytes) / plane 1 / plane 2, in memory order
     size_t frame_stride;
 };
-// tightly packed raw frames, each frame rounded to 256 bytes (the ingest rings); fmt BGR: tight_geom's frame_stride
-static inline size_t raw_frame_bytes(int fmt, int w, int h) { return fmt == CBV_FMT_NV12 ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_YUYV ? 2 : 3); }
+// the bit fields of a format id (include/cbv.h)
+static inline bool raw_fmt_known(int fmt)
+{
+    return fmt == CBV_FMT_NV12 || fmt == CBV_FMT_NV21 || fmt == CBV_FMT_YUV420P || fmt == CBV_FMT_YV12 || fmt == CBV_FMT_YUYV ||
+           fmt == CBV_FMT_YVYU || fmt == CBV_FMT_UYVY;
+}
+static inline bool raw_fmt_420(int fmt) { return (fmt & 15) == CBV_FMT_NV12; }
+static inline int raw_fmt_planes(int fmt) { return !raw_fmt_420(fmt) ? 1 : (fmt & 0x20) ? 3 : 2; }
+static inline const char* raw_fmt_name(int fmt)
+{
+    switch (fmt) {
+    case CBV_FMT_NV12: return "NV12";
+    case CBV_FMT_NV21: return "NV21";
+    case CBV_FMT_YUV420P: return "YUV420P";
+    case CBV_FMT_YV12: return "YV12";
+    case CBV_FMT_YUYV: return "YUYV";
+    case CBV_FMT_YVYU: return "YVYU";
+    case CBV_FMT_UYVY: return "UYVY";
+    }
+    return "?";
+}
+// bytes per row of plane `i` of a w-wide frame (0: the format has no such plane)
+static inline int raw_plane_wbytes(int fmt, int w, int i)
+{
+    if (i == 0) return raw_fmt_420(fmt) ? w : 2 * w;
+    return i >= raw_fmt_planes(fmt) ? 0 : raw_fmt_planes(fmt) == 3 ? w / 2 : w;
+}
+static inline int raw_plane_rows(int fmt, int h, int i) { return i == 0 ? h : h / 2; }
+// tightly packed raw frames, planes back to back, each frame rounded to 256 bytes (the ingest rings); fmt BGR: tight_geom's frame_stride
+static inline size_t raw_frame_bytes(int fmt, int w, int h) { return raw_fmt_420(fmt) ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_BGR ? 3 : 2); }
 static inline RawGeom tight_raw_geom(int fmt, int w, int h)
 {
     RawGeom r;
     r.fmt = fmt;
-    r.stride0 = fmt == CBV_FMT_YUYV ? 2 * w : w;
-    r.stride1 = fmt == CBV_FMT_NV12 ? w : 0;
+    r.stride0 = raw_plane_wbytes(fmt, w, 0);
+    r.stride1 = raw_plane_wbytes(fmt, w, 1);
+    r.stride2 = raw_plane_wbytes(fmt, w, 2);
     r.frame_stride = (raw_frame_bytes(fmt, w, h) + 255) & ~(size_t)255;
     return r;
 }
-// CBV_ERR_ARG unless fmt is a YUV format and w (and h, for NV12) is even
+// the planes of a tightly packed frame (tight_raw_geom) that starts at `base`; null for the planes the format lacks
+struct RawPlanes {
+    const u8* p[3];
+};
+static inline RawPlanes tight_raw_planes(int fmt, int w, int h, const u8* base)
+{
+    RawPlanes r = {{base, nullptr, nullptr}};
+    const int n = raw_fmt_planes(fmt);
+    if (n > 1) r.p[1] = base + (size_t)w * h;
+    if (n > 2) r.p[2] = r.p[1] + (size_t)(w / 2) * (h / 2);
+    return r;
+}
+// CBV_ERR_ARG unless fmt is a YUV format and w (and h, for the 4:2:0 formats) is even
 int check_raw_format(cbv_ctx* ctx, int fmt, int w, int h, const char* what);
-// cv2.cvtColor COLOR_YUV2BGR_NV12 / _YUY2 of `batch` raw frames into BGR frames of geometry g (k_ingest.hip)
-int launch_ingest(cbv_ctx* ctx, const u8* plane0, const u8* plane1, RawGeom r, u8* dst, Geom g, int batch);
-// one raw host frame (NV12 / YUYV, strided views) through the context's staging buffer into a BGR device image
+// CBV_ERR_ARG unless every plane the format has is there with rows of at least their length
+int check_raw_planes(cbv_ctx* ctx, int fmt, int w, const u8* const* planes, const int* strides, const char* what);
+// YV12 -> YUV420P with the chroma planes (and their strides) swapped: the kernels have no YV12 form
+void raw_planes_canonical(RawPlanes* planes, RawGeom* r);
+// cv2.cvtColor COLOR_YUV2BGR_* of `batch` raw frames into BGR frames of geometry g (k_ingest.hip); planes in memory order
+int launch_ingest(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, int batch);
+// the planes and strides a host frame's format has; null / 0 for the rest, whose fields are not read
+void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides);
+// one raw host frame (any YUV format, strided views) through the context's staging buffer into a BGR device image
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
 // launch_warp on raw frames (k_warp_yuv): the output of launch_ingest followed by launch_warp without a byte map, byte for
 // byte, with no BGR frame in between; g = the frames' width and height.  Interior pixels load both taps of a row at once:
-// 4 bytes at the even column of an NV12 chroma row, 8 bytes at the first tap's pair of a YUYV row, which at sx = w - 2 reach
-// 2 / 4 bytes past the row's w (2 w) bytes.  Callers keep >= 8 readable bytes behind the last row of the last plane of the
-// last frame (the pipeline's raw ring has 256); between rows and frames the bytes read belong to the next row or frame.
-int launch_warp_yuv(cbv_ctx* ctx, const u8* plane0, const u8* plane1, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180,
+// 4 bytes at the even column of an NV12 / NV21 chroma row, 8 bytes at the first tap's pair of a packed 4:2:2 row, 2 bytes at
+// column sx >> 1 of each planar chroma row, which at sx = w - 2 reach 2 / 4 / 1 bytes past the row's w (2 w, w / 2) bytes.
+// Callers keep >= 8 readable bytes behind the last row of the last plane of the last frame (the pipeline's raw ring has
+// 256); between rows, planes and frames the bytes read belong to the next row, plane or frame.
+int launch_warp_yuv(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180,
                     u8* dst, int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 
 void build_gaussian_q8_sigma(int k, double sigma, int* coef);
@@ -571,7 +619,7 @@ void hough_board_cfgs(HoughCfg base, HoughCfg out[2], size_t lds[2]);
 // one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0
 int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, NormSrc norm, int batch,
                    u32* zero_word, u32* zero_word2);
-int launch_warp_yuv_mb(cbv_ctx* ctx, const u8* plane0, const u8* plane1, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
+int launch_warp_yuv_mb(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
                        int batch, u32* zero_word, u32* zero_word2);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,

@@ -1047,6 +1047,12 @@ extern "C" int cbv_pipeline_update_references(cbv_pipeline* p, int slot, int res
 static const char* const kRawModeMsg = "the pipeline runs without enhancement on a YUV input format (raw mode): its frames are the raw "
                                        "ring, written by cbv_pipeline_upload_raw or cbv_pipeline_submit in that format";
 
+// the planes of slot `slot` of the device ring of raw frames
+static RawPlanes slot_planes(const Pipe& P, int slot)
+{
+    return tight_raw_planes(P.in_fmt, P.w, P.h, P.raw_ring + tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride * slot);
+}
+
 // the device ring of raw frames in the current (YUV) input format
 static int ensure_raw_ring(Pipe& P)
 {
@@ -1087,16 +1093,16 @@ extern "C" int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_
     if (P.raw_mode()) { // the frame as it is into its slot of the raw ring, rows packed
         if (raw->fmt != P.in_fmt)
             return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: format %d, but %s (format %d)", raw->fmt, kRawModeMsg, P.in_fmt);
-        const bool nv12 = raw->fmt == CBV_FMT_NV12;
-        const int wb0 = nv12 ? P.w : 2 * P.w;
-        if (!raw->plane0 || raw->stride0 < wb0 || (nv12 && (!raw->plane1 || raw->stride1 < P.w)))
-            return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_upload_raw: bad planes or strides of the raw frame (stride0=%d stride1=%d)", raw->stride0, raw->stride1);
+        const u8* planes[3];
+        int strides[3];
+        raw_frame_planes(raw, planes, strides);
+        RC(check_raw_planes(ctx, raw->fmt, P.w, planes, strides, "cbv_pipeline_upload_raw"));
         RC(ensure_raw_ring(P));
         // the raw ring is the only frame store here: a copy of this slot that cbv_pipeline_submit left in flight lands first
         if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
-        u8* dst = P.raw_ring + tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride * slot;
-        RC(rows_h2d(ctx, dst, raw->plane0, raw->stride0, wb0, P.h));
-        if (nv12) RC(rows_h2d(ctx, dst + (size_t)P.w * P.h, raw->plane1, raw->stride1, P.w, P.h / 2));
+        const RawPlanes dst = slot_planes(P, slot);
+        for (int i = 0; i < raw_fmt_planes(raw->fmt); i++)
+            RC(rows_h2d(ctx, (u8*)dst.p[i], planes[i], strides[i], raw_plane_wbytes(raw->fmt, P.w, i), raw_plane_rows(raw->fmt, P.h, i)));
         CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return CBV_OK;
     }
@@ -1194,9 +1200,7 @@ extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
         if (read_ev) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, read_ev, 0));
         hipStream_t caller = ctx->stream;
         ctx->stream = P.copy_stream;
-        const int rc = P.raw_mode() ? CBV_OK
-                                    : launch_ingest(ctx, raw, P.in_fmt == CBV_FMT_NV12 ? raw + (size_t)P.w * P.h : nullptr, rg,
-                                                    P.frames + P.g.frame_stride * slot0, P.g, count);
+        const int rc = P.raw_mode() ? CBV_OK : launch_ingest(ctx, slot_planes(P, slot0), rg, P.frames + P.g.frame_stride * slot0, P.g, count);
         ctx->stream = caller;
         RC(rc);
     }
@@ -1263,16 +1267,16 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
 {
     cbv_ctx* ctx = P.ctx;
     RawGeom rg = {};
-    const u8 *raw0 = nullptr, *raw1 = nullptr; // raw mode: the chunk's luma (or YUYV) plane and NV12's chroma plane
+    RawPlanes raw = {{nullptr, nullptr, nullptr}}; // raw mode: the planes of the chunk's first slot
     if (!res) {
         rg = tight_raw_geom(P.in_fmt, P.w, P.h);
-        raw0 = P.raw_ring + rg.frame_stride * s0;
-        if (P.in_fmt == CBV_FMT_NV12) raw1 = raw0 + (size_t)P.w * P.h;
+        raw = slot_planes(P, s0);
     }
+    const u8* raw0 = raw.p[0];
     if (P.boards.size() > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         const int nb = (int)P.boards.size();
-        if (raw0) RC(launch_warp_yuv_mb(ctx, raw0, raw1, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
+        if (raw0) RC(launch_warp_yuv_mb(ctx, raw, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
         else RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
         if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, s0, b, P.max_px));
@@ -1284,7 +1288,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     u8* gray = T.gray + T.plane_total * s0;
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
     cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
-    if (raw0) RC(launch_warp_yuv(ctx, raw0, raw1, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
+    if (raw0) RC(launch_warp_yuv(ctx, raw, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
     else RC(launch_warp(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, norm, b, work, retry0));
     RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
                                  T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));
@@ -1636,9 +1640,8 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
             if (!P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: no raw frame was ever uploaded or submitted");
             if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // submitted copies of the slot
             const RawGeom rg = tight_raw_geom(P.in_fmt, P.w, P.h);
-            const u8* raw = P.raw_ring + rg.frame_stride * slot;
             RC(dev_ensure(ctx, &ctx->a, P.g.frame_stride + 256));
-            RC(launch_ingest(ctx, raw, P.in_fmt == CBV_FMT_NV12 ? raw + (size_t)P.w * P.h : nullptr, rg, (u8*)ctx->a.p, P.g, 1));
+            RC(launch_ingest(ctx, slot_planes(P, slot), rg, (u8*)ctx->a.p, P.g, 1));
             src = (const u8*)ctx->a.p;
         }
     } else if (which == 1) {

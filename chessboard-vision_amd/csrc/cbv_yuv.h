@@ -1,12 +1,23 @@
-// One YUV pixel to BGR: cv2.cvtColor's COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_YUY2 arithmetic on 8-bit data (include/cbv.h),
-// the ONE definition behind k_ingest (whole frames) and k_warp_yuv (the four taps of a warped pixel).
+// One YUV pixel to BGR: cv2.cvtColor's COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12 / _YUY2 / _YVYU / _UYVY arithmetic on 8-bit
+// data (include/cbv.h), the ONE definition behind k_ingest (whole frames) and k_warp_yuv (the four taps of a warped pixel),
+// and where the bytes of each layout lie.
 #pragma once
 #include "cbv_device.h"
 
 // round(c * 2^20) of 1.164, 2.018, -0.391, -0.813, 1.596
 enum { YUV_SHIFT = 20, YUV_CY = 1220542, YUV_CUB = 2116026, YUV_CUG = -409993, YUV_CVG = -852492, YUV_CVR = 1673527 };
 
-// The chroma part of the three sums, rounding constant included: shared by the pixels of a 2x2 block (NV12) or a pair (YUYV).
+// Where a format's bytes lie, from the bit fields of its id (include/cbv.h), as compile-time constants of the kernels' bodies.
+// YV12 has no entry of its own: it is YUV420P with the two chroma planes swapped by the host.
+template <int FMT>
+struct YuvLay {
+    static constexpr bool F420 = (FMT & 15) == CBV_FMT_NV12, VU = (FMT & 0x10) != 0, ALT = (FMT & 0x20) != 0;
+    static constexpr bool PLANAR = F420 && ALT;
+    static constexpr int CU = VU ? 1 : 0, CV = 1 - CU;                                                      // NV12 / NV21: byte of U, V in a chroma pair
+    static constexpr int Y0 = ALT ? 1 : 0, Y1 = Y0 + 2, PU = (ALT ? 0 : 1) + (VU ? 2 : 0), PV = PU ^ 2; // packed 4:2:2: bytes of a pair's dword
+};
+
+// The chroma part of the three sums, rounding constant included: shared by the pixels of a 2x2 block (4:2:0) or a pair (4:2:2).
 // Everything stays inside signed 32 bits: the luma term is at most (255 - 16) * 1220542 = 291 709 538, the rounding
 // constant 524 288, and the chroma terms are at most 128 * 2116026 = 270 851 328 (B), 128 * (852492 + 409993) =
 // 161 598 080 (G) and 128 * 1673527 = 214 211 456 (R) in magnitude: |sum| <= 563 085 154 < 2^31.

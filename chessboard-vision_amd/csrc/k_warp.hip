@@ -164,7 +164,7 @@ __device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, co
 }
 
 // ---------------------------------------------------------------------------
-// The warp straight from camera-native frames (pipelines without enhancement whose input format is NV12 or YUYV): the
+// The warp straight from camera-native frames (pipelines without enhancement whose input format is a YUV format): the
 // BGR frame k_ingest would write is never made.  The conversion is pointwise (a pixel takes the chroma of its 2x2 block
 // or pair, nothing is interpolated), so converting the four taps and blending them is, bit for bit, sampling the
 // converted frame: same coordinates (warp_taps), same conversion (d_yuv_bgr), same blend (warp_blend).  A tap outside
@@ -172,27 +172,42 @@ __device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, co
 // ---------------------------------------------------------------------------
 // pixel (x, y) of one raw frame with byte loads (the taps of pixels on the frame's border)
 template <int FMT>
-__device__ __forceinline__ u32 d_raw_px(const u8* __restrict__ f0, const u8* __restrict__ f1, const RawGeom& r, int x, int y)
+__device__ __forceinline__ u32 d_raw_px(const u8* __restrict__ f0, const u8* __restrict__ f1, const u8* __restrict__ f2, const RawGeom& r, int x,
+                                        int y)
 {
-    if (FMT == CBV_FMT_NV12) {
+    typedef YuvLay<FMT> L;
+    if (L::PLANAR)
+        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x],
+                         d_chroma(f1[(size_t)(y >> 1) * r.stride1 + (x >> 1)], f2[(size_t)(y >> 1) * r.stride2 + (x >> 1)]));
+    if (L::F420) {
         const u8* c = f1 + (size_t)(y >> 1) * r.stride1 + (x & ~1);
-        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x], d_chroma(c[0], c[1]));
+        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x], d_chroma(c[L::CU], c[L::CV]));
     }
     const u8* s = f0 + (size_t)y * r.stride0 + (size_t)(x >> 1) * 4;
-    return d_yuv_bgr(s[(x & 1) * 2], d_chroma(s[1], s[3]));
+    return d_yuv_bgr(s[L::Y0 + (x & 1) * 2], d_chroma(s[L::PU], s[L::PV]));
 }
 
-// Interior pixels, per frame and row of taps.  NV12: one 2-byte load holds both luma samples and one 4-byte load at the
-// even column holds U V of the first tap's pair and of the next pair, which is the second tap's when sx is odd (when sx is
-// even both taps share the first); the rows share the chroma row when sy is even.  YUYV: one 8-byte load at the first tap's
-// pair, Y0 U Y1 V | Y2 U Y3 V, holds both taps and their chroma for either parity.  The bytes read past the second tap's
-// pair (sx even) stay inside the buffer: the ring keeps 256 bytes of slack behind the last frame.
+// the chroma of byte pair `p` of an NV12 (U V) / NV21 (V U) row
+template <int FMT>
+__device__ __forceinline__ Chroma d_chroma_pair(u32 p)
+{
+    return d_chroma((p >> (8 * YuvLay<FMT>::CU)) & 255, (p >> (8 * YuvLay<FMT>::CV)) & 255);
+}
+
+// Interior pixels, per frame and row of taps.  NV12 / NV21: one 2-byte load holds both luma samples and one 4-byte load at
+// the even column holds the chroma of the first tap's pair and of the next pair, which is the second tap's when sx is odd
+// (when sx is even both taps share the first); the rows share the chroma row when sy is even.  Planar chroma (YUV420P; YV12
+// arrives with p1 and p2 swapped): the same 2-byte luma load, and per chroma row one 2-byte load of U and one of V at column
+// sx >> 1, which hold the first tap's sample and the next, the second tap's when sx is odd.  Packed 4:2:2: one 8-byte load
+// at the first tap's pair, e.g. Y0 U Y1 V | Y2 U Y3 V, holds both taps and their chroma for either parity.  The bytes read
+// past the second tap's pair (sx even) stay inside the buffer: the ring keeps 256 bytes of slack behind the last frame.
 template <int FMT, int FPT>
-__device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u8* __restrict__ p1, RawGeom r, int sw, int sh,
-                                              const double* __restrict__ M, int dw, int dh, int bw0, int rot180, u8* __restrict__ dst,
+__device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw,
+                                              int sh, const double* __restrict__ M, int dw, int dh, int bw0, int rot180, u8* __restrict__ dst,
                                               int dst_stride, size_t dst_frame_stride, u32* __restrict__ zero_word,
                                               u32* __restrict__ zero_word2, int batch, int bz)
 {
+    typedef YuvLay<FMT> L;
     warp_zero_words(zero_word, zero_word2);
     const int f0 = bz * FPT;
     const int nf = min(FPT, batch - f0);
@@ -201,28 +216,45 @@ __device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u
     if (dx >= dw || dy >= dh) return;
     const WarpTaps t = warp_taps(dx, dy, sw, sh, M, dw, dh, bw0, rot180, dst_stride);
     const bool odd = t.sx & 1;
-    constexpr bool NV12 = FMT == CBV_FMT_NV12;
-    const bool two_crows = NV12 && (t.sy & 1); // the rows of taps lie in different chroma rows
+    constexpr bool NV12 = L::F420 && !L::PLANAR, PLANAR = L::PLANAR;
+    const bool two_crows = L::F420 && (t.sy & 1); // the rows of taps lie in different chroma rows
     // (offsets are only used where the taps are inside)
-    const size_t l_off = NV12 ? (size_t)t.sy * r.stride0 + (size_t)t.sx : (size_t)t.sy * r.stride0 + (size_t)(t.sx >> 1) * 4;
-    const size_t c_off = (size_t)(t.sy >> 1) * r.stride1 + (size_t)(t.sx & ~1);
-    u64 la[FPT], lb[FPT]; // NV12: 2 luma bytes; YUYV: the 8 bytes of two pairs
-    u32 ca[FPT], cb[FPT]; // NV12: U V U V
+    const size_t l_off = L::F420 ? (size_t)t.sy * r.stride0 + (size_t)t.sx : (size_t)t.sy * r.stride0 + (size_t)(t.sx >> 1) * 4;
+    const size_t c_off = (size_t)(t.sy >> 1) * r.stride1 + (size_t)(PLANAR ? t.sx >> 1 : t.sx & ~1);
+    const size_t c2_off = (size_t)(t.sy >> 1) * r.stride2 + (size_t)(t.sx >> 1);
+    u64 la[FPT], lb[FPT]; // 4:2:0: 2 luma bytes; 4:2:2: the 8 bytes of two pairs
+    u32 ca[FPT], cb[FPT]; // NV12: U V U V; planar: U U
+    u32 va[FPT], vb[FPT]; // planar: V V
     if (t.interior)
 #pragma unroll
         for (int k = 0; k < FPT; k++)
             if (k < nf) {
                 const u8* l = p0 + (size_t)(f0 + k) * r.frame_stride + l_off;
-                if (NV12) {
+                if (L::F420) {
                     u16 a, b;
                     __builtin_memcpy(&a, l, 2);
                     __builtin_memcpy(&b, l + r.stride0, 2);
                     la[k] = a;
                     lb[k] = b;
                     const u8* c = p1 + (size_t)(f0 + k) * r.frame_stride + c_off;
-                    __builtin_memcpy(&ca[k], c, 4);
-                    cb[k] = ca[k];
-                    if (two_crows) __builtin_memcpy(&cb[k], c + r.stride1, 4);
+                    if (NV12) {
+                        __builtin_memcpy(&ca[k], c, 4);
+                        cb[k] = ca[k];
+                        if (two_crows) __builtin_memcpy(&cb[k], c + r.stride1, 4);
+                    } else {
+                        const u8* c2 = p2 + (size_t)(f0 + k) * r.frame_stride + c2_off;
+                        u16 u, v;
+                        __builtin_memcpy(&u, c, 2);
+                        __builtin_memcpy(&v, c2, 2);
+                        ca[k] = cb[k] = u;
+                        va[k] = vb[k] = v;
+                        if (two_crows) {
+                            __builtin_memcpy(&u, c + r.stride1, 2);
+                            __builtin_memcpy(&v, c2 + r.stride2, 2);
+                            cb[k] = u;
+                            vb[k] = v;
+                        }
+                    }
                 } else {
                     __builtin_memcpy(&la[k], l, 8);
                     __builtin_memcpy(&lb[k], l + r.stride0, 8);
@@ -235,14 +267,30 @@ __device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u
         if (t.any_in) {
             u32 q[4] = {0u, 0u, 0u, 0u}; // taps 00, 01, 10, 11 as b | g << 8 | r << 16; border taps are 0
             if (t.interior) {
-                if (NV12) {
-                    const u32 a = ca[k], sa = odd ? a >> 16 : a;
-                    const Chroma a0 = d_chroma(a & 255, (a >> 8) & 255), a1 = d_chroma(sa & 255, (sa >> 8) & 255);
-                    Chroma b0 = a0, b1 = a1;
-                    if (two_crows) {
-                        const u32 b = cb[k], sb = odd ? b >> 16 : b;
-                        b0 = d_chroma(b & 255, (b >> 8) & 255);
-                        b1 = d_chroma(sb & 255, (sb >> 8) & 255);
+                if (L::F420) {
+                    Chroma a0, a1, b0, b1;
+                    if (NV12) {
+                        const u32 a = ca[k], sa = odd ? a >> 16 : a;
+                        a0 = d_chroma_pair<FMT>(a);
+                        a1 = d_chroma_pair<FMT>(sa);
+                        b0 = a0;
+                        b1 = a1;
+                        if (two_crows) {
+                            const u32 b = cb[k], sb = odd ? b >> 16 : b;
+                            b0 = d_chroma_pair<FMT>(b);
+                            b1 = d_chroma_pair<FMT>(sb);
+                        }
+                    } else {
+                        const u32 u = ca[k], v = va[k];
+                        a0 = d_chroma(u & 255, v & 255);
+                        a1 = d_chroma((odd ? u >> 8 : u) & 255, (odd ? v >> 8 : v) & 255);
+                        b0 = a0;
+                        b1 = a1;
+                        if (two_crows) {
+                            const u32 u1 = cb[k], v1 = vb[k];
+                            b0 = d_chroma(u1 & 255, v1 & 255);
+                            b1 = d_chroma((odd ? u1 >> 8 : u1) & 255, (odd ? v1 >> 8 : v1) & 255);
+                        }
                     }
                     q[0] = d_yuv_bgr((int)(la[k] & 255), a0);
                     q[1] = d_yuv_bgr((int)((la[k] >> 8) & 255), a1);
@@ -253,18 +301,20 @@ __device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u
                     for (int row = 0; row < 2; row++) {
                         const u64 w = row ? lb[k] : la[k];
                         const u32 lo = (u32)w, hi = (u32)(w >> 32), s1 = odd ? hi : lo;
-                        const Chroma c0 = d_chroma((lo >> 8) & 255, lo >> 24), c1 = d_chroma((s1 >> 8) & 255, s1 >> 24);
-                        q[2 * row] = d_yuv_bgr((int)((odd ? lo >> 16 : lo) & 255), c0);
-                        q[2 * row + 1] = d_yuv_bgr((int)((odd ? hi : lo >> 16) & 255), c1);
+                        const Chroma c0 = d_chroma((lo >> (8 * L::PU)) & 255, (lo >> (8 * L::PV)) & 255);
+                        const Chroma c1 = d_chroma((s1 >> (8 * L::PU)) & 255, (s1 >> (8 * L::PV)) & 255);
+                        q[2 * row] = d_yuv_bgr((int)((odd ? lo >> (8 * L::Y1) : lo >> (8 * L::Y0)) & 255), c0);
+                        q[2 * row + 1] = d_yuv_bgr((int)((odd ? hi >> (8 * L::Y0) : lo >> (8 * L::Y1)) & 255), c1);
                     }
                 }
             } else {
                 const u8* f0p = p0 + (size_t)(f0 + k) * r.frame_stride;
-                const u8* f1p = NV12 ? p1 + (size_t)(f0 + k) * r.frame_stride : nullptr;
-                if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, r, t.sx, t.sy);
-                if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, r, t.sx + 1, t.sy);
-                if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, r, t.sx, t.sy + 1);
-                if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, r, t.sx + 1, t.sy + 1);
+                const u8* f1p = L::F420 ? p1 + (size_t)(f0 + k) * r.frame_stride : nullptr;
+                const u8* f2p = PLANAR ? p2 + (size_t)(f0 + k) * r.frame_stride : nullptr;
+                if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx, t.sy);
+                if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx + 1, t.sy);
+                if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx, t.sy + 1);
+                if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx + 1, t.sy + 1);
             }
 #pragma unroll
             for (int c = 0; c < 3; c++)
@@ -279,24 +329,24 @@ __device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u
 }
 
 template <int FMT, int FPT>
-__global__ __launch_bounds__(256) void k_warp_yuv(const u8* __restrict__ p0, const u8* __restrict__ p1, RawGeom r, int sw, int sh, WarpM M,
+__global__ __launch_bounds__(256) void k_warp_yuv(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw, int sh, WarpM M,
                                                    int dw, int dh, int bw0, int rot180, u8* __restrict__ dst, int dst_stride,
                                                    size_t dst_frame_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
 {
-    warp_yuv_body<FMT, FPT>(p0, p1, r, sw, sh, M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch,
+    warp_yuv_body<FMT, FPT>(p0, p1, p2, r, sw, sh, M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch,
                             blockIdx.z);
 }
 
 // every board of a pipeline in one launch, as k_warp_mb
 template <int FMT, int FPT>
-__global__ __launch_bounds__(256) void k_warp_yuv_mb(const u8* __restrict__ p0, const u8* __restrict__ p1, RawGeom r, int sw, int sh,
+__global__ __launch_bounds__(256) void k_warp_yuv_mb(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw, int sh,
                                                       const BoardDev* __restrict__ tab, int nz, int s0, u32* __restrict__ zero_word,
                                                       u32* __restrict__ zero_word2, int batch)
 {
     const int b = blockIdx.z / nz;
     const BoardDev& T = tab[b];
     if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
-    warp_yuv_body<FMT, FPT>(p0, p1, r, sw, sh, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3,
+    warp_yuv_body<FMT, FPT>(p0, p1, p2, r, sw, sh, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3,
                             T.warped_stride, zero_word, zero_word2, batch, blockIdx.z - b * nz);
 }
 
@@ -393,21 +443,33 @@ int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw
     return CBV_OK;
 }
 
-// the raw planes a fused warp may read: what launch_ingest asks of them
-static int check_warp_yuv(cbv_ctx* ctx, const u8* p0, const u8* p1, RawGeom r, Geom g, int batch)
+// the raw planes a fused warp may read: what launch_ingest asks of them (YV12 leaves as YUV420P)
+static int check_warp_yuv(cbv_ctx* ctx, RawPlanes* pl, RawGeom* r, Geom g, int batch)
 {
-    RC(check_raw_format(ctx, r.fmt, g.w, g.h, "launch_warp_yuv"));
-    const bool nv12 = r.fmt == CBV_FMT_NV12;
-    if (batch <= 0 || !p0 || (nv12 && !p1) || r.stride0 < (nv12 ? g.w : 2 * g.w) || (nv12 && r.stride1 < g.w))
-        return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_yuv: bad planes or strides");
+    RC(check_raw_format(ctx, r->fmt, g.w, g.h, "launch_warp_yuv"));
+    if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_yuv: bad planes or strides");
+    const int strides[3] = {r->stride0, r->stride1, r->stride2};
+    RC(check_raw_planes(ctx, r->fmt, g.w, pl->p, strides, "launch_warp_yuv"));
+    raw_planes_canonical(pl, r);
     return CBV_OK;
 }
 
+// one case per layout the kernels have a form for, both frames-per-thread counts each
+#define CBV_WARP_YUV_FORMATS(LAUNCH)                   \
+    switch (r.fmt) {                                   \
+    case CBV_FMT_NV12: LAUNCH(CBV_FMT_NV12); break;    \
+    case CBV_FMT_NV21: LAUNCH(CBV_FMT_NV21); break;    \
+    case CBV_FMT_YUYV: LAUNCH(CBV_FMT_YUYV); break;    \
+    case CBV_FMT_YVYU: LAUNCH(CBV_FMT_YVYU); break;    \
+    case CBV_FMT_UYVY: LAUNCH(CBV_FMT_UYVY); break;    \
+    default: LAUNCH(CBV_FMT_YUV420P);                  \
+    }
+
 // as launch_warp: four frames per thread in batched launches, one thread per pixel and frame in a launch of a frame or two
-int launch_warp_yuv(cbv_ctx* ctx, const u8* p0, const u8* p1, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
-                    int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2)
+int launch_warp_yuv(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
+                    size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2)
 {
-    RC(check_warp_yuv(ctx, p0, p1, r, g, batch));
+    RC(check_warp_yuv(ctx, &pl, &r, g, batch));
     WarpM M;
     for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
     int bw0, bh0;
@@ -415,39 +477,36 @@ int launch_warp_yuv(cbv_ctx* ctx, const u8* p0, const u8* p1, RawGeom r, Geom g,
     const int fpt = batch >= 8 ? 4 : 1;
     const dim3 grid((dw + 63) / 64, (dh + 3) / 4, (batch + fpt - 1) / fpt);
     prof_begin(ctx, CBV_K_WARP_YUV);
-#define CBV_WARP_YUV(FMT, FPT)                                                                                                        \
-    hipLaunchKernelGGL((k_warp_yuv<FMT, FPT>), grid, dim3(256), 0, ctx->stream, p0, p1, r, g.w, g.h, M, dw, dh, bw0, rot180, dst, dst_stride, \
-                       dst_frame_stride, zero_word, zero_word2, batch)
-    if (r.fmt == CBV_FMT_NV12) {
-        if (fpt == 4) CBV_WARP_YUV(CBV_FMT_NV12, 4);
-        else CBV_WARP_YUV(CBV_FMT_NV12, 1);
-    } else {
-        if (fpt == 4) CBV_WARP_YUV(CBV_FMT_YUYV, 4);
-        else CBV_WARP_YUV(CBV_FMT_YUYV, 1);
-    }
+#define CBV_WARP_YUV_K(FMT, FPT)                                                                                                          \
+    hipLaunchKernelGGL((k_warp_yuv<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], pl.p[1], pl.p[2], r, g.w, g.h, M, dw, dh, bw0, rot180, \
+                       dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch)
+#define CBV_WARP_YUV(FMT)             \
+    if (fpt == 4) CBV_WARP_YUV_K(FMT, 4); \
+    else CBV_WARP_YUV_K(FMT, 1)
+    CBV_WARP_YUV_FORMATS(CBV_WARP_YUV)
 #undef CBV_WARP_YUV
+#undef CBV_WARP_YUV_K
     prof_end(ctx, CBV_K_WARP_YUV);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }
 
-int launch_warp_yuv_mb(cbv_ctx* ctx, const u8* p0, const u8* p1, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0, int batch,
-                       u32* zero_word, u32* zero_word2)
+int launch_warp_yuv_mb(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word,
+                       u32* zero_word2)
 {
-    RC(check_warp_yuv(ctx, p0, p1, r, g, batch));
+    RC(check_warp_yuv(ctx, &pl, &r, g, batch));
     const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
     const dim3 grid((maxS + 63) / 64, (maxS + 3) / 4, nz * nb);
     prof_begin(ctx, CBV_K_WARP_YUV);
-#define CBV_WARP_YUV_MB(FMT, FPT)                                                                                                     \
-    hipLaunchKernelGGL((k_warp_yuv_mb<FMT, FPT>), grid, dim3(256), 0, ctx->stream, p0, p1, r, g.w, g.h, tab, nz, s0, zero_word, zero_word2, batch)
-    if (r.fmt == CBV_FMT_NV12) {
-        if (fpt == 4) CBV_WARP_YUV_MB(CBV_FMT_NV12, 4);
-        else CBV_WARP_YUV_MB(CBV_FMT_NV12, 1);
-    } else {
-        if (fpt == 4) CBV_WARP_YUV_MB(CBV_FMT_YUYV, 4);
-        else CBV_WARP_YUV_MB(CBV_FMT_YUYV, 1);
-    }
+#define CBV_WARP_YUV_MB_K(FMT, FPT)                                                                                                        \
+    hipLaunchKernelGGL((k_warp_yuv_mb<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], pl.p[1], pl.p[2], r, g.w, g.h, tab, nz, s0, zero_word, \
+                       zero_word2, batch)
+#define CBV_WARP_YUV_MB(FMT)             \
+    if (fpt == 4) CBV_WARP_YUV_MB_K(FMT, 4); \
+    else CBV_WARP_YUV_MB_K(FMT, 1)
+    CBV_WARP_YUV_FORMATS(CBV_WARP_YUV_MB)
 #undef CBV_WARP_YUV_MB
+#undef CBV_WARP_YUV_MB_K
     prof_end(ctx, CBV_K_WARP_YUV);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;

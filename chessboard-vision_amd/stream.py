@@ -617,9 +617,11 @@ class BoardPipeline(_BoardMethods):
         return self.ctx.lib.cbv_pipeline_frames_dev(self.h_)
 
     def upload(self, slot, frame, fmt="bgr"):
-        """One frame into a slot, synchronous.  `fmt` "nv12" (one [h * 3 // 2, w] array or a (y, uv) pair of possibly
-        strided views) and "yuyv" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h, cbv_pipeline_upload_raw); in
-        raw mode (`configure(enhance=False)` with a YUV `set_input_format`) the frame is stored as it is."""
+        """One frame into a slot, synchronous.  `fmt` "nv12" / "nv21" (one [h * 3 // 2, w] array or a (y, chroma) pair of
+        possibly strided views), "yuv420p" / "yv12" (one contiguous [h * 3 // 2, w] array or the three planes in memory
+        order, (y, u, v) / (y, v, u)) and "yuyv" / "yvyu" / "uyvy" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h,
+        cbv_pipeline_upload_raw; "i420" is not a name, the format is "yuv420p"); in raw mode (`configure(enhance=False)` with
+        a YUV `set_input_format`) the frame is stored as it is."""
         if N.format_id(fmt) == N.FMT_BGR:
             f = N.as_bgr(frame)
             assert f.shape[:2] == (self.h, self.w)
@@ -631,16 +633,17 @@ class BoardPipeline(_BoardMethods):
         self.ctx.check(self.ctx.lib.cbv_pipeline_upload_raw(self.h_, slot, raw))
 
     def set_input_format(self, fmt):
-        """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12" or "yuyv".  Raw
-        frames cross PCIe as they are and are converted to BGR on the GPU behind their copy.  The ring is freed here and
+        """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12", "nv21", "yuv420p"
+        (cv2's I420; "i420" itself is an unknown format), "yv12", "yuyv", "yvyu" or "uyvy".  Raw frames cross PCIe as they are and are converted to BGR on the GPU behind their copy.  The ring is freed here and
         allocated again by the next `host_ring()`: an array that call returned earlier must not be touched any more."""
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt)))
         self.input_format = fmt.lower()
 
     def host_ring(self):
         """Pinned host mirror of the frame ring as a numpy array: the capture side writes frames here, `submit` copies
-        them to the GPU asynchronously.  [max_frames, h, w, 3] for BGR, [max_frames, h * 3 // 2, w] for NV12 (luma rows,
-        then the U V rows), [max_frames, h, w, 2] for YUYV (`set_input_format`)."""
+        them to the GPU asynchronously.  [max_frames, h, w, 3] for BGR; [max_frames, h * 3 // 2, w] for the 4:2:0 layouts
+        (luma rows, then the chroma rows of NV12 / NV21, or the two chroma planes of yuv420p / yv12 back to back, each
+        h // 2 rows of w // 2 bytes); [max_frames, h, w, 2] for YUYV, YVYU and UYVY (`set_input_format`)."""
         ptr = self.ctx.lib.cbv_pipeline_host_ring(self.h_)
         if not ptr:
             raise RuntimeError(self.ctx.lib.cbv_last_error(self.ctx.h).decode())
@@ -648,8 +651,12 @@ class BoardPipeline(_BoardMethods):
         buf = (C.c_uint8 * (fs * self.max_frames)).from_address(ptr)
         flat = np.frombuffer(buf, dtype=np.uint8)
         w, h = self.w, self.h
-        shape, strides = {"bgr": ((h, w, 3), (w * 3, 3, 1)), "nv12": ((h * 3 // 2, w), (w, 1)),
-                          "yuyv": ((h, w, 2), (w * 2, 2, 1))}[self.input_format]
+        if self.input_format == "bgr":
+            shape, strides = (h, w, 3), (w * 3, 3, 1)
+        elif self.input_format in N.FORMATS_420:
+            shape, strides = (h * 3 // 2, w), (w, 1)
+        else:
+            shape, strides = (h, w, 2), (w * 2, 2, 1)
         return np.lib.stride_tricks.as_strided(flat, shape=(self.max_frames,) + shape, strides=(fs,) + strides)
 
     def submit(self, slot0, count):

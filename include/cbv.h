@@ -466,31 +466,50 @@ CBV_API int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats* o
 CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out);
 
 /* ------------------------------------------------------------------ */
-/* camera-native frames: NV12 and YUYV, converted to BGR on the device */
+/* camera-native frames (NV12, NV21, yuv420p, YV12, YUYV, YVYU, UYVY), converted to BGR on the device */
 /* ------------------------------------------------------------------ */
-/* Cameras deliver YUYV and decoders NV12; cv2.VideoCapture converts them to BGR on a host core before the application
- * sees a frame.  Here the raw frame crosses PCIe (2 or 1.5 bytes per pixel instead of 3) and one kernel writes BGR into
- * the pipeline's frame ring, so everything downstream is unchanged.  The conversion is cv2.cvtColor's
- * COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_YUY2 on 8-bit data: BT.601, limited range, fixed point with 20 fraction bits, no
- * chroma interpolation (a pixel takes the U, V of its 2x2 block or of its horizontal pair).  With
+/* Cameras deliver YUYV / UYVY / YVYU, hardware decoders NV12 / NV21 and software decoders yuv420p / YV12;
+ * cv2.VideoCapture converts them to BGR on a host core before the application sees a frame.  Here the raw frame crosses
+ * PCIe (2 or 1.5 bytes per pixel instead of 3) and one kernel writes BGR into the pipeline's frame ring, so everything
+ * downstream is unchanged.  The conversion is cv2.cvtColor's COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12 / _YUY2 / _YVYU /
+ * _UYVY on 8-bit data: BT.601, limited range, fixed point with 20 fraction bits, no chroma interpolation (a pixel takes
+ * the U, V of its 2x2 block or of its horizontal pair).  With
  * y = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128, h = 1 << 19, in signed 32-bit arithmetic:
  *     B = sat_u8((y + h + 2116026 * u) >> 20)
  *     G = sat_u8((y + h -  852492 * v - 409993 * u) >> 20)
  *     R = sat_u8((y + h + 1673527 * v) >> 20)
- * Layouts.  NV12: h rows of w luma bytes (plane0), then h / 2 rows of w bytes U V U V ... (plane1); w and h even.
- * YUYV (YUY2): h rows of 2 w bytes Y0 U Y1 V (plane0); w even. */
-#define CBV_FMT_BGR  0
-#define CBV_FMT_NV12 1
-#define CBV_FMT_YUYV 2
+ * Only where the bytes lie differs between the layouts.
+ * 4:2:0 (w and h even), plane0 = h rows of w luma bytes, then
+ *     NV12:    plane1 = h / 2 rows of w bytes U V U V ...
+ *     NV21:    plane1 = h / 2 rows of w bytes V U V U ...
+ *     YUV420P: plane1 = U, h / 2 rows of w / 2 bytes; plane2 = V, the same shape   (I420 / IYUV)
+ *     YV12:    as YUV420P with V in plane1 and U in plane2
+ * packed 4:2:2 (w even), plane0 = h rows of 2 w bytes
+ *     YUYV (YUY2): Y0 U Y1 V      YVYU: Y0 V Y1 U      UYVY: U Y0 V Y1
+ * The ids are bit fields: the low nibble is the family (1 = 4:2:0, 2 = packed 4:2:2), 0x10 = V comes before U, 0x20 =
+ * planar chroma (4:2:0) or chroma-first bytes (4:2:2).  Every id not listed here is refused. */
+#define CBV_FMT_BGR     0
+#define CBV_FMT_NV12    1
+#define CBV_FMT_YUYV    2
+#define CBV_FMT_NV21    0x11
+#define CBV_FMT_YUV420P 0x21
+#define CBV_FMT_YV12    0x31
+#define CBV_FMT_YVYU    0x12
+#define CBV_FMT_UYVY    0x22
 
-typedef struct {            /* one raw frame in host memory */
+/* One raw frame in host memory.  stride2 and plane2 are read only for the three-plane formats (YUV420P, YV12): stride2
+ * lies in what was padding and plane2 behind what was the end of the struct, so a caller built against the 32-byte struct
+ * of the two-plane formats keeps working. */
+typedef struct {
     int32_t fmt;            /* CBV_FMT_* */
     int32_t stride0, stride1;   /* bytes per row of plane0 / plane1 */
-    const uint8_t* plane0;  /* BGR, YUYV, or the NV12 luma plane */
-    const uint8_t* plane1;  /* NV12 chroma plane, else NULL */
+    int32_t stride2;        /* bytes per row of plane2 */
+    const uint8_t* plane0;  /* BGR, the packed 4:2:2 bytes, or the luma plane */
+    const uint8_t* plane1;  /* NV12 / NV21 chroma plane, YUV420P's U or YV12's V plane, else NULL */
+    const uint8_t* plane2;  /* YUV420P's V or YV12's U plane */
 } cbv_raw_frame;
 
-/* host in, host out: the cvtColor call on its own (fmt = CBV_FMT_NV12 or CBV_FMT_YUYV) */
+/* host in, host out: the cvtColor call on its own (fmt = any CBV_FMT_* but BGR) */
 CBV_API int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride);
 /* one frame of any format into a slot of the frame ring, synchronous, like cbv_pipeline_upload */
 CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_frame* raw);
@@ -500,7 +519,7 @@ CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_fra
  * to 256 bytes: cbv_pipeline_host_slot_bytes).  With a YUV format cbv_pipeline_submit copies the raw slots to a device
  * ring of the same layout and converts them into the BGR frame ring behind the copy; its ordering promises are the
  * same (a run of the slots waits for the copy and its conversion).  On the pipeline only (a board handle:
- * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, or odd h with NV12, and then nothing has changed.
+ * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, or odd h with a 4:2:0 format, and then nothing has changed.
  * Raw mode: on a pipeline configured with skip_enhance a YUV format makes the raw ring THE frames.  cbv_pipeline_submit
  * only copies the raw slots, cbv_pipeline_upload_raw (that format only) writes a raw slot, cbv_pipeline_run warps straight
  * from the raw frames (k_warp_yuv: byte for byte what the conversion followed by the warp gives) and no BGR frame is ever

@@ -4,7 +4,7 @@ overlapped rates per input format, all from one process:
 
     python tools/ingest_timing.py --format all --reps 3
 
-With "nv12" / "yuyv" the ring holds raw frames (BoardPipeline.set_input_format) and a submit is the copy plus the
+With a YUV format ("nv12", "nv21", "yuv420p", "yv12", "yuyv", "yvyu", "uyvy") the ring holds raw frames (BoardPipeline.set_input_format) and a submit is the copy plus the
 conversion kernel; "H2D only" then includes that kernel.  `--reps` alternates the formats and prints every repetition
 and, for each format, the ratio to BGR of the same repetition."""
 import argparse
@@ -14,14 +14,15 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
+from chessboard_vision_amd import _native as N  # noqa: E402
 from chessboard_vision_amd import synth as S  # noqa: E402
 from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--format", default="bgr", choices=["bgr", "nv12", "yuyv", "all"])
+ap.add_argument("--format", default="bgr", choices=list(N.FORMATS) + ["all"])
 ap.add_argument("--reps", type=int, default=1)
 args = ap.parse_args()
-formats = ["bgr", "nv12", "yuyv"] if args.format == "all" else [args.format]
+formats = list(N.FORMATS) if args.format == "all" else [args.format]
 
 W, H, HALF, ROUNDS = 1920, 1080, 128, 6
 n = 2 * HALF
@@ -38,10 +39,14 @@ def to_raw(f, fmt):
     b, g, r = (f[..., i].astype(np.float32) for i in range(3))
     q = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
     y, u, v = q(16 + 0.257 * r + 0.504 * g + 0.098 * b), q(128 - 0.148 * r - 0.291 * g + 0.439 * b), q(128 + 0.439 * r - 0.368 * g - 0.071 * b)
-    if fmt == "nv12":
-        return np.concatenate([y, np.stack([u[::2, ::2], v[::2, ::2]], axis=-1).reshape(H // 2, W)])
+    if fmt in N.FORMATS_420:
+        c = (u[::2, ::2], v[::2, ::2]) if fmt in ("nv12", "yuv420p") else (v[::2, ::2], u[::2, ::2])
+        chroma = np.stack(c, axis=-1) if fmt in ("nv12", "nv21") else np.stack(c)  # interleaved pairs, or one plane after the other
+        return np.concatenate([y, chroma.reshape(H // 2, W)])
+    first, second = (u[:, ::2], v[:, ::2]) if fmt != "yvyu" else (v[:, ::2], u[:, ::2])
     out = np.empty((H, W, 2), np.uint8)
-    out[..., 0], out[:, 0::2, 1], out[:, 1::2, 1] = y, u[:, ::2], v[:, ::2]
+    yb, cb = (1, 0) if fmt == "uyvy" else (0, 1)   # UYVY carries the chroma byte first
+    out[..., yb], out[:, 0::2, cb], out[:, 1::2, cb] = y, first, second
     return out
 
 

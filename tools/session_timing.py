@@ -1,15 +1,15 @@
 """What the session chain (BoardPipeline.configure(enhance=False)) and the warp from raw frames (k_warp_yuv) are worth.
 Prints ONE JSON object:
 
-  fused     per-frame kernel time of k_warp_yuv against k_ingest + k_warp (cbv_profile_read event pairs), NV12 and YUYV,
-            1080p and 4K, batches larger than the Infinity Cache, `--rounds` alternating rounds, each listed
+  fused     per-frame kernel time of k_warp_yuv against k_ingest + k_warp (cbv_profile_read event pairs), every YUV format
+            (`--formats` picks some), 1080p and 4K, batches larger than the Infinity Cache, `--rounds` alternating rounds, each listed
   resident  frames/s with enhance=False against enhance=True: device-resident BGR, 512 frames in flight, 1080p and 4K,
             1 and 4 boards (median and spread of `--reps` steps)
-  host_fed  frames/s of NV12 / YUYV frames fed through the pinned ring in two halves, the copy of one half overlapping the
+  host_fed  frames/s of YUV frames fed through the pinned ring in two halves, the copy of one half overlapping the
             run of the other; the copy alone and the runs alone beside it say which of the two limits the rate
   latency   wall time of run + results of one frame
 
-    python tools/session_timing.py [--quick] [--rounds N] [--reps N]      (GPU box)
+    python tools/session_timing.py [--quick] [--rounds N] [--reps N] [--formats nv12,yuv420p] [--sizes 1080p]      (GPU box)
 """
 import argparse
 import json
@@ -26,7 +26,7 @@ from chessboard_vision_amd import synth as S  # noqa: E402
 from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
 
 SIZES = {"1080p": (1920, 1080), "4k": (3840, 2160)}
-FMTS = ("nv12", "yuyv")
+FMTS = tuple(f for f in N.FORMATS if f != "bgr")
 
 
 def spread(v):
@@ -184,17 +184,20 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="1080p only, small batches: a functional check of the tool")
     ap.add_argument("--only", default="fused,resident,host_fed")
+    ap.add_argument("--formats", default=",".join(FMTS))
+    ap.add_argument("--sizes", default="1080p,4k")
     a = ap.parse_args()
-    sizes = ["1080p"] if a.quick else ["1080p", "4k"]
+    sizes = ["1080p"] if a.quick else a.sizes.split(",")
+    fmts = a.formats.split(",")
     ctx = N.context()
     out = dict(device=ctx.lib.cbv_device_name(ctx.h).decode())
     if "fused" in a.only:
         # raw batches of 384 / 512 MiB (NV12 / YUYV at 1080p: 128 frames) and more: beyond the 256 MiB Infinity Cache
-        out["fused"] = [fused_against_unfused(s, f, 16 if a.quick else {"1080p": 128, "4k": 40}[s], a.rounds) for s in sizes for f in FMTS]
+        out["fused"] = [fused_against_unfused(s, f, 16 if a.quick else {"1080p": 128, "4k": 40}[s], a.rounds) for s in sizes for f in fmts]
     if "resident" in a.only:
         out["resident"] = [resident(s, k, 32 if a.quick else 512, a.reps) for s in sizes for k in (1, 4)]
     if "host_fed" in a.only:
-        out["host_fed"] = [host_fed(s, f, 16 if a.quick else {"1080p": 128, "4k": 64}[s], a.reps) for s in sizes for f in FMTS]
+        out["host_fed"] = [host_fed(s, f, 16 if a.quick else {"1080p": 128, "4k": 64}[s], a.reps) for s in sizes for f in fmts]
     print(json.dumps(out))
 
 
