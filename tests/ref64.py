@@ -179,21 +179,69 @@ def filter2d_3x3(img, kernel):
     return out
 
 
+def gaussian_kernel(k):
+    """cv2.getGaussianKernel(k, 0) for odd k: the fixed tables [1], [1 2 1]/4, [1 4 6 4 1]/16 and [1 3.5 7 9 7 3.5 1]/32
+    for k = 1, 3, 5, 7; otherwise exp(-x^2 / (2 s^2)) at x = i - (k-1)/2 with s = 0.3 ((k-1)/2 - 1) + 0.8, normalised
+    to sum 1."""
+    small = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
+             7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}
+    if k in small:
+        return np.array(small[k], np.float64)
+    assert k % 2 == 1 and k > 7, k
+    sigma = 0.3 * ((k - 1) / 2.0 - 1.0) + 0.8
+    x = np.arange(k, dtype=np.float64) - (k - 1) / 2.0
+    c = np.exp(-x * x / (2.0 * sigma * sigma))
+    return c / c.sum()
+
+
+def gaussian_q8(k):
+    """The 8-bit GaussianBlur's kernel in 8 fractional bits: from the edge towards the centre
+    q_i = floor(256 c_i + err + 0.5), err carrying the remainder on to the next coefficient (error diffusion); the
+    other half mirrors it and the centre is 256 - 2 * sum, so the kernel sums to exactly 256."""
+    c = gaussian_kernel(k)
+    q = np.zeros(k, np.int64)
+    err = 0.0
+    for i in range(k // 2):
+        adj = 256.0 * c[i] + err
+        q[i] = q[k - 1 - i] = int(np.floor(adj + 0.5))
+        err = adj - q[i]
+    q[k // 2] = 256 - q.sum()
+    return q
+
+
+def _separable101(a, kern):
+    """sum_y sum_x kern[y] kern[x] a(.), BORDER_REFLECT_101 on the array alone, in a's dtype: rows first, no rounding
+    in between."""
+    h, w = a.shape
+    r = len(kern) // 2
+    p = _pad101(a, r, r)
+    tmp = sum(kern[j] * p[:, j:j + w] for j in range(len(kern)))
+    return sum(kern[i] * tmp[i:i + h] for i in range(len(kern)))
+
+
+def gaussian_blur(gray, k):
+    """cv2.GaussianBlur(src, (k, k), 0): gaussian_kernel(k) applied separably with BORDER_REFLECT_101 (reflection is
+    repeated where the radius exceeds the array).  Unrounded float64."""
+    return _separable101(np.asarray(gray, np.float64), gaussian_kernel(k))
+
+
+def gaussian_blur_u8(gray, k):
+    """The 8-bit GaussianBlur result in integers: min((sum_y sum_x q_y q_x g + 2^15) >> 16, 255) with q = gaussian_q8(k);
+    one rounding (halves upward), none between the two passes."""
+    acc = _separable101(np.asarray(gray, np.int64), gaussian_q8(k))
+    return np.minimum((acc + (1 << 15)) >> 16, 255).astype(np.uint8)
+
+
 def gaussian_blur_5x5(gray):
     """cv2.GaussianBlur(src, (5, 5), 0): sigma 0 with ksize 5 selects the fixed binomial kernel [1 4 6 4 1] / 16,
     applied separably with BORDER_REFLECT_101.  Unrounded (a multiple of 1/256)."""
-    f = np.asarray(gray, np.float64)
-    h, w = f.shape
-    k = np.array([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
-    p = _pad101(f, 2, 2)
-    tmp = sum(k[j] * p[:, j:j + w] for j in range(5))
-    return sum(k[i] * tmp[i:i + h] for i in range(5))
+    return gaussian_blur(gray, 5)
 
 
 def gaussian_blur_5x5_u8(gray):
     """The 8-bit GaussianBlur result: the kernel is exact in 8 fractional bits, so the 8-bit path rounds the exact
     sum once, halves upward (fixed-point +0.5 then shift)."""
-    return np.floor(gaussian_blur_5x5(gray) + 0.5).astype(np.uint8)
+    return gaussian_blur_u8(gray, 5)
 
 
 def otsu_threshold(hist):
@@ -359,3 +407,82 @@ def warp_perspective(img, M, dsize):
     out = (tap(y0, x0) * (1 - ax) * (1 - ay) + tap(y0, x0 + 1) * ax * (1 - ay)
            + tap(y0 + 1, x0) * (1 - ax) * ay + tap(y0 + 1, x0 + 1) * ax * ay)
     return out, X, Y
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Canny
+# ---------------------------------------------------------------------------------------------------------------
+
+
+def sobel3(gray):
+    """cv2.Sobel(gray, CV_16S, 1, 0 / 0, 1, ksize=3) with BORDER_REPLICATE, as cv2.Canny takes its gradients:
+    dx = [1 2 1]^T (x) [-1 0 1], dy = [-1 0 1]^T (x) [1 2 1].  Returns integer (dx, dy)."""
+    g = np.asarray(gray, np.int64)
+    h, w = g.shape
+    p = g[np.clip(np.arange(-1, h + 1), 0, h - 1)][:, np.clip(np.arange(-1, w + 1), 0, w - 1)]
+    dx = (p[:-2, 2:] - p[:-2, :-2]) + 2 * (p[1:-1, 2:] - p[1:-1, :-2]) + (p[2:, 2:] - p[2:, :-2])
+    dy = (p[2:, :-2] - p[:-2, :-2]) + 2 * (p[2:, 1:-1] - p[:-2, 1:-1]) + (p[2:, 2:] - p[:-2, 2:])
+    return dx, dy
+
+
+def canny_sector(dx, dy):
+    """0 horizontal, 1 vertical, 2 diagonal: the sector of the real gradient angle atan2(|dy|, |dx|), below 22.5 degrees,
+    above 67.5 degrees, or between.  (No integer pair lies on a boundary: tan 22.5 degrees is irrational, and the nearest
+    ratio of Sobel outputs is 3.6e-7 away.)"""
+    ang = np.degrees(np.arctan2(np.abs(dy).astype(np.float64), np.abs(dx).astype(np.float64)))
+    return np.where(ang < 22.5, 0, np.where(ang > 67.5, 1, 2))
+
+
+def hysteresis(cand, strong):
+    """The pixels of `cand` 8-connected, through cand, to a pixel of cand & strong: 3x3 growth restricted to cand,
+    iterated until nothing changes."""
+    h, w = cand.shape
+    cur = cand & strong
+    while True:
+        p = np.zeros((h + 2, w + 2), bool)
+        p[1:-1, 1:-1] = cur
+        grown = cur.copy()
+        for i in range(3):
+            for j in range(3):
+                grown |= p[i:i + h, j:j + w]
+        grown &= cand
+        if np.array_equal(grown, cur):
+            return cur
+        cur = grown
+
+
+def canny_candidates(gray, t1, t2):
+    """(M, low, high, strict, loose, conv) of cv2.Canny(gray, t1, t2) (aperture 3, L1 gradient): low, high =
+    sorted((floor(t1), floor(t2))); M = |dx| + |dy|; the two neighbours of a pixel lie along its gradient's sector
+    (left / right, up / down, or the diagonal chosen by the sign of dx * dy: along (+1, +1) when positive, (+1, -1) when
+    negative), neighbours outside the image counting as 0.  A candidate has M > low and M above both neighbours:
+    strictly (`strict`), or at least equal (`loose`), or by OpenCV's tie rule (`conv`): > towards left / up,
+    >= towards right / down, > on both diagonal neighbours."""
+    low, high = sorted((int(np.floor(t1)), int(np.floor(t2))))
+    dx, dy = sobel3(gray)
+    M = np.abs(dx) + np.abs(dy)
+    h, w = M.shape
+    p = np.zeros((h + 2, w + 2), np.int64)
+    p[1:-1, 1:-1] = M
+
+    def nb(oy, ox):
+        return p[1 + oy:1 + oy + h, 1 + ox:1 + ox + w]
+
+    sec = canny_sector(dx, dy)
+    pos = dx * dy > 0
+    a = np.where(sec == 0, nb(0, -1), np.where(sec == 1, nb(-1, 0), np.where(pos, nb(-1, -1), nb(-1, 1))))
+    b = np.where(sec == 0, nb(0, 1), np.where(sec == 1, nb(1, 0), np.where(pos, nb(1, 1), nb(1, -1))))
+    over = M > low
+    strict = over & (M > a) & (M > b)
+    loose = over & (M >= a) & (M >= b)
+    conv = over & (M > a) & np.where(sec == 2, M > b, M >= b)
+    return M, low, high, strict, loose, conv
+
+
+def canny_sets(gray, t1, t2):
+    """(hyst(strict), hyst(loose), hyst(conv)) as boolean maps, hyst(S) = the pixels of S 8-connected through S to a pixel
+    of S with M > high.  Whatever tie rule an implementation of Canny uses, its edges lie between the first two;
+    cv2.Canny's are the third."""
+    M, _, high, strict, loose, conv = canny_candidates(gray, t1, t2)
+    strong = M > high
+    return hysteresis(strict, strong), hysteresis(loose, strong), hysteresis(conv, strong)

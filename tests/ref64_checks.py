@@ -70,6 +70,148 @@ def frame(content, w, h, seed=0):
     return CONTENTS[content](w, h, seed + 7 * w + 13 * h)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# inputs of the detector-side checks (GaussianBlur k = 1..31 on squares, Canny)
+# ---------------------------------------------------------------------------------------------------------------
+
+BLUR_KS = list(range(1, 32, 2))
+# h x w (x 3 = BGR): smaller than the radius in one or both axes (reflection repeats), either side of the 16-lane column
+# grid and of the row step, and the largest square the library takes
+SQUARE_SHAPES = [(128, 128, 3), (1, 1), (5, 7, 3), (77, 80), (3, 128, 3), (128, 2), (16, 15), (1, 31), (17, 16, 3), (15, 33)]
+
+
+def ramp(w, h, seed):
+    yy, xx = np.mgrid[:h, :w]
+    v = (xx * (2 + seed % 3) + yy * 3 + seed) % 512
+    return np.repeat(np.where(v > 255, 511 - v, v).astype(np.uint8)[..., None], 3, axis=2)
+
+
+def white(w, h, seed):
+    return np.full((h, w, 3), 255, np.uint8)
+
+
+SQUARE_CONTENTS = {"noise": noise, "ramp": ramp, "white": white, "edges": edges}
+
+
+def blur_squares():
+    """{(shape index, content): uint8 square} for every SQUARE_SHAPES x SQUARE_CONTENTS: 40 squares, one SquareSet."""
+    out = {}
+    for i, s in enumerate(SQUARE_SHAPES):
+        for c, fn in SQUARE_CONTENTS.items():
+            img = fn(s[1], s[0], 100 + i)
+            out[(i, c)] = img if len(s) == 3 else img[..., 1].copy()
+    return out
+
+
+CANNY_SHAPES = [(131, 257), (64, 64), (65, 129), (5, 7), (1, 40), (40, 1), (2, 2), (200, 193)]          # h x w
+CANNY_THRESHOLDS = [(30, 100), (50, 150), (150, 50), (50.5, 149.9)]
+CANNY_TIE_CAP = {"texture": 0.02, "noise": 0.02, "poster": None}
+
+
+def canny_input(content, h, w):
+    """texture: the waves-and-checkers image of test_gpu_stages.test_canny_matches_oracle under the 5 x 5 blur (of this
+    module's reference); noise: white noise; poster: the texture in 8 levels (plateaus: many equal magnitudes)."""
+    rng = np.random.default_rng(h * 7 + w)
+    if content == "noise":
+        return rng.integers(0, 256, (h, w), dtype=np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    img = (96 + 60 * np.sin(xx / 9.0) * np.cos(yy / 13.0) + 50 * ((xx // 40 + yy // 40) % 2)).astype(np.float64)
+    img = np.clip(img + rng.normal(0, 6, img.shape), 0, 255).astype(np.uint8)
+    g = R.gaussian_blur_u8(img, 5) if min(h, w) >= 5 else img
+    return g if content == "texture" else (g // 32 * 32).astype(np.uint8)
+
+
+def canny_cases():
+    return [(h, w, c, t) for (h, w) in CANNY_SHAPES for c in CANNY_TIE_CAP for t in CANNY_THRESHOLDS]
+
+
+def canny_tie_cap(content, h, w):
+    """The cap on the share of pixels where hyst(loose) and hyst(strict) differ: 2 % for texture and noise.  It is a share,
+    so it binds only where one tied pixel is less than the cap (h * w >= 50); smaller images run without it, as the
+    posterised ones do, and are held by the exact comparison alone."""
+    cap = CANNY_TIE_CAP[content]
+    return cap if cap is not None and h * w * cap >= 1 else None
+
+
+# One weak curve across the 64 x 64 hysteresis tiles of a 130 x 197 image: the boundary y = 64 + 30 sin(x / 10) between
+# gray 100 and 100 + a.  A step of height a gives M = 4a on a straight stretch and up to 6a on a diagonal one, so a = 10
+# stays inside (20, 80] everywhere; over the 10 columns at one end a = 30 (M >= 120 > 80) and falls back to 10 over the next 12.
+CURVE_SHAPE = (130, 197)
+CURVE_THRESHOLDS = (20, 80)
+
+
+def hysteresis_curve(end):
+    """end = "left" / "right": where the strong stretch lies; None: no strong stretch at all."""
+    h, w = CURVE_SHAPE
+    yy, xx = np.mgrid[:h, :w]
+    x = np.arange(w)
+    d = {"left": x, "right": w - 1 - x, None: np.full(w, 1000)}[end]    # distance from the strong end
+    a = np.where(d < 10, 30.0, np.clip(10 + (22 - d) * 20 / 12.0, 10, 30))
+    return np.rint(np.where(yy > 64 + 30 * np.sin(xx / 10.0), 100 + a[None, :], 100)).astype(np.uint8)
+
+
+def check_hysteresis_curve(edges, end):
+    """First the case itself, on the reference alone: the curve crosses x = 64, x = 128 and y = 64 at least six times, all of
+    it is weak except at the one end, hyst(conv) holds more than half of its pixels and reaches the far end, and without the
+    strong stretch nothing is an edge.  Then the output under test equals hyst(conv)."""
+    h, w = CURVE_SHAPE
+    gray = hysteresis_curve(end)
+    M, low, high, _, _, cand = R.canny_candidates(gray, *CURVE_THRESHOLDS)
+    yc = 64 + 30 * np.sin(np.arange(w) / 10.0)
+    assert int((np.diff(np.sign(yc - 64.0)) != 0).sum()) + 2 >= 6                     # y = 64, plus x = 64 and x = 128
+    strong_cols = np.nonzero((cand & (M > high)).any(axis=0))[0]
+    assert len(strong_cols) and (strong_cols.max() < 24 if end == "left" else strong_cols.min() > w - 25), strong_cols
+    conv = R.canny_sets(gray, *CURVE_THRESHOLDS)[2]
+    assert conv.sum() > cand.sum() / 2 and cand.sum() > 300, (int(conv.sum()), int(cand.sum()))
+    cols = np.nonzero(conv.any(axis=0))[0]
+    assert cols.min() == 0 and cols.max() == w - 1
+    assert conv[:64].any() and conv[64:128].any() and all(conv[:, a:b].any() for a, b in ((0, 64), (64, 128), (128, w)))
+    assert not R.canny_sets(hysteresis_curve(None), *CURVE_THRESHOLDS)[1].any()
+    edges = np.asarray(edges)
+    assert np.isin(edges, (0, 255)).all()
+    diff = int(((edges > 0) != conv).sum())
+    assert diff == 0, "weak curve, strong stretch at the %s end: %d of %d curve pixels differ" % (end, diff, int(conv.sum()))
+    return {"edges": int(conv.sum())}
+
+
+# Horizontal steps whose magnitude sits exactly on a threshold.  M is always even (dx + dy is), and a straight step of
+# height a has M = 4a.  threshold_step(): gray 100 above row 20, below it 130 over the first 20 columns and 110 over the rest
+# (M = 120 / 40).  At (40, 100) the weak stretch has M == low and is out; at (38, 100) it is in.  threshold_step(False): 130
+# below row 20 all along.  At (38, 120) it has M == high everywhere, nothing is strong and nothing is an edge; at
+# (38, 118) the whole row is.
+THRESHOLD_STEP_CASES = [(True, (40, 100)), (True, (38, 100)), (False, (38, 120)), (False, (38, 118))]
+
+
+def threshold_step(two_levels=True):
+    g = np.full((40, 70), 100, np.uint8)
+    g[20:] = 130
+    if two_levels:
+        g[20:, 20:] = 110
+    return g
+
+
+def check_threshold_step(canny_fn):
+    """canny_fn(gray, t1, t2) under check_canny at the four THRESHOLD_STEP_CASES, after the reference alone has shown that
+    the cases of a pair differ, and only through pixels whose magnitude equals a threshold."""
+    M = R.canny_candidates(threshold_step(), 0, 0)[0]
+    assert (M[19, 25:] == 40).all() and (M[19, :15] == 120).all()
+    assert (R.canny_candidates(threshold_step(False), 0, 0)[0][19:21] == 120).all()
+    conv = [R.canny_sets(threshold_step(two), *t)[2] for two, t in THRESHOLD_STEP_CASES]
+    assert conv[1][:, 25:].sum() == 45 and not conv[0][:, 25:].any() and conv[0][:, :15].sum() == 15
+    assert not conv[2].any() and conv[3].sum() == 70
+    return [check_canny(canny_fn(threshold_step(two), *t), threshold_step(two), *t) for two, t in THRESHOLD_STEP_CASES]
+
+
+def change_stats_ref(gray, ref, mean, var, z_threshold):
+    """sad_ref, z_count, z_max of one square in numpy float32, as ChangeDetector writes them: z = |float32(g) - mu| /
+    sqrt(var), counted with z > threshold; a variance of 0 gives inf (counts) or NaN (does not count; z_max is then NaN)."""
+    sad = int(np.abs(gray.astype(np.int64) - ref.astype(np.int64)).sum())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.abs(gray.astype(np.float32) - mean.astype(np.float32)) / np.sqrt(var.astype(np.float32))
+    assert z.dtype == np.float32
+    return sad, int((z > np.float32(z_threshold)).sum()), np.float32(np.max(z))
+
+
 # the (d, sigma_color, sigma_space) and (clip, grid) sweeps of test_gpu_stages.py
 GPU_BILATERAL_SWEEP = [(3, 40.0, 10.0), (5, 75.0, 75.0), (7, 20.0, 3.0), (9, 150.0, 1.5), (-1, 30.0, 1.0)]
 CLAHE_SWEEP = [(3.0, (8, 8)), (1.5, (5, 7)), (1.0, (8, 8)), (0.0, (3, 2)), (40.0, (1, 9)), (2.0, (9, 1)), (8.0, (4, 6))]
@@ -212,6 +354,64 @@ def check_blur(out, gray):
     d = np.abs(np.asarray(out, np.float64) - R.gaussian_blur_5x5(gray))
     assert d.max() <= 0.5
     return _stats(d)
+
+
+def gaussian_e1(k):
+    """||E||_1 of E = q (x) q / 65536 - c (x) c: how far the 8.8 fixed-point kernel is from the real one, from the
+    coefficients of ref64.py alone (0 for k <= 7, 0.013 for k = 9, 0.060 for k = 31)."""
+    q, c = R.gaussian_q8(k).astype(np.float64), R.gaussian_kernel(k)
+    return float(np.abs(np.outer(q, q) / 65536.0 - np.outer(c, c)).sum())
+
+
+def window_range(gray, k):
+    """max - min of gray over every pixel's REFLECT_101 k x k window."""
+    g = np.asarray(gray, np.int64)
+    h, w = g.shape
+    r = k // 2
+    p = R._pad101(g, r, r)
+    rows_hi = np.max([p[:, j:j + w] for j in range(k)], axis=0)
+    rows_lo = np.min([p[:, j:j + w] for j in range(k)], axis=0)
+    return np.max([rows_hi[i:i + h] for i in range(k)], axis=0) - np.min([rows_lo[i:i + h] for i in range(k)], axis=0)
+
+
+def check_gaussian(out, gray, k):
+    """cv2.GaussianBlur(gray, (k, k), 0) on 8 bits.  First the integer form, exactly.  Then the float64 definition: both
+    kernels sum to 1, so out's exact value minus the definition is sum E_ij (g_ij - mid) for any mid, at most
+    ||E||_1 * range / 2 with range = max - min of the pixel's window and mid their mean; rounding adds 0.5."""
+    gray = np.asarray(gray)
+    what = "GaussianBlur k=%d %s" % (k, gray.shape)
+    check_exact(out, R.gaussian_blur_u8(gray, k), what + " integer form")
+    d = np.abs(np.asarray(out, np.float64) - R.gaussian_blur(gray, k))
+    e1 = gaussian_e1(k)
+    bound = 0.5 + e1 * window_range(gray, k) / 2.0
+    bad = d > bound
+    if bad.any():
+        i = np.unravel_index(np.argmax(d - bound), d.shape)
+        raise AssertionError("%s: %d of %d values outside 0.5 + %.4f * range / 2, worst %.4f against %.4f at %s"
+                             % (what, int(bad.sum()), d.size, e1, d[i], bound[i], i))
+    return dict(_stats(d), e1=e1, bound=float(bound.max()))
+
+
+def check_canny(edges, gray, t1, t2, tie_cap=None):
+    """cv2.Canny(gray, t1, t2): 0 / 255 only; between hyst(strict) and hyst(loose) of ref64.canny_sets (true under any
+    tie rule); equal to hyst(conv), OpenCV's tie rule.  With tie_cap, hyst(loose) and hyst(strict) may differ on at most
+    that share of the pixels (else the sandwich says little)."""
+    edges, gray = np.asarray(edges), np.asarray(gray)
+    what = "Canny %s t=(%g, %g)" % (gray.shape, t1, t2)
+    assert edges.shape == gray.shape, (what, edges.shape)
+    assert np.isin(edges, (0, 255)).all(), what + ": values other than 0 / 255"
+    e = edges > 0
+    strict, loose, conv = R.canny_sets(gray, t1, t2)
+    assert not (strict & ~loose).any(), what + ": reference sets not nested"
+    gap = float((strict != loose).mean())
+    if tie_cap is not None:
+        assert gap <= tie_cap, "%s: hyst(loose) and hyst(strict) differ on %.2f %% of the pixels" % (what, 100 * gap)
+    missing, extra = int((strict & ~e).sum()), int((e & ~loose).sum())
+    assert missing == 0 and extra == 0, ("%s: outside the sandwich under any tie rule: %d pixels of hyst(strict) missing, "
+                                         "%d edges outside hyst(loose)" % (what, missing, extra))
+    diff = int((e != conv).sum())
+    assert diff == 0, "%s: inside the sandwich, but %d pixels differ from OpenCV's tie rule" % (what, diff)
+    return {"edges": int(e.sum()), "gap": gap, "strict": int(strict.sum()), "loose": int(loose.sum())}
 
 
 def check_prepare_analysis(gray, binary, t, img):
