@@ -1,5 +1,5 @@
 // C-ABI of libcbv_hip.so (include/cbv.h): context, host-buffer stage entry
-// points and per-square detector state (the device-resident pipeline: cbv_pipeline.cpp).
+// points and per-square detector state (the device-resident pipeline: cbv_pipeline*.cpp).
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>

@@ -324,6 +324,17 @@ static inline NormSrc norm_from_minmax(const u32* aux, int tiles)
     return n;
 }
 int launch_normalize(cbv_ctx* ctx, const u8* src, u8* dst, NormSrc norm, Geom g, int batch);
+// WarpPerspectiveInvoker's block shape of a dw x dh destination (BLOCK_SZ = 32): what the warp launchers pass to their
+// kernels and the multi-board table holds per board (BoardDev::bw0, bh0)
+static inline void warp_block_shape(int dw, int dh, int* bw0_out, int* bh0_out)
+{
+    const int BLOCK_SZ = 32;
+    int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : dh;
+    int bw0 = BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : dw;
+    bh0 = BLOCK_SZ * BLOCK_SZ / bw0 < dh ? BLOCK_SZ * BLOCK_SZ / bw0 : dh;
+    *bw0_out = bw0;
+    *bh0_out = bh0;
+}
 int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
                 int dst_stride, size_t dst_frame_stride, NormSrc norm, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 int launch_gray_blur_hist(cbv_ctx* ctx, const u8* src, u8* gray, u8* blur, u32* aux, int tiles, Geom g, int batch);
@@ -674,7 +685,7 @@ int launch_piece_sweep_eval(cbv_ctx* ctx, const SquareDesc* descs, int n, const 
                             cbv_piece_sweep_summary* sums);
 
 // ---------------------------------------------------------------------------
-// Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline.cpp) shares
+// Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline*.cpp) shares
 // ---------------------------------------------------------------------------
 #define RC(x)             \
     do {                  \

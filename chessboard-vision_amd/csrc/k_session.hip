@@ -17,7 +17,7 @@
 // The list is built once per walk and kept while the board stands (a rejected rule call, the radar); an accepted move
 // ends the walk.
 // Online play (include/cbv.h): the turn gate is part of ses_frame_rule; a board event (cbv_pipeline_session_sync) is
-// k_session_event between two segments of a run, each segment being the rounds above on its own frames (cbv_pipeline.cpp,
+// k_session_event between two segments of a run, each segment being the rounds above on its own frames (cbv_pipeline_run.cpp,
 // board_scan); the radar is computed by the walk in front of the stable-move step of each frame, its destinations as an
 // OR across the lanes over the kept list.
 #include "cbv_internal.h"

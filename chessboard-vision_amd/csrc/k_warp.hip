@@ -400,17 +400,6 @@ int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int
     return CBV_OK;
 }
 
-// WarpPerspectiveInvoker's block shape of a dw x dh destination (BLOCK_SZ = 32)
-static void warp_block_shape(int dw, int dh, int* bw0_out, int* bh0_out)
-{
-    const int BLOCK_SZ = 32;
-    int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : dh;
-    int bw0 = BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : dw;
-    bh0 = BLOCK_SZ * BLOCK_SZ / bw0 < dh ? BLOCK_SZ * BLOCK_SZ / bw0 : dh;
-    *bw0_out = bw0;
-    *bh0_out = bh0;
-}
-
 int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
                 int dst_stride, size_t dst_frame_stride, NormSrc norm, int batch, u32* zero_word, u32* zero_word2)
 {
