@@ -235,6 +235,16 @@ class PieceSweepInfo(C.Structure):
     _fields_ = [("hough_ms", C.c_float), ("eval_ms", C.c_float), ("param1_distinct", C.c_int32), ("chunk_frames", C.c_int32)]
 
 
+class ColorSweepInfo(C.Structure):
+    """cbv_color_sweep_info: GPU time of the four stages of cbv_pipeline_color_sweep and the chunk sizes used."""
+    _fields_ = [("warp_ms", C.c_float), ("squares_ms", C.c_float), ("hough_ms", C.c_float), ("eval_ms", C.c_float),
+                ("chunk_frames", C.c_int32), ("chunk_profiles", C.c_int32)]
+
+
+COLOR_SWEEP_MAX_PROFILES = 65536
+SKIP_ENHANCE_PROFILE = 2  # cbv_pipeline_config::skip_enhance: the colour profile only (CBV_SKIP_ENHANCE_PROFILE)
+
+
 class PieceChoice(C.Structure):
     """What k_piece_sweep_hough leaves per (setting, frame, square); cbv_piece_sweep_eval_host reads arrays of it."""
     _fields_ = [("kind", C.c_uint8), ("flags", C.c_uint8), ("r", C.c_int16), ("cx", C.c_int16), ("cy", C.c_int16)]
@@ -319,6 +329,7 @@ def load():
         "cbv_process_pipeline": (i32, [vp, u8p, i32, i32, i32, P(EnhanceParams), u8p, i32]),
         "cbv_get_perspective_transform": (i32, [vp, vp, vp]),
         "cbv_warp_perspective": (i32, [vp, u8p, i32, i32, i32, vp, i32, i32, i32, u8p, i32]),
+        "cbv_warp_color_profile": (i32, [vp, u8p, i32, i32, i32, P(ColorProfile), vp, i32, i32, i32, u8p, i32]),
         "cbv_squares_create": (i32, [vp, P(vp)]),
         "cbv_squares_destroy": (None, [vp]),
         "cbv_squares_load": (i32, [vp, P(SquareView), i32, i32]),
@@ -375,6 +386,7 @@ def load():
         "cbv_sweep_eval_host": (i32, [vp, vp, i32, vp, i32, vp]),
         "cbv_pipeline_piece_sweep": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, P(PieceSweepInfo)]),
         "cbv_pipeline_piece_detail": (i32, [vp, i32, P(HoughParams), vp]),
+        "cbv_pipeline_color_sweep": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, P(ColorSweepInfo)]),
         "cbv_piece_sweep_eval_host": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
         "cbv_pipeline_session_begin": (i32, [vp, P(SessionConfig), C.c_char_p]),
         "cbv_pipeline_session_end": (i32, [vp]),

@@ -58,6 +58,30 @@ def warp_image(img, points, display_size=(1280, 720), margin=100):
     return warped, matrix, board_size
 
 
+def warp_perspective_profiled(img, M, dsize, profile, rot180=False):
+    """warp_perspective(ImageEnhancer(profile).apply_color_profile(img), M, dsize, rot180), byte for byte, in one kernel: the
+    profile is applied to the four source pixels each destination pixel blends (include/cbv.h, cbv_warp_color_profile).
+    `profile`: a dict with the keys of color_profile.json, `None` / `{}` = no profile."""
+    c = N.context()
+    f = N.as_bgr(img)
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    dw, dh = int(dsize[0]), int(dsize[1])
+    out = np.empty((dh, dw, 3), np.uint8)
+    c.check(c.lib.cbv_warp_color_profile(c.h, N.ptr(f), f.shape[1], f.shape[0], f.strides[0], N.ColorProfile.from_dict(profile), N.ptr(M), dw, dh,
+                                         1 if rot180 else 0, N.ptr(out), out.strides[0]))
+    return out
+
+
+def warp_image_profiled(img, points, profile, display_size=(1280, 720), margin=100, rot180=False):
+    """warp_image(ImageEnhancer(profile).apply_color_profile(img), points, display_size, margin) in one kernel
+    (warp_perspective_profiled); `rot180` adds cv2.rotate(ROTATE_180).  Returns what warp_image returns:
+    (warped, matrix, board_size)."""
+    board_size = min(display_size) - margin
+    pts2 = np.float32([[0, 0], [board_size, 0], [0, board_size], [board_size, board_size]])
+    matrix = get_perspective_transform(np.float32(points), pts2)
+    return warp_perspective_profiled(img, matrix, (board_size, board_size), profile, rot180), matrix, board_size
+
+
 def yuv_to_bgr(frame, fmt):
     """cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12 / _YUY2 / _YVYU / _UYVY) on the GPU (include/cbv.h,
     cbv_yuv_to_bgr): a new uint8 [h, w, 3] array.  `fmt` "nv12" / "nv21": one [h * 3 // 2, w] array or a (y, chroma) pair of

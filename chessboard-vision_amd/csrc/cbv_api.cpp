@@ -299,6 +299,24 @@ int ctx_set_profile(cbv_ctx* ctx, const cbv_color_profile* p)
     return CBV_OK;
 }
 
+// the tables of a profile that belongs to a pipeline or a call (k_warp_profile), never ctx->ptabs: the profile as
+// ctx_set_profile reads it (flags as 0 / 1), null = disabled
+int profile_tabs_checked(cbv_ctx* ctx, const cbv_color_profile* p, ProfileTabs* out, const char* who)
+{
+    cbv_color_profile key;
+    memset(&key, 0, sizeof(key));
+    if (p && p->enabled) {
+        const double v[7] = {p->hue_shift, p->sat_scale, p->val_scale, p->contrast, p->brightness, p->target_hue, p->hue_window};
+        for (double x : v)
+            if (!std::isfinite(x)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: a field of the colour profile is not finite", who);
+        key = *p;
+        key.radical_mode = p->radical_mode ? 1 : 0;
+        key.enabled = 1;
+    }
+    build_profile_tabs(&key, out);
+    return CBV_OK;
+}
+
 int ctx_set_bilateral(cbv_ctx* ctx, int d, double sc, double ss)
 {
     if (ctx->b_d == d && ctx->b_sc == sc && ctx->b_ss == ss) return CBV_OK;
@@ -745,6 +763,28 @@ extern "C" int cbv_warp_perspective(cbv_ctx* ctx, const uint8_t* bgr, int w, int
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (tm) fprintf(stderr, "warp: h2d %.1f launch %.1f d2h %.1f sync %.1f us (rows %d..%d)\n", t1 - t0, t2 - t1, t3 - t2, now() - t3, y0, y1);
     return CBV_OK;
+}
+
+extern "C" int cbv_warp_color_profile(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, const cbv_color_profile* profile,
+                                      const double* M9, int dw, int dh, int rot180, uint8_t* out, int out_stride)
+{
+    RC(check_img(ctx, bgr, w, h, stride, 3, "cbv_warp_color_profile"));
+    if (!out || !M9 || !profile || dw <= 0 || dh <= 0 || dw > 8192 || dh > 8192 || out_stride < dw * 3)
+        return cbv_fail(ctx, CBV_ERR_ARG, "cbv_warp_color_profile: bad arguments");
+    if (!profile->enabled) return cbv_warp_perspective(ctx, bgr, w, h, stride, M9, dw, dh, rot180, out, out_stride);
+    ProfileTabs pt;
+    RC(profile_tabs_checked(ctx, profile, &pt, "cbv_warp_color_profile"));
+    CBV_ENTER(ctx);
+    double Minv[9];
+    if (!host_invert3x3(M9, Minv)) memset(Minv, 0, sizeof(Minv));
+    RC(upload(ctx, &ctx->in, bgr, w * 3, h, stride));
+    RC(dev_ensure(ctx, &ctx->a, (size_t)dw * dh * 3 + 256));
+    RC(dev_ensure(ctx, &ctx->b, sizeof(ProfileTabs))); // the call's tables
+    CBV_HIP(ctx, hipMemcpyAsync(ctx->b.p, &pt, sizeof(pt), hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt is on this stack)
+    RC(launch_warp_profile(ctx, (const u8*)ctx->in.p, tight_geom(w, h), Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, 0,
+                           (const ProfileTabs*)ctx->b.p, 1, 1));
+    return download(ctx, ctx->a.p, out, dw * 3, dh, out_stride);
 }
 
 // ---------------------------------------------------------------------------

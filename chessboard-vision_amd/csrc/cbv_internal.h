@@ -159,6 +159,7 @@ int dev_ensure(cbv_ctx* ctx, DevBuf* b, size_t bytes);
 void dev_free(DevBuf* b);
 int ctx_set_profile(cbv_ctx* ctx, const cbv_color_profile* p);
 int ctx_set_bilateral(cbv_ctx* ctx, int d, double sc, double ss);
+int profile_tabs_checked(cbv_ctx* ctx, const cbv_color_profile* p, ProfileTabs* out, const char* who);
 
 // RAII-less helpers to bracket a launch with profiling events
 void prof_begin(cbv_ctx* ctx, int kid);
@@ -337,6 +338,14 @@ static inline void warp_block_shape(int dw, int dh, int* bw0_out, int* bh0_out)
 }
 int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
                 int dst_stride, size_t dst_frame_stride, NormSrc norm, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
+// launch_warp with the colour profile applied to the taps (k_warp_profile): apply_color_profile followed by the warp, byte
+// for byte, with no converted frame in between, for `np` profiles at once.  ptabs[np] = device tables (build_profile_tabs),
+// the caller's, not ctx->ptabs; profile p writes its `batch` frames at dst + p * dst_profile_stride; a table with
+// enabled = 0 is the plain warp.  np x groups of frames (four frames a group from batch 8 on) <= 65535.  Counted as
+// CBV_K_WARP: the enumeration of profile ids is closed.
+int launch_warp_profile(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
+                        size_t dst_frame_stride, size_t dst_profile_stride, const ProfileTabs* ptabs, int np, int batch,
+                        u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 int launch_gray_blur_hist(cbv_ctx* ctx, const u8* src, u8* gray, u8* blur, u32* aux, int tiles, Geom g, int batch);
 int launch_otsu(cbv_ctx* ctx, u32* aux, int tiles, int total, int batch);
 int launch_threshold(cbv_ctx* ctx, const u8* blur, u8* binary, const u32* aux, int tiles, int w, int h, int batch);
@@ -630,6 +639,8 @@ void hough_board_cfgs(HoughCfg base, HoughCfg out[2], size_t lds[2]);
 // one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0
 int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, NormSrc norm, int batch,
                    u32* zero_word, u32* zero_word2);
+int launch_warp_profile_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, const ProfileTabs* pt, int batch,
+                           u32* zero_word, u32* zero_word2);
 int launch_warp_yuv_mb(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
                        int batch, u32* zero_word, u32* zero_word2);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
@@ -679,10 +690,11 @@ size_t piece_sweep_layout(HoughCfg* cfg, int* off_steps);
 int launch_piece_sweep_hough(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, const cbv_sq_stats* stats,
                              HoughCfg cfg, const PieceSet* sets, int ns, int frames, PieceChoice* out, int out_frames);
 // decision, history and records of `frames` frames in order: hist[ns][CBV_MAX_SQUARES] and sums[ns] are read and updated,
-// rec (may be null) = [setting][rec_stride], expected (may be null) = [frames]
+// rec (may be null) = [setting][rec_stride], expected (may be null) = [frames]; stat_stride = 0: stats[frames][n] serve every
+// setting; otherwise setting s reads stats[s * stat_stride + frame][n]
 int launch_piece_sweep_eval(cbv_ctx* ctx, const SquareDesc* descs, int n, const cbv_sq_stats* stats, const PieceChoice* choices, int choice_frames,
                             int frames, int ns, const u64* expected, u32* hist, cbv_piece_sweep_record* rec, int rec_stride,
-                            cbv_piece_sweep_summary* sums);
+                            cbv_piece_sweep_summary* sums, int stat_stride = 0);
 
 // ---------------------------------------------------------------------------
 // Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline*.cpp) shares

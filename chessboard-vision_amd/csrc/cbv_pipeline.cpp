@@ -370,6 +370,7 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     if (P->enhanced) (void)hipFree(P->enhanced);
     dev_free(&P->d_synth);
     dev_free(&P->d_boards);
+    dev_free(&P->d_ptabs);
     for (cbv_pipeline* q : P->boards) board_free(q); // board 0 (p) included
     delete P;
 }
@@ -391,12 +392,21 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     if (cfg->skip_enhance && cfg->enhance_region)
         return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_configure: skip_enhance with enhance_region (there is no enhancement to limit)");
     if (!cfg->skip_enhance) RC(check_params(ctx, &cfg->enhance));
+    const bool profile_only = cfg->skip_enhance == CBV_SKIP_ENHANCE_PROFILE;
+    ProfileTabs ptabs;
+    if (profile_only) RC(profile_tabs_checked(ctx, &cfg->enhance.profile, &ptabs, "cbv_pipeline_configure"));
     // every argument check that needs no state is done; from here on a failure leaves the pipeline UNconfigured
     // (run / results / ... return CBV_ERR_STATE) instead of half reconfigured
     P.configured = false;
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     P.keep_enhanced = cfg->keep_enhanced != 0;
     P.skip_enhance = cfg->skip_enhance != 0;
+    P.profile_only = profile_only;
+    P.profile_on = profile_only && cfg->enhance.profile.enabled; // a disabled profile: the plain warp, no table
+    if (P.profile_on) {
+        RC(dev_ensure(ctx, &P.d_ptabs, sizeof(ProfileTabs)));
+        CBV_HIP(ctx, hipMemcpy(P.d_ptabs.p, &ptabs, sizeof(ptabs), hipMemcpyHostToDevice));
+    } else dev_free(&P.d_ptabs);
     int chunk = cfg->chunk;
     if (chunk <= 0) chunk = 32;
     if (chunk > P.max_frames) chunk = P.max_frames;

@@ -62,6 +62,10 @@ struct Pipe {
     bool configured = false;
     bool keep_enhanced = false;
     bool skip_enhance = false; // cfg.skip_enhance: the warp samples the frames as they are, no enhancement scratch exists
+    // cfg.skip_enhance == CBV_SKIP_ENHANCE_PROFILE: the warp samples the BGR ring and, with an enabled profile (profile_on),
+    // applies the colour profile to its taps (k_warp_profile) with the pipeline's own table, d_ptabs
+    bool profile_only = false, profile_on = false;
+    DevBuf d_ptabs;
     int chunk = 8;
     u8* frames = nullptr;
     // Lanes: chunk c runs on lane c % n_lanes, each lane with its own HIP stream and scratch, so a
@@ -131,7 +135,7 @@ struct Pipe {
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
     Board& b0() const { return boards[0]->b; }
-    bool raw_mode() const { return skip_enhance && in_fmt != CBV_FMT_BGR; }
+    bool raw_mode() const { return skip_enhance && !profile_only && in_fmt != CBV_FMT_BGR; }
 };
 // cbv_pipeline.cpp: board handles, the ordering of the runs in flight, the boards' kernel arguments, read-backs
 bool attached(const cbv_pipeline* p);

@@ -5,7 +5,8 @@
 
 // the per-board stages of a chunk of b frames from slot s0 (warp, square statistics, HoughCircles' first pass): with boards
 // attached one launch each for all of them, otherwise the single-board launches with board 0's arguments
-// (res = the BGR frames the warp samples; in raw mode null, and the warp samples the chunk's slots of the raw ring)
+// (res = the BGR frames the warp samples; in raw mode null, and the warp samples the chunk's slots of the raw ring;
+// with the profile-only mode's enabled profile the warp applies it to its taps)
 static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, int b, u32* work, u32* retry0, u32* retry, int retry_base)
 {
     cbv_ctx* ctx = P.ctx;
@@ -20,6 +21,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         const int nb = (int)P.boards.size();
         if (raw0) RC(launch_warp_yuv_mb(ctx, raw, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
+        else if (P.profile_on) RC(launch_warp_profile_mb(ctx, res, P.g, tab, nb, P.max_S, s0, (const ProfileTabs*)P.d_ptabs.p, b, work, retry0));
         else RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
         if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, s0, b, P.max_px));
@@ -32,6 +34,9 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
     cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
     if (raw0) RC(launch_warp_yuv(ctx, raw, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
+    else if (P.profile_on)
+        RC(launch_warp_profile(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, 0, (const ProfileTabs*)P.d_ptabs.p, 1, b, work,
+                               retry0));
     else RC(launch_warp(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, norm, b, work, retry0));
     RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
                                  T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));

@@ -9,7 +9,9 @@
 //                      setting to setting.  Per setting: clear the accumulator, vote, P5-P7; a setting whose radii (for
 //                      this square) equal its predecessor's keeps the accumulator and redoes P5-P7 only.  8 bytes leave
 //                      per (setting, frame, square): PieceChoice.  Squares the statistics gate as uniform leave at once.
-// k_piece_sweep_eval   one wave per setting, lane = square: walks the chunk's frames in order with the 5-deep history of
+// k_piece_sweep_eval   (statistics: [frame][square] shared by the settings, or, stat_stride != 0, one set per setting,
+//                      stat_stride frames apart: the colour profile sweep, whose settings change the pixels)
+//                      one wave per setting, lane = square: walks the chunk's frames in order with the 5-deep history of
 //                      (setting, square) in a register (carried from chunk to chunk in a device buffer), decides
 //                      (piece_sweep_core.h), ballots into the six square sets, writes the record and adds to the summary.
 //                      A wave owns its setting: no atomics.
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(HG_NT) void k_piece_sweep_hough(const SquareDesc* _
 
 #define PS_EVAL_WAVES 4
 __global__ __launch_bounds__(64 * PS_EVAL_WAVES) void k_piece_sweep_eval(const SquareDesc* __restrict__ descs, int n, const cbv_sq_stats* __restrict__ stats,
-                                                                         const PieceChoice* __restrict__ choices, int choice_frames, int frames, int ns,
+                                                                         int stat_stride, const PieceChoice* __restrict__ choices, int choice_frames, int frames, int ns,
                                                                          const u64* __restrict__ expected, u32* __restrict__ hist,
                                                                          cbv_piece_sweep_record* __restrict__ rec, int rec_stride,
                                                                          cbv_piece_sweep_summary* __restrict__ sums)
@@ -146,7 +148,7 @@ __global__ __launch_bounds__(64 * PS_EVAL_WAVES) void k_piece_sweep_eval(const S
         PieceChoice c = {0, 0, 0, 0, 0};
         bool raw = false, stable = false;
         if (in) {
-            const cbv_sq_stats st = stats[(size_t)f * n + lane];
+            const cbv_sq_stats st = stats[((size_t)si * stat_stride + f) * n + lane];
             c = choices[((size_t)si * choice_frames + f) * CBV_MAX_SQUARES + lane];
             piece_decide_choice(&st, c, w, h, &res);
             raw = res.has_piece != 0;
@@ -204,10 +206,10 @@ int launch_piece_sweep_hough(cbv_ctx* ctx, const SquareDesc* descs, int n, const
 
 int launch_piece_sweep_eval(cbv_ctx* ctx, const SquareDesc* descs, int n, const cbv_sq_stats* stats, const PieceChoice* choices, int choice_frames,
                             int frames, int ns, const u64* expected, u32* hist, cbv_piece_sweep_record* rec, int rec_stride,
-                            cbv_piece_sweep_summary* sums)
+                            cbv_piece_sweep_summary* sums, int stat_stride)
 {
     hipLaunchKernelGGL(k_piece_sweep_eval, dim3((ns + PS_EVAL_WAVES - 1) / PS_EVAL_WAVES), dim3(64 * PS_EVAL_WAVES), 0, ctx->stream, descs, n, stats,
-                       choices, choice_frames, frames, ns, expected, hist, rec, rec_stride, sums);
+                       stat_stride, choices, choice_frames, frames, ns, expected, hist, rec, rec_stride, sums);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }

@@ -9,6 +9,7 @@
 // operation; coordinates are quantised to 1/32 px and sampled with the 15-bit
 // fixed-point bilinear table of remap().
 // Also here: the synthetic frame generator used by bench/tests.
+#include "cbv_profile_px.h"
 #include "cbv_yuv.h"
 
 struct WarpM {
@@ -350,6 +351,115 @@ __global__ __launch_bounds__(256) void k_warp_yuv_mb(const u8* __restrict__ p0, 
                             T.warped_stride, zero_word, zero_word2, batch, blockIdx.z - b * nz);
 }
 
+// ---------------------------------------------------------------------------
+// The warp with the colour profile applied to its taps (cbv_warp_color_profile, pipelines configured with
+// CBV_SKIP_ENHANCE_PROFILE, cbv_pipeline_color_sweep): apply_color_profile is a function of the pixel alone, so converting
+// the four taps and blending them is, byte for byte, sampling the converted frame: same coordinates (warp_taps), same
+// conversion (d_profile_px), same blend (warp_blend).  A tap outside the frame is BGR (0, 0, 0) as in k_warp, not the
+// profile of black.  This is k_warp_yuv's arrangement with d_profile_px in the place of d_yuv_bgr.
+// A workgroup stages the 7.5 KB d_profile_px reads (ProfileLds) and then covers WP_ROWS destination rows of its 64
+// columns, FPT frames each: 1920 staged words against 4096 conversions per frame.  The tables are an argument, one
+// ProfileTabs per profile of the launch (the grid's z runs over profile x group of frames); a table with enabled = 0
+// leaves the taps as they are.
+// ---------------------------------------------------------------------------
+#define WP_ROWS 16 // destination rows per workgroup: one row of WarpPerspectiveInvoker's 64 x 16 blocks
+
+// bz = the group of frames, pt = the profile's table; src and dst = frame 0 of the batch (for this profile)
+template <int FPT>
+__device__ __forceinline__ void warp_profile_body(const u8* __restrict__ src, Geom g, const double* __restrict__ M, int dw, int dh, int bw0,
+                                                  int rot180, u8* __restrict__ dst, int dst_stride, size_t dst_frame_stride,
+                                                  const StaticTabs* __restrict__ st, const ProfileTabs* __restrict__ pt,
+                                                  u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
+{
+    __shared__ ProfileLds L;
+    warp_zero_words(zero_word, zero_word2);
+    lds_copy(L.sdiv, st->sdiv, sizeof(L.sdiv));
+    lds_copy(L.hdiv, st->hdiv, sizeof(L.hdiv));
+    lds_copy(L.pt.csa, pt->csa, sizeof(L.pt.csa));
+    lds_copy(L.pt.hmask, pt->hmask, sizeof(L.pt.hmask));
+    lds_copy(L.pt.hsel, pt->hsel, sizeof(L.pt.hsel));
+    lds_copy(L.pt.hfr, pt->hfr, sizeof(L.pt.hfr));
+    lds_copy(L.pt.s_f, pt->s_f, sizeof(L.pt.s_f));
+    lds_copy(L.pt.v_f, pt->v_f, sizeof(L.pt.v_f));
+    const bool on = pt->enabled != 0, radical = pt->radical != 0; // uniform
+    __syncthreads();
+    const int f0 = bz * FPT;
+    const int nf = min(FPT, batch - f0);
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (dx >= dw) return;
+    // a tap as b | g << 8 | r << 16 (the low three bytes of v) through the profile
+    auto conv = [&](u32 v) -> u32 { return on ? d_profile_px(L, (int)(v & 255u), (int)((v >> 8) & 255u), (int)((v >> 16) & 255u), radical) : (v & 0xFFFFFFu); };
+    for (int dy = blockIdx.y * WP_ROWS + (threadIdx.x >> 6), r = 0; r < WP_ROWS / 4 && dy < dh; r++, dy += 4) {
+        const WarpTaps t = warp_taps(dx, dy, g.w, g.h, M, dw, dh, bw0, rot180, dst_stride);
+        const size_t tap = (size_t)t.sy * g.stride + (size_t)t.sx * 3; // (only dereferenced where the taps are inside)
+        // interior: one unaligned 8-byte load per row of taps, as warp_body (>= 8 bytes of slack behind the last frame)
+        u64 ta[FPT], tb[FPT];
+        if (t.interior)
+#pragma unroll
+            for (int k = 0; k < FPT; k++)
+                if (k < nf) {
+                    const u8* p00 = src + (size_t)(f0 + k) * g.frame_stride + tap;
+                    __builtin_memcpy(&ta[k], p00, 8);
+                    __builtin_memcpy(&tb[k], p00 + g.stride, 8);
+                }
+#pragma unroll
+        for (int k = 0; k < FPT; k++) {
+            if (k >= nf) break;
+            int o[3] = {0, 0, 0};
+            if (t.any_in) {
+                u32 q[4] = {0u, 0u, 0u, 0u}; // taps 00, 01, 10, 11; border taps are 0
+                if (t.interior) {
+                    q[0] = conv((u32)ta[k]);
+                    q[1] = conv((u32)(ta[k] >> 24));
+                    q[2] = conv((u32)tb[k]);
+                    q[3] = conv((u32)(tb[k] >> 24));
+                } else {
+                    const u8* p00 = src + (size_t)(f0 + k) * g.frame_stride + tap;
+                    const u8* p10 = p00 + g.stride;
+                    auto px = [&](const u8* p) -> u32 { return conv((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16)); };
+                    if (t.x0in && t.y0in) q[0] = px(p00);
+                    if (t.x1in && t.y0in) q[1] = px(p00 + 3);
+                    if (t.x0in && t.y1in) q[2] = px(p10);
+                    if (t.x1in && t.y1in) q[3] = px(p10 + 3);
+                }
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                    o[c] = warp_blend((int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255),
+                                      (int)((q[3] >> (8 * c)) & 255), t);
+            }
+            u8* out = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
+            out[0] = (u8)o[0];
+            out[1] = (u8)o[1];
+            out[2] = (u8)o[2];
+        }
+    }
+}
+
+// blockIdx.z = profile * nz + group of frames; profile p writes its frames dst_profile_stride bytes behind profile p - 1's
+template <int FPT>
+__global__ __launch_bounds__(256) void k_warp_profile(const u8* __restrict__ src, Geom g, WarpM M, int dw, int dh, int bw0, int rot180,
+                                                       u8* __restrict__ dst, int dst_stride, size_t dst_frame_stride, size_t dst_profile_stride,
+                                                       const StaticTabs* __restrict__ st, const ProfileTabs* __restrict__ ptabs, int nz,
+                                                       u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    const int pi = blockIdx.z / nz;
+    warp_profile_body<FPT>(src, g, M.m, dw, dh, bw0, rot180, dst + (size_t)pi * dst_profile_stride, dst_stride, dst_frame_stride, st, ptabs + pi,
+                           zero_word, zero_word2, batch, blockIdx.z - pi * nz);
+}
+
+// every board of a pipeline in one launch, as k_warp_mb; the profile is the pipeline's: one table
+template <int FPT>
+__global__ __launch_bounds__(256) void k_warp_profile_mb(const u8* __restrict__ src, Geom g, const BoardDev* __restrict__ tab, int nz, int s0,
+                                                          const StaticTabs* __restrict__ st, const ProfileTabs* __restrict__ pt,
+                                                          u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * WP_ROWS >= T.S)) return;
+    warp_profile_body<FPT>(src, g, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride, st, pt,
+                           zero_word, zero_word2, batch, blockIdx.z - b * nz);
+}
+
 template <int FPT, bool CALC>
 __global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g, WarpM M, int dw, int dh, int bw0,
                                                int bh0, int rot180, u8* __restrict__ dst, int dst_stride,
@@ -427,6 +537,45 @@ int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw
             hipLaunchKernelGGL((k_warp<1, false>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, bh0, rot180, dst, dst_stride,
                                dst_frame_stride, norm.lut, nullptr, 0, zero_word, zero_word2, batch);
     }
+    prof_end(ctx, CBV_K_WARP);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+// as launch_warp (four frames per thread in batched launches), for `np` profiles at once: ptabs[np] on the device
+int launch_warp_profile(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
+                        size_t dst_frame_stride, size_t dst_profile_stride, const ProfileTabs* ptabs, int np, int batch, u32* zero_word,
+                        u32* zero_word2)
+{
+    WarpM M;
+    for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
+    int bw0, bh0;
+    warp_block_shape(dw, dh, &bw0, &bh0);
+    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
+    if (np <= 0 || batch <= 0 || (long long)np * nz > 65535) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_profile: %d profiles x %d frames do not fit a launch", np, batch);
+    const dim3 grid((dw + 63) / 64, (dh + WP_ROWS - 1) / WP_ROWS, np * nz);
+    prof_begin(ctx, CBV_K_WARP);
+    if (fpt == 4)
+        hipLaunchKernelGGL((k_warp_profile<4>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride,
+                           dst_profile_stride, ctx->tabs, ptabs, nz, zero_word, zero_word2, batch);
+    else
+        hipLaunchKernelGGL((k_warp_profile<1>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride,
+                           dst_profile_stride, ctx->tabs, ptabs, nz, zero_word, zero_word2, batch);
+    prof_end(ctx, CBV_K_WARP);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_warp_profile_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, const ProfileTabs* pt, int batch,
+                           u32* zero_word, u32* zero_word2)
+{
+    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
+    const dim3 grid((maxS + 63) / 64, (maxS + WP_ROWS - 1) / WP_ROWS, nz * nb);
+    prof_begin(ctx, CBV_K_WARP);
+    if (fpt == 4)
+        hipLaunchKernelGGL((k_warp_profile_mb<4>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, ctx->tabs, pt, zero_word, zero_word2, batch);
+    else
+        hipLaunchKernelGGL((k_warp_profile_mb<1>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, ctx->tabs, pt, zero_word, zero_word2, batch);
     prof_end(ctx, CBV_K_WARP);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;

@@ -156,6 +156,66 @@ class PieceSweepResult:
         return min(range(len(sm)), key=lambda j: (-int(sm["frames_exact"][j]), int(sm["missed"][j]) + int(sm["false_pos"][j]), j))
 
 
+class ColorSweepResult(PieceSweepResult):
+    """What `color_sweep` returns.  `profiles`: the dicts as given (`None` / `{}` = disabled).  With records: the fields of
+    PieceSweepResult as [P, F] arrays.  `summary`: [P] structured array as PieceSweepResult's.  `info`: dict of the GPU
+    times (ms) of the four stages (warp, squares, hough, eval) and the chunk sizes.  `occupied(p, i)` and `best()` as
+    PieceSweepResult's."""
+
+    def __init__(self, profiles, records, summary, info, rois_rc):
+        PieceSweepResult.__init__(self, profiles, records, summary, info, rois_rc)
+        self.profiles = profiles
+
+
+# calibrate_colors.py:194-203, the keys of color_profile.json in the tool's order
+COLOR_PROFILE_KEYS = ("hue_shift", "sat_scale", "val_scale", "contrast", "brightness", "radical_mode", "target_hue", "hue_window")
+
+
+def color_trackbar_axes():
+    """{key: [values]}: every value each trackbar of calibrate_colors.py can produce, in trackbar order (:23-42 the
+    ranges, :137-145 the formulas): hue_shift pos - 180 for 0..360, sat_scale / val_scale / contrast pos / 100.0 for
+    0..300, brightness pos - 100 for 0..200, radical_mode 0 / 1, target_hue 0..179, hue_window 0..50."""
+    scale = [pos / 100.0 for pos in range(301)]
+    return {"hue_shift": [pos - 180 for pos in range(361)], "sat_scale": list(scale), "val_scale": list(scale), "contrast": list(scale),
+            "brightness": [pos - 100 for pos in range(201)], "radical_mode": [0, 1], "target_hue": list(range(180)),
+            "hue_window": list(range(51))}
+
+
+def color_full_profile(profile):
+    """The eight keys of `profile` with ImageEnhancer.apply_color_profile's defaults (frame_enhancer.py:61-68) for the
+    missing ones: an ENABLED profile, also for `None` / `{}`."""
+    d = dict(hue_shift=0, sat_scale=1.0, val_scale=1.0, contrast=1.0, brightness=0, radical_mode=0, target_hue=0, hue_window=20)
+    d.update({k: v for k, v in (profile or {}).items() if k in COLOR_PROFILE_KEYS})
+    return d
+
+
+def color_axis_profiles(base, axis, values=None):
+    """The profiles along one trackbar: `base` (missing keys take the defaults) with `axis` set to each of `values`
+    (default: every position of that trackbar, `color_trackbar_axes`)."""
+    if axis not in COLOR_PROFILE_KEYS:
+        raise ValueError("colour profile axis %r: expected one of %s" % (axis, ", ".join(COLOR_PROFILE_KEYS)))
+    if values is None:
+        values = color_trackbar_axes()[axis]
+    return [dict(color_full_profile(base), **{axis: v}) for v in values]
+
+
+def save_color_profile(path, profile):
+    """Write the color_profile.json calibrate_colors.py saves (:194-204, :54-57: the eight keys, json, indent 4), which
+    ImageEnhancer.load_profile reads from the working directory.  Missing keys take the defaults.  Returns what was
+    written."""
+    full = color_full_profile(profile)
+    data = {k: full[k] for k in COLOR_PROFILE_KEYS}
+    with open(path, "w") as f:
+        json.dump(data, f, indent=4)
+    return data
+
+
+def load_color_profile(path="color_profile.json"):
+    """The profile dict of a color_profile.json, as ImageEnhancer.load_profile returns it."""
+    with open(path) as f:
+        return json.load(f)
+
+
 class SweepResult:
     """What `sensitivity_sweep` returns.  `settings`: [S] structured array (z_threshold, initial_variance, blur_kernel as
     given).  With records: `changed`, `parcial`, `total` (uint64 square sets, bit i = roi i), `z_max`, `n_changed`,
@@ -326,6 +386,30 @@ class _BoardMethods:
         self.ctx.check(self.ctx.lib.cbv_pipeline_piece_sweep(self.h_, slot0, count, N.ptr(sets), len(sets), N.ptr(exp) if exp is not None else None,
                                                              chunk_frames, N.ptr(rec) if records else None, N.ptr(summ), info))
         return PieceSweepResult(sets, rec, summ, {name: getattr(info, name) for name, _ in N.PieceSweepInfo._fields_}, self.rois_rc)
+
+    def color_sweep(self, slot0, count, profiles, expected=None, chunk_frames=0, records=True):
+        """What calibrate_colors.py's trackbars do to the PieceDetector, for many positions at once (include/cbv.h,
+        cbv_pipeline_color_sweep): every profile on the frames in the slots slot0 .. slot0 + count - 1 (as uploaded; they
+        need not have been run), as a board configured with `enhance="profile"`, that profile and every square checked
+        reports them: apply_color_profile -> warp -> split -> a fresh PieceDetector with this board's radii and Hough
+        settings.  `profiles`: dicts with the keys of color_profile.json (missing keys take ImageEnhancer's defaults),
+        `None` / `{}` = the frame as it is.  `expected`: per frame a {(file, rank)} set or a roi bitset, for the summary's
+        frames_exact / missed / false_pos.  The board itself is not touched.  `records=False` returns the per-profile
+        summary only.  Returns a ColorSweepResult."""
+        profiles = list(profiles)
+        profs = (N.ColorProfile * len(profiles))(*[N.ColorProfile.from_dict(d) for d in profiles])
+        exp = None
+        if expected is not None:
+            if len(expected) != count:
+                raise ValueError("color_sweep: `expected` needs one entry per frame")
+            roi_of = {(c, 7 - r): i for i, (r, c) in enumerate(self.rois_rc)}
+            exp = np.array([e if isinstance(e, (int, np.integer)) else sum(1 << roi_of[pos] for pos in e) for e in expected], np.uint64)
+        rec = np.zeros((len(profiles), count), N.record_dtype(N.PieceSweepRecord)) if records else None
+        summ = np.zeros(len(profiles), N.record_dtype(N.PieceSweepSummary))
+        info = N.ColorSweepInfo()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_color_sweep(self.h_, slot0, count, profs, len(profiles), N.ptr(exp) if exp is not None else None,
+                                                             chunk_frames, N.ptr(rec) if records else None, N.ptr(summ), info))
+        return ColorSweepResult(profiles, rec, summ, {name: getattr(info, name) for name, _ in N.ColorSweepInfo._fields_}, self.rois_rc)
 
     def piece_detail(self, slot, min_radius_ratio=_D["min_radius_ratio"], max_radius_ratio=_D["max_radius_ratio"],
                      param1=_D["hough_param1"], param2=_D["hough_param2"]):
@@ -574,9 +658,14 @@ class BoardPipeline(_BoardMethods):
         `enhance_region` (only without keep_enhanced): enhance the part of each frame the warp samples first and the rest
         only when normalize's global min / max could depend on it; every output stays identical (include/cbv.h).
         `enhance=True` (default) reproduces the composed chain process_pipeline -> warp -> split -> detect.
+        `enhance="profile"` runs apply_color_profile -> warp -> rotate -> split -> detect: of the enhancement only the
+        colour `profile`, applied inside the warp at nearly the cost of `enhance=False`; the CLAHE and sharpen settings are
+        ignored, `keep_enhanced` and `enhance_region` are errors, a `None` / `{}` profile is `enhance=False`'s warp, and
+        YUV frames are converted into the BGR ring as with `enhance=True` (no raw mode).  `color_sweep` judges profiles
+        for this mode.
         `enhance=False` reproduces what GameSession.on_frame (game_session.py:123-161) and calibrate_sensitivity.py:142-157
-        run: the warp samples the camera frame as it is, then rotate, split and detect; `profile`, the CLAHE and sharpen
-        settings are ignored, `keep_enhanced` and `enhance_region` are errors, and with a YUV `set_input_format` the warp
+        run: the warp samples the camera frame as it is, then rotate, split and detect; `profile` (used by `enhance=True`
+        and `enhance="profile"` only), the CLAHE and sharpen settings are ignored, `keep_enhanced` and `enhance_region` are errors, and with a YUV `set_input_format` the warp
         reads the raw frames directly (raw mode: `upload` takes that format only, `synth` is an error, `download(0, slot)`
         converts the slot).
         `blur_kernel`: ChangeDetector.blur_kernel (`set_change_blur`)."""
@@ -595,7 +684,9 @@ class BoardPipeline(_BoardMethods):
                                      max_radius_ratio, hough_param1, hough_param2)
         cfg.chunk, cfg.lanes, cfg.keep_enhanced = chunk, lanes, 1 if keep_enhanced else 0
         cfg.enhance_region = 1 if enhance_region else 0
-        cfg.skip_enhance = 0 if enhance else 1
+        if isinstance(enhance, str) and enhance != "profile":
+            raise ValueError("enhance %r: expected True, False or \"profile\"" % (enhance,))
+        cfg.skip_enhance = N.SKIP_ENHANCE_PROFILE if enhance == "profile" else (0 if enhance else 1)
         self.ctx.check(self.ctx.lib.cbv_pipeline_configure(self.h_, cfg))
         self.rois_rc = rois_rc
         self.board_size = S_

@@ -178,6 +178,13 @@ CBV_API int cbv_get_perspective_transform(const float* src8, const float* dst8, 
 CBV_API int cbv_warp_perspective(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, const double* M9, int dw,
                          int dh, int rot180, uint8_t* out, int out_stride);
 
+/* = cbv_apply_color_profile followed by cbv_warp_perspective (+ rotate 180), byte for byte; profile->enabled = 0 is the
+ * plain warp.  One kernel (k_warp_profile): warpPerspective blends four source pixels of apply_color_profile(frame), and the
+ * profile is a function of the pixel alone, so the four taps are converted and then blended; no converted frame exists.  A
+ * tap outside the frame is BGR 0 (BORDER_CONSTANT), not the profile of black.  The profile's tables belong to the call. */
+CBV_API int cbv_warp_color_profile(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, const cbv_color_profile* profile,
+                                   const double* M9, int dw, int dh, int rot180, uint8_t* out, int out_stride);
+
 /* ------------------------------------------------------------------ */
 /* per-square detector state (change_detector.py, piece_detector.py)   */
 /* ------------------------------------------------------------------ */
@@ -373,8 +380,16 @@ typedef struct {
                                     in front of the detectors: warp -> rotate -> split -> detect.  `enhance` is ignored;
                                     with keep_enhanced or enhance_region: CBV_ERR_ARG; cbv_pipeline_download(which = 1):
                                     CBV_ERR_STATE.  With a YUV input format the warp reads the raw frames (see
-                                    cbv_pipeline_set_input_format).  0: the composed chain enhance -> warp -> detect */
+                                    cbv_pipeline_set_input_format).  0: the composed chain enhance -> warp -> detect.
+                                    CBV_SKIP_ENHANCE_PROFILE (2): the colour profile only: apply_color_profile -> warp ->
+                                    rotate -> split -> detect, the profile applied to the warp's taps (k_warp_profile), no
+                                    enhancement scratch.  Of `enhance` only enhance.profile is read and checked; the
+                                    profile is the pipeline's (every board's); keep_enhanced / enhance_region / download
+                                    (which = 1) as for 1.  A disabled profile takes the plain warp.  With a YUV input format
+                                    the frames are converted into the BGR ring as with enhancement (raw mode is 1 only).
+                                    Every other non-zero value means 1 */
 } cbv_pipeline_config;
+#define CBV_SKIP_ENHANCE_PROFILE 2 /* cbv_pipeline_config::skip_enhance: the colour profile and nothing else of the enhancement */
 
 /* Per frame result of PieceDetector.detect_all_pieces(use_smoothing=True,
  * use_delta=True, squares_to_check=None) (piece_detector.py:348-440);
@@ -880,6 +895,42 @@ CBV_API int cbv_pipeline_piece_detail(cbv_pipeline* board, int slot, const cbv_h
 CBV_API int cbv_piece_sweep_eval_host(const cbv_sq_stats* stats, const int32_t* ws, const int32_t* hs, int n, int frames,
                                       const void* choices, int ns, const uint64_t* expected, cbv_piece_sweep_record* records,
                                       cbv_piece_sweep_summary* summary);
+
+/* ------------------------------------------------------------------ */
+/* Colour profile sweep on the device                                   */
+/* ------------------------------------------------------------------ */
+/* What calibrate_colors.py's eight trackbars (hue_shift, sat_scale, val_scale, contrast, brightness, radical_mode,
+ * target_hue, hue_window) do to the PieceDetector, for many positions at once, on frames in the ring.
+ * DEFINITION: profile c on the frames slot0 .. slot0 + count - 1 is what a fresh reference PieceDetector (history_size 5,
+ * min_presence 0.6, circle_threshold 0.6; radii and Hough parameters: the board's configured ones) returns when
+ * detect_all_pieces(squares_i, use_smoothing=True, squares_to_check=<all squares>) is called on the frames in order with
+ * squares_i = split_board(rotate?(warp_image(ImageEnhancer(profile = c).apply_color_profile(frame_i)))), the board's corners,
+ * rotation and grid.  That is what a board configured with CBV_SKIP_ENHANCE_PROFILE, profile c, use_hough = 2 and every
+ * square checked reports.  The result is in cbv_pipeline_piece_sweep's terms: records [np][count] (profile major; may be
+ * NULL), summary [np], `expected` (may be NULL), CBV_PIECE_SWEEP_OVERFLOW.  An entry with enabled = 0 is the frame as it is.
+ * Any board handle.  Reads the BGR frame ring (the frames as uploaded, before any enhancement, whatever the pipeline's
+ * mode) and the board's geometry, square table, masks and Hough settings (cfg.hough, whether or not use_hough is set);
+ * writes nothing of the board's, does not need the slots to have been run, and a pipeline that never calls it launches
+ * and allocates nothing for it.  Waits for the runs in flight.  Per chunk of profiles x chunk of frames: k_warp_profile
+ * into scratch boards [profile][frame], the fused gray + 5 x 5 blur + statistics kernel on them, the sweep's HoughCircles
+ * kernel (k_piece_sweep_hough, one setting) on every square the std < 15 gate lets through, k_piece_sweep_eval with the
+ * statistics of each profile; history and summaries stay on the device from chunk to chunk.  `info` (may be NULL) gets the
+ * four stages' GPU time (event pairs) and the chunk sizes used.  chunk_frames: 0 = CBV_SWEEP_DEFAULT_CHUNK, at most
+ * CBV_SWEEP_MAX_CHUNK; the profiles of a chunk are as many as keep the scratch below 256 MiB (and the launch's grid inside
+ * its limits).  Device memory of the call, with P = profiles per chunk, F = chunk_frames, S = board_size:
+ * P x F x (3 S^2 + the squares' gray planes + n_rois x 72 bytes of statistics + 64 x 8 bytes of circle choices),
+ * P x 6.5 KB of tables, np x (256 bytes of history + 56 of summary) and, with `records`, P x F x 56 bytes of staging (and as
+ * much pinned host memory), all freed before the call returns.  The result does not depend on the chunk sizes, on the order of the profiles
+ * or on duplicates.
+ * CBV_ERR_STATE: not configured.  CBV_ERR_ARG: null or empty arguments, no summary, slots outside the ring, chunk_frames
+ * outside 0..CBV_SWEEP_MAX_CHUNK, np above CBV_COLOR_SWEEP_MAX_PROFILES, a profile field that is not finite.
+ * CBV_ERR_UNSUPPORTED: raw mode (there is no BGR ring), or squares that do not fit the HoughCircles kernel's LDS layout.
+ * After any error nothing has changed. */
+typedef struct { float warp_ms, squares_ms, hough_ms, eval_ms; int32_t chunk_frames, chunk_profiles; } cbv_color_sweep_info;
+#define CBV_COLOR_SWEEP_MAX_PROFILES 65536
+CBV_API int cbv_pipeline_color_sweep(cbv_pipeline* board, int slot0, int count, const cbv_color_profile* profiles, int np,
+                                     const uint64_t* expected, int chunk_frames, cbv_piece_sweep_record* records,
+                                     cbv_piece_sweep_summary* summary, cbv_color_sweep_info* info);
 
 #ifdef __cplusplus
 }

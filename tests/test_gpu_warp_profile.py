@@ -1,0 +1,119 @@
+"""cbv_warp_color_profile (k_warp_profile) against the oracle: O.apply_color_profile followed by O.warp_perspective, and
+against the two existing product entry points composed.  Shapes are the smallest at which the kernel can go wrong: a source
+smaller than a tile, widths that are no multiple of 4, a strided view, destinations that are no multiple of the 64 x 16
+workgroup tile and one of many tiles, quads partly, mirrored and entirely outside the frame, with and without the rotation.
+Tolerance 0."""
+import numpy as np
+import pytest
+
+import color_sweep_ref as CS
+from helpers import random_frame
+
+pytestmark = pytest.mark.gpu
+
+PROFILES = dict(CS.PROFILES, stages_fractional=CS.STAGES_FRACTIONAL)
+DESTS = ((33, 21), (620, 620))
+
+
+def _sources():
+    big = random_frame(700, 500, 31)
+    return {"37x29": random_frame(37, 29, 13), "5x3": random_frame(5, 3, 14, smooth=False), "317x203": random_frame(317, 203, 15),
+            "strided": big[11:491, 23:663],  # a 640 x 480 view of a larger frame: row stride 2100
+            "640x480": np.array(CS.frame("lilac", 0))}
+
+
+def _quads(w, h):
+    """source corners TL, TR, BL, BR"""
+    return {"inside": [[w * .2, h * .1], [w * .85, h * .15], [w * .1, h * .9], [w * .95, h * .8]],
+            "partly_outside": [[-w * .1, -h * .1], [w * 1.1, h * .05], [w * .02, h * 1.1], [w * .9, h * .95]],
+            "mirrored": [[w * .9, h * .1], [w * .1, h * .1], [w * .9, h * .9], [w * .1, h * .9]],
+            "outside": [[w + 40, h + 30], [w + 140, h + 35], [w + 45, h + 120], [w + 150, h + 130]]}
+
+
+def _matrix(quad, dw, dh):
+    from chessboard_vision_amd.board_detection import get_perspective_transform
+    return get_perspective_transform(np.float32(quad), np.float32([[0, 0], [dw, 0], [0, dh], [dw, dh]]))
+
+
+@pytest.fixture(scope="module")
+def sources():
+    return _sources()
+
+
+@pytest.mark.parametrize("dest", DESTS, ids=lambda d: "%dx%d" % d)
+@pytest.mark.parametrize("src", ["37x29", "5x3", "317x203", "strided", "640x480"])
+def test_equals_the_oracle_and_the_composed_entry_points(gpu_ctx, oracle, sources, src, dest):
+    """every quad, both rotations; the profiles are dealt round the (quad, rotation) cases so that every profile meets
+    every source and destination, and the shipped one meets every case"""
+    from chessboard_vision_amd.board_detection import warp_perspective, warp_perspective_profiled
+    from chessboard_vision_amd.frame_enhancer import ImageEnhancerHIP
+    f = sources[src]
+    h, w = f.shape[:2]
+    names = [n for n in PROFILES if PROFILES[n]]
+    enh = ImageEnhancerHIP()
+    k = 0
+    for qname, quad in _quads(w, h).items():
+        M = _matrix(quad, *dest)
+        for rot in (False, True):
+            for name in {"shipped", names[k % len(names)], names[(k + 5) % len(names)]}:
+                prof = PROFILES[name]
+                col = oracle.apply_color_profile(np.ascontiguousarray(f), prof)
+                want = oracle.warp_perspective(col, M, dest)
+                want = oracle.rotate180(want) if rot else want
+                got = warp_perspective_profiled(f, M, dest, prof, rot180=rot)
+                assert np.array_equal(got, want), (src, dest, qname, rot, name, int((got != want).sum()))
+                if qname == "outside":
+                    assert not got.any()  # BORDER_CONSTANT 0, not the profile of black
+                if name == "shipped":  # the product's own two stages, composed
+                    enh.profile = prof
+                    assert np.array_equal(got, warp_perspective(enh.apply_color_profile(f), M, dest, rot180=rot)), (src, dest, qname, rot)
+            k += 1
+
+
+def test_every_profile_on_the_board_quad(gpu_ctx, oracle):
+    """the yardstick's own case: every profile on a 640 x 480 frame of each palette, the board's quad, 620 x 620"""
+    from chessboard_vision_amd import synth as S
+    from chessboard_vision_amd.board_detection import warp_image_profiled
+    pts = S.scaled_corners(CS.W, CS.H)
+    for pal in CS.PALETTES:
+        f = np.array(CS.frame(pal, 5))
+        for name, prof in PROFILES.items():
+            got, M, bs = warp_image_profiled(f, pts, prof)
+            want, oM, obs = oracle.warp_image(oracle.apply_color_profile(f, prof) if prof else f, pts)
+            assert bs == obs == 620 and np.array_equal(M, oM)
+            assert np.array_equal(got, want), (pal, name, int((got != want).sum()))
+            got180 = warp_image_profiled(f, pts, prof, rot180=True)[0]
+            assert np.array_equal(got180, oracle.rotate180(want)), (pal, name)
+
+
+def test_a_profile_of_black_is_not_black(oracle):
+    """what makes the all-outside case a check: a brightness above 0 turns black into something else"""
+    assert oracle.apply_color_profile(np.zeros((2, 2, 3), np.uint8), PROFILES["radical"]).any()
+
+
+def test_a_disabled_profile_is_the_plain_warp(gpu_ctx, sources):
+    from chessboard_vision_amd.board_detection import warp_perspective, warp_perspective_profiled
+    for src in ("37x29", "strided"):
+        f = sources[src]
+        h, w = f.shape[:2]
+        for quad in _quads(w, h).values():
+            M = _matrix(quad, 33, 21)
+            for prof in (None, {}):
+                for rot in (False, True):
+                    assert np.array_equal(warp_perspective_profiled(f, M, (33, 21), prof, rot180=rot), warp_perspective(f, M, (33, 21), rot180=rot))
+
+
+def test_bad_arguments(gpu_ctx):
+    from chessboard_vision_amd import _native as N
+    lib, ctx = gpu_ctx.lib, gpu_ctx
+    f = random_frame(37, 29, 13)
+    M = np.eye(3)
+    out = np.zeros((21, 33, 3), np.uint8)
+    prof = N.ColorProfile.from_dict(CS.SHIPPED)
+    args = lambda **kw: [kw.get(k, v) for k, v in dict(ctx=ctx.h, img=N.ptr(f), w=37, h=29, stride=f.strides[0], prof=prof, M=N.ptr(M), dw=33, dh=21,  # noqa: E731
+                                                        rot=0, out=N.ptr(out), ostride=out.strides[0]).items()]
+    assert lib.cbv_warp_color_profile(*args()) == 0
+    for bad in (dict(prof=None), dict(M=None), dict(out=None), dict(dw=0), dict(dh=9000), dict(stride=37 * 3 - 1), dict(ostride=33 * 3 - 1), dict(w=0)):
+        assert lib.cbv_warp_color_profile(*args(**bad)) == -1, bad
+    nan = N.ColorProfile.from_dict(dict(CS.SHIPPED, val_scale=float("nan")))
+    assert lib.cbv_warp_color_profile(*args(prof=nan)) == -1
