@@ -274,6 +274,12 @@ FORMATS = {"bgr": FMT_BGR, "nv12": FMT_NV12, "yuyv": FMT_YUYV, "nv21": FMT_NV21,
            "yvyu": FMT_YVYU, "uyvy": FMT_UYVY}
 FORMATS_420 = ("nv12", "nv21", "yuv420p", "yv12")      # ring slots [h * 3 // 2, w]
 FORMATS_422 = ("yuyv", "yvyu", "uyvy")                 # ring slots [h, w, 2]
+# 8-bit Bayer mosaics, named by their top-left 2 x 2 block read row by row (cv2 names its codes by the block at (1, 1):
+# "bayer_rggb" is COLOR_BayerBG2BGR).  Low nibble 4 = the family; 0x10 = blue where RGGB has red; 0x20 = rows start with green.
+# A table of its own: FORMATS stays the BGR and YUV formats.
+FMT_BAYER_RGGB, FMT_BAYER_BGGR, FMT_BAYER_GRBG, FMT_BAYER_GBRG = 0x04, 0x14, 0x24, 0x34
+BAYER_FORMATS = {"bayer_rggb": FMT_BAYER_RGGB, "bayer_bggr": FMT_BAYER_BGGR, "bayer_grbg": FMT_BAYER_GRBG,
+                 "bayer_gbrg": FMT_BAYER_GBRG}                 # ring slots [h, w]
 
 KERNEL_IDS = ["COLOR_LAB_HIST", "CLAHE_LUT", "CLAHE_APPLY", "BILATERAL", "SHARPEN", "NORM_LUT", "NORMALIZE", "WARP",
               "SQUARES", "GRAY_BLUR", "OTSU", "THRESHOLD", "SCAN", "SYNTH", "RESET", "HOUGH", "INGEST"]
@@ -497,12 +503,15 @@ def as_bgr(frame):
 
 
 def format_id(fmt):
-    """CBV_FMT_* of "bgr" | "nv12" | "nv21" | "yuv420p" | "yv12" | "yuyv" | "yvyu" | "uyvy".  The three-plane 4:2:0 format goes
-    by libav's name, "yuv420p" (cv2's COLOR_YUV2BGR_I420 / _IYUV); "i420" is an unknown format and raises ValueError."""
+    """CBV_FMT_* of "bgr" | "nv12" | "nv21" | "yuv420p" | "yv12" | "yuyv" | "yvyu" | "uyvy" | "bayer_rggb" | "bayer_bggr" |
+    "bayer_grbg" | "bayer_gbrg".  The three-plane 4:2:0 format goes by libav's name, "yuv420p" (cv2's COLOR_YUV2BGR_I420 /
+    _IYUV); "i420" is an unknown format and raises ValueError.  A Bayer layout goes by its top-left 2 x 2 block read row by
+    row (libav's bayer_rggb8, V4L2's SRGGB8); cv2 names the block at (1, 1), so "bayer_rggb" is COLOR_BayerBG2BGR."""
     try:
-        return FORMATS[fmt.lower()]
+        name = fmt.lower()
+        return FORMATS[name] if name in FORMATS else BAYER_FORMATS[name]
     except (KeyError, AttributeError):
-        raise ValueError("unknown frame format %r (expected one of %s)" % (fmt, ", ".join(FORMATS)))
+        raise ValueError("unknown frame format %r (expected one of %s)" % (fmt, ", ".join(list(FORMATS) + list(BAYER_FORMATS))))
 
 
 def _rows(a, what):
@@ -522,9 +531,21 @@ def raw_frame(frame, fmt):
     made contiguous first), or a triple of planes in the format's memory order, (y, u, v) for yuv420p and (y, v, u) for
     yv12, of shapes [h, w], [h // 2, w // 2], [h // 2, w // 2].  ("i420" is not a name: see format_id.)
     "yuyv" / "yvyu" / "uyvy": [h, w, 2].  "bgr": [h, w, 3].
+    "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg": one [h, w] array, w and h even and at least 4; a view whose
+    rows are contiguous is taken as it is, whatever its row stride.
     ValueError for other shapes and dtypes, an odd w, and an odd h of a 4:2:0 format."""
     f = format_id(fmt)
     name = fmt.upper()
+    if f & 15 == FMT_BAYER_RGGB:
+        a = np.asarray(frame) if not isinstance(frame, (tuple, list)) else None
+        if a is None or a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError("expected one uint8 HxW %s mosaic, got %s" % (name, _describe(frame)))
+        if a.shape[0] % 2 or a.shape[1] % 2 or min(a.shape) < 4:
+            raise ValueError("a %s frame has an even width and height of at least 4, got %s" % (name, a.shape))
+        a = _rows(a, "the %s frame" % name)
+        r = RawFrame()
+        r.fmt, r.stride0, r.plane0 = f, a.strides[0], a.ctypes.data
+        return r, a.shape[1], a.shape[0], (a,)
     odd_ok = f in (FMT_NV12, FMT_YUYV)   # these two leave odd sizes to the library's own check (a RuntimeError), as they always did
     r = RawFrame()
     r.fmt = f

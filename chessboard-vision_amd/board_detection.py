@@ -87,12 +87,33 @@ def yuv_to_bgr(frame, fmt):
     cbv_yuv_to_bgr): a new uint8 [h, w, 3] array.  `fmt` "nv12" / "nv21": one [h * 3 // 2, w] array or a (y, chroma) pair of
     planes; "yuv420p" / "yv12": one contiguous [h * 3 // 2, w] array or the three planes in memory order, (y, u, v) /
     (y, v, u); "yuyv" / "yvyu" / "uyvy": [h, w, 2].  cv2's I420 goes by libav's name "yuv420p"; "i420" is an unknown
-    format (ValueError).  Strided views are taken as they are (_native.raw_frame).  (A BoardPipeline takes such frames
-    directly: upload(fmt=...), set_input_format.)"""
+    format (ValueError).  Strided views are taken as they are (_native.raw_frame).  A Bayer mosaic ("bayer_rggb", ...) goes
+    to bayer_to_bgr and is refused here (ValueError).  (A BoardPipeline takes such frames directly: upload(fmt=...),
+    set_input_format.)"""
     from . import _native as N
+    if isinstance(fmt, str) and fmt.lower() in N.BAYER_FORMATS:
+        raise ValueError("yuv_to_bgr converts YUV frames; a %s mosaic goes to bayer_to_bgr" % fmt)
     raw, w, h, keep = N.raw_frame(frame, fmt)
     if raw.fmt == N.FMT_BGR:
         raise ValueError("yuv_to_bgr converts YUV frames (%s)" % ", ".join(k for k in N.FORMATS if k != "bgr"))
+    ctx = N.context()
+    out = np.empty((h, w, 3), np.uint8)
+    ctx.check(ctx.lib.cbv_yuv_to_bgr(ctx.h, raw, w, h, N.ptr(out), w * 3))
+    return out
+
+
+def bayer_to_bgr(frame, fmt):
+    """cv2.cvtColor(frame, COLOR_Bayer??2BGR), the bilinear demosaic of an 8-bit mosaic, on the GPU (include/cbv.h,
+    cbv_yuv_to_bgr with a Bayer format): a new uint8 [h, w, 3] array.  `fmt` "bayer_rggb" / "bayer_bggr" / "bayer_grbg" /
+    "bayer_gbrg" names the top-left 2 x 2 block read row by row; cv2 names its codes by the block at (1, 1), so
+    "bayer_rggb" is COLOR_BayerBG2BGR, "bayer_bggr" COLOR_BayerRG2BGR, "bayer_grbg" COLOR_BayerGB2BGR and "bayer_gbrg"
+    COLOR_BayerGR2BGR.  `frame` is one uint8 [h, w] array, w and h even and at least 4; strided views are taken as they are
+    (_native.raw_frame).  No white balance, gamma or colour matrix is applied.  (A BoardPipeline takes such frames
+    directly: upload(fmt=...), set_input_format.)"""
+    from . import _native as N
+    if not (isinstance(fmt, str) and fmt.lower() in N.BAYER_FORMATS):
+        raise ValueError("bayer_to_bgr converts Bayer mosaics (%s), got %r" % (", ".join(N.BAYER_FORMATS), fmt))
+    raw, w, h, keep = N.raw_frame(frame, fmt)
     ctx = N.context()
     out = np.empty((h, w, 3), np.uint8)
     ctx.check(ctx.lib.cbv_yuv_to_bgr(ctx.h, raw, w, h, N.ptr(out), w * 3))

@@ -354,15 +354,19 @@ int launch_synth(cbv_ctx* ctx, u8* dst, Geom g, const u64* seeds_dev, const doub
 
 // Raw (camera-native) frames of a batch for k_ingest: plane pointers are those of frame 0, frames `frame_stride` bytes apart
 struct RawGeom {
-    int fmt;                       // CBV_FMT_* of a YUV format
-    int stride0, stride1, stride2; // bytes per row of plane 0 (luma, or the packed 4:2:2 bytes) / plane 1 / plane 2, in memory order
+    int fmt;                       // CBV_FMT_* of a YUV or Bayer format
+    int stride0, stride1, stride2; // bytes per row of plane 0 (luma, the packed 4:2:2 bytes, or the mosaic) / plane 1 / plane 2, in memory order
     size_t frame_stride;
 };
 // the bit fields of a format id (include/cbv.h)
+static constexpr bool raw_fmt_bayer(int fmt)
+{
+    return fmt == CBV_FMT_BAYER_RGGB || fmt == CBV_FMT_BAYER_BGGR || fmt == CBV_FMT_BAYER_GRBG || fmt == CBV_FMT_BAYER_GBRG;
+}
 static inline bool raw_fmt_known(int fmt)
 {
     return fmt == CBV_FMT_NV12 || fmt == CBV_FMT_NV21 || fmt == CBV_FMT_YUV420P || fmt == CBV_FMT_YV12 || fmt == CBV_FMT_YUYV ||
-           fmt == CBV_FMT_YVYU || fmt == CBV_FMT_UYVY;
+           fmt == CBV_FMT_YVYU || fmt == CBV_FMT_UYVY || raw_fmt_bayer(fmt);
 }
 static inline bool raw_fmt_420(int fmt) { return (fmt & 15) == CBV_FMT_NV12; }
 static inline int raw_fmt_planes(int fmt) { return !raw_fmt_420(fmt) ? 1 : (fmt & 0x20) ? 3 : 2; }
@@ -376,18 +380,25 @@ static inline const char* raw_fmt_name(int fmt)
     case CBV_FMT_YUYV: return "YUYV";
     case CBV_FMT_YVYU: return "YVYU";
     case CBV_FMT_UYVY: return "UYVY";
+    case CBV_FMT_BAYER_RGGB: return "BAYER_RGGB";
+    case CBV_FMT_BAYER_BGGR: return "BAYER_BGGR";
+    case CBV_FMT_BAYER_GRBG: return "BAYER_GRBG";
+    case CBV_FMT_BAYER_GBRG: return "BAYER_GBRG";
     }
     return "?";
 }
 // bytes per row of plane `i` of a w-wide frame (0: the format has no such plane)
 static inline int raw_plane_wbytes(int fmt, int w, int i)
 {
-    if (i == 0) return raw_fmt_420(fmt) ? w : 2 * w;
+    if (i == 0) return raw_fmt_420(fmt) || raw_fmt_bayer(fmt) ? w : 2 * w;
     return i >= raw_fmt_planes(fmt) ? 0 : raw_fmt_planes(fmt) == 3 ? w / 2 : w;
 }
 static inline int raw_plane_rows(int fmt, int h, int i) { return i == 0 ? h : h / 2; }
 // tightly packed raw frames, planes back to back, each frame rounded to 256 bytes (the ingest rings); fmt BGR: tight_geom's frame_stride
-static inline size_t raw_frame_bytes(int fmt, int w, int h) { return raw_fmt_420(fmt) ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_BGR ? 3 : 2); }
+static inline size_t raw_frame_bytes(int fmt, int w, int h)
+{
+    return raw_fmt_420(fmt) ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_BGR ? 3 : raw_fmt_bayer(fmt) ? 1 : 2);
+}
 static inline RawGeom tight_raw_geom(int fmt, int w, int h)
 {
     RawGeom r;
@@ -410,13 +421,15 @@ static inline RawPlanes tight_raw_planes(int fmt, int w, int h, const u8* base)
     if (n > 2) r.p[2] = r.p[1] + (size_t)(w / 2) * (h / 2);
     return r;
 }
-// CBV_ERR_ARG unless fmt is a YUV format and w (and h, for the 4:2:0 formats) is even
+// CBV_ERR_ARG unless fmt is a YUV format and w (and h, for the 4:2:0 formats) is even, or a Bayer format and w and h are
+// even and at least 4
 int check_raw_format(cbv_ctx* ctx, int fmt, int w, int h, const char* what);
 // CBV_ERR_ARG unless every plane the format has is there with rows of at least their length
 int check_raw_planes(cbv_ctx* ctx, int fmt, int w, const u8* const* planes, const int* strides, const char* what);
 // YV12 -> YUV420P with the chroma planes (and their strides) swapped: the kernels have no YV12 form
 void raw_planes_canonical(RawPlanes* planes, RawGeom* r);
-// cv2.cvtColor COLOR_YUV2BGR_* of `batch` raw frames into BGR frames of geometry g (k_ingest.hip); planes in memory order
+// cv2.cvtColor COLOR_YUV2BGR_* / COLOR_Bayer??2BGR of `batch` raw frames into BGR frames of geometry g (k_ingest.hip); planes
+// in memory order
 int launch_ingest(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, int batch);
 // the planes and strides a host frame's format has; null / 0 for the rest, whose fields are not read
 void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides);
@@ -430,6 +443,11 @@ int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* ds
 // 256); between rows, planes and frames the bytes read belong to the next row, plane or frame.
 int launch_warp_yuv(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180,
                     u8* dst, int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
+
+// launch_warp_yuv for the Bayer family (k_warp_bayer): the four taps are demosaiced before the blend.  No byte outside the
+// frames' rows is read.
+int launch_warp_bayer(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180,
+                      u8* dst, int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 
 void build_gaussian_q8_sigma(int k, double sigma, int* coef);
 int launch_gray_gauss(cbv_ctx* ctx, const u8* src, int w, int h, int stride, int cn, const int* coef_dev, int k, u8* dst);
@@ -643,6 +661,8 @@ int launch_warp_profile_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* 
                            u32* zero_word, u32* zero_word2);
 int launch_warp_yuv_mb(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
                        int batch, u32* zero_word, u32* zero_word2);
+int launch_warp_bayer_mb(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
+                         int batch, u32* zero_word, u32* zero_word2);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);

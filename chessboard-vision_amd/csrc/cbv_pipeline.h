@@ -89,7 +89,7 @@ struct Pipe {
     // k_ingest converts into `frames` behind the copy
     u8* host_ring = nullptr;
     int in_fmt = CBV_FMT_BGR;
-    // Without enhancement (skip_enhance) a YUV input format makes the raw ring THE frames: k_warp_yuv samples it, nothing is
+    // Without enhancement (skip_enhance) a YUV or Bayer input format makes the raw ring THE frames: k_warp_yuv / k_warp_bayer samples it, nothing is
     // converted and `frames` is neither written nor read (raw_mode below).
     u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated on first use; null with CBV_FMT_BGR
     hipStream_t copy_stream = nullptr;

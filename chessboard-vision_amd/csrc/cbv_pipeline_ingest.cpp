@@ -3,7 +3,7 @@
 #include "cbv_pipeline.h"
 
 // the raw-frame mode (Pipe::raw_mode) has no BGR frames to write
-static const char* const kRawModeMsg = "the pipeline runs without enhancement on a YUV input format (raw mode): its frames are the raw "
+static const char* const kRawModeMsg = "the pipeline runs without enhancement on a YUV or Bayer input format (raw mode): its frames are the raw "
                                        "ring, written by cbv_pipeline_upload_raw or cbv_pipeline_submit in that format";
 
 // the planes of slot `slot` of the device ring of raw frames

@@ -20,7 +20,8 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     if (P.boards.size() > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         const int nb = (int)P.boards.size();
-        if (raw0) RC(launch_warp_yuv_mb(ctx, raw, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
+        if (raw0 && raw_fmt_bayer(rg.fmt)) RC(launch_warp_bayer_mb(ctx, raw, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
+        else if (raw0) RC(launch_warp_yuv_mb(ctx, raw, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
         else if (P.profile_on) RC(launch_warp_profile_mb(ctx, res, P.g, tab, nb, P.max_S, s0, (const ProfileTabs*)P.d_ptabs.p, b, work, retry0));
         else RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
@@ -33,7 +34,8 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     u8* gray = T.gray + T.plane_total * s0;
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
     cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
-    if (raw0) RC(launch_warp_yuv(ctx, raw, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
+    if (raw0 && raw_fmt_bayer(rg.fmt)) RC(launch_warp_bayer(ctx, raw, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
+    else if (raw0) RC(launch_warp_yuv(ctx, raw, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
     else if (P.profile_on)
         RC(launch_warp_profile(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, 0, (const ProfileTabs*)P.d_ptabs.p, 1, b, work,
                                retry0));

@@ -9,6 +9,7 @@
 // operation; coordinates are quantised to 1/32 px and sampled with the 15-bit
 // fixed-point bilinear table of remap().
 // Also here: the synthetic frame generator used by bench/tests.
+#include "cbv_bayer.h"
 #include "cbv_profile_px.h"
 #include "cbv_yuv.h"
 
@@ -352,6 +353,105 @@ __global__ __launch_bounds__(256) void k_warp_yuv_mb(const u8* __restrict__ p0, 
 }
 
 // ---------------------------------------------------------------------------
+// The warp straight from 8-bit Bayer mosaics (pipelines without enhancement whose input format is a Bayer format):
+// k_warp_yuv's gather with the four taps demosaiced (d_bayer_bgr, cbv_bayer.h) before the blend.  A tap is a pixel of the
+// frame k_ingest would write, so demosaicing the taps and blending them is, bit for bit, sampling that frame: same
+// coordinates (warp_taps), same conversion, same blend (warp_blend).  A tap outside the frame is BGR (0, 0, 0); a tap on
+// the frame's outermost rows or columns is the result of the clamped site, as in k_ingest.
+// ---------------------------------------------------------------------------
+// pixel (x, y) of one mosaic, inside the frame, with byte loads: the site is clamped, its neighbourhood lies inside
+template <int FMT>
+__device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride, int w, int h, int x, int y)
+{
+    const int cx = min(max(x, 1), w - 2), cy = min(max(y, 1), h - 2);
+    const u8* m = f0 + (size_t)cy * stride + cx;
+    u32 row[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const u8* q = m + (ptrdiff_t)(i - 1) * stride;
+        row[i] = (u32)q[-1] | ((u32)q[0] << 8) | ((u32)q[1] << 16);
+    }
+    return d_bayer_bgr<FMT>(cx, cy, row[0], row[1], row[2]);
+}
+
+// Pixels whose four taps are all interior sites (1 <= sx, sx + 1 <= w - 2, the same in y): the taps' 3 x 3 neighbourhoods
+// lie in the 4 x 4 bytes at (sx - 1, sy - 1), which is four unaligned 4-byte loads per frame, inside the frame's rows.
+// Everything else with a tap inside the frame takes d_bayer_px per tap.
+template <int FMT, int FPT>
+__device__ __forceinline__ void warp_bayer_body(const u8* __restrict__ p0, RawGeom r, int sw, int sh, const double* __restrict__ M, int dw, int dh,
+                                                int bw0, int rot180, u8* __restrict__ dst, int dst_stride, size_t dst_frame_stride,
+                                                u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
+{
+    warp_zero_words(zero_word, zero_word2);
+    const int f0 = bz * FPT;
+    const int nf = min(FPT, batch - f0);
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= dw || dy >= dh) return;
+    const WarpTaps t = warp_taps(dx, dy, sw, sh, M, dw, dh, bw0, rot180, dst_stride);
+    const bool inner = t.sx >= 1 && t.sx + 2 < sw && t.sy >= 1 && t.sy + 2 < sh;
+    const size_t off = (size_t)(t.sy - 1) * r.stride0 + (size_t)(t.sx - 1); // (only used where inner)
+    u32 rows[FPT][4];
+    if (inner)
+#pragma unroll
+        for (int k = 0; k < FPT; k++)
+            if (k < nf) {
+                const u8* m = p0 + (size_t)(f0 + k) * r.frame_stride + off;
+#pragma unroll
+                for (int i = 0; i < 4; i++) __builtin_memcpy(&rows[k][i], m + (size_t)i * r.stride0, 4);
+            }
+#pragma unroll
+    for (int k = 0; k < FPT; k++) {
+        if (k >= nf) break;
+        int o[3] = {0, 0, 0};
+        if (t.any_in) {
+            u32 q[4] = {0u, 0u, 0u, 0u}; // taps 00, 01, 10, 11 as b | g << 8 | r << 16; border taps are 0
+            if (inner) {
+                const u32* w = rows[k];
+                q[0] = d_bayer_bgr<FMT>(t.sx, t.sy, w[0], w[1], w[2]);
+                q[1] = d_bayer_bgr<FMT>(t.sx + 1, t.sy, w[0] >> 8, w[1] >> 8, w[2] >> 8);
+                q[2] = d_bayer_bgr<FMT>(t.sx, t.sy + 1, w[1], w[2], w[3]);
+                q[3] = d_bayer_bgr<FMT>(t.sx + 1, t.sy + 1, w[1] >> 8, w[2] >> 8, w[3] >> 8);
+            } else {
+                const u8* fp = p0 + (size_t)(f0 + k) * r.frame_stride;
+                if (t.x0in && t.y0in) q[0] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx, t.sy);
+                if (t.x1in && t.y0in) q[1] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx + 1, t.sy);
+                if (t.x0in && t.y1in) q[2] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx, t.sy + 1);
+                if (t.x1in && t.y1in) q[3] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx + 1, t.sy + 1);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                o[c] = warp_blend((int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255),
+                                  (int)((q[3] >> (8 * c)) & 255), t);
+        }
+        u8* out = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
+        out[0] = (u8)o[0];
+        out[1] = (u8)o[1];
+        out[2] = (u8)o[2];
+    }
+}
+
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_bayer(const u8* __restrict__ p0, RawGeom r, int sw, int sh, WarpM M, int dw, int dh, int bw0, int rot180,
+                                                     u8* __restrict__ dst, int dst_stride, size_t dst_frame_stride, u32* __restrict__ zero_word,
+                                                     u32* __restrict__ zero_word2, int batch)
+{
+    warp_bayer_body<FMT, FPT>(p0, r, sw, sh, M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch, blockIdx.z);
+}
+
+// every board of a pipeline in one launch, as k_warp_mb
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_bayer_mb(const u8* __restrict__ p0, RawGeom r, int sw, int sh, const BoardDev* __restrict__ tab, int nz,
+                                                        int s0, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
+    warp_bayer_body<FMT, FPT>(p0, r, sw, sh, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride,
+                              zero_word, zero_word2, batch, blockIdx.z - b * nz);
+}
+
+// ---------------------------------------------------------------------------
 // The warp with the colour profile applied to its taps (cbv_warp_color_profile, pipelines configured with
 // CBV_SKIP_ENHANCE_PROFILE, cbv_pipeline_color_sweep): apply_color_profile is a function of the pixel alone, so converting
 // the four taps and blending them is, byte for byte, sampling the converted frame: same coordinates (warp_taps), same
@@ -645,6 +745,70 @@ int launch_warp_yuv_mb(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const Boar
     CBV_WARP_YUV_FORMATS(CBV_WARP_YUV_MB)
 #undef CBV_WARP_YUV_MB
 #undef CBV_WARP_YUV_MB_K
+    prof_end(ctx, CBV_K_WARP_YUV);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+// the mosaics a fused warp may read: what launch_ingest asks of them
+static int check_warp_bayer(cbv_ctx* ctx, const RawPlanes& pl, const RawGeom& r, Geom g, int batch)
+{
+    RC(check_raw_format(ctx, r.fmt, g.w, g.h, "launch_warp_bayer"));
+    if (!raw_fmt_bayer(r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_bayer: format %d is not a Bayer format", r.fmt);
+    if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_bayer: bad planes or strides");
+    const int strides[3] = {r.stride0, r.stride1, r.stride2};
+    return check_raw_planes(ctx, r.fmt, g.w, pl.p, strides, "launch_warp_bayer");
+}
+
+#define CBV_WARP_BAYER_FORMATS(LAUNCH)                                 \
+    switch (r.fmt) {                                                   \
+    case CBV_FMT_BAYER_RGGB: LAUNCH(CBV_FMT_BAYER_RGGB); break;        \
+    case CBV_FMT_BAYER_BGGR: LAUNCH(CBV_FMT_BAYER_BGGR); break;        \
+    case CBV_FMT_BAYER_GRBG: LAUNCH(CBV_FMT_BAYER_GRBG); break;        \
+    default: LAUNCH(CBV_FMT_BAYER_GBRG);                               \
+    }
+
+// as launch_warp_yuv: four frames per thread in batched launches, one thread per pixel and frame in a launch of a frame or two
+int launch_warp_bayer(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
+                      size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2)
+{
+    RC(check_warp_bayer(ctx, pl, r, g, batch));
+    WarpM M;
+    for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
+    int bw0, bh0;
+    warp_block_shape(dw, dh, &bw0, &bh0);
+    const int fpt = batch >= 8 ? 4 : 1;
+    const dim3 grid((dw + 63) / 64, (dh + 3) / 4, (batch + fpt - 1) / fpt);
+    prof_begin(ctx, CBV_K_WARP_YUV);
+#define CBV_WARP_BAYER_K(FMT, FPT)                                                                                                      \
+    hipLaunchKernelGGL((k_warp_bayer<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], r, g.w, g.h, M, dw, dh, bw0, rot180, dst, dst_stride, \
+                       dst_frame_stride, zero_word, zero_word2, batch)
+#define CBV_WARP_BAYER(FMT)                 \
+    if (fpt == 4) CBV_WARP_BAYER_K(FMT, 4); \
+    else CBV_WARP_BAYER_K(FMT, 1)
+    CBV_WARP_BAYER_FORMATS(CBV_WARP_BAYER)
+#undef CBV_WARP_BAYER
+#undef CBV_WARP_BAYER_K
+    prof_end(ctx, CBV_K_WARP_YUV);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_warp_bayer_mb(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word,
+                         u32* zero_word2)
+{
+    RC(check_warp_bayer(ctx, pl, r, g, batch));
+    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
+    const dim3 grid((maxS + 63) / 64, (maxS + 3) / 4, nz * nb);
+    prof_begin(ctx, CBV_K_WARP_YUV);
+#define CBV_WARP_BAYER_MB_K(FMT, FPT)                                                                                                  \
+    hipLaunchKernelGGL((k_warp_bayer_mb<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], r, g.w, g.h, tab, nz, s0, zero_word, zero_word2, batch)
+#define CBV_WARP_BAYER_MB(FMT)                 \
+    if (fpt == 4) CBV_WARP_BAYER_MB_K(FMT, 4); \
+    else CBV_WARP_BAYER_MB_K(FMT, 1)
+    CBV_WARP_BAYER_FORMATS(CBV_WARP_BAYER_MB)
+#undef CBV_WARP_BAYER_MB
+#undef CBV_WARP_BAYER_MB_K
     prof_end(ctx, CBV_K_WARP_YUV);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;

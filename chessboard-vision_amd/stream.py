@@ -711,8 +711,10 @@ class BoardPipeline(_BoardMethods):
         """One frame into a slot, synchronous.  `fmt` "nv12" / "nv21" (one [h * 3 // 2, w] array or a (y, chroma) pair of
         possibly strided views), "yuv420p" / "yv12" (one contiguous [h * 3 // 2, w] array or the three planes in memory
         order, (y, u, v) / (y, v, u)) and "yuyv" / "yvyu" / "uyvy" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h,
-        cbv_pipeline_upload_raw; "i420" is not a name, the format is "yuv420p"); in raw mode (`configure(enhance=False)` with
-        a YUV `set_input_format`) the frame is stored as it is."""
+        cbv_pipeline_upload_raw; "i420" is not a name, the format is "yuv420p"), and so are the 8-bit Bayer mosaics
+        "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg" (one [h, w] array, named by the top-left 2 x 2 block:
+        cv2's COLOR_BayerBG2BGR is "bayer_rggb"); in raw mode (`configure(enhance=False)` with a YUV or Bayer
+        `set_input_format`) the frame is stored as it is."""
         if N.format_id(fmt) == N.FMT_BGR:
             f = N.as_bgr(frame)
             assert f.shape[:2] == (self.h, self.w)
@@ -725,7 +727,9 @@ class BoardPipeline(_BoardMethods):
 
     def set_input_format(self, fmt):
         """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12", "nv21", "yuv420p"
-        (cv2's I420; "i420" itself is an unknown format), "yv12", "yuyv", "yvyu" or "uyvy".  Raw frames cross PCIe as they are and are converted to BGR on the GPU behind their copy.  The ring is freed here and
+        (cv2's I420; "i420" itself is an unknown format), "yv12", "yuyv", "yvyu", "uyvy", or an 8-bit Bayer mosaic
+        "bayer_rggb", "bayer_bggr", "bayer_grbg" or "bayer_gbrg" (w and h even and at least 4).  Raw frames cross PCIe as
+        they are and are converted to BGR on the GPU behind their copy.  The ring is freed here and
         allocated again by the next `host_ring()`: an array that call returned earlier must not be touched any more."""
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt)))
         self.input_format = fmt.lower()
@@ -734,7 +738,8 @@ class BoardPipeline(_BoardMethods):
         """Pinned host mirror of the frame ring as a numpy array: the capture side writes frames here, `submit` copies
         them to the GPU asynchronously.  [max_frames, h, w, 3] for BGR; [max_frames, h * 3 // 2, w] for the 4:2:0 layouts
         (luma rows, then the chroma rows of NV12 / NV21, or the two chroma planes of yuv420p / yv12 back to back, each
-        h // 2 rows of w // 2 bytes); [max_frames, h, w, 2] for YUYV, YVYU and UYVY (`set_input_format`)."""
+        h // 2 rows of w // 2 bytes); [max_frames, h, w, 2] for YUYV, YVYU and UYVY; [max_frames, h, w] for the Bayer
+        mosaics (`set_input_format`)."""
         ptr = self.ctx.lib.cbv_pipeline_host_ring(self.h_)
         if not ptr:
             raise RuntimeError(self.ctx.lib.cbv_last_error(self.ctx.h).decode())
@@ -746,6 +751,8 @@ class BoardPipeline(_BoardMethods):
             shape, strides = (h, w, 3), (w * 3, 3, 1)
         elif self.input_format in N.FORMATS_420:
             shape, strides = (h * 3 // 2, w), (w, 1)
+        elif self.input_format in N.BAYER_FORMATS:
+            shape, strides = (h, w), (w, 1)
         else:
             shape, strides = (h, w, 2), (w * 2, 2, 1)
         return np.lib.stride_tricks.as_strided(flat, shape=(self.max_frames,) + shape, strides=(fs,) + strides)

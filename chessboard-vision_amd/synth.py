@@ -93,3 +93,13 @@ def position_for_frame(frame_idx, frames_per_ply=32):
 
 def frame_seed(stream_id, frame_idx):
     return (0xC0FFEE + (stream_id << 32) + frame_idx) & 0xFFFFFFFFFFFFFFFF
+
+
+def bayer_mosaic(bgr, fmt):
+    """The 8-bit Bayer mosaic a sensor with layout `fmt` ("bayer_rggb", "bayer_bggr", "bayer_grbg", "bayer_gbrg": the
+    top-left 2 x 2 block read row by row) would deliver of a BGR frame: each pixel keeps its one colour.  [h, w] uint8."""
+    block = ["bgr".index(c) for c in fmt.lower()[-4:]]
+    out = np.empty(bgr.shape[:2], np.uint8)
+    for i, c in enumerate(block):
+        out[i >> 1::2, i & 1::2] = bgr[i >> 1::2, i & 1::2, c]
+    return out

@@ -481,7 +481,7 @@ CBV_API int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats* o
 CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out);
 
 /* ------------------------------------------------------------------ */
-/* camera-native frames (NV12, NV21, yuv420p, YV12, YUYV, YVYU, UYVY), converted to BGR on the device */
+/* camera-native frames (NV12, NV21, yuv420p, YV12, YUYV, YVYU, UYVY, 8-bit Bayer), converted to BGR on the device */
 /* ------------------------------------------------------------------ */
 /* Cameras deliver YUYV / UYVY / YVYU, hardware decoders NV12 / NV21 and software decoders yuv420p / YV12;
  * cv2.VideoCapture converts them to BGR on a host core before the application sees a frame.  Here the raw frame crosses
@@ -512,6 +512,39 @@ CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out)
 #define CBV_FMT_YVYU    0x12
 #define CBV_FMT_UYVY    0x22
 
+/* 8-bit Bayer mosaics (machine-vision cameras, the raw mode of most sensors): one plane of h rows of w bytes, one byte and
+ * one colour per pixel, a third of BGR's bytes.  The conversion is the bilinear demosaic of
+ * cv2.cvtColor(raw, COLOR_Bayer??2BGR) on 8-bit data (not the _VNG or _EA variants); no white balance, gamma or colour
+ * matrix is applied.  A layout is named by its top-left 2 x 2 block, read row by row.  OpenCV names its codes by the block
+ * at (1, 1) instead, so the code of a layout carries the OTHER pair of letters:
+ *     id                        rows 0 / 1     cv2 code                                     libav / V4L2
+ *     CBV_FMT_BAYER_RGGB 0x04   R G / G B      COLOR_BayerBG2BGR (= COLOR_BayerRGGB2BGR)    bayer_rggb8 / SRGGB8
+ *     CBV_FMT_BAYER_BGGR 0x14   B G / G R      COLOR_BayerRG2BGR (= COLOR_BayerBGGR2BGR)    bayer_bggr8 / SBGGR8
+ *     CBV_FMT_BAYER_GRBG 0x24   G R / B G      COLOR_BayerGB2BGR (= COLOR_BayerGRBG2BGR)    bayer_grbg8 / SGRBG8
+ *     CBV_FMT_BAYER_GBRG 0x34   G B / R G      COLOR_BayerGR2BGR (= COLOR_BayerGBRG2BGR)    bayer_gbrg8 / SGBRG8
+ * The ids are bit fields like those above: the low nibble 4 is the family, 0x10 = blue sits where RGGB has red, 0x20 = the
+ * row starts with green.  Site (x, y) carries the colour of (x & 1, y & 1) in the 2 x 2 block; p(x, y) is the raw byte.
+ * Interior (1 <= x <= w - 2, 1 <= y <= h - 2), value D(x, y):
+ *   a red or blue site, own colour C:
+ *     C = p(x, y)
+ *     G = (p(x-1,y) + p(x+1,y) + p(x,y-1) + p(x,y+1) + 2) >> 2
+ *     the other of red / blue = (p(x-1,y-1) + p(x+1,y-1) + p(x-1,y+1) + p(x+1,y+1) + 2) >> 2
+ *   a green site:
+ *     G = p(x, y)
+ *     the colour whose samples lie in this row              = (p(x-1,y) + p(x+1,y) + 1) >> 1
+ *     the colour whose samples lie in the rows above, below = (p(x,y-1) + p(x,y+1) + 1) >> 1
+ * which is "each missing colour is the mean of the nearest samples of that colour, rounded half up".
+ * Frame edge: the outermost rows and columns copy their neighbours' results,
+ *     out(x, y) = D(clamp(x, 1, w - 2), clamp(y, 1, h - 2)),
+ * as OpenCV fills them (the left and right pixel of each row from columns 1 and w - 2, then the first and last row from
+ * rows 1 and h - 2).  w and h must be even and at least 4: otherwise CBV_ERR_ARG, and nothing has changed.
+ * Like the YUV conversion above this is restated from the published algorithm and is not pinned
+ * against a cv2 build. */
+#define CBV_FMT_BAYER_RGGB 0x04
+#define CBV_FMT_BAYER_BGGR 0x14
+#define CBV_FMT_BAYER_GRBG 0x24
+#define CBV_FMT_BAYER_GBRG 0x34
+
 /* One raw frame in host memory.  stride2 and plane2 are read only for the three-plane formats (YUV420P, YV12): stride2
  * lies in what was padding and plane2 behind what was the end of the struct, so a caller built against the 32-byte struct
  * of the two-plane formats keeps working. */
@@ -519,12 +552,12 @@ typedef struct {
     int32_t fmt;            /* CBV_FMT_* */
     int32_t stride0, stride1;   /* bytes per row of plane0 / plane1 */
     int32_t stride2;        /* bytes per row of plane2 */
-    const uint8_t* plane0;  /* BGR, the packed 4:2:2 bytes, or the luma plane */
+    const uint8_t* plane0;  /* BGR, the packed 4:2:2 bytes, the Bayer mosaic, or the luma plane */
     const uint8_t* plane1;  /* NV12 / NV21 chroma plane, YUV420P's U or YV12's V plane, else NULL */
     const uint8_t* plane2;  /* YUV420P's V or YV12's U plane */
 } cbv_raw_frame;
 
-/* host in, host out: the cvtColor call on its own (fmt = any CBV_FMT_* but BGR) */
+/* host in, host out: the cvtColor call on its own (fmt = any CBV_FMT_* but BGR, the Bayer mosaics included) */
 CBV_API int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride);
 /* one frame of any format into a slot of the frame ring, synchronous, like cbv_pipeline_upload */
 CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_frame* raw);
@@ -534,10 +567,11 @@ CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_fra
  * to 256 bytes: cbv_pipeline_host_slot_bytes).  With a YUV format cbv_pipeline_submit copies the raw slots to a device
  * ring of the same layout and converts them into the BGR frame ring behind the copy; its ordering promises are the
  * same (a run of the slots waits for the copy and its conversion).  On the pipeline only (a board handle:
- * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, or odd h with a 4:2:0 format, and then nothing has changed.
- * Raw mode: on a pipeline configured with skip_enhance a YUV format makes the raw ring THE frames.  cbv_pipeline_submit
+ * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, odd h with a 4:2:0 or Bayer format, or a Bayer frame below
+ * 4 x 4, and then nothing has changed.
+ * Raw mode: on a pipeline configured with skip_enhance a YUV or Bayer format makes the raw ring THE frames.  cbv_pipeline_submit
  * only copies the raw slots, cbv_pipeline_upload_raw (that format only) writes a raw slot, cbv_pipeline_run warps straight
- * from the raw frames (k_warp_yuv: byte for byte what the conversion followed by the warp gives) and no BGR frame is ever
+ * from the raw frames (k_warp_yuv, k_warp_bayer: byte for byte what the conversion followed by the warp gives) and no BGR frame is ever
  * written; cbv_pipeline_upload (BGR), cbv_pipeline_synth and cbv_pipeline_upload_raw in another format return
  * CBV_ERR_STATE, cbv_pipeline_download(which = 0) converts the slot on demand.  One format per pipeline at a time. */
 CBV_API int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt);

@@ -4,7 +4,8 @@ overlapped rates per input format, all from one process:
 
     python tools/ingest_timing.py --format all --reps 3
 
-With a YUV format ("nv12", "nv21", "yuv420p", "yv12", "yuyv", "yvyu", "uyvy") the ring holds raw frames (BoardPipeline.set_input_format) and a submit is the copy plus the
+With a YUV format ("nv12", "nv21", "yuv420p", "yv12", "yuyv", "yvyu", "uyvy") or a Bayer format ("bayer_rggb",
+"bayer_bggr", "bayer_grbg", "bayer_gbrg": the frames sampled to a mosaic, synth.bayer_mosaic) the ring holds raw frames (BoardPipeline.set_input_format) and a submit is the copy plus the
 conversion kernel; "H2D only" then includes that kernel.  `--reps` alternates the formats and prints every repetition
 and, for each format, the ratio to BGR of the same repetition."""
 import argparse
@@ -19,10 +20,13 @@ from chessboard_vision_amd import synth as S  # noqa: E402
 from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--format", default="bgr", choices=list(N.FORMATS) + ["all"])
+ALL = list(N.FORMATS) + list(N.BAYER_FORMATS)
+ap.add_argument("--format", default="bgr", help="one of %s, a comma-separated list of them, or all" % ", ".join(ALL))
 ap.add_argument("--reps", type=int, default=1)
 args = ap.parse_args()
-formats = list(N.FORMATS) if args.format == "all" else [args.format]
+formats = ALL if args.format == "all" else args.format.split(",")
+for f in formats:
+    N.format_id(f)
 
 W, H, HALF, ROUNDS = 1920, 1080, 128, 6
 n = 2 * HALF
@@ -36,6 +40,8 @@ def to_raw(f, fmt):
     """a camera-native frame of a BGR one (float BT.601 forward transform, chroma of the first pixel of each block)"""
     if fmt == "bgr":
         return f
+    if fmt in N.BAYER_FORMATS:
+        return S.bayer_mosaic(f, fmt)
     b, g, r = (f[..., i].astype(np.float32) for i in range(3))
     q = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
     y, u, v = q(16 + 0.257 * r + 0.504 * g + 0.098 * b), q(128 - 0.148 * r - 0.291 * g + 0.439 * b), q(128 + 0.439 * r - 0.368 * g - 0.071 * b)
@@ -64,7 +70,7 @@ def measure(fmt):
     p.submit(0, n)
     p.run(0, n)
     sync()
-    # H2D only (+ the conversion of a YUV format)
+    # H2D only (+ the conversion of a YUV or Bayer format)
     t0 = time.perf_counter()
     for r in range(ROUNDS):
         p.submit(0, HALF)

@@ -1,11 +1,12 @@
-"""What the session chain (BoardPipeline.configure(enhance=False)) and the warp from raw frames (k_warp_yuv) are worth.
+"""What the session chain (BoardPipeline.configure(enhance=False)) and the warp from raw frames (k_warp_yuv, k_warp_bayer)
+are worth.
 Prints ONE JSON object:
 
-  fused     per-frame kernel time of k_warp_yuv against k_ingest + k_warp (cbv_profile_read event pairs), every YUV format
+  fused     per-frame kernel time of k_warp_yuv / k_warp_bayer against k_ingest + k_warp (cbv_profile_read event pairs), every YUV and Bayer format
             (`--formats` picks some), 1080p and 4K, batches larger than the Infinity Cache, `--rounds` alternating rounds, each listed
   resident  frames/s with enhance=False against enhance=True: device-resident BGR, 512 frames in flight, 1080p and 4K,
             1 and 4 boards (median and spread of `--reps` steps)
-  host_fed  frames/s of YUV frames fed through the pinned ring in two halves, the copy of one half overlapping the
+  host_fed  frames/s of YUV and Bayer frames fed through the pinned ring in two halves, the copy of one half overlapping the
             run of the other; the copy alone and the runs alone beside it say which of the two limits the rate
   latency   wall time of run + results of one frame
 
@@ -26,7 +27,7 @@ from chessboard_vision_amd import synth as S  # noqa: E402
 from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
 
 SIZES = {"1080p": (1920, 1080), "4k": (3840, 2160)}
-FMTS = tuple(f for f in N.FORMATS if f != "bgr")
+FMTS = tuple(f for f in N.FORMATS if f != "bgr") + tuple(N.BAYER_FORMATS)
 
 
 def spread(v):
@@ -53,6 +54,11 @@ def fused_against_unfused(size, fmt, n, rounds):
     ing.configure(pts, profile=S.SHIPPED_PROFILE, chunk=1, lanes=1)
     ing.set_input_format(fmt)
     ing.host_ring()[:] = 96
+    if fmt in N.BAYER_FORMATS:  # a mosaic of a scene instead of one level: the frames k_warp samples, as a sensor would deliver them
+        bgr0 = BoardPipeline(w, h, 1)
+        bgr0.synth(0, 1, scene="normal")
+        ing.host_ring()[:] = S.bayer_mosaic(bgr0.download(0, 0), fmt)
+        bgr0.close()
     bgr = BoardPipeline(w, h, n)  # k_warp on BGR frames, no byte map: the unfused chain's second kernel
     bgr.configure(pts, chunk=n, lanes=1, use_hough=False, enhance=False)
     bgr.synth(0, n, scene="normal", frames_per_ply=32)
@@ -192,7 +198,8 @@ def main():
     ctx = N.context()
     out = dict(device=ctx.lib.cbv_device_name(ctx.h).decode())
     if "fused" in a.only:
-        # raw batches of 384 / 512 MiB (NV12 / YUYV at 1080p: 128 frames) and more: beyond the 256 MiB Infinity Cache
+        # raw batches of 384 / 512 MiB (NV12 / YUYV at 1080p: 128 frames; a Bayer batch is 253 MiB of mosaics, and the warped
+        # frames written beside it are 141 MiB more) and more: beyond the 256 MiB Infinity Cache
         out["fused"] = [fused_against_unfused(s, f, 16 if a.quick else {"1080p": 128, "4k": 40}[s], a.rounds) for s in sizes for f in fmts]
     if "resident" in a.only:
         out["resident"] = [resident(s, k, 32 if a.quick else 512, a.reps) for s in sizes for k in (1, 4)]
