@@ -1134,6 +1134,8 @@ int hough_cfg(cbv_ctx* ctx, const cbv_hough_params* prm, const std::vector<Squar
     for (const SquareDesc& d : descs) {
         hc->maxw = std::max(hc->maxw, d.w);
         hc->maxh = std::max(hc->maxh, d.h);
+        const int m = std::min(d.w, d.h);
+        hc->min_dim = hc->min_dim == 0 ? m : std::min(hc->min_dim, m);
     }
     return CBV_OK;
 }

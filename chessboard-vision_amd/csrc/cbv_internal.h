@@ -495,8 +495,11 @@ struct HoughCfg {
     int canny_thr, acc_thr;
     double min_ratio, max_ratio;
     int maxw, maxh; // largest square of the set
+    int min_dim;    // shortest side of any square of the set (0: not known, taken as 2)
     int gs, mw, mag_bytes; // padded row strides of the gray/map planes (bytes) and the magnitude plane (u16)
     int off_map, off_mag, off_acc, off_centres, off_bins, off_order, max_bins;
+    int off_g, off_circ; // the gray plane; the candidate circles of P6 (over planes that are dead by then)
+    int keep_acc;        // the accumulator outlives P6 (k_piece_sweep_hough re-reads it per setting): nothing may overlay it
     u32* overflow_count; // device counter of squares whose candidate list overflowed (CBV_HOUGH_OVERFLOW), or null
     int maxc;            // accumulator maxima / candidate circles kept per square (set by launch_hough)
     u32* retry;          // first pass: squares with more than `maxc` maxima are listed here (count, then frame << 8 | square)

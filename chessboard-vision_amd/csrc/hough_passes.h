@@ -61,6 +61,10 @@ __device__ __forceinline__ void hg_sobel(const u8* g, int gs, int x, int y, int&
     dy = (p - a) + 2 * (q - b) + (r - c);
 }
 
+// n / d by the reciprocal ceil(2^32 / d) that hg_square stores.  For d = 1 (a square at most four pixels wide has one
+// group a row; an accumulator with dp >= w has one column) that is 2^32, which a u32 holds as 0: the quotient is n itself.
+__device__ __forceinline__ int hg_div(int n, u32 inv) { return inv ? (int)__umulhi((u32)n, inv) : n; }
+
 __device__ __forceinline__ int hg_sel4(int i, int a, int b, int c, int d) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
 
 // One square in LDS: its geometry, the planes of the layout (hough_layout) and the counters of the workgroup.
@@ -75,7 +79,7 @@ struct HgSq {
     int* acc;     // accumulator; the weak list before P4
     u16* centres;
     int* bins;    // [HG_NW][max_bins]
-    HgCircle* circ; // P6..P7, over g + map (both dead by then)
+    HgCircle* circ; // P6..P7, over g + map (both dead by then) and, where hough_layout lets it, the accumulator
     u16* weak;
     u16* edges;
     float dp, idp;
@@ -97,13 +101,13 @@ __device__ __forceinline__ void hg_square(HgSq& q, const SquareDesc& d, const Ho
     q.wave = q.tid >> 6;
     q.gs = cfg.gs;
     q.mw = cfg.mw;
-    q.g = smem;
+    q.g = smem + cfg.off_g;
     q.map = smem + cfg.off_map;
     q.mag = (u16*)(smem + cfg.off_mag);
     q.acc = (int*)(smem + cfg.off_acc);
     q.centres = (u16*)(smem + cfg.off_centres);
     q.bins = (int*)(smem + cfg.off_bins);
-    q.circ = (HgCircle*)smem;
+    q.circ = (HgCircle*)(smem + cfg.off_circ);
     q.weak = (u16*)q.acc;
     q.edges = q.mag;
     q.dp = cfg.dp;
@@ -178,7 +182,7 @@ __device__ __forceinline__ void hg_p1(const HgSq& q)
     u8* map = q.map;
     u16* mag = q.mag;
     for (int t = tid; t < ngroups; t += HG_NT) {
-        const int y = __umulhi((u32)t, q.inv_ngx), x0 = (t - y * ngx) << 2;
+        const int y = hg_div(t, q.inv_ngx), x0 = (t - y * ngx) << 2;
         int S[6], D[6];
         {
             int T[6], M[6], B[6];
@@ -229,7 +233,7 @@ __device__ __forceinline__ void hg_p2(const HgSq& q, int low, int high)
     for (int t0 = 0; t0 < ngroups; t0 += HG_NT) { // uniform trip count: hg_append uses wave ballots
         const int t = t0 + tid;
         const bool act = t < ngroups;
-        const int y = act ? __umulhi((u32)t, q.inv_ngx) : 0, x0 = act ? (t - y * ngx) << 2 : 0;
+        const int y = act ? hg_div(t, q.inv_ngx) : 0, x0 = act ? (t - y * ngx) << 2 : 0;
         int E[3][6];
 #pragma unroll
         for (int r = 0; r < 3; r++) {
@@ -332,7 +336,7 @@ __device__ __forceinline__ void hg_list_edges(const HgSq& q)
     for (int t0 = 0; t0 < ngroups; t0 += HG_NT) {
         const int t = t0 + tid;
         const bool act = t < ngroups;
-        const int y = act ? __umulhi((u32)t, q.inv_ngx) : 0, x0 = act ? (t - y * ngx) << 2 : 0;
+        const int y = act ? hg_div(t, q.inv_ngx) : 0, x0 = act ? (t - y * ngx) << 2 : 0;
         const u32 codes = act ? *(const u32*)(map + (y + 1) * gs + 4 + x0) : 0x01010101u;
         bool isedge[4];
         int slot[4];
@@ -397,7 +401,7 @@ __device__ __forceinline__ void hg_p5(const HgSq& q, int acc_thr, int maxc)
     const int* acc = q.acc;
     const int acols = q.acols, astep = q.astep;
     for (int i = q.tid; i < q.arows * acols; i += HG_NT) {
-        const int yy = __umulhi((u32)i, q.inv_ac), xx = i - yy * acols;
+        const int yy = hg_div(i, q.inv_ac), xx = i - yy * acols;
         const int base = (yy + 1) * astep + xx + 1;
         const int a = acc[base];
         if (a > acc_thr && a > acc[base - 1] && a >= acc[base + 1] && a > acc[base - astep] && a >= acc[base + astep]) {
@@ -610,26 +614,46 @@ static inline size_t hough_layout(HoughCfg& cfg)
     // bins of the radius histogram: round((max_radius - min_radius) / dp * 10) for the largest square
     const int md = cfg.maxw > cfg.maxh ? cfg.maxw : cfg.maxh, mind = cfg.maxw < cfg.maxh ? cfg.maxw : cfg.maxh;
     int span = md + 2;
-    if (cfg.max_ratio > 0 && cfg.max_ratio <= 4) {
+    // (a square so small that int(min_dim * max_ratio) is 0 takes max(w, h) for its maximum, as with a ratio of 0)
+    if (cfg.max_ratio > 0 && cfg.max_ratio <= 4 && (int)((cfg.min_dim > 0 ? cfg.min_dim : 2) * cfg.max_ratio) > 0) {
         span = (int)(mind * cfg.max_ratio) - (int)(mind * cfg.min_ratio) + 2;
-        if (span < 4) span = 4;
-        if (span > md + 2) span = md + 2;
+        if (span < 4) span = 4; // (ratios above 1 ask for more bins than a side has pixels: every bin is zeroed and walked)
     }
     cfg.max_bins = (int)(span / cfg.dp * 10) + 16;
+    const size_t acc_bytes = up16(acells * 4 > maxn * 2 ? acells * 4 : maxn * 2); // the weak list (u16 a pixel) shares it
+    const size_t bin_bytes = (size_t)HG_NW * cfg.max_bins * 4, circ_bytes = cfg.maxc * sizeof(HgCircle);
     size_t off = 0;
+    if (!cfg.keep_acc) {
+        // The planes in the order of their deaths: magnitude / edge list (to P6) and centres (P5..P6) stay apart; gray and
+        // map die with the vote, the accumulator with P5.  From P6 on the three are one region: candidates, then the bins of
+        // P6, and over the bins (dead behind P6's last barrier) the candidates in HoughCircles' order.  A 128 x 128 square at
+        // dp = 1 fits this way, with room for some 3 000 maxima in the second pass.
+        cfg.off_mag = 0;
+        cfg.off_centres = cfg.mag_bytes; // >= 2 bytes a pixel: the edge list reuses the magnitude plane
+        cfg.off_g = cfg.off_centres + (int)up16((size_t)cfg.maxc * 2);
+        cfg.off_map = cfg.off_g + (int)up16(gbytes);
+        cfg.off_acc = cfg.off_map + (int)up16(gbytes);
+        cfg.off_circ = cfg.off_g;
+        cfg.off_bins = cfg.off_circ + (int)circ_bytes;
+        cfg.off_order = cfg.off_bins;
+        const size_t planes = (size_t)cfg.off_acc + acc_bytes, lists = (size_t)cfg.off_bins + (bin_bytes > circ_bytes ? bin_bytes : circ_bytes);
+        return planes > lists ? planes : lists;
+    }
+    cfg.off_g = 0;
+    cfg.off_circ = 0;
     cfg.off_map = (int)up16(gbytes);
     off = cfg.off_map + up16(gbytes);
-    if (off < cfg.maxc * sizeof(HgCircle)) off = cfg.maxc * sizeof(HgCircle); // candidates overlay g + map
+    if (off < circ_bytes) off = circ_bytes; // candidates overlay g + map
     cfg.off_mag = (int)off;
     off += (size_t)cfg.mag_bytes; // >= 2 bytes a pixel: the edge list reuses it
     cfg.off_acc = (int)off;
-    off += up16(acells * 4 > maxn * 2 ? acells * 4 : maxn * 2); // the weak list (u16 a pixel) shares it
+    off += acc_bytes;
     cfg.off_centres = (int)off;
     off += up16((size_t)cfg.maxc * 2);
     cfg.off_bins = (int)off;
-    off += (size_t)HG_NW * cfg.max_bins * 4;
+    off += bin_bytes;
     cfg.off_order = (int)off; // candidates in HoughCircles' order
-    off += cfg.maxc * sizeof(HgCircle);
+    off += circ_bytes;
     return off;
 }
 

@@ -177,6 +177,7 @@ size_t piece_sweep_layout(HoughCfg* cfg, int* off_steps)
 {
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t steps = up16((size_t)cfg->maxw * cfg->maxh * 4); // one step pair per edge pixel at most
+    cfg->keep_acc = 1; // settings that share their radii share the votes
     *cfg = hough_pass_cfg(*cfg, 1, steps);
     const size_t lds = up16(hough_layout(*cfg));
     *off_steps = (int)lds;

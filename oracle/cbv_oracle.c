@@ -1252,9 +1252,11 @@ static int cmp_circle(const void* a, const void* b)
 }
 static inline int cv_ceil_f(float v) { int i = (int)v; return i + (i < v); }
 
-ORC_API int orc_hough_circles(const u8* gray, int w, int h, double dp_d, double min_dist_d, double param1,
-                              double param2, int min_radius, int max_radius, orc_circle* out, int max_out,
-                              u8* edges_out)
+/* counts[3], optional: accumulator maxima above param2, circles before the minDist suppression, circles returned;
+ * cand, optional: the first max_cand circles before the suppression, sorted */
+ORC_API int orc_hough_circles_counts(const u8* gray, int w, int h, double dp_d, double min_dist_d, double param1,
+                                     double param2, int min_radius, int max_radius, orc_circle* out, int max_out,
+                                     u8* edges_out, int* counts, orc_circle* cand, int max_cand)
 {
     float dp = (float)dp_d;
     if (dp < 1.f) dp = 1.f;
@@ -1302,7 +1304,7 @@ ORC_API int orc_hough_circles(const u8* gray, int w, int h, double dp_d, double 
                 sy = -sy;
             }
         }
-    int ncirc = 0;
+    int ncirc = 0, n_centres = 0, n_candidates = 0;
     orc_circle* circ = NULL;
     if (nz > 0) {
         int* centers = (int*)malloc(sizeof(int) * (size_t)(arows + 2) * astep);
@@ -1315,6 +1317,7 @@ ORC_API int orc_hough_circles(const u8* gray, int w, int h, double dp_d, double 
                     centers[nc++] = base;
             }
         qsort_r(centers, nc, sizeof(int), cmp_center, acc);
+        n_centres = nc;
         const int nBinsPerDr = 10;
         const int nBins = cv_round_f((max_radius - min_radius) / dp * nBinsPerDr);
         int* bins = (int*)malloc(sizeof(int) * (nBins > 0 ? nBins : 1));
@@ -1361,6 +1364,8 @@ ORC_API int orc_hough_circles(const u8* gray, int w, int h, double dp_d, double 
             }
         }
         qsort(circ, ncirc, sizeof(orc_circle), cmp_circle);
+        n_candidates = ncirc;
+        for (int i = 0; cand && i < ncirc && i < max_cand; i++) cand[i] = circ[i];
         /* RemoveOverlaps */
         float md = (float)min_dist_d;
         if (md < dp) md = dp;
@@ -1389,7 +1394,19 @@ ORC_API int orc_hough_circles(const u8* gray, int w, int h, double dp_d, double 
     free(dx);
     free(dy);
     free(edges);
+    if (counts) {
+        counts[0] = n_centres;
+        counts[1] = n_candidates;
+        counts[2] = ncirc;
+    }
     return ncirc;
+}
+
+ORC_API int orc_hough_circles(const u8* gray, int w, int h, double dp_d, double min_dist_d, double param1,
+                              double param2, int min_radius, int max_radius, orc_circle* out, int max_out,
+                              u8* edges_out)
+{
+    return orc_hough_circles_counts(gray, w, h, dp_d, min_dist_d, param1, param2, min_radius, max_radius, out, max_out, edges_out, NULL, NULL, 0);
 }
 
 /* cv2.Canny(gray, t1, t2) (grid_extractor.py:75): aperture 3, L1 gradient; thresholds ordered and floored. */

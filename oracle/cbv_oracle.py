@@ -314,17 +314,24 @@ class Circle(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("r", C.c_float), ("votes", C.c_int)]
 
 
-def hough_circles(gray, dp=1.2, min_dist=25, param1=100, param2=25, min_radius=19, max_radius=42, return_edges=False):
-    """cv2.HoughCircles(gray, HOUGH_GRADIENT, ...) restated (parity unpinned).  Returns [(x, y, r, votes)]."""
+def hough_circles(gray, dp=1.2, min_dist=25, param1=100, param2=25, min_radius=19, max_radius=42, return_edges=False,
+                  return_counts=False, return_candidates=False, max_out=64):
+    """cv2.HoughCircles(gray, HOUGH_GRADIENT, ...) restated (parity unpinned).  Returns [(x, y, r, votes)], the first
+    `max_out` of them.  return_counts adds (accumulator maxima above param2, circles before the minDist suppression,
+    circles returned), which no list length shows; return_candidates the first `max_out` sorted circles before the
+    suppression."""
     gray = np.ascontiguousarray(_u8(gray))
     h, w = gray.shape
-    out = (Circle * 64)()
+    out, cand = (Circle * max_out)(), (Circle * max_out)()
     edges = np.empty((h, w), np.uint8)
-    lib().orc_hough_circles.restype = C.c_int
-    n = lib().orc_hough_circles(_p(gray), w, h, C.c_double(dp), C.c_double(min_dist), C.c_double(param1), C.c_double(param2),
-                                int(min_radius), int(max_radius), out, 64, _p(edges))
-    res = [(out[i].x, out[i].y, out[i].r, out[i].votes) for i in range(min(n, 64))]
-    return (res, edges) if return_edges else res
+    counts = (C.c_int * 3)()
+    lib().orc_hough_circles_counts.restype = C.c_int
+    n = lib().orc_hough_circles_counts(_p(gray), w, h, C.c_double(dp), C.c_double(min_dist), C.c_double(param1), C.c_double(param2),
+                                       int(min_radius), int(max_radius), out, int(max_out), _p(edges), counts, cand, int(max_out))
+    res = [(out[i].x, out[i].y, out[i].r, out[i].votes) for i in range(min(n, max_out))]
+    cands = [(cand[i].x, cand[i].y, cand[i].r, cand[i].votes) for i in range(min(counts[1], max_out))]
+    ret = (res,) + ((edges,) if return_edges else ()) + ((tuple(counts),) if return_counts else ()) + ((cands,) if return_candidates else ())
+    return ret if len(ret) > 1 else res
 
 
 def canny(gray, t1, t2):

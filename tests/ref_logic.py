@@ -8,12 +8,13 @@ import numpy as np
 from oracle import cbv_oracle as O
 
 
-def detect_circle_unified(gray, min_radius_ratio=0.20, max_radius_ratio=0.55, param1=100, param2=25):
+def detect_circle_unified(gray, min_radius_ratio=0.20, max_radius_ratio=0.55, param1=100, param2=25, dp=1.2):
     """piece_detector.py:210-270 on the oracle's HoughCircles restatement (numpy float32 arithmetic for the pick,
-    as `cx`, `cy` are float32 there)."""
+    as `cx`, `cy` are float32 there).  The reference calls with dp = 1.2; the pick runs over every returned circle."""
     h, w = gray.shape
     min_dim = min(h, w)
-    circles = O.hough_circles(gray, 1.2, min_dim // 3, param1, param2, int(min_dim * min_radius_ratio), int(min_dim * max_radius_ratio))
+    circles = O.hough_circles(gray, dp, min_dim // 3, param1, param2, int(min_dim * min_radius_ratio), int(min_dim * max_radius_ratio),
+                              max_out=max(64, h * w))
     best, best_dist = None, float("inf")
     max_offset = min_dim * 0.3
     for (cx, cy, r, _) in circles:
