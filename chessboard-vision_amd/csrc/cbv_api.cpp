@@ -756,7 +756,7 @@ extern "C" int cbv_warp_perspective(cbv_ctx* ctx, const uint8_t* bgr, int w, int
     const double t1 = tm ? now() : 0;
     Geom g = tight_geom(w, h);
     RC(dev_ensure(ctx, &ctx->a, (size_t)dw * dh * 3 + 256));
-    RC(launch_warp(ctx, (const u8*)ctx->in.p, g, Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, NormSrc(), 1));
+    RC(launch_warp(ctx, warp_src_bgr((const u8*)ctx->in.p, g, NormSrc()), Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, 1));
     const double t2 = tm ? now() : 0;
     RC(rows_d2h(ctx, out, out_stride, ctx->a.p, dw * 3, dh));
     const double t3 = tm ? now() : 0;
@@ -782,8 +782,8 @@ extern "C" int cbv_warp_color_profile(cbv_ctx* ctx, const uint8_t* bgr, int w, i
     RC(dev_ensure(ctx, &ctx->b, sizeof(ProfileTabs))); // the call's tables
     CBV_HIP(ctx, hipMemcpyAsync(ctx->b.p, &pt, sizeof(pt), hipMemcpyHostToDevice, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt is on this stack)
-    RC(launch_warp_profile(ctx, (const u8*)ctx->in.p, tight_geom(w, h), Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, 0,
-                           (const ProfileTabs*)ctx->b.p, 1, 1));
+    RC(launch_warp(ctx, warp_src_profile((const u8*)ctx->in.p, tight_geom(w, h), (const ProfileTabs*)ctx->b.p), Minv, dw, dh, rot180, (u8*)ctx->a.p,
+                   dw * 3, (size_t)dw * dh * 3, 1));
     return download(ctx, ctx->a.p, out, dw * 3, dh, out_stride);
 }
 

@@ -336,16 +336,6 @@ static inline void warp_block_shape(int dw, int dh, int* bw0_out, int* bh0_out)
     *bw0_out = bw0;
     *bh0_out = bh0;
 }
-int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
-                int dst_stride, size_t dst_frame_stride, NormSrc norm, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
-// launch_warp with the colour profile applied to the taps (k_warp_profile): apply_color_profile followed by the warp, byte
-// for byte, with no converted frame in between, for `np` profiles at once.  ptabs[np] = device tables (build_profile_tabs),
-// the caller's, not ctx->ptabs; profile p writes its `batch` frames at dst + p * dst_profile_stride; a table with
-// enabled = 0 is the plain warp.  np x groups of frames (four frames a group from batch 8 on) <= 65535.  Counted as
-// CBV_K_WARP: the enumeration of profile ids is closed.
-int launch_warp_profile(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
-                        size_t dst_frame_stride, size_t dst_profile_stride, const ProfileTabs* ptabs, int np, int batch,
-                        u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 int launch_gray_blur_hist(cbv_ctx* ctx, const u8* src, u8* gray, u8* blur, u32* aux, int tiles, Geom g, int batch);
 int launch_otsu(cbv_ctx* ctx, u32* aux, int tiles, int total, int batch);
 int launch_threshold(cbv_ctx* ctx, const u8* blur, u8* binary, const u32* aux, int tiles, int w, int h, int batch);
@@ -435,19 +425,64 @@ int launch_ingest(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, in
 void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides);
 // one raw host frame (any YUV format, strided views) through the context's staging buffer into a BGR device image
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
-// launch_warp on raw frames (k_warp_yuv): the output of launch_ingest followed by launch_warp without a byte map, byte for
-// byte, with no BGR frame in between; g = the frames' width and height.  Interior pixels load both taps of a row at once:
-// 4 bytes at the even column of an NV12 / NV21 chroma row, 8 bytes at the first tap's pair of a packed 4:2:2 row, 2 bytes at
-// column sx >> 1 of each planar chroma row, which at sx = w - 2 reach 2 / 4 / 1 bytes past the row's w (2 w, w / 2) bytes.
-// Callers keep >= 8 readable bytes behind the last row of the last plane of the last frame (the pipeline's raw ring has
-// 256); between rows, planes and frames the bytes read belong to the next row, plane or frame.
-int launch_warp_yuv(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180,
-                    u8* dst, int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 
-// launch_warp_yuv for the Bayer family (k_warp_bayer): the four taps are demosaiced before the blend.  No byte outside the
-// frames' rows is read.
-int launch_warp_bayer(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180,
-                      u8* dst, int dst_stride, size_t dst_frame_stride, int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
+// What the warp samples (k_warp.hip): the frames of a batch, frame 0's pointers.
+struct WarpSrc {
+    enum Kind { BGR, PROFILE, YUV, BAYER } kind;
+    Geom g;                    // the frames' width and height; BGR, PROFILE: their strides too
+    const u8* bgr;             // BGR, PROFILE
+    NormSrc norm;              // BGR: cv2.normalize's byte map applied to the taps (none: the plain warp)
+    const ProfileTabs* ptabs;  // PROFILE: device tables [np]
+    int np;
+    size_t dst_profile_stride;
+    RawPlanes planes;          // YUV, BAYER: in memory order
+    RawGeom r;                 // (fmt = CBV_FMT_BGR for BGR and PROFILE)
+    bool raw() const { return kind == YUV || kind == BAYER; }
+};
+// BGR frames (k_warp), the taps through `norm`
+static inline WarpSrc warp_src_bgr(const u8* src, Geom g, NormSrc norm)
+{
+    WarpSrc s = {};
+    s.kind = WarpSrc::BGR;
+    s.g = g;
+    s.bgr = src;
+    s.norm = norm;
+    s.r.fmt = CBV_FMT_BGR;
+    return s;
+}
+// BGR frames with the colour profile applied to the taps (k_warp_profile): apply_color_profile followed by the warp, byte
+// for byte, with no converted frame in between, for `np` profiles at once.  ptabs[np] = device tables (build_profile_tabs),
+// the caller's, not ctx->ptabs; profile p writes its `batch` frames at dst + p * dst_profile_stride; a table with
+// enabled = 0 is the plain warp.  np x groups of frames (four frames a group from batch 8 on) <= 65535.  The multi-board
+// launch takes one table, the pipeline's.  Counted as CBV_K_WARP: the enumeration of profile ids is closed.
+static inline WarpSrc warp_src_profile(const u8* src, Geom g, const ProfileTabs* ptabs, int np = 1, size_t dst_profile_stride = 0)
+{
+    WarpSrc s = warp_src_bgr(src, g, NormSrc());
+    s.kind = WarpSrc::PROFILE;
+    s.ptabs = ptabs;
+    s.np = np;
+    s.dst_profile_stride = dst_profile_stride;
+    return s;
+}
+// Raw frames (k_warp_yuv; the Bayer family: k_warp_bayer): the output of launch_ingest followed by the warp without a byte
+// map, byte for byte, with no BGR frame in between; g = the frames' width and height.  YUV: interior pixels load both taps
+// of a row at once: 4 bytes at the even column of an NV12 / NV21 chroma row, 8 bytes at the first tap's pair of a packed
+// 4:2:2 row, 2 bytes at column sx >> 1 of each planar chroma row, which at sx = w - 2 reach 2 / 4 / 1 bytes past the row's
+// w (2 w, w / 2) bytes.  Callers keep >= 8 readable bytes behind the last row of the last plane of the last frame (the
+// pipeline's raw ring has 256); between rows, planes and frames the bytes read belong to the next row, plane or frame.
+// Bayer: the four taps are demosaiced before the blend, and no byte outside the frames' rows is read.
+static inline WarpSrc warp_src_raw(RawPlanes planes, RawGeom r, Geom g)
+{
+    WarpSrc s = {};
+    s.kind = raw_fmt_bayer(r.fmt) ? WarpSrc::BAYER : WarpSrc::YUV;
+    s.g = g;
+    s.planes = planes;
+    s.r = r;
+    return s;
+}
+// `batch` frames of `src` onto one dw x dh board: four frames per thread from batch 8 on, one thread per pixel and frame below
+int launch_warp(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
+                int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 
 void build_gaussian_q8_sigma(int k, double sigma, int* coef);
 int launch_gray_gauss(cbv_ctx* ctx, const u8* src, int w, int h, int stride, int cn, const int* coef_dev, int k, u8* dst);
@@ -658,14 +693,7 @@ ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
 // of each pass, 0 when the squares cannot run (the single-board launchers' checks)
 void hough_board_cfgs(HoughCfg base, HoughCfg out[2], size_t lds[2]);
 // one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0
-int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, NormSrc norm, int batch,
-                   u32* zero_word, u32* zero_word2);
-int launch_warp_profile_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, const ProfileTabs* pt, int batch,
-                           u32* zero_word, u32* zero_word2);
-int launch_warp_yuv_mb(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
-                       int batch, u32* zero_word, u32* zero_word2);
-int launch_warp_bayer_mb(cbv_ctx* ctx, RawPlanes planes, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0,
-                         int batch, u32* zero_word, u32* zero_word2);
+int launch_warp_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);

@@ -10,20 +10,14 @@
 static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, int b, u32* work, u32* retry0, u32* retry, int retry_base)
 {
     cbv_ctx* ctx = P.ctx;
-    RawGeom rg = {};
-    RawPlanes raw = {{nullptr, nullptr, nullptr}}; // raw mode: the planes of the chunk's first slot
-    if (!res) {
-        rg = tight_raw_geom(P.in_fmt, P.w, P.h);
-        raw = slot_planes(P, s0);
-    }
-    const u8* raw0 = raw.p[0];
+    // what the warp samples (raw mode: the planes of the chunk's first slot)
+    const WarpSrc src = !res             ? warp_src_raw(slot_planes(P, s0), tight_raw_geom(P.in_fmt, P.w, P.h), P.g)
+                        : P.profile_on ? warp_src_profile(res, P.g, (const ProfileTabs*)P.d_ptabs.p)
+                                       : warp_src_bgr(res, P.g, norm);
     if (P.boards.size() > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         const int nb = (int)P.boards.size();
-        if (raw0 && raw_fmt_bayer(rg.fmt)) RC(launch_warp_bayer_mb(ctx, raw, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
-        else if (raw0) RC(launch_warp_yuv_mb(ctx, raw, rg, P.g, tab, nb, P.max_S, s0, b, work, retry0));
-        else if (P.profile_on) RC(launch_warp_profile_mb(ctx, res, P.g, tab, nb, P.max_S, s0, (const ProfileTabs*)P.d_ptabs.p, b, work, retry0));
-        else RC(launch_warp_mb(ctx, res, P.g, tab, nb, P.max_S, s0, norm, b, work, retry0));
+        RC(launch_warp_mb(ctx, src, tab, nb, P.max_S, s0, b, work, retry0));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
         if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, s0, b, P.max_px));
         if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, P.hough_lds[0], retry, retry_base, 0));
@@ -34,12 +28,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     u8* gray = T.gray + T.plane_total * s0;
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
     cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
-    if (raw0 && raw_fmt_bayer(rg.fmt)) RC(launch_warp_bayer(ctx, raw, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
-    else if (raw0) RC(launch_warp_yuv(ctx, raw, rg, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
-    else if (P.profile_on)
-        RC(launch_warp_profile(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, 0, (const ProfileTabs*)P.d_ptabs.p, 1, b, work,
-                               retry0));
-    else RC(launch_warp(ctx, res, P.g, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, norm, b, work, retry0));
+    RC(launch_warp(ctx, src, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
     RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
                                  T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));
     if (P.any_own_blur)

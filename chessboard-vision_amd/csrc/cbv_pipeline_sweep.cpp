@@ -412,8 +412,8 @@ extern "C" int cbv_pipeline_color_sweep(cbv_pipeline* p, int slot0, int count, c
         for (int c0 = 0; c0 < count; c0 += chunk) {
             const int cf = std::min(chunk, count - c0), nb = pc * cf; // scratch frame of (profile i, frame f) = i * cf + f
             CBV_HIP(ctx, hipEventRecord(S.ev[0], ctx->stream));
-            RC(launch_warp_profile(ctx, P.frames + P.g.frame_stride * (slot0 + c0), P.g, B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p, S_ * 3,
-                                   B.warped_stride, B.warped_stride * cf, (const ProfileTabs*)S.tabs.p, pc, cf));
+            RC(launch_warp(ctx, warp_src_profile(P.frames + P.g.frame_stride * (slot0 + c0), P.g, (const ProfileTabs*)S.tabs.p, pc, B.warped_stride * cf),
+                           B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p, S_ * 3, B.warped_stride, cf));
             CBV_HIP(ctx, hipEventRecord(S.ev[1], ctx->stream));
             RC(launch_squares_pre5_stats(ctx, (const u8*)S.boards.p, B.warped_stride, descs, n, (u8*)S.gray.p, B.plane_total, nullptr, nullptr,
                                          (const u8*)B.d_masks.p, (float)B.cfg.z_threshold, (cbv_sq_stats*)S.stats.p, nb, nullptr, 0, nullptr, nullptr,

@@ -8,6 +8,13 @@
 // left edge and advanced by M*x1 inside the block, in double, one rounding per
 // operation; coordinates are quantised to 1/32 px and sampled with the 15-bit
 // fixed-point bilinear table of remap().
+//
+// One gather (warp_gather) serves every kind of source frame.  What a tap is worth is a function of the source pixel alone
+// for every kind (a byte map, a pointwise YUV conversion, the demosaic of a site, the colour profile), so converting the
+// four taps and blending them is, bit for bit, sampling the converted frame: same coordinates (warp_taps), same conversion,
+// same blend (warp_blend).  A tap outside the frame is BGR (0, 0, 0) for every source, not the conversion of zero.  The
+// sources: WarpBgr (BGR frames through cv2.normalize's byte map), WarpProfile (BGR frames through apply_color_profile) and
+// WarpRaw<FMT> (camera-native YUV frames and Bayer mosaics: the BGR frame k_ingest would write is never made).
 // Also here: the synthetic frame generator used by bench/tests.
 #include "cbv_bayer.h"
 #include "cbv_profile_px.h"
@@ -18,7 +25,7 @@ struct WarpM {
 };
 
 // What a destination pixel samples, whatever the format of the frames: the top-left tap, the four weights, which taps are
-// inside the source, and where the pixel goes.  (warp_body and warp_yuv_body share it.)
+// inside the source, and where the pixel goes.
 struct WarpTaps {
     int sx, sy;
     int w00, w01, w10, w11;
@@ -78,101 +85,81 @@ __device__ __forceinline__ int warp_blend(int t0, int t1, int t2, int t3, const 
     return d_sat8((t0 * t.w00 + t1 * t.w01 + t2 * t.w10 + t3 * t.w11 + (1 << 14)) >> 15);
 }
 
-// FPT frames per thread: the coordinates of a destination pixel depend on the matrix and the pixel, not on the frame, and
-// they are most of the kernel's instructions (about 100 of 190 per output pixel, in double precision): a thread works
-// them out once and samples FPT consecutive frames of the batch with them (blockIdx.z counts groups of FPT frames).
-// CALC: the byte map is worked out here from the frames' [min, max] words (NormSrc::minmax) instead of read from a table.
-// (the body of k_warp and k_warp_mb; bz = the group of frames, blockIdx.z of a single-board launch)
-template <int FPT, bool CALC>
-__device__ __forceinline__ void warp_body(const u8* __restrict__ src, Geom g, const double* __restrict__ M, int dw, int dh, int bw0,
-                                          int bh0, int rot180, u8* __restrict__ dst, int dst_stride,
-                                          size_t dst_frame_stride, const u8* __restrict__ norm_lut, const u32* __restrict__ minmax,
-                                          size_t mm_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
-{
-    __shared__ u8 lut[FPT][256];
-    warp_zero_words(zero_word, zero_word2);
-    const bool use_lut = CALC || norm_lut != nullptr;
-    const int f0 = bz * FPT;
-    const int nf = min(FPT, batch - f0);
-    if (CALC) {
-#pragma unroll
-        for (int k = 0; k < FPT; k++)
-            if (k < nf) {
-                const u32* mm = minmax + (size_t)(f0 + k) * mm_stride;
-                lut[k][threadIdx.x] = d_norm_lut_entry((int)mm[0], (int)mm[1], (int)threadIdx.x);
-            }
-    } else if (use_lut)
-#pragma unroll
-        for (int k = 0; k < FPT; k++)
-            if (k < nf) lut[k][threadIdx.x] = norm_lut[(size_t)(f0 + k) * 256 + threadIdx.x];
-    __syncthreads();
-    (void)bh0;
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const WarpTaps t = warp_taps(dx, dy, g.w, g.h, M, dw, dh, bw0, rot180, dst_stride);
-    const size_t tap = (size_t)t.sy * g.stride + (size_t)t.sx * 3; // (only dereferenced where the taps are inside)
-    // interior: the two taps of a row are 6 contiguous bytes -> ONE unaligned 8-byte load per row instead of six byte
-    // loads (the gather is bound by the number of memory instructions, not by bytes); the two bytes read past the second
-    // tap stay inside the buffer (callers keep >= 8 bytes of slack behind the last frame).  All frames' loads are issued
-    // before the first is used.
-    u64 ta[FPT], tb[FPT];
-    if (t.interior)
-#pragma unroll
-        for (int k = 0; k < FPT; k++)
-            if (k < nf) {
-                const u8* p00 = src + (size_t)(f0 + k) * g.frame_stride + tap;
-                __builtin_memcpy(&ta[k], p00, 8);
-                __builtin_memcpy(&tb[k], p00 + g.stride, 8);
-            }
-#pragma unroll
-    for (int k = 0; k < FPT; k++) {
-        if (k >= nf) break;
-        int o[3] = {0, 0, 0};
-        if (t.any_in) {
-            int v[4][3]; // taps 00, 01, 10, 11
-            if (t.interior) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    v[0][c] = (int)((ta[k] >> (8 * c)) & 255);
-                    v[1][c] = (int)((ta[k] >> (8 * (3 + c))) & 255);
-                    v[2][c] = (int)((tb[k] >> (8 * c)) & 255);
-                    v[3][c] = (int)((tb[k] >> (8 * (3 + c))) & 255);
-                }
-            } else {
-                const u8* p00 = src + (size_t)(f0 + k) * g.frame_stride + tap;
-                const u8* p10 = p00 + g.stride;
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    v[0][c] = (t.x0in && t.y0in) ? p00[c] : -1;
-                    v[1][c] = (t.x1in && t.y0in) ? p00[3 + c] : -1;
-                    v[2][c] = (t.x0in && t.y1in) ? p10[c] : -1;
-                    v[3][c] = (t.x1in && t.y1in) ? p10[3 + c] : -1;
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                int q[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) q[i] = v[i][c] < 0 ? 0 : (use_lut ? (int)lut[k][v[i][c]] : v[i][c]); // border taps are 0
-                o[c] = warp_blend(q[0], q[1], q[2], q[3], t);
-            }
-        }
-        u8* q = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
-        q[0] = (u8)o[0];
-        q[1] = (u8)o[1];
-        q[2] = (u8)o[2];
-    }
-}
+// where a launch writes one board: the matrix, the dw x dh destination, frame 0 of the batch
+struct WarpDst {
+    const double* M;
+    int dw, dh, bw0, rot180;
+    u8* dst;
+    int stride;
+    size_t frame_stride;
+};
 
 // ---------------------------------------------------------------------------
-// The warp straight from camera-native frames (pipelines without enhancement whose input format is a YUV format): the
-// BGR frame k_ingest would write is never made.  The conversion is pointwise (a pixel takes the chroma of its 2x2 block
-// or pair, nothing is interpolated), so converting the four taps and blending them is, bit for bit, sampling the
-// converted frame: same coordinates (warp_taps), same conversion (d_yuv_bgr), same blend (warp_blend).  A tap outside
-// the frame is BGR (0, 0, 0) as in k_warp, not the conversion of zero YUV.
+// The sources: what the frames are and how the BGR value of a tap is obtained.  A source is plain data and constants; what
+// it does differently stands in warp_gather under its KIND.  (The text stays in the one function on purpose: the compiler
+// simplifies every function on its own before it inlines, and the gather split into per-source functions compiles to
+// other instructions than this.)
 // ---------------------------------------------------------------------------
-// pixel (x, y) of one raw frame with byte loads (the taps of pixels on the frame's border)
+enum { WARP_BGR, WARP_PROFILE, WARP_YUV, WARP_BAYER };
+#define WP_ROWS 16 // destination rows per workgroup of WarpProfile: one row of WarpPerspectiveInvoker's 64 x 16 blocks
+
+// BGR frames through cv2.normalize's byte map, which is staged in LDS per frame.  CALC: the map is worked out here from the
+// frames' [min, max] words (NormSrc::minmax) instead of read from a table ([frame][256]); neither: no mapping.  The taps
+// stay channel by channel, as bytes index the map.
+template <bool CALC_>
+struct WarpBgr {
+    static constexpr int KIND = WARP_BGR, ROWS = 4, FMT = CBV_FMT_BGR;
+    static constexpr bool CALC = CALC_;
+    template <int FPT>
+    struct Lds {
+        u8 lut[FPT][256];
+    };
+    const u8* src;
+    Geom g;
+    const u8* norm_lut;
+    const u32* minmax;
+    size_t mm_stride;
+    __device__ __forceinline__ int w() const { return g.w; }
+    __device__ __forceinline__ int h() const { return g.h; }
+};
+
+// BGR frames through the colour profile (cbv_warp_color_profile, pipelines configured with CBV_SKIP_ENHANCE_PROFILE,
+// cbv_pipeline_color_sweep): the loads of WarpBgr, d_profile_px on each tap.  A workgroup stages the 7.5 KB d_profile_px
+// reads (ProfileLds) and then covers WP_ROWS destination rows of its 64 columns, FPT frames each: 1920 staged words against
+// 4096 conversions per frame.  The tables are an argument, one ProfileTabs per profile of the launch; a table with
+// enabled = 0 leaves the taps as they are.
+struct WarpProfile {
+    static constexpr int KIND = WARP_PROFILE, ROWS = WP_ROWS, FMT = CBV_FMT_BGR;
+    template <int FPT>
+    using Lds = ProfileLds;
+    const u8* src;
+    Geom g;
+    const StaticTabs* st;
+    const ProfileTabs* pt; // the profile's table
+    __device__ __forceinline__ int w() const { return g.w; }
+    __device__ __forceinline__ int h() const { return g.h; }
+};
+
+// Camera-native frames (pipelines without enhancement whose input is raw): the BGR frame k_ingest would write is never made.
+// YUV: the taps through d_yuv_bgr; the conversion is pointwise (a pixel takes the chroma of its 2x2 block or pair, nothing
+// is interpolated).  Bayer: the taps demosaiced (d_bayer_bgr, cbv_bayer.h); a tap on the frame's outermost rows or
+// columns is the result of the clamped site, as in k_ingest.  Nothing is staged.
+template <int FMT_>
+struct WarpRaw {
+    static constexpr int KIND = raw_fmt_bayer(FMT_) ? WARP_BAYER : WARP_YUV, ROWS = 4, FMT = FMT_;
+    template <int FPT>
+    struct Lds {
+    };
+    const u8* p0;
+    const u8* p1;
+    const u8* p2;
+    RawGeom r;
+    int sw, sh;
+    __device__ __forceinline__ int w() const { return sw; }
+    __device__ __forceinline__ int h() const { return sh; }
+};
+
+// pixel (x, y) of one raw YUV frame with byte loads (the taps of pixels on the frame's border)
 template <int FMT>
 __device__ __forceinline__ u32 d_raw_px(const u8* __restrict__ f0, const u8* __restrict__ f1, const u8* __restrict__ f2, const RawGeom& r, int x,
                                         int y)
@@ -196,169 +183,6 @@ __device__ __forceinline__ Chroma d_chroma_pair(u32 p)
     return d_chroma((p >> (8 * YuvLay<FMT>::CU)) & 255, (p >> (8 * YuvLay<FMT>::CV)) & 255);
 }
 
-// Interior pixels, per frame and row of taps.  NV12 / NV21: one 2-byte load holds both luma samples and one 4-byte load at
-// the even column holds the chroma of the first tap's pair and of the next pair, which is the second tap's when sx is odd
-// (when sx is even both taps share the first); the rows share the chroma row when sy is even.  Planar chroma (YUV420P; YV12
-// arrives with p1 and p2 swapped): the same 2-byte luma load, and per chroma row one 2-byte load of U and one of V at column
-// sx >> 1, which hold the first tap's sample and the next, the second tap's when sx is odd.  Packed 4:2:2: one 8-byte load
-// at the first tap's pair, e.g. Y0 U Y1 V | Y2 U Y3 V, holds both taps and their chroma for either parity.  The bytes read
-// past the second tap's pair (sx even) stay inside the buffer: the ring keeps 256 bytes of slack behind the last frame.
-template <int FMT, int FPT>
-__device__ __forceinline__ void warp_yuv_body(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw,
-                                              int sh, const double* __restrict__ M, int dw, int dh, int bw0, int rot180, u8* __restrict__ dst,
-                                              int dst_stride, size_t dst_frame_stride, u32* __restrict__ zero_word,
-                                              u32* __restrict__ zero_word2, int batch, int bz)
-{
-    typedef YuvLay<FMT> L;
-    warp_zero_words(zero_word, zero_word2);
-    const int f0 = bz * FPT;
-    const int nf = min(FPT, batch - f0);
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const WarpTaps t = warp_taps(dx, dy, sw, sh, M, dw, dh, bw0, rot180, dst_stride);
-    const bool odd = t.sx & 1;
-    constexpr bool NV12 = L::F420 && !L::PLANAR, PLANAR = L::PLANAR;
-    const bool two_crows = L::F420 && (t.sy & 1); // the rows of taps lie in different chroma rows
-    // (offsets are only used where the taps are inside)
-    const size_t l_off = L::F420 ? (size_t)t.sy * r.stride0 + (size_t)t.sx : (size_t)t.sy * r.stride0 + (size_t)(t.sx >> 1) * 4;
-    const size_t c_off = (size_t)(t.sy >> 1) * r.stride1 + (size_t)(PLANAR ? t.sx >> 1 : t.sx & ~1);
-    const size_t c2_off = (size_t)(t.sy >> 1) * r.stride2 + (size_t)(t.sx >> 1);
-    u64 la[FPT], lb[FPT]; // 4:2:0: 2 luma bytes; 4:2:2: the 8 bytes of two pairs
-    u32 ca[FPT], cb[FPT]; // NV12: U V U V; planar: U U
-    u32 va[FPT], vb[FPT]; // planar: V V
-    if (t.interior)
-#pragma unroll
-        for (int k = 0; k < FPT; k++)
-            if (k < nf) {
-                const u8* l = p0 + (size_t)(f0 + k) * r.frame_stride + l_off;
-                if (L::F420) {
-                    u16 a, b;
-                    __builtin_memcpy(&a, l, 2);
-                    __builtin_memcpy(&b, l + r.stride0, 2);
-                    la[k] = a;
-                    lb[k] = b;
-                    const u8* c = p1 + (size_t)(f0 + k) * r.frame_stride + c_off;
-                    if (NV12) {
-                        __builtin_memcpy(&ca[k], c, 4);
-                        cb[k] = ca[k];
-                        if (two_crows) __builtin_memcpy(&cb[k], c + r.stride1, 4);
-                    } else {
-                        const u8* c2 = p2 + (size_t)(f0 + k) * r.frame_stride + c2_off;
-                        u16 u, v;
-                        __builtin_memcpy(&u, c, 2);
-                        __builtin_memcpy(&v, c2, 2);
-                        ca[k] = cb[k] = u;
-                        va[k] = vb[k] = v;
-                        if (two_crows) {
-                            __builtin_memcpy(&u, c + r.stride1, 2);
-                            __builtin_memcpy(&v, c2 + r.stride2, 2);
-                            cb[k] = u;
-                            vb[k] = v;
-                        }
-                    }
-                } else {
-                    __builtin_memcpy(&la[k], l, 8);
-                    __builtin_memcpy(&lb[k], l + r.stride0, 8);
-                }
-            }
-#pragma unroll
-    for (int k = 0; k < FPT; k++) {
-        if (k >= nf) break;
-        int o[3] = {0, 0, 0};
-        if (t.any_in) {
-            u32 q[4] = {0u, 0u, 0u, 0u}; // taps 00, 01, 10, 11 as b | g << 8 | r << 16; border taps are 0
-            if (t.interior) {
-                if (L::F420) {
-                    Chroma a0, a1, b0, b1;
-                    if (NV12) {
-                        const u32 a = ca[k], sa = odd ? a >> 16 : a;
-                        a0 = d_chroma_pair<FMT>(a);
-                        a1 = d_chroma_pair<FMT>(sa);
-                        b0 = a0;
-                        b1 = a1;
-                        if (two_crows) {
-                            const u32 b = cb[k], sb = odd ? b >> 16 : b;
-                            b0 = d_chroma_pair<FMT>(b);
-                            b1 = d_chroma_pair<FMT>(sb);
-                        }
-                    } else {
-                        const u32 u = ca[k], v = va[k];
-                        a0 = d_chroma(u & 255, v & 255);
-                        a1 = d_chroma((odd ? u >> 8 : u) & 255, (odd ? v >> 8 : v) & 255);
-                        b0 = a0;
-                        b1 = a1;
-                        if (two_crows) {
-                            const u32 u1 = cb[k], v1 = vb[k];
-                            b0 = d_chroma(u1 & 255, v1 & 255);
-                            b1 = d_chroma((odd ? u1 >> 8 : u1) & 255, (odd ? v1 >> 8 : v1) & 255);
-                        }
-                    }
-                    q[0] = d_yuv_bgr((int)(la[k] & 255), a0);
-                    q[1] = d_yuv_bgr((int)((la[k] >> 8) & 255), a1);
-                    q[2] = d_yuv_bgr((int)(lb[k] & 255), b0);
-                    q[3] = d_yuv_bgr((int)((lb[k] >> 8) & 255), b1);
-                } else {
-#pragma unroll
-                    for (int row = 0; row < 2; row++) {
-                        const u64 w = row ? lb[k] : la[k];
-                        const u32 lo = (u32)w, hi = (u32)(w >> 32), s1 = odd ? hi : lo;
-                        const Chroma c0 = d_chroma((lo >> (8 * L::PU)) & 255, (lo >> (8 * L::PV)) & 255);
-                        const Chroma c1 = d_chroma((s1 >> (8 * L::PU)) & 255, (s1 >> (8 * L::PV)) & 255);
-                        q[2 * row] = d_yuv_bgr((int)((odd ? lo >> (8 * L::Y1) : lo >> (8 * L::Y0)) & 255), c0);
-                        q[2 * row + 1] = d_yuv_bgr((int)((odd ? hi >> (8 * L::Y0) : lo >> (8 * L::Y1)) & 255), c1);
-                    }
-                }
-            } else {
-                const u8* f0p = p0 + (size_t)(f0 + k) * r.frame_stride;
-                const u8* f1p = L::F420 ? p1 + (size_t)(f0 + k) * r.frame_stride : nullptr;
-                const u8* f2p = PLANAR ? p2 + (size_t)(f0 + k) * r.frame_stride : nullptr;
-                if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx, t.sy);
-                if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx + 1, t.sy);
-                if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx, t.sy + 1);
-                if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, f2p, r, t.sx + 1, t.sy + 1);
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++)
-                o[c] = warp_blend((int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255),
-                                  (int)((q[3] >> (8 * c)) & 255), t);
-        }
-        u8* out = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
-        out[0] = (u8)o[0];
-        out[1] = (u8)o[1];
-        out[2] = (u8)o[2];
-    }
-}
-
-template <int FMT, int FPT>
-__global__ __launch_bounds__(256) void k_warp_yuv(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw, int sh, WarpM M,
-                                                   int dw, int dh, int bw0, int rot180, u8* __restrict__ dst, int dst_stride,
-                                                   size_t dst_frame_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
-{
-    warp_yuv_body<FMT, FPT>(p0, p1, p2, r, sw, sh, M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch,
-                            blockIdx.z);
-}
-
-// every board of a pipeline in one launch, as k_warp_mb
-template <int FMT, int FPT>
-__global__ __launch_bounds__(256) void k_warp_yuv_mb(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw, int sh,
-                                                      const BoardDev* __restrict__ tab, int nz, int s0, u32* __restrict__ zero_word,
-                                                      u32* __restrict__ zero_word2, int batch)
-{
-    const int b = blockIdx.z / nz;
-    const BoardDev& T = tab[b];
-    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
-    warp_yuv_body<FMT, FPT>(p0, p1, p2, r, sw, sh, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3,
-                            T.warped_stride, zero_word, zero_word2, batch, blockIdx.z - b * nz);
-}
-
-// ---------------------------------------------------------------------------
-// The warp straight from 8-bit Bayer mosaics (pipelines without enhancement whose input format is a Bayer format):
-// k_warp_yuv's gather with the four taps demosaiced (d_bayer_bgr, cbv_bayer.h) before the blend.  A tap is a pixel of the
-// frame k_ingest would write, so demosaicing the taps and blending them is, bit for bit, sampling that frame: same
-// coordinates (warp_taps), same conversion, same blend (warp_blend).  A tap outside the frame is BGR (0, 0, 0); a tap on
-// the frame's outermost rows or columns is the result of the clamped site, as in k_ingest.
-// ---------------------------------------------------------------------------
 // pixel (x, y) of one mosaic, inside the frame, with byte loads: the site is clamped, its neighbourhood lies inside
 template <int FMT>
 __device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride, int w, int h, int x, int y)
@@ -374,61 +198,319 @@ __device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride,
     return d_bayer_bgr<FMT>(cx, cy, row[0], row[1], row[2]);
 }
 
-// Pixels whose four taps are all interior sites (1 <= sx, sx + 1 <= w - 2, the same in y): the taps' 3 x 3 neighbourhoods
-// lie in the 4 x 4 bytes at (sx - 1, sy - 1), which is four unaligned 4-byte loads per frame, inside the frame's rows.
-// Everything else with a tap inside the frame takes d_bayer_px per tap.
-template <int FMT, int FPT>
-__device__ __forceinline__ void warp_bayer_body(const u8* __restrict__ p0, RawGeom r, int sw, int sh, const double* __restrict__ M, int dw, int dh,
-                                                int bw0, int rot180, u8* __restrict__ dst, int dst_stride, size_t dst_frame_stride,
-                                                u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
+// The gather.  FPT frames per thread: the coordinates of a destination pixel depend on the matrix and the pixel, not on the
+// frame, and they are most of the kernel's instructions (about 100 of 190 per output pixel, in double precision): a thread
+// works them out once and samples FPT consecutive frames of the batch with them (bz = the group of FPT frames, blockIdx.z
+// of a single-board launch; the last group of a batch may hold fewer).  A workgroup covers Src::ROWS rows of 64 columns.
+// Per source: what is staged in LDS, which pixels fetch their taps with wide loads (`fast`) and what those loads are, the
+// taps of a fast pixel, and a tap by byte loads for the pixels with taps outside the frame.  The rest is shared.
+//
+// The wide loads.  BGR and profile, interior pixels: the two taps of a row are 6 contiguous bytes -> ONE unaligned 8-byte
+// load per row instead of six byte loads; the two bytes read past the second tap stay inside the buffer (callers keep >= 8
+// bytes of slack behind the last frame).  YUV, interior pixels, per row of taps.  NV12 / NV21: one 2-byte load holds both
+// luma samples and one 4-byte load at the even column holds the chroma of the first tap's pair and of the next pair, which
+// is the second tap's when sx is odd (when sx is even both taps share the first); the rows share the chroma row when sy is
+// even.  Planar chroma (YUV420P; YV12 arrives with p1 and p2 swapped): the same 2-byte luma load, and per chroma row one
+// 2-byte load of U and one of V at column sx >> 1, which hold the first tap's sample and the next, the second tap's when sx
+// is odd.  Packed 4:2:2: one 8-byte load at the first tap's pair, e.g. Y0 U Y1 V | Y2 U Y3 V, holds both taps and their
+// chroma for either parity.  The bytes read past the second tap's pair (sx even) stay inside the buffer: the ring keeps 256
+// bytes of slack behind the last frame.  Bayer, pixels whose four taps are all interior sites (1 <= sx, sx + 1 <= w - 2,
+// the same in y): the taps' 3 x 3 neighbourhoods lie in the 4 x 4 bytes at (sx - 1, sy - 1), which is four unaligned 4-byte
+// loads per frame, inside the frame's rows.
+template <class Src, int FPT>
+__device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
 {
+    constexpr int KIND = Src::KIND, FMT = Src::FMT;
+    constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV;
+    typedef YuvLay<YUV ? FMT : CBV_FMT_NV12> L; // (only read where YUV)
+    constexpr bool NV12 = L::F420 && !L::PLANAR, PLANAR = L::PLANAR;
+    __shared__ typename Src::template Lds<FPT> lds;
     warp_zero_words(zero_word, zero_word2);
+    bool use_lut = false, on = false, radical = false; // uniform
+    if constexpr (BGR) use_lut = Src::CALC || S.norm_lut != nullptr;
+    if constexpr (PROFILE) {
+        lds_copy(lds.sdiv, S.st->sdiv, sizeof(lds.sdiv));
+        lds_copy(lds.hdiv, S.st->hdiv, sizeof(lds.hdiv));
+        lds_copy(lds.pt.csa, S.pt->csa, sizeof(lds.pt.csa));
+        lds_copy(lds.pt.hmask, S.pt->hmask, sizeof(lds.pt.hmask));
+        lds_copy(lds.pt.hsel, S.pt->hsel, sizeof(lds.pt.hsel));
+        lds_copy(lds.pt.hfr, S.pt->hfr, sizeof(lds.pt.hfr));
+        lds_copy(lds.pt.s_f, S.pt->s_f, sizeof(lds.pt.s_f));
+        lds_copy(lds.pt.v_f, S.pt->v_f, sizeof(lds.pt.v_f));
+        on = S.pt->enabled != 0;
+        radical = S.pt->radical != 0;
+        __syncthreads();
+    }
     const int f0 = bz * FPT;
     const int nf = min(FPT, batch - f0);
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const WarpTaps t = warp_taps(dx, dy, sw, sh, M, dw, dh, bw0, rot180, dst_stride);
-    const bool inner = t.sx >= 1 && t.sx + 2 < sw && t.sy >= 1 && t.sy + 2 < sh;
-    const size_t off = (size_t)(t.sy - 1) * r.stride0 + (size_t)(t.sx - 1); // (only used where inner)
-    u32 rows[FPT][4];
-    if (inner)
+    if constexpr (BGR) {
+        if (Src::CALC) {
 #pragma unroll
-        for (int k = 0; k < FPT; k++)
-            if (k < nf) {
-                const u8* m = p0 + (size_t)(f0 + k) * r.frame_stride + off;
+            for (int k = 0; k < FPT; k++)
+                if (k < nf) {
+                    const u32* mm = S.minmax + (size_t)(f0 + k) * S.mm_stride;
+                    lds.lut[k][threadIdx.x] = d_norm_lut_entry((int)mm[0], (int)mm[1], (int)threadIdx.x);
+                }
+        } else if (use_lut)
 #pragma unroll
-                for (int i = 0; i < 4; i++) __builtin_memcpy(&rows[k][i], m + (size_t)i * r.stride0, 4);
-            }
-#pragma unroll
-    for (int k = 0; k < FPT; k++) {
-        if (k >= nf) break;
-        int o[3] = {0, 0, 0};
-        if (t.any_in) {
-            u32 q[4] = {0u, 0u, 0u, 0u}; // taps 00, 01, 10, 11 as b | g << 8 | r << 16; border taps are 0
-            if (inner) {
-                const u32* w = rows[k];
-                q[0] = d_bayer_bgr<FMT>(t.sx, t.sy, w[0], w[1], w[2]);
-                q[1] = d_bayer_bgr<FMT>(t.sx + 1, t.sy, w[0] >> 8, w[1] >> 8, w[2] >> 8);
-                q[2] = d_bayer_bgr<FMT>(t.sx, t.sy + 1, w[1], w[2], w[3]);
-                q[3] = d_bayer_bgr<FMT>(t.sx + 1, t.sy + 1, w[1] >> 8, w[2] >> 8, w[3] >> 8);
-            } else {
-                const u8* fp = p0 + (size_t)(f0 + k) * r.frame_stride;
-                if (t.x0in && t.y0in) q[0] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx, t.sy);
-                if (t.x1in && t.y0in) q[1] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx + 1, t.sy);
-                if (t.x0in && t.y1in) q[2] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx, t.sy + 1);
-                if (t.x1in && t.y1in) q[3] = d_bayer_px<FMT>(fp, r.stride0, sw, sh, t.sx + 1, t.sy + 1);
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++)
-                o[c] = warp_blend((int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255),
-                                  (int)((q[3] >> (8 * c)) & 255), t);
-        }
-        u8* out = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
-        out[0] = (u8)o[0];
-        out[1] = (u8)o[1];
-        out[2] = (u8)o[2];
+            for (int k = 0; k < FPT; k++)
+                if (k < nf) lds.lut[k][threadIdx.x] = S.norm_lut[(size_t)(f0 + k) * 256 + threadIdx.x];
+        __syncthreads();
     }
+    // a tap as b | g << 8 | r << 16 (the low three bytes of v) through the profile
+    auto conv = [&](u32 v) -> u32 {
+        if constexpr (PROFILE) return on ? d_profile_px(lds, (int)(v & 255u), (int)((v >> 8) & 255u), (int)((v >> 16) & 255u), radical) : (v & 0xFFFFFFu);
+        else return v;
+    };
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
+    int dy = blockIdx.y * Src::ROWS + (threadIdx.x >> 6), row = 0;
+    if (dx >= D.dw || dy >= D.dh) return;
+    do {
+        const WarpTaps t = warp_taps(dx, dy, S.w(), S.h(), D.M, D.dw, D.dh, D.bw0, D.rot180, D.stride);
+        // ---- the offsets of the loads (only used where the taps are inside) and the wide loads of every frame, which are
+        // all issued before the first is used: the gather is bound by the number of memory instructions, not by bytes
+        bool fast = t.interior;
+        size_t tap = 0, c_off = 0, c2_off = 0; // tap: of tap 00 (YUV: its luma, or its pair; Bayer: of the 4 x 4 bytes)
+        bool odd = false, two_crows = false;   // YUV; two_crows: the rows of taps lie in different chroma rows
+        if constexpr (BGR || PROFILE) tap = (size_t)t.sy * S.g.stride + (size_t)t.sx * 3;
+        else if constexpr (YUV) {
+            odd = t.sx & 1;
+            two_crows = L::F420 && (t.sy & 1);
+            tap = L::F420 ? (size_t)t.sy * S.r.stride0 + (size_t)t.sx : (size_t)t.sy * S.r.stride0 + (size_t)(t.sx >> 1) * 4;
+            c_off = (size_t)(t.sy >> 1) * S.r.stride1 + (size_t)(PLANAR ? t.sx >> 1 : t.sx & ~1);
+            c2_off = (size_t)(t.sy >> 1) * S.r.stride2 + (size_t)(t.sx >> 1);
+        } else {
+            fast = t.sx >= 1 && t.sx + 2 < S.sw && t.sy >= 1 && t.sy + 2 < S.sh;
+            tap = (size_t)(t.sy - 1) * S.r.stride0 + (size_t)(t.sx - 1);
+        }
+        u64 ta[FPT], tb[FPT]; // the rows of taps.  BGR, profile: 8 bytes; YUV 4:2:0: 2 luma bytes; 4:2:2: the 8 bytes of two pairs
+        u32 ca[FPT], cb[FPT]; // NV12: U V U V; planar: U U
+        u32 va[FPT], vb[FPT]; // planar: V V
+        u32 rows[FPT][4];     // Bayer
+        if (fast)
+#pragma unroll
+            for (int k = 0; k < FPT; k++)
+                if (k < nf) {
+                    if constexpr (BGR || PROFILE) {
+                        const u8* p00 = S.src + (size_t)(f0 + k) * S.g.frame_stride + tap;
+                        __builtin_memcpy(&ta[k], p00, 8);
+                        __builtin_memcpy(&tb[k], p00 + S.g.stride, 8);
+                    } else if constexpr (YUV) {
+                        const u8* l = S.p0 + (size_t)(f0 + k) * S.r.frame_stride + tap;
+                        if (L::F420) {
+                            u16 a, b;
+                            __builtin_memcpy(&a, l, 2);
+                            __builtin_memcpy(&b, l + S.r.stride0, 2);
+                            ta[k] = a;
+                            tb[k] = b;
+                            const u8* c = S.p1 + (size_t)(f0 + k) * S.r.frame_stride + c_off;
+                            if (NV12) {
+                                __builtin_memcpy(&ca[k], c, 4);
+                                cb[k] = ca[k];
+                                if (two_crows) __builtin_memcpy(&cb[k], c + S.r.stride1, 4);
+                            } else {
+                                const u8* c2 = S.p2 + (size_t)(f0 + k) * S.r.frame_stride + c2_off;
+                                u16 u, v;
+                                __builtin_memcpy(&u, c, 2);
+                                __builtin_memcpy(&v, c2, 2);
+                                ca[k] = cb[k] = u;
+                                va[k] = vb[k] = v;
+                                if (two_crows) {
+                                    __builtin_memcpy(&u, c + S.r.stride1, 2);
+                                    __builtin_memcpy(&v, c2 + S.r.stride2, 2);
+                                    cb[k] = u;
+                                    vb[k] = v;
+                                }
+                            }
+                        } else {
+                            __builtin_memcpy(&ta[k], l, 8);
+                            __builtin_memcpy(&tb[k], l + S.r.stride0, 8);
+                        }
+                    } else {
+                        const u8* m = S.p0 + (size_t)(f0 + k) * S.r.frame_stride + tap;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) __builtin_memcpy(&rows[k][i], m + (size_t)i * S.r.stride0, 4);
+                    }
+                }
+#pragma unroll
+        for (int k = 0; k < FPT; k++) {
+            if (k >= nf) break;
+            int o[3] = {0, 0, 0};
+            if (t.any_in) {
+                // ---- the taps 00, 01, 10, 11.  BGR: v, the bytes as they lie in the frame, -1 for a tap outside it; the
+                // others: q, converted, as b | g << 8 | r << 16, 0 for a tap outside
+                int v[4][3];
+                u32 q[4] = {0u, 0u, 0u, 0u};
+                if constexpr (BGR) {
+                    if (fast) {
+#pragma unroll
+                        for (int c = 0; c < 3; c++) {
+                            v[0][c] = (int)((ta[k] >> (8 * c)) & 255);
+                            v[1][c] = (int)((ta[k] >> (8 * (3 + c))) & 255);
+                            v[2][c] = (int)((tb[k] >> (8 * c)) & 255);
+                            v[3][c] = (int)((tb[k] >> (8 * (3 + c))) & 255);
+                        }
+                    } else {
+                        const u8* p00 = S.src + (size_t)(f0 + k) * S.g.frame_stride + tap;
+                        const u8* p10 = p00 + S.g.stride;
+#pragma unroll
+                        for (int c = 0; c < 3; c++) {
+                            v[0][c] = (t.x0in && t.y0in) ? p00[c] : -1;
+                            v[1][c] = (t.x1in && t.y0in) ? p00[3 + c] : -1;
+                            v[2][c] = (t.x0in && t.y1in) ? p10[c] : -1;
+                            v[3][c] = (t.x1in && t.y1in) ? p10[3 + c] : -1;
+                        }
+                    }
+                } else if (fast) {
+                    if constexpr (PROFILE) {
+                        q[0] = conv((u32)ta[k]);
+                        q[1] = conv((u32)(ta[k] >> 24));
+                        q[2] = conv((u32)tb[k]);
+                        q[3] = conv((u32)(tb[k] >> 24));
+                    } else if constexpr (YUV) {
+                        if (L::F420) {
+                            Chroma a0, a1, b0, b1;
+                            if (NV12) {
+                                const u32 a = ca[k], sa = odd ? a >> 16 : a;
+                                a0 = d_chroma_pair<FMT>(a);
+                                a1 = d_chroma_pair<FMT>(sa);
+                                b0 = a0;
+                                b1 = a1;
+                                if (two_crows) {
+                                    const u32 b = cb[k], sb = odd ? b >> 16 : b;
+                                    b0 = d_chroma_pair<FMT>(b);
+                                    b1 = d_chroma_pair<FMT>(sb);
+                                }
+                            } else {
+                                const u32 u0 = ca[k], v0 = va[k];
+                                a0 = d_chroma(u0 & 255, v0 & 255);
+                                a1 = d_chroma((odd ? u0 >> 8 : u0) & 255, (odd ? v0 >> 8 : v0) & 255);
+                                b0 = a0;
+                                b1 = a1;
+                                if (two_crows) {
+                                    const u32 u1 = cb[k], v1 = vb[k];
+                                    b0 = d_chroma(u1 & 255, v1 & 255);
+                                    b1 = d_chroma((odd ? u1 >> 8 : u1) & 255, (odd ? v1 >> 8 : v1) & 255);
+                                }
+                            }
+                            q[0] = d_yuv_bgr((int)(ta[k] & 255), a0);
+                            q[1] = d_yuv_bgr((int)((ta[k] >> 8) & 255), a1);
+                            q[2] = d_yuv_bgr((int)(tb[k] & 255), b0);
+                            q[3] = d_yuv_bgr((int)((tb[k] >> 8) & 255), b1);
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 2; r++) {
+                                const u64 w = r ? tb[k] : ta[k];
+                                const u32 lo = (u32)w, hi = (u32)(w >> 32), s1 = odd ? hi : lo;
+                                const Chroma c0 = d_chroma((lo >> (8 * L::PU)) & 255, (lo >> (8 * L::PV)) & 255);
+                                const Chroma c1 = d_chroma((s1 >> (8 * L::PU)) & 255, (s1 >> (8 * L::PV)) & 255);
+                                q[2 * r] = d_yuv_bgr((int)((odd ? lo >> (8 * L::Y1) : lo >> (8 * L::Y0)) & 255), c0);
+                                q[2 * r + 1] = d_yuv_bgr((int)((odd ? hi >> (8 * L::Y0) : lo >> (8 * L::Y1)) & 255), c1);
+                            }
+                        }
+                    } else {
+                        const u32* w = rows[k];
+                        q[0] = d_bayer_bgr<FMT>(t.sx, t.sy, w[0], w[1], w[2]);
+                        q[1] = d_bayer_bgr<FMT>(t.sx + 1, t.sy, w[0] >> 8, w[1] >> 8, w[2] >> 8);
+                        q[2] = d_bayer_bgr<FMT>(t.sx, t.sy + 1, w[1], w[2], w[3]);
+                        q[3] = d_bayer_bgr<FMT>(t.sx + 1, t.sy + 1, w[1] >> 8, w[2] >> 8, w[3] >> 8);
+                    }
+                } else {
+                    if constexpr (PROFILE) {
+                        const u8* p00 = S.src + (size_t)(f0 + k) * S.g.frame_stride + tap;
+                        const u8* p10 = p00 + S.g.stride;
+                        auto px = [&](const u8* p) -> u32 { return conv((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16)); };
+                        if (t.x0in && t.y0in) q[0] = px(p00);
+                        if (t.x1in && t.y0in) q[1] = px(p00 + 3);
+                        if (t.x0in && t.y1in) q[2] = px(p10);
+                        if (t.x1in && t.y1in) q[3] = px(p10 + 3);
+                    } else if constexpr (YUV) {
+                        const u8* f0p = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
+                        const u8* f1p = L::F420 ? S.p1 + (size_t)(f0 + k) * S.r.frame_stride : nullptr;
+                        const u8* f2p = PLANAR ? S.p2 + (size_t)(f0 + k) * S.r.frame_stride : nullptr;
+                        if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy);
+                        if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy);
+                        if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy + 1);
+                        if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy + 1);
+                    } else {
+                        const u8* fp = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
+                        if (t.x0in && t.y0in) q[0] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx, t.sy);
+                        if (t.x1in && t.y0in) q[1] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx + 1, t.sy);
+                        if (t.x0in && t.y1in) q[2] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx, t.sy + 1);
+                        if (t.x1in && t.y1in) q[3] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx + 1, t.sy + 1);
+                    }
+                }
+                // ---- the blend
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    int b[4] = {(int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255), (int)((q[3] >> (8 * c)) & 255)};
+                    if constexpr (BGR)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) b[i] = v[i][c] < 0 ? 0 : (use_lut ? (int)lds.lut[k][v[i][c]] : v[i][c]); // border taps are 0
+                    o[c] = warp_blend(b[0], b[1], b[2], b[3], t);
+                }
+            }
+            u8* out = D.dst + (size_t)(f0 + k) * D.frame_stride + t.out_off;
+            out[0] = (u8)o[0];
+            out[1] = (u8)o[1];
+            out[2] = (u8)o[2];
+        }
+        dy += 4;
+    } while (Src::ROWS > 4 && ++row < Src::ROWS / 4 && dy < D.dh);
+}
+
+// ---------------------------------------------------------------------------
+// The kernels: per source one for a single board, which takes the matrix by value, and one (_mb) for every board of a
+// pipeline in one launch: blockIdx.z = board * nz + group of frames; the grid covers the largest board and the blocks
+// outside a smaller one leave at once (what is staged for the shared frames is the same for every board).
+// ---------------------------------------------------------------------------
+// where a multi-board launch writes board T; s0 = the slot of the chunk's frame 0
+__device__ __forceinline__ WarpDst warp_board_dst(const BoardDev& T, int s0)
+{
+    return WarpDst{T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride};
+}
+
+template <int FPT, bool CALC>
+__global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g, WarpM M, int dw, int dh, int bw0,
+                                               int bh0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                               size_t dst_frame_stride, const u8* __restrict__ norm_lut, const u32* __restrict__ minmax,
+                                               size_t mm_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    (void)bh0;
+    warp_gather<WarpBgr<CALC>, FPT>(WarpBgr<CALC>{src, g, norm_lut, minmax, mm_stride}, WarpDst{M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride},
+                                    zero_word, zero_word2, batch, blockIdx.z);
+}
+
+template <int FPT, bool CALC>
+__global__ __launch_bounds__(256) void k_warp_mb(const u8* __restrict__ src, Geom g, const BoardDev* __restrict__ tab, int nz, int s0,
+                                                  const u8* __restrict__ norm_lut, const u32* __restrict__ minmax, size_t mm_stride,
+                                                  u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
+    warp_gather<WarpBgr<CALC>, FPT>(WarpBgr<CALC>{src, g, norm_lut, minmax, mm_stride}, warp_board_dst(T, s0), zero_word, zero_word2, batch,
+                                    blockIdx.z - b * nz);
+}
+
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_yuv(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw, int sh, WarpM M,
+                                                   int dw, int dh, int bw0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                                   size_t dst_frame_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+{
+    warp_gather<WarpRaw<FMT>, FPT>(WarpRaw<FMT>{p0, p1, p2, r, sw, sh}, WarpDst{M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride}, zero_word,
+                                   zero_word2, batch, blockIdx.z);
+}
+
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_yuv_mb(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw, int sh,
+                                                      const BoardDev* __restrict__ tab, int nz, int s0, u32* __restrict__ zero_word,
+                                                      u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
+    warp_gather<WarpRaw<FMT>, FPT>(WarpRaw<FMT>{p0, p1, p2, r, sw, sh}, warp_board_dst(T, s0), zero_word, zero_word2, batch, blockIdx.z - b * nz);
 }
 
 template <int FMT, int FPT>
@@ -436,10 +518,10 @@ __global__ __launch_bounds__(256) void k_warp_bayer(const u8* __restrict__ p0, R
                                                      u8* __restrict__ dst, int dst_stride, size_t dst_frame_stride, u32* __restrict__ zero_word,
                                                      u32* __restrict__ zero_word2, int batch)
 {
-    warp_bayer_body<FMT, FPT>(p0, r, sw, sh, M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch, blockIdx.z);
+    warp_gather<WarpRaw<FMT>, FPT>(WarpRaw<FMT>{p0, nullptr, nullptr, r, sw, sh}, WarpDst{M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride},
+                                   zero_word, zero_word2, batch, blockIdx.z);
 }
 
-// every board of a pipeline in one launch, as k_warp_mb
 template <int FMT, int FPT>
 __global__ __launch_bounds__(256) void k_warp_bayer_mb(const u8* __restrict__ p0, RawGeom r, int sw, int sh, const BoardDev* __restrict__ tab, int nz,
                                                         int s0, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
@@ -447,92 +529,8 @@ __global__ __launch_bounds__(256) void k_warp_bayer_mb(const u8* __restrict__ p0
     const int b = blockIdx.z / nz;
     const BoardDev& T = tab[b];
     if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
-    warp_bayer_body<FMT, FPT>(p0, r, sw, sh, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride,
-                              zero_word, zero_word2, batch, blockIdx.z - b * nz);
-}
-
-// ---------------------------------------------------------------------------
-// The warp with the colour profile applied to its taps (cbv_warp_color_profile, pipelines configured with
-// CBV_SKIP_ENHANCE_PROFILE, cbv_pipeline_color_sweep): apply_color_profile is a function of the pixel alone, so converting
-// the four taps and blending them is, byte for byte, sampling the converted frame: same coordinates (warp_taps), same
-// conversion (d_profile_px), same blend (warp_blend).  A tap outside the frame is BGR (0, 0, 0) as in k_warp, not the
-// profile of black.  This is k_warp_yuv's arrangement with d_profile_px in the place of d_yuv_bgr.
-// A workgroup stages the 7.5 KB d_profile_px reads (ProfileLds) and then covers WP_ROWS destination rows of its 64
-// columns, FPT frames each: 1920 staged words against 4096 conversions per frame.  The tables are an argument, one
-// ProfileTabs per profile of the launch (the grid's z runs over profile x group of frames); a table with enabled = 0
-// leaves the taps as they are.
-// ---------------------------------------------------------------------------
-#define WP_ROWS 16 // destination rows per workgroup: one row of WarpPerspectiveInvoker's 64 x 16 blocks
-
-// bz = the group of frames, pt = the profile's table; src and dst = frame 0 of the batch (for this profile)
-template <int FPT>
-__device__ __forceinline__ void warp_profile_body(const u8* __restrict__ src, Geom g, const double* __restrict__ M, int dw, int dh, int bw0,
-                                                  int rot180, u8* __restrict__ dst, int dst_stride, size_t dst_frame_stride,
-                                                  const StaticTabs* __restrict__ st, const ProfileTabs* __restrict__ pt,
-                                                  u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
-{
-    __shared__ ProfileLds L;
-    warp_zero_words(zero_word, zero_word2);
-    lds_copy(L.sdiv, st->sdiv, sizeof(L.sdiv));
-    lds_copy(L.hdiv, st->hdiv, sizeof(L.hdiv));
-    lds_copy(L.pt.csa, pt->csa, sizeof(L.pt.csa));
-    lds_copy(L.pt.hmask, pt->hmask, sizeof(L.pt.hmask));
-    lds_copy(L.pt.hsel, pt->hsel, sizeof(L.pt.hsel));
-    lds_copy(L.pt.hfr, pt->hfr, sizeof(L.pt.hfr));
-    lds_copy(L.pt.s_f, pt->s_f, sizeof(L.pt.s_f));
-    lds_copy(L.pt.v_f, pt->v_f, sizeof(L.pt.v_f));
-    const bool on = pt->enabled != 0, radical = pt->radical != 0; // uniform
-    __syncthreads();
-    const int f0 = bz * FPT;
-    const int nf = min(FPT, batch - f0);
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    if (dx >= dw) return;
-    // a tap as b | g << 8 | r << 16 (the low three bytes of v) through the profile
-    auto conv = [&](u32 v) -> u32 { return on ? d_profile_px(L, (int)(v & 255u), (int)((v >> 8) & 255u), (int)((v >> 16) & 255u), radical) : (v & 0xFFFFFFu); };
-    for (int dy = blockIdx.y * WP_ROWS + (threadIdx.x >> 6), r = 0; r < WP_ROWS / 4 && dy < dh; r++, dy += 4) {
-        const WarpTaps t = warp_taps(dx, dy, g.w, g.h, M, dw, dh, bw0, rot180, dst_stride);
-        const size_t tap = (size_t)t.sy * g.stride + (size_t)t.sx * 3; // (only dereferenced where the taps are inside)
-        // interior: one unaligned 8-byte load per row of taps, as warp_body (>= 8 bytes of slack behind the last frame)
-        u64 ta[FPT], tb[FPT];
-        if (t.interior)
-#pragma unroll
-            for (int k = 0; k < FPT; k++)
-                if (k < nf) {
-                    const u8* p00 = src + (size_t)(f0 + k) * g.frame_stride + tap;
-                    __builtin_memcpy(&ta[k], p00, 8);
-                    __builtin_memcpy(&tb[k], p00 + g.stride, 8);
-                }
-#pragma unroll
-        for (int k = 0; k < FPT; k++) {
-            if (k >= nf) break;
-            int o[3] = {0, 0, 0};
-            if (t.any_in) {
-                u32 q[4] = {0u, 0u, 0u, 0u}; // taps 00, 01, 10, 11; border taps are 0
-                if (t.interior) {
-                    q[0] = conv((u32)ta[k]);
-                    q[1] = conv((u32)(ta[k] >> 24));
-                    q[2] = conv((u32)tb[k]);
-                    q[3] = conv((u32)(tb[k] >> 24));
-                } else {
-                    const u8* p00 = src + (size_t)(f0 + k) * g.frame_stride + tap;
-                    const u8* p10 = p00 + g.stride;
-                    auto px = [&](const u8* p) -> u32 { return conv((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16)); };
-                    if (t.x0in && t.y0in) q[0] = px(p00);
-                    if (t.x1in && t.y0in) q[1] = px(p00 + 3);
-                    if (t.x0in && t.y1in) q[2] = px(p10);
-                    if (t.x1in && t.y1in) q[3] = px(p10 + 3);
-                }
-#pragma unroll
-                for (int c = 0; c < 3; c++)
-                    o[c] = warp_blend((int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255),
-                                      (int)((q[3] >> (8 * c)) & 255), t);
-            }
-            u8* out = dst + (size_t)(f0 + k) * dst_frame_stride + t.out_off;
-            out[0] = (u8)o[0];
-            out[1] = (u8)o[1];
-            out[2] = (u8)o[2];
-        }
-    }
+    warp_gather<WarpRaw<FMT>, FPT>(WarpRaw<FMT>{p0, nullptr, nullptr, r, sw, sh}, warp_board_dst(T, s0), zero_word, zero_word2, batch,
+                                   blockIdx.z - b * nz);
 }
 
 // blockIdx.z = profile * nz + group of frames; profile p writes its frames dst_profile_stride bytes behind profile p - 1's
@@ -543,11 +541,12 @@ __global__ __launch_bounds__(256) void k_warp_profile(const u8* __restrict__ src
                                                        u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
 {
     const int pi = blockIdx.z / nz;
-    warp_profile_body<FPT>(src, g, M.m, dw, dh, bw0, rot180, dst + (size_t)pi * dst_profile_stride, dst_stride, dst_frame_stride, st, ptabs + pi,
-                           zero_word, zero_word2, batch, blockIdx.z - pi * nz);
+    warp_gather<WarpProfile, FPT>(WarpProfile{src, g, st, ptabs + pi},
+                                  WarpDst{M.m, dw, dh, bw0, rot180, dst + (size_t)pi * dst_profile_stride, dst_stride, dst_frame_stride}, zero_word,
+                                  zero_word2, batch, blockIdx.z - pi * nz);
 }
 
-// every board of a pipeline in one launch, as k_warp_mb; the profile is the pipeline's: one table
+// the profile is the pipeline's: one table
 template <int FPT>
 __global__ __launch_bounds__(256) void k_warp_profile_mb(const u8* __restrict__ src, Geom g, const BoardDev* __restrict__ tab, int nz, int s0,
                                                           const StaticTabs* __restrict__ st, const ProfileTabs* __restrict__ pt,
@@ -556,262 +555,127 @@ __global__ __launch_bounds__(256) void k_warp_profile_mb(const u8* __restrict__ 
     const int b = blockIdx.z / nz;
     const BoardDev& T = tab[b];
     if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * WP_ROWS >= T.S)) return;
-    warp_profile_body<FPT>(src, g, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride, st, pt,
-                           zero_word, zero_word2, batch, blockIdx.z - b * nz);
+    warp_gather<WarpProfile, FPT>(WarpProfile{src, g, st, pt}, warp_board_dst(T, s0), zero_word, zero_word2, batch, blockIdx.z - b * nz);
 }
 
-template <int FPT, bool CALC>
-__global__ __launch_bounds__(256) void k_warp(const u8* __restrict__ src, Geom g, WarpM M, int dw, int dh, int bw0,
-                                               int bh0, int rot180, u8* __restrict__ dst, int dst_stride,
-                                               size_t dst_frame_stride, const u8* __restrict__ norm_lut, const u32* __restrict__ minmax,
-                                               size_t mm_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
+// ---------------------------------------------------------------------------
+// The launchers.  Batched launches take four frames per thread (eight: 13 % fewer instructions again, no change on the
+// path); a launch of a frame or two keeps one thread per pixel and frame.
+// ---------------------------------------------------------------------------
+// groups of frames of a launch: four frames a group from batch 8 on
+static int warp_groups(int batch)
 {
-    warp_body<FPT, CALC>(src, g, M.m, dw, dh, bw0, bh0, rot180, dst, dst_stride, dst_frame_stride, norm_lut, minmax, mm_stride,
-                         zero_word, zero_word2, batch, blockIdx.z);
-}
-
-// every board of a pipeline in one launch: blockIdx.z = board * nz + group of frames; the grid covers the largest board
-// and the blocks outside a smaller one leave at once (the shared frames' byte map is the same for every board)
-template <int FPT, bool CALC>
-__global__ __launch_bounds__(256) void k_warp_mb(const u8* __restrict__ src, Geom g, const BoardDev* __restrict__ tab, int nz, int s0,
-                                                  const u8* __restrict__ norm_lut, const u32* __restrict__ minmax, size_t mm_stride,
-                                                  u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch)
-{
-    const int b = blockIdx.z / nz;
-    const BoardDev& T = tab[b];
-    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * 4 >= T.S)) return;
-    warp_body<FPT, CALC>(src, g, T.Minv, T.S, T.S, T.bw0, T.bh0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3,
-                         T.warped_stride, norm_lut, minmax, mm_stride, zero_word, zero_word2, batch, blockIdx.z - b * nz);
-}
-
-int launch_warp_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, NormSrc norm, int batch,
-                   u32* zero_word, u32* zero_word2)
-{
-    prof_begin(ctx, CBV_K_WARP);
-    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
-    dim3 grid((maxS + 63) / 64, (maxS + 3) / 4, nz * nb);
-    if (fpt == 4) {
-        if (norm.minmax)
-            hipLaunchKernelGGL((k_warp_mb<4, true>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, nullptr, norm.minmax, norm.mm_stride,
-                               zero_word, zero_word2, batch);
-        else
-            hipLaunchKernelGGL((k_warp_mb<4, false>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, norm.lut, nullptr, 0, zero_word,
-                               zero_word2, batch);
-    } else {
-        if (norm.minmax)
-            hipLaunchKernelGGL((k_warp_mb<1, true>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, nullptr, norm.minmax, norm.mm_stride,
-                               zero_word, zero_word2, batch);
-        else
-            hipLaunchKernelGGL((k_warp_mb<1, false>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, norm.lut, nullptr, 0, zero_word,
-                               zero_word2, batch);
-    }
-    prof_end(ctx, CBV_K_WARP);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
-}
-
-int launch_warp(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst,
-                int dst_stride, size_t dst_frame_stride, NormSrc norm, int batch, u32* zero_word, u32* zero_word2)
-{
-    WarpM M;
-    for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
-    int bw0, bh0;
-    warp_block_shape(dw, dh, &bw0, &bh0);
-    prof_begin(ctx, CBV_K_WARP);
-    // batched launches: four frames per thread (eight: 13 % fewer instructions again, no change on the path); a launch of
-    // a frame or two keeps one thread per pixel and frame
-    if (batch >= 8) {
-        dim3 grid((dw + 63) / 64, (dh + 3) / 4, (batch + 3) / 4);
-        if (norm.minmax)
-            hipLaunchKernelGGL((k_warp<4, true>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, bh0, rot180, dst, dst_stride,
-                               dst_frame_stride, nullptr, norm.minmax, norm.mm_stride, zero_word, zero_word2, batch);
-        else
-            hipLaunchKernelGGL((k_warp<4, false>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, bh0, rot180, dst, dst_stride,
-                               dst_frame_stride, norm.lut, nullptr, 0, zero_word, zero_word2, batch);
-    } else {
-        dim3 grid((dw + 63) / 64, (dh + 3) / 4, batch);
-        if (norm.minmax)
-            hipLaunchKernelGGL((k_warp<1, true>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, bh0, rot180, dst, dst_stride,
-                               dst_frame_stride, nullptr, norm.minmax, norm.mm_stride, zero_word, zero_word2, batch);
-        else
-            hipLaunchKernelGGL((k_warp<1, false>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, bh0, rot180, dst, dst_stride,
-                               dst_frame_stride, norm.lut, nullptr, 0, zero_word, zero_word2, batch);
-    }
-    prof_end(ctx, CBV_K_WARP);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
-}
-
-// as launch_warp (four frames per thread in batched launches), for `np` profiles at once: ptabs[np] on the device
-int launch_warp_profile(cbv_ctx* ctx, const u8* src, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
-                        size_t dst_frame_stride, size_t dst_profile_stride, const ProfileTabs* ptabs, int np, int batch, u32* zero_word,
-                        u32* zero_word2)
-{
-    WarpM M;
-    for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
-    int bw0, bh0;
-    warp_block_shape(dw, dh, &bw0, &bh0);
-    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
-    if (np <= 0 || batch <= 0 || (long long)np * nz > 65535) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_profile: %d profiles x %d frames do not fit a launch", np, batch);
-    const dim3 grid((dw + 63) / 64, (dh + WP_ROWS - 1) / WP_ROWS, np * nz);
-    prof_begin(ctx, CBV_K_WARP);
-    if (fpt == 4)
-        hipLaunchKernelGGL((k_warp_profile<4>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride,
-                           dst_profile_stride, ctx->tabs, ptabs, nz, zero_word, zero_word2, batch);
-    else
-        hipLaunchKernelGGL((k_warp_profile<1>), grid, dim3(256), 0, ctx->stream, src, g, M, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride,
-                           dst_profile_stride, ctx->tabs, ptabs, nz, zero_word, zero_word2, batch);
-    prof_end(ctx, CBV_K_WARP);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
-}
-
-int launch_warp_profile_mb(cbv_ctx* ctx, const u8* src, Geom g, const BoardDev* tab, int nb, int maxS, int s0, const ProfileTabs* pt, int batch,
-                           u32* zero_word, u32* zero_word2)
-{
-    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
-    const dim3 grid((maxS + 63) / 64, (maxS + WP_ROWS - 1) / WP_ROWS, nz * nb);
-    prof_begin(ctx, CBV_K_WARP);
-    if (fpt == 4)
-        hipLaunchKernelGGL((k_warp_profile_mb<4>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, ctx->tabs, pt, zero_word, zero_word2, batch);
-    else
-        hipLaunchKernelGGL((k_warp_profile_mb<1>), grid, dim3(256), 0, ctx->stream, src, g, tab, nz, s0, ctx->tabs, pt, zero_word, zero_word2, batch);
-    prof_end(ctx, CBV_K_WARP);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
-}
-
-// the raw planes a fused warp may read: what launch_ingest asks of them (YV12 leaves as YUV420P)
-static int check_warp_yuv(cbv_ctx* ctx, RawPlanes* pl, RawGeom* r, Geom g, int batch)
-{
-    RC(check_raw_format(ctx, r->fmt, g.w, g.h, "launch_warp_yuv"));
-    if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_yuv: bad planes or strides");
-    const int strides[3] = {r->stride0, r->stride1, r->stride2};
-    RC(check_raw_planes(ctx, r->fmt, g.w, pl->p, strides, "launch_warp_yuv"));
-    raw_planes_canonical(pl, r);
-    return CBV_OK;
-}
-
-// one case per layout the kernels have a form for, both frames-per-thread counts each
-#define CBV_WARP_YUV_FORMATS(LAUNCH)                   \
-    switch (r.fmt) {                                   \
-    case CBV_FMT_NV12: LAUNCH(CBV_FMT_NV12); break;    \
-    case CBV_FMT_NV21: LAUNCH(CBV_FMT_NV21); break;    \
-    case CBV_FMT_YUYV: LAUNCH(CBV_FMT_YUYV); break;    \
-    case CBV_FMT_YVYU: LAUNCH(CBV_FMT_YVYU); break;    \
-    case CBV_FMT_UYVY: LAUNCH(CBV_FMT_UYVY); break;    \
-    default: LAUNCH(CBV_FMT_YUV420P);                  \
-    }
-
-// as launch_warp: four frames per thread in batched launches, one thread per pixel and frame in a launch of a frame or two
-int launch_warp_yuv(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
-                    size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2)
-{
-    RC(check_warp_yuv(ctx, &pl, &r, g, batch));
-    WarpM M;
-    for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
-    int bw0, bh0;
-    warp_block_shape(dw, dh, &bw0, &bh0);
     const int fpt = batch >= 8 ? 4 : 1;
-    const dim3 grid((dw + 63) / 64, (dh + 3) / 4, (batch + fpt - 1) / fpt);
-    prof_begin(ctx, CBV_K_WARP_YUV);
-#define CBV_WARP_YUV_K(FMT, FPT)                                                                                                          \
-    hipLaunchKernelGGL((k_warp_yuv<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], pl.p[1], pl.p[2], r, g.w, g.h, M, dw, dh, bw0, rot180, \
-                       dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch)
-#define CBV_WARP_YUV(FMT)             \
-    if (fpt == 4) CBV_WARP_YUV_K(FMT, 4); \
-    else CBV_WARP_YUV_K(FMT, 1)
-    CBV_WARP_YUV_FORMATS(CBV_WARP_YUV)
-#undef CBV_WARP_YUV
-#undef CBV_WARP_YUV_K
-    prof_end(ctx, CBV_K_WARP_YUV);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
+    return (batch + fpt - 1) / fpt;
 }
 
-int launch_warp_yuv_mb(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word,
-                       u32* zero_word2)
+template <int N>
+using WarpInt = std::integral_constant<int, N>;
+
+// launch(fmt, fpt) with the compile-time forms of a raw format id and of the frames per thread of `batch` frames
+// (CBV_FMT_BGR: the BGR sources, whose kernels have no format parameter)
+template <class F>
+static void warp_dispatch(int fmt, int batch, F&& launch)
 {
-    RC(check_warp_yuv(ctx, &pl, &r, g, batch));
-    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
-    const dim3 grid((maxS + 63) / 64, (maxS + 3) / 4, nz * nb);
-    prof_begin(ctx, CBV_K_WARP_YUV);
-#define CBV_WARP_YUV_MB_K(FMT, FPT)                                                                                                        \
-    hipLaunchKernelGGL((k_warp_yuv_mb<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], pl.p[1], pl.p[2], r, g.w, g.h, tab, nz, s0, zero_word, \
-                       zero_word2, batch)
-#define CBV_WARP_YUV_MB(FMT)             \
-    if (fpt == 4) CBV_WARP_YUV_MB_K(FMT, 4); \
-    else CBV_WARP_YUV_MB_K(FMT, 1)
-    CBV_WARP_YUV_FORMATS(CBV_WARP_YUV_MB)
-#undef CBV_WARP_YUV_MB
-#undef CBV_WARP_YUV_MB_K
-    prof_end(ctx, CBV_K_WARP_YUV);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
-}
-
-// the mosaics a fused warp may read: what launch_ingest asks of them
-static int check_warp_bayer(cbv_ctx* ctx, const RawPlanes& pl, const RawGeom& r, Geom g, int batch)
-{
-    RC(check_raw_format(ctx, r.fmt, g.w, g.h, "launch_warp_bayer"));
-    if (!raw_fmt_bayer(r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_bayer: format %d is not a Bayer format", r.fmt);
-    if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_bayer: bad planes or strides");
-    const int strides[3] = {r.stride0, r.stride1, r.stride2};
-    return check_raw_planes(ctx, r.fmt, g.w, pl.p, strides, "launch_warp_bayer");
-}
-
-#define CBV_WARP_BAYER_FORMATS(LAUNCH)                                 \
-    switch (r.fmt) {                                                   \
-    case CBV_FMT_BAYER_RGGB: LAUNCH(CBV_FMT_BAYER_RGGB); break;        \
-    case CBV_FMT_BAYER_BGGR: LAUNCH(CBV_FMT_BAYER_BGGR); break;        \
-    case CBV_FMT_BAYER_GRBG: LAUNCH(CBV_FMT_BAYER_GRBG); break;        \
-    default: LAUNCH(CBV_FMT_BAYER_GBRG);                               \
+    auto with_fmt = [&](auto f) {
+        if (batch >= 8) launch(f, WarpInt<4>());
+        else launch(f, WarpInt<1>());
+    };
+    switch (fmt) {
+    case CBV_FMT_BGR: return with_fmt(WarpInt<CBV_FMT_BGR>());
+    case CBV_FMT_NV12: return with_fmt(WarpInt<CBV_FMT_NV12>());
+    case CBV_FMT_NV21: return with_fmt(WarpInt<CBV_FMT_NV21>());
+    case CBV_FMT_YUYV: return with_fmt(WarpInt<CBV_FMT_YUYV>());
+    case CBV_FMT_YVYU: return with_fmt(WarpInt<CBV_FMT_YVYU>());
+    case CBV_FMT_UYVY: return with_fmt(WarpInt<CBV_FMT_UYVY>());
+    case CBV_FMT_BAYER_RGGB: return with_fmt(WarpInt<CBV_FMT_BAYER_RGGB>());
+    case CBV_FMT_BAYER_BGGR: return with_fmt(WarpInt<CBV_FMT_BAYER_BGGR>());
+    case CBV_FMT_BAYER_GRBG: return with_fmt(WarpInt<CBV_FMT_BAYER_GRBG>());
+    case CBV_FMT_BAYER_GBRG: return with_fmt(WarpInt<CBV_FMT_BAYER_GBRG>());
+    default: return with_fmt(WarpInt<CBV_FMT_YUV420P>());
     }
+}
 
-// as launch_warp_yuv: four frames per thread in batched launches, one thread per pixel and frame in a launch of a frame or two
-int launch_warp_bayer(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
-                      size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2)
+// What both launchers do around their kernels: the refusals of the source (raw planes: what launch_ingest asks of them; YV12
+// leaves as YUV420P), the groups of frames, the grid of a dw x dh destination with nz * zmul layers, the profiling bracket.
+// launch(fmt, fpt, grid, nz) issues the kernel of the source's kind.
+template <class F>
+static int warp_launch(cbv_ctx* ctx, WarpSrc* s, int dw, int dh, int zmul, int batch, F&& launch)
 {
-    RC(check_warp_bayer(ctx, pl, r, g, batch));
+    if (s->raw()) {
+        const char* what = s->kind == WarpSrc::BAYER ? "launch_warp_bayer" : "launch_warp_yuv";
+        RC(check_raw_format(ctx, s->r.fmt, s->g.w, s->g.h, what));
+        // (warp_src_raw takes the kind from the format: only a WarpSrc filled by hand can fail this)
+        if (s->kind == WarpSrc::BAYER && !raw_fmt_bayer(s->r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a Bayer format", what, s->r.fmt);
+        if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes or strides", what);
+        const int strides[3] = {s->r.stride0, s->r.stride1, s->r.stride2};
+        RC(check_raw_planes(ctx, s->r.fmt, s->g.w, s->planes.p, strides, what));
+        raw_planes_canonical(&s->planes, &s->r);
+    }
+    const int nz = warp_groups(batch), rows = s->kind == WarpSrc::PROFILE ? WP_ROWS : 4;
+    const dim3 grid((dw + 63) / 64, (dh + rows - 1) / rows, nz * zmul);
+    const int prof = s->raw() ? CBV_K_WARP_YUV : CBV_K_WARP;
+    prof_begin(ctx, prof);
+    warp_dispatch(s->raw() ? s->r.fmt : CBV_FMT_BGR, batch, [&](auto fmt, auto fpt) { launch(fmt, fpt, grid, nz); });
+    prof_end(ctx, prof);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_warp(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
+                int batch, u32* zero_word, u32* zero_word2)
+{
     WarpM M;
     for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
     int bw0, bh0;
     warp_block_shape(dw, dh, &bw0, &bh0);
-    const int fpt = batch >= 8 ? 4 : 1;
-    const dim3 grid((dw + 63) / 64, (dh + 3) / 4, (batch + fpt - 1) / fpt);
-    prof_begin(ctx, CBV_K_WARP_YUV);
-#define CBV_WARP_BAYER_K(FMT, FPT)                                                                                                      \
-    hipLaunchKernelGGL((k_warp_bayer<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], r, g.w, g.h, M, dw, dh, bw0, rot180, dst, dst_stride, \
-                       dst_frame_stride, zero_word, zero_word2, batch)
-#define CBV_WARP_BAYER(FMT)                 \
-    if (fpt == 4) CBV_WARP_BAYER_K(FMT, 4); \
-    else CBV_WARP_BAYER_K(FMT, 1)
-    CBV_WARP_BAYER_FORMATS(CBV_WARP_BAYER)
-#undef CBV_WARP_BAYER
-#undef CBV_WARP_BAYER_K
-    prof_end(ctx, CBV_K_WARP_YUV);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
+    const bool profile = s.kind == WarpSrc::PROFILE;
+    if (profile && (s.np <= 0 || batch <= 0 || (long long)s.np * warp_groups(batch) > 65535))
+        return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_profile: %d profiles x %d frames do not fit a launch", s.np, batch);
+    const hipStream_t st = ctx->stream;
+    return warp_launch(ctx, &s, dw, dh, profile ? s.np : 1, batch, [&](auto fmt, auto fpt, dim3 grid, int nz) {
+        constexpr int FMT = decltype(fmt)::value, FPT = decltype(fpt)::value;
+        if constexpr (FMT == CBV_FMT_BGR) {
+            if (profile)
+                hipLaunchKernelGGL((k_warp_profile<FPT>), grid, dim3(256), 0, st, s.bgr, s.g, M, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride,
+                                   s.dst_profile_stride, ctx->tabs, s.ptabs, nz, zero_word, zero_word2, batch);
+            else if (s.norm.minmax)
+                hipLaunchKernelGGL((k_warp<FPT, true>), grid, dim3(256), 0, st, s.bgr, s.g, M, dw, dh, bw0, bh0, rot180, dst, dst_stride,
+                                   dst_frame_stride, nullptr, s.norm.minmax, s.norm.mm_stride, zero_word, zero_word2, batch);
+            else
+                hipLaunchKernelGGL((k_warp<FPT, false>), grid, dim3(256), 0, st, s.bgr, s.g, M, dw, dh, bw0, bh0, rot180, dst, dst_stride,
+                                   dst_frame_stride, s.norm.lut, nullptr, 0, zero_word, zero_word2, batch);
+        } else if constexpr (raw_fmt_bayer(FMT))
+            hipLaunchKernelGGL((k_warp_bayer<FMT, FPT>), grid, dim3(256), 0, st, s.planes.p[0], s.r, s.g.w, s.g.h, M, dw, dh, bw0, rot180, dst,
+                               dst_stride, dst_frame_stride, zero_word, zero_word2, batch);
+        else
+            hipLaunchKernelGGL((k_warp_yuv<FMT, FPT>), grid, dim3(256), 0, st, s.planes.p[0], s.planes.p[1], s.planes.p[2], s.r, s.g.w, s.g.h, M, dw,
+                               dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch);
+    });
 }
 
-int launch_warp_bayer_mb(cbv_ctx* ctx, RawPlanes pl, RawGeom r, Geom g, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word,
-                         u32* zero_word2)
+int launch_warp_mb(cbv_ctx* ctx, WarpSrc s, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2)
 {
-    RC(check_warp_bayer(ctx, pl, r, g, batch));
-    const int fpt = batch >= 8 ? 4 : 1, nz = (batch + fpt - 1) / fpt;
-    const dim3 grid((maxS + 63) / 64, (maxS + 3) / 4, nz * nb);
-    prof_begin(ctx, CBV_K_WARP_YUV);
-#define CBV_WARP_BAYER_MB_K(FMT, FPT)                                                                                                  \
-    hipLaunchKernelGGL((k_warp_bayer_mb<FMT, FPT>), grid, dim3(256), 0, ctx->stream, pl.p[0], r, g.w, g.h, tab, nz, s0, zero_word, zero_word2, batch)
-#define CBV_WARP_BAYER_MB(FMT)                 \
-    if (fpt == 4) CBV_WARP_BAYER_MB_K(FMT, 4); \
-    else CBV_WARP_BAYER_MB_K(FMT, 1)
-    CBV_WARP_BAYER_FORMATS(CBV_WARP_BAYER_MB)
-#undef CBV_WARP_BAYER_MB
-#undef CBV_WARP_BAYER_MB_K
-    prof_end(ctx, CBV_K_WARP_YUV);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
+    const hipStream_t st = ctx->stream;
+    return warp_launch(ctx, &s, maxS, maxS, nb, batch, [&](auto fmt, auto fpt, dim3 grid, int nz) {
+        constexpr int FMT = decltype(fmt)::value, FPT = decltype(fpt)::value;
+        if constexpr (FMT == CBV_FMT_BGR) {
+            if (s.kind == WarpSrc::PROFILE)
+                hipLaunchKernelGGL((k_warp_profile_mb<FPT>), grid, dim3(256), 0, st, s.bgr, s.g, tab, nz, s0, ctx->tabs, s.ptabs, zero_word, zero_word2,
+                                   batch);
+            else if (s.norm.minmax)
+                hipLaunchKernelGGL((k_warp_mb<FPT, true>), grid, dim3(256), 0, st, s.bgr, s.g, tab, nz, s0, nullptr, s.norm.minmax, s.norm.mm_stride,
+                                   zero_word, zero_word2, batch);
+            else
+                hipLaunchKernelGGL((k_warp_mb<FPT, false>), grid, dim3(256), 0, st, s.bgr, s.g, tab, nz, s0, s.norm.lut, nullptr, 0, zero_word,
+                                   zero_word2, batch);
+        } else if constexpr (raw_fmt_bayer(FMT))
+            hipLaunchKernelGGL((k_warp_bayer_mb<FMT, FPT>), grid, dim3(256), 0, st, s.planes.p[0], s.r, s.g.w, s.g.h, tab, nz, s0, zero_word, zero_word2,
+                               batch);
+        else
+            hipLaunchKernelGGL((k_warp_yuv_mb<FMT, FPT>), grid, dim3(256), 0, st, s.planes.p[0], s.planes.p[1], s.planes.p[2], s.r, s.g.w, s.g.h, tab, nz,
+                               s0, zero_word, zero_word2, batch);
+    });
 }
 
 // ---------------------------------------------------------------------------

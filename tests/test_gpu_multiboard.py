@@ -161,6 +161,36 @@ def test_two_boards_match_the_oracle_chain(gpu_ctx, oracle):
     p.close()
 
 
+@pytest.mark.parametrize("attached", [0, 1], ids=["1board", "2boards"])
+def test_warp_short_last_group_and_taps_outside(gpu_ctx, oracle, attached):
+    """the warp with the folded normalize where the runs above do not take it: a quad whose right and top parts leave the
+    322 x 242 frame, in one run of 11 frames in one chunk (groups of four frames per thread, the last one of three, the byte
+    map from the table) and then in a run of 2 frames (one frame per thread, the byte map worked out from [min, max]), with
+    one board (k_warp) and with two (k_warp_mb; the second smaller and rotated), against the oracle's chain"""
+    from chessboard_vision_amd.stream import BoardPipeline
+    from helpers import oracle_frame
+    w, h, n = 322, 242, 13
+    quad = S.scaled_corners(w, h) + np.float32([0.42 * w, -0.3 * h])
+    assert (quad[:, 0] > w).any() and (quad[:, 1] < 0).any()
+    frames = [oracle_frame(w, h, "dim", frame_idx=k, frames_per_ply=2) for k in range(n)]
+    p = BoardPipeline(w, h, n)
+    p.configure(quad, profile=S.SHIPPED_PROFILE, chunk=11, lanes=1)
+    boards = [(p, quad, dict(), False)]
+    if attached:
+        size = dict(display_size=(800, 600), margin=100)
+        boards.append((p.add_board(quad + np.float32(3), rot180=True, **size), quad + np.float32(3), size, True))
+    for k, f in enumerate(frames):
+        p.upload(k, f)
+    p.run(0, 11)
+    p.run(11, 2)
+    for k, f in enumerate(frames):
+        enh = oracle.process_pipeline(f, S.SHIPPED_PROFILE)
+        for b, pts, size, rot in boards:
+            want = oracle.warp_image(enh, pts, **size)[0]
+            assert np.array_equal(b.download(2, k), oracle.rotate180(want) if rot else want), (attached, b is p, k)
+    p.close()
+
+
 def _launches(ctx, n_boards):
     from chessboard_vision_amd import _native as N
     from chessboard_vision_amd.stream import BoardPipeline

@@ -2,6 +2,7 @@
 against the two existing product entry points composed.  Shapes are the smallest at which the kernel can go wrong: a source
 smaller than a tile, widths that are no multiple of 4, a strided view, destinations that are no multiple of the 64 x 16
 workgroup tile and one of many tiles, quads partly, mirrored and entirely outside the frame, with and without the rotation.
+One case takes the pipeline's profile-only mode through the four-frames-per-thread form with a short last group.
 Tolerance 0."""
 import numpy as np
 import pytest
@@ -84,6 +85,34 @@ def test_every_profile_on_the_board_quad(gpu_ctx, oracle):
             assert np.array_equal(got, want), (pal, name, int((got != want).sum()))
             got180 = warp_image_profiled(f, pts, prof, rot180=True)[0]
             assert np.array_equal(got180, oracle.rotate180(want)), (pal, name)
+
+
+@pytest.mark.parametrize("attached", [0, 1], ids=["1board", "2boards"])
+def test_profile_mode_short_last_group_and_taps_outside(gpu_ctx, oracle, attached):
+    """the pipeline's profile-only mode where the other tests do not take it: a chunk of 11 frames (groups of four frames per
+    thread, the last one of three), a quad whose right and top parts leave the 322 x 242 frame, one board (k_warp_profile) and
+    two (k_warp_profile_mb; the second smaller and rotated), against the oracle's apply_color_profile -> warp_image"""
+    from chessboard_vision_amd import synth as S
+    from chessboard_vision_amd.stream import BoardPipeline
+    w, h, n = 322, 242, 11
+    prof = PROFILES["shipped"]
+    quad = S.scaled_corners(w, h) + np.float32([0.42 * w, -0.3 * h])
+    assert (quad[:, 0] > w).any() and (quad[:, 1] < 0).any()
+    p = BoardPipeline(w, h, n)
+    p.configure(quad, profile=prof, chunk=n, lanes=1, enhance="profile")
+    boards = [(p, quad, dict(), False)]
+    if attached:
+        size = dict(display_size=(800, 600), margin=100)
+        boards.append((p.add_board(quad + np.float32(3), rot180=True, **size), quad + np.float32(3), size, True))
+    p.synth(0, n, scene="normal")
+    p.run(0, n)
+    for i in range(n):
+        col = oracle.apply_color_profile(p.download(0, i), prof)
+        for b, pts, size, rot in boards:
+            want = oracle.warp_image(col, pts, **size)[0]
+            want = oracle.rotate180(want) if rot else want
+            assert np.array_equal(b.download(2, i), want), (attached, b is p, i)
+    p.close()
 
 
 def test_a_profile_of_black_is_not_black(oracle):
