@@ -243,6 +243,7 @@ class ColorSweepInfo(C.Structure):
 
 COLOR_SWEEP_MAX_PROFILES = 65536
 SKIP_ENHANCE_PROFILE = 2  # cbv_pipeline_config::skip_enhance: the colour profile only (CBV_SKIP_ENHANCE_PROFILE)
+SKIP_ENHANCE_PROFILE_RAW = 3  # ... and camera-native frames are sampled as they are (CBV_SKIP_ENHANCE_PROFILE_RAW)
 
 
 class PieceChoice(C.Structure):
@@ -386,6 +387,8 @@ def load():
         "cbv_pipeline_host_slot_bytes": (C.c_size_t, [vp]),
         "cbv_pipeline_set_model_update": (i32, [vp, i32, dbl]),
         "cbv_pipeline_set_change_blur": (i32, [vp, i32]),
+        "cbv_pipeline_set_profile": (i32, [vp, P(ColorProfile)]),
+        "cbv_warp_color_profile_raw": (i32, [vp, P(RawFrame), i32, i32, P(ColorProfile), vp, i32, i32, i32, u8p, i32]),
         "cbv_pipeline_model": (i32, [vp, i32, i32, vp]),
         "cbv_pipeline_sweep": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, P(SweepInfo)]),
         "cbv_pipeline_change_hist": (i32, [vp, i32, i32, i32, vp]),

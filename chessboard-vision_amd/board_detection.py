@@ -58,11 +58,21 @@ def warp_image(img, points, display_size=(1280, 720), margin=100):
     return warped, matrix, board_size
 
 
-def warp_perspective_profiled(img, M, dsize, profile, rot180=False):
+def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr"):
     """warp_perspective(ImageEnhancer(profile).apply_color_profile(img), M, dsize, rot180), byte for byte, in one kernel: the
     profile is applied to the four source pixels each destination pixel blends (include/cbv.h, cbv_warp_color_profile).
-    `profile`: a dict with the keys of color_profile.json, `None` / `{}` = no profile."""
+    `profile`: a dict with the keys of color_profile.json, `None` / `{}` = no profile.
+    `fmt` other than "bgr": `img` is a camera-native frame in the layout yuv_to_bgr / bayer_to_bgr take, and the result is
+    that of the converted frame, with neither the BGR frame nor the profiled frame made (cbv_warp_color_profile_raw)."""
     c = N.context()
+    if N.format_id(fmt) != N.FMT_BGR:
+        raw, w, h, keep = N.raw_frame(img, fmt)
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        dw, dh = int(dsize[0]), int(dsize[1])
+        out = np.empty((dh, dw, 3), np.uint8)
+        c.check(c.lib.cbv_warp_color_profile_raw(c.h, raw, w, h, N.ColorProfile.from_dict(profile), N.ptr(M), dw, dh, 1 if rot180 else 0,
+                                                 N.ptr(out), out.strides[0]))
+        return out
     f = N.as_bgr(img)
     M = np.ascontiguousarray(M, dtype=np.float64)
     dw, dh = int(dsize[0]), int(dsize[1])
@@ -72,14 +82,14 @@ def warp_perspective_profiled(img, M, dsize, profile, rot180=False):
     return out
 
 
-def warp_image_profiled(img, points, profile, display_size=(1280, 720), margin=100, rot180=False):
+def warp_image_profiled(img, points, profile, display_size=(1280, 720), margin=100, rot180=False, fmt="bgr"):
     """warp_image(ImageEnhancer(profile).apply_color_profile(img), points, display_size, margin) in one kernel
-    (warp_perspective_profiled); `rot180` adds cv2.rotate(ROTATE_180).  Returns what warp_image returns:
-    (warped, matrix, board_size)."""
+    (warp_perspective_profiled); `rot180` adds cv2.rotate(ROTATE_180); `fmt`: the format of a camera-native `img`.
+    Returns what warp_image returns: (warped, matrix, board_size)."""
     board_size = min(display_size) - margin
     pts2 = np.float32([[0, 0], [board_size, 0], [0, board_size], [board_size, board_size]])
     matrix = get_perspective_transform(np.float32(points), pts2)
-    return warp_perspective_profiled(img, matrix, (board_size, board_size), profile, rot180), matrix, board_size
+    return warp_perspective_profiled(img, matrix, (board_size, board_size), profile, rot180, fmt), matrix, board_size
 
 
 def yuv_to_bgr(frame, fmt):

@@ -812,7 +812,7 @@ void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides)
     planes[2] = n > 2 ? raw->plane2 : nullptr, strides[2] = n > 2 ? raw->stride2 : 0;
 }
 
-int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what)
+int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlanes* dev_out, RawGeom* r_out, const char* what)
 {
     RC(check_raw_format(ctx, raw->fmt, w, h, what));
     const u8* planes[3];
@@ -838,6 +838,16 @@ int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* ds
         dev.p[i] = st + off[i];
     }
     r.stride0 = dev_stride[0], r.stride1 = dev_stride[1], r.stride2 = dev_stride[2];
+    *dev_out = dev;
+    *r_out = r;
+    return CBV_OK;
+}
+
+int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what)
+{
+    RawPlanes dev;
+    RawGeom r;
+    RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, what));
     return launch_ingest(ctx, dev, r, dst, g, 1);
 }
 
@@ -851,6 +861,35 @@ extern "C" int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int
     RC(dev_ensure(ctx, &ctx->a, g.frame_stride));
     RC(raw_h2d_convert(ctx, raw, w, h, (u8*)ctx->a.p, g, "cbv_yuv_to_bgr"));
     return download(ctx, ctx->a.p, bgr, w * 3, h, bgr_stride);
+}
+
+extern "C" int cbv_warp_color_profile_raw(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, const cbv_color_profile* profile, const double* M9,
+                                          int dw, int dh, int rot180, uint8_t* out, int out_stride)
+{
+    const char* who = "cbv_warp_color_profile_raw";
+    if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
+    if (!raw || !out || !M9 || !profile || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dw > 8192 || dh > 8192 || out_stride < dw * 3)
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
+    RC(check_raw_format(ctx, raw->fmt, w, h, who)); // (a BGR frame goes to cbv_warp_color_profile)
+    ProfileTabs pt;
+    RC(profile_tabs_checked(ctx, profile, &pt, who));
+    CBV_ENTER(ctx);
+    double Minv[9];
+    if (!host_invert3x3(M9, Minv)) memset(Minv, 0, sizeof(Minv));
+    RawPlanes dev;
+    RawGeom r;
+    RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, who)); // (the staging buffer keeps 256 bytes behind the last plane: the wide loads' slack)
+    RC(dev_ensure(ctx, &ctx->a, (size_t)dw * dh * 3 + 256));
+    Geom g = tight_geom(w, h);
+    WarpSrc src = warp_src_raw(dev, r, g); // a disabled profile: the plain raw warp
+    if (profile->enabled) {
+        RC(dev_ensure(ctx, &ctx->b, sizeof(ProfileTabs))); // the call's tables
+        CBV_HIP(ctx, hipMemcpyAsync(ctx->b.p, &pt, sizeof(pt), hipMemcpyHostToDevice, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt is on this stack)
+        src = warp_src_raw_profile(dev, r, g, (const ProfileTabs*)ctx->b.p);
+    }
+    RC(launch_warp(ctx, src, Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, 1));
+    return download(ctx, ctx->a.p, out, dw * 3, dh, out_stride);
 }
 
 // ---------------------------------------------------------------------------

@@ -423,7 +423,10 @@ void raw_planes_canonical(RawPlanes* planes, RawGeom* r);
 int launch_ingest(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, int batch);
 // the planes and strides a host frame's format has; null / 0 for the rest, whose fields are not read
 void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides);
-// one raw host frame (any YUV format, strided views) through the context's staging buffer into a BGR device image
+// one raw host frame (any YUV or Bayer format, strided views) into the context's staging buffer (ctx->in), which keeps 256
+// readable bytes behind the last plane: its device planes and their strides
+int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlanes* dev, RawGeom* r, const char* what);
+// ... and from there into a BGR device image
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
 
 // What the warp samples (k_warp.hip): the frames of a batch, frame 0's pointers.
@@ -432,12 +435,13 @@ struct WarpSrc {
     Geom g;                    // the frames' width and height; BGR, PROFILE: their strides too
     const u8* bgr;             // BGR, PROFILE
     NormSrc norm;              // BGR: cv2.normalize's byte map applied to the taps (none: the plain warp)
-    const ProfileTabs* ptabs;  // PROFILE: device tables [np]
+    const ProfileTabs* ptabs;  // PROFILE, and YUV / BAYER with a profile (warp_src_raw_profile): device tables [np]
     int np;
     size_t dst_profile_stride;
     RawPlanes planes;          // YUV, BAYER: in memory order
     RawGeom r;                 // (fmt = CBV_FMT_BGR for BGR and PROFILE)
     bool raw() const { return kind == YUV || kind == BAYER; }
+    bool profiled() const { return kind == PROFILE || (raw() && ptabs); } // the profile kernels' tiling (WP_ROWS rows a workgroup)
 };
 // BGR frames (k_warp), the taps through `norm`
 static inline WarpSrc warp_src_bgr(const u8* src, Geom g, NormSrc norm)
@@ -454,7 +458,8 @@ static inline WarpSrc warp_src_bgr(const u8* src, Geom g, NormSrc norm)
 // for byte, with no converted frame in between, for `np` profiles at once.  ptabs[np] = device tables (build_profile_tabs),
 // the caller's, not ctx->ptabs; profile p writes its `batch` frames at dst + p * dst_profile_stride; a table with
 // enabled = 0 is the plain warp.  np x groups of frames (four frames a group from batch 8 on) <= 65535.  The multi-board
-// launch takes one table, the pipeline's.  Counted as CBV_K_WARP: the enumeration of profile ids is closed.
+// launch reads the boards' own tables (BoardDev::ptabs) instead of `ptabs`.  Counted as CBV_K_WARP: the enumeration of profile
+// ids is closed.
 static inline WarpSrc warp_src_profile(const u8* src, Geom g, const ProfileTabs* ptabs, int np = 1, size_t dst_profile_stride = 0)
 {
     WarpSrc s = warp_src_bgr(src, g, NormSrc());
@@ -478,6 +483,18 @@ static inline WarpSrc warp_src_raw(RawPlanes planes, RawGeom r, Geom g)
     s.g = g;
     s.planes = planes;
     s.r = r;
+    return s;
+}
+// Raw frames with the colour profile applied to the converted taps (k_warp_raw_profile.hip): launch_ingest, then
+// apply_color_profile, then the warp, byte for byte, with neither frame in between; ptabs / np / dst_profile_stride as
+// warp_src_profile takes them, the slack behind the frames as warp_src_raw asks.  The multi-board launch reads the boards'
+// own tables (BoardDev::ptabs) instead of `ptabs`, which only has to be non-null there.  Counted as CBV_K_WARP_YUV.
+static inline WarpSrc warp_src_raw_profile(RawPlanes planes, RawGeom r, Geom g, const ProfileTabs* ptabs, int np = 1, size_t dst_profile_stride = 0)
+{
+    WarpSrc s = warp_src_raw(planes, r, g);
+    s.ptabs = ptabs;
+    s.np = np;
+    s.dst_profile_stride = dst_profile_stride;
     return s;
 }
 // `batch` frames of `src` onto one dw x dh board: four frames per thread from batch 8 on, one thread per pixel and frame below
@@ -687,6 +704,9 @@ struct BoardDev {
     const float* cmean;
     const float* csd;
     ChangeBlur cb;
+    // the board's colour profile (cbv_pipeline_set_profile): its device table in the profile modes (enabled = 0 in it: the
+    // board's taps stay as they are), null otherwise; read by k_warp_profile_mb and k_warp_raw_profile_mb
+    const ProfileTabs* ptabs;
 };
 ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
 // per-pass HoughCfg of a board (layout and maxc as launch_hough / launch_hough_second set them); returns the LDS bytes
@@ -694,6 +714,10 @@ ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
 void hough_board_cfgs(HoughCfg base, HoughCfg out[2], size_t lds[2]);
 // one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0
 int launch_warp_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
+// what launch_warp / launch_warp_mb hand a raw source with a profile (warp_src_raw_profile) to: k_warp_raw_profile.hip
+int launch_warp_raw_profile(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
+                            size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2);
+int launch_warp_raw_profile_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);

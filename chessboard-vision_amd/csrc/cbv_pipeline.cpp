@@ -133,6 +133,7 @@ static BoardDev board_dev(const Board& q, size_t lds[2])
     T.mirror = (cbv_frame_result*)q.h_stage;
     T.over_src = c.use_hough ? (const u32*)q.d_hough_over.p : nullptr;
     T.over_dst = q.over_h;
+    T.ptabs = (const ProfileTabs*)q.d_ptabs.p;
     return T;
 }
 
@@ -145,7 +146,7 @@ int pipeline_tables(Pipe& P)
     cbv_ctx* ctx = P.ctx;
     const int nb = (int)P.boards.size();
     P.tab.resize(nb);
-    P.any_hough = P.any_adaptive = P.any_session = P.any_own_blur = false;
+    P.any_hough = P.any_adaptive = P.any_session = P.any_own_blur = P.profile_on = false;
     P.hough_lds[0] = P.hough_lds[1] = 0;
     P.max_px = P.max_S = 0;
     for (int k = 0; k < nb; k++) {
@@ -164,6 +165,7 @@ int pipeline_tables(Pipe& P)
         P.any_adaptive = P.any_adaptive || q.adaptive();
         P.any_session = P.any_session || q.session;
         P.any_own_blur = P.any_own_blur || q.own_blur();
+        P.profile_on = P.profile_on || (P.profile_only && q.profile.enabled); // no board has one: the plain warp, no table is read
         P.max_px = std::max(P.max_px, q.max_px);
         P.max_S = std::max(P.max_S, q.cfg.board_size);
     }
@@ -171,6 +173,30 @@ int pipeline_tables(Pipe& P)
     RC(dev_ensure(ctx, &P.d_boards, sizeof(BoardDev) * nb));
     CBV_HIP(ctx, hipMemcpyAsync(P.d_boards.p, P.tab.data(), sizeof(BoardDev) * nb, hipMemcpyHostToDevice, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}
+
+// The BGR frame ring exists unless the pipeline is configured with CBV_SKIP_ENHANCE_PROFILE_RAW and its input format is raw:
+// then the raw ring holds every byte, nothing reads or writes BGR frames, and the ring (6.2 MB a 1080p slot) is given back.
+// (skip_enhance = 1 keeps its ring in raw mode, as it always did.)  Called when the mode or the input format changes; what
+// is in flight is joined before the ring goes.
+int pipeline_frame_ring(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    const bool want = !(P.configured_raw_profile() && P.in_fmt != CBV_FMT_BGR);
+    if (want && !P.frames) {
+        const size_t bytes = P.g.frame_stride * P.max_frames;
+        if (hipMalloc((void**)&P.frames, bytes + 256) != hipSuccess) {
+            P.frames = nullptr;
+            return cbv_fail(ctx, CBV_ERR_HIP, "hipMalloc of %zu bytes for the frame ring failed", bytes);
+        }
+    } else if (!want && P.frames) {
+        RC(join_scan(P));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+        (void)hipFree(P.frames);
+        P.frames = nullptr;
+    }
     return CBV_OK;
 }
 
@@ -306,7 +332,7 @@ static void board_free(cbv_pipeline* p)
     if (b.warped) (void)hipFree(b.warped);
     DevBuf* bufs[] = {&b.d_descs, &b.d_masks, &b.d_gray, &b.d_stats, &b.d_ref, &b.d_state, &b.d_results, &b.d_flags, &b.d_dec, &b.d_mean,
                       &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over, &b.d_session, &b.d_hist, &b.d_radar,
-                      &b.d_cgray};
+                      &b.d_cgray, &b.d_ptabs};
     for (auto d : bufs) dev_free(d);
     delete p;
 }
@@ -370,11 +396,11 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     if (P->enhanced) (void)hipFree(P->enhanced);
     dev_free(&P->d_synth);
     dev_free(&P->d_boards);
-    dev_free(&P->d_ptabs);
     for (cbv_pipeline* q : P->boards) board_free(q); // board 0 (p) included
     delete P;
 }
 
+// (null while a CBV_SKIP_ENHANCE_PROFILE_RAW pipeline's frames are raw: it has no BGR ring)
 extern "C" void* cbv_pipeline_frames_dev(cbv_pipeline* p) { return p && !attached(p) ? p->pipe->frames : nullptr; }
 
 extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* cfg)
@@ -392,7 +418,8 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     if (cfg->skip_enhance && cfg->enhance_region)
         return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_configure: skip_enhance with enhance_region (there is no enhancement to limit)");
     if (!cfg->skip_enhance) RC(check_params(ctx, &cfg->enhance));
-    const bool profile_only = cfg->skip_enhance == CBV_SKIP_ENHANCE_PROFILE;
+    const bool profile_raw = cfg->skip_enhance == CBV_SKIP_ENHANCE_PROFILE_RAW;
+    const bool profile_only = cfg->skip_enhance == CBV_SKIP_ENHANCE_PROFILE || profile_raw;
     ProfileTabs ptabs;
     if (profile_only) RC(profile_tabs_checked(ctx, &cfg->enhance.profile, &ptabs, "cbv_pipeline_configure"));
     // every argument check that needs no state is done; from here on a failure leaves the pipeline UNconfigured
@@ -402,11 +429,7 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     P.keep_enhanced = cfg->keep_enhanced != 0;
     P.skip_enhance = cfg->skip_enhance != 0;
     P.profile_only = profile_only;
-    P.profile_on = profile_only && cfg->enhance.profile.enabled; // a disabled profile: the plain warp, no table
-    if (P.profile_on) {
-        RC(dev_ensure(ctx, &P.d_ptabs, sizeof(ProfileTabs)));
-        CBV_HIP(ctx, hipMemcpy(P.d_ptabs.p, &ptabs, sizeof(ptabs), hipMemcpyHostToDevice));
-    } else dev_free(&P.d_ptabs);
+    P.profile_raw = profile_raw;
     int chunk = cfg->chunk;
     if (chunk <= 0) chunk = 32;
     if (chunk > P.max_frames) chunk = P.max_frames;
@@ -433,9 +456,11 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     }
     if (P.keep_enhanced) CBV_HIP(ctx, hipMalloc((void**)&P.enhanced, P.g.frame_stride * P.max_frames + 256));
     RC(board_setup(P, p->b, *cfg));
+    RC(board_set_profile(P, p->b, &cfg->enhance.profile, "cbv_pipeline_configure"));
     // region-limited enhancement: the source footprint of the S x S warp (warp_footprint)
     RC(pipeline_update_region(P));
     RC(pipeline_tables(P));
+    RC(pipeline_frame_ring(P));
     P.configured = true;
     return CBV_OK;
 }
@@ -475,6 +500,7 @@ extern "C" int cbv_pipeline_add_board(cbv_pipeline* p, const cbv_board_config* b
         RC(dev_ensure(ctx, &P.lane_work[l], sizeof(u32) * (1 + (size_t)CBV_MAX_SQUARES * P.chunk * (P.boards.size() + 1))));
     cbv_pipeline* b = new cbv_pipeline{&P, Board()};
     int rc = board_setup(P, b->b, cfg);
+    if (rc == CBV_OK) rc = board_set_profile(P, b->b, &cfg.enhance.profile, "cbv_pipeline_add_board"); // the pipeline's configured profile
     if (rc == CBV_OK) {
         P.boards.push_back(b);
         rc = pipeline_tables(P);
@@ -549,6 +575,42 @@ extern "C" int cbv_pipeline_set_model_update(cbv_pipeline* p, int mode, double a
     B.model_mode = mode;
     B.model_alpha = alpha;
     return P.configured ? pipeline_tables(P) : CBV_OK;
+}
+
+// The board's profile and its device table (profile modes only; otherwise the board has neither).  Nothing may be in flight
+// that reads the table: the callers joined the runs.
+int board_set_profile(Pipe& P, Board& b, const cbv_color_profile* profile, const char* who)
+{
+    cbv_ctx* ctx = P.ctx;
+    if (!P.profile_only) {
+        memset(&b.profile, 0, sizeof(b.profile));
+        dev_free(&b.d_ptabs);
+        return CBV_OK;
+    }
+    ProfileTabs pt;
+    RC(profile_tabs_checked(ctx, profile, &pt, who));
+    RC(dev_ensure(ctx, &b.d_ptabs, sizeof(ProfileTabs)));
+    CBV_HIP(ctx, hipMemcpyAsync(b.d_ptabs.p, &pt, sizeof(pt), hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt is on this stack)
+    b.profile = *profile;
+    b.profile.enabled = profile->enabled ? 1 : 0;
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_set_profile(cbv_pipeline* p, const cbv_color_profile* profile)
+{
+    const char* who = "cbv_pipeline_set_profile";
+    if (!p || !profile) return cbv_fail(p ? p->pipe->ctx : nullptr, CBV_ERR_ARG, "%s: null argument", who);
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (!P.configured || !P.profile_only)
+        return cbv_fail(ctx, CBV_ERR_STATE, "%s: the pipeline is not configured with CBV_SKIP_ENHANCE_PROFILE or CBV_SKIP_ENHANCE_PROFILE_RAW", who);
+    ProfileTabs probe;
+    RC(profile_tabs_checked(ctx, profile, &probe, who)); // a rejected profile changes nothing
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // the runs in flight read the table that is replaced here
+    RC(board_set_profile(P, p->b, profile, who));
+    return pipeline_tables(P); // (whether any board has an enabled profile decides the warp's kernel)
 }
 
 extern "C" int cbv_pipeline_set_change_blur(cbv_pipeline* p, int blur_kernel)
@@ -676,7 +738,7 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
     size_t bytes;
     if (attached(p) && which != 2) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: a board holds only its warped frames (which = 2)");
     if (which == 0) {
-        src = P.frames + P.g.frame_stride * slot;
+        src = P.raw_mode() ? nullptr : P.frames + P.g.frame_stride * slot;
         bytes = (size_t)P.w * P.h * 3;
         if (P.raw_mode()) { // the frames are raw: the slot is converted for the caller
             if (!P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: no raw frame was ever uploaded or submitted");

@@ -44,6 +44,10 @@ struct Board {
     int ses_frames = 0;
     DevBuf d_radar;
     bool adaptive() const { return calibrated && model_mode != CBV_MODEL_FROZEN; } // k_model_scan runs for this board
+    // the board's colour profile in the profile modes (cbv_pipeline_set_profile; the pipeline's configured one until then) and
+    // its device table, which exists in those modes whether the profile is enabled or not
+    cbv_color_profile profile = {};
+    DevBuf d_ptabs;
 };
 
 struct Pipe;
@@ -62,12 +66,13 @@ struct Pipe {
     bool configured = false;
     bool keep_enhanced = false;
     bool skip_enhance = false; // cfg.skip_enhance: the warp samples the frames as they are, no enhancement scratch exists
-    // cfg.skip_enhance == CBV_SKIP_ENHANCE_PROFILE: the warp samples the BGR ring and, with an enabled profile (profile_on),
-    // applies the colour profile to its taps (k_warp_profile) with the pipeline's own table, d_ptabs
-    bool profile_only = false, profile_on = false;
-    DevBuf d_ptabs;
+    // cfg.skip_enhance == CBV_SKIP_ENHANCE_PROFILE or CBV_SKIP_ENHANCE_PROFILE_RAW: the warp samples the frames and, when a
+    // board has an enabled profile (profile_on), applies each board's colour profile to its taps (k_warp_profile,
+    // k_warp_raw_profile) from the boards' own tables, Board::d_ptabs.  profile_raw: the latter mode, in which a YUV or Bayer
+    // input format makes the raw ring the frames (raw_mode below)
+    bool profile_only = false, profile_on = false, profile_raw = false;
     int chunk = 8;
-    u8* frames = nullptr;
+    u8* frames = nullptr; // the BGR frame ring; null while a CBV_SKIP_ENHANCE_PROFILE_RAW pipeline's frames are raw (pipeline_frame_ring)
     // Lanes: chunk c runs on lane c % n_lanes, each lane with its own HIP stream and scratch, so a
     // VALU-bound bilateral launch of one chunk overlaps the memory-latency-bound kernels of another.
     enum { MAX_LANES = 4 };
@@ -89,8 +94,8 @@ struct Pipe {
     // k_ingest converts into `frames` behind the copy
     u8* host_ring = nullptr;
     int in_fmt = CBV_FMT_BGR;
-    // Without enhancement (skip_enhance) a YUV or Bayer input format makes the raw ring THE frames: k_warp_yuv / k_warp_bayer samples it, nothing is
-    // converted and `frames` is neither written nor read (raw_mode below).
+    // Without enhancement (skip_enhance 1 or CBV_SKIP_ENHANCE_PROFILE_RAW) a YUV or Bayer input format makes the raw ring THE frames: k_warp_yuv /
+    // k_warp_bayer / k_warp_raw_profile samples it, nothing is converted and `frames` is neither written nor read (raw_mode below).
     u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated on first use; null with CBV_FMT_BGR
     hipStream_t copy_stream = nullptr;
     struct CopyRec {
@@ -135,7 +140,8 @@ struct Pipe {
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
     Board& b0() const { return boards[0]->b; }
-    bool raw_mode() const { return skip_enhance && !profile_only && in_fmt != CBV_FMT_BGR; }
+    bool configured_raw_profile() const { return skip_enhance && profile_raw; }
+    bool raw_mode() const { return skip_enhance && (!profile_only || profile_raw) && in_fmt != CBV_FMT_BGR; }
 };
 // cbv_pipeline.cpp: board handles, the ordering of the runs in flight, the boards' kernel arguments, read-backs
 bool attached(const cbv_pipeline* p);
@@ -146,6 +152,8 @@ int join_scan(Pipe& P);
 int join_slots(Pipe& P, int s0, int cnt);
 ChangeBlur change_blur_coef(int k);
 int pipeline_tables(Pipe& P);
+int pipeline_frame_ring(Pipe& P);
+int board_set_profile(Pipe& P, Board& b, const cbv_color_profile* profile, const char* who);
 int pipeline_update_region(Pipe& P);
 int pipeline_readback(Pipe& P, void* out, const void* dev, size_t bytes);
 // cbv_pipeline_ingest.cpp

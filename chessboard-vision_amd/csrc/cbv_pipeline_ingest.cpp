@@ -98,7 +98,7 @@ extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
     if (P.raw_ring) (void)hipFree(P.raw_ring);
     P.host_ring = P.raw_ring = nullptr;
     P.in_fmt = fmt;
-    return CBV_OK;
+    return pipeline_frame_ring(P); // (a CBV_SKIP_ENHANCE_PROFILE_RAW pipeline has a BGR ring only while its frames are BGR)
 }
 
 extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)

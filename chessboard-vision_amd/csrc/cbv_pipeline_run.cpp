@@ -11,9 +11,12 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
 {
     cbv_ctx* ctx = P.ctx;
     // what the warp samples (raw mode: the planes of the chunk's first slot)
-    const WarpSrc src = !res             ? warp_src_raw(slot_planes(P, s0), tight_raw_geom(P.in_fmt, P.w, P.h), P.g)
-                        : P.profile_on ? warp_src_profile(res, P.g, (const ProfileTabs*)P.d_ptabs.p)
-                                       : warp_src_bgr(res, P.g, norm);
+    // (the profile's table: board 0's for the single-board launch; the multi-board kernels read the boards' own)
+    const ProfileTabs* pt = P.profile_on ? (const ProfileTabs*)P.b0().d_ptabs.p : nullptr;
+    const WarpSrc src = !res ? (pt ? warp_src_raw_profile(slot_planes(P, s0), tight_raw_geom(P.in_fmt, P.w, P.h), P.g, pt)
+                                   : warp_src_raw(slot_planes(P, s0), tight_raw_geom(P.in_fmt, P.w, P.h), P.g))
+                        : pt ? warp_src_profile(res, P.g, pt)
+                             : warp_src_bgr(res, P.g, norm);
     if (P.boards.size() > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         const int nb = (int)P.boards.size();
@@ -231,11 +234,11 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
         const int lane = (lane_base + ci) % P.n_lanes;
         ctx->stream = lane == 0 ? main_stream : P.lane_stream[lane];
         const int b = std::min(P.chunk, slot0 + count - s0);
-        const u8* src = P.frames + P.g.frame_stride * s0;
+        const u8* src = P.raw_mode() ? nullptr : P.frames + P.g.frame_stride * s0; // (raw mode: the warp samples the raw ring)
         u32* work = P.any_hough ? (u32*)P.lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
         u32* retry0 = P.any_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
         if (P.skip_enhance) { // the session's chain: the warp samples the frames as they are (in raw mode the raw ring: no BGR source)
-            rc_all = pipeline_chunk_boards(P, P.raw_mode() ? nullptr : src, NormSrc(), s0, b, work, retry0, (u32*)rec->retry.p, s0 - slot0);
+            rc_all = pipeline_chunk_boards(P, src, NormSrc(), s0, b, work, retry0, (u32*)rec->retry.p, s0 - slot0);
             continue;
         }
         SmallLayout SL;

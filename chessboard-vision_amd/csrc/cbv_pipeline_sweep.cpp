@@ -334,7 +334,8 @@ extern "C" int cbv_pipeline_piece_detail(cbv_pipeline* p, int slot, const cbv_ho
 
 // ---------------------------------------------------------------------------
 // The colour profile sweep (include/cbv.h, cbv_pipeline_color_sweep).  Everything it allocates belongs to the call and is
-// freed when it returns; of the pipeline it reads the BGR frame ring, of the board its geometry, square table, masks and
+// freed when it returns; of the pipeline it reads the BGR frame ring (in the raw mode of CBV_SKIP_ENHANCE_PROFILE_RAW: the
+// raw ring, through k_warp_raw_profile), of the board its geometry, square table, masks and
 // Hough settings.  The scratch boards, planes, statistics and circle choices of a chunk are laid out [profile][frame]
 // with the chunk's frame count between profiles, so that the statistics kernel and k_piece_sweep_hough (one setting) see
 // profiles x frames as one batch of frames and k_piece_sweep_eval sees the profiles as its settings.
@@ -354,7 +355,10 @@ extern "C" int cbv_pipeline_color_sweep(cbv_pipeline* p, int slot0, int count, c
     if (np > CBV_COLOR_SWEEP_MAX_PROFILES) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %d profiles (at most %d)", who, np, CBV_COLOR_SWEEP_MAX_PROFILES);
     if (chunk < 0 || chunk > CBV_SWEEP_MAX_CHUNK) return cbv_fail(ctx, CBV_ERR_ARG, "%s: chunk_frames %d is outside 0..%d", who, chunk, CBV_SWEEP_MAX_CHUNK);
     if (slot0 < 0 || slot0 > P.max_frames - count) return cbv_fail(ctx, CBV_ERR_ARG, "%s: slots outside the ring of %d", who, P.max_frames);
-    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: the pipeline's frames are raw (there is no BGR ring to read)", who);
+    if (P.raw_mode() && !P.profile_raw)
+        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: the pipeline's frames are raw and it has no profile kernel (there is no BGR ring to read; "
+                        "configure CBV_SKIP_ENHANCE_PROFILE_RAW, with a disabled profile for the plain raw warp)", who);
+    if (P.raw_mode() && !P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "%s: no raw frame was ever uploaded or submitted", who);
     const int n = B.cfg.n_rois, S_ = B.cfg.board_size;
     HoughCfg hc;
     memset(&hc, 0, sizeof(hc));
@@ -412,8 +416,10 @@ extern "C" int cbv_pipeline_color_sweep(cbv_pipeline* p, int slot0, int count, c
         for (int c0 = 0; c0 < count; c0 += chunk) {
             const int cf = std::min(chunk, count - c0), nb = pc * cf; // scratch frame of (profile i, frame f) = i * cf + f
             CBV_HIP(ctx, hipEventRecord(S.ev[0], ctx->stream));
-            RC(launch_warp(ctx, warp_src_profile(P.frames + P.g.frame_stride * (slot0 + c0), P.g, (const ProfileTabs*)S.tabs.p, pc, B.warped_stride * cf),
-                           B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p, S_ * 3, B.warped_stride, cf));
+            const ProfileTabs* pt = (const ProfileTabs*)S.tabs.p;
+            const WarpSrc src = P.raw_mode() ? warp_src_raw_profile(slot_planes(P, slot0 + c0), tight_raw_geom(P.in_fmt, P.w, P.h), P.g, pt, pc, B.warped_stride * cf)
+                                             : warp_src_profile(P.frames + P.g.frame_stride * (slot0 + c0), P.g, pt, pc, B.warped_stride * cf);
+            RC(launch_warp(ctx, src, B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p, S_ * 3, B.warped_stride, cf));
             CBV_HIP(ctx, hipEventRecord(S.ev[1], ctx->stream));
             RC(launch_squares_pre5_stats(ctx, (const u8*)S.boards.p, B.warped_stride, descs, n, (u8*)S.gray.p, B.plane_total, nullptr, nullptr,
                                          (const u8*)B.d_masks.p, (float)B.cfg.z_threshold, (cbv_sq_stats*)S.stats.p, nb, nullptr, 0, nullptr, nullptr,

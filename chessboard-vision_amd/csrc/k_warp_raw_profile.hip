@@ -1,0 +1,105 @@
+// The warp of camera-native frames through the colour profile: warp(apply_color_profile(to_bgr(raw))), bit for bit, with
+// neither the BGR frame nor the profiled frame ever written (pipelines configured with CBV_SKIP_ENHANCE_PROFILE_RAW, their
+// colour sweep, cbv_warp_color_profile_raw).  The gather is warp_gather (warp_gather.h) with the source WarpRawProfile<FMT>:
+// coordinates, wide loads, the `fast` predicate per family, rot180 and the zeroed words are the gather's own; what this
+// source adds is d_profile_px on each converted tap inside the frame, from the 7.5 KB of tables a workgroup stages once for
+// its WP_ROWS rows.  A tap outside the frame is BGR 0, not the profile of black; a table with enabled = 0 leaves the taps
+// alone.  The kernels live in a file of their own: k_warp.hip's 52 stay what they are.
+#include "warp_gather.h"
+
+// Frames per thread of the many-frames form (batch >= 8), per family.  The profile's registers come on top of the
+// conversion's: the four-frame form of every family needs more than 64 VGPRs (NV12 79, planar 4:2:0 91, packed 4:2:2 71,
+// Bayer 72), and so does the two-frame form of the 4:2:0 families (68, 77); at or under 64 stay two frames of packed 4:2:2
+// and Bayer (60, 62) and one frame of the 4:2:0 families (58, 62).  Each family ships the form that was fastest INSIDE
+// p.run on an MI355X (1080p, 512 frames, two lanes), and a form above 64 only where it beat the best one at or under 64 by
+// more than the runs' range: per frame, 1 / 2 / 4 frames a thread, NV12 8.00 / 6.92 / 6.77 us, planar 8.56 / 7.50 / 7.57,
+// packed 4:2:2 7.50 / 6.30 / 6.05, Bayer 7.92 / 6.83 / 6.20 (ranges 0.02 - 0.06).  So four frames everywhere but planar
+// 4:2:0, which takes two.  DESIGN.md section 6n has the table; tests/test_warp_raw_profile_resources.py pins the counts.
+// (RAW_PROFILE_FPT = 1, 2 or 4 in the build's environment gives every family that form: tools/raw_profile_timing.py's
+// comparison.)
+static constexpr int raw_profile_fpt(int fmt)
+{
+#ifdef RAW_PROFILE_FPT
+    return RAW_PROFILE_FPT;
+#else
+    return (fmt & 15) == CBV_FMT_NV12 && (fmt & 0x20) ? 2 : 4; // planar 4:2:0 (YUV420P): two
+#endif
+}
+
+// blockIdx.z = profile * nz + group of frames; profile p writes its frames dst_profile_stride bytes behind profile p - 1's
+// (Bayer: p1 = p2 = null)
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_raw_profile(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r, int sw,
+                                                           int sh, WarpM M, int dw, int dh, int bw0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                                           size_t dst_frame_stride, size_t dst_profile_stride, const StaticTabs* __restrict__ st,
+                                                           const ProfileTabs* __restrict__ ptabs, int nz, u32* __restrict__ zero_word,
+                                                           u32* __restrict__ zero_word2, int batch)
+{
+    const int pi = blockIdx.z / nz;
+    warp_gather<WarpRawProfile<FMT>, FPT>(WarpRawProfile<FMT>{{p0, p1, p2, r, sw, sh}, st, ptabs + pi},
+                                          WarpDst{M.m, dw, dh, bw0, rot180, dst + (size_t)pi * dst_profile_stride, dst_stride, dst_frame_stride},
+                                          zero_word, zero_word2, batch, blockIdx.z - pi * nz);
+}
+
+// every board of a pipeline in one launch: blockIdx.z = board * nz + group of frames; a workgroup stages its board's table
+template <int FMT, int FPT>
+__global__ __launch_bounds__(256) void k_warp_raw_profile_mb(const u8* __restrict__ p0, const u8* __restrict__ p1, const u8* __restrict__ p2, RawGeom r,
+                                                              int sw, int sh, const BoardDev* __restrict__ tab, int nz, int s0,
+                                                              const StaticTabs* __restrict__ st, u32* __restrict__ zero_word,
+                                                              u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * WP_ROWS >= T.S)) return;
+    warp_gather<WarpRawProfile<FMT>, FPT>(WarpRawProfile<FMT>{{p0, p1, p2, r, sw, sh}, st, T.ptabs}, warp_board_dst(T, s0), zero_word, zero_word2, batch,
+                                          blockIdx.z - b * nz);
+}
+
+// the frames per thread of the many-frames form of a format as the caller names it (YV12 is launched as YUV420P)
+static int raw_profile_many(int fmt)
+{
+    return raw_profile_fpt(fmt == CBV_FMT_YV12 ? CBV_FMT_YUV420P : fmt);
+}
+
+int launch_warp_raw_profile(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
+                            int batch, u32* zero_word, u32* zero_word2)
+{
+    if (!s.raw() || !s.ptabs) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_raw_profile: not a raw source with a profile");
+    WarpM M;
+    for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
+    int bw0, bh0;
+    warp_block_shape(dw, dh, &bw0, &bh0);
+    const int many = raw_profile_many(s.r.fmt);
+    if (s.np <= 0 || batch <= 0 || (long long)s.np * warp_groups(batch, many) > 65535)
+        return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_raw_profile: %d profiles x %d frames do not fit a launch", s.np, batch);
+    const hipStream_t st = ctx->stream;
+    return warp_launch(
+        ctx, &s, dw, dh, s.np, batch,
+        [&](auto fmt, auto fpt, dim3 grid, int nz) {
+            constexpr int FMT = decltype(fmt)::value;
+            if constexpr (FMT != CBV_FMT_BGR) {
+                constexpr int FPT = decltype(fpt)::value == 1 ? 1 : raw_profile_fpt(FMT);
+                hipLaunchKernelGGL((k_warp_raw_profile<FMT, FPT>), grid, dim3(256), 0, st, s.planes.p[0], s.planes.p[1], s.planes.p[2], s.r, s.g.w, s.g.h, M,
+                                   dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, s.dst_profile_stride, ctx->tabs, s.ptabs, nz, zero_word,
+                                   zero_word2, batch);
+            }
+        },
+        many);
+}
+
+int launch_warp_raw_profile_mb(cbv_ctx* ctx, WarpSrc s, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2)
+{
+    if (!s.raw() || !s.ptabs) return cbv_fail(ctx, CBV_ERR_ARG, "launch_warp_raw_profile_mb: not a raw source with a profile");
+    const hipStream_t st = ctx->stream;
+    return warp_launch(
+        ctx, &s, maxS, maxS, nb, batch,
+        [&](auto fmt, auto fpt, dim3 grid, int nz) {
+            constexpr int FMT = decltype(fmt)::value;
+            if constexpr (FMT != CBV_FMT_BGR) {
+                constexpr int FPT = decltype(fpt)::value == 1 ? 1 : raw_profile_fpt(FMT);
+                hipLaunchKernelGGL((k_warp_raw_profile_mb<FMT, FPT>), grid, dim3(256), 0, st, s.planes.p[0], s.planes.p[1], s.planes.p[2], s.r, s.g.w,
+                                   s.g.h, tab, nz, s0, ctx->tabs, zero_word, zero_word2, batch);
+            }
+        },
+        raw_profile_many(s.r.fmt));
+}

@@ -1,0 +1,545 @@
+// The warp's one gather (warp_gather), its sources and what the launchers share, for the translation units that hold
+// warp kernels: k_warp.hip and k_warp_raw_profile.hip.  Private.
+#pragma once
+#include "cbv_bayer.h"
+#include "cbv_profile_px.h"
+#include "cbv_yuv.h"
+
+struct WarpM {
+    double m[9];
+};
+
+// What a destination pixel samples, whatever the format of the frames: the top-left tap, the four weights, which taps are
+// inside the source, and where the pixel goes.
+struct WarpTaps {
+    int sx, sy;
+    int w00, w01, w10, w11;
+    bool any_in, x0in, x1in, y0in, y1in, interior;
+    size_t out_off; // byte offset of the pixel inside a destination frame
+};
+
+// destination pixel (dx, dy) of a dw x dh destination; sw x sh = the source frame
+__device__ __forceinline__ WarpTaps warp_taps(int dx, int dy, int sw, int sh, const double* __restrict__ M, int dw, int dh, int bw0, int rot180,
+                                              int dst_stride)
+{
+    WarpTaps t;
+    const int bx = (dx / bw0) * bw0, x1 = dx - bx; // block origin and offset inside it
+    // (rows are evaluated independently of the block row)
+    const double X0 = M[0] * bx + M[1] * dy + M[2];
+    const double Y0 = M[3] * bx + M[4] * dy + M[5];
+    const double W0 = M[6] * bx + M[7] * dy + M[8];
+    double W = W0 + M[6] * x1;
+    W = W != 0. ? 32. / W : 0.;
+    double fX = (X0 + M[0] * x1) * W;
+    double fY = (Y0 + M[3] * x1) * W;
+    fX = fmax(-2147483648.0, fmin(2147483647.0, fX));
+    fY = fmax(-2147483648.0, fmin(2147483647.0, fY));
+    const int X = d_round_d(fX), Y = d_round_d(fY);
+    const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
+    const int fx = X & 31, fy = Y & 31;
+    t.sx = sx;
+    t.sy = sy;
+    t.w00 = (32 - fx) * (32 - fy) * 32;
+    t.w01 = fx * (32 - fy) * 32;
+    t.w10 = (32 - fx) * fy * 32;
+    t.w11 = fx * fy * 32;
+    t.any_in = !(sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0);
+    t.x0in = sx >= 0 && sx < sw;
+    t.x1in = sx + 1 >= 0 && sx + 1 < sw;
+    t.y0in = sy >= 0 && sy < sh;
+    t.y1in = sy + 1 >= 0 && sy + 1 < sh;
+    t.interior = t.x0in && t.x1in && t.y0in && t.y1in;
+    const int ox = rot180 ? dw - 1 - dx : dx, oy = rot180 ? dh - 1 - dy : dy;
+    t.out_off = (size_t)oy * dst_stride + (size_t)ox * 3;
+    return t;
+}
+
+// the pipeline's HoughCircles worklist counter, filled by the NEXT kernel in the stream (k_squares_pre5_stats):
+// zeroed here instead of by a 4-byte memset, which is one more ~4.5 us launch in a single-frame run
+__device__ __forceinline__ void warp_zero_words(u32* __restrict__ zero_word, u32* __restrict__ zero_word2)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
+        if (zero_word) *zero_word = 0u;
+        if (zero_word2) *zero_word2 = 0u; // the run's second-pass list, when this launch is the run's only chunk
+    }
+}
+
+// remap()'s 15-bit fixed-point bilinear of one channel
+__device__ __forceinline__ int warp_blend(int t0, int t1, int t2, int t3, const WarpTaps& t)
+{
+    return d_sat8((t0 * t.w00 + t1 * t.w01 + t2 * t.w10 + t3 * t.w11 + (1 << 14)) >> 15);
+}
+
+// where a launch writes one board: the matrix, the dw x dh destination, frame 0 of the batch
+struct WarpDst {
+    const double* M;
+    int dw, dh, bw0, rot180;
+    u8* dst;
+    int stride;
+    size_t frame_stride;
+};
+
+// ---------------------------------------------------------------------------
+// The sources: what the frames are and how the BGR value of a tap is obtained.  A source is plain data and constants; what
+// it does differently stands in warp_gather under its KIND.  (The text stays in the one function on purpose: the compiler
+// simplifies every function on its own before it inlines, and the gather split into per-source functions compiles to
+// other instructions than this.)
+// ---------------------------------------------------------------------------
+enum { WARP_BGR, WARP_PROFILE, WARP_YUV, WARP_BAYER };
+#define WP_ROWS 16 // destination rows per workgroup of WarpProfile: one row of WarpPerspectiveInvoker's 64 x 16 blocks
+
+// BGR frames through cv2.normalize's byte map, which is staged in LDS per frame.  CALC: the map is worked out here from the
+// frames' [min, max] words (NormSrc::minmax) instead of read from a table ([frame][256]); neither: no mapping.  The taps
+// stay channel by channel, as bytes index the map.
+template <bool CALC_>
+struct WarpBgr {
+    static constexpr int KIND = WARP_BGR, ROWS = 4, FMT = CBV_FMT_BGR;
+    static constexpr bool CALC = CALC_, TABS = false;
+    template <int FPT>
+    struct Lds {
+        u8 lut[FPT][256];
+    };
+    const u8* src;
+    Geom g;
+    const u8* norm_lut;
+    const u32* minmax;
+    size_t mm_stride;
+    __device__ __forceinline__ int w() const { return g.w; }
+    __device__ __forceinline__ int h() const { return g.h; }
+};
+
+// BGR frames through the colour profile (cbv_warp_color_profile, pipelines configured with CBV_SKIP_ENHANCE_PROFILE,
+// cbv_pipeline_color_sweep): the loads of WarpBgr, d_profile_px on each tap.  A workgroup stages the 7.5 KB d_profile_px
+// reads (ProfileLds) and then covers WP_ROWS destination rows of its 64 columns, FPT frames each: 1920 staged words against
+// 4096 conversions per frame.  The tables are an argument, one ProfileTabs per profile of the launch; a table with
+// enabled = 0 leaves the taps as they are.
+struct WarpProfile {
+    static constexpr int KIND = WARP_PROFILE, ROWS = WP_ROWS, FMT = CBV_FMT_BGR;
+    static constexpr bool TABS = true;
+    template <int FPT>
+    using Lds = ProfileLds;
+    const u8* src;
+    Geom g;
+    const StaticTabs* st;
+    const ProfileTabs* pt; // the profile's table
+    __device__ __forceinline__ int w() const { return g.w; }
+    __device__ __forceinline__ int h() const { return g.h; }
+};
+
+// Camera-native frames (pipelines without enhancement whose input is raw): the BGR frame k_ingest would write is never made.
+// YUV: the taps through d_yuv_bgr; the conversion is pointwise (a pixel takes the chroma of its 2x2 block or pair, nothing
+// is interpolated).  Bayer: the taps demosaiced (d_bayer_bgr, cbv_bayer.h); a tap on the frame's outermost rows or
+// columns is the result of the clamped site, as in k_ingest.  Nothing is staged.
+template <int FMT_>
+struct WarpRaw {
+    static constexpr int KIND = raw_fmt_bayer(FMT_) ? WARP_BAYER : WARP_YUV, ROWS = 4, FMT = FMT_;
+    static constexpr bool TABS = false;
+    template <int FPT>
+    struct Lds {
+    };
+    const u8* p0;
+    const u8* p1;
+    const u8* p2;
+    RawGeom r;
+    int sw, sh;
+    __device__ __forceinline__ int w() const { return sw; }
+    __device__ __forceinline__ int h() const { return sh; }
+};
+
+// Camera-native frames through the colour profile (k_warp_raw_profile.hip: pipelines configured with
+// CBV_SKIP_ENHANCE_PROFILE_RAW, their colour sweep, cbv_warp_color_profile_raw): the loads and the conversion of WarpRaw,
+// then d_profile_px on each converted tap that lies inside the frame, staged and tiled as WarpProfile is.  Neither the BGR
+// frame nor the profiled frame is ever made.
+template <int FMT_>
+struct WarpRawProfile : WarpRaw<FMT_> {
+    static constexpr int ROWS = WP_ROWS;
+    static constexpr bool TABS = true;
+    template <int FPT>
+    using Lds = ProfileLds;
+    const StaticTabs* st;
+    const ProfileTabs* pt; // the profile's table
+};
+
+// pixel (x, y) of one raw YUV frame with byte loads (the taps of pixels on the frame's border)
+template <int FMT>
+__device__ __forceinline__ u32 d_raw_px(const u8* __restrict__ f0, const u8* __restrict__ f1, const u8* __restrict__ f2, const RawGeom& r, int x,
+                                        int y)
+{
+    typedef YuvLay<FMT> L;
+    if (L::PLANAR)
+        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x],
+                         d_chroma(f1[(size_t)(y >> 1) * r.stride1 + (x >> 1)], f2[(size_t)(y >> 1) * r.stride2 + (x >> 1)]));
+    if (L::F420) {
+        const u8* c = f1 + (size_t)(y >> 1) * r.stride1 + (x & ~1);
+        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x], d_chroma(c[L::CU], c[L::CV]));
+    }
+    const u8* s = f0 + (size_t)y * r.stride0 + (size_t)(x >> 1) * 4;
+    return d_yuv_bgr(s[L::Y0 + (x & 1) * 2], d_chroma(s[L::PU], s[L::PV]));
+}
+
+// the chroma of byte pair `p` of an NV12 (U V) / NV21 (V U) row
+template <int FMT>
+__device__ __forceinline__ Chroma d_chroma_pair(u32 p)
+{
+    return d_chroma((p >> (8 * YuvLay<FMT>::CU)) & 255, (p >> (8 * YuvLay<FMT>::CV)) & 255);
+}
+
+// pixel (x, y) of one mosaic, inside the frame, with byte loads: the site is clamped, its neighbourhood lies inside
+template <int FMT>
+__device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride, int w, int h, int x, int y)
+{
+    const int cx = min(max(x, 1), w - 2), cy = min(max(y, 1), h - 2);
+    const u8* m = f0 + (size_t)cy * stride + cx;
+    u32 row[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const u8* q = m + (ptrdiff_t)(i - 1) * stride;
+        row[i] = (u32)q[-1] | ((u32)q[0] << 8) | ((u32)q[1] << 16);
+    }
+    return d_bayer_bgr<FMT>(cx, cy, row[0], row[1], row[2]);
+}
+
+// The gather.  FPT frames per thread: the coordinates of a destination pixel depend on the matrix and the pixel, not on the
+// frame, and they are most of the kernel's instructions (about 100 of 190 per output pixel, in double precision): a thread
+// works them out once and samples FPT consecutive frames of the batch with them (bz = the group of FPT frames, blockIdx.z
+// of a single-board launch; the last group of a batch may hold fewer).  A workgroup covers Src::ROWS rows of 64 columns.
+// Per source: what is staged in LDS, which pixels fetch their taps with wide loads (`fast`) and what those loads are, the
+// taps of a fast pixel, and a tap by byte loads for the pixels with taps outside the frame.  The rest is shared.
+//
+// The wide loads.  BGR and profile, interior pixels: the two taps of a row are 6 contiguous bytes -> ONE unaligned 8-byte
+// load per row instead of six byte loads; the two bytes read past the second tap stay inside the buffer (callers keep >= 8
+// bytes of slack behind the last frame).  YUV, interior pixels, per row of taps.  NV12 / NV21: one 2-byte load holds both
+// luma samples and one 4-byte load at the even column holds the chroma of the first tap's pair and of the next pair, which
+// is the second tap's when sx is odd (when sx is even both taps share the first); the rows share the chroma row when sy is
+// even.  Planar chroma (YUV420P; YV12 arrives with p1 and p2 swapped): the same 2-byte luma load, and per chroma row one
+// 2-byte load of U and one of V at column sx >> 1, which hold the first tap's sample and the next, the second tap's when sx
+// is odd.  Packed 4:2:2: one 8-byte load at the first tap's pair, e.g. Y0 U Y1 V | Y2 U Y3 V, holds both taps and their
+// chroma for either parity.  The bytes read past the second tap's pair (sx even) stay inside the buffer: the ring keeps 256
+// bytes of slack behind the last frame.  Bayer, pixels whose four taps are all interior sites (1 <= sx, sx + 1 <= w - 2,
+// the same in y): the taps' 3 x 3 neighbourhoods lie in the 4 x 4 bytes at (sx - 1, sy - 1), which is four unaligned 4-byte
+// loads per frame, inside the frame's rows.
+template <class Src, int FPT>
+__device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
+{
+    constexpr int KIND = Src::KIND, FMT = Src::FMT;
+    constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV;
+    constexpr bool TABS = Src::TABS, RAW_TABS = TABS && !PROFILE; // the profile's tables are staged; ... for the taps of a raw source
+    typedef YuvLay<YUV ? FMT : CBV_FMT_NV12> L; // (only read where YUV)
+    constexpr bool NV12 = L::F420 && !L::PLANAR, PLANAR = L::PLANAR;
+    __shared__ typename Src::template Lds<FPT> lds;
+    warp_zero_words(zero_word, zero_word2);
+    bool use_lut = false, on = false, radical = false; // uniform
+    if constexpr (BGR) use_lut = Src::CALC || S.norm_lut != nullptr;
+    if constexpr (TABS) {
+        lds_copy(lds.sdiv, S.st->sdiv, sizeof(lds.sdiv));
+        lds_copy(lds.hdiv, S.st->hdiv, sizeof(lds.hdiv));
+        lds_copy(lds.pt.csa, S.pt->csa, sizeof(lds.pt.csa));
+        lds_copy(lds.pt.hmask, S.pt->hmask, sizeof(lds.pt.hmask));
+        lds_copy(lds.pt.hsel, S.pt->hsel, sizeof(lds.pt.hsel));
+        lds_copy(lds.pt.hfr, S.pt->hfr, sizeof(lds.pt.hfr));
+        lds_copy(lds.pt.s_f, S.pt->s_f, sizeof(lds.pt.s_f));
+        lds_copy(lds.pt.v_f, S.pt->v_f, sizeof(lds.pt.v_f));
+        on = S.pt->enabled != 0;
+        radical = S.pt->radical != 0;
+        __syncthreads();
+    }
+    const int f0 = bz * FPT;
+    const int nf = min(FPT, batch - f0);
+    if constexpr (BGR) {
+        if (Src::CALC) {
+#pragma unroll
+            for (int k = 0; k < FPT; k++)
+                if (k < nf) {
+                    const u32* mm = S.minmax + (size_t)(f0 + k) * S.mm_stride;
+                    lds.lut[k][threadIdx.x] = d_norm_lut_entry((int)mm[0], (int)mm[1], (int)threadIdx.x);
+                }
+        } else if (use_lut)
+#pragma unroll
+            for (int k = 0; k < FPT; k++)
+                if (k < nf) lds.lut[k][threadIdx.x] = S.norm_lut[(size_t)(f0 + k) * 256 + threadIdx.x];
+        __syncthreads();
+    }
+    // a tap as b | g << 8 | r << 16 (the low three bytes of v) through the profile
+    auto conv = [&](u32 v) -> u32 {
+        if constexpr (TABS) return on ? d_profile_px(lds, (int)(v & 255u), (int)((v >> 8) & 255u), (int)((v >> 16) & 255u), radical) : (v & 0xFFFFFFu);
+        else return v;
+    };
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
+    int dy = blockIdx.y * Src::ROWS + (threadIdx.x >> 6), row = 0;
+    if (dx >= D.dw || dy >= D.dh) return;
+    do {
+        const WarpTaps t = warp_taps(dx, dy, S.w(), S.h(), D.M, D.dw, D.dh, D.bw0, D.rot180, D.stride);
+        // ---- the offsets of the loads (only used where the taps are inside) and the wide loads of every frame, which are
+        // all issued before the first is used: the gather is bound by the number of memory instructions, not by bytes
+        bool fast = t.interior;
+        size_t tap = 0, c_off = 0, c2_off = 0; // tap: of tap 00 (YUV: its luma, or its pair; Bayer: of the 4 x 4 bytes)
+        bool odd = false, two_crows = false;   // YUV; two_crows: the rows of taps lie in different chroma rows
+        if constexpr (BGR || PROFILE) tap = (size_t)t.sy * S.g.stride + (size_t)t.sx * 3;
+        else if constexpr (YUV) {
+            odd = t.sx & 1;
+            two_crows = L::F420 && (t.sy & 1);
+            tap = L::F420 ? (size_t)t.sy * S.r.stride0 + (size_t)t.sx : (size_t)t.sy * S.r.stride0 + (size_t)(t.sx >> 1) * 4;
+            c_off = (size_t)(t.sy >> 1) * S.r.stride1 + (size_t)(PLANAR ? t.sx >> 1 : t.sx & ~1);
+            c2_off = (size_t)(t.sy >> 1) * S.r.stride2 + (size_t)(t.sx >> 1);
+        } else {
+            fast = t.sx >= 1 && t.sx + 2 < S.sw && t.sy >= 1 && t.sy + 2 < S.sh;
+            tap = (size_t)(t.sy - 1) * S.r.stride0 + (size_t)(t.sx - 1);
+        }
+        u64 ta[FPT], tb[FPT]; // the rows of taps.  BGR, profile: 8 bytes; YUV 4:2:0: 2 luma bytes; 4:2:2: the 8 bytes of two pairs
+        u32 ca[FPT], cb[FPT]; // NV12: U V U V; planar: U U
+        u32 va[FPT], vb[FPT]; // planar: V V
+        u32 rows[FPT][4];     // Bayer
+        if (fast)
+#pragma unroll
+            for (int k = 0; k < FPT; k++)
+                if (k < nf) {
+                    if constexpr (BGR || PROFILE) {
+                        const u8* p00 = S.src + (size_t)(f0 + k) * S.g.frame_stride + tap;
+                        __builtin_memcpy(&ta[k], p00, 8);
+                        __builtin_memcpy(&tb[k], p00 + S.g.stride, 8);
+                    } else if constexpr (YUV) {
+                        const u8* l = S.p0 + (size_t)(f0 + k) * S.r.frame_stride + tap;
+                        if (L::F420) {
+                            u16 a, b;
+                            __builtin_memcpy(&a, l, 2);
+                            __builtin_memcpy(&b, l + S.r.stride0, 2);
+                            ta[k] = a;
+                            tb[k] = b;
+                            const u8* c = S.p1 + (size_t)(f0 + k) * S.r.frame_stride + c_off;
+                            if (NV12) {
+                                __builtin_memcpy(&ca[k], c, 4);
+                                cb[k] = ca[k];
+                                if (two_crows) __builtin_memcpy(&cb[k], c + S.r.stride1, 4);
+                            } else {
+                                const u8* c2 = S.p2 + (size_t)(f0 + k) * S.r.frame_stride + c2_off;
+                                u16 u, v;
+                                __builtin_memcpy(&u, c, 2);
+                                __builtin_memcpy(&v, c2, 2);
+                                ca[k] = cb[k] = u;
+                                va[k] = vb[k] = v;
+                                if (two_crows) {
+                                    __builtin_memcpy(&u, c + S.r.stride1, 2);
+                                    __builtin_memcpy(&v, c2 + S.r.stride2, 2);
+                                    cb[k] = u;
+                                    vb[k] = v;
+                                }
+                            }
+                        } else {
+                            __builtin_memcpy(&ta[k], l, 8);
+                            __builtin_memcpy(&tb[k], l + S.r.stride0, 8);
+                        }
+                    } else {
+                        const u8* m = S.p0 + (size_t)(f0 + k) * S.r.frame_stride + tap;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) __builtin_memcpy(&rows[k][i], m + (size_t)i * S.r.stride0, 4);
+                    }
+                }
+#pragma unroll
+        for (int k = 0; k < FPT; k++) {
+            if (k >= nf) break;
+            int o[3] = {0, 0, 0};
+            if (t.any_in) {
+                // ---- the taps 00, 01, 10, 11.  BGR: v, the bytes as they lie in the frame, -1 for a tap outside it; the
+                // others: q, converted, as b | g << 8 | r << 16, 0 for a tap outside
+                int v[4][3];
+                u32 q[4] = {0u, 0u, 0u, 0u};
+                if constexpr (BGR) {
+                    if (fast) {
+#pragma unroll
+                        for (int c = 0; c < 3; c++) {
+                            v[0][c] = (int)((ta[k] >> (8 * c)) & 255);
+                            v[1][c] = (int)((ta[k] >> (8 * (3 + c))) & 255);
+                            v[2][c] = (int)((tb[k] >> (8 * c)) & 255);
+                            v[3][c] = (int)((tb[k] >> (8 * (3 + c))) & 255);
+                        }
+                    } else {
+                        const u8* p00 = S.src + (size_t)(f0 + k) * S.g.frame_stride + tap;
+                        const u8* p10 = p00 + S.g.stride;
+#pragma unroll
+                        for (int c = 0; c < 3; c++) {
+                            v[0][c] = (t.x0in && t.y0in) ? p00[c] : -1;
+                            v[1][c] = (t.x1in && t.y0in) ? p00[3 + c] : -1;
+                            v[2][c] = (t.x0in && t.y1in) ? p10[c] : -1;
+                            v[3][c] = (t.x1in && t.y1in) ? p10[3 + c] : -1;
+                        }
+                    }
+                } else if (fast) {
+                    if constexpr (PROFILE) {
+                        q[0] = conv((u32)ta[k]);
+                        q[1] = conv((u32)(ta[k] >> 24));
+                        q[2] = conv((u32)tb[k]);
+                        q[3] = conv((u32)(tb[k] >> 24));
+                    } else if constexpr (YUV) {
+                        if (L::F420) {
+                            Chroma a0, a1, b0, b1;
+                            if (NV12) {
+                                const u32 a = ca[k], sa = odd ? a >> 16 : a;
+                                a0 = d_chroma_pair<FMT>(a);
+                                a1 = d_chroma_pair<FMT>(sa);
+                                b0 = a0;
+                                b1 = a1;
+                                if (two_crows) {
+                                    const u32 b = cb[k], sb = odd ? b >> 16 : b;
+                                    b0 = d_chroma_pair<FMT>(b);
+                                    b1 = d_chroma_pair<FMT>(sb);
+                                }
+                            } else {
+                                const u32 u0 = ca[k], v0 = va[k];
+                                a0 = d_chroma(u0 & 255, v0 & 255);
+                                a1 = d_chroma((odd ? u0 >> 8 : u0) & 255, (odd ? v0 >> 8 : v0) & 255);
+                                b0 = a0;
+                                b1 = a1;
+                                if (two_crows) {
+                                    const u32 u1 = cb[k], v1 = vb[k];
+                                    b0 = d_chroma(u1 & 255, v1 & 255);
+                                    b1 = d_chroma((odd ? u1 >> 8 : u1) & 255, (odd ? v1 >> 8 : v1) & 255);
+                                }
+                            }
+                            q[0] = d_yuv_bgr((int)(ta[k] & 255), a0);
+                            q[1] = d_yuv_bgr((int)((ta[k] >> 8) & 255), a1);
+                            q[2] = d_yuv_bgr((int)(tb[k] & 255), b0);
+                            q[3] = d_yuv_bgr((int)((tb[k] >> 8) & 255), b1);
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 2; r++) {
+                                const u64 w = r ? tb[k] : ta[k];
+                                const u32 lo = (u32)w, hi = (u32)(w >> 32), s1 = odd ? hi : lo;
+                                const Chroma c0 = d_chroma((lo >> (8 * L::PU)) & 255, (lo >> (8 * L::PV)) & 255);
+                                const Chroma c1 = d_chroma((s1 >> (8 * L::PU)) & 255, (s1 >> (8 * L::PV)) & 255);
+                                q[2 * r] = d_yuv_bgr((int)((odd ? lo >> (8 * L::Y1) : lo >> (8 * L::Y0)) & 255), c0);
+                                q[2 * r + 1] = d_yuv_bgr((int)((odd ? hi >> (8 * L::Y0) : lo >> (8 * L::Y1)) & 255), c1);
+                            }
+                        }
+                    } else {
+                        const u32* w = rows[k];
+                        q[0] = d_bayer_bgr<FMT>(t.sx, t.sy, w[0], w[1], w[2]);
+                        q[1] = d_bayer_bgr<FMT>(t.sx + 1, t.sy, w[0] >> 8, w[1] >> 8, w[2] >> 8);
+                        q[2] = d_bayer_bgr<FMT>(t.sx, t.sy + 1, w[1], w[2], w[3]);
+                        q[3] = d_bayer_bgr<FMT>(t.sx + 1, t.sy + 1, w[1] >> 8, w[2] >> 8, w[3] >> 8);
+                    }
+                } else {
+                    if constexpr (PROFILE) {
+                        const u8* p00 = S.src + (size_t)(f0 + k) * S.g.frame_stride + tap;
+                        const u8* p10 = p00 + S.g.stride;
+                        auto px = [&](const u8* p) -> u32 { return conv((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16)); };
+                        if (t.x0in && t.y0in) q[0] = px(p00);
+                        if (t.x1in && t.y0in) q[1] = px(p00 + 3);
+                        if (t.x0in && t.y1in) q[2] = px(p10);
+                        if (t.x1in && t.y1in) q[3] = px(p10 + 3);
+                    } else if constexpr (YUV) {
+                        const u8* f0p = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
+                        const u8* f1p = L::F420 ? S.p1 + (size_t)(f0 + k) * S.r.frame_stride : nullptr;
+                        const u8* f2p = PLANAR ? S.p2 + (size_t)(f0 + k) * S.r.frame_stride : nullptr;
+                        if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy);
+                        if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy);
+                        if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy + 1);
+                        if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy + 1);
+                    } else {
+                        const u8* fp = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
+                        if (t.x0in && t.y0in) q[0] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx, t.sy);
+                        if (t.x1in && t.y0in) q[1] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx + 1, t.sy);
+                        if (t.x0in && t.y1in) q[2] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx, t.sy + 1);
+                        if (t.x1in && t.y1in) q[3] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx + 1, t.sy + 1);
+                    }
+                }
+                // a raw source's profile: on the converted taps inside the frame (a fast pixel has all four there)
+                if constexpr (RAW_TABS) {
+                    const bool in[4] = {t.x0in && t.y0in, t.x1in && t.y0in, t.x0in && t.y1in, t.x1in && t.y1in};
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (fast || in[i]) q[i] = conv(q[i]);
+                }
+                // ---- the blend
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    int b[4] = {(int)((q[0] >> (8 * c)) & 255), (int)((q[1] >> (8 * c)) & 255), (int)((q[2] >> (8 * c)) & 255), (int)((q[3] >> (8 * c)) & 255)};
+                    if constexpr (BGR)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) b[i] = v[i][c] < 0 ? 0 : (use_lut ? (int)lds.lut[k][v[i][c]] : v[i][c]); // border taps are 0
+                    o[c] = warp_blend(b[0], b[1], b[2], b[3], t);
+                }
+            }
+            u8* out = D.dst + (size_t)(f0 + k) * D.frame_stride + t.out_off;
+            out[0] = (u8)o[0];
+            out[1] = (u8)o[1];
+            out[2] = (u8)o[2];
+        }
+        dy += 4;
+    } while (Src::ROWS > 4 && ++row < Src::ROWS / 4 && dy < D.dh);
+}
+
+// ---------------------------------------------------------------------------
+// The kernels: per source one for a single board, which takes the matrix by value, and one (_mb) for every board of a
+// pipeline in one launch: blockIdx.z = board * nz + group of frames; the grid covers the largest board and the blocks
+// outside a smaller one leave at once (what is staged for the shared frames is the same for every board).
+// ---------------------------------------------------------------------------
+// where a multi-board launch writes board T; s0 = the slot of the chunk's frame 0
+__device__ __forceinline__ WarpDst warp_board_dst(const BoardDev& T, int s0)
+{
+    return WarpDst{T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride};
+}
+
+// ---------------------------------------------------------------------------
+// The launchers.  Batched launches take four frames per thread (eight: 13 % fewer instructions again, no change on the
+// path); a launch of a frame or two keeps one thread per pixel and frame.
+// ---------------------------------------------------------------------------
+// groups of frames of a launch: `many` frames a group from batch 8 on (four, but for the raw sources with a profile, whose
+// kernels choose per family: raw_profile_fpt)
+static int warp_groups(int batch, int many = 4)
+{
+    const int fpt = batch >= 8 ? many : 1;
+    return (batch + fpt - 1) / fpt;
+}
+
+template <int N>
+using WarpInt = std::integral_constant<int, N>;
+
+// launch(fmt, fpt) with the compile-time forms of a raw format id and of the frames per thread of `batch` frames: 1, or 4
+// for the many-frames form (CBV_FMT_BGR: the BGR sources, whose kernels have no format parameter)
+template <class F>
+static void warp_dispatch(int fmt, int batch, F&& launch)
+{
+    auto with_fmt = [&](auto f) {
+        if (batch >= 8) launch(f, WarpInt<4>());
+        else launch(f, WarpInt<1>());
+    };
+    switch (fmt) {
+    case CBV_FMT_BGR: return with_fmt(WarpInt<CBV_FMT_BGR>());
+    case CBV_FMT_NV12: return with_fmt(WarpInt<CBV_FMT_NV12>());
+    case CBV_FMT_NV21: return with_fmt(WarpInt<CBV_FMT_NV21>());
+    case CBV_FMT_YUYV: return with_fmt(WarpInt<CBV_FMT_YUYV>());
+    case CBV_FMT_YVYU: return with_fmt(WarpInt<CBV_FMT_YVYU>());
+    case CBV_FMT_UYVY: return with_fmt(WarpInt<CBV_FMT_UYVY>());
+    case CBV_FMT_BAYER_RGGB: return with_fmt(WarpInt<CBV_FMT_BAYER_RGGB>());
+    case CBV_FMT_BAYER_BGGR: return with_fmt(WarpInt<CBV_FMT_BAYER_BGGR>());
+    case CBV_FMT_BAYER_GRBG: return with_fmt(WarpInt<CBV_FMT_BAYER_GRBG>());
+    case CBV_FMT_BAYER_GBRG: return with_fmt(WarpInt<CBV_FMT_BAYER_GBRG>());
+    default: return with_fmt(WarpInt<CBV_FMT_YUV420P>());
+    }
+}
+
+// What both launchers do around their kernels: the refusals of the source (raw planes: what launch_ingest asks of them; YV12
+// leaves as YUV420P), the groups of frames, the grid of a dw x dh destination with nz * zmul layers, the profiling bracket.
+// launch(fmt, fpt, grid, nz) issues the kernel of the source's kind; `many` = the frames per thread of its many-frames form.
+template <class F>
+static int warp_launch(cbv_ctx* ctx, WarpSrc* s, int dw, int dh, int zmul, int batch, F&& launch, int many = 4)
+{
+    if (s->raw()) {
+        const char* what = s->kind == WarpSrc::BAYER ? "launch_warp_bayer" : "launch_warp_yuv";
+        RC(check_raw_format(ctx, s->r.fmt, s->g.w, s->g.h, what));
+        // (warp_src_raw takes the kind from the format: only a WarpSrc filled by hand can fail this)
+        if (s->kind == WarpSrc::BAYER && !raw_fmt_bayer(s->r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a Bayer format", what, s->r.fmt);
+        if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes or strides", what);
+        const int strides[3] = {s->r.stride0, s->r.stride1, s->r.stride2};
+        RC(check_raw_planes(ctx, s->r.fmt, s->g.w, s->planes.p, strides, what));
+        raw_planes_canonical(&s->planes, &s->r);
+    }
+    const int nz = warp_groups(batch, many), rows = s->profiled() ? WP_ROWS : 4;
+    const dim3 grid((dw + 63) / 64, (dh + rows - 1) / rows, nz * zmul);
+    const int prof = s->raw() ? CBV_K_WARP_YUV : CBV_K_WARP;
+    prof_begin(ctx, prof);
+    warp_dispatch(s->raw() ? s->r.fmt : CBV_FMT_BGR, batch, [&](auto fmt, auto fpt) { launch(fmt, fpt, grid, nz); });
+    prof_end(ctx, prof);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}

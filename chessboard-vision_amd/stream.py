@@ -325,6 +325,13 @@ class _BoardMethods:
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_change_blur(self.h_, int(blur_kernel)))
         self._change_blur = max(int(blur_kernel), 1) | 1
 
+    def set_profile(self, profile):
+        """The colour profile of this board (the pipeline's own board or an attached one) for the runs enqueued from now
+        on: a dict with the keys of color_profile.json, `None` / `{}` = none.  Only on a pipeline configured with
+        `enhance="profile"`; every board starts with the profile `configure` was given.  Detector, model, noise and
+        session state are kept (include/cbv.h, cbv_pipeline_set_profile)."""
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_profile(self.h_, N.ColorProfile.from_dict(profile)))
+
     @property
     def change_blur(self):
         """The blur kernel the ChangeDetector stage of this board runs with."""
@@ -620,6 +627,9 @@ class Session:
         self._open = False
 
 
+_NO_PROFILE = object()  # add_board(profile=...) not given: the board keeps the pipeline's configured profile
+
+
 class BoardPipeline(_BoardMethods):
     def __init__(self, w, h, max_frames, ctx=None):
         self.ctx = ctx or N.context()
@@ -652,7 +662,7 @@ class BoardPipeline(_BoardMethods):
                   z_threshold=_D["z_threshold"], initial_variance=_D["initial_variance"], use_hough=_D["use_hough"],
                   min_radius_ratio=_D["min_radius_ratio"], max_radius_ratio=_D["max_radius_ratio"],
                   hough_param1=_D["hough_param1"], hough_param2=_D["hough_param2"], enhance_region=False, enhance=True,
-                  blur_kernel=5):
+                  blur_kernel=5, raw=False):
         """`use_hough` and the radii mirror PieceDetector's attributes (piece_detector.py:33-35,222-230);
         pass min_radius / 100 and max_radius / 100 of piece_detector_settings.json as the application does.
         `enhance_region` (only without keep_enhanced): enhance the part of each frame the warp samples first and the rest
@@ -661,8 +671,11 @@ class BoardPipeline(_BoardMethods):
         `enhance="profile"` runs apply_color_profile -> warp -> rotate -> split -> detect: of the enhancement only the
         colour `profile`, applied inside the warp at nearly the cost of `enhance=False`; the CLAHE and sharpen settings are
         ignored, `keep_enhanced` and `enhance_region` are errors, a `None` / `{}` profile is `enhance=False`'s warp, and
-        YUV frames are converted into the BGR ring as with `enhance=True` (no raw mode).  `color_sweep` judges profiles
-        for this mode.
+        YUV frames are converted into the BGR ring as with `enhance=True`, unless `raw=True`: then a YUV or Bayer
+        `set_input_format` makes the raw ring the frames, as with `enhance=False`, and the warp converts its taps and
+        applies the profile to them (`raw=True` with any other `enhance` is a ValueError; with BGR frames it changes
+        nothing).  `color_sweep` judges profiles for this mode, on either kind of ring; `set_profile` gives a board a
+        profile of its own.
         `enhance=False` reproduces what GameSession.on_frame (game_session.py:123-161) and calibrate_sensitivity.py:142-157
         run: the warp samples the camera frame as it is, then rotate, split and detect; `profile` (used by `enhance=True`
         and `enhance="profile"` only), the CLAHE and sharpen settings are ignored, `keep_enhanced` and `enhance_region` are errors, and with a YUV `set_input_format` the warp
@@ -686,7 +699,9 @@ class BoardPipeline(_BoardMethods):
         cfg.enhance_region = 1 if enhance_region else 0
         if isinstance(enhance, str) and enhance != "profile":
             raise ValueError("enhance %r: expected True, False or \"profile\"" % (enhance,))
-        cfg.skip_enhance = N.SKIP_ENHANCE_PROFILE if enhance == "profile" else (0 if enhance else 1)
+        if raw and enhance != "profile":
+            raise ValueError("raw=True goes with enhance=\"profile\" (enhance=False samples raw frames as it is), got enhance=%r" % (enhance,))
+        cfg.skip_enhance = (N.SKIP_ENHANCE_PROFILE_RAW if raw else N.SKIP_ENHANCE_PROFILE) if enhance == "profile" else (0 if enhance else 1)
         self.ctx.check(self.ctx.lib.cbv_pipeline_configure(self.h_, cfg))
         self.rois_rc = rois_rc
         self.board_size = S_
@@ -694,14 +709,18 @@ class BoardPipeline(_BoardMethods):
         self._cfg = cfg
         self.set_change_blur(blur_kernel)
 
-    def add_board(self, points, grid_lines=None, rot180=False, display_size=(1280, 720), margin=100, blur_kernel=5, **detector):
+    def add_board(self, points, grid_lines=None, rot180=False, display_size=(1280, 720), margin=100, blur_kernel=5, profile=_NO_PROFILE,
+                  **detector):
         """Attach another board seen by the same camera (include/cbv.h, cbv_pipeline_add_board): it shares this
         pipeline's frames and enhancement, and has its own geometry, detector settings (the detector keywords of
         `configure`: history_size, min_presence, change_threshold, z_threshold, initial_variance, use_hough,
-        min_radius_ratio, max_radius_ratio, hough_param1, hough_param2), `blur_kernel` (`set_change_blur`) and temporal
-        state.  `run` processes every attached board.  Returns a Board with the per-board methods of this class."""
+        min_radius_ratio, max_radius_ratio, hough_param1, hough_param2), `blur_kernel` (`set_change_blur`), colour
+        `profile` (`set_profile`; not given: the pipeline's configured one) and temporal state.  `run` processes every
+        attached board.  Returns a Board with the per-board methods of this class."""
         b = Board(self, points, grid_lines, rot180, display_size, margin, **detector)
         b.set_change_blur(blur_kernel)
+        if profile is not _NO_PROFILE:
+            b.set_profile(profile)
         return b
 
     def frames_ptr(self):
@@ -713,7 +732,7 @@ class BoardPipeline(_BoardMethods):
         order, (y, u, v) / (y, v, u)) and "yuyv" / "yvyu" / "uyvy" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h,
         cbv_pipeline_upload_raw; "i420" is not a name, the format is "yuv420p"), and so are the 8-bit Bayer mosaics
         "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg" (one [h, w] array, named by the top-left 2 x 2 block:
-        cv2's COLOR_BayerBG2BGR is "bayer_rggb"); in raw mode (`configure(enhance=False)` with a YUV or Bayer
+        cv2's COLOR_BayerBG2BGR is "bayer_rggb"); in raw mode (`configure(enhance=False)` or `(enhance="profile", raw=True)` with a YUV or Bayer
         `set_input_format`) the frame is stored as it is."""
         if N.format_id(fmt) == N.FMT_BGR:
             f = N.as_bgr(frame)

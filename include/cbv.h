@@ -184,7 +184,6 @@ CBV_API int cbv_warp_perspective(cbv_ctx* ctx, const uint8_t* bgr, int w, int h,
  * tap outside the frame is BGR 0 (BORDER_CONSTANT), not the profile of black.  The profile's tables belong to the call. */
 CBV_API int cbv_warp_color_profile(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, const cbv_color_profile* profile,
                                    const double* M9, int dw, int dh, int rot180, uint8_t* out, int out_stride);
-
 /* ------------------------------------------------------------------ */
 /* per-square detector state (change_detector.py, piece_detector.py)   */
 /* ------------------------------------------------------------------ */
@@ -383,13 +382,19 @@ typedef struct {
                                     cbv_pipeline_set_input_format).  0: the composed chain enhance -> warp -> detect.
                                     CBV_SKIP_ENHANCE_PROFILE (2): the colour profile only: apply_color_profile -> warp ->
                                     rotate -> split -> detect, the profile applied to the warp's taps (k_warp_profile), no
-                                    enhancement scratch.  Of `enhance` only enhance.profile is read and checked; the
-                                    profile is the pipeline's (every board's); keep_enhanced / enhance_region / download
-                                    (which = 1) as for 1.  A disabled profile takes the plain warp.  With a YUV input format
-                                    the frames are converted into the BGR ring as with enhancement (raw mode is 1 only).
-                                    Every other non-zero value means 1 */
+                                    enhancement scratch.  Of `enhance` only enhance.profile is read and checked; it is
+                                    the profile every board starts with (cbv_pipeline_set_profile gives a board its own);
+                                    keep_enhanced / enhance_region / download (which = 1) as for 1.  While no board has an
+                                    enabled profile the plain warp runs.  With a YUV or Bayer input format the frames are
+                                    converted into the BGR ring as with enhancement.
+                                    CBV_SKIP_ENHANCE_PROFILE_RAW (3): as 2, and a YUV or Bayer input format makes the raw
+                                    ring THE frames, as with 1 (raw mode, cbv_pipeline_set_input_format): the warp converts
+                                    its taps and applies the profile to them (k_warp_raw_profile), no frame is converted,
+                                    and while the input format is raw the pipeline holds no BGR frame ring (it is freed
+                                    and allocated again as the mode and the format change).  With BGR input 3 is 2.  Every other non-zero value means 1 */
 } cbv_pipeline_config;
 #define CBV_SKIP_ENHANCE_PROFILE 2 /* cbv_pipeline_config::skip_enhance: the colour profile and nothing else of the enhancement */
+#define CBV_SKIP_ENHANCE_PROFILE_RAW 3 /* ... and camera-native frames are sampled as they are (raw mode) */
 
 /* Per frame result of PieceDetector.detect_all_pieces(use_smoothing=True,
  * use_delta=True, squares_to_check=None) (piece_detector.py:348-440);
@@ -436,7 +441,8 @@ CBV_API int cbv_noise_run(cbv_ctx* ctx, const uint64_t* changes, int n, cbv_nois
 CBV_API int cbv_pipeline_create(cbv_ctx* ctx, int w, int h, int max_frames, cbv_pipeline** out);
 CBV_API void cbv_pipeline_destroy(cbv_pipeline* p);
 CBV_API int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* cfg);
-/* device pointer of the input frame ring: [max_frames][h][w][3] uint8 */
+/* device pointer of the input frame ring: [max_frames][h][w][3] uint8 (NULL while a pipeline configured with
+ * CBV_SKIP_ENHANCE_PROFILE_RAW has a YUV or Bayer input format: it holds no BGR ring) */
 CBV_API void* cbv_pipeline_frames_dev(cbv_pipeline* p);
 CBV_API int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr, int stride);
 /* Ingest front end: a pinned host mirror of the frame ring ([max_frames][h][w][3], or raw frames after
@@ -559,6 +565,15 @@ typedef struct {
 
 /* host in, host out: the cvtColor call on its own (fmt = any CBV_FMT_* but BGR, the Bayer mosaics included) */
 CBV_API int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride);
+/* cbv_warp_color_profile on one camera-native frame (any CBV_FMT_* but BGR): = cbv_yuv_to_bgr, then
+ * cbv_apply_color_profile, then cbv_warp_perspective (+ rotate 180), byte for byte, in one kernel (k_warp_raw_profile):
+ * the four taps are converted (YUV) or demosaiced (Bayer), the profile is applied to each tap inside the frame, and they
+ * are blended; neither the BGR frame nor the profiled frame exists.  A tap outside the frame is BGR 0.  profile->enabled
+ * = 0 is the plain raw warp (k_warp_yuv, k_warp_bayer).  Host in, host out.  CBV_ERR_ARG, with `out` untouched: null
+ * arguments, BGR or an unknown format, odd w, odd h with a 4:2:0 or Bayer format, a Bayer frame below 4 x 4, a missing
+ * plane or a stride below its row, a profile field that is not finite. */
+CBV_API int cbv_warp_color_profile_raw(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, const cbv_color_profile* profile,
+                                       const double* M9, int dw, int dh, int rot180, uint8_t* out, int out_stride);
 /* one frame of any format into a slot of the frame ring, synchronous, like cbv_pipeline_upload */
 CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_frame* raw);
 /* Format of the pinned ingest ring; CBV_FMT_BGR is the default.  Waits for the submitted copies, then FREES the pinned
@@ -569,7 +584,8 @@ CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_fra
  * same (a run of the slots waits for the copy and its conversion).  On the pipeline only (a board handle:
  * CBV_ERR_STATE); CBV_ERR_ARG for an unknown format, odd w, odd h with a 4:2:0 or Bayer format, or a Bayer frame below
  * 4 x 4, and then nothing has changed.
- * Raw mode: on a pipeline configured with skip_enhance a YUV or Bayer format makes the raw ring THE frames.  cbv_pipeline_submit
+ * Raw mode: on a pipeline configured with skip_enhance 1 or CBV_SKIP_ENHANCE_PROFILE_RAW a YUV or Bayer format makes the raw ring
+ * THE frames (with the latter the warp also applies the boards' colour profiles to its taps, k_warp_raw_profile).  cbv_pipeline_submit
  * only copies the raw slots, cbv_pipeline_upload_raw (that format only) writes a raw slot, cbv_pipeline_run warps straight
  * from the raw frames (k_warp_yuv, k_warp_bayer: byte for byte what the conversion followed by the warp gives) and no BGR frame is ever
  * written; cbv_pipeline_upload (BGR), cbv_pipeline_synth and cbv_pipeline_upload_raw in another format return
@@ -659,6 +675,14 @@ CBV_API int cbv_pipeline_set_model_update(cbv_pipeline* board, int mode, double 
  * with CBV_ERR_STATE: run the slot again first.  k > 31: CBV_ERR_UNSUPPORTED (cbv_squares_load's limit), and then nothing
  * has changed.  REFLECT_101 folds as often as needed, so every kernel fits every square. */
 CBV_API int cbv_pipeline_set_change_blur(cbv_pipeline* board, int blur_kernel);
+/* The colour profile of a board (pipeline = board 0, or an attached board) in the profile modes (skip_enhance =
+ * CBV_SKIP_ENHANCE_PROFILE or CBV_SKIP_ENHANCE_PROFILE_RAW; otherwise CBV_ERR_STATE): one camera may watch a lilac board
+ * beside a green one.  Every board starts with the pipeline's configured profile (cfg.enhance.profile).  Joins the runs in
+ * flight and applies to the runs enqueued after the call; detector, model, noise and session state are kept.  While no
+ * board has an enabled profile the plain warp is launched; otherwise the profile kernel runs with one table per board,
+ * and a board whose profile is disabled keeps its taps as they are.  CBV_ERR_ARG for a profile field that is not finite,
+ * and then nothing has changed.  cbv_pipeline_configure sets every board's profile anew. */
+CBV_API int cbv_pipeline_set_profile(cbv_pipeline* board, const cbv_color_profile* profile);
 /* The model of square `roi` after every run enqueued so far (waits for them): which = 0 the mean plane
  * (change_detector.py:44), 1 the variance plane (change_detector.py:45), `out` = w * h floats, row major.  Read only.
  * CBV_ERR_STATE while the board is not calibrated. */
@@ -943,7 +967,8 @@ CBV_API int cbv_piece_sweep_eval_host(const cbv_sq_stats* stats, const int32_t* 
  * square checked reports.  The result is in cbv_pipeline_piece_sweep's terms: records [np][count] (profile major; may be
  * NULL), summary [np], `expected` (may be NULL), CBV_PIECE_SWEEP_OVERFLOW.  An entry with enabled = 0 is the frame as it is.
  * Any board handle.  Reads the BGR frame ring (the frames as uploaded, before any enhancement, whatever the pipeline's
- * mode) and the board's geometry, square table, masks and Hough settings (cfg.hough, whether or not use_hough is set);
+ * mode), or, in the raw mode of CBV_SKIP_ENHANCE_PROFILE_RAW, the raw ring through k_warp_raw_profile (the same scratch
+ * layout, stages, records, summaries and `info`; the result is that of the converted frames), and the board's geometry, square table, masks and Hough settings (cfg.hough, whether or not use_hough is set);
  * writes nothing of the board's, does not need the slots to have been run, and a pipeline that never calls it launches
  * and allocates nothing for it.  Waits for the runs in flight.  Per chunk of profiles x chunk of frames: k_warp_profile
  * into scratch boards [profile][frame], the fused gray + 5 x 5 blur + statistics kernel on them, the sweep's HoughCircles
@@ -958,7 +983,8 @@ CBV_API int cbv_piece_sweep_eval_host(const cbv_sq_stats* stats, const int32_t* 
  * or on duplicates.
  * CBV_ERR_STATE: not configured.  CBV_ERR_ARG: null or empty arguments, no summary, slots outside the ring, chunk_frames
  * outside 0..CBV_SWEEP_MAX_CHUNK, np above CBV_COLOR_SWEEP_MAX_PROFILES, a profile field that is not finite.
- * CBV_ERR_UNSUPPORTED: raw mode (there is no BGR ring), or squares that do not fit the HoughCircles kernel's LDS layout.
+ * CBV_ERR_UNSUPPORTED: the raw mode of skip_enhance = 1 (there is no BGR ring and no profile kernel; configure
+ * CBV_SKIP_ENHANCE_PROFILE_RAW with a disabled profile instead: that runs the plain raw warp and can sweep), or squares that do not fit the HoughCircles kernel's LDS layout.
  * After any error nothing has changed. */
 typedef struct { float warp_ms, squares_ms, hough_ms, eval_ms; int32_t chunk_frames, chunk_profiles; } cbv_color_sweep_info;
 #define CBV_COLOR_SWEEP_MAX_PROFILES 65536
