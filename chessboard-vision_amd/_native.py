@@ -282,6 +282,17 @@ FMT_BAYER_RGGB, FMT_BAYER_BGGR, FMT_BAYER_GRBG, FMT_BAYER_GBRG = 0x04, 0x14, 0x2
 BAYER_FORMATS = {"bayer_rggb": FMT_BAYER_RGGB, "bayer_bggr": FMT_BAYER_BGGR, "bayer_grbg": FMT_BAYER_GRBG,
                  "bayer_gbrg": FMT_BAYER_GBRG}                 # ring slots [h, w]
 
+FMT_MJPEG = 0x08  # one JPEG stream per frame: jpeg_to_bgr, BoardPipeline.set_input_format("mjpeg"); has no raw_frame() layout
+JPEG_BAD_CODE, JPEG_NO_DATA, JPEG_RESTART = 1, 2, 4
+
+
+class JpegInfo(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("restart_interval", C.c_int32), ("intervals", C.c_int32), ("std_tables", C.c_int32),
+                ("entropy_offset", C.c_uint32), ("entropy_length", C.c_uint32), ("plane_elems", C.c_uint32),
+                ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3)]
+
+
 KERNEL_IDS = ["COLOR_LAB_HIST", "CLAHE_LUT", "CLAHE_APPLY", "BILATERAL", "SHARPEN", "NORM_LUT", "NORMALIZE", "WARP",
               "SQUARES", "GRAY_BLUR", "OTSU", "THRESHOLD", "SCAN", "SYNTH", "RESET", "HOUGH", "INGEST"]
 K = {name: i for i, name in enumerate(KERNEL_IDS)}
@@ -413,6 +424,13 @@ def load():
         "cbv_session_state_init_cfg": (i32, [P(SessionState), P(SessionConfig), C.c_char_p]),
         "cbv_session_device_legal_moves": (i32, [vp, C.c_char_p, P(C.c_uint16), i32, P(i32)]),
         "cbv_session_generator_time": (i32, [vp, C.c_char_p, i32, P(dbl)]),
+        "cbv_jpeg_probe": (i32, [vp, C.c_size_t, P(JpegInfo)]),
+        "cbv_jpeg_decode_host": (i32, [vp, C.c_size_t, u8p, i32, vp, vp, P(C.c_int32)]),
+        "cbv_jpeg_decode": (i32, [vp, vp, C.c_size_t, u8p, i32, vp, vp, P(C.c_int32)]),
+        "cbv_pipeline_host_jpeg_lengths": (C.c_void_p, [vp]),
+        "cbv_pipeline_set_jpeg_slot_bytes": (i32, [vp, C.c_size_t]),
+        "cbv_pipeline_upload_jpeg": (i32, [vp, i32, vp, C.c_size_t]),
+        "cbv_pipeline_jpeg_status": (i32, [vp, i32, i32, vp]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

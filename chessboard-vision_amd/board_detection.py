@@ -130,6 +130,64 @@ def bayer_to_bgr(frame, fmt):
     return out
 
 
+def _jpeg_bytes(data):
+    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if a.size == 0:
+        raise ValueError("an empty JPEG stream")
+    return a
+
+
+def jpeg_probe(data):
+    """The header of one baseline JPEG stream (include/cbv.h, cbv_jpeg_probe) as a dict: w, h, components, hs, vs (luma
+    sampling), restart_interval, intervals, std_tables (no DHT in the stream), entropy_offset, entropy_length, plane_elems,
+    blocks (per component: blocks wide, blocks high).  Host only.  ValueError for a stream the decode refuses."""
+    lib = N.load()
+    a = _jpeg_bytes(data)
+    info = N.JpegInfo()
+    rc = lib.cbv_jpeg_probe(N.ptr(a), a.size, C.byref(info))
+    if rc != 0:
+        raise ValueError("%s (code %d)" % (lib.cbv_last_error(None).decode(), rc))
+    d = {k: getattr(info, k) for k, _ in N.JpegInfo._fields_ if not k.startswith("blocks")}
+    d["blocks"] = [(info.blocks_w[c], info.blocks_h[c]) for c in range(info.components)]
+    return d
+
+
+def jpeg_decode(data, host=False):
+    """One baseline JPEG stream with its stage outputs: (bgr [h, w, 3], coef int16 [plane_elems], planes uint8 [plane_elems],
+    status).  On the GPU (cbv_jpeg_decode), or with host=True by the library's host twin (cbv_jpeg_decode_host, no GPU): the
+    same bodies, byte for byte.  The layout of coef and planes: jpeg_probe(data)["blocks"] and include/cbv.h.  status:
+    _native.JPEG_BAD_CODE | JPEG_NO_DATA | JPEG_RESTART, 0 for an undamaged stream."""
+    a = _jpeg_bytes(data)
+    info = jpeg_probe(a)
+    bgr = np.empty((info["h"], info["w"], 3), np.uint8)
+    coef = np.empty(info["plane_elems"], np.int16)
+    planes = np.empty(info["plane_elems"], np.uint8)
+    st = C.c_int32()
+    if host:
+        lib = N.load()
+        rc = lib.cbv_jpeg_decode_host(N.ptr(a), a.size, N.ptr(bgr), info["w"] * 3, N.ptr(coef), N.ptr(planes), C.byref(st))
+        if rc != 0:
+            raise RuntimeError("libcbv_hip: %s (code %d)" % (lib.cbv_last_error(None).decode(), rc))
+    else:
+        ctx = N.context()
+        ctx.check(ctx.lib.cbv_jpeg_decode(ctx.h, N.ptr(a), a.size, N.ptr(bgr), info["w"] * 3, N.ptr(coef), N.ptr(planes), C.byref(st)))
+    return bgr, coef, planes, st.value
+
+
+def jpeg_to_bgr(data):
+    """cv2.imdecode(data, IMREAD_COLOR) of a baseline JPEG stream (a Motion-JPEG frame), on the GPU: a new uint8 [h, w, 3]
+    array, the bytes libjpeg's defaults give (slow-integer IDCT, fancy upsampling; include/cbv.h).  `data`: bytes or a uint8
+    array.  A damaged stream decodes as far as it goes (jpeg_decode returns the status word); a stream outside the
+    accepted set raises ValueError."""
+    a = _jpeg_bytes(data)
+    info = jpeg_probe(a)
+    ctx = N.context()
+    bgr = np.empty((info["h"], info["w"], 3), np.uint8)
+    st = C.c_int32()
+    ctx.check(ctx.lib.cbv_jpeg_decode(ctx.h, N.ptr(a), a.size, N.ptr(bgr), info["w"] * 3, None, None, C.byref(st)))
+    return bgr
+
+
 def crop_inner_squares(img_warped, board_size, offset=0):
     """The warped board without an `offset`-pixel border, as a view, and the new board size (board_detection.py:74-82)."""
     cropped = img_warped[offset:board_size - offset, offset:board_size - offset]

@@ -812,3 +812,31 @@ int hough_cfg(cbv_ctx* ctx, const cbv_hough_params* prm, const std::vector<Squar
 // the square table of n squares ws[i] x hs[i]: descriptors with w, h and the plane / mask offsets (each plane rounded to
 // 16 B), the piece masks and their region counts; returns the bytes of one plane set
 size_t square_table(const int* ws, const int* hs, int n, std::vector<SquareDesc>* descs, std::vector<u8>* masks);
+
+// Baseline JPEG decode (k_jpeg.hip; the bodies and the descriptor types are jpeg_core.h's).  `nframes` streams, frame f's
+// bytes at data + f * data_stride, decoded by restart interval: ioff[nframes + 1] = the prefix sums of the frames' interval
+// counts, mpos[ioff[nframes]] = scratch for the restart markers' positions.  Outputs of frame f: coef + f * coef_stride
+// (int16 elements; a multiple of 64), planes + f * plane_stride (a multiple of 8), bgr + f * bgr_frame_stride, status[f].
+struct JpegDesc;
+struct JpegTables;
+struct JpegBatch {
+    const u8* data;
+    size_t data_stride;
+    const JpegDesc* descs;
+    const JpegTables* tables; // the table sets JpegDesc::table_set names
+    const u32* ioff;
+    u32* mpos;
+    int* nfound;              // [nframes] scratch: restart markers found, at most the frame's intervals - 1
+    int* status;              // [nframes] JP_ST_* bits
+    int16_t* coef;
+    size_t coef_stride;
+    u8* planes;
+    size_t plane_stride;
+    u8* bgr;
+    int bgr_stride;
+    size_t bgr_frame_stride;
+    int nframes;
+};
+// zeroes coef, status and nfound, then the four kernels on ctx->stream; total_intervals = ioff[nframes], max_blocks = the
+// largest plane_total / 64, max_w x max_h = the largest frame
+int launch_jpeg_decode(cbv_ctx* ctx, const JpegBatch& B, u32 total_intervals, int any_dri, u32 max_blocks, int max_w, int max_h);

@@ -1,0 +1,373 @@
+// Motion-JPEG entry points (include/cbv.h): the header probe, the host twin and the single-frame GPU decode.  The host
+// reads the header only; the entropy data is the kernels' (k_jpeg.hip).
+#include <algorithm>
+
+#include "cbv_pipeline.h"
+
+#include "jpeg_core.h"
+
+static int jpeg_header(cbv_ctx* ctx, const char* who, const uint8_t* data, size_t n, JpegDesc* D, JpegTables* T)
+{
+    char msg[200];
+    const int rc = jpeg_parse_header(data, n, D, T, msg, sizeof(msg));
+    if (rc) return cbv_fail(ctx, rc, "%s: %s", who, msg);
+    return CBV_OK;
+}
+
+extern "C" int cbv_jpeg_probe(const uint8_t* data, size_t n, cbv_jpeg_info* info)
+{
+    if (!data || !info) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_jpeg_probe: null argument");
+    JpegDesc D;
+    JpegTables T;
+    RC(jpeg_header(nullptr, "cbv_jpeg_probe", data, n, &D, &T));
+    memset(info, 0, sizeof(*info));
+    info->w = D.w;
+    info->h = D.h;
+    info->components = D.ncomp;
+    info->hs = D.hs;
+    info->vs = D.vs;
+    info->restart_interval = D.dri;
+    info->intervals = D.nint;
+    info->std_tables = D.std_tables;
+    info->entropy_offset = D.ent_off;
+    info->entropy_length = D.ent_len;
+    info->plane_elems = D.plane_total;
+    for (int c = 0; c < D.ncomp; c++) {
+        info->blocks_w[c] = D.bw[c];
+        info->blocks_h[c] = D.bh[c];
+    }
+    return CBV_OK;
+}
+
+extern "C" int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes, int32_t* status)
+{
+    const char* who = "cbv_jpeg_decode_host";
+    if (!data || !bgr || !status) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: null argument", who);
+    JpegDesc D;
+    JpegTables T;
+    RC(jpeg_header(nullptr, who, data, n, &D, &T));
+    if (stride < D.w * 3) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: stride %d below the %d bytes of a row", who, stride, D.w * 3);
+    std::vector<int16_t> cbuf;
+    std::vector<uint8_t> pbuf;
+    if (!coef) {
+        cbuf.resize(D.plane_total);
+        coef = cbuf.data();
+    }
+    if (!planes) {
+        pbuf.resize(D.plane_total);
+        planes = pbuf.data();
+    }
+    int st = 0;
+    jpeg_decode_host(data, D, T, coef, planes, bgr, (size_t)stride, &st);
+    *status = st;
+    return CBV_OK;
+}
+
+// One stream through the four kernels on ctx->stream, with the context's scratch: the stream in ctx->in, coefficients in
+// ctx->a, planes in ctx->b, the small block (descriptor, tables, interval prefix, counters, marker positions) in ctx->small.
+// bgr_dev null: the BGR frame goes to ctx->c, tightly packed.  Nothing is waited for; *B tells where everything lies.
+static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc& D, const JpegTables& T, u8* bgr_dev, Geom g, JpegBatch* Bout)
+{
+    const size_t o_desc = 0, o_tab = (sizeof(JpegDesc) + 255) & ~(size_t)255, o_ioff = (o_tab + sizeof(JpegTables) + 255) & ~(size_t)255;
+    const size_t o_nfound = o_ioff + 16, o_status = o_ioff + 32, o_mpos = o_ioff + 64;
+    const size_t head = o_mpos; // what the host fills
+    RC(dev_ensure(ctx, &ctx->small, o_mpos + (size_t)D.nint * sizeof(u32)));
+    ctx->small.tag = 0; // (not the enhancement chain's layout any more)
+    RC(dev_ensure(ctx, &ctx->in, n + 256));
+    RC(dev_ensure(ctx, &ctx->a, (size_t)D.plane_total * sizeof(int16_t)));
+    RC(dev_ensure(ctx, &ctx->b, D.plane_total));
+    if (!bgr_dev) {
+        RC(dev_ensure(ctx, &ctx->c, g.frame_stride));
+        bgr_dev = (u8*)ctx->c.p;
+    }
+    u8* hs;
+    RC(ctx_hstage(ctx, head, &hs));
+    memset(hs, 0, head);
+    D.table_set = 0;
+    memcpy(hs + o_desc, &D, sizeof(D));
+    memcpy(hs + o_tab, &T, sizeof(T));
+    const u32 ioff[2] = {0u, (u32)D.nint};
+    memcpy(hs + o_ioff, ioff, sizeof(ioff));
+    u8* sm = (u8*)ctx->small.p;
+    CBV_HIP(ctx, hipMemcpyAsync(sm, hs, head, hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipMemcpyAsync(ctx->in.p, data, n, hipMemcpyHostToDevice, ctx->stream));
+    JpegBatch B;
+    B.data = (const u8*)ctx->in.p;
+    B.data_stride = 0;
+    B.descs = (const JpegDesc*)(sm + o_desc);
+    B.tables = (const JpegTables*)(sm + o_tab);
+    B.ioff = (const u32*)(sm + o_ioff);
+    B.mpos = (u32*)(sm + o_mpos);
+    B.nfound = (int*)(sm + o_nfound);
+    B.status = (int*)(sm + o_status);
+    B.coef = (int16_t*)ctx->a.p;
+    B.coef_stride = D.plane_total;
+    B.planes = (u8*)ctx->b.p;
+    B.plane_stride = D.plane_total;
+    B.bgr = bgr_dev;
+    B.bgr_stride = g.stride;
+    B.bgr_frame_stride = g.frame_stride;
+    B.nframes = 1;
+    *Bout = B;
+    return launch_jpeg_decode(ctx, B, (u32)D.nint, D.dri != 0, D.plane_total / 64u, D.w, D.h);
+}
+
+extern "C" int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes,
+                               int32_t* status)
+{
+    const char* who = "cbv_jpeg_decode";
+    if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
+    if (!data || !bgr || !status) return cbv_fail(ctx, CBV_ERR_ARG, "%s: null argument", who);
+    JpegDesc D;
+    JpegTables T;
+    RC(jpeg_header(ctx, who, data, n, &D, &T));
+    if (stride < D.w * 3) return cbv_fail(ctx, CBV_ERR_ARG, "%s: stride %d below the %d bytes of a row", who, stride, D.w * 3);
+    if (D.h > 65535) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: %d rows", who, D.h);
+    CBV_ENTER(ctx);
+    const Geom g = tight_geom(D.w, D.h);
+    JpegBatch B;
+    RC(jpeg_single_dev(ctx, data, n, D, T, nullptr, g, &B));
+    int st = 0;
+    CBV_HIP(ctx, hipMemcpyAsync(&st, B.status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (coef) CBV_HIP(ctx, hipMemcpyAsync(coef, B.coef, (size_t)D.plane_total * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (planes) CBV_HIP(ctx, hipMemcpyAsync(planes, B.planes, D.plane_total, hipMemcpyDeviceToHost, ctx->stream));
+    if (stride == g.stride) CBV_HIP(ctx, hipMemcpyAsync(bgr, B.bgr, (size_t)g.stride * D.h, hipMemcpyDeviceToHost, ctx->stream));
+    else CBV_HIP(ctx, hipMemcpy2DAsync(bgr, stride, B.bgr, g.stride, g.stride, D.h, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *status = st;
+    return CBV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The pipeline's Motion-JPEG ingest (cbv_pipeline_set_input_format(p, CBV_FMT_MJPEG)).  The host ring holds one stream per
+// slot, `lengths` says how many bytes of each slot are used.  cbv_pipeline_submit parses the slots' headers out of the
+// pinned ring (a few hundred bytes each; the entropy data is never read on the host), copies the used bytes and enqueues the
+// decode on the copy stream behind the copy, CHUNK frames at a time through one set of scratch buffers.
+// ---------------------------------------------------------------------------------------------------------------------
+struct JpegState {
+    enum { CHUNK = 8, NSETS = 16 };
+    // pinned, with the slots' lifetime
+    u32* h_lengths = nullptr;   // [max_frames], the capture side's
+    JpegDesc* h_desc = nullptr; // [max_frames]
+    u32* h_ioff = nullptr;      // [2 * max_frames]: the chunk that starts at slot s has its prefix sums at 2 s
+    JpegTables* h_tabs = nullptr; // [NSETS] the table sets seen, by content
+    int nsets = 0;
+    // device
+    JpegDesc* d_desc = nullptr;
+    u32* d_ioff = nullptr;
+    JpegTables* d_tabs = nullptr;
+    int* d_status = nullptr; // [max_frames]
+    int* d_nfound = nullptr; // [max_frames]
+    u32* d_mpos = nullptr;   // [CHUNK * max_intervals]
+    int16_t* d_coef = nullptr; // [CHUNK][frame_elems]
+    u8* d_planes = nullptr;
+    size_t frame_elems = 0;
+};
+
+size_t pipeline_jpeg_default_slot_bytes(int w, int h) { return (((size_t)w * h + 1) / 2 + 255) & ~(size_t)255; }
+
+void pipeline_jpeg_free(Pipe& P)
+{
+    JpegState* J = P.jpeg;
+    if (!J) return;
+    if (J->h_lengths) (void)hipHostFree(J->h_lengths);
+    if (J->h_desc) (void)hipHostFree(J->h_desc);
+    if (J->h_ioff) (void)hipHostFree(J->h_ioff);
+    if (J->h_tabs) (void)hipHostFree(J->h_tabs);
+    void* dev[] = {J->d_desc, J->d_ioff, J->d_tabs, J->d_status, J->d_nfound, J->d_mpos, J->d_coef, J->d_planes};
+    for (void* q : dev)
+        if (q) (void)hipFree(q);
+    delete J;
+    P.jpeg = nullptr;
+}
+
+// the decode's scratch, sized once for CHUNK frames of the pipeline's size in the sampling that needs most (4:4:4 padded to
+// the 16 x 16 MCUs of 4:2:0) and a restart interval of one MCU
+int pipeline_jpeg_ensure(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    if (P.jpeg) return CBV_OK;
+    if (P.h > 65535) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "Motion-JPEG frames of %d rows", P.h);
+    JpegState* J = new JpegState;
+    P.jpeg = J;
+    const size_t n = (size_t)P.max_frames;
+    const size_t pw = ((size_t)P.w + 15) & ~(size_t)15, ph = ((size_t)P.h + 15) & ~(size_t)15;
+    J->frame_elems = 3 * pw * ph;
+    const size_t max_int = ((size_t)P.w + 7) / 8 * (((size_t)P.h + 7) / 8);
+    bool ok = hipHostMalloc((void**)&J->h_lengths, n * sizeof(u32), hipHostMallocDefault) == hipSuccess &&
+              hipHostMalloc((void**)&J->h_desc, n * sizeof(JpegDesc), hipHostMallocDefault) == hipSuccess &&
+              hipHostMalloc((void**)&J->h_ioff, 2 * n * sizeof(u32), hipHostMallocDefault) == hipSuccess &&
+              hipHostMalloc((void**)&J->h_tabs, JpegState::NSETS * sizeof(JpegTables), hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void**)&J->d_desc, n * sizeof(JpegDesc)) == hipSuccess && hipMalloc((void**)&J->d_ioff, 2 * n * sizeof(u32)) == hipSuccess &&
+              hipMalloc((void**)&J->d_tabs, JpegState::NSETS * sizeof(JpegTables)) == hipSuccess &&
+              hipMalloc((void**)&J->d_status, n * sizeof(int)) == hipSuccess && hipMalloc((void**)&J->d_nfound, n * sizeof(int)) == hipSuccess &&
+              hipMalloc((void**)&J->d_mpos, JpegState::CHUNK * max_int * sizeof(u32)) == hipSuccess &&
+              hipMalloc((void**)&J->d_coef, JpegState::CHUNK * J->frame_elems * sizeof(int16_t)) == hipSuccess &&
+              hipMalloc((void**)&J->d_planes, JpegState::CHUNK * J->frame_elems) == hipSuccess;
+    if (ok) ok = hipMemset(J->d_status, 0, n * sizeof(int)) == hipSuccess;
+    if (!ok) {
+        pipeline_jpeg_free(P);
+        return cbv_fail(ctx, CBV_ERR_HIP, "the Motion-JPEG decode's buffers could not be allocated");
+    }
+    memset(J->h_lengths, 0, n * sizeof(u32));
+    return CBV_OK;
+}
+
+// a stream's header against the pipeline: its size, and a table set for it (one of the cache, or a new one at *new_sets)
+static int jpeg_slot_header(Pipe& P, const char* who, int slot, const u8* data, size_t n, JpegDesc* D)
+{
+    cbv_ctx* ctx = P.ctx;
+    JpegState* J = P.jpeg;
+    JpegTables T;
+    char msg[200];
+    const int rc = jpeg_parse_header(data, n, D, &T, msg, sizeof(msg));
+    if (rc) return cbv_fail(ctx, rc, "%s: slot %d: %s", who, slot, msg);
+    if (D->w != P.w || D->h != P.h)
+        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: slot %d: a %d x %d frame, the pipeline's are %d x %d", who, slot, D->w, D->h, P.w, P.h);
+    int k = 0;
+    while (k < J->nsets && memcmp(&J->h_tabs[k], &T, sizeof(T))) k++;
+    if (k == J->nsets) {
+        if (k == JpegState::NSETS) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: slot %d: more than %d different table sets in flight", who, slot, k);
+        memcpy(&J->h_tabs[k], &T, sizeof(T));
+        J->nsets++;
+    }
+    D->table_set = k;
+    return CBV_OK;
+}
+
+// cbv_pipeline_submit with the Motion-JPEG format: called under the context's lock with the copy stream made; read_ev = what the
+// writes into the frame ring wait for (may be null)
+int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
+{
+    cbv_ctx* ctx = P.ctx;
+    JpegState* J = P.jpeg;
+    const char* who = "cbv_pipeline_submit";
+    const size_t sb = P.jpeg_slot_bytes;
+    if (J->nsets == JpegState::NSETS) { // the cache is full: start again once nothing reads it
+        CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+        J->nsets = 0;
+    }
+    const int sets_before = J->nsets;
+    // 1. every header, before anything is enqueued
+    for (int s = slot0; s < slot0 + count; s++) {
+        const u32 len = J->h_lengths[s];
+        int rc = CBV_OK;
+        if (len == 0 || len > sb) rc = cbv_fail(ctx, CBV_ERR_ARG, "%s: slot %d: length %u, a slot holds %zu bytes", who, s, len, sb);
+        else rc = jpeg_slot_header(P, who, s, P.host_ring + sb * s, len, &J->h_desc[s]);
+        if (rc) {
+            J->nsets = sets_before;
+            return rc;
+        }
+    }
+    for (int c0 = 0; c0 < count; c0 += JpegState::CHUNK) {
+        const int s = slot0 + c0, cf = std::min<int>(JpegState::CHUNK, count - c0);
+        u32 acc = 0;
+        for (int i = 0; i < cf; i++) {
+            J->h_ioff[2 * s + i] = acc;
+            acc += (u32)J->h_desc[s + i].nint;
+        }
+        J->h_ioff[2 * s + cf] = acc;
+    }
+    // 2. the used bytes of every slot, the descriptors, the new table sets
+    for (int s = slot0; s < slot0 + count; s++) {
+        const size_t bytes = std::min(sb, ((size_t)J->h_lengths[s] + 255) & ~(size_t)255);
+        CBV_HIP(ctx, hipMemcpyAsync(P.raw_ring + sb * s, P.host_ring + sb * s, bytes, hipMemcpyHostToDevice, P.copy_stream));
+    }
+    CBV_HIP(ctx, hipMemcpyAsync(J->d_desc + slot0, J->h_desc + slot0, (size_t)count * sizeof(JpegDesc), hipMemcpyHostToDevice, P.copy_stream));
+    CBV_HIP(ctx, hipMemcpyAsync(J->d_ioff + 2 * slot0, J->h_ioff + 2 * slot0, (size_t)2 * count * sizeof(u32), hipMemcpyHostToDevice, P.copy_stream));
+    if (J->nsets > sets_before)
+        CBV_HIP(ctx, hipMemcpyAsync(J->d_tabs + sets_before, J->h_tabs + sets_before, (size_t)(J->nsets - sets_before) * sizeof(JpegTables),
+                                    hipMemcpyHostToDevice, P.copy_stream));
+    if (read_ev) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, read_ev, 0));
+    // 3. the decode, a chunk of frames at a time through the one set of scratch buffers (stream order keeps them apart)
+    hipStream_t caller = ctx->stream;
+    ctx->stream = P.copy_stream;
+    int rc = CBV_OK;
+    for (int c0 = 0; c0 < count && !rc; c0 += JpegState::CHUNK) {
+        const int s = slot0 + c0, cf = std::min<int>(JpegState::CHUNK, count - c0);
+        JpegBatch B;
+        B.data = P.raw_ring + sb * s;
+        B.data_stride = sb;
+        B.descs = J->d_desc + s;
+        B.tables = J->d_tabs;
+        B.ioff = J->d_ioff + 2 * s;
+        B.mpos = J->d_mpos;
+        B.nfound = J->d_nfound + s;
+        B.status = J->d_status + s;
+        B.coef = J->d_coef;
+        B.coef_stride = J->frame_elems;
+        B.planes = J->d_planes;
+        B.plane_stride = J->frame_elems;
+        B.bgr = P.frames + P.g.frame_stride * s;
+        B.bgr_stride = P.g.stride;
+        B.bgr_frame_stride = P.g.frame_stride;
+        B.nframes = cf;
+        int any_dri = 0;
+        u32 max_blocks = 0;
+        for (int i = 0; i < cf; i++) {
+            any_dri |= J->h_desc[s + i].dri != 0;
+            max_blocks = std::max(max_blocks, J->h_desc[s + i].plane_total / 64u);
+        }
+        rc = launch_jpeg_decode(ctx, B, J->h_ioff[2 * s + cf], any_dri, max_blocks, P.w, P.h);
+    }
+    ctx->stream = caller;
+    return rc;
+}
+
+extern "C" uint32_t* cbv_pipeline_host_jpeg_lengths(cbv_pipeline* p)
+{
+    if (!p || attached(p) || !p->pipe->jpeg) return nullptr;
+    return p->pipe->jpeg->h_lengths;
+}
+
+extern "C" int cbv_pipeline_jpeg_status(cbv_pipeline* p, int slot0, int count, int32_t* out)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_pipeline_jpeg_status: the pipeline is null");
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_jpeg_status: frames go to the parent of a board");
+    if (!out || slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_jpeg_status: bad slot range");
+    if (!P.jpeg) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_jpeg_status: no Motion-JPEG frame was ever given to the pipeline");
+    CBV_ENTER(ctx);
+    if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+    CBV_HIP(ctx, hipMemcpy(out, P.jpeg->d_status + slot0, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_set_jpeg_slot_bytes(cbv_pipeline* p, size_t bytes)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_pipeline_set_jpeg_slot_bytes: the pipeline is null");
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_set_jpeg_slot_bytes: frames go to the parent of a board");
+    if (bytes < 256 || bytes > ((size_t)1 << 30)) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_set_jpeg_slot_bytes: %zu bytes", bytes);
+    P.jpeg_slot_bytes = (bytes + 255) & ~(size_t)255;
+    if (P.in_fmt != CBV_FMT_MJPEG) return CBV_OK;
+    return cbv_pipeline_set_input_format(p, CBV_FMT_MJPEG); // frees both rings, as a format change does
+}
+
+extern "C" int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t* data, size_t n)
+{
+    const char* who = "cbv_pipeline_upload_jpeg";
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the pipeline is null", who);
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who);
+    if (!data || slot < 0 || slot >= P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
+    JpegDesc D;
+    JpegTables T;
+    char msg[200];
+    const int rc = jpeg_parse_header(data, n, &D, &T, msg, sizeof(msg));
+    if (rc) return cbv_fail(ctx, rc, "%s: %s", who, msg);
+    if (D.w != P.w || D.h != P.h) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: a %d x %d frame, the pipeline's are %d x %d", who, D.w, D.h, P.w, P.h);
+    CBV_ENTER(ctx);
+    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the pipeline's frames are its raw ring (raw mode); it has no BGR frames to decode into", who);
+    RC(pipeline_jpeg_ensure(P));
+    RC(join_scan(P)); // lanes and scan of the last run
+    if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // a submitted decode of this slot lands first
+    JpegBatch B;
+    RC(jpeg_single_dev(ctx, data, n, D, T, P.frames + P.g.frame_stride * slot, P.g, &B));
+    CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_status + slot, B.status, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_OK;
+}

@@ -183,7 +183,7 @@ int pipeline_tables(Pipe& P)
 int pipeline_frame_ring(Pipe& P)
 {
     cbv_ctx* ctx = P.ctx;
-    const bool want = !(P.configured_raw_profile() && P.in_fmt != CBV_FMT_BGR);
+    const bool want = !(P.configured_raw_profile() && P.fmt_is_raw());
     if (want && !P.frames) {
         const size_t bytes = P.g.frame_stride * P.max_frames;
         if (hipMalloc((void**)&P.frames, bytes + 256) != hipSuccess) {
@@ -392,6 +392,7 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     for (auto& c : P->copies) (void)hipEventDestroy(c.ev);
     if (P->host_ring) (void)hipHostFree(P->host_ring);
     if (P->raw_ring) (void)hipFree(P->raw_ring);
+    pipeline_jpeg_free(*P);
     if (P->frames) (void)hipFree(P->frames);
     if (P->enhanced) (void)hipFree(P->enhanced);
     dev_free(&P->d_synth);

@@ -97,6 +97,10 @@ struct Pipe {
     // Without enhancement (skip_enhance 1 or CBV_SKIP_ENHANCE_PROFILE_RAW) a YUV or Bayer input format makes the raw ring THE frames: k_warp_yuv /
     // k_warp_bayer / k_warp_raw_profile samples it, nothing is converted and `frames` is neither written nor read (raw_mode below).
     u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated on first use; null with CBV_FMT_BGR
+    // Motion-JPEG (CBV_FMT_MJPEG): both rings hold one JPEG stream per slot, jpeg_slot_bytes apart, and the decode writes
+    // `frames` behind the copy (cbv_jpeg.cpp); never raw mode, the BGR ring stays
+    struct JpegState* jpeg = nullptr;
+    size_t jpeg_slot_bytes = 0;
     hipStream_t copy_stream = nullptr;
     struct CopyRec {
         int s0, cnt;
@@ -141,7 +145,8 @@ struct Pipe {
     int max_px = 0, max_S = 0;
     Board& b0() const { return boards[0]->b; }
     bool configured_raw_profile() const { return skip_enhance && profile_raw; }
-    bool raw_mode() const { return skip_enhance && (!profile_only || profile_raw) && in_fmt != CBV_FMT_BGR; }
+    bool fmt_is_raw() const { return in_fmt != CBV_FMT_BGR && in_fmt != CBV_FMT_MJPEG; } // a YUV or Bayer format
+    bool raw_mode() const { return skip_enhance && (!profile_only || profile_raw) && fmt_is_raw(); }
 };
 // cbv_pipeline.cpp: board handles, the ordering of the runs in flight, the boards' kernel arguments, read-backs
 bool attached(const cbv_pipeline* p);
@@ -158,3 +163,8 @@ int pipeline_update_region(Pipe& P);
 int pipeline_readback(Pipe& P, void* out, const void* dev, size_t bytes);
 // cbv_pipeline_ingest.cpp
 RawPlanes slot_planes(const Pipe& P, int slot);
+// cbv_jpeg.cpp: the Motion-JPEG ingest
+size_t pipeline_jpeg_default_slot_bytes(int w, int h);
+int pipeline_jpeg_ensure(Pipe& P);
+void pipeline_jpeg_free(Pipe& P);
+int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev);

@@ -12,12 +12,19 @@ RawPlanes slot_planes(const Pipe& P, int slot)
     return tight_raw_planes(P.in_fmt, P.w, P.h, P.raw_ring + tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride * slot);
 }
 
-// the device ring of raw frames in the current (YUV) input format
+// bytes between the slots of the ingest rings in the current input format
+static size_t host_slot_bytes(const Pipe& P)
+{
+    if (P.in_fmt == CBV_FMT_MJPEG) return P.jpeg_slot_bytes;
+    return P.in_fmt == CBV_FMT_BGR ? P.g.frame_stride : tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride;
+}
+
+// the device ring of raw frames (or of JPEG streams) in the current input format
 static int ensure_raw_ring(Pipe& P)
 {
     cbv_ctx* ctx = P.ctx;
     if (P.raw_ring) return CBV_OK;
-    const size_t bytes = tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride * P.max_frames;
+    const size_t bytes = host_slot_bytes(P) * P.max_frames;
     if (hipMalloc((void**)&P.raw_ring, bytes + 256) != hipSuccess) {
         P.raw_ring = nullptr;
         return cbv_fail(ctx, CBV_ERR_HIP, "device ring of %zu bytes for the raw frames could not be allocated", bytes);
@@ -70,8 +77,6 @@ extern "C" int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_
     return CBV_OK;
 }
 
-// bytes between the slots of the ingest rings in the current input format
-static size_t host_slot_bytes(const Pipe& P) { return P.in_fmt == CBV_FMT_BGR ? P.g.frame_stride : tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride; }
 
 extern "C" size_t cbv_pipeline_host_slot_bytes(cbv_pipeline* p)
 {
@@ -86,8 +91,12 @@ extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
     Pipe& P = *p->pipe;
     cbv_ctx* ctx = P.ctx;
     if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_set_input_format: frames go to the parent of a board");
-    if (fmt != CBV_FMT_BGR) RC(check_raw_format(ctx, fmt, P.w, P.h, "cbv_pipeline_set_input_format"));
+    if (fmt != CBV_FMT_BGR && fmt != CBV_FMT_MJPEG) RC(check_raw_format(ctx, fmt, P.w, P.h, "cbv_pipeline_set_input_format"));
     CBV_ENTER(ctx);
+    if (fmt == CBV_FMT_MJPEG) { // the decode's scratch is sized here, once: cbv_pipeline_submit never allocates
+        RC(pipeline_jpeg_ensure(P));
+        if (!P.jpeg_slot_bytes) P.jpeg_slot_bytes = pipeline_jpeg_default_slot_bytes(P.w, P.h);
+    }
     // the copies and conversions in flight read the rings that go away here (both run on the copy stream)
     if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
     if (P.raw_mode()) { // ... and so do the runs in flight
@@ -138,7 +147,9 @@ extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
     // do not overwrite device slots a run that is still in flight reads: ANY such run, not only the last one
     retire_runs(P);
     Pipe::RunRec* reader = newest_run(P, slot0, count, 0);
-    if (P.in_fmt == CBV_FMT_BGR) {
+    if (P.in_fmt == CBV_FMT_MJPEG) {
+        RC(pipeline_jpeg_submit(P, slot0, count, reader ? (reader->one_event ? reader->scan_ev : reader->lanes_ev) : nullptr));
+    } else if (P.in_fmt == CBV_FMT_BGR) {
         if (reader) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, reader->one_event ? reader->scan_ev : reader->lanes_ev, 0));
         CBV_HIP(ctx, hipMemcpyAsync(P.frames + P.g.frame_stride * slot0, P.host_ring + P.g.frame_stride * slot0,
                                     P.g.frame_stride * count, hipMemcpyHostToDevice, P.copy_stream));

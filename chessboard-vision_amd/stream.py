@@ -734,6 +734,10 @@ class BoardPipeline(_BoardMethods):
         "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg" (one [h, w] array, named by the top-left 2 x 2 block:
         cv2's COLOR_BayerBG2BGR is "bayer_rggb"); in raw mode (`configure(enhance=False)` or `(enhance="profile", raw=True)` with a YUV or Bayer
         `set_input_format`) the frame is stored as it is."""
+        if isinstance(fmt, str) and fmt.lower() == "mjpeg":  # one baseline JPEG stream (bytes or a uint8 array), decoded on the GPU
+            a = np.frombuffer(frame, np.uint8) if isinstance(frame, (bytes, bytearray, memoryview)) else np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
+            self.ctx.check(self.ctx.lib.cbv_pipeline_upload_jpeg(self.h_, slot, N.ptr(a), a.size))
+            return
         if N.format_id(fmt) == N.FMT_BGR:
             f = N.as_bgr(frame)
             assert f.shape[:2] == (self.h, self.w)
@@ -744,12 +748,23 @@ class BoardPipeline(_BoardMethods):
             raise ValueError("a %dx%d %s frame does not fit the pipeline's %dx%d frames" % (w, h, fmt, self.w, self.h))
         self.ctx.check(self.ctx.lib.cbv_pipeline_upload_raw(self.h_, slot, raw))
 
-    def set_input_format(self, fmt):
+    def set_input_format(self, fmt, slot_bytes=None):
         """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12", "nv21", "yuv420p"
         (cv2's I420; "i420" itself is an unknown format), "yv12", "yuyv", "yvyu", "uyvy", or an 8-bit Bayer mosaic
         "bayer_rggb", "bayer_bggr", "bayer_grbg" or "bayer_gbrg" (w and h even and at least 4).  Raw frames cross PCIe as
         they are and are converted to BGR on the GPU behind their copy.  The ring is freed here and
-        allocated again by the next `host_ring()`: an array that call returned earlier must not be touched any more."""
+        allocated again by the next `host_ring()`: an array that call returned earlier must not be touched any more.
+        "mjpeg": a slot holds one baseline JPEG stream (a Motion-JPEG frame) of up to `slot_bytes` bytes (default w * h / 2,
+        rounded up to 256), its length goes into `jpeg_lengths()`, and `submit` copies only the used bytes and decodes them on
+        the GPU into the BGR frames (include/cbv.h, CBV_FMT_MJPEG)."""
+        if isinstance(fmt, str) and fmt.lower() == "mjpeg":
+            if slot_bytes is not None:
+                self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_slot_bytes(self.h_, int(slot_bytes)))
+            self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.FMT_MJPEG))
+            self.input_format = "mjpeg"
+            return
+        if slot_bytes is not None:
+            raise ValueError("slot_bytes belongs to the \"mjpeg\" format")
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt)))
         self.input_format = fmt.lower()
 
@@ -758,7 +773,7 @@ class BoardPipeline(_BoardMethods):
         them to the GPU asynchronously.  [max_frames, h, w, 3] for BGR; [max_frames, h * 3 // 2, w] for the 4:2:0 layouts
         (luma rows, then the chroma rows of NV12 / NV21, or the two chroma planes of yuv420p / yv12 back to back, each
         h // 2 rows of w // 2 bytes); [max_frames, h, w, 2] for YUYV, YVYU and UYVY; [max_frames, h, w] for the Bayer
-        mosaics (`set_input_format`)."""
+        mosaics; [max_frames, slot_bytes] for "mjpeg" (`set_input_format`)."""
         ptr = self.ctx.lib.cbv_pipeline_host_ring(self.h_)
         if not ptr:
             raise RuntimeError(self.ctx.lib.cbv_last_error(self.ctx.h).decode())
@@ -766,6 +781,8 @@ class BoardPipeline(_BoardMethods):
         buf = (C.c_uint8 * (fs * self.max_frames)).from_address(ptr)
         flat = np.frombuffer(buf, dtype=np.uint8)
         w, h = self.w, self.h
+        if self.input_format == "mjpeg":
+            return flat.reshape(self.max_frames, fs)
         if self.input_format == "bgr":
             shape, strides = (h, w, 3), (w * 3, 3, 1)
         elif self.input_format in N.FORMATS_420:
@@ -775,6 +792,20 @@ class BoardPipeline(_BoardMethods):
         else:
             shape, strides = (h, w, 2), (w * 2, 2, 1)
         return np.lib.stride_tricks.as_strided(flat, shape=(self.max_frames,) + shape, strides=(fs,) + strides)
+
+    def jpeg_lengths(self):
+        """The pinned uint32 [max_frames] array of the streams' lengths in the "mjpeg" host ring; the capture side fills it."""
+        ptr = self.ctx.lib.cbv_pipeline_host_jpeg_lengths(self.h_)
+        if not ptr:
+            raise RuntimeError("the pipeline's input format was never \"mjpeg\"")
+        return np.frombuffer((C.c_uint32 * self.max_frames).from_address(ptr), dtype=np.uint32)
+
+    def jpeg_status(self, slot0, count):
+        """The status words of the streams last decoded into the slots (0, or _native.JPEG_BAD_CODE | JPEG_NO_DATA |
+        JPEG_RESTART for damaged entropy data, which decodes as far as it goes); waits for the submitted decodes."""
+        out = np.zeros(count, np.int32)
+        self.ctx.check(self.ctx.lib.cbv_pipeline_jpeg_status(self.h_, slot0, count, N.ptr(out)))
+        return out
 
     def submit(self, slot0, count):
         """Enqueue host ring -> device ring for the slots; run() of those slots waits for the copy."""

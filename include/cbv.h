@@ -595,6 +595,92 @@ CBV_API int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt);
 CBV_API size_t cbv_pipeline_host_slot_bytes(cbv_pipeline* p);
 
 /* ------------------------------------------------------------------ */
+/* Motion-JPEG frames: baseline JPEG decoded on the GPU                */
+/* ------------------------------------------------------------------ */
+/* CBV_FMT_MJPEG 0x08: one frame is one JPEG stream as a camera emits it (a UVC webcam at 1080p, an IP camera, AVI MJPEG).
+ * The single-frame entry points below decode it, and cbv_pipeline_set_input_format takes it as the format of the ingest ring.
+ *
+ * Accepted: SOF0 (baseline, Huffman, 8-bit samples); one interleaved scan; three components YCbCr with luma sampling
+ * 1x1 / 2x1 / 2x2 and chroma 1x1 (4:4:4, 4:2:2, 4:2:0), or one gray component; 8-bit DQT, ids 0..3; up to two DC and two AC
+ * tables, several per DHT segment; NO DHT AT ALL = the typical tables of T.81 Annex K.3 (UVC cameras and AVI MJPEG omit
+ * them; ids DC 0 / AC 0 luminance, DC 1 / AC 1 chrominance); DRI with any interval; APPn, COM and other segments with a
+ * length, skipped; fill 0xFF bytes before a marker; any w, h >= 1 with w * h <= 2^28, partial MCUs cropped.
+ * CBV_ERR_UNSUPPORTED, the message naming the reason: progressive, arithmetic, extended or lossless SOFs, 12-bit samples,
+ * a 16-bit DQT, a scan that does not hold every component (several scans), four components, an Adobe marker with
+ * transform 0, any other sampling, a Huffman table id above 1.  CBV_ERR_ARG: a malformed header.
+ *
+ * Samples, as libjpeg computes them with its defaults (JDCT_ISLOW, fancy upsampling; what cv2.imdecode calls):
+ *   IDCT      jidctint's slow-integer transform on dequantised coefficients: CONST_BITS 13, PASS1_BITS 2, constants 2446,
+ *             3196, 4433, 6270, 7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172; columns first with descale 11, rows
+ *             with descale 18, DESCALE(x, n) = (x + 2^(n-1)) >> n; sample = clamp(x + 128, 0, 255); int32 arithmetic.
+ *             libjpeg's range-limit table WRAPS for x outside [-512, 511]; this definition is the clamp and does not follow
+ *             the wrap.  No stream encoded from 8-bit pixels gets near it.
+ *   upsample  the "fancy" triangle filter on the component's true size ceil(w * hs / hmax) x ceil(h * vs / vmax), edges
+ *             replicated.  h2v1: out[2i] = (3 p[i] + p[i-1] + 1) >> 2, out[2i+1] = (3 p[i] + p[i+1] + 2) >> 2.  h2v2: the
+ *             column sum s = 3 p[row] + p[nearer row] (the row above for even output rows, below for odd ones), then
+ *             (3 s[i] + s[i-1] + 8) >> 4 and (3 s[i] + s[i+1] + 7) >> 4.  A chroma component whose true width is 1 or 2
+ *             (w <= 4) is not filtered but replicated, 2 x 1 or 2 x 2: libjpeg-turbo does so, and its bytes are the pin.
+ *   colour    with cb, cr less 128 and F(c) = int(c * 65536 + 0.5): R = y + ((F(1.402) cr + 32768) >> 16),
+ *             B = y + ((F(1.772) cb + 32768) >> 16), G = y + ((-F(0.34414) cb - F(0.71414) cr + 32768) >> 16), each
+ *             clamped.  A gray stream gives B = G = R = Y, as imdecode(IMREAD_COLOR) does.
+ *
+ * Damaged entropy data never fails a call and never leaves bounds.  The frame decodes by restart interval (the whole
+ * frame without DRI); an interval's bytes end at its restart marker, reads past them return zero bits, decoding of an
+ * interval stops at its first bad code, and the coefficients not decoded are 0.  *status gets CBV_JPEG_BAD_CODE (a bit
+ * pattern that is no code, a DC size above 15, a run past coefficient 63), CBV_JPEG_NO_DATA (an interval used bits past
+ * its end) and CBV_JPEG_RESTART (the number of restart markers is not intervals - 1, or they do not count 0..7 in cycles;
+ * intervals whose marker is missing have no data). */
+#define CBV_FMT_MJPEG 0x08
+#define CBV_JPEG_BAD_CODE 1
+#define CBV_JPEG_NO_DATA 2
+#define CBV_JPEG_RESTART 4
+typedef struct {
+    int32_t w, h;
+    int32_t components;        /* 1 or 3 */
+    int32_t hs, vs;            /* luma sampling: 1,1 (4:4:4, gray) 2,1 (4:2:2) 2,2 (4:2:0) */
+    int32_t restart_interval;  /* MCUs, 0 = none */
+    int32_t intervals;         /* restart intervals of the frame, 1 without DRI */
+    int32_t std_tables;        /* 1: the stream has no DHT */
+    uint32_t entropy_offset, entropy_length; /* from the byte behind SOS to the end of the stream */
+    /* Stage outputs: samples of all component planes, each padded to whole MCUs, back to back (Y, Cb, Cr).  Component c
+     * is blocks_w[c] x blocks_h[c] blocks; its plane has rows of blocks_w[c] * 8 bytes, and its coefficients are
+     * [block row][block column][64] int16 in natural (row-major) order at the same element offset. */
+    uint32_t plane_elems;
+    int32_t blocks_w[3], blocks_h[3];
+} cbv_jpeg_info;
+/* the header of a stream, up to SOS; host only, reads no entropy data */
+CBV_API int cbv_jpeg_probe(const uint8_t* data, size_t n, cbv_jpeg_info* info);
+/* The host twin: the same bodies as the kernels, serial, no GPU.  bgr = h rows of w * 3 bytes `stride` apart; coef
+ * (int16[plane_elems]) and planes (uint8[plane_elems]) may be NULL. */
+CBV_API int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes, int32_t* status);
+/* the same on the GPU: the single-frame call and the stage entry point */
+CBV_API int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes,
+                            int32_t* status);
+/* The ingest ring in Motion-JPEG: cbv_pipeline_set_input_format(p, CBV_FMT_MJPEG).  A slot of the host ring holds one
+ * stream from its first byte; cbv_pipeline_host_slot_bytes is the capacity of a slot, w * h / 2 rounded up to 256 unless
+ * cbv_pipeline_set_jpeg_slot_bytes set another (rounded up to 256; with the format set it frees both rings, as a format
+ * change does).  The capture side writes a stream's length into its entry of cbv_pipeline_host_jpeg_lengths (a pinned
+ * uint32[max_frames] that lives as long as the pipeline; NULL before the format was first set).
+ * cbv_pipeline_submit then parses the headers of the slots straight from the pinned ring (it never reads the entropy
+ * data).  On the first slot it cannot take it returns that slot's error, the message naming the slot, with nothing
+ * enqueued: a length of 0 or above the capacity (CBV_ERR_ARG), a malformed or unsupported stream (as above), a size that
+ * differs from the pipeline's (CBV_ERR_UNSUPPORTED), more than 16 different table sets (Huffman and quantisation tables, by
+ * content) since the cache was last emptied (CBV_ERR_UNSUPPORTED; a camera's tables do not change).  Otherwise it copies no
+ * more than each slot's used bytes (rounded up to 256) and enqueues the decode into the BGR frame ring on the copy stream
+ * behind the copy, with the ordering promises of the other formats.  Frames of different sampling and restart interval may
+ * share a submit.  The decode's device scratch is sized when the format is set, for chunks of 8 frames in the sampling that
+ * needs most; submit allocates nothing.  Motion-JPEG is never raw mode: a pipeline without enhancement keeps its BGR ring, as
+ * for BGR input, and the decode fills it.  Until the copy has completed (cbv_pipeline_wait_submitted) the slots' bytes and
+ * lengths belong to it. */
+CBV_API uint32_t* cbv_pipeline_host_jpeg_lengths(cbv_pipeline* p);
+CBV_API int cbv_pipeline_set_jpeg_slot_bytes(cbv_pipeline* p, size_t bytes);
+/* one stream decoded into a slot of the frame ring, synchronous, like cbv_pipeline_upload; in any input format but not in
+ * raw mode (CBV_ERR_STATE) */
+CBV_API int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t* data, size_t n);
+/* the status words (CBV_JPEG_*) of the streams last decoded into the slots; waits for the submitted decodes */
+CBV_API int cbv_pipeline_jpeg_status(cbv_pipeline* p, int slot0, int count, int32_t* status);
+
+/* ------------------------------------------------------------------ */
 /* several boards seen by one camera                                   */
 /* ------------------------------------------------------------------ */
 /* A configured pipeline holds up to CBV_MAX_BOARDS boards; the pipeline itself is board 0.  Extra boards share its frame
