@@ -293,6 +293,13 @@ class JpegInfo(C.Structure):
                 ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3)]
 
 
+JPEG_ENTROPY = {"auto": 0, "interval": 1, "pieces": 2}  # CBV_JPEG_ENTROPY_*
+
+
+class JpegDecodeStats(C.Structure):
+    _fields_ = [("pieces", C.c_uint32), ("rounds", C.c_uint32), ("settled_round0", C.c_uint32)]
+
+
 KERNEL_IDS = ["COLOR_LAB_HIST", "CLAHE_LUT", "CLAHE_APPLY", "BILATERAL", "SHARPEN", "NORM_LUT", "NORMALIZE", "WARP",
               "SQUARES", "GRAY_BLUR", "OTSU", "THRESHOLD", "SCAN", "SYNTH", "RESET", "HOUGH", "INGEST"]
 K = {name: i for i, name in enumerate(KERNEL_IDS)}
@@ -431,6 +438,10 @@ def load():
         "cbv_pipeline_set_jpeg_slot_bytes": (i32, [vp, C.c_size_t]),
         "cbv_pipeline_upload_jpeg": (i32, [vp, i32, vp, C.c_size_t]),
         "cbv_pipeline_jpeg_status": (i32, [vp, i32, i32, vp]),
+        "cbv_jpeg_decode_host_ex": (i32, [vp, C.c_size_t, u8p, i32, vp, vp, P(C.c_int32), i32, C.c_uint32, P(JpegDecodeStats)]),
+        "cbv_jpeg_decode_ex": (i32, [vp, vp, C.c_size_t, u8p, i32, vp, vp, P(C.c_int32), i32, C.c_uint32, P(JpegDecodeStats)]),
+        "cbv_pipeline_set_jpeg_entropy": (i32, [vp, i32, C.c_uint32]),
+        "cbv_pipeline_jpeg_stats": (i32, [vp, i32, i32, vp]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

@@ -152,25 +152,34 @@ def jpeg_probe(data):
     return d
 
 
-def jpeg_decode(data, host=False):
+def jpeg_decode(data, host=False, entropy="auto", piece_bytes=0, stats=False):
     """One baseline JPEG stream with its stage outputs: (bgr [h, w, 3], coef int16 [plane_elems], planes uint8 [plane_elems],
-    status).  On the GPU (cbv_jpeg_decode), or with host=True by the library's host twin (cbv_jpeg_decode_host, no GPU): the
-    same bodies, byte for byte.  The layout of coef and planes: jpeg_probe(data)["blocks"] and include/cbv.h.  status:
-    _native.JPEG_BAD_CODE | JPEG_NO_DATA | JPEG_RESTART, 0 for an undamaged stream."""
+    status).  On the GPU (cbv_jpeg_decode_ex), or with host=True by the library's host twin (cbv_jpeg_decode_host_ex, no
+    GPU): the same bodies, byte for byte.  The layout of coef and planes: jpeg_probe(data)["blocks"] and include/cbv.h.
+    status: _native.JPEG_BAD_CODE | JPEG_NO_DATA | JPEG_RESTART, 0 for an undamaged stream.  entropy: "auto" (pieces for a
+    stream without DRI, restart intervals otherwise), "interval" or "pieces", and piece_bytes the piece size (0: the
+    default, otherwise a multiple of 4); neither changes the result.  stats=True appends a dict with pieces, rounds and
+    settled_round0 (zeros for a stream decoded by interval)."""
     a = _jpeg_bytes(data)
     info = jpeg_probe(a)
     bgr = np.empty((info["h"], info["w"], 3), np.uint8)
     coef = np.empty(info["plane_elems"], np.int16)
     planes = np.empty(info["plane_elems"], np.uint8)
     st = C.c_int32()
+    ps = N.JpegDecodeStats()
+    mode = N.JPEG_ENTROPY[entropy]
     if host:
         lib = N.load()
-        rc = lib.cbv_jpeg_decode_host(N.ptr(a), a.size, N.ptr(bgr), info["w"] * 3, N.ptr(coef), N.ptr(planes), C.byref(st))
+        rc = lib.cbv_jpeg_decode_host_ex(N.ptr(a), a.size, N.ptr(bgr), info["w"] * 3, N.ptr(coef), N.ptr(planes), C.byref(st), mode, int(piece_bytes),
+                                         C.byref(ps))
         if rc != 0:
             raise RuntimeError("libcbv_hip: %s (code %d)" % (lib.cbv_last_error(None).decode(), rc))
     else:
         ctx = N.context()
-        ctx.check(ctx.lib.cbv_jpeg_decode(ctx.h, N.ptr(a), a.size, N.ptr(bgr), info["w"] * 3, N.ptr(coef), N.ptr(planes), C.byref(st)))
+        ctx.check(ctx.lib.cbv_jpeg_decode_ex(ctx.h, N.ptr(a), a.size, N.ptr(bgr), info["w"] * 3, N.ptr(coef), N.ptr(planes), C.byref(st), mode,
+                                             int(piece_bytes), C.byref(ps)))
+    if stats:
+        return bgr, coef, planes, st.value, {k: getattr(ps, k) for k, _ in N.JpegDecodeStats._fields_}
     return bgr, coef, planes, st.value
 
 

@@ -836,7 +836,14 @@ struct JpegBatch {
     int bgr_stride;
     size_t bgr_frame_stride;
     int nframes;
+    // the piece path (k_jpeg_pieces): frames without DRI go it when piece_bytes (a multiple of 4) is not 0.  Frame f's
+    // scratch is pieces + f * piece_stride, JPEG_PIECE_WORDS u32 for each of its ceil(ent_len / piece_bytes) pieces.
+    u32 piece_bytes;
+    u32* pieces;
+    size_t piece_stride;
+    u32* stats;               // [nframes][3]: pieces, rounds, settled in round 0; zeros for a frame decoded by interval
 };
-// zeroes coef, status and nfound, then the four kernels on ctx->stream; total_intervals = ioff[nframes], max_blocks = the
-// largest plane_total / 64, max_w x max_h = the largest frame
-int launch_jpeg_decode(cbv_ctx* ctx, const JpegBatch& B, u32 total_intervals, int any_dri, u32 max_blocks, int max_w, int max_h);
+enum { JPEG_PIECE_WORDS = 9 }; // four states (this round's and the last one's exit, the entry, round 0's exit) and a block count
+// zeroes coef, status, nfound and stats, then the kernels on ctx->stream; total_intervals = ioff[nframes], any_dri / any_pieces:
+// a frame has restart intervals / goes the piece path, max_blocks = the largest plane_total / 64, max_w x max_h = the largest frame
+int launch_jpeg_decode(cbv_ctx* ctx, const JpegBatch& B, u32 total_intervals, int any_dri, int any_pieces, u32 max_blocks, int max_w, int max_h);

@@ -39,10 +39,24 @@ extern "C" int cbv_jpeg_probe(const uint8_t* data, size_t n, cbv_jpeg_info* info
     return CBV_OK;
 }
 
-extern "C" int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes, int32_t* status)
+// the piece size a mode and a piece_bytes argument mean (0: every frame by restart interval), or an error
+static int jpeg_piece_size(cbv_ctx* ctx, const char* who, int mode, uint32_t piece_bytes, u32* S)
+{
+    if (mode != CBV_JPEG_ENTROPY_AUTO && mode != CBV_JPEG_ENTROPY_INTERVAL && mode != CBV_JPEG_ENTROPY_PIECES)
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: entropy mode %d", who, mode);
+    if (piece_bytes && (piece_bytes < 4 || (piece_bytes & 3u) || piece_bytes > (1u << 24)))
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: pieces of %u bytes (a multiple of 4, from 4 to 2^24, or 0 for the default)", who, piece_bytes);
+    *S = mode == CBV_JPEG_ENTROPY_INTERVAL ? 0u : piece_bytes ? piece_bytes : (u32)JP_PIECE_DEFAULT;
+    return CBV_OK;
+}
+
+extern "C" int cbv_jpeg_decode_host_ex(const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes, int32_t* status,
+                                       int mode, uint32_t piece_bytes, cbv_jpeg_decode_stats* stats)
 {
     const char* who = "cbv_jpeg_decode_host";
     if (!data || !bgr || !status) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: null argument", who);
+    u32 S;
+    RC(jpeg_piece_size(nullptr, who, mode, piece_bytes, &S));
     JpegDesc D;
     JpegTables T;
     RC(jpeg_header(nullptr, who, data, n, &D, &T));
@@ -58,20 +72,35 @@ extern "C" int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr,
         planes = pbuf.data();
     }
     int st = 0;
-    jpeg_decode_host(data, D, T, coef, planes, bgr, (size_t)stride, &st);
+    JpegPieceStats ps;
+    jpeg_decode_host(data, D, T, coef, planes, bgr, (size_t)stride, &st, S, &ps);
     *status = st;
+    if (stats) {
+        stats->pieces = ps.pieces;
+        stats->rounds = ps.rounds;
+        stats->settled_round0 = ps.settled;
+    }
     return CBV_OK;
 }
 
+extern "C" int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes, int32_t* status)
+{
+    return cbv_jpeg_decode_host_ex(data, n, bgr, stride, coef, planes, status, CBV_JPEG_ENTROPY_AUTO, 0, nullptr);
+}
+
 // One stream through the four kernels on ctx->stream, with the context's scratch: the stream in ctx->in, coefficients in
-// ctx->a, planes in ctx->b, the small block (descriptor, tables, interval prefix, counters, marker positions) in ctx->small.
+// ctx->a, planes in ctx->b, the small block (descriptor, tables, interval prefix, counters, marker positions, and the piece
+// path's states, sized from the stream's length) in ctx->small.  S = the piece size, 0: by restart interval.
 // bgr_dev null: the BGR frame goes to ctx->c, tightly packed.  Nothing is waited for; *B tells where everything lies.
-static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc& D, const JpegTables& T, u8* bgr_dev, Geom g, JpegBatch* Bout)
+static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc& D, const JpegTables& T, u32 S, u8* bgr_dev, Geom g, JpegBatch* Bout)
 {
     const size_t o_desc = 0, o_tab = (sizeof(JpegDesc) + 255) & ~(size_t)255, o_ioff = (o_tab + sizeof(JpegTables) + 255) & ~(size_t)255;
-    const size_t o_nfound = o_ioff + 16, o_status = o_ioff + 32, o_mpos = o_ioff + 64;
+    const size_t o_nfound = o_ioff + 16, o_status = o_ioff + 32, o_stats = o_ioff + 48, o_mpos = o_ioff + 64;
     const size_t head = o_mpos; // what the host fills
-    RC(dev_ensure(ctx, &ctx->small, o_mpos + (size_t)D.nint * sizeof(u32)));
+    const int pieces = S && !D.dri;
+    const size_t o_pieces = (o_mpos + (size_t)D.nint * sizeof(u32) + 255) & ~(size_t)255;
+    const size_t piece_words = pieces ? (size_t)jpeg_piece_count(D, S) * JPEG_PIECE_WORDS : 0;
+    RC(dev_ensure(ctx, &ctx->small, o_pieces + piece_words * sizeof(u32)));
     ctx->small.tag = 0; // (not the enhancement chain's layout any more)
     RC(dev_ensure(ctx, &ctx->in, n + 256));
     RC(dev_ensure(ctx, &ctx->a, (size_t)D.plane_total * sizeof(int16_t)));
@@ -108,16 +137,22 @@ static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc
     B.bgr_stride = g.stride;
     B.bgr_frame_stride = g.frame_stride;
     B.nframes = 1;
+    B.piece_bytes = S;
+    B.pieces = (u32*)(sm + o_pieces);
+    B.piece_stride = piece_words;
+    B.stats = (u32*)(sm + o_stats);
     *Bout = B;
-    return launch_jpeg_decode(ctx, B, (u32)D.nint, D.dri != 0, D.plane_total / 64u, D.w, D.h);
+    return launch_jpeg_decode(ctx, B, (u32)D.nint, D.dri != 0, pieces, D.plane_total / 64u, D.w, D.h);
 }
 
-extern "C" int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes,
-                               int32_t* status)
+extern "C" int cbv_jpeg_decode_ex(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes,
+                                  int32_t* status, int mode, uint32_t piece_bytes, cbv_jpeg_decode_stats* stats)
 {
     const char* who = "cbv_jpeg_decode";
     if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
     if (!data || !bgr || !status) return cbv_fail(ctx, CBV_ERR_ARG, "%s: null argument", who);
+    u32 S;
+    RC(jpeg_piece_size(ctx, who, mode, piece_bytes, &S));
     JpegDesc D;
     JpegTables T;
     RC(jpeg_header(ctx, who, data, n, &D, &T));
@@ -126,16 +161,29 @@ extern "C" int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint
     CBV_ENTER(ctx);
     const Geom g = tight_geom(D.w, D.h);
     JpegBatch B;
-    RC(jpeg_single_dev(ctx, data, n, D, T, nullptr, g, &B));
+    RC(jpeg_single_dev(ctx, data, n, D, T, S, nullptr, g, &B));
     int st = 0;
+    u32 ps[3] = {0, 0, 0};
     CBV_HIP(ctx, hipMemcpyAsync(&st, B.status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (stats) CBV_HIP(ctx, hipMemcpyAsync(ps, B.stats, sizeof(ps), hipMemcpyDeviceToHost, ctx->stream));
     if (coef) CBV_HIP(ctx, hipMemcpyAsync(coef, B.coef, (size_t)D.plane_total * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
     if (planes) CBV_HIP(ctx, hipMemcpyAsync(planes, B.planes, D.plane_total, hipMemcpyDeviceToHost, ctx->stream));
     if (stride == g.stride) CBV_HIP(ctx, hipMemcpyAsync(bgr, B.bgr, (size_t)g.stride * D.h, hipMemcpyDeviceToHost, ctx->stream));
     else CBV_HIP(ctx, hipMemcpy2DAsync(bgr, stride, B.bgr, g.stride, g.stride, D.h, hipMemcpyDeviceToHost, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *status = st;
+    if (stats) {
+        stats->pieces = ps[0];
+        stats->rounds = ps[1];
+        stats->settled_round0 = ps[2];
+    }
     return CBV_OK;
+}
+
+extern "C" int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes,
+                               int32_t* status)
+{
+    return cbv_jpeg_decode_ex(ctx, data, n, bgr, stride, coef, planes, status, CBV_JPEG_ENTROPY_AUTO, 0, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -162,6 +210,11 @@ struct JpegState {
     int16_t* d_coef = nullptr; // [CHUNK][frame_elems]
     u8* d_planes = nullptr;
     size_t frame_elems = 0;
+    u32* d_stats = nullptr;   // [max_frames][3]
+    // the piece path: CHUNK frames of ceil(slot bytes / piece bytes) pieces, sized with the format (pipeline_jpeg_size_pieces)
+    u32* d_pieces = nullptr;
+    size_t piece_stride = 0;  // u32 words per frame
+    u32 piece_bytes = 0;      // 0: every frame by restart interval
 };
 
 size_t pipeline_jpeg_default_slot_bytes(int w, int h) { return (((size_t)w * h + 1) / 2 + 255) & ~(size_t)255; }
@@ -174,7 +227,7 @@ void pipeline_jpeg_free(Pipe& P)
     if (J->h_desc) (void)hipHostFree(J->h_desc);
     if (J->h_ioff) (void)hipHostFree(J->h_ioff);
     if (J->h_tabs) (void)hipHostFree(J->h_tabs);
-    void* dev[] = {J->d_desc, J->d_ioff, J->d_tabs, J->d_status, J->d_nfound, J->d_mpos, J->d_coef, J->d_planes};
+    void* dev[] = {J->d_desc, J->d_ioff, J->d_tabs, J->d_status, J->d_nfound, J->d_mpos, J->d_coef, J->d_planes, J->d_stats, J->d_pieces};
     for (void* q : dev)
         if (q) (void)hipFree(q);
     delete J;
@@ -203,13 +256,37 @@ int pipeline_jpeg_ensure(Pipe& P)
               hipMalloc((void**)&J->d_status, n * sizeof(int)) == hipSuccess && hipMalloc((void**)&J->d_nfound, n * sizeof(int)) == hipSuccess &&
               hipMalloc((void**)&J->d_mpos, JpegState::CHUNK * max_int * sizeof(u32)) == hipSuccess &&
               hipMalloc((void**)&J->d_coef, JpegState::CHUNK * J->frame_elems * sizeof(int16_t)) == hipSuccess &&
-              hipMalloc((void**)&J->d_planes, JpegState::CHUNK * J->frame_elems) == hipSuccess;
-    if (ok) ok = hipMemset(J->d_status, 0, n * sizeof(int)) == hipSuccess;
+              hipMalloc((void**)&J->d_planes, JpegState::CHUNK * J->frame_elems) == hipSuccess &&
+              hipMalloc((void**)&J->d_stats, n * 3 * sizeof(u32)) == hipSuccess;
+    if (ok) ok = hipMemset(J->d_status, 0, n * sizeof(int)) == hipSuccess && hipMemset(J->d_stats, 0, n * 3 * sizeof(u32)) == hipSuccess;
     if (!ok) {
         pipeline_jpeg_free(P);
         return cbv_fail(ctx, CBV_ERR_HIP, "the Motion-JPEG decode's buffers could not be allocated");
     }
     memset(J->h_lengths, 0, n * sizeof(u32));
+    return CBV_OK;
+}
+
+// The piece path's scratch for the pipeline's slot size and entropy setting; the caller has waited for the copy stream.
+int pipeline_jpeg_size_pieces(Pipe& P)
+{
+    cbv_ctx* ctx = P.ctx;
+    JpegState* J = P.jpeg;
+    u32 S = 0;
+    RC(jpeg_piece_size(ctx, "cbv_pipeline_set_jpeg_entropy", P.jpeg_entropy, P.jpeg_piece_bytes, &S));
+    const size_t stride = S ? ((P.jpeg_slot_bytes + S - 1) / S) * JPEG_PIECE_WORDS : 0;
+    if (stride != J->piece_stride) {
+        if (J->d_pieces) (void)hipFree(J->d_pieces);
+        J->d_pieces = nullptr;
+        J->piece_stride = 0;
+        J->piece_bytes = 0;
+        if (stride && hipMalloc((void**)&J->d_pieces, JpegState::CHUNK * stride * sizeof(u32)) != hipSuccess) {
+            J->d_pieces = nullptr;
+            return cbv_fail(ctx, CBV_ERR_HIP, "the Motion-JPEG piece states (%zu bytes) could not be allocated", JpegState::CHUNK * stride * sizeof(u32));
+        }
+        J->piece_stride = stride;
+    }
+    J->piece_bytes = S;
     return CBV_OK;
 }
 
@@ -302,13 +379,18 @@ int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
         B.bgr_stride = P.g.stride;
         B.bgr_frame_stride = P.g.frame_stride;
         B.nframes = cf;
-        int any_dri = 0;
+        B.piece_bytes = J->piece_bytes;
+        B.pieces = J->d_pieces;
+        B.piece_stride = J->piece_stride;
+        B.stats = J->d_stats + 3 * (size_t)s;
+        int any_dri = 0, any_pieces = 0;
         u32 max_blocks = 0;
         for (int i = 0; i < cf; i++) {
             any_dri |= J->h_desc[s + i].dri != 0;
+            any_pieces |= J->piece_bytes && !J->h_desc[s + i].dri;
             max_blocks = std::max(max_blocks, J->h_desc[s + i].plane_total / 64u);
         }
-        rc = launch_jpeg_decode(ctx, B, J->h_ioff[2 * s + cf], any_dri, max_blocks, P.w, P.h);
+        rc = launch_jpeg_decode(ctx, B, J->h_ioff[2 * s + cf], any_dri, any_pieces, max_blocks, P.w, P.h);
     }
     ctx->stream = caller;
     return rc;
@@ -332,6 +414,51 @@ extern "C" int cbv_pipeline_jpeg_status(cbv_pipeline* p, int slot0, int count, i
     if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
     CBV_HIP(ctx, hipMemcpy(out, P.jpeg->d_status + slot0, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
     return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_jpeg_stats(cbv_pipeline* p, int slot0, int count, cbv_jpeg_decode_stats* out)
+{
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "cbv_pipeline_jpeg_stats: the pipeline is null");
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_jpeg_stats: frames go to the parent of a board");
+    if (!out || slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_jpeg_stats: bad slot range");
+    if (!P.jpeg) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_jpeg_stats: no Motion-JPEG frame was ever given to the pipeline");
+    CBV_ENTER(ctx);
+    if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+    static_assert(sizeof(cbv_jpeg_decode_stats) == 3 * sizeof(u32), "cbv_jpeg_decode_stats is three words");
+    CBV_HIP(ctx, hipMemcpy(out, P.jpeg->d_stats + 3 * (size_t)slot0, (size_t)count * sizeof(cbv_jpeg_decode_stats), hipMemcpyDeviceToHost));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_set_jpeg_entropy(cbv_pipeline* p, int mode, uint32_t piece_bytes)
+{
+    const char* who = "cbv_pipeline_set_jpeg_entropy";
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the pipeline is null", who);
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who);
+    u32 S;
+    RC(jpeg_piece_size(ctx, who, mode, piece_bytes, &S));
+    CBV_ENTER(ctx);
+    const int mode_was = P.jpeg_entropy;
+    const uint32_t bytes_was = P.jpeg_piece_bytes;
+    P.jpeg_entropy = mode;
+    P.jpeg_piece_bytes = piece_bytes;
+    if (!P.jpeg || !P.jpeg_slot_bytes) return CBV_OK; // sized when the format is set
+    int rc = P.copy_stream && hipStreamSynchronize(P.copy_stream) != hipSuccess // the decodes in flight use the scratch
+                 ? cbv_fail(ctx, CBV_ERR_HIP, "%s: the copy stream could not be waited for", who)
+                 : pipeline_jpeg_size_pieces(P);
+    if (rc) { // the setting that was stays, with its scratch; if that cannot be had back either, the pipeline says what it does
+        P.jpeg_entropy = mode_was;
+        P.jpeg_piece_bytes = bytes_was;
+        if (pipeline_jpeg_size_pieces(P) != CBV_OK) {
+            P.jpeg_entropy = CBV_JPEG_ENTROPY_INTERVAL;
+            P.jpeg_piece_bytes = 0;
+            (void)pipeline_jpeg_size_pieces(P); // (frees; allocates nothing)
+        }
+    }
+    return rc;
 }
 
 extern "C" int cbv_pipeline_set_jpeg_slot_bytes(cbv_pipeline* p, size_t bytes)
@@ -366,8 +493,11 @@ extern "C" int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t
     RC(join_scan(P)); // lanes and scan of the last run
     if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // a submitted decode of this slot lands first
     JpegBatch B;
-    RC(jpeg_single_dev(ctx, data, n, D, T, P.frames + P.g.frame_stride * slot, P.g, &B));
+    u32 S;
+    RC(jpeg_piece_size(ctx, who, P.jpeg_entropy, P.jpeg_piece_bytes, &S));
+    RC(jpeg_single_dev(ctx, data, n, D, T, S, P.frames + P.g.frame_stride * slot, P.g, &B));
     CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_status + slot, B.status, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+    CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_stats + 3 * (size_t)slot, B.stats, 3 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CBV_OK;
 }

@@ -115,8 +115,51 @@ JP_HD void jpeg_bits_skip(JpegBits& b, int l)
 // were appended bits consumed?  (n <= 32 of the bits are left, the appended ones last)
 JP_HD bool jpeg_bits_overran(const JpegBits& b) { return b.n < b.fake; }
 
-// the next symbol, or -1
-JP_HD int jpeg_huff_symbol(JpegBits& b, const JpegHuff& t)
+// The piece path's reader: the same bits, and it knows where they came from.  `hist` holds two bits for each of the last
+// four bytes loaded: the raw bytes it took (1, 2 for FF 00, 0 for an appended zero byte).  After a fill 25..32 bits are
+// left, so exactly those four bytes are (partly) unconsumed, and the next bit's raw position follows (jpeg_piece_run).
+// At a marker `end` moves to the marker's FF and pos stays there.
+struct JpegPieceBits {
+    const uint8_t* d;
+    uint32_t pos, end;
+    uint32_t acc;
+    int32_t n;
+    int32_t fake;
+    uint32_t hist;
+};
+
+JP_HD void jpeg_bits_fill(JpegPieceBits& b)
+{
+    while (b.n <= 24) {
+        uint32_t byte = 0, adv = 0;
+        if (b.pos < b.end) {
+            byte = b.d[b.pos];
+            adv = 1;
+            if (byte == 0xFF) {
+                if (b.pos + 1 < b.end && b.d[b.pos + 1] == 0) adv = 2;
+                else { // a marker, or FF as the last byte: the data ends here
+                    b.end = b.pos;
+                    byte = 0;
+                    adv = 0;
+                }
+            }
+            b.pos += adv;
+        }
+        if (!adv) b.fake = b.fake > (1 << 20) ? b.fake : b.fake + 8;
+        b.acc |= byte << (24 - b.n);
+        b.n += 8;
+        b.hist = (b.hist << 2 | adv) & 0xFFu;
+    }
+}
+JP_HD void jpeg_bits_skip(JpegPieceBits& b, int l)
+{
+    b.acc <<= l;
+    b.n -= l;
+}
+
+// the next symbol, or -1 (BR: JpegBits or JpegPieceBits)
+template <class BR>
+JP_HD int jpeg_huff_symbol(BR& b, const JpegHuff& t)
 {
     jpeg_bits_fill(b);
     const uint32_t v = b.acc >> 16;
@@ -129,7 +172,8 @@ JP_HD int jpeg_huff_symbol(JpegBits& b, const JpegHuff& t)
 }
 
 // s bits (1..15) as a signed value (T.81 F.2.2.1 EXTEND)
-JP_HD int jpeg_receive_extend(JpegBits& b, int s)
+template <class BR>
+JP_HD int jpeg_receive_extend(BR& b, int s)
 {
     jpeg_bits_fill(b);
     const int v = (int)(b.acc >> (32 - s));
@@ -208,6 +252,191 @@ JP_HD void jpeg_interval_bytes(const JpegDesc& D, const uint32_t* mpos, int nfou
     }
     *start = iv == 0 ? D.ent_off : mpos[iv - 1] + 2;
     *end = iv < nfound ? mpos[iv] : e;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The piece path: a scan without restart markers decoded by many lanes (include/cbv.h, CBV_JPEG_ENTROPY_PIECES).  Piece i
+// is bytes [ent_off + i S, ent_off + (i + 1) S) of the entropy data.  The decoder's state between two symbols (a symbol
+// = a Huffman code and its value bits) is a JpegPieceState: the raw position of the next bit (never the 00 of an FF 00
+// pair), the block within the MCU and the zig-zag index k (0: a DC symbol is next).  X[i] = the state at the first symbol
+// boundary at or past piece i's end.  A lane that meets a bad code, or the end of the data (every real bit consumed), has no
+// such boundary: its X[i] is the guess piece i + 1 starts round 0 from, marked JP_PS_DEAD or JP_PS_ENDED.  The mark is not
+// part of the next lane's entry, so a mark that came from a wrong guess holds up nobody, and lanes behind a true mark settle
+// like all others.  With the true state in front of piece 0 the X are unique; up to the first marked piece they are the
+// serial decode's own, that piece is where the serial decode dies or runs out of data, and nothing behind it is written.
+// ---------------------------------------------------------------------------------------------------------------------
+enum { JP_PS_ENDED = 1 << 12, JP_PS_DEAD = 1 << 13 };
+enum { JP_PIECE_DEFAULT = 64 }; // bytes; DESIGN.md section 6o has the measurement behind it
+struct JpegPieceState {
+    uint32_t pos;
+    uint32_t w; // bit in byte | block in MCU << 3 | k << 6 | JP_PS_* (marks of an exit, see above)
+};
+struct JpegPieceStats {
+    uint32_t pieces, rounds, settled;
+};
+JP_HD bool jpeg_piece_same(const JpegPieceState& a, const JpegPieceState& b) { return a.pos == b.pos && a.w == b.w; }
+JP_HD uint32_t jpeg_piece_count(const JpegDesc& D, uint32_t S)
+{
+    const uint32_t n = D.ent_len / S + (D.ent_len % S ? 1u : 0u);
+    return n ? n : 1u;
+}
+JP_HD uint32_t jpeg_piece_end(const JpegDesc& D, uint32_t S, uint32_t i, uint32_t npieces)
+{
+    return i + 1 >= npieces ? D.ent_off + D.ent_len : D.ent_off + (i + 1) * S;
+}
+JP_HD int jpeg_mcu_blocks(const JpegDesc& D) { return D.ncomp == 1 ? 1 : D.hs * D.vs + 2; }
+JP_HD uint32_t jpeg_scan_blocks(const JpegDesc& D) { return (uint32_t)(D.mcux * D.mcuy) * (uint32_t)jpeg_mcu_blocks(D); }
+// the component of block `blk` of an MCU
+JP_HD int jpeg_mcu_comp(const JpegDesc& D, int blk)
+{
+    const int nl = D.ncomp == 1 ? 1 : D.hs * D.vs;
+    return blk < nl ? 0 : blk - nl + 1;
+}
+// where block B of the scan (MCU by MCU, as jpeg_decode_interval walks them) lies in the coefficient buffer
+JP_HD size_t jpeg_scan_block_elem(const JpegDesc& D, uint32_t B)
+{
+    const uint32_t bpm = (uint32_t)jpeg_mcu_blocks(D);
+    const uint32_t m = B / bpm;
+    const int blk = (int)(B - m * bpm);
+    const int c = jpeg_mcu_comp(D, blk);
+    const int my = (int)(m / (uint32_t)D.mcux), mx = (int)(m - (uint32_t)my * (uint32_t)D.mcux);
+    const int ch = c == 0 ? D.hs : 1, cv = c == 0 ? D.vs : 1;
+    const int by = c == 0 ? blk / D.hs : 0, bx = c == 0 ? blk - by * D.hs : 0;
+    return D.poff[c] + ((size_t)(my * cv + by) * D.bw[c] + (mx * ch + bx)) * 64;
+}
+// block j of component c in scan order, as a block number of the scan
+JP_HD uint32_t jpeg_comp_block(const JpegDesc& D, int c, uint32_t j)
+{
+    const uint32_t nl = D.ncomp == 1 ? 1u : (uint32_t)(D.hs * D.vs);
+    const uint32_t per = c == 0 ? nl : 1u, first = c == 0 ? 0u : nl + (uint32_t)c - 1u;
+    const uint32_t m = j / per;
+    return m * (uint32_t)jpeg_mcu_blocks(D) + first + (j - m * per);
+}
+// how many of the scan's first ndc blocks are component c's
+JP_HD uint32_t jpeg_comp_blocks_in(const JpegDesc& D, int c, uint32_t ndc)
+{
+    const uint32_t bpm = (uint32_t)jpeg_mcu_blocks(D);
+    const uint32_t nl = D.ncomp == 1 ? 1u : (uint32_t)(D.hs * D.vs);
+    const uint32_t per = c == 0 ? nl : 1u, first = c == 0 ? 0u : nl + (uint32_t)c - 1u;
+    const uint32_t m = ndc / bpm, rem = ndc - m * bpm;
+    const uint32_t part = rem <= first ? 0u : rem - first > per ? per : rem - first;
+    return m * per + part;
+}
+
+// what lane i > 0 starts round 0 from: the first bit of its piece (behind the 00 of an FF 00 pair cut by the boundary), a
+// DC symbol of block 0
+// (i = the number of pieces: the data's end)
+JP_HD JpegPieceState jpeg_piece_guess(const uint8_t* d, const JpegDesc& D, uint32_t S, uint32_t i, uint32_t npieces)
+{
+    JpegPieceState x;
+    x.pos = i >= npieces ? D.ent_off + D.ent_len : D.ent_off + i * S;
+    x.w = 0;
+    if (i && i < npieces && d[x.pos] == 0 && d[x.pos - 1] == 0xFF) x.pos++;
+    return x;
+}
+
+// One symbol at zig-zag index k (0: the DC symbol) with the block's tables.  Returns the k behind it (64 or more: the
+// block is complete) or -1 for a bad code; *at = the zig-zag index of the coefficient it carried (-1: none), *val = its
+// value (k = 0: the DC difference).  Consumes what jpeg_decode_block consumes, bad codes included.
+JP_HD int jpeg_piece_step(JpegPieceBits& b, const JpegHuff& dc, const JpegHuff& ac, int k, int* at, int* val)
+{
+    *at = -1;
+    *val = 0;
+    if (k == 0) {
+        const int s = jpeg_huff_symbol(b, dc);
+        if (s < 0 || s > 15) return -1;
+        if (s) *val = jpeg_receive_extend(b, s);
+        *at = 0;
+        return 1;
+    }
+    const int rs = jpeg_huff_symbol(b, ac);
+    if (rs < 0) return -1;
+    const int r = rs >> 4, s = rs & 15;
+    if (s == 0) return r != 15 ? 64 : k + 16; // EOB, ZRL
+    k += r;
+    if (k > 63) return -1;
+    *val = jpeg_receive_extend(b, s);
+    *at = k;
+    return k + 1;
+}
+
+// Piece i of npieces (S bytes each) decoded from `entry`, whose marks are ignored.  W false, a round: stops at the first
+// symbol boundary at or past the piece's end and returns that state, or the marked guess of piece i + 1 where the data
+// ended or a code was bad; *nblocks = the blocks completed on the way.  W true, the write pass from the piece's true
+// entry, whose block number in the scan is B: the AC coefficients go in place and the DC DIFFERENCE into out[0]; the lane
+// that meets the data's end goes on through the zero bits behind it as the serial decode does, until the scan's blocks
+// are done or a code is bad.  *status gets JP_ST_* bits, *ndc one more than the last block whose DC symbol was decoded.
+// No block at or past the scan's count is touched.  max_steps bounds the loop: 8 S + 8 for a round (every symbol takes a
+// bit of the piece), 64 (blocks + 1) for the write pass (a block has at most 64 symbols).
+template <bool W>
+JP_HD JpegPieceState jpeg_piece_run(const uint8_t* d, const JpegDesc& D, const JpegTables& T, JpegPieceState entry, uint32_t S, uint32_t i,
+                                    uint32_t npieces, uint32_t max_steps, uint32_t* nblocks, int16_t* coef, uint32_t B, int* status, uint32_t* ndc)
+{
+    *nblocks = 0;
+    entry.w &= 0xFFFu;
+    const uint32_t total = jpeg_scan_blocks(D);
+    if (W && B >= total) return entry;
+    const uint32_t pend = jpeg_piece_end(D, S, i, npieces);
+    JpegPieceBits b;
+    b.d = d;
+    b.pos = entry.pos;
+    b.end = D.ent_off + D.ent_len;
+    b.acc = 0;
+    b.n = 0;
+    b.fake = 0;
+    b.hist = 0;
+    jpeg_bits_fill(b);
+    jpeg_bits_skip(b, (int)(entry.w & 7u));
+    int blk = (int)(entry.w >> 3) & 7, k = (int)(entry.w >> 6) & 63;
+    const int bpm = jpeg_mcu_blocks(D);
+    int16_t* out = (W && k) ? coef + jpeg_scan_block_elem(D, B) : nullptr;
+    uint32_t done = 0;
+    int st = 0;
+    JpegPieceState x = entry;
+    for (uint32_t step = 0;; step++) {
+        jpeg_bits_fill(b);
+        const uint32_t h = b.hist;
+        const bool ended = ((h >> 6) & 3u) == 0; // the oldest of the four bytes left is an appended one: no real bit is left
+        x.pos = b.pos - ((h & 3u) + ((h >> 2) & 3u) + ((h >> 4) & 3u) + ((h >> 6) & 3u));
+        x.w = (uint32_t)(32 - b.n) | (uint32_t)blk << 3 | (uint32_t)k << 6;
+        if (ended && !W) {
+            x = jpeg_piece_guess(d, D, S, i + 1, npieces);
+            x.w |= JP_PS_ENDED;
+            break;
+        }
+        if (!ended && x.pos >= pend) break;
+        if (W && B + done >= total) break;
+        if (step >= max_steps) break;
+        const int c = jpeg_mcu_comp(D, blk);
+        int at, val;
+        k = jpeg_piece_step(b, T.dc[D.td[c] & 1], T.ac[D.ta[c] & 1], k, &at, &val);
+        if (k < 0) {
+            st |= JP_ST_BAD_CODE;
+            if (!W) {
+                x = jpeg_piece_guess(d, D, S, i + 1, npieces);
+                x.w |= JP_PS_DEAD;
+            }
+            break;
+        }
+        if (W && at >= 0) {
+            if (at == 0) {
+                out = coef + jpeg_scan_block_elem(D, B + done);
+                *ndc = B + done + 1;
+            }
+            out[jpeg_natural(at)] = (int16_t)val;
+        }
+        if (k >= 64) {
+            k = 0;
+            blk = blk + 1 == bpm ? 0 : blk + 1;
+            done++;
+        }
+    }
+    if (W) {
+        if (b.n < b.fake) st |= JP_ST_NO_DATA;
+        *status |= st;
+    }
+    *nblocks = done;
+    return x;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -548,19 +777,85 @@ static inline void jpeg_find_restarts_host(const uint8_t* d, const JpegDesc& D, 
     if ((int)total != D.nint - 1) *st |= JP_ST_RESTART;
 }
 
+// The piece path on the host, the algorithm k_jpeg_pieces runs: the states in vectors, the rounds in Jacobi order (round r
+// reads only round r - 1's exits), the prefix sum, the write pass, the DC pass.  coef is zeroed by the caller.  S = the
+// piece size in bytes, a multiple of 4.  Returns status bits.
+static inline int jpeg_decode_pieces_host(const uint8_t* d, const JpegDesc& D, const JpegTables& T, uint32_t S, int16_t* coef, JpegPieceStats* ps)
+{
+    const uint32_t np = jpeg_piece_count(D, S), total = jpeg_scan_blocks(D);
+    const uint32_t round_steps = 8 * S + 8, write_steps = 64 * (total + 1);
+    const JpegPieceState first = {D.ent_off, 0};
+    std::vector<JpegPieceState> cur(np), nxt(np), ent(np), r0(np);
+    std::vector<uint32_t> cnt(np);
+    for (uint32_t i = 0; i < np; i++) { // round 0
+        ent[i] = i ? jpeg_piece_guess(d, D, S, i, np) : first;
+        cur[i] = r0[i] = jpeg_piece_run<false>(d, D, T, ent[i], S, i, np, round_steps, &cnt[i], nullptr, 0, nullptr, nullptr);
+    }
+    uint32_t rounds = 1;
+    for (uint32_t r = 1; r < np; r++) { // after round r the exits 0..r are true: round np could change nothing
+        bool changed = false;
+        for (uint32_t i = 0; i < np; i++) {
+            const JpegPieceState e = i ? cur[i - 1] : first;
+            if (jpeg_piece_same(e, ent[i])) {
+                nxt[i] = cur[i];
+                continue;
+            }
+            ent[i] = e;
+            nxt[i] = jpeg_piece_run<false>(d, D, T, e, S, i, np, round_steps, &cnt[i], nullptr, 0, nullptr, nullptr);
+            changed |= !jpeg_piece_same(nxt[i], cur[i]);
+        }
+        cur.swap(nxt);
+        if (!changed) break;
+        rounds++;
+    }
+    int st = 0;
+    uint32_t ndc = 0, B = 0, settled = 0;
+    uint32_t last = np - 1; // the first marked piece: where the serial decode dies or runs out of data
+    for (uint32_t i = 0; i < np; i++) {
+        settled += jpeg_piece_same(r0[i], cur[i]) ? 1u : 0u;
+        if (i < last && (cur[i].w & (JP_PS_ENDED | JP_PS_DEAD))) last = i;
+    }
+    for (uint32_t i = 0; i <= last; i++) {
+        uint32_t done, mine = 0;
+        jpeg_piece_run<true>(d, D, T, i ? cur[i - 1] : first, S, i, np, write_steps, &done, coef, B, &st, &mine);
+        ndc = mine > ndc ? mine : ndc;
+        B += cnt[i];
+    }
+    for (int c = 0; c < D.ncomp; c++) { // differences to predictions, mod 2^16
+        const uint32_t n = jpeg_comp_blocks_in(D, c, ndc);
+        uint16_t pred = 0;
+        for (uint32_t j = 0; j < n; j++) {
+            int16_t* o = coef + jpeg_scan_block_elem(D, jpeg_comp_block(D, c, j));
+            pred = (uint16_t)(pred + (uint16_t)o[0]);
+            o[0] = (int16_t)pred;
+        }
+    }
+    if (ps) {
+        ps->pieces = np;
+        ps->rounds = rounds;
+        ps->settled = settled;
+    }
+    return st;
+}
+
 // The twin: coef[plane_total] and planes[plane_total] are scratch the caller provides (coef is zeroed here), bgr = h rows
-// of w * 3 bytes, `stride` apart.
+// of w * 3 bytes, `stride` apart.  piece_bytes 0: every frame by restart interval; otherwise a frame without DRI goes the
+// piece path with pieces of that size, and *ps (may be null) gets its figures (zeros for a frame by interval).
 static inline void jpeg_decode_host(const uint8_t* d, const JpegDesc& D, const JpegTables& T, int16_t* coef, uint8_t* planes, uint8_t* bgr,
-                                    size_t stride, int* status)
+                                    size_t stride, int* status, uint32_t piece_bytes = 0, JpegPieceStats* ps = nullptr)
 {
     int st = 0;
     memset(coef, 0, (size_t)D.plane_total * sizeof(int16_t));
-    std::vector<uint32_t> mpos;
-    jpeg_find_restarts_host(d, D, &mpos, &st);
-    for (int iv = 0; iv < D.nint; iv++) {
-        uint32_t a, b;
-        jpeg_interval_bytes(D, mpos.data(), (int)mpos.size(), iv, &a, &b);
-        st |= jpeg_decode_interval(d, D, T, a, b, iv, coef);
+    if (ps) memset(ps, 0, sizeof(*ps));
+    if (piece_bytes && !D.dri) st |= jpeg_decode_pieces_host(d, D, T, piece_bytes, coef, ps);
+    else {
+        std::vector<uint32_t> mpos;
+        jpeg_find_restarts_host(d, D, &mpos, &st);
+        for (int iv = 0; iv < D.nint; iv++) {
+            uint32_t a, b;
+            jpeg_interval_bytes(D, mpos.data(), (int)mpos.size(), iv, &a, &b);
+            st |= jpeg_decode_interval(d, D, T, a, b, iv, coef);
+        }
     }
     for (int c = 0; c < D.ncomp; c++) {
         const int ps = D.bw[c] * 8;

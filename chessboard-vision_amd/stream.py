@@ -807,6 +807,19 @@ class BoardPipeline(_BoardMethods):
         self.ctx.check(self.ctx.lib.cbv_pipeline_jpeg_status(self.h_, slot0, count, N.ptr(out)))
         return out
 
+    def set_jpeg_entropy(self, mode, piece_bytes=0):
+        """The entropy path of the "mjpeg" decodes: "auto" (pieces for streams without DRI, restart intervals otherwise; the
+        default), "interval" or "pieces", and the piece size in bytes (0: the library's default, otherwise a multiple of 4).
+        The frames do not depend on either (include/cbv.h).  Call between runs."""
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_entropy(self.h_, N.JPEG_ENTROPY[mode], int(piece_bytes)))
+
+    def jpeg_stats(self, slot0, count):
+        """The piece path's figures of the streams last decoded into the slots: a [count, 3] uint32 array of pieces, rounds and
+        settled_round0 (zeros for a stream decoded by restart interval); waits for the submitted decodes."""
+        out = np.zeros((count, 3), np.uint32)
+        self.ctx.check(self.ctx.lib.cbv_pipeline_jpeg_stats(self.h_, slot0, count, N.ptr(out)))
+        return out
+
     def submit(self, slot0, count):
         """Enqueue host ring -> device ring for the slots; run() of those slots waits for the copy."""
         self.ctx.check(self.ctx.lib.cbv_pipeline_submit(self.h_, slot0, count))

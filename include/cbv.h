@@ -656,6 +656,36 @@ CBV_API int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr, in
 /* the same on the GPU: the single-frame call and the stage entry point */
 CBV_API int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes,
                             int32_t* status);
+/* The entropy decode has two paths, and the result does not depend on which one runs.
+ *   by interval  a lane per restart interval.  A stream without DRI (what a UVC webcam, an IP camera and AVI MJPEG send) is
+ *                one interval: one lane.
+ *   by piece     for frames without DRI.  The entropy data is cut into pieces of piece_bytes bytes, a lane each.  The state
+ *                between two symbols is (byte, bit, block within the MCU, zig-zag index).  Lane 0 starts from the true state,
+ *                every other lane from a guess, and each stores the state it leaves its piece with.  In every further round a
+ *                lane decodes its piece again from the state the lane before it left, until a round changes nothing.  With
+ *                the true state in front of piece 0 that fixpoint is unique, the serial decode's state at every boundary:
+ *                after round r the exits of pieces 0..r are true whatever was guessed, so there are at most as many rounds as
+ *                pieces, and Huffman codes resynchronise, so there are few.  A prefix sum over the blocks the pieces hold
+ *                numbers the blocks, a last pass writes the coefficients with the DC differences, and a per-component scan
+ *                sums those.  Coefficients, planes, BGR and status are the interval path's bit for bit, for damaged data as
+ *                well, at every piece size.  The zero bits behind the data's end are decoded by one lane, as by interval.
+ * CBV_JPEG_ENTROPY_AUTO (the default) takes pieces for frames without DRI and intervals otherwise; _INTERVAL takes intervals
+ * for every frame; _PIECES is AUTO's choice today, reserved for cutting long restart intervals as well.  piece_bytes: 0 = the
+ * library's default (64), otherwise a multiple of 4 from 4 to 2^24; small pieces exist for tests (a symbol then spans
+ * several pieces, and a piece inside one symbol decodes nothing and passes its entry on). */
+#define CBV_JPEG_ENTROPY_AUTO 0
+#define CBV_JPEG_ENTROPY_INTERVAL 1
+#define CBV_JPEG_ENTROPY_PIECES 2
+typedef struct {
+    uint32_t pieces;          /* pieces of the frame, ceil(entropy_length / piece_bytes); 0: the frame was decoded by interval */
+    uint32_t rounds;          /* rounds until nothing changed, round 0 counted: 1 <= rounds <= pieces */
+    uint32_t settled_round0;  /* pieces whose exit state of round 0 was already the true one */
+} cbv_jpeg_decode_stats;
+/* cbv_jpeg_decode_host / cbv_jpeg_decode with the path chosen; stats may be NULL.  The plain calls are these with AUTO, 0, NULL. */
+CBV_API int cbv_jpeg_decode_host_ex(const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes, int32_t* status,
+                                    int mode, uint32_t piece_bytes, cbv_jpeg_decode_stats* stats);
+CBV_API int cbv_jpeg_decode_ex(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t* bgr, int stride, int16_t* coef, uint8_t* planes,
+                               int32_t* status, int mode, uint32_t piece_bytes, cbv_jpeg_decode_stats* stats);
 /* The ingest ring in Motion-JPEG: cbv_pipeline_set_input_format(p, CBV_FMT_MJPEG).  A slot of the host ring holds one
  * stream from its first byte; cbv_pipeline_host_slot_bytes is the capacity of a slot, w * h / 2 rounded up to 256 unless
  * cbv_pipeline_set_jpeg_slot_bytes set another (rounded up to 256; with the format set it frees both rings, as a format
@@ -679,6 +709,13 @@ CBV_API int cbv_pipeline_set_jpeg_slot_bytes(cbv_pipeline* p, size_t bytes);
 CBV_API int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t* data, size_t n);
 /* the status words (CBV_JPEG_*) of the streams last decoded into the slots; waits for the submitted decodes */
 CBV_API int cbv_pipeline_jpeg_status(cbv_pipeline* p, int slot0, int count, int32_t* status);
+/* The entropy path of the pipeline's decodes (submit and upload_jpeg) and its piece size; call between runs.  The piece
+ * path's device scratch, 8 x ceil(slot bytes / piece_bytes) piece states, is sized here and when the format is set; submit
+ * still allocates nothing.  When the scratch cannot be allocated the call fails and the setting that was stays (by interval
+ * if its scratch cannot be had back either).  CBV_ERR_STATE on a board handle. */
+CBV_API int cbv_pipeline_set_jpeg_entropy(cbv_pipeline* p, int mode, uint32_t piece_bytes);
+/* the figures of the streams last decoded into the slots (zeros for a frame decoded by interval); waits like cbv_pipeline_jpeg_status */
+CBV_API int cbv_pipeline_jpeg_stats(cbv_pipeline* p, int slot0, int count, cbv_jpeg_decode_stats* stats);
 
 /* ------------------------------------------------------------------ */
 /* several boards seen by one camera                                   */

@@ -1,12 +1,15 @@
 """Host-fed throughput of the Motion-JPEG ingest beside NV12 and Bayer, in one session (never bench.py's `value`): 1080p
 frames sit in the pinned host ring; batch k+1 is copied and decoded (cbv_pipeline_submit) while batch k runs.
 
-    python tools/jpeg_timing.py [--streams FILE.npz] [--make-streams FILE.npz] [--reps 2]
+    python tools/jpeg_timing.py [--streams FILE.npz] [--make-streams FILE.npz] [--reps 2] [--entropy auto|interval|pieces]
+                                [--piece-bytes N]
 
 Per variant (quality 75 / 90, 4:2:2 / 4:2:0, without DRI and with a restart interval of one MCU row) it prints the submit-only
 rate (copy + decode), the overlapped submit || run rate, the bytes that crossed the link per frame, and the latency of ONE
-frame in flight (submit of a single slot until its decode has completed), the case a stream without DRI loses: its entropy
-decode is one lane.  The per-kernel times come from a kernel trace of this script (rocprofv3 --kernel-trace --stats).
+frame in flight (submit of a single slot until its decode has completed).  --entropy and --piece-bytes choose the entropy
+path (BoardPipeline.set_jpeg_entropy; "interval" is one lane for a stream without DRI), and every JPEG row ends with the
+piece path's figures for the streams of the variant: pieces, rounds and the share of pieces settled in round 0.  The
+per-kernel times come from a kernel trace of this script (rocprofv3 --kernel-trace --stats).
 
 Encoding 1080p frames with tests/ref_jpeg.py takes a few seconds each, so the streams can be made once on any machine
 (--make-streams, no GPU: the frames are then the CPU oracle's synthetic scene) and loaded with --streams."""
@@ -25,6 +28,8 @@ ap.add_argument("--streams", help="npz of encoded streams (from --make-streams)"
 ap.add_argument("--make-streams", help="encode the streams into this npz and exit (needs no GPU)")
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--frames", type=int, default=2, help="distinct source frames per variant")
+ap.add_argument("--entropy", default="auto", choices=("auto", "interval", "pieces"))
+ap.add_argument("--piece-bytes", type=int, default=0, help="piece size of the piece path (0: the library's default)")
 ap.add_argument("--only", help="comma-separated variants to run (default: bgr, nv12, bayer_rggb and every JPEG variant)")
 args = ap.parse_args()
 
@@ -58,6 +63,7 @@ from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
 n = 2 * HALF
 p = BoardPipeline(W, H, n)
 p.configure(S.scaled_corners(W, H), profile=S.SHIPPED_PROFILE, grid_lines=(S.CALIB_GRID_X, S.CALIB_GRID_Y), **S.SHIPPED_DETECTOR)
+p.set_jpeg_entropy(args.entropy, args.piece_bytes)
 if args.streams:
     z = np.load(args.streams)
     streams = {k: z[k] for k in z.files}
@@ -128,13 +134,17 @@ def measure(fmt):
         p.wait_submitted()
     t_one = (time.perf_counter() - t0) / 20
     frames = ROUNDS * n
-    return frames / t_copy, frames / t_ovl, link, t_one
+    stats = p.jpeg_stats(0, nsrc) if p.input_format == "mjpeg" else None
+    return frames / t_copy, frames / t_ovl, link, t_one, stats
 
 
 formats = args.only.split(",") if args.only else ["bgr", "nv12", "bayer_rggb"] + [vname(*v) for v in VARIANTS]
 for rep in range(args.reps):
     for fmt in formats:
-        c, o, link, one = measure(fmt)
-        print("[%s, rep %d] submit only %8.0f frames/s   submit || run %8.0f frames/s   link %9.0f bytes/frame   one frame in flight %7.1f us"
-              % (fmt, rep + 1, c, o, link, one * 1e6), flush=True)
+        c, o, link, one, stats = measure(fmt)
+        tail = ""
+        if stats is not None and stats[:, 0].any():
+            tail = "   pieces %s rounds %s settled in round 0 %.2f" % (stats[:, 0].tolist(), stats[:, 1].tolist(), stats[:, 2].sum() / stats[:, 0].sum())
+        print("[%s, rep %d] submit only %8.0f frames/s   submit || run %8.0f frames/s   link %9.0f bytes/frame   one frame in flight %7.1f us%s"
+              % (fmt, rep + 1, c, o, link, one * 1e6, tail), flush=True)
 p.close()
