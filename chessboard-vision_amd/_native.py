@@ -293,7 +293,7 @@ class JpegInfo(C.Structure):
                 ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3)]
 
 
-JPEG_ENTROPY = {"auto": 0, "interval": 1, "pieces": 2}  # CBV_JPEG_ENTROPY_*
+JPEG_ENTROPY = {"auto": 0, "interval": 1, "pieces": 2, "segments": 4}  # CBV_JPEG_ENTROPY_* (3 is no mode)
 
 
 class JpegDecodeStats(C.Structure):
@@ -442,6 +442,8 @@ def load():
         "cbv_jpeg_decode_ex": (i32, [vp, vp, C.c_size_t, u8p, i32, vp, vp, P(C.c_int32), i32, C.c_uint32, P(JpegDecodeStats)]),
         "cbv_pipeline_set_jpeg_entropy": (i32, [vp, i32, C.c_uint32]),
         "cbv_pipeline_jpeg_stats": (i32, [vp, i32, i32, vp]),
+        "cbv_pipeline_set_jpeg_depth": (i32, [vp, i32]),
+        "cbv_pipeline_jpeg_depth": (i32, [vp]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

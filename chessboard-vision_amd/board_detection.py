@@ -157,9 +157,9 @@ def jpeg_decode(data, host=False, entropy="auto", piece_bytes=0, stats=False):
     status).  On the GPU (cbv_jpeg_decode_ex), or with host=True by the library's host twin (cbv_jpeg_decode_host_ex, no
     GPU): the same bodies, byte for byte.  The layout of coef and planes: jpeg_probe(data)["blocks"] and include/cbv.h.
     status: _native.JPEG_BAD_CODE | JPEG_NO_DATA | JPEG_RESTART, 0 for an undamaged stream.  entropy: "auto" (pieces for a
-    stream without DRI, restart intervals otherwise), "interval" or "pieces", and piece_bytes the piece size (0: the
-    default, otherwise a multiple of 4); neither changes the result.  stats=True appends a dict with pieces, rounds and
-    settled_round0 (zeros for a stream decoded by interval)."""
+    stream without DRI, restart intervals otherwise), "interval", "pieces" or "segments" (restart intervals cut into pieces
+    too), and piece_bytes the piece size (0: the default, otherwise a multiple of 4); neither changes the result.
+    stats=True appends a dict with pieces, rounds and settled_round0 (zeros for a stream decoded by interval)."""
     a = _jpeg_bytes(data)
     info = jpeg_probe(a)
     bgr = np.empty((info["h"], info["w"], 3), np.uint8)

@@ -836,14 +836,25 @@ struct JpegBatch {
     int bgr_stride;
     size_t bgr_frame_stride;
     int nframes;
-    // the piece path (k_jpeg_pieces): frames without DRI go it when piece_bytes (a multiple of 4) is not 0.  Frame f's
-    // scratch is pieces + f * piece_stride, JPEG_PIECE_WORDS u32 for each of its ceil(ent_len / piece_bytes) pieces.
+    // the piece path (k_jpeg_pieces): frames without DRI go it when piece_bytes (a multiple of 4) is not 0, and with
+    // `segments` frames with DRI do too, every restart interval cut into pieces.  Frame f's scratch is pieces + f * piece_stride:
+    // JPEG_PIECE_WORDS u32 (one more with `segments`: the piece's segment) for each of its pieces, of which it may have
+    // piece_cap; and with `segments`, segs + f * seg_stride: JPEG_SEG_WORDS u32 for each of its intervals and one more.
     u32 piece_bytes;
     u32* pieces;
     size_t piece_stride;
+    u32 piece_cap;
+    int segments;
+    u32* segs;
+    size_t seg_stride;
     u32* stats;               // [nframes][3]: pieces, rounds, settled in round 0; zeros for a frame decoded by interval
 };
 enum { JPEG_PIECE_WORDS = 9 }; // four states (this round's and the last one's exit, the entry, round 0's exit) and a block count
-// zeroes coef, status, nfound and stats, then the kernels on ctx->stream; total_intervals = ioff[nframes], any_dri / any_pieces:
-// a frame has restart intervals / goes the piece path, max_blocks = the largest plane_total / 64, max_w x max_h = the largest frame
+enum { JPEG_SEG_WORDS = 3 };   // a segment's first piece, its last written piece, one past its last block with a decoded DC symbol
+// the piece path's scratch per frame, in u32 words, for `pieces` pieces and (in segments mode) `intervals` restart intervals
+inline size_t jpeg_piece_words(size_t pieces, int segments) { return pieces * (size_t)(JPEG_PIECE_WORDS + (segments ? 1 : 0)); }
+inline size_t jpeg_seg_words(size_t intervals) { return intervals * JPEG_SEG_WORDS + 1; }
+// zeroes coef, status, nfound, stats and the segment scratch, then the kernels on ctx->stream; total_intervals = ioff[nframes],
+// any_dri / any_pieces: a frame has restart intervals / goes the piece path, max_blocks = the largest plane_total / 64,
+// max_w x max_h = the largest frame
 int launch_jpeg_decode(cbv_ctx* ctx, const JpegBatch& B, u32 total_intervals, int any_dri, int any_pieces, u32 max_blocks, int max_w, int max_h);

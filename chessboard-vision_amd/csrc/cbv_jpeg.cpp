@@ -39,14 +39,16 @@ extern "C" int cbv_jpeg_probe(const uint8_t* data, size_t n, cbv_jpeg_info* info
     return CBV_OK;
 }
 
-// the piece size a mode and a piece_bytes argument mean (0: every frame by restart interval), or an error
-static int jpeg_piece_size(cbv_ctx* ctx, const char* who, int mode, uint32_t piece_bytes, u32* S)
+// the piece size a mode and a piece_bytes argument mean (0: every frame by restart interval), and whether frames with DRI
+// go the piece path too (CBV_JPEG_ENTROPY_SEGMENTS); or an error
+static int jpeg_piece_size(cbv_ctx* ctx, const char* who, int mode, uint32_t piece_bytes, u32* S, int* segments)
 {
-    if (mode != CBV_JPEG_ENTROPY_AUTO && mode != CBV_JPEG_ENTROPY_INTERVAL && mode != CBV_JPEG_ENTROPY_PIECES)
+    if (mode != CBV_JPEG_ENTROPY_AUTO && mode != CBV_JPEG_ENTROPY_INTERVAL && mode != CBV_JPEG_ENTROPY_PIECES && mode != CBV_JPEG_ENTROPY_SEGMENTS)
         return cbv_fail(ctx, CBV_ERR_ARG, "%s: entropy mode %d", who, mode);
     if (piece_bytes && (piece_bytes < 4 || (piece_bytes & 3u) || piece_bytes > (1u << 24)))
         return cbv_fail(ctx, CBV_ERR_ARG, "%s: pieces of %u bytes (a multiple of 4, from 4 to 2^24, or 0 for the default)", who, piece_bytes);
     *S = mode == CBV_JPEG_ENTROPY_INTERVAL ? 0u : piece_bytes ? piece_bytes : (u32)JP_PIECE_DEFAULT;
+    *segments = mode == CBV_JPEG_ENTROPY_SEGMENTS;
     return CBV_OK;
 }
 
@@ -56,7 +58,8 @@ extern "C" int cbv_jpeg_decode_host_ex(const uint8_t* data, size_t n, uint8_t* b
     const char* who = "cbv_jpeg_decode_host";
     if (!data || !bgr || !status) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: null argument", who);
     u32 S;
-    RC(jpeg_piece_size(nullptr, who, mode, piece_bytes, &S));
+    int segments;
+    RC(jpeg_piece_size(nullptr, who, mode, piece_bytes, &S, &segments));
     JpegDesc D;
     JpegTables T;
     RC(jpeg_header(nullptr, who, data, n, &D, &T));
@@ -73,7 +76,7 @@ extern "C" int cbv_jpeg_decode_host_ex(const uint8_t* data, size_t n, uint8_t* b
     }
     int st = 0;
     JpegPieceStats ps;
-    jpeg_decode_host(data, D, T, coef, planes, bgr, (size_t)stride, &st, S, &ps);
+    jpeg_decode_host(data, D, T, coef, planes, bgr, (size_t)stride, &st, S, &ps, segments != 0);
     *status = st;
     if (stats) {
         stats->pieces = ps.pieces;
@@ -88,19 +91,26 @@ extern "C" int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr,
     return cbv_jpeg_decode_host_ex(data, n, bgr, stride, coef, planes, status, CBV_JPEG_ENTROPY_AUTO, 0, nullptr);
 }
 
-// One stream through the four kernels on ctx->stream, with the context's scratch: the stream in ctx->in, coefficients in
+// One stream through the kernels on ctx->stream, with the context's scratch: the stream in ctx->in, coefficients in
 // ctx->a, planes in ctx->b, the small block (descriptor, tables, interval prefix, counters, marker positions, and the piece
-// path's states, sized from the stream's length) in ctx->small.  S = the piece size, 0: by restart interval.
+// path's states and segment table, sized from the stream's length and its intervals) in ctx->small.  S = the piece size, 0:
+// by restart interval; segments: a frame with DRI goes the piece path too.
 // bgr_dev null: the BGR frame goes to ctx->c, tightly packed.  Nothing is waited for; *B tells where everything lies.
-static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc& D, const JpegTables& T, u32 S, u8* bgr_dev, Geom g, JpegBatch* Bout)
+static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc& D, const JpegTables& T, u32 S, int segments, u8* bgr_dev, Geom g,
+                           JpegBatch* Bout)
 {
     const size_t o_desc = 0, o_tab = (sizeof(JpegDesc) + 255) & ~(size_t)255, o_ioff = (o_tab + sizeof(JpegTables) + 255) & ~(size_t)255;
     const size_t o_nfound = o_ioff + 16, o_status = o_ioff + 32, o_stats = o_ioff + 48, o_mpos = o_ioff + 64;
     const size_t head = o_mpos; // what the host fills
-    const int pieces = S && !D.dri;
+    segments = segments && S;
+    const int pieces = S && (!D.dri || segments);
     const size_t o_pieces = (o_mpos + (size_t)D.nint * sizeof(u32) + 255) & ~(size_t)255;
-    const size_t piece_words = pieces ? (size_t)jpeg_piece_count(D, S) * JPEG_PIECE_WORDS : 0;
-    RC(dev_ensure(ctx, &ctx->small, o_pieces + piece_words * sizeof(u32)));
+    // the intervals' pieces: sum ceil(len_j / S) <= ceil(ent_len / S) + intervals, an empty interval counted as one piece
+    const size_t piece_cap = pieces ? (size_t)jpeg_piece_count(D, S) + (segments && D.dri ? (size_t)D.nint : 0) : 0;
+    const size_t piece_words = jpeg_piece_words(piece_cap, segments);
+    const size_t o_segs = (o_pieces + piece_words * sizeof(u32) + 255) & ~(size_t)255;
+    const size_t seg_words = segments ? jpeg_seg_words((size_t)D.nint) : 0;
+    RC(dev_ensure(ctx, &ctx->small, o_segs + seg_words * sizeof(u32)));
     ctx->small.tag = 0; // (not the enhancement chain's layout any more)
     RC(dev_ensure(ctx, &ctx->in, n + 256));
     RC(dev_ensure(ctx, &ctx->a, (size_t)D.plane_total * sizeof(int16_t)));
@@ -140,6 +150,10 @@ static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc
     B.piece_bytes = S;
     B.pieces = (u32*)(sm + o_pieces);
     B.piece_stride = piece_words;
+    B.piece_cap = (u32)piece_cap;
+    B.segments = segments;
+    B.segs = (u32*)(sm + o_segs);
+    B.seg_stride = seg_words;
     B.stats = (u32*)(sm + o_stats);
     *Bout = B;
     return launch_jpeg_decode(ctx, B, (u32)D.nint, D.dri != 0, pieces, D.plane_total / 64u, D.w, D.h);
@@ -152,7 +166,8 @@ extern "C" int cbv_jpeg_decode_ex(cbv_ctx* ctx, const uint8_t* data, size_t n, u
     if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
     if (!data || !bgr || !status) return cbv_fail(ctx, CBV_ERR_ARG, "%s: null argument", who);
     u32 S;
-    RC(jpeg_piece_size(ctx, who, mode, piece_bytes, &S));
+    int segments;
+    RC(jpeg_piece_size(ctx, who, mode, piece_bytes, &S, &segments));
     JpegDesc D;
     JpegTables T;
     RC(jpeg_header(ctx, who, data, n, &D, &T));
@@ -161,7 +176,7 @@ extern "C" int cbv_jpeg_decode_ex(cbv_ctx* ctx, const uint8_t* data, size_t n, u
     CBV_ENTER(ctx);
     const Geom g = tight_geom(D.w, D.h);
     JpegBatch B;
-    RC(jpeg_single_dev(ctx, data, n, D, T, S, nullptr, g, &B));
+    RC(jpeg_single_dev(ctx, data, n, D, T, S, segments, nullptr, g, &B));
     int st = 0;
     u32 ps[3] = {0, 0, 0};
     CBV_HIP(ctx, hipMemcpyAsync(&st, B.status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -190,10 +205,26 @@ extern "C" int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint
 // The pipeline's Motion-JPEG ingest (cbv_pipeline_set_input_format(p, CBV_FMT_MJPEG)).  The host ring holds one stream per
 // slot, `lengths` says how many bytes of each slot are used.  cbv_pipeline_submit parses the slots' headers out of the
 // pinned ring (a few hundred bytes each; the entropy data is never read on the host), copies the used bytes and enqueues the
-// decode on the copy stream behind the copy, CHUNK frames at a time through one set of scratch buffers.
+// decode on the copy stream behind the copy, `depth` frames at a time through one set of scratch buffers
+// (cbv_pipeline_set_jpeg_depth).
 // ---------------------------------------------------------------------------------------------------------------------
+// the scratch of one launch, `depth` frames of everything: allocated as a set, replaced as a set
+struct JpegScratch {
+    int depth = 0;
+    u32* mpos = nullptr;     // [depth * max_intervals]
+    int16_t* coef = nullptr; // [depth][frame_elems]
+    u8* planes = nullptr;
+    // the piece path: `depth` frames of piece_cap pieces and, in segments mode, of max_intervals segments
+    u32* pieces = nullptr;
+    size_t piece_stride = 0; // u32 words per frame
+    u32 piece_cap = 0;       // pieces a frame may have
+    u32 piece_bytes = 0;     // 0: every frame by restart interval
+    int segments = 0;
+    u32* segs = nullptr;
+    size_t seg_stride = 0;   // u32 words per frame
+};
 struct JpegState {
-    enum { CHUNK = 8, NSETS = 16 };
+    enum { NSETS = 16 };
     // pinned, with the slots' lifetime
     u32* h_lengths = nullptr;   // [max_frames], the capture side's
     JpegDesc* h_desc = nullptr; // [max_frames]
@@ -206,18 +237,21 @@ struct JpegState {
     JpegTables* d_tabs = nullptr;
     int* d_status = nullptr; // [max_frames]
     int* d_nfound = nullptr; // [max_frames]
-    u32* d_mpos = nullptr;   // [CHUNK * max_intervals]
-    int16_t* d_coef = nullptr; // [CHUNK][frame_elems]
-    u8* d_planes = nullptr;
     size_t frame_elems = 0;
+    size_t max_int = 0;       // the intervals a frame can have: a restart interval of one MCU in the sampling with most MCUs
     u32* d_stats = nullptr;   // [max_frames][3]
-    // the piece path: CHUNK frames of ceil(slot bytes / piece bytes) pieces, sized with the format (pipeline_jpeg_size_pieces)
-    u32* d_pieces = nullptr;
-    size_t piece_stride = 0;  // u32 words per frame
-    u32 piece_bytes = 0;      // 0: every frame by restart interval
+    JpegScratch sc;           // sized with the format, the entropy setting and the depth (pipeline_jpeg_size_scratch)
 };
 
 size_t pipeline_jpeg_default_slot_bytes(int w, int h) { return (((size_t)w * h + 1) / 2 + 255) & ~(size_t)255; }
+
+static void jpeg_scratch_free(JpegScratch& sc)
+{
+    void* dev[] = {sc.mpos, sc.coef, sc.planes, sc.pieces, sc.segs};
+    for (void* q : dev)
+        if (q) (void)hipFree(q);
+    sc = JpegScratch();
+}
 
 void pipeline_jpeg_free(Pipe& P)
 {
@@ -227,15 +261,15 @@ void pipeline_jpeg_free(Pipe& P)
     if (J->h_desc) (void)hipHostFree(J->h_desc);
     if (J->h_ioff) (void)hipHostFree(J->h_ioff);
     if (J->h_tabs) (void)hipHostFree(J->h_tabs);
-    void* dev[] = {J->d_desc, J->d_ioff, J->d_tabs, J->d_status, J->d_nfound, J->d_mpos, J->d_coef, J->d_planes, J->d_stats, J->d_pieces};
+    void* dev[] = {J->d_desc, J->d_ioff, J->d_tabs, J->d_status, J->d_nfound, J->d_stats};
     for (void* q : dev)
         if (q) (void)hipFree(q);
+    jpeg_scratch_free(J->sc);
     delete J;
     P.jpeg = nullptr;
 }
 
-// the decode's scratch, sized once for CHUNK frames of the pipeline's size in the sampling that needs most (4:4:4 padded to
-// the 16 x 16 MCUs of 4:2:0) and a restart interval of one MCU
+// what lives as long as the slots; the decode's scratch is pipeline_jpeg_size_scratch's
 int pipeline_jpeg_ensure(Pipe& P)
 {
     cbv_ctx* ctx = P.ctx;
@@ -246,7 +280,7 @@ int pipeline_jpeg_ensure(Pipe& P)
     const size_t n = (size_t)P.max_frames;
     const size_t pw = ((size_t)P.w + 15) & ~(size_t)15, ph = ((size_t)P.h + 15) & ~(size_t)15;
     J->frame_elems = 3 * pw * ph;
-    const size_t max_int = ((size_t)P.w + 7) / 8 * (((size_t)P.h + 7) / 8);
+    J->max_int = ((size_t)P.w + 7) / 8 * (((size_t)P.h + 7) / 8);
     bool ok = hipHostMalloc((void**)&J->h_lengths, n * sizeof(u32), hipHostMallocDefault) == hipSuccess &&
               hipHostMalloc((void**)&J->h_desc, n * sizeof(JpegDesc), hipHostMallocDefault) == hipSuccess &&
               hipHostMalloc((void**)&J->h_ioff, 2 * n * sizeof(u32), hipHostMallocDefault) == hipSuccess &&
@@ -254,9 +288,6 @@ int pipeline_jpeg_ensure(Pipe& P)
               hipMalloc((void**)&J->d_desc, n * sizeof(JpegDesc)) == hipSuccess && hipMalloc((void**)&J->d_ioff, 2 * n * sizeof(u32)) == hipSuccess &&
               hipMalloc((void**)&J->d_tabs, JpegState::NSETS * sizeof(JpegTables)) == hipSuccess &&
               hipMalloc((void**)&J->d_status, n * sizeof(int)) == hipSuccess && hipMalloc((void**)&J->d_nfound, n * sizeof(int)) == hipSuccess &&
-              hipMalloc((void**)&J->d_mpos, JpegState::CHUNK * max_int * sizeof(u32)) == hipSuccess &&
-              hipMalloc((void**)&J->d_coef, JpegState::CHUNK * J->frame_elems * sizeof(int16_t)) == hipSuccess &&
-              hipMalloc((void**)&J->d_planes, JpegState::CHUNK * J->frame_elems) == hipSuccess &&
               hipMalloc((void**)&J->d_stats, n * 3 * sizeof(u32)) == hipSuccess;
     if (ok) ok = hipMemset(J->d_status, 0, n * sizeof(int)) == hipSuccess && hipMemset(J->d_stats, 0, n * 3 * sizeof(u32)) == hipSuccess;
     if (!ok) {
@@ -267,26 +298,47 @@ int pipeline_jpeg_ensure(Pipe& P)
     return CBV_OK;
 }
 
-// The piece path's scratch for the pipeline's slot size and entropy setting; the caller has waited for the copy stream.
-int pipeline_jpeg_size_pieces(Pipe& P)
+// The decode's scratch for the pipeline's slot size, entropy setting and depth: `depth` frames of the pipeline's size in the
+// sampling that needs most (4:4:4 padded to the 16 x 16 MCUs of 4:2:0) and a restart interval of one MCU; a frame's pieces
+// are at most ceil(slot bytes / S), and with segments max_intervals more (every interval's last piece may be a short one,
+// an empty interval is one piece).  The new set is allocated before the old one is freed: when it cannot be had the old one
+// stays as it is.  The caller has waited for the copy stream; `who` names it in the messages.
+int pipeline_jpeg_size_scratch(Pipe& P, const char* who)
 {
     cbv_ctx* ctx = P.ctx;
     JpegState* J = P.jpeg;
     u32 S = 0;
-    RC(jpeg_piece_size(ctx, "cbv_pipeline_set_jpeg_entropy", P.jpeg_entropy, P.jpeg_piece_bytes, &S));
-    const size_t stride = S ? ((P.jpeg_slot_bytes + S - 1) / S) * JPEG_PIECE_WORDS : 0;
-    if (stride != J->piece_stride) {
-        if (J->d_pieces) (void)hipFree(J->d_pieces);
-        J->d_pieces = nullptr;
-        J->piece_stride = 0;
-        J->piece_bytes = 0;
-        if (stride && hipMalloc((void**)&J->d_pieces, JpegState::CHUNK * stride * sizeof(u32)) != hipSuccess) {
-            J->d_pieces = nullptr;
-            return cbv_fail(ctx, CBV_ERR_HIP, "the Motion-JPEG piece states (%zu bytes) could not be allocated", JpegState::CHUNK * stride * sizeof(u32));
-        }
-        J->piece_stride = stride;
+    int segments = 0;
+    RC(jpeg_piece_size(ctx, who, P.jpeg_entropy, P.jpeg_piece_bytes, &S, &segments));
+    const size_t depth = (size_t)P.jpeg_depth;
+    JpegScratch n;
+    n.depth = P.jpeg_depth;
+    n.piece_bytes = S;
+    n.segments = segments;
+    const size_t cap = S ? (P.jpeg_slot_bytes + S - 1) / S + (segments ? J->max_int : 0) : 0;
+    if (cap > 0xFFFFFFFFu) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %zu pieces per frame", who, cap);
+    n.piece_cap = (u32)cap;
+    n.piece_stride = jpeg_piece_words(cap, segments);
+    n.seg_stride = segments ? jpeg_seg_words(J->max_int) : 0;
+    const JpegScratch& o = J->sc;
+    if (o.depth == n.depth && o.piece_stride == n.piece_stride && o.seg_stride == n.seg_stride && o.piece_cap == n.piece_cap) { // the buffers serve
+        J->sc.piece_bytes = S;
+        J->sc.segments = segments;
+        return CBV_OK;
     }
-    J->piece_bytes = S;
+    const size_t b_mpos = depth * J->max_int * sizeof(u32), b_coef = depth * J->frame_elems * sizeof(int16_t), b_planes = depth * J->frame_elems;
+    const size_t b_pieces = depth * n.piece_stride * sizeof(u32), b_segs = depth * n.seg_stride * sizeof(u32);
+    const bool ok = hipMalloc((void**)&n.mpos, b_mpos) == hipSuccess && hipMalloc((void**)&n.coef, b_coef) == hipSuccess &&
+                    hipMalloc((void**)&n.planes, b_planes) == hipSuccess && (!b_pieces || hipMalloc((void**)&n.pieces, b_pieces) == hipSuccess) &&
+                    (!b_segs || hipMalloc((void**)&n.segs, b_segs) == hipSuccess);
+    if (!ok) {
+        (void)hipGetLastError();
+        jpeg_scratch_free(n);
+        return cbv_fail(ctx, CBV_ERR_HIP, "%s: the Motion-JPEG decode's scratch (%zu bytes for %zu frames per launch) could not be allocated", who,
+                        b_mpos + b_coef + b_planes + b_pieces + b_segs, depth);
+    }
+    jpeg_scratch_free(J->sc);
+    J->sc = n;
     return CBV_OK;
 }
 
@@ -320,6 +372,7 @@ int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
     JpegState* J = P.jpeg;
     const char* who = "cbv_pipeline_submit";
     const size_t sb = P.jpeg_slot_bytes;
+    if (J->sc.depth < 1) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the Motion-JPEG decode has no scratch", who);
     if (J->nsets == JpegState::NSETS) { // the cache is full: start again once nothing reads it
         CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
         J->nsets = 0;
@@ -336,8 +389,8 @@ int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
             return rc;
         }
     }
-    for (int c0 = 0; c0 < count; c0 += JpegState::CHUNK) {
-        const int s = slot0 + c0, cf = std::min<int>(JpegState::CHUNK, count - c0);
+    for (int c0 = 0; c0 < count; c0 += J->sc.depth) {
+        const int s = slot0 + c0, cf = std::min<int>(J->sc.depth, count - c0);
         u32 acc = 0;
         for (int i = 0; i < cf; i++) {
             J->h_ioff[2 * s + i] = acc;
@@ -360,34 +413,38 @@ int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
     hipStream_t caller = ctx->stream;
     ctx->stream = P.copy_stream;
     int rc = CBV_OK;
-    for (int c0 = 0; c0 < count && !rc; c0 += JpegState::CHUNK) {
-        const int s = slot0 + c0, cf = std::min<int>(JpegState::CHUNK, count - c0);
+    for (int c0 = 0; c0 < count && !rc; c0 += J->sc.depth) {
+        const int s = slot0 + c0, cf = std::min<int>(J->sc.depth, count - c0);
         JpegBatch B;
         B.data = P.raw_ring + sb * s;
         B.data_stride = sb;
         B.descs = J->d_desc + s;
         B.tables = J->d_tabs;
         B.ioff = J->d_ioff + 2 * s;
-        B.mpos = J->d_mpos;
+        B.mpos = J->sc.mpos;
         B.nfound = J->d_nfound + s;
         B.status = J->d_status + s;
-        B.coef = J->d_coef;
+        B.coef = J->sc.coef;
         B.coef_stride = J->frame_elems;
-        B.planes = J->d_planes;
+        B.planes = J->sc.planes;
         B.plane_stride = J->frame_elems;
         B.bgr = P.frames + P.g.frame_stride * s;
         B.bgr_stride = P.g.stride;
         B.bgr_frame_stride = P.g.frame_stride;
         B.nframes = cf;
-        B.piece_bytes = J->piece_bytes;
-        B.pieces = J->d_pieces;
-        B.piece_stride = J->piece_stride;
+        B.piece_bytes = J->sc.piece_bytes;
+        B.pieces = J->sc.pieces;
+        B.piece_stride = J->sc.piece_stride;
+        B.piece_cap = J->sc.piece_cap;
+        B.segments = J->sc.segments;
+        B.segs = J->sc.segs;
+        B.seg_stride = J->sc.seg_stride;
         B.stats = J->d_stats + 3 * (size_t)s;
         int any_dri = 0, any_pieces = 0;
         u32 max_blocks = 0;
         for (int i = 0; i < cf; i++) {
             any_dri |= J->h_desc[s + i].dri != 0;
-            any_pieces |= J->piece_bytes && !J->h_desc[s + i].dri;
+            any_pieces |= J->sc.piece_bytes && (J->sc.segments || !J->h_desc[s + i].dri);
             max_blocks = std::max(max_blocks, J->h_desc[s + i].plane_total / 64u);
         }
         rc = launch_jpeg_decode(ctx, B, J->h_ioff[2 * s + cf], any_dri, any_pieces, max_blocks, P.w, P.h);
@@ -439,26 +496,49 @@ extern "C" int cbv_pipeline_set_jpeg_entropy(cbv_pipeline* p, int mode, uint32_t
     cbv_ctx* ctx = P.ctx;
     if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who);
     u32 S;
-    RC(jpeg_piece_size(ctx, who, mode, piece_bytes, &S));
+    int segments;
+    RC(jpeg_piece_size(ctx, who, mode, piece_bytes, &S, &segments));
     CBV_ENTER(ctx);
     const int mode_was = P.jpeg_entropy;
     const uint32_t bytes_was = P.jpeg_piece_bytes;
     P.jpeg_entropy = mode;
     P.jpeg_piece_bytes = piece_bytes;
     if (!P.jpeg || !P.jpeg_slot_bytes) return CBV_OK; // sized when the format is set
-    int rc = P.copy_stream && hipStreamSynchronize(P.copy_stream) != hipSuccess // the decodes in flight use the scratch
-                 ? cbv_fail(ctx, CBV_ERR_HIP, "%s: the copy stream could not be waited for", who)
-                 : pipeline_jpeg_size_pieces(P);
-    if (rc) { // the setting that was stays, with its scratch; if that cannot be had back either, the pipeline says what it does
+    const int rc = P.copy_stream && hipStreamSynchronize(P.copy_stream) != hipSuccess // the decodes in flight use the scratch
+                       ? cbv_fail(ctx, CBV_ERR_HIP, "%s: the copy stream could not be waited for", who)
+                       : pipeline_jpeg_size_scratch(P, who);
+    if (rc) { // the setting that was stays, with its scratch (the new one is allocated before the old one is let go)
         P.jpeg_entropy = mode_was;
         P.jpeg_piece_bytes = bytes_was;
-        if (pipeline_jpeg_size_pieces(P) != CBV_OK) {
-            P.jpeg_entropy = CBV_JPEG_ENTROPY_INTERVAL;
-            P.jpeg_piece_bytes = 0;
-            (void)pipeline_jpeg_size_pieces(P); // (frees; allocates nothing)
-        }
     }
     return rc;
+}
+
+extern "C" int cbv_pipeline_set_jpeg_depth(cbv_pipeline* p, int frames)
+{
+    const char* who = "cbv_pipeline_set_jpeg_depth";
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the pipeline is null", who);
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who);
+    if (frames < 1 || frames > CBV_JPEG_DEPTH_MAX) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %d frames per launch (1 to %d)", who, frames, CBV_JPEG_DEPTH_MAX);
+    CBV_ENTER(ctx);
+    const int was = P.jpeg_depth;
+    P.jpeg_depth = frames;
+    if (!P.jpeg || !P.jpeg_slot_bytes) return CBV_OK; // sized when the format is set
+    const int rc = P.copy_stream && hipStreamSynchronize(P.copy_stream) != hipSuccess // the decodes in flight use the scratch
+                       ? cbv_fail(ctx, CBV_ERR_HIP, "%s: the copy stream could not be waited for", who)
+                       : pipeline_jpeg_size_scratch(P, who);
+    if (rc) P.jpeg_depth = was; // with its scratch
+    return rc;
+}
+
+extern "C" int cbv_pipeline_jpeg_depth(cbv_pipeline* p)
+{
+    const char* who = "cbv_pipeline_jpeg_depth";
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the pipeline is null", who);
+    if (attached(p)) return cbv_fail(p->pipe->ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who);
+    return p->pipe->jpeg_depth;
 }
 
 extern "C" int cbv_pipeline_set_jpeg_slot_bytes(cbv_pipeline* p, size_t bytes)
@@ -494,8 +574,9 @@ extern "C" int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t
     if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // a submitted decode of this slot lands first
     JpegBatch B;
     u32 S;
-    RC(jpeg_piece_size(ctx, who, P.jpeg_entropy, P.jpeg_piece_bytes, &S));
-    RC(jpeg_single_dev(ctx, data, n, D, T, S, P.frames + P.g.frame_stride * slot, P.g, &B));
+    int segments;
+    RC(jpeg_piece_size(ctx, who, P.jpeg_entropy, P.jpeg_piece_bytes, &S, &segments));
+    RC(jpeg_single_dev(ctx, data, n, D, T, S, segments, P.frames + P.g.frame_stride * slot, P.g, &B));
     CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_status + slot, B.status, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
     CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_stats + 3 * (size_t)slot, B.stats, 3 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));

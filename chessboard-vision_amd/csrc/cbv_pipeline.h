@@ -146,6 +146,7 @@ struct Pipe {
     // Motion-JPEG: CBV_JPEG_ENTROPY_* and the piece size (0: the default), cbv_pipeline_set_jpeg_entropy
     int jpeg_entropy = 0;
     uint32_t jpeg_piece_bytes = 0;
+    int jpeg_depth = CBV_JPEG_DEPTH_DEFAULT; // frames per launch of a Motion-JPEG submit, cbv_pipeline_set_jpeg_depth
     Board& b0() const { return boards[0]->b; }
     bool configured_raw_profile() const { return skip_enhance && profile_raw; }
     bool fmt_is_raw() const { return in_fmt != CBV_FMT_BGR && in_fmt != CBV_FMT_MJPEG; } // a YUV or Bayer format
@@ -169,6 +170,6 @@ RawPlanes slot_planes(const Pipe& P, int slot);
 // cbv_jpeg.cpp: the Motion-JPEG ingest
 size_t pipeline_jpeg_default_slot_bytes(int w, int h);
 int pipeline_jpeg_ensure(Pipe& P);
-int pipeline_jpeg_size_pieces(Pipe& P);
+int pipeline_jpeg_size_scratch(Pipe& P, const char* who);
 void pipeline_jpeg_free(Pipe& P);
 int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev);

@@ -99,7 +99,7 @@ extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
     }
     // the copies and conversions in flight read the rings that go away here (both run on the copy stream)
     if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
-    if (fmt == CBV_FMT_MJPEG) RC(pipeline_jpeg_size_pieces(P)); // ... for this slot size
+    if (fmt == CBV_FMT_MJPEG) RC(pipeline_jpeg_size_scratch(P, "cbv_pipeline_set_input_format")); // ... for this slot size, entropy setting and depth
     if (P.raw_mode()) { // ... and so do the runs in flight
         RC(join_scan(P));
         CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));

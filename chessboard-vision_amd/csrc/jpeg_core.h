@@ -255,15 +255,18 @@ JP_HD void jpeg_interval_bytes(const JpegDesc& D, const uint32_t* mpos, int nfou
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The piece path: a scan without restart markers decoded by many lanes (include/cbv.h, CBV_JPEG_ENTROPY_PIECES).  Piece i
-// is bytes [ent_off + i S, ent_off + (i + 1) S) of the entropy data.  The decoder's state between two symbols (a symbol
-// = a Huffman code and its value bits) is a JpegPieceState: the raw position of the next bit (never the 00 of an FF 00
-// pair), the block within the MCU and the zig-zag index k (0: a DC symbol is next).  X[i] = the state at the first symbol
-// boundary at or past piece i's end.  A lane that meets a bad code, or the end of the data (every real bit consumed), has no
-// such boundary: its X[i] is the guess piece i + 1 starts round 0 from, marked JP_PS_DEAD or JP_PS_ENDED.  The mark is not
-// part of the next lane's entry, so a mark that came from a wrong guess holds up nobody, and lanes behind a true mark settle
-// like all others.  With the true state in front of piece 0 the X are unique; up to the first marked piece they are the
-// serial decode's own, that piece is where the serial decode dies or runs out of data, and nothing behind it is written.
+// The piece path: entropy data decoded by many lanes (include/cbv.h, CBV_JPEG_ENTROPY_PIECES and _SEGMENTS).  A SEGMENT is
+// a stretch of entropy data in front of which the decoder's state is known: the whole scan of a frame without DRI, or one
+// restart interval (bit 0, block 0 of an MCU, a DC symbol next, predictions 0).  Piece i of a segment is bytes
+// [a + i S, a + (i + 1) S) of its bytes [a, b).  The decoder's state between two symbols (a symbol = a Huffman code and its
+// value bits) is a JpegPieceState: the raw position of the next bit (never the 00 of an FF 00 pair), the block within the
+// MCU and the zig-zag index k (0: a DC symbol is next).  X[i] = the state at the first symbol boundary at or past piece i's
+// end.  A lane that meets a bad code, or the end of the data (every real bit consumed), has no such boundary: its X[i] is
+// the guess piece i + 1 starts round 0 from, marked JP_PS_DEAD or JP_PS_ENDED.  The mark is not part of the next lane's
+// entry, so a mark that came from a wrong guess holds up nobody, and lanes behind a true mark settle like all others.  With
+// the true state in front of a segment's piece 0 its X are unique; up to the first marked piece they are the serial decode's
+// own, that piece is where the serial decode of the segment dies or runs out of data, and nothing behind it in the segment
+// is written.  Segments share nothing: a piece takes its entry from the piece before it in its own segment only.
 // ---------------------------------------------------------------------------------------------------------------------
 enum { JP_PS_ENDED = 1 << 12, JP_PS_DEAD = 1 << 13 };
 enum { JP_PIECE_DEFAULT = 64 }; // bytes; DESIGN.md section 6o has the measurement behind it
@@ -274,18 +277,46 @@ struct JpegPieceState {
 struct JpegPieceStats {
     uint32_t pieces, rounds, settled;
 };
+// bytes [a, b) of the stream, and the blocks of the scan (MCU by MCU) they hold: `blocks` of them from block `first`
+struct JpegSegment {
+    uint32_t a, b;
+    uint32_t first, blocks;
+};
 JP_HD bool jpeg_piece_same(const JpegPieceState& a, const JpegPieceState& b) { return a.pos == b.pos && a.w == b.w; }
-JP_HD uint32_t jpeg_piece_count(const JpegDesc& D, uint32_t S)
+// pieces of S bytes in `len` bytes; an empty stretch is one (empty) piece
+JP_HD uint32_t jpeg_piece_count(uint32_t len, uint32_t S)
 {
-    const uint32_t n = D.ent_len / S + (D.ent_len % S ? 1u : 0u);
+    const uint32_t n = len / S + (len % S ? 1u : 0u);
     return n ? n : 1u;
 }
-JP_HD uint32_t jpeg_piece_end(const JpegDesc& D, uint32_t S, uint32_t i, uint32_t npieces)
+JP_HD uint32_t jpeg_piece_count(const JpegDesc& D, uint32_t S) { return jpeg_piece_count(D.ent_len, S); }
+JP_HD uint32_t jpeg_piece_end(const JpegSegment& G, uint32_t S, uint32_t i, uint32_t npieces)
 {
-    return i + 1 >= npieces ? D.ent_off + D.ent_len : D.ent_off + (i + 1) * S;
+    return i + 1 >= npieces ? G.b : G.a + (i + 1) * S;
 }
 JP_HD int jpeg_mcu_blocks(const JpegDesc& D) { return D.ncomp == 1 ? 1 : D.hs * D.vs + 2; }
 JP_HD uint32_t jpeg_scan_blocks(const JpegDesc& D) { return (uint32_t)(D.mcux * D.mcuy) * (uint32_t)jpeg_mcu_blocks(D); }
+// the whole scan as one segment (a frame without DRI)
+JP_HD JpegSegment jpeg_scan_segment(const JpegDesc& D)
+{
+    const JpegSegment G = {D.ent_off, D.ent_off + D.ent_len, 0u, jpeg_scan_blocks(D)};
+    return G;
+}
+// Segment j of a frame: restart interval j with jpeg_interval_bytes' bytes (an interval whose marker is missing is empty, at
+// the data's end) and the blocks of its MCUs [j dri, min((j + 1) dri, mcus)); the scan itself for a frame without DRI.
+JP_HD JpegSegment jpeg_frame_segment(const JpegDesc& D, const uint32_t* mpos, int nfound, uint32_t j)
+{
+    if (!D.dri) return jpeg_scan_segment(D);
+    JpegSegment G;
+    jpeg_interval_bytes(D, mpos, nfound, (int)j, &G.a, &G.b);
+    if (G.b < G.a) G.b = G.a; // (markers in order lie two bytes apart at least: cannot happen)
+    const uint32_t nmcu = (uint32_t)(D.mcux * D.mcuy), bpm = (uint32_t)jpeg_mcu_blocks(D);
+    const uint32_t m0 = j * (uint32_t)D.dri < nmcu ? j * (uint32_t)D.dri : nmcu;
+    const uint32_t m1 = nmcu - m0 < (uint32_t)D.dri ? nmcu : m0 + (uint32_t)D.dri;
+    G.first = m0 * bpm;
+    G.blocks = (m1 - m0) * bpm;
+    return G;
+}
 // the component of block `blk` of an MCU
 JP_HD int jpeg_mcu_comp(const JpegDesc& D, int blk)
 {
@@ -325,11 +356,11 @@ JP_HD uint32_t jpeg_comp_blocks_in(const JpegDesc& D, int c, uint32_t ndc)
 
 // what lane i > 0 starts round 0 from: the first bit of its piece (behind the 00 of an FF 00 pair cut by the boundary), a
 // DC symbol of block 0
-// (i = the number of pieces: the data's end)
-JP_HD JpegPieceState jpeg_piece_guess(const uint8_t* d, const JpegDesc& D, uint32_t S, uint32_t i, uint32_t npieces)
+// (i = the number of pieces: the segment's end)
+JP_HD JpegPieceState jpeg_piece_guess(const uint8_t* d, const JpegSegment& G, uint32_t S, uint32_t i, uint32_t npieces)
 {
     JpegPieceState x;
-    x.pos = i >= npieces ? D.ent_off + D.ent_len : D.ent_off + i * S;
+    x.pos = i >= npieces ? G.b : G.a + i * S;
     x.w = 0;
     if (i && i < npieces && d[x.pos] == 0 && d[x.pos - 1] == 0xFF) x.pos++;
     return x;
@@ -360,27 +391,29 @@ JP_HD int jpeg_piece_step(JpegPieceBits& b, const JpegHuff& dc, const JpegHuff& 
     return k + 1;
 }
 
-// Piece i of npieces (S bytes each) decoded from `entry`, whose marks are ignored.  W false, a round: stops at the first
-// symbol boundary at or past the piece's end and returns that state, or the marked guess of piece i + 1 where the data
-// ended or a code was bad; *nblocks = the blocks completed on the way.  W true, the write pass from the piece's true
-// entry, whose block number in the scan is B: the AC coefficients go in place and the DC DIFFERENCE into out[0]; the lane
-// that meets the data's end goes on through the zero bits behind it as the serial decode does, until the scan's blocks
-// are done or a code is bad.  *status gets JP_ST_* bits, *ndc one more than the last block whose DC symbol was decoded.
-// No block at or past the scan's count is touched.  max_steps bounds the loop: 8 S + 8 for a round (every symbol takes a
-// bit of the piece), 64 (blocks + 1) for the write pass (a block has at most 64 symbols).
+// Piece i of the npieces (S bytes each) of segment G decoded from `entry`, whose marks are ignored.  W false, a round: stops
+// at the first symbol boundary at or past the piece's end and returns that state, or the marked guess of piece i + 1 where
+// the data ended or a code was bad; *nblocks = the blocks completed on the way.  W true, the write pass from the piece's
+// true entry, whose block number in the scan is B: the AC coefficients go in place and the DC DIFFERENCE into out[0]; the
+// lane that meets the segment's end goes on through the zero bits behind it as the serial decode does, until the segment's
+// blocks are done or a code is bad.  *status gets JP_ST_* bits, *ndc one more than the last block (of the scan) whose DC
+// symbol was decoded.  No block outside [G.first, G.first + G.blocks) is touched, and no byte at or past G.b is read (a
+// restart marker never is).  max_steps bounds the loop: 8 S + 8 for a round (every symbol takes a bit of the piece),
+// 64 (segment blocks + 1) for the write pass (a block has at most 64 symbols).
 template <bool W>
-JP_HD JpegPieceState jpeg_piece_run(const uint8_t* d, const JpegDesc& D, const JpegTables& T, JpegPieceState entry, uint32_t S, uint32_t i,
-                                    uint32_t npieces, uint32_t max_steps, uint32_t* nblocks, int16_t* coef, uint32_t B, int* status, uint32_t* ndc)
+JP_HD JpegPieceState jpeg_piece_run(const uint8_t* d, const JpegDesc& D, const JpegTables& T, JpegPieceState entry, const JpegSegment& G, uint32_t S,
+                                    uint32_t i, uint32_t npieces, uint32_t max_steps, uint32_t* nblocks, int16_t* coef, uint32_t B, int* status,
+                                    uint32_t* ndc)
 {
     *nblocks = 0;
     entry.w &= 0xFFFu;
-    const uint32_t total = jpeg_scan_blocks(D);
-    if (W && B >= total) return entry;
-    const uint32_t pend = jpeg_piece_end(D, S, i, npieces);
+    const uint32_t total = G.first + G.blocks;
+    if (W && (B < G.first || B >= total)) return entry;
+    const uint32_t pend = jpeg_piece_end(G, S, i, npieces);
     JpegPieceBits b;
     b.d = d;
     b.pos = entry.pos;
-    b.end = D.ent_off + D.ent_len;
+    b.end = G.b;
     b.acc = 0;
     b.n = 0;
     b.fake = 0;
@@ -400,7 +433,7 @@ JP_HD JpegPieceState jpeg_piece_run(const uint8_t* d, const JpegDesc& D, const J
         x.pos = b.pos - ((h & 3u) + ((h >> 2) & 3u) + ((h >> 4) & 3u) + ((h >> 6) & 3u));
         x.w = (uint32_t)(32 - b.n) | (uint32_t)blk << 3 | (uint32_t)k << 6;
         if (ended && !W) {
-            x = jpeg_piece_guess(d, D, S, i + 1, npieces);
+            x = jpeg_piece_guess(d, G, S, i + 1, npieces);
             x.w |= JP_PS_ENDED;
             break;
         }
@@ -413,7 +446,7 @@ JP_HD JpegPieceState jpeg_piece_run(const uint8_t* d, const JpegDesc& D, const J
         if (k < 0) {
             st |= JP_ST_BAD_CODE;
             if (!W) {
-                x = jpeg_piece_guess(d, D, S, i + 1, npieces);
+                x = jpeg_piece_guess(d, G, S, i + 1, npieces);
                 x.w |= JP_PS_DEAD;
             }
             break;
@@ -777,57 +810,82 @@ static inline void jpeg_find_restarts_host(const uint8_t* d, const JpegDesc& D, 
     if ((int)total != D.nint - 1) *st |= JP_ST_RESTART;
 }
 
-// The piece path on the host, the algorithm k_jpeg_pieces runs: the states in vectors, the rounds in Jacobi order (round r
-// reads only round r - 1's exits), the prefix sum, the write pass, the DC pass.  coef is zeroed by the caller.  S = the
-// piece size in bytes, a multiple of 4.  Returns status bits.
-static inline int jpeg_decode_pieces_host(const uint8_t* d, const JpegDesc& D, const JpegTables& T, uint32_t S, int16_t* coef, JpegPieceStats* ps)
+// The piece path on the host, the algorithm k_jpeg_pieces runs, over the frame's segments (one: the scan of a frame without
+// DRI; with `segments`, its restart intervals as the markers at mpos[0 .. nfound) bound them): the states in vectors, the
+// pieces of all segments flattened; the rounds in Jacobi order (round r reads only round r - 1's exits) over all of them
+// until no exit of the frame changes; then per segment the prefix sum, the first marked piece, the write pass and the DC
+// pass.  coef is zeroed by the caller.  S = the piece size in bytes, a multiple of 4.  Returns status bits.
+static inline int jpeg_decode_pieces_host(const uint8_t* d, const JpegDesc& D, const JpegTables& T, uint32_t S, int16_t* coef, JpegPieceStats* ps,
+                                          bool segments = false, const uint32_t* mpos = nullptr, int nfound = 0)
 {
-    const uint32_t np = jpeg_piece_count(D, S), total = jpeg_scan_blocks(D);
-    const uint32_t round_steps = 8 * S + 8, write_steps = 64 * (total + 1);
-    const JpegPieceState first = {D.ent_off, 0};
+    const uint32_t nseg = segments ? (uint32_t)D.nint : 1u;
+    std::vector<JpegSegment> seg(nseg);
+    std::vector<uint32_t> poff(nseg + 1, 0u); // segment j's pieces are poff[j] .. poff[j + 1] of the flattened ones
+    uint32_t maxn = 1;
+    for (uint32_t j = 0; j < nseg; j++) {
+        seg[j] = segments ? jpeg_frame_segment(D, mpos, nfound, j) : jpeg_scan_segment(D);
+        const uint32_t n = jpeg_piece_count(seg[j].b - seg[j].a, S);
+        poff[j + 1] = poff[j] + n;
+        maxn = n > maxn ? n : maxn;
+    }
+    const uint32_t np = poff[nseg];
+    const uint32_t round_steps = 8 * S + 8;
     std::vector<JpegPieceState> cur(np), nxt(np), ent(np), r0(np);
-    std::vector<uint32_t> cnt(np);
-    for (uint32_t i = 0; i < np; i++) { // round 0
-        ent[i] = i ? jpeg_piece_guess(d, D, S, i, np) : first;
-        cur[i] = r0[i] = jpeg_piece_run<false>(d, D, T, ent[i], S, i, np, round_steps, &cnt[i], nullptr, 0, nullptr, nullptr);
+    std::vector<uint32_t> cnt(np), sof(np);
+    for (uint32_t j = 0; j < nseg; j++)
+        for (uint32_t p = poff[j]; p < poff[j + 1]; p++) sof[p] = j;
+    for (uint32_t p = 0; p < np; p++) { // round 0: the first piece of every segment from the true state
+        const JpegSegment& G = seg[sof[p]];
+        const uint32_t i = p - poff[sof[p]], n = poff[sof[p] + 1] - poff[sof[p]];
+        const JpegPieceState first = {G.a, 0};
+        ent[p] = i ? jpeg_piece_guess(d, G, S, i, n) : first;
+        cur[p] = r0[p] = jpeg_piece_run<false>(d, D, T, ent[p], G, S, i, n, round_steps, &cnt[p], nullptr, 0, nullptr, nullptr);
     }
     uint32_t rounds = 1;
-    for (uint32_t r = 1; r < np; r++) { // after round r the exits 0..r are true: round np could change nothing
+    for (uint32_t r = 1; r < maxn; r++) { // after round r the exits 0..r of every segment are true: round max n_j could change nothing
         bool changed = false;
-        for (uint32_t i = 0; i < np; i++) {
-            const JpegPieceState e = i ? cur[i - 1] : first;
-            if (jpeg_piece_same(e, ent[i])) {
-                nxt[i] = cur[i];
+        for (uint32_t p = 0; p < np; p++) {
+            const JpegSegment& G = seg[sof[p]];
+            const uint32_t i = p - poff[sof[p]], n = poff[sof[p] + 1] - poff[sof[p]];
+            const JpegPieceState first = {G.a, 0};
+            const JpegPieceState e = i ? cur[p - 1] : first;
+            if (jpeg_piece_same(e, ent[p])) {
+                nxt[p] = cur[p];
                 continue;
             }
-            ent[i] = e;
-            nxt[i] = jpeg_piece_run<false>(d, D, T, e, S, i, np, round_steps, &cnt[i], nullptr, 0, nullptr, nullptr);
-            changed |= !jpeg_piece_same(nxt[i], cur[i]);
+            ent[p] = e;
+            nxt[p] = jpeg_piece_run<false>(d, D, T, e, G, S, i, n, round_steps, &cnt[p], nullptr, 0, nullptr, nullptr);
+            changed |= !jpeg_piece_same(nxt[p], cur[p]);
         }
         cur.swap(nxt);
         if (!changed) break;
         rounds++;
     }
     int st = 0;
-    uint32_t ndc = 0, B = 0, settled = 0;
-    uint32_t last = np - 1; // the first marked piece: where the serial decode dies or runs out of data
-    for (uint32_t i = 0; i < np; i++) {
-        settled += jpeg_piece_same(r0[i], cur[i]) ? 1u : 0u;
-        if (i < last && (cur[i].w & (JP_PS_ENDED | JP_PS_DEAD))) last = i;
-    }
-    for (uint32_t i = 0; i <= last; i++) {
-        uint32_t done, mine = 0;
-        jpeg_piece_run<true>(d, D, T, i ? cur[i - 1] : first, S, i, np, write_steps, &done, coef, B, &st, &mine);
-        ndc = mine > ndc ? mine : ndc;
-        B += cnt[i];
-    }
-    for (int c = 0; c < D.ncomp; c++) { // differences to predictions, mod 2^16
-        const uint32_t n = jpeg_comp_blocks_in(D, c, ndc);
-        uint16_t pred = 0;
-        for (uint32_t j = 0; j < n; j++) {
-            int16_t* o = coef + jpeg_scan_block_elem(D, jpeg_comp_block(D, c, j));
-            pred = (uint16_t)(pred + (uint16_t)o[0]);
-            o[0] = (int16_t)pred;
+    uint32_t settled = 0;
+    for (uint32_t p = 0; p < np; p++) settled += jpeg_piece_same(r0[p], cur[p]) ? 1u : 0u;
+    for (uint32_t j = 0; j < nseg; j++) {
+        const JpegSegment& G = seg[j];
+        const uint32_t p0 = poff[j], n = poff[j + 1] - p0, write_steps = 64 * (G.blocks + 1);
+        const JpegPieceState first = {G.a, 0};
+        uint32_t last = n - 1; // the first marked piece: where the serial decode of the segment dies or runs out of data
+        for (uint32_t i = 0; i < n; i++)
+            if (i < last && (cur[p0 + i].w & (JP_PS_ENDED | JP_PS_DEAD))) last = i;
+        uint32_t ndc = 0, B = G.first;
+        for (uint32_t i = 0; i <= last; i++) {
+            uint32_t done, mine = 0;
+            jpeg_piece_run<true>(d, D, T, i ? cur[p0 + i - 1] : first, G, S, i, n, write_steps, &done, coef, B, &st, &mine);
+            ndc = mine > ndc ? mine : ndc;
+            B += cnt[p0 + i];
+        }
+        for (int c = 0; c < D.ncomp; c++) { // differences to predictions, mod 2^16, from 0 at the segment's start
+            const uint32_t q0 = jpeg_comp_blocks_in(D, c, G.first), q1 = jpeg_comp_blocks_in(D, c, ndc);
+            uint16_t pred = 0;
+            for (uint32_t q = q0; q < q1; q++) {
+                int16_t* o = coef + jpeg_scan_block_elem(D, jpeg_comp_block(D, c, q));
+                pred = (uint16_t)(pred + (uint16_t)o[0]);
+                o[0] = (int16_t)pred;
+            }
         }
     }
     if (ps) {
@@ -840,9 +898,10 @@ static inline int jpeg_decode_pieces_host(const uint8_t* d, const JpegDesc& D, c
 
 // The twin: coef[plane_total] and planes[plane_total] are scratch the caller provides (coef is zeroed here), bgr = h rows
 // of w * 3 bytes, `stride` apart.  piece_bytes 0: every frame by restart interval; otherwise a frame without DRI goes the
-// piece path with pieces of that size, and *ps (may be null) gets its figures (zeros for a frame by interval).
+// piece path with pieces of that size, and with `segments` a frame with DRI does too, its restart intervals cut into
+// pieces; *ps (may be null) gets the piece path's figures (zeros for a frame by interval).
 static inline void jpeg_decode_host(const uint8_t* d, const JpegDesc& D, const JpegTables& T, int16_t* coef, uint8_t* planes, uint8_t* bgr,
-                                    size_t stride, int* status, uint32_t piece_bytes = 0, JpegPieceStats* ps = nullptr)
+                                    size_t stride, int* status, uint32_t piece_bytes = 0, JpegPieceStats* ps = nullptr, bool segments = false)
 {
     int st = 0;
     memset(coef, 0, (size_t)D.plane_total * sizeof(int16_t));
@@ -851,11 +910,13 @@ static inline void jpeg_decode_host(const uint8_t* d, const JpegDesc& D, const J
     else {
         std::vector<uint32_t> mpos;
         jpeg_find_restarts_host(d, D, &mpos, &st);
-        for (int iv = 0; iv < D.nint; iv++) {
-            uint32_t a, b;
-            jpeg_interval_bytes(D, mpos.data(), (int)mpos.size(), iv, &a, &b);
-            st |= jpeg_decode_interval(d, D, T, a, b, iv, coef);
-        }
+        if (piece_bytes && segments) st |= jpeg_decode_pieces_host(d, D, T, piece_bytes, coef, ps, true, mpos.data(), (int)mpos.size());
+        else
+            for (int iv = 0; iv < D.nint; iv++) {
+                uint32_t a, b;
+                jpeg_interval_bytes(D, mpos.data(), (int)mpos.size(), iv, &a, &b);
+                st |= jpeg_decode_interval(d, D, T, a, b, iv, coef);
+            }
     }
     for (int c = 0; c < D.ncomp; c++) {
         const int ps = D.bw[c] * 8;

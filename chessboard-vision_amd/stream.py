@@ -809,9 +809,22 @@ class BoardPipeline(_BoardMethods):
 
     def set_jpeg_entropy(self, mode, piece_bytes=0):
         """The entropy path of the "mjpeg" decodes: "auto" (pieces for streams without DRI, restart intervals otherwise; the
-        default), "interval" or "pieces", and the piece size in bytes (0: the library's default, otherwise a multiple of 4).
-        The frames do not depend on either (include/cbv.h).  Call between runs."""
+        default), "interval", "pieces" or "segments" (the piece path for every stream, restart intervals cut into pieces), and
+        the piece size in bytes (0: the library's default, otherwise a multiple of 4).  The frames do not depend on either
+        (include/cbv.h).  Call between runs."""
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_entropy(self.h_, N.JPEG_ENTROPY[mode], int(piece_bytes)))
+
+    def set_jpeg_depth(self, n):
+        """How many frames an "mjpeg" submit decodes per launch through one set of scratch buffers (1 to 64, default 8): device
+        memory for throughput (include/cbv.h, cbv_pipeline_set_jpeg_depth).  The frames do not depend on it.  Call between runs."""
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_depth(self.h_, int(n)))
+
+    @property
+    def jpeg_depth(self):
+        n = self.ctx.lib.cbv_pipeline_jpeg_depth(self.h_)
+        if n < 0:
+            self.ctx.check(n)
+        return n
 
     def jpeg_stats(self, slot0, count):
         """The piece path's figures of the streams last decoded into the slots: a [count, 3] uint32 array of pieces, rounds and

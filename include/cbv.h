@@ -659,26 +659,40 @@ CBV_API int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint8_t
 /* The entropy decode has two paths, and the result does not depend on which one runs.
  *   by interval  a lane per restart interval.  A stream without DRI (what a UVC webcam, an IP camera and AVI MJPEG send) is
  *                one interval: one lane.
- *   by piece     for frames without DRI.  The entropy data is cut into pieces of piece_bytes bytes, a lane each.  The state
- *                between two symbols is (byte, bit, block within the MCU, zig-zag index).  Lane 0 starts from the true state,
- *                every other lane from a guess, and each stores the state it leaves its piece with.  In every further round a
- *                lane decodes its piece again from the state the lane before it left, until a round changes nothing.  With
- *                the true state in front of piece 0 that fixpoint is unique, the serial decode's state at every boundary:
- *                after round r the exits of pieces 0..r are true whatever was guessed, so there are at most as many rounds as
- *                pieces, and Huffman codes resynchronise, so there are few.  A prefix sum over the blocks the pieces hold
- *                numbers the blocks, a last pass writes the coefficients with the DC differences, and a per-component scan
- *                sums those.  Coefficients, planes, BGR and status are the interval path's bit for bit, for damaged data as
- *                well, at every piece size.  The zero bits behind the data's end are decoded by one lane, as by interval.
+ *   by piece     A SEGMENT is a stretch of entropy data in front of which the decoder's state is known: the whole scan of a
+ *                frame without DRI, or one restart interval (bit 0, block 0, a DC symbol next, predictions 0).  A segment
+ *                is cut into pieces of piece_bytes bytes, a lane each.  The state between two symbols is (byte, bit, block
+ *                within the MCU, zig-zag index).  The lane of a segment's first piece starts from the true state, every
+ *                other lane from a guess, and each stores the state it leaves its piece with.  In every further round a
+ *                lane decodes its piece again from the state the lane before it IN ITS SEGMENT left, until a round changes
+ *                nothing.  With the true state in front of a segment's piece 0 that fixpoint is unique, the serial decode's
+ *                state at every boundary: after round r the exits of pieces 0..r of every segment are true whatever was
+ *                guessed, so there are at most as many rounds as the longest segment has pieces, and Huffman codes
+ *                resynchronise, so there are few.  Per segment, a prefix sum over the blocks the pieces hold numbers the
+ *                blocks from the segment's first one, a last pass writes the coefficients with the DC differences (no
+ *                block outside the segment's own MCUs, and nothing behind the piece where the serial decode of that
+ *                interval dies or runs out of data), and a per-component scan that starts from 0 at every segment sums the
+ *                differences of the blocks decoded.  Coefficients, planes, BGR and status are the interval path's bit for
+ *                bit, for damaged data as well (markers missing, extra or misnumbered, truncated data, bad codes), at every
+ *                piece size.  The zero bits behind a segment's end are decoded by one lane, as by interval, and no piece
+ *                reads a restart marker.
  * CBV_JPEG_ENTROPY_AUTO (the default) takes pieces for frames without DRI and intervals otherwise; _INTERVAL takes intervals
- * for every frame; _PIECES is AUTO's choice today, reserved for cutting long restart intervals as well.  piece_bytes: 0 = the
- * library's default (64), otherwise a multiple of 4 from 4 to 2^24; small pieces exist for tests (a symbol then spans
- * several pieces, and a piece inside one symbol decodes nothing and passes its entry on). */
+ * for every frame; _PIECES is AUTO's choice: a frame with DRI still goes by interval and reports zero figures; _SEGMENTS takes
+ * the piece path for every frame, a frame with DRI with its restart intervals as segments (segment j = the bytes between
+ * markers j - 1 and j of those found, empty at the data's end where its marker is missing;
+ * n_j = max(1, ceil(bytes / piece_bytes)) pieces), a frame without DRI exactly as _PIECES.  3 is no mode and stays
+ * CBV_ERR_ARG (tests of the piece path hold that).  piece_bytes: 0 = the library's default (64), otherwise a multiple of 4
+ * from 4 to 2^24; small pieces exist for tests (a symbol then spans several pieces, and a piece
+ * inside one symbol decodes nothing and passes its entry on). */
 #define CBV_JPEG_ENTROPY_AUTO 0
 #define CBV_JPEG_ENTROPY_INTERVAL 1
 #define CBV_JPEG_ENTROPY_PIECES 2
+#define CBV_JPEG_ENTROPY_SEGMENTS 4
+/* By segments: pieces = the sum of the n_j, rounds <= the largest n_j, settled_round0 >= the intervals (every first piece
+ * is true in round 0). */
 typedef struct {
     uint32_t pieces;          /* pieces of the frame, ceil(entropy_length / piece_bytes); 0: the frame was decoded by interval */
-    uint32_t rounds;          /* rounds until nothing changed, round 0 counted: 1 <= rounds <= pieces */
+    uint32_t rounds;          /* rounds until no exit of the frame changed, round 0 counted: 1 <= rounds <= pieces */
     uint32_t settled_round0;  /* pieces whose exit state of round 0 was already the true one */
 } cbv_jpeg_decode_stats;
 /* cbv_jpeg_decode_host / cbv_jpeg_decode with the path chosen; stats may be NULL.  The plain calls are these with AUTO, 0, NULL. */
@@ -698,9 +712,9 @@ CBV_API int cbv_jpeg_decode_ex(cbv_ctx* ctx, const uint8_t* data, size_t n, uint
  * content) since the cache was last emptied (CBV_ERR_UNSUPPORTED; a camera's tables do not change).  Otherwise it copies no
  * more than each slot's used bytes (rounded up to 256) and enqueues the decode into the BGR frame ring on the copy stream
  * behind the copy, with the ordering promises of the other formats.  Frames of different sampling and restart interval may
- * share a submit.  The decode's device scratch is sized when the format is set, for chunks of 8 frames in the sampling that
- * needs most; submit allocates nothing.  Motion-JPEG is never raw mode: a pipeline without enhancement keeps its BGR ring, as
- * for BGR input, and the decode fills it.  Until the copy has completed (cbv_pipeline_wait_submitted) the slots' bytes and
+ * share a submit.  The decode's device scratch is sized when the format is set, for chunks of cbv_pipeline_jpeg_depth
+ * frames (8 unless set) in the sampling that needs most; submit allocates nothing.  Motion-JPEG is never raw mode: a
+ * pipeline without enhancement keeps its BGR ring, as for BGR input, and the decode fills it.  Until the copy has completed (cbv_pipeline_wait_submitted) the slots' bytes and
  * lengths belong to it. */
 CBV_API uint32_t* cbv_pipeline_host_jpeg_lengths(cbv_pipeline* p);
 CBV_API int cbv_pipeline_set_jpeg_slot_bytes(cbv_pipeline* p, size_t bytes);
@@ -710,12 +724,27 @@ CBV_API int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t* d
 /* the status words (CBV_JPEG_*) of the streams last decoded into the slots; waits for the submitted decodes */
 CBV_API int cbv_pipeline_jpeg_status(cbv_pipeline* p, int slot0, int count, int32_t* status);
 /* The entropy path of the pipeline's decodes (submit and upload_jpeg) and its piece size; call between runs.  The piece
- * path's device scratch, 8 x ceil(slot bytes / piece_bytes) piece states, is sized here and when the format is set; submit
- * still allocates nothing.  When the scratch cannot be allocated the call fails and the setting that was stays (by interval
- * if its scratch cannot be had back either).  CBV_ERR_STATE on a board handle. */
+ * path's device scratch, depth x ceil(slot bytes / piece_bytes) piece states (by segments ceil(w / 8) x ceil(h / 8) more
+ * per frame, and three words per possible interval), is sized here and when the format is set; submit still allocates
+ * nothing.  When the scratch cannot be allocated the call fails and the setting that was stays with its scratch.
+ * CBV_ERR_STATE on a board handle. */
 CBV_API int cbv_pipeline_set_jpeg_entropy(cbv_pipeline* p, int mode, uint32_t piece_bytes);
 /* the figures of the streams last decoded into the slots (zeros for a frame decoded by interval); waits like cbv_pipeline_jpeg_status */
 CBV_API int cbv_pipeline_jpeg_stats(cbv_pipeline* p, int slot0, int count, cbv_jpeg_decode_stats* stats);
+/* The decode depth: how many frames a Motion-JPEG submit decodes per launch through one set of scratch buffers, 1 to 64,
+ * 8 unless set.  A frame on the piece path is one workgroup, so the depth is how many of them a launch puts on the GPU.
+ * Frames, status, figures and detector results do not depend on it.  Call between runs: it waits for the copy stream and
+ * sizes the coefficient, plane, marker, piece and segment scratch anew, all of which scale with it; before the format is
+ * set it is only stored.  The cost: per frame of depth, 3 bytes per sample of the frame in the sampling that needs most
+ * (4:4:4 padded to 16 x 16 MCUs: 18.8 MB at 1080p) and 4 bytes per possible restart interval (ceil(w / 8) x ceil(h / 8) of
+ * them), plus the piece states (36 bytes per piece; by segments 40 per piece and 12 more per possible interval, the
+ * segment words; the piece counts are cbv_pipeline_set_jpeg_entropy's).  CBV_ERR_ARG outside 1..64, CBV_ERR_STATE on a board handle; when the scratch
+ * cannot be allocated the call fails and the depth that was stays with its scratch. */
+#define CBV_JPEG_DEPTH_DEFAULT 8
+#define CBV_JPEG_DEPTH_MAX 64
+CBV_API int cbv_pipeline_set_jpeg_depth(cbv_pipeline* p, int frames);
+/* the depth set (or the default); negative: an error */
+CBV_API int cbv_pipeline_jpeg_depth(cbv_pipeline* p);
 
 /* ------------------------------------------------------------------ */
 /* several boards seen by one camera                                   */

@@ -1,14 +1,17 @@
 """Host-fed throughput of the Motion-JPEG ingest beside NV12 and Bayer, in one session (never bench.py's `value`): 1080p
 frames sit in the pinned host ring; batch k+1 is copied and decoded (cbv_pipeline_submit) while batch k runs.
 
-    python tools/jpeg_timing.py [--streams FILE.npz] [--make-streams FILE.npz] [--reps 2] [--entropy auto|interval|pieces]
-                                [--piece-bytes N]
+    python tools/jpeg_timing.py [--streams FILE.npz] [--make-streams FILE.npz] [--reps 2]
+                                [--entropy auto|interval|pieces|segments] [--piece-bytes N] [--depth N]
 
-Per variant (quality 75 / 90, 4:2:2 / 4:2:0, without DRI and with a restart interval of one MCU row) it prints the submit-only
+Per variant (quality 75 / 90, 4:2:2 / 4:2:0; without DRI, with a restart interval of one MCU row ("-dri") and with one of
+eight MCU rows ("-dri8": a few long intervals, as a hardware encoder emits them) it prints the submit-only
 rate (copy + decode), the overlapped submit || run rate, the bytes that crossed the link per frame, and the latency of ONE
 frame in flight (submit of a single slot until its decode has completed).  --entropy and --piece-bytes choose the entropy
-path (BoardPipeline.set_jpeg_entropy; "interval" is one lane for a stream without DRI), and every JPEG row ends with the
-piece path's figures for the streams of the variant: pieces, rounds and the share of pieces settled in round 0.  The
+path (BoardPipeline.set_jpeg_entropy; "interval" is one lane for a stream without DRI, "segments" cuts restart intervals
+into pieces too), --depth the frames a submit decodes per launch (BoardPipeline.set_jpeg_depth), and every JPEG row ends
+with the decode's scratch in bytes (include/cbv.h's formula for the row's slot size) and the piece path's figures for the
+streams of the variant: pieces, rounds and the share of pieces settled in round 0.  The
 per-kernel times come from a kernel trace of this script (rocprofv3 --kernel-trace --stats).
 
 Encoding 1080p frames with tests/ref_jpeg.py takes a few seconds each, so the streams can be made once on any machine
@@ -28,17 +31,18 @@ ap.add_argument("--streams", help="npz of encoded streams (from --make-streams)"
 ap.add_argument("--make-streams", help="encode the streams into this npz and exit (needs no GPU)")
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--frames", type=int, default=2, help="distinct source frames per variant")
-ap.add_argument("--entropy", default="auto", choices=("auto", "interval", "pieces"))
+ap.add_argument("--entropy", default="auto", choices=("auto", "interval", "pieces", "segments"))
+ap.add_argument("--depth", type=int, default=0, help="frames a Motion-JPEG submit decodes per launch (0: the library's default)")
 ap.add_argument("--piece-bytes", type=int, default=0, help="piece size of the piece path (0: the library's default)")
 ap.add_argument("--only", help="comma-separated variants to run (default: bgr, nv12, bayer_rggb and every JPEG variant)")
 args = ap.parse_args()
 
 W, H, HALF, ROUNDS = 1920, 1080, 64, 4
-VARIANTS = [(q, s, dri) for q in (75, 90) for s in ("422", "420") for dri in (0, 1)]
+VARIANTS = [(q, s, dri) for q in (75, 90) for s in ("422", "420") for dri in (0, 1, 8)]  # dri: the restart interval in MCU rows
 
 
 def vname(q, s, dri):
-    return "q%d-%s-%s" % (q, s, "dri" if dri else "nodri")
+    return "q%d-%s-%s" % (q, s, "dri8" if dri == 8 else "dri" if dri else "nodri")
 
 
 def make_streams(frames):
@@ -47,7 +51,7 @@ def make_streams(frames):
     for q, s, dri in VARIANTS:
         row = W // 16  # MCUs per row, both samplings
         for i, f in enumerate(frames):
-            out["%s_%d" % (vname(q, s, dri), i)] = np.frombuffer(R.encode_image(f, quality=q, sampling=s, dri=row if dri else 0), np.uint8)
+            out["%s_%d" % (vname(q, s, dri), i)] = np.frombuffer(R.encode_image(f, quality=q, sampling=s, dri=row * dri), np.uint8)
     return out
 
 
@@ -64,6 +68,8 @@ n = 2 * HALF
 p = BoardPipeline(W, H, n)
 p.configure(S.scaled_corners(W, H), profile=S.SHIPPED_PROFILE, grid_lines=(S.CALIB_GRID_X, S.CALIB_GRID_Y), **S.SHIPPED_DETECTOR)
 p.set_jpeg_entropy(args.entropy, args.piece_bytes)
+if args.depth:
+    p.set_jpeg_depth(args.depth)
 if args.streams:
     z = np.load(args.streams)
     streams = {k: z[k] for k in z.files}
@@ -81,6 +87,16 @@ def nv12(f):
     q = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
     y, u, v = q(16 + 0.257 * r + 0.504 * g + 0.098 * b), q(128 - 0.148 * r - 0.291 * g + 0.439 * b), q(128 + 0.439 * r - 0.368 * g - 0.071 * b)
     return np.concatenate([y, np.stack((u[::2, ::2], v[::2, ::2]), axis=-1).reshape(H // 2, W)])
+
+
+def scratch_bytes(slot_bytes):
+    """the decode's device scratch for the pipeline's settings (include/cbv.h, cbv_pipeline_set_jpeg_depth)"""
+    pw, ph = (W + 15) // 16 * 16, (H + 15) // 16 * 16
+    max_int = (W + 7) // 8 * ((H + 7) // 8)
+    S = 0 if args.entropy == "interval" else args.piece_bytes or 64
+    seg = args.entropy == "segments"
+    pieces = (-(-slot_bytes // S) + (max_int if seg else 0)) if S else 0
+    return p.jpeg_depth * (3 * 3 * pw * ph + 4 * max_int + pieces * (40 if seg else 36) + (4 * (3 * max_int + 1) if seg else 0))
 
 
 def sync():
@@ -135,16 +151,17 @@ def measure(fmt):
     t_one = (time.perf_counter() - t0) / 20
     frames = ROUNDS * n
     stats = p.jpeg_stats(0, nsrc) if p.input_format == "mjpeg" else None
-    return frames / t_copy, frames / t_ovl, link, t_one, stats
+    scratch = scratch_bytes(p.ctx.lib.cbv_pipeline_host_slot_bytes(p.h_)) if p.input_format == "mjpeg" else 0
+    return frames / t_copy, frames / t_ovl, link, t_one, stats, scratch
 
 
 formats = args.only.split(",") if args.only else ["bgr", "nv12", "bayer_rggb"] + [vname(*v) for v in VARIANTS]
 for rep in range(args.reps):
     for fmt in formats:
-        c, o, link, one, stats = measure(fmt)
-        tail = ""
+        c, o, link, one, stats, scratch = measure(fmt)
+        tail = "   depth %d scratch %d bytes" % (p.jpeg_depth, scratch) if scratch else ""
         if stats is not None and stats[:, 0].any():
-            tail = "   pieces %s rounds %s settled in round 0 %.2f" % (stats[:, 0].tolist(), stats[:, 1].tolist(), stats[:, 2].sum() / stats[:, 0].sum())
+            tail += "   pieces %s rounds %s settled in round 0 %.2f" % (stats[:, 0].tolist(), stats[:, 1].tolist(), stats[:, 2].sum() / stats[:, 0].sum())
         print("[%s, rep %d] submit only %8.0f frames/s   submit || run %8.0f frames/s   link %9.0f bytes/frame   one frame in flight %7.1f us%s"
               % (fmt, rep + 1, c, o, link, one * 1e6, tail), flush=True)
 p.close()
