@@ -1,5 +1,8 @@
 """Python face of cbv_squares: device-resident per-square planes (current
-gray, reference, mean, variance) for an ordered set of board squares."""
+gray, reference, mean, variance) for an ordered set of board squares.
+`get` also reads plane 4, sqrt(variance) as the statistics kernels read it;
+it is derived from the variance (writing VAR refreshes it) and read-only:
+`set(4, ...)` raises with CBV_ERR_ARG."""
 import ctypes as C
 
 import numpy as np

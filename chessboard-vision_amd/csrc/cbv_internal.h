@@ -78,6 +78,7 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     unsigned long long tag = 0; // what the owner knows about the contents; 0 after every (re)allocation
+    template <class T> T* as() const { return (T*)p; }
 };
 
 struct ProfSlot {
@@ -122,7 +123,7 @@ struct cbv_ctx {
     // pinned staging for the small records the one-frame-per-call (class API) entry points move in either direction
     // (square descriptors, worklists, statistics, HoughCircles results): a copy from / to pinned memory is one DMA
     // (12 us for 16 KB against 26 us through the runtime's pageable path); guarded by `mu`, and every call that uses
-    // it synchronises before it returns
+    // it synchronises before it returns, with an error code too (CBV_ENTER_DRAINED)
     u8* h_stage = nullptr;
     size_t h_stage_cap = 0;
     int debug_poison = 0; // tests: fill partially uploaded staging buffers with 0xA5 first (cbv_debug_poison)
@@ -154,6 +155,21 @@ int cbv_fail(cbv_ctx* ctx, int code, const char* fmt, ...);
 #define CBV_ENTER(ctx)                                   \
     std::lock_guard<std::recursive_mutex> lock__((ctx)->mu); \
     CBV_HIP(ctx, hipSetDevice((ctx)->device))
+
+// CBV_ENTER for an entry point that copies from or to the caller's memory or h_stage on ctx->stream: it returns
+// `CBV_DONE(rc)` where it is finished, and every return with an error code (RC, CBV_HIP and cbv_fail included) waits for
+// the stream first, so nothing is in flight from or to memory the caller, or the next call, may reuse.  The wait's own
+// result is dropped: the first error is the one reported.  A successful call never reaches the wait.
+struct StreamDrain {
+    cbv_ctx* ctx;
+    bool armed = true;
+    int done(int rc) { armed = rc != CBV_OK; return rc; }
+    ~StreamDrain() { if (armed) (void)hipStreamSynchronize(ctx->stream); }
+};
+#define CBV_ENTER_DRAINED(ctx) \
+    CBV_ENTER(ctx);            \
+    StreamDrain drain__{ctx}
+#define CBV_DONE(rc) drain__.done(rc)
 
 int dev_ensure(cbv_ctx* ctx, DevBuf* b, size_t bytes);
 void dev_free(DevBuf* b);
@@ -532,8 +548,10 @@ struct DetectMasks {
     int check_given = 0; // squares_to_check is not None
     int use_delta = 1;
     double change_threshold = 25.0;
-    u8* dflags = nullptr; // out, per square: 1 has_changed_visual, 2 should_process, 4 detect_piece is evaluated, 8 std >= 15
+    u8* dflags = nullptr; // out, per square: the CBV_GATE_* bits
 };
+// the bits of a dflags byte as k_squares_pre5_stats packs them (k_squares.hip, "dm.dflags[blockIdx.x] =")
+enum : u8 { CBV_GATE_CHANGED = 1, CBV_GATE_PROCESS = 2, CBV_GATE_EVALUATED = 4, CBV_GATE_STD_OK = 8 }; // (std >= 15: HoughCircles ran)
 int launch_squares_preprocess(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n,
                               const int* coef_dev, int blur_k, u8* gray, size_t gray_frame_stride, int batch, int max_px = 0);
 int launch_squares_stats(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride,
@@ -772,7 +790,7 @@ int launch_piece_sweep_eval(cbv_ctx* ctx, const SquareDesc* descs, int n, const 
                             cbv_piece_sweep_summary* sums, int stat_stride = 0);
 
 // ---------------------------------------------------------------------------
-// Helpers of the host entry points (cbv_api.cpp) that the device-resident pipeline (cbv_pipeline*.cpp) shares
+// Helpers of the host entry points (cbv_api.cpp, cbv_squares.cpp) that the device-resident pipeline (cbv_pipeline*.cpp) shares
 // ---------------------------------------------------------------------------
 #define RC(x)             \
     do {                  \

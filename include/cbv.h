@@ -14,7 +14,9 @@
  *   - images are uint8, HWC, BGR, row stride in bytes given explicitly
  *     (numpy frames from cv2.VideoCapture; views into them are fine).
  *   - "host" entry points copy in, run the kernels, copy out and synchronise;
- *     the library keeps no host pointer after returning.
+ *     the library keeps no host pointer after returning, and no copy from or
+ *     to the caller's memory is still in flight then, with an error code as
+ *     with CBV_OK (the cbv_pipeline_* ring calls document their own rules).
  *   - "dev" entry points take device pointers, enqueue on the context's
  *     stream and do not synchronise.
  *   - one cbv_ctx per GPU is the intended use.  A ctx is ONE queue of work (shared scratch buffers, one current
@@ -234,7 +236,9 @@ typedef struct {
     float circles[CBV_HOUGH_KEEP][4]; /* first circles in HoughCircles' order: x, y, r, support */
 } cbv_hough_result;
 CBV_API int cbv_squares_hough(cbv_squares* sq, const cbv_hough_params* prm, cbv_hough_result* out);
-/* download / upload per-square planes (tight w*h): which = 0 gray(u8) 1 ref(u8) 2 mean(f32) 3 var(f32) */
+/* download / upload per-square planes (tight w*h): which = 0 gray(u8) 1 ref(u8) 2 mean(f32) 3 var(f32), and for
+   cbv_squares_get alone 4 sqrt(var)(f32) as the statistics kernels read it.  Plane 4 is derived: writing plane 3
+   refreshes it, and cbv_squares_set(4) returns CBV_ERR_ARG and writes nothing. */
 CBV_API int cbv_squares_get(cbv_squares* sq, int which, int index, void* out);
 CBV_API int cbv_squares_set(cbv_squares* sq, int which, int index, const void* in);
 CBV_API int cbv_squares_geometry(cbv_squares* sq, int index, int* w, int* h);

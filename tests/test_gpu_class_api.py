@@ -400,3 +400,106 @@ def test_one_call_paths_take_the_second_hough_pass_when_a_square_needs_it(gpu_ct
         r_ref, v_ref = ref.detect_all_pieces(sq)
         assert v == v_ref and r == r_ref
         assert cd.detect_changes_detailed(sq) == cref.detect_changes_detailed(sq)
+
+
+def _board64(seed):
+    """A 64 x 64 single-channel board, its cbv_host_image and its 64 squares of 8 x 8: the smallest geometry that fills
+    every bit of the 64-bit masks and the whole worklist."""
+    from chessboard_vision_amd._squares import _image_of
+    from chessboard_vision_amd.grid_extractor import SquareLayout
+    board = np.random.default_rng(seed).integers(0, 256, (64, 64), dtype=np.uint8)
+    lay = SquareLayout([(c, r) for r in range(8) for c in range(8)], [(c * 8, r * 8, 8, 8) for r in range(8) for c in range(8)])
+    return board, _image_of(board), lay
+
+
+@pytest.mark.parametrize("poisoned", [False, True])
+def test_an_error_after_staging_leaves_the_detector_usable(gpu_ctx, poisoned):
+    """cbv_squares_detect_changes with 4 ROIs on a detector calibrated for 64 fails with CBV_ERR_STATE after the image
+    and the descriptors were enqueued.  The caller overwrites its image at once, and the detector goes on: its results
+    and planes 0-4 equal those of a detector on the same context that never saw the failing call.  The race an
+    undrained error return would open is not deterministic, so this pins the contract and the state after the error;
+    the drain itself is verified by reading the one place it lives (StreamDrain in cbv_internal.h)."""
+    from chessboard_vision_amd import _native as N
+    from chessboard_vision_amd._squares import SquareSet
+    first, img1, lay = _board64(21)
+    img1_was, img2 = _board64(21)[1], _board64(22)[1]  # (each keeps its array alive)
+    cp = N.ChangeParams()
+    cp.z_threshold, cp.select, cp.circle_threshold, cp.hough = 2.5, lay.all_mask, 0.6, N.HoughParams(1.2, 100.0, 25.0, 0.2, 0.55)
+    dp = N.DetectParams()
+    dp.change_threshold, dp.circle_threshold, dp.use_delta, dp.hough, dp.has_ref = 25.0, 0.6, 1, cp.hough, lay.all_mask
+    lib = gpu_ctx.lib
+    gpu_ctx.check(lib.cbv_debug_poison(gpu_ctx.h, 1 if poisoned else 0))
+    try:
+        a, b = SquareSet(gpu_ctx), SquareSet(gpu_ctx)
+        a.load_image(img1, lay, 5)
+        a.calibrate(100.0)
+        cout = np.zeros(64, N.record_dtype(N.ChangeResult))
+        assert lib.cbv_squares_detect_changes(a.h, img1, lay.rois, 4, 5, cp, cout.ctypes.data) == -4
+        assert b"geometry changed since calibrate" in lib.cbv_last_error(gpu_ctx.h)
+        first[:] = np.random.default_rng(23).integers(0, 256, (64, 64), dtype=np.uint8)  # the caller reuses its image at once
+        b.load_image(img1_was, lay, 5)  # the valid calls alone
+        b.calibrate(100.0)
+        got, want = [], []
+        for ss, rows in ((a, got), (b, want)):
+            ss.load_image(img2, lay, 5)
+            ss.set_ref()
+            ss.calibrate(100.0)
+            rows.append(ss.detect_changes(img2, lay, 5, cp))
+            rows.append(ss.detect_changes(img1, lay, 5, cp))  # the overwritten array, as both detectors see it now
+            rows.append(ss.detect_all(img1, lay, dp))
+        assert got == want
+        # (the calls did something: nothing changed against the model's own image; noise against noise changes most
+        # squares, which HoughCircles then runs on; without cached results every square is evaluated)
+        assert not any(r[0] for r in got[0]) and sum(r[0] for r in got[1]) > 32 and all(r[4] == 1 for r in got[2])
+        for pos in lay.keys:
+            for which in range(5):
+                assert np.array_equal(a.get(which, pos), b.get(which, pos)), (which, pos)
+        assert np.array_equal(a.get(3, (7, 7)), np.full((8, 8), 100.0, np.float32))
+    finally:
+        gpu_ctx.check(lib.cbv_debug_poison(gpu_ctx.h, 0))
+
+
+def test_single_channel_board_through_the_one_call_paths(gpu_ctx):
+    """A gray board (views of one 2-D array) takes the one-call entry points, whose fused preprocess + statistics kernel
+    stages BGR pixels only: the library then runs the two launches it fuses.  Same results as the packed-view path
+    (squares that own their pixels) of the same classes."""
+    from chessboard_vision_amd.change_detector import ChangeDetector
+    from chessboard_vision_amd.piece_detector import PieceDetector
+    boards = [_board64(seed)[0] for seed in (41, 42)]
+    boards.append(np.full((64, 64), 90, np.uint8))
+    boards[2][18:30, 34:46] = 230  # a bright blob over four squares of a flat board
+    lay = _board64(0)[2]
+    views = [{k: b[y:y + h, x:x + w] for k, (x, y, w, h) in zip(lay.keys, lay.rects)} for b in boards]
+    copies = [{k: v.copy() for k, v in sq.items()} for sq in views]
+    for blur in (5, 3):
+        fast, slow, cf, cs = PieceDetector(), PieceDetector(), ChangeDetector(), ChangeDetector()
+        cf.blur_kernel = cs.blur_kernel = blur
+        cf._kernel = cs._kernel = blur
+        fast.update_references(views[2])
+        slow.update_references(copies[2])
+        cf.calibrate(views[2])
+        cs.calibrate(copies[2])
+        for sq, cp in zip(views, copies):
+            assert fast.detect_all_pieces(sq) == slow.detect_all_pieces(cp)
+            got = cf.detect_changes_detailed(sq)
+            assert got == cs.detect_changes_detailed(cp)
+        assert got == {}  # the calibration board itself came last
+
+
+def test_the_sd_plane_is_read_only(gpu_ctx):
+    """Plane 4, sqrt(variance) as the statistics kernels read it, is derived from plane 3: writing it is refused with
+    CBV_ERR_ARG and changes nothing, and writing plane 3 still refreshes it (np.sqrt on float32, bit for bit)."""
+    from chessboard_vision_amd._squares import SquareSet
+    _, img, lay = _board64(31)
+    ss = SquareSet(gpu_ctx)
+    ss.load_image(img, lay, 5)
+    ss.calibrate(100.0)
+    pos = (5, 2)
+    var3, sd4 = ss.get(3, pos), ss.get(4, pos)
+    assert sd4.dtype == np.float32 and np.array_equal(sd4, np.sqrt(var3))
+    with pytest.raises(RuntimeError, match=r"read-only.*\(code -1\)"):
+        ss.set(4, pos, np.full((8, 8), 7.0, np.float32))
+    assert np.array_equal(ss.get(3, pos), var3) and np.array_equal(ss.get(4, pos), sd4)
+    var = np.random.default_rng(32).uniform(0.5, 900.0, (8, 8)).astype(np.float32)
+    ss.set(3, pos, var)
+    assert np.array_equal(ss.get(3, pos), var) and np.array_equal(ss.get(4, pos), np.sqrt(var))
