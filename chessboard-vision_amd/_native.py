@@ -282,6 +282,21 @@ FMT_BAYER_RGGB, FMT_BAYER_BGGR, FMT_BAYER_GRBG, FMT_BAYER_GBRG = 0x04, 0x14, 0x2
 BAYER_FORMATS = {"bayer_rggb": FMT_BAYER_RGGB, "bayer_bggr": FMT_BAYER_BGGR, "bayer_grbg": FMT_BAYER_GRBG,
                  "bayer_gbrg": FMT_BAYER_GBRG}                 # ring slots [h, w]
 
+# cbv_pipeline_set_jpeg_planes: the largest sampling a slot of the plane ring holds (gray < 4:2:0 < 4:2:2 < 4:4:4)
+JPEG_PLANES = {"off": 0, "gray": 1, "420": 2, "422": 3, "444": 4}
+
+
+def jpeg_planes_id(planes):
+    """False / None -> off, True -> "444", or one of the names of JPEG_PLANES."""
+    if planes is None or planes is False:
+        return 0
+    if planes is True:
+        return JPEG_PLANES["444"]
+    if isinstance(planes, str) and planes.lower() in JPEG_PLANES:
+        return JPEG_PLANES[planes.lower()]
+    raise ValueError("planes %r: False, True (= \"444\"), \"444\", \"422\", \"420\" or \"gray\"" % (planes,))
+
+
 FMT_MJPEG = 0x08  # one JPEG stream per frame: jpeg_to_bgr, BoardPipeline.set_input_format("mjpeg"); has no raw_frame() layout
 JPEG_BAD_CODE, JPEG_NO_DATA, JPEG_RESTART = 1, 2, 4
 
@@ -444,6 +459,10 @@ def load():
         "cbv_pipeline_jpeg_stats": (i32, [vp, i32, i32, vp]),
         "cbv_pipeline_set_jpeg_depth": (i32, [vp, i32]),
         "cbv_pipeline_jpeg_depth": (i32, [vp]),
+        "cbv_pipeline_set_jpeg_planes": (i32, [vp, i32]),
+        "cbv_pipeline_jpeg_planes": (i32, [vp]),
+        "cbv_jpeg_plane_slot_bytes": (C.c_size_t, [i32, i32, i32]),
+        "cbv_warp_jpeg": (i32, [vp, vp, C.c_size_t, P(ColorProfile), vp, i32, i32, i32, u8p, i32, P(C.c_int32)]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

@@ -58,13 +58,34 @@ def warp_image(img, points, display_size=(1280, 720), margin=100):
     return warped, matrix, board_size
 
 
+def warp_jpeg(data, M, dsize, profile=None, rot180=False, out=None):
+    """warp_perspective_profiled(jpeg_to_bgr(data), M, dsize, profile, rot180), byte for byte, sampled from the decoded planes
+    with the BGR frame never made (include/cbv.h, cbv_warp_jpeg).  `data`: one baseline JPEG stream, bytes or a uint8 array.
+    Returns (warped, status), status = the decode's status word (jpeg_decode).  `out`: a uint8 [dh, dw, 3] array to write."""
+    c = N.context()
+    a = _jpeg_bytes(data)
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if out is None:
+        out = np.empty((dh, dw, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.shape == (dh, dw, 3) and out.strides[1:] == (3, 1)
+    st = C.c_int32(0)
+    c.check(c.lib.cbv_warp_jpeg(c.h, N.ptr(a), a.size, N.ColorProfile.from_dict(profile), N.ptr(M), dw, dh, 1 if rot180 else 0, N.ptr(out),
+                                out.strides[0], C.byref(st)))
+    return out, int(st.value)
+
+
 def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr"):
     """warp_perspective(ImageEnhancer(profile).apply_color_profile(img), M, dsize, rot180), byte for byte, in one kernel: the
     profile is applied to the four source pixels each destination pixel blends (include/cbv.h, cbv_warp_color_profile).
     `profile`: a dict with the keys of color_profile.json, `None` / `{}` = no profile.
     `fmt` other than "bgr": `img` is a camera-native frame in the layout yuv_to_bgr / bayer_to_bgr take, and the result is
-    that of the converted frame, with neither the BGR frame nor the profiled frame made (cbv_warp_color_profile_raw)."""
+    that of the converted frame, with neither the BGR frame nor the profiled frame made (cbv_warp_color_profile_raw).
+    `fmt` "mjpeg": `img` is one baseline JPEG stream (bytes or a uint8 array), and the result is that of jpeg_to_bgr's frame,
+    sampled from the decoded planes (cbv_warp_jpeg)."""
     c = N.context()
+    if isinstance(fmt, str) and fmt.lower() == "mjpeg":
+        return warp_jpeg(img, M, dsize, profile, rot180)[0]
     if N.format_id(fmt) != N.FMT_BGR:
         raw, w, h, keep = N.raw_frame(img, fmt)
         M = np.ascontiguousarray(M, dtype=np.float64)

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libcbv_hip.so")
 SOURCES = ["cbv_ctx.cpp", "cbv_api.cpp", "cbv_squares.cpp", "cbv_pipeline.cpp", "cbv_pipeline_run.cpp", "cbv_pipeline_ingest.cpp", "cbv_pipeline_sweep.cpp", "cbv_pipeline_session.cpp",
-           "cbv_tables.cpp", "k_enhance.hip", "k_bilateral.hip", "k_warp.hip", "k_warp_raw_profile.hip", "k_analysis.hip",
+           "cbv_tables.cpp", "k_enhance.hip", "k_bilateral.hip", "k_warp.hip", "k_warp_raw_profile.hip", "k_warp_jpeg.hip", "k_analysis.hip",
            "k_squares.hip", "k_hough.hip", "k_canny.hip", "k_ingest.hip", "k_session.hip", "k_sweep.hip", "k_piece_sweep.hip", "chess_rules.cpp", "contours.cpp",
            "k_jpeg.hip", "cbv_jpeg.cpp"]
 HEADERS = ["cbv_internal.h", "cbv_pipeline.h", "cbv_device.h", "cbv_profile_px.h", "cbv_yuv.h", "cbv_bayer.h", "warp_gather.h", "chess_core.h", "session_core.h", "noise_core.h", "change_blur.h", "sweep_core.h", "hough_passes.h", "piece_sweep_core.h", "jpeg_core.h", os.path.join("..", "..", "include", "cbv_chess.h"), os.path.join("..", "..", "include", "cbv.h")]

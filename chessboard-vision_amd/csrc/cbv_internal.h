@@ -446,8 +446,9 @@ int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlane
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
 
 // What the warp samples (k_warp.hip): the frames of a batch, frame 0's pointers.
+struct JpegDesc;
 struct WarpSrc {
-    enum Kind { BGR, PROFILE, YUV, BAYER } kind;
+    enum Kind { BGR, PROFILE, YUV, BAYER, JPEG } kind;
     Geom g;                    // the frames' width and height; BGR, PROFILE: their strides too
     const u8* bgr;             // BGR, PROFILE
     NormSrc norm;              // BGR: cv2.normalize's byte map applied to the taps (none: the plain warp)
@@ -456,8 +457,11 @@ struct WarpSrc {
     size_t dst_profile_stride;
     RawPlanes planes;          // YUV, BAYER: in memory order
     RawGeom r;                 // (fmt = CBV_FMT_BGR for BGR and PROFILE)
+    const u8* jpeg_planes;     // JPEG: the decoded planes of frame 0, frame f's jpeg_plane_stride * f bytes behind
+    size_t jpeg_plane_stride;
+    const JpegDesc* jpeg_descs; // JPEG: device, frame 0's; each frame has its own layout
     bool raw() const { return kind == YUV || kind == BAYER; }
-    bool profiled() const { return kind == PROFILE || (raw() && ptabs); } // the profile kernels' tiling (WP_ROWS rows a workgroup)
+    bool profiled() const { return kind == PROFILE || ((raw() || kind == JPEG) && ptabs); } // the profile kernels' tiling (WP_ROWS rows a workgroup)
 };
 // BGR frames (k_warp), the taps through `norm`
 static inline WarpSrc warp_src_bgr(const u8* src, Geom g, NormSrc norm)
@@ -508,6 +512,26 @@ static inline WarpSrc warp_src_raw(RawPlanes planes, RawGeom r, Geom g)
 static inline WarpSrc warp_src_raw_profile(RawPlanes planes, RawGeom r, Geom g, const ProfileTabs* ptabs, int np = 1, size_t dst_profile_stride = 0)
 {
     WarpSrc s = warp_src_raw(planes, r, g);
+    s.ptabs = ptabs;
+    s.np = np;
+    s.dst_profile_stride = dst_profile_stride;
+    return s;
+}
+// The decoded planes of Motion-JPEG frames (k_warp_jpeg.hip): k_jpeg_color followed by the warp (with ptabs: and the colour
+// profile in between), byte for byte, with no BGR frame; g = the frames' width and height, which every descriptor has too.
+// A chroma window's 4-byte load reaches at most 3 bytes past the last plane's last row: callers keep >= 4 readable bytes
+// behind the last frame's planes (the pipeline's plane ring has 256).  ptabs / np / dst_profile_stride as warp_src_profile
+// takes them.  Counted as CBV_K_WARP_YUV.
+static inline WarpSrc warp_src_jpeg(const u8* planes, size_t plane_stride, const JpegDesc* descs, Geom g, const ProfileTabs* ptabs = nullptr, int np = 1,
+                                    size_t dst_profile_stride = 0)
+{
+    WarpSrc s = {};
+    s.kind = WarpSrc::JPEG;
+    s.g = g;
+    s.r.fmt = CBV_FMT_MJPEG;
+    s.jpeg_planes = planes;
+    s.jpeg_plane_stride = plane_stride;
+    s.jpeg_descs = descs;
     s.ptabs = ptabs;
     s.np = np;
     s.dst_profile_stride = dst_profile_stride;
@@ -736,6 +760,10 @@ int launch_warp_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int m
 int launch_warp_raw_profile(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
                             size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2);
 int launch_warp_raw_profile_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
+// ... and a source of JPEG planes (warp_src_jpeg), with a profile or without: k_warp_jpeg.hip
+int launch_warp_jpeg(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
+                     int batch, u32* zero_word, u32* zero_word2);
+int launch_warp_jpeg_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);
@@ -875,4 +903,7 @@ inline size_t jpeg_seg_words(size_t intervals) { return intervals * JPEG_SEG_WOR
 // zeroes coef, status, nfound, stats and the segment scratch, then the kernels on ctx->stream; total_intervals = ioff[nframes],
 // any_dri / any_pieces: a frame has restart intervals / goes the piece path, max_blocks = the largest plane_total / 64,
 // max_w x max_h = the largest frame
+// B.bgr null: the decode stops at the planes (k_jpeg_color is not launched)
 int launch_jpeg_decode(cbv_ctx* ctx, const JpegBatch& B, u32 total_intervals, int any_dri, int any_pieces, u32 max_blocks, int max_w, int max_h);
+// k_jpeg_color alone: the BGR frames of B.nframes decoded frames from B.descs and B.planes
+int launch_jpeg_color(cbv_ctx* ctx, const JpegBatch& B, int max_w, int max_h);

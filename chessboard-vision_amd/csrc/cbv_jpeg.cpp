@@ -95,9 +95,11 @@ extern "C" int cbv_jpeg_decode_host(const uint8_t* data, size_t n, uint8_t* bgr,
 // ctx->a, planes in ctx->b, the small block (descriptor, tables, interval prefix, counters, marker positions, and the piece
 // path's states and segment table, sized from the stream's length and its intervals) in ctx->small.  S = the piece size, 0:
 // by restart interval; segments: a frame with DRI goes the piece path too.
-// bgr_dev null: the BGR frame goes to ctx->c, tightly packed.  Nothing is waited for; *B tells where everything lies.
+// bgr_dev null: the BGR frame goes to ctx->c, tightly packed.  planes_dev: the planes go there instead of ctx->b; no_bgr: the
+// decode stops at the planes.  ctx->b keeps 256 bytes behind the planes (the slack warp_src_jpeg asks for).  Nothing is
+// waited for; *B tells where everything lies.
 static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc& D, const JpegTables& T, u32 S, int segments, u8* bgr_dev, Geom g,
-                           JpegBatch* Bout)
+                           JpegBatch* Bout, u8* planes_dev = nullptr, bool no_bgr = false)
 {
     const size_t o_desc = 0, o_tab = (sizeof(JpegDesc) + 255) & ~(size_t)255, o_ioff = (o_tab + sizeof(JpegTables) + 255) & ~(size_t)255;
     const size_t o_nfound = o_ioff + 16, o_status = o_ioff + 32, o_stats = o_ioff + 48, o_mpos = o_ioff + 64;
@@ -114,8 +116,8 @@ static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc
     ctx->small.tag = 0; // (not the enhancement chain's layout any more)
     RC(dev_ensure(ctx, &ctx->in, n + 256));
     RC(dev_ensure(ctx, &ctx->a, (size_t)D.plane_total * sizeof(int16_t)));
-    RC(dev_ensure(ctx, &ctx->b, D.plane_total));
-    if (!bgr_dev) {
+    if (!planes_dev) RC(dev_ensure(ctx, &ctx->b, (size_t)D.plane_total + 256));
+    if (!bgr_dev && !no_bgr) {
         RC(dev_ensure(ctx, &ctx->c, g.frame_stride));
         bgr_dev = (u8*)ctx->c.p;
     }
@@ -141,9 +143,9 @@ static int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc
     B.status = (int*)(sm + o_status);
     B.coef = (int16_t*)ctx->a.p;
     B.coef_stride = D.plane_total;
-    B.planes = (u8*)ctx->b.p;
+    B.planes = planes_dev ? planes_dev : (u8*)ctx->b.p;
     B.plane_stride = D.plane_total;
-    B.bgr = bgr_dev;
+    B.bgr = no_bgr ? nullptr : bgr_dev;
     B.bgr_stride = g.stride;
     B.bgr_frame_stride = g.frame_stride;
     B.nframes = 1;
@@ -213,7 +215,8 @@ struct JpegScratch {
     int depth = 0;
     u32* mpos = nullptr;     // [depth * max_intervals]
     int16_t* coef = nullptr; // [depth][frame_elems]
-    u8* planes = nullptr;
+    u8* planes = nullptr;    // null where the decode writes the plane ring
+    bool has_planes = false;
     // the piece path: `depth` frames of piece_cap pieces and, in segments mode, of max_intervals segments
     u32* pieces = nullptr;
     size_t piece_stride = 0; // u32 words per frame
@@ -240,8 +243,125 @@ struct JpegState {
     size_t frame_elems = 0;
     size_t max_int = 0;       // the intervals a frame can have: a restart interval of one MCU in the sampling with most MCUs
     u32* d_stats = nullptr;   // [max_frames][3]
+    // planes mode (cbv_pipeline_set_jpeg_planes): the plane ring, [max_frames] slots of plane_slot bytes and 256 more, and the
+    // descriptors the WARP reads, which change only behind the wait for the runs that read them (d_desc is the decode's)
+    u8* d_pring = nullptr;
+    size_t plane_slot = 0;
+    int pring_mode = CBV_JPEG_PLANES_OFF;
+    JpegDesc* d_wdesc = nullptr; // [max_frames]
     JpegScratch sc;           // sized with the format, the entropy setting and the depth (pipeline_jpeg_size_scratch)
 };
+
+// the samplings in the order in which the planes modes admit them: CBV_JPEG_PLANES_<X> admits those up to X
+static int jpeg_sampling(const JpegDesc& D) { return D.ncomp == 1 ? CBV_JPEG_PLANES_GRAY : D.hs == 1 ? CBV_JPEG_PLANES_444 : D.vs == 1 ? CBV_JPEG_PLANES_422 : CBV_JPEG_PLANES_420; }
+static const char* jpeg_sampling_name(int s)
+{
+    return s == CBV_JPEG_PLANES_GRAY ? "gray" : s == CBV_JPEG_PLANES_420 ? "4:2:0" : s == CBV_JPEG_PLANES_422 ? "4:2:2" : s == CBV_JPEG_PLANES_444 ? "4:4:4" : "off";
+}
+static bool jpeg_planes_mode_ok(int mode) { return mode >= CBV_JPEG_PLANES_OFF && mode <= CBV_JPEG_PLANES_444; }
+// plane_total of a w x h frame in a sampling (jpeg_parse_header's, whole MCUs)
+static size_t jpeg_plane_elems(int w, int h, int sampling)
+{
+    const size_t hs = sampling == CBV_JPEG_PLANES_420 || sampling == CBV_JPEG_PLANES_422 ? 2 : 1, vs = sampling == CBV_JPEG_PLANES_420 ? 2 : 1;
+    const size_t mcux = ((size_t)w + 8 * hs - 1) / (8 * hs), mcuy = ((size_t)h + 8 * vs - 1) / (8 * vs);
+    return mcux * mcuy * 64 * (sampling == CBV_JPEG_PLANES_GRAY ? 1 : hs * vs + 2);
+}
+
+extern "C" size_t cbv_jpeg_plane_slot_bytes(int w, int h, int mode)
+{
+    if (w < 1 || h < 1 || !jpeg_planes_mode_ok(mode) || mode == CBV_JPEG_PLANES_OFF) return 0;
+    size_t most = 0;
+    for (int s = CBV_JPEG_PLANES_GRAY; s <= mode; s++) most = std::max(most, jpeg_plane_elems(w, h, s));
+    return (most + 255) & ~(size_t)255;
+}
+
+// a gray frame of the pipeline's size: what the warp reads of a slot that was never decoded, over zeroed planes
+static JpegDesc jpeg_gray_desc(int w, int h)
+{
+    JpegDesc D;
+    memset(&D, 0, sizeof(D));
+    D.w = w;
+    D.h = h;
+    D.ncomp = 1;
+    D.hs = D.vs = 1;
+    D.mcux = (w + 7) / 8;
+    D.mcuy = (h + 7) / 8;
+    D.nint = 1;
+    D.bw[0] = D.mcux;
+    D.bh[0] = D.mcuy;
+    D.cw[0] = w;
+    D.ch[0] = h;
+    D.plane_total = (uint32_t)D.mcux * (uint32_t)D.mcuy * 64u;
+    D.std_tables = 1;
+    return D;
+}
+
+bool pipeline_jpeg_has_planes(const Pipe& P) { return P.jpeg && P.jpeg->d_pring; }
+
+// a new ring for `mode` (null for OFF): zeroed, 256 bytes of slack behind the last slot
+static int jpeg_plane_ring_alloc(Pipe& P, int mode, const char* who, u8** ring, size_t* slot)
+{
+    *ring = nullptr;
+    *slot = cbv_jpeg_plane_slot_bytes(P.w, P.h, mode);
+    if (!*slot) return CBV_OK;
+    const size_t bytes = *slot * (size_t)P.max_frames + 256;
+    if (hipMalloc((void**)ring, bytes) != hipSuccess || hipMemset(*ring, 0, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (*ring) (void)hipFree(*ring);
+        *ring = nullptr;
+        return cbv_fail(P.ctx, CBV_ERR_HIP, "%s: the plane ring of %zu bytes could not be allocated", who, bytes);
+    }
+    return CBV_OK;
+}
+
+// the ring `ring` takes the place of the one that is there; the warp's descriptors become gray frames
+static int jpeg_plane_ring_install(Pipe& P, u8* ring, size_t slot, int mode)
+{
+    cbv_ctx* ctx = P.ctx;
+    JpegState* J = P.jpeg;
+    if (J->d_pring) (void)hipFree(J->d_pring);
+    J->d_pring = ring;
+    J->plane_slot = slot;
+    J->pring_mode = ring ? mode : CBV_JPEG_PLANES_OFF;
+    if (ring) {
+        const std::vector<JpegDesc> gray((size_t)P.max_frames, jpeg_gray_desc(P.w, P.h));
+        CBV_HIP(ctx, hipMemcpy(J->d_wdesc, gray.data(), gray.size() * sizeof(JpegDesc), hipMemcpyHostToDevice));
+    }
+    return CBV_OK;
+}
+
+int pipeline_jpeg_plane_ring(Pipe& P, const char* who)
+{
+    JpegState* J = P.jpeg;
+    if (!J) return CBV_OK;
+    const int mode = P.jpeg_planes_on() ? P.jpeg_planes : CBV_JPEG_PLANES_OFF;
+    if (J->pring_mode == mode && (J->d_pring != nullptr) == (mode != CBV_JPEG_PLANES_OFF)) return CBV_OK;
+    u8* ring;
+    size_t slot;
+    RC(jpeg_plane_ring_alloc(P, mode, who, &ring, &slot));
+    return jpeg_plane_ring_install(P, ring, slot, mode);
+}
+
+WarpSrc pipeline_jpeg_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs, int np, size_t dst_profile_stride)
+{
+    const JpegState* J = P.jpeg;
+    return warp_src_jpeg(J->d_pring + J->plane_slot * slot0, J->plane_slot, J->d_wdesc + slot0, P.g, ptabs, np, dst_profile_stride);
+}
+
+int pipeline_jpeg_slot_bgr(Pipe& P, int slot, u8* bgr)
+{
+    JpegState* J = P.jpeg;
+    JpegBatch B;
+    memset(&B, 0, sizeof(B));
+    B.descs = J->d_wdesc + slot;
+    B.planes = J->d_pring + J->plane_slot * slot;
+    B.plane_stride = J->plane_slot;
+    B.bgr = bgr;
+    B.bgr_stride = P.g.stride;
+    B.bgr_frame_stride = P.g.frame_stride;
+    B.nframes = 1;
+    return launch_jpeg_color(P.ctx, B, P.w, P.h);
+}
 
 size_t pipeline_jpeg_default_slot_bytes(int w, int h) { return (((size_t)w * h + 1) / 2 + 255) & ~(size_t)255; }
 
@@ -261,7 +381,7 @@ void pipeline_jpeg_free(Pipe& P)
     if (J->h_desc) (void)hipHostFree(J->h_desc);
     if (J->h_ioff) (void)hipHostFree(J->h_ioff);
     if (J->h_tabs) (void)hipHostFree(J->h_tabs);
-    void* dev[] = {J->d_desc, J->d_ioff, J->d_tabs, J->d_status, J->d_nfound, J->d_stats};
+    void* dev[] = {J->d_desc, J->d_ioff, J->d_tabs, J->d_status, J->d_nfound, J->d_stats, J->d_pring, J->d_wdesc};
     for (void* q : dev)
         if (q) (void)hipFree(q);
     jpeg_scratch_free(J->sc);
@@ -288,7 +408,7 @@ int pipeline_jpeg_ensure(Pipe& P)
               hipMalloc((void**)&J->d_desc, n * sizeof(JpegDesc)) == hipSuccess && hipMalloc((void**)&J->d_ioff, 2 * n * sizeof(u32)) == hipSuccess &&
               hipMalloc((void**)&J->d_tabs, JpegState::NSETS * sizeof(JpegTables)) == hipSuccess &&
               hipMalloc((void**)&J->d_status, n * sizeof(int)) == hipSuccess && hipMalloc((void**)&J->d_nfound, n * sizeof(int)) == hipSuccess &&
-              hipMalloc((void**)&J->d_stats, n * 3 * sizeof(u32)) == hipSuccess;
+              hipMalloc((void**)&J->d_stats, n * 3 * sizeof(u32)) == hipSuccess && hipMalloc((void**)&J->d_wdesc, n * sizeof(JpegDesc)) == hipSuccess;
     if (ok) ok = hipMemset(J->d_status, 0, n * sizeof(int)) == hipSuccess && hipMemset(J->d_stats, 0, n * 3 * sizeof(u32)) == hipSuccess;
     if (!ok) {
         pipeline_jpeg_free(P);
@@ -298,7 +418,8 @@ int pipeline_jpeg_ensure(Pipe& P)
     return CBV_OK;
 }
 
-// The decode's scratch for the pipeline's slot size, entropy setting and depth: `depth` frames of the pipeline's size in the
+// The decode's scratch for the pipeline's slot size, entropy setting and depth: `depth` frames of the pipeline's size (the
+// coefficients, 2 bytes a sample, and, unless the planes go to the plane ring, the planes, 1 byte a sample) in the
 // sampling that needs most (4:4:4 padded to the 16 x 16 MCUs of 4:2:0) and a restart interval of one MCU; a frame's pieces
 // are at most ceil(slot bytes / S), and with segments max_intervals more (every interval's last piece may be a short one,
 // an empty interval is one piece).  The new set is allocated before the old one is freed: when it cannot be had the old one
@@ -320,16 +441,17 @@ int pipeline_jpeg_size_scratch(Pipe& P, const char* who)
     n.piece_cap = (u32)cap;
     n.piece_stride = jpeg_piece_words(cap, segments);
     n.seg_stride = segments ? jpeg_seg_words(J->max_int) : 0;
+    n.has_planes = !(P.jpeg_planes != CBV_JPEG_PLANES_OFF && P.raw_config()); // (there the decode writes the plane ring)
     const JpegScratch& o = J->sc;
-    if (o.depth == n.depth && o.piece_stride == n.piece_stride && o.seg_stride == n.seg_stride && o.piece_cap == n.piece_cap) { // the buffers serve
+    if (o.depth == n.depth && o.has_planes == n.has_planes && o.piece_stride == n.piece_stride && o.seg_stride == n.seg_stride && o.piece_cap == n.piece_cap) { // the buffers serve
         J->sc.piece_bytes = S;
         J->sc.segments = segments;
         return CBV_OK;
     }
-    const size_t b_mpos = depth * J->max_int * sizeof(u32), b_coef = depth * J->frame_elems * sizeof(int16_t), b_planes = depth * J->frame_elems;
+    const size_t b_mpos = depth * J->max_int * sizeof(u32), b_coef = depth * J->frame_elems * sizeof(int16_t), b_planes = n.has_planes ? depth * J->frame_elems : 0;
     const size_t b_pieces = depth * n.piece_stride * sizeof(u32), b_segs = depth * n.seg_stride * sizeof(u32);
     const bool ok = hipMalloc((void**)&n.mpos, b_mpos) == hipSuccess && hipMalloc((void**)&n.coef, b_coef) == hipSuccess &&
-                    hipMalloc((void**)&n.planes, b_planes) == hipSuccess && (!b_pieces || hipMalloc((void**)&n.pieces, b_pieces) == hipSuccess) &&
+                    (!b_planes || hipMalloc((void**)&n.planes, b_planes) == hipSuccess) && (!b_pieces || hipMalloc((void**)&n.pieces, b_pieces) == hipSuccess) &&
                     (!b_segs || hipMalloc((void**)&n.segs, b_segs) == hipSuccess);
     if (!ok) {
         (void)hipGetLastError();
@@ -353,6 +475,9 @@ static int jpeg_slot_header(Pipe& P, const char* who, int slot, const u8* data, 
     if (rc) return cbv_fail(ctx, rc, "%s: slot %d: %s", who, slot, msg);
     if (D->w != P.w || D->h != P.h)
         return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: slot %d: a %d x %d frame, the pipeline's are %d x %d", who, slot, D->w, D->h, P.w, P.h);
+    if (P.jpeg_planes_on() && jpeg_sampling(*D) > P.jpeg_planes)
+        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: slot %d: a %s frame, the plane ring's slots hold up to %s (cbv_pipeline_set_jpeg_planes)", who, slot,
+                        jpeg_sampling_name(jpeg_sampling(*D)), jpeg_sampling_name(P.jpeg_planes));
     int k = 0;
     while (k < J->nsets && memcmp(&J->h_tabs[k], &T, sizeof(T))) k++;
     if (k == J->nsets) {
@@ -373,6 +498,8 @@ int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
     const char* who = "cbv_pipeline_submit";
     const size_t sb = P.jpeg_slot_bytes;
     if (J->sc.depth < 1) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the Motion-JPEG decode has no scratch", who);
+    const bool to_ring = P.jpeg_raw(); // raw mode on the plane ring: the decode stops at the slots' planes
+    if (to_ring ? !J->d_pring : !J->sc.planes) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the Motion-JPEG decode has nowhere to put the planes", who);
     if (J->nsets == JpegState::NSETS) { // the cache is full: start again once nothing reads it
         CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
         J->nsets = 0;
@@ -409,6 +536,10 @@ int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
         CBV_HIP(ctx, hipMemcpyAsync(J->d_tabs + sets_before, J->h_tabs + sets_before, (size_t)(J->nsets - sets_before) * sizeof(JpegTables),
                                     hipMemcpyHostToDevice, P.copy_stream));
     if (read_ev) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, read_ev, 0));
+    // The runs in flight read the plane ring and the warp's descriptors of their slots: both change only from here on, behind
+    // the wait.  (d_desc above is read by the decode alone, whose launches of these slots are in stream order.)
+    if (to_ring)
+        CBV_HIP(ctx, hipMemcpyAsync(J->d_wdesc + slot0, J->d_desc + slot0, (size_t)count * sizeof(JpegDesc), hipMemcpyDeviceToDevice, P.copy_stream));
     // 3. the decode, a chunk of frames at a time through the one set of scratch buffers (stream order keeps them apart)
     hipStream_t caller = ctx->stream;
     ctx->stream = P.copy_stream;
@@ -426,9 +557,9 @@ int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev)
         B.status = J->d_status + s;
         B.coef = J->sc.coef;
         B.coef_stride = J->frame_elems;
-        B.planes = J->sc.planes;
-        B.plane_stride = J->frame_elems;
-        B.bgr = P.frames + P.g.frame_stride * s;
+        B.planes = to_ring ? J->d_pring + J->plane_slot * s : J->sc.planes;
+        B.plane_stride = to_ring ? J->plane_slot : J->frame_elems;
+        B.bgr = to_ring ? nullptr : P.frames + P.g.frame_stride * s;
         B.bgr_stride = P.g.stride;
         B.bgr_frame_stride = P.g.frame_stride;
         B.nframes = cf;
@@ -568,7 +699,12 @@ extern "C" int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t
     if (rc) return cbv_fail(ctx, rc, "%s: %s", who, msg);
     if (D.w != P.w || D.h != P.h) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: a %d x %d frame, the pipeline's are %d x %d", who, D.w, D.h, P.w, P.h);
     CBV_ENTER(ctx);
-    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the pipeline's frames are its raw ring (raw mode); it has no BGR frames to decode into", who);
+    const bool to_ring = P.jpeg_raw(); // raw mode on the plane ring: the decode stops at the slot's planes
+    if (P.raw_mode() && !to_ring)
+        return cbv_fail(ctx, CBV_ERR_STATE, "%s: the pipeline's frames are its raw ring (raw mode); it has no BGR frames to decode into", who);
+    if (P.jpeg_planes_on() && jpeg_sampling(D) > P.jpeg_planes)
+        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: slot %d: a %s frame, the plane ring's slots hold up to %s (cbv_pipeline_set_jpeg_planes)", who, slot,
+                        jpeg_sampling_name(jpeg_sampling(D)), jpeg_sampling_name(P.jpeg_planes));
     RC(pipeline_jpeg_ensure(P));
     RC(join_scan(P)); // lanes and scan of the last run
     if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // a submitted decode of this slot lands first
@@ -576,9 +712,98 @@ extern "C" int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t
     u32 S;
     int segments;
     RC(jpeg_piece_size(ctx, who, P.jpeg_entropy, P.jpeg_piece_bytes, &S, &segments));
-    RC(jpeg_single_dev(ctx, data, n, D, T, S, segments, P.frames + P.g.frame_stride * slot, P.g, &B));
+    if (to_ring) {
+        JpegState* J = P.jpeg;
+        if (!J->d_pring) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the pipeline has no plane ring", who);
+        RC(jpeg_single_dev(ctx, data, n, D, T, S, segments, nullptr, P.g, &B, J->d_pring + J->plane_slot * slot, true));
+    } else RC(jpeg_single_dev(ctx, data, n, D, T, S, segments, P.frames + P.g.frame_stride * slot, P.g, &B));
+    if (to_ring) // the slot's descriptor for the warp (the runs are joined)
+        CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_wdesc + slot, B.descs, sizeof(JpegDesc), hipMemcpyDeviceToDevice, ctx->stream));
     CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_status + slot, B.status, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
     CBV_HIP(ctx, hipMemcpyAsync(P.jpeg->d_stats + 3 * (size_t)slot, B.stats, 3 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_set_jpeg_planes(cbv_pipeline* p, int mode)
+{
+    const char* who = "cbv_pipeline_set_jpeg_planes";
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the pipeline is null", who);
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who);
+    if (!jpeg_planes_mode_ok(mode)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: mode %d", who, mode);
+    CBV_ENTER(ctx);
+    if (P.in_fmt != CBV_FMT_MJPEG) { // only stored: the ring comes with the format
+        P.jpeg_planes = mode;
+        return CBV_OK;
+    }
+    if (mode == P.jpeg_planes) return CBV_OK;
+    // what is in flight reads the rings that go away here
+    RC(join_scan(P));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+    // the new ring before the old one is let go: when it cannot be had, the setting that was stays, with its rings
+    u8* ring;
+    size_t slot;
+    RC(jpeg_plane_ring_alloc(P, mode, who, &ring, &slot));
+    const int was = P.jpeg_planes;
+    P.jpeg_planes = mode;
+    int rc = pipeline_jpeg_size_scratch(P, who); // (allocates before it frees)
+    if (rc == CBV_OK && !P.frames && !P.jpeg_raw()) rc = pipeline_frame_ring(P); // the BGR ring comes back
+    if (rc) {
+        P.jpeg_planes = was;
+        if (ring) (void)hipFree(ring);
+        return rc;
+    }
+    RC(jpeg_plane_ring_install(P, ring, slot, mode));
+    return cbv_pipeline_set_input_format(p, CBV_FMT_MJPEG); // frees the ingest rings (and a BGR ring no longer needed), as a format change does
+}
+
+extern "C" int cbv_pipeline_jpeg_planes(cbv_pipeline* p)
+{
+    const char* who = "cbv_pipeline_jpeg_planes";
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the pipeline is null", who);
+    if (attached(p)) return cbv_fail(p->pipe->ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who);
+    return p->pipe->jpeg_planes;
+}
+
+extern "C" int cbv_warp_jpeg(cbv_ctx* ctx, const uint8_t* data, size_t n, const cbv_color_profile* profile, const double* M9, int dw, int dh, int rot180,
+                             uint8_t* out, int out_stride, int32_t* status)
+{
+    const char* who = "cbv_warp_jpeg";
+    if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
+    if (!data || !out || !M9 || !profile || !status || dw <= 0 || dh <= 0 || dw > 8192 || dh > 8192 || out_stride < dw * 3)
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
+    JpegDesc D;
+    JpegTables T;
+    RC(jpeg_header(ctx, who, data, n, &D, &T));
+    if (D.h > 65535) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: %d rows", who, D.h);
+    ProfileTabs pt;
+    RC(profile_tabs_checked(ctx, profile, &pt, who));
+    u32 S;
+    int segments;
+    RC(jpeg_piece_size(ctx, who, CBV_JPEG_ENTROPY_AUTO, 0, &S, &segments));
+    CBV_ENTER_DRAINED(ctx);
+    double Minv[9];
+    if (!host_invert3x3(M9, Minv)) memset(Minv, 0, sizeof(Minv));
+    const Geom g = tight_geom(D.w, D.h);
+    // the warped board in ctx->c, the call's tables behind it
+    const size_t o_tabs = ((size_t)dw * dh * 3 + 255) & ~(size_t)255;
+    RC(dev_ensure(ctx, &ctx->c, o_tabs + sizeof(ProfileTabs) + 256));
+    JpegBatch B;
+    RC(jpeg_single_dev(ctx, data, n, D, T, S, segments, nullptr, g, &B, nullptr, true)); // the decode stops at the planes
+    const ProfileTabs* dpt = nullptr; // a disabled profile: the plain warp
+    if (profile->enabled) {
+        CBV_HIP(ctx, hipMemcpyAsync((u8*)ctx->c.p + o_tabs, &pt, sizeof(pt), hipMemcpyHostToDevice, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt is on this stack)
+        dpt = (const ProfileTabs*)((u8*)ctx->c.p + o_tabs);
+    }
+    RC(launch_warp(ctx, warp_src_jpeg(B.planes, B.plane_stride, B.descs, g, dpt), Minv, dw, dh, rot180, (u8*)ctx->c.p, dw * 3, (size_t)dw * dh * 3, 1));
+    int st = 0;
+    CBV_HIP(ctx, hipMemcpyAsync(&st, B.status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipMemcpy2DAsync(out, out_stride, ctx->c.p, (size_t)dw * 3, (size_t)dw * 3, dh, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *status = st;
+    return CBV_DONE(CBV_OK);
 }

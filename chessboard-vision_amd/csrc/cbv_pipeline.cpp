@@ -178,12 +178,13 @@ int pipeline_tables(Pipe& P)
 
 // The BGR frame ring exists unless the pipeline is configured with CBV_SKIP_ENHANCE_PROFILE_RAW and its input format is raw:
 // then the raw ring holds every byte, nothing reads or writes BGR frames, and the ring (6.2 MB a 1080p slot) is given back.
-// (skip_enhance = 1 keeps its ring in raw mode, as it always did.)  Called when the mode or the input format changes; what
+// (skip_enhance = 1 keeps its ring in raw mode, as it always did.)  Motion-JPEG in planes mode has no BGR ring in either raw
+// configuration: the plane ring holds the frames.  Called when the mode or the input format changes; what
 // is in flight is joined before the ring goes.
 int pipeline_frame_ring(Pipe& P)
 {
     cbv_ctx* ctx = P.ctx;
-    const bool want = !(P.configured_raw_profile() && P.fmt_is_raw());
+    const bool want = !((P.configured_raw_profile() && P.fmt_is_raw()) || P.jpeg_raw());
     if (want && !P.frames) {
         const size_t bytes = P.g.frame_stride * P.max_frames;
         if (hipMalloc((void**)&P.frames, bytes + 256) != hipSuccess) {
@@ -462,6 +463,10 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     RC(pipeline_update_region(P));
     RC(pipeline_tables(P));
     RC(pipeline_frame_ring(P));
+    if (P.in_fmt == CBV_FMT_MJPEG && P.jpeg && P.jpeg_slot_bytes) { // the decode's scratch has a plane buffer only where the planes do not go to the ring
+        if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+        RC(pipeline_jpeg_size_scratch(P, "cbv_pipeline_configure"));
+    }
     P.configured = true;
     return CBV_OK;
 }
@@ -742,11 +747,12 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
         src = P.raw_mode() ? nullptr : P.frames + P.g.frame_stride * slot;
         bytes = (size_t)P.w * P.h * 3;
         if (P.raw_mode()) { // the frames are raw: the slot is converted for the caller
-            if (!P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: no raw frame was ever uploaded or submitted");
+            if (!pipeline_raw_frames_exist(P)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: no raw frame was ever uploaded or submitted");
             if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // submitted copies of the slot
             const RawGeom rg = tight_raw_geom(P.in_fmt, P.w, P.h);
             RC(dev_ensure(ctx, &ctx->a, P.g.frame_stride + 256));
-            RC(launch_ingest(ctx, slot_planes(P, slot), rg, (u8*)ctx->a.p, P.g, 1));
+            if (P.jpeg_planes_on()) RC(pipeline_jpeg_slot_bgr(P, slot, (u8*)ctx->a.p)); // k_jpeg_color on the slot's planes
+            else RC(launch_ingest(ctx, slot_planes(P, slot), rg, (u8*)ctx->a.p, P.g, 1));
             src = (const u8*)ctx->a.p;
         }
     } else if (which == 1) {

@@ -98,9 +98,12 @@ struct Pipe {
     // k_warp_bayer / k_warp_raw_profile samples it, nothing is converted and `frames` is neither written nor read (raw_mode below).
     u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated on first use; null with CBV_FMT_BGR
     // Motion-JPEG (CBV_FMT_MJPEG): both rings hold one JPEG stream per slot, jpeg_slot_bytes apart, and the decode writes
-    // `frames` behind the copy (cbv_jpeg.cpp); never raw mode, the BGR ring stays
+    // `frames` behind the copy (cbv_jpeg.cpp).  With jpeg_planes (cbv_pipeline_set_jpeg_planes) other than OFF the format is a
+    // raw one: without enhancement the decode stops at the planes, which it writes into the plane ring (JpegState), the warp
+    // samples that ring (k_warp_jpeg) and the BGR ring is given back.
     struct JpegState* jpeg = nullptr;
     size_t jpeg_slot_bytes = 0;
+    int jpeg_planes = CBV_JPEG_PLANES_OFF;
     hipStream_t copy_stream = nullptr;
     struct CopyRec {
         int s0, cnt;
@@ -149,8 +152,11 @@ struct Pipe {
     int jpeg_depth = CBV_JPEG_DEPTH_DEFAULT; // frames per launch of a Motion-JPEG submit, cbv_pipeline_set_jpeg_depth
     Board& b0() const { return boards[0]->b; }
     bool configured_raw_profile() const { return skip_enhance && profile_raw; }
-    bool fmt_is_raw() const { return in_fmt != CBV_FMT_BGR && in_fmt != CBV_FMT_MJPEG; } // a YUV or Bayer format
-    bool raw_mode() const { return skip_enhance && (!profile_only || profile_raw) && fmt_is_raw(); }
+    bool jpeg_planes_on() const { return in_fmt == CBV_FMT_MJPEG && jpeg_planes != CBV_JPEG_PLANES_OFF; }
+    bool fmt_is_raw() const { return (in_fmt != CBV_FMT_BGR && in_fmt != CBV_FMT_MJPEG) || jpeg_planes_on(); } // YUV, Bayer, or JPEG planes
+    bool raw_config() const { return skip_enhance && (!profile_only || profile_raw); } // a configuration in which a raw format's frames stay raw
+    bool raw_mode() const { return raw_config() && fmt_is_raw(); }
+    bool jpeg_raw() const { return raw_config() && jpeg_planes_on(); } // raw mode on the plane ring
 };
 // cbv_pipeline.cpp: board handles, the ordering of the runs in flight, the boards' kernel arguments, read-backs
 bool attached(const cbv_pipeline* p);
@@ -173,3 +179,14 @@ int pipeline_jpeg_ensure(Pipe& P);
 int pipeline_jpeg_size_scratch(Pipe& P, const char* who);
 void pipeline_jpeg_free(Pipe& P);
 int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev);
+// the plane ring of the pipeline's jpeg_planes mode: made (zeroed, the warp's descriptors gray frames) when the mode has one
+// and it is not there, let go when the mode is OFF; the caller has joined what reads it
+int pipeline_jpeg_plane_ring(Pipe& P, const char* who);
+bool pipeline_jpeg_has_planes(const Pipe& P);
+// what the warp samples in raw mode on the plane ring: `slot0`'s planes and descriptor, the frames behind them
+WarpSrc pipeline_jpeg_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs = nullptr, int np = 1, size_t dst_profile_stride = 0);
+// cbv_pipeline_download(which = 0) in raw mode on the plane ring: k_jpeg_color of the slot into `bgr` (device, P.g)
+int pipeline_jpeg_slot_bgr(Pipe& P, int slot, u8* bgr);
+// what the warp samples in raw mode, whatever the raw format (cbv_pipeline_ingest.cpp)
+WarpSrc pipeline_raw_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs = nullptr, int np = 1, size_t dst_profile_stride = 0);
+bool pipeline_raw_frames_exist(const Pipe& P);

@@ -5,12 +5,24 @@
 // the raw-frame mode (Pipe::raw_mode) has no BGR frames to write
 static const char* const kRawModeMsg = "the pipeline runs without enhancement on a YUV or Bayer input format (raw mode): its frames are the raw "
                                        "ring, written by cbv_pipeline_upload_raw or cbv_pipeline_submit in that format";
+static const char* const kJpegRawModeMsg = "the pipeline runs without enhancement on Motion-JPEG input in planes mode (raw mode): its frames are "
+                                           "the decoded planes, written by cbv_pipeline_upload_jpeg or cbv_pipeline_submit";
+static const char* raw_mode_msg(const Pipe& P) { return P.jpeg_planes_on() ? kJpegRawModeMsg : kRawModeMsg; }
 
 // the planes of slot `slot` of the device ring of raw frames
 RawPlanes slot_planes(const Pipe& P, int slot)
 {
     return tight_raw_planes(P.in_fmt, P.w, P.h, P.raw_ring + tight_raw_geom(P.in_fmt, P.w, P.h).frame_stride * slot);
 }
+
+WarpSrc pipeline_raw_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs, int np, size_t dst_profile_stride)
+{
+    if (P.jpeg_planes_on()) return pipeline_jpeg_warp_src(P, slot0, ptabs, np, dst_profile_stride);
+    const RawGeom rg = tight_raw_geom(P.in_fmt, P.w, P.h);
+    return ptabs ? warp_src_raw_profile(slot_planes(P, slot0), rg, P.g, ptabs, np, dst_profile_stride) : warp_src_raw(slot_planes(P, slot0), rg, P.g);
+}
+
+bool pipeline_raw_frames_exist(const Pipe& P) { return P.jpeg_planes_on() ? pipeline_jpeg_has_planes(P) : P.raw_ring != nullptr; }
 
 // bytes between the slots of the ingest rings in the current input format
 static size_t host_slot_bytes(const Pipe& P)
@@ -39,7 +51,7 @@ extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr
     Pipe& P = *p->pipe;
     cbv_ctx* ctx = P.ctx;
     CBV_ENTER(ctx);
-    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload: %s", kRawModeMsg);
+    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload: %s", raw_mode_msg(P));
     RC(join_scan(P)); // lanes and scan of the last run
     RC(rows_h2d(ctx, P.frames + P.g.frame_stride * slot, bgr, stride, P.w * 3, P.h));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -57,6 +69,7 @@ extern "C" int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_
     CBV_ENTER(ctx);
     RC(join_scan(P)); // lanes and scan of the last run
     if (P.raw_mode()) { // the frame as it is into its slot of the raw ring, rows packed
+        if (P.jpeg_planes_on()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: format %d, but %s", raw->fmt, kJpegRawModeMsg);
         if (raw->fmt != P.in_fmt)
             return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: format %d, but %s (format %d)", raw->fmt, kRawModeMsg, P.in_fmt);
         const u8* planes[3];
@@ -107,7 +120,16 @@ extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
     if (P.host_ring) (void)hipHostFree(P.host_ring);
     if (P.raw_ring) (void)hipFree(P.raw_ring);
     P.host_ring = P.raw_ring = nullptr;
+    const int fmt_was = P.in_fmt;
     P.in_fmt = fmt;
+    if (P.jpeg) { // the plane ring of the planes mode comes with the format and goes with it
+        const int rc = pipeline_jpeg_plane_ring(P, "cbv_pipeline_set_input_format");
+        if (rc) {
+            P.in_fmt = fmt_was == CBV_FMT_MJPEG ? CBV_FMT_BGR : fmt_was; // (the ingest rings are gone: they come back on first use)
+            if (pipeline_frame_ring(P) != CBV_OK) P.configured = false;  // no ring for that format either: nothing may run
+            return rc;
+        }
+    }
     return pipeline_frame_ring(P); // (a CBV_SKIP_ENHANCE_PROFILE_RAW pipeline has a BGR ring only while its frames are BGR)
 }
 
@@ -212,7 +234,7 @@ extern "C" int cbv_pipeline_synth(cbv_pipeline* p, int slot0, int count, const u
     Pipe& P = *p->pipe;
     cbv_ctx* ctx = P.ctx;
     CBV_ENTER(ctx);
-    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_synth: %s", kRawModeMsg);
+    if (P.raw_mode()) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_synth: %s", raw_mode_msg(P));
     RC(join_scan(P)); // lanes and scan of the last run
     size_t o_seeds = 0, o_h = (size_t)count * 8, o_b = o_h + 72, o_s = (o_b + (size_t)count * 64 + 15) & ~(size_t)15;
     size_t total = o_s + sizeof(cbv_scene);

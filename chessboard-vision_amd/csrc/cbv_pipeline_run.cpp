@@ -13,8 +13,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     // what the warp samples (raw mode: the planes of the chunk's first slot)
     // (the profile's table: board 0's for the single-board launch; the multi-board kernels read the boards' own)
     const ProfileTabs* pt = P.profile_on ? (const ProfileTabs*)P.b0().d_ptabs.p : nullptr;
-    const WarpSrc src = !res ? (pt ? warp_src_raw_profile(slot_planes(P, s0), tight_raw_geom(P.in_fmt, P.w, P.h), P.g, pt)
-                                   : warp_src_raw(slot_planes(P, s0), tight_raw_geom(P.in_fmt, P.w, P.h), P.g))
+    const WarpSrc src = !res ? pipeline_raw_warp_src(P, s0, pt)
                         : pt ? warp_src_profile(res, P.g, pt)
                              : warp_src_bgr(res, P.g, norm);
     if (P.boards.size() > 1) {
@@ -174,7 +173,7 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
     if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: a board is run by its parent");
     if (slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_run: bad slot range");
     CBV_ENTER(ctx);
-    if (P.raw_mode() && !P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: no raw frame was ever uploaded or submitted");
+    if (P.raw_mode() && !pipeline_raw_frames_exist(P)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: no raw frame was ever uploaded or submitted");
     const cbv_enhance_params& enh = P.b0().cfg.enhance;
     // Lane 0 is the context's stream; lanes 1.. are worker streams forked from it and joined before
     // the temporal scan (which needs every frame's statistics, in order).

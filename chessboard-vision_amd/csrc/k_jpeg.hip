@@ -439,7 +439,16 @@ int launch_jpeg_decode(cbv_ctx* ctx, const JpegBatch& B, u32 total_intervals, in
     } else if (any_pieces) hipLaunchKernelGGL(k_jpeg_pieces<false>, dim3(B.nframes), dim3(JP_PIECE_LANES), 0, s, B);
     if (!B.segments && (any_dri || !any_pieces)) hipLaunchKernelGGL(k_jpeg_entropy, dim3((total_intervals + 63u) / 64u), dim3(64), 0, s, B);
     hipLaunchKernelGGL(k_jpeg_idct, dim3((max_blocks + 63u) / 64u, B.nframes), dim3(64), 0, s, B);
-    hipLaunchKernelGGL(k_jpeg_color, dim3((max_w + 255) / 256, max_h, B.nframes), dim3(256), 0, s, B);
+    if (B.bgr) hipLaunchKernelGGL(k_jpeg_color, dim3((max_w + 255) / 256, max_h, B.nframes), dim3(256), 0, s, B);
+    CBV_HIP(ctx, hipGetLastError());
+    return CBV_OK;
+}
+
+int launch_jpeg_color(cbv_ctx* ctx, const JpegBatch& B, int max_w, int max_h)
+{
+    if (B.nframes <= 0 || B.nframes > 65535 || max_w < 1 || max_h < 1 || max_h > 65535 || !B.bgr || !B.planes || !B.descs)
+        return cbv_fail(ctx, CBV_ERR_ARG, "launch_jpeg_color: bad batch");
+    hipLaunchKernelGGL(k_jpeg_color, dim3((max_w + 255) / 256, max_h, B.nframes), dim3(256), 0, ctx->stream, B);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }

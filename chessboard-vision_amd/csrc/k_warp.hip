@@ -112,6 +112,7 @@ __global__ __launch_bounds__(256) void k_warp_profile_mb(const u8* __restrict__ 
 int launch_warp(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
                 int batch, u32* zero_word, u32* zero_word2)
 {
+    if (s.kind == WarpSrc::JPEG) return launch_warp_jpeg(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     if (s.raw() && s.ptabs) return launch_warp_raw_profile(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     WarpM M;
     for (int i = 0; i < 9; i++) M.m[i] = Minv9[i];
@@ -144,6 +145,7 @@ int launch_warp(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, in
 
 int launch_warp_mb(cbv_ctx* ctx, WarpSrc s, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2)
 {
+    if (s.kind == WarpSrc::JPEG) return launch_warp_jpeg_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     if (s.raw() && s.ptabs) return launch_warp_raw_profile_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     const hipStream_t st = ctx->stream;
     return warp_launch(ctx, &s, maxS, maxS, nb, batch, [&](auto fmt, auto fpt, dim3 grid, int nz) {

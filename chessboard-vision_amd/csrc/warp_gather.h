@@ -1,9 +1,10 @@
 // The warp's one gather (warp_gather), its sources and what the launchers share, for the translation units that hold
-// warp kernels: k_warp.hip and k_warp_raw_profile.hip.  Private.
+// warp kernels: k_warp.hip, k_warp_raw_profile.hip and k_warp_jpeg.hip.  Private.
 #pragma once
 #include "cbv_bayer.h"
 #include "cbv_profile_px.h"
 #include "cbv_yuv.h"
+#include "jpeg_core.h"
 
 struct WarpM {
     double m[9];
@@ -85,7 +86,7 @@ struct WarpDst {
 // simplifies every function on its own before it inlines, and the gather split into per-source functions compiles to
 // other instructions than this.)
 // ---------------------------------------------------------------------------
-enum { WARP_BGR, WARP_PROFILE, WARP_YUV, WARP_BAYER };
+enum { WARP_BGR, WARP_PROFILE, WARP_YUV, WARP_BAYER, WARP_JPEG };
 #define WP_ROWS 16 // destination rows per workgroup of WarpProfile: one row of WarpPerspectiveInvoker's 64 x 16 blocks
 
 // BGR frames through cv2.normalize's byte map, which is staged in LDS per frame.  CALC: the map is worked out here from the
@@ -160,6 +161,104 @@ struct WarpRawProfile : WarpRaw<FMT_> {
     const ProfileTabs* pt; // the profile's table
 };
 
+// The decoded planes of Motion-JPEG frames (k_warp_jpeg.hip: pipelines in planes mode without enhancement, cbv_warp_jpeg): a
+// tap at (x, y) is jpeg_pixel(D, planes, x, y) of the frame's own descriptor D, so the BGR frame k_jpeg_color would write is
+// never made.  Frame f's planes lie at planes + f * plane_stride, its descriptor is descs[f]: gray, 4:4:4, 4:2:2 and 4:2:0
+// frames may share a launch.
+struct WarpJpeg {
+    static constexpr int KIND = WARP_JPEG, ROWS = 4, FMT = CBV_FMT_MJPEG;
+    static constexpr bool TABS = false;
+    template <int FPT>
+    struct Lds {
+    };
+    const u8* planes;
+    size_t plane_stride;
+    const JpegDesc* descs;
+    int sw, sh;
+    __device__ __forceinline__ int w() const { return sw; }
+    __device__ __forceinline__ int h() const { return sh; }
+};
+
+// ... through the colour profile: d_profile_px on each tap inside the frame, staged and tiled as WarpProfile is
+struct WarpJpegProfile : WarpJpeg {
+    static constexpr int ROWS = WP_ROWS;
+    static constexpr bool TABS = true;
+    template <int FPT>
+    using Lds = ProfileLds;
+    const StaticTabs* st;
+    const ProfileTabs* pt; // the profile's table
+};
+
+// What the taps of one JPEG frame need of its descriptor, read once per thread and frame (the descriptor is the same for the
+// whole workgroup): the planes' offsets and row lengths, the chroma planes' true size, and the sampling.  `wide`: the fast
+// pixels of the frame take their chroma from 4-byte loads; not so where a subsampled component is 1 or 2 wide, which is
+// replicated, not filtered (jpeg_chroma_at): those frames are at most 4 pixels wide and go through jpeg_pixel.
+struct JpegTapDesc {
+    u32 o0, o1, o2;
+    int s0, s1, cw, ch;
+    int mode; // 0 gray, 1 4:4:4, 2 4:2:2, 3 4:2:0
+    bool wide;
+};
+__device__ __forceinline__ JpegTapDesc jpeg_tap_desc(const JpegDesc& D)
+{
+    JpegTapDesc J;
+    J.o0 = D.poff[0];
+    J.o1 = D.poff[1];
+    J.o2 = D.poff[2];
+    J.s0 = D.bw[0] * 8;
+    J.s1 = D.bw[1] * 8;
+    J.cw = D.cw[1];
+    J.ch = D.ch[1];
+    J.mode = D.ncomp == 1 ? 0 : D.hs == 1 ? 1 : D.vs == 1 ? 2 : 3;
+    J.wide = J.mode < 2 || J.cw > 2;
+    return J;
+}
+__device__ __forceinline__ int d_byte(u32 w, int i) { return (int)((w >> (8 * i)) & 255u); }
+// what the wide loads of a fast pixel hold of one frame: the rows of luma taps and the rows of the chroma windows, which
+// start at column ws (2:1 chroma) and row rs (4:2:0)
+struct JpegWin {
+    u32 ya, yb;
+    u32 cb[3], cr[3];
+    int ws, rs;
+};
+__device__ __forceinline__ u32 d_sel3(const u32 (&w)[3], int i) { return i == 0 ? w[0] : i == 1 ? w[1] : w[2]; }
+// tap (sx + tx, sy + ty) of a fast pixel from the window: jpeg_pixel's arithmetic on the loaded bytes
+__device__ __forceinline__ u32 d_jpeg_tap(const JpegTapDesc& J, const JpegWin& W, int sx, int sy, int tx, int ty)
+{
+    const int x = sx + tx, y = sy + ty;
+    const int Y = d_byte(ty ? W.yb : W.ya, tx);
+    if (J.mode == 0) return (u32)Y * 0x010101u;
+    int cb, cr;
+    if (J.mode == 1) {
+        cb = d_byte(W.cb[ty], tx);
+        cr = d_byte(W.cr[ty], tx);
+    } else { // jpeg_chroma_at's filter
+        const int ci = x >> 1, cn = (x & 1) ? min(ci + 1, J.cw - 1) : max(ci - 1, 0);
+        const int ri = ci - W.ws, rn = cn - W.ws;
+        if (J.mode == 2) {
+            const int rnd = (x & 1) ? 2 : 1;
+            cb = (3 * d_byte(W.cb[ty], ri) + d_byte(W.cb[ty], rn) + rnd) >> 2;
+            cr = (3 * d_byte(W.cr[ty], ri) + d_byte(W.cr[ty], rn) + rnd) >> 2;
+        } else {
+            const int cj = y >> 1, cjn = (y & 1) ? min(cj + 1, J.ch - 1) : max(cj - 1, 0);
+            const int a = cj - W.rs, b = cjn - W.rs, rnd = (x & 1) ? 7 : 8;
+            const u32 b0 = d_sel3(W.cb, a), b1 = d_sel3(W.cb, b), r0 = d_sel3(W.cr, a), r1 = d_sel3(W.cr, b);
+            cb = (3 * (3 * d_byte(b0, ri) + d_byte(b1, ri)) + (3 * d_byte(b0, rn) + d_byte(b1, rn)) + rnd) >> 4;
+            cr = (3 * (3 * d_byte(r0, ri) + d_byte(r1, ri)) + (3 * d_byte(r0, rn) + d_byte(r1, rn)) + rnd) >> 4;
+        }
+    }
+    u8 o[3];
+    jpeg_ycc_to_bgr(Y, cb, cr, o);
+    return (u32)o[0] | ((u32)o[1] << 8) | ((u32)o[2] << 16);
+}
+// pixel (x, y) of one JPEG frame with byte loads, as b | g << 8 | r << 16
+__device__ __forceinline__ u32 d_jpeg_px(const JpegDesc& D, const u8* __restrict__ planes, int x, int y)
+{
+    u8 px[3];
+    jpeg_pixel(D, planes, x, y, px);
+    return (u32)px[0] | ((u32)px[1] << 8) | ((u32)px[2] << 16);
+}
+
 // pixel (x, y) of one raw YUV frame with byte loads (the taps of pixels on the frame's border)
 template <int FMT>
 __device__ __forceinline__ u32 d_raw_px(const u8* __restrict__ f0, const u8* __restrict__ f1, const u8* __restrict__ f2, const RawGeom& r, int x,
@@ -217,12 +316,18 @@ __device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride,
 // chroma for either parity.  The bytes read past the second tap's pair (sx even) stay inside the buffer: the ring keeps 256
 // bytes of slack behind the last frame.  Bayer, pixels whose four taps are all interior sites (1 <= sx, sx + 1 <= w - 2,
 // the same in y): the taps' 3 x 3 neighbourhoods lie in the 4 x 4 bytes at (sx - 1, sy - 1), which is four unaligned 4-byte
-// loads per frame, inside the frame's rows.
+// loads per frame, inside the frame's rows.  JPEG planes, interior pixels: one 2-byte load per row of taps holds both luma
+// samples.  The chroma of a 2 x 2 block of taps and of the neighbours its triangle filter reads lies in 3 columns (4:2:2,
+// 4:2:0; 2 for 4:4:4) of 3 rows (4:2:0; 2 otherwise) of each chroma plane: one 4-byte load per row and plane at the window's
+// first column, which is the taps' column for 4:4:4 and max(((sx + 1) >> 1) - 1, 0) otherwise; the rows start at
+// max(((sy + 1) >> 1) - 1, 0) for 4:2:0 and are clamped to the component's last row, which only moves rows no tap reads.  So
+// 4 loads (gray: 2), 6 (4:4:4, 4:2:2) or 8 (4:2:0) per frame.  The planes are whole MCUs, and the bytes a load reads past
+// the window belong to the next row, plane or slot: callers keep >= 4 readable bytes behind the last frame's planes.
 template <class Src, int FPT>
 __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
 {
     constexpr int KIND = Src::KIND, FMT = Src::FMT;
-    constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV;
+    constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV, JPEG = KIND == WARP_JPEG;
     constexpr bool TABS = Src::TABS, RAW_TABS = TABS && !PROFILE; // the profile's tables are staged; ... for the taps of a raw source
     typedef YuvLay<YUV ? FMT : CBV_FMT_NV12> L; // (only read where YUV)
     constexpr bool NV12 = L::F420 && !L::PLANAR, PLANAR = L::PLANAR;
@@ -264,6 +369,11 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
         if constexpr (TABS) return on ? d_profile_px(lds, (int)(v & 255u), (int)((v >> 8) & 255u), (int)((v >> 16) & 255u), radical) : (v & 0xFFFFFFu);
         else return v;
     };
+    JpegTapDesc jt[JPEG ? FPT : 1]; // JPEG: per frame, outside the loops over rows and taps
+    if constexpr (JPEG)
+#pragma unroll
+        for (int k = 0; k < FPT; k++)
+            if (k < nf) jt[k] = jpeg_tap_desc(S.descs[f0 + k]);
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     int dy = blockIdx.y * Src::ROWS + (threadIdx.x >> 6), row = 0;
     if (dx >= D.dw || dy >= D.dh) return;
@@ -281,6 +391,8 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
             tap = L::F420 ? (size_t)t.sy * S.r.stride0 + (size_t)t.sx : (size_t)t.sy * S.r.stride0 + (size_t)(t.sx >> 1) * 4;
             c_off = (size_t)(t.sy >> 1) * S.r.stride1 + (size_t)(PLANAR ? t.sx >> 1 : t.sx & ~1);
             c2_off = (size_t)(t.sy >> 1) * S.r.stride2 + (size_t)(t.sx >> 1);
+        } else if constexpr (JPEG) {
+            // (the offsets depend on the frame's layout: worked out per frame below)
         } else {
             fast = t.sx >= 1 && t.sx + 2 < S.sw && t.sy >= 1 && t.sy + 2 < S.sh;
             tap = (size_t)(t.sy - 1) * S.r.stride0 + (size_t)(t.sx - 1);
@@ -289,6 +401,9 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
         u32 ca[FPT], cb[FPT]; // NV12: U V U V; planar: U U
         u32 va[FPT], vb[FPT]; // planar: V V
         u32 rows[FPT][4];     // Bayer
+        u32 jcb[FPT][3], jcr[FPT][3]; // JPEG: the chroma windows' rows
+        // JPEG: the first column and row of the chroma windows of a frame with 2:1 chroma (the same for 4:2:2 and 4:2:0)
+        const int jws = max(((t.sx + 1) >> 1) - 1, 0), jrs = max(((t.sy + 1) >> 1) - 1, 0);
         if (fast)
 #pragma unroll
             for (int k = 0; k < FPT; k++)
@@ -328,6 +443,32 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                             __builtin_memcpy(&ta[k], l, 8);
                             __builtin_memcpy(&tb[k], l + S.r.stride0, 8);
                         }
+                    } else if constexpr (JPEG) {
+                        const JpegTapDesc& J = jt[k];
+                        if (J.wide) {
+                            const u8* pl = S.planes + (size_t)(f0 + k) * S.plane_stride;
+                            const u8* l = pl + J.o0 + (size_t)t.sy * J.s0 + t.sx;
+                            u16 a, b;
+                            __builtin_memcpy(&a, l, 2);
+                            __builtin_memcpy(&b, l + J.s0, 2);
+                            ta[k] = a;
+                            tb[k] = b;
+                            if (J.mode) {
+                                const int ws = J.mode >= 2 ? jws : t.sx, r0 = J.mode == 3 ? jrs : t.sy;
+                                const int r1 = J.mode == 3 ? min(r0 + 1, J.ch - 1) : r0 + 1;
+                                const u8* c1 = pl + J.o1 + ws;
+                                const u8* c2 = pl + J.o2 + ws;
+                                __builtin_memcpy(&jcb[k][0], c1 + (size_t)r0 * J.s1, 4);
+                                __builtin_memcpy(&jcb[k][1], c1 + (size_t)r1 * J.s1, 4);
+                                __builtin_memcpy(&jcr[k][0], c2 + (size_t)r0 * J.s1, 4);
+                                __builtin_memcpy(&jcr[k][1], c2 + (size_t)r1 * J.s1, 4);
+                                if (J.mode == 3) {
+                                    const int r2 = min(r0 + 2, J.ch - 1);
+                                    __builtin_memcpy(&jcb[k][2], c1 + (size_t)r2 * J.s1, 4);
+                                    __builtin_memcpy(&jcr[k][2], c2 + (size_t)r2 * J.s1, 4);
+                                }
+                            }
+                        }
                     } else {
                         const u8* m = S.p0 + (size_t)(f0 + k) * S.r.frame_stride + tap;
 #pragma unroll
@@ -338,6 +479,8 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
         for (int k = 0; k < FPT; k++) {
             if (k >= nf) break;
             int o[3] = {0, 0, 0};
+            bool fastk = fast; // (JPEG: and the frame's layout has the wide loads)
+            if constexpr (JPEG) fastk = fast && jt[k].wide;
             if (t.any_in) {
                 // ---- the taps 00, 01, 10, 11.  BGR: v, the bytes as they lie in the frame, -1 for a tap outside it; the
                 // others: q, converted, as b | g << 8 | r << 16, 0 for a tap outside
@@ -363,7 +506,7 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                             v[3][c] = (t.x1in && t.y1in) ? p10[3 + c] : -1;
                         }
                     }
-                } else if (fast) {
+                } else if (fastk) {
                     if constexpr (PROFILE) {
                         q[0] = conv((u32)ta[k]);
                         q[1] = conv((u32)(ta[k] >> 24));
@@ -410,6 +553,13 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                                 q[2 * r + 1] = d_yuv_bgr((int)((odd ? hi >> (8 * L::Y0) : lo >> (8 * L::Y1)) & 255), c1);
                             }
                         }
+                    } else if constexpr (JPEG) {
+                        const JpegTapDesc& J = jt[k];
+                        const JpegWin W = {(u32)ta[k], (u32)tb[k], {jcb[k][0], jcb[k][1], jcb[k][2]}, {jcr[k][0], jcr[k][1], jcr[k][2]}, jws, jrs};
+                        q[0] = d_jpeg_tap(J, W, t.sx, t.sy, 0, 0);
+                        q[1] = d_jpeg_tap(J, W, t.sx, t.sy, 1, 0);
+                        q[2] = d_jpeg_tap(J, W, t.sx, t.sy, 0, 1);
+                        q[3] = d_jpeg_tap(J, W, t.sx, t.sy, 1, 1);
                     } else {
                         const u32* w = rows[k];
                         q[0] = d_bayer_bgr<FMT>(t.sx, t.sy, w[0], w[1], w[2]);
@@ -434,6 +584,13 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                         if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy);
                         if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy + 1);
                         if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy + 1);
+                    } else if constexpr (JPEG) {
+                        const JpegDesc& D = S.descs[f0 + k];
+                        const u8* pl = S.planes + (size_t)(f0 + k) * S.plane_stride;
+                        if (t.x0in && t.y0in) q[0] = d_jpeg_px(D, pl, t.sx, t.sy);
+                        if (t.x1in && t.y0in) q[1] = d_jpeg_px(D, pl, t.sx + 1, t.sy);
+                        if (t.x0in && t.y1in) q[2] = d_jpeg_px(D, pl, t.sx, t.sy + 1);
+                        if (t.x1in && t.y1in) q[3] = d_jpeg_px(D, pl, t.sx + 1, t.sy + 1);
                     } else {
                         const u8* fp = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
                         if (t.x0in && t.y0in) q[0] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx, t.sy);
@@ -447,7 +604,7 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                     const bool in[4] = {t.x0in && t.y0in, t.x1in && t.y0in, t.x0in && t.y1in, t.x1in && t.y1in};
 #pragma unroll
                     for (int i = 0; i < 4; i++)
-                        if (fast || in[i]) q[i] = conv(q[i]);
+                        if (fastk || in[i]) q[i] = conv(q[i]);
                 }
                 // ---- the blend
 #pragma unroll

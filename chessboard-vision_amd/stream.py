@@ -748,7 +748,7 @@ class BoardPipeline(_BoardMethods):
             raise ValueError("a %dx%d %s frame does not fit the pipeline's %dx%d frames" % (w, h, fmt, self.w, self.h))
         self.ctx.check(self.ctx.lib.cbv_pipeline_upload_raw(self.h_, slot, raw))
 
-    def set_input_format(self, fmt, slot_bytes=None):
+    def set_input_format(self, fmt, slot_bytes=None, planes=False):
         """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12", "nv21", "yuv420p"
         (cv2's I420; "i420" itself is an unknown format), "yv12", "yuyv", "yvyu", "uyvy", or an 8-bit Bayer mosaic
         "bayer_rggb", "bayer_bggr", "bayer_grbg" or "bayer_gbrg" (w and h even and at least 4).  Raw frames cross PCIe as
@@ -756,8 +756,12 @@ class BoardPipeline(_BoardMethods):
         allocated again by the next `host_ring()`: an array that call returned earlier must not be touched any more.
         "mjpeg": a slot holds one baseline JPEG stream (a Motion-JPEG frame) of up to `slot_bytes` bytes (default w * h / 2,
         rounded up to 256), its length goes into `jpeg_lengths()`, and `submit` copies only the used bytes and decodes them on
-        the GPU into the BGR frames (include/cbv.h, CBV_FMT_MJPEG)."""
+        the GPU into the BGR frames (include/cbv.h, CBV_FMT_MJPEG).  `planes` (False, True = "444", "444", "422", "420" or
+        "gray": the largest chroma sampling the streams may have) makes "mjpeg" a raw format: on a pipeline configured with
+        `enhance=False` or `enhance="profile", raw=True` the decode stops at the planes, no BGR frame is written, and the warp
+        samples the planes with the same bytes as a result (include/cbv.h, cbv_pipeline_set_jpeg_planes)."""
         if isinstance(fmt, str) and fmt.lower() == "mjpeg":
+            self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_planes(self.h_, N.jpeg_planes_id(planes)))
             if slot_bytes is not None:
                 self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_slot_bytes(self.h_, int(slot_bytes)))
             self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.FMT_MJPEG))
@@ -765,6 +769,8 @@ class BoardPipeline(_BoardMethods):
             return
         if slot_bytes is not None:
             raise ValueError("slot_bytes belongs to the \"mjpeg\" format")
+        if N.jpeg_planes_id(planes):
+            raise ValueError("planes belongs to the \"mjpeg\" format")
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt)))
         self.input_format = fmt.lower()
 
@@ -799,6 +805,14 @@ class BoardPipeline(_BoardMethods):
         if not ptr:
             raise RuntimeError("the pipeline's input format was never \"mjpeg\"")
         return np.frombuffer((C.c_uint32 * self.max_frames).from_address(ptr), dtype=np.uint32)
+
+    @property
+    def jpeg_planes(self):
+        """The planes mode of the "mjpeg" format (`set_input_format`): "off", "gray", "420", "422" or "444"."""
+        n = self.ctx.lib.cbv_pipeline_jpeg_planes(self.h_)
+        if n < 0:
+            self.ctx.check(n)
+        return {v: k for k, v in N.JPEG_PLANES.items()}[n]
 
     def jpeg_status(self, slot0, count):
         """The status words of the streams last decoded into the slots (0, or _native.JPEG_BAD_CODE | JPEG_NO_DATA |
@@ -889,3 +903,10 @@ class Board(_BoardMethods):
             self.close()
         except Exception:
             pass
+
+
+def jpeg_plane_slot_bytes(w, h, planes):
+    """Bytes of one slot of the plane ring of a w x h "mjpeg" pipeline in planes mode `planes` (`set_input_format`): the
+    largest plane_elems among the samplings the mode admits, rounded up to 256; 0 for off (include/cbv.h,
+    cbv_jpeg_plane_slot_bytes).  Needs no GPU."""
+    return int(N.load().cbv_jpeg_plane_slot_bytes(int(w), int(h), N.jpeg_planes_id(planes)))

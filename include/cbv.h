@@ -717,13 +717,14 @@ CBV_API int cbv_jpeg_decode_ex(cbv_ctx* ctx, const uint8_t* data, size_t n, uint
  * more than each slot's used bytes (rounded up to 256) and enqueues the decode into the BGR frame ring on the copy stream
  * behind the copy, with the ordering promises of the other formats.  Frames of different sampling and restart interval may
  * share a submit.  The decode's device scratch is sized when the format is set, for chunks of cbv_pipeline_jpeg_depth
- * frames (8 unless set) in the sampling that needs most; submit allocates nothing.  Motion-JPEG is never raw mode: a
- * pipeline without enhancement keeps its BGR ring, as for BGR input, and the decode fills it.  Until the copy has completed (cbv_pipeline_wait_submitted) the slots' bytes and
- * lengths belong to it. */
+ * frames (8 unless set) in the sampling that needs most; submit allocates nothing.  Unless the planes mode below is set,
+ * Motion-JPEG is not a raw format: a pipeline without enhancement keeps its BGR ring, as for BGR input, and the decode
+ * fills it.  Until the copy has completed (cbv_pipeline_wait_submitted) the slots' bytes and lengths belong to it. */
 CBV_API uint32_t* cbv_pipeline_host_jpeg_lengths(cbv_pipeline* p);
 CBV_API int cbv_pipeline_set_jpeg_slot_bytes(cbv_pipeline* p, size_t bytes);
 /* one stream decoded into a slot of the frame ring, synchronous, like cbv_pipeline_upload; in any input format but not in
- * raw mode (CBV_ERR_STATE) */
+ * the raw mode of a YUV or Bayer format (CBV_ERR_STATE).  In the raw mode of the planes mode below it decodes into the
+ * slot of the plane ring and writes status, figures and descriptor as cbv_pipeline_submit does. */
 CBV_API int cbv_pipeline_upload_jpeg(cbv_pipeline* p, int slot, const uint8_t* data, size_t n);
 /* the status words (CBV_JPEG_*) of the streams last decoded into the slots; waits for the submitted decodes */
 CBV_API int cbv_pipeline_jpeg_status(cbv_pipeline* p, int slot0, int count, int32_t* status);
@@ -740,7 +741,8 @@ CBV_API int cbv_pipeline_jpeg_stats(cbv_pipeline* p, int slot0, int count, cbv_j
  * Frames, status, figures and detector results do not depend on it.  Call between runs: it waits for the copy stream and
  * sizes the coefficient, plane, marker, piece and segment scratch anew, all of which scale with it; before the format is
  * set it is only stored.  The cost: per frame of depth, 3 bytes per sample of the frame in the sampling that needs most
- * (4:4:4 padded to 16 x 16 MCUs: 18.8 MB at 1080p) and 4 bytes per possible restart interval (ceil(w / 8) x ceil(h / 8) of
+ * (4:4:4 padded to 16 x 16 MCUs: 18.8 MB at 1080p; 2 bytes per sample, 12.5 MB, where the planes go to the plane ring of
+ * the planes mode below and the scratch holds none) and 4 bytes per possible restart interval (ceil(w / 8) x ceil(h / 8) of
  * them), plus the piece states (36 bytes per piece; by segments 40 per piece and 12 more per possible interval, the
  * segment words; the piece counts are cbv_pipeline_set_jpeg_entropy's).  CBV_ERR_ARG outside 1..64, CBV_ERR_STATE on a board handle; when the scratch
  * cannot be allocated the call fails and the depth that was stays with its scratch. */
@@ -749,6 +751,48 @@ CBV_API int cbv_pipeline_jpeg_stats(cbv_pipeline* p, int slot0, int count, cbv_j
 CBV_API int cbv_pipeline_set_jpeg_depth(cbv_pipeline* p, int frames);
 /* the depth set (or the default); negative: an error */
 CBV_API int cbv_pipeline_jpeg_depth(cbv_pipeline* p);
+/* The planes mode: Motion-JPEG as a raw format.  Off by default, and then everything above holds as it stands.  With a
+ * mode other than CBV_JPEG_PLANES_OFF, CBV_FMT_MJPEG is a raw format like the YUV and Bayer ones: on a pipeline configured
+ * with skip_enhance 1 or CBV_SKIP_ENHANCE_PROFILE_RAW the decode stops at the planes, which the inverse DCT writes straight
+ * into the frame's slot of a device plane ring; the colour step is not run, the decode's scratch holds no plane buffer, the
+ * pipeline holds no BGR ring, and the warp samples the plane ring: a tap at (x, y) is the pixel defined above (the luma
+ * sample, the chroma upsampled on the component's true size, the colour step), through the board's colour profile in the
+ * profile mode, so the results are byte for byte those of the decode followed by the warp.  A tap outside the frame is BGR 0.
+ * On a pipeline with enhancement, or configured CBV_SKIP_ENHANCE_PROFILE, the mode changes nothing but the refusal below:
+ * the decode fills the BGR ring.
+ *   The mode names the largest sampling a slot of the ring can hold; samplings in the order gray, 4:2:0, 4:2:2, 4:4:4:
+ * _GRAY admits gray streams, _420 gray and 4:2:0, _422 those and 4:2:2, _444 all.  cbv_jpeg_plane_slot_bytes(w, h, mode) is
+ * the size of a slot: the largest plane_elems (cbv_jpeg_info) among the samplings the mode admits, whole MCUs, rounded up
+ * to 256 (at 16 x 1, 4:2:0 needs 384 samples and 4:2:2 256); 0 for _OFF, an unknown mode, w < 1 or h < 1.  Host only.  At
+ * 1080p a _420 slot is 3.1 MB, a _422 slot 4.1 MB and a _444 slot 6.2 MB, as much as a BGR slot.
+ *   cbv_pipeline_set_jpeg_planes: on the pipeline only (CBV_ERR_STATE on a board handle); an unknown mode is CBV_ERR_ARG and
+ * changes nothing.  Before the format is set the mode is only stored; with the format set it waits for what is in flight,
+ * makes the new ring before it lets the old one go (when an allocation fails the setting that was stays, with its rings),
+ * and frees the ingest rings as a format change does.  The ring is zeroed and the descriptors the warp reads are gray
+ * frames of the pipeline's size, so a slot never decoded is a black frame and every read is in bounds.
+ *   In planes mode, whatever the configuration, cbv_pipeline_submit and cbv_pipeline_upload_jpeg refuse a stream whose
+ * sampling the mode does not admit like a stream of another size: CBV_ERR_UNSUPPORTED, the message naming the slot and
+ * the sampling, nothing enqueued.  A run in flight reads the planes and the descriptors of its slots; submit changes both
+ * only behind its wait for the newest run that reads the slots.  Every address the warp forms comes from the descriptor the
+ * host parser has validated, none from entropy data: a damaged stream changes sample values and nothing else.
+ *   In the raw mode of the planes mode: cbv_pipeline_download(which = 0) converts the slot on demand (the colour step on
+ * that slot: cbv_jpeg_decode_host's frame byte for byte); cbv_pipeline_upload, _synth and _upload_raw return CBV_ERR_STATE;
+ * status, figures, entropy path and depth work as before; cbv_pipeline_color_sweep samples the plane ring. */
+#define CBV_JPEG_PLANES_OFF 0
+#define CBV_JPEG_PLANES_GRAY 1
+#define CBV_JPEG_PLANES_420 2
+#define CBV_JPEG_PLANES_422 3
+#define CBV_JPEG_PLANES_444 4
+CBV_API int cbv_pipeline_set_jpeg_planes(cbv_pipeline* p, int mode);
+/* the mode set; negative: an error */
+CBV_API int cbv_pipeline_jpeg_planes(cbv_pipeline* p);
+CBV_API size_t cbv_jpeg_plane_slot_bytes(int w, int h, int mode);
+/* The stage entry point, host in, host out, beside cbv_warp_color_profile_raw: cbv_jpeg_decode, then
+ * cbv_apply_color_profile when profile->enabled, then cbv_warp_perspective (and the rotation by 180 degrees), byte for
+ * byte, with the BGR frame never made.  A tap outside the frame is BGR 0.  *status = the decode's status word.  Refusals:
+ * those of cbv_jpeg_decode and those of cbv_warp_color_profile_raw, with `out` untouched. */
+CBV_API int cbv_warp_jpeg(cbv_ctx* ctx, const uint8_t* data, size_t n, const cbv_color_profile* profile, const double* M9, int dw, int dh, int rot180,
+                          uint8_t* out, int out_stride, int32_t* status);
 
 /* ------------------------------------------------------------------ */
 /* several boards seen by one camera                                   */

@@ -3,6 +3,7 @@ frames sit in the pinned host ring; batch k+1 is copied and decoded (cbv_pipelin
 
     python tools/jpeg_timing.py [--streams FILE.npz] [--make-streams FILE.npz] [--reps 2]
                                 [--entropy auto|interval|pieces|segments] [--piece-bytes N] [--depth N]
+                                [--planes MODE[,MODE...]]
 
 Per variant (quality 75 / 90, 4:2:2 / 4:2:0; without DRI, with a restart interval of one MCU row ("-dri") and with one of
 eight MCU rows ("-dri8": a few long intervals, as a hardware encoder emits them) it prints the submit-only
@@ -13,6 +14,12 @@ into pieces too), --depth the frames a submit decodes per launch (BoardPipeline.
 with the decode's scratch in bytes (include/cbv.h's formula for the row's slot size) and the piece path's figures for the
 streams of the variant: pieces, rounds and the share of pieces settled in round 0.  The
 per-kernel times come from a kernel trace of this script (rocprofv3 --kernel-trace --stats).
+
+--planes measures the session chain instead (configure(enhance=False), what GameSession.on_frame runs) with the planes mode
+of the Motion-JPEG format as named: off, gray, 420, 422 or 444 (set_input_format("mjpeg", planes=...)).  Several modes,
+e.g. --planes off,422, are measured alternately in the one session, every repetition one after the other: "off" is the
+decode into the BGR ring (k_jpeg_color, then k_warp), any other mode the decode into the plane ring and k_warp_jpeg.  A
+stream whose sampling a mode does not admit is left out of that mode's rows.
 
 Encoding 1080p frames with tests/ref_jpeg.py takes a few seconds each, so the streams can be made once on any machine
 (--make-streams, no GPU: the frames are then the CPU oracle's synthetic scene) and loaded with --streams."""
@@ -34,6 +41,7 @@ ap.add_argument("--frames", type=int, default=2, help="distinct source frames pe
 ap.add_argument("--entropy", default="auto", choices=("auto", "interval", "pieces", "segments"))
 ap.add_argument("--depth", type=int, default=0, help="frames a Motion-JPEG submit decodes per launch (0: the library's default)")
 ap.add_argument("--piece-bytes", type=int, default=0, help="piece size of the piece path (0: the library's default)")
+ap.add_argument("--planes", help="comma-separated planes modes of the session chain (off, gray, 420, 422, 444) to measure alternately")
 ap.add_argument("--only", help="comma-separated variants to run (default: bgr, nv12, bayer_rggb and every JPEG variant)")
 args = ap.parse_args()
 
@@ -66,7 +74,9 @@ from chessboard_vision_amd.stream import BoardPipeline  # noqa: E402
 
 n = 2 * HALF
 p = BoardPipeline(W, H, n)
-p.configure(S.scaled_corners(W, H), profile=S.SHIPPED_PROFILE, grid_lines=(S.CALIB_GRID_X, S.CALIB_GRID_Y), **S.SHIPPED_DETECTOR)
+PLANES = args.planes.split(",") if args.planes else [None]  # None: the enhanced pipeline, as before --planes existed
+p.configure(S.scaled_corners(W, H), profile=S.SHIPPED_PROFILE, grid_lines=(S.CALIB_GRID_X, S.CALIB_GRID_Y),
+            **(dict(enhance=False) if args.planes else {}), **S.SHIPPED_DETECTOR)
 p.set_jpeg_entropy(args.entropy, args.piece_bytes)
 if args.depth:
     p.set_jpeg_depth(args.depth)
@@ -89,14 +99,15 @@ def nv12(f):
     return np.concatenate([y, np.stack((u[::2, ::2], v[::2, ::2]), axis=-1).reshape(H // 2, W)])
 
 
-def scratch_bytes(slot_bytes):
+def scratch_bytes(slot_bytes, planes=None):
     """the decode's device scratch for the pipeline's settings (include/cbv.h, cbv_pipeline_set_jpeg_depth)"""
     pw, ph = (W + 15) // 16 * 16, (H + 15) // 16 * 16
     max_int = (W + 7) // 8 * ((H + 7) // 8)
     S = 0 if args.entropy == "interval" else args.piece_bytes or 64
     seg = args.entropy == "segments"
     pieces = (-(-slot_bytes // S) + (max_int if seg else 0)) if S else 0
-    return p.jpeg_depth * (3 * 3 * pw * ph + 4 * max_int + pieces * (40 if seg else 36) + (4 * (3 * max_int + 1) if seg else 0))
+    per_sample = 2 if planes not in (None, "off") else 3  # the planes go to the plane ring: the scratch holds the coefficients alone
+    return p.jpeg_depth * (per_sample * 3 * pw * ph + 4 * max_int + pieces * (40 if seg else 36) + (4 * (3 * max_int + 1) if seg else 0))
 
 
 def sync():
@@ -105,7 +116,10 @@ def sync():
     p.results(0, 1)
 
 
-def load(fmt):
+ADMITS = {"gray": (), "420": ("420",), "422": ("420", "422"), "444": ("420", "422", "444")}
+
+
+def load(fmt, planes=None):
     """the ring filled in `fmt`; returns the bytes a submit of one frame moves, on average"""
     if fmt in ("nv12", "bayer_rggb", "bgr"):
         p.set_input_format(fmt)
@@ -115,7 +129,7 @@ def load(fmt):
             ring[i] = src[i % nsrc]
         return src[0].size
     data = [streams["%s_%d" % (fmt, i)] for i in range(nsrc)]
-    p.set_input_format("mjpeg", slot_bytes=max(len(d) for d in data))
+    p.set_input_format("mjpeg", slot_bytes=max(len(d) for d in data), planes=planes if planes not in (None, "off") else False)
     ring, lengths = p.host_ring(), p.jpeg_lengths()
     for i in range(n):
         d = data[i % nsrc]
@@ -124,8 +138,8 @@ def load(fmt):
     return sum((len(d) + 255) // 256 * 256 for d in data) / nsrc
 
 
-def measure(fmt):
-    link = load(fmt)
+def measure(fmt, planes=None):
+    link = load(fmt, planes)
     p.submit(0, n)
     p.run(0, n)
     sync()
@@ -151,17 +165,19 @@ def measure(fmt):
     t_one = (time.perf_counter() - t0) / 20
     frames = ROUNDS * n
     stats = p.jpeg_stats(0, nsrc) if p.input_format == "mjpeg" else None
-    scratch = scratch_bytes(p.ctx.lib.cbv_pipeline_host_slot_bytes(p.h_)) if p.input_format == "mjpeg" else 0
+    scratch = scratch_bytes(p.ctx.lib.cbv_pipeline_host_slot_bytes(p.h_), planes) if p.input_format == "mjpeg" else 0
     return frames / t_copy, frames / t_ovl, link, t_one, stats, scratch
 
 
 formats = args.only.split(",") if args.only else ["bgr", "nv12", "bayer_rggb"] + [vname(*v) for v in VARIANTS]
-for rep in range(args.reps):
-    for fmt in formats:
-        c, o, link, one, stats, scratch = measure(fmt)
-        tail = "   depth %d scratch %d bytes" % (p.jpeg_depth, scratch) if scratch else ""
-        if stats is not None and stats[:, 0].any():
-            tail += "   pieces %s rounds %s settled in round 0 %.2f" % (stats[:, 0].tolist(), stats[:, 1].tolist(), stats[:, 2].sum() / stats[:, 0].sum())
-        print("[%s, rep %d] submit only %8.0f frames/s   submit || run %8.0f frames/s   link %9.0f bytes/frame   one frame in flight %7.1f us%s"
-              % (fmt, rep + 1, c, o, link, one * 1e6, tail), flush=True)
+for rep, fmt, planes in ((r, f, m) for r in range(args.reps) for f in formats for m in PLANES):
+    if planes not in (None, "off") and fmt.startswith("q") and fmt.split("-")[1] not in ADMITS[planes]:
+        continue
+    c, o, link, one, stats, scratch = measure(fmt, planes)
+    row = fmt if planes is None else "%s planes %s" % (fmt, planes)
+    tail = "   depth %d scratch %d bytes" % (p.jpeg_depth, scratch) if scratch else ""
+    if stats is not None and stats[:, 0].any():
+        tail += "   pieces %s rounds %s settled in round 0 %.2f" % (stats[:, 0].tolist(), stats[:, 1].tolist(), stats[:, 2].sum() / stats[:, 0].sum())
+    print("[%s, rep %d] submit only %8.0f frames/s   submit || run %8.0f frames/s   link %9.0f bytes/frame   one frame in flight %7.1f us%s"
+          % (row, rep + 1, c, o, link, one * 1e6, tail), flush=True)
 p.close()

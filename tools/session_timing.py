@@ -9,6 +9,11 @@ Prints ONE JSON object:
   host_fed  frames/s of YUV and Bayer frames fed through the pinned ring in two halves, the copy of one half overlapping the
             run of the other; the copy alone and the runs alone beside it say which of the two limits the rate
   latency   wall time of run + results of one frame
+  mjpeg     (`--only mjpeg`, 1080p) the session chain fed Motion-JPEG streams through the pinned ring, planes off (the decode
+            fills the BGR ring, k_warp samples it) and planes on (the decode stops at the plane ring, k_warp_jpeg samples it),
+            measured alternately: frames/s as in host_fed, and the latency of submit + run + results of one frame.  The
+            streams are those of `tools/jpeg_timing.py --make-streams FILE.npz` (`--mjpeg-streams FILE.npz`, variant
+            `--mjpeg-variant`), or, without a file, one synthetic frame encoded here by tests/ref_jpeg.py.
 
     python tools/session_timing.py [--quick] [--rounds N] [--reps N] [--formats nv12,yuv420p] [--sizes 1080p]      (GPU box)
 """
@@ -184,6 +189,84 @@ def host_fed(size, fmt, ring, reps):
     return row
 
 
+def mjpeg_fed(ring, reps, streams_file, variant, rounds):
+    """the session chain at 1080p fed JPEG streams, planes off and on alternately, `rounds` times each"""
+    w, h = SIZES["1080p"]
+    pts = S.scaled_corners(w, h)
+    half = ring // 2
+    if streams_file:
+        z = np.load(streams_file)
+        data = [z[k] for k in sorted(z.files) if k.startswith(variant + "_")]
+    else:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import ref_jpeg as R
+        q, sampling = variant.split("-")[:2]
+        src = BoardPipeline(w, h, 1)
+        src.synth(0, 1, scene="normal")
+        data = [np.frombuffer(R.encode_image(src.download(0, 0), quality=int(q[1:]), sampling=sampling), np.uint8)]
+        src.close()
+    assert data, "no stream of variant %s" % variant
+    planes_on = variant.split("-")[1]
+    row = dict(size="1080p", variant=variant, ring=ring, stream_bytes=[int(len(d)) for d in data], planes_off=[], planes_on=[])
+    for r in range(rounds):
+        for planes in (False, planes_on):
+            p = BoardPipeline(w, h, ring)
+            p.configure(pts, profile=S.SHIPPED_PROFILE, chunk=min(64, half), enhance=False, **S.SHIPPED_DETECTOR)
+            p.set_input_format("mjpeg", slot_bytes=max(len(d) for d in data), planes=planes)
+            hr, lengths = p.host_ring(), p.jpeg_lengths()
+            for i in range(ring):
+                d = data[i % len(data)]
+                hr[i, :len(d)] = d
+                lengths[i] = len(d)
+
+            def both(n=4):
+                p.submit(0, half)
+                for k in range(n):
+                    for hf in (0, 1):
+                        if k + 1 < n or hf == 0:
+                            p.submit((1 - hf) * half, half)  # the other half is copied and decoded while this one runs
+                        p.run(hf * half, half)
+                p.results(0, ring)
+                return 2 * n * half
+
+            def copies(n=4):
+                for _ in range(n):
+                    p.submit(0, half)
+                    p.submit(half, half)
+                p.wait_submitted()
+                return 2 * n * half
+
+            def runs(n=4):
+                for _ in range(n):
+                    p.run(0, half)
+                    p.run(half, half)
+                p.results(0, ring)
+                return 2 * n * half
+
+            res = {}
+            for name, fn in (("overlapped", both), ("submit_only", copies), ("run_only", runs)):
+                fn(1)
+                t = []
+                for _ in range(reps):
+                    p.ctx.synchronize()
+                    t0 = time.perf_counter()
+                    nfr = fn()
+                    p.ctx.synchronize()
+                    t.append(nfr / (time.perf_counter() - t0))
+                res[name] = spread(t)
+            t = []
+            for i in range(120):  # one frame from the ring to its results
+                t0 = time.perf_counter()
+                p.submit(i % 2, 1)
+                p.run(i % 2, 1)
+                p.results(i % 2, 1)
+                t.append(time.perf_counter() - t0)
+            res["one_frame_ms"] = spread([1e3 * x for x in t[20:]])
+            row["planes_on" if planes else "planes_off"].append(res)
+            p.close()
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -192,6 +275,8 @@ def main():
     ap.add_argument("--only", default="fused,resident,host_fed")
     ap.add_argument("--formats", default=",".join(FMTS))
     ap.add_argument("--sizes", default="1080p,4k")
+    ap.add_argument("--mjpeg-streams", help="npz of 1080p streams from tools/jpeg_timing.py --make-streams (the mjpeg rows)")
+    ap.add_argument("--mjpeg-variant", default="q90-422-nodri")
     a = ap.parse_args()
     sizes = ["1080p"] if a.quick else a.sizes.split(",")
     fmts = a.formats.split(",")
@@ -205,6 +290,8 @@ def main():
         out["resident"] = [resident(s, k, 32 if a.quick else 512, a.reps) for s in sizes for k in (1, 4)]
     if "host_fed" in a.only:
         out["host_fed"] = [host_fed(s, f, 16 if a.quick else {"1080p": 128, "4k": 64}[s], a.reps) for s in sizes for f in fmts]
+    if "mjpeg" in a.only:
+        out["mjpeg"] = [mjpeg_fed(16 if a.quick else 128, a.reps, a.mjpeg_streams, a.mjpeg_variant, 1 if a.quick else a.rounds)]
     print(json.dumps(out))
 
 
