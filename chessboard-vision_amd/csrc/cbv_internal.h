@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/cbv.h"
+#include "frame_plan.h"
 
 typedef uint8_t u8;
 typedef uint16_t u16;
@@ -364,17 +365,12 @@ struct RawGeom {
     int stride0, stride1, stride2; // bytes per row of plane 0 (luma, the packed 4:2:2 bytes, or the mosaic) / plane 1 / plane 2, in memory order
     size_t frame_stride;
 };
-// the bit fields of a format id (include/cbv.h)
-static constexpr bool raw_fmt_bayer(int fmt)
-{
-    return fmt == CBV_FMT_BAYER_RGGB || fmt == CBV_FMT_BAYER_BGGR || fmt == CBV_FMT_BAYER_GRBG || fmt == CBV_FMT_BAYER_GBRG;
-}
+// (the bit fields of a format id: frame_plan.h has raw_fmt_bayer, raw_fmt_420 and raw_frame_bytes)
 static inline bool raw_fmt_known(int fmt)
 {
     return fmt == CBV_FMT_NV12 || fmt == CBV_FMT_NV21 || fmt == CBV_FMT_YUV420P || fmt == CBV_FMT_YV12 || fmt == CBV_FMT_YUYV ||
            fmt == CBV_FMT_YVYU || fmt == CBV_FMT_UYVY || raw_fmt_bayer(fmt);
 }
-static inline bool raw_fmt_420(int fmt) { return (fmt & 15) == CBV_FMT_NV12; }
 static inline int raw_fmt_planes(int fmt) { return !raw_fmt_420(fmt) ? 1 : (fmt & 0x20) ? 3 : 2; }
 static inline const char* raw_fmt_name(int fmt)
 {
@@ -401,10 +397,6 @@ static inline int raw_plane_wbytes(int fmt, int w, int i)
 }
 static inline int raw_plane_rows(int fmt, int h, int i) { return i == 0 ? h : h / 2; }
 // tightly packed raw frames, planes back to back, each frame rounded to 256 bytes (the ingest rings); fmt BGR: tight_geom's frame_stride
-static inline size_t raw_frame_bytes(int fmt, int w, int h)
-{
-    return raw_fmt_420(fmt) ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_BGR ? 3 : raw_fmt_bayer(fmt) ? 1 : 2);
-}
 static inline RawGeom tight_raw_geom(int fmt, int w, int h)
 {
     RawGeom r;
@@ -895,11 +887,7 @@ struct JpegBatch {
     size_t seg_stride;
     u32* stats;               // [nframes][3]: pieces, rounds, settled in round 0; zeros for a frame decoded by interval
 };
-enum { JPEG_PIECE_WORDS = 9 }; // four states (this round's and the last one's exit, the entry, round 0's exit) and a block count
-enum { JPEG_SEG_WORDS = 3 };   // a segment's first piece, its last written piece, one past its last block with a decoded DC symbol
-// the piece path's scratch per frame, in u32 words, for `pieces` pieces and (in segments mode) `intervals` restart intervals
-inline size_t jpeg_piece_words(size_t pieces, int segments) { return pieces * (size_t)(JPEG_PIECE_WORDS + (segments ? 1 : 0)); }
-inline size_t jpeg_seg_words(size_t intervals) { return intervals * JPEG_SEG_WORDS + 1; }
+// (JPEG_PIECE_WORDS, JPEG_SEG_WORDS, jpeg_piece_words and jpeg_seg_words: frame_plan.h)
 // zeroes coef, status, nfound, stats and the segment scratch, then the kernels on ctx->stream; total_intervals = ioff[nframes],
 // any_dri / any_pieces: a frame has restart intervals / goes the piece path, max_blocks = the largest plane_total / 64,
 // max_w x max_h = the largest frame

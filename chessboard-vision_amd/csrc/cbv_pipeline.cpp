@@ -5,6 +5,13 @@
 // a handle of a board attached by cbv_pipeline_add_board (not board 0, which stands for the whole pipeline)
 bool attached(const cbv_pipeline* p) { return p != p->pipe->boards[0]; }
 
+Pipe* frames_owner(cbv_pipeline* p, const char* who, const char* null_msg, int* rc)
+{
+    *rc = !p ? (null_msg ? cbv_fail(nullptr, CBV_ERR_ARG, "%s: %s", who, null_msg) : CBV_ERR_ARG)
+             : attached(p) ? cbv_fail(p->pipe->ctx, CBV_ERR_STATE, "%s: frames go to the parent of a board", who) : CBV_OK;
+    return *rc ? nullptr : p->pipe;
+}
+
 bool ranges_overlap(int a0, int an, int b0, int bn) { return a0 < b0 + bn && b0 < a0 + an; }
 
 void retire_runs(Pipe& P)
@@ -176,31 +183,6 @@ int pipeline_tables(Pipe& P)
     return CBV_OK;
 }
 
-// The BGR frame ring exists unless the pipeline is configured with CBV_SKIP_ENHANCE_PROFILE_RAW and its input format is raw:
-// then the raw ring holds every byte, nothing reads or writes BGR frames, and the ring (6.2 MB a 1080p slot) is given back.
-// (skip_enhance = 1 keeps its ring in raw mode, as it always did.)  Motion-JPEG in planes mode has no BGR ring in either raw
-// configuration: the plane ring holds the frames.  Called when the mode or the input format changes; what
-// is in flight is joined before the ring goes.
-int pipeline_frame_ring(Pipe& P)
-{
-    cbv_ctx* ctx = P.ctx;
-    const bool want = !((P.configured_raw_profile() && P.fmt_is_raw()) || P.jpeg_raw());
-    if (want && !P.frames) {
-        const size_t bytes = P.g.frame_stride * P.max_frames;
-        if (hipMalloc((void**)&P.frames, bytes + 256) != hipSuccess) {
-            P.frames = nullptr;
-            return cbv_fail(ctx, CBV_ERR_HIP, "hipMalloc of %zu bytes for the frame ring failed", bytes);
-        }
-    } else if (!want && P.frames) {
-        RC(join_scan(P));
-        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
-        (void)hipFree(P.frames);
-        P.frames = nullptr;
-    }
-    return CBV_OK;
-}
-
 // enhance_region: the bounding rectangle of every board's warp footprint (any board without one: the whole frame); the
 // third scratch frame set is allocated when the region first becomes usable
 int pipeline_update_region(Pipe& P)
@@ -348,11 +330,14 @@ extern "C" int cbv_pipeline_create(cbv_ctx* ctx, int w, int h, int max_frames, c
     P->h = h;
     P->max_frames = max_frames;
     P->g = tight_geom(w, h);
-    hipError_t e = hipMalloc((void**)&P->frames, P->g.frame_stride * max_frames + 256);
-    if (e != hipSuccess) {
-        const size_t want = P->g.frame_stride * max_frames;
+    FrameSettings fs;
+    fs.w = w;
+    fs.h = h;
+    fs.max_frames = max_frames;
+    const int rc = pipeline_set_frames(*P, fs, "cbv_pipeline_create", false); // the BGR ring
+    if (rc) {
         delete P;
-        return cbv_fail(ctx, CBV_ERR_HIP, "hipMalloc of %zu bytes for the frame ring failed: %s", want, hipGetErrorString(e));
+        return rc;
     }
     P->boards.push_back(new cbv_pipeline{P, Board()});
     *out = P->boards[0];
@@ -391,10 +376,7 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     if (P->main_done) (void)hipEventDestroy(P->main_done);
     if (P->copy_stream) (void)hipStreamSynchronize(P->copy_stream);
     for (auto& c : P->copies) (void)hipEventDestroy(c.ev);
-    if (P->host_ring) (void)hipHostFree(P->host_ring);
-    if (P->raw_ring) (void)hipFree(P->raw_ring);
-    pipeline_jpeg_free(*P);
-    if (P->frames) (void)hipFree(P->frames);
+    pipeline_frames_free(*P);
     if (P->enhanced) (void)hipFree(P->enhanced);
     dev_free(&P->d_synth);
     dev_free(&P->d_boards);
@@ -402,7 +384,7 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     delete P;
 }
 
-// (null while a CBV_SKIP_ENHANCE_PROFILE_RAW pipeline's frames are raw: it has no BGR ring)
+// (null where the plan has no BGR ring)
 extern "C" void* cbv_pipeline_frames_dev(cbv_pipeline* p) { return p && !attached(p) ? p->pipe->frames : nullptr; }
 
 extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config* cfg)
@@ -462,11 +444,9 @@ extern "C" int cbv_pipeline_configure(cbv_pipeline* p, const cbv_pipeline_config
     // region-limited enhancement: the source footprint of the S x S warp (warp_footprint)
     RC(pipeline_update_region(P));
     RC(pipeline_tables(P));
-    RC(pipeline_frame_ring(P));
-    if (P.in_fmt == CBV_FMT_MJPEG && P.jpeg && P.jpeg_slot_bytes) { // the decode's scratch has a plane buffer only where the planes do not go to the ring
-        if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
-        RC(pipeline_jpeg_size_scratch(P, "cbv_pipeline_configure"));
-    }
+    FrameSettings next = P.fs; // the configuration decides where a raw format's frames live
+    next.kind = frame_kind(cfg->skip_enhance);
+    RC(pipeline_set_frames(P, next, "cbv_pipeline_configure", false));
     P.configured = true;
     return CBV_OK;
 }
@@ -744,15 +724,14 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
     size_t bytes;
     if (attached(p) && which != 2) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: a board holds only its warped frames (which = 2)");
     if (which == 0) {
-        src = P.raw_mode() ? nullptr : P.frames + P.g.frame_stride * slot;
+        src = P.plan.raw() ? nullptr : P.frames + P.g.frame_stride * slot;
         bytes = (size_t)P.w * P.h * 3;
-        if (P.raw_mode()) { // the frames are raw: the slot is converted for the caller
-            if (!pipeline_raw_frames_exist(P)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: no raw frame was ever uploaded or submitted");
+        if (P.plan.raw()) { // the frames are raw: the slot is converted for the caller
+            if (P.plan.source == FRAMES_RAW && !P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_download: no raw frame was ever uploaded or submitted");
             if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // submitted copies of the slot
-            const RawGeom rg = tight_raw_geom(P.in_fmt, P.w, P.h);
             RC(dev_ensure(ctx, &ctx->a, P.g.frame_stride + 256));
-            if (P.jpeg_planes_on()) RC(pipeline_jpeg_slot_bgr(P, slot, (u8*)ctx->a.p)); // k_jpeg_color on the slot's planes
-            else RC(launch_ingest(ctx, slot_planes(P, slot), rg, (u8*)ctx->a.p, P.g, 1));
+            if (P.plan.source == FRAMES_PLANES) RC(pipeline_jpeg_slot_bgr(P, slot, (u8*)ctx->a.p)); // k_jpeg_color on the slot's planes
+            else RC(launch_ingest(ctx, slot_planes(P, slot), tight_raw_geom(P.fs.fmt, P.w, P.h), (u8*)ctx->a.p, P.g, 1));
             src = (const u8*)ctx->a.p;
         }
     } else if (which == 1) {

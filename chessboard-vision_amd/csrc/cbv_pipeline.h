@@ -68,11 +68,10 @@ struct Pipe {
     bool skip_enhance = false; // cfg.skip_enhance: the warp samples the frames as they are, no enhancement scratch exists
     // cfg.skip_enhance == CBV_SKIP_ENHANCE_PROFILE or CBV_SKIP_ENHANCE_PROFILE_RAW: the warp samples the frames and, when a
     // board has an enabled profile (profile_on), applies each board's colour profile to its taps (k_warp_profile,
-    // k_warp_raw_profile) from the boards' own tables, Board::d_ptabs.  profile_raw: the latter mode, in which a YUV or Bayer
-    // input format makes the raw ring the frames (raw_mode below)
+    // k_warp_raw_profile) from the boards' own tables, Board::d_ptabs.  profile_raw: the latter mode
     bool profile_only = false, profile_on = false, profile_raw = false;
     int chunk = 8;
-    u8* frames = nullptr; // the BGR frame ring; null while a CBV_SKIP_ENHANCE_PROFILE_RAW pipeline's frames are raw (pipeline_frame_ring)
+    u8* frames = nullptr; // the BGR frame ring; null where plan.bgr_ring says so
     // Lanes: chunk c runs on lane c % n_lanes, each lane with its own HIP stream and scratch, so a
     // VALU-bound bilateral launch of one chunk overlaps the memory-latency-bound kernels of another.
     enum { MAX_LANES = 4 };
@@ -89,21 +88,25 @@ struct Pipe {
     DevBuf lane_work[MAX_LANES]; // HoughCircles worklist of the lane's current chunk: count, then frame << 8 | square
     u8* enhanced = nullptr;      // [max_frames] when keep_enhanced
     DevBuf d_synth;
-    // ingest: pinned host mirror of the frame ring, filled by the capture side and copied on its own stream; with a YUV
-    // input format (cbv_pipeline_set_input_format) both it and `raw_ring`, its device copy, hold raw frames, which
-    // k_ingest converts into `frames` behind the copy
+    // ingest: pinned host mirror of the frame ring, filled by the capture side and copied on its own stream; with a YUV or
+    // Bayer input format both it and `raw_ring`, its device copy, hold raw frames, which k_ingest converts into `frames`
+    // behind the copy, unless the raw ring is THE frames (plan.source == FRAMES_RAW: the warp samples it, nothing is converted).
+    // Motion-JPEG: both rings hold one JPEG stream per slot and the decode writes `frames` behind the copy, or, where the
+    // plane ring is the frames (FRAMES_PLANES), stops at the planes, which it writes there (cbv_pipeline_jpeg.cpp).
+    // `fs` says which of these holds and `plan` what follows from it (frame_plan.h); cbv_pipeline_frames.cpp alone changes
+    // either, together with the buffers below, which always match `plan`.
+    FrameSettings fs;
+    FramePlan plan;
     u8* host_ring = nullptr;
-    int in_fmt = CBV_FMT_BGR;
-    // Without enhancement (skip_enhance 1 or CBV_SKIP_ENHANCE_PROFILE_RAW) a YUV or Bayer input format makes the raw ring THE frames: k_warp_yuv /
-    // k_warp_bayer / k_warp_raw_profile samples it, nothing is converted and `frames` is neither written nor read (raw_mode below).
-    u8* raw_ring = nullptr; // [max_frames] raw frames (tight_raw_geom), allocated on first use; null with CBV_FMT_BGR
-    // Motion-JPEG (CBV_FMT_MJPEG): both rings hold one JPEG stream per slot, jpeg_slot_bytes apart, and the decode writes
-    // `frames` behind the copy (cbv_jpeg.cpp).  With jpeg_planes (cbv_pipeline_set_jpeg_planes) other than OFF the format is a
-    // raw one: without enhancement the decode stops at the planes, which it writes into the plane ring (JpegState), the warp
-    // samples that ring (k_warp_jpeg) and the BGR ring is given back.
-    struct JpegState* jpeg = nullptr;
-    size_t jpeg_slot_bytes = 0;
-    int jpeg_planes = CBV_JPEG_PLANES_OFF;
+    u8* raw_ring = nullptr;   // [max_frames] slots of plan.slot_bytes; both made on first use, let go by every format change
+    u8* plane_ring = nullptr; // [max_frames] slots of plan.plane_slot bytes and 256 more
+    struct JpegScratch {      // the scratch of one launch of a submit's decode, plan.depth frames of everything
+        u32* mpos = nullptr;     // [depth * max_int]
+        int16_t* coef = nullptr; // [depth][frame_elems]
+        u8* planes = nullptr;    // [depth][frame_elems] with plan.own_planes
+        u32 *pieces = nullptr, *segs = nullptr; // [depth][piece_words], [depth][seg_words]
+    } jsc;
+    struct JpegState* jpeg = nullptr; // what lives as long as the slots, from the first Motion-JPEG frame or format on
     hipStream_t copy_stream = nullptr;
     struct CopyRec {
         int s0, cnt;
@@ -146,17 +149,7 @@ struct Pipe {
     bool any_own_blur = false; // some board's ChangeDetector has a blur kernel of its own: k_change_blur_stats runs behind the statistics
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
-    // Motion-JPEG: CBV_JPEG_ENTROPY_* and the piece size (0: the default), cbv_pipeline_set_jpeg_entropy
-    int jpeg_entropy = 0;
-    uint32_t jpeg_piece_bytes = 0;
-    int jpeg_depth = CBV_JPEG_DEPTH_DEFAULT; // frames per launch of a Motion-JPEG submit, cbv_pipeline_set_jpeg_depth
     Board& b0() const { return boards[0]->b; }
-    bool configured_raw_profile() const { return skip_enhance && profile_raw; }
-    bool jpeg_planes_on() const { return in_fmt == CBV_FMT_MJPEG && jpeg_planes != CBV_JPEG_PLANES_OFF; }
-    bool fmt_is_raw() const { return (in_fmt != CBV_FMT_BGR && in_fmt != CBV_FMT_MJPEG) || jpeg_planes_on(); } // YUV, Bayer, or JPEG planes
-    bool raw_config() const { return skip_enhance && (!profile_only || profile_raw); } // a configuration in which a raw format's frames stay raw
-    bool raw_mode() const { return raw_config() && fmt_is_raw(); }
-    bool jpeg_raw() const { return raw_config() && jpeg_planes_on(); } // raw mode on the plane ring
 };
 // cbv_pipeline.cpp: board handles, the ordering of the runs in flight, the boards' kernel arguments, read-backs
 bool attached(const cbv_pipeline* p);
@@ -167,26 +160,49 @@ int join_scan(Pipe& P);
 int join_slots(Pipe& P, int s0, int cnt);
 ChangeBlur change_blur_coef(int k);
 int pipeline_tables(Pipe& P);
-int pipeline_frame_ring(Pipe& P);
 int board_set_profile(Pipe& P, Board& b, const cbv_color_profile* profile, const char* who);
 int pipeline_update_region(Pipe& P);
 int pipeline_readback(Pipe& P, void* out, const void* dev, size_t bytes);
+// The pipeline whose frames the handle stands for, or null with *rc set: a null handle is CBV_ERR_ARG, with "<who>: <null_msg>"
+// as the error text unless null_msg is null; a board's handle is CBV_ERR_STATE, "<who>: frames go to the parent of a board".
+Pipe* frames_owner(cbv_pipeline* p, const char* who, const char* null_msg, int* rc);
+// cbv_pipeline_frames.cpp: the one place where the frame store's settings and buffers change.  Makes the buffers match
+// frame_plan(next) and commits `next`; on failure every setting and buffer is as it was.  drop_ingest: the call is a format
+// change, which lets both ingest rings go (they come back on first use).
+int pipeline_set_frames(Pipe& P, const FrameSettings& next, const char* who, bool drop_ingest);
+int pipeline_host_ring(Pipe& P); // the lazy ingest rings: the pinned one (and, for a format other than BGR, the device one)
+int pipeline_raw_ring(Pipe& P);
+int pipeline_jpeg_ensure(Pipe& P);
+void pipeline_frames_free(Pipe& P);
 // cbv_pipeline_ingest.cpp
 RawPlanes slot_planes(const Pipe& P, int slot);
-// cbv_jpeg.cpp: the Motion-JPEG ingest
-size_t pipeline_jpeg_default_slot_bytes(int w, int h);
-int pipeline_jpeg_ensure(Pipe& P);
-int pipeline_jpeg_size_scratch(Pipe& P, const char* who);
-void pipeline_jpeg_free(Pipe& P);
-int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev);
-// the plane ring of the pipeline's jpeg_planes mode: made (zeroed, the warp's descriptors gray frames) when the mode has one
-// and it is not there, let go when the mode is OFF; the caller has joined what reads it
-int pipeline_jpeg_plane_ring(Pipe& P, const char* who);
-bool pipeline_jpeg_has_planes(const Pipe& P);
-// what the warp samples in raw mode on the plane ring: `slot0`'s planes and descriptor, the frames behind them
-WarpSrc pipeline_jpeg_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs = nullptr, int np = 1, size_t dst_profile_stride = 0);
-// cbv_pipeline_download(which = 0) in raw mode on the plane ring: k_jpeg_color of the slot into `bgr` (device, P.g)
-int pipeline_jpeg_slot_bgr(Pipe& P, int slot, u8* bgr);
-// what the warp samples in raw mode, whatever the raw format (cbv_pipeline_ingest.cpp)
+// what the warp samples where plan.raw(), whatever the raw format
 WarpSrc pipeline_raw_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs = nullptr, int np = 1, size_t dst_profile_stride = 0);
-bool pipeline_raw_frames_exist(const Pipe& P);
+// cbv_pipeline_jpeg.cpp: the Motion-JPEG ingest
+struct JpegState {
+    enum { NSETS = 16 };
+    // pinned
+    u32* h_lengths = nullptr;   // [max_frames], the capture side's
+    JpegDesc* h_desc = nullptr; // [max_frames]
+    u32* h_ioff = nullptr;      // [2 * max_frames]: the chunk that starts at slot s has its prefix sums at 2 s
+    JpegTables* h_tabs = nullptr; // [NSETS] the table sets seen, by content
+    int nsets = 0;
+    // device
+    JpegDesc* d_desc = nullptr;
+    u32* d_ioff = nullptr;
+    JpegTables* d_tabs = nullptr;
+    int* d_status = nullptr; // [max_frames]
+    int* d_nfound = nullptr; // [max_frames]
+    u32* d_stats = nullptr;  // [max_frames][3]
+    // the descriptors the WARP reads beside the plane ring, which change only behind the wait for the runs that read them
+    // (d_desc is the decode's)
+    JpegDesc* d_wdesc = nullptr; // [max_frames]
+};
+int pipeline_jpeg_submit(Pipe& P, int slot0, int count, hipEvent_t read_ev);
+// what the warp samples on the plane ring: `slot0`'s planes and descriptor, the frames behind them
+WarpSrc pipeline_jpeg_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs = nullptr, int np = 1, size_t dst_profile_stride = 0);
+// cbv_pipeline_download(which = 0) on the plane ring: k_jpeg_color of the slot into `bgr` (device, P.g)
+int pipeline_jpeg_slot_bgr(Pipe& P, int slot, u8* bgr);
+// cbv_jpeg.cpp: one stream through the decode kernels on ctx->stream with the context's scratch
+int jpeg_single_dev(cbv_ctx* ctx, const uint8_t* data, size_t n, JpegDesc& D, const JpegTables& T, u32 S, int segments, u8* bgr_dev, Geom g,
+                    JpegBatch* Bout, u8* planes_dev = nullptr, bool no_bgr = false);

@@ -173,7 +173,7 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
     if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: a board is run by its parent");
     if (slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_run: bad slot range");
     CBV_ENTER(ctx);
-    if (P.raw_mode() && !pipeline_raw_frames_exist(P)) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: no raw frame was ever uploaded or submitted");
+    if (P.plan.source == FRAMES_RAW && !P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: no raw frame was ever uploaded or submitted");
     const cbv_enhance_params& enh = P.b0().cfg.enhance;
     // Lane 0 is the context's stream; lanes 1.. are worker streams forked from it and joined before
     // the temporal scan (which needs every frame's statistics, in order).
@@ -233,7 +233,7 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
         const int lane = (lane_base + ci) % P.n_lanes;
         ctx->stream = lane == 0 ? main_stream : P.lane_stream[lane];
         const int b = std::min(P.chunk, slot0 + count - s0);
-        const u8* src = P.raw_mode() ? nullptr : P.frames + P.g.frame_stride * s0; // (raw mode: the warp samples the raw ring)
+        const u8* src = P.plan.raw() ? nullptr : P.frames + P.g.frame_stride * s0; // (raw mode: the warp samples the raw ring)
         u32* work = P.any_hough ? (u32*)P.lane_work[lane].p : nullptr; // worklist counter: zeroed by k_warp
         u32* retry0 = P.any_hough && retry_zero_in_warp ? (u32*)rec->retry.p : nullptr;
         if (P.skip_enhance) { // the session's chain: the warp samples the frames as they are (in raw mode the raw ring: no BGR source)

@@ -355,10 +355,10 @@ extern "C" int cbv_pipeline_color_sweep(cbv_pipeline* p, int slot0, int count, c
     if (np > CBV_COLOR_SWEEP_MAX_PROFILES) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %d profiles (at most %d)", who, np, CBV_COLOR_SWEEP_MAX_PROFILES);
     if (chunk < 0 || chunk > CBV_SWEEP_MAX_CHUNK) return cbv_fail(ctx, CBV_ERR_ARG, "%s: chunk_frames %d is outside 0..%d", who, chunk, CBV_SWEEP_MAX_CHUNK);
     if (slot0 < 0 || slot0 > P.max_frames - count) return cbv_fail(ctx, CBV_ERR_ARG, "%s: slots outside the ring of %d", who, P.max_frames);
-    if (P.raw_mode() && !P.profile_raw)
+    if (P.plan.raw() && !P.profile_raw)
         return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: the pipeline's frames are raw and it has no profile kernel (there is no BGR ring to read; "
                         "configure CBV_SKIP_ENHANCE_PROFILE_RAW, with a disabled profile for the plain raw warp)", who);
-    if (P.raw_mode() && !pipeline_raw_frames_exist(P)) return cbv_fail(ctx, CBV_ERR_STATE, "%s: no raw frame was ever uploaded or submitted", who);
+    if (P.plan.source == FRAMES_RAW && !P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "%s: no raw frame was ever uploaded or submitted", who);
     const int n = B.cfg.n_rois, S_ = B.cfg.board_size;
     HoughCfg hc;
     memset(&hc, 0, sizeof(hc));
@@ -417,7 +417,7 @@ extern "C" int cbv_pipeline_color_sweep(cbv_pipeline* p, int slot0, int count, c
             const int cf = std::min(chunk, count - c0), nb = pc * cf; // scratch frame of (profile i, frame f) = i * cf + f
             CBV_HIP(ctx, hipEventRecord(S.ev[0], ctx->stream));
             const ProfileTabs* pt = (const ProfileTabs*)S.tabs.p;
-            const WarpSrc src = P.raw_mode() ? pipeline_raw_warp_src(P, slot0 + c0, pt, pc, B.warped_stride * cf)
+            const WarpSrc src = P.plan.raw() ? pipeline_raw_warp_src(P, slot0 + c0, pt, pc, B.warped_stride * cf)
                                              : warp_src_profile(P.frames + P.g.frame_stride * (slot0 + c0), P.g, pt, pc, B.warped_stride * cf);
             RC(launch_warp(ctx, src, B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p, S_ * 3, B.warped_stride, cf));
             CBV_HIP(ctx, hipEventRecord(S.ev[1], ctx->stream));

@@ -22,6 +22,8 @@ rng = np.random.default_rng(1)
 w, h = 640, 480
 frame = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
 pts = S.scaled_corners(w, h)
+import jpeg_streams  # noqa: E402
+JPEG = np.frombuffer(jpeg_streams.shape_stream(w, h, "420"), np.uint8)
 log = []
 for it in range(n):
     p = BoardPipeline(w, h, 16)
@@ -46,9 +48,13 @@ for it in range(n):
         p.results(0, 8)
     ring = p.host_ring() if hasattr(p, "host_ring") and it % 4 == 0 else None
     if it % 2 == 0:  # the ingest rings in every format, back and forth (each switch frees the pinned and the device raw ring)
-        for fmt in ("nv12", "yuyv", "bgr", "nv12"):
-            p.set_input_format(fmt)
-            p.host_ring()[:] = 128
+        for fmt, planes in (("nv12", False), ("yuyv", False), ("bayer_rggb", False), ("mjpeg", False), ("mjpeg", True), ("bgr", False), ("nv12", False)):
+            p.set_input_format(fmt, slot_bytes=JPEG.size if fmt == "mjpeg" else None, planes=planes)
+            if fmt == "mjpeg":  # (the plane ring and the decode's scratch come and go with the format)
+                p.host_ring()[:8, :len(JPEG)] = JPEG
+                p.jpeg_lengths()[:8] = len(JPEG)
+            else:
+                p.host_ring()[:] = 128
             p.submit(0, 8)
             p.run(0, 8)
             p.results(0, 8)
