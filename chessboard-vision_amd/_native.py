@@ -42,6 +42,12 @@ class ColorProfile(C.Structure):
         return p
 
 
+class LensStruct(C.Structure):
+    """cbv_lens: OpenCV's camera matrix and five distortion coefficients (stream.Lens is the Python face of it)."""
+    _fields_ = [("enabled", C.c_int32), ("pad", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("k3", C.c_double)]
+
+
 class EnhanceParams(C.Structure):
     _fields_ = [("profile", ColorProfile), ("clahe_clip_limit", C.c_double), ("tiles_x", C.c_int32),
                 ("tiles_y", C.c_int32), ("bilateral_d", C.c_int32), ("sigma_color", C.c_double),
@@ -463,6 +469,13 @@ def load():
         "cbv_pipeline_jpeg_planes": (i32, [vp]),
         "cbv_jpeg_plane_slot_bytes": (C.c_size_t, [i32, i32, i32]),
         "cbv_warp_jpeg": (i32, [vp, vp, C.c_size_t, P(ColorProfile), vp, i32, i32, i32, u8p, i32, P(C.c_int32)]),
+        "cbv_lens_distort_points": (i32, [P(LensStruct), vp, i32, vp]),
+        "cbv_lens_undistort_points": (i32, [P(LensStruct), vp, i32, vp]),
+        "cbv_lens_warp_coords": (i32, [P(LensStruct), vp, i32, i32, vp]),
+        "cbv_lens_warp_footprint": (i32, [P(LensStruct), vp, i32, i32, i32, i32, vp]),
+        "cbv_warp_lens": (i32, [vp, P(RawFrame), i32, i32, P(ColorProfile), P(LensStruct), vp, i32, i32, i32, u8p, i32]),
+        "cbv_warp_jpeg_lens": (i32, [vp, vp, C.c_size_t, P(ColorProfile), P(LensStruct), vp, i32, i32, i32, u8p, i32, P(C.c_int32)]),
+        "cbv_pipeline_set_lens": (i32, [vp, P(LensStruct)]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

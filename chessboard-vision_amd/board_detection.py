@@ -47,14 +47,65 @@ def warp_perspective(img, M, dsize, rot180=False):
     return out
 
 
-def warp_image(img, points, display_size=(1280, 720), margin=100):
+def _lens_struct(lens):
+    return lens.struct() if lens is not None else N.LensStruct()
+
+
+def _lens_points(fn, points, lens):
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 2))
+    out = np.empty_like(p)
+    lib = N.load()
+    if getattr(lib, fn)(_lens_struct(lens), N.ptr(p), p.shape[0], N.ptr(out)) != 0:
+        raise ValueError(lib.cbv_last_error(None).decode())
+    return out
+
+
+def undistort_points(points, lens):
+    """Positions in the frame as the camera delivers it -> ideal (pinhole) positions, float64 [n, 2]: the fixed-point
+    iteration of cv2.undistortPoints(points, K, dist, P=K) with exactly 40 rounds (include/cbv.h,
+    cbv_lens_undistort_points).  `lens`: a stream.Lens.  Host only."""
+    return _lens_points("cbv_lens_undistort_points", points, lens)
+
+
+def distort_points(points, lens):
+    """Ideal positions -> where the delivered frame shows them, float64 [n, 2]: the forward model of the lens
+    (cbv_lens_distort_points).  Host only."""
+    return _lens_points("cbv_lens_distort_points", points, lens)
+
+
+def warp_lens(img, M, dsize, lens, profile=None, rot180=False, fmt="bgr"):
+    """warp_perspective_profiled through the camera's `lens` (a stream.Lens): the format's conversion, the profile, then the
+    warp whose coordinates go through the lens model, in one kernel with one interpolation per pixel (include/cbv.h,
+    cbv_warp_lens, cbv_warp_jpeg_lens).  `M` is the ideal-coordinate matrix.  lens=None is the lens-free call."""
+    c = N.context()
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    dw, dh = int(dsize[0]), int(dsize[1])
+    out = np.empty((dh, dw, 3), np.uint8)
+    if isinstance(fmt, str) and fmt.lower() == "mjpeg":
+        a = _jpeg_bytes(img)
+        st = C.c_int32(0)
+        c.check(c.lib.cbv_warp_jpeg_lens(c.h, N.ptr(a), a.size, N.ColorProfile.from_dict(profile), _lens_struct(lens), N.ptr(M), dw, dh,
+                                         1 if rot180 else 0, N.ptr(out), out.strides[0], C.byref(st)))
+        return out
+    raw, w, h, keep = N.raw_frame(img, fmt)
+    c.check(c.lib.cbv_warp_lens(c.h, raw, w, h, N.ColorProfile.from_dict(profile), _lens_struct(lens), N.ptr(M), dw, dh, 1 if rot180 else 0,
+                                N.ptr(out), out.strides[0]))
+    return out
+
+
+def warp_image(img, points, display_size=(1280, 720), margin=100, lens=None):
     """Top-down view of the board (board_detection.py:61-71).
-    Returns (warped, matrix, board_size)."""
+    Returns (warped, matrix, board_size).  With a `lens` (stream.Lens) the `points` are positions in the frame as delivered:
+    they are undistorted before getPerspectiveTransform, the matrix returned is the ideal-coordinate one, and the warp
+    corrects the distortion in its gather."""
     board_size = min(display_size) - margin
-    pts1 = np.float32(points)
+    pts1 = np.float32(points if lens is None else undistort_points(points, lens))
     pts2 = np.float32([[0, 0], [board_size, 0], [0, board_size], [board_size, board_size]])
     matrix = get_perspective_transform(pts1, pts2)
-    warped = warp_perspective(img, matrix, (board_size, board_size))
+    if lens is None:
+        warped = warp_perspective(img, matrix, (board_size, board_size))
+    else:
+        warped = warp_lens(img, matrix, (board_size, board_size), lens)
     return warped, matrix, board_size
 
 
@@ -75,14 +126,18 @@ def warp_jpeg(data, M, dsize, profile=None, rot180=False, out=None):
     return out, int(st.value)
 
 
-def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr"):
+def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr", lens=None):
     """warp_perspective(ImageEnhancer(profile).apply_color_profile(img), M, dsize, rot180), byte for byte, in one kernel: the
     profile is applied to the four source pixels each destination pixel blends (include/cbv.h, cbv_warp_color_profile).
     `profile`: a dict with the keys of color_profile.json, `None` / `{}` = no profile.
     `fmt` other than "bgr": `img` is a camera-native frame in the layout yuv_to_bgr / bayer_to_bgr take, and the result is
     that of the converted frame, with neither the BGR frame nor the profiled frame made (cbv_warp_color_profile_raw).
     `fmt` "mjpeg": `img` is one baseline JPEG stream (bytes or a uint8 array), and the result is that of jpeg_to_bgr's frame,
-    sampled from the decoded planes (cbv_warp_jpeg)."""
+    sampled from the decoded planes (cbv_warp_jpeg).
+    `lens` (a stream.Lens): the warp corrects the camera's lens distortion in its gather and `M` is the ideal-coordinate
+    matrix (warp_lens)."""
+    if lens is not None:
+        return warp_lens(img, M, dsize, lens, profile, rot180, fmt)
     c = N.context()
     if isinstance(fmt, str) and fmt.lower() == "mjpeg":
         return warp_jpeg(img, M, dsize, profile, rot180)[0]

@@ -552,6 +552,62 @@ extern "C" int cbv_warp_color_profile_raw(cbv_ctx* ctx, const cbv_raw_frame* raw
     return CBV_DONE(download(ctx, ctx->a.p, out, dw * 3, dh, out_stride));
 }
 
+// One frame of any format through the lens (include/cbv.h).  The staging buffer holds the frame, ctx->a the board, ctx->b the
+// call's profile table and, behind it, the launch's table of one entry.
+extern "C" int cbv_warp_lens(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, const cbv_color_profile* profile, const cbv_lens* lens,
+                             const double* M9, int dw, int dh, int rot180, uint8_t* out, int out_stride)
+{
+    const char* who = "cbv_warp_lens";
+    if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
+    if (!raw || !out || !M9 || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dw > 8192 || dh > 8192 || out_stride < dw * 3)
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
+    const bool bgr = raw->fmt == CBV_FMT_BGR;
+    if (bgr) RC(check_img(ctx, raw->plane0, w, h, raw->stride0, 3, who));
+    else RC(check_raw_format(ctx, raw->fmt, w, h, who));
+    const cbv_color_profile none = {};
+    const bool profiled = profile && profile->enabled;
+    if (!lens || !lens->enabled) { // the lens-free call of the format
+        if (!bgr) return cbv_warp_color_profile_raw(ctx, raw, w, h, profile ? profile : &none, M9, dw, dh, rot180, out, out_stride);
+        if (profiled) return cbv_warp_color_profile(ctx, raw->plane0, w, h, raw->stride0, profile, M9, dw, dh, rot180, out, out_stride);
+        return cbv_warp_perspective(ctx, raw->plane0, w, h, raw->stride0, M9, dw, dh, rot180, out, out_stride);
+    }
+    LensDev L;
+    RC(lens_checked(ctx, lens, &L, who));
+    ProfileTabs pt;
+    RC(profile_tabs_checked(ctx, profile ? profile : &none, &pt, who));
+    CBV_ENTER_DRAINED(ctx);
+    double Minv[9];
+    if (!host_invert3x3(M9, Minv)) memset(Minv, 0, sizeof(Minv));
+    const Geom g = tight_geom(w, h);
+    WarpSrc src;
+    const size_t o_tab = (sizeof(ProfileTabs) + 255) & ~(size_t)255;
+    RC(dev_ensure(ctx, &ctx->b, o_tab + sizeof(LensBoard)));
+    const ProfileTabs* dpt = profiled ? ctx->b.as<ProfileTabs>() : nullptr;
+    if (bgr) {
+        // only the rows the warp can sample cross PCIe, as in cbv_warp_perspective; with a lens the footprint is
+        // warp_footprint_lens's
+        PxRect fp;
+        int y0 = 0, y1 = h;
+        if (warp_footprint_lens(Minv, &L, dw, dh, w, h, &fp)) y0 = fp.y0, y1 = fp.y1;
+        RC(dev_ensure(ctx, &ctx->in, (size_t)w * 3 * h + 256));
+        if (ctx->debug_poison) CBV_HIP(ctx, hipMemsetAsync(ctx->in.p, 0xA5, (size_t)w * 3 * h, ctx->stream));
+        RC(rows_h2d(ctx, ctx->in.as<u8>() + (size_t)y0 * w * 3, raw->plane0 + (size_t)y0 * raw->stride0, raw->stride0, w * 3, y1 - y0));
+        src = profiled ? warp_src_profile(ctx->in.as<u8>(), g, dpt) : warp_src_bgr(ctx->in.as<u8>(), g, NormSrc());
+    } else {
+        RawPlanes dev;
+        RawGeom r;
+        RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, who)); // (the staging buffer keeps 256 bytes behind the last plane: the wide loads' slack)
+        src = profiled ? warp_src_raw_profile(dev, r, g, dpt) : warp_src_raw(dev, r, g);
+    }
+    RC(dev_ensure(ctx, &ctx->a, (size_t)dw * dh * 3 + 256));
+    const LensBoard T = lens_board(Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, dpt);
+    if (profiled) CBV_HIP(ctx, hipMemcpyAsync(ctx->b.p, &pt, sizeof(pt), hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipMemcpyAsync((u8*)ctx->b.p + o_tab, &T, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt and T are on this stack)
+    RC(launch_warp_lens(ctx, src, L, (const LensBoard*)((u8*)ctx->b.p + o_tab), 1, dw, dh, 0, 1, nullptr, nullptr));
+    return CBV_DONE(download(ctx, ctx->a.p, out, dw * 3, dh, out_stride));
+}
+
 extern "C" int cbv_noise_run(cbv_ctx* ctx, const uint64_t* changes, int n, cbv_noise_state* state, cbv_noise_result* out)
 {
     if (!ctx || !changes || !state || !out || n <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_noise_run: bad arguments");

@@ -9,6 +9,7 @@
 
 #include "../../include/cbv.h"
 #include "frame_plan.h"
+#include "lens_core.h"
 
 typedef uint8_t u8;
 typedef uint16_t u16;
@@ -756,6 +757,38 @@ int launch_warp_raw_profile_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, i
 int launch_warp_jpeg(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
                      int batch, u32* zero_word, u32* zero_word2);
 int launch_warp_jpeg_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
+// The warp through the camera's lens model (lens_core.h): k_warp_lens.hip, and k_warp_lens_profile.hip for the raw and JPEG
+// sources with a profile.  Every source kind has the table-driven form only: entry e of `tab` (device, ne entries) is one
+// destination of the launch, a board of a pipeline or a profile of a colour sweep, and a single-frame call passes a
+// table of one.  blockIdx.z = entry * nz + group of frames; the grid covers max_dw x max_dh.  Frame f of the launch goes
+// to dst + (s0 + f) * frame_stride.  A profiled source reads the entries' own tables (ptabs), never WarpSrc::ptabs, which
+// only says that the source is profiled.
+struct LensBoard {
+    double Minv[9];
+    int dw, dh, bw0, rot180;
+    u8* dst;
+    size_t frame_stride;
+    int stride, pad;
+    const ProfileTabs* ptabs;
+};
+static inline LensBoard lens_board(const double* Minv9, int dw, int dh, int rot180, u8* dst, int stride, size_t frame_stride, const ProfileTabs* ptabs)
+{
+    LensBoard T;
+    memset(&T, 0, sizeof(T));
+    memcpy(T.Minv, Minv9, sizeof(T.Minv));
+    int bh0;
+    warp_block_shape(dw, dh, &T.bw0, &bh0);
+    T.dw = dw, T.dh = dh, T.rot180 = rot180, T.dst = dst, T.stride = stride, T.frame_stride = frame_stride, T.ptabs = ptabs;
+    return T;
+}
+int launch_warp_lens(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
+                     u32* zero_word, u32* zero_word2);
+int launch_warp_lens_profile(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
+                             u32* zero_word, u32* zero_word2);
+// cbv_lens -> LensDev; CBV_ERR_ARG for a field that is not finite or a focal length that is not positive
+int lens_checked(cbv_ctx* ctx, const cbv_lens* lens, LensDev* out, const char* who);
+// warp_footprint through the lens: every border pixel of the destination through the full map, one more pixel of margin
+bool warp_footprint_lens(const double* Minv, const LensDev* lens, int dw, int dh, int w, int h, PxRect* out);
 int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);

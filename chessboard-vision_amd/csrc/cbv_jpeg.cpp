@@ -201,10 +201,10 @@ extern "C" int cbv_jpeg_decode(cbv_ctx* ctx, const uint8_t* data, size_t n, uint
 
 extern "C" size_t cbv_jpeg_plane_slot_bytes(int w, int h, int mode) { return jpeg_plane_slot_bytes(w, h, mode); }
 
-extern "C" int cbv_warp_jpeg(cbv_ctx* ctx, const uint8_t* data, size_t n, const cbv_color_profile* profile, const double* M9, int dw, int dh, int rot180,
-                             uint8_t* out, int out_stride, int32_t* status)
+// cbv_warp_jpeg, and with a lens cbv_warp_jpeg_lens: the lens's table of one entry lies behind the call's profile table
+static int warp_jpeg_call(cbv_ctx* ctx, const char* who, const uint8_t* data, size_t n, const cbv_color_profile* profile, const cbv_lens* lens,
+                          const double* M9, int dw, int dh, int rot180, uint8_t* out, int out_stride, int32_t* status)
 {
-    const char* who = "cbv_warp_jpeg";
     if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
     if (!data || !out || !M9 || !profile || !status || dw <= 0 || dh <= 0 || dw > 8192 || dh > 8192 || out_stride < dw * 3)
         return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
@@ -214,6 +214,8 @@ extern "C" int cbv_warp_jpeg(cbv_ctx* ctx, const uint8_t* data, size_t n, const 
     if (D.h > 65535) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "%s: %d rows", who, D.h);
     ProfileTabs pt;
     RC(profile_tabs_checked(ctx, profile, &pt, who));
+    LensDev L;
+    if (lens) RC(lens_checked(ctx, lens, &L, who));
     u32 S;
     int segments;
     RC(jpeg_piece_size(ctx, who, CBV_JPEG_ENTROPY_AUTO, 0, &S, &segments));
@@ -223,7 +225,8 @@ extern "C" int cbv_warp_jpeg(cbv_ctx* ctx, const uint8_t* data, size_t n, const 
     const Geom g = tight_geom(D.w, D.h);
     // the warped board in ctx->c, the call's tables behind it
     const size_t o_tabs = ((size_t)dw * dh * 3 + 255) & ~(size_t)255;
-    RC(dev_ensure(ctx, &ctx->c, o_tabs + sizeof(ProfileTabs) + 256));
+    const size_t o_lens = o_tabs + ((sizeof(ProfileTabs) + 255) & ~(size_t)255);
+    RC(dev_ensure(ctx, &ctx->c, o_lens + sizeof(LensBoard) + 256));
     JpegBatch B;
     RC(jpeg_single_dev(ctx, data, n, D, T, S, segments, nullptr, g, &B, nullptr, true)); // the decode stops at the planes
     const ProfileTabs* dpt = nullptr; // a disabled profile: the plain warp
@@ -232,11 +235,32 @@ extern "C" int cbv_warp_jpeg(cbv_ctx* ctx, const uint8_t* data, size_t n, const 
         CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt is on this stack)
         dpt = (const ProfileTabs*)((u8*)ctx->c.p + o_tabs);
     }
-    RC(launch_warp(ctx, warp_src_jpeg(B.planes, B.plane_stride, B.descs, g, dpt), Minv, dw, dh, rot180, (u8*)ctx->c.p, dw * 3, (size_t)dw * dh * 3, 1));
+    const WarpSrc src = warp_src_jpeg(B.planes, B.plane_stride, B.descs, g, dpt);
+    if (lens) {
+        const LensBoard T = lens_board(Minv, dw, dh, rot180, (u8*)ctx->c.p, dw * 3, (size_t)dw * dh * 3, dpt);
+        CBV_HIP(ctx, hipMemcpyAsync((u8*)ctx->c.p + o_lens, &T, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (T is on this stack)
+        RC(launch_warp_lens(ctx, src, L, (const LensBoard*)((u8*)ctx->c.p + o_lens), 1, dw, dh, 0, 1, nullptr, nullptr));
+    } else
+        RC(launch_warp(ctx, src, Minv, dw, dh, rot180, (u8*)ctx->c.p, dw * 3, (size_t)dw * dh * 3, 1));
     int st = 0;
     CBV_HIP(ctx, hipMemcpyAsync(&st, B.status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     CBV_HIP(ctx, hipMemcpy2DAsync(out, out_stride, ctx->c.p, (size_t)dw * 3, (size_t)dw * 3, dh, hipMemcpyDeviceToHost, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *status = st;
     return CBV_DONE(CBV_OK);
+}
+
+extern "C" int cbv_warp_jpeg(cbv_ctx* ctx, const uint8_t* data, size_t n, const cbv_color_profile* profile, const double* M9, int dw, int dh, int rot180,
+                             uint8_t* out, int out_stride, int32_t* status)
+{
+    return warp_jpeg_call(ctx, "cbv_warp_jpeg", data, n, profile, nullptr, M9, dw, dh, rot180, out, out_stride, status);
+}
+
+extern "C" int cbv_warp_jpeg_lens(cbv_ctx* ctx, const uint8_t* data, size_t n, const cbv_color_profile* profile, const cbv_lens* lens, const double* M9,
+                                  int dw, int dh, int rot180, uint8_t* out, int out_stride, int32_t* status)
+{
+    const cbv_color_profile none = {};
+    return warp_jpeg_call(ctx, "cbv_warp_jpeg_lens", data, n, profile ? profile : &none, lens && lens->enabled ? lens : nullptr, M9, dw, dh, rot180, out,
+                          out_stride, status);
 }

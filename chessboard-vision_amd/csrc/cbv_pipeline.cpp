@@ -176,6 +176,16 @@ int pipeline_tables(Pipe& P)
         P.max_px = std::max(P.max_px, q.max_px);
         P.max_S = std::max(P.max_S, q.cfg.board_size);
     }
+    if (P.lens_on) { // the lens kernels' table: the warp's part of every board, a single one included
+        std::vector<LensBoard> lt((size_t)nb);
+        for (int k = 0; k < nb; k++) {
+            const BoardDev& T = P.tab[k];
+            lt[k] = lens_board(T.Minv, T.S, T.S, T.rot180, T.warped, T.S * 3, T.warped_stride, T.ptabs);
+        }
+        RC(dev_ensure(ctx, &P.d_lens_tab, sizeof(LensBoard) * nb));
+        CBV_HIP(ctx, hipMemcpyAsync(P.d_lens_tab.p, lt.data(), sizeof(LensBoard) * nb, hipMemcpyHostToDevice, ctx->stream));
+        CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (lt is on this stack)
+    }
     if (nb == 1) return CBV_OK;
     RC(dev_ensure(ctx, &P.d_boards, sizeof(BoardDev) * nb));
     CBV_HIP(ctx, hipMemcpyAsync(P.d_boards.p, P.tab.data(), sizeof(BoardDev) * nb, hipMemcpyHostToDevice, ctx->stream));
@@ -194,7 +204,7 @@ int pipeline_update_region(Pipe& P)
     for (size_t k = 0; use && k < P.boards.size(); k++) {
         const Board& q = P.boards[k]->b;
         PxRect r;
-        use = warp_footprint(q.Minv, q.cfg.board_size, q.cfg.board_size, P.w, P.h, &r);
+        use = warp_footprint_lens(q.Minv, P.lens_ptr(), q.cfg.board_size, q.cfg.board_size, P.w, P.h, &r);
         if (use) u = k == 0 ? r : PxRect{std::min(u.x0, r.x0), std::min(u.y0, r.y0), std::max(u.x1, r.x1), std::max(u.y1, r.y1)};
     }
     if (use)
@@ -380,6 +390,7 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     if (P->enhanced) (void)hipFree(P->enhanced);
     dev_free(&P->d_synth);
     dev_free(&P->d_boards);
+    dev_free(&P->d_lens_tab);
     for (cbv_pipeline* q : P->boards) board_free(q); // board 0 (p) included
     delete P;
 }
@@ -597,6 +608,26 @@ extern "C" int cbv_pipeline_set_profile(cbv_pipeline* p, const cbv_color_profile
     RC(join_scan(P)); // the runs in flight read the table that is replaced here
     RC(board_set_profile(P, p->b, profile, who));
     return pipeline_tables(P); // (whether any board has an enabled profile decides the warp's kernel)
+}
+
+extern "C" int cbv_pipeline_set_lens(cbv_pipeline* p, const cbv_lens* lens)
+{
+    const char* who = "cbv_pipeline_set_lens";
+    if (!p) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: the pipeline is null", who);
+    Pipe& P = *p->pipe;
+    cbv_ctx* ctx = P.ctx;
+    if (attached(p)) return cbv_fail(ctx, CBV_ERR_STATE, "%s: the lens is the camera's: it goes to the parent of a board", who);
+    const bool on = lens && lens->enabled;
+    LensDev L = {};
+    if (on) RC(lens_checked(ctx, lens, &L, who)); // a rejected lens changes nothing
+    CBV_ENTER(ctx);
+    RC(join_scan(P)); // the runs in flight keep their table and their region; what comes next is ordered behind them
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    P.lens_on = on;
+    P.lens = L;
+    if (!P.configured) return CBV_OK;
+    RC(pipeline_update_region(P)); // enhance_region's footprint follows the lens
+    return pipeline_tables(P);
 }
 
 extern "C" int cbv_pipeline_set_change_blur(cbv_pipeline* p, int blur_kernel)

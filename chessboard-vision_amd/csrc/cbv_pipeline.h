@@ -143,6 +143,12 @@ struct Pipe {
     std::vector<cbv_pipeline*> boards;
     std::vector<BoardDev> tab;
     DevBuf d_boards;
+    // the camera's lens (cbv_pipeline_set_lens), shared by every board: with it on, every warp of a board goes through
+    // launch_warp_lens with d_lens_tab, one LensBoard per board (pipeline_tables), whatever the number of boards
+    bool lens_on = false;
+    LensDev lens = {};
+    DevBuf d_lens_tab;
+    const LensDev* lens_ptr() const { return lens_on ? &lens : nullptr; }
     bool any_hough = false;
     bool any_adaptive = false; // some board's model follows the frames: k_model_scan runs in front of the temporal scan
     bool any_session = false;  // some board runs a game session: the boards' scans are launched board by board

@@ -16,10 +16,12 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     const WarpSrc src = !res ? pipeline_raw_warp_src(P, s0, pt)
                         : pt ? warp_src_profile(res, P.g, pt)
                              : warp_src_bgr(res, P.g, norm);
-    if (P.boards.size() > 1) {
+    // the camera's lens: one launch of the lens kernels for every board, from the lens table, in place of either warp below
+    const int nb = (int)P.boards.size();
+    if (P.lens_on) RC(launch_warp_lens(ctx, src, P.lens, (const LensBoard*)P.d_lens_tab.p, nb, P.max_S, P.max_S, s0, b, work, retry0));
+    if (nb > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
-        const int nb = (int)P.boards.size();
-        RC(launch_warp_mb(ctx, src, tab, nb, P.max_S, s0, b, work, retry0));
+        if (!P.lens_on) RC(launch_warp_mb(ctx, src, tab, nb, P.max_S, s0, b, work, retry0));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
         if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, s0, b, P.max_px));
         if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, P.hough_lds[0], retry, retry_base, 0));
@@ -30,7 +32,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     u8* gray = T.gray + T.plane_total * s0;
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
     cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
-    RC(launch_warp(ctx, src, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
+    if (!P.lens_on) RC(launch_warp(ctx, src, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
     RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
                                  T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));
     if (P.any_own_blur)

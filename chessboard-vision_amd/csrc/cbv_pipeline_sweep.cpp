@@ -11,12 +11,13 @@ struct SweepCall {
     DevBuf planes, kbeg;      // ChangeDetector sweep
     DevBuf choices, expected; // PieceDetector sweep
     DevBuf tabs, boards, gray, stats; // colour profile sweep (four stages: ev[0..4], ms[0..3])
+    DevBuf lens_tab;                  // ... with the pipeline's lens on: a LensBoard per profile of the chunk
     u8* h_rec = nullptr; // pinned staging of a chunk's records
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float ms[4] = {0.f, 0.f, 0.f, 0.f};
     ~SweepCall()
     {
-        for (DevBuf* b : {&sets, &hist, &rec, &sums, &planes, &kbeg, &choices, &expected, &tabs, &boards, &gray, &stats}) dev_free(b);
+        for (DevBuf* b : {&sets, &hist, &rec, &sums, &planes, &kbeg, &choices, &expected, &tabs, &boards, &gray, &stats, &lens_tab}) dev_free(b);
         if (h_rec) (void)hipHostFree(h_rec);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -419,7 +420,15 @@ extern "C" int cbv_pipeline_color_sweep(cbv_pipeline* p, int slot0, int count, c
             const ProfileTabs* pt = (const ProfileTabs*)S.tabs.p;
             const WarpSrc src = P.plan.raw() ? pipeline_raw_warp_src(P, slot0 + c0, pt, pc, B.warped_stride * cf)
                                              : warp_src_profile(P.frames + P.g.frame_stride * (slot0 + c0), P.g, pt, pc, B.warped_stride * cf);
-            RC(launch_warp(ctx, src, B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p, S_ * 3, B.warped_stride, cf));
+            if (P.lens_on) { // the lens kernels are table-driven: profile i of the chunk is entry i, its frames where launch_warp puts them
+                std::vector<LensBoard> lt((size_t)pc);
+                for (int i = 0; i < pc; i++)
+                    lt[(size_t)i] = lens_board(B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p + B.warped_stride * cf * i, S_ * 3, B.warped_stride, pt + i);
+                RC(dev_ensure(ctx, &S.lens_tab, sizeof(LensBoard) * pchunk));
+                CBV_HIP(ctx, hipMemcpy(S.lens_tab.p, lt.data(), sizeof(LensBoard) * pc, hipMemcpyHostToDevice)); // (the stream is idle: sweep_chunk_end)
+                RC(launch_warp_lens(ctx, src, P.lens, (const LensBoard*)S.lens_tab.p, pc, S_, S_, 0, cf, nullptr, nullptr));
+            } else
+                RC(launch_warp(ctx, src, B.Minv, S_, S_, B.cfg.rot180, (u8*)S.boards.p, S_ * 3, B.warped_stride, cf));
             CBV_HIP(ctx, hipEventRecord(S.ev[1], ctx->stream));
             RC(launch_squares_pre5_stats(ctx, (const u8*)S.boards.p, B.warped_stride, descs, n, (u8*)S.gray.p, B.plane_total, nullptr, nullptr,
                                          (const u8*)B.d_masks.p, (float)B.cfg.z_threshold, (cbv_sq_stats*)S.stats.p, nb, nullptr, 0, nullptr, nullptr,

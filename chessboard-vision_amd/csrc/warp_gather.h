@@ -1,10 +1,12 @@
 // The warp's one gather (warp_gather), its sources and what the launchers share, for the translation units that hold
-// warp kernels: k_warp.hip, k_warp_raw_profile.hip and k_warp_jpeg.hip.  Private.
+// warp kernels: k_warp.hip, k_warp_raw_profile.hip, k_warp_jpeg.hip and the lens forms' k_warp_lens.hip and
+// k_warp_lens_profile.hip.  Private.
 #pragma once
 #include "cbv_bayer.h"
 #include "cbv_profile_px.h"
 #include "cbv_yuv.h"
 #include "jpeg_core.h"
+#include "lens_core.h"
 
 struct WarpM {
     double m[9];
@@ -19,22 +21,28 @@ struct WarpTaps {
     size_t out_off; // byte offset of the pixel inside a destination frame
 };
 
-// destination pixel (dx, dy) of a dw x dh destination; sw x sh = the source frame
+// destination pixel (dx, dy) of a dw x dh destination; sw x sh = the source frame.  LENS: the ideal position goes through
+// the camera's lens model (lens_core.h, *lens) before it is quantised: one more step in the coordinate, the same taps after it
+template <bool LENS = false>
 __device__ __forceinline__ WarpTaps warp_taps(int dx, int dy, int sw, int sh, const double* __restrict__ M, int dw, int dh, int bw0, int rot180,
-                                              int dst_stride)
+                                              int dst_stride, const LensDev* lens = nullptr)
 {
     WarpTaps t;
     const int bx = (dx / bw0) * bw0, x1 = dx - bx; // block origin and offset inside it
     // (rows are evaluated independently of the block row)
-    const double X0 = M[0] * bx + M[1] * dy + M[2];
-    const double Y0 = M[3] * bx + M[4] * dy + M[5];
-    const double W0 = M[6] * bx + M[7] * dy + M[8];
-    double W = W0 + M[6] * x1;
-    W = W != 0. ? 32. / W : 0.;
-    double fX = (X0 + M[0] * x1) * W;
-    double fY = (Y0 + M[3] * x1) * W;
-    fX = fmax(-2147483648.0, fmin(2147483647.0, fX));
-    fY = fmax(-2147483648.0, fmin(2147483647.0, fY));
+    double fX, fY;
+    if constexpr (LENS) lens_warp_xy32(*lens, M, bx, x1, dy, &fX, &fY);
+    else {
+        const double X0 = M[0] * bx + M[1] * dy + M[2];
+        const double Y0 = M[3] * bx + M[4] * dy + M[5];
+        const double W0 = M[6] * bx + M[7] * dy + M[8];
+        double W = W0 + M[6] * x1;
+        W = W != 0. ? 32. / W : 0.;
+        fX = (X0 + M[0] * x1) * W;
+        fY = (Y0 + M[3] * x1) * W;
+        fX = fmax(-2147483648.0, fmin(2147483647.0, fX));
+        fY = fmax(-2147483648.0, fmin(2147483647.0, fY));
+    }
     const int X = d_round_d(fX), Y = d_round_d(fY);
     const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
     const int fx = X & 31, fy = Y & 31;
@@ -323,8 +331,9 @@ __device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride,
 // max(((sy + 1) >> 1) - 1, 0) for 4:2:0 and are clamped to the component's last row, which only moves rows no tap reads.  So
 // 4 loads (gray: 2), 6 (4:4:4, 4:2:2) or 8 (4:2:0) per frame.  The planes are whole MCUs, and the bytes a load reads past
 // the window belong to the next row, plane or slot: callers keep >= 4 readable bytes behind the last frame's planes.
-template <class Src, int FPT>
-__device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz)
+template <class Src, int FPT, bool LENS = false>
+__device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz,
+                                            const LensDev* lens = nullptr)
 {
     constexpr int KIND = Src::KIND, FMT = Src::FMT;
     constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV, JPEG = KIND == WARP_JPEG;
@@ -378,7 +387,7 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
     int dy = blockIdx.y * Src::ROWS + (threadIdx.x >> 6), row = 0;
     if (dx >= D.dw || dy >= D.dh) return;
     do {
-        const WarpTaps t = warp_taps(dx, dy, S.w(), S.h(), D.M, D.dw, D.dh, D.bw0, D.rot180, D.stride);
+        const WarpTaps t = warp_taps<LENS>(dx, dy, S.w(), S.h(), D.M, D.dw, D.dh, D.bw0, D.rot180, D.stride, lens);
         // ---- the offsets of the loads (only used where the taps are inside) and the wide loads of every frame, which are
         // all issued before the first is used: the gather is bound by the number of memory instructions, not by bytes
         bool fast = t.interior;
@@ -678,19 +687,25 @@ static void warp_dispatch(int fmt, int batch, F&& launch)
 // What both launchers do around their kernels: the refusals of the source (raw planes: what launch_ingest asks of them; YV12
 // leaves as YUV420P), the groups of frames, the grid of a dw x dh destination with nz * zmul layers, the profiling bracket.
 // launch(fmt, fpt, grid, nz) issues the kernel of the source's kind; `many` = the frames per thread of its many-frames form.
+// the refusals of a raw source (what launch_ingest asks of the planes), and YV12 made YUV420P; other sources pass
+static int warp_raw_checked(cbv_ctx* ctx, WarpSrc* s, int batch)
+{
+    if (!s->raw()) return CBV_OK;
+    const char* what = s->kind == WarpSrc::BAYER ? "launch_warp_bayer" : "launch_warp_yuv";
+    RC(check_raw_format(ctx, s->r.fmt, s->g.w, s->g.h, what));
+    // (warp_src_raw takes the kind from the format: only a WarpSrc filled by hand can fail this)
+    if (s->kind == WarpSrc::BAYER && !raw_fmt_bayer(s->r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a Bayer format", what, s->r.fmt);
+    if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes or strides", what);
+    const int strides[3] = {s->r.stride0, s->r.stride1, s->r.stride2};
+    RC(check_raw_planes(ctx, s->r.fmt, s->g.w, s->planes.p, strides, what));
+    raw_planes_canonical(&s->planes, &s->r);
+    return CBV_OK;
+}
+
 template <class F>
 static int warp_launch(cbv_ctx* ctx, WarpSrc* s, int dw, int dh, int zmul, int batch, F&& launch, int many = 4)
 {
-    if (s->raw()) {
-        const char* what = s->kind == WarpSrc::BAYER ? "launch_warp_bayer" : "launch_warp_yuv";
-        RC(check_raw_format(ctx, s->r.fmt, s->g.w, s->g.h, what));
-        // (warp_src_raw takes the kind from the format: only a WarpSrc filled by hand can fail this)
-        if (s->kind == WarpSrc::BAYER && !raw_fmt_bayer(s->r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a Bayer format", what, s->r.fmt);
-        if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes or strides", what);
-        const int strides[3] = {s->r.stride0, s->r.stride1, s->r.stride2};
-        RC(check_raw_planes(ctx, s->r.fmt, s->g.w, s->planes.p, strides, what));
-        raw_planes_canonical(&s->planes, &s->r);
-    }
+    RC(warp_raw_checked(ctx, s, batch));
     const int nz = warp_groups(batch, many), rows = s->profiled() ? WP_ROWS : 4;
     const dim3 grid((dw + 63) / 64, (dh + rows - 1) / rows, nz * zmul);
     const int prof = s->raw() ? CBV_K_WARP_YUV : CBV_K_WARP;

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _native as N
 from . import synth as S
-from .board_detection import get_perspective_transform
+from .board_detection import get_perspective_transform, undistort_points
 from .grid_extractor import GridExtractor, SmartGridExtractor
 
 
@@ -216,6 +216,81 @@ def load_color_profile(path="color_profile.json"):
         return json.load(f)
 
 
+class Lens:
+    """The camera's lens as cv2.calibrateCamera describes it: the camera matrix (fx, fy, cx, cy) and OpenCV's first five
+    distortion coefficients (k1, k2, p1, p2, k3), include/cbv.h's cbv_lens.  The warp corrects the distortion in its gather
+    (`BoardPipeline.configure(lens=...)`, `set_lens`, `board_detection.warp_image(lens=...)`): one interpolation per pixel,
+    for every frame format.  Estimating the coefficients is cv2's business; this class consumes them."""
+    FIELDS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+
+    def __init__(self, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+        self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+        self.k1, self.k2, self.p1, self.p2, self.k3 = float(k1), float(k2), float(p1), float(p2), float(k3)
+
+    @classmethod
+    def from_opencv(cls, camera_matrix, dist_coeffs):
+        """From the 3 x 3 camera_matrix and the dist_coeffs (4 or 5 of them: k1, k2, p1, p2[, k3]) of cv2.calibrateCamera.
+        Longer vectors are taken when everything beyond the fifth coefficient is zero; the rational, thin-prism and tilt
+        terms are not modelled (ValueError)."""
+        K = np.asarray(camera_matrix, dtype=np.float64).reshape(3, 3)
+        d = np.asarray(dist_coeffs, dtype=np.float64).reshape(-1)
+        if d.size < 4:
+            raise ValueError("dist_coeffs: 4 or 5 coefficients (k1, k2, p1, p2[, k3]), got %d" % d.size)
+        if np.any(d[5:] != 0):
+            raise ValueError("dist_coeffs beyond k3 are not zero: the rational and thin-prism terms are not modelled")
+        return cls(K[0, 0], K[1, 1], K[0, 2], K[1, 2], d[0], d[1], d[2], d[3], d[4] if d.size > 4 else 0.0)
+
+    def scaled(self, from_size, to_size):
+        """The same lens for frames of another resolution: from_size, to_size = (w, h).  fx, cx scale with the width and
+        fy, cy with the height; the coefficients act on normalised coordinates and stay."""
+        sx, sy = float(to_size[0]) / float(from_size[0]), float(to_size[1]) / float(from_size[1])
+        return Lens(self.fx * sx, self.fy * sy, self.cx * sx, self.cy * sy, self.k1, self.k2, self.p1, self.p2, self.k3)
+
+    @property
+    def camera_matrix(self):
+        return np.array([[self.fx, 0.0, self.cx], [0.0, self.fy, self.cy], [0.0, 0.0, 1.0]])
+
+    @property
+    def dist_coeffs(self):
+        return np.array([self.k1, self.k2, self.p1, self.p2, self.k3])
+
+    def struct(self):
+        """The cbv_lens of this lens, enabled."""
+        return N.LensStruct(1, 0, *(getattr(self, k) for k in self.FIELDS))
+
+    def __eq__(self, other):
+        return isinstance(other, Lens) and all(getattr(self, k) == getattr(other, k) for k in self.FIELDS)
+
+    def __repr__(self):
+        return "Lens(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.FIELDS)
+
+
+def lens_struct(lens):
+    """The cbv_lens of a Lens; None is the disabled one."""
+    return lens.struct() if lens is not None else N.LensStruct()
+
+
+def save_lens(path, lens, image_size=None):
+    """Write a lens as JSON: camera_matrix (3 x 3), dist_coeffs (5) and, when given, image_size = [w, h], the resolution
+    the calibration was made at (`Lens.scaled` takes it from there to another).  Returns what was written."""
+    data = {"camera_matrix": lens.camera_matrix.tolist(), "dist_coeffs": lens.dist_coeffs.tolist()}
+    if image_size is not None:
+        data["image_size"] = [int(image_size[0]), int(image_size[1])]
+    with open(path, "w") as f:
+        json.dump(data, f, indent=4)
+    return data
+
+
+def load_lens(path, with_size=False):
+    """The Lens of a JSON file with camera_matrix and dist_coeffs (`save_lens`, or the two arrays cv2.calibrateCamera
+    returned, dumped as lists).  with_size=True: (lens, image_size or None)."""
+    with open(path) as f:
+        data = json.load(f)
+    lens = Lens.from_opencv(data["camera_matrix"], data["dist_coeffs"])
+    size = tuple(int(v) for v in data["image_size"]) if data.get("image_size") is not None else None
+    return (lens, size) if with_size else lens
+
+
 class SweepResult:
     """What `sensitivity_sweep` returns.  `settings`: [S] structured array (z_threshold, initial_variance, blur_kernel as
     given).  With records: `changed`, `parcial`, `total` (uint64 square sets, bit i = roi i), `z_max`, `n_changed`,
@@ -248,9 +323,13 @@ def classify_hand_bits(changed, total, rois_rc):
 
 
 def _fill_board(cfg, points, grid_lines, rot180, display_size, margin, history_size, min_presence, change_threshold,
-                z_threshold, initial_variance, use_hough, min_radius_ratio, max_radius_ratio, hough_param1, hough_param2):
-    """The per-board fields of a PipelineConfig or BoardConfig: geometry, square table and detector settings."""
+                z_threshold, initial_variance, use_hough, min_radius_ratio, max_radius_ratio, hough_param1, hough_param2, lens=None):
+    """The per-board fields of a PipelineConfig or BoardConfig: geometry, square table and detector settings.  With a
+    `lens` the points are positions in the frame as delivered: they are undistorted first, and the matrix is the
+    ideal-coordinate one."""
     S_ = min(display_size) - margin
+    if lens is not None:
+        points = undistort_points(points, lens)
     M = get_perspective_transform(np.float32(points), np.float32([[0, 0], [S_, 0], [0, S_], [S_, S_]]))
     for i in range(9):
         cfg.M[i] = float(M.reshape(9)[i])
@@ -641,6 +720,14 @@ class BoardPipeline(_BoardMethods):
         self.board_size = 0
         self._boards = []
         self.input_format = "bgr"
+        self.lens = None
+
+    def set_lens(self, lens):
+        """The camera's lens (a `Lens`; None turns it off), shared by every board of the pipeline: every warp goes through
+        it from the next run on (include/cbv.h, cbv_pipeline_set_lens).  The boards' matrices stay as they are: with a lens
+        they are expected in ideal coordinates, which `configure(points, lens=...)` and `add_board` see to."""
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_lens(self.h_, lens_struct(lens)))
+        self.lens = lens
 
     def close(self):
         if self.h_:
@@ -662,8 +749,10 @@ class BoardPipeline(_BoardMethods):
                   z_threshold=_D["z_threshold"], initial_variance=_D["initial_variance"], use_hough=_D["use_hough"],
                   min_radius_ratio=_D["min_radius_ratio"], max_radius_ratio=_D["max_radius_ratio"],
                   hough_param1=_D["hough_param1"], hough_param2=_D["hough_param2"], enhance_region=False, enhance=True,
-                  blur_kernel=5, raw=False):
-        """`use_hough` and the radii mirror PieceDetector's attributes (piece_detector.py:33-35,222-230);
+                  blur_kernel=5, raw=False, lens=None):
+        """`lens` (a `Lens`, or None for a pinhole camera): the camera's lens distortion is corrected inside the warp of
+        every board of this pipeline (`set_lens`), and `points` are the corners as clicked in the frame as delivered.
+        `use_hough` and the radii mirror PieceDetector's attributes (piece_detector.py:33-35,222-230);
         pass min_radius / 100 and max_radius / 100 of piece_detector_settings.json as the application does.
         `enhance_region` (only without keep_enhanced): enhance the part of each frame the warp samples first and the rest
         only when normalize's global min / max could depend on it; every output stays identical (include/cbv.h).
@@ -694,7 +783,7 @@ class BoardPipeline(_BoardMethods):
             e.sharpen_kernel[i] = float(k[i])
         S_, M, rois_rc = _fill_board(cfg, points, grid_lines, rot180, display_size, margin, history_size, min_presence,
                                      change_threshold, z_threshold, initial_variance, use_hough, min_radius_ratio,
-                                     max_radius_ratio, hough_param1, hough_param2)
+                                     max_radius_ratio, hough_param1, hough_param2, lens=lens)
         cfg.chunk, cfg.lanes, cfg.keep_enhanced = chunk, lanes, 1 if keep_enhanced else 0
         cfg.enhance_region = 1 if enhance_region else 0
         if isinstance(enhance, str) and enhance != "profile":
@@ -702,6 +791,8 @@ class BoardPipeline(_BoardMethods):
         if raw and enhance != "profile":
             raise ValueError("raw=True goes with enhance=\"profile\" (enhance=False samples raw frames as it is), got enhance=%r" % (enhance,))
         cfg.skip_enhance = (N.SKIP_ENHANCE_PROFILE_RAW if raw else N.SKIP_ENHANCE_PROFILE) if enhance == "profile" else (0 if enhance else 1)
+        if lens is not None or getattr(self, "lens", None) is not None:  # (a caller without a lens makes the calls it always made)
+            self.set_lens(lens)
         self.ctx.check(self.ctx.lib.cbv_pipeline_configure(self.h_, cfg))
         self.rois_rc = rois_rc
         self.board_size = S_
@@ -884,8 +975,9 @@ class Board(_BoardMethods):
         unknown = set(detector) - set(DETECTOR_DEFAULTS)
         if unknown:
             raise TypeError("add_board: unknown detector keyword(s) %s" % ", ".join(sorted(unknown)))
+        # (the points are seen through the pipeline's lens, the camera's)
         self.board_size, self.matrix, self.rois_rc = _fill_board(cfg, points, grid_lines, rot180, display_size, margin,
-                                                                 **dict(DETECTOR_DEFAULTS, **detector))
+                                                                 lens=getattr(pipeline, "lens", None), **dict(DETECTOR_DEFAULTS, **detector))
         hdl = C.c_void_p()
         self.ctx.check(self.ctx.lib.cbv_pipeline_add_board(pipeline.h_, cfg, C.byref(hdl)))
         self.h_ = hdl

@@ -1192,6 +1192,64 @@ CBV_API int cbv_pipeline_color_sweep(cbv_pipeline* board, int slot0, int count, 
                                      const uint64_t* expected, int chunk_frames, cbv_piece_sweep_record* records,
                                      cbv_piece_sweep_summary* summary, cbv_color_sweep_info* info);
 
+/* ---------------------------------------------------------------------------
+ * Lens distortion corrected in the warp's gather
+ * ---------------------------------------------------------------------------
+ * OpenCV's five-coefficient Brown-Conrady model: the camera_matrix (fx, fy, cx, cy) and dist_coeffs (k1, k2, p1, p2, k3)
+ * that cv2.calibrateCamera writes.  The new camera matrix equals the camera matrix and there is no rectification.  The
+ * homography of a warp then lives in IDEAL (pinhole) pixel coordinates, and the lens says where the delivered frame shows
+ * an ideal position.  A destination pixel (dx, dy) gets its ideal position as the lens-free warp computes it, in the
+ * block-origin form: bx = (dx / bw0) * bw0, x1 = dx - bx, X0, Y0, W0 evaluated at (bx, dy), W = W0 + M[6] * x1 (M = the
+ * inverse of the matrix passed).  Then, in float64, every operation rounded once and never fused, in this order:
+ *     Wi = W != 0 ? 1.0 / W : 0.0
+ *     u  = (X0 + M[0]*x1) * Wi          v  = (Y0 + M[3]*x1) * Wi
+ *     x  = (u - cx) / fx                y  = (v - cy) / fy
+ *     r2 = x*x + y*y
+ *     kr = 1.0 + ((k3*r2 + k2)*r2 + k1)*r2
+ *     xy2 = 2.0*x*y
+ *     xd = x*kr + p1*xy2 + p2*(r2 + 2.0*x*x)
+ *     yd = y*kr + p1*(r2 + 2.0*y*y) + p2*xy2
+ *     fX = (xd*fx + cx) * 32.0          fY = (yd*fy + cy) * 32.0
+ * and from there the warp's own step: clamp to the int32 range, round to nearest even, split into sx, sy and the 1/32
+ * fractions, four taps (BGR 0 for a tap outside the frame), the 15-bit fixed-point blend, the optional rotation by 180
+ * degrees.  One interpolation per pixel, for every source format.  If fX or fY is not a number, both become the lowest
+ * int32: the pixel lies outside the frame, reads nothing and is 0.  An infinite coordinate is clamped and is outside too.
+ * In exact arithmetic this is cv2.remap(frame, map, INTER_LINEAR, BORDER_CONSTANT 0) with the map of
+ * cv2.initUndistortRectifyMap(K, dist, I, K) composed with the inverse homography; it is not pinned against a cv2 build,
+ * which keeps its maps in float32.
+ * enabled = 0 (or a null lens) is the lens-free warp, bit for bit.  A lens whose coefficients are all zero is NOT promised
+ * to equal the lens-free warp: ((u - cx) / fx) * fx + cx rounds differently from u.
+ * Refused with CBV_ERR_ARG and nothing changed: a field that is not finite, fx <= 0 or fy <= 0. */
+typedef struct { int32_t enabled, pad; double fx, fy, cx, cy, k1, k2, p1, p2, k3; } cbv_lens;
+/* The forward model on n points (x, y pairs): ideal pixel positions -> positions in the frame as delivered.  Host only. */
+CBV_API int cbv_lens_distort_points(const cbv_lens* lens, const double* xy_in, int n, double* xy_out);
+/* The inverse, for the corner points a person clicks in the delivered frame: cv2.undistortPoints' fixed-point iteration,
+ * start at x = xd, exactly 40 rounds of x = (xd - tangential(x, y)) / kr(x, y) (the same for y), back with * fx + cx.  The
+ * count is fixed: the result is a function of the input alone.  Host only.  Both ignore `enabled`. */
+CBV_API int cbv_lens_undistort_points(const cbv_lens* lens, const double* xy_in, int n, double* xy_out);
+/* The host twin of the kernels' coordinates: XY[dh][dw][2] = the rounded 1/32-px X, Y of every destination pixel of a
+ * dw x dh warp with the inverse homography M9 (NOT inverted here), before the split into sx, sy and the fractions. */
+CBV_API int cbv_lens_warp_coords(const cbv_lens* lens, const double* M9, int dw, int dh, int32_t* XY);
+/* The source pixels a dw x dh warp can sample in a w x h frame, [x0, x1) x [y0, y1): every border pixel of the destination
+ * through the full map, the bounding box with 4 pixels of margin, clipped.  Returns 1 with rect4 filled, 0 when there is no
+ * usable footprint (callers take the whole frame).  lens may be null: the four corners, 3 pixels. */
+CBV_API int cbv_lens_warp_footprint(const cbv_lens* lens, const double* Minv9, int dw, int dh, int w, int h, int32_t* rect4);
+/* One frame through the lens, host in, host out: raw->fmt = any CBV_FMT_*, CBV_FMT_BGR included (plane0 / stride0 = the
+ * BGR rows); profile may be null; = the format's conversion, then cbv_apply_color_profile when the profile is enabled,
+ * then the warp defined above on that frame, byte for byte, in one kernel.  M9 is the matrix as cbv_warp_perspective takes
+ * it (board <- ideal frame).  A null or disabled lens is the lens-free call of the format. */
+CBV_API int cbv_warp_lens(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, const cbv_color_profile* profile, const cbv_lens* lens,
+                          const double* M9, int dw, int dh, int rot180, uint8_t* out, int out_stride);
+/* ... and one Motion-JPEG frame, as cbv_warp_jpeg takes it */
+CBV_API int cbv_warp_jpeg_lens(cbv_ctx* ctx, const uint8_t* data, size_t n, const cbv_color_profile* profile, const cbv_lens* lens, const double* M9,
+                               int dw, int dh, int rot180, uint8_t* out, int out_stride, int32_t* status);
+/* The camera's lens of a pipeline, shared by every board: every warp of a board of the pipeline goes through it
+ * (cbv_pipeline_run in all modes, the colour sweep's scratch warps), and enhance_region's footprint follows it.  The
+ * pipeline's own handle only: a board's handle is CBV_ERR_STATE.  Allowed between runs, waits for the runs in flight.  Null
+ * or enabled = 0 turns it off.  The boards' matrices are then ideal-coordinate ones (cbv_lens_undistort_points on the
+ * clicked corners before cbv_get_perspective_transform). */
+CBV_API int cbv_pipeline_set_lens(cbv_pipeline* p, const cbv_lens* lens);
+
 #ifdef __cplusplus
 }
 #endif
