@@ -288,6 +288,26 @@ FMT_BAYER_RGGB, FMT_BAYER_BGGR, FMT_BAYER_GRBG, FMT_BAYER_GBRG = 0x04, 0x14, 0x2
 BAYER_FORMATS = {"bayer_rggb": FMT_BAYER_RGGB, "bayer_bggr": FMT_BAYER_BGGR, "bayer_grbg": FMT_BAYER_GRBG,
                  "bayer_gbrg": FMT_BAYER_GBRG}                 # ring slots [h, w]
 
+# The colour space of a YUV frame travels in its format id (include/cbv.h): CBV_CS_* bits OR-ed onto a YUV id.  "bt601" is
+# cv2.cvtColor's BT.601 limited range, the default and all there was; "bt601-full" is JFIF (phone cameras, full-range UVC
+# modes), "bt709" decoded video at 720p and above, "bt709-full" capture cards in PC range.
+CS_FULL, CS_BT709, CS_MASK = 0x400, 0x800, 0xC00
+COLORSPACES = {"bt601": 0, "bt601-full": CS_FULL, "bt709": CS_BT709, "bt709-full": CS_BT709 | CS_FULL}
+
+
+def colorspace_bits(colorspace, fmt):
+    """CBV_CS_* bits of a colour space name for frames of format `fmt` (a name).  ValueError for an unknown name and for a
+    colour space other than "bt601" with a format that is not YUV (BGR, Bayer, Motion-JPEG)."""
+    try:
+        bits = COLORSPACES[colorspace.lower()]
+    except (KeyError, AttributeError):
+        raise ValueError("unknown colour space %r (expected one of %s)" % (colorspace, ", ".join(COLORSPACES)))
+    name = fmt.lower() if isinstance(fmt, str) else fmt
+    if bits and (name == "bgr" or name not in FORMATS):
+        raise ValueError("colour space %r goes with the YUV formats (%s), not with %r" % (colorspace, ", ".join(k for k in FORMATS if k != "bgr"), fmt))
+    return bits
+
+
 # cbv_pipeline_set_jpeg_planes: the largest sampling a slot of the plane ring holds (gray < 4:2:0 < 4:2:2 < 4:4:4)
 JPEG_PLANES = {"off": 0, "gray": 1, "420": 2, "422": 3, "444": 4}
 
@@ -590,7 +610,7 @@ def _rows(a, what):
     return a
 
 
-def raw_frame(frame, fmt):
+def raw_frame(frame, fmt, colorspace="bt601"):
     """(RawFrame, w, h, arrays the struct points into) of a camera-native frame.  Row strides are free unless stated.
     "nv12" / "nv21": one [h * 3 // 2, w] array or a (y [h, w], chroma [h // 2, w] or [h // 2, w // 2, 2]) pair.
     "yuv420p" / "yv12": one [h * 3 // 2, w] array, cv2's single-matrix layout with the planes back to back (a strided one is
@@ -599,7 +619,17 @@ def raw_frame(frame, fmt):
     "yuyv" / "yvyu" / "uyvy": [h, w, 2].  "bgr": [h, w, 3].
     "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg": one [h, w] array, w and h even and at least 4; a view whose
     rows are contiguous is taken as it is, whatever its row stride.
-    ValueError for other shapes and dtypes, an odd w, and an odd h of a 4:2:0 format."""
+    ValueError for other shapes and dtypes, an odd w, and an odd h of a 4:2:0 format.
+    `colorspace` (COLORSPACES; YUV formats only) goes into the struct's format id: ValueError for an unknown name, and for
+    another colour space than "bt601" with a format that is not YUV."""
+    bits = colorspace_bits(colorspace, fmt)
+    r, w, h, keep = _raw_frame(frame, fmt)
+    r.fmt |= bits
+    return r, w, h, keep
+
+
+def _raw_frame(frame, fmt):
+    """raw_frame in colour space "bt601"."""
     f = format_id(fmt)
     name = fmt.upper()
     if f & 15 == FMT_BAYER_RGGB:

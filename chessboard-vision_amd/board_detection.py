@@ -73,10 +73,12 @@ def distort_points(points, lens):
     return _lens_points("cbv_lens_distort_points", points, lens)
 
 
-def warp_lens(img, M, dsize, lens, profile=None, rot180=False, fmt="bgr"):
+def warp_lens(img, M, dsize, lens, profile=None, rot180=False, fmt="bgr", colorspace="bt601"):
     """warp_perspective_profiled through the camera's `lens` (a stream.Lens): the format's conversion, the profile, then the
     warp whose coordinates go through the lens model, in one kernel with one interpolation per pixel (include/cbv.h,
-    cbv_warp_lens, cbv_warp_jpeg_lens).  `M` is the ideal-coordinate matrix.  lens=None is the lens-free call."""
+    cbv_warp_lens, cbv_warp_jpeg_lens).  `M` is the ideal-coordinate matrix.  lens=None is the lens-free call.  `colorspace`: of a
+    YUV `fmt` (yuv_to_bgr)."""
+    N.colorspace_bits(colorspace, fmt)  # (refused before the library is called)
     c = N.context()
     M = np.ascontiguousarray(M, dtype=np.float64)
     dw, dh = int(dsize[0]), int(dsize[1])
@@ -87,25 +89,27 @@ def warp_lens(img, M, dsize, lens, profile=None, rot180=False, fmt="bgr"):
         c.check(c.lib.cbv_warp_jpeg_lens(c.h, N.ptr(a), a.size, N.ColorProfile.from_dict(profile), _lens_struct(lens), N.ptr(M), dw, dh,
                                          1 if rot180 else 0, N.ptr(out), out.strides[0], C.byref(st)))
         return out
-    raw, w, h, keep = N.raw_frame(img, fmt)
+    raw, w, h, keep = N.raw_frame(img, fmt, colorspace)
     c.check(c.lib.cbv_warp_lens(c.h, raw, w, h, N.ColorProfile.from_dict(profile), _lens_struct(lens), N.ptr(M), dw, dh, 1 if rot180 else 0,
                                 N.ptr(out), out.strides[0]))
     return out
 
 
-def warp_image(img, points, display_size=(1280, 720), margin=100, lens=None):
+def warp_image(img, points, display_size=(1280, 720), margin=100, lens=None, fmt="bgr", colorspace="bt601"):
     """Top-down view of the board (board_detection.py:61-71).
     Returns (warped, matrix, board_size).  With a `lens` (stream.Lens) the `points` are positions in the frame as delivered:
     they are undistorted before getPerspectiveTransform, the matrix returned is the ideal-coordinate one, and the warp
-    corrects the distortion in its gather."""
+    corrects the distortion in its gather; there `fmt` / `colorspace` name a camera-native `img` (warp_lens)."""
     board_size = min(display_size) - margin
     pts1 = np.float32(points if lens is None else undistort_points(points, lens))
     pts2 = np.float32([[0, 0], [board_size, 0], [0, board_size], [board_size, board_size]])
     matrix = get_perspective_transform(pts1, pts2)
     if lens is None:
+        if fmt != "bgr" or colorspace != "bt601":
+            raise ValueError("fmt / colorspace belong to the lens form of warp_image; warp_image_profiled takes a camera-native frame without a lens")
         warped = warp_perspective(img, matrix, (board_size, board_size))
     else:
-        warped = warp_lens(img, matrix, (board_size, board_size), lens)
+        warped = warp_lens(img, matrix, (board_size, board_size), lens, fmt=fmt, colorspace=colorspace)
     return warped, matrix, board_size
 
 
@@ -126,7 +130,7 @@ def warp_jpeg(data, M, dsize, profile=None, rot180=False, out=None):
     return out, int(st.value)
 
 
-def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr", lens=None):
+def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr", lens=None, colorspace="bt601"):
     """warp_perspective(ImageEnhancer(profile).apply_color_profile(img), M, dsize, rot180), byte for byte, in one kernel: the
     profile is applied to the four source pixels each destination pixel blends (include/cbv.h, cbv_warp_color_profile).
     `profile`: a dict with the keys of color_profile.json, `None` / `{}` = no profile.
@@ -135,14 +139,17 @@ def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr", l
     `fmt` "mjpeg": `img` is one baseline JPEG stream (bytes or a uint8 array), and the result is that of jpeg_to_bgr's frame,
     sampled from the decoded planes (cbv_warp_jpeg).
     `lens` (a stream.Lens): the warp corrects the camera's lens distortion in its gather and `M` is the ideal-coordinate
-    matrix (warp_lens)."""
+    matrix (warp_lens).
+    `colorspace`: of a YUV `fmt`, "bt601" (default), "bt601-full", "bt709" or "bt709-full" (yuv_to_bgr); ValueError with
+    another format."""
     if lens is not None:
-        return warp_lens(img, M, dsize, lens, profile, rot180, fmt)
+        return warp_lens(img, M, dsize, lens, profile, rot180, fmt, colorspace)
+    N.colorspace_bits(colorspace, fmt)  # (refused before the library is called)
     c = N.context()
     if isinstance(fmt, str) and fmt.lower() == "mjpeg":
         return warp_jpeg(img, M, dsize, profile, rot180)[0]
     if N.format_id(fmt) != N.FMT_BGR:
-        raw, w, h, keep = N.raw_frame(img, fmt)
+        raw, w, h, keep = N.raw_frame(img, fmt, colorspace)
         M = np.ascontiguousarray(M, dtype=np.float64)
         dw, dh = int(dsize[0]), int(dsize[1])
         out = np.empty((dh, dw, 3), np.uint8)
@@ -158,28 +165,31 @@ def warp_perspective_profiled(img, M, dsize, profile, rot180=False, fmt="bgr", l
     return out
 
 
-def warp_image_profiled(img, points, profile, display_size=(1280, 720), margin=100, rot180=False, fmt="bgr"):
+def warp_image_profiled(img, points, profile, display_size=(1280, 720), margin=100, rot180=False, fmt="bgr", colorspace="bt601"):
     """warp_image(ImageEnhancer(profile).apply_color_profile(img), points, display_size, margin) in one kernel
-    (warp_perspective_profiled); `rot180` adds cv2.rotate(ROTATE_180); `fmt`: the format of a camera-native `img`.
-    Returns what warp_image returns: (warped, matrix, board_size)."""
+    (warp_perspective_profiled); `rot180` adds cv2.rotate(ROTATE_180); `fmt`: the format of a camera-native `img`, `colorspace`:
+    the colour space of a YUV one.  Returns what warp_image returns: (warped, matrix, board_size)."""
     board_size = min(display_size) - margin
     pts2 = np.float32([[0, 0], [board_size, 0], [0, board_size], [board_size, board_size]])
     matrix = get_perspective_transform(np.float32(points), pts2)
-    return warp_perspective_profiled(img, matrix, (board_size, board_size), profile, rot180, fmt), matrix, board_size
+    return warp_perspective_profiled(img, matrix, (board_size, board_size), profile, rot180, fmt, colorspace=colorspace), matrix, board_size
 
 
-def yuv_to_bgr(frame, fmt):
+def yuv_to_bgr(frame, fmt, colorspace="bt601"):
     """cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12 / _YUY2 / _YVYU / _UYVY) on the GPU (include/cbv.h,
     cbv_yuv_to_bgr): a new uint8 [h, w, 3] array.  `fmt` "nv12" / "nv21": one [h * 3 // 2, w] array or a (y, chroma) pair of
     planes; "yuv420p" / "yv12": one contiguous [h * 3 // 2, w] array or the three planes in memory order, (y, u, v) /
     (y, v, u); "yuyv" / "yvyu" / "uyvy": [h, w, 2].  cv2's I420 goes by libav's name "yuv420p"; "i420" is an unknown
     format (ValueError).  Strided views are taken as they are (_native.raw_frame).  A Bayer mosaic ("bayer_rggb", ...) goes
     to bayer_to_bgr and is refused here (ValueError).  (A BoardPipeline takes such frames directly: upload(fmt=...),
-    set_input_format.)"""
+    set_input_format.)
+    `colorspace`: "bt601" (default: cv2's BT.601 limited range, what a UVC webcam's YUYV needs), "bt601-full" (JFIF: phone
+    cameras, full-range UVC modes), "bt709" (decoded video at 720p and above) or "bt709-full" (capture cards in PC range);
+    the same fixed-point arithmetic with that colour space's constants (include/cbv.h, CBV_CS_*)."""
     from . import _native as N
     if isinstance(fmt, str) and fmt.lower() in N.BAYER_FORMATS:
         raise ValueError("yuv_to_bgr converts YUV frames; a %s mosaic goes to bayer_to_bgr" % fmt)
-    raw, w, h, keep = N.raw_frame(frame, fmt)
+    raw, w, h, keep = N.raw_frame(frame, fmt, colorspace)
     if raw.fmt == N.FMT_BGR:
         raise ValueError("yuv_to_bgr converts YUV frames (%s)" % ", ".join(k for k in N.FORMATS if k != "bgr"))
     ctx = N.context()

@@ -466,40 +466,42 @@ static int plane_h2d(cbv_ctx* ctx, u8* dst, const u8* src, int stride, int wbyte
 // caller may have been built against the struct that ended with plane1)
 void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides)
 {
-    const int n = raw_fmt_planes(raw->fmt);
+    const int n = raw_fmt_planes(raw_fmt_layout(raw->fmt));
     planes[0] = raw->plane0, strides[0] = raw->stride0;
     planes[1] = n > 1 ? raw->plane1 : nullptr, strides[1] = n > 1 ? raw->stride1 : 0;
     planes[2] = n > 2 ? raw->plane2 : nullptr, strides[2] = n > 2 ? raw->stride2 : 0;
 }
 
-int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlanes* dev_out, RawGeom* r_out, const char* what)
+int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlanes* dev_out, RawGeom* r_out, int* cs_out, const char* what)
 {
     RC(check_raw_format(ctx, raw->fmt, w, h, what));
+    const int fmt = raw_fmt_layout(raw->fmt);
     const u8* planes[3];
     int strides[3];
     raw_frame_planes(raw, planes, strides);
-    RC(check_raw_planes(ctx, raw->fmt, w, planes, strides, what));
+    RC(check_raw_planes(ctx, fmt, w, planes, strides, what));
     if ((size_t)w * h > (size_t)1 << 28) return cbv_fail(ctx, CBV_ERR_ARG, "%s: image too large", what);
     // a plane follows the largest possible device copy of the one before (rows of twice their length), on a 256-byte boundary
-    const int np = raw_fmt_planes(raw->fmt);
+    const int np = raw_fmt_planes(fmt);
     size_t off[4] = {0, 0, 0, 0};
     for (int i = 0; i < np; i++)
-        off[i + 1] = (off[i] + (size_t)2 * raw_plane_wbytes(raw->fmt, w, i) * raw_plane_rows(raw->fmt, h, i) + 255) & ~(size_t)255;
+        off[i + 1] = (off[i] + (size_t)2 * raw_plane_wbytes(fmt, w, i) * raw_plane_rows(fmt, h, i) + 255) & ~(size_t)255;
     const size_t total = off[np];
     RC(dev_ensure(ctx, &ctx->in, total + 256));
     if (ctx->debug_poison) CBV_HIP(ctx, hipMemsetAsync(ctx->in.p, 0xA5, total, ctx->stream));
     RawGeom r = {};
-    r.fmt = raw->fmt;
+    r.fmt = fmt;
     u8* st = (u8*)ctx->in.p;
     RawPlanes dev = {{nullptr, nullptr, nullptr}};
     int dev_stride[3] = {0, 0, 0};
     for (int i = 0; i < np; i++) {
-        RC(plane_h2d(ctx, st + off[i], planes[i], strides[i], raw_plane_wbytes(raw->fmt, w, i), raw_plane_rows(raw->fmt, h, i), &dev_stride[i]));
+        RC(plane_h2d(ctx, st + off[i], planes[i], strides[i], raw_plane_wbytes(fmt, w, i), raw_plane_rows(fmt, h, i), &dev_stride[i]));
         dev.p[i] = st + off[i];
     }
     r.stride0 = dev_stride[0], r.stride1 = dev_stride[1], r.stride2 = dev_stride[2];
     *dev_out = dev;
     *r_out = r;
+    *cs_out = raw_fmt_cs(raw->fmt);
     return CBV_OK;
 }
 
@@ -507,8 +509,9 @@ int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* ds
 {
     RawPlanes dev;
     RawGeom r;
-    RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, what));
-    return launch_ingest(ctx, dev, r, dst, g, 1);
+    int cs;
+    RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, &cs, what));
+    return launch_ingest(ctx, dev, r, dst, g, 1, cs);
 }
 
 extern "C" int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride)
@@ -538,15 +541,16 @@ extern "C" int cbv_warp_color_profile_raw(cbv_ctx* ctx, const cbv_raw_frame* raw
     if (!host_invert3x3(M9, Minv)) memset(Minv, 0, sizeof(Minv));
     RawPlanes dev;
     RawGeom r;
-    RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, who)); // (the staging buffer keeps 256 bytes behind the last plane: the wide loads' slack)
+    int cs;
+    RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, &cs, who)); // (the staging buffer keeps 256 bytes behind the last plane: the wide loads' slack)
     RC(dev_ensure(ctx, &ctx->a, (size_t)dw * dh * 3 + 256));
     Geom g = tight_geom(w, h);
-    WarpSrc src = warp_src_raw(dev, r, g); // a disabled profile: the plain raw warp
+    WarpSrc src = warp_src_raw(dev, r, g, cs); // a disabled profile: the plain raw warp
     if (profile->enabled) {
         RC(dev_ensure(ctx, &ctx->b, sizeof(ProfileTabs))); // the call's tables
         CBV_HIP(ctx, hipMemcpyAsync(ctx->b.p, &pt, sizeof(pt), hipMemcpyHostToDevice, ctx->stream));
         CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pt is on this stack)
-        src = warp_src_raw_profile(dev, r, g, ctx->b.as<ProfileTabs>());
+        src = warp_src_raw_profile(dev, r, g, ctx->b.as<ProfileTabs>(), 1, 0, cs);
     }
     RC(launch_warp(ctx, src, Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, 1));
     return CBV_DONE(download(ctx, ctx->a.p, out, dw * 3, dh, out_stride));
@@ -561,6 +565,7 @@ extern "C" int cbv_warp_lens(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int 
     if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
     if (!raw || !out || !M9 || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dw > 8192 || dh > 8192 || out_stride < dw * 3)
         return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
+    RC(check_fmt_cs(ctx, raw->fmt, who));
     const bool bgr = raw->fmt == CBV_FMT_BGR;
     if (bgr) RC(check_img(ctx, raw->plane0, w, h, raw->stride0, 3, who));
     else RC(check_raw_format(ctx, raw->fmt, w, h, who));
@@ -596,8 +601,9 @@ extern "C" int cbv_warp_lens(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int 
     } else {
         RawPlanes dev;
         RawGeom r;
-        RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, who)); // (the staging buffer keeps 256 bytes behind the last plane: the wide loads' slack)
-        src = profiled ? warp_src_raw_profile(dev, r, g, dpt) : warp_src_raw(dev, r, g);
+        int cs;
+        RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, &cs, who)); // (the staging buffer keeps 256 bytes behind the last plane: the wide loads' slack)
+        src = profiled ? warp_src_raw_profile(dev, r, g, dpt, 1, 0, cs) : warp_src_raw(dev, r, g, cs);
     }
     RC(dev_ensure(ctx, &ctx->a, (size_t)dw * dh * 3 + 256));
     const LensBoard T = lens_board(Minv, dw, dh, rot180, (u8*)ctx->a.p, dw * 3, (size_t)dw * dh * 3, dpt);

@@ -376,6 +376,8 @@ static inline int raw_fmt_planes(int fmt) { return !raw_fmt_420(fmt) ? 1 : (fmt 
 static inline const char* raw_fmt_name(int fmt)
 {
     switch (fmt) {
+    case CBV_FMT_BGR: return "BGR";
+    case CBV_FMT_MJPEG: return "MJPEG";
     case CBV_FMT_NV12: return "NV12";
     case CBV_FMT_NV21: return "NV21";
     case CBV_FMT_YUV420P: return "YUV420P";
@@ -420,21 +422,26 @@ static inline RawPlanes tight_raw_planes(int fmt, int w, int h, const u8* base)
     if (n > 2) r.p[2] = r.p[1] + (size_t)(w / 2) * (h / 2);
     return r;
 }
+// CBV_ERR_ARG, with the format's name, for colour-space bits (CBV_CS_*) on an id that is not one of the YUV formats
+int check_fmt_cs(cbv_ctx* ctx, int fmt, const char* what);
 // CBV_ERR_ARG unless fmt is a YUV format and w (and h, for the 4:2:0 formats) is even, or a Bayer format and w and h are
-// even and at least 4
+// even and at least 4.  fmt: an id as the caller passed it (check_fmt_cs is part of this) or its layout alone
 int check_raw_format(cbv_ctx* ctx, int fmt, int w, int h, const char* what);
 // CBV_ERR_ARG unless every plane the format has is there with rows of at least their length
 int check_raw_planes(cbv_ctx* ctx, int fmt, int w, const u8* const* planes, const int* strides, const char* what);
 // YV12 -> YUV420P with the chroma planes (and their strides) swapped: the kernels have no YV12 form
 void raw_planes_canonical(RawPlanes* planes, RawGeom* r);
 // cv2.cvtColor COLOR_YUV2BGR_* / COLOR_Bayer??2BGR of `batch` raw frames into BGR frames of geometry g (k_ingest.hip); planes
-// in memory order
-int launch_ingest(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, int batch);
+// in memory order.  r.fmt is the layout; cs (raw_fmt_cs: 0 .. 3, YUV only) chooses the colour space: 0 launches k_ingest, the
+// others k_ingest_cs (k_ingest_cs.hip) with that row of kYuvCs
+int launch_ingest(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, int batch, int cs = 0);
+void launch_ingest_cs(cbv_ctx* ctx, const RawPlanes& planes, const RawGeom& r, u8* dst, const Geom& g, int batch, int cs, bool wide);
 // the planes and strides a host frame's format has; null / 0 for the rest, whose fields are not read
 void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides);
 // one raw host frame (any YUV or Bayer format, strided views) into the context's staging buffer (ctx->in), which keeps 256
-// readable bytes behind the last plane: its device planes and their strides
-int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlanes* dev, RawGeom* r, const char* what);
+// readable bytes behind the last plane: its device planes and their strides.  raw->fmt is split here: r->fmt is the layout,
+// *cs the colour space
+int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlanes* dev, RawGeom* r, int* cs, const char* what);
 // ... and from there into a BGR device image
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
 
@@ -450,6 +457,7 @@ struct WarpSrc {
     size_t dst_profile_stride;
     RawPlanes planes;          // YUV, BAYER: in memory order
     RawGeom r;                 // (fmt = CBV_FMT_BGR for BGR and PROFILE)
+    int cs;                    // YUV: the colour space (raw_fmt_cs); not 0: the runtime-matrix kernels (k_warp_cs.hip, k_warp_lens_cs.hip)
     const u8* jpeg_planes;     // JPEG: the decoded planes of frame 0, frame f's jpeg_plane_stride * f bytes behind
     size_t jpeg_plane_stride;
     const JpegDesc* jpeg_descs; // JPEG: device, frame 0's; each frame has its own layout
@@ -489,22 +497,24 @@ static inline WarpSrc warp_src_profile(const u8* src, Geom g, const ProfileTabs*
 // w (2 w, w / 2) bytes.  Callers keep >= 8 readable bytes behind the last row of the last plane of the last frame (the
 // pipeline's raw ring has 256); between rows, planes and frames the bytes read belong to the next row, plane or frame.
 // Bayer: the four taps are demosaiced before the blend, and no byte outside the frames' rows is read.
-static inline WarpSrc warp_src_raw(RawPlanes planes, RawGeom r, Geom g)
+static inline WarpSrc warp_src_raw(RawPlanes planes, RawGeom r, Geom g, int cs = 0)
 {
     WarpSrc s = {};
     s.kind = raw_fmt_bayer(r.fmt) ? WarpSrc::BAYER : WarpSrc::YUV;
     s.g = g;
     s.planes = planes;
     s.r = r;
+    s.cs = cs;
     return s;
 }
 // Raw frames with the colour profile applied to the converted taps (k_warp_raw_profile.hip): launch_ingest, then
 // apply_color_profile, then the warp, byte for byte, with neither frame in between; ptabs / np / dst_profile_stride as
 // warp_src_profile takes them, the slack behind the frames as warp_src_raw asks.  The multi-board launch reads the boards'
 // own tables (BoardDev::ptabs) instead of `ptabs`, which only has to be non-null there.  Counted as CBV_K_WARP_YUV.
-static inline WarpSrc warp_src_raw_profile(RawPlanes planes, RawGeom r, Geom g, const ProfileTabs* ptabs, int np = 1, size_t dst_profile_stride = 0)
+static inline WarpSrc warp_src_raw_profile(RawPlanes planes, RawGeom r, Geom g, const ProfileTabs* ptabs, int np = 1, size_t dst_profile_stride = 0,
+                                           int cs = 0)
 {
-    WarpSrc s = warp_src_raw(planes, r, g);
+    WarpSrc s = warp_src_raw(planes, r, g, cs);
     s.ptabs = ptabs;
     s.np = np;
     s.dst_profile_stride = dst_profile_stride;
@@ -753,6 +763,10 @@ int launch_warp_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int m
 int launch_warp_raw_profile(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
                             size_t dst_frame_stride, int batch, u32* zero_word, u32* zero_word2);
 int launch_warp_raw_profile_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
+// ... a YUV source whose colour space is not 0, with or without a profile, to: k_warp_cs.hip
+int launch_warp_cs(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride, int batch,
+                   u32* zero_word, u32* zero_word2);
+int launch_warp_cs_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
 // ... and a source of JPEG planes (warp_src_jpeg), with a profile or without: k_warp_jpeg.hip
 int launch_warp_jpeg(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
                      int batch, u32* zero_word, u32* zero_word2);
@@ -785,6 +799,9 @@ int launch_warp_lens(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensB
                      u32* zero_word, u32* zero_word2);
 int launch_warp_lens_profile(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
                              u32* zero_word, u32* zero_word2);
+// what launch_warp_lens hands a YUV source whose colour space is not 0 to: k_warp_lens_cs.hip
+int launch_warp_lens_cs(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
+                        u32* zero_word, u32* zero_word2);
 // cbv_lens -> LensDev; CBV_ERR_ARG for a field that is not finite or a focal length that is not positive
 int lens_checked(cbv_ctx* ctx, const cbv_lens* lens, LensDev* out, const char* who);
 // warp_footprint through the lens: every border pixel of the destination through the full map, one more pixel of margin

@@ -762,7 +762,7 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
             if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // submitted copies of the slot
             RC(dev_ensure(ctx, &ctx->a, P.g.frame_stride + 256));
             if (P.plan.source == FRAMES_PLANES) RC(pipeline_jpeg_slot_bgr(P, slot, (u8*)ctx->a.p)); // k_jpeg_color on the slot's planes
-            else RC(launch_ingest(ctx, slot_planes(P, slot), tight_raw_geom(P.fs.fmt, P.w, P.h), (u8*)ctx->a.p, P.g, 1));
+            else RC(launch_ingest(ctx, slot_planes(P, slot), tight_raw_geom(P.fs.fmt, P.w, P.h), (u8*)ctx->a.p, P.g, 1, P.fs.cs));
             src = (const u8*)ctx->a.p;
         }
     } else if (which == 1) {

@@ -19,7 +19,7 @@ WarpSrc pipeline_raw_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs
 {
     if (P.plan.source == FRAMES_PLANES) return pipeline_jpeg_warp_src(P, slot0, ptabs, np, dst_profile_stride);
     const RawGeom rg = tight_raw_geom(P.fs.fmt, P.w, P.h);
-    return ptabs ? warp_src_raw_profile(slot_planes(P, slot0), rg, P.g, ptabs, np, dst_profile_stride) : warp_src_raw(slot_planes(P, slot0), rg, P.g);
+    return ptabs ? warp_src_raw_profile(slot_planes(P, slot0), rg, P.g, ptabs, np, dst_profile_stride, P.fs.cs) : warp_src_raw(slot_planes(P, slot0), rg, P.g, P.fs.cs);
 }
 
 extern "C" int cbv_pipeline_upload(cbv_pipeline* p, int slot, const uint8_t* bgr, int stride)
@@ -48,22 +48,23 @@ extern "C" int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_
     if (!raw || slot < 0 || slot >= P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_upload_raw: bad arguments");
     if (raw->fmt == CBV_FMT_BGR) return cbv_pipeline_upload(p, slot, raw->plane0, raw->stride0);
     RC(check_raw_format(ctx, raw->fmt, P.w, P.h, "cbv_pipeline_upload_raw"));
+    const int fmt = raw_fmt_layout(raw->fmt), cs = raw_fmt_cs(raw->fmt);
     CBV_ENTER(ctx);
     RC(join_scan(P)); // lanes and scan of the last run
     if (P.plan.raw()) { // the frame as it is into its slot of the raw ring, rows packed
         if (P.plan.source == FRAMES_PLANES) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: format %d, but %s", raw->fmt, kJpegRawModeMsg);
-        if (raw->fmt != P.fs.fmt)
-            return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: format %d, but %s (format %d)", raw->fmt, kRawModeMsg, P.fs.fmt);
+        if (fmt != P.fs.fmt || cs != P.fs.cs) // (the whole id: an NV12 / BT.709 ring refuses an NV12 / BT.601 frame)
+            return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_upload_raw: format %d, but %s (format %d)", raw->fmt, kRawModeMsg, P.fs.fmt | P.fs.cs * CBV_CS_FULL);
         const u8* planes[3];
         int strides[3];
         raw_frame_planes(raw, planes, strides);
-        RC(check_raw_planes(ctx, raw->fmt, P.w, planes, strides, "cbv_pipeline_upload_raw"));
+        RC(check_raw_planes(ctx, fmt, P.w, planes, strides, "cbv_pipeline_upload_raw"));
         RC(pipeline_raw_ring(P));
         // the raw ring is the only frame store here: a copy of this slot that cbv_pipeline_submit left in flight lands first
         if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
         const RawPlanes dst = slot_planes(P, slot);
-        for (int i = 0; i < raw_fmt_planes(raw->fmt); i++)
-            RC(rows_h2d(ctx, (u8*)dst.p[i], planes[i], strides[i], raw_plane_wbytes(raw->fmt, P.w, i), raw_plane_rows(raw->fmt, P.h, i)));
+        for (int i = 0; i < raw_fmt_planes(fmt); i++)
+            RC(rows_h2d(ctx, (u8*)dst.p[i], planes[i], strides[i], raw_plane_wbytes(fmt, P.w, i), raw_plane_rows(fmt, P.h, i)));
         CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return CBV_OK;
     }
@@ -86,10 +87,12 @@ extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
     int rc;
     Pipe* P = frames_owner(p, who, "the pipeline is null", &rc);
     if (!P) return rc;
+    RC(check_fmt_cs(P->ctx, fmt, who)); // (colour-space bits on BGR or Motion-JPEG)
     if (fmt != CBV_FMT_BGR && fmt != CBV_FMT_MJPEG) RC(check_raw_format(P->ctx, fmt, P->w, P->h, who));
     CBV_ENTER(P->ctx);
     FrameSettings next = P->fs;
-    next.fmt = fmt;
+    next.fmt = raw_fmt_layout(fmt);
+    next.cs = raw_fmt_cs(fmt);
     return pipeline_set_frames(*P, next, who, true); // both ingest rings go, whatever the format was
 }
 
@@ -141,7 +144,7 @@ extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
         if (read_ev) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, read_ev, 0));
         hipStream_t caller = ctx->stream;
         ctx->stream = P.copy_stream;
-        const int rc_ingest = P.plan.raw() ? CBV_OK : launch_ingest(ctx, slot_planes(P, slot0), rg, P.frames + P.g.frame_stride * slot0, P.g, count);
+        const int rc_ingest = P.plan.raw() ? CBV_OK : launch_ingest(ctx, slot_planes(P, slot0), rg, P.frames + P.g.frame_stride * slot0, P.g, count, P.fs.cs);
         ctx->stream = caller;
         RC(rc_ingest);
     }

@@ -1,6 +1,7 @@
 // One YUV pixel to BGR: cv2.cvtColor's COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12 / _YUY2 / _YVYU / _UYVY arithmetic on 8-bit
 // data (include/cbv.h), the ONE definition behind k_ingest (whole frames) and k_warp_yuv (the four taps of a warped pixel),
-// and where the bytes of each layout lie.
+// and where the bytes of each layout lie.  That is colour space 0, BT.601 limited range; the other three (BT.601 full range,
+// BT.709 limited and full range) are the same arithmetic with other constants: the second half of this file.
 #pragma once
 #include "cbv_device.h"
 
@@ -40,5 +41,38 @@ __device__ __forceinline__ u32 d_sat8_shr20(int v) { return (u32)min(max(v, 0), 
 __device__ __forceinline__ u32 d_yuv_bgr(int Y, const Chroma& c)
 {
     const int y = max(0, Y - 16) * YUV_CY;
+    return d_sat8_shr20(y + c.b) | (d_sat8_shr20(y + c.g) << 8) | (d_sat8_shr20(y + c.r) << 16);
+}
+
+// ---------------------------------------------------------------------------
+// The other colour spaces (include/cbv.h, CBV_CS_*): the same arithmetic with the six constants taken from a kernel
+// argument.  They are uniform over a launch, so they live in scalar registers; the kernels that take them (k_ingest_cs.hip,
+// k_warp_cs.hip) exist once per layout, not once per colour space.  Colour space 0 keeps the functions above, whose
+// constants are the compiler's.
+// Everything stays inside signed 32 bits for every row of the table: the largest magnitude a sum can reach is BT.709
+// limited's B, (255 - 16) * 1220945 + 524288 + 128 * 2215014 = 575 851 935 < 2^31.
+// ---------------------------------------------------------------------------
+struct YuvCs {
+    int cy, cub, cug, cvg, cvr, yoff;
+};
+
+// row = raw_fmt_cs(fmt), (fmt & CBV_CS_MASK) / CBV_CS_FULL: BT.601 limited (cv2's three-decimal constants, the enum above), BT.601 full (JFIF),
+// BT.709 limited, BT.709 full.  Rows 1 to 3 are round(c * 2^20) of the exact coefficients (include/cbv.h has the fractions).
+static constexpr YuvCs kYuvCs[4] = {
+    {YUV_CY, YUV_CUB, YUV_CUG, YUV_CVG, YUV_CVR, 16},
+    {1048576, 1858077, -360853, -748826, 1470104, 0},
+    {1220945, 2215014, -223607, -558796, 1879825, 16},
+    {1048576, 1945738, -196424, -490864, 1651297, 0},
+};
+
+__device__ __forceinline__ Chroma d_chroma(int U, int V, const YuvCs& k)
+{
+    const int u = U - 128, v = V - 128, half = 1 << (YUV_SHIFT - 1);
+    return Chroma{half + k.cub * u, half + k.cvg * v + k.cug * u, half + k.cvr * v};
+}
+
+__device__ __forceinline__ u32 d_yuv_bgr(int Y, const Chroma& c, const YuvCs& k)
+{
+    const int y = max(0, Y - k.yoff) * k.cy;
     return d_sat8_shr20(y + c.b) | (d_sat8_shr20(y + c.g) << 8) | (d_sat8_shr20(y + c.r) << 16);
 }

@@ -16,6 +16,12 @@ static constexpr bool raw_fmt_bayer(int fmt)
     return fmt == CBV_FMT_BAYER_RGGB || fmt == CBV_FMT_BAYER_BGGR || fmt == CBV_FMT_BAYER_GRBG || fmt == CBV_FMT_BAYER_GBRG;
 }
 static inline bool raw_fmt_420(int fmt) { return (fmt & 15) == CBV_FMT_NV12; }
+// the YUV families (of a known layout)
+static constexpr bool raw_fmt_yuv(int fmt) { return (fmt & 15) == CBV_FMT_NV12 || (fmt & 15) == CBV_FMT_YUYV; }
+// An id as a caller passes it = layout | colour space (CBV_CS_*, YUV only).  It is split once, where it enters the library;
+// everything below sees the layout, and the colour space (0 .. 3, the row of cbv_yuv.h's table) travels beside it.
+static constexpr int raw_fmt_layout(int fmt) { return fmt & ~CBV_CS_MASK; }
+static constexpr int raw_fmt_cs(int fmt) { return (fmt & CBV_CS_MASK) / CBV_CS_FULL; }
 // tightly packed raw frames, planes back to back (the ingest rings round each frame to 256 bytes); fmt BGR: tight_geom's bytes
 static inline size_t raw_frame_bytes(int fmt, int w, int h)
 {
@@ -75,7 +81,8 @@ enum FrameSource { FRAMES_BGR = 0, FRAMES_RAW, FRAMES_PLANES };
 
 struct FrameSettings {
     int kind = FRAMES_ENHANCE;
-    int fmt = CBV_FMT_BGR;                // cbv_pipeline_set_input_format
+    int fmt = CBV_FMT_BGR;                // cbv_pipeline_set_input_format: the layout
+    int cs = 0;                           // ... and the colour space of a YUV layout (raw_fmt_cs); the plan does not depend on it
     int planes = CBV_JPEG_PLANES_OFF;     // cbv_pipeline_set_jpeg_planes; means something with CBV_FMT_MJPEG only
     int w = 0, h = 0, max_frames = 0;
     size_t jpeg_slot_bytes = 0;           // cbv_pipeline_set_jpeg_slot_bytes; 0: the default

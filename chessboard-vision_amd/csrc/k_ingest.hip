@@ -168,8 +168,17 @@ __global__ __launch_bounds__(256) void k_ingest(const u8* __restrict__ p0, const
     }
 }
 
+int check_fmt_cs(cbv_ctx* ctx, int fmt, const char* what)
+{
+    if (!raw_fmt_cs(fmt) || (raw_fmt_known(raw_fmt_layout(fmt)) && raw_fmt_yuv(raw_fmt_layout(fmt)))) return CBV_OK;
+    return cbv_fail(ctx, CBV_ERR_ARG, "%s: colour-space bits 0x%x on format %d (%s): a colour space goes with the YUV formats only", what, fmt & CBV_CS_MASK,
+                    raw_fmt_layout(fmt), raw_fmt_name(raw_fmt_layout(fmt)));
+}
+
 int check_raw_format(cbv_ctx* ctx, int fmt, int w, int h, const char* what)
 {
+    RC(check_fmt_cs(ctx, fmt, what));
+    fmt = raw_fmt_layout(fmt); // (the colour space of a YUV id asks nothing of the frame)
     if (!raw_fmt_known(fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: unknown raw format %d", what, fmt);
     if (raw_fmt_bayer(fmt)) {
         if (w < 4 || h < 4 || ((w | h) & 1))
@@ -207,9 +216,11 @@ static void ingest_launch(cbv_ctx* ctx, const RawPlanes& pl, RawGeom r, u8* dst,
     hipLaunchKernelGGL((k_ingest<FMT, PX>), grid, dim3(256), 0, ctx->stream, pl.p[0], pl.p[1], pl.p[2], r, dst, g);
 }
 
-int launch_ingest(cbv_ctx* ctx, RawPlanes pl, RawGeom r, u8* dst, Geom g, int batch)
+int launch_ingest(cbv_ctx* ctx, RawPlanes pl, RawGeom r, u8* dst, Geom g, int batch, int cs)
 {
     RC(check_raw_format(ctx, r.fmt, g.w, g.h, "launch_ingest"));
+    if (raw_fmt_cs(r.fmt) || cs < 0 || cs > 3 || (cs && !raw_fmt_yuv(r.fmt)))
+        return cbv_fail(ctx, CBV_ERR_ARG, "launch_ingest: colour space %d with layout %d (the layout and the colour space are split where an id enters)", cs, r.fmt);
     const int strides[3] = {r.stride0, r.stride1, r.stride2};
     if (batch <= 0 || !dst || g.stride < g.w * 3) return cbv_fail(ctx, CBV_ERR_ARG, "launch_ingest: bad planes or strides");
     RC(check_raw_planes(ctx, r.fmt, g.w, pl.p, strides, "launch_ingest"));
@@ -226,7 +237,8 @@ int launch_ingest(cbv_ctx* ctx, RawPlanes pl, RawGeom r, u8* dst, Geom g, int ba
         if (wide) ingest_launch<FMT, 4>(ctx, pl, r, dst, g, batch);                      \
         else ingest_launch<FMT, 2>(ctx, pl, r, dst, g, batch);                           \
         break
-    switch (r.fmt) {
+    if (cs) launch_ingest_cs(ctx, pl, r, dst, g, batch, cs, wide); // the runtime-matrix form (k_ingest_cs.hip)
+    else switch (r.fmt) {
         CBV_INGEST(CBV_FMT_NV12);
         CBV_INGEST(CBV_FMT_NV21);
         CBV_INGEST(CBV_FMT_YUYV);

@@ -15,7 +15,8 @@
 // same blend (warp_blend).  A tap outside the frame is BGR (0, 0, 0) for every source, not the conversion of zero.  The
 // sources: WarpBgr (BGR frames through cv2.normalize's byte map), WarpProfile (BGR frames through apply_color_profile) and
 // WarpRaw<FMT> (camera-native YUV frames and Bayer mosaics: the BGR frame k_ingest would write is never made).  The raw
-// sources that carry a colour profile (WarpRawProfile<FMT>) have their kernels in k_warp_raw_profile.hip.
+// sources that carry a colour profile (WarpRawProfile<FMT>) have their kernels in k_warp_raw_profile.hip, and YUV frames in
+// a colour space other than 0 (WarpSrc::cs) theirs in k_warp_cs.hip.
 // Also here: the synthetic frame generator used by bench/tests.
 #include "warp_gather.h"
 
@@ -112,6 +113,7 @@ __global__ __launch_bounds__(256) void k_warp_profile_mb(const u8* __restrict__ 
 int launch_warp(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
                 int batch, u32* zero_word, u32* zero_word2)
 {
+    if (s.cs) return launch_warp_cs(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     if (s.kind == WarpSrc::JPEG) return launch_warp_jpeg(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     if (s.raw() && s.ptabs) return launch_warp_raw_profile(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     WarpM M;
@@ -145,6 +147,7 @@ int launch_warp(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, in
 
 int launch_warp_mb(cbv_ctx* ctx, WarpSrc s, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2)
 {
+    if (s.cs) return launch_warp_cs_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     if (s.kind == WarpSrc::JPEG) return launch_warp_jpeg_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     if (s.raw() && s.ptabs) return launch_warp_raw_profile_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     const hipStream_t st = ctx->stream;

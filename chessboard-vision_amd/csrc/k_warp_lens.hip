@@ -9,6 +9,7 @@
 int launch_warp_lens(cbv_ctx* ctx, WarpSrc s, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
                      u32* zero_word, u32* zero_word2)
 {
+    if (s.cs) return launch_warp_lens_cs(ctx, s, lens, tab, ne, max_dw, max_dh, s0, batch, zero_word, zero_word2);
     if ((s.raw() || s.kind == WarpSrc::JPEG) && s.ptabs) return launch_warp_lens_profile(ctx, s, lens, tab, ne, max_dw, max_dh, s0, batch, zero_word, zero_word2);
     if (s.kind == WarpSrc::JPEG) {
         RC(warp_lens_jpeg_checked(ctx, s));

@@ -7,24 +7,7 @@
 // alone.  The kernels live in a file of their own: k_warp.hip's 52 stay what they are.
 #include "warp_gather.h"
 
-// Frames per thread of the many-frames form (batch >= 8), per family.  The profile's registers come on top of the
-// conversion's: the four-frame form of every family needs more than 64 VGPRs (NV12 79, planar 4:2:0 91, packed 4:2:2 71,
-// Bayer 72), and so does the two-frame form of the 4:2:0 families (68, 77); at or under 64 stay two frames of packed 4:2:2
-// and Bayer (60, 62) and one frame of the 4:2:0 families (58, 62).  Each family ships the form that was fastest INSIDE
-// p.run on an MI355X (1080p, 512 frames, two lanes), and a form above 64 only where it beat the best one at or under 64 by
-// more than the runs' range: per frame, 1 / 2 / 4 frames a thread, NV12 8.00 / 6.92 / 6.77 us, planar 8.56 / 7.50 / 7.57,
-// packed 4:2:2 7.50 / 6.30 / 6.05, Bayer 7.92 / 6.83 / 6.20 (ranges 0.02 - 0.06).  So four frames everywhere but planar
-// 4:2:0, which takes two.  DESIGN.md section 6n has the table; tests/test_warp_raw_profile_resources.py pins the counts.
-// (RAW_PROFILE_FPT = 1, 2 or 4 in the build's environment gives every family that form: tools/raw_profile_timing.py's
-// comparison.)
-static constexpr int raw_profile_fpt(int fmt)
-{
-#ifdef RAW_PROFILE_FPT
-    return RAW_PROFILE_FPT;
-#else
-    return (fmt & 15) == CBV_FMT_NV12 && (fmt & 0x20) ? 2 : 4; // planar 4:2:0 (YUV420P): two
-#endif
-}
+// (the frames per thread of the many-frames form, per family: raw_profile_fpt, warp_gather.h)
 
 // blockIdx.z = profile * nz + group of frames; profile p writes its frames dst_profile_stride bytes behind profile p - 1's
 // (Bayer: p1 = p2 = null)
@@ -53,12 +36,6 @@ __global__ __launch_bounds__(256) void k_warp_raw_profile_mb(const u8* __restric
     if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * WP_ROWS >= T.S)) return;
     warp_gather<WarpRawProfile<FMT>, FPT>(WarpRawProfile<FMT>{{p0, p1, p2, r, sw, sh}, st, T.ptabs}, warp_board_dst(T, s0), zero_word, zero_word2, batch,
                                           blockIdx.z - b * nz);
-}
-
-// the frames per thread of the many-frames form of a format as the caller names it (YV12 is launched as YUV420P)
-static int raw_profile_many(int fmt)
-{
-    return raw_profile_fpt(fmt == CBV_FMT_YV12 ? CBV_FMT_YUV420P : fmt);
 }
 
 int launch_warp_raw_profile(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,

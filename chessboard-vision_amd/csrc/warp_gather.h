@@ -1,6 +1,6 @@
 // The warp's one gather (warp_gather), its sources and what the launchers share, for the translation units that hold
-// warp kernels: k_warp.hip, k_warp_raw_profile.hip, k_warp_jpeg.hip and the lens forms' k_warp_lens.hip and
-// k_warp_lens_profile.hip.  Private.
+// warp kernels: k_warp.hip, k_warp_raw_profile.hip, k_warp_jpeg.hip, the lens forms' k_warp_lens.hip and
+// k_warp_lens_profile.hip, and k_warp_cs.hip and k_warp_lens_cs.hip (YUV frames in a colour space other than 0).  Private.
 #pragma once
 #include "cbv_bayer.h"
 #include "cbv_profile_px.h"
@@ -103,7 +103,7 @@ enum { WARP_BGR, WARP_PROFILE, WARP_YUV, WARP_BAYER, WARP_JPEG };
 template <bool CALC_>
 struct WarpBgr {
     static constexpr int KIND = WARP_BGR, ROWS = 4, FMT = CBV_FMT_BGR;
-    static constexpr bool CALC = CALC_, TABS = false;
+    static constexpr bool CALC = CALC_, TABS = false, CS = false;
     template <int FPT>
     struct Lds {
         u8 lut[FPT][256];
@@ -124,7 +124,7 @@ struct WarpBgr {
 // enabled = 0 leaves the taps as they are.
 struct WarpProfile {
     static constexpr int KIND = WARP_PROFILE, ROWS = WP_ROWS, FMT = CBV_FMT_BGR;
-    static constexpr bool TABS = true;
+    static constexpr bool TABS = true, CS = false;
     template <int FPT>
     using Lds = ProfileLds;
     const u8* src;
@@ -142,7 +142,7 @@ struct WarpProfile {
 template <int FMT_>
 struct WarpRaw {
     static constexpr int KIND = raw_fmt_bayer(FMT_) ? WARP_BAYER : WARP_YUV, ROWS = 4, FMT = FMT_;
-    static constexpr bool TABS = false;
+    static constexpr bool TABS = false, CS = false;
     template <int FPT>
     struct Lds {
     };
@@ -169,13 +169,28 @@ struct WarpRawProfile : WarpRaw<FMT_> {
     const ProfileTabs* pt; // the profile's table
 };
 
+// YUV frames in another colour space than 0 (include/cbv.h, CBV_CS_*; k_warp_cs.hip and k_warp_lens_cs.hip): the loads of
+// WarpRaw, the taps converted with the six constants the source carries (cbv_yuv.h, YuvCs), which are uniform and stay in
+// scalar registers.  Their kernels hand `cs` to warp_gather as its last argument (CS tells the one kernel template of the lens
+// forms to).
+template <int FMT_>
+struct WarpRawCs : WarpRaw<FMT_> {
+    static constexpr bool CS = true;
+    YuvCs cs;
+};
+template <int FMT_>
+struct WarpRawProfileCs : WarpRawProfile<FMT_> {
+    static constexpr bool CS = true;
+    YuvCs cs;
+};
+
 // The decoded planes of Motion-JPEG frames (k_warp_jpeg.hip: pipelines in planes mode without enhancement, cbv_warp_jpeg): a
 // tap at (x, y) is jpeg_pixel(D, planes, x, y) of the frame's own descriptor D, so the BGR frame k_jpeg_color would write is
 // never made.  Frame f's planes lie at planes + f * plane_stride, its descriptor is descs[f]: gray, 4:4:4, 4:2:2 and 4:2:0
 // frames may share a launch.
 struct WarpJpeg {
     static constexpr int KIND = WARP_JPEG, ROWS = 4, FMT = CBV_FMT_MJPEG;
-    static constexpr bool TABS = false;
+    static constexpr bool TABS = false, CS = false;
     template <int FPT>
     struct Lds {
     };
@@ -268,27 +283,29 @@ __device__ __forceinline__ u32 d_jpeg_px(const JpegDesc& D, const u8* __restrict
 }
 
 // pixel (x, y) of one raw YUV frame with byte loads (the taps of pixels on the frame's border)
-template <int FMT>
+// (K, here and below: nothing, or the YuvCs of a source in another colour space than 0, which every call of d_chroma and
+// d_yuv_bgr then takes as its last argument: warp_gather)
+template <int FMT, class... K>
 __device__ __forceinline__ u32 d_raw_px(const u8* __restrict__ f0, const u8* __restrict__ f1, const u8* __restrict__ f2, const RawGeom& r, int x,
-                                        int y)
+                                        int y, K... k)
 {
     typedef YuvLay<FMT> L;
     if (L::PLANAR)
         return d_yuv_bgr(f0[(size_t)y * r.stride0 + x],
-                         d_chroma(f1[(size_t)(y >> 1) * r.stride1 + (x >> 1)], f2[(size_t)(y >> 1) * r.stride2 + (x >> 1)]));
+                         d_chroma(f1[(size_t)(y >> 1) * r.stride1 + (x >> 1)], f2[(size_t)(y >> 1) * r.stride2 + (x >> 1)], k...), k...);
     if (L::F420) {
         const u8* c = f1 + (size_t)(y >> 1) * r.stride1 + (x & ~1);
-        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x], d_chroma(c[L::CU], c[L::CV]));
+        return d_yuv_bgr(f0[(size_t)y * r.stride0 + x], d_chroma(c[L::CU], c[L::CV], k...), k...);
     }
     const u8* s = f0 + (size_t)y * r.stride0 + (size_t)(x >> 1) * 4;
-    return d_yuv_bgr(s[L::Y0 + (x & 1) * 2], d_chroma(s[L::PU], s[L::PV]));
+    return d_yuv_bgr(s[L::Y0 + (x & 1) * 2], d_chroma(s[L::PU], s[L::PV], k...), k...);
 }
 
 // the chroma of byte pair `p` of an NV12 (U V) / NV21 (V U) row
-template <int FMT>
-__device__ __forceinline__ Chroma d_chroma_pair(u32 p)
+template <int FMT, class... K>
+__device__ __forceinline__ Chroma d_chroma_pair(u32 p, K... k)
 {
-    return d_chroma((p >> (8 * YuvLay<FMT>::CU)) & 255, (p >> (8 * YuvLay<FMT>::CV)) & 255);
+    return d_chroma((p >> (8 * YuvLay<FMT>::CU)) & 255, (p >> (8 * YuvLay<FMT>::CV)) & 255, k...);
 }
 
 // pixel (x, y) of one mosaic, inside the frame, with byte loads: the site is clamped, its neighbourhood lies inside
@@ -331,9 +348,13 @@ __device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride,
 // max(((sy + 1) >> 1) - 1, 0) for 4:2:0 and are clamped to the component's last row, which only moves rows no tap reads.  So
 // 4 loads (gray: 2), 6 (4:4:4, 4:2:2) or 8 (4:2:0) per frame.  The planes are whole MCUs, and the bytes a load reads past
 // the window belong to the next row, plane or slot: callers keep >= 4 readable bytes behind the last frame's planes.
-template <class Src, int FPT, bool LENS = false>
+//
+// K: nothing, or the YuvCs of a YUV source in another colour space than 0 (WarpRawCs, WarpRawProfileCs: their `cs`).  `cs...`
+// closes every call of the conversion, so colour space 0's calls are the ones with the compile-time constants, as they
+// always were, and the others' take the launch's.
+template <class Src, int FPT, bool LENS = false, class... K>
 __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz,
-                                            const LensDev* lens = nullptr)
+                                            const LensDev* lens = nullptr, K... cs)
 {
     constexpr int KIND = Src::KIND, FMT = Src::FMT;
     constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV, JPEG = KIND == WARP_JPEG;
@@ -526,40 +547,40 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                             Chroma a0, a1, b0, b1;
                             if (NV12) {
                                 const u32 a = ca[k], sa = odd ? a >> 16 : a;
-                                a0 = d_chroma_pair<FMT>(a);
-                                a1 = d_chroma_pair<FMT>(sa);
+                                a0 = d_chroma_pair<FMT>(a, cs...);
+                                a1 = d_chroma_pair<FMT>(sa, cs...);
                                 b0 = a0;
                                 b1 = a1;
                                 if (two_crows) {
                                     const u32 b = cb[k], sb = odd ? b >> 16 : b;
-                                    b0 = d_chroma_pair<FMT>(b);
-                                    b1 = d_chroma_pair<FMT>(sb);
+                                    b0 = d_chroma_pair<FMT>(b, cs...);
+                                    b1 = d_chroma_pair<FMT>(sb, cs...);
                                 }
                             } else {
                                 const u32 u0 = ca[k], v0 = va[k];
-                                a0 = d_chroma(u0 & 255, v0 & 255);
-                                a1 = d_chroma((odd ? u0 >> 8 : u0) & 255, (odd ? v0 >> 8 : v0) & 255);
+                                a0 = d_chroma(u0 & 255, v0 & 255, cs...);
+                                a1 = d_chroma((odd ? u0 >> 8 : u0) & 255, (odd ? v0 >> 8 : v0) & 255, cs...);
                                 b0 = a0;
                                 b1 = a1;
                                 if (two_crows) {
                                     const u32 u1 = cb[k], v1 = vb[k];
-                                    b0 = d_chroma(u1 & 255, v1 & 255);
-                                    b1 = d_chroma((odd ? u1 >> 8 : u1) & 255, (odd ? v1 >> 8 : v1) & 255);
+                                    b0 = d_chroma(u1 & 255, v1 & 255, cs...);
+                                    b1 = d_chroma((odd ? u1 >> 8 : u1) & 255, (odd ? v1 >> 8 : v1) & 255, cs...);
                                 }
                             }
-                            q[0] = d_yuv_bgr((int)(ta[k] & 255), a0);
-                            q[1] = d_yuv_bgr((int)((ta[k] >> 8) & 255), a1);
-                            q[2] = d_yuv_bgr((int)(tb[k] & 255), b0);
-                            q[3] = d_yuv_bgr((int)((tb[k] >> 8) & 255), b1);
+                            q[0] = d_yuv_bgr((int)(ta[k] & 255), a0, cs...);
+                            q[1] = d_yuv_bgr((int)((ta[k] >> 8) & 255), a1, cs...);
+                            q[2] = d_yuv_bgr((int)(tb[k] & 255), b0, cs...);
+                            q[3] = d_yuv_bgr((int)((tb[k] >> 8) & 255), b1, cs...);
                         } else {
 #pragma unroll
                             for (int r = 0; r < 2; r++) {
                                 const u64 w = r ? tb[k] : ta[k];
                                 const u32 lo = (u32)w, hi = (u32)(w >> 32), s1 = odd ? hi : lo;
-                                const Chroma c0 = d_chroma((lo >> (8 * L::PU)) & 255, (lo >> (8 * L::PV)) & 255);
-                                const Chroma c1 = d_chroma((s1 >> (8 * L::PU)) & 255, (s1 >> (8 * L::PV)) & 255);
-                                q[2 * r] = d_yuv_bgr((int)((odd ? lo >> (8 * L::Y1) : lo >> (8 * L::Y0)) & 255), c0);
-                                q[2 * r + 1] = d_yuv_bgr((int)((odd ? hi >> (8 * L::Y0) : lo >> (8 * L::Y1)) & 255), c1);
+                                const Chroma c0 = d_chroma((lo >> (8 * L::PU)) & 255, (lo >> (8 * L::PV)) & 255, cs...);
+                                const Chroma c1 = d_chroma((s1 >> (8 * L::PU)) & 255, (s1 >> (8 * L::PV)) & 255, cs...);
+                                q[2 * r] = d_yuv_bgr((int)((odd ? lo >> (8 * L::Y1) : lo >> (8 * L::Y0)) & 255), c0, cs...);
+                                q[2 * r + 1] = d_yuv_bgr((int)((odd ? hi >> (8 * L::Y0) : lo >> (8 * L::Y1)) & 255), c1, cs...);
                             }
                         }
                     } else if constexpr (JPEG) {
@@ -589,10 +610,10 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                         const u8* f0p = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
                         const u8* f1p = L::F420 ? S.p1 + (size_t)(f0 + k) * S.r.frame_stride : nullptr;
                         const u8* f2p = PLANAR ? S.p2 + (size_t)(f0 + k) * S.r.frame_stride : nullptr;
-                        if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy);
-                        if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy);
-                        if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy + 1);
-                        if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy + 1);
+                        if (t.x0in && t.y0in) q[0] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy, cs...);
+                        if (t.x1in && t.y0in) q[1] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy, cs...);
+                        if (t.x0in && t.y1in) q[2] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx, t.sy + 1, cs...);
+                        if (t.x1in && t.y1in) q[3] = d_raw_px<FMT>(f0p, f1p, f2p, S.r, t.sx + 1, t.sy + 1, cs...);
                     } else if constexpr (JPEG) {
                         const JpegDesc& D = S.descs[f0 + k];
                         const u8* pl = S.planes + (size_t)(f0 + k) * S.plane_stride;
@@ -656,6 +677,39 @@ static int warp_groups(int batch, int many = 4)
     const int fpt = batch >= 8 ? many : 1;
     return (batch + fpt - 1) / fpt;
 }
+
+// Frames per thread of the many-frames form (batch >= 8) of the raw sources with a profile (k_warp_raw_profile.hip, and
+// k_warp_cs.hip, whose forms take what their siblings take), per family.  The profile's registers come on top of the
+// conversion's: the four-frame form of every family needs more than 64 VGPRs (NV12 79, planar 4:2:0 91, packed 4:2:2 71,
+// Bayer 72), and so does the two-frame form of the 4:2:0 families (68, 77); at or under 64 stay two frames of packed 4:2:2
+// and Bayer (60, 62) and one frame of the 4:2:0 families (58, 62).  Each family ships the form that was fastest INSIDE
+// p.run on an MI355X (1080p, 512 frames, two lanes), and a form above 64 only where it beat the best one at or under 64 by
+// more than the runs' range: per frame, 1 / 2 / 4 frames a thread, NV12 8.00 / 6.92 / 6.77 us, planar 8.56 / 7.50 / 7.57,
+// packed 4:2:2 7.50 / 6.30 / 6.05, Bayer 7.92 / 6.83 / 6.20 (ranges 0.02 - 0.06).  So four frames everywhere but planar
+// 4:2:0, which takes two.  DESIGN.md section 6n has the table; tests/test_warp_raw_profile_resources.py pins the counts.
+// (RAW_PROFILE_FPT = 1, 2 or 4 in the build's environment gives every family that form: tools/raw_profile_timing.py's
+// comparison.)
+static constexpr int raw_profile_fpt(int fmt)
+{
+#ifdef RAW_PROFILE_FPT
+    return RAW_PROFILE_FPT;
+#else
+    return (fmt & 15) == CBV_FMT_NV12 && (fmt & 0x20) ? 2 : 4; // planar 4:2:0 (YUV420P): two
+#endif
+}
+
+// the frames per thread of the many-frames form of a format as the caller names it (YV12 is launched as YUV420P)
+static int raw_profile_many(int fmt)
+{
+    return raw_profile_fpt(fmt == CBV_FMT_YV12 ? CBV_FMT_YUV420P : fmt);
+}
+
+// Frames per thread of the many-frames form of the YUV sources in another colour space than 0 without a profile
+// (k_warp_cs.hip, k_warp_lens_cs.hip): four, as their siblings take, but for planar 4:2:0, whose four-frame form needs 65 or 66
+// VGPRs once the constants are the launch's (63 with the compiler's: the multiplies no longer fold into 24-bit
+// multiply-adds) and so crosses the 64 of 8 waves per SIMD.  It takes two, as its family does with a profile.
+static constexpr int yuv_cs_fpt(int fmt) { return (fmt & 15) == CBV_FMT_NV12 && (fmt & 0x20) ? 2 : 4; }
+static int yuv_cs_many(int fmt) { return yuv_cs_fpt(fmt == CBV_FMT_YV12 ? CBV_FMT_YUV420P : fmt); }
 
 template <int N>
 using WarpInt = std::integral_constant<int, N>;

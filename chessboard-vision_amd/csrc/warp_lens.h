@@ -15,8 +15,9 @@ __global__ __launch_bounds__(256) void k_warp_lens(Src S, const LensBoard* __res
     const LensBoard& T = tab[e];
     if (e > 0 && ((int)blockIdx.x * 64 >= T.dw || (int)blockIdx.y * Src::ROWS >= T.dh)) return;
     if constexpr (Src::TABS) S.pt = T.ptabs; // the profile is the entry's: a workgroup stages its entry's table
-    warp_gather<Src, FPT, true>(S, WarpDst{T.Minv, T.dw, T.dh, T.bw0, T.rot180, T.dst + (size_t)s0 * T.frame_stride, T.stride, T.frame_stride},
-                                zero_word, zero_word2, batch, blockIdx.z - e * nz, &lens);
+    const WarpDst D = {T.Minv, T.dw, T.dh, T.bw0, T.rot180, T.dst + (size_t)s0 * T.frame_stride, T.stride, T.frame_stride};
+    if constexpr (Src::CS) warp_gather<Src, FPT, true>(S, D, zero_word, zero_word2, batch, blockIdx.z - e * nz, &lens, S.cs); // (a colour space other than 0)
+    else warp_gather<Src, FPT, true>(S, D, zero_word, zero_word2, batch, blockIdx.z - e * nz, &lens);
 }
 
 // One launch of source S over `ne` table entries: one frame per thread below batch 8, MANY from there on.

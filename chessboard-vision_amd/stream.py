@@ -817,14 +817,16 @@ class BoardPipeline(_BoardMethods):
     def frames_ptr(self):
         return self.ctx.lib.cbv_pipeline_frames_dev(self.h_)
 
-    def upload(self, slot, frame, fmt="bgr"):
+    def upload(self, slot, frame, fmt="bgr", colorspace="bt601"):
         """One frame into a slot, synchronous.  `fmt` "nv12" / "nv21" (one [h * 3 // 2, w] array or a (y, chroma) pair of
         possibly strided views), "yuv420p" / "yv12" (one contiguous [h * 3 // 2, w] array or the three planes in memory
         order, (y, u, v) / (y, v, u)) and "yuyv" / "yvyu" / "uyvy" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h,
         cbv_pipeline_upload_raw; "i420" is not a name, the format is "yuv420p"), and so are the 8-bit Bayer mosaics
         "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg" (one [h, w] array, named by the top-left 2 x 2 block:
         cv2's COLOR_BayerBG2BGR is "bayer_rggb"); in raw mode (`configure(enhance=False)` or `(enhance="profile", raw=True)` with a YUV or Bayer
-        `set_input_format`) the frame is stored as it is."""
+        `set_input_format`) the frame is stored as it is.  `colorspace`: of a YUV frame (`set_input_format`); a raw-mode
+        ring takes frames of its own format and colour space only."""
+        N.colorspace_bits(colorspace, fmt)
         if isinstance(fmt, str) and fmt.lower() == "mjpeg":  # one baseline JPEG stream (bytes or a uint8 array), decoded on the GPU
             a = np.frombuffer(frame, np.uint8) if isinstance(frame, (bytes, bytearray, memoryview)) else np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
             self.ctx.check(self.ctx.lib.cbv_pipeline_upload_jpeg(self.h_, slot, N.ptr(a), a.size))
@@ -834,12 +836,12 @@ class BoardPipeline(_BoardMethods):
             assert f.shape[:2] == (self.h, self.w)
             self.ctx.check(self.ctx.lib.cbv_pipeline_upload(self.h_, slot, N.ptr(f), f.strides[0]))
             return
-        raw, w, h, keep = N.raw_frame(frame, fmt)
+        raw, w, h, keep = N.raw_frame(frame, fmt, colorspace)
         if (h, w) != (self.h, self.w):
             raise ValueError("a %dx%d %s frame does not fit the pipeline's %dx%d frames" % (w, h, fmt, self.w, self.h))
         self.ctx.check(self.ctx.lib.cbv_pipeline_upload_raw(self.h_, slot, raw))
 
-    def set_input_format(self, fmt, slot_bytes=None, planes=False):
+    def set_input_format(self, fmt, slot_bytes=None, planes=False, colorspace="bt601"):
         """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12", "nv21", "yuv420p"
         (cv2's I420; "i420" itself is an unknown format), "yv12", "yuyv", "yvyu", "uyvy", or an 8-bit Bayer mosaic
         "bayer_rggb", "bayer_bggr", "bayer_grbg" or "bayer_gbrg" (w and h even and at least 4).  Raw frames cross PCIe as
@@ -850,20 +852,26 @@ class BoardPipeline(_BoardMethods):
         the GPU into the BGR frames (include/cbv.h, CBV_FMT_MJPEG).  `planes` (False, True = "444", "444", "422", "420" or
         "gray": the largest chroma sampling the streams may have) makes "mjpeg" a raw format: on a pipeline configured with
         `enhance=False` or `enhance="profile", raw=True` the decode stops at the planes, no BGR frame is written, and the warp
-        samples the planes with the same bytes as a result (include/cbv.h, cbv_pipeline_set_jpeg_planes)."""
+        samples the planes with the same bytes as a result (include/cbv.h, cbv_pipeline_set_jpeg_planes).
+        `colorspace` of a YUV format: "bt601" (default; cv2's BT.601 limited range: a UVC webcam's YUYV), "bt601-full" (JFIF:
+        phone cameras, full-range UVC modes), "bt709" (decoded video at 720p and above) or "bt709-full" (capture cards in
+        PC range).  It is stored with the ring's format (`input_colorspace`) and honoured wherever the ring's frames are
+        converted: `submit`, raw mode, `color_sweep`, attached boards, `set_lens`.  ValueError for an unknown name, and
+        for another colour space than "bt601" with a format that is not YUV."""
+        bits = N.colorspace_bits(colorspace, fmt)
         if isinstance(fmt, str) and fmt.lower() == "mjpeg":
             self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_planes(self.h_, N.jpeg_planes_id(planes)))
             if slot_bytes is not None:
                 self.ctx.check(self.ctx.lib.cbv_pipeline_set_jpeg_slot_bytes(self.h_, int(slot_bytes)))
             self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.FMT_MJPEG))
-            self.input_format = "mjpeg"
+            self.input_format, self.input_colorspace = "mjpeg", "bt601"
             return
         if slot_bytes is not None:
             raise ValueError("slot_bytes belongs to the \"mjpeg\" format")
         if N.jpeg_planes_id(planes):
             raise ValueError("planes belongs to the \"mjpeg\" format")
-        self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt)))
-        self.input_format = fmt.lower()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt) | bits))
+        self.input_format, self.input_colorspace = fmt.lower(), colorspace.lower()
 
     def host_ring(self):
         """Pinned host mirror of the frame ring as a numpy array: the capture side writes frames here, `submit` copies

@@ -103,3 +103,45 @@ def bayer_mosaic(bgr, fmt):
     for i, c in enumerate(block):
         out[i >> 1::2, i & 1::2] = bgr[i >> 1::2, i & 1::2, c]
     return out
+
+
+# Kr, Kb of the colour spaces a YUV frame can be in (_native.COLORSPACES; include/cbv.h, CBV_CS_*)
+YUV_KR_KB = {"bt601": (0.299, 0.114), "bt601-full": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt709-full": (0.2126, 0.0722)}
+
+
+def bgr_to_yuv(bgr, fmt, colorspace="bt601"):
+    """A plausible camera-native YUV frame of a BGR picture (even w and h), for examples, tools and tests: the float64
+    forward transform of the colour space's Kr / Kb and range (limited: Y in 16 .. 235, chroma in 16 .. 240; "-full": 0 ..
+    255), chroma averaged over a pixel's 2 x 2 block (4:2:0) or pair (4:2:2), in the layout of `fmt`: [h * 3 // 2, w] for
+    "nv12", "nv21", "yuv420p", "yv12", [h, w, 2] for "yuyv", "yvyu", "uyvy".  An input generator: what the library makes of
+    such a frame is defined by include/cbv.h, not by inverting this."""
+    kr, kb = YUV_KR_KB[colorspace]
+    b, g, r = (np.asarray(bgr, np.float64)[..., i] for i in range(3))
+    h, w = b.shape
+    if h % 2 or w % 2:
+        raise ValueError("an even width and height, got %dx%d" % (w, h))
+    y = kr * r + (1 - kr - kb) * g + kb * b
+    u, v = (b - y) / (2 * (1 - kb)), (r - y) / (2 * (1 - kr))
+    if colorspace.endswith("-full"):
+        u, v = 128 + u, 128 + v
+    else:
+        y, u, v = 16 + y * 219 / 255, 128 + u * 224 / 255, 128 + v * 224 / 255
+    to8 = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)  # noqa: E731
+    if fmt in ("nv12", "nv21", "yuv420p", "yv12"):
+        cu, cv = (to8(c.reshape(h // 2, 2, w // 2, 2).mean(axis=(1, 3))) for c in (u, v))
+        out = np.empty((h * 3 // 2, w), np.uint8)
+        out[:h] = to8(y)
+        first, second = (cu, cv) if fmt in ("nv12", "yuv420p") else (cv, cu)
+        if fmt in ("nv12", "nv21"):
+            out[h:, 0::2], out[h:, 1::2] = first, second
+        else:
+            out[h:] = np.concatenate([first.ravel(), second.ravel()]).reshape(h // 2, w)
+        return out
+    if fmt not in ("yuyv", "yvyu", "uyvy"):
+        raise ValueError("a YUV format, got %r" % (fmt,))
+    cu, cv = (to8(c.reshape(h, w // 2, 2).mean(axis=2)) for c in (u, v))
+    out = np.empty((h, w, 2), np.uint8)
+    yb, cb = (1, 0) if fmt == "uyvy" else (0, 1)
+    out[..., yb] = to8(y)
+    out[:, 0::2, cb], out[:, 1::2, cb] = (cv, cu) if fmt == "yvyu" else (cu, cv)
+    return out

@@ -522,6 +522,29 @@ CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out)
 #define CBV_FMT_YVYU    0x12
 #define CBV_FMT_UYVY    0x22
 
+/* The colour space of a YUV frame travels in its format id: CBV_CS_* bits OR-ed onto any of the seven YUV ids above, wherever
+ * a raw format id is taken (cbv_raw_frame::fmt of cbv_yuv_to_bgr, cbv_warp_color_profile_raw, cbv_warp_lens and
+ * cbv_pipeline_upload_raw; cbv_pipeline_set_input_format).  No bits = the arithmetic above, which is what most UVC webcams'
+ * YUYV needs.  The other three replace its constants and nothing else:
+ *     yy = max(0, Y - yoff) * CY, u = U - 128, v = V - 128, h = 1 << 19
+ *     B = clamp(yy + h + CUB * u, 0, (256 << 20) - 1) >> 20
+ *     G = clamp(yy + h + CVG * v + CUG * u, 0, (256 << 20) - 1) >> 20
+ *     R = clamp(yy + h + CVR * v, 0, (256 << 20) - 1) >> 20
+ *     bits                         matrix, range        yoff  CY       CUB      CUG      CVG      CVR
+ *     0                            BT.601 (cv2), limited  16  1220542  2116026  -409993  -852492  1673527
+ *     CBV_CS_FULL                  BT.601 (JFIF), full     0  1048576  1858077  -360853  -748826  1470104
+ *     CBV_CS_BT709                 BT.709, limited        16  1220945  2215014  -223607  -558796  1879825
+ *     CBV_CS_BT709 | CBV_CS_FULL   BT.709, full            0  1048576  1945738  -196424  -490864  1651297
+ * The last three rows are round(c * 2^20) of the exact coefficients (Kr, Kb = 0.299, 0.114 / 0.2126, 0.0722; luma scale
+ * 255 / 219 and chroma scale 255 / 224 for limited range, 1 for full).  Every sum stays inside signed 32 bits.  Chroma siting
+ * and upsampling are unchanged.  Decoded video at 720p and above is BT.709 limited; phone cameras and JFIF-like sources are
+ * BT.601 full.  Colour-space bits on CBV_FMT_BGR, a Bayer id or CBV_FMT_MJPEG (JFIF by definition) are CBV_ERR_ARG.  A
+ * pipeline in raw mode compares the whole id: an NV12 / BT.709 ring refuses an NV12 / BT.601 frame.  (The bits lie above
+ * 0x3FF: ids such as 0x121 and 0x104 were always refused as unassigned, and stay so.) */
+#define CBV_CS_FULL  0x400
+#define CBV_CS_BT709 0x800
+#define CBV_CS_MASK  0xC00
+
 /* 8-bit Bayer mosaics (machine-vision cameras, the raw mode of most sensors): one plane of h rows of w bytes, one byte and
  * one colour per pixel, a third of BGR's bytes.  The conversion is the bilinear demosaic of
  * cv2.cvtColor(raw, COLOR_Bayer??2BGR) on 8-bit data (not the _VNG or _EA variants); no white balance, gamma or colour

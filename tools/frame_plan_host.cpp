@@ -2,7 +2,7 @@
 // four configuration kinds x every input format class and planes mode, for one size and one set of Motion-JPEG settings.
 // Host code only: tests/test_frame_plan_host.py builds it with the host compiler under AddressSanitizer and UBSan.
 //
-//     frame_plan_host W H SLOT_BYTES ENTROPY PIECE_BYTES DEPTH     one line per cell
+//     frame_plan_host W H SLOT_BYTES ENTROPY PIECE_BYTES DEPTH [CS]  one line per cell (CS: the colour space of the YUV cells, 0 .. 3)
 //     frame_plan_host --piece-size MODE PIECE_BYTES [...]          what jpeg_piece_size makes of each pair
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,8 +25,8 @@ int main(int argc, char** argv)
         }
         return 0;
     }
-    if (argc != 7) {
-        fprintf(stderr, "usage: %s W H SLOT_BYTES ENTROPY PIECE_BYTES DEPTH | --piece-size MODE PIECE_BYTES [...]\n", argv[0]);
+    if (argc != 7 && argc != 8) {
+        fprintf(stderr, "usage: %s W H SLOT_BYTES ENTROPY PIECE_BYTES DEPTH [CS] | --piece-size MODE PIECE_BYTES [...]\n", argv[0]);
         return 2;
     }
     FrameSettings s;
@@ -43,6 +43,7 @@ int main(int argc, char** argv)
             for (s.planes = CBV_JPEG_PLANES_OFF; s.planes <= CBV_JPEG_PLANES_444; s.planes++) {
                 if (fmt != CBV_FMT_MJPEG && s.planes != CBV_JPEG_PLANES_OFF && s.planes != CBV_JPEG_PLANES_444) continue; // (there the mode is only stored)
                 s.fmt = fmt;
+                s.cs = argc == 8 && raw_fmt_yuv(fmt) ? atoi(argv[7]) : 0;
                 FramePlan p;
                 const int rc = frame_plan(s, &p, msg, sizeof(msg));
                 printf("%d %d %d ", s.kind, s.fmt, s.planes);
