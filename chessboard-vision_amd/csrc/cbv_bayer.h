@@ -1,5 +1,5 @@
 // One site of an 8-bit Bayer mosaic to BGR: cv2.cvtColor's bilinear COLOR_Bayer??2BGR (include/cbv.h), the ONE definition
-// behind k_ingest (whole frames) and k_warp_bayer (the four taps of a warped pixel), and which colour a site carries.
+// behind k_ingest (whole frames) and the warp of a mosaic (WarpRaw<FMT>, warp_gather.h: the four taps of a warped pixel), and which colour a site carries.
 #pragma once
 #include "cbv_device.h"
 

@@ -295,7 +295,7 @@ int ctx_set_profile(cbv_ctx* ctx, const cbv_color_profile* p)
     return CBV_OK;
 }
 
-// the tables of a profile that belongs to a pipeline or a call (k_warp_profile), never ctx->ptabs: the profile as
+// the tables of a profile that belongs to a pipeline or a call (the warp of a source with a profile), never ctx->ptabs: the profile as
 // ctx_set_profile reads it (flags as 0 / 1), null = disabled
 int profile_tabs_checked(cbv_ctx* ctx, const cbv_color_profile* p, ProfileTabs* out, const char* who)
 {

@@ -445,7 +445,8 @@ int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlane
 // ... and from there into a BGR device image
 int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
 
-// What the warp samples (k_warp.hip): the frames of a batch, frame 0's pointers.
+// What the warp samples: the frames of a batch, frame 0's pointers.  The launchers turn it into the typed source of the
+// kernels (warp_gather.h, warp_typed_*).
 struct JpegDesc;
 struct WarpSrc {
     enum Kind { BGR, PROFILE, YUV, BAYER, JPEG } kind;
@@ -464,7 +465,7 @@ struct WarpSrc {
     bool raw() const { return kind == YUV || kind == BAYER; }
     bool profiled() const { return kind == PROFILE || ((raw() || kind == JPEG) && ptabs); } // the profile kernels' tiling (WP_ROWS rows a workgroup)
 };
-// BGR frames (k_warp), the taps through `norm`
+// BGR frames (WarpBgr), the taps through `norm`
 static inline WarpSrc warp_src_bgr(const u8* src, Geom g, NormSrc norm)
 {
     WarpSrc s = {};
@@ -475,10 +476,10 @@ static inline WarpSrc warp_src_bgr(const u8* src, Geom g, NormSrc norm)
     s.r.fmt = CBV_FMT_BGR;
     return s;
 }
-// BGR frames with the colour profile applied to the taps (k_warp_profile): apply_color_profile followed by the warp, byte
+// BGR frames with the colour profile applied to the taps (WarpProfile): apply_color_profile followed by the warp, byte
 // for byte, with no converted frame in between, for `np` profiles at once.  ptabs[np] = device tables (build_profile_tabs),
 // the caller's, not ctx->ptabs; profile p writes its `batch` frames at dst + p * dst_profile_stride; a table with
-// enabled = 0 is the plain warp.  np x groups of frames (four frames a group from batch 8 on) <= 65535.  The multi-board
+// enabled = 0 is the plain warp.  np x groups of frames (warp_many frames a group from batch 8 on) <= 65535.  The multi-board
 // launch reads the boards' own tables (BoardDev::ptabs) instead of `ptabs`.  Counted as CBV_K_WARP: the enumeration of profile
 // ids is closed.
 static inline WarpSrc warp_src_profile(const u8* src, Geom g, const ProfileTabs* ptabs, int np = 1, size_t dst_profile_stride = 0)
@@ -490,7 +491,7 @@ static inline WarpSrc warp_src_profile(const u8* src, Geom g, const ProfileTabs*
     s.dst_profile_stride = dst_profile_stride;
     return s;
 }
-// Raw frames (k_warp_yuv; the Bayer family: k_warp_bayer): the output of launch_ingest followed by the warp without a byte
+// Raw frames (WarpRaw<FMT>, YUV layouts and mosaics): the output of launch_ingest followed by the warp without a byte
 // map, byte for byte, with no BGR frame in between; g = the frames' width and height.  YUV: interior pixels load both taps
 // of a row at once: 4 bytes at the even column of an NV12 / NV21 chroma row, 8 bytes at the first tap's pair of a packed
 // 4:2:2 row, 2 bytes at column sx >> 1 of each planar chroma row, which at sx = w - 2 reach 2 / 4 / 1 bytes past the row's
@@ -540,7 +541,8 @@ static inline WarpSrc warp_src_jpeg(const u8* planes, size_t plane_stride, const
     s.dst_profile_stride = dst_profile_stride;
     return s;
 }
-// `batch` frames of `src` onto one dw x dh board: four frames per thread from batch 8 on, one thread per pixel and frame below
+// `batch` frames of `src` onto one dw x dh board (k_warp_one): from batch 8 on the source's many-frames form (warp_many,
+// warp_gather.h: four frames per thread for most), one thread per pixel and frame below
 int launch_warp(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
                 int batch, u32* zero_word = nullptr, u32* zero_word2 = nullptr);
 
@@ -750,14 +752,14 @@ struct BoardDev {
     const float* csd;
     ChangeBlur cb;
     // the board's colour profile (cbv_pipeline_set_profile): its device table in the profile modes (enabled = 0 in it: the
-    // board's taps stay as they are), null otherwise; read by k_warp_profile_mb and k_warp_raw_profile_mb
+    // board's taps stay as they are), null otherwise; read by k_warp_boards of the sources with a profile
     const ProfileTabs* ptabs;
 };
 ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
 // per-pass HoughCfg of a board (layout and maxc as launch_hough / launch_hough_second set them); returns the LDS bytes
 // of each pass, 0 when the squares cannot run (the single-board launchers' checks)
 void hough_board_cfgs(HoughCfg base, HoughCfg out[2], size_t lds[2]);
-// one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0
+// one launch each for `nb` boards; `tab` = device table, `s0` = slot of the chunk's (run's) frame 0 (the warp: k_warp_boards)
 int launch_warp_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
 // what launch_warp / launch_warp_mb hand a raw source with a profile (warp_src_raw_profile) to: k_warp_raw_profile.hip
 int launch_warp_raw_profile(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride,
@@ -773,8 +775,8 @@ int launch_warp_jpeg(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int
 int launch_warp_jpeg_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
 // The warp through the camera's lens model (lens_core.h): k_warp_lens.hip, and k_warp_lens_profile.hip for the raw and JPEG
 // sources with a profile.  Every source kind has the table-driven form only: entry e of `tab` (device, ne entries) is one
-// destination of the launch, a board of a pipeline or a profile of a colour sweep, and a single-frame call passes a
-// table of one.  blockIdx.z = entry * nz + group of frames; the grid covers max_dw x max_dh.  Frame f of the launch goes
+// destination of the launch (k_warp_lens), a board of a pipeline or a profile of a colour sweep, and a single-frame call
+// passes a table of one.  blockIdx.z = entry * nz + group of frames; the grid covers max_dw x max_dh.  Frame f of the launch goes
 // to dst + (s0 + f) * frame_stride.  A profiled source reads the entries' own tables (ptabs), never WarpSrc::ptabs, which
 // only says that the source is profiled.
 struct LensBoard {
@@ -797,6 +799,7 @@ static inline LensBoard lens_board(const double* Minv9, int dw, int dh, int rot1
 }
 int launch_warp_lens(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
                      u32* zero_word, u32* zero_word2);
+// what launch_warp_lens hands a raw or JPEG source with a profile to: k_warp_lens_profile.hip
 int launch_warp_lens_profile(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
                              u32* zero_word, u32* zero_word2);
 // what launch_warp_lens hands a YUV source whose colour space is not 0 to: k_warp_lens_cs.hip

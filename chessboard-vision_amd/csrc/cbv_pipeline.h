@@ -67,8 +67,8 @@ struct Pipe {
     bool keep_enhanced = false;
     bool skip_enhance = false; // cfg.skip_enhance: the warp samples the frames as they are, no enhancement scratch exists
     // cfg.skip_enhance == CBV_SKIP_ENHANCE_PROFILE or CBV_SKIP_ENHANCE_PROFILE_RAW: the warp samples the frames and, when a
-    // board has an enabled profile (profile_on), applies each board's colour profile to its taps (k_warp_profile,
-    // k_warp_raw_profile) from the boards' own tables, Board::d_ptabs.  profile_raw: the latter mode
+    // board has an enabled profile (profile_on), applies each board's colour profile to its taps (WarpProfile,
+    // WarpRawProfile<FMT>: warp_gather.h) from the boards' own tables, Board::d_ptabs.  profile_raw: the latter mode
     bool profile_only = false, profile_on = false, profile_raw = false;
     int chunk = 8;
     u8* frames = nullptr; // the BGR frame ring; null where plan.bgr_ring says so

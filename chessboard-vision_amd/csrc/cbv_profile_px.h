@@ -1,4 +1,4 @@
-// apply_color_profile for one pixel, shared by k_color_lab_hist (k_enhance.hip) and k_warp_profile (k_warp.hip).
+// apply_color_profile for one pixel, shared by k_color_lab_hist (k_enhance.hip) and the warp of the sources with a profile (warp_gather.h).
 #pragma once
 #include "cbv_device.h"
 

@@ -1,5 +1,5 @@
 // One YUV pixel to BGR: cv2.cvtColor's COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12 / _YUY2 / _YVYU / _UYVY arithmetic on 8-bit
-// data (include/cbv.h), the ONE definition behind k_ingest (whole frames) and k_warp_yuv (the four taps of a warped pixel),
+// data (include/cbv.h), the ONE definition behind k_ingest (whole frames) and the warp of a YUV frame (WarpRaw<FMT>, warp_gather.h: the four taps of a warped pixel),
 // and where the bytes of each layout lie.  That is colour space 0, BT.601 limited range; the other three (BT.601 full range,
 // BT.709 limited and full range) are the same arithmetic with other constants: the second half of this file.
 #pragma once

@@ -1,6 +1,8 @@
-// The warp's one gather (warp_gather), its sources and what the launchers share, for the translation units that hold
-// warp kernels: k_warp.hip, k_warp_raw_profile.hip, k_warp_jpeg.hip, the lens forms' k_warp_lens.hip and
-// k_warp_lens_profile.hip, and k_warp_cs.hip and k_warp_lens_cs.hip (YUV frames in a colour space other than 0).  Private.
+// The warp, for the translation units that hold its kernels (k_warp.hip, k_warp_raw_profile.hip, k_warp_jpeg.hip, k_warp_cs.hip
+// and, through warp_lens.h, k_warp_lens.hip, k_warp_lens_profile.hip, k_warp_lens_cs.hip): the sources, the one gather
+// (warp_gather), the kernel templates k_warp_one and k_warp_boards (k_warp_lens: warp_lens.h), the frames per thread of every
+// source's many-frames form (warp_many), the dispatch from a WarpSrc to the typed source (warp_typed_*) and the launch
+// templates.  A unit is its exported launchers: dispatch the source, call the launch template.  Private.
 #pragma once
 #include "cbv_bayer.h"
 #include "cbv_profile_px.h"
@@ -171,8 +173,7 @@ struct WarpRawProfile : WarpRaw<FMT_> {
 
 // YUV frames in another colour space than 0 (include/cbv.h, CBV_CS_*; k_warp_cs.hip and k_warp_lens_cs.hip): the loads of
 // WarpRaw, the taps converted with the six constants the source carries (cbv_yuv.h, YuvCs), which are uniform and stay in
-// scalar registers.  Their kernels hand `cs` to warp_gather as its last argument (CS tells the one kernel template of the lens
-// forms to).
+// scalar registers.  CS tells the kernels to hand `cs` to warp_gather as its last argument (warp_gather_of).
 template <int FMT_>
 struct WarpRawCs : WarpRaw<FMT_> {
     static constexpr bool CS = true;
@@ -656,96 +657,130 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// The kernels: per source one for a single board, which takes the matrix by value, and one (_mb) for every board of a
-// pipeline in one launch: blockIdx.z = board * nz + group of frames; the grid covers the largest board and the blocks
-// outside a smaller one leave at once (what is staged for the shared frames is the same for every board).
+// The kernels: one template per launch shape, whatever the source, which travels by value as the first argument.
+//   k_warp_one     one destination, the matrix by value (launch_warp and what it hands over to)
+//   k_warp_boards  every board of a pipeline in one launch, from the BoardDev table (launch_warp_mb ...)
+//   k_warp_lens    the table-driven lens form (warp_lens.h), which calls warp_gather itself
 // ---------------------------------------------------------------------------
-// where a multi-board launch writes board T; s0 = the slot of the chunk's frame 0
-__device__ __forceinline__ WarpDst warp_board_dst(const BoardDev& T, int s0)
+// The gather of source S onto the destination that k_warp_one or k_warp_boards names; a source in another colour space than 0
+// hands its constants on as the gather's trailing pack.  `dst` is restrict here because the source's pointers, inside a struct, cannot be: that
+// no store to the destination changes what the source's pointers read is what lets the compiler keep the uniform reads of a
+// source (a JPEG frame's descriptor) in scalar loads where the destination comes out of a table.
+template <class Src, int FPT, bool LENS = false>
+__device__ __forceinline__ void warp_gather_of(Src S, const double* M, int dw, int dh, int bw0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                               size_t dst_frame_stride, u32* __restrict__ zero_word, u32* __restrict__ zero_word2, int batch, int bz,
+                                               const LensDev* lens = nullptr)
 {
-    return WarpDst{T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride};
+    const WarpDst D = {M, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride};
+    if constexpr (Src::CS) warp_gather<Src, FPT, LENS>(S, D, zero_word, zero_word2, batch, bz, lens, S.cs);
+    else warp_gather<Src, FPT, LENS>(S, D, zero_word, zero_word2, batch, bz, lens);
+}
+
+// blockIdx.z = the group of frames.  A source with a profile (Src::TABS): blockIdx.z = profile * nz + group of frames;
+// profile p stages S.pt[p] and writes its frames dst_profile_stride bytes behind profile p - 1's
+template <class Src, int FPT>
+__global__ __launch_bounds__(256) void k_warp_one(Src S, WarpM M, int dw, int dh, int bw0, int rot180, u8* __restrict__ dst, int dst_stride,
+                                                   size_t dst_frame_stride, size_t dst_profile_stride, int nz, u32* __restrict__ zero_word,
+                                                   u32* __restrict__ zero_word2, int batch)
+{
+    int bz = blockIdx.z;
+    if constexpr (Src::TABS) {
+        const int pi = blockIdx.z / nz;
+        S.pt += pi;
+        dst += (size_t)pi * dst_profile_stride;
+        bz -= pi * nz;
+    }
+    warp_gather_of<Src, FPT>(S, M.m, dw, dh, bw0, rot180, dst, dst_stride, dst_frame_stride, zero_word, zero_word2, batch, bz);
+}
+
+// blockIdx.z = board * nz + group of frames; the grid covers the largest board and the blocks outside a smaller one leave
+// at once (what is staged for the shared frames is the same for every board).  A profile is the board's: a workgroup stages
+// its board's table.  s0 = the slot of the chunk's frame 0
+template <class Src, int FPT>
+__global__ __launch_bounds__(256) void k_warp_boards(Src S, const BoardDev* __restrict__ tab, int nz, int s0, u32* __restrict__ zero_word,
+                                                      u32* __restrict__ zero_word2, int batch)
+{
+    const int b = blockIdx.z / nz;
+    const BoardDev& T = tab[b];
+    if (b > 0 && ((int)blockIdx.x * 64 >= T.S || (int)blockIdx.y * Src::ROWS >= T.S)) return;
+    if constexpr (Src::TABS) S.pt = T.ptabs;
+    warp_gather_of<Src, FPT>(S, T.Minv, T.S, T.S, T.bw0, T.rot180, T.warped + (size_t)s0 * T.warped_stride, T.S * 3, T.warped_stride, zero_word, zero_word2,
+                             batch, blockIdx.z - b * nz);
 }
 
 // ---------------------------------------------------------------------------
-// The launchers.  Batched launches take four frames per thread (eight: 13 % fewer instructions again, no change on the
-// path); a launch of a frame or two keeps one thread per pixel and frame.
+// The frames per thread of the many-frames form (batch >= 8) of every source; a launch of fewer frames keeps one thread
+// per pixel and frame.  Four (eight: 13 % fewer instructions again, no change on the path), but for:
+//
+// The raw sources with a profile (k_warp_raw_profile.hip, and k_warp_cs.hip, whose forms take what their siblings take),
+// per family.  The profile's registers come on top of the conversion's: the four-frame form of every family needs more
+// than 64 VGPRs (NV12 79, planar 4:2:0 91, packed 4:2:2 71, Bayer 72), and so does the two-frame form of the 4:2:0
+// families (68, 77); at or under 64 stay two frames of packed 4:2:2 and Bayer (60, 62) and one frame of the 4:2:0 families
+// (58, 62).  Each family ships the form that was fastest INSIDE p.run on an MI355X (1080p, 512 frames, two lanes), and a
+// form above 64 only where it beat the best one at or under 64 by more than the runs' range: per frame, 1 / 2 / 4 frames a
+// thread, NV12 8.00 / 6.92 / 6.77 us, planar 4:2:0 8.56 / 7.50 / 7.57, packed 4:2:2 7.50 / 6.30 / 6.05, Bayer 7.92 / 6.83 /
+// 6.20 (ranges 0.02 - 0.06).  So four frames everywhere but planar 4:2:0, which takes two.  DESIGN.md section 6n has the
+// table; tests/test_warp_raw_profile_resources.py pins the counts.  (RAW_PROFILE_FPT = 1, 2 or 4 in the build's environment
+// gives every family that form: tools/raw_profile_timing.py's comparison.)
+//
+// The YUV sources in another colour space than 0 without a profile (k_warp_cs.hip, k_warp_lens_cs.hip): planar 4:2:0 takes
+// two, as its family does with a profile.  Its four-frame form needs 65 or 66 VGPRs once the constants are the launch's (63
+// with the compiler's: the multiplies no longer fold into 24-bit multiply-adds) and so crosses the 64 of 8 waves per SIMD.
+//
+// JPEG planes with a profile (k_warp_jpeg.hip): two.  The plain kernels need 44 VGPRs at one frame and 83 at four; with the
+// profile's registers on top 70 at one frame and 93 at two, as the planar 4:2:0 family with a profile, whose loads these
+// resemble.  The forms were not timed against each other; tests/test_warp_jpeg_resources.py pins
+// the counts.
+//
+// Under a lens (k_warp_lens_profile.hip, k_warp_lens_cs.hip) every raw or JPEG source with a profile: two.  The lens's
+// doubles come on top of the profile's registers and the conversion's, and two is what planar 4:2:0 and the JPEG planes
+// take lens-free; the lens forms were not timed against each other.
 // ---------------------------------------------------------------------------
-// groups of frames of a launch: `many` frames a group from batch 8 on (four, but for the raw sources with a profile, whose
-// kernels choose per family: raw_profile_fpt)
-static int warp_groups(int batch, int many = 4)
+template <class Src, bool LENS = false>
+constexpr int warp_many()
 {
-    const int fpt = batch >= 8 ? many : 1;
-    return (batch + fpt - 1) / fpt;
-}
-
-// Frames per thread of the many-frames form (batch >= 8) of the raw sources with a profile (k_warp_raw_profile.hip, and
-// k_warp_cs.hip, whose forms take what their siblings take), per family.  The profile's registers come on top of the
-// conversion's: the four-frame form of every family needs more than 64 VGPRs (NV12 79, planar 4:2:0 91, packed 4:2:2 71,
-// Bayer 72), and so does the two-frame form of the 4:2:0 families (68, 77); at or under 64 stay two frames of packed 4:2:2
-// and Bayer (60, 62) and one frame of the 4:2:0 families (58, 62).  Each family ships the form that was fastest INSIDE
-// p.run on an MI355X (1080p, 512 frames, two lanes), and a form above 64 only where it beat the best one at or under 64 by
-// more than the runs' range: per frame, 1 / 2 / 4 frames a thread, NV12 8.00 / 6.92 / 6.77 us, planar 8.56 / 7.50 / 7.57,
-// packed 4:2:2 7.50 / 6.30 / 6.05, Bayer 7.92 / 6.83 / 6.20 (ranges 0.02 - 0.06).  So four frames everywhere but planar
-// 4:2:0, which takes two.  DESIGN.md section 6n has the table; tests/test_warp_raw_profile_resources.py pins the counts.
-// (RAW_PROFILE_FPT = 1, 2 or 4 in the build's environment gives every family that form: tools/raw_profile_timing.py's
-// comparison.)
-static constexpr int raw_profile_fpt(int fmt)
-{
+    constexpr bool RAW = Src::KIND == WARP_YUV || Src::KIND == WARP_BAYER, JPEG = Src::KIND == WARP_JPEG;
+    constexpr bool PLANAR420 = Src::KIND == WARP_YUV && (Src::FMT & 15) == CBV_FMT_NV12 && (Src::FMT & 0x20); // YUV420P
+    if ((RAW || JPEG) && Src::TABS && LENS) return 2;
+    if (JPEG) return Src::TABS ? 2 : 4;
 #ifdef RAW_PROFILE_FPT
-    return RAW_PROFILE_FPT;
-#else
-    return (fmt & 15) == CBV_FMT_NV12 && (fmt & 0x20) ? 2 : 4; // planar 4:2:0 (YUV420P): two
+    if (RAW && Src::TABS) return RAW_PROFILE_FPT;
 #endif
+    if (RAW && (Src::TABS || Src::CS)) return PLANAR420 ? 2 : 4;
+    return 4;
 }
 
-// the frames per thread of the many-frames form of a format as the caller names it (YV12 is launched as YUV420P)
-static int raw_profile_many(int fmt)
-{
-    return raw_profile_fpt(fmt == CBV_FMT_YV12 ? CBV_FMT_YUV420P : fmt);
-}
-
-// Frames per thread of the many-frames form of the YUV sources in another colour space than 0 without a profile
-// (k_warp_cs.hip, k_warp_lens_cs.hip): four, as their siblings take, but for planar 4:2:0, whose four-frame form needs 65 or 66
-// VGPRs once the constants are the launch's (63 with the compiler's: the multiplies no longer fold into 24-bit
-// multiply-adds) and so crosses the 64 of 8 waves per SIMD.  It takes two, as its family does with a profile.
-static constexpr int yuv_cs_fpt(int fmt) { return (fmt & 15) == CBV_FMT_NV12 && (fmt & 0x20) ? 2 : 4; }
-static int yuv_cs_many(int fmt) { return yuv_cs_fpt(fmt == CBV_FMT_YV12 ? CBV_FMT_YUV420P : fmt); }
-
+// ---------------------------------------------------------------------------
+// From a WarpSrc to the typed source: per family of sources one function that makes the family's refusals and calls
+// f(S) with the source struct, which returns the launch's code.  A unit calls its family's from its lens-free launchers
+// and from its lens launcher alike, and instantiates what f does for every source of the family, nothing else.
+// ---------------------------------------------------------------------------
 template <int N>
 using WarpInt = std::integral_constant<int, N>;
 
-// launch(fmt, fpt) with the compile-time forms of a raw format id and of the frames per thread of `batch` frames: 1, or 4
-// for the many-frames form (CBV_FMT_BGR: the BGR sources, whose kernels have no format parameter)
+// f(fmt) with the compile-time form of the id of a raw format that has passed check_raw_format
 template <class F>
-static void warp_dispatch(int fmt, int batch, F&& launch)
+static int warp_raw_fmt(int fmt, F&& f)
 {
-    auto with_fmt = [&](auto f) {
-        if (batch >= 8) launch(f, WarpInt<4>());
-        else launch(f, WarpInt<1>());
-    };
     switch (fmt) {
-    case CBV_FMT_BGR: return with_fmt(WarpInt<CBV_FMT_BGR>());
-    case CBV_FMT_NV12: return with_fmt(WarpInt<CBV_FMT_NV12>());
-    case CBV_FMT_NV21: return with_fmt(WarpInt<CBV_FMT_NV21>());
-    case CBV_FMT_YUYV: return with_fmt(WarpInt<CBV_FMT_YUYV>());
-    case CBV_FMT_YVYU: return with_fmt(WarpInt<CBV_FMT_YVYU>());
-    case CBV_FMT_UYVY: return with_fmt(WarpInt<CBV_FMT_UYVY>());
-    case CBV_FMT_BAYER_RGGB: return with_fmt(WarpInt<CBV_FMT_BAYER_RGGB>());
-    case CBV_FMT_BAYER_BGGR: return with_fmt(WarpInt<CBV_FMT_BAYER_BGGR>());
-    case CBV_FMT_BAYER_GRBG: return with_fmt(WarpInt<CBV_FMT_BAYER_GRBG>());
-    case CBV_FMT_BAYER_GBRG: return with_fmt(WarpInt<CBV_FMT_BAYER_GBRG>());
-    default: return with_fmt(WarpInt<CBV_FMT_YUV420P>());
+    case CBV_FMT_NV12: return f(WarpInt<CBV_FMT_NV12>());
+    case CBV_FMT_NV21: return f(WarpInt<CBV_FMT_NV21>());
+    case CBV_FMT_YUYV: return f(WarpInt<CBV_FMT_YUYV>());
+    case CBV_FMT_YVYU: return f(WarpInt<CBV_FMT_YVYU>());
+    case CBV_FMT_UYVY: return f(WarpInt<CBV_FMT_UYVY>());
+    case CBV_FMT_BAYER_RGGB: return f(WarpInt<CBV_FMT_BAYER_RGGB>());
+    case CBV_FMT_BAYER_BGGR: return f(WarpInt<CBV_FMT_BAYER_BGGR>());
+    case CBV_FMT_BAYER_GRBG: return f(WarpInt<CBV_FMT_BAYER_GRBG>());
+    case CBV_FMT_BAYER_GBRG: return f(WarpInt<CBV_FMT_BAYER_GBRG>());
+    default: return f(WarpInt<CBV_FMT_YUV420P>());
     }
 }
 
-// What both launchers do around their kernels: the refusals of the source (raw planes: what launch_ingest asks of them; YV12
-// leaves as YUV420P), the groups of frames, the grid of a dw x dh destination with nz * zmul layers, the profiling bracket.
-// launch(fmt, fpt, grid, nz) issues the kernel of the source's kind; `many` = the frames per thread of its many-frames form.
-// the refusals of a raw source (what launch_ingest asks of the planes), and YV12 made YUV420P; other sources pass
+// the refusals of a raw source (what launch_ingest asks of the planes), and YV12 made YUV420P
 static int warp_raw_checked(cbv_ctx* ctx, WarpSrc* s, int batch)
 {
-    if (!s->raw()) return CBV_OK;
     const char* what = s->kind == WarpSrc::BAYER ? "launch_warp_bayer" : "launch_warp_yuv";
+    if (!s->raw()) return cbv_fail(ctx, CBV_ERR_ARG, "%s: not a raw source", what);
     RC(check_raw_format(ctx, s->r.fmt, s->g.w, s->g.h, what));
     // (warp_src_raw takes the kind from the format: only a WarpSrc filled by hand can fail this)
     if (s->kind == WarpSrc::BAYER && !raw_fmt_bayer(s->r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a Bayer format", what, s->r.fmt);
@@ -756,16 +791,122 @@ static int warp_raw_checked(cbv_ctx* ctx, WarpSrc* s, int batch)
     return CBV_OK;
 }
 
-template <class F>
-static int warp_launch(cbv_ctx* ctx, WarpSrc* s, int dw, int dh, int zmul, int batch, F&& launch, int many = 4)
+// (a mosaic has one plane)
+template <int FMT>
+static WarpRaw<FMT> warp_raw_of(const WarpSrc& s)
 {
+    const bool bayer = raw_fmt_bayer(FMT);
+    return WarpRaw<FMT>{s.planes.p[0], bayer ? nullptr : s.planes.p[1], bayer ? nullptr : s.planes.p[2], s.r, s.g.w, s.g.h};
+}
+
+// BGR frames (both byte-map forms), BGR frames through the profile, raw frames without one: k_warp.hip, k_warp_lens.hip
+template <class F>
+static int warp_typed_plain(cbv_ctx* ctx, WarpSrc* s, int batch, F&& f)
+{
+    if (s->kind == WarpSrc::PROFILE) return f(WarpProfile{s->bgr, s->g, ctx->tabs, s->ptabs});
+    if (s->kind == WarpSrc::BGR) {
+        if (s->norm.minmax) return f(WarpBgr<true>{s->bgr, s->g, nullptr, s->norm.minmax, s->norm.mm_stride});
+        return f(WarpBgr<false>{s->bgr, s->g, s->norm.lut, nullptr, 0});
+    }
     RC(warp_raw_checked(ctx, s, batch));
-    const int nz = warp_groups(batch, many), rows = s->profiled() ? WP_ROWS : 4;
-    const dim3 grid((dw + 63) / 64, (dh + rows - 1) / rows, nz * zmul);
-    const int prof = s->raw() ? CBV_K_WARP_YUV : CBV_K_WARP;
+    return warp_raw_fmt(s->r.fmt, [&](auto fmt) { return f(warp_raw_of<decltype(fmt)::value>(*s)); });
+}
+
+// raw frames with a profile: k_warp_raw_profile.hip, k_warp_lens_profile.hip
+template <class F>
+static int warp_typed_raw_profile(cbv_ctx* ctx, WarpSrc* s, int batch, const char* who, F&& f)
+{
+    if (!s->raw() || !s->ptabs) return cbv_fail(ctx, CBV_ERR_ARG, "%s: not a raw source with a profile", who);
+    RC(warp_raw_checked(ctx, s, batch));
+    return warp_raw_fmt(s->r.fmt, [&](auto fmt) {
+        constexpr int FMT = decltype(fmt)::value;
+        return f(WarpRawProfile<FMT>{warp_raw_of<FMT>(*s), ctx->tabs, s->ptabs});
+    });
+}
+
+// YUV frames in colour space 1 to 3, with a profile or without: k_warp_cs.hip, k_warp_lens_cs.hip
+template <class F>
+static int warp_typed_cs(cbv_ctx* ctx, WarpSrc* s, int batch, const char* who, F&& f)
+{
+    if (s->kind != WarpSrc::YUV || s->cs < 1 || s->cs > 3) return cbv_fail(ctx, CBV_ERR_ARG, "%s: not a YUV source in colour space 1 to 3 (%d)", who, s->cs);
+    RC(warp_raw_checked(ctx, s, batch));
+    const YuvCs cs = kYuvCs[s->cs];
+    return warp_raw_fmt(s->r.fmt, [&](auto fmt) -> int {
+        constexpr int FMT = decltype(fmt)::value;
+        if constexpr (raw_fmt_yuv(FMT)) {
+            if (s->ptabs) return f(WarpRawProfileCs<FMT>{{warp_raw_of<FMT>(*s), ctx->tabs, s->ptabs}, cs});
+            return f(WarpRawCs<FMT>{warp_raw_of<FMT>(*s), cs});
+        } else return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a YUV format", who, s->r.fmt);
+    });
+}
+
+// The decoded planes of JPEG frames, PROFILE: with a profile.  Unlike the three above this one decides at compile time, and
+// its callers write `s.ptabs ? <true> : <false>` where they want both: k_warp_jpeg.hip holds both sources, but the lens
+// forms are split over k_warp_lens.hip (WarpJpeg) and k_warp_lens_profile.hip (WarpJpegProfile), and a dispatch that chose
+// at run time would instantiate both in each, which the units' exact kernel lists forbid.  (const WarpSrc&: nothing to
+// canonicalise, where the raw families rewrite YV12's planes.)
+template <bool PROFILE, class F>
+static int warp_typed_jpeg(cbv_ctx* ctx, const WarpSrc& s, const char* who, F&& f)
+{
+    if (s.kind != WarpSrc::JPEG || !s.jpeg_planes || !s.jpeg_descs || (s.jpeg_plane_stride & 7) || s.g.w < 1 || s.g.h < 1)
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: not a source of JPEG planes", who);
+    const WarpJpeg J = {s.jpeg_planes, s.jpeg_plane_stride, s.jpeg_descs, s.g.w, s.g.h};
+    if constexpr (PROFILE) return f(WarpJpegProfile{J, ctx->tabs, s.ptabs});
+    else return f(J);
+}
+
+// ---------------------------------------------------------------------------
+// The launches: one template per kernel template.  MANY = the frames per thread of the many-frames form.
+// ---------------------------------------------------------------------------
+// What every launch does around its kernel: the groups of frames (MANY frames a group from batch 8 on, one below), the
+// refusal of more than 65535 layers, the grid of a dw x dh destination with `zmul` layers per group, the profiling bracket.
+// launch(fpt, grid, nz) issues the kernel with fpt's frames per thread; `layers` names what zmul counts, for the message.
+template <class Src, int MANY, class L>
+static int warp_launch_grid(cbv_ctx* ctx, const char* who, const char* layers, int dw, int dh, int zmul, int batch, L&& launch)
+{
+    if (batch <= 0 || dw < 1 || dh < 1 || zmul < 1) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad batch or destination", who);
+    const int fpt = batch >= 8 ? MANY : 1, nz = (batch + fpt - 1) / fpt;
+    if ((long long)nz * zmul > 65535) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %d %s x %d frames do not fit a launch", who, zmul, layers, batch);
+    const dim3 grid((dw + 63) / 64, (dh + Src::ROWS - 1) / Src::ROWS, nz * zmul);
+    constexpr int prof = Src::FMT == CBV_FMT_BGR ? CBV_K_WARP : CBV_K_WARP_YUV;
     prof_begin(ctx, prof);
-    warp_dispatch(s->raw() ? s->r.fmt : CBV_FMT_BGR, batch, [&](auto fmt, auto fpt) { launch(fmt, fpt, grid, nz); });
+    if (batch >= 8) launch(WarpInt<MANY>(), grid, nz);
+    else launch(WarpInt<1>(), grid, nz);
     prof_end(ctx, prof);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
+}
+
+// where launch_warp and its kin write: one dw x dh board; np profiles of a source with a profile, dst_profile_stride apart
+struct WarpOneTo {
+    const double* Minv9;
+    int dw, dh, rot180;
+    u8* dst;
+    int stride;
+    size_t frame_stride;
+    int np;
+    size_t profile_stride;
+};
+
+template <class Src, int MANY = warp_many<Src>()>
+static int warp_launch_one(cbv_ctx* ctx, const char* who, const Src& S, const WarpOneTo& to, int batch, u32* zero_word, u32* zero_word2)
+{
+    WarpM M;
+    for (int i = 0; i < 9; i++) M.m[i] = to.Minv9[i];
+    int bw0, bh0;
+    warp_block_shape(to.dw, to.dh, &bw0, &bh0);
+    return warp_launch_grid<Src, MANY>(ctx, who, "profiles", to.dw, to.dh, Src::TABS ? to.np : 1, batch, [&](auto fpt, dim3 grid, int nz) {
+        hipLaunchKernelGGL((k_warp_one<Src, decltype(fpt)::value>), grid, dim3(256), 0, ctx->stream, S, M, to.dw, to.dh, bw0, to.rot180, to.dst, to.stride,
+                           to.frame_stride, to.profile_stride, nz, zero_word, zero_word2, batch);
+    });
+}
+
+// nb boards of at most maxS x maxS
+template <class Src, int MANY = warp_many<Src>()>
+static int warp_launch_boards(cbv_ctx* ctx, const char* who, const Src& S, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word,
+                              u32* zero_word2)
+{
+    return warp_launch_grid<Src, MANY>(ctx, who, "boards", maxS, maxS, nb, batch, [&](auto fpt, dim3 grid, int nz) {
+        hipLaunchKernelGGL((k_warp_boards<Src, decltype(fpt)::value>), grid, dim3(256), 0, ctx->stream, S, tab, nz, s0, zero_word, zero_word2, batch);
+    });
 }

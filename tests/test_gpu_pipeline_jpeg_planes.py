@@ -367,3 +367,55 @@ def test_a_slot_rewritten_while_a_run_is_in_flight(gpu_ctx):
     assert [p.download(2, i).tobytes() for i in range(n)] == want_new, "the next run did not see the new frames"
     assert np.array_equal(p.download(0, 0), bgr[10]) and np.array_equal(p.download(0, 4), bgr[11]) and np.array_equal(p.download(0, 3), bgr[3])
     p.close()
+
+
+@functools.lru_cache(maxsize=None)
+def small_game():
+    """13 frames of the synthetic scene at 322 x 242 (no multiple of an MCU) as JPEG streams, the samplings mixed"""
+    from chessboard_vision_amd.stream import BoardPipeline
+    w, h, n = 322, 242, 13
+    p = BoardPipeline(w, h, n)
+    p.synth(0, n, scene="normal", frames_per_ply=2)
+    frames = [p.download(0, i) for i in range(n)]
+    p.close()
+    return [R.encode_image(f, quality=90, sampling=MIX[i % len(MIX)][0], dri=MIX[i % len(MIX)][1]) for i, f in enumerate(frames)]
+
+
+@pytest.mark.parametrize("lens", [False, True], ids=["lens_free", "lens"])
+@pytest.mark.parametrize("attached", [0, 1], ids=["1board", "2boards"])
+@pytest.mark.parametrize("mode", sorted(MODES))
+def test_short_last_group_and_taps_outside(gpu_ctx, mode, attached, lens):
+    """the warp from the planes where the runs above do not take it: a quad whose right and top parts leave the 322 x 242
+    frame, in one run of 11 frames in one chunk (plain: groups of four frames per thread and a last one of three; with a
+    profile: five groups of two and a last one of one) and then in a run of 2 frames (one frame per thread), with one board
+    and with two (the second smaller, rotated, with a profile of its own), lens-free and through a lens (the table-driven
+    kernel), against the planes-off pipeline, whose decode fills the BGR ring"""
+    import ref_lens as RL
+    from chessboard_vision_amd.stream import BoardPipeline, Lens
+    w, h, n = 322, 242, 13
+    quad = S.scaled_corners(w, h) + np.float32([0.42 * w, -0.3 * h])
+    assert (quad[:, 0] > w).any() and (quad[:, 1] < 0).any()
+    streams = small_game()
+    outs = []
+    for planes in (False, True):
+        p = BoardPipeline(w, h, n)
+        p.configure(quad, profile=S.SHIPPED_PROFILE, chunk=11, lanes=1, lens=Lens(*(RL.BARREL[:2] + (w / 2, h / 2) + RL.BARREL[4:])) if lens else None,
+                    **MODES[mode])
+        p.set_input_format("mjpeg", planes=planes)
+        assert bool(p.frames_ptr()) == (not planes)
+        boards = [p]
+        if attached:
+            own = dict(profile=CS.PROFILES["sat3"]) if mode == "profile_raw" else {}
+            boards.append(p.add_board(quad + np.float32(3), rot180=True, display_size=(800, 600), margin=100, **own))
+        for i in range(n):
+            p.upload(i, streams[i], fmt="mjpeg")
+        p.run(0, 11)
+        p.run(11, 2)
+        assert not p.jpeg_status(0, n).any()
+        outs.append([b.download(2, i) for b in boards for i in range(n)])
+        p.close()
+    assert len(outs[0]) == n * (1 + attached)
+    for k, (off, on) in enumerate(zip(*outs)):
+        assert np.array_equal(off, on), (mode, attached, lens, k, int((off != on).sum()))
+        black = (~on.any(2)).mean()  # the part of the board that lies outside the frame
+        assert 0.05 < black < 0.9, (k, black)

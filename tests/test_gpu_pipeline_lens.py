@@ -217,3 +217,60 @@ def test_color_sweep_with_the_pipelines_profile_reports_what_the_run_reports(gpu
             assert (out[i].raw_occupied, out[i].stable_occupied) == (int(res.raw_occupied[0, i]), int(res.stable_occupied[0, i])), (raw, i)
         assert any(out[i].raw_occupied for i in range(n))  # the frames show pieces
         p.close()
+
+
+# --- every raw layout in the many-frames forms ---------------------------------------------------------------------------------
+RAW_W, RAW_H, RAW_N = 322, 242, 13
+
+
+@functools.lru_cache(maxsize=None)
+def _raw_game(fmt):
+    """13 frames of a scripted game in the raw layout (inputs), and the BGR frames the restatement makes of them (the
+    reference pipeline's input)"""
+    import raw_profile_ref as RP
+    from chessboard_vision_amd.stream import BoardPipeline
+    p = BoardPipeline(RAW_W, RAW_H, RAW_N)
+    p.synth(0, RAW_N, frames_per_ply=2)
+    raw = [RP.from_bgr(p.download(0, i), fmt) for i in range(RAW_N)]
+    p.close()
+    return raw, [np.ascontiguousarray(RP.to_bgr(f, fmt)) for f in raw]
+
+
+def _raw_boards(fmt, frames, profile, lens):
+    """the warped boards of two boards of a pipeline fed `frames` in `fmt`: one run of 11 frames in one chunk, then one of 2"""
+    import color_sweep_ref as CS
+    from chessboard_vision_amd.stream import BoardPipeline
+    quad = S.scaled_corners(RAW_W, RAW_H) + np.float32([0.42 * RAW_W, -0.3 * RAW_H])
+    assert (quad[:, 0] > RAW_W).any() and (quad[:, 1] < 0).any()
+    kw = dict(enhance="profile", raw=True) if profile else dict(enhance=False)
+    p = BoardPipeline(RAW_W, RAW_H, RAW_N)
+    p.configure(quad, profile=CS.PROFILES["radical"], chunk=11, lanes=1, lens=_lens(R.BARREL[:2] + (RAW_W / 2, RAW_H / 2) + R.BARREL[4:]) if lens else None, **kw)
+    b = p.add_board(quad + np.float32(3), rot180=True, display_size=(800, 600), margin=100, **(dict(profile=CS.SHIPPED) if profile else {}))
+    if fmt != "bgr":
+        p.set_input_format(fmt)
+    for i, f in enumerate(frames):
+        p.upload(i, f, fmt=fmt)
+    p.run(0, 11)
+    p.run(11, 2)
+    out = [x.download(2, i) for x in (p, b) for i in range(RAW_N)]
+    p.close()
+    return out
+
+
+@pytest.mark.parametrize("lens", [False, True], ids=["lens_free", "lens"])
+@pytest.mark.parametrize("profile", [False, True], ids=["plain", "profile"])
+@pytest.mark.parametrize("fmt", ["nv12", "nv21", "yuv420p", "yv12", "yuyv", "yvyu", "uyvy", "bayer_rggb", "bayer_bggr", "bayer_grbg", "bayer_gbrg"])
+def test_every_raw_layout_short_last_group_and_taps_outside(gpu_ctx, fmt, profile, lens):
+    """the warp from raw frames of every layout, with a colour profile and without, lens-free and through the lens, where the
+    tests of the layouts do not take it: two boards (the second smaller and rotated) whose quads leave the 322 x 242 frame
+    to the right and at the top, one run of 11 frames in one chunk (groups of four frames per thread and a last one of three;
+    where the form takes two frames per thread, five groups and a last one of one) and a run of 2 frames (one frame per
+    thread), against the same pipeline fed the BGR frames that the restatement makes of the raw ones"""
+    raw, bgr = _raw_game(fmt)
+    got = _raw_boards(fmt, raw, profile, lens)
+    want = _raw_boards("bgr", bgr, profile, lens)
+    assert len(got) == 2 * RAW_N
+    for k, (g, w_) in enumerate(zip(got, want)):
+        assert np.array_equal(g, w_), (fmt, profile, lens, k, int((g != w_).sum()))
+        black = (~g.any(2)).mean()  # the part of the board that lies outside the frame
+        assert 0.05 < black < 0.9, (k, black)

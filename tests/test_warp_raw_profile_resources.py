@@ -1,20 +1,16 @@
 """Every kernel of k_warp_raw_profile.hip as the compiler reports it, with the build's own flags: per raw format the warp
-knows one k_warp_raw_profile and one k_warp_raw_profile_mb with one frame per thread and one each with the family's
+knows one k_warp_one and one k_warp_boards of WarpRawProfile with one frame per thread and one each with the family's
 many-frames form (four frames a thread; planar 4:2:0 two); none uses scratch, each stages the 7 680 B of the profile's tables
 and nothing else, and each stays at or under the VGPR count written down here when the form was chosen, so that a
 regression shows.  The one-frame forms are at or under 64, the line DESIGN.md section 4 gives for 8 waves per SIMD; the
 many-frames forms are above it on purpose: they were the fastest inside the run.
 No device is needed; the file is compiled for the device only and nothing is written."""
-import functools
-import os
-import re
-import subprocess
-
+import warp_kernels as W
 from chessboard_vision_amd import _native as N
 from chessboard_vision_amd import build as B
 
 FMT = dict(N.FORMATS, **N.BAYER_FORMATS)
-# (format, frames per thread) -> VGPRs of (k_warp_raw_profile, k_warp_raw_profile_mb); YV12 is launched as yuv420p
+# (format, frames per thread) -> VGPRs of WarpRawProfile in (k_warp_one, k_warp_boards); YV12 is launched as yuv420p
 VGPRS = {
     ("nv12", 1): (58, 52), ("nv21", 1): (58, 52), ("yuv420p", 1): (62, 56),
     ("yuyv", 1): (46, 46), ("yvyu", 1): (46, 46), ("uyvy", 1): (44, 44),
@@ -23,27 +19,11 @@ VGPRS = {
     ("bayer_rggb", 1): (57, 55), ("bayer_bggr", 1): (57, 55), ("bayer_grbg", 1): (55, 53), ("bayer_gbrg", 1): (55, 53),
     ("bayer_rggb", 4): (72, 72), ("bayer_bggr", 4): (72, 72), ("bayer_grbg", 4): (72, 72), ("bayer_gbrg", 4): (72, 72),
 }
-KERNELS = ("k_warp_raw_profile", "k_warp_raw_profile_mb")
+KERNELS = ("k_warp_one", "k_warp_boards")
 
 
-@functools.lru_cache(maxsize=None)
-def _remarks():
-    src = os.path.join(B.CSRC, "k_warp_raw_profile.hip")
-    cmd = [B._hipcc(), *B.FLAGS, "--cuda-device-only", "-S", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    for fn, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", r.stderr, re.S):
-        out[fn] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", body)}
-    return out
-
-
-def _instance(mangled):
-    """(kernel, format id, frames per thread) of _Z<len><name>ILi<fmt>ELi<fpt>EE..."""
-    m = re.match(r"_Z(\d+)", mangled)
-    name = mangled[m.end():m.end() + int(m.group(1))]
-    a = re.match(r"ILi(\d+)ELi(\d+)E", mangled[m.end() + int(m.group(1)):])
-    return name, int(a.group(1)), int(a.group(2))
+def _instances():
+    return W.instances("k_warp_raw_profile.hip")
 
 
 def test_the_file_is_in_the_build():
@@ -51,17 +31,17 @@ def test_the_file_is_in_the_build():
 
 
 def test_the_file_yields_the_expected_instantiations():
-    got = sorted(_instance(n) for n in _remarks())
-    want = sorted((k, FMT[f], fpt) for (f, fpt) in VGPRS for k in KERNELS)
+    got = sorted(_instances())
+    want = sorted((k, "WarpRawProfile", FMT[f], fpt) for (f, fpt) in VGPRS for k in KERNELS)
     assert got == want and len(got) == 40
     assert "yv12" not in {f for f, _ in VGPRS} and set(f for f, _ in VGPRS) == set(FMT) - {"bgr", "yv12"}
 
 
 def test_no_scratch_the_tables_lds_and_the_committed_registers():
-    rem = {_instance(n): v for n, v in _remarks().items()}
+    rem = _instances()
     for (f, fpt), counts in VGPRS.items():
         for k, most in zip(KERNELS, counts):
-            v = rem[(k, FMT[f], fpt)]
+            v = rem[(k, "WarpRawProfile", FMT[f], fpt)]
             assert v["ScratchSize"] == 0, (k, f, fpt, v)
             assert v["LDS Size"] == 7680, (k, f, fpt, v)
             assert v["VGPRs"] <= most and (fpt > 1 or most <= 64), (k, f, fpt, v)

@@ -1,36 +1,28 @@
 """Every kernel of k_warp.hip as the compiler reports it, with the build's own flags: the one gather (warp_gather) yields
-exactly the 52 warp kernels (8 k_warp / k_warp_mb, 4 k_warp_profile / k_warp_profile_mb, 24 k_warp_yuv / k_warp_yuv_mb,
-16 k_warp_bayer / k_warp_bayer_mb) beside k_synth, none of them uses scratch, and each stays at or under 64 VGPRs, the
+exactly the 52 warp kernels (k_warp_one and k_warp_boards of: WarpBgr 4 each, WarpProfile 2 each, WarpRaw of the YUV layouts 12
+each, WarpRaw of the mosaics 8 each) beside k_synth, none of them uses scratch, and each stays at or under 64 VGPRs, the
 line DESIGN.md section 4 gives for running at 8 waves per SIMD.
 No device is needed; the file is compiled for the device only and nothing is written."""
-import functools
-import os
-import re
-import subprocess
+import warp_kernels as W
 
-from chessboard_vision_amd import build as B
-
-# kernel -> instantiations: formats (or byte-map forms) x frames per thread
-EXPECTED = {"k_warp": 4, "k_warp_mb": 4, "k_warp_profile": 2, "k_warp_profile_mb": 2, "k_warp_yuv": 12, "k_warp_yuv_mb": 12,
-            "k_warp_bayer": 8, "k_warp_bayer_mb": 8}
+# (kernel template, source) -> instantiations: formats (or byte-map forms) x frames per thread
+EXPECTED = {("k_warp_one", "WarpBgr"): 4, ("k_warp_boards", "WarpBgr"): 4, ("k_warp_one", "WarpProfile"): 2, ("k_warp_boards", "WarpProfile"): 2,
+            ("k_warp_one", "WarpRaw yuv"): 12, ("k_warp_boards", "WarpRaw yuv"): 12, ("k_warp_one", "WarpRaw bayer"): 8, ("k_warp_boards", "WarpRaw bayer"): 8}
 
 
-@functools.lru_cache(maxsize=None)
 def _remarks():
-    src = os.path.join(B.CSRC, "k_warp.hip")
-    cmd = [B._hipcc(), *B.FLAGS, "--cuda-device-only", "-S", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    for fn, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", r.stderr, re.S):
-        out[fn] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", body)}
-    return out
+    return W.remarks("k_warp.hip")
 
 
 def _kernel(mangled):
-    """the template's name of _Z<len><name>I...; the plain name of an extern "C"-like symbol"""
-    m = re.match(r"_Z(\d+)", mangled)
-    return mangled[m.end():m.end() + int(m.group(1))] if m else mangled
+    """(template, source) of a warp kernel, the raw source split into its YUV and Bayer formats; the plain name of k_synth"""
+    if "k_synth" in mangled:
+        return "k_synth"
+    name, src, arg, fpt = W.instance(mangled)
+    assert fpt in (1, 4), mangled
+    if src == "WarpRaw":
+        src += " bayer" if arg in W.BAYER_IDS else " yuv"
+    return name, src
 
 
 def test_the_file_yields_the_52_warp_kernels_and_k_synth():

@@ -2,21 +2,19 @@
 k_warp_lens_cs.hip) as the compiler reports it, with the build's own flags.  Per YUV layout the kernels know (six: YV12 is
 launched as yuv420p):
   k_ingest_cs.hip      12 = 6 layouts x {dword path, byte path}
-  k_warp_cs.hip        48 = 6 layouts x {k_warp_yuv_cs, k_warp_yuv_cs_mb, k_warp_raw_profile_cs, k_warp_raw_profile_cs_mb}
+  k_warp_cs.hip        48 = 6 layouts x {k_warp_one, k_warp_boards} x {WarpRawCs, WarpRawProfileCs}
                             x {one frame a thread, the many-frames form}
-  k_warp_lens_cs.hip   24 = 6 layouts x {WarpRawCs, WarpRawProfileCs} x {one frame a thread, the many-frames form}
+  k_warp_lens_cs.hip   24 = 6 layouts x k_warp_lens x {WarpRawCs, WarpRawProfileCs} x {one frame a thread, the many-frames form}
 The many-frames forms: four frames without a profile, planar 4:2:0 two (its four-frame form needs 65 VGPRs once the constants
 are the launch's); with a profile what the siblings take (four, planar 4:2:0 two; two with a lens).  None uses scratch; the
 forms without a profile stay at or under 64 VGPRs (8 waves per SIMD, as k_warp.hip's) and use no LDS; the profile forms stage
 the 7 680 B of the profile's tables and nothing else, and their one-frame forms stay at or under 64 VGPRs like their siblings'.
 No device is needed; the files are compiled for the device only and nothing is written."""
-import functools
-import os
 import re
-import subprocess
 
 import pytest
 
+import warp_kernels as W
 from chessboard_vision_amd import _native as N
 from chessboard_vision_amd import build as B
 
@@ -25,27 +23,18 @@ PLANAR = N.FMT_YUV420P
 UNITS = ("k_ingest_cs.hip", "k_warp_cs.hip", "k_warp_lens_cs.hip")
 
 
-@functools.lru_cache(maxsize=None)
 def _remarks(unit):
-    cmd = [B._hipcc(), *B.FLAGS, "--cuda-device-only", "-S", os.path.join(B.CSRC, unit), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    for fn, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", r.stderr, re.S):
-        out[_instance(fn)] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", body)}
-    return out
+    """(kernel, format id, second template number) -> figures of k_ingest_cs.hip; (kernel template, source, format id, frames
+    per thread) -> figures of the warp units"""
+    if unit != "k_ingest_cs.hip":
+        return W.instances(unit)
+    return {_ingest_instance(n): v for n, v in W.remarks(unit).items()}
 
 
-def _instance(mangled):
-    """(kernel or source, format id, second template number) of _Z<len><name>ILi<fmt>ELi<n>EE... or
-    _Z11k_warp_lensI<len><source>ILi<fmt>EELi<fpt>EE..."""
+def _ingest_instance(mangled):
+    """(kernel, format id, second template number) of _Z<len><name>ILi<fmt>ELi<n>EE..."""
     m = re.match(r"_Z(\d+)", mangled)
     name, rest = mangled[m.end():m.end() + int(m.group(1))], mangled[m.end() + int(m.group(1)):]
-    if name == "k_warp_lens":
-        a = re.match(r"I(\d+)", rest)
-        src = rest[a.end():a.end() + int(a.group(1))]
-        b = re.match(r"ILi(\d+)EELi(\d+)E", rest[a.end() + int(a.group(1)):])
-        return src, int(b.group(1)), int(b.group(2))
     a = re.match(r"ILi(\d+)ELi(\d+)E", rest)
     return name, int(a.group(1)), int(a.group(2))
 
@@ -63,16 +52,17 @@ def test_the_units_are_in_the_build():
 def test_the_exact_kernel_lists():
     want = sorted(("k_ingest_cs", f, px) for f in YUV.values() for px in (2, 4))
     assert sorted(_remarks("k_ingest_cs.hip")) == want and len(want) == 12
-    want = sorted((k, f, fpt) for f in YUV.values() for k in ("k_warp_yuv_cs", "k_warp_yuv_cs_mb", "k_warp_raw_profile_cs", "k_warp_raw_profile_cs_mb")
-                  for fpt in (1, _many(f, "profile" in k)))
+    want = sorted((k, s, f, fpt) for f in YUV.values() for k in ("k_warp_one", "k_warp_boards") for s in ("WarpRawCs", "WarpRawProfileCs")
+                  for fpt in (1, _many(f, "Profile" in s)))
     assert sorted(_remarks("k_warp_cs.hip")) == want and len(want) == 48
-    want = sorted((s, f, fpt) for f in YUV.values() for s in ("WarpRawCs", "WarpRawProfileCs") for fpt in (1, _many(f, "Profile" in s, lens=True)))
+    want = sorted(("k_warp_lens", s, f, fpt) for f in YUV.values() for s in ("WarpRawCs", "WarpRawProfileCs") for fpt in (1, _many(f, "Profile" in s, lens=True)))
     assert sorted(_remarks("k_warp_lens_cs.hip")) == want and len(want) == 24
 
 
 @pytest.mark.parametrize("unit", UNITS)
 def test_no_scratch_registers_and_lds(unit):
-    for (name, f, n), v in _remarks(unit).items():
+    for key, v in _remarks(unit).items():
+        name, f, n = key[-3:]  # (a warp kernel: its source)
         profile = "rofile" in name
         assert v["ScratchSize"] == 0, (name, f, n, v)
         assert v["LDS Size"] == (7680 if profile else 0), (name, f, n, v)
