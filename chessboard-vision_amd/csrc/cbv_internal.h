@@ -697,8 +697,6 @@ struct ModelScan {
     float* var;
     float* sd;
 };
-int launch_model_scan(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, ModelScan ms,
-                      cbv_sq_stats* stats, u8* decisions, int count, int max_px);
 
 // The ChangeDetector stage's own blur (cbv_pipeline_set_change_blur): ChangeDetector._preprocess with a kernel other than the
 // PieceDetector's 5 x 5.  cf[j] = the 8.8 fixed-point coefficient (build_gaussian_q8) j taps from the centre: the kernel is
@@ -809,17 +807,19 @@ int launch_warp_lens_cs(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const Le
 int lens_checked(cbv_ctx* ctx, const cbv_lens* lens, LensDev* out, const char* who);
 // warp_footprint through the lens: every border pixel of the destination through the full map, one more pixel of margin
 bool warp_footprint_lens(const double* Minv, const LensDev* lens, int dw, int dh, int w, int h, PxRect* out);
-int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px);
+// (n_squares: the boards' n_rois summed; the statistics launches choose 1024 or 256 lanes a square from n_squares * batch)
+int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int n_squares, int s0, int batch, int any_hough, u32* hough_work,
+                                 int max_px);
 int launch_hough_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, const u32* work, int max_items, size_t lds, u32* retry,
                     int retry_frame_base, int pass);
 int launch_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int mirrored);
-int launch_model_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int max_px);
+int launch_model_scan(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int max_px);
 // ChangeDetector._preprocess with the board's own kernel on `batch` warped frames, and (mean != null) the z-score fields of
 // the records and the class bits of the decision bytes k_squares_pre5_stats wrote before it on the same stream
 int launch_change_blur_stats(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n, u8* plane,
                              size_t plane_frame_stride, const float* mean, const float* sd, float z_thresh, cbv_sq_stats* stats,
                              int batch, u8* decisions, const ChangeBlur& cb, int max_px);
-int launch_change_blur_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int max_px);
+int launch_change_blur_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int n_squares, int s0, int batch, int max_px);
 
 // The ChangeDetector sensitivity sweep (cbv_pipeline_sweep, k_sweep.hip).  A setting as the kernels read it: the float32
 // casts of cbv_pipeline_configure and the setting's place in the caller's list; the call sorts them by blur kernel.

@@ -145,9 +145,8 @@ static BoardDev board_dev(const Board& q, size_t lds[2])
 }
 
 // Rebuild the boards' kernel arguments whenever a board is set up, attached, detached or calibrated, or its model-update
-// mode or its ChangeDetector blur kernel changes.  The device table
-// and the maxima of the multi-board launches exist only with boards attached.  Nothing may be in flight: the callers
-// joined the runs.
+// mode or its ChangeDetector blur kernel changes, and upload them as the device table (one small copy and a wait, never
+// in the frame chain), for a single board too.  Nothing may be in flight: the callers joined the runs.
 int pipeline_tables(Pipe& P)
 {
     cbv_ctx* ctx = P.ctx;
@@ -155,13 +154,13 @@ int pipeline_tables(Pipe& P)
     P.tab.resize(nb);
     P.any_hough = P.any_adaptive = P.any_session = P.any_own_blur = P.profile_on = false;
     P.hough_lds[0] = P.hough_lds[1] = 0;
-    P.max_px = P.max_S = 0;
+    P.max_px = P.max_S = P.n_squares = 0;
     for (int k = 0; k < nb; k++) {
         const Board& q = P.boards[k]->b;
         size_t lds[2];
         P.tab[k] = board_dev(q, lds);
         if (q.cfg.use_hough) {
-            // (a single board's launchers check the layout themselves, at run time)
+            // (a single board is configured with such squares, and cbv_pipeline_run refuses it)
             if (nb > 1 && (!lds[0] || !lds[1]))
                 return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles stage: %dx%d squares of board %d do not fit the LDS layout",
                                 q.hough_cfg.maxw, q.hough_cfg.maxh, k);
@@ -175,6 +174,7 @@ int pipeline_tables(Pipe& P)
         P.profile_on = P.profile_on || (P.profile_only && q.profile.enabled); // no board has one: the plain warp, no table is read
         P.max_px = std::max(P.max_px, q.max_px);
         P.max_S = std::max(P.max_S, q.cfg.board_size);
+        P.n_squares += q.cfg.n_rois;
     }
     if (P.lens_on) { // the lens kernels' table: the warp's part of every board, a single one included
         std::vector<LensBoard> lt((size_t)nb);
@@ -186,7 +186,6 @@ int pipeline_tables(Pipe& P)
         CBV_HIP(ctx, hipMemcpyAsync(P.d_lens_tab.p, lt.data(), sizeof(LensBoard) * nb, hipMemcpyHostToDevice, ctx->stream));
         CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (lt is on this stack)
     }
-    if (nb == 1) return CBV_OK;
     RC(dev_ensure(ctx, &P.d_boards, sizeof(BoardDev) * nb));
     CBV_HIP(ctx, hipMemcpyAsync(P.d_boards.p, P.tab.data(), sizeof(BoardDev) * nb, hipMemcpyHostToDevice, ctx->stream));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));

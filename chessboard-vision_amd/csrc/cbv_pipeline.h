@@ -138,8 +138,9 @@ struct Pipe {
     unsigned long long joined_seq = 0; // runs up to this one are ordered before later work on `joined_stream`
     hipStream_t joined_stream = nullptr;
     // the boards (board 0 = the handle cbv_pipeline_create returned) and their kernel arguments: `tab` holds one BoardDev
-    // per board (board_dev), tab[0] feeds the single-board launches; with boards attached it is uploaded to d_boards for the
-    // multi-board launches, which also take the maxima over the boards below
+    // per board (board_dev), tab[0] feeds the single-board launches; d_boards is its device copy, uploaded for a single board
+    // too (k_model_scan is table-driven for every number of boards), for the multi-board launches, which also take the
+    // maxima and the sum over the boards below
     std::vector<cbv_pipeline*> boards;
     std::vector<BoardDev> tab;
     DevBuf d_boards;
@@ -155,6 +156,7 @@ struct Pipe {
     bool any_own_blur = false; // some board's ChangeDetector has a blur kernel of its own: k_change_blur_stats runs behind the statistics
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
+    int n_squares = 0; // the squares that exist, the boards' n_rois summed: sizes the statistics kernels' workgroups
     Board& b0() const { return boards[0]->b; }
 };
 // cbv_pipeline.cpp: board handles, the ordering of the runs in flight, the boards' kernel arguments, read-backs

@@ -4,7 +4,8 @@
 #include "session_core.h"
 
 // the per-board stages of a chunk of b frames from slot s0 (warp, square statistics, HoughCircles' first pass): with boards
-// attached one launch each for all of them, otherwise the single-board launches with board 0's arguments
+// attached one launch each for all of them, otherwise the single-board launches with board 0's arguments, which measured
+// faster on one board than the table-driven kernels with a table of one
 // (res = the BGR frames the warp samples; in raw mode null, and the warp samples the chunk's slots of the raw ring;
 // with the profile-only mode's enabled profile the warp applies it to its taps)
 static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, int b, u32* work, u32* retry0, u32* retry, int retry_base)
@@ -22,8 +23,8 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     if (nb > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         if (!P.lens_on) RC(launch_warp_mb(ctx, src, tab, nb, P.max_S, s0, b, work, retry0));
-        RC(launch_squares_pre5_stats_mb(ctx, tab, nb, s0, b, P.any_hough, work, P.max_px));
-        if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, s0, b, P.max_px));
+        RC(launch_squares_pre5_stats_mb(ctx, tab, nb, P.n_squares, s0, b, P.any_hough, work, P.max_px));
+        if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, P.n_squares, s0, b, P.max_px));
         if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, P.hough_lds[0], retry, retry_base, 0));
         return CBV_OK;
     }
@@ -48,21 +49,14 @@ static void mark_mirrored(Pipe& P, int s0, int cnt, bool held)
     for (cbv_pipeline* q : P.boards) std::fill(q->b.slot_mirrored.begin() + s0, q->b.slot_mirrored.begin() + s0 + cnt, held ? 1 : 0);
 }
 
-// The scan stage of ONE board for a run: HoughCircles' second pass and the model scan (`with_pre`: not yet done by the
-// multi-board launches), the temporal scan, packing and NoiseHandler; with a game session the rounds of k_session.hip.
-static int board_scan(Pipe& P, Board& q, const BoardDev& T, int slot0, int count, bool mirrored, bool with_pre, const u32* retry)
+// The scan stage of ONE board for a run: the temporal scan, packing and NoiseHandler; with a game session the rounds of
+// k_session.hip (temporal scan, then packing, NoiseHandler and the session's walk).
+static int board_scan(Pipe& P, Board& q, const BoardDev& T, int slot0, int count, bool mirrored)
 {
     cbv_ctx* ctx = P.ctx;
     const u8* gray = T.gray + T.plane_total * slot0;
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * slot0;
     u8* flags = T.flags + (size_t)CBV_MAX_SQUARES * slot0;
-    if (with_pre && T.want_hough) // squares whose first HoughCircles pass overflowed (normally none), before the scan reads the decisions
-        RC(launch_hough_second(ctx, T.descs, T.n, gray, T.plane_total, q.hough_cfg, T.hough + (size_t)CBV_MAX_SQUARES * slot0, dec,
-                               retry, T.n * count));
-    // the z-score statistics and the model update of a board whose model follows the frames, before the scan reads the classes
-    if (with_pre && q.adaptive())
-        RC(launch_model_scan(ctx, T.descs, T.n, T.cgray + T.plane_total * slot0, T.plane_total, T.ms, T.stats + (size_t)T.n * slot0, dec, count,
-                             q.max_px));
     ResultMirror mir;
     if (mirrored) {
         mir.records = T.mirror + slot0;
@@ -148,15 +142,22 @@ static int pipeline_run_tail(Pipe& P, Pipe::RunRec* rec, int slot0, int count, b
     const int nb = (int)P.boards.size();
     const BoardDev* tab = (const BoardDev*)P.d_boards.p;
     const u32* retry = (const u32*)rec->retry.p;
-    if (nb > 1) { // with boards attached every board's second pass and model scan are one launch each
-        if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, slot0, retry, CBV_MAX_SQUARES * nb * count, P.hough_lds[1], nullptr, 0, 1));
-        if (P.any_adaptive) RC(launch_model_scan_mb(ctx, tab, nb, slot0, count, P.max_px));
-    }
-    // ... and so are their scan, packing and NoiseHandler, unless a board runs a game session: a session scans in rounds of
-    // its own, so every board's scan is launched by itself, as a pipeline without boards launches its one
+    // squares whose first HoughCircles pass overflowed (normally none), before the scan reads the decisions: one launch for
+    // the boards of a table, the explicit one for a single board (as the first pass)
+    const BoardDev& T0 = P.tab[0];
+    if (P.any_hough && nb > 1) RC(launch_hough_mb(ctx, tab, nb, slot0, retry, CBV_MAX_SQUARES * nb * count, P.hough_lds[1], nullptr, 0, 1));
+    else if (P.any_hough)
+        RC(launch_hough_second(ctx, T0.descs, T0.n, T0.gray + T0.plane_total * slot0, T0.plane_total, P.b0().hough_cfg,
+                               T0.hough + (size_t)CBV_MAX_SQUARES * slot0, T0.dec + (size_t)CBV_MAX_SQUARES * slot0, retry, T0.n * count));
+    // the z-score statistics and the model update of the boards whose model follows the frames, before the scan reads the
+    // classes: table-driven for every number of boards, a single board being a table of one
+    if (P.any_adaptive) RC(launch_model_scan(ctx, tab, nb, slot0, count, P.max_px));
+    // The scan, packing and NoiseHandler of several boards are one launch each too, unless a board runs a game session: a
+    // session scans in rounds of its own, so every board's scan is launched by itself.  So is a single board's: the
+    // table-driven scan measured 1.5 to 3 % slower on it.
     if (nb > 1 && !P.any_session) RC(launch_scan_mb(ctx, tab, nb, slot0, count, mirrored ? 1 : 0));
     else
-        for (int k = 0; k < nb; k++) RC(board_scan(P, P.boards[k]->b, P.tab[k], slot0, count, mirrored, nb == 1, retry));
+        for (int k = 0; k < nb; k++) RC(board_scan(P, P.boards[k]->b, P.tab[k], slot0, count, mirrored));
     CBV_HIP(ctx, hipEventRecord(rec->scan_ev, scan_on));
     mark_mirrored(P, slot0, count, mirrored);
     for (cbv_pipeline* q : P.boards) std::fill(q->b.slot_blur.begin() + slot0, q->b.slot_blur.begin() + slot0 + count, (u8)q->b.change_k);
@@ -176,6 +177,14 @@ extern "C" int cbv_pipeline_run(cbv_pipeline* p, int slot0, int count)
     if (slot0 < 0 || count <= 0 || slot0 + count > P.max_frames) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_run: bad slot range");
     CBV_ENTER(ctx);
     if (P.plan.source == FRAMES_RAW && !P.raw_ring) return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_run: no raw frame was ever uploaded or submitted");
+    // Squares HoughCircles cannot run on: with boards attached pipeline_tables refused them; a pipeline of one board is
+    // configured with them and refused here, before anything is enqueued
+    if (P.any_hough && (!P.hough_lds[0] || !P.hough_lds[1])) {
+        const HoughCfg& hc = P.b0().hough_cfg;
+        if (hc.maxw < 2 || hc.maxh < 2 || hc.maxw > 250 || hc.maxh > 250) // (hough_dims_ok)
+            return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles stage: squares must be 2..250 px (got %dx%d)", hc.maxw, hc.maxh);
+        return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles stage: %dx%d squares do not fit the LDS layout", hc.maxw, hc.maxh);
+    }
     const cbv_enhance_params& enh = P.b0().cfg.enhance;
     // Lane 0 is the context's stream; lanes 1.. are worker streams forked from it and joined before
     // the temporal scan (which needs every frame's statistics, in order).

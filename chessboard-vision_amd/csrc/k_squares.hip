@@ -427,14 +427,16 @@ __global__ __launch_bounds__(NT) void k_squares_pre5_stats_mb(const BoardDev* __
                                nullptr, DetectMasks(), (u32)b << MB_BOARD_SHIFT, acc, zm, nanf_);
 }
 
-int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int any_hough, u32* hough_work, int max_px)
+// (n_squares: the boards' n_rois summed, the workgroups of a frame that stay)
+int launch_squares_pre5_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int n_squares, int s0, int batch, int any_hough, u32* hough_work,
+                                 int max_px)
 {
     if (max_px <= 0 || max_px > CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM) max_px = CBV_MAX_SQUARE_DIM * CBV_MAX_SQUARE_DIM;
     const size_t lds = (size_t)((max_px + 15) & ~15) + 2 * (size_t)max_px;
     u32* work = any_hough ? hough_work : nullptr;
     prof_begin(ctx, CBV_K_SQUARES);
     const dim3 grid(CBV_MAX_SQUARES, nb, batch);
-    if ((long long)CBV_MAX_SQUARES * nb * batch <= 2 * ctx->num_cus)
+    if ((long long)n_squares * batch <= 2 * ctx->num_cus)
         hipLaunchKernelGGL((k_squares_pre5_stats_mb<1024>), grid, dim3(1024), lds, ctx->stream, tab, s0, work);
     else
         hipLaunchKernelGGL((k_squares_pre5_stats_mb<256>), grid, dim3(256), lds, ctx->stream, tab, s0, work);
@@ -801,16 +803,8 @@ __device__ __forceinline__ void model_scan_square(const SquareDesc* __restrict__
     else model_scan_body<false>(d, gray, gray_frame_stride, ms, stats, nsq, decisions, count, blockIdx.x, part);
 }
 
-__global__ __launch_bounds__(1024) void k_model_scan(const SquareDesc* __restrict__ descs, const u8* __restrict__ gray, size_t gray_frame_stride,
-                                                      const ModelScan ms, cbv_sq_stats* __restrict__ stats, int nsq,
-                                                      u8* __restrict__ decisions, int count)
-{
-    __shared__ uint2 part[2][MS_MAXW];
-    model_scan_square(descs, gray, gray_frame_stride, ms, stats, nsq, decisions, count, part);
-}
-
 // every board of a pipeline: grid (CBV_MAX_SQUARES, boards); boards whose model is frozen (or not calibrated) leave
-__global__ __launch_bounds__(1024) void k_model_scan_mb(const BoardDev* __restrict__ tab, int s0, int count)
+__global__ __launch_bounds__(1024) void k_model_scan(const BoardDev* __restrict__ tab, int s0, int count)
 {
     __shared__ uint2 part[2][MS_MAXW];
     const BoardDev& T = tab[blockIdx.y];
@@ -827,22 +821,10 @@ static int model_scan_threads(int max_px)
     return (lanes + 63) & ~63;
 }
 
-int launch_model_scan(cbv_ctx* ctx, const SquareDesc* descs, int n, const u8* gray, size_t gray_frame_stride, ModelScan ms,
-                      cbv_sq_stats* stats, u8* decisions, int count, int max_px)
-{
-    if (ms.mode == CBV_MODEL_FROZEN) return CBV_OK;
-    prof_begin(ctx, CBV_K_MODEL_SCAN);
-    hipLaunchKernelGGL(k_model_scan, dim3(n), dim3(model_scan_threads(max_px)), 0, ctx->stream, descs, gray, gray_frame_stride, ms, stats, n,
-                       decisions, count);
-    prof_end(ctx, CBV_K_MODEL_SCAN);
-    CBV_HIP(ctx, hipGetLastError());
-    return CBV_OK;
-}
-
-int launch_model_scan_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int max_px)
+int launch_model_scan(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int count, int max_px)
 {
     prof_begin(ctx, CBV_K_MODEL_SCAN);
-    hipLaunchKernelGGL(k_model_scan_mb, dim3(CBV_MAX_SQUARES, nb), dim3(model_scan_threads(max_px)), 0, ctx->stream, tab, s0, count);
+    hipLaunchKernelGGL(k_model_scan, dim3(CBV_MAX_SQUARES, nb), dim3(model_scan_threads(max_px)), 0, ctx->stream, tab, s0, count);
     prof_end(ctx, CBV_K_MODEL_SCAN);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
@@ -945,12 +927,12 @@ int launch_change_blur_stats(cbv_ctx* ctx, const u8* src, size_t src_frame_strid
     return CBV_OK;
 }
 
-int launch_change_blur_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch, int max_px)
+int launch_change_blur_stats_mb(cbv_ctx* ctx, const BoardDev* tab, int nb, int n_squares, int s0, int batch, int max_px)
 {
     const size_t lds = change_blur_lds(max_px);
     prof_begin(ctx, CBV_K_CHANGE_BLUR);
     const dim3 grid(CBV_MAX_SQUARES, nb, batch);
-    if ((long long)CBV_MAX_SQUARES * nb * batch <= 2 * ctx->num_cus)
+    if ((long long)n_squares * batch <= 2 * ctx->num_cus)
         hipLaunchKernelGGL((k_change_blur_stats_mb<1024>), grid, dim3(1024), lds, ctx->stream, tab, s0);
     else
         hipLaunchKernelGGL((k_change_blur_stats_mb<256>), grid, dim3(256), lds, ctx->stream, tab, s0);

@@ -594,3 +594,63 @@ def test_pipeline_update_references_mid_stream(gpu_ctx, oracle):
             det.update_references(sq)
             nh.reset()
     assert len(bits_to_positions(res[k + 1].processed, p.rois_rc)) == 64, "cleared cache: everything is processed again"
+
+
+def test_one_board_hough_refusal_comes_from_run(gpu_ctx):
+    """Squares HoughCircles cannot run on (here 1 px wide: a 108 x 108 display with a margin of 100 is a board of 8 px): a
+    pipeline of one board is configured with them, run refuses them with CBV_ERR_UNSUPPORTED (-5) and enqueues nothing,
+    and the pipeline works again once it is configured with squares that fit."""
+    from chessboard_vision_amd.stream import BoardPipeline
+    pts = S.scaled_corners(W, H)
+    p = BoardPipeline(W, H, 2)
+    p.configure(pts, enhance=False, display_size=(108, 108), margin=100)
+    assert p.board_size == 8 and p._cfg.rois[0].w == 1
+    p.synth(0, 2)
+    for _ in range(2):  # a refusal leaves nothing behind that would change the next one
+        with pytest.raises(RuntimeError, match=r"squares must be 2\.\.250 px \(got 1x1\) \(code -5\)"):
+            p.run(0, 2)
+    p.configure(pts, enhance=False)
+    p.run(0, 2)
+    got = bytes(p.results(0, 2))
+    p.close()
+    q = BoardPipeline(W, H, 2)
+    q.configure(pts, enhance=False)
+    q.synth(0, 2)
+    q.run(0, 2)
+    want = bytes(q.results(0, 2))
+    q.close()
+    assert got == want and any(want)
+
+
+def test_one_board_with_five_squares(gpu_ctx):
+    """A board of 5 squares (neither 64 nor a multiple of 4; configured through the C ABI, the Python surface always has
+    64): its statistics and result bits are those of the same 5 ROIs as the first five of the 64-square board on the same
+    frames, and no result word has a bit past the board's squares.  Runs of 2 and of 4 frames (the fused pack +
+    NoiseHandler launch) and of 6 (the separate ones)."""
+    import ctypes as C
+    from chessboard_vision_amd import _native as N
+    from chessboard_vision_amd.stream import BoardPipeline
+    pts = S.scaled_corners(W, H)
+    n = 12
+
+    def run(n_rois):
+        p = BoardPipeline(W, H, n)
+        p.configure(pts, enhance=False)
+        if n_rois != 64:
+            p._cfg.n_rois = n_rois
+            p.ctx.check(p.ctx.lib.cbv_pipeline_configure(p.h_, p._cfg))
+            p.rois_rc = p.rois_rc[:n_rois]
+        p.synth(0, n, frames_per_ply=2)
+        p.run(0, 2)
+        p.run(2, 4)
+        p.run(6, 6)
+        res = np.frombuffer(bytes(p.results(0, n)), np.uint64).reshape(n, -1).copy()
+        stats = [bytes(p.square_stats(s))[:5 * C.sizeof(N.SqStats)] for s in range(n)]
+        p.close()
+        return res, stats
+
+    res5, stats5 = run(5)
+    res64, stats64 = run(64)
+    assert stats5 == stats64
+    assert np.array_equal(res5, res64 & np.uint64(31))
+    assert (res64 & np.uint64(31)).any() and (res64 >> np.uint64(5)).any()

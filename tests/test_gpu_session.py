@@ -284,3 +284,39 @@ def test_off_means_off_and_errors(gpu_ctx):
     p.set_check_squares(0, [set()])  # the check sets stay the caller's
     s.end()
     p.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _short_runs(boards, session_on):
+    """12 frames at 5 frames per ply in runs of 1, 3 and 8 frames (at most 4: the fused pack + NoiseHandler launch; more:
+    the separate ones) -> board 0's results, noise records and square statistics, and the moves of the session on board
+    `session_on` (None: no session)."""
+    from chessboard_vision_amd.stream import BoardPipeline
+    n = 12
+    pts = S.scaled_corners(W, H)
+    p = BoardPipeline(W, H, n)
+    p.configure(pts, enhance=False, chunk=16, lanes=2)
+    for k in range(boards):
+        p.add_board(pts + np.float32(2 * (k + 1)))
+    p.synth(0, n, scene="normal", frames_per_ply=5, points=pts)
+    all_boards = [p] + list(p._boards)
+    ses = all_boards[session_on].session_begin(stability_required=2, cooldown_frames=1) if session_on is not None else None
+    t = 0
+    for c in (1, 3, 8):
+        p.run(t, c)
+        t += c
+    out = dict(results=bytes(p.results(0, n)), noise=bytes(_noise_bytes(p, 0, n)), stats=[bytes(p.square_stats(s)) for s in range(n)],
+               moves=[m.uci() for _, m, _ in ses.moves()] if ses else [])
+    p.close()
+    return out
+
+
+def test_board_without_session_beside_one_with_a_session_in_short_runs(gpu_ctx):
+    """A board without a session in a pipeline where another board runs one is scanned by itself, behind the table-driven
+    HoughCircles passes of both boards: in runs of 1, 3 and 8 frames it gives what the same board gives in a pipeline
+    of its own."""
+    got, want = _short_runs(1, 1), _short_runs(0, None)
+    assert got["moves"], "the session accepted no move: the case tests nothing"
+    assert got["results"] == want["results"] and any(want["results"])
+    assert got["noise"] == want["noise"]
+    assert got["stats"] == want["stats"]
