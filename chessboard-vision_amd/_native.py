@@ -287,6 +287,33 @@ FORMATS_422 = ("yuyv", "yvyu", "uyvy")                 # ring slots [h, w, 2]
 FMT_BAYER_RGGB, FMT_BAYER_BGGR, FMT_BAYER_GRBG, FMT_BAYER_GBRG = 0x04, 0x14, 0x24, 0x34
 BAYER_FORMATS = {"bayer_rggb": FMT_BAYER_RGGB, "bayer_bggr": FMT_BAYER_BGGR, "bayer_grbg": FMT_BAYER_GRBG,
                  "bayer_gbrg": FMT_BAYER_GBRG}                 # ring slots [h, w]
+# Sample encodings of more than 8 bits (include/cbv.h, "developed mosaics"): a field OR-ed onto a layout's id, a suffix on its
+# name.  "16": a little-endian 16-bit container holding 10, 12, 14 or 16 bits (V4L2 SRGGB10 / 12 / 14 / 16, libav
+# bayer_rggb16le); "10p" / "12p": MIPI RAW10 / RAW12 packed rows (V4L2 SRGGB10P / SRGGB12P).  A table of its own again:
+# BAYER_FORMATS stays the 8-bit mosaics.
+BAYER_16, BAYER_10P, BAYER_12P, BAYER_ENC_MASK = 0x1000, 0x2000, 0x3000, 0xF000
+BAYER_ENCODINGS = {"16": BAYER_16, "10p": BAYER_10P, "12p": BAYER_12P}
+BAYER_DEEP_FORMATS = {name + suffix: fid | enc for name, fid in BAYER_FORMATS.items() for suffix, enc in BAYER_ENCODINGS.items()}
+BAYER_TABLE_BITS = {0: (8,), BAYER_16: (10, 12, 14, 16), BAYER_10P: (10,), BAYER_12P: (12,)}  # the bits an encoding's tables may have
+BAYER_DEFAULT_BITS = {0: 0, BAYER_16: 16, BAYER_10P: 10, BAYER_12P: 12}                       # ... and its default table's (0: none)
+
+
+def bayer_row_bytes(fmt_id, w):
+    """Bytes of a row of w samples of a Bayer id."""
+    enc = fmt_id & BAYER_ENC_MASK
+    return {0: w, BAYER_16: 2 * w, BAYER_10P: w // 4 * 5, BAYER_12P: w // 2 * 3}[enc]
+
+
+def is_bayer(fmt):
+    """`fmt` names a Bayer mosaic of any encoding."""
+    return isinstance(fmt, str) and (fmt.lower() in BAYER_FORMATS or fmt.lower() in BAYER_DEEP_FORMATS)
+
+
+def neutral_tables(bits):
+    """The neutral tables of `bits` bits, uint8 [3, 2^bits]: v * 255 / M rounded half up, M = 2^bits - 1, for every colour."""
+    m = (1 << bits) - 1
+    v = np.arange(m + 1, dtype=np.int64)
+    return np.repeat(((510 * v + m) // (2 * m)).astype(np.uint8)[None], 3, axis=0)
 
 # The colour space of a YUV frame travels in its format id (include/cbv.h): CBV_CS_* bits OR-ed onto a YUV id.  "bt601" is
 # cv2.cvtColor's BT.601 limited range, the default and all there was; "bt601-full" is JFIF (phone cameras, full-range UVC
@@ -352,6 +379,11 @@ K_WARP_YUV = K["MODEL_SCAN"] + 1
 # ... and k_change_blur_stats (boards whose ChangeDetector has a blur kernel of its own, set_change_blur) follows that
 K_CHANGE_BLUR = K_WARP_YUV + 1
 K_ALL = dict(K, WARP_YUV=K_WARP_YUV, CHANGE_BLUR=K_CHANGE_BLUR)  # every id by name (K itself stays as tests/test_model_update_host.py pins it)
+# ... and the kernels of developed mosaics (k_ingest_deep, the warp kernels of k_warp_deep.hip and k_warp_lens_deep.hip) follow
+# one id further on: tests/test_change_blur_host.py pins that K_CHANGE_BLUR is K_ALL's last id and that the id behind it has
+# no name, so that id stays empty and K_ALL stays as it is.  K_EVERY is every id by name.
+K_INGEST_BAYER_DEEP, K_WARP_BAYER_DEEP = K_CHANGE_BLUR + 2, K_CHANGE_BLUR + 3
+K_EVERY = dict(K_ALL, INGEST_BAYER_DEEP=K_INGEST_BAYER_DEEP, WARP_BAYER_DEEP=K_WARP_BAYER_DEEP)
 
 MODEL_FROZEN, MODEL_EVERY, MODEL_UNCHANGED = 0, 1, 2
 MODEL_MODES = {"frozen": MODEL_FROZEN, "every": MODEL_EVERY, "unchanged": MODEL_UNCHANGED}
@@ -441,6 +473,8 @@ def load():
         "cbv_pipeline_hough": (i32, [vp, i32, P(HoughResult)]),
         "cbv_pipeline_add_board": (i32, [vp, P(BoardConfig), P(vp)]),
         "cbv_yuv_to_bgr": (i32, [vp, P(RawFrame), i32, i32, u8p, i32]),
+        "cbv_bayer_to_bgr": (i32, [vp, P(RawFrame), i32, i32, u8p, i32, u8p, i32]),
+        "cbv_pipeline_set_bayer_tables": (i32, [vp, u8p, i32]),
         "cbv_pipeline_upload_raw": (i32, [vp, i32, P(RawFrame)]),
         "cbv_pipeline_set_input_format": (i32, [vp, i32]),
         "cbv_pipeline_host_slot_bytes": (C.c_size_t, [vp]),
@@ -590,14 +624,14 @@ def as_bgr(frame):
 
 def format_id(fmt):
     """CBV_FMT_* of "bgr" | "nv12" | "nv21" | "yuv420p" | "yv12" | "yuyv" | "yvyu" | "uyvy" | "bayer_rggb" | "bayer_bggr" |
-    "bayer_grbg" | "bayer_gbrg".  The three-plane 4:2:0 format goes by libav's name, "yuv420p" (cv2's COLOR_YUV2BGR_I420 /
+    "bayer_grbg" | "bayer_gbrg", or one of those four with "16", "10p" or "12p" behind it (BAYER_DEEP_FORMATS).  The three-plane 4:2:0 format goes by libav's name, "yuv420p" (cv2's COLOR_YUV2BGR_I420 /
     _IYUV); "i420" is an unknown format and raises ValueError.  A Bayer layout goes by its top-left 2 x 2 block read row by
     row (libav's bayer_rggb8, V4L2's SRGGB8); cv2 names the block at (1, 1), so "bayer_rggb" is COLOR_BayerBG2BGR."""
     try:
         name = fmt.lower()
-        return FORMATS[name] if name in FORMATS else BAYER_FORMATS[name]
+        return FORMATS[name] if name in FORMATS else BAYER_FORMATS[name] if name in BAYER_FORMATS else BAYER_DEEP_FORMATS[name]
     except (KeyError, AttributeError):
-        raise ValueError("unknown frame format %r (expected one of %s)" % (fmt, ", ".join(list(FORMATS) + list(BAYER_FORMATS))))
+        raise ValueError("unknown frame format %r (expected one of %s)" % (fmt, ", ".join(list(FORMATS) + list(BAYER_FORMATS) + list(BAYER_DEEP_FORMATS))))
 
 
 def _rows(a, what):
@@ -618,7 +652,9 @@ def raw_frame(frame, fmt, colorspace="bt601"):
     yv12, of shapes [h, w], [h // 2, w // 2], [h // 2, w // 2].  ("i420" is not a name: see format_id.)
     "yuyv" / "yvyu" / "uyvy": [h, w, 2].  "bgr": [h, w, 3].
     "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg": one [h, w] array, w and h even and at least 4; a view whose
-    rows are contiguous is taken as it is, whatever its row stride.
+    rows are contiguous is taken as it is, whatever its row stride.  With "16" behind the name: one uint16 [h, w] array; with
+    "10p": one uint8 [h, w * 5 // 4] array of MIPI RAW10 rows (w a multiple of 4); with "12p": one uint8 [h, w * 3 // 2] array
+    of MIPI RAW12 rows; the row stride is free again (V4L2's bytesperline padding).
     ValueError for other shapes and dtypes, an odd w, and an odd h of a 4:2:0 format.
     `colorspace` (COLORSPACES; YUV formats only) goes into the struct's format id: ValueError for an unknown name, and for
     another colour space than "bt601" with a format that is not YUV."""
@@ -632,6 +668,23 @@ def _raw_frame(frame, fmt):
     """raw_frame in colour space "bt601"."""
     f = format_id(fmt)
     name = fmt.upper()
+    if f & 15 == FMT_BAYER_RGGB and f & BAYER_ENC_MASK:
+        enc = f & BAYER_ENC_MASK
+        a = np.asarray(frame) if not isinstance(frame, (tuple, list)) else None
+        item = 2 if enc == BAYER_16 else 1
+        if a is None or a.dtype != (np.uint16 if enc == BAYER_16 else np.uint8) or a.ndim != 2:
+            raise ValueError("expected one %s 2-D %s mosaic, got %s" % ("uint16" if enc == BAYER_16 else "uint8", name, _describe(frame)))
+        if a.strides[1] != item or a.strides[0] < a.shape[1] * item:
+            a = np.ascontiguousarray(a)
+        group, samples = {BAYER_16: (1, 1), BAYER_10P: (5, 4), BAYER_12P: (3, 2)}[enc]
+        if a.shape[1] % group:
+            raise ValueError("a %s row is a multiple of %d bytes, got %s" % (name, group, a.shape))
+        w, h = a.shape[1] // group * samples, a.shape[0]
+        if h % 2 or w % 2 or min(w, h) < 4:
+            raise ValueError("a %s frame has an even width and height of at least 4, got %dx%d" % (name, w, h))
+        r = RawFrame()
+        r.fmt, r.stride0, r.plane0 = f, a.strides[0], a.ctypes.data
+        return r, w, h, (a,)
     if f & 15 == FMT_BAYER_RGGB:
         a = np.asarray(frame) if not isinstance(frame, (tuple, list)) else None
         if a is None or a.dtype != np.uint8 or a.ndim != 2:

@@ -187,7 +187,7 @@ def yuv_to_bgr(frame, fmt, colorspace="bt601"):
     cameras, full-range UVC modes), "bt709" (decoded video at 720p and above) or "bt709-full" (capture cards in PC range);
     the same fixed-point arithmetic with that colour space's constants (include/cbv.h, CBV_CS_*)."""
     from . import _native as N
-    if isinstance(fmt, str) and fmt.lower() in N.BAYER_FORMATS:
+    if N.is_bayer(fmt):
         raise ValueError("yuv_to_bgr converts YUV frames; a %s mosaic goes to bayer_to_bgr" % fmt)
     raw, w, h, keep = N.raw_frame(frame, fmt, colorspace)
     if raw.fmt == N.FMT_BGR:
@@ -198,21 +198,28 @@ def yuv_to_bgr(frame, fmt, colorspace="bt601"):
     return out
 
 
-def bayer_to_bgr(frame, fmt):
+def bayer_to_bgr(frame, fmt, develop=None):
     """cv2.cvtColor(frame, COLOR_Bayer??2BGR), the bilinear demosaic of an 8-bit mosaic, on the GPU (include/cbv.h,
-    cbv_yuv_to_bgr with a Bayer format): a new uint8 [h, w, 3] array.  `fmt` "bayer_rggb" / "bayer_bggr" / "bayer_grbg" /
+    cbv_bayer_to_bgr): a new uint8 [h, w, 3] array.  `fmt` "bayer_rggb" / "bayer_bggr" / "bayer_grbg" /
     "bayer_gbrg" names the top-left 2 x 2 block read row by row; cv2 names its codes by the block at (1, 1), so
     "bayer_rggb" is COLOR_BayerBG2BGR, "bayer_bggr" COLOR_BayerRG2BGR, "bayer_grbg" COLOR_BayerGB2BGR and "bayer_gbrg"
     COLOR_BayerGR2BGR.  `frame` is one uint8 [h, w] array, w and h even and at least 4; strided views are taken as they are
-    (_native.raw_frame).  No white balance, gamma or colour matrix is applied.  (A BoardPipeline takes such frames
-    directly: upload(fmt=...), set_input_format.)"""
+    (_native.raw_frame).  With "16", "10p" or "12p" behind the name the samples are 10 to 16 bits in a little-endian 16-bit
+    container (one uint16 [h, w] array), or MIPI RAW10 / RAW12 packed rows (uint8 [h, w * 5 // 4] / [h, w * 3 // 2]).
+    `develop` (a `develop.Develop`, a uint8 [3, 2^bits] array with rows B, G, R, or None) is the per-colour table every
+    sample goes through in front of the demosaic: black and white level, white-balance gains and a tone curve.  None is the
+    format's default: the neutral table v * 255 / (2^bits - 1), rounded half up, for the three encodings, and no table at all
+    for an 8-bit mosaic.  No colour matrix is applied.  (A BoardPipeline takes such frames directly: upload(fmt=...),
+    set_input_format.)"""
     from . import _native as N
-    if not (isinstance(fmt, str) and fmt.lower() in N.BAYER_FORMATS):
-        raise ValueError("bayer_to_bgr converts Bayer mosaics (%s), got %r" % (", ".join(N.BAYER_FORMATS), fmt))
+    from .develop import develop_tables
+    if not N.is_bayer(fmt):
+        raise ValueError("bayer_to_bgr converts Bayer mosaics (%s), got %r" % (", ".join(list(N.BAYER_FORMATS) + list(N.BAYER_DEEP_FORMATS)), fmt))
     raw, w, h, keep = N.raw_frame(frame, fmt)
+    tables, bits = develop_tables(develop, raw.fmt)
     ctx = N.context()
     out = np.empty((h, w, 3), np.uint8)
-    ctx.check(ctx.lib.cbv_yuv_to_bgr(ctx.h, raw, w, h, N.ptr(out), w * 3))
+    ctx.check(ctx.lib.cbv_bayer_to_bgr(ctx.h, raw, w, h, N.ptr(tables) if tables is not None else None, bits, N.ptr(out), w * 3))
     return out
 
 

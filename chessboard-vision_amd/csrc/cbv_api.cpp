@@ -505,13 +505,39 @@ int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlane
     return CBV_OK;
 }
 
-int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what)
+int bayer_tables_upload(cbv_ctx* ctx, DevBuf* buf, int fmt, const u8* tables, int bits, BayerDeep* out, const char* who)
+{
+    if (!raw_fmt_bayer(fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a Bayer format", who, fmt);
+    if (!tables) bits = bayer_default_bits(fmt);
+    *out = BayerDeep();
+    if (!tables && !bits) return CBV_OK; // an 8-bit id's default: no table
+    if (!bayer_bits_ok(fmt, bits)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: tables of %d bits do not go with format %d (%s)", who, bits, fmt, raw_fmt_name(fmt));
+    const size_t n = (size_t)1 << bits;
+    std::vector<u8> neutral;
+    if (!tables) { // the neutral table, the same for the three colours
+        neutral.resize(3 * n);
+        bayer_neutral_table(bits, neutral.data());
+        memcpy(neutral.data() + n, neutral.data(), n);
+        memcpy(neutral.data() + 2 * n, neutral.data(), n);
+        tables = neutral.data();
+    }
+    RC(dev_ensure(ctx, buf, 3 * n));
+    CBV_HIP(ctx, hipMemcpyAsync(buf->p, tables, 3 * n, hipMemcpyHostToDevice, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the caller's memory, or this stack's)
+    out->tab = buf->as<u8>();
+    out->bits = bits;
+    return CBV_OK;
+}
+
+int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what, const BayerDeep* deep)
 {
     RawPlanes dev;
     RawGeom r;
     int cs;
     RC(raw_h2d_stage(ctx, raw, w, h, &dev, &r, &cs, what));
-    return launch_ingest(ctx, dev, r, dst, g, 1, cs);
+    BayerDeep d = deep ? *deep : BayerDeep();
+    if (!deep && raw_fmt_enc(r.fmt)) RC(bayer_tables_upload(ctx, &ctx->b, r.fmt, nullptr, 0, &d, what)); // the encoding's default table
+    return launch_ingest_any(ctx, dev, r, dst, g, 1, cs, d);
 }
 
 extern "C" int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride)
@@ -526,6 +552,32 @@ extern "C" int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int
     return CBV_DONE(download(ctx, ctx->a.p, bgr, w * 3, h, bgr_stride));
 }
 
+extern "C" int cbv_bayer_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, const uint8_t* tables, int bits, uint8_t* bgr, int bgr_stride)
+{
+    const char* who = "cbv_bayer_to_bgr";
+    if (!ctx) return cbv_fail(nullptr, CBV_ERR_ARG, "%s: ctx is null", who);
+    if (!raw || !bgr || w <= 0 || h <= 0 || bgr_stride < w * 3) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
+    RC(check_raw_format(ctx, raw->fmt, w, h, who));
+    if (!raw_fmt_bayer(raw->fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d (%s) is not a Bayer format", who, raw->fmt, raw_fmt_name(raw_fmt_layout(raw->fmt)));
+    if (tables && !bayer_bits_ok(raw->fmt, bits))
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: tables of %d bits do not go with format %d (%s)", who, bits, raw->fmt, raw_fmt_name(raw->fmt));
+    CBV_ENTER_DRAINED(ctx);
+    BayerDeep deep;
+    RC(bayer_tables_upload(ctx, &ctx->b, raw->fmt, tables, bits, &deep, who));
+    const Geom g = tight_geom(w, h);
+    RC(dev_ensure(ctx, &ctx->a, g.frame_stride));
+    RC(raw_h2d_convert(ctx, raw, w, h, (u8*)ctx->a.p, g, who, &deep));
+    return CBV_DONE(download(ctx, ctx->a.p, bgr, w * 3, h, bgr_stride));
+}
+
+// the single-frame raw warps have no tables: a sample encoding goes through a pipeline (include/cbv.h)
+static int refuse_bayer_enc(cbv_ctx* ctx, int fmt, const char* who)
+{
+    if (!raw_fmt_enc(raw_fmt_layout(fmt))) return CBV_OK;
+    return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d (%s) is a sample encoding of a Bayer mosaic, which a pipeline warps (cbv_pipeline_set_input_format)", who, fmt,
+                    raw_fmt_name(raw_fmt_layout(fmt)));
+}
+
 extern "C" int cbv_warp_color_profile_raw(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, const cbv_color_profile* profile, const double* M9,
                                           int dw, int dh, int rot180, uint8_t* out, int out_stride)
 {
@@ -534,6 +586,7 @@ extern "C" int cbv_warp_color_profile_raw(cbv_ctx* ctx, const cbv_raw_frame* raw
     if (!raw || !out || !M9 || !profile || w <= 0 || h <= 0 || dw <= 0 || dh <= 0 || dw > 8192 || dh > 8192 || out_stride < dw * 3)
         return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad arguments", who);
     RC(check_raw_format(ctx, raw->fmt, w, h, who)); // (a BGR frame goes to cbv_warp_color_profile)
+    RC(refuse_bayer_enc(ctx, raw->fmt, who));
     ProfileTabs pt;
     RC(profile_tabs_checked(ctx, profile, &pt, who));
     CBV_ENTER_DRAINED(ctx);
@@ -569,6 +622,7 @@ extern "C" int cbv_warp_lens(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int 
     const bool bgr = raw->fmt == CBV_FMT_BGR;
     if (bgr) RC(check_img(ctx, raw->plane0, w, h, raw->stride0, 3, who));
     else RC(check_raw_format(ctx, raw->fmt, w, h, who));
+    if (!bgr) RC(refuse_bayer_enc(ctx, raw->fmt, who));
     const cbv_color_profile none = {};
     const bool profiled = profile && profile->enabled;
     if (!lens || !lens->enabled) { // the lens-free call of the format

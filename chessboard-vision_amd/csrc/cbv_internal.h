@@ -390,12 +390,18 @@ static inline const char* raw_fmt_name(int fmt)
     case CBV_FMT_BAYER_GRBG: return "BAYER_GRBG";
     case CBV_FMT_BAYER_GBRG: return "BAYER_GBRG";
     }
+    if (raw_fmt_bayer(fmt)) { // a layout with a sample encoding (CBV_BAYER_*)
+        static const char* const kDeep[3][4] = {{"BAYER_RGGB16", "BAYER_BGGR16", "BAYER_GRBG16", "BAYER_GBRG16"},
+                                                {"BAYER_RGGB10P", "BAYER_BGGR10P", "BAYER_GRBG10P", "BAYER_GBRG10P"},
+                                                {"BAYER_RGGB12P", "BAYER_BGGR12P", "BAYER_GRBG12P", "BAYER_GBRG12P"}};
+        return kDeep[raw_fmt_enc(fmt) - 1][(fmt >> 4) & 3];
+    }
     return "?";
 }
 // bytes per row of plane `i` of a w-wide frame (0: the format has no such plane)
 static inline int raw_plane_wbytes(int fmt, int w, int i)
 {
-    if (i == 0) return raw_fmt_420(fmt) || raw_fmt_bayer(fmt) ? w : 2 * w;
+    if (i == 0) return raw_fmt_bayer(fmt) ? bayer_row_bytes(fmt, w) : raw_fmt_420(fmt) ? w : 2 * w;
     return i >= raw_fmt_planes(fmt) ? 0 : raw_fmt_planes(fmt) == 3 ? w / 2 : w;
 }
 static inline int raw_plane_rows(int fmt, int h, int i) { return i == 0 ? h : h / 2; }
@@ -422,6 +428,13 @@ static inline RawPlanes tight_raw_planes(int fmt, int w, int h, const u8* base)
     if (n > 2) r.p[2] = r.p[1] + (size_t)(w / 2) * (h / 2);
     return r;
 }
+// How the samples of a mosaic become bytes (include/cbv.h, "developed mosaics"): the device tables [3][1 << bits], B G R.
+// tab == null: none, which only an 8-bit id may have; it then runs k_ingest and the WarpRaw kernels as it always did.
+struct BayerDeep {
+    const u8* tab = nullptr;
+    int bits = 0;
+};
+static inline bool bayer_deep(int fmt, const BayerDeep& d) { return raw_fmt_enc(fmt) != 0 || d.tab != nullptr; }
 // CBV_ERR_ARG, with the format's name, for colour-space bits (CBV_CS_*) on an id that is not one of the YUV formats
 int check_fmt_cs(cbv_ctx* ctx, int fmt, const char* what);
 // CBV_ERR_ARG unless fmt is a YUV format and w (and h, for the 4:2:0 formats) is even, or a Bayer format and w and h are
@@ -435,6 +448,15 @@ void raw_planes_canonical(RawPlanes* planes, RawGeom* r);
 // in memory order.  r.fmt is the layout; cs (raw_fmt_cs: 0 .. 3, YUV only) chooses the colour space: 0 launches k_ingest, the
 // others k_ingest_cs (k_ingest_cs.hip) with that row of kYuvCs
 int launch_ingest(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, int batch, int cs = 0);
+// the same for developed mosaics (k_ingest_deep.hip): r.fmt a Bayer id of any encoding, deep.tab its tables (never null here),
+// deep.bits what bayer_bits_ok admits.  Counted as CBV_K_INGEST_BAYER_DEEP
+int launch_ingest_deep(cbv_ctx* ctx, const u8* mosaic, RawGeom r, u8* dst, Geom g, int batch, BayerDeep deep);
+// launch_ingest or launch_ingest_deep, as bayer_deep(r.fmt, deep) says
+int launch_ingest_any(cbv_ctx* ctx, RawPlanes planes, RawGeom r, u8* dst, Geom g, int batch, int cs, BayerDeep deep);
+// The tables of a developed mosaic on the device: `tables` ([3][1 << bits], host) or, null, the default of `fmt` (the neutral
+// table of bayer_default_bits; none for an 8-bit id: *out is then empty).  CBV_ERR_ARG for bits that do not go with fmt.
+// Synchronous: the copy has landed when it returns.  The caller has made sure nothing in flight reads `buf`.
+int bayer_tables_upload(cbv_ctx* ctx, DevBuf* buf, int fmt, const u8* tables, int bits, BayerDeep* out, const char* who);
 void launch_ingest_cs(cbv_ctx* ctx, const RawPlanes& planes, const RawGeom& r, u8* dst, const Geom& g, int batch, int cs, bool wide);
 // the planes and strides a host frame's format has; null / 0 for the rest, whose fields are not read
 void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides);
@@ -443,7 +465,8 @@ void raw_frame_planes(const cbv_raw_frame* raw, const u8** planes, int* strides)
 // *cs the colour space
 int raw_h2d_stage(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, RawPlanes* dev, RawGeom* r, int* cs, const char* what);
 // ... and from there into a BGR device image
-int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what);
+// (a Bayer frame: *deep are its tables; null = the default of its format, which for a sample encoding is uploaded to ctx->b)
+int raw_h2d_convert(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, u8* dst, Geom g, const char* what, const BayerDeep* deep = nullptr);
 
 // What the warp samples: the frames of a batch, frame 0's pointers.  The launchers turn it into the typed source of the
 // kernels (warp_gather.h, warp_typed_*).
@@ -462,6 +485,8 @@ struct WarpSrc {
     const u8* jpeg_planes;     // JPEG: the decoded planes of frame 0, frame f's jpeg_plane_stride * f bytes behind
     size_t jpeg_plane_stride;
     const JpegDesc* jpeg_descs; // JPEG: device, frame 0's; each frame has its own layout
+    BayerDeep bdeep;           // BAYER: the tables of a developed mosaic (warp_src_raw_deep)
+    bool deep() const { return kind == BAYER && bayer_deep(r.fmt, bdeep); } // ... which k_warp_deep.hip and k_warp_lens_deep.hip warp
     bool raw() const { return kind == YUV || kind == BAYER; }
     bool profiled() const { return kind == PROFILE || ((raw() || kind == JPEG) && ptabs); } // the profile kernels' tiling (WP_ROWS rows a workgroup)
 };
@@ -506,6 +531,20 @@ static inline WarpSrc warp_src_raw(RawPlanes planes, RawGeom r, Geom g, int cs =
     s.planes = planes;
     s.r = r;
     s.cs = cs;
+    return s;
+}
+// A developed mosaic (include/cbv.h; k_warp_deep.hip, k_warp_lens_deep.hip: WarpDeep, WarpDeepProfile): launch_ingest_deep
+// followed by the warp (with ptabs: and the colour profile in between), byte for byte.  r.fmt is a Bayer id of any encoding, the
+// rows are bayer_row_bytes long, and no byte outside the frames' rows is read.  ptabs / np / dst_profile_stride as
+// warp_src_raw_profile takes them.  Counted as CBV_K_WARP_BAYER_DEEP.
+static inline WarpSrc warp_src_raw_deep(RawPlanes planes, RawGeom r, Geom g, BayerDeep deep, const ProfileTabs* ptabs = nullptr, int np = 1,
+                                        size_t dst_profile_stride = 0)
+{
+    WarpSrc s = warp_src_raw(planes, r, g, 0);
+    s.bdeep = deep;
+    s.ptabs = ptabs;
+    s.np = np;
+    s.dst_profile_stride = dst_profile_stride;
     return s;
 }
 // Raw frames with the colour profile applied to the converted taps (k_warp_raw_profile.hip): launch_ingest, then
@@ -767,6 +806,10 @@ int launch_warp_raw_profile_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, i
 int launch_warp_cs(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride, int batch,
                    u32* zero_word, u32* zero_word2);
 int launch_warp_cs_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
+// ... a developed mosaic (WarpSrc::deep), with a profile or without, to: k_warp_deep.hip
+int launch_warp_deep(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride, int batch,
+                     u32* zero_word, u32* zero_word2);
+int launch_warp_deep_mb(cbv_ctx* ctx, WarpSrc src, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2);
 // ... and a source of JPEG planes (warp_src_jpeg), with a profile or without: k_warp_jpeg.hip
 int launch_warp_jpeg(cbv_ctx* ctx, WarpSrc src, const double* Minv9, int dw, int dh, int rot180, u8* dst, int dst_stride, size_t dst_frame_stride,
                      int batch, u32* zero_word, u32* zero_word2);
@@ -803,6 +846,9 @@ int launch_warp_lens_profile(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, con
 // what launch_warp_lens hands a YUV source whose colour space is not 0 to: k_warp_lens_cs.hip
 int launch_warp_lens_cs(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
                         u32* zero_word, u32* zero_word2);
+// what launch_warp_lens hands a developed mosaic (WarpSrc::deep) to, with a profile or without: k_warp_lens_deep.hip
+int launch_warp_lens_deep(cbv_ctx* ctx, WarpSrc src, const LensDev& lens, const LensBoard* tab, int ne, int max_dw, int max_dh, int s0, int batch,
+                          u32* zero_word, u32* zero_word2);
 // cbv_lens -> LensDev; CBV_ERR_ARG for a field that is not finite or a focal length that is not positive
 int lens_checked(cbv_ctx* ctx, const cbv_lens* lens, LensDev* out, const char* who);
 // warp_footprint through the lens: every border pixel of the destination through the full map, one more pixel of margin

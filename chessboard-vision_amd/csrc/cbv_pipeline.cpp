@@ -388,6 +388,7 @@ extern "C" void cbv_pipeline_destroy(cbv_pipeline* p)
     pipeline_frames_free(*P);
     if (P->enhanced) (void)hipFree(P->enhanced);
     dev_free(&P->d_synth);
+    dev_free(&P->d_btab);
     dev_free(&P->d_boards);
     dev_free(&P->d_lens_tab);
     for (cbv_pipeline* q : P->boards) board_free(q); // board 0 (p) included
@@ -761,7 +762,7 @@ extern "C" int cbv_pipeline_download(cbv_pipeline* p, int which, int slot, uint8
             if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream)); // submitted copies of the slot
             RC(dev_ensure(ctx, &ctx->a, P.g.frame_stride + 256));
             if (P.plan.source == FRAMES_PLANES) RC(pipeline_jpeg_slot_bgr(P, slot, (u8*)ctx->a.p)); // k_jpeg_color on the slot's planes
-            else RC(launch_ingest(ctx, slot_planes(P, slot), tight_raw_geom(P.fs.fmt, P.w, P.h), (u8*)ctx->a.p, P.g, 1, P.fs.cs));
+            else RC(launch_ingest_any(ctx, slot_planes(P, slot), tight_raw_geom(P.fs.fmt, P.w, P.h), (u8*)ctx->a.p, P.g, 1, P.fs.cs, P.bdeep));
             src = (const u8*)ctx->a.p;
         }
     } else if (which == 1) {

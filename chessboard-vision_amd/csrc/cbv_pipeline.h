@@ -97,6 +97,10 @@ struct Pipe {
     // either, together with the buffers below, which always match `plan`.
     FrameSettings fs;
     FramePlan plan;
+    // the tables of a Bayer input format (cbv_pipeline_set_bayer_tables; include/cbv.h, "developed mosaics"): d_btab holds them,
+    // bdeep says what they are (tab null: none, an 8-bit id as it always ran).  Set with the format, to its default.
+    DevBuf d_btab;
+    BayerDeep bdeep;
     u8* host_ring = nullptr;
     u8* raw_ring = nullptr;   // [max_frames] slots of plan.slot_bytes; both made on first use, let go by every format change
     u8* plane_ring = nullptr; // [max_frames] slots of plan.plane_slot bytes and 256 more

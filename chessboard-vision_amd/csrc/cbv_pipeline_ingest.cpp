@@ -19,6 +19,7 @@ WarpSrc pipeline_raw_warp_src(const Pipe& P, int slot0, const ProfileTabs* ptabs
 {
     if (P.plan.source == FRAMES_PLANES) return pipeline_jpeg_warp_src(P, slot0, ptabs, np, dst_profile_stride);
     const RawGeom rg = tight_raw_geom(P.fs.fmt, P.w, P.h);
+    if (raw_fmt_bayer(P.fs.fmt) && bayer_deep(P.fs.fmt, P.bdeep)) return warp_src_raw_deep(slot_planes(P, slot0), rg, P.g, P.bdeep, ptabs, np, dst_profile_stride);
     return ptabs ? warp_src_raw_profile(slot_planes(P, slot0), rg, P.g, ptabs, np, dst_profile_stride, P.fs.cs) : warp_src_raw(slot_planes(P, slot0), rg, P.g, P.fs.cs);
 }
 
@@ -68,7 +69,8 @@ extern "C" int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_
         CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return CBV_OK;
     }
-    RC(raw_h2d_convert(ctx, raw, P.w, P.h, P.frames + P.g.frame_stride * slot, P.g, "cbv_pipeline_upload_raw"));
+    // (a mosaic in the pipeline's own format goes through the pipeline's tables, any other Bayer frame through its format's default)
+    RC(raw_h2d_convert(ctx, raw, P.w, P.h, P.frames + P.g.frame_stride * slot, P.g, "cbv_pipeline_upload_raw", fmt == P.fs.fmt ? &P.bdeep : nullptr));
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CBV_OK;
 }
@@ -93,7 +95,34 @@ extern "C" int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt)
     FrameSettings next = P->fs;
     next.fmt = raw_fmt_layout(fmt);
     next.cs = raw_fmt_cs(fmt);
-    return pipeline_set_frames(*P, next, who, true); // both ingest rings go, whatever the format was
+    RC(pipeline_set_frames(*P, next, who, true)); // both ingest rings go, whatever the format was
+    // the tables are the new format's default (pipeline_set_frames has waited for everything that read the old ones)
+    P->bdeep = BayerDeep();
+    if (raw_fmt_bayer(next.fmt)) RC(bayer_tables_upload(P->ctx, &P->d_btab, next.fmt, nullptr, 0, &P->bdeep, who));
+    return CBV_OK;
+}
+
+extern "C" int cbv_pipeline_set_bayer_tables(cbv_pipeline* p, const uint8_t* tables, int bits)
+{
+    const char* who = "cbv_pipeline_set_bayer_tables";
+    int rc;
+    Pipe* owner = frames_owner(p, who, "the pipeline is null", &rc);
+    if (!owner) return rc;
+    Pipe& P = *owner;
+    cbv_ctx* ctx = P.ctx;
+    CBV_ENTER(ctx);
+    if (!raw_fmt_bayer(P.fs.fmt))
+        return cbv_fail(ctx, CBV_ERR_STATE, "%s: the input format is %d (%s), not a Bayer format", who, P.fs.fmt, raw_fmt_name(P.fs.fmt));
+    if (tables && !bayer_bits_ok(P.fs.fmt, bits))
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: tables of %d bits do not go with format %d (%s)", who, bits, P.fs.fmt, raw_fmt_name(P.fs.fmt));
+    // the runs in flight and the conversions of the copy stream read the tables that change here
+    RC(join_scan(P));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (P.copy_stream) CBV_HIP(ctx, hipStreamSynchronize(P.copy_stream));
+    BayerDeep next;
+    RC(bayer_tables_upload(ctx, &P.d_btab, P.fs.fmt, tables, bits, &next, who));
+    P.bdeep = next;
+    return CBV_OK;
 }
 
 extern "C" uint8_t* cbv_pipeline_host_ring(cbv_pipeline* p)
@@ -144,7 +173,7 @@ extern "C" int cbv_pipeline_submit(cbv_pipeline* p, int slot0, int count)
         if (read_ev) CBV_HIP(ctx, hipStreamWaitEvent(P.copy_stream, read_ev, 0));
         hipStream_t caller = ctx->stream;
         ctx->stream = P.copy_stream;
-        const int rc_ingest = P.plan.raw() ? CBV_OK : launch_ingest(ctx, slot_planes(P, slot0), rg, P.frames + P.g.frame_stride * slot0, P.g, count, P.fs.cs);
+        const int rc_ingest = P.plan.raw() ? CBV_OK : launch_ingest_any(ctx, slot_planes(P, slot0), rg, P.frames + P.g.frame_stride * slot0, P.g, count, P.fs.cs, P.bdeep);
         ctx->stream = caller;
         RC(rc_ingest);
     }

@@ -11,9 +11,34 @@
 #include "jpeg_core.h"
 
 // the bit fields of a format id (include/cbv.h)
-static constexpr bool raw_fmt_bayer(int fmt)
+static constexpr bool raw_fmt_bayer8(int fmt)
 {
     return fmt == CBV_FMT_BAYER_RGGB || fmt == CBV_FMT_BAYER_BGGR || fmt == CBV_FMT_BAYER_GRBG || fmt == CBV_FMT_BAYER_GBRG;
+}
+// the sample encoding of a Bayer id (0: bytes; CBV_BAYER_16, _10P, _12P >> 12) and the Bayer ids of every assigned encoding
+enum { BAYER_ENC_8 = 0, BAYER_ENC_16 = CBV_BAYER_16 >> 12, BAYER_ENC_10P = CBV_BAYER_10P >> 12, BAYER_ENC_12P = CBV_BAYER_12P >> 12 };
+static constexpr int raw_fmt_enc(int fmt) { return (fmt & CBV_BAYER_ENC_MASK) >> 12; }
+static constexpr bool raw_fmt_bayer(int fmt) { return raw_fmt_bayer8(fmt & ~CBV_BAYER_ENC_MASK) && raw_fmt_enc(fmt) <= BAYER_ENC_12P; }
+// bytes of a row of w samples of a Bayer id (10P: w % 4 == 0)
+static constexpr int bayer_row_bytes(int fmt, int w)
+{
+    return raw_fmt_enc(fmt) == BAYER_ENC_16 ? 2 * w : raw_fmt_enc(fmt) == BAYER_ENC_10P ? w / 4 * 5 : raw_fmt_enc(fmt) == BAYER_ENC_12P ? w / 2 * 3 : w;
+}
+// The tables of a developed mosaic (include/cbv.h): the bits an encoding's tables may have, its default's (0: the 8-bit ids
+// have no table by default), and the neutral table, v * 255 / M rounded half up, of one colour
+static constexpr bool bayer_bits_ok(int fmt, int bits)
+{
+    return raw_fmt_enc(fmt) == BAYER_ENC_16 ? (bits == 10 || bits == 12 || bits == 14 || bits == 16)
+                                            : bits == (raw_fmt_enc(fmt) == BAYER_ENC_10P ? 10 : raw_fmt_enc(fmt) == BAYER_ENC_12P ? 12 : 8);
+}
+static constexpr int bayer_default_bits(int fmt)
+{
+    return raw_fmt_enc(fmt) == BAYER_ENC_16 ? 16 : raw_fmt_enc(fmt) == BAYER_ENC_10P ? 10 : raw_fmt_enc(fmt) == BAYER_ENC_12P ? 12 : 0;
+}
+static inline void bayer_neutral_table(int bits, uint8_t* t /* [1 << bits] */)
+{
+    const uint32_t M = (1u << bits) - 1;
+    for (uint32_t v = 0; v <= M; v++) t[v] = (uint8_t)((510u * v + M) / (2u * M));
 }
 static inline bool raw_fmt_420(int fmt) { return (fmt & 15) == CBV_FMT_NV12; }
 // the YUV families (of a known layout)
@@ -25,7 +50,8 @@ static constexpr int raw_fmt_cs(int fmt) { return (fmt & CBV_CS_MASK) / CBV_CS_F
 // tightly packed raw frames, planes back to back (the ingest rings round each frame to 256 bytes); fmt BGR: tight_geom's bytes
 static inline size_t raw_frame_bytes(int fmt, int w, int h)
 {
-    return raw_fmt_420(fmt) ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_BGR ? 3 : raw_fmt_bayer(fmt) ? 1 : 2);
+    if (raw_fmt_bayer(fmt)) return (size_t)bayer_row_bytes(fmt, w) * h;
+    return raw_fmt_420(fmt) ? (size_t)w * h * 3 / 2 : (size_t)w * h * (fmt == CBV_FMT_BGR ? 3 : 2);
 }
 
 enum { JPEG_PIECE_WORDS = 9 }; // four states (this round's and the last one's exit, the entry, round 0's exit) and a block count

@@ -183,6 +183,8 @@ int check_raw_format(cbv_ctx* ctx, int fmt, int w, int h, const char* what)
     if (raw_fmt_bayer(fmt)) {
         if (w < 4 || h < 4 || ((w | h) & 1))
             return cbv_fail(ctx, CBV_ERR_ARG, "%s: %s frames need an even width and height of at least 4 (%dx%d)", what, raw_fmt_name(fmt), w, h);
+        if (raw_fmt_enc(fmt) == BAYER_ENC_10P && (w & 3)) // (a RAW10 group is four samples)
+            return cbv_fail(ctx, CBV_ERR_ARG, "%s: %s frames need a width that is a multiple of 4 (%dx%d)", what, raw_fmt_name(fmt), w, h);
         return CBV_OK;
     }
     if (w <= 0 || h <= 0 || (w & 1)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %s frames need an even width (%dx%d)", what, raw_fmt_name(fmt), w, h);
@@ -221,6 +223,8 @@ int launch_ingest(cbv_ctx* ctx, RawPlanes pl, RawGeom r, u8* dst, Geom g, int ba
     RC(check_raw_format(ctx, r.fmt, g.w, g.h, "launch_ingest"));
     if (raw_fmt_cs(r.fmt) || cs < 0 || cs > 3 || (cs && !raw_fmt_yuv(r.fmt)))
         return cbv_fail(ctx, CBV_ERR_ARG, "launch_ingest: colour space %d with layout %d (the layout and the colour space are split where an id enters)", cs, r.fmt);
+    if (raw_fmt_enc(r.fmt)) // (a sample encoding: launch_ingest_deep, k_ingest_deep.hip; the switch below knows the 8-bit ids)
+        return cbv_fail(ctx, CBV_ERR_ARG, "launch_ingest: format %d (%s) is a developed mosaic", r.fmt, raw_fmt_name(r.fmt));
     const int strides[3] = {r.stride0, r.stride1, r.stride2};
     if (batch <= 0 || !dst || g.stride < g.w * 3) return cbv_fail(ctx, CBV_ERR_ARG, "launch_ingest: bad planes or strides");
     RC(check_raw_planes(ctx, r.fmt, g.w, pl.p, strides, "launch_ingest"));

@@ -18,7 +18,7 @@
 // the BGR frame k_ingest would write is never made), with one frame per thread and with four: 52 kernels.  launch_warp and
 // launch_warp_mb hand the other sources to their units: the raw sources that carry a colour profile (WarpRawProfile<FMT>) to
 // k_warp_raw_profile.hip, YUV frames in a colour space other than 0 (WarpSrc::cs) to k_warp_cs.hip, JPEG planes to
-// k_warp_jpeg.hip.
+// k_warp_jpeg.hip, developed mosaics (WarpSrc::deep) to k_warp_deep.hip.
 // Also here: the synthetic frame generator used by bench/tests.
 #include "warp_gather.h"
 
@@ -26,6 +26,7 @@ int launch_warp(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, in
                 int batch, u32* zero_word, u32* zero_word2)
 {
     if (s.cs) return launch_warp_cs(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
+    if (s.deep()) return launch_warp_deep(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     if (s.kind == WarpSrc::JPEG) return launch_warp_jpeg(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     if (s.raw() && s.ptabs) return launch_warp_raw_profile(ctx, s, Minv9, dw, dh, rot180, dst, dst_stride, dst_frame_stride, batch, zero_word, zero_word2);
     const char* who = s.kind == WarpSrc::PROFILE ? "launch_warp_profile" : "launch_warp";
@@ -36,6 +37,7 @@ int launch_warp(cbv_ctx* ctx, WarpSrc s, const double* Minv9, int dw, int dh, in
 int launch_warp_mb(cbv_ctx* ctx, WarpSrc s, const BoardDev* tab, int nb, int maxS, int s0, int batch, u32* zero_word, u32* zero_word2)
 {
     if (s.cs) return launch_warp_cs_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
+    if (s.deep()) return launch_warp_deep_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     if (s.kind == WarpSrc::JPEG) return launch_warp_jpeg_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     if (s.raw() && s.ptabs) return launch_warp_raw_profile_mb(ctx, s, tab, nb, maxS, s0, batch, zero_word, zero_word2);
     return warp_typed_plain(ctx, &s, batch, [&](auto S) { return warp_launch_boards(ctx, "launch_warp_mb", S, tab, nb, maxS, s0, batch, zero_word, zero_word2); });

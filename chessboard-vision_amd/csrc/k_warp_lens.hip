@@ -11,6 +11,7 @@ int launch_warp_lens(cbv_ctx* ctx, WarpSrc s, const LensDev& lens, const LensBoa
                      u32* zero_word, u32* zero_word2)
 {
     if (s.cs) return launch_warp_lens_cs(ctx, s, lens, tab, ne, max_dw, max_dh, s0, batch, zero_word, zero_word2);
+    if (s.deep()) return launch_warp_lens_deep(ctx, s, lens, tab, ne, max_dw, max_dh, s0, batch, zero_word, zero_word2); // (k_warp_lens_deep.hip)
     if ((s.raw() || s.kind == WarpSrc::JPEG) && s.ptabs) return launch_warp_lens_profile(ctx, s, lens, tab, ne, max_dw, max_dh, s0, batch, zero_word, zero_word2);
     const WarpLensTo to = {lens, tab, ne, max_dw, max_dh, s0};
     auto go = [&](auto S) { return warp_launch_lens(ctx, S, to, batch, zero_word, zero_word2); };

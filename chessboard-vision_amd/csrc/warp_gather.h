@@ -4,7 +4,7 @@
 // source's many-frames form (warp_many), the dispatch from a WarpSrc to the typed source (warp_typed_*) and the launch
 // templates.  A unit is its exported launchers: dispatch the source, call the launch template.  Private.
 #pragma once
-#include "cbv_bayer.h"
+#include "cbv_bayer_deep.h"
 #include "cbv_profile_px.h"
 #include "cbv_yuv.h"
 #include "jpeg_core.h"
@@ -96,7 +96,7 @@ struct WarpDst {
 // simplifies every function on its own before it inlines, and the gather split into per-source functions compiles to
 // other instructions than this.)
 // ---------------------------------------------------------------------------
-enum { WARP_BGR, WARP_PROFILE, WARP_YUV, WARP_BAYER, WARP_JPEG };
+enum { WARP_BGR, WARP_PROFILE, WARP_YUV, WARP_BAYER, WARP_JPEG, WARP_DEEP };
 #define WP_ROWS 16 // destination rows per workgroup of WarpProfile: one row of WarpPerspectiveInvoker's 64 x 16 blocks
 
 // BGR frames through cv2.normalize's byte map, which is staged in LDS per frame.  CALC: the map is worked out here from the
@@ -183,6 +183,43 @@ template <int FMT_>
 struct WarpRawProfileCs : WarpRawProfile<FMT_> {
     static constexpr bool CS = true;
     YuvCs cs;
+};
+
+// Developed mosaics (include/cbv.h; k_warp_deep.hip, k_warp_lens_deep.hip: pipelines in raw mode whose input is a Bayer id with a
+// sample encoding or with tables): the Bayer branch of the gather with the 4 x 4 bytes of a fast pixel, and the 3 x 3 of a tap
+// by byte loads, made of developed samples (cbv_bayer_deep.h: unpack, then the site's colour's table) instead of loaded;
+// everything behind them is shared, and the BGR frame k_ingest_deep would write is never made.  The layout's phase bits and the
+// encoding are uniform values of the source, so there is one form for the four layouts and the four encodings.  LDS_: tables
+// of up to 12 bits are staged per workgroup (12 KB); 14- and 16-bit tables are read from global memory through the cache.
+#define WARP_DEEP_LDS_BITS 12
+template <bool LDS_>
+struct WarpDeep {
+    static constexpr int KIND = WARP_DEEP, ROWS = 4, FMT = CBV_FMT_BAYER_RGGB;
+    static constexpr bool TABS = false, CS = false, LDS = LDS_;
+    template <int FPT>
+    struct Lds {
+        u8 deep[LDS_ ? (3 << WARP_DEEP_LDS_BITS) : 4];
+    };
+    const u8* p0;
+    RawGeom r;
+    int sw, sh;
+    DeepDev d;
+    __device__ __forceinline__ int w() const { return sw; }
+    __device__ __forceinline__ int h() const { return sh; }
+};
+template <bool LDS_>
+struct DeepProfileLds : ProfileLds {
+    u8 deep[LDS_ ? (3 << WARP_DEEP_LDS_BITS) : 4];
+};
+// ... through the colour profile: d_profile_px on each developed, demosaiced tap inside the frame, staged and tiled as WarpProfile is
+template <bool LDS_>
+struct WarpDeepProfile : WarpDeep<LDS_> {
+    static constexpr int ROWS = WP_ROWS;
+    static constexpr bool TABS = true;
+    template <int FPT>
+    using Lds = DeepProfileLds<LDS_>;
+    const StaticTabs* st;
+    const ProfileTabs* pt; // the profile's table
 };
 
 // The decoded planes of Motion-JPEG frames (k_warp_jpeg.hip: pipelines in planes mode without enhancement, cbv_warp_jpeg): a
@@ -324,6 +361,21 @@ __device__ __forceinline__ u32 d_bayer_px(const u8* __restrict__ f0, int stride,
     return d_bayer_bgr<FMT>(cx, cy, row[0], row[1], row[2]);
 }
 
+// pixel (x, y) of one developed mosaic, inside the frame, with byte loads: the site is clamped, its neighbourhood lies inside
+__device__ __forceinline__ u32 d_deep_px(const u8* __restrict__ f0, int stride, int w, int h, const u8* __restrict__ tab, const DeepDev& d, int x, int y)
+{
+    const int cx = min(max(x, 1), w - 2), cy = min(max(y, 1), h - 2);
+    u32 row[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const u8* q = f0 + (size_t)(cy + i - 1) * stride;
+        row[i] = 0;
+#pragma unroll
+        for (int j = 0; j < 3; j++) row[i] |= d_deep_byte(tab, d, d_deep_sample(q, cx + j - 1, d.enc), cx + j - 1, cy + i - 1) << (8 * j);
+    }
+    return d_deep_bgr(d.ph, cx, cy, row[0], row[1], row[2]);
+}
+
 // The gather.  FPT frames per thread: the coordinates of a destination pixel depend on the matrix and the pixel, not on the
 // frame, and they are most of the kernel's instructions (about 100 of 190 per output pixel, in double precision): a thread
 // works them out once and samples FPT consecutive frames of the batch with them (bz = the group of FPT frames, blockIdx.z
@@ -358,7 +410,7 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                                             const LensDev* lens = nullptr, K... cs)
 {
     constexpr int KIND = Src::KIND, FMT = Src::FMT;
-    constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV, JPEG = KIND == WARP_JPEG;
+    constexpr bool BGR = KIND == WARP_BGR, PROFILE = KIND == WARP_PROFILE, YUV = KIND == WARP_YUV, JPEG = KIND == WARP_JPEG, DEEP = KIND == WARP_DEEP;
     constexpr bool TABS = Src::TABS, RAW_TABS = TABS && !PROFILE; // the profile's tables are staged; ... for the taps of a raw source
     typedef YuvLay<YUV ? FMT : CBV_FMT_NV12> L; // (only read where YUV)
     constexpr bool NV12 = L::F420 && !L::PLANAR, PLANAR = L::PLANAR;
@@ -366,6 +418,14 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
     warp_zero_words(zero_word, zero_word2);
     bool use_lut = false, on = false, radical = false; // uniform
     if constexpr (BGR) use_lut = Src::CALC || S.norm_lut != nullptr;
+    const u8* __restrict__ deep_tab = nullptr; // DEEP: the tables the samples go through, staged or the device's
+    if constexpr (DEEP) {
+        if constexpr (Src::LDS) {
+            lds_copy(lds.deep, S.d.tab, 3 << S.d.bits);
+            deep_tab = lds.deep;
+            if constexpr (!TABS) __syncthreads(); // (with a profile: behind its tables, below)
+        } else deep_tab = S.d.tab;
+    }
     if constexpr (TABS) {
         lds_copy(lds.sdiv, S.st->sdiv, sizeof(lds.sdiv));
         lds_copy(lds.hdiv, S.st->hdiv, sizeof(lds.hdiv));
@@ -424,6 +484,9 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
             c2_off = (size_t)(t.sy >> 1) * S.r.stride2 + (size_t)(t.sx >> 1);
         } else if constexpr (JPEG) {
             // (the offsets depend on the frame's layout: worked out per frame below)
+        } else if constexpr (DEEP) {
+            fast = t.sx >= 1 && t.sx + 2 < S.sw && t.sy >= 1 && t.sy + 2 < S.sh;
+            tap = (size_t)(t.sy - 1) * S.r.stride0; // of the first of the four rows; the column depends on the encoding
         } else {
             fast = t.sx >= 1 && t.sx + 2 < S.sw && t.sy >= 1 && t.sy + 2 < S.sh;
             tap = (size_t)(t.sy - 1) * S.r.stride0 + (size_t)(t.sx - 1);
@@ -499,6 +562,17 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                                     __builtin_memcpy(&jcr[k][2], c2 + (size_t)r2 * J.s1, 4);
                                 }
                             }
+                        }
+                    } else if constexpr (DEEP) {
+                        // the 4 x 4 bytes of the 8-bit source, made of the developed samples of columns sx - 1 .. sx + 2
+                        const u8* m = S.p0 + (size_t)(f0 + k) * S.r.frame_stride + tap;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            u32 s4[4];
+                            d_deep_row4(m + (size_t)i * S.r.stride0, t.sx - 1, S.d.enc, s4);
+                            rows[k][i] = 0;
+#pragma unroll
+                            for (int j = 0; j < 4; j++) rows[k][i] |= d_deep_byte(deep_tab, S.d, s4[j], t.sx - 1 + j, t.sy - 1 + i) << (8 * j);
                         }
                     } else {
                         const u8* m = S.p0 + (size_t)(f0 + k) * S.r.frame_stride + tap;
@@ -591,6 +665,12 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                         q[1] = d_jpeg_tap(J, W, t.sx, t.sy, 1, 0);
                         q[2] = d_jpeg_tap(J, W, t.sx, t.sy, 0, 1);
                         q[3] = d_jpeg_tap(J, W, t.sx, t.sy, 1, 1);
+                    } else if constexpr (DEEP) {
+                        const u32* w = rows[k];
+                        q[0] = d_deep_bgr(S.d.ph, t.sx, t.sy, w[0], w[1], w[2]);
+                        q[1] = d_deep_bgr(S.d.ph, t.sx + 1, t.sy, w[0] >> 8, w[1] >> 8, w[2] >> 8);
+                        q[2] = d_deep_bgr(S.d.ph, t.sx, t.sy + 1, w[1], w[2], w[3]);
+                        q[3] = d_deep_bgr(S.d.ph, t.sx + 1, t.sy + 1, w[1] >> 8, w[2] >> 8, w[3] >> 8);
                     } else {
                         const u32* w = rows[k];
                         q[0] = d_bayer_bgr<FMT>(t.sx, t.sy, w[0], w[1], w[2]);
@@ -622,6 +702,12 @@ __device__ __forceinline__ void warp_gather(Src S, WarpDst D, u32* __restrict__ 
                         if (t.x1in && t.y0in) q[1] = d_jpeg_px(D, pl, t.sx + 1, t.sy);
                         if (t.x0in && t.y1in) q[2] = d_jpeg_px(D, pl, t.sx, t.sy + 1);
                         if (t.x1in && t.y1in) q[3] = d_jpeg_px(D, pl, t.sx + 1, t.sy + 1);
+                    } else if constexpr (DEEP) {
+                        const u8* fp = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
+                        if (t.x0in && t.y0in) q[0] = d_deep_px(fp, S.r.stride0, S.sw, S.sh, deep_tab, S.d, t.sx, t.sy);
+                        if (t.x1in && t.y0in) q[1] = d_deep_px(fp, S.r.stride0, S.sw, S.sh, deep_tab, S.d, t.sx + 1, t.sy);
+                        if (t.x0in && t.y1in) q[2] = d_deep_px(fp, S.r.stride0, S.sw, S.sh, deep_tab, S.d, t.sx, t.sy + 1);
+                        if (t.x1in && t.y1in) q[3] = d_deep_px(fp, S.r.stride0, S.sw, S.sh, deep_tab, S.d, t.sx + 1, t.sy + 1);
                     } else {
                         const u8* fp = S.p0 + (size_t)(f0 + k) * S.r.frame_stride;
                         if (t.x0in && t.y0in) q[0] = d_bayer_px<FMT>(fp, S.r.stride0, S.sw, S.sh, t.sx, t.sy);
@@ -741,6 +827,9 @@ constexpr int warp_many()
 {
     constexpr bool RAW = Src::KIND == WARP_YUV || Src::KIND == WARP_BAYER, JPEG = Src::KIND == WARP_JPEG;
     constexpr bool PLANAR420 = Src::KIND == WARP_YUV && (Src::FMT & 15) == CBV_FMT_NV12 && (Src::FMT & 0x20); // YUV420P
+    // developed mosaics: two, with a profile or without, under a lens or not.  Sixteen table reads per frame come on top of the
+    // 8-bit source's registers; the forms were not timed against each other
+    if (Src::KIND == WARP_DEEP) return 2;
     if ((RAW || JPEG) && Src::TABS && LENS) return 2;
     if (JPEG) return Src::TABS ? 2 : 4;
 #ifdef RAW_PROFILE_FPT
@@ -782,6 +871,7 @@ static int warp_raw_checked(cbv_ctx* ctx, WarpSrc* s, int batch)
     const char* what = s->kind == WarpSrc::BAYER ? "launch_warp_bayer" : "launch_warp_yuv";
     if (!s->raw()) return cbv_fail(ctx, CBV_ERR_ARG, "%s: not a raw source", what);
     RC(check_raw_format(ctx, s->r.fmt, s->g.w, s->g.h, what));
+    if (s->deep()) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is a developed mosaic (warp_typed_deep)", what, s->r.fmt);
     // (warp_src_raw takes the kind from the format: only a WarpSrc filled by hand can fail this)
     if (s->kind == WarpSrc::BAYER && !raw_fmt_bayer(s->r.fmt)) return cbv_fail(ctx, CBV_ERR_ARG, "%s: format %d is not a Bayer format", what, s->r.fmt);
     if (batch <= 0) return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes or strides", what);
@@ -840,6 +930,24 @@ static int warp_typed_cs(cbv_ctx* ctx, WarpSrc* s, int batch, const char* who, F
     });
 }
 
+// developed mosaics, with a profile or without: k_warp_deep.hip, k_warp_lens_deep.hip
+template <class F>
+static int warp_typed_deep(cbv_ctx* ctx, WarpSrc* s, int batch, const char* who, F&& f)
+{
+    if (!s->deep()) return cbv_fail(ctx, CBV_ERR_ARG, "%s: not a developed mosaic", who);
+    RC(check_raw_format(ctx, s->r.fmt, s->g.w, s->g.h, who));
+    if (batch <= 0 || !s->planes.p[0] || !s->bdeep.tab || !bayer_bits_ok(s->r.fmt, s->bdeep.bits) || s->r.stride0 < bayer_row_bytes(s->r.fmt, s->g.w))
+        return cbv_fail(ctx, CBV_ERR_ARG, "%s: bad planes, strides or tables (%d bits)", who, s->bdeep.bits);
+    const DeepDev d = {s->bdeep.tab, s->bdeep.bits, raw_fmt_enc(s->r.fmt), s->r.fmt & 0x30};
+    auto go = [&](auto lds) -> int {
+        constexpr bool LDS = decltype(lds)::value != 0;
+        const WarpDeep<LDS> D = {s->planes.p[0], s->r, s->g.w, s->g.h, d};
+        if (s->ptabs) return f(WarpDeepProfile<LDS>{D, ctx->tabs, s->ptabs});
+        return f(D);
+    };
+    return s->bdeep.bits <= WARP_DEEP_LDS_BITS ? go(WarpInt<1>()) : go(WarpInt<0>());
+}
+
 // The decoded planes of JPEG frames, PROFILE: with a profile.  Unlike the three above this one decides at compile time, and
 // its callers write `s.ptabs ? <true> : <false>` where they want both: k_warp_jpeg.hip holds both sources, but the lens
 // forms are split over k_warp_lens.hip (WarpJpeg) and k_warp_lens_profile.hip (WarpJpegProfile), and a dispatch that chose
@@ -868,7 +976,7 @@ static int warp_launch_grid(cbv_ctx* ctx, const char* who, const char* layers, i
     const int fpt = batch >= 8 ? MANY : 1, nz = (batch + fpt - 1) / fpt;
     if ((long long)nz * zmul > 65535) return cbv_fail(ctx, CBV_ERR_ARG, "%s: %d %s x %d frames do not fit a launch", who, zmul, layers, batch);
     const dim3 grid((dw + 63) / 64, (dh + Src::ROWS - 1) / Src::ROWS, nz * zmul);
-    constexpr int prof = Src::FMT == CBV_FMT_BGR ? CBV_K_WARP : CBV_K_WARP_YUV;
+    constexpr int prof = Src::KIND == WARP_DEEP ? CBV_K_WARP_BAYER_DEEP : Src::FMT == CBV_FMT_BGR ? CBV_K_WARP : CBV_K_WARP_YUV;
     prof_begin(ctx, prof);
     if (batch >= 8) launch(WarpInt<MANY>(), grid, nz);
     else launch(WarpInt<1>(), grid, nz);

@@ -14,6 +14,7 @@ import numpy as np
 from . import _native as N
 from . import synth as S
 from .board_detection import get_perspective_transform, undistort_points
+from .develop import Develop, develop_tables, load_develop, save_develop  # noqa: F401  (Develop and its JSON belong to this module's surface)
 from .grid_extractor import GridExtractor, SmartGridExtractor
 
 
@@ -720,6 +721,7 @@ class BoardPipeline(_BoardMethods):
         self.board_size = 0
         self._boards = []
         self.input_format = "bgr"
+        self.develop = None
         self.lens = None
 
     def set_lens(self, lens):
@@ -823,7 +825,9 @@ class BoardPipeline(_BoardMethods):
         order, (y, u, v) / (y, v, u)) and "yuyv" / "yvyu" / "uyvy" ([h, w, 2]) are converted to BGR on the GPU (include/cbv.h,
         cbv_pipeline_upload_raw; "i420" is not a name, the format is "yuv420p"), and so are the 8-bit Bayer mosaics
         "bayer_rggb" / "bayer_bggr" / "bayer_grbg" / "bayer_gbrg" (one [h, w] array, named by the top-left 2 x 2 block:
-        cv2's COLOR_BayerBG2BGR is "bayer_rggb"); in raw mode (`configure(enhance=False)` or `(enhance="profile", raw=True)` with a YUV or Bayer
+        cv2's COLOR_BayerBG2BGR is "bayer_rggb") and those of more bits, "...16" (one uint16 [h, w] array), "...10p" and "...12p"
+        (MIPI-packed rows, uint8 [h, w * 5 // 4] / [h, w * 3 // 2]), which go through the pipeline's tables (`set_develop`) when
+        the format is the pipeline's own and through their format's default otherwise; in raw mode (`configure(enhance=False)` or `(enhance="profile", raw=True)` with a YUV or Bayer
         `set_input_format`) the frame is stored as it is.  `colorspace`: of a YUV frame (`set_input_format`); a raw-mode
         ring takes frames of its own format and colour space only."""
         N.colorspace_bits(colorspace, fmt)
@@ -841,10 +845,25 @@ class BoardPipeline(_BoardMethods):
             raise ValueError("a %dx%d %s frame does not fit the pipeline's %dx%d frames" % (w, h, fmt, self.w, self.h))
         self.ctx.check(self.ctx.lib.cbv_pipeline_upload_raw(self.h_, slot, raw))
 
-    def set_input_format(self, fmt, slot_bytes=None, planes=False, colorspace="bt601"):
+    def set_develop(self, develop):
+        """The per-colour tables of the pipeline's Bayer input format (include/cbv.h, cbv_pipeline_set_bayer_tables): a
+        `Develop`, a uint8 [3, 2^bits] array (rows B, G, R), or None for the format's default (the neutral table of a
+        "...16" / "...10p" / "...12p" format, no table for an 8-bit mosaic).  They apply wherever the ring's mosaics become
+        BGR: `submit`, raw mode's warp, `upload` in the pipeline's format, `download(0, slot)` in raw mode, `color_sweep`.
+        Call between runs; detector, model and session state are kept.  RuntimeError when the input format is not Bayer."""
+        # (another input format: the library refuses the call whatever the tables are, so none are built)
+        tables, bits = develop_tables(develop, N.format_id(self.input_format)) if N.is_bayer(self.input_format) else (None, 0)
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_bayer_tables(self.h_, N.ptr(tables) if tables is not None else None, bits))
+        self.develop = develop
+
+    def set_input_format(self, fmt, slot_bytes=None, planes=False, colorspace="bt601", develop=None):
         """Format of the frames the capture side writes into `host_ring()`: "bgr" (default), "nv12", "nv21", "yuv420p"
         (cv2's I420; "i420" itself is an unknown format), "yv12", "yuyv", "yvyu", "uyvy", or an 8-bit Bayer mosaic
-        "bayer_rggb", "bayer_bggr", "bayer_grbg" or "bayer_gbrg" (w and h even and at least 4).  Raw frames cross PCIe as
+        "bayer_rggb", "bayer_bggr", "bayer_grbg" or "bayer_gbrg" (w and h even and at least 4), or one of those four with
+        "16" (10 to 16 bits in a little-endian 16-bit container), "10p" or "12p" (MIPI RAW10 / RAW12 packed rows; "10p": w a
+        multiple of 4) behind it.  `develop` (a `Develop`, a uint8 [3, 2^bits] array, or None for the format's default) gives
+        a Bayer format its per-colour tables: black and white level, white balance, tone curve (`set_develop`; every format
+        change resets them to the default).  Raw frames cross PCIe as
         they are and are converted to BGR on the GPU behind their copy.  The ring is freed here and
         allocated again by the next `host_ring()`: an array that call returned earlier must not be touched any more.
         "mjpeg": a slot holds one baseline JPEG stream (a Motion-JPEG frame) of up to `slot_bytes` bytes (default w * h / 2,
@@ -870,15 +889,20 @@ class BoardPipeline(_BoardMethods):
             raise ValueError("slot_bytes belongs to the \"mjpeg\" format")
         if N.jpeg_planes_id(planes):
             raise ValueError("planes belongs to the \"mjpeg\" format")
+        if develop is not None and not N.is_bayer(fmt):
+            raise ValueError("develop belongs to the Bayer formats, not to %r" % (fmt,))
+        tables = develop_tables(develop, N.format_id(fmt)) if develop is not None else None  # (refused before anything changes)
         self.ctx.check(self.ctx.lib.cbv_pipeline_set_input_format(self.h_, N.format_id(fmt) | bits))
-        self.input_format, self.input_colorspace = fmt.lower(), colorspace.lower()
+        self.input_format, self.input_colorspace, self.develop = fmt.lower(), colorspace.lower(), None
+        if tables is not None:
+            self.set_develop(develop)
 
     def host_ring(self):
         """Pinned host mirror of the frame ring as a numpy array: the capture side writes frames here, `submit` copies
         them to the GPU asynchronously.  [max_frames, h, w, 3] for BGR; [max_frames, h * 3 // 2, w] for the 4:2:0 layouts
         (luma rows, then the chroma rows of NV12 / NV21, or the two chroma planes of yuv420p / yv12 back to back, each
         h // 2 rows of w // 2 bytes); [max_frames, h, w, 2] for YUYV, YVYU and UYVY; [max_frames, h, w] for the Bayer
-        mosaics; [max_frames, slot_bytes] for "mjpeg" (`set_input_format`)."""
+        mosaics (uint16 for "...16"; uint8 [max_frames, h, w * 5 // 4] for "...10p" and [max_frames, h, w * 3 // 2] for "...12p"); [max_frames, slot_bytes] for "mjpeg" (`set_input_format`)."""
         ptr = self.ctx.lib.cbv_pipeline_host_ring(self.h_)
         if not ptr:
             raise RuntimeError(self.ctx.lib.cbv_last_error(self.ctx.h).decode())
@@ -894,6 +918,13 @@ class BoardPipeline(_BoardMethods):
             shape, strides = (h * 3 // 2, w), (w, 1)
         elif self.input_format in N.BAYER_FORMATS:
             shape, strides = (h, w), (w, 1)
+        elif self.input_format in N.BAYER_DEEP_FORMATS:  # [h, w] uint16, or the packed rows as bytes
+            fid = N.format_id(self.input_format)
+            rb = N.bayer_row_bytes(fid, w)
+            if fid & N.BAYER_ENC_MASK == N.BAYER_16:
+                ring = np.frombuffer(buf, dtype=np.uint16)
+                return np.lib.stride_tricks.as_strided(ring, shape=(self.max_frames, h, w), strides=(fs, rb, 2))
+            shape, strides = (h, rb), (rb, 1)
         else:
             shape, strides = (h, w, 2), (w * 2, 2, 1)
         return np.lib.stride_tricks.as_strided(flat, shape=(self.max_frames,) + shape, strides=(fs,) + strides)

@@ -135,7 +135,10 @@ enum {
 /* The enumeration above is closed: callers size arrays by CBV_K_COUNT.  Kernels added since then take the ids behind it,
  * and CBV_K_END is one past the last id cbv_profile_read and cbv_kernel_name know. */
 #define CBV_K_CHANGE_BLUR CBV_K_COUNT /* k_change_blur_stats (cbv_pipeline_set_change_blur) */
-#define CBV_K_END (CBV_K_COUNT + 1)
+/* (CBV_K_COUNT + 1 is no kernel and has the empty name) */
+#define CBV_K_INGEST_BAYER_DEEP (CBV_K_COUNT + 2) /* k_ingest_deep: developed mosaics (CBV_BAYER_*, cbv_pipeline_set_bayer_tables) to BGR */
+#define CBV_K_WARP_BAYER_DEEP (CBV_K_COUNT + 3)   /* the warp kernels of a developed mosaic (raw mode) */
+#define CBV_K_END (CBV_K_COUNT + 4)
 CBV_API int cbv_profile_enable(cbv_ctx* ctx, int kid /* -1 = all, -2 = none */);
 CBV_API int cbv_profile_read(cbv_ctx* ctx, int kid, double* total_ms, long long* launches);
 CBV_API int cbv_profile_reset(cbv_ctx* ctx);
@@ -491,7 +494,7 @@ CBV_API int cbv_pipeline_square_stats(cbv_pipeline* p, int slot, cbv_sq_stats* o
 CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out);
 
 /* ------------------------------------------------------------------ */
-/* camera-native frames (NV12, NV21, yuv420p, YV12, YUYV, YVYU, UYVY, 8-bit Bayer), converted to BGR on the device */
+/* camera-native frames (NV12, NV21, yuv420p, YV12, YUYV, YVYU, UYVY, Bayer mosaics of 8 to 16 bits), converted to BGR on the device */
 /* ------------------------------------------------------------------ */
 /* Cameras deliver YUYV / UYVY / YVYU, hardware decoders NV12 / NV21 and software decoders yuv420p / YV12;
  * cv2.VideoCapture converts them to BGR on a host core before the application sees a frame.  Here the raw frame crosses
@@ -547,8 +550,8 @@ CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out)
 
 /* 8-bit Bayer mosaics (machine-vision cameras, the raw mode of most sensors): one plane of h rows of w bytes, one byte and
  * one colour per pixel, a third of BGR's bytes.  The conversion is the bilinear demosaic of
- * cv2.cvtColor(raw, COLOR_Bayer??2BGR) on 8-bit data (not the _VNG or _EA variants); no white balance, gamma or colour
- * matrix is applied.  A layout is named by its top-left 2 x 2 block, read row by row.  OpenCV names its codes by the block
+ * cv2.cvtColor(raw, COLOR_Bayer??2BGR) on 8-bit data (not the _VNG or _EA variants).  White balance, black and white level and
+ * a tone curve are per-colour tables in front of it ("developed mosaics" below); no colour matrix is applied.  A layout is named by its top-left 2 x 2 block, read row by row.  OpenCV names its codes by the block
  * at (1, 1) instead, so the code of a layout carries the OTHER pair of letters:
  *     id                        rows 0 / 1     cv2 code                                     libav / V4L2
  *     CBV_FMT_BAYER_RGGB 0x04   R G / G B      COLOR_BayerBG2BGR (= COLOR_BayerRGGB2BGR)    bayer_rggb8 / SRGGB8
@@ -578,6 +581,35 @@ CBV_API int cbv_pipeline_hough(cbv_pipeline* p, int slot, cbv_hough_result* out)
 #define CBV_FMT_BAYER_GRBG 0x24
 #define CBV_FMT_BAYER_GBRG 0x34
 
+/* Developed mosaics: sample encodings of more than 8 bits, and per-colour tables in front of the demosaic.
+ * A developed mosaic is  m8(x, y) = T[c(x, y)][min(s(x, y), 2^bits - 1)]:  s is the raw sample at site (x, y), c the colour
+ * the site carries in the layout (above), as the BGR channel index (0 blue, 1 green, 2 red), and T three tables of 2^bits
+ * bytes in B, G, R order.  The clamp on the index is part of the definition: a 16-bit container may hold anything, and no
+ * table is ever read outside.  The BGR frame is the 8-bit demosaic above of m8, edge rule included; nothing else is new
+ * arithmetic.  Black level, white level, white-balance gains and a tone curve are all functions of one sample of one
+ * colour, so they are all one table (the caller builds it; the library evaluates no power function).
+ * The sample encoding is a field of the format id, CBV_BAYER_* OR-ed onto one of the four layouts above; row B of the mosaic:
+ *     field            row bytes  sample x                                                       bits         V4L2 / libav
+ *     0 (the ids above) w         B[x]                                                           8            SRGGB8 / bayer_rggb8
+ *     CBV_BAYER_16      2 w       B[2x] | B[2x+1] << 8            (little-endian container)      10 12 14 16  SRGGB10, 12, 14, 16 / bayer_rggb16le
+ *     CBV_BAYER_10P     5 w / 4   g = x >> 2, i = x & 3: B[5g+i] << 2 | (B[5g+4] >> 2i) & 3      10           SRGGB10P (MIPI RAW10), w % 4 == 0
+ *     CBV_BAYER_12P     3 w / 2   g = x >> 1: even B[3g] << 4 | B[3g+2] & 15,                    12           SRGGB12P (MIPI RAW12)
+ *                                             odd  B[3g+1] << 4 | B[3g+2] >> 4
+ * w and h are even and at least 4 as above, CBV_BAYER_10P also needs w % 4 == 0, and a row stride is at least the row
+ * bytes (V4L2's bytesperline padding is a stride).  Every other value of the field, and colour-space bits on any Bayer
+ * id, are CBV_ERR_ARG.  (GenICam's LSB-first 10p / 12p packings are not these: such cameras go through the 16-bit container.)
+ * The NEUTRAL table of `bits` bits is T[c][v] = (510 v + M) / (2 M) in integer division with M = 2^bits - 1: v 255 / M
+ * rounded half up.  It is the default of the three encodings above (bits 10 for 10P, 12 for 12P, 16 for the container: a
+ * 16-bit table also covers MSB-aligned data).  The 8-bit ids have NO table by default and then run the kernels they always
+ * ran; a table given for them (bits 8) makes them developed mosaics too.
+ * Where ids are taken: cbv_raw_frame::fmt of cbv_yuv_to_bgr (the default table), cbv_bayer_to_bgr and cbv_pipeline_upload_raw,
+ * and cbv_pipeline_set_input_format.  The single-frame raw warps (cbv_warp_color_profile_raw, cbv_warp_lens with a raw
+ * frame) refuse the three encodings with CBV_ERR_ARG and have no tables: a pipeline warps from developed mosaics. */
+#define CBV_BAYER_16       0x1000
+#define CBV_BAYER_10P      0x2000
+#define CBV_BAYER_12P      0x3000
+#define CBV_BAYER_ENC_MASK 0xF000
+
 /* One raw frame in host memory.  stride2 and plane2 are read only for the three-plane formats (YUV420P, YV12): stride2
  * lies in what was padding and plane2 behind what was the end of the struct, so a caller built against the 32-byte struct
  * of the two-plane formats keeps working. */
@@ -590,8 +622,13 @@ typedef struct {
     const uint8_t* plane2;  /* YUV420P's V or YV12's U plane */
 } cbv_raw_frame;
 
-/* host in, host out: the cvtColor call on its own (fmt = any CBV_FMT_* but BGR, the Bayer mosaics included) */
+/* host in, host out: the cvtColor call on its own (fmt = any CBV_FMT_* but BGR, the Bayer mosaics included; a
+ * CBV_BAYER_* encoding is developed with its default table) */
 CBV_API int cbv_yuv_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, uint8_t* bgr, int bgr_stride);
+/* host in, host out: one developed mosaic to BGR.  raw->fmt is a Bayer id of any encoding; tables = [3][1 << bits] bytes,
+ * B G R, or NULL for the format's default (bits is then ignored; an 8-bit id: no table, cbv_yuv_to_bgr's result).
+ * CBV_ERR_ARG: not a Bayer id, a size or stride the format refuses, bits that do not go with the encoding. */
+CBV_API int cbv_bayer_to_bgr(cbv_ctx* ctx, const cbv_raw_frame* raw, int w, int h, const uint8_t* tables, int bits, uint8_t* bgr, int bgr_stride);
 /* cbv_warp_color_profile on one camera-native frame (any CBV_FMT_* but BGR): = cbv_yuv_to_bgr, then
  * cbv_apply_color_profile, then cbv_warp_perspective (+ rotate 180), byte for byte, in one kernel (k_warp_raw_profile):
  * the four taps are converted (YUV) or demosaiced (Bayer), the profile is applied to each tap inside the frame, and they
@@ -618,6 +655,16 @@ CBV_API int cbv_pipeline_upload_raw(cbv_pipeline* p, int slot, const cbv_raw_fra
  * written; cbv_pipeline_upload (BGR), cbv_pipeline_synth and cbv_pipeline_upload_raw in another format return
  * CBV_ERR_STATE, cbv_pipeline_download(which = 0) converts the slot on demand.  One format per pipeline at a time. */
 CBV_API int cbv_pipeline_set_input_format(cbv_pipeline* p, int fmt);
+/* The tables of a pipeline whose input format is a Bayer id (developed mosaics, above): [3][1 << bits] bytes, B G R, copied
+ * by the call.  tables == NULL restores the format's default (bits is ignored).  cbv_pipeline_set_input_format resets them to
+ * the new format's default.  They are used wherever the ring's mosaics become BGR: cbv_pipeline_submit's conversion, raw
+ * mode's warp (no BGR ring exists under CBV_SKIP_ENHANCE_PROFILE_RAW, as for 8-bit mosaics), cbv_pipeline_upload_raw of a
+ * frame in the pipeline's format, cbv_pipeline_download(which = 0) in raw mode, cbv_pipeline_color_sweep.  Call it between
+ * runs: it waits for the runs and copies in flight.  Detector, model and session state are kept, as with
+ * cbv_pipeline_set_profile.  On the pipeline only (a board handle: CBV_ERR_STATE); CBV_ERR_STATE when the input format is
+ * not a Bayer id; CBV_ERR_ARG when bits does not go with the encoding (8 / 10, 12, 14 or 16 / 10 / 12), and then nothing
+ * has changed.  Frames converted earlier stay as they were converted. */
+CBV_API int cbv_pipeline_set_bayer_tables(cbv_pipeline* p, const uint8_t* tables, int bits);
 /* bytes from one host-ring slot to the next in the current format (a multiple of 256); 0 for a board handle */
 CBV_API size_t cbv_pipeline_host_slot_bytes(cbv_pipeline* p);
 
