@@ -174,7 +174,7 @@ class SessionConfig(C.Structure):
     """cbv_session_config: the game session of a board (include/cbv.h)."""
     _fields_ = [("rule", C.c_int32), ("stability_required", C.c_int32), ("cooldown_frames", C.c_int32),
                 ("scan_period", C.c_int32), ("max_diff", C.c_int32), ("smart_scan", C.c_int32),
-                ("online", C.c_int32), ("radar", C.c_int32)]
+                ("online", C.c_int32), ("radar", C.c_int32), ("tone", C.c_int32)]
 
 
 class SessionMove(C.Structure):
@@ -202,6 +202,24 @@ class SessionEvent(C.Structure):
 
 class SessionRadar(C.Structure):
     _fields_ = [("lifted", C.c_int8), ("destinations", C.c_uint64)]
+
+
+class ToneSums(C.Structure):
+    """cbv_tone_sums: the B, G, R sums and the pixel count of a square's centre disc."""
+    _fields_ = [("sum", C.c_uint32 * 3), ("cnt", C.c_uint32)]
+
+
+class ToneModel(C.Structure):
+    """cbv_tone_model: centroid[light, dark][white piece, black piece][b, g, r], the dead zone's margin."""
+    _fields_ = [("centroid", ((C.c_double * 3) * 2) * 2), ("margin", C.c_double), ("calibrated", C.c_int32), ("pad", C.c_int32)]
+
+
+class ToneResult(C.Structure):
+    _fields_ = [("white", C.c_uint64), ("black", C.c_uint64)]
+
+
+class ToneReport(C.Structure):
+    _fields_ = [("samples", (C.c_int32 * 2) * 2), ("D", C.c_double * 2), ("misclassified", C.c_uint64), ("undecided", C.c_uint64)]
 
 
 class SweepSetting(C.Structure):
@@ -384,6 +402,9 @@ K_ALL = dict(K, WARP_YUV=K_WARP_YUV, CHANGE_BLUR=K_CHANGE_BLUR)  # every id by n
 # no name, so that id stays empty and K_ALL stays as it is.  K_EVERY is every id by name.
 K_INGEST_BAYER_DEEP, K_WARP_BAYER_DEEP = K_CHANGE_BLUR + 2, K_CHANGE_BLUR + 3
 K_EVERY = dict(K_ALL, INGEST_BAYER_DEEP=K_INGEST_BAYER_DEEP, WARP_BAYER_DEEP=K_WARP_BAYER_DEEP)
+# ... and k_piece_tone (piece colour per square: set_tones, tone_sums_image) two ids further on, under a name of its own: the
+# id behind K_WARP_BAYER_DEEP stays without a name (tests/test_bayer_deep_host.py pins that), and K_EVERY stays as it is
+K_TONE = K_WARP_BAYER_DEEP + 2
 
 MODEL_FROZEN, MODEL_EVERY, MODEL_UNCHANGED = 0, 1, 2
 MODEL_MODES = {"frozen": MODEL_FROZEN, "every": MODEL_EVERY, "unchanged": MODEL_UNCHANGED}
@@ -530,6 +551,14 @@ def load():
         "cbv_warp_lens": (i32, [vp, P(RawFrame), i32, i32, P(ColorProfile), P(LensStruct), vp, i32, i32, i32, u8p, i32]),
         "cbv_warp_jpeg_lens": (i32, [vp, vp, C.c_size_t, P(ColorProfile), P(LensStruct), vp, i32, i32, i32, u8p, i32, P(C.c_int32)]),
         "cbv_pipeline_set_lens": (i32, [vp, P(LensStruct)]),
+        "cbv_tone_sums_image": (i32, [vp, P(HostImage), P(Roi), i32, P(ToneSums)]),
+        "cbv_tone_calibrate_host": (i32, [P(ToneSums), vp, dbl, P(ToneModel), P(ToneReport)]),
+        "cbv_tone_classify_host": (i32, [P(ToneModel), P(ToneSums), i32, P(C.c_uint64), P(C.c_uint64)]),
+        "cbv_pipeline_set_tones": (i32, [vp, P(ToneModel)]),
+        "cbv_pipeline_tone_sums": (i32, [vp, i32, P(ToneSums)]),
+        "cbv_pipeline_tones": (i32, [vp, i32, i32, P(ToneResult)]),
+        "cbv_session_walk_tones": (i32, [P(SessionConfig), P(SessionState), P(FrameResult), P(NoiseResult), i32, P(SessionEvent), i32,
+                                         P(i32), P(SessionRadar), P(ToneResult), P(SessionMove), P(i32)]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale

@@ -78,7 +78,7 @@ void dev_free(DevBuf* b)
 static const char* kKernelNames[CBV_K_END] = {
     "k_color_lab_hist", "k_clahe_lut", "k_clahe_apply", "k_bilateral", "k_sharpen", "k_norm_lut", "k_normalize",
     "k_warp", "k_squares", "k_gray_blur_hist", "k_otsu", "k_threshold", "k_scan", "k_synth", "k_reset_aux", "k_hough", "k_ingest", "k_model_scan",
-    "k_warp_yuv", "k_change_blur_stats", "", "k_ingest_deep", "k_warp_deep"};
+    "k_warp_yuv", "k_change_blur_stats", "", "k_ingest_deep", "k_warp_deep", "", "k_piece_tone"};
 
 static hipEvent_t prof_get_event(cbv_ctx* ctx)
 {

@@ -709,9 +709,11 @@ struct SessionDev {
 int launch_scan_session(cbv_ctx* ctx, const SquareDesc* descs, ScanParams sp, const u8* gray, size_t gray_frame_stride,
                         const u8* decisions, u8* ref, ScanState* state, u8* flags, int count, const u64* check,
                         const SessionDev* ses, int first_round, u16* hist);
-// packing, NoiseHandler and the session's walk of one round: frames [resume, count) of the run
+// packing, NoiseHandler and the session's walk of one round: frames [resume, count) of the run; `tones` = the frames' piece
+// tones for the rules' tie-break (cfg.tone), or null
 int launch_session_walk(cbv_ctx* ctx, const u8* flags, int n, cbv_frame_result* results, int count, cbv_noise_state* noise_state,
-                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round, cbv_session_radar* radar);
+                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round, cbv_session_radar* radar,
+                        const cbv_tone_result* tones);
 // a board event between two segments of a run (cbv_pipeline_session_sync): *ev is read now and travels with the launch
 int launch_session_event(cbv_ctx* ctx, SessionDev* ses, const cbv_session_event* ev);
 // the wave generator alone, `reps` times on the position at the head of *state_dev (tests, timing)
@@ -791,7 +793,17 @@ struct BoardDev {
     // the board's colour profile (cbv_pipeline_set_profile): its device table in the profile modes (enabled = 0 in it: the
     // board's taps stay as they are), null otherwise; read by k_warp_boards of the sources with a profile
     const ProfileTabs* ptabs;
+    // piece tones (cbv_pipeline_set_tones; k_tone.hip): all null while the board's tones are off, and k_piece_tone_boards
+    // leaves the board at once
+    cbv_tone_sums* tone_sums;        // [slot][CBV_MAX_SQUARES]
+    cbv_tone_result* tone_res;       // [slot]
+    const cbv_tone_model* tone_model; // the board's model (calibrated)
 };
+// k_piece_tone (k_tone.hip).  The sums of `batch` frames of n squares, explicit arguments: out[frame][CBV_MAX_SQUARES];
+// only w, h, src_off, stride and cnt[0] of a descriptor are read, and cn must be 3
+int launch_piece_tone(cbv_ctx* ctx, const u8* src, size_t src_frame_stride, const SquareDesc* descs, int n, cbv_tone_sums* out, int batch);
+// ... and of every board of `tab` with tones on, then their records: two launches for all boards of a chunk
+int launch_piece_tone_boards(cbv_ctx* ctx, const BoardDev* tab, int nb, int s0, int batch);
 ScanParams scan_params(const cbv_pipeline_config& cfg, bool calibrated);
 // per-pass HoughCfg of a board (layout and maxc as launch_hough / launch_hough_second set them); returns the LDS bytes
 // of each pass, 0 when the squares cannot run (the single-board launchers' checks)

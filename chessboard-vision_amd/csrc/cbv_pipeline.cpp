@@ -141,6 +141,9 @@ static BoardDev board_dev(const Board& q, size_t lds[2])
     T.over_src = c.use_hough ? (const u32*)q.d_hough_over.p : nullptr;
     T.over_dst = q.over_h;
     T.ptabs = (const ProfileTabs*)q.d_ptabs.p;
+    T.tone_sums = q.tones ? (cbv_tone_sums*)q.d_tone_sums.p : nullptr;
+    T.tone_res = q.tones ? (cbv_tone_result*)q.d_tone_res.p : nullptr;
+    T.tone_model = q.tones ? (const cbv_tone_model*)q.d_tone_model.p : nullptr;
     return T;
 }
 
@@ -152,7 +155,7 @@ int pipeline_tables(Pipe& P)
     cbv_ctx* ctx = P.ctx;
     const int nb = (int)P.boards.size();
     P.tab.resize(nb);
-    P.any_hough = P.any_adaptive = P.any_session = P.any_own_blur = P.profile_on = false;
+    P.any_hough = P.any_adaptive = P.any_session = P.any_own_blur = P.profile_on = P.any_tones = false;
     P.hough_lds[0] = P.hough_lds[1] = 0;
     P.max_px = P.max_S = P.n_squares = 0;
     for (int k = 0; k < nb; k++) {
@@ -171,6 +174,7 @@ int pipeline_tables(Pipe& P)
         P.any_adaptive = P.any_adaptive || q.adaptive();
         P.any_session = P.any_session || q.session;
         P.any_own_blur = P.any_own_blur || q.own_blur();
+        P.any_tones = P.any_tones || q.tones;
         P.profile_on = P.profile_on || (P.profile_only && q.profile.enabled); // no board has one: the plain warp, no table is read
         P.max_px = std::max(P.max_px, q.max_px);
         P.max_S = std::max(P.max_S, q.cfg.board_size);
@@ -272,6 +276,7 @@ static int board_setup(const Pipe& P, Board& b, const cbv_pipeline_config& cfg)
     RC(dev_ensure(ctx, &b.d_var, off * 8)); // variance plane, then its square root
     b.calibrated = false;
     b.session = false; // a session belongs to the configuration it began on
+    b.tones = false;   // ... and so do the tones: their model was calibrated on its squares
     RC(dev_ensure(ctx, &b.d_state, sizeof(ScanState) * n));
     RC(dev_ensure(ctx, &b.d_results, sizeof(cbv_frame_result) * P.max_frames));
     const size_t want = sizeof(cbv_frame_result) * (size_t)P.max_frames + 16; // (max_frames is fixed: allocated once)
@@ -324,7 +329,7 @@ static void board_free(cbv_pipeline* p)
     if (b.warped) (void)hipFree(b.warped);
     DevBuf* bufs[] = {&b.d_descs, &b.d_masks, &b.d_gray, &b.d_stats, &b.d_ref, &b.d_state, &b.d_results, &b.d_flags, &b.d_dec, &b.d_mean,
                       &b.d_var, &b.d_noise, &b.d_noise_state, &b.d_hough, &b.d_check, &b.d_hough_over, &b.d_session, &b.d_hist, &b.d_radar,
-                      &b.d_cgray, &b.d_ptabs};
+                      &b.d_cgray, &b.d_ptabs, &b.d_tone_sums, &b.d_tone_res, &b.d_tone_model};
     for (auto d : bufs) dev_free(d);
     delete p;
 }

@@ -48,6 +48,11 @@ struct Board {
     // its device table, which exists in those modes whether the profile is enabled or not
     cbv_color_profile profile = {};
     DevBuf d_ptabs;
+    // piece tones (cbv_pipeline_set_tones): the model, its device copy, and per slot the 64 tone sums and the record; the
+    // buffers are made when the board first enables tones
+    bool tones = false;
+    cbv_tone_model tone_model = {};
+    DevBuf d_tone_sums, d_tone_res, d_tone_model;
 };
 
 struct Pipe;
@@ -158,6 +163,7 @@ struct Pipe {
     bool any_adaptive = false; // some board's model follows the frames: k_model_scan runs in front of the temporal scan
     bool any_session = false;  // some board runs a game session: the boards' scans are launched board by board
     bool any_own_blur = false; // some board's ChangeDetector has a blur kernel of its own: k_change_blur_stats runs behind the statistics
+    bool any_tones = false;    // some board's tones are on: k_piece_tone runs behind the warp of every chunk
     size_t hough_lds[2] = {0, 0};
     int max_px = 0, max_S = 0;
     int n_squares = 0; // the squares that exist, the boards' n_rois summed: sizes the statistics kernels' workgroups

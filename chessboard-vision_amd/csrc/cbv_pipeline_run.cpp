@@ -23,6 +23,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     if (nb > 1) {
         const BoardDev* tab = (const BoardDev*)P.d_boards.p;
         if (!P.lens_on) RC(launch_warp_mb(ctx, src, tab, nb, P.max_S, s0, b, work, retry0));
+        if (P.any_tones) RC(launch_piece_tone_boards(ctx, tab, nb, s0, b));
         RC(launch_squares_pre5_stats_mb(ctx, tab, nb, P.n_squares, s0, b, P.any_hough, work, P.max_px));
         if (P.any_own_blur) RC(launch_change_blur_stats_mb(ctx, tab, nb, P.n_squares, s0, b, P.max_px));
         if (P.any_hough) RC(launch_hough_mb(ctx, tab, nb, s0, work, CBV_MAX_SQUARES * nb * b, P.hough_lds[0], retry, retry_base, 0));
@@ -34,6 +35,7 @@ static int pipeline_chunk_boards(Pipe& P, const u8* res, NormSrc norm, int s0, i
     u8* dec = T.dec + (size_t)CBV_MAX_SQUARES * s0;
     cbv_hough_result* hres = T.hough ? T.hough + (size_t)CBV_MAX_SQUARES * s0 : nullptr;
     if (!P.lens_on) RC(launch_warp(ctx, src, T.Minv, T.S, T.S, T.rot180, wdst, T.S * 3, T.warped_stride, b, work, retry0));
+    if (P.any_tones) RC(launch_piece_tone_boards(ctx, (const BoardDev*)P.d_boards.p, 1, s0, b)); // (table-driven for one board too)
     RC(launch_squares_pre5_stats(ctx, wdst, T.warped_stride, T.descs, T.n, gray, T.plane_total, T.mean, T.sd, T.masks, T.z_thresh,
                                  T.stats + (size_t)T.n * s0, b, dec, T.want_hough, work, hres, P.b0().max_px));
     if (P.any_own_blur)
@@ -73,6 +75,7 @@ static int board_scan(Pipe& P, Board& q, const BoardDev& T, int slot0, int count
     SessionDev* ses = (SessionDev*)q.d_session.p;
     u16* hist = (u16*)q.d_hist.p + (size_t)CBV_MAX_SQUARES * slot0;
     cbv_session_radar* radar = q.ses_cfg.radar ? (cbv_session_radar*)q.d_radar.p + slot0 : nullptr;
+    const cbv_tone_result* tones = q.ses_cfg.tone ? T.tone_res + slot0 : nullptr; // the rules' tie-break (begin checked that tones are on)
     // The run is cut at the board events that fall inside it (cbv_pipeline_session_sync): an event changes the smart mask,
     // so the frames behind it must not be scanned with the check sets of the board that was.  Each segment is the rounds
     // above on its own frames, k_session_event sits between them on the same stream, and nothing waits for the host.  With
@@ -96,7 +99,7 @@ static int board_scan(Pipe& P, Board& q, const BoardDev& T, int slot0, int count
             RC(launch_scan_session(ctx, T.descs, T.sp, gray + T.plane_total * a, T.plane_total, dec + sq0, T.ref, T.state, flags + sq0, len,
                                    check ? check + a : nullptr, ses, k == 0, hist + sq0));
             RC(launch_session_walk(ctx, flags + sq0, T.n, T.results + slot0 + a, len, T.noise_state, T.noise + slot0 + a, smir, ses, k == 0,
-                                   radar ? radar + a : nullptr));
+                                   radar ? radar + a : nullptr, tones ? tones + a : nullptr));
             prof_end(ctx, CBV_K_SCAN);
         }
         a = b;

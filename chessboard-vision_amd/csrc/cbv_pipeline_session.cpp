@@ -27,8 +27,10 @@ extern "C" int cbv_pipeline_session_begin(cbv_pipeline* p, const cbv_session_con
         cfg->stability_required > frames_max || cfg->cooldown_frames < 0 || cfg->cooldown_frames > frames_max || cfg->scan_period < 0 || cfg->max_diff < 0 ||
         !ses_config_ok(cfg))
         return cbv_fail(ctx, CBV_ERR_ARG, "cbv_pipeline_session_begin: bad configuration (rule %d, stability_required %d, cooldown_frames %d, scan_period %d, max_diff %d, "
-                        "online %d, radar %d; online needs CBV_SESSION_RULE_INFER)",
-                        cfg->rule, cfg->stability_required, cfg->cooldown_frames, cfg->scan_period, cfg->max_diff, cfg->online, cfg->radar);
+                        "online %d, radar %d, tone %d; online needs CBV_SESSION_RULE_INFER)",
+                        cfg->rule, cfg->stability_required, cfg->cooldown_frames, cfg->scan_period, cfg->max_diff, cfg->online, cfg->radar, cfg->tone);
+    if (cfg->tone && !B.tones)
+        return cbv_fail(ctx, CBV_ERR_STATE, "cbv_pipeline_session_begin: cfg.tone needs the board's tones (cbv_pipeline_set_tones), which are off");
     std::vector<SessionDev> host(1);
     memset(host.data(), 0, sizeof(SessionDev));
     host[0].cfg = *cfg;

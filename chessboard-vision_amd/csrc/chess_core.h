@@ -427,8 +427,17 @@ CBV_HD inline void cc_gen_legal(const cbv_pos* b, cbv_movelist* out, cbv_movelis
         if (cc_king_safe(b, pseudo->m[i])) cc_add(out, pseudo->m[i]);
 }
 
-// cbv_game_process_occupancy on a POD board; `legal` = its legal moves
-CBV_HD inline int cc_process_occupancy(cbv_pos* b, const cbv_movelist* legal, cc_u64 vision, cbv_move* move_out)
+// The tie-break by piece tones (include/cbv_chess.h): is candidate m contradicted?  Its destination looks like a piece of
+// the side NOT to move.  tone_w / tone_b: square-numbered sets; a square in both or in neither is undecided.
+CBV_HD inline bool cc_tone_contradicted(const cbv_pos* b, cbv_move m, cc_u64 tone_w, cc_u64 tone_b)
+{
+    const cc_u64 bit = cc_bit(cc_to(m));
+    const cc_u64 theirs = b->turn ? tone_b & ~tone_w : tone_w & ~tone_b;
+    return (theirs & bit) != 0;
+}
+
+// cbv_game_process_occupancy_tones on a POD board; `legal` = its legal moves
+CBV_HD inline int cc_process_occupancy_tones(cbv_pos* b, const cbv_movelist* legal, cc_u64 vision, cc_u64 tone_w, cc_u64 tone_b, cbv_move* move_out)
 {
     *move_out = CBV_MOVE_NONE;
     const cc_u64 logical = cc_occupancy(b);
@@ -474,14 +483,22 @@ CBV_HD inline int cc_process_occupancy(cbv_pos* b, const cbv_movelist* legal, cc
     }
     if (nv == 1 && na == 0) { // capture: the attacker left and now stands on a square that was occupied (:162-183)
         const int src = cc_msb(vanished);
-        int n = 0;
-        cbv_move cand = CBV_MOVE_NONE;
+        int n = 0, kept = 0; // captures; those the tones do not contradict
+        cbv_move cand = CBV_MOVE_NONE, cand_kept = CBV_MOVE_NONE;
         for (int i = 0, cnt = cc_stored(legal); i < cnt; i++) {
             const cbv_move m = legal->m[i];
             if (cc_from(m) == src && cc_capture(b, m) && (vision & cc_bit(cc_to(m)))) {
                 if (n == 0) cand = m;
                 n++;
+                if (!cc_tone_contradicted(b, m, tone_w, tone_b)) {
+                    if (kept == 0) cand_kept = m;
+                    kept++;
+                }
             }
+        }
+        if (n > 1 && kept == 1) { // the tie-break: one capture left
+            cand = cand_kept;
+            n = 1;
         }
         if (n == 1) {
             *move_out = cand;
@@ -493,9 +510,16 @@ CBV_HD inline int cc_process_occupancy(cbv_pos* b, const cbv_movelist* legal, cc
     return CBV_GAME_NO_VALID_CHANGE;
 }
 
-// cbv_game_infer_move on a POD board; `legal` = its legal moves, `cand` is scratch.  Returns the number of distinct
-// candidates, *move_out is set when it is exactly one.
-CBV_HD inline int cc_infer_move(const cbv_pos* b, const cbv_movelist* legal, cbv_movelist* cand, cc_u64 vision, cbv_move* move_out)
+// cbv_game_process_occupancy on a POD board: no tone is decided, nothing is contradicted
+CBV_HD inline int cc_process_occupancy(cbv_pos* b, const cbv_movelist* legal, cc_u64 vision, cbv_move* move_out)
+{
+    return cc_process_occupancy_tones(b, legal, vision, 0, 0, move_out);
+}
+
+// cbv_game_infer_move_tones on a POD board; `legal` = its legal moves, `cand` is scratch.  Returns the number of distinct
+// candidates (before the tie-break), *move_out is set when it is exactly one or the tie-break leaves exactly one.
+CBV_HD inline int cc_infer_move_tones(const cbv_pos* b, const cbv_movelist* legal, cbv_movelist* cand, cc_u64 vision, cc_u64 tone_w, cc_u64 tone_b,
+                                      cbv_move* move_out)
 {
     *move_out = CBV_MOVE_NONE;
     const cc_u64 logical = cc_occupancy(b);
@@ -520,7 +544,22 @@ CBV_HD inline int cc_infer_move(const cbv_pos* b, const cbv_movelist* legal, cbv
         if ((missing & cc_bit(cc_from(m))) && cc_capture(b, m) && (vision & cc_bit(cc_to(m))) && !cc_has(cand, m)) cc_add(cand, m);
     }
     if (cand->n == 1) *move_out = cand->m[0];
+    else if (cand->n > 1 && (tone_w | tone_b)) { // the tie-break
+        int kept = 0;
+        cbv_move last = CBV_MOVE_NONE;
+        for (int i = 0, cnt = cc_stored(cand); i < cnt; i++)
+            if (!cc_tone_contradicted(b, cand->m[i], tone_w, tone_b)) {
+                last = cand->m[i];
+                kept++;
+            }
+        if (kept == 1) *move_out = last;
+    }
     return cand->n;
+}
+
+CBV_HD inline int cc_infer_move(const cbv_pos* b, const cbv_movelist* legal, cbv_movelist* cand, cc_u64 vision, cbv_move* move_out)
+{
+    return cc_infer_move_tones(b, legal, cand, vision, 0, 0, move_out);
 }
 
 // ROI-numbered bits (8 * row + col, row 0 = rank 8) <-> python-chess square bits: the rows swap, i.e. the bytes

@@ -307,7 +307,7 @@ static const char* kStatus[] = {"no_valid_change", "move_confirmed", "illegal_mo
                                 "en_passant_confirmed", "capture_confirmed", "ambiguous_capture"};
 const char* cbv_game_status_name(int status) { return (status >= 0 && status < 7) ? kStatus[status] : ""; }
 
-int cbv_game_process_occupancy(cbv_board* b, uint64_t vision, cbv_move* move_out)
+int cbv_game_process_occupancy_tones(cbv_board* b, uint64_t vision, uint64_t tone_white, uint64_t tone_black, cbv_move* move_out)
 {
     if (move_out) *move_out = CBV_MOVE_NONE;
     if (!b) return CBV_GAME_NO_VALID_CHANGE;
@@ -315,23 +315,30 @@ int cbv_game_process_occupancy(cbv_board* b, uint64_t vision, cbv_move* move_out
     cc_gen_legal(b, &legal, &pseudo);
     cbv_pos t = *b; // the core pushes on the POD board; the move goes through the undo stack here
     cbv_move m;
-    const int status = cc_process_occupancy(&t, &legal, vision, &m);
+    const int status = cc_process_occupancy_tones(&t, &legal, vision, tone_white, tone_black, &m);
     if (m != CBV_MOVE_NONE) do_push(b, m);
     if (move_out) *move_out = m;
     return status;
 }
 
-int cbv_game_infer_move(const cbv_board* b, uint64_t vision, cbv_move* move_out)
+int cbv_game_process_occupancy(cbv_board* b, uint64_t vision, cbv_move* move_out)
+{
+    return cbv_game_process_occupancy_tones(b, vision, 0, 0, move_out);
+}
+
+int cbv_game_infer_move_tones(const cbv_board* b, uint64_t vision, uint64_t tone_white, uint64_t tone_black, cbv_move* move_out)
 {
     if (move_out) *move_out = CBV_MOVE_NONE;
     if (!b) return 0;
     cbv_movelist legal, scratch;
     cc_gen_legal(b, &legal, &scratch);
     cbv_move m;
-    const int n = cc_infer_move(b, &legal, &scratch, vision, &m);
+    const int n = cc_infer_move_tones(b, &legal, &scratch, vision, tone_white, tone_black, &m);
     if (move_out) *move_out = m;
     return n;
 }
+
+int cbv_game_infer_move(const cbv_board* b, uint64_t vision, cbv_move* move_out) { return cbv_game_infer_move_tones(b, vision, 0, 0, move_out); }
 
 uint64_t cbv_roi_bits_to_squares(uint64_t roi_bits) { return cc_flip_rows(roi_bits); }
 
@@ -371,7 +378,7 @@ int cbv_session_walk(const cbv_session_config* cfg, cbv_session_state* st, const
         const u64 vision = results[t].stable_occupied;
         if (!ses_frame_pre(cfg, st, vision, noise && noise[t].state == 1)) continue;
         cc_gen_legal(ses_pos(st), &legal, &scratch);
-        if (!ses_frame_rule(cfg, st, vision, &legal, &scratch, move)) continue;
+        if (!ses_frame_rule(cfg, st, vision, 0, 0, &legal, &scratch, move)) continue;
         cc_gen_legal(ses_pos(st), &legal, &scratch);
         ses_refresh(st, ses_dest_squares(&legal));
         *accepted = 1;
@@ -426,9 +433,9 @@ int cbv_session_pos_from_moves(const char* moves, cbv_session_pos* out, int* pus
     return 0;
 }
 
-int cbv_session_walk_events(const cbv_session_config* cfg, cbv_session_state* st, const cbv_frame_result* results,
-                            const cbv_noise_result* noise, int n, const cbv_session_event* events, int n_events, int* events_used,
-                            cbv_session_radar* radar, cbv_session_move* move, int* accepted)
+int cbv_session_walk_tones(const cbv_session_config* cfg, cbv_session_state* st, const cbv_frame_result* results,
+                           const cbv_noise_result* noise, int n, const cbv_session_event* events, int n_events, int* events_used,
+                           cbv_session_radar* radar, const cbv_tone_result* tones, cbv_session_move* move, int* accepted)
 {
     if (accepted) *accepted = 0;
     if (events_used) *events_used = 0;
@@ -462,13 +469,20 @@ int cbv_session_walk_events(const cbv_session_config* cfg, cbv_session_state* st
         if (!ses_frame_pre(cfg, st, vision, noise && noise[t].state == 1)) continue;
         if (!have_legal) cc_gen_legal(ses_pos(st), &legal, &scratch);
         have_legal = true;
-        if (!ses_frame_rule(cfg, st, vision, &legal, &scratch, move)) continue;
+        if (!ses_frame_rule(cfg, st, vision, tones ? tones[t].white : 0ull, tones ? tones[t].black : 0ull, &legal, &scratch, move)) continue;
         cc_gen_legal(ses_pos(st), &legal, &scratch);
         ses_refresh(st, ses_dest_squares(&legal));
         *accepted = 1;
         return t + 1;
     }
     return n;
+}
+
+int cbv_session_walk_events(const cbv_session_config* cfg, cbv_session_state* st, const cbv_frame_result* results,
+                            const cbv_noise_result* noise, int n, const cbv_session_event* events, int n_events, int* events_used,
+                            cbv_session_radar* radar, cbv_session_move* move, int* accepted)
+{
+    return cbv_session_walk_tones(cfg, st, results, noise, n, events, n_events, events_used, radar, nullptr, move, accepted);
 }
 
 } // extern "C"

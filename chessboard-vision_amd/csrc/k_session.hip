@@ -71,7 +71,7 @@ __device__ u64 wave_gen_legal(const cbv_pos* b, WalkLds* L)
 __global__ __launch_bounds__(64) void k_session_walk(const u8* __restrict__ flags, int n, cbv_frame_result* __restrict__ results, int count,
                                                       cbv_noise_state* __restrict__ noise_state, cbv_noise_result* __restrict__ noise_out,
                                                       ResultMirror mir, SessionDev* __restrict__ ses, int first_round,
-                                                      cbv_session_radar* __restrict__ radar)
+                                                      cbv_session_radar* __restrict__ radar, const cbv_tone_result* __restrict__ tones)
 {
     __shared__ WalkLds L;
     __shared__ cbv_session_state st;
@@ -148,7 +148,9 @@ __global__ __launch_bounds__(64) void k_session_walk(const u8* __restrict__ flag
         }
         if (lane == 0) {
             cbv_session_move rec;
-            const bool acc = ses_frame_rule(&cfg, &st, results[t].stable_occupied, &L.legal, &L.scratch, &rec);
+            // the frame's piece tones (k_piece_tone wrote them on the lanes, in front of the scan stage): the rules' tie-break
+            const u64 tw = tones ? tones[t].white : 0ull, tb = tones ? tones[t].black : 0ull;
+            const bool acc = ses_frame_rule(&cfg, &st, results[t].stable_occupied, tw, tb, &L.legal, &L.scratch, &rec);
             if (acc) ses->ring[(u32)(st.n_moves - 1) % CBV_SESSION_RING] = rec;
             sh_flag = acc ? 1 : 0;
         }
@@ -210,10 +212,11 @@ __global__ __launch_bounds__(64) void k_session_legal(const cbv_session_state* _
 } // namespace
 
 int launch_session_walk(cbv_ctx* ctx, const u8* flags, int n, cbv_frame_result* results, int count, cbv_noise_state* noise_state,
-                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round, cbv_session_radar* radar)
+                        cbv_noise_result* noise_out, ResultMirror mir, SessionDev* ses, int first_round, cbv_session_radar* radar,
+                        const cbv_tone_result* tones)
 {
     hipLaunchKernelGGL(k_session_walk, dim3(1), dim3(64), 0, ctx->stream, flags, n, results, count, noise_state, noise_out, mir, ses, first_round,
-                       radar);
+                       radar, tones);
     CBV_HIP(ctx, hipGetLastError());
     return CBV_OK;
 }

@@ -41,19 +41,21 @@ CBV_HD inline bool ses_frame_pre(const cbv_session_config* cfg, cbv_session_stat
     return true;
 }
 
-// steps 6, 7 (board part): `legal` = legal moves of the board, `scratch` a second list
-CBV_HD inline bool ses_frame_rule(const cbv_session_config* cfg, cbv_session_state* st, cc_u64 vision, const cbv_movelist* legal,
-                                  cbv_movelist* scratch, cbv_session_move* rec)
+// steps 6, 7 (board part): `legal` = legal moves of the board, `scratch` a second list; tone_w / tone_b = the frame's
+// cbv_tone_result (ROI numbering like `vision`), read with cfg->tone only: the rules' tie-break (include/cbv_chess.h)
+CBV_HD inline bool ses_frame_rule(const cbv_session_config* cfg, cbv_session_state* st, cc_u64 vision, cc_u64 tone_w, cc_u64 tone_b,
+                                  const cbv_movelist* legal, cbv_movelist* scratch, cbv_session_move* rec)
 {
     cbv_pos* b = ses_pos(st);
     const cc_u64 vis_sq = cc_flip_rows(vision);
+    const cc_u64 tw = cfg->tone ? cc_flip_rows(tone_w) : 0ull, tb = cfg->tone ? cc_flip_rows(tone_b) : 0ull;
     cbv_move m = CBV_MOVE_NONE;
     int status = CBV_GAME_MOVE_CONFIRMED, cand = 1;
     if (cfg->rule == CBV_SESSION_RULE_OCCUPANCY) {
-        status = cc_process_occupancy(b, legal, vis_sq, &m);
+        status = cc_process_occupancy_tones(b, legal, vis_sq, tw, tb, &m);
         st->last_candidates = status;
     } else {
-        cand = cc_infer_move(b, legal, scratch, vis_sq, &m);
+        cand = cc_infer_move_tones(b, legal, scratch, vis_sq, tw, tb, &m);
         st->last_candidates = cand;
         if (m != CBV_MOVE_NONE && cfg->online && st->waiting_for_opponent) {
             // on_move_detected returns False (lichess_session.py:46-48): nothing is pushed and nothing restarts; the
@@ -103,6 +105,7 @@ CBV_HD inline bool ses_config_ok(const cbv_session_config* cfg)
 {
     if (cfg->online < CBV_SESSION_ONLINE_OFF || cfg->online > CBV_SESSION_ONLINE_BLACK) return false;
     if (cfg->online && cfg->rule != CBV_SESSION_RULE_INFER) return false; // LichessSession is GameSession._infer_move
+    if (cfg->tone != 0 && cfg->tone != 1) return false;
     return cfg->radar == 0 || cfg->radar == 1;
 }
 

@@ -45,16 +45,21 @@ class GameState:
         bits = self.board.occupancy_bits()
         return {(s & 7, s >> 3) for s in range(64) if (bits >> s) & 1}
 
-    def process_occupancy_change(self, vision_occupancy_grid):
-        """(move, status) like game_state.py:40-112; the board is advanced when a move is confirmed."""
-        return self.process_occupancy_bits(_bits(vision_occupancy_grid))
+    def process_occupancy_change(self, vision_occupancy_grid, tones=None):
+        """(move, status) like game_state.py:40-112; the board is advanced when a move is confirmed.  `tones`: (white,
+        black) sets of (file, rank) squares whose piece looks white / black (BoardPipeline.piece_colours), which break
+        the tie of a capture with two possible victims (include/cbv_chess.h) and change nothing else."""
+        return self.process_occupancy_bits(_bits(vision_occupancy_grid), None if tones is None else (_bits(tones[0]), _bits(tones[1])))
 
-    def process_occupancy_bits(self, square_bits):
+    def process_occupancy_bits(self, square_bits, tones=None):
         """Same, from an occupancy word (bit = python-chess square), e.g.
-        chess_rules.roi_bits_to_squares(frame_result.stable_occupied)."""
+        chess_rules.roi_bits_to_squares(frame_result.stable_occupied); `tones` = (white, black) words in the same numbering."""
         lib = chess._L()
         code = C.c_uint16(chess.MOVE_NONE)
-        status = lib.cbv_game_process_occupancy(self.board._h, square_bits, C.byref(code))
+        if tones is None:
+            status = lib.cbv_game_process_occupancy(self.board._h, square_bits, C.byref(code))
+        else:
+            status = lib.cbv_game_process_occupancy_tones(self.board._h, square_bits, tones[0], tones[1], C.byref(code))
         return chess.Move._from_code(code.value), lib.cbv_game_status_name(status).decode()
 
     def radar(self, vision_occupied):
@@ -140,15 +145,21 @@ class StableMoveTracker:
         self.last_move_time = float("-inf")
         return self.clock
 
-    def infer_move(self, vision_occupied):
-        """(move or None, number of candidate moves) — game_session.py:229-265."""
+    def infer_move(self, vision_occupied, tones=None):
+        """(move or None, number of candidate moves) — game_session.py:229-265.  `tones` = (white_set, black_set) of
+        (file, rank) squares: with more than one candidate, the one whose destination does not look like a piece of
+        the side not to move, if it is the only one (the count stays the number of candidates)."""
         lib = chess._L()
         code = C.c_uint16(chess.MOVE_NONE)
-        n = lib.cbv_game_infer_move(self.game.board._h, _bits(vision_occupied), C.byref(code))
+        if tones is None:
+            n = lib.cbv_game_infer_move(self.game.board._h, _bits(vision_occupied), C.byref(code))
+        else:
+            n = lib.cbv_game_infer_move_tones(self.game.board._h, _bits(vision_occupied), _bits(tones[0]), _bits(tones[1]), C.byref(code))
         return chess.Move._from_code(code.value), n
 
-    def process(self, vision_occupied, noise_active=False):
-        """One frame; returns the move that was pushed on the board, or None."""
+    def process(self, vision_occupied, noise_active=False, tones=None):
+        """One frame; returns the move that was pushed on the board, or None.  `tones` = (white_set, black_set): the
+        frame's piece colours, for the rules' tie-break."""
         expected = self.game.get_board_occupancy()
         total_diff = len(expected - vision_occupied) + len(vision_occupied - expected)
         if total_diff > 4:                       # a hand or noise: start over
@@ -163,11 +174,13 @@ class StableMoveTracker:
         if self.stable_count < self.STABILITY_REQUIRED or not (now - self.last_move_time) > self.MOVE_COOLDOWN or noise_active:
             return None
         if self.rule == "game_state":  # process_occupancy_change recognises and pushes in one step
-            move, self.last_status = self.game.process_occupancy_change(vision_occupied)
+            # (without tones the calls are the ones that were always made: callers wrap and replace these methods)
+            move, self.last_status = (self.game.process_occupancy_change(vision_occupied) if tones is None
+                                      else self.game.process_occupancy_change(vision_occupied, tones))
             if move is None:
                 return None
         else:
-            move, _ = self.infer_move(vision_occupied)
+            move, _ = self.infer_move(vision_occupied) if tones is None else self.infer_move(vision_occupied, tones)
             if move is None or not self.on_move_detected(move):
                 return None
             if move not in self.game.board.legal_moves:

@@ -271,6 +271,29 @@ def lens_struct(lens):
     return lens.struct() if lens is not None else N.LensStruct()
 
 
+def save_tones(path, model):
+    """Write a ToneModel as tone_model.json beside the other settings files: {"centroid": [light, dark][white, black][b, g, r],
+    "margin"}.  The doubles round-trip exactly (repr)."""
+    d = {"centroid": [[[float(model.centroid[k][p][c]) for c in range(3)] for p in range(2)] for k in range(2)], "margin": float(model.margin)}
+    with open(path, "w") as f:
+        json.dump(d, f, indent=2)
+    return d
+
+
+def load_tones(path="tone_model.json"):
+    """The ToneModel save_tones wrote."""
+    with open(path) as f:
+        d = json.load(f)
+    m = N.ToneModel()
+    for k in range(2):
+        for p in range(2):
+            for c in range(3):
+                m.centroid[k][p][c] = float(d["centroid"][k][p][c])
+    m.margin = float(d.get("margin", 0.125))
+    m.calibrated = 1
+    return m
+
+
 def save_lens(path, lens, image_size=None):
     """Write a lens as JSON: camera_matrix (3 x 3), dist_coeffs (5) and, when given, image_size = [w, h], the resolution
     the calibration was made at (`Lens.scaled` takes it from there to another).  Returns what was written."""
@@ -596,7 +619,66 @@ class _BoardMethods:
     def occupied(self, result, stable=True):
         return bits_to_positions(result.stable_occupied if stable else result.raw_occupied, self.rois_rc)
 
-    def session_begin(self, rule="session", fps=30, fen=None, online=None, radar=False, **cfg):
+    # ---- piece colour per square (include/cbv.h, "piece colour per square") ----
+
+    def tone_sums(self, slot):
+        """cbv_tone_sums of the 64 squares of a processed slot (index = roi), with tones on or off."""
+        out = (N.ToneSums * N.MAX_SQUARES)()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_tone_sums(self.h_, slot, out))
+        return out
+
+    def set_tones(self, model):
+        """Turn the board's tone stage on with a calibrated ToneModel, or off with None: with it on every processed frame
+        leaves its tone record (`tones`), and a session begun with tones=True breaks the rules' ties with it."""
+        self.ctx.check(self.ctx.lib.cbv_pipeline_set_tones(self.h_, model))
+        self.tone_model = model
+
+    def calibrate_tones(self, slot, position=None, margin=0.125):
+        """Calibrate the tones on a processed slot that shows a known position and turn the stage on.  `position`: 64 bytes
+        in synth.board_array's convention (0 empty, 1 white, 2 black, ROI order), a FEN, or None = the board of the session
+        running on this board, else the start position.  Returns the report: {"samples", "D", "misclassified",
+        "undecided"}, the last two as lists of (file, rank) squares the new model does not classify cleanly."""
+        from .piece_tone import position_array, report_dict
+        if position is None:
+            ses = getattr(self, "_session", None)
+            position = ses.fen() if ses is not None and ses._open else None
+        pos = position_array(position)
+        model, rep = N.ToneModel(), N.ToneReport()
+        self.ctx.check(self.ctx.lib.cbv_tone_calibrate_host(self.tone_sums(slot), N.ptr(pos), float(margin), model, rep))
+        self.set_tones(model)
+        return report_dict(rep)
+
+    def tones(self, slot0, count):
+        """cbv_tone_result of processed slots: .white / .black, bit = roi, all 64 squares whatever their occupancy."""
+        out = (N.ToneResult * count)()
+        self.ctx.check(self.ctx.lib.cbv_pipeline_tones(self.h_, slot0, count, out))
+        return out
+
+    def piece_colours(self, result, tone):
+        """{(file, rank): "w" | "b" | None} for the stably occupied squares of a frame (its FrameResult and ToneResult)."""
+        out = {}
+        for i, (r, c) in enumerate(self.rois_rc):
+            if (result.stable_occupied >> i) & 1:
+                w, b = (tone.white >> i) & 1, (tone.black >> i) & 1
+                out[(c, 7 - r)] = "w" if w and not b else "b" if b and not w else None
+        return out
+
+    def verify_position(self, slot, fen=None):
+        """The slot's stable occupancy and tones against a position (None = the start position): {"ok", "missing" (expected,
+        not seen), "extra" (seen, not expected), "wrong_colour", "undecided"}, lists of (file, rank).  The reference's
+        unbuilt initial-position check ("Confirmar posição inicial com visão")."""
+        from .piece_tone import position_array
+        pos = position_array(fen)
+        seen = self.piece_colours(self.results(slot, 1)[0], self.tones(slot, 1)[0])
+        want = {(i & 7, 7 - (i >> 3)): "w" if pos[i] == 1 else "b" for i in range(64) if pos[i]}
+        both = sorted(set(seen) & set(want))
+        rep = {"missing": sorted(set(want) - set(seen)), "extra": sorted(set(seen) - set(want)),
+               "wrong_colour": [s for s in both if seen[s] is not None and seen[s] != want[s]],
+               "undecided": [s for s in both if seen[s] is None]}
+        rep["ok"] = not any(rep.values())
+        return rep
+
+    def session_begin(self, rule="session", fps=30, fen=None, online=None, radar=False, tones=False, **cfg):
         """Start a game session on this board (include/cbv.h, cbv_pipeline_session_begin): from now on every frame of
         every `run` also goes through the back half of GameSession.on_frame on the device (smart-scan check sets, stable
         move detection, the move rule, and after an accepted move update_references + NoiseHandler.reset()), whatever the
@@ -605,6 +687,7 @@ class _BoardMethods:
         smart_scan (True).  `online` "white" / "black": the session of LichessSession for that player (rule "session"
         only) — moves found while it is the opponent's turn are turned down, and the opponent's moves arrive through
         Session.sync_moves.  `radar`: every frame leaves the lifted piece and its destinations (Session.radar).
+        `tones`: the rule breaks ties with the board's piece tones (calibrate_tones / set_tones first).
         Returns a Session."""
         from .game_state import StableMoveTracker
         if rule not in N.SESSION_RULES:
@@ -618,9 +701,10 @@ class _BoardMethods:
         if online not in N.SESSION_ONLINE:
             raise ValueError("online %r: expected 'white', 'black' or None" % (online,))
         c = N.SessionConfig(N.SESSION_RULES[rule], int(d["stability_required"]), int(d["cooldown_frames"]), int(d["scan_period"]),
-                            int(d["max_diff"]), 1 if d["smart_scan"] else 0, N.SESSION_ONLINE[online], 1 if radar else 0)
+                            int(d["max_diff"]), 1 if d["smart_scan"] else 0, N.SESSION_ONLINE[online], 1 if radar else 0, 1 if tones else 0)
         self.ctx.check(self.ctx.lib.cbv_pipeline_session_begin(self.h_, c, fen.encode() if fen is not None else None))
-        return Session(self, c)
+        self._session = Session(self, c)
+        return self._session
 
 
 class Session:

@@ -138,7 +138,9 @@ enum {
 /* (CBV_K_COUNT + 1 is no kernel and has the empty name) */
 #define CBV_K_INGEST_BAYER_DEEP (CBV_K_COUNT + 2) /* k_ingest_deep: developed mosaics (CBV_BAYER_*, cbv_pipeline_set_bayer_tables) to BGR */
 #define CBV_K_WARP_BAYER_DEEP (CBV_K_COUNT + 3)   /* the warp kernels of a developed mosaic (raw mode) */
-#define CBV_K_END (CBV_K_COUNT + 4)
+/* (CBV_K_COUNT + 4 is no kernel and has the empty name) */
+#define CBV_K_TONE (CBV_K_COUNT + 5) /* k_piece_tone: piece colour per square (cbv_pipeline_set_tones, cbv_tone_sums_image) */
+#define CBV_K_END (CBV_K_COUNT + 6)
 CBV_API int cbv_profile_enable(cbv_ctx* ctx, int kid /* -1 = all, -2 = none */);
 CBV_API int cbv_profile_read(cbv_ctx* ctx, int kid, double* total_ms, long long* launches);
 CBV_API int cbv_profile_reset(cbv_ctx* ctx);
@@ -1038,6 +1040,7 @@ typedef struct {
     int32_t smart_scan;         /* 1: the session owns the boards' check sets; 0: they stay the caller's */
     int32_t online;             /* CBV_SESSION_ONLINE_*: 0 off, 1 the player is white, 2 black (rule INFER only) */
     int32_t radar;              /* 1: every frame leaves a cbv_session_radar record (cbv_pipeline_session_radar) */
+    int32_t tone;               /* 1: the rule breaks ties with the board's piece tones (cbv_pipeline_set_tones); 0: off */
 } cbv_session_config;
 typedef struct {
     int32_t frame;      /* frames since cbv_pipeline_session_begin, 0 based */
@@ -1067,7 +1070,9 @@ typedef struct {
 /* Start a session on a board (any board handle) of a configured pipeline, from `fen` (NULL = the start position).
  * CBV_ERR_STATE before cbv_pipeline_configure or on a board that has not 64 squares, CBV_ERR_ARG for a bad FEN or
  * configuration.  A running session is replaced.  With smart_scan, cbv_pipeline_set_check_squares on the board returns
- * CBV_ERR_STATE until the session ends; cbv_pipeline_update_references and cbv_pipeline_reset_state stay legal. */
+ * CBV_ERR_STATE until the session ends; cbv_pipeline_update_references and cbv_pipeline_reset_state stay legal.
+ * cfg.tone: the rule breaks ties with the frame's piece tones (include/cbv_chess.h, "tie-break"); CBV_ERR_STATE on a board
+ * whose tones are off (cbv_pipeline_set_tones). */
 CBV_API int cbv_pipeline_session_begin(cbv_pipeline* board, const cbv_session_config* cfg, const char* fen);
 /* End it: later runs are what they were before the session, with the check sets the caller had set before it. */
 CBV_API int cbv_pipeline_session_end(cbv_pipeline* board);
@@ -1153,6 +1158,66 @@ CBV_API int cbv_session_state_init_cfg(cbv_session_state* state, const cbv_sessi
 CBV_API int cbv_session_device_legal_moves(cbv_ctx* ctx, const char* fen, uint16_t* out, int cap, int* n);
 /* ... and its time: one launch that builds the list `reps` times, *ms = the launch's GPU time (timing tools) */
 CBV_API int cbv_session_generator_time(cbv_ctx* ctx, const char* fen, int reps, double* ms);
+
+/* ------------------------------------------------------------------ */
+/* piece colour per square (tones) and the tie-break of the move rules  */
+/* ------------------------------------------------------------------ */
+/* The reference detects occupancy only.  This stage adds one measurement per square, whether the piece on it is white or
+ * black, and the move rules use it to break ties and for nothing else.
+ * Tone sums of a square: over the pixels of the centre disc of _detect_center_vs_border (piece_detector.py:184-190),
+ * (x - w/2)^2 + (y - h/2)^2 <= (min(w, h)/4)^2 with integer divisions (bit 0 of the square's mask; SquareDesc::cnt[0]
+ * pixels), of the warped board as the detectors receive it (3 channels, not blurred): the three channel sums (B, G, R)
+ * and the pixel count.  Squares of 1 x 1 to CBV_MAX_SQUARE_DIM are legal; a radius of 0 leaves the centre pixel; the sums
+ * of a 128 x 128 square stay far below 2^32.
+ * Square colour: ROI i = 8 * row + col is dark iff row + col is odd (a1 = row 7, col 0 is dark): tones need the 64 ROIs of
+ * a board in that numbering.
+ * Classification of one square, all in float64, every multiply, add and divide rounded by itself, in this order:
+ *   f[c] = (double)sum[c] / (double)cnt
+ *   dW = (f[0]-cW[0])^2 + (f[1]-cW[1])^2 + (f[2]-cW[2])^2, left to right; dB likewise; D likewise from cW - cB,
+ *   cW / cB = centroid[colour of the square][0 / 1];  T = (2.0 * margin) * D
+ *   white iff dB - dW >= T, otherwise black iff dW - dB >= T, otherwise undecided (so is a square with cnt == 0).
+ * That is the sign of the projection onto the axis between the two centroids with a dead zone of `margin` on either side
+ * of the midpoint; margin lies in [0, 0.5), 0.125 by default. */
+typedef struct { uint32_t sum[3]; uint32_t cnt; } cbv_tone_sums; /* B, G, R */
+typedef struct {
+    double centroid[2][2][3]; /* [light, dark][white piece, black piece][b, g, r] */
+    double margin;
+    int32_t calibrated, pad;
+} cbv_tone_model;
+/* bit i = ROI i; all 64 squares whatever their occupancy: the bits of an empty square mean nothing, AND with the occupancy */
+typedef struct { uint64_t white, black; } cbv_tone_result;
+typedef struct {
+    int32_t samples[2][2];    /* calibration squares per class: [light, dark][white piece, black piece] */
+    double D[2];              /* squared distance of the two centroids per square colour */
+    uint64_t misclassified;   /* calibration squares the new model gives the other colour (bit = ROI) */
+    uint64_t undecided;       /* ... or leaves undecided */
+} cbv_tone_report;
+/* Tone sums of n ROIs (any table, n <= CBV_MAX_SQUARES) of one 3-channel board in host memory: k_piece_tone on one frame. */
+CBV_API int cbv_tone_sums_image(cbv_ctx* ctx, const cbv_host_image* board, const cbv_roi* rois, int n, cbv_tone_sums* out);
+/* Host only.  A model from the sums of the 64 squares of one frame and a known position: position[i] = 0 empty, 1 white,
+ * 2 black for ROI i.  Each centroid is the mean of f over its class, the squares summed in ROI order and divided by their
+ * number.  CBV_ERR_ARG for an empty class, D == 0 of a square colour, an occupied square with cnt == 0 or a margin outside
+ * [0, 0.5).  *report (may be NULL) says how the new model classifies its own samples: a calibration that does not is
+ * returned, not hidden. */
+CBV_API int cbv_tone_calibrate_host(const cbv_tone_sums* sums, const uint8_t* position, double margin, cbv_tone_model* model,
+                                    cbv_tone_report* report);
+/* Host only.  Squares [0, n) (n <= 64, index = ROI) -> the two words.  CBV_ERR_ARG for an uncalibrated model. */
+CBV_API int cbv_tone_classify_host(const cbv_tone_model* model, const cbv_tone_sums* sums, int n, uint64_t* white, uint64_t* black);
+/* Tones of a board of a pipeline: with a model every processed frame leaves its sums and its cbv_tone_result (k_piece_tone
+ * behind the warp of each chunk, one launch for the sums of all boards and one for their records).  NULL turns them off.
+ * CBV_ERR_ARG for an uncalibrated model, CBV_ERR_STATE on a board that has not 64 squares, and for NULL while a session
+ * with cfg.tone runs on the board.  A pipeline that never calls this or cbv_pipeline_tone_sums launches and allocates
+ * nothing for it. */
+CBV_API int cbv_pipeline_set_tones(cbv_pipeline* board, const cbv_tone_model* model);
+/* the sums of the 64 squares of a processed slot, with tones on or off (calibration reads them) */
+CBV_API int cbv_pipeline_tone_sums(cbv_pipeline* board, int slot, cbv_tone_sums* out);
+/* the records of processed slots; CBV_ERR_STATE while tones are off */
+CBV_API int cbv_pipeline_tones(cbv_pipeline* board, int slot0, int count, cbv_tone_result* out);
+/* cbv_session_walk_events with the frames' tone records (NULL = all undecided); read only with cfg->tone */
+CBV_API int cbv_session_walk_tones(const cbv_session_config* cfg, cbv_session_state* state, const cbv_frame_result* results,
+                                   const cbv_noise_result* noise, int n, const cbv_session_event* events, int n_events,
+                                   int* events_used, cbv_session_radar* radar, const cbv_tone_result* tones, cbv_session_move* move,
+                                   int* accepted);
 
 /* ------------------------------------------------------------------ */
 /* PieceDetector radius and Hough settings sweep on the device          */

@@ -80,6 +80,19 @@ CBV_API const char* cbv_game_status_name(int status);
  * the number of distinct candidates; *move_out is set only when it is exactly one.  The board is not changed. */
 CBV_API int cbv_game_infer_move(const cbv_board* b, uint64_t vision_occupancy, cbv_move* move_out);
 
+/* Tie-break by piece tones (include/cbv.h, "piece colour per square"): `tone_white` / `tone_black` are square-numbered sets
+ * (bit s = the piece on square s looks white / black; a square in both or in neither is undecided).  Tones only ever break
+ * ties: a call that ends with at most one candidate gives exactly what the plain function gives, whatever the words are.
+ * When cbv_game_infer_move ends with more than one candidate, or the capture case of cbv_game_process_occupancy with more
+ * than one capture, a candidate is contradicted iff the tone of its destination square is decided and is the colour of
+ * the side NOT to move (after a capture the destination carries the mover's colour; after a quiet move the squares the
+ * mover could have captured on still carry the opponent's).  If exactly one candidate is not contradicted it is the move
+ * (CBV_GAME_CAPTURE_CONFIRMED in the capture case); otherwise the outcome is what it was.  cbv_game_infer_move_tones still
+ * returns the number of candidates before the filter; *move_out tells whether one was chosen.  Castling under _infer_move
+ * stays ambiguous: its four candidates all end on squares of the mover's colour. */
+CBV_API int cbv_game_process_occupancy_tones(cbv_board* b, uint64_t vision_occupancy, uint64_t tone_white, uint64_t tone_black, cbv_move* move_out);
+CBV_API int cbv_game_infer_move_tones(const cbv_board* b, uint64_t vision_occupancy, uint64_t tone_white, uint64_t tone_black, cbv_move* move_out);
+
 /* ROI-numbered bits of cbv_frame_result (bit 8 * row + col, row 0 = rank 8 of the warped board, or its 180-degree
  * turn when the pipeline was configured with rot180) -> python-chess square bits (grid_extractor.py:31-40 numbering: file = col, rank = 7 - row) */
 CBV_API uint64_t cbv_roi_bits_to_squares(uint64_t roi_bits);
