@@ -465,6 +465,7 @@ def load():
         "cbv_squares_load_image": (i32, [vp, P(HostImage), P(Roi), i32, i32]),
         "cbv_squares_set_ref_mask": (i32, [vp, C.c_uint64]),
         "cbv_decide_piece": (i32, [P(SqStats), P(HoughResult), i32, i32, dbl, P(PieceResult)]),
+        "cbv_np_std_below_15": (i32, [vp, i32, P(C.c_double)]),
         "cbv_squares_detect_all": (i32, [vp, P(HostImage), P(Roi), i32, P(DetectParams), vp]),
         "cbv_squares_detect_changes": (i32, [vp, P(HostImage), P(Roi), i32, i32, P(ChangeParams), vp]),
         "cbv_debug_poison": (i32, [vp, i32]),

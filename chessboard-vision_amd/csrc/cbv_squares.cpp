@@ -472,6 +472,76 @@ extern "C" int cbv_squares_set_ref_mask(cbv_squares* s, uint64_t mask)
     return CBV_OK; // asynchronous: later calls on this context are ordered behind it
 }
 
+// np.std(gray) (piece_detector.py:305) of a C-contiguous uint8 array in numpy's own float64 steps: the mean is the exact
+// sum divided once; each deviation is rounded, squared and rounded; the squares are added by numpy's pairwise summation
+// (below 8 elements left to right, up to 128 eight interleaved partial sums combined as a tree plus the tail, above that
+// halves cut at a multiple of eight) inside chunks of 8192 elements (the ufunc buffer), chunk after chunk onto 0; one
+// division, one square root.  This file is compiled without contraction, so every line below rounds once.
+static inline double np_sq_dev(u8 x, double mean)
+{
+    const double d = (double)x - mean;
+    return d * d;
+}
+
+static double np_pairwise_sq_dev(const u8* px, int n, double mean)
+{
+    if (n < 8) {
+        double res = 0.;
+        for (int i = 0; i < n; i++) res = res + np_sq_dev(px[i], mean);
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int j = 0; j < 8; j++) r[j] = np_sq_dev(px[j], mean);
+        int i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; j++) r[j] = r[j] + np_sq_dev(px[i + j], mean);
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; i++) res = res + np_sq_dev(px[i], mean);
+        return res;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    const double a = np_pairwise_sq_dev(px, n2, mean);
+    const double b = np_pairwise_sq_dev(px + n2, n - n2, mean);
+    return a + b;
+}
+
+extern "C" int cbv_np_std_below_15(const uint8_t* gray, int n, double* std_out)
+{
+    if (!gray || n <= 0) return CBV_ERR_ARG;
+    unsigned long long sum = 0;
+    for (int i = 0; i < n; i++) sum += gray[i];
+    const double mean = (double)sum / (double)n;
+    double acc = 0.;
+    for (int i = 0; i < n; i += 8192) acc = acc + np_pairwise_sq_dev(gray + i, n - i < 8192 ? n - i : 8192, mean);
+    const double sd = sqrt(acc / (double)n);
+    if (std_out) *std_out = sd;
+    return sd < 15 ? 1 : 0;
+}
+
+// The variance of the square is exactly 225: the one case in which numpy's rounded np.std(gray) < 15 can differ from the
+// exact integer test of piece_uniform (it then says 14.999999999999998 for some pixel orders; DESIGN.md section 6,
+// "Square regions").  With the pixels at hand the one-call entry points follow numpy there.
+static bool piece_std_tie(const cbv_sq_stats* st)
+{
+    const long long n = st->n, sm = st->sum;
+    return n * (long long)st->sumsq - sm * sm == 225ll * n * n;
+}
+
+// `uniform` of square i of the set whose planes are at `planes`, read back and evaluated as numpy does (rare: ties only);
+// the stream is idle when the callers get here
+static int squares_uniform_at_tie(cbv_squares* s, const u8* planes, int i, bool* uniform)
+{
+    cbv_ctx* ctx = s->ctx;
+    const SquareDesc& d = s->descs[i];
+    std::vector<u8> px((size_t)d.w * d.h);
+    CBV_HIP(ctx, hipMemcpyAsync(px.data(), planes + d.plane_off, px.size(), hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *uniform = cbv_np_std_below_15(px.data(), (int)px.size(), nullptr) == 1;
+    return CBV_OK;
+}
+
 // PieceDetector.detect_piece (piece_detector.py:289-345) for one square from its statistics and its HoughCircles
 // record: the decision itself is piece_decide (piece_sweep_core.h), which the settings sweep shares.
 extern "C" int cbv_decide_piece(const cbv_sq_stats* st, const cbv_hough_result* hg, int w, int h, double circle_threshold,
@@ -525,7 +595,9 @@ extern "C" int cbv_squares_detect_all(cbv_squares* s, const cbv_host_image* img,
     for (int i = 0; i < n; i++) {
         cbv_piece_result r;
         memset(&r, 0, sizeof(r));
-        if (fl[i] & CBV_GATE_EVALUATED) { // detect_piece is evaluated for this square
+        bool uniform = false; // (np.std's verdict at a variance of exactly 225; everywhere else piece_decide's integer test is it)
+        if ((fl[i] & CBV_GATE_EVALUATED) && piece_std_tie(&st[i])) RC(squares_uniform_at_tie(s, s->gray(), i, &uniform));
+        if ((fl[i] & CBV_GATE_EVALUATED) && !uniform) { // detect_piece is evaluated for this square
             const bool hough_ran = (fl[i] & CBV_GATE_STD_OK) != 0;
             if (cbv_decide_piece(&st[i], hough_ran ? &hg[i] : nullptr, s->descs[i].w, s->descs[i].h, prm->circle_threshold, &r) != CBV_OK)
                 return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "HoughCircles candidate list overflowed (more accumulator maxima than the second pass holds in a "
@@ -574,6 +646,7 @@ extern "C" int cbv_squares_detect_changes(cbv_squares* s, const cbv_host_image* 
     // change_detector.py:124-150: squares of the selection whose share of changed pixels reaches 5 %
     u32* work = (u32*)(hst + HStage::work);
     int nwork = 0;
+    u64 uniform_ties = 0; // reported squares of variance exactly 225 that np.std calls uniform
     for (int i = 0; i < n; i++) {
         cbv_change_result r;
         memset(&r, 0, sizeof(r));
@@ -585,8 +658,12 @@ extern "C" int cbv_squares_detect_changes(cbv_squares* s, const cbv_host_image* 
             if (!(pct < 5.0)) {
                 r.in_result = 1;
                 r.intensity = pct > 75.0 ? 3 : (pct > 15.0 ? 2 : 1);
-                const long long nn = st5[i].n, sm = st5[i].sum;
-                if (!(nn * (long long)st5[i].sumsq - sm * sm < 225ll * nn * nn)) work[1 + nwork++] = (u32)i; // HoughCircles runs on it
+                bool uniform = piece_uniform(&st5[i]);
+                if (piece_std_tie(&st5[i])) {
+                    RC(squares_uniform_at_tie(s, five ? s->gray() : s->d_gray5.as<u8>(), i, &uniform));
+                    if (uniform) uniform_ties |= 1ull << i;
+                }
+                if (!uniform) work[1 + nwork++] = (u32)i; // HoughCircles runs on it
             }
         }
         out[i] = r;
@@ -607,7 +684,7 @@ extern "C" int cbv_squares_detect_changes(cbv_squares* s, const cbv_host_image* 
         if (*retry_back != 0) RC(squares_hough_second(s, n, g5, hc, L.hough, L.retry, back + FastLayout::o_hough, n));
     }
     for (int i = 0; i < n; i++) {
-        if (!out[i].in_result) continue;
+        if (!out[i].in_result || ((uniform_ties >> i) & 1ull)) continue;
         bool ran = false;
         for (int k = 0; k < nwork && !ran; k++) ran = work[1 + k] == (u32)i;
         cbv_piece_result pr;

@@ -260,7 +260,9 @@ void build_piece_mask(int w, int h, u8* mask)
             if (d2 <= (long long)radius * radius) m |= 1;
             bool in_r = (y < corner) || (y >= h - corner);
             bool in_c = (x < corner) || (x >= w - corner);
-            if (corner > 0 && in_r && in_c) m |= 2;
+            // corner == 0 (short side < 4): numpy's `-0:` slices are `0:`, so the last of the four assignments
+            // (piece_detector.py:198) selects the whole square
+            if (corner == 0 || (in_r && in_c)) m |= 2;
             double dist = sqrt((double)d2);
             for (int k = 0; k < 4; k++) {
                 double r = mn * ratios[k];

@@ -69,14 +69,17 @@ class PieceDetectorHIP:
             return False, None, None, None
         return True, (int(hg.cx), int(hg.cy)), int(hg.r), ("tower_top" if hg.kind == 2 else "hough")
 
-    def _decide(self, st, shape, hg=None):
-        """piece_detector.py:289-345 for one square given its cbv_sq_stats and cbv_hough_result."""
+    def _decide(self, st, shape, hg=None, plane=None):
+        """piece_detector.py:289-345 for one square given its cbv_sq_stats and cbv_hough_result.  `plane`: a callable
+        that returns the square's gray plane; it is asked only when the variance is exactly 225."""
         h, w = shape
         result = {"has_piece": False, "confidence": 0.0, "center": None, "radius": None, "method": None,
                   "center_border_diff": 0, "is_ellipse": False, "axes": None}
         n, s, ss = int(st.n), int(st.sum), int(st.sumsq)
-        # np.std(gray) < 15  <=>  n*sumsq - sum^2 < 225 n^2
-        if n * ss - s * s < 225 * n * n:
+        # np.std(gray) < 15  <=>  n*sumsq - sum^2 < 225 n^2, except that at equality numpy's rounded result can be
+        # 14.999999999999998: there np.std itself decides, on the plane
+        lhs = n * ss - s * s
+        if lhs < 225 * n * n or (lhs == 225 * n * n and plane is not None and np.std(plane()) < 15):
             return result
         if hg is not None and hg.flags & N.HOUGH_OVERFLOW:
             # more accumulator maxima than the kernel keeps: a truncated list could change has_piece, so it is
@@ -136,7 +139,7 @@ class PieceDetectorHIP:
             self._scratch.load(part, 5)
             st = self._scratch.stats()
             hg = self._scratch.hough(**self._hough_kwargs())
-            out += [self._decide(st[i], self._scratch.shapes[i], hg[i]) for i in range(len(part))]
+            out += [self._decide(st[i], self._scratch.shapes[i], hg[i], plane=lambda i=i: self._scratch.get(GRAY, i)) for i in range(len(part))]
         return out
 
     def detect_piece(self, square_img, pos=None):
@@ -153,7 +156,7 @@ class PieceDetectorHIP:
         st = self._state.stats()
         hg = self._state.hough(**self._hough_kwargs())
         for i, pos in enumerate(self._state.keys):
-            self.cached_results[pos] = self._decide(st[i], self._state.shapes[i], hg[i])
+            self.cached_results[pos] = self._decide(st[i], self._state.shapes[i], hg[i], plane=lambda pos=pos: self._state.get(GRAY, pos))
 
     def update_references(self, squares_dict):
         """piece_detector.py:447-453"""
@@ -276,7 +279,7 @@ class PieceDetectorHIP:
                 if pos not in self.cached_results or has_changed_visual:
                     should_process = True
             if should_process or pos not in self.cached_results:
-                raw_result = self._decide(s, shape, hg[i])
+                raw_result = self._decide(s, shape, hg[i], plane=lambda pos=pos: self._state.get(GRAY, pos))
                 self.cached_results[pos] = raw_result.copy()
             else:
                 raw_result = self.cached_results[pos].copy()

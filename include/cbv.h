@@ -288,6 +288,23 @@ typedef struct {
  * only, no GPU.  CBV_ERR_UNSUPPORTED when the record carries CBV_HOUGH_OVERFLOW. */
 CBV_API int cbv_decide_piece(const cbv_sq_stats* st, const cbv_hough_result* hg, int w, int h, double circle_threshold,
                              cbv_piece_result* out);
+/* np.std(gray) < 15 (piece_detector.py:305) of n contiguous pixels as numpy evaluates it in float64: 1 / 0, and np.std's
+ * value in *std_out when given; host only.  It differs from the exact test on the sums that cbv_decide_piece makes only
+ * where the variance is exactly 225, where rounding can leave 14.999999999999998; cbv_squares_detect_all and
+ * cbv_squares_detect_changes, which hold the pixels, ask it there.
+ * The numpy behaviour this restates (numpy 1.22 to 2.2, default settings; none of it is documented API):
+ *  - np.std of an integer array works in float64: mean = exact sum / n, one division;
+ *  - `arr - mean` and the square are two element-wise steps, each rounded once (no fused multiply-add);
+ *  - np.add.reduce over a C-contiguous float64 array runs in memory order, in pieces of the ufunc buffer, 8192 elements
+ *    (np.getbufsize()), each piece's sum added to the running total, which starts at 0;
+ *  - within a piece, pairwise summation: below 8 elements left to right; up to 128 elements eight interleaved partial
+ *    sums, combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the tail left to right; above 128 the
+ *    piece is halved at a multiple of 8 and the halves' sums are added;
+ *  - one division by n, one correctly rounded square root.
+ * np.setbufsize, another array layout or a numpy whose reduction differs changes the last bit of np.std and with it the
+ * verdict at a tie; tests/test_regions_host.py::test_np_std_below_15_is_numpy_bit_for_bit compares this function with the
+ * installed numpy bit for bit and fails when that happens. */
+CBV_API int cbv_np_std_below_15(const uint8_t* gray, int n, double* std_out);
 
 typedef struct {
     double change_threshold;   /* 25   piece_detector.py:50 */

@@ -1015,7 +1015,8 @@ ORC_API void orc_piece_masks(int w, int h, u8* mask)
             if (d2 <= (long long)radius * radius) m |= 1;
             int in_r = (y < corner) || (y >= h - corner);
             int in_c = (x < corner) || (x >= w - corner);
-            if (corner > 0 && in_r && in_c) m |= 2;
+            /* corner == 0: `border_mask[-0:, -0:] = True` is the whole square (piece_detector.py:198) */
+            if (corner == 0 || (in_r && in_c)) m |= 2;
             double dist = sqrt((double)d2);
             for (int k = 0; k < 4; k++) {
                 double r = mn * ratios[k];
