@@ -461,6 +461,11 @@ def load():
         "cbv_largest_contour_polygon": (i32, [u8p, i32, i32, i32, dbl, C.POINTER(C.c_int32), i32, C.POINTER(dbl), C.POINTER(i32)]),
         "cbv_find_chessboard_corners": (i32, [vp, u8p, i32, i32, i32, C.POINTER(C.c_int32), u8p, i32]),
         "cbv_canny": (i32, [vp, u8p, i32, i32, i32, i32, dbl, dbl, u8p, i32]),
+        "cbv_gaussian_blur": (i32, [vp, u8p, i32, i32, i32, i32, i32, dbl, u8p, i32, P(C.c_int32)]),
+        "cbv_gaussian_q8": (i32, [i32, dbl, P(C.c_int32)]),
+        "cbv_dilate_rect": (i32, [vp, u8p, i32, i32, i32, i32, u8p, i32]),
+        "cbv_external_contours": (i32, [u8p, i32, i32, i32, P(C.c_int32), i32, P(C.c_int32), P(dbl), P(dbl), i32, P(i32), P(i32)]),
+        "cbv_approx_poly_closed": (i32, [P(C.c_int32), i32, dbl, P(C.c_int32), i32]),
         "cbv_squares_hough": (i32, [vp, P(HoughParams), P(HoughResult)]),
         "cbv_squares_load_image": (i32, [vp, P(HostImage), P(Roi), i32, i32]),
         "cbv_squares_set_ref_mask": (i32, [vp, C.c_uint64]),

@@ -309,6 +309,43 @@ def corners_from_edges(edges):
     return (np.array(pts, np.int32).reshape(4, 1, 2) if rc == 1 else None), n.value
 
 
+def external_contours(img):
+    """Inspection: cv2.findContours(img, RETR_EXTERNAL, CHAIN_APPROX_NONE) with contourArea and arcLength(closed) of each
+    contour: (list of int32 (n, 2) point arrays in cv2's order, areas, perimeters).  Host only."""
+    from . import _native as N
+    import ctypes as C
+    e = np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
+    lib = N.load()
+    nc, npts = C.c_int(0), C.c_int(0)
+    args = (e.ctypes.data, e.shape[1], e.shape[0], e.strides[0])
+    rc = lib.cbv_external_contours(*args, None, 0, None, None, None, 0, C.byref(nc), C.byref(npts))
+    if rc < 0 and (nc.value == 0 and npts.value == 0):
+        raise ValueError("external_contours: bad arguments")
+    pts = np.zeros((max(npts.value, 1), 2), np.int32)
+    lens = np.zeros(max(nc.value, 1), np.int32)
+    areas, perims = np.zeros(max(nc.value, 1)), np.zeros(max(nc.value, 1))
+    i32p, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    rc = lib.cbv_external_contours(*args, pts.ctypes.data_as(i32p), npts.value, lens.ctypes.data_as(i32p), areas.ctypes.data_as(dp),
+                                   perims.ctypes.data_as(dp), nc.value, C.byref(nc), C.byref(npts))
+    if rc != 0:
+        raise ValueError("external_contours: bad arguments")
+    ends = np.cumsum(lens[:nc.value])
+    return [pts[b - n:b].copy() for b, n in zip(ends, lens[:nc.value])], areas[:nc.value].copy(), perims[:nc.value].copy()
+
+
+def approx_poly_closed(curve, eps):
+    """Inspection: cv2.approxPolyDP(curve, eps, True) of an integer (n, 2) curve, as int32 (m, 2).  Host only."""
+    from . import _native as N
+    import ctypes as C
+    c = np.ascontiguousarray(np.asarray(curve, dtype=np.int32).reshape(-1, 2))
+    out = np.zeros((max(len(c), 1), 2), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    n = N.load().cbv_approx_poly_closed(c.ctypes.data_as(i32p), len(c), float(eps), out.ctypes.data_as(i32p), len(c))
+    if n < 0:
+        raise ValueError("approx_poly_closed: bad arguments")
+    return out[:n].copy()
+
+
 def find_chessboard_corners(img, debug=False):
     """board_detection.py:4-28: the four corners (reordered TL, TR, BL, BR; int32 (4,1,2)) of the largest
     four-cornered contour of the dilated Canny edges, or an empty array.  Pixel stages on the GPU, contour

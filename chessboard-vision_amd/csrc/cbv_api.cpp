@@ -267,6 +267,67 @@ extern "C" int cbv_find_chessboard_corners(cbv_ctx* ctx, const uint8_t* bgr, int
     return CBV_DONE(board_corners_from_edges(host.data(), w, h, pts8, &n_contours));
 }
 
+// calibration / inspection: the stages of cbv_find_chessboard_corners one at a time
+static bool gauss_k_ok(int k) { return k >= 1 && k <= 15 && (k & 1); }
+
+extern "C" int cbv_gaussian_q8(int k, double sigma, int32_t* coef)
+{
+    if (!coef || !gauss_k_ok(k)) return CBV_ERR_ARG;
+    int q[16] = {0};
+    build_gaussian_q8_sigma(k, sigma, q);
+    for (int i = 0; i < k; i++) coef[i] = q[i];
+    return CBV_OK;
+}
+
+extern "C" int cbv_gaussian_blur(cbv_ctx* ctx, const uint8_t* img, int w, int h, int stride, int cn, int k, double sigma,
+                                 uint8_t* out, int out_stride, int32_t* coef_out)
+{
+    RC(check_img(ctx, img, w, h, stride, cn, "cbv_gaussian_blur"));
+    if (!out || out_stride < w || (cn != 1 && cn != 3)) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_gaussian_blur: bad output or unsupported channel count");
+    if (!gauss_k_ok(k)) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "Gaussian kernel size %d is not supported (odd, <= 15)", k);
+    CBV_ENTER_DRAINED(ctx);
+    RC(upload(ctx, &ctx->in, img, w * cn, h, stride));
+    const size_t plane = ((size_t)w * h + 255) & ~(size_t)255;
+    RC(dev_ensure(ctx, &ctx->a, plane + 256));
+    int coef[16] = {0};
+    build_gaussian_q8_sigma(k, sigma, coef);
+    if (coef_out)
+        for (int i = 0; i < k; i++) coef_out[i] = coef[i];
+    int* coef_dev = (int*)((u8*)ctx->a.p + plane);
+    CBV_HIP(ctx, hipMemcpyAsync(coef_dev, coef, sizeof(int) * 16, hipMemcpyHostToDevice, ctx->stream));
+    RC(launch_gray_gauss(ctx, (const u8*)ctx->in.p, w, h, w * cn, cn, coef_dev, k, (u8*)ctx->a.p));
+    return CBV_DONE(download(ctx, ctx->a.p, out, w, h, out_stride));
+}
+
+extern "C" int cbv_dilate_rect(cbv_ctx* ctx, const uint8_t* img, int w, int h, int stride, int r, uint8_t* out, int out_stride)
+{
+    RC(check_img(ctx, img, w, h, stride, 1, "cbv_dilate_rect"));
+    if (!out || out_stride < w) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_dilate_rect: bad output");
+    if (r < 0 || r > 7) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "dilation radius %d is not supported (<= 7)", r);
+    CBV_ENTER_DRAINED(ctx);
+    RC(upload(ctx, &ctx->in, img, w, h, stride));
+    RC(dev_ensure(ctx, &ctx->a, ((size_t)w * h + 255) & ~(size_t)255));
+    RC(launch_dilate_rect(ctx, (const u8*)ctx->in.p, w, h, r, (u8*)ctx->a.p));
+    return CBV_DONE(download(ctx, ctx->a.p, out, w, h, out_stride));
+}
+
+extern "C" int cbv_external_contours(const uint8_t* img, int w, int h, int stride, int32_t* pts, int pts_cap, int32_t* lens,
+                                     double* areas, double* perims, int contours_cap, int* n_contours, int* n_points)
+{
+    if (!img || !n_contours || !n_points || w <= 0 || h <= 0 || stride < w || pts_cap < 0 || contours_cap < 0) return CBV_ERR_ARG;
+    if ((pts_cap > 0 && !pts) || (contours_cap > 0 && (!lens || !areas || !perims))) return CBV_ERR_ARG;
+    if ((size_t)w * h > (size_t)1 << 28) return CBV_ERR_ARG;
+    std::vector<u8> tight((size_t)w * h);
+    for (int y = 0; y < h; y++) memcpy(tight.data() + (size_t)y * w, img + (size_t)y * stride, (size_t)w);
+    return external_contours(tight.data(), w, h, pts, pts_cap, lens, areas, perims, contours_cap, n_contours, n_points);
+}
+
+extern "C" int cbv_approx_poly_closed(const int32_t* pts, int n, double eps, int32_t* out, int cap)
+{
+    if (!pts || n <= 0 || cap < 0 || (cap > 0 && !out) || !(eps >= 0)) return CBV_ERR_ARG;
+    return approx_poly_closed_pts(pts, n, eps, out, cap);
+}
+
 // enhancement chain on device buffers: src -> (A, B ping-pong) ; result pointer returned.
 // When `fold_norm` the final normalize pass is skipped and the caller applies S.norm_lut downstream.
 static PxRect px_dilate(PxRect r, int d, Geom g)

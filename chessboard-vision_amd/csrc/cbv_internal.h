@@ -590,6 +590,9 @@ int launch_gray_gauss(cbv_ctx* ctx, const u8* src, int w, int h, int stride, int
 int launch_dilate_rect(cbv_ctx* ctx, const u8* src, int w, int h, int r, u8* dst);
 int largest_contour_polygon(const uint8_t* img, int w, int h, double eps_frac, int32_t* pts, int cap, double* area_out, int* contour_len);
 int board_corners_from_edges(const uint8_t* dilated, int w, int h, int32_t pts[8], int* n_contours);
+int external_contours(const uint8_t* img, int w, int h, int32_t* pts, int pts_cap, int32_t* lens, double* areas, double* perims,
+                      int contours_cap, int* n_contours, int* n_points);
+int approx_poly_closed_pts(const int32_t* pts, int n, double eps, int32_t* out, int cap);
 int launch_canny(cbv_ctx* ctx, const u8* src, int w, int h, int stride, int cn, int low, int high, u8* edges, DevBuf* scratch);
 
 // squares

@@ -266,3 +266,43 @@ int largest_contour_polygon(const uint8_t* img, int w, int h, double eps_frac, i
     }
     return (int)poly.size();
 }
+
+// inspection: every external contour, in cv2.findContours' order (the last one found first), with its length,
+// contourArea and closed arcLength.  The needed sizes are always reported; the arrays are written only when they all fit.
+int external_contours(const uint8_t* img, int w, int h, int32_t* pts, int pts_cap, int32_t* lens, double* areas, double* perims,
+                      int contours_cap, int* n_contours, int* n_points)
+{
+    std::vector<std::vector<Pt>> cs;
+    find_external_contours(img, w, h, cs);
+    size_t total = 0;
+    for (const auto& c : cs) total += c.size();
+    *n_contours = (int)cs.size();
+    *n_points = (int)total;
+    if (cs.size() > (size_t)contours_cap || total > (size_t)pts_cap) return CBV_ERR_ARG;
+    size_t at = 0;
+    for (int i = (int)cs.size() - 1, j = 0; i >= 0; i--, j++) {
+        lens[j] = (int32_t)cs[i].size();
+        areas[j] = contour_area(cs[i]);
+        perims[j] = arc_length_closed(cs[i]);
+        for (const Pt& p : cs[i]) {
+            pts[2 * at] = p.x;
+            pts[2 * at + 1] = p.y;
+            at++;
+        }
+    }
+    return CBV_OK;
+}
+
+// inspection: approx_poly_closed on a caller's curve; the vertex count, or CBV_ERR_ARG when it exceeds cap
+int approx_poly_closed_pts(const int32_t* pts, int n, double eps, int32_t* out, int cap)
+{
+    std::vector<Pt> src((size_t)n), dst;
+    for (int i = 0; i < n; i++) src[i] = {pts[2 * i], pts[2 * i + 1]};
+    approx_poly_closed(src, eps, dst);
+    if ((int)dst.size() > cap) return CBV_ERR_ARG;
+    for (size_t i = 0; i < dst.size(); i++) {
+        out[2 * i] = dst[i].x;
+        out[2 * i + 1] = dst[i].y;
+    }
+    return (int)dst.size();
+}

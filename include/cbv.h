@@ -368,6 +368,29 @@ CBV_API int cbv_largest_contour_polygon(const uint8_t* edges, int w, int h, int 
                                         int cap, double* area, int* contour_len);
 CBV_API int cbv_find_chessboard_corners(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, int32_t* pts8,
                                         uint8_t* dilated_out, int dilated_stride);
+/* Calibration and inspection calls: the stages of cbv_find_chessboard_corners one at a time, so that each can be held to
+ * its definition on its own (cbv_canny above is the third pixel stage).
+ * cv2.GaussianBlur(gray, (k, k), sigma) on 8 bits: img has 1 or 3 channels (BGR is converted with BGR2GRAY first), k is
+ * odd and 1..15, sigma <= 0 means cv2's sigma-from-k kernel; out is one w x h plane.  coef_out (optional, k entries)
+ * receives the 8.8 fixed-point taps the kernel ran with. */
+CBV_API int cbv_gaussian_blur(cbv_ctx* ctx, const uint8_t* img, int w, int h, int stride, int cn, int k, double sigma,
+                              uint8_t* out, int out_stride, int32_t* coef_out);
+/* Host only: those taps alone (k odd, 1..15). */
+CBV_API int cbv_gaussian_q8(int k, double sigma, int32_t* coef);
+/* cv2.dilate with a (2r + 1) x (2r + 1) rectangle of ones on any u8 plane, r = 0..7: the maximum over the window, pixels
+ * outside the image not taking part. */
+CBV_API int cbv_dilate_rect(cbv_ctx* ctx, const uint8_t* img, int w, int h, int stride, int r, uint8_t* out,
+                            int out_stride);
+/* Host only: cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_NONE) of a 0 / non-zero image, contours in the order cv2 lists
+ * them (the last one found first).  n_contours and n_points always receive the sizes needed.  When pts_cap points and
+ * contours_cap contours suffice, pts receives every contour's (x, y) points one contour after the other, lens each
+ * contour's point count, areas its contourArea and perims its closed arcLength, and the call returns 0; otherwise
+ * nothing is written to those four and it returns CBV_ERR_ARG.  The four may be null when their capacity is 0. */
+CBV_API int cbv_external_contours(const uint8_t* img, int w, int h, int stride, int32_t* pts, int pts_cap, int32_t* lens,
+                                  double* areas, double* perims, int contours_cap, int* n_contours, int* n_points);
+/* Host only: cv2.approxPolyDP(curve, eps, closed=True) of n integer (x, y) points.  Returns the vertex count, or
+ * CBV_ERR_ARG when it exceeds cap (nothing is written then) or an argument is bad. */
+CBV_API int cbv_approx_poly_closed(const int32_t* pts, int n, double eps, int32_t* out, int cap);
 
 /* ------------------------------------------------------------------ */
 /* device-resident batched pipeline: enhance -> warp -> 64-square detect */

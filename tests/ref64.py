@@ -179,26 +179,28 @@ def filter2d_3x3(img, kernel):
     return out
 
 
-def gaussian_kernel(k):
-    """cv2.getGaussianKernel(k, 0) for odd k: the fixed tables [1], [1 2 1]/4, [1 4 6 4 1]/16 and [1 3.5 7 9 7 3.5 1]/32
-    for k = 1, 3, 5, 7; otherwise exp(-x^2 / (2 s^2)) at x = i - (k-1)/2 with s = 0.3 ((k-1)/2 - 1) + 0.8, normalised
-    to sum 1."""
-    small = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
-             7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}
-    if k in small:
-        return np.array(small[k], np.float64)
-    assert k % 2 == 1 and k > 7, k
-    sigma = 0.3 * ((k - 1) / 2.0 - 1.0) + 0.8
+def gaussian_kernel(k, sigma=0.0):
+    """cv2.getGaussianKernel(k, sigma) for odd k.  sigma <= 0: the fixed tables [1], [1 2 1]/4, [1 4 6 4 1]/16 and
+    [1 3.5 7 9 7 3.5 1]/32 for k = 1, 3, 5, 7; otherwise exp(-x^2 / (2 s^2)) at x = i - (k-1)/2 with
+    s = 0.3 ((k-1)/2 - 1) + 0.8, normalised to sum 1.  sigma > 0: exp(-x^2 / (2 sigma^2)) normalised, for every k (the
+    fixed tables do not apply, k = 7 included)."""
+    assert k % 2 == 1 and k >= 1, k
+    if sigma <= 0:
+        small = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
+                 7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}
+        if k in small:
+            return np.array(small[k], np.float64)
+        sigma = 0.3 * ((k - 1) / 2.0 - 1.0) + 0.8
     x = np.arange(k, dtype=np.float64) - (k - 1) / 2.0
     c = np.exp(-x * x / (2.0 * sigma * sigma))
     return c / c.sum()
 
 
-def gaussian_q8(k):
+def gaussian_q8(k, sigma=0.0):
     """The 8-bit GaussianBlur's kernel in 8 fractional bits: from the edge towards the centre
     q_i = floor(256 c_i + err + 0.5), err carrying the remainder on to the next coefficient (error diffusion); the
     other half mirrors it and the centre is 256 - 2 * sum, so the kernel sums to exactly 256."""
-    c = gaussian_kernel(k)
+    c = gaussian_kernel(k, sigma)
     q = np.zeros(k, np.int64)
     err = 0.0
     for i in range(k // 2):
@@ -219,17 +221,46 @@ def _separable101(a, kern):
     return sum(kern[i] * tmp[i:i + h] for i in range(len(kern)))
 
 
-def gaussian_blur(gray, k):
-    """cv2.GaussianBlur(src, (k, k), 0): gaussian_kernel(k) applied separably with BORDER_REFLECT_101 (reflection is
-    repeated where the radius exceeds the array).  Unrounded float64."""
-    return _separable101(np.asarray(gray, np.float64), gaussian_kernel(k))
+def gaussian_blur(gray, k, sigma=0.0):
+    """cv2.GaussianBlur(src, (k, k), sigma): gaussian_kernel(k, sigma) applied separably with BORDER_REFLECT_101
+    (reflection is repeated where the radius exceeds the array).  Unrounded float64."""
+    return _separable101(np.asarray(gray, np.float64), gaussian_kernel(k, sigma))
 
 
-def gaussian_blur_u8(gray, k):
-    """The 8-bit GaussianBlur result in integers: min((sum_y sum_x q_y q_x g + 2^15) >> 16, 255) with q = gaussian_q8(k);
-    one rounding (halves upward), none between the two passes."""
-    acc = _separable101(np.asarray(gray, np.int64), gaussian_q8(k))
+def gaussian_blur_u8(gray, k, sigma=0.0):
+    """The 8-bit GaussianBlur result in integers: min((sum_y sum_x q_y q_x g + 2^15) >> 16, 255) with
+    q = gaussian_q8(k, sigma); one rounding (halves upward), none between the two passes."""
+    acc = _separable101(np.asarray(gray, np.int64), gaussian_q8(k, sigma))
     return np.minimum((acc + (1 << 15)) >> 16, 255).astype(np.uint8)
+
+
+def gaussian_q8_envelope(k, sigma=0.0, value_range=255.0):
+    """Bound on |gaussian_blur_u8 - gaussian_blur|: 0.5 for the one rounding, plus ||E||_1 * range / 2 with
+    E = q (x) q / 65536 - c (x) c (E sums to 0, so only the spread of the window's values around their mid-range counts)."""
+    q = gaussian_q8(k, sigma).astype(np.float64)
+    c = gaussian_kernel(k, sigma)
+    return 0.5 + np.abs(np.outer(q, q) / 65536.0 - np.outer(c, c)).sum() * value_range / 2.0
+
+
+def dilate_rect(a, r):
+    """cv2.dilate(a, ones((2r+1, 2r+1))): the maximum over the (2r+1)^2 window centred on each pixel; pixels outside the
+    image do not take part (the default border value never wins a maximum)."""
+    a = np.asarray(a)
+    h, w = a.shape
+    p = np.full((h + 2 * r, w + 2 * r), -1, np.int64)     # -1 outside: below every pixel, and the centre always takes part
+    p[r:r + h, r:r + w] = a
+    out = p[r:r + h, r:r + w].copy()
+    for i in range(2 * r + 1):
+        for j in range(2 * r + 1):
+            np.maximum(out, p[i:i + h, j:j + w], out=out)
+    return out.astype(a.dtype)
+
+
+def dilate_5x5_iter3(a):
+    """cv2.dilate(a, ones((5, 5)), iterations=3), literally: three passes of the 5 x 5 form."""
+    for _ in range(3):
+        a = dilate_rect(a, 2)
+    return a
 
 
 def gaussian_blur_5x5(gray):
