@@ -475,6 +475,8 @@ def load():
         "cbv_squares_detect_changes": (i32, [vp, P(HostImage), P(Roi), i32, i32, P(ChangeParams), vp]),
         "cbv_debug_poison": (i32, [vp, i32]),
         "cbv_debug_bilateral_offsets": (i32, [i32, dbl, dbl]),
+        "cbv_debug_bilateral_centre_is_one": (i32, [i32, dbl, dbl]),
+        "cbv_debug_reduce_noise_batch": (i32, [vp, u8p, i32, i32, i32, i32, dbl, dbl, u8p]),
         "cbv_squares_get": (i32, [vp, i32, i32, vp]),
         "cbv_squares_set": (i32, [vp, i32, i32, vp]),
         "cbv_squares_geometry": (i32, [vp, i32, P(i32), P(i32)]),

@@ -22,7 +22,7 @@ SOURCES = ["cbv_ctx.cpp", "cbv_api.cpp", "cbv_squares.cpp", "cbv_pipeline.cpp", 
            "k_ingest_cs.hip", "k_warp_cs.hip", "k_warp_lens_cs.hip", "k_ingest_deep.hip", "k_warp_deep.hip", "k_warp_lens_deep.hip", "k_tone.hip", "cbv_tone.cpp"]
 LONGEST = ("k_warp_deep.hip", "k_warp_lens_deep.hip")  # compiled first (build)
 HEADERS = ["cbv_internal.h", "cbv_pipeline.h", "cbv_device.h", "cbv_profile_px.h", "cbv_yuv.h", "cbv_bayer.h", "cbv_bayer_deep.h", "warp_gather.h", "chess_core.h", "session_core.h", "noise_core.h", "change_blur.h", "sweep_core.h", "hough_passes.h", "piece_sweep_core.h", "jpeg_core.h", "frame_plan.h", "lens_core.h", "warp_lens.h", "tone_core.h", os.path.join("..", "..", "include", "cbv_chess.h"), os.path.join("..", "..", "include", "cbv.h")]
-FLAGS = [*(["-DHG_TIMING"] if os.environ.get("HG_TIMING") else []), *(["-DBL_TWO_COPIES"] if os.environ.get("BL_TWO_COPIES") else []), *(["-DBL_NO_PAIRS"] if os.environ.get("BL_NO_PAIRS") else []), *(["-DBL_NT1024"] if os.environ.get("BL_NT1024") else []), *(["-DBL_NO_CAP"] if os.environ.get("BL_NO_CAP") else []), *(["-DSH_TIMING"] if os.environ.get("SH_TIMING") else []), *(["-DSW_HIST_PLAIN"] if os.environ.get("SW_HIST_PLAIN") else []), *(["-DRAW_PROFILE_FPT=%d" % int(os.environ["RAW_PROFILE_FPT"])] if os.environ.get("RAW_PROFILE_FPT") else []), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
+FLAGS = [*(["-DHG_TIMING"] if os.environ.get("HG_TIMING") else []), *(["-DBL_TWO_COPIES"] if os.environ.get("BL_TWO_COPIES") else []), *(["-DBL_NO_PAIRS"] if os.environ.get("BL_NO_PAIRS") else []), *(["-DBL_NT1024"] if os.environ.get("BL_NT1024") else []), *(["-DBL_NO_CAP"] if os.environ.get("BL_NO_CAP") else []), *(["-D" + k for k in ("BL_NO_CENTRE", "BL_ZERO_INIT", "BL_FULL_TILES") if os.environ.get(k)]), *(["-DSH_TIMING"] if os.environ.get("SH_TIMING") else []), *(["-DSW_HIST_PLAIN"] if os.environ.get("SW_HIST_PLAIN") else []), *(["-DRAW_PROFILE_FPT=%d" % int(os.environ["RAW_PROFILE_FPT"])] if os.environ.get("RAW_PROFILE_FPT") else []), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-x", "hip"]
 
 

@@ -143,6 +143,29 @@ extern "C" int cbv_reduce_noise(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, 
     return CBV_DONE(download(ctx, ctx->a.p, out, w * 3, h, out_stride));
 }
 
+// Not in include/cbv.h: for tests/test_gpu_bilateral_walk.py.  cbv_reduce_noise on `n` tightly packed w x h frames in ONE
+// launch, as the pipeline's chunks run it: the batched forms of k_bilateral are selected by the launch's tile count.
+// cbv_reduce_noise itself launches one frame, and frames stacked into one tall image are no substitute: every frame
+// has its own REFLECT_101 border and its own ragged bottom tile row.  Buffers as in cbv_reduce_noise (the input with
+// 256 bytes of slack for the dword prefetch, the output without).
+extern "C" CBV_API int cbv_debug_reduce_noise_batch(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, int n, int d, double sigma_color,
+                                                    double sigma_space, uint8_t* out)
+{
+    RC(check_img(ctx, bgr, w, h, w * 3, 3, "cbv_debug_reduce_noise_batch"));
+    if (!out || n < 1 || n > 4096) return cbv_fail(ctx, CBV_ERR_ARG, "cbv_debug_reduce_noise_batch: bad arguments");
+    CBV_ENTER_DRAINED(ctx);
+    RC(ctx_set_bilateral(ctx, d, sigma_color, sigma_space));
+    const Geom g = tight_geom(w, h);
+    const size_t fbytes = (size_t)w * 3 * h;
+    RC(dev_ensure(ctx, &ctx->in, g.frame_stride * n + 256));
+    RC(dev_ensure(ctx, &ctx->a, g.frame_stride * n));
+    CBV_HIP(ctx, hipMemcpy2DAsync(ctx->in.p, g.frame_stride, bgr, fbytes, fbytes, n, hipMemcpyHostToDevice, ctx->stream));
+    RC(launch_bilateral(ctx, (const u8*)ctx->in.p, (u8*)ctx->a.p, g, n));
+    CBV_HIP(ctx, hipMemcpy2DAsync(out, fbytes, ctx->a.p, g.frame_stride, fbytes, n, hipMemcpyDeviceToHost, ctx->stream));
+    CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CBV_DONE(CBV_OK);
+}
+
 extern "C" int cbv_sharpen(cbv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, const float* kernel9, uint8_t* out,
                            int out_stride)
 {

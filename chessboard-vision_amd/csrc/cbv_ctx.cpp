@@ -320,6 +320,7 @@ int ctx_set_bilateral(cbv_ctx* ctx, int d, double sc, double ss)
         return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "bilateral d=%d not supported (radius <= 4)", d);
     if (ctx->btabs_host.radius > 4) return cbv_fail(ctx, CBV_ERR_UNSUPPORTED, "bilateral d=%d not supported (radius <= 4)", d);
     ctx->btabs_offsets_bad = bilateral_offsets_mismatch(&ctx->btabs_host);
+    ctx->btabs_centre_bad = bilateral_centre_mismatch(&ctx->btabs_host);
     CBV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     CBV_HIP(ctx, hipMemcpy(ctx->btabs, &ctx->btabs_host, sizeof(BilateralTabs), hipMemcpyHostToDevice));
     ctx->b_d = d;
@@ -344,4 +345,13 @@ extern "C" CBV_API int cbv_debug_bilateral_offsets(int d, double sigma_color, do
     auto t = std::make_unique<BilateralTabs>();
     if (build_bilateral_tabs(d, sigma_color, sigma_space, t.get()) != 0 || t->radius > 4) return -1;
     return bilateral_offsets_mismatch(t.get());
+}
+
+// Not in include/cbv.h: for tests/test_bilateral_walk_host.py.  1 when the centre tap's entry of the host-built table is
+// exactly 1.0f (the constant the batched d = 9 kernel uses in its place), 0 when it is not; -1: radius not supported.
+extern "C" CBV_API int cbv_debug_bilateral_centre_is_one(int d, double sigma_color, double sigma_space)
+{
+    auto t = std::make_unique<BilateralTabs>();
+    if (build_bilateral_tabs(d, sigma_color, sigma_space, t.get()) != 0 || t->radius > 4) return -1;
+    return bilateral_centre_mismatch(t.get()) ? 0 : 1;
 }

@@ -103,6 +103,7 @@ struct cbv_ctx {
     BilateralTabs* btabs = nullptr;      // device
     BilateralTabs btabs_host;
     int btabs_offsets_bad = 0;           // bilateral_offsets_mismatch(&btabs_host), worked out when the tables are built
+    bool btabs_centre_bad = false;       // bilateral_centre_mismatch(&btabs_host), likewise
     int b_d = -1;
     double b_sc = 0, b_ss = 0;
 
@@ -319,6 +320,8 @@ PxRect sharpen_region_cover(Geom g, PxRect need);
 PxRect bilateral_region_cover(cbv_ctx* ctx, Geom g, int batch, PxRect need);
 // taps whose compile-time table offset in k_bilateral.hip differs from t->tap_off (0: the straight-line rows may run)
 int bilateral_offsets_mismatch(const BilateralTabs* t);
+// the centre tap's table entry is not exactly 1.0f, the constant the straight-line rows use in its place
+bool bilateral_centre_mismatch(const BilateralTabs* t);
 PxRect clahe_region_cover(Geom g, PxRect need);
 int launch_norm_lut(cbv_ctx* ctx, const u32* aux, int tiles, u8* norm_lut, int batch);
 // Where a kernel takes cv2.normalize's byte map from: a table k_norm_lut built ([frame][256]), or the frames' [min, max]

@@ -48,6 +48,12 @@
 //     BL_NT1024=1 builds it with 1024 lanes on 128x64 tiles, held to 96 registers (five waves per SIMD by registers,
 //     amdgpu_waves_per_eu on that instantiation only: 94 VGPRs, no scratch, 69 888 B), BL_NO_CAP=1 on top of it without
 //     that cap, for A/B runs: both are slower on the path.
+//   - round 6 takes out work the result does not need (94 VGPRs, no scratch, the same LDS):
+//     the straight-line form takes tap (0, 0)'s weight as the constant 1.0f (8 of a lane step's 364 sad + shift + gather
+//     triples; the launcher checks the table's entry once per table) and starts its sums from their first tap instead
+//     of zeroing them; in every form a wave whose four tile rows lie below the frame (half of the waves of the 23rd
+//     tile row at 1080 rows) commits and prefetches but does not filter.  BL_NO_CENTRE=1, BL_ZERO_INIT=1 and
+//     BL_FULL_TILES=1 build the kernel without the one part, for A/B runs.
 #include "cbv_device.h"
 #include <type_traits>
 
@@ -55,6 +61,24 @@
 #define BL_HALO 4        // halo in pixels (radius <= 4; 4 keeps ds_read_b128 aligned)
 #define BL_PITCH (BL_TW + 2 * BL_HALO)
 #define BL_LUT_WORDS (CBV_BL_MAXCLS * 768)
+
+// Round 6: three pieces of work the result does not need, each behind its own switch for A/B runs (tools/ab.sh); the
+// switch builds the form WITHOUT the part.  None of them changes an operand or the order of an accumulation.
+#ifdef BL_NO_CENTRE
+constexpr bool BL_CENTRE_FREE = false; // tap (0, 0) is looked up like any other
+#else
+constexpr bool BL_CENTRE_FREE = true;  // straight-line form: tap (0, 0) has SAD 0 and weight folded[class(0, 0)][0] == 1.0f
+#endif
+#ifdef BL_ZERO_INIT
+constexpr bool BL_FIRST_TAP_INIT = false; // the sums start from 0.f
+#else
+constexpr bool BL_FIRST_TAP_INIT = true;  // straight-line form: the sums start from their first tap, (-R, 0)
+#endif
+#ifdef BL_FULL_TILES
+constexpr bool BL_SKIP_BELOW = false; // rows below the frame are filtered and dropped by the store
+#else
+constexpr bool BL_SKIP_BELOW = true;  // a wave whose four tile rows all lie below the frame only commits and prefetches
+#endif
 
 __host__ __device__ constexpr int bl_row_reach(int R, int dy)
 {
@@ -89,6 +113,15 @@ int bilateral_offsets_mismatch(const BilateralTabs* t)
     for (int dy = -R; dy <= R; dy++)
         for (int dx = -R; dx <= R; dx++) bad += bl_class_off(R, dy, dx) != t->tap_off[dy + R][dx + R];
     return bad;
+}
+
+// The straight-line rows take the centre tap's weight as the constant 1.0f (space 1 x colour 1, SAD 0) instead of looking
+// it up: true when the table's entry is anything else.
+bool bilateral_centre_mismatch(const BilateralTabs* t)
+{
+    if (t->radius < 1 || t->radius > 4) return true;
+    const int off = bl_class_off(t->radius, 0, 0);
+    return off < 0 || off >= t->ncls * 768 || (&t->folded[0][0])[off] != 1.0f;
 }
 
 // bl_class_off for every tap of radius R, as a constant the unrolled straight-line rows index with literal subscripts
@@ -134,6 +167,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                                                            SatGate gate)
 {
     static_assert((2 * R + 1) * (2 * R + 1) < 128, "the epilogue's d_rcp_1_64 is verified for weight sums in [1, 128)");
+    static_assert(bl_row_reach(R, R) == 0, "an output's first tap in raster order is (-R, 0): accumulate starts the sums there");
     // static LDS (69 KB): compile-time addresses let the table gather use the ds_read immediate offset
 #ifdef BL_TWO_COPIES
     // experiment (profiles/r03/bilateral_two_copies.txt): a second copy of the table 16 banks further on, used by the odd
@@ -236,6 +270,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     }
     const int sx = tid & 31;  // strip: pixels 4*sx .. 4*sx+3
     const int ly = (tid >> 5) * 2; // first of the lane's two tile rows
+    const int wrow = __builtin_amdgcn_readfirstlane(tid >> 6) * 4; // first of the wave's four tile rows (wave-uniform)
 
     while (s < ntiles) {
         const TileAt here = cur;
@@ -259,16 +294,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             }
         }
 
+        // No work below the frame: a wave owns four tile rows, and when all four lie below the frame (half of the waves on
+        // the 23rd tile row of a 1080-row frame) the store would drop everything it computes.  Such a wave has committed
+        // its part of the tile and prefetches its part of the next one, and filters nothing (wave-uniform).
+        const bool live = !BL_SKIP_BELOW || here.py0 + wrow < g.h;
+
         // outputs: [row a/b][pixel 0..3]
         float sb[2][4], sg[2][4], sr[2][4], sw[2][4];
         u32 ctr[2][4];
+        if (live) {
 #pragma unroll
-        for (int a = 0; a < 2; a++)
+            for (int a = 0; a < 2; a++)
 #pragma unroll
-            for (int o = 0; o < 4; o++) {
-                sb[a][o] = sg[a][o] = sr[a][o] = sw[a][o] = 0.f;
-                ctr[a][o] = tile[(ly + a + R) * BL_PITCH + BL_HALO + sx * 4 + o];
-            }
+                for (int o = 0; o < 4; o++) {
+                    if (!PAIRS || !BL_FIRST_TAP_INIT) sb[a][o] = sg[a][o] = sr[a][o] = sw[a][o] = 0.f; // else: from the first tap (accumulate)
+                    ctr[a][o] = tile[(ly + a + R) * BL_PITCH + BL_HALO + sx * 4 + o];
+                }
+        }
         // One tile row per iteration, NOT unrolled (a fully unrolled body makes hipcc schedule ~250
         // live registers).  Tile row ly + i is tap row dy = i - R of output row a and dy = i - 1 - R of
         // output row b; every output still sees its taps in ascending (dy, dx) order.
@@ -372,6 +414,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                         wt[B][a][o] = wh[o][pc];
                     else if (mine && dy > 0)
                         wt[B][a][o] = wv[pc][o];
+                    else if (BL_CENTRE_FREE && dy == 0 && dx == 0)
+                        // the pixel against itself: SAD 0, space 1 x colour 1 (launch_bilateral checks the table's entry): no
+                        // v_sad_u8, no shift, no gather, and fma(px, 1.0f, sum) and sum + 1.0f round as with the looked-up 1.0f
+                        wt[B][a][o] = 1.0f;
                     else {
                         const u32 idx = __builtin_amdgcn_sad_u8(pj, ctr[a][o], (u32)bl_offsets<R>.v[dy + R][dx + R]);
                         const float wgt = *(const float*)((const u8*)fw + (idx << 2));
@@ -397,6 +443,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                     const int dx = j - 4 - o;
                     if ((dx < 0 ? -dx : dx) > bl_row_reach(R, dy < 0 ? -dy : dy)) continue;
                     const float wgt = wt[B][a][o];
+                    if (BL_FIRST_TAP_INIT && dy == -R && dx == 0) { // the only tap of row -R (static_assert above)
+                        // the output's first tap in raster order: px * w and w are the bits of fma(px, w, 0.f) and 0.f + w
+                        // (every operand is >= +0), so the sums start here and are never zeroed
+                        sb[a][o] = fb * wgt;
+                        sg[a][o] = fg * wgt;
+                        sr[a][o] = fr * wgt;
+                        sw[a][o] = wgt;
+                        continue;
+                    }
                     sb[a][o] = __fmaf_rn(fb, wgt, sb[a][o]);
                     sg[a][o] = __fmaf_rn(fg, wgt, sg[a][o]);
                     sr[a][o] = __fmaf_rn(fr, wgt, sr[a][o]);
@@ -404,6 +459,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                 }
                 // The step's sums are complete at this point of the instruction stream.  Without it hipcc looks up the
                 // weights of the whole tile first and accumulates afterwards: 168 VGPRs and 1.8 KB of scratch.
+                // It names all 16 sums of the output row, so it starts with the step that gives the last of them (o = 3) its
+                // first tap: the three pixel steps before it have one tap each and nothing to hold back.
+                if (BL_FIRST_TAP_INIT && dy == -R && j < 7) continue; // output o's first tap is pixel j = 4 + o
                 asm volatile("" : "+v"(sb[a][0]), "+v"(sg[a][0]), "+v"(sr[a][0]), "+v"(sw[a][0]), "+v"(sb[a][1]), "+v"(sg[a][1]), "+v"(sr[a][1]), "+v"(sw[a][1]),
                              "+v"(sb[a][2]), "+v"(sg[a][2]), "+v"(sr[a][2]), "+v"(sw[a][2]), "+v"(sb[a][3]), "+v"(sg[a][3]), "+v"(sr[a][3]), "+v"(sw[a][3]));
             }
@@ -411,13 +469,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         };
         if constexpr (PAIRS) {
             constexpr int HALF = 12 * (R + 2) * 2; // the lane's two own rows end here
-            look_up(std::integral_constant<int, 0>());
             auto step = [&](auto t) __attribute__((always_inline)) {
                 constexpr int U = decltype(t)::value;
                 if constexpr (U + 1 < STEPS) look_up(std::integral_constant<int, U + 1>());
                 accumulate(t);
             };
-            bl_static_for<0, HALF>(step);
+            if (live) {
+                look_up(std::integral_constant<int, 0>());
+                bl_static_for<0, HALF>(step);
+            }
             // the next tile's prefetch, issued only now: pre is dead while wh and wv are live, and the R tile rows that
             // follow still cover the loads (the same statements as above: as a lambda shared by both places they cost the
             // forms without PAIRS six registers)
@@ -430,11 +490,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                     if (gi < NG) prefetch(cur, gi, pre[k]);
                 }
             }
-            bl_static_for<HALF, STEPS>(step);
-        } else {
+            if (live) bl_static_for<HALF, STEPS>(step);
+        } else if (live) {
 #pragma unroll 1
             for (int i = 0; i <= 2 * R + 1; i++) tile_row(i);
         }
+        if (!live) continue;
         const int f = here.f;
         const int x = here.px0 + sx * 4;
 #pragma unroll
@@ -551,6 +612,7 @@ int launch_bilateral(cbv_ctx* ctx, const u8* src, u8* dst, Geom g, int batch, co
     default:
         // the straight-line rows carry their table offsets as compile-time constants: never compute with a table they do not fit
         if (ctx->btabs_offsets_bad) return cbv_fail(ctx, CBV_ERR_STATE, "bilateral: compile-time tap offsets differ from the table's");
+        if (BL_CENTRE_FREE && ctx->btabs_centre_bad) return cbv_fail(ctx, CBV_ERR_STATE, "bilateral: the table's centre weight is not 1.0f");
         return launch_bilateral_r<4, BL_NT9, true, BL_WAVES9>(ctx, src, dst, g, batch, 1, er);
 #endif
     }
