@@ -75,6 +75,65 @@ def hsv2bgr(hsv):
     return np.stack([b, g, r], axis=-1) * 255.0
 
 
+def bgr2hsv_u8(img):
+    """The 8-bit integer form of COLOR_BGR2HSV: 12-bit reciprocal tables sdiv[v] = rint((255 << 12) / v) and
+    hdiv[d] = rint((180 << 12) / (6 d)) (0 at index 0); V = max; S = (diff sdiv[V] + 2048) >> 12; H from G - B if V == R,
+    else B - R + 2 diff if V == G, else R - G + 4 diff, then (H hdiv[diff] + 2048) >> 12, + 180 when negative.  Returns
+    uint8 H, S, V (H may be 180: the form does not fold it to 0)."""
+    i = np.asarray(img, np.int64)
+    b, g, r = i[..., 0], i[..., 1], i[..., 2]
+    n = np.arange(1, 256, dtype=np.float64)
+    sdiv = np.zeros(256, np.int64)
+    hdiv = np.zeros(256, np.int64)
+    sdiv[1:] = np.rint((255 << 12) / n)
+    hdiv[1:] = np.rint((180 << 12) / (6.0 * n))
+    v = i.max(axis=-1)
+    diff = v - i.min(axis=-1)
+    s = (diff * sdiv[v] + (1 << 11)) >> 12
+    h = np.where(v == r, g - b, np.where(v == g, b - r + 2 * diff, r - g + 4 * diff))
+    h = (h * hdiv[diff] + (1 << 11)) >> 12
+    h = np.where(h < 0, h + 180, h)
+    return np.stack([h, s, v], axis=-1).astype(np.uint8)
+
+
+PROFILE_DEFAULTS = {"hue_shift": 0, "sat_scale": 1.0, "val_scale": 1.0, "contrast": 1.0, "brightness": 0, "radical_mode": 0,
+                    "target_hue": 0, "hue_window": 20}
+
+
+def _profile_adjust(hsv_u8, profile, dtype=np.float32, mod=np.mod, less=np.less, wrap=True, to_u8=lambda a: a.astype(np.uint8)):
+    """color_profile_adjust with each convention as a parameter, so that a test can state one misreading at a time and show
+    that its cases tell it from the definition.  The defaults are the definition."""
+    p = dict(PROFILE_DEFAULTS, **profile)
+    k = dtype                                              # a Python scalar next to a float32 array enters as float32
+    hsv = np.asarray(hsv_u8).astype(dtype)
+    h, s, v = hsv[..., 0], hsv[..., 1], hsv[..., 2]
+    if p["radical_mode"]:
+        h_dist = np.abs(h - k(p["target_hue"]))
+        if wrap:
+            h_dist = np.minimum(h_dist, k(180) - h_dist)
+        mask = less(h_dist, k(p["hue_window"]))
+        s = np.where(mask, s * k(2.0), s * k(0.5))
+    h = mod(h + k(p["hue_shift"]), k(180))
+    s = s * k(p["sat_scale"])
+    v = v * k(p["val_scale"])
+    h = np.clip(h, 0, 179)
+    s = np.clip(s, 0, 255)
+    v = np.clip(v, 0, 255)
+    out = np.stack([h, s, v], axis=-1)
+    assert out.dtype == dtype
+    return to_u8(out)
+
+
+def color_profile_adjust(hsv_u8, profile):
+    """The numpy middle of the reference's apply_color_profile, between its BGR2HSV and its HSV2BGR, as numpy evaluates it:
+    the 8-bit H, S, V as float32 arrays, every profile value a float32; in radical mode the hue distance
+    min(|h - target|, 180 - |h - target|), strictly below hue_window, selects s * 2.0, the rest s * 0.5;
+    h = np.mod(h + hue_shift, 180) (floored: the sign of 180); s *= sat_scale; v *= val_scale; clips to [0, 179], [0, 255],
+    [0, 255]; astype(uint8), which truncates.  `profile`: a dict with the keys of color_profile.json, missing keys at the
+    reference's defaults (hue_window 20).  Returns uint8 H, S, V."""
+    return _profile_adjust(hsv_u8, profile)
+
+
 # OpenCV's documented RGB -> XYZ matrix (Rec. 709 primaries) and D65 white point (cvtColor docs, "RGB <-> CIE L*a*b*")
 RGB2XYZ = np.array([[0.412453, 0.357580, 0.180423],
                     [0.212671, 0.715160, 0.072169],

@@ -7,6 +7,8 @@ tables, 1/32-pixel warp coordinates), not fitted to a measurement; each constant
 A checker returns a small dict of statistics (max |out - ref|, share of values more than 1 LSB off, ties) so the
 envelope table in DESIGN.md can be regenerated from the same code.
 """
+import functools
+
 import numpy as np
 
 import ref64 as R
@@ -487,6 +489,143 @@ def check_profile_neutral(out, img):
         best = d if best is None else np.minimum(best, d)
     assert best.max() <= 0.5 + HSV2BGR_EPS, ("neutral profile", float(best.max()), int((best > 0.5 + HSV2BGR_EPS).sum()))
     return _stats(best)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# apply_color_profile beyond the neutral setting: convertScaleAbs, BGR2HSV (integer form), the numpy middle, HSV2BGR
+# ---------------------------------------------------------------------------------------------------------------
+
+PROFILE_TIE_CAP = 0.05           # on the colour cubes; the reference alone gives at most 2.9 % (sat3)
+PROFILE_FRAMES = [(37, 29), (13, 1), (1, 11), (3, 2), (61, 9), (62, 9), (63, 9), (64, 9)]      # (w, h)
+PROFILE_FRAME_CONTENTS = ("noise", "smooth")
+GRAY_RAMP = np.repeat(np.arange(256, dtype=np.uint8)[None, :, None], 3, axis=2)               # B = G = R = 0..255
+
+
+def _profile_cases():
+    import color_sweep_ref as CS
+    cases = {n: p for n, p in CS.PROFILES.items() if p is not None}
+    cases["stages_fractional"] = CS.STAGES_FRACTIONAL
+    cases.update({
+        "neg_scales": {"sat_scale": -0.5, "val_scale": -1.0},
+        "neg_contrast": {"contrast": -0.71, "brightness": 12.9},     # levels 40, 140, 240 on a .5 tie of convertScaleAbs
+        "zero_contrast": {"contrast": 0.0, "brightness": 77},
+        "bright_300": {"brightness": 300},
+        "huge_shift": {"hue_shift": 1000003.25},
+        "neg_frac_shift": {"hue_shift": -0.25},
+        "window0": {"radical_mode": 1, "target_hue": 60, "hue_window": 0},
+        "window90": {"radical_mode": 1, "target_hue": 60, "hue_window": 90},
+        "target_out": {"radical_mode": 1, "target_hue": 200, "hue_window": 15},
+        "target_neg": {"radical_mode": 1, "target_hue": -10.5, "hue_window": 15.5},
+        "radical_default_window": {"radical_mode": 1, "target_hue": 100},
+    })
+    return cases
+
+
+PROFILE_CASES = _profile_cases()
+
+
+def profile_cube_offsets(name):
+    """The cubes a profile meets: the three are dealt round PROFILE_CASES in order; the shipped profile meets all three."""
+    return (0, 1, 2) if name == "shipped" else (list(PROFILE_CASES).index(name) % 3,)
+
+
+def profile_cube_cases():
+    return [(n, o) for n in PROFILE_CASES for o in profile_cube_offsets(n)]
+
+
+def color_cube(offset):
+    """Every third level of each channel from `offset`: 86^3 (85^3 from 1 and 2) colours as one frame, blue slowest."""
+    v = np.arange(offset, 256, 3, dtype=np.uint8)
+    b, g, r = np.meshgrid(v, v, v, indexing="ij")
+    return np.stack([b, g, r], axis=-1).reshape(len(v) * len(v), len(v), 3)
+
+
+def profile_frames():
+    """[(what, frame)]: PROFILE_FRAMES x PROFILE_FRAME_CONTENTS.  Feed the code under test view(frame)."""
+    return [("%s %dx%d" % (c, w, h), frame(c, w, h)) for (w, h) in PROFILE_FRAMES for c in PROFILE_FRAME_CONTENTS]
+
+
+def byte_map_profile(profile):
+    """The profile whose output on GRAY_RAMP is the convertScaleAbs byte map: the profile itself where val_scale is 1 (gray
+    has s = 0, which every saturation map keeps, and the hue of a gray does not show), else its contrast and brightness alone."""
+    if profile.get("val_scale", 1.0) == 1:
+        return profile
+    return {"contrast": profile.get("contrast", 1.0), "brightness": profile.get("brightness", 0)}
+
+
+def csa_eps(alpha, beta):
+    """float32 alpha, beta and one fused multiply-add: error below 4 u (255 |alpha| + |beta|)."""
+    return 4 * U32 * (255 * abs(alpha) + abs(beta))
+
+
+def profile_byte_map(ramp_out, profile):
+    """ramp_out: the code under test on GRAY_RAMP with byte_map_profile(profile).  It must be gray and convertScaleAbs of the
+    level, rounded once and saturated, within csa_eps.  Returns the 256-entry byte map that check_profile indexes: rint of the
+    float64 value, saturated, except at levels within csa_eps of a .5 tie, where the value just shown admissible is taken."""
+    assert profile.get("val_scale", 1.0) == 1, "the byte map is read off a profile that leaves V alone: byte_map_profile()"
+    alpha, beta = profile.get("contrast", 1.0), profile.get("brightness", 0)
+    out = np.asarray(ramp_out).reshape(256, 3)
+    assert (out == out[:, :1]).all(), ("profile on a gray ramp is not gray", int((out != out[:, :1]).any(axis=1).sum()))
+    eps = csa_eps(alpha, beta)
+    ref = np.clip(R.convert_scale_abs(np.arange(256), alpha, beta), 0, 255)
+    check_rounded(out[:, 0], ref, eps, "convertScaleAbs alpha=%g beta=%g" % (alpha, beta))
+    tie = np.abs(ref - np.floor(ref) - 0.5) <= eps
+    return np.where(tie, out[:, 0], np.rint(ref)).astype(np.uint8)
+
+
+def byte_map_definition(profile):
+    """The byte map from the definition alone: rint of the float64 |alpha x + beta|, saturated (a tie goes to the even side)."""
+    x = R.convert_scale_abs(np.arange(256), profile.get("contrast", 1.0), profile.get("brightness", 0))
+    return np.clip(np.rint(x), 0, 255).astype(np.uint8)
+
+
+def profile_reference(img, profile, byte_map):
+    """B, G, R unrounded: HSV2BGR of the numpy middle of the integer BGR2HSV of byte_map[img], from ref64 alone."""
+    return R.hsv2bgr(R.color_profile_adjust(R.bgr2hsv_u8(np.asarray(byte_map, np.uint8)[img]), profile))
+
+
+def check_profile(out, img, profile, byte_map, ref=None, tie_cap=None, what="profile"):
+    """apply_color_profile(img, profile): every stage before HSV2BGR is defined on integers (the byte map, the integer
+    BGR2HSV, the truncating cast), so there is one candidate per pixel, and out is HSV2BGR of it rounded once:
+    check_rounded with HSV2BGR_EPS.  `ref`: profile_reference(img, profile, byte_map) where a caller shares it.  `tie_cap`:
+    the share of values within HSV2BGR_EPS of a .5 tie that the case may have (check_rounded's TIE_SHARE_CAP without it)."""
+    if ref is None:
+        ref = profile_reference(img, profile, byte_map)
+    s = check_rounded(out, ref, HSV2BGR_EPS, what)
+    if tie_cap is not None:
+        assert s["ties"] <= tie_cap * ref.size, "%s: %.2f %% of values on a rounding tie" % (what, 100.0 * s["ties"] / ref.size)
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def cube_reference(name, offset, byte_map_bytes):
+    """profile_reference of PROFILE_CASES[name] on color_cube(offset), computed once for the host and the GPU tests of one run
+    (they arrive at the same byte map unless they take different neighbours of a convertScaleAbs tie).  Read-only."""
+    ref = profile_reference(color_cube(offset), PROFILE_CASES[name], np.frombuffer(byte_map_bytes, np.uint8))
+    ref.setflags(write=False)
+    return ref
+
+
+def observed_byte_map(apply, profile):
+    """apply(img, profile) -> uint8 BGR is the code under test: its byte map, checked (profile_byte_map)."""
+    bmp = byte_map_profile(profile)
+    return profile_byte_map(apply(GRAY_RAMP, bmp), bmp)
+
+
+def check_profile_cube(apply, name, offset):
+    """The code under test on color_cube(offset) with PROFILE_CASES[name], one call, under check_profile and the cubes' tie cap."""
+    profile, cube = PROFILE_CASES[name], color_cube(offset)
+    byte_map = observed_byte_map(apply, profile)
+    return check_profile(apply(cube, profile), cube, profile, byte_map, ref=cube_reference(name, offset, byte_map.tobytes()),
+                         tie_cap=PROFILE_TIE_CAP, what="profile %s, cube %d" % (name, offset))
+
+
+def check_profile_frames(apply, name):
+    """The code under test on the small frames, as strided and misaligned views, with PROFILE_CASES[name]."""
+    profile = PROFILE_CASES[name]
+    byte_map = observed_byte_map(apply, profile)
+    return [check_profile(apply(view(img), profile), img, profile, byte_map, what="profile %s, %s" % (name, what))
+            for what, img in profile_frames()]
 
 
 def check_lab(out, ref, what):

@@ -1,7 +1,10 @@
 """The HIP kernels against tests/ref64.py directly: the same inputs and envelope checks as test_ref64_oracle.py, with
 the expected values computed on the host from each operation's definition and never from the oracle.  The library
 has no stand-alone Lab or HSV call, so the colour conversions are reached through the neutral colour profile (an HSV
-round trip) and through correct_lighting (Lab -> CLAHE(L) -> BGR) on inputs whose bound can be derived."""
+round trip) and through correct_lighting (Lab -> CLAHE(L) -> BGR) on inputs whose bound can be derived.  The colour profile
+away from the neutral setting (its byte map, its hue, saturation and value maps, the radical window) is held to
+ref64_checks.check_profile, one admissible value per pixel: cbv_apply_color_profile, the warp's own copy of the table
+consumer, and the context's table cache."""
 import ctypes as C
 import os
 
@@ -140,6 +143,84 @@ def test_profile_neutral_sampled_cube(enh):
         K.check_profile_neutral(enh.apply_color_profile(img), img)
     finally:
         enh.profile = {}
+
+
+# ------------------------------------------------------------------ the colour profile beyond the neutral setting
+
+
+@pytest.fixture
+def profiled(enh):
+    """apply(img, profile): cbv_apply_color_profile through ImageEnhancer.apply_color_profile."""
+    def apply(img, profile):
+        enh.profile = profile
+        try:
+            return enh.apply_color_profile(img)
+        finally:
+            enh.profile = {}
+    return apply
+
+
+def warp_identity(rot180):
+    """apply(img, profile): k_warp_profile at integer positions, where the 1/32-pixel blend is exact: the warp's own copy of
+    the table consumer and nothing else.  With rot180 the output is turned back, so the checks compare against the reference
+    reversed."""
+    from chessboard_vision_amd.board_detection import warp_perspective_profiled
+
+    def apply(img, profile):
+        out = warp_perspective_profiled(img, np.eye(3), (img.shape[1], img.shape[0]), profile, rot180=rot180)
+        return out[::-1, ::-1] if rot180 else out
+    return apply
+
+
+@pytest.mark.parametrize("name,offset", K.profile_cube_cases())
+def test_profile_on_cube(profiled, name, offset):
+    """86^2 x 86 pixels, one launch per cube (and one of 256 pixels for the byte map)."""
+    s = K.check_profile_cube(profiled, name, offset)
+    print("profile %s cube %d: max %.4f, over 1 LSB %.4f, ties %d" % (name, offset, s["max"], s["over1"], s["ties"]))
+
+
+@pytest.mark.parametrize("name", list(K.PROFILE_CASES))
+def test_profile_on_small_frames(profiled, name):
+    K.check_profile_frames(profiled, name)
+
+
+WARP_PROFILES = ("shipped", "radical_wrap", "clipping", "neg_contrast")
+
+
+@pytest.mark.parametrize("rot180", [False, True])
+@pytest.mark.parametrize("name", WARP_PROFILES)
+def test_warp_profile_table_consumer(gpu_ctx, name, rot180):
+    """warp_perspective_profiled with the identity matrix against the definition directly, not against
+    cbv_apply_color_profile: the cube with offset 0 as an 860 x 740 frame (its first 344 colours once more fill the last
+    row) and the 37 x 29 frame as a strided view."""
+    apply = warp_identity(rot180)
+    profile = K.PROFILE_CASES[name]
+    byte_map = K.observed_byte_map(apply, profile)
+
+    def as_frame(a):
+        flat = a.reshape(-1, 3)
+        return np.concatenate([flat, flat[:860 * 740 - len(flat)]]).reshape(740, 860, 3)
+
+    cube = as_frame(K.color_cube(0))
+    K.check_profile(apply(cube, profile), cube, profile, byte_map, ref=as_frame(K.cube_reference(name, 0, byte_map.tobytes())),
+                    tie_cap=K.PROFILE_TIE_CAP, what="warp profile %s rot180=%d, cube" % (name, rot180))
+    img = K.frame("noise", 37, 29)
+    K.check_profile(apply(K.view(img), profile), img, profile, byte_map, what="warp profile %s rot180=%d, 37x29" % (name, rot180))
+
+
+@pytest.mark.parametrize("a,b", [("shipped", "radical_wrap"), ("radical_wrap", dict(K.PROFILE_CASES["radical_wrap"], hue_window=13)),
+                                 ("neg_contrast", {"contrast": -0.71, "brightness": 13.9})])
+def test_profile_table_cache(profiled, a, b):
+    """The context keeps the tables of the last profile and compares the next one with it: A, B, A on one context, B a
+    different profile or A with one field changed.  Each output is held to its own profile, and the two of A are equal."""
+    pa, pb = K.PROFILE_CASES[a], (K.PROFILE_CASES[b] if isinstance(b, str) else b)
+    img = K.frame("noise", 37, 29)
+    maps = [K.observed_byte_map(profiled, p) for p in (pa, pb, pa)]
+    outs = [profiled(K.view(img), p) for p in (pa, pb, pa)]                 # back to back: nothing else sets a profile between
+    for p, byte_map, out in zip((pa, pb, pa), maps, outs):
+        K.check_profile(out, img, p, byte_map, what="profile after another profile")
+    assert np.array_equal(outs[0], outs[2])
+    assert not np.array_equal(outs[0], outs[1]), "the two profiles do not differ on this frame: the case says nothing"
 
 
 @pytest.mark.parametrize("seed", range(12))
